@@ -1,8 +1,20 @@
 #!/usr/bin/env python3
 """bench.py -- the driver's measurement contract for the KZG segment-prover hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload msm20|msm26|kzg22]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload msm20|msm26|kzg22] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the JSON line (`metric`, `value`,
+`unit`, `ms_per_step`, ...).  Its warm-up of an MSM workload is max(W, 32) untimed steps (a clock ramp: the GPU needs ~40 ms
+of sustained load to reach its clocks, which a --full run gets from its `pipelined` region) followed by the W declared
+steps; `msms_before_timed_region` counts both.  Its timed region records no HIP events; a --full run brackets every
+k_msm_accumulate launch of the timed region with two (the live `roofline.kernel_ms`), so the two headlines are not
+measured identically.  `--full` adds everything else listed below: the `pipelined` region,
+the live kernel timing and `roofline` / `mad_issue`, the stage table, single-request latency, adversarial inputs, the CPU
+baseline, the commit+open and from-text rows, and with a process group the `msm26` / `pianist_kzg22` objects.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (its bytes as float64; inputs are seeded,
+so two builds compare output for output).  The arrays are bytes of compressed curve points and field elements: compare
+them for exact equality -- a tolerance on them means nothing.
 
 Default workload `msm20` (BASELINE.json configs[1], the one the metric is quoted on): one step = one 2^20-point
 BLS12-381 G1 Pippenger MSM per GPU over a cached (device-resident) SRS segment with device-resident random scalars.
@@ -35,7 +47,7 @@ Robustness of a multi-rank launch (the driver's SCALE runs cannot be watched or 
 BENCH_BACKEND=nccl + BENCH_COLLECTIVE=torch is the round-4 form (torch's RCCL group carries everything): the A/B.
 BENCH_FAULT=<phase>:<rank> (msm26_setup, msm26_step, pianist_kzg22_setup, comm_init) injects a failure for the tests.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (with --full):
   roofline         dominant kernel (k_msm_accumulate): duration from HIP events on the library's own stream inside the
                    timed region, denominators from SURVEY.md 8d (128 B per point)
   mad_issue        what actually bounds that kernel: v_mad_u64_u32 wave-instructions per second against the chip's
@@ -67,6 +79,17 @@ from benchlib.control import Ctl, Fault, inject, make_collective, self_launch  #
 from benchlib.extras import dist_extra_workloads, e2e_from_text_report, kzg_rows_report  # noqa: E402,F401
 
 
+def dump_outputs(dirname, result):
+    """--dump-outputs: the answer of the last timed step as a caller receives it -- the compressed G1 point of an MSM, or
+    commitment / evaluation / proof of a commit+open -- one .npy each, every byte a float64 (exact)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"msm_point": result} if isinstance(result, (bytes, bytearray)) else dict(zip(("commitment", "evaluation", "proof"), result))
+    for name, raw in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.frombuffer(bytes(raw), dtype=np.uint8).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -95,9 +118,15 @@ def main():
     ap.add_argument("--kzg22-log", type=int, default=22, help="log2(row length) of the `pianist_kzg22` object")
     ap.add_argument("--headline-only", action="store_true",
                     help="timed region only (profiling runs: every k_msm_accumulate launch is then an uncontended launch "
-                         "of the headline size, so rocprofv3's average matches `roofline.kernel_ms`)")
+                         "of the headline size, so with --full rocprofv3's average matches `roofline.kernel_ms`)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline (the extra objects of the docstring); "
+                         "a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64, one element per byte; "
+                         "compare for exact equality)")
     args = ap.parse_args()
-    if args.headline_only:
+    if args.headline_only or not args.full:
         args.no_pipelined = args.no_kzg_rows = args.no_cpu_baseline = args.no_adversarial = args.no_dist_extra = args.no_e2e = True
 
     rank = int(os.environ.get("RANK", "0"))
@@ -278,25 +307,30 @@ def main():
         pipe_s = ctl.max_over_ranks(pipe_s)
         pipelined = {"requests_in_flight": 2, "value": n_total * args.steps / pipe_s, "unit": "points/s",
                      "ms_per_step": pipe_s / args.steps * 1e3, "msms_before_region": pipe_warm}
-    msms_before = len(results)             # MSMs this GPU ran before the declared warm-up (the `pipelined` measurement)
+    elif is_msm and not args.full:
+        # a plain run has no `pipelined` region to bring the clocks up: the same >= 32 steps of load, one at a time, untimed
+        run_steps(max(args.warmup, 32), False)
+    msms_before = len(results)             # MSMs this GPU ran before the declared warm-up (`pipelined` or the clock ramp)
     run_steps(args.warmup, False)
     results.clear()
     step_ms.clear()
-    # The timed region carries HIP events around the dominant kernel only (profiling level 2: two events per
+    # With --full the timed region carries HIP events around the dominant kernel only (profiling level 2: two events per
     # k_msm_accumulate launch, on the stream it is launched on -- the roofline's kernel time is measured live over exactly
     # these K steps).  A full set of stage spans costs ~0.09 ms per 2^20 MSM (every event is a barrier packet on the
     # stream) and pins concurrent calls to one lane, so the per-stage table comes from extra, serialised steps afterwards.
-    live_level = 2 if is_msm and depth == 1 else 0
+    # A plain run records no events in the timed region (level 0).
+    live_level = 2 if args.full and is_msm and depth == 1 else 0
     eng.set_profiling(live_level)
     barrier()
     t0 = time.perf_counter()
     run_steps(args.steps, live_level == 2)
     barrier()
     elapsed = time.perf_counter() - t0
+    last_result = results[-1]              # what the caller of the timed path received in its last step (--dump-outputs)
     # the bound of the dominant kernel, measured NOW on this box at the clocks the timed region left behind (~2 ms: a
     # v_mad_u64_u32 chain at 2 waves per SIMD on every SIMD, csrc/calibrate.hip): mad_issue.frac is a same-run ratio
     calib = None
-    if is_msm:
+    if is_msm and args.full:
         try:
             # the clock the SIMDs ran at is calib["memtime_ticks_per_ns"] (s_memtime over the kernel itself); the sysfs
             # pp_dpm_sclk node lags by hundreds of milliseconds (it showed 158 MHz, 1941 MHz and 2398 MHz around identical
@@ -307,27 +341,29 @@ def main():
     acc_live_ms = stage_sum.get("accumulate", 0.0) / args.steps if live_level == 2 else None
     stage_sum.clear()
     timed_step_ms = list(step_ms)
-    state["depth"] = 1
-    eng.set_profiling(1)
     n_prof = min(args.steps, 5)
-    run_steps(n_prof, True)
-    state["depth"] = depth
-    eng.set_profiling(0)
-    # single-request latency (one request at a time, result on the host before the next starts)
-    lat = []
-    for _ in range(min(args.steps, 10)):
-        tl = time.perf_counter()
-        if is_msm:
-            if not use_dist:
-                results.append(eng.msm_resident(0, n, 0))
-            elif gather_step is not None:
-                results.append(gather_step.msm(0, n, 0))
+    latency_ms = None
+    if args.full:
+        state["depth"] = 1
+        eng.set_profiling(1)
+        run_steps(n_prof, True)
+        state["depth"] = depth
+        eng.set_profiling(0)
+        # single-request latency (one request at a time, result on the host before the next starts)
+        lat = []
+        for _ in range(min(args.steps, 10)):
+            tl = time.perf_counter()
+            if is_msm:
+                if not use_dist:
+                    results.append(eng.msm_resident(0, n, 0))
+                elif gather_step is not None:
+                    results.append(gather_step.msm(0, n, 0))
+                else:
+                    results.append(eng.g1_sum(b"".join(all_gather_partials(eng.msm_partial_resident(0, n, 0)))))
             else:
-                results.append(eng.g1_sum(b"".join(all_gather_partials(eng.msm_partial_resident(0, n, 0)))))
-        else:
-            results.append(eng.commit_open_resident(0, 0, n, alpha, True))
-        lat.append((time.perf_counter() - tl) * 1e3)
-    latency_ms = sorted(lat)[len(lat) // 2]
+                results.append(eng.commit_open_resident(0, 0, n, alpha, True))
+            lat.append((time.perf_counter() - tl) * 1e3)
+        latency_ms = sorted(lat)[len(lat) // 2]
     elapsed = ctl.max_over_ranks(elapsed)
     assert all(r == results[0] for r in results), "non-deterministic result across steps"
     window_bits = eng.window
@@ -368,25 +404,6 @@ def main():
             launches = 1 if batched else 2
             metric, unit, value = "KZG commit+open coefficients/sec at 2^22", "coefficients/s", units / elapsed
             wl = f"degree-2^{lg} KZG commit+open per GPU (INTT + 2 MSM + quotient), evaluation-form input"
-        copy_gbs = measured_copy_peak_gbs(torch) if world == 1 else None
-        per_launch_s = acc_ms / 1e3 / launches if acc_ms else float("nan")
-        achieved = alg_bytes / per_launch_s / 1e9 if acc_ms else None
-        # HBM traffic and instruction counts of the dominant kernel: PMC counters cannot be read from inside this process,
-        # so the values are the ones measured with rocprofv3 --pmc (separate FETCH_SIZE / WRITE_SIZE / SQ passes, gfx950
-        # x2 FETCH correction) on this exact configuration and committed under profiles/; null for any other configuration.
-        traffic = valu_insts = mads = None
-        try:
-            with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
-                pmc = json.load(f)
-            if (pmc["workload"], pmc["points_per_gpu"], pmc["window_bits"]) == ("msm20" if is_msm else args.workload, n, window_bits):
-                traffic = pmc["traffic_bytes_per_launch"]
-                valu_insts = pmc.get("sq_insts_valu_per_launch")
-                mads = pmc.get("wave_mads_per_launch")
-        except (OSError, KeyError, ValueError):
-            pass
-        mad_peak_file = SIMDS / MAD_NS             # the committed ubench figure: kept as a cross-check only
-        live = calib is not None and "gmad_per_s" in calib
-        mad_peak = calib["gmad_per_s"] if live else mad_peak_file
         out = {
             "metric": metric, "value": value, "unit": unit, "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
@@ -402,51 +419,76 @@ def main():
                         else f"Pianist segments x{world}, no exchange")},
             # `warmup` is the W the contract declares; what really preceded the timed region on this GPU is this count
             "msms_before_timed_region": msms_before + args.warmup,
-            "msms_before_timed_region_note": "MSMs this GPU ran before the K timed steps: the `pipelined` measurement (taken first "
-                                             "so that the one-at-a-time region starts on warm clocks) + the W declared warm-up steps",
+            "msms_before_timed_region_note": "MSMs this GPU ran before the K timed steps: the `pipelined` measurement (--full) or "
+                                             "the clock ramp (plain run), so that the timed region starts on warm clocks, + the W "
+                                             "declared warm-up steps",
             "identity": identity(),
             # what kzg_create measured about this process: lanes, lanes really running concurrently (hardware queues), HIP
             # already live when the library was loaded, GPU_MAX_HW_QUEUES as seen -- `pipelined` means little if this is < 2
             "runtime_info": eng.runtime_info(),
-            "roofline": {"bound": "hbm", "kernel": "k_msm_accumulate", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
-                         "kernel_ms": per_launch_s * 1e3 if acc_ms else None, "algorithmic_bytes": alg_bytes,
-                         "measured_copy_peak_gbs": round(copy_gbs, 1) if copy_gbs else None,
-                         "frac_of_measured_copy_peak": (achieved / (copy_gbs or HBM_COPY_GBS)) if achieved else None,
-                         "traffic_source": "profiles/pmc_traffic.json (rocprofv3 --pmc, 2 x FETCH_SIZE + WRITE_SIZE)" if traffic else None,
-                         "note": "integer-multiply-bound (14 x 28-bit-limb Montgomery products on v_mad_u64_u32), not "
-                                 "HBM-bound: see mad_issue and DESIGN.md 3.3"},
-            # what actually bounds the kernel: v_mad_u64_u32 wave-instructions per second against the
-            # measured rate of that instruction (5.0 cycles per wave-instruction per SIMD, 1024 SIMDs, clock held under
-            # this load); counts from the code object / SQ_INSTS_VALU passes under profiles/
-            "mad_issue": ({"wave_mads_per_launch": mads, "wave_valu_insts_per_launch": valu_insts,
-                           "achieved_gmad_s": mads / per_launch_s / 1e9, "peak_gmad_s": mad_peak,
-                           "frac": mads / per_launch_s / 1e9 / mad_peak,
-                           "peak_source": "kzg_calibrate in this run, right after the timed region" if live else
-                                          "profiles/ubench_valu_rates.txt (another box: treat frac as +-14 %)",
-                           "calibration": calib,
-                           "peak_gmad_s_committed_ubench": mad_peak_file,
-                           "live_vs_committed_peak": (mad_peak / mad_peak_file) if live else None,
-                           "peak_basis": (f"{calib['simds']} SIMDs / {calib['ns_per_mad_per_simd']:.3f} ns per v_mad_u64_u32 "
-                                          f"wave-instruction per SIMD at 2 waves per SIMD, measured in this run" if live else
-                                          f"{SIMDS} SIMDs / {MAD_NS} ns per v_mad_u64_u32 wave-instruction "
-                                          "(profiles/ubench_valu_rates.txt, 2 and 4 waves per SIMD)")
-                                         + "; mads per launch from the ISA (profiles/isa_counts.json) x additions per lane "
-                                           "x waves",
-                           "simd32_full_rate_ginst_s": VALU_FULL_RATE_GINST_S}
-                          if mads and acc_ms else None),
             "result_hex": results[0].hex() if isinstance(results[0], (bytes, bytearray)) else b"".join(results[0]).hex(),
-            "stages_ms": {k: round(v, 4) for k, v in stages.items()},
-            "stages_ms_source": f"{n_prof} extra steps with every stage bracketed by HIP events, after the timed region; "
-                                "roofline.kernel_ms is measured inside the timed region"
-                                + ("" if acc_live_ms else " of those extra steps (two-lane commit+open: timed unprofiled)"),
-            "single_request_latency_ms": round(latency_ms, 4),
-            "pipelined": pipelined,
             "step_ms": {"median": round(pctl(timed_step_ms, 0.5), 4), "p10": round(pctl(timed_step_ms, 0.1), 4),
                         "p90": round(pctl(timed_step_ms, 0.9), 4)},
             "setup_s": round(setup_s, 2),
         }
-        if args.workload == "kzg22":
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_result)
+        if args.full:
+            copy_gbs = measured_copy_peak_gbs(torch) if world == 1 else None
+            per_launch_s = acc_ms / 1e3 / launches if acc_ms else float("nan")
+            achieved = alg_bytes / per_launch_s / 1e9 if acc_ms else None
+            # HBM traffic and instruction counts of the dominant kernel: PMC counters cannot be read from inside this process,
+            # so the values are the ones measured with rocprofv3 --pmc (separate FETCH_SIZE / WRITE_SIZE / SQ passes, gfx950
+            # x2 FETCH correction) on this exact configuration and committed under profiles/; null for any other configuration.
+            traffic = valu_insts = mads = None
+            try:
+                with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
+                    pmc = json.load(f)
+                if (pmc["workload"], pmc["points_per_gpu"], pmc["window_bits"]) == ("msm20" if is_msm else args.workload, n, window_bits):
+                    traffic = pmc["traffic_bytes_per_launch"]
+                    valu_insts = pmc.get("sq_insts_valu_per_launch")
+                    mads = pmc.get("wave_mads_per_launch")
+            except (OSError, KeyError, ValueError):
+                pass
+            mad_peak_file = SIMDS / MAD_NS             # the committed ubench figure: kept as a cross-check only
+            live = calib is not None and "gmad_per_s" in calib
+            mad_peak = calib["gmad_per_s"] if live else mad_peak_file
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": "k_msm_accumulate", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
+                             "kernel_ms": per_launch_s * 1e3 if acc_ms else None, "algorithmic_bytes": alg_bytes,
+                             "measured_copy_peak_gbs": round(copy_gbs, 1) if copy_gbs else None,
+                             "frac_of_measured_copy_peak": (achieved / (copy_gbs or HBM_COPY_GBS)) if achieved else None,
+                             "traffic_source": "profiles/pmc_traffic.json (rocprofv3 --pmc, 2 x FETCH_SIZE + WRITE_SIZE)" if traffic else None,
+                             "note": "integer-multiply-bound (14 x 28-bit-limb Montgomery products on v_mad_u64_u32), not "
+                                     "HBM-bound: see mad_issue and DESIGN.md 3.3"},
+                # what actually bounds the kernel: v_mad_u64_u32 wave-instructions per second against the
+                # measured rate of that instruction (5.0 cycles per wave-instruction per SIMD, 1024 SIMDs, clock held under
+                # this load); counts from the code object / SQ_INSTS_VALU passes under profiles/
+                "mad_issue": ({"wave_mads_per_launch": mads, "wave_valu_insts_per_launch": valu_insts,
+                               "achieved_gmad_s": mads / per_launch_s / 1e9, "peak_gmad_s": mad_peak,
+                               "frac": mads / per_launch_s / 1e9 / mad_peak,
+                               "peak_source": "kzg_calibrate in this run, right after the timed region" if live else
+                                              "profiles/ubench_valu_rates.txt (another box: treat frac as +-14 %)",
+                               "calibration": calib,
+                               "peak_gmad_s_committed_ubench": mad_peak_file,
+                               "live_vs_committed_peak": (mad_peak / mad_peak_file) if live else None,
+                               "peak_basis": (f"{calib['simds']} SIMDs / {calib['ns_per_mad_per_simd']:.3f} ns per v_mad_u64_u32 "
+                                              f"wave-instruction per SIMD at 2 waves per SIMD, measured in this run" if live else
+                                              f"{SIMDS} SIMDs / {MAD_NS} ns per v_mad_u64_u32 wave-instruction "
+                                              "(profiles/ubench_valu_rates.txt, 2 and 4 waves per SIMD)")
+                                             + "; mads per launch from the ISA (profiles/isa_counts.json) x additions per lane "
+                                               "x waves",
+                               "simd32_full_rate_ginst_s": VALU_FULL_RATE_GINST_S}
+                              if mads and acc_ms else None),
+                "stages_ms": {k: round(v, 4) for k, v in stages.items()},
+                "stages_ms_source": f"{n_prof} extra steps with every stage bracketed by HIP events, after the timed region; "
+                                    "roofline.kernel_ms is measured inside the timed region"
+                                    + ("" if acc_live_ms else " of those extra steps (two-lane commit+open: timed unprofiled)"),
+                "single_request_latency_ms": round(latency_ms, 4),
+                "pipelined": pipelined,
+            })
+        if args.workload == "kzg22" and args.full:
             out["kzg_commit_open_latency_ms"] = latency_ms
             if world == 1:      # the same call fed from host memory: + H2D of the row (never part of `value`)
                 tp = time.perf_counter()
@@ -528,7 +570,7 @@ def main():
                     "note": "plain-C stand-in (oracle/kzg_cpu.c, __int128 limbs); an asm-backed Pippenger (blst-class, what the reference's Rust prover most likely links) is expected to be 1.5-2x faster per core -- the GPU/CPU ratio is an upper estimate",
                     "matches_gpu_bit_exact": cpu_res == tuple(gpu_same)}
                 assert cpu_res == tuple(gpu_same), "GPU commit+open differs from the CPU oracle on the baseline sample"
-        if use_dist:
+        if use_dist and args.full:
             # the headline is complete: print it NOW.  The extras below (the largest tables of the launch, a collective per
             # step) can then cost at most themselves; the augmented line printed after them supersedes this one (the LAST
             # JSON line is the record).

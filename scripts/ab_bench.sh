@@ -7,6 +7,6 @@ ARGS=${1:---headline-only --steps 15}
 ROUNDS=${2:-3}
 for r in $(seq $ROUNDS); do
   for v in ${VARIANTS:-A B}; do
-    echo -n "$v "; KZG_MI355X_LIB=$PWD/zkp_subnet_amd/ab/$v.so python bench.py $ARGS 2>&1 | tail -1 | grep -o "ms_per_step[^,]*\|\"accumulate[^,]*\|\"digits[^,]*\|\"tree[^,]*\|single_request_latency_ms[^,]*\|pipelined\": {[^}]*}" | tr "\n" " "; echo
+    echo -n "$v "; KZG_MI355X_LIB=$PWD/zkp_subnet_amd/ab/$v.so python bench.py --full $ARGS 2>&1 | tail -1 | grep -o "ms_per_step[^,]*\|\"accumulate[^,]*\|\"digits[^,]*\|\"tree[^,]*\|single_request_latency_ms[^,]*\|pipelined\": {[^}]*}" | tr "\n" " "; echo
   done
 done

@@ -7,7 +7,7 @@
 #            chained by events (kzg_msm_sharded_begin / _finish): the round-4 form
 # Prints: variant, ms_per_step, single-request latency, live accumulate ms, collective description.
 cd ${GRAFT_REPO_ROOT:-/root/repo}
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-kzg-rows --no-adversarial --no-e2e --no-dist-extra --no-pipelined"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-kzg-rows --no-adversarial --no-e2e --no-dist-extra --no-pipelined"
 show='import json,sys
 ls=[l for l in sys.stdin.readlines() if l.startswith("{")]
 d=json.loads(ls[-1]); print(sys.argv[1], round(d["ms_per_step"],4), d["single_request_latency_ms"], round(d["roofline"]["kernel_ms"],4), (d["config"].get("collective") or "-")[:60])'

@@ -7,7 +7,7 @@ ROUNDS=${1:-2}
 IFS='|' read -ra SETS <<< "${SETTINGS}"
 for r in $(seq $ROUNDS); do
   for v in "${SETS[@]}"; do
-    env ${v//,/ } python bench.py --no-adversarial --no-cpu-baseline --no-pipelined --steps 30 --no-kzg-rows 2>/dev/null | tail -1 | python -c "
+    env ${v//,/ } python bench.py --full --no-adversarial --no-cpu-baseline --no-pipelined --steps 30 --no-kzg-rows 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 s=d['stages_ms']

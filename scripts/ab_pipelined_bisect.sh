@@ -12,6 +12,6 @@ show='import json,sys
 d=json.loads(sys.stdin.readlines()[-1]); print(sys.argv[1], round(d["ms_per_step"],4), round(d["pipelined"]["ms_per_step"],4), round(d["roofline"]["kernel_ms"],4))'
 for r in 1 2 3; do
   for v in wa wb; do (cd scripts/ab_trees/$v && python bench.py $ARGS 2>/dev/null | python -c "$show" $v); done
-  for v in C D; do KZG_MI355X_LIB=$ROOT/zkp_subnet_amd/ab/$v.so python bench.py $ARGS 2>/dev/null | python -c "$show" $v; done
-  GPU_MAX_HW_QUEUES=8 KZG_MI355X_LIB=$ROOT/zkp_subnet_amd/ab/C.so python bench.py $ARGS 2>/dev/null | python -c "$show" Cq8
+  for v in C D; do KZG_MI355X_LIB=$ROOT/zkp_subnet_amd/ab/$v.so python bench.py --full $ARGS 2>/dev/null | python -c "$show" $v; done
+  GPU_MAX_HW_QUEUES=8 KZG_MI355X_LIB=$ROOT/zkp_subnet_amd/ab/C.so python bench.py --full $ARGS 2>/dev/null | python -c "$show" Cq8
 done

@@ -4,7 +4,7 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 ROUNDS=${1:-2}
 for r in $(seq $ROUNDS); do
   for v in ${VARIANTS:-A B}; do
-    KZG_MI355X_LIB=$PWD/zkp_subnet_amd/ab/$v.so python bench.py --no-adversarial --no-cpu-baseline --no-pipelined --steps 20 --kzg-rows ${ROWS:-22,20,16,12} 2>/dev/null | tail -1 | python -c "
+    KZG_MI355X_LIB=$PWD/zkp_subnet_amd/ab/$v.so python bench.py --full --no-adversarial --no-cpu-baseline --no-pipelined --steps 20 --kzg-rows ${ROWS:-22,20,16,12} 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 s=d['stages_ms']

@@ -15,7 +15,7 @@ for r in 1 2 3; do
   for v in A B; do
     LIB=$PWD/zkp_subnet_amd/libkzg_mi355x.so; [ $v = B ] && LIB=$PWD/zkp_subnet_amd/ab/split.so
     echo -n "round $r $v: "
-    KZG_MI355X_LIB=$LIB python bench.py --steps 20 --warmup 5 --no-kzg-rows --no-cpu-baseline --no-adversarial --no-e2e 2>/dev/null | tail -1 | python -c "
+    KZG_MI355X_LIB=$LIB python bench.py --full --steps 20 --warmup 5 --no-kzg-rows --no-cpu-baseline --no-adversarial --no-e2e 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 st=d.get('stages_ms',{})

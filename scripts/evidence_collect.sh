@@ -1,9 +1,10 @@
 #!/bin/bash
-# After `gpurun -- 'bash scripts/evidence_round.sh'`: the round's evidence from gpurun_out/ into profiles/<round>_*.
+# After `bash scripts/evidence_round.sh` on an MI355X: the round's evidence from $OUT/prof (default out/prof, the folder
+# evidence_round.sh writes) into profiles/<round>_*.
 # Bench lines go through scripts/evidence_keep.py (refused unless their identity.source_sha16 is this tree's, and unless no
 # other evidence file has the same bytes); kernel stats, PMC tables and logs are copied.   ROUND=r06 bash scripts/evidence_collect.sh
 R=$(cd "$(dirname "$0")/.." && pwd); cd $R
-ROUND=${ROUND:-r06}; P=gpurun_out/prof; rc=0
+ROUND=${ROUND:-r06}; P=${OUT:-out}/prof; rc=0
 keep() { python scripts/evidence_keep.py "$@" || rc=1; }
 keep $P/bench_driver_style.json profiles/${ROUND}_bench_driver_style.json \
      $P/bench_default.json profiles/${ROUND}_bench_default.json \

@@ -1,4 +1,4 @@
-"""Copies measured JSON lines from gpurun_out/ into profiles/ -- and REFUSES any file that does not identify itself as a
+"""Copies measured JSON lines from the evidence scripts' output folder ($OUT/prof, default out/prof) into profiles/ -- and REFUSES any file that does not identify itself as a
 measurement of THIS tree (VERDICT r4 task 4: an "r04" evidence file turned out to be round 3's, byte for byte).
 
     python scripts/evidence_keep.py <src.json> <profiles/rNN_name.json> [more pairs ...]

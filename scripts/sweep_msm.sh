@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 for lg in ${SIZES:-20 21 22 23 24}; do
   for w in ${WINDOWS:-0}; do
-    python bench.py --headline-only --steps 10 --warmup 3 --log-n $lg --window $w 2>/dev/null | tail -1 | python -c "
+    python bench.py --full --headline-only --steps 10 --warmup 3 --log-n $lg --window $w 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 s=d['stages_ms']; c=d['config']

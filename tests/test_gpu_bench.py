@@ -18,15 +18,17 @@ pytestmark = pytest.mark.gpu
 
 
 def test_bench_contract_line(hip):
-    """bench.py prints ONE JSON line, last on stdout, with the driver's keys plus `roofline` and `cpu_baseline`."""
+    """bench.py --full prints ONE JSON line, last on stdout, with the driver's keys plus `roofline` and `cpu_baseline`."""
     import json
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--log-n", "14", "--steps", "3", "--warmup", "1",
+    # GPU_MAX_HW_QUEUES left to bench.py: the caller's environment may hold a value of its own, and the line must show bench.py's
+    env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--log-n", "14", "--steps", "3", "--warmup", "1",
                           "--cpu-sample-log", "12", "--kzg-rows", "10,8", "--e2e-rows", "10,8"], capture_output=True, text=True,
-                         timeout=600, cwd=root)
+                         timeout=600, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert sum(1 for ln in lines if ln.startswith("{")) == 1            # N = 1: exactly ONE JSON line
@@ -65,7 +67,7 @@ def test_bench_contract_line(hip):
     # the collective path (1-rank group; the all_gather is the LIBRARY's: kzg_comm_init / kzg_msm_sharded on real RCCL)
     # gives the same point
     env = dict(os.environ, BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29547")
-    out2 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--log-n", "14", "--steps", "3", "--warmup", "1",
+    out2 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--log-n", "14", "--steps", "3", "--warmup", "1",
                            "--no-cpu-baseline", "--no-adversarial", "--no-kzg-rows", "--msm26-log", "16", "--kzg22-log", "12"],
                           capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert out2.returncode == 0, out2.stderr[-2000:]
@@ -97,7 +99,7 @@ def test_bench_contract_line(hip):
     # a communicator that cannot be built (injected on the only rank): every rank falls back to the process group's
     # all_gather, the line says so, the result is the same
     env3 = dict(env, BENCH_FAULT="comm_init:0", MASTER_PORT="29548")
-    out3 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--log-n", "14", "--steps", "3", "--warmup", "1",
+    out3 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--log-n", "14", "--steps", "3", "--warmup", "1",
                            "--no-cpu-baseline", "--no-adversarial", "--no-dist-extra", "--no-pipelined"],
                           capture_output=True, text=True, timeout=600, cwd=root, env=env3)
     assert out3.returncode == 0, out3.stderr[-2000:]
@@ -105,6 +107,50 @@ def test_bench_contract_line(hip):
     assert rec3["result_hex"] == rec["result_hex"]
     assert rec3["config"]["collective"].startswith("gloo fallback (library RCCL preflight failed on rank 0: Fault")
     assert rec3["config"]["rccl_version"].startswith("none (gloo fallback")
+
+
+def test_bench_plain_line_and_dump_outputs(hip, tmp_path):
+    """A plain run (no --full) times the headline and nothing else; --dump-outputs writes what the last timed step returned,
+    byte for byte, for the MSM and for the commit+open workload, and that answer is the oracle's on the same seeded inputs."""
+    import subprocess
+    import sys
+
+    from bench import TAU, R_MOD, uniform_fr
+    from zkp_subnet_amd.engine import lagrange_factor
+
+    def run(*extra):
+        d = tmp_path / "_".join(x.strip("-") for x in extra)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(d)] + list(extra), capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert sum(1 for ln in lines if ln.startswith("{")) == 1
+        rec = json.loads(lines[-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in rec, k
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["higher_is_better"] is True
+        assert abs(rec["value"] - rec["config"]["points_per_gpu"] * 3 / (rec["ms_per_step"] * 3e-3)) / rec["value"] < 1e-6
+        for k in ("roofline", "mad_issue", "cpu_baseline", "pipelined", "stages_ms", "single_request_latency_ms", "adversarial",
+                  "kzg_commit_open", "e2e_from_text", "msm26", "pianist_kzg22"):
+            assert k not in rec, k
+        dumped = {p.stem: np.load(p) for p in d.glob("*.npy")}
+        assert all(a.dtype == np.float64 for a in dumped.values())
+        return rec, {k: bytes(a.astype(np.uint8)) for k, a in dumped.items()}
+
+    rec, dumped = run("--log-n", "14")
+    assert rec["msms_before_timed_region"] == 32 + 1             # the clock ramp, then W
+    assert list(dumped) == ["msm_point"] and dumped["msm_point"].hex() == rec["result_hex"]
+    e = hip()
+    e.gen_srs(TAU, 1, 14, 0)
+    assert dumped["msm_point"] == oc.msm(e.srs_read(0, 1 << 14), uniform_fr(1 << 14, 0), threads=4)
+
+    rec, dumped = run("--workload", "kzg22", "--log-n", "12")
+    assert sorted(dumped) == ["commitment", "evaluation", "proof"]
+    assert (dumped["commitment"] + dumped["evaluation"] + dumped["proof"]).hex() == rec["result_hex"]
+    e.gen_srs(TAU, 0, 12, 0, factors=[lagrange_factor(0, 0, (TAU * 7 + 1) % R_MOD)])
+    srs, row, alpha = e.srs_read(0, 1 << 12), uniform_fr(1 << 12, 0), uniform_fr(1, 1)
+    assert dumped["commitment"] == oc.commit(srs, row, True)
+    assert (dumped["evaluation"], dumped["proof"]) == oc.open_(srs, row, alpha, True)
 
 
 def test_bench_pipelined_region_overlaps_two_requests(hip):
@@ -115,7 +161,7 @@ def test_bench_pipelined_region_overlaps_two_requests(hip):
     import subprocess
     import sys
 
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline",
                           "--no-kzg-rows", "--no-adversarial", "--no-e2e"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")][-1])
@@ -138,7 +184,7 @@ def test_bench_two_ranks_on_one_gpu_exercises_the_multi_rank_logic(hip):
 
     env = dict(os.environ, BENCH_ONE_GPU="1", MASTER_ADDR="127.0.0.1", BENCH_COMM_INIT_TIMEOUT_S="60")
     env.pop("BENCH_BACKEND", None)
-    args = ["--gpus", "2", "--log-n", "13", "--steps", "3", "--warmup", "1", "--msm26-log", "15", "--kzg22-log", "11",
+    args = ["--full", "--gpus", "2", "--log-n", "13", "--steps", "3", "--warmup", "1", "--msm26-log", "15", "--kzg22-log", "11",
             "--cpu-sample-log", "12"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29561", os.path.join(ROOT, "bench.py")] + args
@@ -211,7 +257,7 @@ def test_bench_multi_rank_failures_never_cost_the_headline(hip):
 
     base = dict(os.environ, BENCH_ONE_GPU="1", MASTER_ADDR="127.0.0.1", BENCH_COMM_INIT_TIMEOUT_S="60", BENCH_PG_TIMEOUT_S="15")
     base.pop("BENCH_BACKEND", None)
-    args = ["--gpus", "2", "--log-n", "13", "--steps", "4", "--warmup", "1", "--msm26-log", "15", "--kzg22-log", "11",
+    args = ["--full", "--gpus", "2", "--log-n", "13", "--steps", "4", "--warmup", "1", "--msm26-log", "15", "--kzg22-log", "11",
             "--no-cpu-baseline", "--no-pipelined"]
 
     def launch(fault, port):

@@ -573,7 +573,7 @@ def test_real_ranks_bench_contract_with_every_visible_gpu():
 
     N = _need_gpus()
     N = 1 << (N.bit_length() - 1)           # msm26 needs a power-of-two number of ranks
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(N), "--steps", "3", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(N), "--steps", "3", "--warmup", "1"],
                          capture_output=True, text=True, timeout=3000, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     line = _last_json(out.stdout)
