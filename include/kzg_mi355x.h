@@ -125,6 +125,20 @@ int kzg_open(kzg_ctx* ctx, uint32_t i, const uint8_t* row_be32, uint64_t T, int 
 int kzg_commit_open(kzg_ctx* ctx, uint32_t i, const uint8_t* row_be32, uint64_t T, int evaluation_form,
                     const uint8_t alpha_be32[32], uint8_t out_commitment48[48], uint8_t out_eval32[32],
                     uint8_t out_proof48[48]);
+/* Batched opening of k rows of worker i at ONE point alpha (the GWC batched opening a PLONK prover uses for the polynomials
+ * of one sub-circuit): rows_be32 holds k rows of T elements each, row-major; out_commitments48[j] = kzg_commit(i, f_j),
+ * out_evals32[j] = f_j(alpha), and ONE proof pi = MSM(U_i, (h - h(alpha)) / (X - alpha)) for h = sum_j gamma^j f_j --
+ * exactly the proof of kzg_open(i, h, alpha).  k = 1 reproduces kzg_commit_open.  Verification (kzg_vk_verify_open_batch):
+ *   e(sum_j gamma^j C_j - (sum_j gamma^j y_j) [L_i]_1, [1]_2) == e(pi, [tau_x - alpha]_2).
+ * SOUNDNESS: gamma must be chosen by the verifier AFTER the commitments are fixed (a prover who knows gamma in advance can
+ * make a false y_j cancel in the combination).  The library takes gamma as an input, like alpha, and derives nothing: the
+ * caller's protocol supplies both.  k = 0, k > KZG_MAX_BATCH_OPEN, alpha or gamma >= r and every worker-index / length
+ * check of kzg_commit_open give KZG_E_ARG; the context keeps serving.  Rows up to 2^18 run as ONE MSM pass with k + 1
+ * scalar sets (one sort, one bucket tree with k + 1 roots). */
+#define KZG_MAX_BATCH_OPEN 16
+int kzg_commit_open_batch(kzg_ctx* ctx, uint32_t i, uint32_t k, const uint8_t* rows_be32 /* k*T*32, row-major */,
+                          uint64_t T, int evaluation_form, const uint8_t alpha_be32[32], const uint8_t gamma_be32[32],
+                          uint8_t* out_commitments48 /* k*48 */, uint8_t* out_evals32 /* k*32 */, uint8_t out_proof48[48]);
 /* The UNCHANGED reference miner makes two calls per request with the same row -- worker_commit(i, poly), then
  * worker_open(i, poly, x) (neurons/miner.py:56-61).  These forms take a 128-bit content tag identifying the row's bytes
  * (the host codec computes it while decoding the text); the coefficient vectors of the last four rows stay on the
@@ -173,6 +187,13 @@ int kzg_vk_verify(const kzg_vk* vk, uint32_t i, const uint8_t proof48[48], const
 int kzg_vk_verify_batch(const kzg_vk* vk, uint32_t n, const uint32_t* idx, const uint8_t* proofs48,
                         const uint8_t alpha_be32[32], const uint8_t* evals_be32, const uint8_t* commitments48, int threads,
                         int* out_all_valid);
+/* One batched opening (kzg_commit_open_batch) of k rows of slice i:
+ *   e(sum_j gamma^j C_j - (sum_j gamma^j y_j) [L_i]_1, [1]_2) == e(pi, [tau_x - alpha]_2).
+ * Same rules as kzg_vk_verify: malformed, off-curve or non-G1 commitment / proof bytes give *out_valid = 0 (not an error);
+ * k = 0, k > KZG_MAX_BATCH_OPEN or i outside the key -> KZG_E_ARG; alpha, gamma or an evaluation >= r -> KZG_E_SCALAR. */
+int kzg_vk_verify_open_batch(const kzg_vk* vk, uint32_t i, uint32_t k, const uint8_t* commitments48,
+                             const uint8_t* evals_be32, const uint8_t alpha_be32[32], const uint8_t gamma_be32[32],
+                             const uint8_t proof48[48], int* out_valid);
 
 /* ---- multi-GPU: each rank reduces its SRS shard to ONE partial sum; the 192-byte partials are exchanged by
  *      the caller (RCCL all_gather over xGMI in zkp_subnet_amd.distributed) and summed on any rank. */
@@ -293,6 +314,10 @@ int kzg_multi_commit_open(kzg_multi* m, uint32_t i, const uint8_t* row_be32, uin
 int kzg_multi_commit_open_rows(kzg_multi* m, uint32_t n_rows, const uint32_t* indices, const uint8_t* rows_be32, uint64_t T,
                                int evaluation_form, const uint8_t alpha_be32[32], uint8_t* out_commitments48,
                                uint8_t* out_evals32, uint8_t* out_proofs48, int* out_status);
+/* kzg_commit_open_batch on the device of worker i (routed like kzg_multi_commit_open) */
+int kzg_multi_commit_open_batch(kzg_multi* m, uint32_t i, uint32_t k, const uint8_t* rows_be32, uint64_t T,
+                                int evaluation_form, const uint8_t alpha_be32[32], const uint8_t gamma_be32[32],
+                                uint8_t* out_commitments48, uint8_t* out_evals32, uint8_t out_proof48[48]);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

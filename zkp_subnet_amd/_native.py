@@ -16,6 +16,7 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 # scripts point at it instead of overwriting the shipped file.  Never a different implementation, never a fallback.
 LIB_PATH = os.environ.get("KZG_MI355X_LIB") or os.path.join(HERE, "libkzg_mi355x.so")
 
+KZG_MAX_BATCH_OPEN = 16   # include/kzg_mi355x.h
 KZG_OK, KZG_E_ARG, KZG_E_SCALAR, KZG_E_POINT, KZG_E_HIP, KZG_E_NOMEM, KZG_E_BUSY, KZG_E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
 STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_SCALAR", -3: "E_POINT", -4: "E_HIP", -5: "E_NOMEM", -6: "E_BUSY", -7: "E_COMM"}
 TIMING_NAMES = ["decode", "ntt", "digits", "scan", "scatter", "accumulate", "fixup", "tree", "final", "poly", "total", "collective"]
@@ -48,6 +49,7 @@ SYMBOLS = {
     "kzg_commit": (_I, [_P, _U32, _B, _U64, _I, _B]),
     "kzg_open": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B]),
     "kzg_commit_open": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B, _B]),
+    "kzg_commit_open_batch": (_I, [_P, _U32, _U32, _B, _U64, _I, _B, _B, _B, _B, _B]),
     "kzg_commit_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B]),
     "kzg_open_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B, _B]),
     "kzg_row_cache_stats": (_I, [_P, ctypes.POINTER(_U64)]),
@@ -61,6 +63,7 @@ SYMBOLS = {
     "kzg_vk_export": (_I, [_P, _B, _U64]),
     "kzg_vk_verify": (_I, [_P, _U32, _B, _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_vk_verify_batch": (_I, [_P, _U32, ctypes.POINTER(_U32), _B, _B, _B, _B, _I, ctypes.POINTER(_I)]),
+    "kzg_vk_verify_open_batch": (_I, [_P, _U32, _U32, _B, _B, _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_vk_pairing": (_I, [_B, _B, _B]),
     "kzg_msm_partial": (_I, [_P, _B, _U64, _U64, _B]),
     "kzg_g1_sum": (_I, [_P, _B, _U32, _B]),
@@ -95,6 +98,7 @@ SYMBOLS = {
     "kzg_multi_commit": (_I, [_P, _U32, _B, _U64, _I, _B]),
     "kzg_multi_open": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B]),
     "kzg_multi_commit_open": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B, _B]),
+    "kzg_multi_commit_open_batch": (_I, [_P, _U32, _U32, _B, _U64, _I, _B, _B, _B, _B, _B]),
     "kzg_multi_commit_open_rows": (_I, [_P, _U32, ctypes.POINTER(_U32), _B, _U64, _I, _B, _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_upload_fr": (_I, [_P, _I, _B, _U64, _I]),
     "kzg_msm_resident": (_I, [_P, _I, _U64, _U64, _B]),

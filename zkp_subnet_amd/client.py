@@ -18,7 +18,7 @@ import secrets
 from typing import Any, Dict, List, Optional, Sequence
 
 from . import codec
-from ._native import KZG_E_ARG, KZG_E_POINT, KZG_E_SCALAR, KzgError
+from ._native import KZG_E_ARG, KZG_E_POINT, KZG_E_SCALAR, KZG_MAX_BATCH_OPEN, KzgError
 
 R_MODULUS = codec.R_MODULUS
 log = logging.getLogger("zkp_subnet_amd.client")
@@ -210,6 +210,22 @@ class Client:
         return {"commitment": codec.g1_to_b64(c), "eval": codec.be32_to_fr(ev), "proof": codec.g1_to_b64(pf)}
 
     @_guard
+    def worker_commit_open_batch(self, i: int, polys: Sequence[Sequence[str]], x: str, gamma: str):
+        """Extension: k rows of worker i (a PLONK sub-circuit's wires, permutation and quotient pieces) opened at x with
+        ONE proof for sum_j gamma^j f_j.  gamma must be drawn by the verifier after the commitments are fixed."""
+        k = len(polys)
+        if k == 0 or k > KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"worker_commit_open_batch: {k} rows, expected 1 .. {KZG_MAX_BATCH_OPEN}")
+        if any(len(p) != len(polys[0]) for p in polys):
+            raise codec.CodecError("worker_commit_open_batch: rows of unequal length")
+        a, g = codec.fr_to_be32(x), codec.fr_to_be32(gamma)
+        fast = getattr(self.engine, "commit_open_batch_list", None)
+        cs, evs, pf = fast(self._slice(i), polys, a, g, True) if fast and codec._wire else \
+            self.engine.commit_open_batch(self._slice(i), [codec.fr_list_to_be32(p) for p in polys], a, g, True)
+        return {"commitments": [codec.g1_to_b64(c) for c in cs], "evals": [codec.be32_to_fr(e) for e in evs],
+                "proof": codec.g1_to_b64(pf)}
+
+    @_guard
     def aggregate_commitments(self, commitments: Sequence[str]):
         """Pianist master aggregation: sum_i commit_i of the worker rows' commitments = the commitment of the whole
         bivariate polynomial (reference neurons/validator.py:196-198 distributes the rows; README.md:38 names the
@@ -225,6 +241,19 @@ class Client:
             raise NotImplementedError("this engine has no verifier")
         ok = verify(self._slice(i), codec.g1_from_b64(proof), codec.fr_to_be32(alpha), codec.fr_to_be32(eval),
                     codec.g1_from_b64(commitment))
+        return {"valid": bool(ok)}
+
+    @_guard
+    def worker_verify_open_batch(self, i: int, proof: str, alpha: str, gamma: str, evals: Sequence[str],
+                                 commitments: Sequence[str]):
+        """Extension: the pairing check of one worker_commit_open_batch answer."""
+        vb = getattr(self.engine, "verify_open_batch", None)
+        if vb is None:
+            raise NotImplementedError("this engine has no batched-opening verifier")
+        if len(evals) != len(commitments) or not 1 <= len(evals) <= KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"worker_verify_open_batch: {len(evals)} evals for {len(commitments)} commitments")
+        ok = vb(self._slice(i), [codec.g1_from_b64(c) for c in commitments], [codec.fr_to_be32(e) for e in evals],
+                codec.fr_to_be32(alpha), codec.fr_to_be32(gamma), codec.g1_from_b64(proof))
         return {"valid": bool(ok)}
 
     @_guard

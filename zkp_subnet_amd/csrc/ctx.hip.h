@@ -55,6 +55,8 @@ namespace kzg_host {  // finish_host.cpp
 void xyzz_to_c48(const uint32_t* xyzz, uint8_t out48[48]);
 void xyzz_pair_to_c48(const uint32_t* xyzz0, const uint32_t* xyzz1, uint8_t out0[48], uint8_t out1[48]);
 void xyzz_to_partial192(const uint32_t* xyzz, uint8_t out192[192]);
+// n points (56 words each, consecutive), one shared inversion
+void xyzz_batch_to_c48(const uint32_t* xyzz, uint32_t n, uint8_t* out48);
 }  // namespace kzg_host
 
 namespace kzg_impl {
@@ -122,6 +124,14 @@ enum {
     TB_COPY = 832,
     TB_ALPHA_M = 832, TB_Y_M = 864, TB_ALPHA_BE = 896, TB_SIZE = 1024
 };
+// the batched opening's record (kzg_commit_open_batch; device Lane::brec, pinned Lane::bpin): k + 1 result points in the
+// XYZZ working form (C_0 .. C_{k-1}, pi), k evaluations big-endian, the GPU-side encodings (host_finish off); [0, BR_COPY)
+// comes back to the host page in one copy before the lane's ordinary record
+enum {
+    BR_RES = 0, BR_EVAL = BR_RES + MSM_MAX_SETS * 224, BR_C48 = BR_EVAL + KZG_MAX_BATCH_OPEN * 32,
+    BR_COPY = BR_C48 + MSM_MAX_SETS * 48, BR_Y_M = BR_COPY, BR_SIZE = BR_Y_M + KZG_MAX_BATCH_OPEN * 32
+};
+static_assert(BR_COPY % 4 == 0 && BR_COPY <= 8192, "the batched record is published by words into an 8 KB page");
 #define PIN_MAXLEN 1024           // offset of the fold-depth read-back inside the lane's pinned page
 #define PIN_SEQ 2048              // sequence word of the last published record (polled by finish())
 #define PIN_SEQ_SORT 2052         // sequence word of the last published fold-depth / overflow pair (polled by msm_core)
@@ -149,6 +159,11 @@ struct Lane {
     hipEvent_t ev_verify = nullptr;  // beside the request's own kernels (the lane's publish waits for this event)
     DevBuf vbuf;
     bool partial = false;         // outstanding ticket wants the 192-byte partial
+    // kzg_commit_open_batch: its record (BR_*; device + an 8 KB pinned, mapped page), the rows' coefficients and their
+    // gamma-combination -- allocated by the first batched call on the lane
+    DevBuf brec, bcoef, bcomb;
+    uint8_t* bpin = nullptr;
+    uint8_t* bpin_dev = nullptr;
     // profiling spans of the call running on this lane
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
@@ -321,7 +336,7 @@ inline int ilog2_exact(uint64_t n) {
 }
 int pick_chunk(uint64_t entries);
 int msm_core(kzg_ctx* ctx, Lane& L, const uint32_t* scalars, int mont, uint64_t n, uint64_t srs_offset, g1_xyzz_t* out_xyzz,
-             const uint32_t* scalars2 = nullptr, int mont2 = 0);
+             const uint32_t* scalars2 = nullptr, int mont2 = 0, int nrows = 1, uint64_t row_stride = 0);
 int ensure_twiddles(kzg_ctx* ctx, Lane& L, int log_n, int inverse, uint32_t** tw, uint32_t** invn);
 int row_to_coeffs(kzg_ctx* ctx, Lane& L, const uint32_t* row_dev, uint64_t T, int evaluation_form, const uint32_t** coeffs,
                   uint32_t* dst = nullptr);
@@ -336,6 +351,11 @@ struct VerifyJob {   // a row-cache hit's evidence: the caller's row (host) agai
 int commit_open_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* row_dev, uint64_t T, int evaluation_form,
                     const uint8_t* alpha_be32, uint8_t* out_c48, uint8_t* out_eval32, uint8_t* out_p48,
                     const uint32_t* coeffs_ready = nullptr, uint32_t* coeffs_dst = nullptr, const VerifyJob* verify = nullptr);
+// k rows (Montgomery, k x T elements at row_dev) of worker i, one point alpha, one challenge gamma: the k commitments, the k
+// evaluations and ONE proof for h = sum_j gamma^j f_j (kzg_commit_open_batch)
+int commit_open_batch_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* rows_dev, uint32_t k, uint64_t T,
+                          int evaluation_form, const uint8_t* alpha_be32, const uint8_t* gamma_be32, uint8_t* out_c48,
+                          uint8_t* out_evals32, uint8_t* out_p48);
 
 // ---- the collective (comm.hip)
 void comm_teardown(kzg_ctx* ctx);

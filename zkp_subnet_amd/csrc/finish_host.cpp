@@ -7,6 +7,8 @@
 // in the same copy that used to carry the 48.  It is an encoding step of O(1) work per request, not a fallback: the
 // sums themselves never leave the GPU, and nothing here runs when the HIP path fails.  kzg_set_host_finish(ctx, 0)
 // keeps the encoding on the GPU (the device-to-device entry points always do).
+#include <vector>
+
 #include "fp_host.h"
 
 namespace kzg_host {
@@ -102,6 +104,34 @@ void xyzz_pair_to_c48(const uint32_t* xyzz0, const uint32_t* xyzz1, uint8_t out0
     const Fp i0 = i * d1, i1 = i * d0;   // 1 / d0, 1 / d1
     affine_to_c48(X0 * (i0 * ZZZ0), Y0 * (i0 * ZZ0), out0);
     affine_to_c48(X1 * (i1 * ZZZ1), Y1 * (i1 * ZZ1), out1);
+}
+// the k + 1 points of a batched opening: ONE inversion for all of them (Montgomery's trick over the finite ones)
+void xyzz_batch_to_c48(const uint32_t* xyzz, uint32_t n, uint8_t* out48) {
+    std::vector<Fp> d(n), pre(n);
+    std::vector<uint32_t> fin;
+    fin.reserve(n);
+    for (uint32_t p = 0; p < n; p++) {
+        const uint32_t* q = xyzz + 56 * (size_t)p;
+        if (limbs_all_zero(q + 28)) {
+            infinity_c48(out48 + 48 * (size_t)p);
+            continue;
+        }
+        d[fin.size()] = fp_from_limbs28(q + 28) * fp_from_limbs28(q + 42);   // ZZ * ZZZ
+        fin.push_back(p);
+    }
+    if (fin.empty()) return;
+    const size_t m = fin.size();
+    pre[0] = d[0];
+    for (size_t t = 1; t < m; t++) pre[t] = pre[t - 1] * d[t];
+    Fp acc = inv(pre[m - 1]);   // 1 / (d_0 ... d_{m-1})
+    for (size_t t = m; t-- > 0;) {
+        const Fp it = t ? acc * pre[t - 1] : acc;   // 1 / d_t
+        if (t) acc = acc * d[t];
+        const uint32_t* q = xyzz + 56 * (size_t)fin[t];
+        const Fp X = fp_from_limbs28(q), Y = fp_from_limbs28(q + 14), ZZ = fp_from_limbs28(q + 28),
+                 ZZZ = fp_from_limbs28(q + 42);
+        affine_to_c48(X * (it * ZZZ), Y * (it * ZZ), out48 + 48 * (size_t)fin[t]);
+    }
 }
 // 192-byte partial-sum record: X, Y, ZZ, ZZZ as canonical residues (still Montgomery, R = 2^392), 12 x u32 LE each;
 // all zeros = infinity (include/kzg_mi355x.h, kzg_msm_partial)

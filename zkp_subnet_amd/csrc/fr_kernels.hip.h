@@ -27,5 +27,15 @@ void launch_fr_ntt(hipStream_t s, const uint32_t* in, uint32_t* out, int log_n, 
 void launch_poly_open(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t* alpha_mont, uint32_t* h,
                       uint32_t* hnext, uint32_t* y_mont, uint32_t* q_canon_or_null,
                       const uint8_t* alpha_be32_host = nullptr, uint32_t* bad = nullptr, uint8_t* y_be_or_null = nullptr);
+// the batched opening: y_r = f_r(alpha) for `rows` rows of n Montgomery coefficients at a stride of n elements, in the
+// launches of ONE evaluation (row index in the grid).  h, hnext: rows x h_row_words words of scratch each (h_row_words >=
+// 8 x the single-row size above); y_mont: rows x 8 words; y_be: rows x 32 bytes; alpha as in launch_poly_open
+void launch_poly_eval_rows(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t rows, uint32_t* alpha_mont,
+                           uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont,
+                           const uint8_t* alpha_be32_host, uint32_t* bad, uint8_t* y_be);
+// out[t] = sum_j gamma^j rows[j * n + t] (Montgomery in and out), j < k <= 16; gamma as 32 big-endian HOST bytes (a kernel
+// argument), *bad raised when it is >= r
+void launch_fr_combine_rows(hipStream_t s, const uint32_t* rows_mont, uint64_t n, uint32_t k, const uint8_t gamma_be32_host[32],
+                            uint32_t* out_mont, uint32_t* bad);
 // *flag |= 1 when a[0, n_words) and b[0, n_words) differ (n_words a multiple of 4): verification of a row-cache hit
 void launch_words_differ(hipStream_t s, const uint32_t* a, const uint32_t* b, uint64_t n_words, uint32_t* flag);

@@ -27,12 +27,16 @@ KZG_DEV void fr9_pow2k(fr9_t& a, int k) {  // a <- a^(2^k), canonical in and out
 // ARG: alpha comes as the kernel ARGUMENT (its 32 big-endian bytes) instead of from memory: the first kernel of an
 // opening converts it itself -- every lane, it is one product -- and lane 0 leaves the Montgomery form at alpha_out for
 // the kernels behind it (and raises *bad for a value >= r); a 1-lane conversion kernel ahead of it was ~5 us of latency
+// Several rows at once (the batched opening): row blockIdx.y reads f + y * f_rs and writes h + y * h_rs (words).
 template <bool ARG>
 __global__ void __launch_bounds__(256) k_poly_chunk_eval(const uint32_t* __restrict__ f, uint64_t n, int lchunk,
                                                           const uint32_t* __restrict__ alpha_mont, int sq,
                                                           uint32_t* __restrict__ h, const FrArg arg,
-                                                          uint32_t* __restrict__ alpha_out, uint32_t* __restrict__ bad) {
+                                                          uint32_t* __restrict__ alpha_out, uint32_t* __restrict__ bad,
+                                                          uint64_t f_rs, uint64_t h_rs) {
     uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    f += blockIdx.y * f_rs;
+    h += blockIdx.y * h_rs;
     const uint64_t L = (uint64_t)1 << lchunk;
     uint64_t lo = t * L;
     fr9_t a, s, c;
@@ -42,7 +46,7 @@ __global__ void __launch_bounds__(256) k_poly_chunk_eval(const uint32_t* __restr
         for (int i = 0; i < 8; i++) w[i] = bswap32(arg.w[7 - i]);
         fr9_from_words(a, w);
         fr9_to_mont(a, a);
-        if (t == 0) {
+        if (t == 0 && blockIdx.y == 0) {
             if (fr_words_ge_r(w)) atomicOr(bad, 1u);
             fr9_store(alpha_out, a);
         }
@@ -62,13 +66,17 @@ __global__ void __launch_bounds__(256) k_poly_chunk_eval(const uint32_t* __restr
 }
 // Suffix recurrence over chunks, H_t = h_t + beta H_{t+1}, beta = alpha^L: one NT_-lane block; lane v serially
 // folds m consecutive chunks, then a Hillis-Steele suffix scan whose multiplier (beta^m)^(2^step) is uniform.
-// Writes hnext[t] = H_{t+1} and y = H_0 = f(alpha).
+// Writes hnext[t] = H_{t+1} and y = H_0 = f(alpha).  Workgroup b scans row b: h and hnext at + b * h_rs words, y at + b.
 template <uint32_t NT_>
 __global__ void __launch_bounds__(NT_) k_poly_chunk_scan(const uint32_t* __restrict__ h, uint64_t nchunks, int lchunk,
                                                            const uint32_t* __restrict__ alpha_mont,
                                                            uint32_t* __restrict__ hnext, uint32_t* __restrict__ y_mont,
-                                                           uint8_t* __restrict__ y_be_or_null) {
+                                                           uint8_t* __restrict__ y_be_or_null, uint64_t h_rs) {
     __shared__ uint32_t sm[9][NT_];
+    h += blockIdx.x * h_rs;
+    hnext += blockIdx.x * h_rs;
+    y_mont += 8 * blockIdx.x;
+    if (y_be_or_null) y_be_or_null += 32 * blockIdx.x;
     const uint32_t v = threadIdx.x;
     const uint64_t m = (nchunks + NT_ - 1) / NT_;
     const uint64_t lo = (uint64_t)v * m;
@@ -189,6 +197,39 @@ __global__ void __launch_bounds__(256) k_poly_quotient(const uint32_t* __restric
     }
 }
 
+// ---- the batched opening's combination h[t] = sum_j gamma^j c_j[t] over k Montgomery rows at a stride of n elements
+// (Horner from the last row: k - 1 dependent products per element, gamma in registers -- no table of its powers is read
+// from memory).  HBM-bound: k * 32 bytes in and 32 out per element.  gamma arrives as the kernel ARGUMENT (32 big-endian
+// bytes, as alpha does in k_poly_chunk_eval); every lane converts it -- one product -- and lane 0 raises *bad for a value
+// >= r.  The running value stays lazy (the chunk loop's bound: <= 16 steps) and is canonicalised once, when stored.
+__global__ void __launch_bounds__(256) k_fr_combine_rows(const uint32_t* __restrict__ rows, uint64_t n, uint32_t k,
+                                                          const FrArg arg, uint32_t* __restrict__ out,
+                                                          uint32_t* __restrict__ bad) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t w[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) w[i] = bswap32(arg.w[7 - i]);
+    if (t == 0 && fr_words_ge_r(w)) atomicOr(bad, 1u);
+    if (t >= n) return;
+    fr9_t g, s, c;
+    fr9_from_words(g, w);
+    fr9_to_mont(g, g);
+    fr9_load(s, rows + 8 * ((uint64_t)(k - 1) * n + t));
+    for (uint32_t j = k - 1; j-- > 0;) {
+        fr9_load(c, rows + 8 * ((uint64_t)j * n + t));
+        fr9_mul(s, s, g);
+        fr9_add(s, s, c);
+    }
+    fr9_reduce(s, s);
+    fr9_store(out + 8 * t, s);
+}
+void launch_fr_combine_rows(hipStream_t s, const uint32_t* rows_mont, uint64_t n, uint32_t k, const uint8_t gamma_be32_host[32],
+                            uint32_t* out_mont, uint32_t* bad) {
+    FrArg arg;
+    memcpy(arg.w, gamma_be32_host, 32);
+    if (n && k) k_fr_combine_rows<<<nblk(n, 256), 256, 0, s>>>(rows_mont, n, k, arg, out_mont, bad);
+}
+
 // ---- long rows (16 coefficients per lane): the quotient (and, as an A/B form, the level-0 fold) with the coefficients
 // staged through LDS.  A lane of the kernels above walks ITS 512-byte chunk, so one wave load touches 64 pieces of 32
 // bytes at a 512-byte stride (k_poly_quotient: 2.3 TB/s for 256 MB, with the caches reassembling the lines).  Here ONE
@@ -284,28 +325,74 @@ void launch_words_differ(hipStream_t s, const uint32_t* a, const uint32_t* b, ui
     k_words_differ<<<blocks, 256, 0, s>>>(reinterpret_cast<const uint4*>(a), reinterpret_cast<const uint4*>(b), n16, flag);
 }
 
-void launch_poly_open(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t* alpha_mont, uint32_t* h,
-                      uint32_t* hnext, uint32_t* y_mont, uint32_t* q_canon_or_null, const uint8_t* alpha_be32_host,
-                      uint32_t* bad, uint8_t* y_be_or_null) {
+// Level 0 folds 2^l0 coefficients per lane, every further level 16 values of the level below, until at most 2048
+// values are left for the single-workgroup scan; then (launch_poly_open) the suffix values H are expanded back down level
+// by level.  Every serial loop is <= 16 long (each step is one dependent Fr product, ~1 us for a lone wave), and
+// all levels but the scan fill the GPU.  The level arrays are stacked in h / hnext (serve.hip / pipeline.hip size them for
+// (n+3)/4 * 3/2 + 64 entries; the levels above the first sum to < 1/3 of it).  `rows` rows of n coefficients (at a
+// stride of n elements) go through the same launches side by side: row r's level arrays at h / hnext + r * h_row_words,
+// its y at y_mont + 8 r (and y_be + 32 r) -- k evaluations for the latency of one.
+struct PolyLevels {
+    int K;
+    int l[16], sq[16];
+    uint64_t n[16], off[16];
+};
+static void poly_up(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t rows, uint32_t* alpha_mont, uint32_t* h,
+                    uint32_t* hnext, uint64_t h_rs, uint32_t* y_mont, const uint8_t* alpha_be32_host, uint32_t* bad,
+                    uint8_t* y_be_or_null, PolyLevels& lv) {
     FrArg arg;
     memset(&arg, 0, sizeof(arg));
     if (alpha_be32_host) memcpy(arg.w, alpha_be32_host, 32);
+    const uint64_t f_rs = rows > 1 ? n * 8 : 0;
+    const int l0 = poly_lchunk(n);
+    const int lup = 4;   // log2 chunk of the levels above the first (4-long chunks + more levels measured no faster on short rows)
+    int* lv_l = lv.l;
+    int* lv_sq = lv.sq;
+    uint64_t* lv_n = lv.n;
+    uint64_t* lv_off = lv.off;
+    int K = 1;
+    lv_l[0] = l0; lv_sq[0] = 0; lv_n[0] = n; lv_off[0] = 0;           // level 0 = f itself (offset unused)
+    lv_n[1] = (n + ((uint64_t)1 << l0) - 1) >> l0; lv_sq[1] = l0; lv_off[1] = 0;
+    if (alpha_be32_host)
+        k_poly_chunk_eval<true><<<dim3(nblk(lv_n[1], 256), rows), 256, 0, s>>>(f_mont, n, l0, alpha_mont, 0, h, arg, alpha_mont,
+                                                                           bad, f_rs, h_rs);
+    else
+        k_poly_chunk_eval<false><<<dim3(nblk(lv_n[1], 256), rows), 256, 0, s>>>(f_mont, n, l0, alpha_mont, 0, h, arg, nullptr,
+                                                                            nullptr, f_rs, h_rs);
+    while (lv_n[K] > 2048 && K < 14) {
+        lv_l[K] = lup;
+        lv_n[K + 1] = (lv_n[K] + ((uint64_t)1 << lup) - 1) >> lup;
+        lv_sq[K + 1] = lv_sq[K] + lup;
+        lv_off[K + 1] = lv_off[K] + lv_n[K];
+        k_poly_chunk_eval<false><<<dim3(nblk(lv_n[K + 1], 256), rows), 256, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lup, alpha_mont,
+                                                                                lv_sq[K], h + 8 * lv_off[K + 1], arg, nullptr,
+                                                                                nullptr, h_rs, h_rs);
+        K++;
+    }
+    // the scan is one workgroup of dependent Fr products: 256 lanes (one wave per SIMD, <= 8 values each) run the chain
+    // at a lone wave's issue rate; 1024 lanes (four waves per SIMD) only when there is more than that to fold
+    if (lv_n[K] <= 1024)
+        k_poly_chunk_scan<256><<<rows, 256, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lv_sq[K], alpha_mont, hnext + 8 * lv_off[K],
+                                                    y_mont, y_be_or_null, h_rs);
+    else
+        k_poly_chunk_scan<1024><<<rows, 1024, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lv_sq[K], alpha_mont, hnext + 8 * lv_off[K],
+                                                      y_mont, y_be_or_null, h_rs);
+    lv.K = K;
+}
+void launch_poly_open(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t* alpha_mont, uint32_t* h,
+                      uint32_t* hnext, uint32_t* y_mont, uint32_t* q_canon_or_null, const uint8_t* alpha_be32_host,
+                      uint32_t* bad, uint8_t* y_be_or_null) {
     if (!n) {
         if (alpha_be32_host) launch_fr_from_host32(s, alpha_be32_host, alpha_mont, 1, bad);
         return;
     }
-    // Level 0 folds 2^l0 coefficients per lane, every further level 16 values of the level below, until at most 2048
-    // values are left for the single-workgroup scan; then the suffix values H are expanded back down level by
-    // level.  Every serial loop is <= 16 long (each step is one dependent Fr product, ~1 us for a lone wave), and
-    // all levels but the scan fill the GPU.  The level arrays are stacked in h / hnext (serve.hip / pipeline.hip size them for
-    // (n+3)/4 * 3/2 + 64 entries; the levels above the first sum to < 1/3 of it).
-    const int l0 = poly_lchunk(n);
-    const int lup = 4;   // log2 chunk of the levels above the first (4-long chunks + more levels measured no faster on short rows)
-    int lv_l[16], lv_sq[16];
-    uint64_t lv_n[16], lv_off[16];
-    int K = 1;
-    lv_l[0] = l0; lv_sq[0] = 0; lv_n[0] = n; lv_off[0] = 0;           // level 0 = f itself (offset unused)
-    lv_n[1] = (n + ((uint64_t)1 << l0) - 1) >> l0; lv_sq[1] = l0; lv_off[1] = 0;
+    PolyLevels lv;
+    poly_up(s, f_mont, n, 1, alpha_mont, h, hnext, 0, y_mont, alpha_be32_host, bad, y_be_or_null, lv);
+    const int l0 = lv.l[0], K = lv.K;
+    const int* lv_l = lv.l;
+    const int* lv_sq = lv.sq;
+    const uint64_t* lv_n = lv.n;
+    const uint64_t* lv_off = lv.off;
     // long rows: the level-0 fold and the quotient with their coefficients staged through LDS (KZG_POLY_NO_LDS=1: the
     // strided forms, kept for the A/B and as the reference of test_poly_kernel_variants_agree)
     static const bool no_lds = getenv("KZG_POLY_NO_LDS") != nullptr;
@@ -315,27 +402,6 @@ void launch_poly_open(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_
     static const int lds_min_log = getenv("KZG_POLY_LDS_MIN_LOG") ? atoi(getenv("KZG_POLY_LDS_MIN_LOG")) : 21;
     const bool lds = !no_lds && l0 == 4 && (n & 1023) == 0 && n >= ((uint64_t)1 << lds_min_log);
     // (the level-0 fold gains nothing from LDS staging: 53 against 49 us, profiles/r04_ab_opening_lds_staging.log -- strided)
-    if (alpha_be32_host)
-        k_poly_chunk_eval<true><<<nblk(lv_n[1], 256), 256, 0, s>>>(f_mont, n, l0, alpha_mont, 0, h, arg, alpha_mont, bad);
-    else
-        k_poly_chunk_eval<false><<<nblk(lv_n[1], 256), 256, 0, s>>>(f_mont, n, l0, alpha_mont, 0, h, arg, nullptr, nullptr);
-    while (lv_n[K] > 2048 && K < 14) {
-        lv_l[K] = lup;
-        lv_n[K + 1] = (lv_n[K] + ((uint64_t)1 << lup) - 1) >> lup;
-        lv_sq[K + 1] = lv_sq[K] + lup;
-        lv_off[K + 1] = lv_off[K] + lv_n[K];
-        k_poly_chunk_eval<false><<<nblk(lv_n[K + 1], 256), 256, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lup, alpha_mont, lv_sq[K],
-                                                                        h + 8 * lv_off[K + 1], arg, nullptr, nullptr);
-        K++;
-    }
-    // the scan is one workgroup of dependent Fr products: 256 lanes (one wave per SIMD, <= 8 values each) run the chain
-    // at a lone wave's issue rate; 1024 lanes (four waves per SIMD) only when there is more than that to fold
-    if (lv_n[K] <= 1024)
-        k_poly_chunk_scan<256><<<1, 256, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lv_sq[K], alpha_mont, hnext + 8 * lv_off[K], y_mont,
-                                                 y_be_or_null);
-    else
-        k_poly_chunk_scan<1024><<<1, 1024, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lv_sq[K], alpha_mont, hnext + 8 * lv_off[K], y_mont,
-                                                   y_be_or_null);
     for (int k = K - 1; k >= 1; k--)
         k_poly_chunk_expand<<<nblk(lv_n[k + 1], 256), 256, 0, s>>>(h + 8 * lv_off[k], lv_n[k], lv_l[k], alpha_mont,
                                                                    lv_sq[k], hnext + 8 * lv_off[k + 1],
@@ -344,5 +410,11 @@ void launch_poly_open(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_
         if (lds) k_poly_quotient16_lds<<<(uint32_t)(n >> 10), 64, 0, s>>>(f_mont, n, alpha_mont, hnext, q_canon_or_null);
         else k_poly_quotient<<<nblk(lv_n[1], 256), 256, 0, s>>>(f_mont, n, l0, alpha_mont, hnext, q_canon_or_null);
     }
+}
+void launch_poly_eval_rows(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t rows, uint32_t* alpha_mont,
+                           uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont,
+                           const uint8_t* alpha_be32_host, uint32_t* bad, uint8_t* y_be) {
+    PolyLevels lv;
+    if (n && rows) poly_up(s, f_mont, n, rows, alpha_mont, h, hnext, h_row_words, y_mont, alpha_be32_host, bad, y_be, lv);
 }
 

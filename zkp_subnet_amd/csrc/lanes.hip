@@ -337,6 +337,7 @@ void kzg_destroy(kzg_ctx* ctx) {
         if (L.vstream) (void)hipStreamDestroy(L.vstream);
         if (L.tail) (void)hipFree(L.tail);
         if (L.pin) (void)hipHostFree(L.pin);
+        if (L.bpin) (void)hipHostFree(L.bpin);
         if (L.stream) (void)hipStreamDestroy(L.stream);
     }
     if (ctx->aux) {

@@ -27,7 +27,7 @@ struct MsmShape {
     WinLayout lay;
     uint32_t nbuckets;   // 2^(c-1) per MSM; nbatch MSMs over the same points use nbatch consecutive bucket sets
     uint64_t n;          // number of (scalar, point) pairs in each MSM of the batch
-    int nbatch;          // 1, or 2: commit + open as ONE pass (scalar set b -> bucket set b), see launch_msm_sort
+    int nbatch;          // 1 .. MSM_MAX_SETS MSMs as ONE pass (scalar set b -> bucket set b), see launch_msm_sort
     uint64_t srs_offset; // first point of the slice inside the resident SRS
     uint64_t srs_stride; // points per window table (= total resident SRS points)
     int chunk;           // sorted entries per lane in msm_accumulate
@@ -35,8 +35,10 @@ struct MsmShape {
 
 // signed-digit recode + two-level counting sort: fills offsets[0..nbuckets] and sorted[0..entries).
 // part_ws: 16384 u32 scratch; parted: one uint2 per entry
-// With sh.nbatch == 2 the second scalar set (scalars2, same length, same points) is sorted into the second bucket set:
-// the key gets one more high bit, everything downstream just sees 2 * nbuckets buckets.
+// With sh.nbatch == S > 1 scalar sets (same length, same points) set b is sorted into bucket set b: sets 0 .. S-2 lie at
+// scalars + b * set_stride words (Montgomery form scalars_mont), set S-1 is scalars2 (scalars2_mont).  The key gets
+// ceil(log2 S) more high bits (key = set << (c-1) | digit - 1, at most 24 bits: msm_sort_max_sets), everything downstream
+// just sees S * nbuckets buckets; partitions of the key space beyond the last set are not launched.
 // part_ws_clean: the partition counts / cursors are known to be zero (a completed sort leaves them so); max_len_word: the
 // MSM's fold-depth word, reset here (launch_fold_maxlen accumulates into it).  fast: no count pass, fixed-capacity
 // partition regions (parted must hold msm_sort_parted_entries(sh, true) entries); when a region overflows,
@@ -55,7 +57,11 @@ struct SortTail {
 void launch_msm_sort(hipStream_t s, const MsmShape& sh, const uint32_t* scalars, int scalars_mont,
                      const uint32_t* scalars2, int scalars2_mont, uint32_t* part_ws, bool part_ws_clean, uint2* parted,
                      uint32_t* offsets, uint32_t* sorted, uint32_t* max_len_word, bool fast, uint32_t* overflow_word,
-                     const SortTail* tail = nullptr);
+                     const SortTail* tail = nullptr, uint64_t set_stride = 0);
+// scalar sets per MSM (one sort, one bucket tree with nbatch roots); KZG_MAX_BATCH_OPEN rows + the batched opening's quotient
+#define MSM_MAX_SETS 17
+// how many scalar sets one pass of window c can carry: the sort's key (set bits + c - 1 digit bits) has at most 24 bits
+int msm_sort_max_sets(int c);
 bool msm_sort_fast_ok(const MsmShape& sh);
 uint64_t msm_sort_parted_entries(const MsmShape& sh, bool fast);
 // bytes (multiple of 4) from device memory to a device-visible host pointer, by a kernel

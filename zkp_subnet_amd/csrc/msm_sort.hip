@@ -26,10 +26,36 @@ KZG_DEV uint32_t signed_digit(const uint32_t* s, int w, const WinLayout& lay, ui
 #define SORT_MAXPART 4096
 struct SortShape {
     uint64_t n, total, srs_offset, srs_stride;  // n scalars per set, total = n * sets
-    const uint32_t* scalars2;                   // second scalar set (batch of two MSMs over the same points) or null
+    const uint32_t* scalars2;                   // the LAST scalar set of a batch of nsets > 1 MSMs over the same points
+    uint64_t stride;                            // words between sets 0 .. nsets-2 (they follow the kernels' `scalars`)
+    int nsets;
     int mont, mont2, keybits, hbits, lbits;     // key = set << keybits | digit magnitude - 1 = (part << lbits) | low
     uint32_t spb;                               // scalars per workgroup in the two level-1 kernels
 };
+// scalar g of the sort's input (nsets sets of n scalars each): its set, its index j inside the set, where the set lies and
+// whether it is in Montgomery form.  MULTI (nsets > 2, the batched opening) is a template argument so that the one- and
+// two-set kernels compile to what they were: the set search costs registers the hot sort kernels have no room for.
+template <bool MULTI>
+KZG_DEV const uint32_t* scalar_set(const uint32_t* scalars, const SortShape& ss, uint64_t g, uint64_t& j, uint32_t& set,
+                                   int& mont) {
+    if constexpr (!MULTI) {
+        const bool second = g >= ss.n;
+        j = second ? g - ss.n : g;
+        set = second ? 1u : 0u;
+        mont = second ? ss.mont2 : ss.mont;
+        return second ? ss.scalars2 : scalars;
+    } else {
+        set = 0;
+        j = g;
+        while (j >= ss.n && set + 1u < (uint32_t)ss.nsets) {   // <= 16 steps, no 64-bit division
+            j -= ss.n;
+            set++;
+        }
+        const bool last = set && set == (uint32_t)ss.nsets - 1u;
+        mont = last ? ss.mont2 : ss.mont;
+        return last ? ss.scalars2 : scalars + (uint64_t)set * ss.stride;
+    }
+}
 // h[key]++ in LDS, returning the old value.  When every active lane of the wave holds the same key (all scalars
 // equal, constant or sparse polynomials ...) one lane adds the whole count: same-address LDS atomics serialise.
 KZG_DEV uint32_t lds_bump(uint32_t* h, uint32_t key) {
@@ -67,17 +93,19 @@ KZG_DEV uint32_t block_scan_1024(uint32_t v, uint32_t* wtot, uint32_t& total) {
     __syncthreads();   // wtot may be reused by the next scan
     return base + inc;
 }
-template <class F>
+template <bool MULTI, class F>
 KZG_DEV void for_each_entry(const uint32_t* __restrict__ scalars, const SortShape& ss, const WinLayout& lay, F&& f) {
     const uint64_t base = (uint64_t)blockIdx.x * ss.spb;
     for (uint32_t r = 0; r < ss.spb / 256; r++) {
         const uint64_t g = base + r * 256 + threadIdx.x;
         if (g >= ss.total) break;
-        const bool second = g >= ss.n;
-        const uint64_t j = second ? g - ss.n : g;
+        uint64_t j;
+        uint32_t set;
+        int mont;
+        const uint32_t* src = scalar_set<MULTI>(scalars, ss, g, j, set, mont);
         uint32_t s[8];
-        load_scalar(s, second ? ss.scalars2 : scalars, j, second ? ss.mont2 : ss.mont);
-        const uint32_t set_bit = second ? 1u << ss.keybits : 0u;
+        load_scalar(s, src, j, mont);
+        const uint32_t set_bit = set << ss.keybits;
         uint32_t carry = 0, neg;
         for (int w = 0; w < lay.nwin; w++) {
             const uint32_t mag = signed_digit(s, w, lay, carry, neg);
@@ -87,7 +115,7 @@ KZG_DEV void for_each_entry(const uint32_t* __restrict__ scalars, const SortShap
 }
 // partition sizes: 1024 lanes x R scalars each.  R = 4 for long inputs (all four loads in flight before the first digit is
 // extracted); R = 1 for short ones, where 4 scalars x nwin LDS atomics per lane on a handful of workgroups is a ~50 us chain
-template <int R>
+template <int R, bool MULTI>
 __global__ void __launch_bounds__(1024) k_sort_count(const uint32_t* __restrict__ scalars, const SortShape ss,
                                                       const WinLayout lay, uint32_t* __restrict__ part_count) {
     __shared__ uint32_t h[SORT_MAXPART];
@@ -95,19 +123,21 @@ __global__ void __launch_bounds__(1024) k_sort_count(const uint32_t* __restrict_
     for (uint32_t i = threadIdx.x; i < npart; i += 1024) h[i] = 0;
     __syncthreads();
     uint32_t sc[R][8];
-    bool live[R], second[R];
+    bool live[R];
+    uint32_t set[R];
 #pragma unroll
     for (int r = 0; r < R; r++) {
         const uint64_t g = (uint64_t)blockIdx.x * (1024 * R) + r * 1024 + threadIdx.x;
         live[r] = g < ss.total;
-        second[r] = live[r] && g >= ss.n;
-        const uint64_t j = second[r] ? g - ss.n : g;
-        if (live[r]) load_scalar(sc[r], second[r] ? ss.scalars2 : scalars, j, second[r] ? ss.mont2 : ss.mont);
+        uint64_t j;
+        int mont;
+        const uint32_t* src = scalar_set<MULTI>(scalars, ss, g, j, set[r], mont);
+        if (live[r]) load_scalar(sc[r], src, j, mont);
     }
 #pragma unroll
     for (int r = 0; r < R; r++) {
         if (!live[r]) continue;
-        const uint32_t set_bit = second[r] ? 1u << ss.keybits : 0u;
+        const uint32_t set_bit = set[r] << ss.keybits;
         uint32_t carry = 0, neg;
         for (int w = 0; w < lay.nwin; w++) {
             const uint32_t mag = signed_digit(sc[r], w, lay, carry, neg);
@@ -147,6 +177,7 @@ __global__ void __launch_bounds__(1024) k_sort_part_scan(uint32_t* __restrict__ 
         if (overflow_word_or_null) *overflow_word_or_null = 0;
     }
 }
+template <bool MULTI>
 __global__ void __launch_bounds__(256) k_sort_partition(const uint32_t* __restrict__ scalars, const SortShape ss,
                                                          const WinLayout lay, const uint32_t* __restrict__ part_base,
                                                          uint32_t* __restrict__ part_cursor, uint2* __restrict__ parted) {
@@ -155,7 +186,7 @@ __global__ void __launch_bounds__(256) k_sort_partition(const uint32_t* __restri
     const uint32_t npart = 1u << ss.hbits;
     for (uint32_t i = threadIdx.x; i < npart; i += 256) h[i] = 0;
     __syncthreads();
-    for_each_entry(scalars, ss, lay, [&](uint32_t key, uint32_t) { lds_bump(h, key >> ss.lbits); });
+    for_each_entry<MULTI>(scalars, ss, lay, [&](uint32_t key, uint32_t) { lds_bump(h, key >> ss.lbits); });
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < npart; i += 256) {
         base[i] = h[i] ? part_base[i] + atomicAdd(&part_cursor[i], h[i]) : 0u;
@@ -163,7 +194,7 @@ __global__ void __launch_bounds__(256) k_sort_partition(const uint32_t* __restri
     }
     __syncthreads();
     const uint32_t lmask = (1u << ss.lbits) - 1u;
-    for_each_entry(scalars, ss, lay, [&](uint32_t key, uint32_t val) {
+    for_each_entry<MULTI>(scalars, ss, lay, [&](uint32_t key, uint32_t val) {
         const uint32_t q = key >> ss.lbits;
         const uint32_t pos = base[q] + lds_bump(h, q);
         parted[pos] = make_uint2(key & lmask, val);
@@ -177,6 +208,7 @@ __global__ void __launch_bounds__(256) k_sort_partition(const uint32_t* __restri
 // region_cap != 0 (FAST mode, no count pass): partition q owns the fixed region [q * region_cap, (q + 1) * region_cap) of
 // `parted`; a workgroup whose run would not fit raises *overflow and drops that partition's entries -- the host then
 // reruns the sort in exact mode (count pass + exact bases), see msm_core.  region_cap == 0: exact bases from part_base.
+template <bool MULTI>
 __global__ void __launch_bounds__(1024) k_sort_partition_staged(const uint32_t* __restrict__ scalars, const SortShape ss,
                                                                  const WinLayout lay, uint32_t spb,
                                                                  const uint32_t* __restrict__ part_base,
@@ -197,14 +229,16 @@ __global__ void __launch_bounds__(1024) k_sort_partition_staged(const uint32_t* 
     uint32_t keyn[SORT1_MAXW], rk[SORT1_MAXW];
     const uint64_t g = (uint64_t)blockIdx.x * spb + t;
     const bool live = t < spb && g < ss.total;
-    const bool second = live && g >= ss.n;
-    const uint64_t j = second ? g - ss.n : g;
+    uint64_t j;
+    uint32_t set;
+    int mont;
+    const uint32_t* src = scalar_set<MULTI>(scalars, ss, g, j, set, mont);
 #pragma unroll
     for (int w = 0; w < SORT1_MAXW; w++) keyn[w] = 0xffffffffu;
     if (live) {
         uint32_t sc[8];
-        load_scalar(sc, second ? ss.scalars2 : scalars, j, second ? ss.mont2 : ss.mont);
-        const uint32_t set_bit = second ? 1u << ss.keybits : 0u;
+        load_scalar(sc, src, j, mont);
+        const uint32_t set_bit = set << ss.keybits;
         uint32_t carry = 0, neg;
 #pragma unroll
         for (int w = 0; w < SORT1_MAXW; w++) {
@@ -269,7 +303,7 @@ __global__ void __launch_bounds__(1024) k_sort_partition_staged(const uint32_t* 
 // for the whole workgroup, so its runs are R times longer (at 2^22 points and 4096 partitions a round leaves 3.25 entries
 // = 26 bytes per partition, and 32-byte sectors written for 26 bytes cost twice the bytes) and the global atomics R times
 // fewer; the R x spb x nwin entries pass through the same stage in R slices of the partition-ordered sequence.
-template <int R, int MAXW>
+template <int R, int MAXW, bool MULTI>
 __global__ void __launch_bounds__(1024) k_sort_partition_staged_multi(const uint32_t* __restrict__ scalars, const SortShape ss,
                                                                  const WinLayout lay, uint32_t spb,
                                                                  const uint32_t* __restrict__ part_base,
@@ -301,19 +335,22 @@ __global__ void __launch_bounds__(1024) k_sort_partition_staged_multi(const uint
 #pragma unroll
     for (int r0 = 0; r0 < R; r0 += PAIR) {
         uint32_t sc[PAIR][8];
-        bool live[PAIR], second[PAIR];
+        bool live[PAIR];
+        uint32_t set[PAIR];
 #pragma unroll
         for (int u = 0; u < PAIR; u++) {
             const uint64_t g = ((uint64_t)blockIdx.x * R + (r0 + u)) * spb + t;
             live[u] = t < spb && g < ss.total;
-            second[u] = live[u] && g >= ss.n;
-            if (live[u]) load_scalar(sc[u], second[u] ? ss.scalars2 : scalars, second[u] ? g - ss.n : g, second[u] ? ss.mont2 : ss.mont);
+            uint64_t j;
+            int mont;
+            const uint32_t* src = scalar_set<MULTI>(scalars, ss, g, j, set[u], mont);
+            if (live[u]) load_scalar(sc[u], src, j, mont);
         }
 #pragma unroll
         for (int u = 0; u < PAIR; u++) {
             if (live[u]) {
                 const int r = r0 + u;
-                const uint32_t set_bit = second[u] ? 1u << ss.keybits : 0u;
+                const uint32_t set_bit = set[u] << ss.keybits;
                 uint32_t carry = 0, neg;
 #pragma unroll
                 for (int w = 0; w < MAXW; w++) {
@@ -359,7 +396,10 @@ __global__ void __launch_bounds__(1024) k_sort_partition_staged_multi(const uint
 #pragma unroll
         for (int r = 0; r < R; r++) {   // (a scalar that is not live has no digits)
             const uint64_t g = ((uint64_t)blockIdx.x * R + r) * spb + t;
-            const uint64_t j = g >= ss.n ? g - ss.n : g;
+            uint64_t j;
+            uint32_t set_r;
+            int mont_r;
+            (void)scalar_set<MULTI>(scalars, ss, g, j, set_r, mont_r);
 #pragma unroll
             for (int w = 0; w < MAXW; w++) {
                 if (keyn[r][w] != 0xffffffffu) {
@@ -601,11 +641,22 @@ bool msm_sort_fast_ok(const MsmShape& sh) {
     const uint64_t entries = (uint64_t)sh.n * sh.nbatch * sh.nwin;
     return sh.nwin <= SORT1_MAXW && entries * 9 / 4 + ((uint64_t)SORT_MAXPART << 11) < ((uint64_t)1 << 32);
 }
-static void sort_shape(const MsmShape& sh, const uint32_t* scalars2, int scalars_mont, int scalars2_mont, SortShape& ss) {
-    const int setbits = sh.nbatch > 1 ? 1 : 0;
+static int set_bits(int nsets) {
+    int b = 0;
+    while ((1 << b) < nsets) b++;
+    return b;
+}
+int msm_sort_max_sets(int c) {
+    const int room = 24 - (c - 1);   // key bits left for the set index
+    return room >= 5 ? MSM_MAX_SETS : 1 << room;
+}
+static void sort_shape(const MsmShape& sh, const uint32_t* scalars2, int scalars_mont, int scalars2_mont, SortShape& ss,
+                       uint64_t set_stride = 0) {
+    const int setbits = set_bits(sh.nbatch);
     const int keybits = sh.c - 1 + setbits;
-    ss.n = sh.n; ss.total = sh.n << setbits; ss.srs_offset = sh.srs_offset; ss.srs_stride = sh.srs_stride;
+    ss.n = sh.n; ss.total = sh.n * (uint64_t)sh.nbatch; ss.srs_offset = sh.srs_offset; ss.srs_stride = sh.srs_stride;
     ss.mont = scalars_mont; ss.scalars2 = scalars2; ss.mont2 = scalars2_mont; ss.keybits = sh.c - 1;
+    ss.stride = set_stride; ss.nsets = sh.nbatch;
     // 1024 partitions (level 2 runs one workgroup per partition), up to 4096 when that brings a partition down to what
     // level 2 can stage in LDS (SORT_STAGE entries; ~13 k on average at 2^20 / 1024, ~27 k at 2^22 / 2048 and 2^23 / 4096)
     const uint64_t entries = ss.total * (uint64_t)sh.nwin;
@@ -617,16 +668,20 @@ static void sort_shape(const MsmShape& sh, const uint32_t* scalars2, int scalars
     while (hbits < 12 && (entries >> hbits) > 24576) hbits++;
     if (hbits > keybits) hbits = keybits;
     if (keybits - hbits > 12) hbits = keybits - 12;  // level 2 histograms at most 4096 buckets
+    // no partition straddles two sets (lbits <= c - 1): the partitions past the last set are then never launched
+    if (hbits < setbits) hbits = setbits;
     ss.hbits = hbits;
     ss.lbits = keybits - hbits;
     ss.spb = ss.total >= (1u << 21) ? 4096u : 1024u;
 }
+// the partitions that hold keys: nbatch sets of 2^(c-1) buckets (all 2^hbits of them unless nbatch is not a power of two)
+static uint32_t sort_npart_used(const SortShape& ss) { return (uint32_t)ss.nsets << (ss.hbits - set_bits(ss.nsets)); }
 uint64_t msm_sort_parted_entries(const MsmShape& sh, bool fast) {  // capacity of `parted`, in entries
     const uint64_t entries = (uint64_t)sh.n * sh.nbatch * sh.nwin;
     if (!fast) return entries;
     SortShape ss;
     sort_shape(sh, nullptr, 0, 0, ss);
-    return msm_sort_region_cap(entries, 1u << ss.hbits) << ss.hbits;
+    return msm_sort_region_cap(entries, sort_npart_used(ss)) * sort_npart_used(ss);
 }
 // rounds per workgroup of the staged level-1 partition (A/B knob KZG_SORT_ROUNDS = 1 | 2): two from 2^20 scalars up
 // (sort 0.146 -> 0.138 ms at 2^20, 0.72 -> 0.58 at 2^22, 2.89 -> 2.25 at 2^24; four rounds spill their digits and lose:
@@ -644,11 +699,20 @@ static void launch_partition_staged(hipStream_t s, const uint32_t* scalars, cons
                                     uint32_t spb2, const uint32_t* part_base, uint32_t* part_cursor, uint2* parted,
                                     uint32_t cap, uint32_t* overflow_word) {
     const int rounds = sort_rounds(ss.total, lay.nwin);
+    if (ss.nsets > 2) {
+        if (rounds == 2)
+            k_sort_partition_staged_multi<2, 16, true><<<nblk(ss.total, 2 * spb2), 1024, 0, s>>>(
+                scalars, ss, lay, spb2, part_base, part_cursor, parted, cap, overflow_word);
+        else
+            k_sort_partition_staged<true><<<nblk(ss.total, spb2), 1024, 0, s>>>(scalars, ss, lay, spb2, part_base, part_cursor,
+                                                                               parted, cap, overflow_word);
+        return;
+    }
     if (rounds == 2)
-        k_sort_partition_staged_multi<2, 16><<<nblk(ss.total, 2 * spb2), 1024, 0, s>>>(scalars, ss, lay, spb2, part_base,
+        k_sort_partition_staged_multi<2, 16, false><<<nblk(ss.total, 2 * spb2), 1024, 0, s>>>(scalars, ss, lay, spb2, part_base,
                                                                                         part_cursor, parted, cap, overflow_word);
     else
-        k_sort_partition_staged<<<nblk(ss.total, spb2), 1024, 0, s>>>(scalars, ss, lay, spb2, part_base, part_cursor,
+        k_sort_partition_staged<false><<<nblk(ss.total, spb2), 1024, 0, s>>>(scalars, ss, lay, spb2, part_base, part_cursor,
                                                                      parted, cap, overflow_word);
 }
 // FAST mode (uniform-ish scalars: the common case): no count pass -- partition straight into fixed-capacity regions, scan
@@ -658,14 +722,20 @@ static void launch_partition_staged(hipStream_t s, const uint32_t* scalars, cons
 void launch_msm_sort(hipStream_t s, const MsmShape& sh, const uint32_t* scalars, int scalars_mont,
                      const uint32_t* scalars2, int scalars2_mont, uint32_t* part_ws, bool part_ws_clean, uint2* parted,
                      uint32_t* offsets, uint32_t* sorted, uint32_t* max_len_word, bool fast, uint32_t* overflow_word,
-                     const SortTail* tail) {
+                     const SortTail* tail, uint64_t set_stride) {
     SortTail tl{0u, nullptr, nullptr, nullptr, 0u};
     if (tail) tl = *tail;
     uint32_t* done = part_ws + 3 * SORT_MAXPART + 16;   // k_sort_buckets' ticket counter (zero between sorts)
+    if (!scalars2 && sh.nbatch > 1) {   // every set at the stride: the last one too
+        scalars2 = scalars + (uint64_t)(sh.nbatch - 1) * set_stride;
+        scalars2_mont = scalars_mont;
+    }
     SortShape ss;
-    sort_shape(sh, scalars2, scalars_mont, scalars2_mont, ss);
+    sort_shape(sh, scalars2, scalars_mont, scalars2_mont, ss, set_stride);
     const uint64_t entries = ss.total * (uint64_t)sh.nwin;
     const uint32_t npart = 1u << ss.hbits;
+    // level 2 runs over the partitions that hold keys only: the bucket arrays downstream hold exactly nbatch * 2^(c-1) buckets
+    const uint32_t npart2 = sort_npart_used(ss);
     uint32_t* part_count = part_ws;                      // [npart]
     uint32_t* part_base = part_ws + SORT_MAXPART;        // [npart + 1]
     uint32_t* part_cursor = part_ws + 2 * SORT_MAXPART + 8;
@@ -673,21 +743,29 @@ void launch_msm_sort(hipStream_t s, const MsmShape& sh, const uint32_t* scalars,
     uint32_t spb2 = (SORT1_STAGE / (uint32_t)sh.nwin) & ~63u;  // staged partition: one scalar per lane, <= SORT1_STAGE entries
     if (spb2 > 1024) spb2 = 1024;
     if (fast) {
-        const uint32_t cap = (uint32_t)msm_sort_region_cap(entries, npart);
+        const uint32_t cap = (uint32_t)msm_sort_region_cap(entries, npart2);
         launch_partition_staged(s, scalars, ss, sh.lay, spb2, part_base, part_cursor, parted, cap, overflow_word);
         k_sort_part_scan<<<1, 1024, 0, s>>>(part_cursor, npart, cap, part_base, max_len_word, nullptr);
-        k_sort_buckets<<<npart, 1024, 0, s>>>(parted, part_base, ss.lbits, offsets, sorted, npart, cap, overflow_word,
-                                              part_cursor, tl, max_len_word, done);
+        k_sort_buckets<<<npart2, 1024, 0, s>>>(parted, part_base, ss.lbits, offsets, sorted, npart2, cap, overflow_word,
+                                               part_cursor, tl, max_len_word, done);
         return;
     }
     const uint32_t blocks = nblk(ss.total, ss.spb);
-    if (ss.total > (1u << 18)) k_sort_count<4><<<nblk(ss.total, 4096), 1024, 0, s>>>(scalars, ss, sh.lay, part_count);
-    else k_sort_count<1><<<nblk(ss.total, 1024), 1024, 0, s>>>(scalars, ss, sh.lay, part_count);
+    const bool multi = ss.nsets > 2;
+    if (ss.total > (1u << 18)) {
+        if (multi) k_sort_count<4, true><<<nblk(ss.total, 4096), 1024, 0, s>>>(scalars, ss, sh.lay, part_count);
+        else k_sort_count<4, false><<<nblk(ss.total, 4096), 1024, 0, s>>>(scalars, ss, sh.lay, part_count);
+    } else {
+        if (multi) k_sort_count<1, true><<<nblk(ss.total, 1024), 1024, 0, s>>>(scalars, ss, sh.lay, part_count);
+        else k_sort_count<1, false><<<nblk(ss.total, 1024), 1024, 0, s>>>(scalars, ss, sh.lay, part_count);
+    }
     k_sort_part_scan<<<1, 1024, 0, s>>>(part_count, npart, 0xffffffffu, part_base, max_len_word, overflow_word);
     if (sh.nwin <= SORT1_MAXW)
         launch_partition_staged(s, scalars, ss, sh.lay, spb2, part_base, part_cursor, parted, 0u, overflow_word);
+    else if (multi)
+        k_sort_partition<true><<<blocks, 256, 0, s>>>(scalars, ss, sh.lay, part_base, part_cursor, parted);
     else
-        k_sort_partition<<<blocks, 256, 0, s>>>(scalars, ss, sh.lay, part_base, part_cursor, parted);
-    k_sort_buckets<<<npart, 1024, 0, s>>>(parted, part_base, ss.lbits, offsets, sorted, npart, 0u, overflow_word, part_cursor,
-                                          tl, max_len_word, done);
+        k_sort_partition<false><<<blocks, 256, 0, s>>>(scalars, ss, sh.lay, part_base, part_cursor, parted);
+    k_sort_buckets<<<npart2, 1024, 0, s>>>(parted, part_base, ss.lbits, offsets, sorted, npart2, 0u, overflow_word, part_cursor,
+                                           tl, max_len_word, done);
 }

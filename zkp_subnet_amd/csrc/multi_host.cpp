@@ -362,6 +362,15 @@ int kzg_multi_commit_open(kzg_multi* m, uint32_t i, const uint8_t* row_be32, uin
     if (int rc = route(m, i, &c, &s)) return rc;
     return relay(c, kzg_commit_open(c, s, row_be32, T, evaluation_form, alpha_be32, out48, out_eval32, out_proof48));
 }
+int kzg_multi_commit_open_batch(kzg_multi* m, uint32_t i, uint32_t k, const uint8_t* rows_be32, uint64_t T, int evaluation_form,
+                                const uint8_t alpha_be32[32], const uint8_t gamma_be32[32], uint8_t* out_commitments48,
+                                uint8_t* out_evals32, uint8_t out_proof48[48]) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(m, i, &c, &s)) return rc;
+    return relay(c, kzg_commit_open_batch(c, s, k, rows_be32, T, evaluation_form, alpha_be32, gamma_be32, out_commitments48,
+                                          out_evals32, out_proof48));
+}
 
 int kzg_multi_create(int device_count, const int* device_ids, kzg_multi** out) {
     return guarded("kzg_multi_create", [&] { return create_impl(device_count, device_ids, out); });

@@ -606,6 +606,74 @@ int kzg_vk_verify_batch(const kzg_vk* vk, uint32_t n, const uint32_t* idx, const
     }
 }
 
+/* sum_j gamma^j x_j mod r (Horner), x_j canonical: the host verifier's only Fr arithmetic -- a 256-step double-and-add
+ * multiplication is plenty for k <= 16 values */
+static void fr_add_mod(u64 a[4], const u64 b[4]) {   // a = a + b mod r, a and b < r
+    u64 s[4], d[4];
+    u128 c = 0;
+    for (int w = 0; w < 4; w++) {
+        c += (u128)a[w] + b[w];
+        s[w] = (u64)c;
+        c >>= 64;
+    }
+    u128 br = 0;
+    for (int w = 0; w < 4; w++) {
+        const u128 t = (u128)s[w] - R_ORDER[w] - (u64)br;
+        d[w] = (u64)t;
+        br = (t >> 64) & 1;
+    }
+    const bool ge = c || !br;   // s >= r (a carry out of 256 bits means s > r too)
+    for (int w = 0; w < 4; w++) a[w] = ge ? d[w] : s[w];
+}
+static void fr_mul_mod(u64 out[4], const u64 a[4], const u64 b[4]) {
+    u64 acc[4] = {0, 0, 0, 0};
+    for (int bit = 255; bit >= 0; bit--) {
+        u64 dbl[4] = {acc[0], acc[1], acc[2], acc[3]};
+        fr_add_mod(acc, dbl);
+        if ((b[bit / 64] >> (bit % 64)) & 1) fr_add_mod(acc, a);
+    }
+    memcpy(out, acc, sizeof(acc));
+}
+/* e(sum gamma^j C_j - (sum gamma^j y_j) L_i, G2) == e(pi, tau G2 - alpha G2).  The two sums by Horner from the last row:
+ * k - 1 scalar multiplications by gamma in G1 and in Fr. */
+int kzg_vk_verify_open_batch(const kzg_vk* vk, uint32_t i, uint32_t k, const uint8_t* commitments48,
+                             const uint8_t* evals_be32, const uint8_t alpha_be32[32], const uint8_t gamma_be32[32],
+                             const uint8_t proof48[48], int* out_valid) {
+    if (!vk || !commitments48 || !evals_be32 || !alpha_be32 || !gamma_be32 || !proof48 || !out_valid) return KZG_E_ARG;
+    *out_valid = 0;
+    if (k == 0 || k > KZG_MAX_BATCH_OPEN || i >= vk->k.li.size()) return KZG_E_ARG;
+    u64 alpha[4], gamma[4];
+    if (!fr_from_be32(alpha, alpha_be32) || !fr_from_be32(gamma, gamma_be32)) return KZG_E_SCALAR;
+    std::vector<u64> y(4 * (size_t)k);
+    for (uint32_t j = 0; j < k; j++)
+        if (!fr_from_be32(&y[4 * (size_t)j], evals_be32 + 32 * (size_t)j)) return KZG_E_SCALAR;
+    try {
+        std::vector<G1A> c(k);
+        G1A pi;
+        // malformed or off-curve / out-of-subgroup group elements are an invalid proof, not a call failure
+        if (!g1_decompress(pi, proof48) || !g1_in_subgroup_fast(pi)) return KZG_OK;
+        for (uint32_t j = 0; j < k; j++)
+            if (!g1_decompress(c[j], commitments48 + 48 * (size_t)j) || !g1_in_subgroup_fast(c[j])) return KZG_OK;
+        Jac<Fp> cs = to_jac(c[k - 1]);
+        u64 ys[4];
+        memcpy(ys, &y[4 * (size_t)(k - 1)], sizeof(ys));
+        for (uint32_t j = k - 1; j-- > 0;) {
+            cs = jac_add(jac_mul(to_aff(cs), gamma, 4), to_jac(c[j]));
+            fr_mul_mod(ys, ys, gamma);
+            fr_add_mod(ys, &y[4 * (size_t)j]);
+        }
+        const Jac<Fp> yl = jac_mul(vk->k.li[i], ys, 4);
+        const G1A lhs = to_aff(jac_add(cs, to_jac(aff_neg(to_aff(yl)))));
+        const Jac<Fp2> ag = jac_mul(vk->k.g2, alpha, 4);
+        const G2A rhs_q = to_aff(jac_add(to_jac(vk->k.tau_g2), to_jac(aff_neg(to_aff(ag)))));
+        const Fp12 f = miller_loop(lhs, aff_neg(vk->k.g2)) * miller_loop(pi, rhs_q);
+        *out_valid = is_one(final_exp_fast(f)) ? 1 : 0;
+        return KZG_OK;
+    } catch (...) {
+        return KZG_E_NOMEM;
+    }
+}
+
 /* test hook: out = final_exp(miller(P, Q)) as 12 x 48 bytes in tower order
  * (c0.c0.c0, c0.c0.c1, c0.c1.c0, ..., c1.c2.c1); P affine be96, Q uncompressed be192 */
 int kzg_vk_pairing(const uint8_t p_be96[96], const uint8_t q_be192[192], uint8_t out_fp12[576]) {

@@ -32,6 +32,8 @@ int pick_chunk(uint64_t entries) {
 // With scalars2 != null: TWO MSMs over the same n points in one pass (the commitment and the opening of one row):
 // set b is sorted into bucket set b, the sort / accumulate / fold / tree kernels simply see twice the buckets, the
 // tree stops at two roots and out_xyzz[0..1] receive the two sums.  One kernel sequence, one latency-bound tail.
+// nrows > 1 (the batched opening): sets 0 .. nrows-1 lie at scalars + b * row_stride words, scalars2 (if given) is set
+// nrows; nrows + 1 <= msm_sort_max_sets(c) sets, nrows + 1 roots at out_xyzz[0 ..].
 // The only host wait inside is on the 4-byte fold-depth read-back; the calling thread holds no lock meanwhile.
 // The bucket tree on stream s: merges level arrays until `stop` nodes are left.  Three buffers in rotation (a level reads its
 // own array and the P array of the level below, writes the next) plus a fourth for the two-level launches.  On return b.in is
@@ -63,9 +65,11 @@ static void run_tree(hipStream_t s, TreeBufs& b, uint32_t n_in, uint32_t stop) {
     }
 }
 int msm_core(kzg_ctx* ctx, Lane& L, const uint32_t* scalars, int mont, uint64_t n, uint64_t srs_offset,
-             g1_xyzz_t* out_xyzz, const uint32_t* scalars2, int mont2) {
+             g1_xyzz_t* out_xyzz, const uint32_t* scalars2, int mont2, int nrows, uint64_t row_stride) {
     hipStream_t s = L.stream;
-    const int nbatch = scalars2 ? 2 : 1;
+    const int nbatch = nrows + (scalars2 ? 1 : 0);
+    if (nrows < 1 || nbatch > std::min(MSM_MAX_SETS, msm_sort_max_sets(ctx->c)))
+        return fail(ctx, KZG_E_ARG, "MSM pass with more scalar sets than the sort's key can carry");
     if (n == 0) {
         HIPCHK(ctx, hipMemsetAsync(out_xyzz, 0, nbatch * sizeof(g1_xyzz_t), s));
         return KZG_OK;
@@ -99,12 +103,19 @@ int msm_core(kzg_ctx* ctx, Lane& L, const uint32_t* scalars, int mont, uint64_t 
     HIPCHK(ctx, L.carry_key.ensure((size_t)nchunks * 4));
     uint32_t* max_len_d = L.flags() + 2;
     uint32_t* max_len_h = reinterpret_cast<uint32_t*>(L.pin + PIN_MAXLEN);
+    if (nbatch > 2) {   // the final's scratch (nbatch x 32 doubled components) outgrows the 16 KB above on narrow windows
+        const size_t fin = (size_t)nbatch * 32 * sizeof(g1_xyzz_t);
+        HIPCHK(ctx, L.bufA.ensure(B * sizeof(g1_xyzz_t) + fin));
+        HIPCHK(ctx, L.bufB.ensure(B * sizeof(g1_xyzz_t) / 2 + fin));
+        HIPCHK(ctx, L.bufC.ensure(B * sizeof(g1_xyzz_t) / 2 + fin));
+        HIPCHK(ctx, L.bufD.ensure((size_t)(LP_MAX_OPS + 64) * sizeof(g1_xyzz_t) + fin));
+    }
     auto sort_and_publish = [&](bool fast_mode, bool ws_clean) {
         const SortTail tail{(uint32_t)sh.chunk, L.bufA.as<g1_xyzz_t>(), reinterpret_cast<uint32_t*>(L.pin_dev + PIN_MAXLEN),
                             reinterpret_cast<uint32_t*>(L.pin_dev + PIN_SEQ_SORT), ++L.sort_seq};
         launch_msm_sort(s, sh, scalars, mont, scalars2, mont2, L.hist.as<uint32_t>(), ws_clean, L.rank.as<uint2>(),
                         L.offsets.as<uint32_t>(), L.sorted.as<uint32_t>(), max_len_d, fast_mode, max_len_d + 1,
-                        &tail);
+                        &tail, row_stride);
     };
     {
         Span sp(ctx, L, KZG_T_DIGITS);
@@ -357,6 +368,112 @@ int commit_open_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* row_d
         if (out_p48) result_c48(ctx, A, 1, out_p48);
     }
     if (out_p48) memcpy(out_eval32, A.pin + TB_EVAL, 32);
+    H.clean = true;
+    return KZG_OK;
+}
+
+
+// ---- the batched opening (kzg_commit_open_batch): k rows f_j of worker i, one point alpha, one challenge gamma.
+//   INTT of each row -> the k evaluations y_j = f_j(alpha) side by side (launch_poly_eval_rows: the launches of ONE
+//   evaluation) -> h = sum_j gamma^j f_j (launch_fr_combine_rows) -> the opening of h (launch_poly_open: its quotient
+//   lands in the proof's scalar set) -> the k + 1 MSMs over the slice U_i.
+//  * rows up to KZG_BATCHED_ROW_MAX (latency-bound): ONE msm_core pass with k + 1 scalar sets -- one sort, one accumulate,
+//    one bucket tree with k + 1 roots -- as far as the window leaves the sort's key room (msm_sort_max_sets); beyond that
+//    as few passes as fit; bucket memory caps a pass at 2^22 buckets;
+//  * longer rows (throughput-bound: a multi-set pass there only adds buckets to a sort that is no longer latency): k + 1
+//    single MSMs alternating between this lane and a second one when one is free, as commit_open_dev spreads its two --
+//    k + 1 MSMs where k single-row calls run 2k.
+#ifndef KZG_BATCH_PASS_SETS
+#define KZG_BATCH_PASS_SETS MSM_MAX_SETS   // (A/B knob: a smaller cap splits a batch into more passes)
+#endif
+int commit_open_batch_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* rows_dev, uint32_t k, uint64_t T,
+                          int evaluation_form, const uint8_t* alpha_be32, const uint8_t* gamma_be32, uint8_t* out_c48,
+                          uint8_t* out_evals32, uint8_t* out_p48) {
+    Lane& A = H.L();
+    hipStream_t s = A.stream;
+    HIPCHK(ctx, A.brec.ensure(BR_SIZE));
+    if (!A.bpin) {
+        uint8_t* p = nullptr;
+        HIPCHK(ctx, hipHostMalloc((void**)&p, 8192, hipHostMallocMapped | hipHostMallocCoherent));
+        A.bpin = p;
+        HIPCHK(ctx, hipHostGetDevicePointer((void**)&A.bpin_dev, A.bpin, 0));
+    }
+    const uint64_t words = T * 8;   // one row, in words
+    const uint32_t* coef = rows_dev;
+    if (evaluation_form && T > 1) {
+        HIPCHK(ctx, A.bcoef.ensure(k * T * 32));
+        for (uint32_t j = 0; j < k; j++) {
+            const uint32_t* c;
+            int rc = row_to_coeffs(ctx, A, rows_dev + j * words, T, 1, &c, A.bcoef.as<uint32_t>() + j * words);
+            if (rc) return rc;
+        }
+        coef = A.bcoef.as<uint32_t>();
+    }
+    uint8_t* rec = A.brec.as<uint8_t>();
+    g1_xyzz_t* res = reinterpret_cast<g1_xyzz_t*>(rec + BR_RES);
+    uint32_t* alpha_m = reinterpret_cast<uint32_t*>(A.tail + TB_ALPHA_M);
+    uint32_t* y_m = reinterpret_cast<uint32_t*>(A.tail + TB_Y_M);
+    const uint64_t nchunks = (T + 3) / 4;
+    const uint64_t hrow = (nchunks + (nchunks >> 1) + 64) * 8;   // level scratch of one row, words
+    HIPCHK(ctx, A.hbuf.ensure(k * hrow * 4));
+    HIPCHK(ctx, A.hnext.ensure(k * hrow * 4));
+    HIPCHK(ctx, A.bcomb.ensure(T * 32));
+    HIPCHK(ctx, A.qbuf.ensure(T * 32));
+    uint32_t* hcomb = A.bcomb.as<uint32_t>();
+    uint32_t* q = A.qbuf.as<uint32_t>();
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        // alpha rides in as an argument of the evaluations' first kernel, gamma as one of the combination's
+        launch_poly_eval_rows(s, coef, T, k, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), hrow,
+                              reinterpret_cast<uint32_t*>(rec + BR_Y_M), alpha_be32, A.flags(), rec + BR_EVAL);
+        launch_fr_combine_rows(s, coef, T, k, gamma_be32, hcomb, A.flags());
+        // k_poly_quotient leaves a zero in slot T - 1: the quotient rides as one more length-T scalar set
+        launch_poly_open(s, hcomb, T, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), y_m, q);
+    }
+    const uint64_t offset = (uint64_t)i * ctx->T;
+    const bool batched = T <= KZG_BATCHED_ROW_MAX;
+    // sets per pass: what the sort's key carries (msm_sort_max_sets), at most 2^22 buckets; long rows one set per pass
+    int per = std::min(KZG_BATCH_PASS_SETS, msm_sort_max_sets(ctx->c));
+    while (per > 2 && (uint64_t)per * ctx->nbuckets > ((uint64_t)1 << 22)) per--;
+    if (!batched) per = 1;
+    const uint32_t sets = k + 1, passes = (sets + per - 1) / per;   // set k is the quotient
+    Lane* B = (!batched && passes > 1) ? H.second() : nullptr;
+    if (B) {
+        HIPCHK(ctx, hipEventRecord(A.ev_coeffs, s));
+        HIPCHK(ctx, hipStreamWaitEvent(B->stream, A.ev_coeffs, 0));
+    }
+    for (uint32_t p = 0; p < passes; p++) {
+        Lane& L = (B && (p & 1)) ? *B : A;
+        const uint32_t a = p * per, b = std::min(sets, a + per);
+        const uint32_t m = std::min(b, k) - std::min(a, k);   // rows in this pass
+        const bool with_q = b == sets;
+        int rc = m ? msm_core(ctx, L, coef + (uint64_t)a * words, 1, T, offset, res + a, with_q ? q : nullptr, 0, (int)m, words)
+                   : msm_core(ctx, L, q, 0, T, offset, res + k);
+        if (rc) return rc;
+    }
+    if (B) {
+        HIPCHK(ctx, hipEventRecord(B->ev_done, B->stream));
+        HIPCHK(ctx, hipStreamWaitEvent(s, B->ev_done, 0));
+    }
+    if (!ctx->host_finish) {
+        Span sp(ctx, A, KZG_T_FINAL);
+        for (uint32_t p = 0; p + 1 < sets; p += 2)
+            launch_g1_compress_pair(s, res + p, res + p + 1, rec + BR_C48 + 48 * p, rec + BR_C48 + 48 * (p + 1));
+        if (sets & 1) launch_g1_compress(s, res + k, rec + BR_C48 + 48 * k);
+    }
+    launch_publish(s, rec, A.bpin_dev, BR_COPY);   // stream-ordered ahead of finish()'s record and its sequence word
+    int rc = finish(ctx, A);
+    if (rc) return rc;
+    if (ctx->host_finish) {
+        uint8_t enc[MSM_MAX_SETS * 48];
+        kzg_host::xyzz_batch_to_c48(reinterpret_cast<const uint32_t*>(A.bpin + BR_RES), sets, enc);
+        memcpy(out_c48, enc, 48 * (size_t)k);
+        memcpy(out_p48, enc + 48 * (size_t)k, 48);
+    } else {
+        memcpy(out_c48, A.bpin + BR_C48, 48 * (size_t)k);
+        memcpy(out_p48, A.bpin + BR_C48 + 48 * (size_t)k, 48);
+    }
+    memcpy(out_evals32, A.bpin + BR_EVAL, 32 * (size_t)k);
     H.clean = true;
     return KZG_OK;
 }

@@ -216,6 +216,39 @@ int kzg_commit_open(kzg_ctx* ctx, uint32_t i, const uint8_t* row_be32, uint64_t 
                             out_proof48);
 }
 
+// 32 big-endian bytes < r (host check of the batched opening's alpha and gamma: an argument error, not a queued failure)
+static bool fr_be32_canonical(const uint8_t b[32]) {
+    static const uint8_t R_BE[32] = {0x73, 0xED, 0xA7, 0x53, 0x29, 0x9D, 0x7D, 0x48, 0x33, 0x39, 0xD8, 0x08, 0x09, 0xA1, 0xD8, 0x05,
+                                     0x53, 0xBD, 0xA4, 0x02, 0xFF, 0xFE, 0x5B, 0xFE, 0xFF, 0xFF, 0xFF, 0xFF, 0x00, 0x00, 0x00, 0x01};
+    return memcmp(b, R_BE, 32) < 0;
+}
+// k rows of worker i opened at one point with ONE proof for sum_j gamma^j f_j (pipeline.hip: commit_open_batch_dev)
+int kzg_commit_open_batch(kzg_ctx* ctx, uint32_t i, uint32_t k, const uint8_t* rows_be32, uint64_t T, int evaluation_form,
+                          const uint8_t alpha_be32[32], const uint8_t gamma_be32[32], uint8_t* out_commitments48,
+                          uint8_t* out_evals32, uint8_t out_proof48[48]) {
+    if (!ctx || !rows_be32 || !alpha_be32 || !gamma_be32 || !out_commitments48 || !out_evals32 || !out_proof48)
+        return KZG_E_ARG;
+    if (k == 0 || k > KZG_MAX_BATCH_OPEN) return fail(ctx, KZG_E_ARG, "batched opening: k must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (!fr_be32_canonical(alpha_be32) || !fr_be32_canonical(gamma_be32))
+        return fail(ctx, KZG_E_ARG, "batched opening: alpha and gamma must be canonical scalars (< r)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;
+    Lane& L = H.L();
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (evaluation_form && T > 1 && ilog2_exact(T) < 0)
+        return fail(ctx, KZG_E_ARG, "evaluation-form row length must be a power of two");
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    HIPCHK(ctx, L.coeffA.ensure(k * T * 32));
+    rc = upload_fr(ctx, L, rows_be32, k * T, L.coeffA.as<uint32_t>(), 1);
+    if (rc) return rc;
+    return commit_open_batch_dev(ctx, H, i, L.coeffA.as<uint32_t>(), k, T, evaluation_form, alpha_be32, gamma_be32,
+                                 out_commitments48, out_evals32, out_proof48);
+}
+
 static int ntt_dev(kzg_ctx* ctx, Lane& L, uint32_t* data, uint64_t n, int inverse) {  // in place via coeffB
     int lg = ilog2_exact(n);
     if (lg < 0) return fail(ctx, KZG_E_ARG, "NTT length must be a power of two");

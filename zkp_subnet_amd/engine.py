@@ -178,6 +178,13 @@ class HipEngine:
             raise NotImplementedError("no verifier key: call set_verifier_key() after load_srs()")
         return self.verifier.verify_batch(indices, proofs48, alpha32, evals32, commitments48, threads)
 
+    def verify_open_batch(self, i: int, commitments48: Sequence[bytes], evals32: Sequence[bytes], alpha32: bytes,
+                          gamma32: bytes, proof48: bytes) -> bool:
+        """Pairing check of one batched opening (commit_open_batch) against resident slice i."""
+        if self.verifier is None:
+            raise NotImplementedError("no verifier key: call set_verifier_key() after load_srs()")
+        return self.verifier.verify_open_batch(i, commitments48, evals32, alpha32, gamma32, proof48)
+
     def srs_read(self, first: int, count: int, window: int = 0, compressed: bool = False) -> bytes:
         out = ctypes.create_string_buffer((48 if compressed else 96) * count)
         fn = self._lib.kzg_srs_read_compressed if compressed else self._lib.kzg_srs_read
@@ -201,6 +208,34 @@ class HipEngine:
         self._chk(self._lib.kzg_commit_open(self._h, i, row_be32, len(row_be32) // 32, int(evaluation_form),
                                             alpha_be32, c, ev, pf))
         return c.raw, ev.raw, pf.raw
+
+    def commit_open_batch(self, i: int, rows_be32: Sequence[bytes], alpha_be32: bytes, gamma_be32: bytes,
+                          evaluation_form: bool = True) -> Tuple[List[bytes], List[bytes], bytes]:
+        """k rows of worker i opened at alpha with ONE proof for sum_j gamma^j f_j (kzg_commit_open_batch): returns
+        ([C_j], [y_j], pi).  gamma must come from the verifier after the commitments are fixed (the library derives none)."""
+        k = len(rows_be32)
+        if k == 0 or k > _native.KZG_MAX_BATCH_OPEN:
+            raise KzgError(_native.KZG_E_ARG, f"commit_open_batch: k = {k} outside [1, {_native.KZG_MAX_BATCH_OPEN}]")
+        if len({len(r) for r in rows_be32}) != 1 or len(rows_be32[0]) % 32:
+            raise KzgError(_native.KZG_E_ARG, "commit_open_batch: rows of unequal length")
+        T = len(rows_be32[0]) // 32
+        return self._commit_open_batch(i, k, b"".join(rows_be32), T, alpha_be32, gamma_be32, evaluation_form)
+
+    def commit_open_batch_joined(self, i: int, rows_be32: bytes, k: int, alpha_be32: bytes, gamma_be32: bytes,
+                                 evaluation_form: bool = True) -> Tuple[List[bytes], List[bytes], bytes]:
+        """commit_open_batch on rows already in the C-ABI layout (k rows of T elements, row-major, one buffer): no join,
+        which at 2^20 x 16 rows costs more host time than the GPU work it feeds."""
+        if k <= 0 or k > _native.KZG_MAX_BATCH_OPEN or len(rows_be32) % (32 * k):
+            raise KzgError(_native.KZG_E_ARG, f"commit_open_batch: {len(rows_be32)} bytes are not {k} equal rows")
+        return self._commit_open_batch(i, k, rows_be32, len(rows_be32) // (32 * k), alpha_be32, gamma_be32, evaluation_form)
+
+    def _commit_open_batch(self, i, k, rows, T, alpha_be32, gamma_be32, evaluation_form):
+        if len(alpha_be32) != 32 or len(gamma_be32) != 32:   # the C side reads exactly 32 bytes of each
+            raise KzgError(_native.KZG_E_ARG, "commit_open_batch: alpha / gamma must be 32 bytes")
+        c, ev, pf = ctypes.create_string_buffer(48 * k), ctypes.create_string_buffer(32 * k), ctypes.create_string_buffer(48)
+        self._chk(self._lib.kzg_commit_open_batch(self._h, i, k, rows, T, int(evaluation_form), alpha_be32, gamma_be32,
+                                                  c, ev, pf))
+        return ([c.raw[48 * j:48 * j + 48] for j in range(k)], [ev.raw[32 * j:32 * j + 32] for j in range(k)], pf.raw)
 
     # ---- the same three calls fed from the synapse's List[str] (reference neurons/miner.py:38-61): the text is decoded
     # by csrc/wire_py.c straight into the library's pinned staging buffer (no bytes object, no pageable bounce)
@@ -271,6 +306,35 @@ class HipEngine:
         with HipEngine._Staged(self, poly) as st:
             self._chk(self._lib.kzg_commit_open(self._h, i, st.row, st.n, int(evaluation_form), alpha_be32, c, ev, pf))
         return c.raw, ev.raw, pf.raw
+
+    def commit_open_batch_list(self, i: int, polys: Sequence[Sequence[str]], alpha_be32: bytes, gamma_be32: bytes,
+                               evaluation_form: bool = True) -> Tuple[List[bytes], List[bytes], bytes]:
+        """commit_open_batch fed from the synapse's text rows: the k lists are decoded by csrc/wire_py.c straight into ONE
+        pinned staging buffer, row j at offset 32 T j (no bytes object in between)."""
+        from . import codec
+
+        if codec._wire is None:
+            raise RuntimeError("zkp_subnet_amd._wire is not built: run `python -m zkp_subnet_amd.build`")
+        k = len(polys)
+        if k == 0 or k > _native.KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"commit_open_batch: k = {k} outside [1, {_native.KZG_MAX_BATCH_OPEN}]")
+        T = len(polys[0])
+        if any(len(p) != T for p in polys):
+            raise codec.CodecError("commit_open_batch: rows of unequal length")
+        cap = 32 * max(k * T, 1)
+        ptr, tok = ctypes.c_void_p(), ctypes.c_int(-1)
+        self._chk(self._lib.kzg_staging_acquire(self._h, cap, ctypes.byref(ptr), ctypes.byref(tok)))
+        try:
+            for j, p in enumerate(polys):
+                try:
+                    got = codec._wire.decode_fr_list_into(p, ptr.value + 32 * T * j, cap - 32 * T * j)
+                except ValueError as e:
+                    raise codec.CodecError(str(e)) from e
+                assert got == T
+            return self._commit_open_batch(i, k, ctypes.cast(ptr, ctypes.c_char_p), T, alpha_be32, gamma_be32,
+                                           evaluation_form)
+        finally:
+            self._lib.kzg_staging_release(self._h, tok.value)
 
     def row_cache_stats(self) -> Tuple[int, int]:
         """(hits, misses) of the coefficient cache behind commit_list / open_list."""

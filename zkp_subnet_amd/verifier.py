@@ -72,6 +72,24 @@ class Verifier:
             raise KzgError(rc, "kzg_vk_verify_batch: bad argument (index or non-canonical scalar)")
         return bool(ok.value)
 
+    def verify_open_batch(self, i: int, commitments48: Sequence[bytes], evals32: Sequence[bytes], alpha32: bytes,
+                          gamma32: bytes, proof48: bytes) -> bool:
+        """One batched opening of k rows of slice i (kzg_vk_verify_open_batch):
+        e(sum_j gamma^j C_j - (sum_j gamma^j y_j) L_i, [1]_2) == e(pi, [tau_x - alpha]_2)."""
+        k = len(commitments48)
+        if k != len(evals32):
+            raise ValueError("verify_open_batch: one evaluation per commitment")
+        if len(alpha32) != 32 or len(gamma32) != 32 or any(len(e) != 32 for e in evals32):
+            raise KzgError(_native.KZG_E_ARG, "kzg_vk_verify_open_batch: alpha / gamma / evals must be 32 bytes each")
+        if len(proof48) != 48 or any(len(c) != 48 for c in commitments48):
+            return False
+        ok = ctypes.c_int(0)
+        rc = self._lib.kzg_vk_verify_open_batch(self._h, i, k, b"".join(commitments48), b"".join(evals32), alpha32, gamma32,
+                                                proof48, ctypes.byref(ok))
+        if rc != 0:
+            raise KzgError(rc, "kzg_vk_verify_open_batch: bad argument (k, index or non-canonical scalar)")
+        return bool(ok.value)
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._lib.kzg_vk_destroy(self._h)
