@@ -139,6 +139,24 @@ int kzg_commit_open(kzg_ctx* ctx, uint32_t i, const uint8_t* row_be32, uint64_t 
 int kzg_commit_open_batch(kzg_ctx* ctx, uint32_t i, uint32_t k, const uint8_t* rows_be32 /* k*T*32, row-major */,
                           uint64_t T, int evaluation_form, const uint8_t alpha_be32[32], const uint8_t gamma_be32[32],
                           uint8_t* out_commitments48 /* k*48 */, uint8_t* out_evals32 /* k*32 */, uint8_t out_proof48[48]);
+/* Multi-point opening of k <= KZG_MAX_BATCH_OPEN rows of worker i at m <= KZG_MAX_OPEN_POINTS points (what a PLONK prover
+ * opens per sub-circuit: every polynomial at zeta, the permutation accumulator and the shifted rows also at zeta * omega).
+ * masks[p] (bit j = row j) names the rows opened at points_be32[p]; gammas_be32[p] is that point's challenge.  Returns the k
+ * commitments, the evaluations y_{j,p} = f_j(alpha_p) of every masked pair (point-major, ascending j inside a point) and one
+ * proof per point:
+ *   pi_p = MSM(U_i, (h_p - h_p(alpha_p)) / (X - alpha_p)),  h_p = sum_t gamma_p^t f_{j_t}  over the masked rows
+ *   j_0 < j_1 < ... of point p.
+ * m = 1 with the full mask reproduces kzg_commit_open_batch byte for byte; two equal points each keep their own proof.
+ * SOUNDNESS: as for kzg_commit_open_batch -- the alpha_p and gamma_p must be drawn by the verifier AFTER the commitments are
+ * fixed; the library derives none of them.  k = 0, k > KZG_MAX_BATCH_OPEN, m = 0, m > KZG_MAX_OPEN_POINTS, a zero mask, a
+ * mask bit >= k, an alpha_p or gamma_p >= r and every worker-index / length check of kzg_commit_open give KZG_E_ARG; the
+ * context keeps serving.  The rows are uploaded and transformed once; rows up to 2^18 run as ONE MSM pass with k + m scalar
+ * sets while the sort's key carries them (else as few passes as fit). */
+#define KZG_MAX_OPEN_POINTS 4
+int kzg_commit_open_multi(kzg_ctx* ctx, uint32_t i, uint32_t k, const uint8_t* rows_be32 /* k*T*32, row-major */, uint64_t T,
+                          int evaluation_form, uint32_t m, const uint8_t* points_be32 /* m*32 */, const uint32_t* masks /* m */,
+                          const uint8_t* gammas_be32 /* m*32 */, uint8_t* out_commitments48 /* k*48 */,
+                          uint8_t* out_evals32 /* sum popcount(masks)*32 */, uint8_t* out_proofs48 /* m*48 */);
 /* The UNCHANGED reference miner makes two calls per request with the same row -- worker_commit(i, poly), then
  * worker_open(i, poly, x) (neurons/miner.py:56-61).  These forms take a 128-bit content tag identifying the row's bytes
  * (the host codec computes it while decoding the text); the coefficient vectors of the last four rows stay on the
@@ -194,6 +212,16 @@ int kzg_vk_verify_batch(const kzg_vk* vk, uint32_t n, const uint32_t* idx, const
 int kzg_vk_verify_open_batch(const kzg_vk* vk, uint32_t i, uint32_t k, const uint8_t* commitments48,
                              const uint8_t* evals_be32, const uint8_t alpha_be32[32], const uint8_t gamma_be32[32],
                              const uint8_t proof48[48], int* out_valid);
+/* One multi-point opening (kzg_commit_open_multi) of k rows of slice i: for every point p
+ *   e(A_p, [1]_2) == e(pi_p, [tau_x - alpha_p]_2),  A_p = sum_t gamma_p^t C_{j_t} - (sum_t gamma_p^t y_{j_t,p}) [L_i]_1,
+ * folded with fresh 128-bit random weights r_p (getrandom, as in kzg_vk_verify_batch) into two Miller loops:
+ *   e(sum_p r_p (A_p + alpha_p pi_p), [1]_2) * e(-sum_p r_p pi_p, [tau_x]_2) == 1.
+ * evals_be32 in the layout kzg_commit_open_multi writes.  Malformed, off-curve or non-G1 commitment / proof bytes give
+ * *out_valid = 0 (not an error); k, m or a mask outside the rules of kzg_commit_open_multi, or i outside the key -> KZG_E_ARG;
+ * an alpha_p, gamma_p or evaluation >= r -> KZG_E_SCALAR. */
+int kzg_vk_verify_open_multi(const kzg_vk* vk, uint32_t i, uint32_t k, const uint8_t* commitments48, uint32_t m,
+                             const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32,
+                             const uint8_t* evals_be32, const uint8_t* proofs48, int* out_valid);
 
 /* ---- multi-GPU: each rank reduces its SRS shard to ONE partial sum; the 192-byte partials are exchanged by
  *      the caller (RCCL all_gather over xGMI in zkp_subnet_amd.distributed) and summed on any rank. */
@@ -318,6 +346,11 @@ int kzg_multi_commit_open_rows(kzg_multi* m, uint32_t n_rows, const uint32_t* in
 int kzg_multi_commit_open_batch(kzg_multi* m, uint32_t i, uint32_t k, const uint8_t* rows_be32, uint64_t T,
                                 int evaluation_form, const uint8_t alpha_be32[32], const uint8_t gamma_be32[32],
                                 uint8_t* out_commitments48, uint8_t* out_evals32, uint8_t out_proof48[48]);
+/* kzg_commit_open_multi on the device of worker i (routed like kzg_multi_commit_open) */
+int kzg_multi_commit_open_multi(kzg_multi* mh, uint32_t i, uint32_t k, const uint8_t* rows_be32, uint64_t T,
+                                int evaluation_form, uint32_t m, const uint8_t* points_be32, const uint32_t* masks,
+                                const uint8_t* gammas_be32, uint8_t* out_commitments48, uint8_t* out_evals32,
+                                uint8_t* out_proofs48);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

@@ -17,6 +17,7 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 LIB_PATH = os.environ.get("KZG_MI355X_LIB") or os.path.join(HERE, "libkzg_mi355x.so")
 
 KZG_MAX_BATCH_OPEN = 16   # include/kzg_mi355x.h
+KZG_MAX_OPEN_POINTS = 4
 KZG_OK, KZG_E_ARG, KZG_E_SCALAR, KZG_E_POINT, KZG_E_HIP, KZG_E_NOMEM, KZG_E_BUSY, KZG_E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
 STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_SCALAR", -3: "E_POINT", -4: "E_HIP", -5: "E_NOMEM", -6: "E_BUSY", -7: "E_COMM"}
 TIMING_NAMES = ["decode", "ntt", "digits", "scan", "scatter", "accumulate", "fixup", "tree", "final", "poly", "total", "collective"]
@@ -50,6 +51,7 @@ SYMBOLS = {
     "kzg_open": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B]),
     "kzg_commit_open": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B, _B]),
     "kzg_commit_open_batch": (_I, [_P, _U32, _U32, _B, _U64, _I, _B, _B, _B, _B, _B]),
+    "kzg_commit_open_multi": (_I, [_P, _U32, _U32, _B, _U64, _I, _U32, _B, ctypes.POINTER(_U32), _B, _B, _B, _B]),
     "kzg_commit_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B]),
     "kzg_open_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B, _B]),
     "kzg_row_cache_stats": (_I, [_P, ctypes.POINTER(_U64)]),
@@ -64,6 +66,7 @@ SYMBOLS = {
     "kzg_vk_verify": (_I, [_P, _U32, _B, _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_vk_verify_batch": (_I, [_P, _U32, ctypes.POINTER(_U32), _B, _B, _B, _B, _I, ctypes.POINTER(_I)]),
     "kzg_vk_verify_open_batch": (_I, [_P, _U32, _U32, _B, _B, _B, _B, _B, ctypes.POINTER(_I)]),
+    "kzg_vk_verify_open_multi": (_I, [_P, _U32, _U32, _B, _U32, _B, ctypes.POINTER(_U32), _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_vk_pairing": (_I, [_B, _B, _B]),
     "kzg_msm_partial": (_I, [_P, _B, _U64, _U64, _B]),
     "kzg_g1_sum": (_I, [_P, _B, _U32, _B]),
@@ -99,6 +102,7 @@ SYMBOLS = {
     "kzg_multi_open": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B]),
     "kzg_multi_commit_open": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B, _B]),
     "kzg_multi_commit_open_batch": (_I, [_P, _U32, _U32, _B, _U64, _I, _B, _B, _B, _B, _B]),
+    "kzg_multi_commit_open_multi": (_I, [_P, _U32, _U32, _B, _U64, _I, _U32, _B, ctypes.POINTER(_U32), _B, _B, _B, _B]),
     "kzg_multi_commit_open_rows": (_I, [_P, _U32, ctypes.POINTER(_U32), _B, _U64, _I, _B, _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_upload_fr": (_I, [_P, _I, _B, _U64, _I]),
     "kzg_msm_resident": (_I, [_P, _I, _U64, _U64, _B]),
@@ -133,6 +137,21 @@ class KzgError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"kzg_mi355x {STATUS_NAMES.get(code, code)}: {message}")
         self.code = code
+
+
+def open_masks(opened, k: int):
+    """The multi-point opening's row masks (bit j = row j) from opened[p], point p's rows as a strictly increasing list of
+    indices in [0, k); a (ctypes uint32 array, number of evaluations).  KzgError(KZG_E_ARG) for anything else."""
+    m = len(opened)
+    if m == 0 or m > KZG_MAX_OPEN_POINTS:
+        raise KzgError(KZG_E_ARG, f"multi-point opening: {m} points, expected 1 .. {KZG_MAX_OPEN_POINTS}")
+    masks = (ctypes.c_uint32 * m)()
+    for p, rows in enumerate(opened):
+        rows = [int(j) for j in rows]
+        if not rows or any(b <= a for a, b in zip(rows, rows[1:])) or rows[0] < 0 or rows[-1] >= k:
+            raise KzgError(KZG_E_ARG, f"multi-point opening: point {p} opens {rows}, expected increasing rows in [0, {k})")
+        masks[p] = sum(1 << j for j in rows)
+    return masks, sum(len(r) for r in opened)
 
 
 def lib_available() -> bool:

@@ -132,6 +132,18 @@ enum {
     BR_COPY = BR_C48 + MSM_MAX_SETS * 48, BR_Y_M = BR_COPY, BR_SIZE = BR_Y_M + KZG_MAX_BATCH_OPEN * 32
 };
 static_assert(BR_COPY % 4 == 0 && BR_COPY <= 8192, "the batched record is published by words into an 8 KB page");
+// the multi-point opening's record (kzg_commit_open_multi; the same Lane::brec / bpin): k + m result points (C_0 .. C_{k-1},
+// pi_0 .. pi_{m-1}), the evaluations of up to 64 (row, point) pairs big-endian, the GPU-side encodings -- [0, MR_COPY) is
+// published -- then the pairs' Montgomery evaluations, the points' Montgomery forms and the combinations' h_p(alpha_p)
+#define MR_SETS (KZG_MAX_BATCH_OPEN + KZG_MAX_OPEN_POINTS)
+#define MR_PAIRS (KZG_MAX_BATCH_OPEN * KZG_MAX_OPEN_POINTS)
+enum {
+    MR_RES = 0, MR_EVAL = MR_RES + MR_SETS * 224, MR_C48 = MR_EVAL + MR_PAIRS * 32, MR_COPY = MR_C48 + MR_SETS * 48,
+    MR_Y_M = MR_COPY, MR_ALPHA_M = MR_Y_M + MR_PAIRS * 32, MR_HY_M = MR_ALPHA_M + KZG_MAX_OPEN_POINTS * 32,
+    MR_SIZE = MR_HY_M + KZG_MAX_OPEN_POINTS * 32
+};
+static_assert(MR_COPY % 4 == 0 && MR_COPY <= 8192, "the multi-point record is published by words into an 8 KB page");
+static_assert(MR_PAIRS <= POLY_MAX_PAIRS && KZG_MAX_OPEN_POINTS <= POLY_MAX_POINTS, "one evaluation launch holds every pair");
 #define PIN_MAXLEN 1024           // offset of the fold-depth read-back inside the lane's pinned page
 #define PIN_SEQ 2048              // sequence word of the last published record (polled by finish())
 #define PIN_SEQ_SORT 2052         // sequence word of the last published fold-depth / overflow pair (polled by msm_core)
@@ -336,7 +348,7 @@ inline int ilog2_exact(uint64_t n) {
 }
 int pick_chunk(uint64_t entries);
 int msm_core(kzg_ctx* ctx, Lane& L, const uint32_t* scalars, int mont, uint64_t n, uint64_t srs_offset, g1_xyzz_t* out_xyzz,
-             const uint32_t* scalars2 = nullptr, int mont2 = 0, int nrows = 1, uint64_t row_stride = 0);
+             const uint32_t* scalars2 = nullptr, int mont2 = 0, int nrows = 1, uint64_t row_stride = 0, int ntail = 1);
 int ensure_twiddles(kzg_ctx* ctx, Lane& L, int log_n, int inverse, uint32_t** tw, uint32_t** invn);
 int row_to_coeffs(kzg_ctx* ctx, Lane& L, const uint32_t* row_dev, uint64_t T, int evaluation_form, const uint32_t** coeffs,
                   uint32_t* dst = nullptr);
@@ -356,6 +368,11 @@ int commit_open_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* row_d
 int commit_open_batch_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* rows_dev, uint32_t k, uint64_t T,
                           int evaluation_form, const uint8_t* alpha_be32, const uint8_t* gamma_be32, uint8_t* out_c48,
                           uint8_t* out_evals32, uint8_t* out_p48);
+// k rows of worker i opened at m points (kzg_commit_open_multi): masks[p] names point p's rows, gammas their challenge;
+// the k commitments, the evaluations of every masked pair (point-major) and one proof per point
+int commit_open_multi_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* rows_dev, uint32_t k, uint64_t T,
+                          int evaluation_form, uint32_t m, const uint8_t* points_be32, const uint32_t* masks,
+                          const uint8_t* gammas_be32, uint8_t* out_c48, uint8_t* out_evals32, uint8_t* out_p48);
 
 // ---- the collective (comm.hip)
 void comm_teardown(kzg_ctx* ctx);

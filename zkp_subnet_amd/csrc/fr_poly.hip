@@ -28,15 +28,12 @@ KZG_DEV void fr9_pow2k(fr9_t& a, int k) {  // a <- a^(2^k), canonical in and out
 // opening converts it itself -- every lane, it is one product -- and lane 0 leaves the Montgomery form at alpha_out for
 // the kernels behind it (and raises *bad for a value >= r); a 1-lane conversion kernel ahead of it was ~5 us of latency
 // Several rows at once (the batched opening): row blockIdx.y reads f + y * f_rs and writes h + y * h_rs (words).
+// (The body is shared with the multi-point opening's pair kernels below; lead: this grid row publishes alpha.)
 template <bool ARG>
-__global__ void __launch_bounds__(256) k_poly_chunk_eval(const uint32_t* __restrict__ f, uint64_t n, int lchunk,
-                                                          const uint32_t* __restrict__ alpha_mont, int sq,
-                                                          uint32_t* __restrict__ h, const FrArg arg,
-                                                          uint32_t* __restrict__ alpha_out, uint32_t* __restrict__ bad,
-                                                          uint64_t f_rs, uint64_t h_rs) {
+KZG_DEV void poly_chunk_eval(const uint32_t* __restrict__ f, uint64_t n, int lchunk, const uint32_t* __restrict__ alpha_mont,
+                             int sq, uint32_t* __restrict__ h, const FrArg& arg, bool lead, uint32_t* __restrict__ alpha_out,
+                             uint32_t* __restrict__ bad) {
     uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    f += blockIdx.y * f_rs;
-    h += blockIdx.y * h_rs;
     const uint64_t L = (uint64_t)1 << lchunk;
     uint64_t lo = t * L;
     fr9_t a, s, c;
@@ -46,7 +43,7 @@ __global__ void __launch_bounds__(256) k_poly_chunk_eval(const uint32_t* __restr
         for (int i = 0; i < 8; i++) w[i] = bswap32(arg.w[7 - i]);
         fr9_from_words(a, w);
         fr9_to_mont(a, a);
-        if (t == 0 && blockIdx.y == 0) {
+        if (t == 0 && lead) {
             if (fr_words_ge_r(w)) atomicOr(bad, 1u);
             fr9_store(alpha_out, a);
         }
@@ -64,19 +61,22 @@ __global__ void __launch_bounds__(256) k_poly_chunk_eval(const uint32_t* __restr
     fr9_reduce(s, s);
     fr9_store(h + 8 * t, s);
 }
+template <bool ARG>
+__global__ void __launch_bounds__(256) k_poly_chunk_eval(const uint32_t* __restrict__ f, uint64_t n, int lchunk,
+                                                          const uint32_t* __restrict__ alpha_mont, int sq,
+                                                          uint32_t* __restrict__ h, const FrArg arg,
+                                                          uint32_t* __restrict__ alpha_out, uint32_t* __restrict__ bad,
+                                                          uint64_t f_rs, uint64_t h_rs) {
+    poly_chunk_eval<ARG>(f + blockIdx.y * f_rs, n, lchunk, alpha_mont, sq, h + blockIdx.y * h_rs, arg, blockIdx.y == 0,
+                         alpha_out, bad);
+}
 // Suffix recurrence over chunks, H_t = h_t + beta H_{t+1}, beta = alpha^L: one NT_-lane block; lane v serially
 // folds m consecutive chunks, then a Hillis-Steele suffix scan whose multiplier (beta^m)^(2^step) is uniform.
 // Writes hnext[t] = H_{t+1} and y = H_0 = f(alpha).  Workgroup b scans row b: h and hnext at + b * h_rs words, y at + b.
 template <uint32_t NT_>
-__global__ void __launch_bounds__(NT_) k_poly_chunk_scan(const uint32_t* __restrict__ h, uint64_t nchunks, int lchunk,
-                                                           const uint32_t* __restrict__ alpha_mont,
-                                                           uint32_t* __restrict__ hnext, uint32_t* __restrict__ y_mont,
-                                                           uint8_t* __restrict__ y_be_or_null, uint64_t h_rs) {
-    __shared__ uint32_t sm[9][NT_];
-    h += blockIdx.x * h_rs;
-    hnext += blockIdx.x * h_rs;
-    y_mont += 8 * blockIdx.x;
-    if (y_be_or_null) y_be_or_null += 32 * blockIdx.x;
+KZG_DEV void poly_chunk_scan(uint32_t (*sm)[NT_], const uint32_t* __restrict__ h, uint64_t nchunks, int lchunk,
+                             const uint32_t* __restrict__ alpha_mont, uint32_t* __restrict__ hnext,
+                             uint32_t* __restrict__ y_mont, uint8_t* __restrict__ y_be_or_null) {
     const uint32_t v = threadIdx.x;
     const uint64_t m = (nchunks + NT_ - 1) / NT_;
     const uint64_t lo = (uint64_t)v * m;
@@ -146,11 +146,19 @@ __global__ void __launch_bounds__(NT_) k_poly_chunk_scan(const uint32_t* __restr
         }
     }
 }
+template <uint32_t NT_>
+__global__ void __launch_bounds__(NT_) k_poly_chunk_scan(const uint32_t* __restrict__ h, uint64_t nchunks, int lchunk,
+                                                           const uint32_t* __restrict__ alpha_mont,
+                                                           uint32_t* __restrict__ hnext, uint32_t* __restrict__ y_mont,
+                                                           uint8_t* __restrict__ y_be_or_null, uint64_t h_rs) {
+    __shared__ uint32_t sm[9][NT_];
+    const uint32_t b = blockIdx.x;
+    poly_chunk_scan<NT_>(sm, h + b * h_rs, nchunks, lchunk, alpha_mont, hnext + b * h_rs, y_mont + 8 * b,
+                         y_be_or_null ? y_be_or_null + 32 * b : nullptr);
+}
 // second level back down: hnext2[g] = H_{(g+1) * L2} over groups of L2 = 2^l2 first-level chunks -> hnext[u] = H_{u+1}
-__global__ void __launch_bounds__(256) k_poly_chunk_expand(const uint32_t* __restrict__ h, uint64_t nchunks, int l2,
-                                                            const uint32_t* __restrict__ alpha_mont, int sq,
-                                                            const uint32_t* __restrict__ hnext2,
-                                                            uint32_t* __restrict__ hnext) {
+KZG_DEV void poly_chunk_expand(const uint32_t* __restrict__ h, uint64_t nchunks, int l2, const uint32_t* __restrict__ alpha_mont,
+                               int sq, const uint32_t* __restrict__ hnext2, uint32_t* __restrict__ hnext) {
     uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t L = (uint64_t)1 << l2;
     uint64_t lo = g * L;
@@ -169,11 +177,15 @@ __global__ void __launch_bounds__(256) k_poly_chunk_expand(const uint32_t* __res
         fr9_add(s, s, c);
     }
 }
+__global__ void __launch_bounds__(256) k_poly_chunk_expand(const uint32_t* __restrict__ h, uint64_t nchunks, int l2,
+                                                            const uint32_t* __restrict__ alpha_mont, int sq,
+                                                            const uint32_t* __restrict__ hnext2,
+                                                            uint32_t* __restrict__ hnext) {
+    poly_chunk_expand(h, nchunks, l2, alpha_mont, sq, hnext2, hnext);
+}
 // q[j-1] = sum_{k>=j} f_k alpha^(k-j), written canonical (ready to be MSM scalars); q has n-1 entries
-__global__ void __launch_bounds__(256) k_poly_quotient(const uint32_t* __restrict__ f, uint64_t n, int lchunk,
-                                                        const uint32_t* __restrict__ alpha_mont,
-                                                        const uint32_t* __restrict__ hnext,
-                                                        uint32_t* __restrict__ q_canon) {
+KZG_DEV void poly_quotient(const uint32_t* __restrict__ f, uint64_t n, int lchunk, const uint32_t* __restrict__ alpha_mont,
+                           const uint32_t* __restrict__ hnext, uint32_t* __restrict__ q_canon) {
     uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t L = (uint64_t)1 << lchunk;
     uint64_t lo = t * L;
@@ -195,6 +207,51 @@ __global__ void __launch_bounds__(256) k_poly_quotient(const uint32_t* __restric
         fr9_zero(o);
         fr9_store(q_canon + 8 * (n - 1), o);
     }
+}
+__global__ void __launch_bounds__(256) k_poly_quotient(const uint32_t* __restrict__ f, uint64_t n, int lchunk,
+                                                        const uint32_t* __restrict__ alpha_mont,
+                                                        const uint32_t* __restrict__ hnext,
+                                                        uint32_t* __restrict__ q_canon) {
+    poly_quotient(f, n, lchunk, alpha_mont, hnext, q_canon);
+}
+
+// ---- the multi-point opening (kzg_commit_open_multi): grid row y is a PAIR -- row pa.row[y] at point pa.pt[y] -- with
+// its own level arrays at + y * h_rs words.  The first kernel of the evaluations (ARG) converts the pair's point from the
+// kernel argument pa.a[pt] and the point's first pair publishes its Montgomery form at alpha_mont + 8 pt (raising *bad for
+// a value >= r); every later kernel reads it from there.  The openings of the m combinations run as pairs (p, p): their
+// level-0 input is f + y * f_rs.  Same bodies as the kernels above: the same arithmetic, bit for bit.
+template <bool ARG>
+__global__ void __launch_bounds__(256) k_poly_pairs_eval(const uint32_t* __restrict__ f, uint64_t n, int lchunk,
+                                                          uint32_t* __restrict__ alpha_mont, int sq, uint32_t* __restrict__ h,
+                                                          const PairArg pa, uint32_t* __restrict__ bad, uint64_t f_rs,
+                                                          uint64_t h_rs) {
+    const uint32_t y = blockIdx.y, p = pa.pt[y];
+    poly_chunk_eval<ARG>(f + (ARG ? pa.row[y] : y) * f_rs, n, lchunk, alpha_mont + 8 * p, sq, h + y * h_rs, pa.a[p],
+                         y == 0 || pa.pt[y - 1] != p, alpha_mont + 8 * p, bad);
+}
+template <uint32_t NT_>
+__global__ void __launch_bounds__(NT_) k_poly_pairs_scan(const uint32_t* __restrict__ h, uint64_t nchunks, int lchunk,
+                                                           const uint32_t* __restrict__ alpha_mont,
+                                                           uint32_t* __restrict__ hnext, uint32_t* __restrict__ y_mont,
+                                                           uint8_t* __restrict__ y_be_or_null, uint64_t h_rs, const PairArg pa) {
+    __shared__ uint32_t sm[9][NT_];
+    const uint32_t b = blockIdx.x;
+    poly_chunk_scan<NT_>(sm, h + b * h_rs, nchunks, lchunk, alpha_mont + 8 * pa.pt[b], hnext + b * h_rs, y_mont + 8 * b,
+                         y_be_or_null ? y_be_or_null + 32 * b : nullptr);
+}
+__global__ void __launch_bounds__(256) k_poly_pairs_expand(const uint32_t* __restrict__ h, uint64_t nchunks, int l2,
+                                                            const uint32_t* __restrict__ alpha_mont, int sq,
+                                                            const uint32_t* __restrict__ hnext2, uint32_t* __restrict__ hnext,
+                                                            uint64_t h_rs, const PairArg pa) {
+    const uint32_t y = blockIdx.y;
+    poly_chunk_expand(h + y * h_rs, nchunks, l2, alpha_mont + 8 * pa.pt[y], sq, hnext2 + y * h_rs, hnext + y * h_rs);
+}
+__global__ void __launch_bounds__(256) k_poly_pairs_quotient(const uint32_t* __restrict__ f, uint64_t n, int lchunk,
+                                                              const uint32_t* __restrict__ alpha_mont,
+                                                              const uint32_t* __restrict__ hnext, uint32_t* __restrict__ q_canon,
+                                                              uint64_t f_rs, uint64_t h_rs, const PairArg pa) {
+    const uint32_t y = blockIdx.y;
+    poly_quotient(f + y * f_rs, n, lchunk, alpha_mont + 8 * pa.pt[y], hnext + y * h_rs, q_canon + y * f_rs);
 }
 
 // ---- the batched opening's combination h[t] = sum_j gamma^j c_j[t] over k Montgomery rows at a stride of n elements
@@ -228,6 +285,37 @@ void launch_fr_combine_rows(hipStream_t s, const uint32_t* rows_mont, uint64_t n
     FrArg arg;
     memcpy(arg.w, gamma_be32_host, 32);
     if (n && k) k_fr_combine_rows<<<nblk(n, 256), 256, 0, s>>>(rows_mont, n, k, arg, out_mont, bad);
+}
+
+// ---- the multi-point opening's combinations: grid row p computes h_p[t] = sum_t' gamma_p^t' c_{j_t'}[t] over the rows j of
+// ca.mask[p] (Horner from the highest one, as k_fr_combine_rows: one point with the full mask is its h, bit for bit) into
+// out + p * n elements.  Point p's first lane raises *bad for a gamma_p >= r.
+__global__ void __launch_bounds__(256) k_fr_combine_points(const uint32_t* __restrict__ rows, uint64_t n, const CombArg ca,
+                                                            uint32_t* __restrict__ out, uint32_t* __restrict__ bad) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t p = blockIdx.y, mask = ca.mask[p];
+    uint32_t w[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) w[i] = bswap32(ca.g[p].w[7 - i]);
+    if (t == 0 && fr_words_ge_r(w)) atomicOr(bad, 1u);
+    if (t >= n || !mask) return;
+    fr9_t g, s, c;
+    fr9_from_words(g, w);
+    fr9_to_mont(g, g);
+    int j = 31 - __clz(mask);
+    fr9_load(s, rows + 8 * ((uint64_t)j * n + t));
+    while (--j >= 0) {
+        if (!((mask >> j) & 1u)) continue;
+        fr9_load(c, rows + 8 * ((uint64_t)j * n + t));
+        fr9_mul(s, s, g);
+        fr9_add(s, s, c);
+    }
+    fr9_reduce(s, s);
+    fr9_store(out + 8 * ((uint64_t)p * n + t), s);
+}
+void launch_fr_combine_points(hipStream_t s, const uint32_t* rows_mont, uint64_t n, uint32_t m, const CombArg& ca,
+                              uint32_t* out_mont, uint32_t* bad) {
+    if (n && m) k_fr_combine_points<<<dim3(nblk(n, 256), m), 256, 0, s>>>(rows_mont, n, ca, out_mont, bad);
 }
 
 // ---- long rows (16 coefficients per lane): the quotient (and, as an A/B form, the level-0 fold) with the coefficients
@@ -332,14 +420,27 @@ void launch_words_differ(hipStream_t s, const uint32_t* a, const uint32_t* b, ui
 // (n+3)/4 * 3/2 + 64 entries; the levels above the first sum to < 1/3 of it).  `rows` rows of n coefficients (at a
 // stride of n elements) go through the same launches side by side: row r's level arrays at h / hnext + r * h_row_words,
 // its y at y_mont + 8 r (and y_be + 32 r) -- k evaluations for the latency of one.
+// long rows: the level-0 fold and the quotient with their coefficients staged through LDS (KZG_POLY_NO_LDS=1: the
+// strided forms, kept for the A/B and as the reference of test_poly_kernel_variants_agree)
+static bool quotient_lds(uint64_t n, int l0) {
+    static const bool no_lds = getenv("KZG_POLY_NO_LDS") != nullptr;
+    // from 2^21 coefficients: same-box A/Bs (profiles/r04_ab_opening_lds_staging.log, r04_ab_opening_lds_phases.log) of the
+    // opening stage: 2^22 0.284 -> 0.236 ms, 2^21 0.196 -> 0.185, 2^20 0.160 -> 0.167 (one wave per SIMD there: the LDS hop
+    // is pure latency).  KZG_POLY_LDS_MIN_LOG moves the threshold.
+    static const int lds_min_log = getenv("KZG_POLY_LDS_MIN_LOG") ? atoi(getenv("KZG_POLY_LDS_MIN_LOG")) : 21;
+    // (the level-0 fold gains nothing from LDS staging: 53 against 49 us, profiles/r04_ab_opening_lds_staging.log -- strided)
+    return !no_lds && l0 == 4 && (n & 1023) == 0 && n >= ((uint64_t)1 << lds_min_log);
+}
 struct PolyLevels {
     int K;
     int l[16], sq[16];
     uint64_t n[16], off[16];
 };
+// pa given (the multi-point opening): the rows are pairs, each at its own point (k_poly_pairs_*); ARG then stands for
+// alpha_be32_host != null, the points coming from pa.a
 static void poly_up(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t rows, uint32_t* alpha_mont, uint32_t* h,
                     uint32_t* hnext, uint64_t h_rs, uint32_t* y_mont, const uint8_t* alpha_be32_host, uint32_t* bad,
-                    uint8_t* y_be_or_null, PolyLevels& lv) {
+                    uint8_t* y_be_or_null, PolyLevels& lv, const PairArg* pa = nullptr) {
     FrArg arg;
     memset(&arg, 0, sizeof(arg));
     if (alpha_be32_host) memcpy(arg.w, alpha_be32_host, 32);
@@ -353,7 +454,14 @@ static void poly_up(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t 
     int K = 1;
     lv_l[0] = l0; lv_sq[0] = 0; lv_n[0] = n; lv_off[0] = 0;           // level 0 = f itself (offset unused)
     lv_n[1] = (n + ((uint64_t)1 << l0) - 1) >> l0; lv_sq[1] = l0; lv_off[1] = 0;
-    if (alpha_be32_host)
+    if (pa) {
+        if (alpha_be32_host)
+            k_poly_pairs_eval<true><<<dim3(nblk(lv_n[1], 256), rows), 256, 0, s>>>(f_mont, n, l0, alpha_mont, 0, h, *pa, bad,
+                                                                               n * 8, h_rs);
+        else
+            k_poly_pairs_eval<false><<<dim3(nblk(lv_n[1], 256), rows), 256, 0, s>>>(f_mont, n, l0, alpha_mont, 0, h, *pa,
+                                                                                nullptr, n * 8, h_rs);
+    } else if (alpha_be32_host)
         k_poly_chunk_eval<true><<<dim3(nblk(lv_n[1], 256), rows), 256, 0, s>>>(f_mont, n, l0, alpha_mont, 0, h, arg, alpha_mont,
                                                                            bad, f_rs, h_rs);
     else
@@ -364,14 +472,26 @@ static void poly_up(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t 
         lv_n[K + 1] = (lv_n[K] + ((uint64_t)1 << lup) - 1) >> lup;
         lv_sq[K + 1] = lv_sq[K] + lup;
         lv_off[K + 1] = lv_off[K] + lv_n[K];
-        k_poly_chunk_eval<false><<<dim3(nblk(lv_n[K + 1], 256), rows), 256, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lup, alpha_mont,
-                                                                                lv_sq[K], h + 8 * lv_off[K + 1], arg, nullptr,
-                                                                                nullptr, h_rs, h_rs);
+        if (pa)
+            k_poly_pairs_eval<false><<<dim3(nblk(lv_n[K + 1], 256), rows), 256, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lup,
+                                                                                    alpha_mont, lv_sq[K], h + 8 * lv_off[K + 1],
+                                                                                    *pa, nullptr, h_rs, h_rs);
+        else
+            k_poly_chunk_eval<false><<<dim3(nblk(lv_n[K + 1], 256), rows), 256, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lup,
+                                                                                    alpha_mont, lv_sq[K], h + 8 * lv_off[K + 1],
+                                                                                    arg, nullptr, nullptr, h_rs, h_rs);
         K++;
     }
     // the scan is one workgroup of dependent Fr products: 256 lanes (one wave per SIMD, <= 8 values each) run the chain
     // at a lone wave's issue rate; 1024 lanes (four waves per SIMD) only when there is more than that to fold
-    if (lv_n[K] <= 1024)
+    if (pa) {
+        if (lv_n[K] <= 1024)
+            k_poly_pairs_scan<256><<<rows, 256, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lv_sq[K], alpha_mont, hnext + 8 * lv_off[K],
+                                                        y_mont, y_be_or_null, h_rs, *pa);
+        else
+            k_poly_pairs_scan<1024><<<rows, 1024, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lv_sq[K], alpha_mont,
+                                                          hnext + 8 * lv_off[K], y_mont, y_be_or_null, h_rs, *pa);
+    } else if (lv_n[K] <= 1024)
         k_poly_chunk_scan<256><<<rows, 256, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lv_sq[K], alpha_mont, hnext + 8 * lv_off[K],
                                                     y_mont, y_be_or_null, h_rs);
     else
@@ -393,15 +513,7 @@ void launch_poly_open(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_
     const int* lv_sq = lv.sq;
     const uint64_t* lv_n = lv.n;
     const uint64_t* lv_off = lv.off;
-    // long rows: the level-0 fold and the quotient with their coefficients staged through LDS (KZG_POLY_NO_LDS=1: the
-    // strided forms, kept for the A/B and as the reference of test_poly_kernel_variants_agree)
-    static const bool no_lds = getenv("KZG_POLY_NO_LDS") != nullptr;
-    // from 2^21 coefficients: same-box A/Bs (profiles/r04_ab_opening_lds_staging.log, r04_ab_opening_lds_phases.log) of the
-    // opening stage: 2^22 0.284 -> 0.236 ms, 2^21 0.196 -> 0.185, 2^20 0.160 -> 0.167 (one wave per SIMD there: the LDS hop
-    // is pure latency).  KZG_POLY_LDS_MIN_LOG moves the threshold.
-    static const int lds_min_log = getenv("KZG_POLY_LDS_MIN_LOG") ? atoi(getenv("KZG_POLY_LDS_MIN_LOG")) : 21;
-    const bool lds = !no_lds && l0 == 4 && (n & 1023) == 0 && n >= ((uint64_t)1 << lds_min_log);
-    // (the level-0 fold gains nothing from LDS staging: 53 against 49 us, profiles/r04_ab_opening_lds_staging.log -- strided)
+    const bool lds = quotient_lds(n, l0);
     for (int k = K - 1; k >= 1; k--)
         k_poly_chunk_expand<<<nblk(lv_n[k + 1], 256), 256, 0, s>>>(h + 8 * lv_off[k], lv_n[k], lv_l[k], alpha_mont,
                                                                    lv_sq[k], hnext + 8 * lv_off[k + 1],
@@ -418,3 +530,36 @@ void launch_poly_eval_rows(hipStream_t s, const uint32_t* f_mont, uint64_t n, ui
     if (n && rows) poly_up(s, f_mont, n, rows, alpha_mont, h, hnext, h_row_words, y_mont, alpha_be32_host, bad, y_be, lv);
 }
 
+void launch_poly_eval_pairs(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t npairs, const PairArg& pa,
+                            uint32_t* alpha_mont, uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont,
+                            uint32_t* bad, uint8_t* y_be) {
+    static const uint8_t ARG_MARK[32] = {};   // (non-null: the first kernel converts the points of pa.a)
+    PolyLevels lv;
+    if (n && npairs)
+        poly_up(s, f_mont, n, npairs, alpha_mont, h, hnext, h_row_words, y_mont, ARG_MARK, bad, y_be, lv, &pa);
+}
+// the levels go up with the pair kernels (pair p = combination p at point p), then back down as in launch_poly_open with
+// grid y = point; long rows' LDS-staged quotient runs once per point
+void launch_poly_open_points(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t m, const uint32_t* alpha_mont,
+                             uint32_t* h, uint32_t* hnext, uint64_t h_rs, uint32_t* y_mont, uint32_t* q_canon) {
+    if (!n || !m) return;
+    PairArg pa;
+    memset(&pa, 0, sizeof(pa));
+    for (uint32_t p = 0; p < m; p++) pa.row[p] = pa.pt[p] = (uint8_t)p;
+    PolyLevels lv;
+    uint32_t* am = const_cast<uint32_t*>(alpha_mont);   // (read only: no point is converted on this path)
+    poly_up(s, f_mont, n, m, am, h, hnext, h_rs, y_mont, nullptr, nullptr, nullptr, lv, &pa);
+    const int l0 = lv.l[0], K = lv.K;
+    for (int k = K - 1; k >= 1; k--)
+        k_poly_pairs_expand<<<dim3(nblk(lv.n[k + 1], 256), m), 256, 0, s>>>(h + 8 * lv.off[k], lv.n[k], lv.l[k], alpha_mont,
+                                                                            lv.sq[k], hnext + 8 * lv.off[k + 1],
+                                                                            hnext + 8 * lv.off[k], h_rs, pa);
+    if (quotient_lds(n, l0)) {
+        for (uint32_t p = 0; p < m; p++)
+            k_poly_quotient16_lds<<<(uint32_t)(n >> 10), 64, 0, s>>>(f_mont + p * n * 8, n, alpha_mont + 8 * p, hnext + p * h_rs,
+                                                                    q_canon + p * n * 8);
+    } else {
+        k_poly_pairs_quotient<<<dim3(nblk(lv.n[1], 256), m), 256, 0, s>>>(f_mont, n, l0, alpha_mont, hnext, q_canon, n * 8,
+                                                                          h_rs, pa);
+    }
+}

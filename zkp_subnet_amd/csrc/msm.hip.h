@@ -35,8 +35,9 @@ struct MsmShape {
 
 // signed-digit recode + two-level counting sort: fills offsets[0..nbuckets] and sorted[0..entries).
 // part_ws: 16384 u32 scratch; parted: one uint2 per entry
-// With sh.nbatch == S > 1 scalar sets (same length, same points) set b is sorted into bucket set b: sets 0 .. S-2 lie at
-// scalars + b * set_stride words (Montgomery form scalars_mont), set S-1 is scalars2 (scalars2_mont).  The key gets
+// With sh.nbatch == S > 1 scalar sets (same length, same points) set b is sorted into bucket set b: sets 0 .. nrows-1 lie at
+// scalars + b * set_stride words (Montgomery form scalars_mont), sets nrows .. S-1 at scalars2 + (b - nrows) * set_stride
+// (scalars2_mont); nrows < 0 means S - 1 (one trailing set).  The key gets
 // ceil(log2 S) more high bits (key = set << (c-1) | digit - 1, at most 24 bits: msm_sort_max_sets), everything downstream
 // just sees S * nbuckets buckets; partitions of the key space beyond the last set are not launched.
 // part_ws_clean: the partition counts / cursors are known to be zero (a completed sort leaves them so); max_len_word: the
@@ -57,7 +58,7 @@ struct SortTail {
 void launch_msm_sort(hipStream_t s, const MsmShape& sh, const uint32_t* scalars, int scalars_mont,
                      const uint32_t* scalars2, int scalars2_mont, uint32_t* part_ws, bool part_ws_clean, uint2* parted,
                      uint32_t* offsets, uint32_t* sorted, uint32_t* max_len_word, bool fast, uint32_t* overflow_word,
-                     const SortTail* tail = nullptr, uint64_t set_stride = 0);
+                     const SortTail* tail = nullptr, uint64_t set_stride = 0, int nrows = -1);
 // scalar sets per MSM (one sort, one bucket tree with nbatch roots); KZG_MAX_BATCH_OPEN rows + the batched opening's quotient
 #define MSM_MAX_SETS 17
 // how many scalar sets one pass of window c can carry: the sort's key (set bits + c - 1 digit bits) has at most 24 bits

@@ -26,9 +26,9 @@ KZG_DEV uint32_t signed_digit(const uint32_t* s, int w, const WinLayout& lay, ui
 #define SORT_MAXPART 4096
 struct SortShape {
     uint64_t n, total, srs_offset, srs_stride;  // n scalars per set, total = n * sets
-    const uint32_t* scalars2;                   // the LAST scalar set of a batch of nsets > 1 MSMs over the same points
-    uint64_t stride;                            // words between sets 0 .. nsets-2 (they follow the kernels' `scalars`)
-    int nsets;
+    const uint32_t* scalars2;                   // the trailing sets nrows .. nsets-1 of a batch of nsets > 1 MSMs
+    uint64_t stride;                            // words between consecutive sets (rows at `scalars`, trailing at scalars2)
+    int nsets, nrows;                           // nrows: sets at the kernels' `scalars` (nsets - 1 unless set otherwise)
     int mont, mont2, keybits, hbits, lbits;     // key = set << keybits | digit magnitude - 1 = (part << lbits) | low
     uint32_t spb;                               // scalars per workgroup in the two level-1 kernels
 };
@@ -51,9 +51,9 @@ KZG_DEV const uint32_t* scalar_set(const uint32_t* scalars, const SortShape& ss,
             j -= ss.n;
             set++;
         }
-        const bool last = set && set == (uint32_t)ss.nsets - 1u;
-        mont = last ? ss.mont2 : ss.mont;
-        return last ? ss.scalars2 : scalars + (uint64_t)set * ss.stride;
+        const bool tail = set >= (uint32_t)ss.nrows;   // a trailing set (the openings' quotients): at scalars2, canonical
+        mont = tail ? ss.mont2 : ss.mont;
+        return tail ? ss.scalars2 + (uint64_t)(set - (uint32_t)ss.nrows) * ss.stride : scalars + (uint64_t)set * ss.stride;
     }
 }
 // h[key]++ in LDS, returning the old value.  When every active lane of the wave holds the same key (all scalars
@@ -651,12 +651,12 @@ int msm_sort_max_sets(int c) {
     return room >= 5 ? MSM_MAX_SETS : 1 << room;
 }
 static void sort_shape(const MsmShape& sh, const uint32_t* scalars2, int scalars_mont, int scalars2_mont, SortShape& ss,
-                       uint64_t set_stride = 0) {
+                       uint64_t set_stride = 0, int nrows = -1) {
     const int setbits = set_bits(sh.nbatch);
     const int keybits = sh.c - 1 + setbits;
     ss.n = sh.n; ss.total = sh.n * (uint64_t)sh.nbatch; ss.srs_offset = sh.srs_offset; ss.srs_stride = sh.srs_stride;
     ss.mont = scalars_mont; ss.scalars2 = scalars2; ss.mont2 = scalars2_mont; ss.keybits = sh.c - 1;
-    ss.stride = set_stride; ss.nsets = sh.nbatch;
+    ss.stride = set_stride; ss.nsets = sh.nbatch; ss.nrows = nrows < 0 ? sh.nbatch - 1 : nrows;
     // 1024 partitions (level 2 runs one workgroup per partition), up to 4096 when that brings a partition down to what
     // level 2 can stage in LDS (SORT_STAGE entries; ~13 k on average at 2^20 / 1024, ~27 k at 2^22 / 2048 and 2^23 / 4096)
     const uint64_t entries = ss.total * (uint64_t)sh.nwin;
@@ -722,7 +722,7 @@ static void launch_partition_staged(hipStream_t s, const uint32_t* scalars, cons
 void launch_msm_sort(hipStream_t s, const MsmShape& sh, const uint32_t* scalars, int scalars_mont,
                      const uint32_t* scalars2, int scalars2_mont, uint32_t* part_ws, bool part_ws_clean, uint2* parted,
                      uint32_t* offsets, uint32_t* sorted, uint32_t* max_len_word, bool fast, uint32_t* overflow_word,
-                     const SortTail* tail, uint64_t set_stride) {
+                     const SortTail* tail, uint64_t set_stride, int nrows) {
     SortTail tl{0u, nullptr, nullptr, nullptr, 0u};
     if (tail) tl = *tail;
     uint32_t* done = part_ws + 3 * SORT_MAXPART + 16;   // k_sort_buckets' ticket counter (zero between sorts)
@@ -731,7 +731,7 @@ void launch_msm_sort(hipStream_t s, const MsmShape& sh, const uint32_t* scalars,
         scalars2_mont = scalars_mont;
     }
     SortShape ss;
-    sort_shape(sh, scalars2, scalars_mont, scalars2_mont, ss, set_stride);
+    sort_shape(sh, scalars2, scalars_mont, scalars2_mont, ss, set_stride, nrows);
     const uint64_t entries = ss.total * (uint64_t)sh.nwin;
     const uint32_t npart = 1u << ss.hbits;
     // level 2 runs over the partitions that hold keys only: the bucket arrays downstream hold exactly nbatch * 2^(c-1) buckets

@@ -371,6 +371,16 @@ int kzg_multi_commit_open_batch(kzg_multi* m, uint32_t i, uint32_t k, const uint
     return relay(c, kzg_commit_open_batch(c, s, k, rows_be32, T, evaluation_form, alpha_be32, gamma_be32, out_commitments48,
                                           out_evals32, out_proof48));
 }
+int kzg_multi_commit_open_multi(kzg_multi* mh, uint32_t i, uint32_t k, const uint8_t* rows_be32, uint64_t T,
+                                int evaluation_form, uint32_t m, const uint8_t* points_be32, const uint32_t* masks,
+                                const uint8_t* gammas_be32, uint8_t* out_commitments48, uint8_t* out_evals32,
+                                uint8_t* out_proofs48) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_commit_open_multi(c, s, k, rows_be32, T, evaluation_form, m, points_be32, masks, gammas_be32,
+                                          out_commitments48, out_evals32, out_proofs48));
+}
 
 int kzg_multi_create(int device_count, const int* device_ids, kzg_multi** out) {
     return guarded("kzg_multi_create", [&] { return create_impl(device_count, device_ids, out); });

@@ -674,6 +674,91 @@ int kzg_vk_verify_open_batch(const kzg_vk* vk, uint32_t i, uint32_t k, const uin
     }
 }
 
+/* The multi-point opening: point p reduces to D_p = A_p + alpha_p pi_p with e(D_p, [1]_2) == e(pi_p, [tau_x]_2); the m
+ * checks are folded with random 128-bit weights into e(sum_p r_p D_p, [1]_2) * e(-sum_p r_p pi_p, [tau_x]_2) == 1.  A_p by
+ * Horner from the point's last masked row.  One thread per point. */
+int kzg_vk_verify_open_multi(const kzg_vk* vk, uint32_t i, uint32_t k, const uint8_t* commitments48, uint32_t m,
+                             const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32,
+                             const uint8_t* evals_be32, const uint8_t* proofs48, int* out_valid) {
+    if (!vk || !commitments48 || !points_be32 || !masks || !gammas_be32 || !evals_be32 || !proofs48 || !out_valid)
+        return KZG_E_ARG;
+    *out_valid = 0;
+    if (k == 0 || k > KZG_MAX_BATCH_OPEN || m == 0 || m > KZG_MAX_OPEN_POINTS || i >= vk->k.li.size()) return KZG_E_ARG;
+    uint32_t npairs = 0;
+    for (uint32_t p = 0; p < m; p++) {
+        if (masks[p] == 0 || (masks[p] >> k) != 0) return KZG_E_ARG;
+        npairs += (uint32_t)__builtin_popcount(masks[p]);
+    }
+    u64 alpha[KZG_MAX_OPEN_POINTS][4], gamma[KZG_MAX_OPEN_POINTS][4];
+    for (uint32_t p = 0; p < m; p++)
+        if (!fr_from_be32(alpha[p], points_be32 + 32 * (size_t)p) || !fr_from_be32(gamma[p], gammas_be32 + 32 * (size_t)p))
+            return KZG_E_SCALAR;
+    std::vector<u64> y(4 * (size_t)npairs);
+    for (uint32_t t = 0; t < npairs; t++)
+        if (!fr_from_be32(&y[4 * (size_t)t], evals_be32 + 32 * (size_t)t)) return KZG_E_SCALAR;
+    try {
+        u64 w[2 * KZG_MAX_OPEN_POINTS];                      // the weights: 128 random bits per point
+        {
+            size_t need = 2 * (size_t)m * sizeof(u64), got = 0;
+            while (got < need) {
+                const ssize_t r = getrandom(reinterpret_cast<uint8_t*>(w) + got, need - got, 0);
+                if (r < 0 && errno == EINTR) continue;
+                if (r <= 0) return KZG_E_NOMEM;
+                got += (size_t)r;
+            }
+        }
+        // malformed or off-curve / out-of-subgroup group elements are an invalid proof, not a call failure
+        std::vector<G1A> c(k), pi(m);
+        for (uint32_t j = 0; j < k; j++)
+            if (!g1_decompress(c[j], commitments48 + 48 * (size_t)j) || !g1_in_subgroup_fast(c[j])) return KZG_OK;
+        for (uint32_t p = 0; p < m; p++)
+            if (!g1_decompress(pi[p], proofs48 + 48 * (size_t)p) || !g1_in_subgroup_fast(pi[p])) return KZG_OK;
+        uint32_t first[KZG_MAX_OPEN_POINTS];                 // the point's first evaluation
+        for (uint32_t p = 0, t = 0; p < m; t += (uint32_t)__builtin_popcount(masks[p]), p++) first[p] = t;
+        Jac<Fp> accD[KZG_MAX_OPEN_POINTS], accP[KZG_MAX_OPEN_POINTS];
+        auto work = [&](uint32_t p) {
+            const uint32_t mask = masks[p];
+            int j = 31 - __builtin_clz(mask);
+            uint32_t t = first[p] + (uint32_t)__builtin_popcount(mask) - 1;
+            Jac<Fp> cs = to_jac(c[j]);
+            u64 ys[4];
+            memcpy(ys, &y[4 * (size_t)t], sizeof(ys));
+            while (--j >= 0) {
+                if (!((mask >> j) & 1)) continue;
+                t--;
+                cs = jac_add(jac_mul(to_aff(cs), gamma[p], 4), to_jac(c[j]));
+                fr_mul_mod(ys, ys, gamma[p]);
+                fr_add_mod(ys, &y[4 * (size_t)t]);
+            }
+            const Jac<Fp> yl = jac_mul(vk->k.li[i], ys, 4);
+            const Jac<Fp> d = jac_add(jac_add(cs, to_jac(aff_neg(to_aff(yl)))), jac_mul(pi[p], alpha[p], 4));
+            accD[p] = jac_mul(to_aff(d), &w[2 * (size_t)p], 2);
+            accP[p] = jac_mul(pi[p], &w[2 * (size_t)p], 2);
+        };
+        {
+            std::vector<std::thread> th;
+            uint32_t started = 1;                            // point 0 runs on the caller
+            try {
+                for (uint32_t p = 1; p < m; p++, started++) th.emplace_back(work, p);
+            } catch (const std::system_error&) {             // out of threads: the caller takes the points nobody got
+            }
+            work(0);
+            for (uint32_t p = started; p < m; p++) work(p);
+            for (auto& x : th) x.join();
+        }
+        Jac<Fp> D = jac_inf<Fp>(), P = jac_inf<Fp>();
+        for (uint32_t p = 0; p < m; p++) {
+            D = jac_add(D, accD[p]);
+            P = jac_add(P, accP[p]);
+        }
+        const Fp12 f = miller_loop(to_aff(D), vk->k.g2) * miller_loop(aff_neg(to_aff(P)), vk->k.tau_g2);
+        *out_valid = is_one(final_exp_fast(f)) ? 1 : 0;
+        return KZG_OK;
+    } catch (...) {
+        return KZG_E_NOMEM;
+    }
+}
+
 /* test hook: out = final_exp(miller(P, Q)) as 12 x 48 bytes in tower order
  * (c0.c0.c0, c0.c0.c1, c0.c1.c0, ..., c1.c2.c1); P affine be96, Q uncompressed be192 */
 int kzg_vk_pairing(const uint8_t p_be96[96], const uint8_t q_be192[192], uint8_t out_fp12[576]) {

@@ -33,7 +33,8 @@ int pick_chunk(uint64_t entries) {
 // set b is sorted into bucket set b, the sort / accumulate / fold / tree kernels simply see twice the buckets, the
 // tree stops at two roots and out_xyzz[0..1] receive the two sums.  One kernel sequence, one latency-bound tail.
 // nrows > 1 (the batched opening): sets 0 .. nrows-1 lie at scalars + b * row_stride words, scalars2 (if given) is set
-// nrows; nrows + 1 <= msm_sort_max_sets(c) sets, nrows + 1 roots at out_xyzz[0 ..].
+// nrows; nrows + 1 <= msm_sort_max_sets(c) sets, nrows + 1 roots at out_xyzz[0 ..].  ntail > 1 (the multi-point opening):
+// scalars2 holds ntail sets at the same stride (its quotients), sets nrows .. nrows + ntail - 1.
 // The only host wait inside is on the 4-byte fold-depth read-back; the calling thread holds no lock meanwhile.
 // The bucket tree on stream s: merges level arrays until `stop` nodes are left.  Three buffers in rotation (a level reads its
 // own array and the P array of the level below, writes the next) plus a fourth for the two-level launches.  On return b.in is
@@ -65,9 +66,9 @@ static void run_tree(hipStream_t s, TreeBufs& b, uint32_t n_in, uint32_t stop) {
     }
 }
 int msm_core(kzg_ctx* ctx, Lane& L, const uint32_t* scalars, int mont, uint64_t n, uint64_t srs_offset,
-             g1_xyzz_t* out_xyzz, const uint32_t* scalars2, int mont2, int nrows, uint64_t row_stride) {
+             g1_xyzz_t* out_xyzz, const uint32_t* scalars2, int mont2, int nrows, uint64_t row_stride, int ntail) {
     hipStream_t s = L.stream;
-    const int nbatch = nrows + (scalars2 ? 1 : 0);
+    const int nbatch = nrows + (scalars2 ? ntail : 0);
     if (nrows < 1 || nbatch > std::min(MSM_MAX_SETS, msm_sort_max_sets(ctx->c)))
         return fail(ctx, KZG_E_ARG, "MSM pass with more scalar sets than the sort's key can carry");
     if (n == 0) {
@@ -115,7 +116,7 @@ int msm_core(kzg_ctx* ctx, Lane& L, const uint32_t* scalars, int mont, uint64_t 
                             reinterpret_cast<uint32_t*>(L.pin_dev + PIN_SEQ_SORT), ++L.sort_seq};
         launch_msm_sort(s, sh, scalars, mont, scalars2, mont2, L.hist.as<uint32_t>(), ws_clean, L.rank.as<uint2>(),
                         L.offsets.as<uint32_t>(), L.sorted.as<uint32_t>(), max_len_d, fast_mode, max_len_d + 1,
-                        &tail, row_stride);
+                        &tail, row_stride, scalars2 ? nrows : -1);
     };
     {
         Span sp(ctx, L, KZG_T_DIGITS);
@@ -474,6 +475,128 @@ int commit_open_batch_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t*
         memcpy(out_p48, A.bpin + BR_C48 + 48 * (size_t)k, 48);
     }
     memcpy(out_evals32, A.bpin + BR_EVAL, 32 * (size_t)k);
+    H.clean = true;
+    return KZG_OK;
+}
+
+// ---- the multi-point opening (kzg_commit_open_multi): k rows f_j of worker i, m points alpha_p, point p opening the rows of
+// masks[p] with its own challenge gamma_p.
+//   INTT of each row (once) -> every masked (row, point) pair evaluated side by side (launch_poly_eval_pairs: the launches
+//   of ONE evaluation; rows past KZG_BATCHED_ROW_MAX in groups of KZG_MAX_BATCH_OPEN pairs, whose level scratch is large)
+//   -> the m combinations h_p in one launch (launch_fr_combine_points) -> their m openings side by side
+//   (launch_poly_open_points: the quotients land in m consecutive length-T scalar sets) -> the k + m MSMs over U_i, split
+//   into passes exactly as commit_open_batch_dev splits its k + 1 (one pass while the sort's key and 2^22 buckets allow).
+int commit_open_multi_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* rows_dev, uint32_t k, uint64_t T,
+                          int evaluation_form, uint32_t m, const uint8_t* points_be32, const uint32_t* masks,
+                          const uint8_t* gammas_be32, uint8_t* out_c48, uint8_t* out_evals32, uint8_t* out_p48) {
+    Lane& A = H.L();
+    hipStream_t s = A.stream;
+    HIPCHK(ctx, A.brec.ensure(MR_SIZE));
+    if (!A.bpin) {
+        uint8_t* p = nullptr;
+        HIPCHK(ctx, hipHostMalloc((void**)&p, 8192, hipHostMallocMapped | hipHostMallocCoherent));
+        A.bpin = p;
+        HIPCHK(ctx, hipHostGetDevicePointer((void**)&A.bpin_dev, A.bpin, 0));
+    }
+    const uint64_t words = T * 8;   // one row, in words
+    const uint32_t* coef = rows_dev;
+    if (evaluation_form && T > 1) {
+        HIPCHK(ctx, A.bcoef.ensure(k * T * 32));
+        for (uint32_t j = 0; j < k; j++) {
+            const uint32_t* c;
+            int rc = row_to_coeffs(ctx, A, rows_dev + j * words, T, 1, &c, A.bcoef.as<uint32_t>() + j * words);
+            if (rc) return rc;
+        }
+        coef = A.bcoef.as<uint32_t>();
+    }
+    // the pairs, point-major, ascending rows inside a point (the order of out_evals32)
+    PairArg pa;
+    memset(&pa, 0, sizeof(pa));
+    CombArg ca;
+    memset(&ca, 0, sizeof(ca));
+    uint32_t npairs = 0;
+    for (uint32_t p = 0; p < m; p++) {
+        memcpy(pa.a[p].w, points_be32 + 32 * (size_t)p, 32);
+        memcpy(ca.g[p].w, gammas_be32 + 32 * (size_t)p, 32);
+        ca.mask[p] = masks[p];
+        for (uint32_t j = 0; j < k; j++)
+            if ((masks[p] >> j) & 1u) {
+                pa.row[npairs] = (uint8_t)j;
+                pa.pt[npairs++] = (uint8_t)p;
+            }
+    }
+    uint8_t* rec = A.brec.as<uint8_t>();
+    g1_xyzz_t* res = reinterpret_cast<g1_xyzz_t*>(rec + MR_RES);
+    uint32_t* alpha_m = reinterpret_cast<uint32_t*>(rec + MR_ALPHA_M);
+    const uint64_t nchunks = (T + 3) / 4;
+    const uint64_t hrow = (nchunks + (nchunks >> 1) + 64) * 8;   // level scratch of one pair, words
+    const bool batched = T <= KZG_BATCHED_ROW_MAX;
+    const uint32_t group = batched ? npairs : std::min<uint32_t>(npairs, KZG_MAX_BATCH_OPEN);   // pairs per evaluation
+    HIPCHK(ctx, A.hbuf.ensure(std::max(group, m) * hrow * 4));
+    HIPCHK(ctx, A.hnext.ensure(std::max(group, m) * hrow * 4));
+    HIPCHK(ctx, A.bcomb.ensure(m * T * 32));
+    HIPCHK(ctx, A.qbuf.ensure(m * T * 32));
+    uint32_t* hcomb = A.bcomb.as<uint32_t>();
+    uint32_t* q = A.qbuf.as<uint32_t>();
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        for (uint32_t g0 = 0; g0 < npairs; g0 += group) {   // the points ride in as arguments of each group's first kernel
+            const uint32_t ng = std::min(group, npairs - g0);
+            PairArg ga = pa;
+            memmove(ga.row, pa.row + g0, ng);
+            memmove(ga.pt, pa.pt + g0, ng);
+            launch_poly_eval_pairs(s, coef, T, ng, ga, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), hrow,
+                                   reinterpret_cast<uint32_t*>(rec + MR_Y_M) + 8 * g0, A.flags(), rec + MR_EVAL + 32 * g0);
+        }
+        launch_fr_combine_points(s, coef, T, m, ca, hcomb, A.flags());
+        // k_poly_quotient leaves a zero in slot T - 1: each quotient rides as one more length-T scalar set
+        launch_poly_open_points(s, hcomb, T, m, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), hrow,
+                                reinterpret_cast<uint32_t*>(rec + MR_HY_M), q);
+    }
+    const uint64_t offset = (uint64_t)i * ctx->T;
+    // sets per pass: what the sort's key carries (msm_sort_max_sets), at most 2^22 buckets; long rows one set per pass
+    int per = std::min(KZG_BATCH_PASS_SETS, msm_sort_max_sets(ctx->c));
+    while (per > 2 && (uint64_t)per * ctx->nbuckets > ((uint64_t)1 << 22)) per--;
+    if (!batched) per = 1;
+    const uint32_t sets = k + m, passes = (sets + per - 1) / per;   // sets k .. k + m - 1 are the quotients
+    Lane* B = (!batched && passes > 1) ? H.second() : nullptr;
+    if (B) {
+        HIPCHK(ctx, hipEventRecord(A.ev_coeffs, s));
+        HIPCHK(ctx, hipStreamWaitEvent(B->stream, A.ev_coeffs, 0));
+    }
+    for (uint32_t p = 0; p < passes; p++) {
+        Lane& L = (B && (p & 1)) ? *B : A;
+        const uint32_t a = p * per, b = std::min(sets, a + per);
+        const uint32_t nr = std::min(b, k) - std::min(a, k);   // rows in this pass
+        const uint32_t q0 = std::max(a, k) - k, nq = b > k ? b - std::max(a, k) : 0;   // quotients in this pass
+        int rc = nr ? msm_core(ctx, L, coef + (uint64_t)a * words, 1, T, offset, res + a, nq ? q + q0 * words : nullptr, 0,
+                               (int)nr, words, (int)nq)
+                    : msm_core(ctx, L, q + q0 * words, 0, T, offset, res + a, nullptr, 0, (int)nq, words);
+        if (rc) return rc;
+    }
+    if (B) {
+        HIPCHK(ctx, hipEventRecord(B->ev_done, B->stream));
+        HIPCHK(ctx, hipStreamWaitEvent(s, B->ev_done, 0));
+    }
+    if (!ctx->host_finish) {
+        Span sp(ctx, A, KZG_T_FINAL);
+        for (uint32_t p = 0; p + 1 < sets; p += 2)
+            launch_g1_compress_pair(s, res + p, res + p + 1, rec + MR_C48 + 48 * p, rec + MR_C48 + 48 * (p + 1));
+        if (sets & 1) launch_g1_compress(s, res + sets - 1, rec + MR_C48 + 48 * (sets - 1));
+    }
+    launch_publish(s, rec, A.bpin_dev, MR_COPY);   // stream-ordered ahead of finish()'s record and its sequence word
+    int rc = finish(ctx, A);
+    if (rc) return rc;
+    if (ctx->host_finish) {
+        uint8_t enc[MR_SETS * 48];
+        kzg_host::xyzz_batch_to_c48(reinterpret_cast<const uint32_t*>(A.bpin + MR_RES), sets, enc);
+        memcpy(out_c48, enc, 48 * (size_t)k);
+        memcpy(out_p48, enc + 48 * (size_t)k, 48 * (size_t)m);
+    } else {
+        memcpy(out_c48, A.bpin + MR_C48, 48 * (size_t)k);
+        memcpy(out_p48, A.bpin + MR_C48 + 48 * (size_t)k, 48 * (size_t)m);
+    }
+    memcpy(out_evals32, A.bpin + MR_EVAL, 32 * (size_t)npairs);
     H.clean = true;
     return KZG_OK;
 }

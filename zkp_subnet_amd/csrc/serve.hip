@@ -249,6 +249,39 @@ int kzg_commit_open_batch(kzg_ctx* ctx, uint32_t i, uint32_t k, const uint8_t* r
                                  out_commitments48, out_evals32, out_proof48);
 }
 
+// k rows of worker i opened at m points, one proof per point (pipeline.hip: commit_open_multi_dev)
+int kzg_commit_open_multi(kzg_ctx* ctx, uint32_t i, uint32_t k, const uint8_t* rows_be32, uint64_t T, int evaluation_form,
+                          uint32_t m, const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32,
+                          uint8_t* out_commitments48, uint8_t* out_evals32, uint8_t* out_proofs48) {
+    if (!ctx || !rows_be32 || !points_be32 || !masks || !gammas_be32 || !out_commitments48 || !out_evals32 || !out_proofs48)
+        return KZG_E_ARG;
+    if (k == 0 || k > KZG_MAX_BATCH_OPEN) return fail(ctx, KZG_E_ARG, "multi-point opening: k must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (m == 0 || m > KZG_MAX_OPEN_POINTS)
+        return fail(ctx, KZG_E_ARG, "multi-point opening: m must be in [1, KZG_MAX_OPEN_POINTS]");
+    for (uint32_t p = 0; p < m; p++) {
+        if (masks[p] == 0 || (masks[p] >> k) != 0)
+            return fail(ctx, KZG_E_ARG, "multi-point opening: every mask must name at least one row, and rows < k only");
+        if (!fr_be32_canonical(points_be32 + 32 * (size_t)p) || !fr_be32_canonical(gammas_be32 + 32 * (size_t)p))
+            return fail(ctx, KZG_E_ARG, "multi-point opening: points and gammas must be canonical scalars (< r)");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;
+    Lane& L = H.L();
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (evaluation_form && T > 1 && ilog2_exact(T) < 0)
+        return fail(ctx, KZG_E_ARG, "evaluation-form row length must be a power of two");
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    HIPCHK(ctx, L.coeffA.ensure(k * T * 32));
+    rc = upload_fr(ctx, L, rows_be32, k * T, L.coeffA.as<uint32_t>(), 1);
+    if (rc) return rc;
+    return commit_open_multi_dev(ctx, H, i, L.coeffA.as<uint32_t>(), k, T, evaluation_form, m, points_be32, masks,
+                                 gammas_be32, out_commitments48, out_evals32, out_proofs48);
+}
+
 static int ntt_dev(kzg_ctx* ctx, Lane& L, uint32_t* data, uint64_t n, int inverse) {  // in place via coeffB
     int lg = ilog2_exact(n);
     if (lg < 0) return fail(ctx, KZG_E_ARG, "NTT length must be a power of two");

@@ -185,6 +185,14 @@ class HipEngine:
             raise NotImplementedError("no verifier key: call set_verifier_key() after load_srs()")
         return self.verifier.verify_open_batch(i, commitments48, evals32, alpha32, gamma32, proof48)
 
+    def verify_open_multi(self, i: int, commitments48: Sequence[bytes], points32: Sequence[bytes],
+                          opened: Sequence[Sequence[int]], gammas32: Sequence[bytes], evals32: Sequence[Sequence[bytes]],
+                          proofs48: Sequence[bytes]) -> bool:
+        """Pairing check of one multi-point opening (commit_open_multi) against resident slice i."""
+        if self.verifier is None:
+            raise NotImplementedError("no verifier key: call set_verifier_key() after load_srs()")
+        return self.verifier.verify_open_multi(i, commitments48, points32, opened, gammas32, evals32, proofs48)
+
     def srs_read(self, first: int, count: int, window: int = 0, compressed: bool = False) -> bytes:
         out = ctypes.create_string_buffer((48 if compressed else 96) * count)
         fn = self._lib.kzg_srs_read_compressed if compressed else self._lib.kzg_srs_read
@@ -236,6 +244,44 @@ class HipEngine:
         self._chk(self._lib.kzg_commit_open_batch(self._h, i, k, rows, T, int(evaluation_form), alpha_be32, gamma_be32,
                                                   c, ev, pf))
         return ([c.raw[48 * j:48 * j + 48] for j in range(k)], [ev.raw[32 * j:32 * j + 32] for j in range(k)], pf.raw)
+
+    def commit_open_multi(self, i: int, rows_be32: Sequence[bytes], points_be32: Sequence[bytes],
+                          opened: Sequence[Sequence[int]], gammas_be32: Sequence[bytes], evaluation_form: bool = True
+                          ) -> Tuple[List[bytes], List[List[bytes]], List[bytes]]:
+        """k rows of worker i opened at m <= 4 points (kzg_commit_open_multi): opened[p] lists the rows opened at
+        points_be32[p] (strictly increasing), gammas_be32[p] is that point's challenge.  Returns ([C_j], [[y_{j,p} for j in
+        opened[p]] for p], [pi_p]).  The points and gammas must come from the verifier after the commitments are fixed."""
+        k = len(rows_be32)
+        if k == 0 or k > _native.KZG_MAX_BATCH_OPEN:
+            raise KzgError(_native.KZG_E_ARG, f"commit_open_multi: k = {k} outside [1, {_native.KZG_MAX_BATCH_OPEN}]")
+        if len({len(r) for r in rows_be32}) != 1 or len(rows_be32[0]) % 32:
+            raise KzgError(_native.KZG_E_ARG, "commit_open_multi: rows of unequal length")
+        T = len(rows_be32[0]) // 32
+        return self._commit_open_multi(i, k, b"".join(rows_be32), T, points_be32, opened, gammas_be32, evaluation_form)
+
+    def commit_open_multi_joined(self, i: int, rows_be32: bytes, k: int, points_be32: Sequence[bytes],
+                                 opened: Sequence[Sequence[int]], gammas_be32: Sequence[bytes], evaluation_form: bool = True
+                                 ) -> Tuple[List[bytes], List[List[bytes]], List[bytes]]:
+        """commit_open_multi on rows already in the C-ABI layout (k rows of T elements, row-major, one buffer): no join."""
+        if k <= 0 or k > _native.KZG_MAX_BATCH_OPEN or len(rows_be32) % (32 * k):
+            raise KzgError(_native.KZG_E_ARG, f"commit_open_multi: {len(rows_be32)} bytes are not {k} equal rows")
+        return self._commit_open_multi(i, k, rows_be32, len(rows_be32) // (32 * k), points_be32, opened, gammas_be32,
+                                       evaluation_form)
+
+    def _commit_open_multi(self, i, k, rows, T, points_be32, opened, gammas_be32, evaluation_form):
+        masks, npairs = _native.open_masks(opened, k)
+        m = len(opened)
+        if len(points_be32) != m or len(gammas_be32) != m or any(len(x) != 32 for x in list(points_be32) + list(gammas_be32)):
+            raise KzgError(_native.KZG_E_ARG, "commit_open_multi: one 32-byte point and gamma per opened list")
+        c, ev, pf = (ctypes.create_string_buffer(48 * k), ctypes.create_string_buffer(32 * npairs),
+                     ctypes.create_string_buffer(48 * m))
+        self._chk(self._lib.kzg_commit_open_multi(self._h, i, k, rows, T, int(evaluation_form), m, b"".join(points_be32),
+                                                  masks, b"".join(gammas_be32), c, ev, pf))
+        evals, t = [], 0
+        for rws in opened:
+            evals.append([ev.raw[32 * (t + u):32 * (t + u) + 32] for u in range(len(rws))])
+            t += len(rws)
+        return [c.raw[48 * j:48 * j + 48] for j in range(k)], evals, [pf.raw[48 * p:48 * p + 48] for p in range(m)]
 
     # ---- the same three calls fed from the synapse's List[str] (reference neurons/miner.py:38-61): the text is decoded
     # by csrc/wire_py.c straight into the library's pinned staging buffer (no bytes object, no pageable bounce)
@@ -332,6 +378,36 @@ class HipEngine:
                     raise codec.CodecError(str(e)) from e
                 assert got == T
             return self._commit_open_batch(i, k, ctypes.cast(ptr, ctypes.c_char_p), T, alpha_be32, gamma_be32,
+                                           evaluation_form)
+        finally:
+            self._lib.kzg_staging_release(self._h, tok.value)
+
+    def commit_open_multi_list(self, i: int, polys: Sequence[Sequence[str]], points_be32: Sequence[bytes],
+                               opened: Sequence[Sequence[int]], gammas_be32: Sequence[bytes], evaluation_form: bool = True
+                               ) -> Tuple[List[bytes], List[List[bytes]], List[bytes]]:
+        """commit_open_multi fed from the synapse's text rows: decoded by csrc/wire_py.c straight into ONE pinned staging
+        buffer, row j at offset 32 T j (as commit_open_batch_list)."""
+        from . import codec
+
+        if codec._wire is None:
+            raise RuntimeError("zkp_subnet_amd._wire is not built: run `python -m zkp_subnet_amd.build`")
+        k = len(polys)
+        if k == 0 or k > _native.KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"commit_open_multi: k = {k} outside [1, {_native.KZG_MAX_BATCH_OPEN}]")
+        T = len(polys[0])
+        if any(len(p) != T for p in polys):
+            raise codec.CodecError("commit_open_multi: rows of unequal length")
+        cap = 32 * max(k * T, 1)
+        ptr, tok = ctypes.c_void_p(), ctypes.c_int(-1)
+        self._chk(self._lib.kzg_staging_acquire(self._h, cap, ctypes.byref(ptr), ctypes.byref(tok)))
+        try:
+            for j, p in enumerate(polys):
+                try:
+                    got = codec._wire.decode_fr_list_into(p, ptr.value + 32 * T * j, cap - 32 * T * j)
+                except ValueError as e:
+                    raise codec.CodecError(str(e)) from e
+                assert got == T
+            return self._commit_open_multi(i, k, ctypes.cast(ptr, ctypes.c_char_p), T, points_be32, opened, gammas_be32,
                                            evaluation_form)
         finally:
             self._lib.kzg_staging_release(self._h, tok.value)

@@ -101,6 +101,9 @@ class MultiDeviceClient:
     def worker_commit_open_batch(self, i: int, polys: Sequence[Sequence[str]], x: str, gamma: str):
         return self._for(i).worker_commit_open_batch(i, polys, x, gamma)
 
+    def worker_commit_open_multi(self, i: int, polys: Sequence[Sequence[str]], points: Sequence[str], opened, gammas):
+        return self._for(i).worker_commit_open_multi(i, polys, points, opened, gammas)
+
     def commit_and_open_rows(self, indices: Sequence[int], polys: Sequence[Sequence[str]], x: str) -> List[Response]:
         """Pianist rows of one challenge, all devices at once: row k runs on the device of indices[k]; responses in input
         order.  Host threads only (ctypes releases the GIL inside every call); nothing is exchanged between devices."""
@@ -116,6 +119,9 @@ class MultiDeviceClient:
 
     def worker_verify_open_batch(self, i: int, proof: str, alpha: str, gamma: str, evals, commitments):
         return self._for(i).worker_verify_open_batch(i, proof, alpha, gamma, evals, commitments)
+
+    def worker_verify_open_multi(self, i: int, proofs, points, opened, gammas, evals, commitments):
+        return self._for(i).worker_verify_open_multi(i, proofs, points, opened, gammas, evals, commitments)
 
     def worker_verify_batch(self, indices, proofs, alpha, evals, commitments, threads: int = 16):
         """One batched check PER DEVICE, verdicts AND-ed: with a synthetic setup each context holds the slices and

@@ -90,6 +90,32 @@ class Verifier:
             raise KzgError(rc, "kzg_vk_verify_open_batch: bad argument (k, index or non-canonical scalar)")
         return bool(ok.value)
 
+    def verify_open_multi(self, i: int, commitments48: Sequence[bytes], points32: Sequence[bytes],
+                          opened: Sequence[Sequence[int]], gammas32: Sequence[bytes], evals32: Sequence[Sequence[bytes]],
+                          proofs48: Sequence[bytes]) -> bool:
+        """One multi-point opening of k rows of slice i (kzg_vk_verify_open_multi): opened[p] lists the rows opened at
+        points32[p] (increasing), evals32[p] their evaluations there, proofs48[p] that point's proof; for every p
+        e(sum_t gamma_p^t C_{j_t} - (sum_t gamma_p^t y_{j_t,p}) L_i, [1]_2) == e(pi_p, [tau_x - alpha_p]_2)."""
+        k, m = len(commitments48), len(opened)
+        if not (m == len(points32) == len(gammas32) == len(evals32) == len(proofs48)):
+            raise ValueError("verify_open_multi: one point, gamma, evaluation list and proof per opened list")
+        if any(len(e) != len(r) for e, r in zip(evals32, opened)):
+            raise ValueError("verify_open_multi: one evaluation per opened row")
+        if k == 0 or k > _native.KZG_MAX_BATCH_OPEN:
+            raise KzgError(_native.KZG_E_ARG, f"kzg_vk_verify_open_multi: k = {k} outside [1, {_native.KZG_MAX_BATCH_OPEN}]")
+        masks, _ = _native.open_masks(opened, k)
+        flat = [e for ev in evals32 for e in ev]
+        if any(len(x) != 32 for x in list(points32) + list(gammas32) + flat):
+            raise KzgError(_native.KZG_E_ARG, "kzg_vk_verify_open_multi: points / gammas / evals must be 32 bytes each")
+        if any(len(c) != 48 for c in list(commitments48) + list(proofs48)):
+            return False
+        ok = ctypes.c_int(0)
+        rc = self._lib.kzg_vk_verify_open_multi(self._h, i, k, b"".join(commitments48), m, b"".join(points32), masks,
+                                                b"".join(gammas32), b"".join(flat), b"".join(proofs48), ctypes.byref(ok))
+        if rc != 0:
+            raise KzgError(rc, "kzg_vk_verify_open_multi: bad argument (k, m, mask, index or non-canonical scalar)")
+        return bool(ok.value)
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._lib.kzg_vk_destroy(self._h)
