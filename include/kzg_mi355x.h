@@ -157,6 +157,35 @@ int kzg_commit_open_multi(kzg_ctx* ctx, uint32_t i, uint32_t k, const uint8_t* r
                           int evaluation_form, uint32_t m, const uint8_t* points_be32 /* m*32 */, const uint32_t* masks /* m */,
                           const uint8_t* gammas_be32 /* m*32 */, uint8_t* out_commitments48 /* k*48 */,
                           uint8_t* out_evals32 /* sum popcount(masks)*32 */, uint8_t* out_proofs48 /* m*48 */);
+/* Committed row sets: commit k rows once, open them later -- the shape of a Fiat-Shamir prover, whose challenges are hashes
+ * of commitments it has already published (commit the wire rows; derive a challenge, commit the accumulator; derive one,
+ * commit the quotient pieces; derive zeta, open everything at zeta and the accumulator also at zeta * omega).
+ * kzg_rows_commit: k in [1, KZG_MAX_BATCH_OPEN] rows of worker i, with the argument checks of kzg_commit_open_batch (each a
+ * KZG_E_ARG).  out_commitments48[j] == kzg_commit(i, row j) byte for byte.  The set keeps the k coefficient rows on the
+ * device under *out_handle (it remembers i and T).  More than KZG_MAX_ROW_SETS live sets: KZG_E_BUSY; a failed device
+ * allocation: KZG_E_NOMEM.
+ * kzg_rows_open: the rows of the n_handles sets, numbered by concatenating the sets' rows in the order of `handles` (a handle
+ * may appear more than once; at most KZG_MAX_BATCH_OPEN rows in all), opened at m points under the rules of
+ * kzg_commit_open_multi over those rows.  out_evals32 (its point-major layout) and out_proofs48 equal what
+ * kzg_commit_open_multi writes for the concatenated rows, byte for byte, so kzg_vk_verify_open_multi checks them against the
+ * concatenated commitments.  No upload, no INTT, no commitment MSM.  Sets of different workers or lengths, an unknown or
+ * released handle and a set made stale by an SRS (re)load give KZG_E_ARG.  A set can be opened any number of times, also by
+ * concurrent threads.
+ * kzg_rows_release: frees the set; its handle then gives KZG_E_ARG to an open and to a second release.  Handles are never
+ * reused within the process.  A release racing an open of the same set is safe: the open finishes with correct bytes and
+ * the memory is reclaimed after it.  Any kzg_load_srs* / kzg_gen_srs makes every live set stale (its commitments belong to
+ * the old SRS); its release still succeeds.  kzg_destroy frees every set.  After any error the context keeps serving.
+ * kzg_rows_stats: out[0] live sets (stale ones included until released), out[1] the device bytes their rows hold.
+ * SOUNDNESS: with sets the caller can fix and hash the commitments BEFORE it draws the points and gammas of the open, as
+ * kzg_commit_open_batch / _multi require; the library still derives no challenge. */
+#define KZG_MAX_ROW_SETS 64   /* live sets per context */
+int kzg_rows_commit(kzg_ctx* ctx, uint32_t i, uint32_t k, const uint8_t* rows_be32 /* k*T*32 */, uint64_t T,
+                    int evaluation_form, uint8_t* out_commitments48 /* k*48 */, uint64_t* out_handle);
+int kzg_rows_open(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t m, const uint8_t* points_be32 /* m*32 */,
+                  const uint32_t* masks /* m */, const uint8_t* gammas_be32 /* m*32 */,
+                  uint8_t* out_evals32 /* sum popcount(masks)*32 */, uint8_t* out_proofs48 /* m*48 */);
+int kzg_rows_release(kzg_ctx* ctx, uint64_t handle);
+int kzg_rows_stats(kzg_ctx* ctx, uint64_t out_live_sets_bytes[2]);
 /* The UNCHANGED reference miner makes two calls per request with the same row -- worker_commit(i, poly), then
  * worker_open(i, poly, x) (neurons/miner.py:56-61).  These forms take a 128-bit content tag identifying the row's bytes
  * (the host codec computes it while decoding the text); the coefficient vectors of the last four rows stay on the
@@ -351,6 +380,14 @@ int kzg_multi_commit_open_multi(kzg_multi* mh, uint32_t i, uint32_t k, const uin
                                 int evaluation_form, uint32_t m, const uint8_t* points_be32, const uint32_t* masks,
                                 const uint8_t* gammas_be32, uint8_t* out_commitments48, uint8_t* out_evals32,
                                 uint8_t* out_proofs48);
+/* committed row sets on the device of worker i (routed like kzg_multi_commit_open): every set named in an open or a release
+ * must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit(kzg_multi* mh, uint32_t i, uint32_t k, const uint8_t* rows_be32, uint64_t T, int evaluation_form,
+                          uint8_t* out_commitments48, uint64_t* out_handle);
+int kzg_multi_rows_open(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
+                        const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
+                        uint8_t* out_proofs48);
+int kzg_multi_rows_release(kzg_multi* mh, uint32_t i, uint64_t handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("KZG_MI355X_LIB") or os.path.join(HERE, "libkzg_mi355x
 
 KZG_MAX_BATCH_OPEN = 16   # include/kzg_mi355x.h
 KZG_MAX_OPEN_POINTS = 4
+KZG_MAX_ROW_SETS = 64
 KZG_OK, KZG_E_ARG, KZG_E_SCALAR, KZG_E_POINT, KZG_E_HIP, KZG_E_NOMEM, KZG_E_BUSY, KZG_E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
 STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_SCALAR", -3: "E_POINT", -4: "E_HIP", -5: "E_NOMEM", -6: "E_BUSY", -7: "E_COMM"}
 TIMING_NAMES = ["decode", "ntt", "digits", "scan", "scatter", "accumulate", "fixup", "tree", "final", "poly", "total", "collective"]
@@ -52,6 +53,10 @@ SYMBOLS = {
     "kzg_commit_open": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B, _B]),
     "kzg_commit_open_batch": (_I, [_P, _U32, _U32, _B, _U64, _I, _B, _B, _B, _B, _B]),
     "kzg_commit_open_multi": (_I, [_P, _U32, _U32, _B, _U64, _I, _U32, _B, ctypes.POINTER(_U32), _B, _B, _B, _B]),
+    "kzg_rows_commit": (_I, [_P, _U32, _U32, _B, _U64, _I, _B, ctypes.POINTER(_U64)]),
+    "kzg_rows_open": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _B, ctypes.POINTER(_U32), _B, _B, _B]),
+    "kzg_rows_release": (_I, [_P, _U64]),
+    "kzg_rows_stats": (_I, [_P, ctypes.POINTER(_U64)]),
     "kzg_commit_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B]),
     "kzg_open_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B, _B]),
     "kzg_row_cache_stats": (_I, [_P, ctypes.POINTER(_U64)]),
@@ -103,6 +108,9 @@ SYMBOLS = {
     "kzg_multi_commit_open": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B, _B]),
     "kzg_multi_commit_open_batch": (_I, [_P, _U32, _U32, _B, _U64, _I, _B, _B, _B, _B, _B]),
     "kzg_multi_commit_open_multi": (_I, [_P, _U32, _U32, _B, _U64, _I, _U32, _B, ctypes.POINTER(_U32), _B, _B, _B, _B]),
+    "kzg_multi_rows_commit": (_I, [_P, _U32, _U32, _B, _U64, _I, _B, ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_open": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _B, ctypes.POINTER(_U32), _B, _B, _B]),
+    "kzg_multi_rows_release": (_I, [_P, _U32, _U64]),
     "kzg_multi_commit_open_rows": (_I, [_P, _U32, ctypes.POINTER(_U32), _B, _U64, _I, _B, _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_upload_fr": (_I, [_P, _I, _B, _U64, _I]),
     "kzg_msm_resident": (_I, [_P, _I, _U64, _U64, _B]),

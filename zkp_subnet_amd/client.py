@@ -18,7 +18,7 @@ import secrets
 from typing import Any, Dict, List, Optional, Sequence
 
 from . import codec
-from ._native import KZG_E_ARG, KZG_E_POINT, KZG_E_SCALAR, KZG_MAX_BATCH_OPEN, KZG_MAX_OPEN_POINTS, KzgError
+from ._native import KZG_E_ARG, KZG_E_POINT, KZG_E_SCALAR, KZG_MAX_BATCH_OPEN, KZG_MAX_OPEN_POINTS, KzgError, open_masks
 
 R_MODULUS = codec.R_MODULUS
 log = logging.getLogger("zkp_subnet_amd.client")
@@ -63,6 +63,17 @@ def _guard(fn):
     wrapped.__name__ = fn.__name__
     wrapped.__doc__ = fn.__doc__
     return wrapped
+
+
+def _handles(handles) -> List[int]:
+    """committed-row-set handles from a request: 1 .. 16 non-negative integers"""
+    try:
+        hs = [int(h) for h in handles]
+    except (TypeError, ValueError) as e:
+        raise codec.CodecError(f"row-set handles must be integers: {e}") from e
+    if not 1 <= len(hs) <= KZG_MAX_BATCH_OPEN or any(h < 0 or h >= 1 << 64 for h in hs):
+        raise codec.CodecError(f"{len(hs)} row-set handles, expected 1 .. {KZG_MAX_BATCH_OPEN} values in [0, 2^64)")
+    return hs
 
 
 class Client:
@@ -244,6 +255,41 @@ class Client:
             self.engine.commit_open_multi(self._slice(i), [codec.fr_list_to_be32(p) for p in polys], a, opened, g, True)
         return {"commitments": [codec.g1_to_b64(c) for c in cs], "evals": [[codec.be32_to_fr(e) for e in ev] for ev in evs],
                 "proofs": [codec.g1_to_b64(pf) for pf in pfs]}
+
+    @_guard
+    def worker_commit_rows(self, i: int, polys: Sequence[Sequence[str]]):
+        """Extension: k <= 16 rows of worker i committed and kept on the device as one committed row set.  Returns the set's
+        handle and the k commitments; worker_open_rows opens the set later, after the caller has fixed (and hashed) the
+        commitments, and worker_release_rows frees it."""
+        k = len(polys)
+        if k == 0 or k > KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"worker_commit_rows: {k} rows, expected 1 .. {KZG_MAX_BATCH_OPEN}")
+        if any(len(p) != len(polys[0]) for p in polys):
+            raise codec.CodecError("worker_commit_rows: rows of unequal length")
+        rs = self.engine.commit_rows(self._slice(i), [codec.fr_list_to_be32(p) for p in polys], True)
+        return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments]}
+
+    @_guard
+    def worker_open_rows(self, handles: Sequence[int], points: Sequence[str], opened: Sequence[Sequence[int]],
+                         gammas: Sequence[str]):
+        """Extension: the rows of committed sets (numbered by concatenating the sets' rows in the order of `handles`)
+        opened at m <= 4 points, one proof per point for sum_t gamma_p^t f_{j_t} over opened[p].  Equal to
+        worker_commit_open_multi on the concatenated rows; worker_verify_open_multi checks it against the concatenated
+        commitments."""
+        hs = _handles(handles)
+        m = len(points)
+        if m == 0 or m > KZG_MAX_OPEN_POINTS or len(opened) != m or len(gammas) != m:
+            raise codec.CodecError(f"worker_open_rows: {m} points, {len(opened)} row lists, {len(gammas)} gammas")
+        open_masks(opened, KZG_MAX_BATCH_OPEN)   # the shape of `opened`; the engine checks it against the sets' rows
+        a, g = [codec.fr_to_be32(x) for x in points], [codec.fr_to_be32(x) for x in gammas]
+        evs, pfs = self.engine.open_rows(hs, a, opened, g)
+        return {"evals": [[codec.be32_to_fr(e) for e in ev] for ev in evs], "proofs": [codec.g1_to_b64(pf) for pf in pfs]}
+
+    @_guard
+    def worker_release_rows(self, handle: int):
+        """Extension: frees a committed row set."""
+        self.engine.release_rows(_handles([handle])[0])
+        return {"released": True}
 
     @_guard
     def aggregate_commitments(self, commitments: Sequence[str]):

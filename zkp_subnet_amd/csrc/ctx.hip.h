@@ -251,6 +251,23 @@ struct kzg_ctx {
         kzg_impl::DevBuf coef;
         kzg_impl::DevBuf raw;        // the row's 32-byte big-endian elements as they were uploaded: what a hit is verified against
     } rcache[N_LANES];
+    // committed row sets (kzg_rows_commit / kzg_rows_open / kzg_rows_release; serve.hip).  A set keeps the coefficients of
+    // its k rows in its own buffer.  `refs` counts the running opens that read it: a release under an open only unlinks the
+    // handle, and the buffer goes to `sets_free` when the last such open ends.  Released buffers are kept and reused by
+    // capacity (no hipFree on the request path while other lanes run); the free list is trimmed by an SRS (re)load, which
+    // holds every lane and also frees the buffers of the sets it makes stale.
+    struct RowSet {
+        uint32_t i = 0, k = 0;
+        uint64_t T = 0;
+        kzg_impl::DevBuf buf;        // k x T Montgomery coefficients, row-major (empty once stale)
+        int refs = 0;
+        bool stale = false;          // committed under an SRS that has since been replaced
+        bool released = false;       // handle unlinked; the buffer waits for refs == 0
+    };
+    std::mutex sets_mu;              // guards everything below
+    std::map<uint64_t, RowSet> sets; // by handle: live sets, and released ones that an open still reads
+    uint32_t sets_pending = 0;       // commits between their reservation and their insertion (count against the cap)
+    std::vector<kzg_impl::DevBuf> sets_free;
 };
 
 namespace kzg_impl {
@@ -373,6 +390,20 @@ int commit_open_batch_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t*
 int commit_open_multi_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* rows_dev, uint32_t k, uint64_t T,
                           int evaluation_form, uint32_t m, const uint8_t* points_be32, const uint32_t* masks,
                           const uint8_t* gammas_be32, uint8_t* out_c48, uint8_t* out_evals32, uint8_t* out_p48);
+
+// committed row sets: the commit's INTT into the set's buffer dst and its k MSMs; the open of rows read through rt
+int rows_commit_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* rows_dev, uint32_t k, uint64_t T,
+                    int evaluation_form, uint32_t* dst, uint8_t* out_c48);
+int rows_open_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t k, uint64_t T, uint32_t m,
+                  const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
+                  uint8_t* out_p48);
+// an SRS (re)load is installing a new table (every lane held): marks every live set stale, frees its buffer and the free list
+void rows_invalidate(kzg_ctx* ctx);
+// kzg_rows_open with the extra condition that every set belongs to worker `expect_i` (UINT32_MAX: any; kzg_multi_rows_open)
+int rows_open_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
+                   const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
+                   uint8_t* out_proofs48);
+int rows_release_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle);
 
 // ---- the collective (comm.hip)
 void comm_teardown(kzg_ctx* ctx);

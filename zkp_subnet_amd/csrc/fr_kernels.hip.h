@@ -46,24 +46,30 @@ struct PairArg {
     FrArg a[POLY_MAX_POINTS];
     uint8_t row[POLY_MAX_PAIRS], pt[POLY_MAX_PAIRS];
 };
-// y_t = f_{row[t]}(alpha_{pt[t]}) for `npairs` pairs over rows of n Montgomery coefficients at a stride of n elements, in
-// the launches of ONE evaluation.  alpha_mont: POLY_MAX_POINTS x 8 words, each point's Montgomery form is left there (*bad
+// where the opened rows live: row j's n Montgomery coefficients start at r[j] (a kernel argument beside PairArg / CombArg).
+// kzg_commit_open_multi fills it with its strided rows, kzg_rows_open with rows of its committed sets, wherever they lie.
+#define POLY_MAX_ROWS 16
+struct RowTab {
+    const uint32_t* r[POLY_MAX_ROWS];
+};
+// y_t = f_{row[t]}(alpha_{pt[t]}) for `npairs` pairs over rows of n Montgomery coefficients (row j at rt.r[j]), in the
+// launches of ONE evaluation.  alpha_mont: POLY_MAX_POINTS x 8 words, each point's Montgomery form is left there (*bad
 // raised for a point >= r); h, hnext: npairs x h_row_words words each (as launch_poly_eval_rows); y_mont: npairs x 8 words;
 // y_be: npairs x 32 bytes
-void launch_poly_eval_pairs(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t npairs, const PairArg& pa,
+void launch_poly_eval_pairs(hipStream_t s, const RowTab& rt, uint64_t n, uint32_t npairs, const PairArg& pa,
                             uint32_t* alpha_mont, uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont,
                             uint32_t* bad, uint8_t* y_be);
 // m openings side by side: f_p = f_mont + p * n elements at the point alpha_mont + 8 p (Montgomery, already in memory):
 // y_p at y_mont + 8 p and the n-1 canonical quotient coefficients (slot n - 1 zero) at q_canon + p * n elements
 void launch_poly_open_points(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t m, const uint32_t* alpha_mont,
                              uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont, uint32_t* q_canon);
-// h_p[t] = sum gamma_p^j rows[j * n + t] over the rows j of mask[p] (Montgomery in and out) into out + p * n elements, for
+// h_p[t] = sum gamma_p^j rt.r[j][t] over the rows j of mask[p] (Montgomery in and out) into out + p * n elements, for
 // p < m in one launch; g[p]: gamma_p's 32 big-endian bytes, *bad raised when one is >= r
 struct CombArg {
     FrArg g[POLY_MAX_POINTS];
     uint32_t mask[POLY_MAX_POINTS];
 };
-void launch_fr_combine_points(hipStream_t s, const uint32_t* rows_mont, uint64_t n, uint32_t m, const CombArg& ca,
+void launch_fr_combine_points(hipStream_t s, const RowTab& rt, uint64_t n, uint32_t m, const CombArg& ca,
                               uint32_t* out_mont, uint32_t* bad);
 // *flag |= 1 when a[0, n_words) and b[0, n_words) differ (n_words a multiple of 4): verification of a row-cache hit
 void launch_words_differ(hipStream_t s, const uint32_t* a, const uint32_t* b, uint64_t n_words, uint32_t* flag);

@@ -215,18 +215,19 @@ __global__ void __launch_bounds__(256) k_poly_quotient(const uint32_t* __restric
     poly_quotient(f, n, lchunk, alpha_mont, hnext, q_canon);
 }
 
-// ---- the multi-point opening (kzg_commit_open_multi): grid row y is a PAIR -- row pa.row[y] at point pa.pt[y] -- with
-// its own level arrays at + y * h_rs words.  The first kernel of the evaluations (ARG) converts the pair's point from the
-// kernel argument pa.a[pt] and the point's first pair publishes its Montgomery form at alpha_mont + 8 pt (raising *bad for
-// a value >= r); every later kernel reads it from there.  The openings of the m combinations run as pairs (p, p): their
-// level-0 input is f + y * f_rs.  Same bodies as the kernels above: the same arithmetic, bit for bit.
+// ---- the multi-point opening (kzg_commit_open_multi, kzg_rows_open): grid row y is a PAIR -- row pa.row[y] at point
+// pa.pt[y] -- with its own level arrays at + y * h_rs words.  The first kernel of the evaluations (ARG) reads the pair's row
+// through the table rt (the row need not lie next to the others) and converts the pair's point from the kernel argument
+// pa.a[pt]; the point's first pair publishes its Montgomery form at alpha_mont + 8 pt (raising *bad for a value >= r); every
+// later kernel reads it from there.  The openings of the m combinations run as pairs (p, p): their level-0 input is
+// f + y * f_rs.  Same bodies as the kernels above: the same arithmetic, bit for bit.
 template <bool ARG>
 __global__ void __launch_bounds__(256) k_poly_pairs_eval(const uint32_t* __restrict__ f, uint64_t n, int lchunk,
                                                           uint32_t* __restrict__ alpha_mont, int sq, uint32_t* __restrict__ h,
                                                           const PairArg pa, uint32_t* __restrict__ bad, uint64_t f_rs,
-                                                          uint64_t h_rs) {
+                                                          uint64_t h_rs, const RowTab rt) {
     const uint32_t y = blockIdx.y, p = pa.pt[y];
-    poly_chunk_eval<ARG>(f + (ARG ? pa.row[y] : y) * f_rs, n, lchunk, alpha_mont + 8 * p, sq, h + y * h_rs, pa.a[p],
+    poly_chunk_eval<ARG>(ARG ? rt.r[pa.row[y]] : f + y * f_rs, n, lchunk, alpha_mont + 8 * p, sq, h + y * h_rs, pa.a[p],
                          y == 0 || pa.pt[y - 1] != p, alpha_mont + 8 * p, bad);
 }
 template <uint32_t NT_>
@@ -289,8 +290,8 @@ void launch_fr_combine_rows(hipStream_t s, const uint32_t* rows_mont, uint64_t n
 
 // ---- the multi-point opening's combinations: grid row p computes h_p[t] = sum_t' gamma_p^t' c_{j_t'}[t] over the rows j of
 // ca.mask[p] (Horner from the highest one, as k_fr_combine_rows: one point with the full mask is its h, bit for bit) into
-// out + p * n elements.  Point p's first lane raises *bad for a gamma_p >= r.
-__global__ void __launch_bounds__(256) k_fr_combine_points(const uint32_t* __restrict__ rows, uint64_t n, const CombArg ca,
+// out + p * n elements; row j is read at rt.r[j].  Point p's first lane raises *bad for a gamma_p >= r.
+__global__ void __launch_bounds__(256) k_fr_combine_points(const RowTab rt, uint64_t n, const CombArg ca,
                                                             uint32_t* __restrict__ out, uint32_t* __restrict__ bad) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t p = blockIdx.y, mask = ca.mask[p];
@@ -303,19 +304,19 @@ __global__ void __launch_bounds__(256) k_fr_combine_points(const uint32_t* __res
     fr9_from_words(g, w);
     fr9_to_mont(g, g);
     int j = 31 - __clz(mask);
-    fr9_load(s, rows + 8 * ((uint64_t)j * n + t));
+    fr9_load(s, rt.r[j] + 8 * t);
     while (--j >= 0) {
         if (!((mask >> j) & 1u)) continue;
-        fr9_load(c, rows + 8 * ((uint64_t)j * n + t));
+        fr9_load(c, rt.r[j] + 8 * t);
         fr9_mul(s, s, g);
         fr9_add(s, s, c);
     }
     fr9_reduce(s, s);
     fr9_store(out + 8 * ((uint64_t)p * n + t), s);
 }
-void launch_fr_combine_points(hipStream_t s, const uint32_t* rows_mont, uint64_t n, uint32_t m, const CombArg& ca,
+void launch_fr_combine_points(hipStream_t s, const RowTab& rt, uint64_t n, uint32_t m, const CombArg& ca,
                               uint32_t* out_mont, uint32_t* bad) {
-    if (n && m) k_fr_combine_points<<<dim3(nblk(n, 256), m), 256, 0, s>>>(rows_mont, n, ca, out_mont, bad);
+    if (n && m) k_fr_combine_points<<<dim3(nblk(n, 256), m), 256, 0, s>>>(rt, n, ca, out_mont, bad);
 }
 
 // ---- long rows (16 coefficients per lane): the quotient (and, as an A/B form, the level-0 fold) with the coefficients
@@ -437,10 +438,13 @@ struct PolyLevels {
     uint64_t n[16], off[16];
 };
 // pa given (the multi-point opening): the rows are pairs, each at its own point (k_poly_pairs_*); ARG then stands for
-// alpha_be32_host != null, the points coming from pa.a
+// alpha_be32_host != null, the points coming from pa.a and the pairs' rows from the table *rt (f_mont unused)
 static void poly_up(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t rows, uint32_t* alpha_mont, uint32_t* h,
                     uint32_t* hnext, uint64_t h_rs, uint32_t* y_mont, const uint8_t* alpha_be32_host, uint32_t* bad,
-                    uint8_t* y_be_or_null, PolyLevels& lv, const PairArg* pa = nullptr) {
+                    uint8_t* y_be_or_null, PolyLevels& lv, const PairArg* pa = nullptr, const RowTab* rt = nullptr) {
+    RowTab none;
+    memset(&none, 0, sizeof(none));
+    const RowTab& tab = rt ? *rt : none;
     FrArg arg;
     memset(&arg, 0, sizeof(arg));
     if (alpha_be32_host) memcpy(arg.w, alpha_be32_host, 32);
@@ -457,10 +461,10 @@ static void poly_up(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t 
     if (pa) {
         if (alpha_be32_host)
             k_poly_pairs_eval<true><<<dim3(nblk(lv_n[1], 256), rows), 256, 0, s>>>(f_mont, n, l0, alpha_mont, 0, h, *pa, bad,
-                                                                               n * 8, h_rs);
+                                                                               n * 8, h_rs, tab);
         else
             k_poly_pairs_eval<false><<<dim3(nblk(lv_n[1], 256), rows), 256, 0, s>>>(f_mont, n, l0, alpha_mont, 0, h, *pa,
-                                                                                nullptr, n * 8, h_rs);
+                                                                                nullptr, n * 8, h_rs, tab);
     } else if (alpha_be32_host)
         k_poly_chunk_eval<true><<<dim3(nblk(lv_n[1], 256), rows), 256, 0, s>>>(f_mont, n, l0, alpha_mont, 0, h, arg, alpha_mont,
                                                                            bad, f_rs, h_rs);
@@ -475,7 +479,7 @@ static void poly_up(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t 
         if (pa)
             k_poly_pairs_eval<false><<<dim3(nblk(lv_n[K + 1], 256), rows), 256, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lup,
                                                                                     alpha_mont, lv_sq[K], h + 8 * lv_off[K + 1],
-                                                                                    *pa, nullptr, h_rs, h_rs);
+                                                                                    *pa, nullptr, h_rs, h_rs, tab);
         else
             k_poly_chunk_eval<false><<<dim3(nblk(lv_n[K + 1], 256), rows), 256, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lup,
                                                                                     alpha_mont, lv_sq[K], h + 8 * lv_off[K + 1],
@@ -530,13 +534,13 @@ void launch_poly_eval_rows(hipStream_t s, const uint32_t* f_mont, uint64_t n, ui
     if (n && rows) poly_up(s, f_mont, n, rows, alpha_mont, h, hnext, h_row_words, y_mont, alpha_be32_host, bad, y_be, lv);
 }
 
-void launch_poly_eval_pairs(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t npairs, const PairArg& pa,
+void launch_poly_eval_pairs(hipStream_t s, const RowTab& rt, uint64_t n, uint32_t npairs, const PairArg& pa,
                             uint32_t* alpha_mont, uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont,
                             uint32_t* bad, uint8_t* y_be) {
     static const uint8_t ARG_MARK[32] = {};   // (non-null: the first kernel converts the points of pa.a)
     PolyLevels lv;
     if (n && npairs)
-        poly_up(s, f_mont, n, npairs, alpha_mont, h, hnext, h_row_words, y_mont, ARG_MARK, bad, y_be, lv, &pa);
+        poly_up(s, nullptr, n, npairs, alpha_mont, h, hnext, h_row_words, y_mont, ARG_MARK, bad, y_be, lv, &pa, &rt);
 }
 // the levels go up with the pair kernels (pair p = combination p at point p), then back down as in launch_poly_open with
 // grid y = point; long rows' LDS-staged quotient runs once per point

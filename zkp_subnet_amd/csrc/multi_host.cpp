@@ -20,6 +20,15 @@
 
 #include "../../include/kzg_mi355x.h"
 
+// the one exception to the public C-ABI: an open / release of committed row sets that also checks the sets' worker
+// (serve.hip; the public forms accept sets of any one worker)
+namespace kzg_impl {
+int rows_open_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
+                   const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
+                   uint8_t* out_proofs48);
+int rows_release_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle);
+}  // namespace kzg_impl
+
 namespace {
 enum Layout { LAYOUT_NONE = 0, LAYOUT_ROWS_WHOLE, LAYOUT_ROWS_SLICED, LAYOUT_SEGMENTS };
 struct SlotRange {      // what kzg_multi_upload_fr left on the devices: scalars of global points [offset, offset + n)
@@ -380,6 +389,28 @@ int kzg_multi_commit_open_multi(kzg_multi* mh, uint32_t i, uint32_t k, const uin
     if (int rc = route(mh, i, &c, &s)) return rc;
     return relay(c, kzg_commit_open_multi(c, s, k, rows_be32, T, evaluation_form, m, points_be32, masks, gammas_be32,
                                           out_commitments48, out_evals32, out_proofs48));
+}
+int kzg_multi_rows_commit(kzg_multi* mh, uint32_t i, uint32_t k, const uint8_t* rows_be32, uint64_t T, int evaluation_form,
+                          uint8_t* out_commitments48, uint64_t* out_handle) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_rows_commit(c, s, k, rows_be32, T, evaluation_form, out_commitments48, out_handle));
+}
+int kzg_multi_rows_open(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
+                        const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
+                        uint8_t* out_proofs48) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_open_impl(c, s, n_handles, handles, m, points_be32, masks, gammas_be32, out_evals32,
+                                             out_proofs48));
+}
+int kzg_multi_rows_release(kzg_multi* mh, uint32_t i, uint64_t handle) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_release_impl(c, s, handle));
 }
 
 int kzg_multi_create(int device_count, const int* device_ids, kzg_multi** out) {

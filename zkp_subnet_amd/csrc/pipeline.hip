@@ -486,11 +486,11 @@ int commit_open_batch_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t*
 //   -> the m combinations h_p in one launch (launch_fr_combine_points) -> their m openings side by side
 //   (launch_poly_open_points: the quotients land in m consecutive length-T scalar sets) -> the k + m MSMs over U_i, split
 //   into passes exactly as commit_open_batch_dev splits its k + 1 (one pass while the sort's key and 2^22 buckets allow).
-int commit_open_multi_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* rows_dev, uint32_t k, uint64_t T,
-                          int evaluation_form, uint32_t m, const uint8_t* points_be32, const uint32_t* masks,
-                          const uint8_t* gammas_be32, uint8_t* out_c48, uint8_t* out_evals32, uint8_t* out_p48) {
-    Lane& A = H.L();
-    hipStream_t s = A.stream;
+// The committed row sets (kzg_rows_commit / kzg_rows_open) run the two halves of the same sequence: the commit its INTT and
+// k MSMs, the open its pairs, combinations, quotients and m MSMs, reading the rows through the same table of row pointers.
+
+// the multi-row record (MR_*) and its pinned page, allocated by the first multi-row call on the lane
+static int ensure_multi_record(kzg_ctx* ctx, Lane& A) {
     HIPCHK(ctx, A.brec.ensure(MR_SIZE));
     if (!A.bpin) {
         uint8_t* p = nullptr;
@@ -498,17 +498,13 @@ int commit_open_multi_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t*
         A.bpin = p;
         HIPCHK(ctx, hipHostGetDevicePointer((void**)&A.bpin_dev, A.bpin, 0));
     }
-    const uint64_t words = T * 8;   // one row, in words
-    const uint32_t* coef = rows_dev;
-    if (evaluation_form && T > 1) {
-        HIPCHK(ctx, A.bcoef.ensure(k * T * 32));
-        for (uint32_t j = 0; j < k; j++) {
-            const uint32_t* c;
-            int rc = row_to_coeffs(ctx, A, rows_dev + j * words, T, 1, &c, A.bcoef.as<uint32_t>() + j * words);
-            if (rc) return rc;
-        }
-        coef = A.bcoef.as<uint32_t>();
-    }
+    return KZG_OK;
+}
+// the openings of nrows rows (row j's Montgomery coefficients at rt.r[j]) at m points: the pairs' evaluations land in the
+// record (MR_EVAL, point-major), the m quotients in A.qbuf as m consecutive length-T canonical scalar sets
+static int multi_open_poly(kzg_ctx* ctx, Lane& A, const RowTab& rt, uint32_t nrows, uint64_t T, uint32_t m,
+                           const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint32_t* out_npairs) {
+    hipStream_t s = A.stream;
     // the pairs, point-major, ascending rows inside a point (the order of out_evals32)
     PairArg pa;
     memset(&pa, 0, sizeof(pa));
@@ -519,14 +515,13 @@ int commit_open_multi_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t*
         memcpy(pa.a[p].w, points_be32 + 32 * (size_t)p, 32);
         memcpy(ca.g[p].w, gammas_be32 + 32 * (size_t)p, 32);
         ca.mask[p] = masks[p];
-        for (uint32_t j = 0; j < k; j++)
+        for (uint32_t j = 0; j < nrows; j++)
             if ((masks[p] >> j) & 1u) {
                 pa.row[npairs] = (uint8_t)j;
                 pa.pt[npairs++] = (uint8_t)p;
             }
     }
     uint8_t* rec = A.brec.as<uint8_t>();
-    g1_xyzz_t* res = reinterpret_cast<g1_xyzz_t*>(rec + MR_RES);
     uint32_t* alpha_m = reinterpret_cast<uint32_t*>(rec + MR_ALPHA_M);
     const uint64_t nchunks = (T + 3) / 4;
     const uint64_t hrow = (nchunks + (nchunks >> 1) + 64) * 8;   // level scratch of one pair, words
@@ -537,22 +532,35 @@ int commit_open_multi_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t*
     HIPCHK(ctx, A.bcomb.ensure(m * T * 32));
     HIPCHK(ctx, A.qbuf.ensure(m * T * 32));
     uint32_t* hcomb = A.bcomb.as<uint32_t>();
-    uint32_t* q = A.qbuf.as<uint32_t>();
-    {
-        Span sp(ctx, A, KZG_T_POLY);
-        for (uint32_t g0 = 0; g0 < npairs; g0 += group) {   // the points ride in as arguments of each group's first kernel
-            const uint32_t ng = std::min(group, npairs - g0);
-            PairArg ga = pa;
-            memmove(ga.row, pa.row + g0, ng);
-            memmove(ga.pt, pa.pt + g0, ng);
-            launch_poly_eval_pairs(s, coef, T, ng, ga, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), hrow,
-                                   reinterpret_cast<uint32_t*>(rec + MR_Y_M) + 8 * g0, A.flags(), rec + MR_EVAL + 32 * g0);
-        }
-        launch_fr_combine_points(s, coef, T, m, ca, hcomb, A.flags());
-        // k_poly_quotient leaves a zero in slot T - 1: each quotient rides as one more length-T scalar set
-        launch_poly_open_points(s, hcomb, T, m, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), hrow,
-                                reinterpret_cast<uint32_t*>(rec + MR_HY_M), q);
+    Span sp(ctx, A, KZG_T_POLY);
+    for (uint32_t g0 = 0; g0 < npairs; g0 += group) {   // the points ride in as arguments of each group's first kernel
+        const uint32_t ng = std::min(group, npairs - g0);
+        PairArg ga = pa;
+        memmove(ga.row, pa.row + g0, ng);
+        memmove(ga.pt, pa.pt + g0, ng);
+        launch_poly_eval_pairs(s, rt, T, ng, ga, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), hrow,
+                               reinterpret_cast<uint32_t*>(rec + MR_Y_M) + 8 * g0, A.flags(), rec + MR_EVAL + 32 * g0);
     }
+    launch_fr_combine_points(s, rt, T, m, ca, hcomb, A.flags());
+    // k_poly_quotient leaves a zero in slot T - 1: each quotient rides as one more length-T scalar set
+    launch_poly_open_points(s, hcomb, T, m, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), hrow,
+                            reinterpret_cast<uint32_t*>(rec + MR_HY_M), A.qbuf.as<uint32_t>());
+    *out_npairs = npairs;
+    return KZG_OK;
+}
+// the MSMs over U_i and the end of a multi-row call: sets 0 .. k-1 are the rows (Montgomery, consecutive at coef), sets
+// k .. k+m-1 the quotients in A.qbuf.  Rows up to KZG_BATCHED_ROW_MAX share passes of as many sets as the sort's key carries
+// (at most 2^22 buckets); longer rows run one set per pass, alternating with a second lane when one is free.  Writes the k
+// commitments, the npairs evaluations of the record and the m proofs (each output unused when its count is 0).
+static int multi_msms_finish(kzg_ctx* ctx, LaneHold& H, uint32_t i, uint64_t T, const uint32_t* coef, uint32_t k,
+                             uint32_t m, uint32_t npairs, uint8_t* out_c48, uint8_t* out_evals32, uint8_t* out_p48) {
+    Lane& A = H.L();
+    hipStream_t s = A.stream;
+    const uint64_t words = T * 8;   // one row, in words
+    uint8_t* rec = A.brec.as<uint8_t>();
+    g1_xyzz_t* res = reinterpret_cast<g1_xyzz_t*>(rec + MR_RES);
+    const uint32_t* q = A.qbuf.as<uint32_t>();
+    const bool batched = T <= KZG_BATCHED_ROW_MAX;
     const uint64_t offset = (uint64_t)i * ctx->T;
     // sets per pass: what the sort's key carries (msm_sort_max_sets), at most 2^22 buckets; long rows one set per pass
     int per = std::min(KZG_BATCH_PASS_SETS, msm_sort_max_sets(ctx->c));
@@ -590,15 +598,63 @@ int commit_open_multi_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t*
     if (ctx->host_finish) {
         uint8_t enc[MR_SETS * 48];
         kzg_host::xyzz_batch_to_c48(reinterpret_cast<const uint32_t*>(A.bpin + MR_RES), sets, enc);
-        memcpy(out_c48, enc, 48 * (size_t)k);
-        memcpy(out_p48, enc + 48 * (size_t)k, 48 * (size_t)m);
+        if (k) memcpy(out_c48, enc, 48 * (size_t)k);
+        if (m) memcpy(out_p48, enc + 48 * (size_t)k, 48 * (size_t)m);
     } else {
-        memcpy(out_c48, A.bpin + MR_C48, 48 * (size_t)k);
-        memcpy(out_p48, A.bpin + MR_C48 + 48 * (size_t)k, 48 * (size_t)m);
+        if (k) memcpy(out_c48, A.bpin + MR_C48, 48 * (size_t)k);
+        if (m) memcpy(out_p48, A.bpin + MR_C48 + 48 * (size_t)k, 48 * (size_t)m);
     }
-    memcpy(out_evals32, A.bpin + MR_EVAL, 32 * (size_t)npairs);
+    if (npairs) memcpy(out_evals32, A.bpin + MR_EVAL, 32 * (size_t)npairs);
     H.clean = true;
     return KZG_OK;
+}
+int commit_open_multi_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* rows_dev, uint32_t k, uint64_t T,
+                          int evaluation_form, uint32_t m, const uint8_t* points_be32, const uint32_t* masks,
+                          const uint8_t* gammas_be32, uint8_t* out_c48, uint8_t* out_evals32, uint8_t* out_p48) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const uint64_t words = T * 8;   // one row, in words
+    const uint32_t* coef = rows_dev;
+    if (evaluation_form && T > 1) {
+        HIPCHK(ctx, A.bcoef.ensure(k * T * 32));
+        for (uint32_t j = 0; j < k; j++) {
+            const uint32_t* c;
+            int rc = row_to_coeffs(ctx, A, rows_dev + j * words, T, 1, &c, A.bcoef.as<uint32_t>() + j * words);
+            if (rc) return rc;
+        }
+        coef = A.bcoef.as<uint32_t>();
+    }
+    RowTab rt;
+    memset(&rt, 0, sizeof(rt));
+    for (uint32_t j = 0; j < k; j++) rt.r[j] = coef + j * words;
+    uint32_t npairs = 0;
+    if (int rc = multi_open_poly(ctx, A, rt, k, T, m, points_be32, masks, gammas_be32, &npairs)) return rc;
+    return multi_msms_finish(ctx, H, i, T, coef, k, m, npairs, out_c48, out_evals32, out_p48);
+}
+
+// ---- committed row sets.  The commit: rows (Montgomery, k x T at rows_dev) -> their coefficients in the set's own buffer
+// `dst` (the INTT writes there; coefficient-form rows were uploaded there already) -> the k commitment MSMs.
+int rows_commit_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* rows_dev, uint32_t k, uint64_t T,
+                    int evaluation_form, uint32_t* dst, uint8_t* out_c48) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const uint64_t words = T * 8;
+    for (uint32_t j = 0; evaluation_form && T > 1 && j < k; j++) {
+        const uint32_t* c;
+        int rc = row_to_coeffs(ctx, A, rows_dev + j * words, T, 1, &c, dst + j * words);
+        if (rc) return rc;
+    }
+    return multi_msms_finish(ctx, H, i, T, dst, k, 0, 0, out_c48, nullptr, nullptr);
+}
+// The open: the coefficient rows of committed sets (row j at rt.r[j], read in place) at m points -> the m proofs.
+int rows_open_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t k, uint64_t T, uint32_t m,
+                  const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
+                  uint8_t* out_p48) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    uint32_t npairs = 0;
+    if (int rc = multi_open_poly(ctx, A, rt, k, T, m, points_be32, masks, gammas_be32, &npairs)) return rc;
+    return multi_msms_finish(ctx, H, i, T, nullptr, 0, m, npairs, nullptr, out_evals32, out_p48);
 }
 
 }  // namespace kzg_impl

@@ -615,3 +615,210 @@ int kzg_calibrate(kzg_ctx* ctx, int waves_per_simd, double out[6]) {
 }
 
 }  // extern "C"
+
+// ---- committed row sets (kzg_rows_*): the set table of kzg_ctx (ctx.hip.h) around the two halves of the multi-point
+// opening (pipeline.hip: rows_commit_dev, rows_open_dev).  Lock order: a lane first, then sets_mu (an SRS load holds every
+// lane when it marks the sets stale, so no open or commit runs across it).
+namespace kzg_impl {
+
+static std::atomic<uint64_t> g_row_set_handles{0};   // never reused within the process: a stale handle names no newer set
+
+static uint32_t rows_live(const kzg_ctx* ctx) {   // under sets_mu
+    uint32_t n = 0;
+    for (const auto& kv : ctx->sets) n += !kv.second.released;
+    return n;
+}
+// retire a set (under sets_mu): its buffer goes to the free list -- no hipFree while other lanes run
+static void rows_retire(kzg_ctx* ctx, std::map<uint64_t, kzg_ctx::RowSet>::iterator it) {
+    if (it->second.buf.p) ctx->sets_free.push_back(std::move(it->second.buf));
+    ctx->sets.erase(it);
+}
+void rows_invalidate(kzg_ctx* ctx) {
+    std::lock_guard<std::mutex> lk(ctx->sets_mu);
+    for (auto& kv : ctx->sets) {   // every lane is held: no open reads these buffers
+        kv.second.stale = true;
+        kv.second.buf.release();
+    }
+    ctx->sets_free.clear();
+}
+// a commit's reservation against KZG_MAX_ROW_SETS and its buffer until the set is inserted.  Declared before the call's
+// LaneHold, so that a failed call has drained its lane before the buffer goes back to the free list.
+struct RowsPending {
+    kzg_ctx* ctx;
+    DevBuf buf;
+    bool reserved = false;
+    ~RowsPending() {
+        std::lock_guard<std::mutex> lk(ctx->sets_mu);
+        if (reserved) ctx->sets_pending--;
+        if (buf.p) ctx->sets_free.push_back(std::move(buf));
+    }
+};
+// the references an open holds on its sets, dropped after its lane is drained (declared before the LaneHold)
+struct RowsRefs {
+    kzg_ctx* ctx;
+    uint64_t h[KZG_MAX_BATCH_OPEN];
+    uint32_t n = 0;
+    ~RowsRefs() {
+        std::lock_guard<std::mutex> lk(ctx->sets_mu);
+        for (uint32_t t = 0; t < n; t++) {
+            auto it = ctx->sets.find(h[t]);
+            if (it != ctx->sets.end() && --it->second.refs == 0 && it->second.released) rows_retire(ctx, it);
+        }
+    }
+};
+
+int rows_open_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
+                   const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
+                   uint8_t* out_proofs48) {
+    if (!ctx || !handles || !points_be32 || !masks || !gammas_be32 || !out_evals32 || !out_proofs48) return KZG_E_ARG;
+    if (n_handles == 0 || n_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "row-set opening: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (m == 0 || m > KZG_MAX_OPEN_POINTS)
+        return fail(ctx, KZG_E_ARG, "row-set opening: m must be in [1, KZG_MAX_OPEN_POINTS]");
+    for (uint32_t p = 0; p < m; p++)
+        if (!fr_be32_canonical(points_be32 + 32 * (size_t)p) || !fr_be32_canonical(gammas_be32 + 32 * (size_t)p))
+            return fail(ctx, KZG_E_ARG, "row-set opening: points and gammas must be canonical scalars (< r)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsRefs refs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookup: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab rt;
+    memset(&rt, 0, sizeof(rt));
+    uint32_t k = 0, i = 0;
+    uint64_t T = 0;
+    {
+        std::lock_guard<std::mutex> lk(ctx->sets_mu);
+        for (uint32_t t = 0; t < n_handles; t++) {
+            auto it = ctx->sets.find(handles[t]);
+            if (it == ctx->sets.end() || it->second.released)
+                return fail(ctx, KZG_E_ARG, "row-set opening: unknown or released handle");
+            kzg_ctx::RowSet& st = it->second;
+            if (st.stale)
+                return fail(ctx, KZG_E_ARG, "row-set opening: the set was committed under an SRS that has since been "
+                                            "reloaded (its commitments no longer hold): release it and commit its rows again");
+            if (t == 0) {
+                i = st.i;
+                T = st.T;
+            } else if (st.i != i || st.T != T) {
+                return fail(ctx, KZG_E_ARG, "row-set opening: all sets must belong to one worker and have one row length");
+            }
+            if (expect_i != UINT32_MAX && st.i != expect_i)
+                return fail(ctx, KZG_E_ARG, "row-set opening: the set belongs to another worker");
+            if (k + st.k > KZG_MAX_BATCH_OPEN)
+                return fail(ctx, KZG_E_ARG, "row-set opening: more than KZG_MAX_BATCH_OPEN rows in all");
+            for (uint32_t j = 0; j < st.k; j++) rt.r[k + j] = st.buf.as<uint32_t>() + (uint64_t)j * st.T * 8;
+            k += st.k;
+            st.refs++;
+            refs.h[refs.n++] = handles[t];
+        }
+    }
+    for (uint32_t p = 0; p < m; p++)
+        if (masks[p] == 0 || (masks[p] >> k) != 0)
+            return fail(ctx, KZG_E_ARG, "row-set opening: every mask must name at least one row, and rows < k only");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    return rows_open_dev(ctx, H, i, rt, k, T, m, points_be32, masks, gammas_be32, out_evals32, out_proofs48);
+}
+
+int rows_release_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle) {
+    if (!ctx) return KZG_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->sets_mu);
+    auto it = ctx->sets.find(handle);
+    if (it == ctx->sets.end() || it->second.released)
+        return fail(ctx, KZG_E_ARG, "row-set release: unknown or already released handle");
+    if (expect_i != UINT32_MAX && it->second.i != expect_i)
+        return fail(ctx, KZG_E_ARG, "row-set release: the set belongs to another worker");
+    it->second.released = true;
+    if (it->second.refs == 0) rows_retire(ctx, it);   // else the last open that reads it retires it
+    return KZG_OK;
+}
+
+}  // namespace kzg_impl
+
+extern "C" {
+
+// k rows of worker i committed and kept on the device as coefficients (pipeline.hip: rows_commit_dev)
+int kzg_rows_commit(kzg_ctx* ctx, uint32_t i, uint32_t k, const uint8_t* rows_be32, uint64_t T, int evaluation_form,
+                    uint8_t* out_commitments48, uint64_t* out_handle) {
+    if (!ctx || !rows_be32 || !out_commitments48 || !out_handle) return KZG_E_ARG;
+    if (k == 0 || k > KZG_MAX_BATCH_OPEN) return fail(ctx, KZG_E_ARG, "row-set commit: k must be in [1, KZG_MAX_BATCH_OPEN]");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;
+    Lane& L = H.L();
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (evaluation_form && T > 1 && ilog2_exact(T) < 0)
+        return fail(ctx, KZG_E_ARG, "evaluation-form row length must be a power of two");
+    const size_t bytes = (size_t)k * T * 32;
+    {
+        std::lock_guard<std::mutex> lk(ctx->sets_mu);
+        if (rows_live(ctx) + ctx->sets_pending >= KZG_MAX_ROW_SETS)
+            return fail(ctx, KZG_E_BUSY, "row-set commit: KZG_MAX_ROW_SETS sets are live: release one first");
+        ctx->sets_pending++;
+        pend.reserved = true;
+        // the smallest released buffer that fits, else a fresh allocation below
+        size_t best = ctx->sets_free.size();
+        for (size_t b = 0; b < ctx->sets_free.size(); b++)
+            if (ctx->sets_free[b].cap >= bytes && (best == ctx->sets_free.size() || ctx->sets_free[b].cap < ctx->sets_free[best].cap))
+                best = b;
+        if (best < ctx->sets_free.size()) {
+            pend.buf = std::move(ctx->sets_free[best]);
+            ctx->sets_free.erase(ctx->sets_free.begin() + best);
+        }
+    }
+    HIPCHK(ctx, pend.buf.ensure(bytes));
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    // evaluation-form rows are uploaded to the lane and transformed into the set's buffer; coefficient rows land there directly
+    uint32_t* dst = pend.buf.as<uint32_t>();
+    uint32_t* up = dst;
+    if (evaluation_form && T > 1) {
+        HIPCHK(ctx, L.coeffA.ensure(bytes));
+        up = L.coeffA.as<uint32_t>();
+    }
+    rc = upload_fr(ctx, L, rows_be32, (uint64_t)k * T, up, 1);
+    if (rc) return rc;
+    rc = rows_commit_dev(ctx, H, i, up, k, T, evaluation_form, dst, out_commitments48);
+    if (rc) return rc;
+    const uint64_t h = ++g_row_set_handles;
+    {
+        std::lock_guard<std::mutex> lk(ctx->sets_mu);
+        kzg_ctx::RowSet& st = ctx->sets[h];
+        st.i = i;
+        st.k = k;
+        st.T = T;
+        st.buf = std::move(pend.buf);
+        ctx->sets_pending--;
+        pend.reserved = false;
+    }
+    *out_handle = h;
+    return KZG_OK;
+}
+int kzg_rows_open(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t m, const uint8_t* points_be32,
+                  const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32, uint8_t* out_proofs48) {
+    return rows_open_impl(ctx, UINT32_MAX, n_handles, handles, m, points_be32, masks, gammas_be32, out_evals32,
+                          out_proofs48);
+}
+int kzg_rows_release(kzg_ctx* ctx, uint64_t handle) { return rows_release_impl(ctx, UINT32_MAX, handle); }
+int kzg_rows_stats(kzg_ctx* ctx, uint64_t out_live_sets_bytes[2]) {
+    if (!ctx || !out_live_sets_bytes) return KZG_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->sets_mu);
+    uint64_t n = 0, bytes = 0;
+    for (const auto& kv : ctx->sets)
+        if (!kv.second.released) {
+            n++;
+            bytes += kv.second.buf.cap;
+        }
+    out_live_sets_bytes[0] = n;
+    out_live_sets_bytes[1] = bytes;
+    return KZG_OK;
+}
+
+}  // extern "C"

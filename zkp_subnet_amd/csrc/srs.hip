@@ -84,6 +84,7 @@ int alloc_new_table(kzg_ctx* ctx, const TableSpec& sp, DevBuf& nt) {
     return KZG_OK;
 }
 void install_table(kzg_ctx* ctx, const TableSpec& sp, DevBuf& nt) {
+    rows_invalidate(ctx);         // committed row sets were made under the previous table
     ctx->table = std::move(nt);   // frees the previous table
     ctx->c = sp.c; ctx->nwin = sp.nwin; ctx->lay = sp.lay; ctx->nbuckets = sp.nbuckets;
     ctx->stride = sp.stride; ctx->T = sp.T; ctx->scale = sp.scale; ctx->mscale = sp.mscale;

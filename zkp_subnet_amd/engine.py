@@ -283,6 +283,65 @@ class HipEngine:
             t += len(rws)
         return [c.raw[48 * j:48 * j + 48] for j in range(k)], evals, [pf.raw[48 * p:48 * p + 48] for p in range(m)]
 
+    # ---- committed row sets: commit rows once (kzg_rows_commit), open them later (kzg_rows_open), the shape of a
+    # Fiat-Shamir prover that hashes its commitments before it draws the points and gammas
+    def commit_rows(self, i: int, rows_be32: Sequence[bytes], evaluation_form: bool = True) -> "RowSet":
+        """k <= 16 rows of worker i committed and kept on the device: a RowSet (handle, i, k, T, commitments), to be opened
+        by open_rows any number of times and released with RowSet.release() (or as a context manager)."""
+        k = len(rows_be32)
+        if k == 0 or k > _native.KZG_MAX_BATCH_OPEN:
+            raise KzgError(_native.KZG_E_ARG, f"commit_rows: k = {k} outside [1, {_native.KZG_MAX_BATCH_OPEN}]")
+        if len({len(r) for r in rows_be32}) != 1 or len(rows_be32[0]) % 32:
+            raise KzgError(_native.KZG_E_ARG, "commit_rows: rows of unequal length")
+        T = len(rows_be32[0]) // 32
+        return self._commit_rows(i, k, b"".join(rows_be32), T, evaluation_form)
+
+    def _commit_rows(self, i, k, rows, T, evaluation_form):
+        c, h = ctypes.create_string_buffer(48 * k), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit(self._h, i, k, rows, T, int(evaluation_form), c, ctypes.byref(h)))
+        return RowSet(self, h.value, i, k, T, [c.raw[48 * j:48 * j + 48] for j in range(k)])
+
+    def open_rows(self, sets: Sequence[object], points_be32: Sequence[bytes], opened: Sequence[Sequence[int]],
+                  gammas_be32: Sequence[bytes]) -> Tuple[List[List[bytes]], List[bytes]]:
+        """Opens committed sets (RowSet objects or bare handles) at m <= 4 points: their rows are numbered by
+        concatenation in the order given, opened[p] lists point p's rows (as in commit_open_multi).  Returns
+        ([[y_{j,p} for j in opened[p]] for p], [pi_p]), byte-identical to commit_open_multi on the concatenated rows."""
+        handles = [int(getattr(x, "handle", x)) for x in sets]
+        n = len(handles)
+        if n == 0 or n > _native.KZG_MAX_BATCH_OPEN:
+            raise KzgError(_native.KZG_E_ARG, f"open_rows: {n} sets, expected 1 .. {_native.KZG_MAX_BATCH_OPEN}")
+        hs = (ctypes.c_uint64 * n)(*handles)
+        return self._open_rows_call(lambda *a: self._lib.kzg_rows_open(self._h, n, hs, *a), self._rows_of(sets),
+                                    points_be32, opened, gammas_be32)
+
+    def _rows_of(self, sets) -> int:
+        """rows of the concatenation when every entry is a RowSet (a bare handle: checked by the library only)"""
+        ks = [getattr(x, "k", None) for x in sets]
+        return sum(ks) if all(k is not None for k in ks) else _native.KZG_MAX_BATCH_OPEN
+
+    def _open_rows_call(self, call, k, points_be32, opened, gammas_be32):
+        masks, npairs = _native.open_masks(opened, k)
+        m = len(opened)
+        if len(points_be32) != m or len(gammas_be32) != m or any(len(x) != 32 for x in list(points_be32) + list(gammas_be32)):
+            raise KzgError(_native.KZG_E_ARG, "open_rows: one 32-byte point and gamma per opened list")
+        ev, pf = ctypes.create_string_buffer(32 * npairs), ctypes.create_string_buffer(48 * m)
+        self._chk(call(m, b"".join(points_be32), masks, b"".join(gammas_be32), ev, pf))
+        evals, t = [], 0
+        for rws in opened:
+            evals.append([ev.raw[32 * (t + u):32 * (t + u) + 32] for u in range(len(rws))])
+            t += len(rws)
+        return evals, [pf.raw[48 * p:48 * p + 48] for p in range(m)]
+
+    def release_rows(self, handle: int) -> None:
+        """Frees a committed set (kzg_rows_release); KzgError(KZG_E_ARG) for an unknown or already released handle."""
+        self._chk(self._lib.kzg_rows_release(self._h, int(handle)))
+
+    def rows_stats(self) -> Tuple[int, int]:
+        """(live committed sets, device bytes their rows hold)."""
+        arr = (ctypes.c_uint64 * 2)()
+        self._chk(self._lib.kzg_rows_stats(self._h, arr))
+        return arr[0], arr[1]
+
     # ---- the same three calls fed from the synapse's List[str] (reference neurons/miner.py:38-61): the text is decoded
     # by csrc/wire_py.c straight into the library's pinned staging buffer (no bytes object, no pageable bounce)
     class _Staged:
@@ -611,3 +670,28 @@ class HipEngine:
         out = ctypes.create_string_buffer(len(a_be96))
         self._chk(self._lib.kzg_test_g1(self._h, op, a_be96, b_be96, out, len(a_be96) // 96))
         return out.raw
+
+
+class RowSet:
+    """Rows committed by HipEngine.commit_rows and kept on the device: `handle`, worker `i`, `k` rows of `T` elements and
+    their `commitments` (48-byte compressed G1 each).  release() frees the device copy; a `with` block releases on exit."""
+
+    def __init__(self, engine, handle: int, i: int, k: int, T: int, commitments: List[bytes]):
+        self.engine, self.handle, self.i, self.k, self.T = engine, handle, i, k, T
+        self.commitments = commitments
+        self.released = False
+
+    def release(self) -> None:
+        if not self.released:
+            self.released = True
+            self.engine.release_rows(self.handle)
+
+    def __enter__(self) -> "RowSet":
+        return self
+
+    def __exit__(self, *exc) -> bool:
+        self.release()
+        return False
+
+    def __repr__(self) -> str:
+        return f"RowSet(handle={self.handle}, i={self.i}, k={self.k}, T={self.T})"

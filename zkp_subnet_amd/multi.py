@@ -22,7 +22,7 @@ callers working on bytes); this class is the same routing one level up, where th
 from __future__ import annotations
 
 from concurrent.futures import ThreadPoolExecutor
-from typing import List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 from .client import Client, Response
 
@@ -43,6 +43,7 @@ class MultiDeviceClient:
         self.scale = self.machines_scale = 0
         self._rr = 0
         self._pool: Optional[ThreadPoolExecutor] = None
+        self._row_owner: Dict[int, int] = {}   # committed row set handle -> worker index (its device serves the set)
 
     # ------------------------------------------------------------------ lifecycle
     def start(self, scale: int = 18, machines_scale: int = 8) -> None:
@@ -72,6 +73,7 @@ class MultiDeviceClient:
         for c in self.clients:
             c.stop()
         self.clients = []
+        self._row_owner.clear()
 
     # ------------------------------------------------------------------ routing
     def device_of(self, i: int) -> int:
@@ -103,6 +105,35 @@ class MultiDeviceClient:
 
     def worker_commit_open_multi(self, i: int, polys: Sequence[Sequence[str]], points: Sequence[str], opened, gammas):
         return self._for(i).worker_commit_open_multi(i, polys, points, opened, gammas)
+
+    # committed row sets: a set lives on the device of its worker; opens and releases are routed by the handles' worker
+    def worker_commit_rows(self, i: int, polys: Sequence[Sequence[str]]):
+        r = self._for(i).worker_commit_rows(i, polys)
+        if r.status_code == 200:
+            self._row_owner[int(r.json()["handle"])] = int(i)
+        return r
+
+    def _owner(self, handles) -> Optional[int]:
+        try:
+            owners = {self._row_owner.get(int(h)) for h in handles}
+        except (TypeError, ValueError):
+            return None
+        return owners.pop() if len(owners) == 1 else None
+
+    def worker_open_rows(self, handles: Sequence[int], points, opened, gammas):
+        i = self._owner(handles)
+        if i is None:
+            return Response(400, {"error": "worker_open_rows: the handles must name live sets of one worker"})
+        return self._for(i).worker_open_rows(handles, points, opened, gammas)
+
+    def worker_release_rows(self, handle: int):
+        i = self._owner([handle])
+        if i is None:
+            return Response(400, {"error": "worker_release_rows: unknown row-set handle"})
+        r = self._for(i).worker_release_rows(handle)
+        if r.status_code == 200:
+            self._row_owner.pop(int(handle), None)
+        return r
 
     def commit_and_open_rows(self, indices: Sequence[int], polys: Sequence[Sequence[str]], x: str) -> List[Response]:
         """Pianist rows of one challenge, all devices at once: row k runs on the device of indices[k]; responses in input
