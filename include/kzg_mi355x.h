@@ -130,8 +130,11 @@ int kzg_commit_open(kzg_ctx* ctx, uint32_t i, const uint8_t* row_be32, uint64_t 
  * out_evals32[j] = f_j(alpha), and ONE proof pi = MSM(U_i, (h - h(alpha)) / (X - alpha)) for h = sum_j gamma^j f_j --
  * exactly the proof of kzg_open(i, h, alpha).  k = 1 reproduces kzg_commit_open.  Verification (kzg_vk_verify_open_batch):
  *   e(sum_j gamma^j C_j - (sum_j gamma^j y_j) [L_i]_1, [1]_2) == e(pi, [tau_x - alpha]_2).
- * SOUNDNESS: gamma must be chosen by the verifier AFTER the commitments are fixed (a prover who knows gamma in advance can
- * make a false y_j cancel in the combination).  The library takes gamma as an input, like alpha, and derives nothing: the
+ * SOUNDNESS: gamma must be chosen by the verifier AFTER the commitments AND the evaluations y_j are fixed (a prover who
+ * knows gamma before it commits to the y_j can pick two false ones whose errors cancel in the combination).  This call
+ * returns the y_j and the proof together, so a Fiat-Shamir caller, who must hash the y_j before it derives gamma, cannot
+ * use it as one step: it commits the rows as a set (kzg_rows_commit), hashes, gets the y_j from kzg_rows_eval, hashes them,
+ * and proves with kzg_rows_open_lincomb.  The library takes gamma as an input, like alpha, and derives nothing: the
  * caller's protocol supplies both.  k = 0, k > KZG_MAX_BATCH_OPEN, alpha or gamma >= r and every worker-index / length
  * check of kzg_commit_open give KZG_E_ARG; the context keeps serving.  Rows up to 2^18 run as ONE MSM pass with k + 1
  * scalar sets (one sort, one bucket tree with k + 1 roots). */
@@ -147,8 +150,9 @@ int kzg_commit_open_batch(kzg_ctx* ctx, uint32_t i, uint32_t k, const uint8_t* r
  *   pi_p = MSM(U_i, (h_p - h_p(alpha_p)) / (X - alpha_p)),  h_p = sum_t gamma_p^t f_{j_t}  over the masked rows
  *   j_0 < j_1 < ... of point p.
  * m = 1 with the full mask reproduces kzg_commit_open_batch byte for byte; two equal points each keep their own proof.
- * SOUNDNESS: as for kzg_commit_open_batch -- the alpha_p and gamma_p must be drawn by the verifier AFTER the commitments are
- * fixed; the library derives none of them.  k = 0, k > KZG_MAX_BATCH_OPEN, m = 0, m > KZG_MAX_OPEN_POINTS, a zero mask, a
+ * SOUNDNESS: as for kzg_commit_open_batch -- the alpha_p must be drawn AFTER the commitments are fixed, and the gamma_p
+ * AFTER the commitments and the evaluations y_{j,p}; a Fiat-Shamir caller therefore goes through committed row sets,
+ * kzg_rows_eval and kzg_rows_open_lincomb.  The library derives none of them.  k = 0, k > KZG_MAX_BATCH_OPEN, m = 0, m > KZG_MAX_OPEN_POINTS, a zero mask, a
  * mask bit >= k, an alpha_p or gamma_p >= r and every worker-index / length check of kzg_commit_open give KZG_E_ARG; the
  * context keeps serving.  The rows are uploaded and transformed once; rows up to 2^18 run as ONE MSM pass with k + m scalar
  * sets while the sort's key carries them (else as few passes as fit). */
@@ -176,8 +180,10 @@ int kzg_commit_open_multi(kzg_ctx* ctx, uint32_t i, uint32_t k, const uint8_t* r
  * the memory is reclaimed after it.  Any kzg_load_srs* / kzg_gen_srs makes every live set stale (its commitments belong to
  * the old SRS); its release still succeeds.  kzg_destroy frees every set.  After any error the context keeps serving.
  * kzg_rows_stats: out[0] live sets (stale ones included until released), out[1] the device bytes their rows hold.
- * SOUNDNESS: with sets the caller can fix and hash the commitments BEFORE it draws the points and gammas of the open, as
- * kzg_commit_open_batch / _multi require; the library still derives no challenge. */
+ * SOUNDNESS: with sets the caller can fix and hash the commitments BEFORE it draws the points.  kzg_rows_open still takes
+ * the gammas together with returning the evaluations, and the gammas must come AFTER the evaluations are fixed (see
+ * kzg_commit_open_batch); a Fiat-Shamir caller uses kzg_rows_eval, hashes the evaluations, then kzg_rows_open_lincomb.
+ * The library still derives no challenge. */
 #define KZG_MAX_ROW_SETS 64   /* live sets per context */
 int kzg_rows_commit(kzg_ctx* ctx, uint32_t i, uint32_t k, const uint8_t* rows_be32 /* k*T*32 */, uint64_t T,
                     int evaluation_form, uint8_t* out_commitments48 /* k*48 */, uint64_t* out_handle);
@@ -186,6 +192,29 @@ int kzg_rows_open(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uin
                   uint8_t* out_evals32 /* sum popcount(masks)*32 */, uint8_t* out_proofs48 /* m*48 */);
 int kzg_rows_release(kzg_ctx* ctx, uint64_t handle);
 int kzg_rows_stats(kzg_ctx* ctx, uint64_t out_live_sets_bytes[2]);
+/* Evaluate first, then open caller-weighted combinations: the two calls of a Fiat-Shamir opening round (PLONK round 5).
+ *   1. kzg_rows_commit the sets; hash the commitments, derive zeta.
+ *   2. kzg_rows_eval; hash the evaluations, derive v.
+ *   3. compute the combination scalars on the host (the linearisation's c_j from the evaluations, v powers for the rest).
+ *   4. kzg_rows_open_lincomb.
+ * kzg_rows_eval: y_{j,p} = f_j(alpha_p) of every masked (row, point) pair of committed sets, no proof, no MSM.  Rows
+ * numbered, masks, point checks, handle rules (unknown / released / stale / mixed worker or length -> KZG_E_ARG) and the
+ * point-major output layout exactly as kzg_rows_open; out_evals32 equals kzg_rows_open's byte for byte for the same
+ * points / masks.
+ * kzg_rows_open_lincomb: one proof per point for a caller-weighted combination of the k concatenated rows:
+ *   h_p = sum_j lambda_{p,j} f_j,  v_p = h_p(alpha_p),  pi_p = MSM(U_i, (h_p - v_p) / (X - alpha_p))
+ * -- exactly kzg_open(i, h_p, alpha_p).  coeffs_be32: m x k canonical scalars, point-major; a zero coefficient leaves the row
+ * out.  k must equal the rows of the concatenation; a coefficient or point >= r, a point whose k coefficients are all zero,
+ * m = 0 or m > KZG_MAX_OPEN_POINTS -> KZG_E_ARG.  No pair evaluation, no commitment MSM: the combination, the m openings
+ * and the m proof MSMs.  The verifier forms sum_j lambda_{p,j} C_j from commitments it already holds
+ * (kzg_vk_verify_open_lincomb), so a linearisation polynomial is never committed.
+ * Both are thread-safe like kzg_rows_open and follow its rules for a release or an SRS load that races them; after any
+ * error the context keeps serving. */
+int kzg_rows_eval(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t m, const uint8_t* points_be32 /* m*32 */,
+                  const uint32_t* masks /* m */, uint8_t* out_evals32 /* sum popcount(masks)*32 */);
+int kzg_rows_open_lincomb(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
+                          const uint8_t* points_be32 /* m*32 */, const uint8_t* coeffs_be32 /* m*k*32 */,
+                          uint8_t* out_values32 /* m*32 */, uint8_t* out_proofs48 /* m*48 */);
 /* The UNCHANGED reference miner makes two calls per request with the same row -- worker_commit(i, poly), then
  * worker_open(i, poly, x) (neurons/miner.py:56-61).  These forms take a 128-bit content tag identifying the row's bytes
  * (the host codec computes it while decoding the text); the coefficient vectors of the last four rows stay on the
@@ -251,6 +280,15 @@ int kzg_vk_verify_open_batch(const kzg_vk* vk, uint32_t i, uint32_t k, const uin
 int kzg_vk_verify_open_multi(const kzg_vk* vk, uint32_t i, uint32_t k, const uint8_t* commitments48, uint32_t m,
                              const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32,
                              const uint8_t* evals_be32, const uint8_t* proofs48, int* out_valid);
+/* One caller-weighted opening (kzg_rows_open_lincomb) of k rows of slice i, every point folded with random 128-bit weights
+ * into two Miller loops as in kzg_vk_verify_open_multi:
+ *   e(sum_j lambda_{p,j} C_j - v_p [L_i]_1, [1]_2) == e(pi_p, [tau_x - alpha_p]_2)  for every p.
+ * coeffs_be32: m x k, point-major, as kzg_rows_open_lincomb takes them.  Malformed, off-curve or non-G1 commitment / proof
+ * bytes give *out_valid = 0 (not an error); k = 0, k > KZG_MAX_BATCH_OPEN, m = 0, m > KZG_MAX_OPEN_POINTS, a point whose
+ * coefficients are all zero or i outside the key -> KZG_E_ARG; an alpha_p, coefficient or value >= r -> KZG_E_SCALAR. */
+int kzg_vk_verify_open_lincomb(const kzg_vk* vk, uint32_t i, uint32_t k, const uint8_t* commitments48, uint32_t m,
+                               const uint8_t* points_be32, const uint8_t* coeffs_be32, const uint8_t* values_be32,
+                               const uint8_t* proofs48, int* out_valid);
 
 /* ---- multi-GPU: each rank reduces its SRS shard to ONE partial sum; the 192-byte partials are exchanged by
  *      the caller (RCCL all_gather over xGMI in zkp_subnet_amd.distributed) and summed on any rank. */
@@ -380,14 +418,19 @@ int kzg_multi_commit_open_multi(kzg_multi* mh, uint32_t i, uint32_t k, const uin
                                 int evaluation_form, uint32_t m, const uint8_t* points_be32, const uint32_t* masks,
                                 const uint8_t* gammas_be32, uint8_t* out_commitments48, uint8_t* out_evals32,
                                 uint8_t* out_proofs48);
-/* committed row sets on the device of worker i (routed like kzg_multi_commit_open): every set named in an open or a release
- * must belong to worker i, else KZG_E_ARG */
+/* committed row sets on the device of worker i (routed like kzg_multi_commit_open): every set named in an open, an
+ * evaluation, a lincomb opening or a release must belong to worker i, else KZG_E_ARG */
 int kzg_multi_rows_commit(kzg_multi* mh, uint32_t i, uint32_t k, const uint8_t* rows_be32, uint64_t T, int evaluation_form,
                           uint8_t* out_commitments48, uint64_t* out_handle);
 int kzg_multi_rows_open(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
                         const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
                         uint8_t* out_proofs48);
 int kzg_multi_rows_release(kzg_multi* mh, uint32_t i, uint64_t handle);
+int kzg_multi_rows_eval(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
+                        const uint8_t* points_be32, const uint32_t* masks, uint8_t* out_evals32);
+int kzg_multi_rows_open_lincomb(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t k,
+                                uint32_t m, const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32,
+                                uint8_t* out_proofs48);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

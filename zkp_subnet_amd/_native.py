@@ -57,6 +57,8 @@ SYMBOLS = {
     "kzg_rows_open": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _B, ctypes.POINTER(_U32), _B, _B, _B]),
     "kzg_rows_release": (_I, [_P, _U64]),
     "kzg_rows_stats": (_I, [_P, ctypes.POINTER(_U64)]),
+    "kzg_rows_eval": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _B, ctypes.POINTER(_U32), _B]),
+    "kzg_rows_open_lincomb": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _U32, _B, _B, _B, _B]),
     "kzg_commit_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B]),
     "kzg_open_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B, _B]),
     "kzg_row_cache_stats": (_I, [_P, ctypes.POINTER(_U64)]),
@@ -72,6 +74,7 @@ SYMBOLS = {
     "kzg_vk_verify_batch": (_I, [_P, _U32, ctypes.POINTER(_U32), _B, _B, _B, _B, _I, ctypes.POINTER(_I)]),
     "kzg_vk_verify_open_batch": (_I, [_P, _U32, _U32, _B, _B, _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_vk_verify_open_multi": (_I, [_P, _U32, _U32, _B, _U32, _B, ctypes.POINTER(_U32), _B, _B, _B, ctypes.POINTER(_I)]),
+    "kzg_vk_verify_open_lincomb": (_I, [_P, _U32, _U32, _B, _U32, _B, _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_vk_pairing": (_I, [_B, _B, _B]),
     "kzg_msm_partial": (_I, [_P, _B, _U64, _U64, _B]),
     "kzg_g1_sum": (_I, [_P, _B, _U32, _B]),
@@ -111,6 +114,8 @@ SYMBOLS = {
     "kzg_multi_rows_commit": (_I, [_P, _U32, _U32, _B, _U64, _I, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_open": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _B, ctypes.POINTER(_U32), _B, _B, _B]),
     "kzg_multi_rows_release": (_I, [_P, _U32, _U64]),
+    "kzg_multi_rows_eval": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _B, ctypes.POINTER(_U32), _B]),
+    "kzg_multi_rows_open_lincomb": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _U32, _B, _B, _B, _B]),
     "kzg_multi_commit_open_rows": (_I, [_P, _U32, ctypes.POINTER(_U32), _B, _U64, _I, _B, _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_upload_fr": (_I, [_P, _I, _B, _U64, _I]),
     "kzg_msm_resident": (_I, [_P, _I, _U64, _U64, _B]),

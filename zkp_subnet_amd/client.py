@@ -286,6 +286,36 @@ class Client:
         return {"evals": [[codec.be32_to_fr(e) for e in ev] for ev in evs], "proofs": [codec.g1_to_b64(pf) for pf in pfs]}
 
     @_guard
+    def worker_eval_rows(self, handles: Sequence[int], points: Sequence[str], opened: Sequence[Sequence[int]]):
+        """Extension: the evaluations of committed sets (rows numbered as in worker_open_rows) at m <= 4 points, no proof --
+        what a Fiat-Shamir prover hashes before it derives the scalars of worker_open_rows_lincomb.  Equal to the evaluations
+        worker_open_rows returns."""
+        hs = _handles(handles)
+        m = len(points)
+        if m == 0 or m > KZG_MAX_OPEN_POINTS or len(opened) != m:
+            raise codec.CodecError(f"worker_eval_rows: {m} points, {len(opened)} row lists")
+        open_masks(opened, KZG_MAX_BATCH_OPEN)   # the shape of `opened`; the engine checks it against the sets' rows
+        evs = self.engine.eval_rows(hs, [codec.fr_to_be32(x) for x in points], opened)
+        return {"evals": [[codec.be32_to_fr(e) for e in ev] for ev in evs]}
+
+    @_guard
+    def worker_open_rows_lincomb(self, handles: Sequence[int], points: Sequence[str], coeffs: Sequence[Sequence[str]]):
+        """Extension: one proof per point for h_p = sum_j coeffs[p][j] f_j over the k rows of committed sets (numbered as in
+        worker_open_rows; coeffs[p] holds k scalars, a zero one leaves its row out).  Returns the values v_p = h_p(x_p) and
+        the proofs; worker_verify_open_lincomb checks them against the sets' commitments."""
+        hs = _handles(handles)
+        m = len(points)
+        if m == 0 or m > KZG_MAX_OPEN_POINTS or len(coeffs) != m:
+            raise codec.CodecError(f"worker_open_rows_lincomb: {m} points, {len(coeffs)} coefficient lists")
+        k = len(coeffs[0])
+        if not 1 <= k <= KZG_MAX_BATCH_OPEN or any(len(c) != k for c in coeffs):
+            raise codec.CodecError(f"worker_open_rows_lincomb: ragged coefficients, expected {m} lists of 1 .. "
+                                   f"{KZG_MAX_BATCH_OPEN} scalars")
+        vals, pfs = self.engine.open_rows_lincomb(hs, [codec.fr_to_be32(x) for x in points],
+                                                  [[codec.fr_to_be32(c) for c in cs] for cs in coeffs])
+        return {"values": [codec.be32_to_fr(v) for v in vals], "proofs": [codec.g1_to_b64(pf) for pf in pfs]}
+
+    @_guard
     def worker_release_rows(self, handle: int):
         """Extension: frees a committed row set."""
         self.engine.release_rows(_handles([handle])[0])
@@ -335,6 +365,22 @@ class Client:
             raise codec.CodecError("worker_verify_open_multi: ragged points / proofs / opened rows / gammas / evals")
         ok = vm(self._slice(i), [codec.g1_from_b64(c) for c in commitments], [codec.fr_to_be32(x) for x in points], opened,
                 [codec.fr_to_be32(x) for x in gammas], [[codec.fr_to_be32(e) for e in ev] for ev in evals],
+                [codec.g1_from_b64(p) for p in proofs])
+        return {"valid": bool(ok)}
+
+    @_guard
+    def worker_verify_open_lincomb(self, i: int, proofs: Sequence[str], points: Sequence[str],
+                                   coeffs: Sequence[Sequence[str]], values: Sequence[str], commitments: Sequence[str]):
+        """Extension: the pairing check of one worker_open_rows_lincomb answer against the k commitments of its rows."""
+        vl = getattr(self.engine, "verify_open_lincomb", None)
+        if vl is None:
+            raise NotImplementedError("this engine has no caller-weighted-opening verifier")
+        k, m = len(commitments), len(points)
+        if not (1 <= m <= KZG_MAX_OPEN_POINTS and m == len(proofs) == len(coeffs) == len(values)) \
+                or not 1 <= k <= KZG_MAX_BATCH_OPEN or any(len(c) != k for c in coeffs):
+            raise codec.CodecError("worker_verify_open_lincomb: ragged points / proofs / coefficients / values / commitments")
+        ok = vl(self._slice(i), [codec.g1_from_b64(c) for c in commitments], [codec.fr_to_be32(x) for x in points],
+                [[codec.fr_to_be32(c) for c in cs] for cs in coeffs], [codec.fr_to_be32(v) for v in values],
                 [codec.g1_from_b64(p) for p in proofs])
         return {"valid": bool(ok)}
 

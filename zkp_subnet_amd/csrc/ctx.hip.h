@@ -397,12 +397,23 @@ int rows_commit_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* rows_
 int rows_open_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t k, uint64_t T, uint32_t m,
                   const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
                   uint8_t* out_p48);
+// the evaluations of the masked pairs only (kzg_rows_eval); the caller-weighted openings (kzg_rows_open_lincomb: masks[p] =
+// the rows with a nonzero coefficient at point p, coeffs_be32 m x k point-major)
+int rows_eval_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t k, uint64_t T, uint32_t m,
+                  const uint8_t* points_be32, const uint32_t* masks, uint8_t* out_evals32);
+int rows_lincomb_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t k, uint64_t T, uint32_t m,
+                     const uint8_t* points_be32, const uint8_t* coeffs_be32, const uint32_t* masks, uint8_t* out_values32,
+                     uint8_t* out_p48);
 // an SRS (re)load is installing a new table (every lane held): marks every live set stale, frees its buffer and the free list
 void rows_invalidate(kzg_ctx* ctx);
 // kzg_rows_open with the extra condition that every set belongs to worker `expect_i` (UINT32_MAX: any; kzg_multi_rows_open)
 int rows_open_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
                    const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
                    uint8_t* out_proofs48);
+int rows_eval_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
+                   const uint8_t* points_be32, const uint32_t* masks, uint8_t* out_evals32);
+int rows_lincomb_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
+                      const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32, uint8_t* out_proofs48);
 int rows_release_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle);
 
 // ---- the collective (comm.hip)

@@ -61,8 +61,10 @@ void launch_poly_eval_pairs(hipStream_t s, const RowTab& rt, uint64_t n, uint32_
                             uint32_t* bad, uint8_t* y_be);
 // m openings side by side: f_p = f_mont + p * n elements at the point alpha_mont + 8 p (Montgomery, already in memory):
 // y_p at y_mont + 8 p and the n-1 canonical quotient coefficients (slot n - 1 zero) at q_canon + p * n elements
+// (y_be given: y_p also as 32 big-endian bytes at y_be + 32 p)
 void launch_poly_open_points(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t m, const uint32_t* alpha_mont,
-                             uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont, uint32_t* q_canon);
+                             uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont, uint32_t* q_canon,
+                             uint8_t* y_be = nullptr);
 // h_p[t] = sum gamma_p^j rt.r[j][t] over the rows j of mask[p] (Montgomery in and out) into out + p * n elements, for
 // p < m in one launch; g[p]: gamma_p's 32 big-endian bytes, *bad raised when one is >= r
 struct CombArg {
@@ -71,5 +73,13 @@ struct CombArg {
 };
 void launch_fr_combine_points(hipStream_t s, const RowTab& rt, uint64_t n, uint32_t m, const CombArg& ca,
                               uint32_t* out_mont, uint32_t* bad);
+// the caller-weighted combinations of kzg_rows_open_lincomb, p < m in one launch: h_p[t] = sum_j lambda_{p,j} rt.r[j][t]
+// (Montgomery in and out) into out + p * n elements.  coeffs_be32: m x k canonical scalars, point-major; masks[p] bit j set
+// exactly when lambda_{p,j} != 0 (the rows the kernel reads).  Point p (32 big-endian bytes at points_be32 + 32 p) is
+// converted by the launch and left at alpha_mont + 8 p for the openings behind it.  *bad raised for a coefficient or a
+// point >= r.  The launcher packs all of it into ONE kernel argument (2.4 KB at m = 4, k = 16).
+void launch_fr_lincomb_points(hipStream_t s, const RowTab& rt, uint64_t n, uint32_t m, uint32_t k, const uint8_t* coeffs_be32,
+                              const uint32_t* masks, const uint8_t* points_be32, uint32_t* out_mont, uint32_t* alpha_mont,
+                              uint32_t* bad);
 // *flag |= 1 when a[0, n_words) and b[0, n_words) differ (n_words a multiple of 4): verification of a row-cache hit
 void launch_words_differ(hipStream_t s, const uint32_t* a, const uint32_t* b, uint64_t n_words, uint32_t* flag);

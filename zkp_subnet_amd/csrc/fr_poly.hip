@@ -319,6 +319,76 @@ void launch_fr_combine_points(hipStream_t s, const RowTab& rt, uint64_t n, uint3
     if (n && m) k_fr_combine_points<<<dim3(nblk(n, 256), m), 256, 0, s>>>(rt, n, ca, out_mont, bad);
 }
 
+// ---- the caller-weighted combinations (kzg_rows_open_lincomb): grid row p computes h_p[t] = sum_j lambda_{p,j} c_j[t] over
+// the rows j of la.mask[p] (the nonzero coefficients; row j read at rt.r[j]).  HBM-bound like k_fr_combine_points: one
+// product and one lazy sum per row and element.  The coefficients ride in the kernel argument as big-endian bytes; the
+// first lanes of every workgroup convert the point's coefficients to Montgomery form ONCE into LDS (one product per
+// coefficient, in parallel), so the element loop pays no conversion.  The sum is renormalised after every term (limbs
+// < 2^30, value < 32r after 16 terms: a legal fr9_reduce input).  Workgroup (0, p) range-checks the coefficients and
+// converts the point for the openings behind the launch.
+struct LincArg {
+    FrArg lam[POLY_MAX_POINTS][POLY_MAX_ROWS];
+    FrArg a[POLY_MAX_POINTS];
+    uint32_t mask[POLY_MAX_POINTS];
+};
+// HIP takes 4 KB of kernel arguments per launch (the CUDA limit it mirrors); this one is 2.4 KB with the table beside it
+static_assert(sizeof(LincArg) + sizeof(RowTab) + 64 <= 4096, "k_fr_lincomb_points' arguments must fit in 4 KB");
+__global__ void __launch_bounds__(256) k_fr_lincomb_points(const RowTab rt, uint64_t n, const LincArg la,
+                                                            uint32_t* __restrict__ out, uint32_t* __restrict__ alpha_mont,
+                                                            uint32_t* __restrict__ bad) {
+    __shared__ uint32_t lam[POLY_MAX_ROWS][9];
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t p = blockIdx.y, mask = la.mask[p], v = threadIdx.x;
+    if (v < POLY_MAX_ROWS && ((mask >> v) & 1u)) {
+        uint32_t w[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) w[i] = bswap32(la.lam[p][v].w[7 - i]);
+        if (blockIdx.x == 0 && fr_words_ge_r(w)) atomicOr(bad, 1u);
+        fr9_t c;
+        fr9_from_words(c, w);
+        fr9_to_mont(c, c);
+#pragma unroll
+        for (int i = 0; i < 9; i++) lam[v][i] = c.l[i];
+    } else if (v == POLY_MAX_ROWS && blockIdx.x == 0) {   // the point, as the pair kernels' first level publishes it
+        uint32_t w[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) w[i] = bswap32(la.a[p].w[7 - i]);
+        if (fr_words_ge_r(w)) atomicOr(bad, 1u);
+        fr9_t a;
+        fr9_from_words(a, w);
+        fr9_to_mont(a, a);
+        fr9_store(alpha_mont + 8 * p, a);
+    }
+    __syncthreads();
+    if (t >= n) return;
+    fr9_t s, c, l;
+    fr9_zero(s);
+    for (uint32_t mk = mask; mk; mk &= mk - 1) {
+        const int j = __builtin_ctz(mk);
+        fr9_load(c, rt.r[j] + 8 * t);
+#pragma unroll
+        for (int i = 0; i < 9; i++) l.l[i] = lam[j][i];
+        fr9_mul(c, c, l);
+        fr9_add(s, s, c);
+        fr9_norm(s, s);
+    }
+    fr9_reduce(s, s);
+    fr9_store(out + 8 * ((uint64_t)p * n + t), s);
+}
+void launch_fr_lincomb_points(hipStream_t s, const RowTab& rt, uint64_t n, uint32_t m, uint32_t k, const uint8_t* coeffs_be32,
+                              const uint32_t* masks, const uint8_t* points_be32, uint32_t* out_mont, uint32_t* alpha_mont,
+                              uint32_t* bad) {
+    if (!n || !m || m > POLY_MAX_POINTS || k > POLY_MAX_ROWS) return;
+    LincArg la;
+    memset(&la, 0, sizeof(la));
+    for (uint32_t p = 0; p < m; p++) {
+        la.mask[p] = masks[p];
+        memcpy(la.a[p].w, points_be32 + 32 * (size_t)p, 32);
+        for (uint32_t j = 0; j < k; j++) memcpy(la.lam[p][j].w, coeffs_be32 + 32 * ((size_t)p * k + j), 32);
+    }
+    k_fr_lincomb_points<<<dim3(nblk(n, 256), m), 256, 0, s>>>(rt, n, la, out_mont, alpha_mont, bad);
+}
+
 // ---- long rows (16 coefficients per lane): the quotient (and, as an A/B form, the level-0 fold) with the coefficients
 // staged through LDS.  A lane of the kernels above walks ITS 512-byte chunk, so one wave load touches 64 pieces of 32
 // bytes at a 512-byte stride (k_poly_quotient: 2.3 TB/s for 256 MB, with the caches reassembling the lines).  Here ONE
@@ -545,14 +615,15 @@ void launch_poly_eval_pairs(hipStream_t s, const RowTab& rt, uint64_t n, uint32_
 // the levels go up with the pair kernels (pair p = combination p at point p), then back down as in launch_poly_open with
 // grid y = point; long rows' LDS-staged quotient runs once per point
 void launch_poly_open_points(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t m, const uint32_t* alpha_mont,
-                             uint32_t* h, uint32_t* hnext, uint64_t h_rs, uint32_t* y_mont, uint32_t* q_canon) {
+                             uint32_t* h, uint32_t* hnext, uint64_t h_rs, uint32_t* y_mont, uint32_t* q_canon,
+                             uint8_t* y_be) {
     if (!n || !m) return;
     PairArg pa;
     memset(&pa, 0, sizeof(pa));
     for (uint32_t p = 0; p < m; p++) pa.row[p] = pa.pt[p] = (uint8_t)p;
     PolyLevels lv;
     uint32_t* am = const_cast<uint32_t*>(alpha_mont);   // (read only: no point is converted on this path)
-    poly_up(s, f_mont, n, m, am, h, hnext, h_rs, y_mont, nullptr, nullptr, nullptr, lv, &pa);
+    poly_up(s, f_mont, n, m, am, h, hnext, h_rs, y_mont, nullptr, nullptr, y_be, lv, &pa);
     const int l0 = lv.l[0], K = lv.K;
     for (int k = K - 1; k >= 1; k--)
         k_poly_pairs_expand<<<dim3(nblk(lv.n[k + 1], 256), m), 256, 0, s>>>(h + 8 * lv.off[k], lv.n[k], lv.l[k], alpha_mont,

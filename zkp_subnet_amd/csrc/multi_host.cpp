@@ -26,6 +26,10 @@ namespace kzg_impl {
 int rows_open_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
                    const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
                    uint8_t* out_proofs48);
+int rows_eval_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
+                   const uint8_t* points_be32, const uint32_t* masks, uint8_t* out_evals32);
+int rows_lincomb_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
+                      const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32, uint8_t* out_proofs48);
 int rows_release_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle);
 }  // namespace kzg_impl
 
@@ -405,6 +409,22 @@ int kzg_multi_rows_open(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uin
     if (int rc = route(mh, i, &c, &s)) return rc;
     return relay(c, kzg_impl::rows_open_impl(c, s, n_handles, handles, m, points_be32, masks, gammas_be32, out_evals32,
                                              out_proofs48));
+}
+int kzg_multi_rows_eval(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
+                        const uint8_t* points_be32, const uint32_t* masks, uint8_t* out_evals32) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_eval_impl(c, s, n_handles, handles, m, points_be32, masks, out_evals32));
+}
+int kzg_multi_rows_open_lincomb(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t k,
+                                uint32_t m, const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32,
+                                uint8_t* out_proofs48) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_lincomb_impl(c, s, n_handles, handles, k, m, points_be32, coeffs_be32, out_values32,
+                                                out_proofs48));
 }
 int kzg_multi_rows_release(kzg_multi* mh, uint32_t i, uint64_t handle) {
     kzg_ctx* c;

@@ -13,6 +13,7 @@
 #include <cerrno>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <system_error>
@@ -674,9 +675,54 @@ int kzg_vk_verify_open_batch(const kzg_vk* vk, uint32_t i, uint32_t k, const uin
     }
 }
 
-/* The multi-point opening: point p reduces to D_p = A_p + alpha_p pi_p with e(D_p, [1]_2) == e(pi_p, [tau_x]_2); the m
- * checks are folded with random 128-bit weights into e(sum_p r_p D_p, [1]_2) * e(-sum_p r_p pi_p, [tau_x]_2) == 1.  A_p by
- * Horner from the point's last masked row.  One thread per point. */
+/* The m per-point checks e(A_p, [1]_2) == e(pi_p, [tau_x - alpha_p]_2) of a multi-point or caller-weighted opening: point p
+ * reduces to D_p = A_p + alpha_p pi_p with e(D_p, [1]_2) == e(pi_p, [tau_x]_2), and the m checks are folded with random
+ * 128-bit weights into e(sum_p r_p D_p, [1]_2) * e(-sum_p r_p pi_p, [tau_x]_2) == 1.  a_of(p) builds A_p (on its own thread:
+ * one thread per point).  proofs48 are decompressed and checked here; a bad one is valid = 0. */
+static int verify_points_folded(const kzg_vk* vk, uint32_t m, const u64 (*alpha)[4], const uint8_t* proofs48,
+                                const std::function<Jac<Fp>(uint32_t)>& a_of, int* out_valid) {
+    u64 w[2 * KZG_MAX_OPEN_POINTS];                      // the weights: 128 random bits per point
+    {
+        size_t need = 2 * (size_t)m * sizeof(u64), got = 0;
+        while (got < need) {
+            const ssize_t r = getrandom(reinterpret_cast<uint8_t*>(w) + got, need - got, 0);
+            if (r < 0 && errno == EINTR) continue;
+            if (r <= 0) return KZG_E_NOMEM;
+            got += (size_t)r;
+        }
+    }
+    std::vector<G1A> pi(m);
+    for (uint32_t p = 0; p < m; p++)
+        if (!g1_decompress(pi[p], proofs48 + 48 * (size_t)p) || !g1_in_subgroup_fast(pi[p])) return KZG_OK;
+    Jac<Fp> accD[KZG_MAX_OPEN_POINTS], accP[KZG_MAX_OPEN_POINTS];
+    auto work = [&](uint32_t p) {
+        const Jac<Fp> d = jac_add(a_of(p), jac_mul(pi[p], alpha[p], 4));
+        accD[p] = jac_mul(to_aff(d), &w[2 * (size_t)p], 2);
+        accP[p] = jac_mul(pi[p], &w[2 * (size_t)p], 2);
+    };
+    {
+        std::vector<std::thread> th;
+        uint32_t started = 1;                            // point 0 runs on the caller
+        try {
+            for (uint32_t p = 1; p < m; p++, started++) th.emplace_back(work, p);
+        } catch (const std::system_error&) {             // out of threads: the caller takes the points nobody got
+        }
+        work(0);
+        for (uint32_t p = started; p < m; p++) work(p);
+        for (auto& x : th) x.join();
+    }
+    Jac<Fp> D = jac_inf<Fp>(), P = jac_inf<Fp>();
+    for (uint32_t p = 0; p < m; p++) {
+        D = jac_add(D, accD[p]);
+        P = jac_add(P, accP[p]);
+    }
+    const Fp12 f = miller_loop(to_aff(D), vk->k.g2) * miller_loop(aff_neg(to_aff(P)), vk->k.tau_g2);
+    *out_valid = is_one(final_exp_fast(f)) ? 1 : 0;
+    return KZG_OK;
+}
+
+/* The multi-point opening: A_p = sum_t gamma_p^t C_{j_t} - (sum_t gamma_p^t y_{j_t,p}) L_i by Horner from the point's last
+ * masked row, folded by verify_points_folded. */
 int kzg_vk_verify_open_multi(const kzg_vk* vk, uint32_t i, uint32_t k, const uint8_t* commitments48, uint32_t m,
                              const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32,
                              const uint8_t* evals_be32, const uint8_t* proofs48, int* out_valid) {
@@ -697,26 +743,13 @@ int kzg_vk_verify_open_multi(const kzg_vk* vk, uint32_t i, uint32_t k, const uin
     for (uint32_t t = 0; t < npairs; t++)
         if (!fr_from_be32(&y[4 * (size_t)t], evals_be32 + 32 * (size_t)t)) return KZG_E_SCALAR;
     try {
-        u64 w[2 * KZG_MAX_OPEN_POINTS];                      // the weights: 128 random bits per point
-        {
-            size_t need = 2 * (size_t)m * sizeof(u64), got = 0;
-            while (got < need) {
-                const ssize_t r = getrandom(reinterpret_cast<uint8_t*>(w) + got, need - got, 0);
-                if (r < 0 && errno == EINTR) continue;
-                if (r <= 0) return KZG_E_NOMEM;
-                got += (size_t)r;
-            }
-        }
         // malformed or off-curve / out-of-subgroup group elements are an invalid proof, not a call failure
-        std::vector<G1A> c(k), pi(m);
+        std::vector<G1A> c(k);
         for (uint32_t j = 0; j < k; j++)
             if (!g1_decompress(c[j], commitments48 + 48 * (size_t)j) || !g1_in_subgroup_fast(c[j])) return KZG_OK;
-        for (uint32_t p = 0; p < m; p++)
-            if (!g1_decompress(pi[p], proofs48 + 48 * (size_t)p) || !g1_in_subgroup_fast(pi[p])) return KZG_OK;
         uint32_t first[KZG_MAX_OPEN_POINTS];                 // the point's first evaluation
         for (uint32_t p = 0, t = 0; p < m; t += (uint32_t)__builtin_popcount(masks[p]), p++) first[p] = t;
-        Jac<Fp> accD[KZG_MAX_OPEN_POINTS], accP[KZG_MAX_OPEN_POINTS];
-        auto work = [&](uint32_t p) {
+        return verify_points_folded(vk, m, alpha, proofs48, [&](uint32_t p) {
             const uint32_t mask = masks[p];
             int j = 31 - __builtin_clz(mask);
             uint32_t t = first[p] + (uint32_t)__builtin_popcount(mask) - 1;
@@ -731,29 +764,49 @@ int kzg_vk_verify_open_multi(const kzg_vk* vk, uint32_t i, uint32_t k, const uin
                 fr_add_mod(ys, &y[4 * (size_t)t]);
             }
             const Jac<Fp> yl = jac_mul(vk->k.li[i], ys, 4);
-            const Jac<Fp> d = jac_add(jac_add(cs, to_jac(aff_neg(to_aff(yl)))), jac_mul(pi[p], alpha[p], 4));
-            accD[p] = jac_mul(to_aff(d), &w[2 * (size_t)p], 2);
-            accP[p] = jac_mul(pi[p], &w[2 * (size_t)p], 2);
-        };
-        {
-            std::vector<std::thread> th;
-            uint32_t started = 1;                            // point 0 runs on the caller
-            try {
-                for (uint32_t p = 1; p < m; p++, started++) th.emplace_back(work, p);
-            } catch (const std::system_error&) {             // out of threads: the caller takes the points nobody got
+            return jac_add(cs, to_jac(aff_neg(to_aff(yl))));
+        }, out_valid);
+    } catch (...) {
+        return KZG_E_NOMEM;
+    }
+}
+
+/* The caller-weighted opening: A_p = sum_j lambda_{p,j} C_j - v_p L_i from explicit coefficients (a zero one skipped),
+ * folded by verify_points_folded. */
+int kzg_vk_verify_open_lincomb(const kzg_vk* vk, uint32_t i, uint32_t k, const uint8_t* commitments48, uint32_t m,
+                               const uint8_t* points_be32, const uint8_t* coeffs_be32, const uint8_t* values_be32,
+                               const uint8_t* proofs48, int* out_valid) {
+    if (!vk || !commitments48 || !points_be32 || !coeffs_be32 || !values_be32 || !proofs48 || !out_valid) return KZG_E_ARG;
+    *out_valid = 0;
+    if (k == 0 || k > KZG_MAX_BATCH_OPEN || m == 0 || m > KZG_MAX_OPEN_POINTS || i >= vk->k.li.size()) return KZG_E_ARG;
+    u64 alpha[KZG_MAX_OPEN_POINTS][4], v[KZG_MAX_OPEN_POINTS][4];
+    std::vector<u64> lam(4 * (size_t)m * k);
+    int status = KZG_OK;
+    for (uint32_t p = 0; p < m; p++) {
+        if (!fr_from_be32(alpha[p], points_be32 + 32 * (size_t)p) || !fr_from_be32(v[p], values_be32 + 32 * (size_t)p))
+            return KZG_E_SCALAR;
+        bool any = false;
+        for (uint32_t j = 0; j < k; j++) {
+            u64* l = &lam[4 * ((size_t)p * k + j)];
+            if (!fr_from_be32(l, coeffs_be32 + 32 * ((size_t)p * k + j))) return KZG_E_SCALAR;
+            any = any || (l[0] | l[1] | l[2] | l[3]) != 0;
+        }
+        if (!any) status = KZG_E_ARG;                        // (a non-canonical scalar of a later point still wins)
+    }
+    if (status) return status;
+    try {
+        std::vector<G1A> c(k);
+        for (uint32_t j = 0; j < k; j++)
+            if (!g1_decompress(c[j], commitments48 + 48 * (size_t)j) || !g1_in_subgroup_fast(c[j])) return KZG_OK;
+        return verify_points_folded(vk, m, alpha, proofs48, [&](uint32_t p) {
+            Jac<Fp> a = jac_mul(vk->k.li[i], v[p], 4);
+            a = to_jac(aff_neg(to_aff(a)));
+            for (uint32_t j = 0; j < k; j++) {
+                const u64* l = &lam[4 * ((size_t)p * k + j)];
+                if (l[0] | l[1] | l[2] | l[3]) a = jac_add(a, jac_mul(c[j], l, 4));
             }
-            work(0);
-            for (uint32_t p = started; p < m; p++) work(p);
-            for (auto& x : th) x.join();
-        }
-        Jac<Fp> D = jac_inf<Fp>(), P = jac_inf<Fp>();
-        for (uint32_t p = 0; p < m; p++) {
-            D = jac_add(D, accD[p]);
-            P = jac_add(P, accP[p]);
-        }
-        const Fp12 f = miller_loop(to_aff(D), vk->k.g2) * miller_loop(aff_neg(to_aff(P)), vk->k.tau_g2);
-        *out_valid = is_one(final_exp_fast(f)) ? 1 : 0;
-        return KZG_OK;
+            return a;
+        }, out_valid);
     } catch (...) {
         return KZG_E_NOMEM;
     }

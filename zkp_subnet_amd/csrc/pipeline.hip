@@ -500,47 +500,68 @@ static int ensure_multi_record(kzg_ctx* ctx, Lane& A) {
     }
     return KZG_OK;
 }
+// the masked (row, point) pairs of nrows rows at m points, point-major, ascending rows inside a point (the order of
+// out_evals32), with the points as the evaluations' kernel argument; rows past KZG_BATCHED_ROW_MAX are evaluated in groups
+// of KZG_MAX_BATCH_OPEN pairs (their level scratch is large)
+struct PairPlan {
+    PairArg pa;
+    uint32_t npairs, group;
+    uint64_t hrow;   // level scratch of one pair (or one point's combination), words
+};
+static void plan_pairs(PairPlan& pp, uint32_t nrows, uint64_t T, uint32_t m, const uint8_t* points_be32,
+                       const uint32_t* masks) {
+    memset(&pp.pa, 0, sizeof(pp.pa));
+    pp.npairs = 0;
+    for (uint32_t p = 0; p < m; p++) {
+        memcpy(pp.pa.a[p].w, points_be32 + 32 * (size_t)p, 32);
+        for (uint32_t j = 0; j < nrows; j++)
+            if ((masks[p] >> j) & 1u) {
+                pp.pa.row[pp.npairs] = (uint8_t)j;
+                pp.pa.pt[pp.npairs++] = (uint8_t)p;
+            }
+    }
+    const uint64_t nchunks = (T + 3) / 4;
+    pp.hrow = (nchunks + (nchunks >> 1) + 64) * 8;
+    pp.group = T <= KZG_BATCHED_ROW_MAX ? pp.npairs : std::min<uint32_t>(pp.npairs, KZG_MAX_BATCH_OPEN);
+}
+// every pair evaluated (rows read at rt.r[j]): the evaluations land in the record (MR_EVAL big-endian, MR_Y_M Montgomery),
+// the points' Montgomery forms at MR_ALPHA_M.  The lane's level scratch must hold pp.group pairs.
+static void launch_pairs(Lane& A, const RowTab& rt, uint64_t T, const PairPlan& pp) {
+    uint8_t* rec = A.brec.as<uint8_t>();
+    uint32_t* alpha_m = reinterpret_cast<uint32_t*>(rec + MR_ALPHA_M);
+    for (uint32_t g0 = 0; g0 < pp.npairs; g0 += pp.group) {   // the points ride in as arguments of each group's first kernel
+        const uint32_t ng = std::min(pp.group, pp.npairs - g0);
+        PairArg ga = pp.pa;
+        memmove(ga.row, pp.pa.row + g0, ng);
+        memmove(ga.pt, pp.pa.pt + g0, ng);
+        launch_poly_eval_pairs(A.stream, rt, T, ng, ga, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), pp.hrow,
+                               reinterpret_cast<uint32_t*>(rec + MR_Y_M) + 8 * g0, A.flags(), rec + MR_EVAL + 32 * g0);
+    }
+}
 // the openings of nrows rows (row j's Montgomery coefficients at rt.r[j]) at m points: the pairs' evaluations land in the
 // record (MR_EVAL, point-major), the m quotients in A.qbuf as m consecutive length-T canonical scalar sets
 static int multi_open_poly(kzg_ctx* ctx, Lane& A, const RowTab& rt, uint32_t nrows, uint64_t T, uint32_t m,
                            const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint32_t* out_npairs) {
     hipStream_t s = A.stream;
-    // the pairs, point-major, ascending rows inside a point (the order of out_evals32)
-    PairArg pa;
-    memset(&pa, 0, sizeof(pa));
+    PairPlan pp;
+    plan_pairs(pp, nrows, T, m, points_be32, masks);
     CombArg ca;
     memset(&ca, 0, sizeof(ca));
-    uint32_t npairs = 0;
     for (uint32_t p = 0; p < m; p++) {
-        memcpy(pa.a[p].w, points_be32 + 32 * (size_t)p, 32);
         memcpy(ca.g[p].w, gammas_be32 + 32 * (size_t)p, 32);
         ca.mask[p] = masks[p];
-        for (uint32_t j = 0; j < nrows; j++)
-            if ((masks[p] >> j) & 1u) {
-                pa.row[npairs] = (uint8_t)j;
-                pa.pt[npairs++] = (uint8_t)p;
-            }
     }
     uint8_t* rec = A.brec.as<uint8_t>();
     uint32_t* alpha_m = reinterpret_cast<uint32_t*>(rec + MR_ALPHA_M);
-    const uint64_t nchunks = (T + 3) / 4;
-    const uint64_t hrow = (nchunks + (nchunks >> 1) + 64) * 8;   // level scratch of one pair, words
-    const bool batched = T <= KZG_BATCHED_ROW_MAX;
-    const uint32_t group = batched ? npairs : std::min<uint32_t>(npairs, KZG_MAX_BATCH_OPEN);   // pairs per evaluation
-    HIPCHK(ctx, A.hbuf.ensure(std::max(group, m) * hrow * 4));
-    HIPCHK(ctx, A.hnext.ensure(std::max(group, m) * hrow * 4));
+    const uint64_t hrow = pp.hrow;
+    HIPCHK(ctx, A.hbuf.ensure(std::max(pp.group, m) * hrow * 4));
+    HIPCHK(ctx, A.hnext.ensure(std::max(pp.group, m) * hrow * 4));
     HIPCHK(ctx, A.bcomb.ensure(m * T * 32));
     HIPCHK(ctx, A.qbuf.ensure(m * T * 32));
     uint32_t* hcomb = A.bcomb.as<uint32_t>();
+    const uint32_t npairs = pp.npairs;
     Span sp(ctx, A, KZG_T_POLY);
-    for (uint32_t g0 = 0; g0 < npairs; g0 += group) {   // the points ride in as arguments of each group's first kernel
-        const uint32_t ng = std::min(group, npairs - g0);
-        PairArg ga = pa;
-        memmove(ga.row, pa.row + g0, ng);
-        memmove(ga.pt, pa.pt + g0, ng);
-        launch_poly_eval_pairs(s, rt, T, ng, ga, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), hrow,
-                               reinterpret_cast<uint32_t*>(rec + MR_Y_M) + 8 * g0, A.flags(), rec + MR_EVAL + 32 * g0);
-    }
+    launch_pairs(A, rt, T, pp);
     launch_fr_combine_points(s, rt, T, m, ca, hcomb, A.flags());
     // k_poly_quotient leaves a zero in slot T - 1: each quotient rides as one more length-T scalar set
     launch_poly_open_points(s, hcomb, T, m, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), hrow,
@@ -655,6 +676,48 @@ int rows_open_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint3
     uint32_t npairs = 0;
     if (int rc = multi_open_poly(ctx, A, rt, k, T, m, points_be32, masks, gammas_be32, &npairs)) return rc;
     return multi_msms_finish(ctx, H, i, T, nullptr, 0, m, npairs, nullptr, out_evals32, out_p48);
+}
+// The evaluations alone (kzg_rows_eval): the open's pair evaluations, then the record -- no combination, no quotient, no MSM.
+int rows_eval_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t k, uint64_t T, uint32_t m,
+                  const uint8_t* points_be32, const uint32_t* masks, uint8_t* out_evals32) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    PairPlan pp;
+    plan_pairs(pp, k, T, m, points_be32, masks);
+    HIPCHK(ctx, A.hbuf.ensure(pp.group * pp.hrow * 4));
+    HIPCHK(ctx, A.hnext.ensure(pp.group * pp.hrow * 4));
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_pairs(A, rt, T, pp);
+    }
+    A.expect_short = true;   // a few scans, no MSM: finish() may poll for the record
+    return multi_msms_finish(ctx, H, i, T, nullptr, 0, 0, pp.npairs, nullptr, out_evals32, nullptr);
+}
+// The caller-weighted openings (kzg_rows_open_lincomb): the m combinations h_p = sum_j lambda_{p,j} f_j in one launch
+// (k_fr_lincomb_points, which also converts the points), their m openings side by side -- v_p = h_p(alpha_p) leaves the
+// quotient scan big-endian in the MR_EVAL slots, which no pair uses here -- and the m quotient MSMs.  No pair evaluation,
+// no commitment MSM.
+int rows_lincomb_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t k, uint64_t T, uint32_t m,
+                     const uint8_t* points_be32, const uint8_t* coeffs_be32, const uint32_t* masks, uint8_t* out_values32,
+                     uint8_t* out_p48) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    uint8_t* rec = A.brec.as<uint8_t>();
+    uint32_t* alpha_m = reinterpret_cast<uint32_t*>(rec + MR_ALPHA_M);
+    const uint64_t nchunks = (T + 3) / 4;
+    const uint64_t hrow = (nchunks + (nchunks >> 1) + 64) * 8;   // level scratch of one point's combination, words
+    HIPCHK(ctx, A.hbuf.ensure(m * hrow * 4));
+    HIPCHK(ctx, A.hnext.ensure(m * hrow * 4));
+    HIPCHK(ctx, A.bcomb.ensure(m * T * 32));
+    HIPCHK(ctx, A.qbuf.ensure(m * T * 32));
+    uint32_t* hcomb = A.bcomb.as<uint32_t>();
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_fr_lincomb_points(A.stream, rt, T, m, k, coeffs_be32, masks, points_be32, hcomb, alpha_m, A.flags());
+        launch_poly_open_points(A.stream, hcomb, T, m, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), hrow,
+                                reinterpret_cast<uint32_t*>(rec + MR_HY_M), A.qbuf.as<uint32_t>(), rec + MR_EVAL);
+    }
+    return multi_msms_finish(ctx, H, i, T, nullptr, 0, m, m, nullptr, out_values32, out_p48);
 }
 
 }  // namespace kzg_impl

@@ -667,6 +667,42 @@ struct RowsRefs {
     }
 };
 
+// the sets named by `handles` (lane held, so that an SRS load cannot free their buffers under the caller): their rows into
+// rt, numbered by concatenation, the worker and row length into *i / *T, one reference per set into refs.  `what` prefixes
+// the messages.
+static int rows_lookup(kzg_ctx* ctx, const char* what, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                       RowsRefs& refs, RowTab& rt, uint32_t* out_k, uint32_t* out_i, uint64_t* out_T) {
+    auto bad = [&](const char* why) { return fail(ctx, KZG_E_ARG, std::string(what) + why); };
+    memset(&rt, 0, sizeof(rt));
+    uint32_t k = 0, i = 0;
+    uint64_t T = 0;
+    std::lock_guard<std::mutex> lk(ctx->sets_mu);
+    for (uint32_t t = 0; t < n_handles; t++) {
+        auto it = ctx->sets.find(handles[t]);
+        if (it == ctx->sets.end() || it->second.released) return bad(": unknown or released handle");
+        kzg_ctx::RowSet& st = it->second;
+        if (st.stale)
+            return bad(": the set was committed under an SRS that has since been reloaded (its commitments no longer "
+                       "hold): release it and commit its rows again");
+        if (t == 0) {
+            i = st.i;
+            T = st.T;
+        } else if (st.i != i || st.T != T) {
+            return bad(": all sets must belong to one worker and have one row length");
+        }
+        if (expect_i != UINT32_MAX && st.i != expect_i) return bad(": the set belongs to another worker");
+        if (k + st.k > KZG_MAX_BATCH_OPEN) return bad(": more than KZG_MAX_BATCH_OPEN rows in all");
+        for (uint32_t j = 0; j < st.k; j++) rt.r[k + j] = st.buf.as<uint32_t>() + (uint64_t)j * st.T * 8;
+        k += st.k;
+        st.refs++;
+        refs.h[refs.n++] = handles[t];
+    }
+    *out_k = k;
+    *out_i = i;
+    *out_T = T;
+    return KZG_OK;
+}
+
 int rows_open_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
                    const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
                    uint8_t* out_proofs48) {
@@ -684,35 +720,9 @@ int rows_open_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const ui
     if (int rc = H.take()) return rc;   // (before the lookup: an SRS load cannot free the sets' buffers under this call)
     Lane& L = H.L();
     RowTab rt;
-    memset(&rt, 0, sizeof(rt));
     uint32_t k = 0, i = 0;
     uint64_t T = 0;
-    {
-        std::lock_guard<std::mutex> lk(ctx->sets_mu);
-        for (uint32_t t = 0; t < n_handles; t++) {
-            auto it = ctx->sets.find(handles[t]);
-            if (it == ctx->sets.end() || it->second.released)
-                return fail(ctx, KZG_E_ARG, "row-set opening: unknown or released handle");
-            kzg_ctx::RowSet& st = it->second;
-            if (st.stale)
-                return fail(ctx, KZG_E_ARG, "row-set opening: the set was committed under an SRS that has since been "
-                                            "reloaded (its commitments no longer hold): release it and commit its rows again");
-            if (t == 0) {
-                i = st.i;
-                T = st.T;
-            } else if (st.i != i || st.T != T) {
-                return fail(ctx, KZG_E_ARG, "row-set opening: all sets must belong to one worker and have one row length");
-            }
-            if (expect_i != UINT32_MAX && st.i != expect_i)
-                return fail(ctx, KZG_E_ARG, "row-set opening: the set belongs to another worker");
-            if (k + st.k > KZG_MAX_BATCH_OPEN)
-                return fail(ctx, KZG_E_ARG, "row-set opening: more than KZG_MAX_BATCH_OPEN rows in all");
-            for (uint32_t j = 0; j < st.k; j++) rt.r[k + j] = st.buf.as<uint32_t>() + (uint64_t)j * st.T * 8;
-            k += st.k;
-            st.refs++;
-            refs.h[refs.n++] = handles[t];
-        }
-    }
+    if (int rc = rows_lookup(ctx, "row-set opening", expect_i, n_handles, handles, refs, rt, &k, &i, &T)) return rc;
     for (uint32_t p = 0; p < m; p++)
         if (masks[p] == 0 || (masks[p] >> k) != 0)
             return fail(ctx, KZG_E_ARG, "row-set opening: every mask must name at least one row, and rows < k only");
@@ -722,6 +732,75 @@ int rows_open_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const ui
     rc = clear_flags(ctx, L);
     if (rc) return rc;
     return rows_open_dev(ctx, H, i, rt, k, T, m, points_be32, masks, gammas_be32, out_evals32, out_proofs48);
+}
+
+// kzg_rows_eval: the checks and lookup of kzg_rows_open without the gammas
+int rows_eval_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
+                   const uint8_t* points_be32, const uint32_t* masks, uint8_t* out_evals32) {
+    if (!ctx || !handles || !points_be32 || !masks || !out_evals32) return KZG_E_ARG;
+    if (n_handles == 0 || n_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "row-set evaluation: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (m == 0 || m > KZG_MAX_OPEN_POINTS)
+        return fail(ctx, KZG_E_ARG, "row-set evaluation: m must be in [1, KZG_MAX_OPEN_POINTS]");
+    for (uint32_t p = 0; p < m; p++)
+        if (!fr_be32_canonical(points_be32 + 32 * (size_t)p))
+            return fail(ctx, KZG_E_ARG, "row-set evaluation: points must be canonical scalars (< r)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsRefs refs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;
+    Lane& L = H.L();
+    RowTab rt;
+    uint32_t k = 0, i = 0;
+    uint64_t T = 0;
+    if (int rc = rows_lookup(ctx, "row-set evaluation", expect_i, n_handles, handles, refs, rt, &k, &i, &T)) return rc;
+    for (uint32_t p = 0; p < m; p++)
+        if (masks[p] == 0 || (masks[p] >> k) != 0)
+            return fail(ctx, KZG_E_ARG, "row-set evaluation: every mask must name at least one row, and rows < k only");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    return rows_eval_dev(ctx, H, i, rt, k, T, m, points_be32, masks, out_evals32);
+}
+
+// kzg_rows_open_lincomb: every coefficient is range-checked here, and each point's mask of nonzero coefficients built
+int rows_lincomb_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
+                      const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32, uint8_t* out_proofs48) {
+    if (!ctx || !handles || !points_be32 || !coeffs_be32 || !out_values32 || !out_proofs48) return KZG_E_ARG;
+    if (n_handles == 0 || n_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "row-set lincomb: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (m == 0 || m > KZG_MAX_OPEN_POINTS) return fail(ctx, KZG_E_ARG, "row-set lincomb: m must be in [1, KZG_MAX_OPEN_POINTS]");
+    if (k == 0 || k > KZG_MAX_BATCH_OPEN) return fail(ctx, KZG_E_ARG, "row-set lincomb: k must be in [1, KZG_MAX_BATCH_OPEN]");
+    uint32_t masks[KZG_MAX_OPEN_POINTS] = {};
+    static const uint8_t zero[32] = {};
+    for (uint32_t p = 0; p < m; p++) {
+        if (!fr_be32_canonical(points_be32 + 32 * (size_t)p))
+            return fail(ctx, KZG_E_ARG, "row-set lincomb: points must be canonical scalars (< r)");
+        for (uint32_t j = 0; j < k; j++) {
+            const uint8_t* c = coeffs_be32 + 32 * ((size_t)p * k + j);
+            if (!fr_be32_canonical(c)) return fail(ctx, KZG_E_ARG, "row-set lincomb: coefficients must be canonical scalars (< r)");
+            if (memcmp(c, zero, 32) != 0) masks[p] |= 1u << j;
+        }
+        if (!masks[p]) return fail(ctx, KZG_E_ARG, "row-set lincomb: every point needs a nonzero coefficient");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsRefs refs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;
+    Lane& L = H.L();
+    RowTab rt;
+    uint32_t nrows = 0, i = 0;
+    uint64_t T = 0;
+    if (int rc = rows_lookup(ctx, "row-set lincomb", expect_i, n_handles, handles, refs, rt, &nrows, &i, &T)) return rc;
+    if (nrows != k) return fail(ctx, KZG_E_ARG, "row-set lincomb: k must equal the rows of the concatenated sets");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    return rows_lincomb_dev(ctx, H, i, rt, k, T, m, points_be32, coeffs_be32, masks, out_values32, out_proofs48);
 }
 
 int rows_release_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle) {
@@ -805,6 +884,14 @@ int kzg_rows_open(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uin
                   const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32, uint8_t* out_proofs48) {
     return rows_open_impl(ctx, UINT32_MAX, n_handles, handles, m, points_be32, masks, gammas_be32, out_evals32,
                           out_proofs48);
+}
+int kzg_rows_eval(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t m, const uint8_t* points_be32,
+                  const uint32_t* masks, uint8_t* out_evals32) {
+    return rows_eval_impl(ctx, UINT32_MAX, n_handles, handles, m, points_be32, masks, out_evals32);
+}
+int kzg_rows_open_lincomb(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
+                          const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32, uint8_t* out_proofs48) {
+    return rows_lincomb_impl(ctx, UINT32_MAX, n_handles, handles, k, m, points_be32, coeffs_be32, out_values32, out_proofs48);
 }
 int kzg_rows_release(kzg_ctx* ctx, uint64_t handle) { return rows_release_impl(ctx, UINT32_MAX, handle); }
 int kzg_rows_stats(kzg_ctx* ctx, uint64_t out_live_sets_bytes[2]) {

@@ -332,6 +332,57 @@ class HipEngine:
             t += len(rws)
         return evals, [pf.raw[48 * p:48 * p + 48] for p in range(m)]
 
+    # ---- evaluate first, then open caller-weighted combinations: a Fiat-Shamir prover hashes the evaluations of eval_rows
+    # before it derives the scalars it hands to open_rows_lincomb
+    def eval_rows(self, sets: Sequence[object], points_be32: Sequence[bytes],
+                  opened: Sequence[Sequence[int]]) -> List[List[bytes]]:
+        """The evaluations of committed sets at m <= 4 points (kzg_rows_eval), no proof: rows numbered and `opened` as in
+        open_rows.  Returns [[y_{j,p} for j in opened[p]] for p], byte-identical to open_rows' evaluations."""
+        n, hs = self._handle_array(sets, "eval_rows")
+        masks, npairs = _native.open_masks(opened, self._rows_of(sets))
+        m = len(opened)
+        if len(points_be32) != m or any(len(x) != 32 for x in points_be32):
+            raise KzgError(_native.KZG_E_ARG, "eval_rows: one 32-byte point per opened list")
+        ev = ctypes.create_string_buffer(32 * npairs)
+        self._chk(self._lib.kzg_rows_eval(self._h, n, hs, m, b"".join(points_be32), masks, ev))
+        evals, t = [], 0
+        for rws in opened:
+            evals.append([ev.raw[32 * (t + u):32 * (t + u) + 32] for u in range(len(rws))])
+            t += len(rws)
+        return evals
+
+    def open_rows_lincomb(self, sets: Sequence[object], points_be32: Sequence[bytes],
+                          coeffs: Sequence[Sequence[bytes]]) -> Tuple[List[bytes], List[bytes]]:
+        """One proof per point for h_p = sum_j coeffs[p][j] f_j over the k concatenated rows of committed sets
+        (kzg_rows_open_lincomb): coeffs[p] holds k 32-byte scalars (zero leaves a row out).  Returns ([v_p = h_p(alpha_p)],
+        [pi_p]); verify_open_lincomb checks them against the sets' commitments."""
+        n, hs = self._handle_array(sets, "open_rows_lincomb")
+        m = len(points_be32)
+        if m == 0 or m > _native.KZG_MAX_OPEN_POINTS or len(coeffs) != m:
+            raise KzgError(_native.KZG_E_ARG, f"open_rows_lincomb: {m} points and {len(coeffs)} coefficient lists, "
+                                              f"expected 1 .. {_native.KZG_MAX_OPEN_POINTS} of each")
+        k = len(coeffs[0])
+        if any(len(c) != k for c in coeffs) or any(len(x) != 32 for x in list(points_be32) + [c for cs in coeffs for c in cs]):
+            raise KzgError(_native.KZG_E_ARG, "open_rows_lincomb: one 32-byte point and k 32-byte coefficients per point")
+        vals, pf = ctypes.create_string_buffer(32 * m), ctypes.create_string_buffer(48 * m)
+        self._chk(self._lib.kzg_rows_open_lincomb(self._h, n, hs, k, m, b"".join(points_be32),
+                                                  b"".join(c for cs in coeffs for c in cs), vals, pf))
+        return [vals.raw[32 * p:32 * p + 32] for p in range(m)], [pf.raw[48 * p:48 * p + 48] for p in range(m)]
+
+    def _handle_array(self, sets, what):
+        handles = [int(getattr(x, "handle", x)) for x in sets]
+        n = len(handles)
+        if n == 0 or n > _native.KZG_MAX_BATCH_OPEN:
+            raise KzgError(_native.KZG_E_ARG, f"{what}: {n} sets, expected 1 .. {_native.KZG_MAX_BATCH_OPEN}")
+        return n, (ctypes.c_uint64 * n)(*handles)
+
+    def verify_open_lincomb(self, i: int, commitments48: Sequence[bytes], points32: Sequence[bytes],
+                            coeffs: Sequence[Sequence[bytes]], values32: Sequence[bytes], proofs48: Sequence[bytes]) -> bool:
+        """Pairing check of one caller-weighted opening (open_rows_lincomb) against resident slice i."""
+        if self.verifier is None:
+            raise NotImplementedError("no verifier key: call set_verifier_key() after load_srs()")
+        return self.verifier.verify_open_lincomb(i, commitments48, points32, coeffs, values32, proofs48)
+
     def release_rows(self, handle: int) -> None:
         """Frees a committed set (kzg_rows_release); KzgError(KZG_E_ARG) for an unknown or already released handle."""
         self._chk(self._lib.kzg_rows_release(self._h, int(handle)))

@@ -126,6 +126,18 @@ class MultiDeviceClient:
             return Response(400, {"error": "worker_open_rows: the handles must name live sets of one worker"})
         return self._for(i).worker_open_rows(handles, points, opened, gammas)
 
+    def worker_eval_rows(self, handles: Sequence[int], points, opened):
+        i = self._owner(handles)
+        if i is None:
+            return Response(400, {"error": "worker_eval_rows: the handles must name live sets of one worker"})
+        return self._for(i).worker_eval_rows(handles, points, opened)
+
+    def worker_open_rows_lincomb(self, handles: Sequence[int], points, coeffs):
+        i = self._owner(handles)
+        if i is None:
+            return Response(400, {"error": "worker_open_rows_lincomb: the handles must name live sets of one worker"})
+        return self._for(i).worker_open_rows_lincomb(handles, points, coeffs)
+
     def worker_release_rows(self, handle: int):
         i = self._owner([handle])
         if i is None:
@@ -153,6 +165,9 @@ class MultiDeviceClient:
 
     def worker_verify_open_multi(self, i: int, proofs, points, opened, gammas, evals, commitments):
         return self._for(i).worker_verify_open_multi(i, proofs, points, opened, gammas, evals, commitments)
+
+    def worker_verify_open_lincomb(self, i: int, proofs, points, coeffs, values, commitments):
+        return self._for(i).worker_verify_open_lincomb(i, proofs, points, coeffs, values, commitments)
 
     def worker_verify_batch(self, indices, proofs, alpha, evals, commitments, threads: int = 16):
         """One batched check PER DEVICE, verdicts AND-ed: with a synthetic setup each context holds the slices and

@@ -116,6 +116,27 @@ class Verifier:
             raise KzgError(rc, "kzg_vk_verify_open_multi: bad argument (k, m, mask, index or non-canonical scalar)")
         return bool(ok.value)
 
+    def verify_open_lincomb(self, i: int, commitments48: Sequence[bytes], points32: Sequence[bytes],
+                            coeffs: Sequence[Sequence[bytes]], values32: Sequence[bytes], proofs48: Sequence[bytes]) -> bool:
+        """One caller-weighted opening of k rows of slice i (kzg_vk_verify_open_lincomb): coeffs[p] holds the k scalars of
+        point p; for every p  e(sum_j coeffs[p][j] C_j - v_p L_i, [1]_2) == e(pi_p, [tau_x - alpha_p]_2)."""
+        k, m = len(commitments48), len(points32)
+        if not (m == len(coeffs) == len(values32) == len(proofs48)) or any(len(c) != k for c in coeffs):
+            raise ValueError("verify_open_lincomb: one point, k coefficients, value and proof per point")
+        if k == 0 or k > _native.KZG_MAX_BATCH_OPEN or m == 0 or m > _native.KZG_MAX_OPEN_POINTS:
+            raise KzgError(_native.KZG_E_ARG, f"kzg_vk_verify_open_lincomb: k = {k}, m = {m} outside the limits")
+        flat = [c for cs in coeffs for c in cs]
+        if any(len(x) != 32 for x in list(points32) + flat + list(values32)):
+            raise KzgError(_native.KZG_E_ARG, "kzg_vk_verify_open_lincomb: points / coefficients / values must be 32 bytes")
+        if any(len(c) != 48 for c in list(commitments48) + list(proofs48)):
+            return False
+        ok = ctypes.c_int(0)
+        rc = self._lib.kzg_vk_verify_open_lincomb(self._h, i, k, b"".join(commitments48), m, b"".join(points32),
+                                                  b"".join(flat), b"".join(values32), b"".join(proofs48), ctypes.byref(ok))
+        if rc != 0:
+            raise KzgError(rc, "kzg_vk_verify_open_lincomb: bad argument (k, m, all-zero point, index or non-canonical scalar)")
+        return bool(ok.value)
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._lib.kzg_vk_destroy(self._h)
