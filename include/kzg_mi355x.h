@@ -215,6 +215,32 @@ int kzg_rows_eval(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uin
 int kzg_rows_open_lincomb(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
                           const uint8_t* points_be32 /* m*32 */, const uint8_t* coeffs_be32 /* m*k*32 */,
                           uint8_t* out_values32 /* m*32 */, uint8_t* out_proofs48 /* m*48 */);
+/* A set built FROM sets: the permutation grand product (PLONK round 2), computed and committed on the device from rows that
+ * are already resident.  The wire rows a_0 .. a_{k-1} are the concatenated rows of the wire_handles sets, the permutation rows
+ * sigma_0 .. sigma_{k-1} those of the sigma_handles sets.  With w the T-th root of unity of evaluation_form = 1 rows
+ * (7^((r-1)/T), natural order), s_j = shifts[j] and t in [0, T):
+ *   N_t = prod_j (a_j(w^t) + beta s_j w^t + gamma),   D_t = prod_j (a_j(w^t) + beta sigma_j(w^t) + gamma),
+ *   z(w^0) = 1,  z(w^(t+1)) = z(w^t) N_t / D_t  (t < T - 1),   closing = prod_t N_t / prod_t D_t.
+ * The call creates a new ONE-ROW set of the same worker and length holding z's coefficients, exactly as if z's T evaluations
+ * had gone through kzg_rows_commit(i, 1, z, T, 1, ..): out_commitment48 equals that call's byte for byte and *out_handle opens,
+ * evaluates, combines, releases, goes stale and counts against KZG_MAX_ROW_SETS (KZG_E_BUSY; KZG_E_NOMEM on a failed
+ * allocation) like any other.  out_closing32 is what z(w^T) would be, canonical big-endian: 1 exactly when the product
+ * closes.  The library does not judge it.  Nothing row-sized crosses the host link in either direction.
+ * Handle lists follow kzg_rows_open: 1 .. KZG_MAX_BATCH_OPEN handles each, a handle may repeat, unknown / released / stale ->
+ * KZG_E_ARG; each concatenation must hold exactly k rows, 1 <= k <= KZG_MAX_BATCH_OPEN; every set named must belong to one
+ * worker and one (power-of-two) T; beta, gamma or a shift >= r -> KZG_E_ARG.  A zero denominator (some D_t = 0) leaves z
+ * undefined: KZG_E_ARG with a message that says so, no set created.  The source sets are only read; a release or an SRS
+ * load racing the call follows the rules of kzg_rows_open.  Thread-safe like every call; after any error the context keeps
+ * serving.
+ * SOUNDNESS: beta and gamma must be drawn AFTER the wire commitments are fixed (a prover who knows them before it commits
+ * the wires can make a false permutation close).  The library derives no challenge and adds NO BLINDING: a blinded z has
+ * degree >= T and does not fit a T-point slice; a caller who blinds pads its circuit below T and adds the blinding rows
+ * itself through kzg_rows_open_lincomb. */
+int kzg_rows_commit_grand_product(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                  uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
+                                  const uint8_t* shifts_be32 /* k*32 */, const uint8_t beta_be32[32],
+                                  const uint8_t gamma_be32[32], uint8_t out_commitment48[48], uint8_t out_closing32[32],
+                                  uint64_t* out_handle);
 /* The UNCHANGED reference miner makes two calls per request with the same row -- worker_commit(i, poly), then
  * worker_open(i, poly, x) (neurons/miner.py:56-61).  These forms take a 128-bit content tag identifying the row's bytes
  * (the host codec computes it while decoding the text); the coefficient vectors of the last four rows stay on the
@@ -431,6 +457,11 @@ int kzg_multi_rows_eval(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uin
 int kzg_multi_rows_open_lincomb(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t k,
                                 uint32_t m, const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32,
                                 uint8_t* out_proofs48);
+/* kzg_rows_commit_grand_product on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_grand_product(kzg_multi* mh, uint32_t i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                        uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
+                                        const uint8_t* shifts_be32, const uint8_t beta_be32[32], const uint8_t gamma_be32[32],
+                                        uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

@@ -59,6 +59,8 @@ SYMBOLS = {
     "kzg_rows_stats": (_I, [_P, ctypes.POINTER(_U64)]),
     "kzg_rows_eval": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _B, ctypes.POINTER(_U32), _B]),
     "kzg_rows_open_lincomb": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _U32, _B, _B, _B, _B]),
+    "kzg_rows_commit_grand_product": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _B, _B, _B, _B, _B,
+                                           ctypes.POINTER(_U64)]),
     "kzg_commit_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B]),
     "kzg_open_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B, _B]),
     "kzg_row_cache_stats": (_I, [_P, ctypes.POINTER(_U64)]),
@@ -116,6 +118,8 @@ SYMBOLS = {
     "kzg_multi_rows_release": (_I, [_P, _U32, _U64]),
     "kzg_multi_rows_eval": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _B, ctypes.POINTER(_U32), _B]),
     "kzg_multi_rows_open_lincomb": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _U32, _B, _B, _B, _B]),
+    "kzg_multi_rows_commit_grand_product": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _B, _B, _B,
+                                                 _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_commit_open_rows": (_I, [_P, _U32, ctypes.POINTER(_U32), _B, _U64, _I, _B, _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_upload_fr": (_I, [_P, _I, _B, _U64, _I]),
     "kzg_msm_resident": (_I, [_P, _I, _U64, _U64, _B]),

@@ -316,6 +316,23 @@ class Client:
         return {"values": [codec.be32_to_fr(v) for v in vals], "proofs": [codec.g1_to_b64(pf) for pf in pfs]}
 
     @_guard
+    def worker_commit_grand_product(self, wire_handles: Sequence[int], sigma_handles: Sequence[int], shifts: Sequence[str],
+                                    beta: str, gamma: str):
+        """Extension: the permutation grand product z over the rows of committed sets (wire rows a_j from wire_handles,
+        permutation rows sigma_j from sigma_handles, one shift per row), computed and committed on the device as a new
+        one-row set.  Returns its handle, its commitment and the closing value (1 when the permutation holds).  beta and
+        gamma must be drawn after the wire commitments are fixed."""
+        hw, hs = _handles(wire_handles), _handles(sigma_handles)
+        if not 1 <= len(shifts) <= KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"worker_commit_grand_product: {len(shifts)} shifts, expected 1 .. {KZG_MAX_BATCH_OPEN}")
+        sc = [codec.fr_to_be32(x) for x in list(shifts) + [beta, gamma]]
+        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in sc):
+            raise codec.CodecError("worker_commit_grand_product: shifts, beta and gamma must be canonical scalars (< r)")
+        rs, closing = self.engine.commit_grand_product(hw, hs, sc[:-2], sc[-2], sc[-1])
+        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]),
+                "closing": codec.be32_to_fr(closing)}
+
+    @_guard
     def worker_release_rows(self, handle: int):
         """Extension: frees a committed row set."""
         self.engine.release_rows(_handles([handle])[0])

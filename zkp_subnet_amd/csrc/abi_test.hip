@@ -187,6 +187,7 @@ int kzg_test_field(kzg_ctx* ctx, int field, int op, const uint8_t* a_be, const u
     HIPCHK(ctx, hipMemcpyAsync(db, b_be, n * w, hipMemcpyHostToDevice, L.stream));
     uint32_t blocks = (uint32_t)((n + 255) / 256);
     if (field == 0) k_test_fp<<<blocks, 256, 0, L.stream>>>(op, da, db, L.out_be.as<uint8_t>(), n);
+    else if (op == 7 || op == 8) launch_fr_inv_test(L.stream, da, L.out_be.as<uint8_t>(), n, op == 8);   // the device-side inversion alone
     else k_test_fr<<<blocks, 256, 0, L.stream>>>(op, da, db, L.out_be.as<uint8_t>(), n);
     HIPCHK(ctx, hipMemcpyAsync(out_be, L.out_be.p, n * w, hipMemcpyDeviceToHost, L.stream));
     HIPCHK(ctx, hipStreamSynchronize(L.stream));

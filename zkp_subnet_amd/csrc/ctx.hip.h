@@ -404,6 +404,11 @@ int rows_eval_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint3
 int rows_lincomb_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t k, uint64_t T, uint32_t m,
                      const uint8_t* points_be32, const uint8_t* coeffs_be32, const uint32_t* masks, uint8_t* out_values32,
                      uint8_t* out_p48);
+// the grand product of k wire / sigma row pairs (rows read through the two tables) into a new one-row set's buffer dst:
+// its commitment, the closing value, and whether some denominator was zero (z undefined: the caller creates no set)
+int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& wires, const RowTab& sigmas, uint32_t k,
+                           uint64_t T, const uint8_t* shifts_be32, const uint8_t* beta_be32, const uint8_t* gamma_be32,
+                           uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den);
 // an SRS (re)load is installing a new table (every lane held): marks every live set stale, frees its buffer and the free list
 void rows_invalidate(kzg_ctx* ctx);
 // kzg_rows_open with the extra condition that every set belongs to worker `expect_i` (UINT32_MAX: any; kzg_multi_rows_open)
@@ -415,6 +420,10 @@ int rows_eval_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const ui
 int rows_lincomb_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
                       const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32, uint8_t* out_proofs48);
 int rows_release_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle);
+int rows_grand_product_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                            uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
+                            const uint8_t* beta_be32, const uint8_t* gamma_be32, uint8_t* out_commitment48,
+                            uint8_t* out_closing32, uint64_t* out_handle);
 
 // ---- the collective (comm.hip)
 void comm_teardown(kzg_ctx* ctx);

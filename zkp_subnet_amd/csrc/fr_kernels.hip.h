@@ -83,3 +83,18 @@ void launch_fr_lincomb_points(hipStream_t s, const RowTab& rt, uint64_t n, uint3
                               uint32_t* bad);
 // *flag |= 1 when a[0, n_words) and b[0, n_words) differ (n_words a multiple of 4): verification of a row-cache hit
 void launch_words_differ(hipStream_t s, const uint32_t* a, const uint32_t* b, uint64_t n_words, uint32_t* flag);
+// ---- the permutation grand product (fr_prod.hip; kzg_rows_commit_grand_product)
+// one wire / sigma pair folded into the running vectors: N[t] (*)= ea[t] + beta s w^t + gamma, D[t] (*)= ea[t] + beta es[t] +
+// gamma (first: written instead of multiplied).  ea, es: the pair's n evaluations (Montgomery, natural order); tw: the forward
+// table of launch_fr_twiddles for n (unused when n == 1); beta, gamma, s as 32 big-endian HOST bytes, *bad raised when >= r
+void launch_gp_factors(hipStream_t s, const uint32_t* ea, const uint32_t* es, uint32_t* N, uint32_t* D, uint64_t n,
+                       const uint32_t* tw, const uint8_t beta_be32[32], const uint8_t gamma_be32[32],
+                       const uint8_t shift_be32[32], bool first, uint32_t* bad);
+// N[t] <- z(w^t) = (prod_{u<t} N_u) (prod_{u>=t} D_u) / prod_u D_u (D is consumed); scrN, scrD: (n + 3) / 4 * 3 / 2 + 64
+// elements of scratch each.  closing_be (device): prod N / prod D, 32 bytes big-endian; *zero_flag (device): 1 when
+// prod D == 0 (z undefined, N then holds zeros), else 0
+void launch_gp_scan(hipStream_t s, uint32_t* N, uint32_t* D, uint64_t n, uint32_t* scrN, uint32_t* scrD,
+                    uint8_t* closing_be, uint32_t* zero_flag);
+// test hook: out[j] = in[j]^-1 (32 big-endian bytes each, canonical; 0 for in[j] == 0) or, with want_flag, the inversion's
+// zero flag (0 / 1) in the same format
+void launch_fr_inv_test(hipStream_t s, const uint8_t* in_be, uint8_t* out_be, uint64_t n, int want_flag);

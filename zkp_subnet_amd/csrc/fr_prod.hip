@@ -1,0 +1,370 @@
+// fr_prod.hip -- Fr-side kernels, part 3: the permutation grand product of kzg_rows_commit_grand_product.  Element-wise
+// products over transformed rows, a chunked multi-level prefix / suffix PRODUCT scan (the shape of fr_poly.hip's Horner scan
+// with the monoid "multiply") and the library's one device-side Fr inversion.
+//   N_t = prod_j (a_j(w^t) + beta s_j w^t + gamma),  D_t = prod_j (a_j(w^t) + beta sigma_j(w^t) + gamma)
+//   z(w^t) = (prod_{u<t} N_u) (prod_{u>=t} D_u) (prod_u D_u)^-1        -- ONE inversion per call, no batch inversion
+// Every kernel is a chain of fr9_mul: running values stay in the product's output class and are canonicalised on store.
+#include <cstring>
+
+#include "fr_kernels.hip.h"
+
+static inline uint32_t nblk(uint64_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
+
+// ------------------------------------------------------------------------------------------------ inversion
+// a^-1 mod r of a canonical integer a != 0 by the binary extended Euclid (HAC 14.61): u, v shrink by halving and
+// subtracting, x1, x2 follow mod r.  32-bit adds and shifts only -- ~760 steps of ~35 instructions for a random a, against
+// ~330 dependent products (~70 000 instructions) for the Fermat power a^(r-2).  One lane; the bound of 1100 steps covers
+// the worst case (<= 510 halvings, each subtraction is followed by one).
+KZG_DEV void w8_shr1(uint32_t* a, uint32_t top) {
+#pragma unroll
+    for (int i = 0; i < 7; i++) a[i] = (a[i] >> 1) | (a[i + 1] << 31);
+    a[7] = (a[7] >> 1) | (top << 31);
+}
+KZG_DEV void w8_half_mod(uint32_t* x, const uint32_t* r) {   // x <- x / 2 mod r (x < r < 2^255)
+    uint32_t c = 0;
+    if (x[0] & 1u) c = bi_add<8>(x, x, r);
+    w8_shr1(x, c);
+}
+KZG_DEV void w8_sub_mod(uint32_t* x, const uint32_t* y, const uint32_t* r) {   // x <- x - y mod r
+    if (bi_sub<8>(x, x, y)) (void)bi_add<8>(x, x, r);
+}
+KZG_DEV bool w8_is_one(const uint32_t* a) {
+    uint32_t t = a[0] ^ 1u;
+#pragma unroll
+    for (int i = 1; i < 8; i++) t |= a[i];
+    return t == 0;
+}
+// Montgomery form in, Montgomery form out; false (and zero out) for a == 0
+KZG_DEV bool fr9_inv(fr9_t& out, const fr9_t& a_mont_lazy) {
+    constexpr uint32_t RW[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u,
+                                0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
+    uint32_t r[8], u[8], v[8], x1[8], x2[8];
+    fr9_t a;
+    fr9_from_mont(a, a_mont_lazy);
+    fr9_to_words(u, a);
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        r[i] = RW[i];
+        v[i] = RW[i];
+        x1[i] = i == 0 ? 1u : 0u;
+        x2[i] = 0u;
+    }
+    if (bi_is_zero<8>(u)) {
+        fr9_zero(out);
+        return false;
+    }
+    for (int it = 0; it < 1100 && !w8_is_one(u) && !w8_is_one(v); it++) {
+        if (!(u[0] & 1u)) {
+            w8_shr1(u, 0);
+            w8_half_mod(x1, r);
+        } else if (!(v[0] & 1u)) {
+            w8_shr1(v, 0);
+            w8_half_mod(x2, r);
+        } else if (bi_ge<8>(u, v)) {
+            (void)bi_sub<8>(u, u, v);
+            w8_sub_mod(x1, x2, r);
+        } else {
+            (void)bi_sub<8>(v, v, u);
+            w8_sub_mod(x2, x1, r);
+        }
+    }
+    fr9_t y;
+    fr9_from_words(y, w8_is_one(u) ? x1 : x2);
+    fr9_to_mont(out, y);
+    return true;
+}
+// test hook (kzg_test_field, Fr ops 7 / 8): out[j] = in[j]^-1, or the zero flag of that inversion, as 32 big-endian bytes
+__global__ void __launch_bounds__(64) k_fr_inv_test(const uint8_t* __restrict__ in_be, uint8_t* __restrict__ out_be,
+                                                    uint64_t n, int want_flag) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    uint32_t w[8];
+    limbs_from_be<8>(w, in_be + 32 * j);
+    fr9_t a, y;
+    fr9_from_words(a, w);
+    fr9_to_mont(a, a);
+    const bool ok = fr9_inv(y, a);
+    fr9_from_mont(y, y);
+    fr9_to_words(w, y);
+    if (want_flag) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) w[i] = 0;
+        w[0] = ok ? 0u : 1u;
+    }
+    limbs_to_be<8>(out_be + 32 * j, w);
+}
+void launch_fr_inv_test(hipStream_t s, const uint8_t* in_be, uint8_t* out_be, uint64_t n, int want_flag) {
+    if (n) k_fr_inv_test<<<nblk(n, 64), 64, 0, s>>>(in_be, out_be, n, want_flag);
+}
+
+// ------------------------------------------------------------------------------------------------ factors
+// One wire / sigma pair: N[t] (*)= a(w^t) + beta s w^t + gamma, D[t] (*)= a(w^t) + beta sigma(w^t) + gamma, with ea / es the
+// pair's evaluations (forward NTT, natural order) and w^t from the resident forward twiddle table (w^(t + n/2) = -w^t).
+// beta, gamma and beta * s are converted to Montgomery form once per workgroup (three lanes, one or two products each).
+// FIRST: the vectors are written, not multiplied.  Multiplier-bound: 4 products per element (2 when FIRST), 128 B in, 64 out.
+struct GpArg {
+    FrArg beta, gamma, shift;
+};
+KZG_DEV void fr9_from_arg(fr9_t& v, const FrArg& a, uint32_t* __restrict__ bad, bool check) {
+    uint32_t w[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) w[i] = bswap32(a.w[7 - i]);
+    if (check && fr_words_ge_r(w)) atomicOr(bad, 1u);
+    fr9_from_words(v, w);
+    fr9_to_mont(v, v);
+}
+template <bool FIRST>
+__global__ void __launch_bounds__(256) k_gp_factors(const uint32_t* __restrict__ ea, const uint32_t* __restrict__ es,
+                                                     uint32_t* __restrict__ N, uint32_t* __restrict__ D, uint64_t n,
+                                                     const uint32_t* __restrict__ tw, const GpArg arg,
+                                                     uint32_t* __restrict__ bad) {
+    __shared__ uint32_t cst[3][9];   // beta, gamma, beta * s
+    const uint32_t v = threadIdx.x;
+    if (v < 3) {
+        fr9_t c;
+        fr9_from_arg(c, v == 1 ? arg.gamma : arg.beta, bad, blockIdx.x == 0);
+        if (v == 2) {
+            fr9_t s;
+            fr9_from_arg(s, arg.shift, bad, blockIdx.x == 0);
+            fr9_mul(c, c, s);
+            fr9_canon(c, c);
+        }
+#pragma unroll
+        for (int i = 0; i < 9; i++) cst[v][i] = c.l[i];
+    }
+    __syncthreads();
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + v;
+    if (t >= n) return;
+    fr9_t beta, gamma, bs, a, sg, w, x, fn, fd;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        beta.l[i] = cst[0][i];
+        gamma.l[i] = cst[1][i];
+        bs.l[i] = cst[2][i];
+    }
+    fr9_load(a, ea + 8 * t);
+    fr9_load(sg, es + 8 * t);
+    const uint64_t half = n >> 1;
+    if (half) {
+        const uint64_t k = t & (half - 1);
+        const uint4* q = reinterpret_cast<const uint4*>(tw + 12 * k);
+        const uint4 q0 = q[0], q1 = q[1], q2 = q[2];
+        w.l[0] = q0.x; w.l[1] = q0.y; w.l[2] = q0.z; w.l[3] = q0.w;
+        w.l[4] = q1.x; w.l[5] = q1.y; w.l[6] = q1.z; w.l[7] = q1.w;
+        w.l[8] = q2.x;
+        fr9_mul(x, bs, w);                    // beta s w^(t mod n/2), < 2r
+        if (t >= half) {                      // w^t = -w^(t - n/2)
+            fr9_t z;
+            fr9_zero(z);
+            fr9_sub4(x, z, x);                // 4r - x
+        }
+    } else {
+        x = bs;                               // n == 1: w^0 = 1
+    }
+    fr9_add(fn, a, gamma);
+    fr9_add(fn, fn, x);                       // < 6r, limbs < 2^31
+    fr9_norm(fn, fn);
+    fr9_mul(x, sg, beta);
+    fr9_add(fd, a, gamma);
+    fr9_add(fd, fd, x);
+    fr9_norm(fd, fd);
+    if constexpr (FIRST) {
+        fr9_reduce(fn, fn);
+        fr9_reduce(fd, fd);
+    } else {
+        fr9_t o;
+        fr9_load(o, N + 8 * t);
+        fr9_mul(fn, fn, o);
+        fr9_canon(fn, fn);
+        fr9_load(o, D + 8 * t);
+        fr9_mul(fd, fd, o);
+        fr9_canon(fd, fd);
+    }
+    fr9_store(N + 8 * t, fn);
+    fr9_store(D + 8 * t, fd);
+}
+void launch_gp_factors(hipStream_t s, const uint32_t* ea, const uint32_t* es, uint32_t* N, uint32_t* D, uint64_t n,
+                       const uint32_t* tw, const uint8_t beta_be32[32], const uint8_t gamma_be32[32],
+                       const uint8_t shift_be32[32], bool first, uint32_t* bad) {
+    if (!n) return;
+    GpArg arg;
+    memcpy(arg.beta.w, beta_be32, 32);
+    memcpy(arg.gamma.w, gamma_be32, 32);
+    memcpy(arg.shift.w, shift_be32, 32);
+    if (first) k_gp_factors<true><<<nblk(n, 256), 256, 0, s>>>(ea, es, N, D, n, tw, arg, bad);
+    else k_gp_factors<false><<<nblk(n, 256), 256, 0, s>>>(ea, es, N, D, n, tw, arg, bad);
+}
+
+// ------------------------------------------------------------------------------------------------ product scans
+// Level k + 1 holds the products of 2^l consecutive values of level k, for N (grid row 0) and D (grid row 1) side by side.
+__global__ void __launch_bounds__(256) k_gp_chunk_prod(const uint32_t* __restrict__ inN, const uint32_t* __restrict__ inD,
+                                                        uint64_t n, int lchunk, uint32_t* __restrict__ outN,
+                                                        uint32_t* __restrict__ outD) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t L = (uint64_t)1 << lchunk, lo = g * L;
+    if (lo >= n) return;
+    const uint64_t hi = lo + L < n ? lo + L : n;
+    const uint32_t* in = blockIdx.y ? inD : inN;
+    fr9_t p, c;
+    fr9_load(p, in + 8 * lo);
+    for (uint64_t u = lo + 1; u < hi; u++) {
+        fr9_load(c, in + 8 * u);
+        fr9_mul(p, p, c);
+    }
+    fr9_canon(p, p);   // (a lone value is canonical already: fr9_canon keeps it)
+    fr9_store((blockIdx.y ? outD : outN) + 8 * g, p);
+}
+// The top level (m <= GP_TOP_MAX values each), one workgroup: lanes [0, 256) turn vN into its EXCLUSIVE PREFIX products,
+// lanes [256, 512) turn vD into its EXCLUSIVE SUFFIX products (the same code on the mirrored index), in place: a lane folds
+// its <= 8 consecutive values, a Hillis-Steele scan over the 256 lane products gives each lane its start.  Between the scan
+// and the walk one lane inverts the total of D (fr9_inv) and every suffix start is multiplied by that inverse, so that
+// every value expanded from this level carries it.  The record receives closing = total N / total D (32 bytes big-endian)
+// and the zero-denominator flag word.
+#define GP_TOP_MAX 2048
+__global__ void __launch_bounds__(512) k_gp_top(uint32_t* __restrict__ vN, uint32_t* __restrict__ vD, uint32_t m,
+                                                 uint8_t* __restrict__ closing_be, uint32_t* __restrict__ zero_flag) {
+    __shared__ uint32_t sm[2][9][256];
+    __shared__ uint32_t inv_sm[9];
+    const uint32_t side = threadIdx.x >> 8, v = threadIdx.x & 255u;
+    uint32_t* vals = side ? vD : vN;
+    const uint32_t per = (m + 255u) / 256u;
+    const uint32_t lo = v * per, hi = lo + per < m ? lo + per : m;
+    auto at = [&](uint32_t u) { return 8 * (uint64_t)(side ? m - 1 - u : u); };
+    fr9_t g, c;
+    fr9_one(g);
+    for (uint32_t u = lo; u < hi; u++) {
+        fr9_load(c, vals + at(u));
+        fr9_mul(g, g, c);
+    }
+#pragma unroll
+    for (int i = 0; i < 9; i++) sm[side][i][v] = g.l[i];
+    __syncthreads();
+    for (uint32_t d = 1; d < 256; d <<= 1) {   // products of two N-class values (< 2r each) are legal: 4 r^2 < 2^261 r
+        fr9_t other;
+        const bool has = v >= d;
+        if (has) {
+#pragma unroll
+            for (int i = 0; i < 9; i++) other.l[i] = sm[side][i][v - d];
+        }
+        __syncthreads();
+        if (has) {
+            fr9_mul(g, g, other);
+#pragma unroll
+            for (int i = 0; i < 9; i++) sm[side][i][v] = g.l[i];
+        }
+        __syncthreads();
+    }
+    // sm[side][.][v] = product of the values of lanes 0 .. v; lane 255's is the total
+    if (threadIdx.x == 256) {
+        fr9_t tot, inv, totn, cl;
+#pragma unroll
+        for (int i = 0; i < 9; i++) {
+            tot.l[i] = sm[1][i][255];
+            totn.l[i] = sm[0][i][255];
+        }
+        const bool ok = fr9_inv(inv, tot);
+        *zero_flag = ok ? 0u : 1u;
+#pragma unroll
+        for (int i = 0; i < 9; i++) inv_sm[i] = inv.l[i];
+        fr9_mul(cl, totn, inv);
+        fr9_from_mont(cl, cl);
+        uint32_t w[8];
+        fr9_to_words(w, cl);
+        limbs_to_be<8>(closing_be, w);
+    }
+    __syncthreads();
+    fr9_t p;
+    if (v) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) p.l[i] = sm[side][i][v - 1];
+    } else {
+        fr9_one(p);
+    }
+    if (side) {
+        fr9_t inv;
+#pragma unroll
+        for (int i = 0; i < 9; i++) inv.l[i] = inv_sm[i];
+        fr9_mul(p, p, inv);
+    }
+    for (uint32_t u = lo; u < hi; u++) {
+        fr9_t o;
+        fr9_load(c, vals + at(u));
+        fr9_canon(o, p);
+        fr9_store(vals + at(u), o);
+        fr9_mul(p, p, c);
+    }
+}
+// One level down, in place: group g of 2^l values of this level starts from the parent's exclusive value ex[g]; N (grid row
+// 0) walks its group upward, D (grid row 1) downward, each value replaced by the exclusive product in front of it.
+__global__ void __launch_bounds__(256) k_gp_expand(uint32_t* __restrict__ vN, uint32_t* __restrict__ vD, uint64_t n, int l,
+                                                    const uint32_t* __restrict__ exN, const uint32_t* __restrict__ exD) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t L = (uint64_t)1 << l, lo = g * L;
+    if (lo >= n) return;
+    const uint64_t hi = lo + L < n ? lo + L : n;
+    const bool down = blockIdx.y != 0;
+    uint32_t* vals = down ? vD : vN;
+    fr9_t p, c, o;
+    fr9_load(p, (down ? exD : exN) + 8 * g);
+    for (uint64_t k = 0; k < hi - lo; k++) {
+        const uint64_t u = down ? hi - 1 - k : lo + k;
+        fr9_load(c, vals + 8 * u);
+        fr9_canon(o, p);
+        fr9_store(vals + 8 * u, o);
+        fr9_mul(p, p, c);
+    }
+}
+// Level 0: chunk g of 2^l elements.  Downward, D[t] becomes the INCLUSIVE suffix product from t (times the inverse of the
+// total, carried by exD); upward, z(w^t) = (exclusive prefix of N at t) * D[t] replaces N[t].  3 products per element.
+__global__ void __launch_bounds__(256) k_gp_final(uint32_t* __restrict__ N, uint32_t* __restrict__ D, uint64_t n, int l,
+                                                   const uint32_t* __restrict__ exN, const uint32_t* __restrict__ exD) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t L = (uint64_t)1 << l, lo = g * L;
+    if (lo >= n) return;
+    const uint64_t hi = lo + L < n ? lo + L : n;
+    fr9_t p, c, o;
+    fr9_load(p, exD + 8 * g);
+    for (uint64_t t = hi; t-- > lo;) {
+        fr9_load(c, D + 8 * t);
+        fr9_mul(p, p, c);
+        fr9_canon(o, p);
+        fr9_store(D + 8 * t, o);
+    }
+    fr9_load(p, exN + 8 * g);
+    for (uint64_t t = lo; t < hi; t++) {
+        fr9_t z;
+        fr9_load(c, D + 8 * t);       // this lane's own store above
+        fr9_mul(z, p, c);
+        fr9_canon(z, z);
+        fr9_load(c, N + 8 * t);
+        fr9_store(N + 8 * t, z);
+        fr9_mul(p, p, c);
+    }
+}
+// N, D (n Montgomery elements each) -> z's evaluations in N (D is consumed).  scrN / scrD: (n + 3) / 4 * 3 / 2 + 64 elements
+// of level scratch each (the sizing of the opening's h / hnext).  Level 0 folds 2^l0 elements per lane (4 for short rows, 16
+// for long ones, as the opening does), every further level 16, until at most GP_TOP_MAX values are left for k_gp_top.
+void launch_gp_scan(hipStream_t s, uint32_t* N, uint32_t* D, uint64_t n, uint32_t* scrN, uint32_t* scrD,
+                    uint8_t* closing_be, uint32_t* zero_flag) {
+    if (!n) return;
+    int l0 = 2;
+    while (l0 < 4 && (n >> (l0 + 1)) >= 16384) l0++;
+    int K = 1, lv_l[16];
+    uint64_t lv_n[16], lv_off[16];
+    lv_l[0] = l0; lv_n[0] = n; lv_off[0] = 0;
+    lv_n[1] = (n + ((uint64_t)1 << l0) - 1) >> l0; lv_off[1] = 0;
+    k_gp_chunk_prod<<<dim3(nblk(lv_n[1], 256), 2), 256, 0, s>>>(N, D, n, l0, scrN, scrD);
+    while (lv_n[K] > GP_TOP_MAX && K < 14) {
+        lv_l[K] = 4;
+        lv_n[K + 1] = (lv_n[K] + 15) >> 4;
+        lv_off[K + 1] = lv_off[K] + lv_n[K];
+        k_gp_chunk_prod<<<dim3(nblk(lv_n[K + 1], 256), 2), 256, 0, s>>>(scrN + 8 * lv_off[K], scrD + 8 * lv_off[K], lv_n[K], 4,
+                                                                         scrN + 8 * lv_off[K + 1], scrD + 8 * lv_off[K + 1]);
+        K++;
+    }
+    k_gp_top<<<1, 512, 0, s>>>(scrN + 8 * lv_off[K], scrD + 8 * lv_off[K], (uint32_t)lv_n[K], closing_be, zero_flag);
+    for (int k = K - 1; k >= 1; k--)
+        k_gp_expand<<<dim3(nblk(lv_n[k + 1], 256), 2), 256, 0, s>>>(scrN + 8 * lv_off[k], scrD + 8 * lv_off[k], lv_n[k], lv_l[k],
+                                                                    scrN + 8 * lv_off[k + 1], scrD + 8 * lv_off[k + 1]);
+    k_gp_final<<<nblk(lv_n[1], 256), 256, 0, s>>>(N, D, n, l0, scrN, scrD);
+}

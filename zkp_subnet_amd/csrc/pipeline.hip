@@ -719,5 +719,53 @@ int rows_lincomb_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, ui
     }
     return multi_msms_finish(ctx, H, i, T, nullptr, 0, m, m, nullptr, out_values32, out_p48);
 }
+// The permutation grand product (kzg_rows_commit_grand_product): a set built FROM sets.  Per wire / sigma pair two forward
+// transforms of the sets' coefficient rows into two lane buffers and one launch that folds the pair's factors into the
+// running N and D vectors (four vectors of T whatever k is); the product scans and the one inversion turn N into z's
+// evaluations (fr_prod.hip); the inverse transform writes z's coefficients straight into the new set's buffer `dst`; one
+// MSM commits.  The record's first two evaluation slots carry the closing value and the zero-denominator flag word.
+int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& wires, const RowTab& sigmas, uint32_t k,
+                           uint64_t T, const uint8_t* shifts_be32, const uint8_t* beta_be32, const uint8_t* gamma_be32,
+                           uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const int lg = ilog2_exact(T);
+    uint32_t* tw = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
+    const uint64_t nchunks = (T + 3) / 4;
+    HIPCHK(ctx, A.coeffA.ensure(T * 32));
+    HIPCHK(ctx, A.coeffB.ensure(T * 32));
+    HIPCHK(ctx, A.bcomb.ensure(T * 32));
+    HIPCHK(ctx, A.qbuf.ensure(T * 32));
+    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    HIPCHK(ctx, A.hbuf.ensure((nchunks + (nchunks >> 1) + 64) * 32));
+    HIPCHK(ctx, A.hnext.ensure((nchunks + (nchunks >> 1) + 64) * 32));
+    uint32_t *ea = A.coeffA.as<uint32_t>(), *es = A.coeffB.as<uint32_t>();
+    uint32_t *N = A.bcomb.as<uint32_t>(), *D = A.qbuf.as<uint32_t>();
+    uint8_t* rec = A.brec.as<uint8_t>();
+    for (uint32_t j = 0; j < k; j++) {
+        {
+            Span sp(ctx, A, KZG_T_NTT);
+            launch_fr_ntt(A.stream, wires.r[j], ea, lg, tw, nullptr, A.ntt_mid.as<uint32_t>());
+            launch_fr_ntt(A.stream, sigmas.r[j], es, lg, tw, nullptr, A.ntt_mid.as<uint32_t>());
+        }
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_gp_factors(A.stream, ea, es, N, D, T, tw, beta_be32, gamma_be32, shifts_be32 + 32 * (size_t)j, j == 0, A.flags());
+    }
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_gp_scan(A.stream, N, D, T, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), rec + MR_EVAL,
+                       reinterpret_cast<uint32_t*>(rec + MR_EVAL + 32));
+    }
+    const uint32_t* c;
+    if (int rc = row_to_coeffs(ctx, A, N, T, 1, &c, dst)) return rc;
+    uint8_t ev[64];
+    if (int rc = multi_msms_finish(ctx, H, i, T, dst, 1, 0, 2, out_c48, ev, nullptr)) return rc;
+    memcpy(out_closing32, ev, 32);
+    uint32_t zf;
+    memcpy(&zf, ev + 32, 4);
+    *out_zero_den = zf != 0;
+    return KZG_OK;
+}
 
 }  // namespace kzg_impl

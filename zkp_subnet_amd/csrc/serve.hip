@@ -653,6 +653,40 @@ struct RowsPending {
         if (buf.p) ctx->sets_free.push_back(std::move(buf));
     }
 };
+// a new set's place under KZG_MAX_ROW_SETS and its buffer of `bytes` bytes (lane held): the smallest released buffer that
+// fits, else a fresh allocation.  KZG_E_BUSY when the sets are all taken, KZG_E_NOMEM when the device has no room.
+static int rows_reserve(kzg_ctx* ctx, const char* what, RowsPending& pend, size_t bytes) {
+    {
+        std::lock_guard<std::mutex> lk(ctx->sets_mu);
+        if (rows_live(ctx) + ctx->sets_pending >= KZG_MAX_ROW_SETS)
+            return fail(ctx, KZG_E_BUSY, std::string(what) + ": KZG_MAX_ROW_SETS sets are live: release one first");
+        ctx->sets_pending++;
+        pend.reserved = true;
+        size_t best = ctx->sets_free.size();
+        for (size_t b = 0; b < ctx->sets_free.size(); b++)
+            if (ctx->sets_free[b].cap >= bytes && (best == ctx->sets_free.size() || ctx->sets_free[b].cap < ctx->sets_free[best].cap))
+                best = b;
+        if (best < ctx->sets_free.size()) {
+            pend.buf = std::move(ctx->sets_free[best]);
+            ctx->sets_free.erase(ctx->sets_free.begin() + best);
+        }
+    }
+    HIPCHK(ctx, pend.buf.ensure(bytes));
+    return KZG_OK;
+}
+// the reserved set becomes live: k rows of T coefficients of worker i in pend's buffer; returns its handle
+static uint64_t rows_insert(kzg_ctx* ctx, RowsPending& pend, uint32_t i, uint32_t k, uint64_t T) {
+    const uint64_t h = ++g_row_set_handles;
+    std::lock_guard<std::mutex> lk(ctx->sets_mu);
+    kzg_ctx::RowSet& st = ctx->sets[h];
+    st.i = i;
+    st.k = k;
+    st.T = T;
+    st.buf = std::move(pend.buf);
+    ctx->sets_pending--;
+    pend.reserved = false;
+    return h;
+}
 // the references an open holds on its sets, dropped after its lane is drained (declared before the LaneHold)
 struct RowsRefs {
     kzg_ctx* ctx;
@@ -803,6 +837,58 @@ int rows_lincomb_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const
     return rows_lincomb_dev(ctx, H, i, rt, k, T, m, points_be32, coeffs_be32, masks, out_values32, out_proofs48);
 }
 
+// kzg_rows_commit_grand_product: the lookups of an open (two handle lists), the reservation of a commit
+int rows_grand_product_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                            uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
+                            const uint8_t* beta_be32, const uint8_t* gamma_be32, uint8_t* out_commitment48,
+                            uint8_t* out_closing32, uint64_t* out_handle) {
+    if (!ctx || !wire_handles || !sigma_handles || !shifts_be32 || !beta_be32 || !gamma_be32 || !out_commitment48 ||
+        !out_closing32 || !out_handle)
+        return KZG_E_ARG;
+    if (n_wire_handles == 0 || n_wire_handles > KZG_MAX_BATCH_OPEN || n_sigma_handles == 0 || n_sigma_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "grand product: the number of handles in each list must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (k == 0 || k > KZG_MAX_BATCH_OPEN) return fail(ctx, KZG_E_ARG, "grand product: k must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (!fr_be32_canonical(beta_be32) || !fr_be32_canonical(gamma_be32))
+        return fail(ctx, KZG_E_ARG, "grand product: beta and gamma must be canonical scalars (< r)");
+    for (uint32_t j = 0; j < k; j++)
+        if (!fr_be32_canonical(shifts_be32 + 32 * (size_t)j))
+            return fail(ctx, KZG_E_ARG, "grand product: shifts must be canonical scalars (< r)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs wrefs{ctx}, srefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab wt, st;
+    uint32_t kw = 0, ks = 0, i = 0, is = 0;
+    uint64_t T = 0, Ts = 0;
+    if (int rc = rows_lookup(ctx, "grand product (wires)", expect_i, n_wire_handles, wire_handles, wrefs, wt, &kw, &i, &T)) return rc;
+    if (int rc = rows_lookup(ctx, "grand product (sigmas)", expect_i, n_sigma_handles, sigma_handles, srefs, st, &ks, &is, &Ts))
+        return rc;
+    if (is != i || Ts != T) return fail(ctx, KZG_E_ARG, "grand product: all sets must belong to one worker and have one row length");
+    if (kw != k || ks != k)
+        return fail(ctx, KZG_E_ARG, "grand product: the wire sets and the sigma sets must each hold exactly k rows");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "grand product: the row length must be a power of two");
+    if (int rc2 = rows_reserve(ctx, "grand product", pend, (size_t)T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    bool zero_den = false;
+    uint8_t c48[48], closing[32];
+    rc = rows_grand_product_dev(ctx, H, i, wt, st, k, T, shifts_be32, beta_be32, gamma_be32, pend.buf.as<uint32_t>(), c48, closing,
+                                &zero_den);
+    if (rc) return rc;
+    if (zero_den)
+        return fail(ctx, KZG_E_ARG, "grand product: zero denominator (some a_j + beta sigma_j + gamma vanishes on the domain): "
+                                    "z is undefined, no set was created");
+    memcpy(out_commitment48, c48, 48);
+    memcpy(out_closing32, closing, 32);
+    *out_handle = rows_insert(ctx, pend, i, 1, T);
+    return KZG_OK;
+}
+
 int rows_release_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle) {
     if (!ctx) return KZG_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->sets_mu);
@@ -835,23 +921,7 @@ int kzg_rows_commit(kzg_ctx* ctx, uint32_t i, uint32_t k, const uint8_t* rows_be
     if (evaluation_form && T > 1 && ilog2_exact(T) < 0)
         return fail(ctx, KZG_E_ARG, "evaluation-form row length must be a power of two");
     const size_t bytes = (size_t)k * T * 32;
-    {
-        std::lock_guard<std::mutex> lk(ctx->sets_mu);
-        if (rows_live(ctx) + ctx->sets_pending >= KZG_MAX_ROW_SETS)
-            return fail(ctx, KZG_E_BUSY, "row-set commit: KZG_MAX_ROW_SETS sets are live: release one first");
-        ctx->sets_pending++;
-        pend.reserved = true;
-        // the smallest released buffer that fits, else a fresh allocation below
-        size_t best = ctx->sets_free.size();
-        for (size_t b = 0; b < ctx->sets_free.size(); b++)
-            if (ctx->sets_free[b].cap >= bytes && (best == ctx->sets_free.size() || ctx->sets_free[b].cap < ctx->sets_free[best].cap))
-                best = b;
-        if (best < ctx->sets_free.size()) {
-            pend.buf = std::move(ctx->sets_free[best]);
-            ctx->sets_free.erase(ctx->sets_free.begin() + best);
-        }
-    }
-    HIPCHK(ctx, pend.buf.ensure(bytes));
+    if (int rc2 = rows_reserve(ctx, "row-set commit", pend, bytes)) return rc2;
     prof_begin(ctx, L);
     rc = clear_flags(ctx, L);
     if (rc) return rc;
@@ -866,17 +936,7 @@ int kzg_rows_commit(kzg_ctx* ctx, uint32_t i, uint32_t k, const uint8_t* rows_be
     if (rc) return rc;
     rc = rows_commit_dev(ctx, H, i, up, k, T, evaluation_form, dst, out_commitments48);
     if (rc) return rc;
-    const uint64_t h = ++g_row_set_handles;
-    {
-        std::lock_guard<std::mutex> lk(ctx->sets_mu);
-        kzg_ctx::RowSet& st = ctx->sets[h];
-        st.i = i;
-        st.k = k;
-        st.T = T;
-        st.buf = std::move(pend.buf);
-        ctx->sets_pending--;
-        pend.reserved = false;
-    }
+    const uint64_t h = rows_insert(ctx, pend, i, k, T);
     *out_handle = h;
     return KZG_OK;
 }
@@ -892,6 +952,13 @@ int kzg_rows_eval(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uin
 int kzg_rows_open_lincomb(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
                           const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32, uint8_t* out_proofs48) {
     return rows_lincomb_impl(ctx, UINT32_MAX, n_handles, handles, k, m, points_be32, coeffs_be32, out_values32, out_proofs48);
+}
+int kzg_rows_commit_grand_product(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t* wire_handles, uint32_t n_sigma_handles,
+                                  const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
+                                  const uint8_t beta_be32[32], const uint8_t gamma_be32[32], uint8_t out_commitment48[48],
+                                  uint8_t out_closing32[32], uint64_t* out_handle) {
+    return rows_grand_product_impl(ctx, UINT32_MAX, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
+                                   beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle);
 }
 int kzg_rows_release(kzg_ctx* ctx, uint64_t handle) { return rows_release_impl(ctx, UINT32_MAX, handle); }
 int kzg_rows_stats(kzg_ctx* ctx, uint64_t out_live_sets_bytes[2]) {

@@ -369,6 +369,24 @@ class HipEngine:
                                                   b"".join(c for cs in coeffs for c in cs), vals, pf))
         return [vals.raw[32 * p:32 * p + 32] for p in range(m)], [pf.raw[48 * p:48 * p + 48] for p in range(m)]
 
+    # ---- a set built from sets: the permutation grand product (PLONK round 2), computed and committed on the device
+    def commit_grand_product(self, wire_sets: Sequence[object], sigma_sets: Sequence[object], shifts_be32: Sequence[bytes],
+                             beta_be32: bytes, gamma_be32: bytes) -> Tuple["RowSet", bytes]:
+        """z of kzg_rows_commit_grand_product over the k concatenated rows of wire_sets and of sigma_sets (RowSet objects or
+        bare handles), one 32-byte shift per row.  Returns (a one-row RowSet holding z, the closing value as 32 bytes
+        big-endian: 1 when the permutation holds).  beta and gamma must be drawn after the wire commitments are fixed."""
+        nw, hw = self._handle_array(wire_sets, "commit_grand_product (wires)")
+        ns, hs = self._handle_array(sigma_sets, "commit_grand_product (sigmas)")
+        k = len(shifts_be32)
+        if k == 0 or k > _native.KZG_MAX_BATCH_OPEN or any(len(x) != 32 for x in list(shifts_be32) + [beta_be32, gamma_be32]):
+            raise KzgError(_native.KZG_E_ARG, f"commit_grand_product: 1 .. {_native.KZG_MAX_BATCH_OPEN} shifts, beta and gamma "
+                                              "of 32 bytes each")
+        c, cl, h = ctypes.create_string_buffer(48), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_grand_product(self._h, nw, hw, ns, hs, k, b"".join(shifts_be32), beta_be32,
+                                                          gamma_be32, c, cl, ctypes.byref(h)))
+        src = next((x for x in list(wire_sets) + list(sigma_sets) if hasattr(x, "T")), None)
+        return RowSet(self, h.value, getattr(src, "i", None), 1, getattr(src, "T", None), [c.raw]), cl.raw
+
     def _handle_array(self, sets, what):
         handles = [int(getattr(x, "handle", x)) for x in sets]
         n = len(handles)
@@ -716,6 +734,11 @@ class HipEngine:
         out = ctypes.create_string_buffer(len(a_be))
         self._chk(self._lib.kzg_test_field(self._h, field, op, a_be, b_be, out, len(a_be) // w))
         return out.raw
+
+    def test_fr_inv(self, in_be32: bytes) -> Tuple[bytes, List[int]]:
+        """The device-side Fr inversion alone (kzg_test_field, Fr ops 7 and 8): (inverses as n x 32 bytes, zero flags)."""
+        flags = self.test_field(1, 8, in_be32, in_be32)
+        return self.test_field(1, 7, in_be32, in_be32), [flags[32 * j + 31] for j in range(len(in_be32) // 32)]
 
     def test_g1(self, op: int, a_be96: bytes, b_be96: bytes) -> bytes:
         out = ctypes.create_string_buffer(len(a_be96))

@@ -138,6 +138,18 @@ class MultiDeviceClient:
             return Response(400, {"error": "worker_open_rows_lincomb: the handles must name live sets of one worker"})
         return self._for(i).worker_open_rows_lincomb(handles, points, coeffs)
 
+    def worker_commit_grand_product(self, wire_handles: Sequence[int], sigma_handles: Sequence[int], shifts, beta, gamma):
+        try:
+            i = self._owner(list(wire_handles) + list(sigma_handles))
+        except TypeError:
+            i = None
+        if i is None:
+            return Response(400, {"error": "worker_commit_grand_product: the handles must name live sets of one worker"})
+        r = self._for(i).worker_commit_grand_product(wire_handles, sigma_handles, shifts, beta, gamma)
+        if r.status_code == 200:
+            self._row_owner[int(r.json()["handle"])] = i
+        return r
+
     def worker_release_rows(self, handle: int):
         i = self._owner([handle])
         if i is None:
