@@ -241,6 +241,58 @@ int kzg_rows_commit_grand_product(kzg_ctx* ctx, uint32_t n_wire_handles, const u
                                   const uint8_t* shifts_be32 /* k*32 */, const uint8_t beta_be32[32],
                                   const uint8_t gamma_be32[32], uint8_t out_commitment48[48], uint8_t out_closing32[32],
                                   uint64_t* out_handle);
+/* A third set built FROM sets: the PLONK quotient (round 3), computed and committed on the device from rows that are already
+ * resident.  The concatenated rows of the handles (as in kzg_rows_open) are f_0 .. f_{n-1}, n <= KZG_MAX_BATCH_OPEN, all of
+ * one worker and one power-of-two length T; everything below names a row by its index into that list.  A full standard PLONK
+ * circuit is 13 rows: a b c | qL qR qO qM qC | sigma1 sigma2 sigma3 | z (and a public-input row where needed).
+ *   Gate(X) = sum_u c_u prod_{j in term u} f_j(X)     gate->n_terms <= KZG_MAX_GATE_TERMS terms; term u has the canonical
+ *             scalar c_u and term_lens[u] <= E + 1 row indices (term_rows holds the lists one after the other; an index may
+ *             repeat; an empty list makes the constant term c_u).  Standard gate: [qL,a] [qR,b] [qO,c] [qM,a,b] [qC].
+ *   P1(X)   = z(X) prod_j (a_j(X) + beta s_j X + gamma) - z(wX) prod_j (a_j(X) + beta sigma_j(X) + gamma),  j < perm->k
+ *   P2(X)   = (z(X) - 1) L_0(X),   L_0(X) = (X^T - 1) / (T (X - 1))
+ *   num     = Gate + alpha P1 + alpha^2 P2,   t = num / (X^T - 1)
+ * with w the T-th root of unity of the grand product (7^((r-1)/T)).  perm == NULL or perm->k == 0 switches the permutation
+ * part off (t = Gate / (X^T - 1); nothing else of perm is read).  E = 2^ext_log with ext_log in {1, 2, 3} is the factor by
+ * which the work domain exceeds T; every term has at most E + 1 factors and perm->k <= E (P1 has k + 1), so deg num <
+ * (E + 1) T and t has fewer than E T coefficients.  Standard PLONK: k = 3, ext_log = 2, n_pieces = 3 (deg t = 3T - 4).
+ * The call creates a new set of n_pieces = P rows (1 <= P <= E) of the same worker and length: row p holds t's coefficients
+ * [pT, (p+1)T), t = sum_p X^(pT) t_p.  out_commitments48[p] equals kzg_rows_commit(i, 1, t_p, T, evaluation_form = 0, ..)
+ * byte for byte, and *out_handle opens, evaluates, combines, releases, goes stale and counts against KZG_MAX_ROW_SETS
+ * (KZG_E_BUSY; KZG_E_NOMEM on a failed allocation, the lane's workspace of E T-element vectors included) like any other.
+ * Nothing row-sized crosses the host link in either direction.
+ * SHAPE CHECK: when P < E the device checks that every coefficient of t at index >= P T is zero; if one is not, the call
+ * answers KZG_E_ARG with a message that says the constraints do not hold on the domain or P is too small, and creates no
+ * set.  An unsatisfied row makes num / (X^T - 1) a non-polynomial whose interpolant on the work domain has full degree, so
+ * broken instances are caught this way in practice -- but the check is a NECESSARY condition, NOT A PROOF that the
+ * constraints hold: only the verifier's identity at a random point is.  When P = E nothing can be checked and nothing is.
+ * Errors (all KZG_E_ARG unless said): handle rules as in kzg_rows_open (1 .. KZG_MAX_BATCH_OPEN handles, a handle may repeat,
+ * unknown / released / stale); a row index >= n; more than E + 1 factors in a term; k > E; ext_log outside {1, 2, 3};
+ * n_pieces outside [1, E]; more than KZG_MAX_GATE_TERMS terms; neither a term nor a permutation part; a scalar (c_u, s_j,
+ * beta, gamma, alpha) >= r.  The source sets are only read; a release or an SRS load racing the call follows the rules of
+ * kzg_rows_open.  Thread-safe like every call; after any error the context keeps serving.
+ * SOUNDNESS: alpha must be drawn AFTER z's commitment is fixed, and beta, gamma after the wire commitments.  The library
+ * derives no challenge and adds NO BLINDING here either: a blinded t or z has degree >= T per piece and does not fit T-point
+ * slices; a caller who blinds pads its circuit below T and adds the blinding rows itself through kzg_rows_open_lincomb. */
+#define KZG_MAX_GATE_TERMS 16
+typedef struct kzg_quotient_gate {
+    uint32_t n_terms;
+    const uint8_t* coeffs_be32;  /* n_terms * 32 */
+    const uint32_t* term_lens;   /* n_terms */
+    const uint32_t* term_rows;   /* sum of term_lens */
+} kzg_quotient_gate;
+typedef struct kzg_quotient_perm {
+    uint32_t k;
+    uint32_t z_row;
+    const uint32_t* wire_rows;   /* k */
+    const uint32_t* sigma_rows;  /* k */
+    const uint8_t* shifts_be32;  /* k * 32 */
+    const uint8_t* beta_be32;    /* 32 */
+    const uint8_t* gamma_be32;   /* 32 */
+    const uint8_t* alpha_be32;   /* 32 */
+} kzg_quotient_perm;
+int kzg_rows_commit_quotient(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_gate* gate,
+                             const kzg_quotient_perm* perm /* NULL: gate only */, uint32_t ext_log, uint32_t n_pieces,
+                             uint8_t* out_commitments48 /* n_pieces * 48 */, uint64_t* out_handle);
 /* The UNCHANGED reference miner makes two calls per request with the same row -- worker_commit(i, poly), then
  * worker_open(i, poly, x) (neurons/miner.py:56-61).  These forms take a 128-bit content tag identifying the row's bytes
  * (the host codec computes it while decoding the text); the coefficient vectors of the last four rows stay on the
@@ -462,6 +514,10 @@ int kzg_multi_rows_commit_grand_product(kzg_multi* mh, uint32_t i, uint32_t n_wi
                                         uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
                                         const uint8_t* shifts_be32, const uint8_t beta_be32[32], const uint8_t gamma_be32[32],
                                         uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle);
+/* kzg_rows_commit_quotient on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_quotient(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                   const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log,
+                                   uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

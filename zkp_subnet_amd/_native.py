@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("KZG_MI355X_LIB") or os.path.join(HERE, "libkzg_mi355x
 KZG_MAX_BATCH_OPEN = 16   # include/kzg_mi355x.h
 KZG_MAX_OPEN_POINTS = 4
 KZG_MAX_ROW_SETS = 64
+KZG_MAX_GATE_TERMS = 16   # kzg_rows_commit_quotient
 KZG_OK, KZG_E_ARG, KZG_E_SCALAR, KZG_E_POINT, KZG_E_HIP, KZG_E_NOMEM, KZG_E_BUSY, KZG_E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
 STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_SCALAR", -3: "E_POINT", -4: "E_HIP", -5: "E_NOMEM", -6: "E_BUSY", -7: "E_COMM"}
 TIMING_NAMES = ["decode", "ntt", "digits", "scan", "scatter", "accumulate", "fixup", "tree", "final", "poly", "total", "collective"]
@@ -28,6 +29,19 @@ TIMING_NAMES = ["decode", "ntt", "digits", "scan", "scatter", "accumulate", "fix
 _P = ctypes.c_void_p
 _B = ctypes.c_char_p
 _U64, _U32, _I = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
+
+
+class QuotientGate(ctypes.Structure):
+    """kzg_quotient_gate"""
+    _fields_ = [("n_terms", _U32), ("coeffs_be32", _B), ("term_lens", ctypes.POINTER(_U32)), ("term_rows", ctypes.POINTER(_U32))]
+
+
+class QuotientPerm(ctypes.Structure):
+    """kzg_quotient_perm"""
+    _fields_ = [("k", _U32), ("z_row", _U32), ("wire_rows", ctypes.POINTER(_U32)), ("sigma_rows", ctypes.POINTER(_U32)),
+                ("shifts_be32", _B), ("beta_be32", _B), ("gamma_be32", _B), ("alpha_be32", _B)]
+
+
 SYMBOLS = {
     "kzg_create": (_I, [_I, ctypes.POINTER(_P)]),
     "kzg_destroy": (None, [_P]),
@@ -61,6 +75,8 @@ SYMBOLS = {
     "kzg_rows_open_lincomb": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _U32, _B, _B, _B, _B]),
     "kzg_rows_commit_grand_product": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _B, _B, _B, _B, _B,
                                            ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_quotient": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientGate), ctypes.POINTER(QuotientPerm),
+                                      _U32, _U32, _B, ctypes.POINTER(_U64)]),
     "kzg_commit_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B]),
     "kzg_open_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B, _B]),
     "kzg_row_cache_stats": (_I, [_P, ctypes.POINTER(_U64)]),
@@ -120,6 +136,8 @@ SYMBOLS = {
     "kzg_multi_rows_open_lincomb": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _U32, _B, _B, _B, _B]),
     "kzg_multi_rows_commit_grand_product": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _B, _B, _B,
                                                  _B, _B, ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_quotient": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientGate),
+                                            ctypes.POINTER(QuotientPerm), _U32, _U32, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_commit_open_rows": (_I, [_P, _U32, ctypes.POINTER(_U32), _B, _U64, _I, _B, _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_upload_fr": (_I, [_P, _I, _B, _U64, _I]),
     "kzg_msm_resident": (_I, [_P, _I, _U64, _U64, _B]),

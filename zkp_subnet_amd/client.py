@@ -333,6 +333,29 @@ class Client:
                 "closing": codec.be32_to_fr(closing)}
 
     @_guard
+    def worker_commit_quotient(self, handles: Sequence[int], terms, perm=None, ext_log: int = 2, n_pieces: int = 3):
+        """Extension: the PLONK quotient t over the rows of committed sets, computed and committed on the device as a new set
+        of n_pieces rows.  terms: [coefficient, [row indices]] per gate term; perm: None or {"wires", "sigmas", "z",
+        "shifts", "beta", "gamma", "alpha"} (row indices and scalars).  Returns the new handle and the pieces' commitments.
+        alpha must be drawn after z's commitment is fixed, beta and gamma after the wires."""
+        hs = _handles(handles)
+        try:
+            ext_log, n_pieces = int(ext_log), int(n_pieces)
+            tt = [(codec.fr_to_be32(c), [int(j) for j in rows]) for c, rows in terms]
+            pp = None
+            if perm is not None and len(perm["wires"]):   # (no wire: the part is off, as perm->k == 0 in C)
+                pp = {"wires": [int(j) for j in perm["wires"]], "sigmas": [int(j) for j in perm["sigmas"]], "z": int(perm["z"]),
+                      "shifts": [codec.fr_to_be32(x) for x in perm["shifts"]], "beta": codec.fr_to_be32(perm["beta"]),
+                      "gamma": codec.fr_to_be32(perm["gamma"]), "alpha": codec.fr_to_be32(perm["alpha"])}
+        except (TypeError, ValueError, KeyError) as e:
+            raise codec.CodecError(f"worker_commit_quotient: malformed terms or permutation part: {e!r}") from e
+        scal = [c for c, _ in tt] + (pp["shifts"] + [pp["beta"], pp["gamma"], pp["alpha"]] if pp else [])
+        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in scal):
+            raise codec.CodecError("worker_commit_quotient: coefficients, shifts and challenges must be canonical scalars (< r)")
+        rs = self.engine.commit_quotient(hs, tt, pp, ext_log, n_pieces)
+        return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments]}
+
+    @_guard
     def worker_release_rows(self, handle: int):
         """Extension: frees a committed row set."""
         self.engine.release_rows(_handles([handle])[0])

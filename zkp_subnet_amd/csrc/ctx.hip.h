@@ -174,6 +174,9 @@ struct Lane {
     // kzg_commit_open_batch: its record (BR_*; device + an 8 KB pinned, mapped page), the rows' coefficients and their
     // gamma-combination -- allocated by the first batched call on the lane
     DevBuf brec, bcoef, bcomb;
+    // kzg_rows_commit_quotient: the rows' (and L_0's) evaluations on the coset, one vector of E T elements each, and the
+    // staging vector the extensions and the pointwise result pass through -- allocated by the first quotient call on the lane
+    DevBuf qext, qstage;
     uint8_t* bpin = nullptr;
     uint8_t* bpin_dev = nullptr;
     // profiling spans of the call running on this lane
@@ -216,6 +219,7 @@ struct kzg_ctx {
     uint64_t slot_n[N_SLOTS] = {0, 0, 0, 0};
     int slot_mont[N_SLOTS] = {0, 0, 0, 0};
     std::map<int, kzg_impl::DevBuf> tw_fwd, tw_inv, inv_n;
+    std::map<int, kzg_impl::DevBuf> quot_consts;   // kzg_rows_commit_quotient's constants, by log T * 4 + ext_log (under mu)
     kzg_impl::Stage stage[N_STAGE];
     hipStream_t h2d = nullptr;     // the copy stream of kzg_staging_flush (one for all staging buffers: they share the link)
     // kzg_g1_sum*: own stream and buffers, independent of the lanes
@@ -409,6 +413,10 @@ int rows_lincomb_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, ui
 int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& wires, const RowTab& sigmas, uint32_t k,
                            uint64_t T, const uint8_t* shifts_be32, const uint8_t* beta_be32, const uint8_t* gamma_be32,
                            uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den);
+// the quotient pieces of the constraints qp over the n_rows coefficient rows of rt into a new n_pieces-row set's buffer dst:
+// their commitments, and whether a coefficient of t at or above n_pieces T was not zero (the caller creates no set)
+int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t n_rows, uint64_t T, const QuotPlan& qp,
+                      uint32_t n_pieces, uint32_t* dst, uint8_t* out_c48, bool* out_bad_shape);
 // an SRS (re)load is installing a new table (every lane held): marks every live set stale, frees its buffer and the free list
 void rows_invalidate(kzg_ctx* ctx);
 // kzg_rows_open with the extra condition that every set belongs to worker `expect_i` (UINT32_MAX: any; kzg_multi_rows_open)
@@ -424,6 +432,9 @@ int rows_grand_product_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_han
                             uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
                             const uint8_t* beta_be32, const uint8_t* gamma_be32, uint8_t* out_commitment48,
                             uint8_t* out_closing32, uint64_t* out_handle);
+int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                       const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces,
+                       uint8_t* out_commitments48, uint64_t* out_handle);
 
 // ---- the collective (comm.hip)
 void comm_teardown(kzg_ctx* ctx);

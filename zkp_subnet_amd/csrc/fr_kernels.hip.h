@@ -98,3 +98,27 @@ void launch_gp_scan(hipStream_t s, uint32_t* N, uint32_t* D, uint64_t n, uint32_
 // test hook: out[j] = in[j]^-1 (32 big-endian bytes each, canonical; 0 for in[j] == 0) or, with want_flag, the inversion's
 // zero flag (0 / 1) in the same format
 void launch_fr_inv_test(hipStream_t s, const uint8_t* in_be, uint8_t* out_be, uint64_t n, int want_flag);
+// ---- the PLONK quotient (fr_quot.hip; kzg_rows_commit_quotient): T = 2^log_t, E = 2^ext_log, N = E T, coset g H_N with g = 7
+#define QUOT_MAX_TERMS 16
+#define QUOT_MAX_FACTORS 9   // E + 1 at E = 8
+#define QUOT_MAX_WIRES 8     // k <= E
+// the constraints, rows named by index into the table of extended vectors; scalars as 32 big-endian HOST bytes each
+struct QuotPlan {
+    uint32_t ext_log, n_terms, k, z_row;
+    uint8_t term_len[QUOT_MAX_TERMS], term_row[QUOT_MAX_TERMS][QUOT_MAX_FACTORS], wire[QUOT_MAX_WIRES], sigma[QUOT_MAX_WIRES];
+    const uint8_t *term_coeffs_be32, *shifts_be32, *beta_be32, *gamma_be32, *alpha_be32;   // (the last four unused when k == 0)
+};
+// the constants record of one (T, E), in 8-word elements: 1 / Z_H on the coset, 1 / T, g and the power tables of g and 1 / g
+uint64_t quot_consts_elems(int log_t, int ext_log);
+// tw_n: the forward table of launch_fr_twiddles for N (also below)
+void launch_quot_consts(hipStream_t s, uint32_t* qc, int log_t, int ext_log, const uint32_t* tw_n);
+// ext[i] = g^i f[i] for i < T, 0 for T <= i < N (f: T Montgomery coefficients; null: the coefficients of L_0, all 1 / T)
+void launch_quot_extend(hipStream_t s, const uint32_t* f_or_null, uint32_t* ext, int log_t, int ext_log, const uint32_t* qc);
+// out[i] = (Gate + alpha P1 + alpha^2 P2)(x_i) / Z_H(x_i) over the rows' N coset evaluations ext_rows.r[.] and L_0's l0 (unused
+// when k == 0); out must not alias a row (z is read at i + E).  *bad raised for a scalar >= r
+void launch_quot_points(hipStream_t s, const RowTab& ext_rows, const uint32_t* l0, uint32_t* out, int log_t, const QuotPlan& qp,
+                        const uint32_t* tw_n, const uint32_t* qc, uint32_t* bad);
+// in: the N coefficients of t(g X) (inverse transform, 1 / N applied).  dst[i] = g^-i in[i] for i < n_pieces T (the pieces,
+// consecutive); *tail_flag |= 1 when some in[i], i >= n_pieces T, is not zero
+void launch_quot_pieces(hipStream_t s, const uint32_t* in, uint32_t* dst, int log_t, int ext_log, uint32_t n_pieces,
+                        const uint32_t* qc, uint32_t* tail_flag);

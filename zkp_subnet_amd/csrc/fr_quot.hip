@@ -1,0 +1,320 @@
+// fr_quot.hip -- Fr-side kernels, part 4: the PLONK quotient of kzg_rows_commit_quotient.  With T the row length, E = 2^ext_log
+// and N = E T, the rows are evaluated on the coset g H_N (g = 7, H_N the N-th roots of unity, x_i = g w_N^i in natural
+// order), the constraint arithmetic runs point by point there, and the result comes back to coefficients:
+//   k_quot_consts   once per (T, E) and context: 1 / (x^T - 1) for the E values x^T takes on the coset, 1 / T, g, and the
+//                   two-level power tables g^(+-i) = A[i mod 2^h] B[i >> h]  (h = ceil(log N / 2): two tables of ~sqrt N)
+//   k_quot_extend   ext[i] = g^i f[i] (i < T), 0 above: the input of one forward transform of length N per row; with no row,
+//                   the coefficients of L_0 (all 1 / T)
+//   k_quot_points   one lane per coset point: (Gate + alpha P1 + alpha^2 P2) / Z_H
+//   k_quot_pieces   after the inverse transform: t[i] = g^-i v[i] for i < P T into the new set's buffer, the tail [P T, N)
+//                   ORed into a flag word
+// Z_H(x_i) = g^T w_E^(i mod E) - 1: E inversions per (T, E), none per point.  z(w x_i) = z at index (i + E) mod N.
+#include <cstring>
+
+#include "fr_inv.hip.h"
+#include "fr_kernels.hip.h"
+
+static inline uint32_t nblk(uint64_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
+
+// constants record (8-word Montgomery elements): [0, 8) 1 / Z_H by i mod E, [8] 1 / T, [9] g, [16, ..) the power tables
+#define QC_INVT 8
+#define QC_G 9
+#define QC_TABLES 16
+__host__ __device__ static inline int quot_h(int log_n) { return (log_n + 1) / 2; }
+uint64_t quot_consts_elems(int log_t, int ext_log) {
+    const int log_n = log_t + ext_log, h = quot_h(log_n);
+    return QC_TABLES + 2 * (((uint64_t)1 << h) + ((uint64_t)1 << (log_n - h)));
+}
+
+KZG_DEV void fr9_pow(fr9_t& out, const fr9_t& base, uint64_t e) {   // canonical base -> canonical base^e
+    fr9_t cur, pw = base;
+    fr9_one(cur);
+    for (; e; e >>= 1) {
+        if (e & 1) fr9_mul(cur, cur, pw);
+        fr9_mul(pw, pw, pw);
+    }
+    fr9_canon(out, cur);
+}
+KZG_DEV void fr9_coset_gen(fr9_t& g, int inverse) {   // g = 7 or 7^-1 mod r, Montgomery form
+    constexpr uint32_t GI[8] = {0x24924925u, 0xdb6db6dbu, 0x49241a48u, 0xaa362edcu,
+                                0x7077624au, 0x57c7624bu, 0xe7519182u, 0x211f5460u};
+    uint32_t t[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) t[i] = inverse ? GI[i] : (i == 0 ? 7u : 0u);
+    fr9_from_words(g, t);
+    fr9_to_mont(g, g);
+}
+KZG_DEV void tw_get(fr9_t& w, const uint32_t* __restrict__ tw, uint64_t k) {   // the NTT's twiddle slots: nine limbs in 48 bytes
+    const uint4* q = reinterpret_cast<const uint4*>(tw + 12 * k);
+    const uint4 q0 = q[0], q1 = q[1], q2 = q[2];
+    w.l[0] = q0.x; w.l[1] = q0.y; w.l[2] = q0.z; w.l[3] = q0.w;
+    w.l[4] = q1.x; w.l[5] = q1.y; w.l[6] = q1.z; w.l[7] = q1.w;
+    w.l[8] = q2.x;
+}
+
+// ------------------------------------------------------------------------------------------------ constants
+// tw: the forward twiddle table of length N (w_N^k, k < N / 2).  One lane per element of the record.
+__global__ void __launch_bounds__(64) k_quot_consts(uint32_t* __restrict__ qc, int log_t, int ext_log,
+                                                     const uint32_t* __restrict__ tw) {
+    const int log_n = log_t + ext_log, h = quot_h(log_n);
+    const uint64_t SA = (uint64_t)1 << h, SB = (uint64_t)1 << (log_n - h), half = (uint64_t)1 << (log_n - 1);
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t E = 1u << ext_log;
+    fr9_t v;
+    if (t < E) {   // 1 / (g^T w_E^t - 1), w_E^t = w_N^(t T)
+        fr9_t g, w, one;
+        fr9_coset_gen(g, 0);
+        fr9_pow(g, g, (uint64_t)1 << log_t);
+        const uint64_t idx = t << log_t;
+        tw_get(w, tw, idx & (half - 1));
+        fr9_mul(v, g, w);
+        if (idx >= half) {   // w_N^(idx) = -w_N^(idx - N/2)
+            fr9_t z;
+            fr9_zero(z);
+            fr9_sub4(v, z, v);
+        }
+        fr9_one(one);
+        fr9_sub4(v, v, one);
+        fr9_reduce(v, v);
+        (void)fr9_inv(v, v);   // never zero: g^T is not an E-th root of unity
+    } else if (t < QC_INVT) {
+        fr9_zero(v);
+    } else if (t == QC_INVT) {
+        constexpr uint32_t HALF[8] = {0x80000001u, 0x7fffffffu, 0x7fff2dffu, 0xa9ded201u,
+                                      0x04d0ec02u, 0x199cec04u, 0x94cebea4u, 0x39f6d3a9u};   // (r + 1) / 2
+        uint32_t hw[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) hw[i] = HALF[i];
+        fr9_from_words(v, hw);
+        fr9_to_mont(v, v);
+        fr9_pow(v, v, (uint64_t)log_t);
+    } else if (t == QC_G) {
+        fr9_coset_gen(v, 0);
+    } else if (t < QC_TABLES) {
+        fr9_zero(v);
+    } else {
+        const uint64_t u = t - QC_TABLES;
+        if (u >= 2 * (SA + SB)) return;
+        const int inverse = u >= SA + SB;
+        const uint64_t e = inverse ? u - (SA + SB) : u;
+        fr9_coset_gen(v, inverse);
+        fr9_pow(v, v, e < SA ? e : (e - SA) << h);
+    }
+    fr9_store(qc + 8 * t, v);
+}
+void launch_quot_consts(hipStream_t s, uint32_t* qc, int log_t, int ext_log, const uint32_t* tw_n) {
+    k_quot_consts<<<nblk(quot_consts_elems(log_t, ext_log), 64), 64, 0, s>>>(qc, log_t, ext_log, tw_n);
+}
+
+// g^(+-i) from the two tables: one product
+KZG_DEV void quot_gpow(fr9_t& p, const uint32_t* __restrict__ qc, int log_n, int inverse, uint64_t i) {
+    const int h = quot_h(log_n);
+    const uint64_t SA = (uint64_t)1 << h, SB = (uint64_t)1 << (log_n - h);
+    const uint32_t* tab = qc + 8 * (QC_TABLES + (inverse ? SA + SB : 0));
+    fr9_t a, b;
+    fr9_load(a, tab + 8 * (i & (SA - 1)));
+    fr9_load(b, tab + 8 * (SA + (i >> h)));
+    fr9_mul(p, a, b);
+}
+
+// ------------------------------------------------------------------------------------------------ coset extension
+__global__ void __launch_bounds__(256) k_quot_extend(const uint32_t* __restrict__ f, uint32_t* __restrict__ ext, int log_t,
+                                                      int log_n, const uint32_t* __restrict__ qc) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >> log_n) return;
+    if (i >> log_t) {
+        uint4* q = reinterpret_cast<uint4*>(ext + 8 * i);
+        q[0] = make_uint4(0u, 0u, 0u, 0u);
+        q[1] = make_uint4(0u, 0u, 0u, 0u);
+        return;
+    }
+    fr9_t p, c;
+    quot_gpow(p, qc, log_n, 0, i);
+    fr9_load(c, f ? f + 8 * i : qc + 8 * QC_INVT);
+    fr9_mul(p, p, c);
+    fr9_canon(p, p);
+    fr9_store(ext + 8 * i, p);
+}
+void launch_quot_extend(hipStream_t s, const uint32_t* f_or_null, uint32_t* ext, int log_t, int ext_log, const uint32_t* qc) {
+    const int log_n = log_t + ext_log;
+    k_quot_extend<<<nblk((uint64_t)1 << log_n, 256), 256, 0, s>>>(f_or_null, ext, log_t, log_n, qc);
+}
+
+// ------------------------------------------------------------------------------------------------ the constraint arithmetic
+// Everything that describes the constraints rides in ONE kernel argument (1.1 KB); the first lanes of every workgroup convert
+// the scalars to Montgomery form once into LDS (one or two products each, in parallel).  The term loop is uniform over the
+// workgroup (trip counts and row indices come from the argument), so a row pointer is a scalar load and a factor costs one
+// 32-byte vector load and one product.  Sums are renormalised after every term: at most 16 terms + alpha P1 + alpha^2 P2,
+// each below 2r, stay below 36r -- a legal first operand of the closing product by 1 / Z_H.
+struct QuotArg {
+    FrArg c[QUOT_MAX_TERMS], shift[QUOT_MAX_WIRES], beta, gamma, alpha;
+    uint8_t len[QUOT_MAX_TERMS], row[QUOT_MAX_TERMS][QUOT_MAX_FACTORS], wire[QUOT_MAX_WIRES], sigma[QUOT_MAX_WIRES];
+    uint32_t n_terms, k, z_row, ext_log;
+};
+static_assert(sizeof(QuotArg) + sizeof(RowTab) + 64 <= 4096, "k_quot_points' arguments must fit in 4 KB");
+enum { QS_SHIFT = QUOT_MAX_TERMS, QS_BETA = QS_SHIFT + QUOT_MAX_WIRES, QS_GAMMA, QS_ALPHA, QS_ALPHA2, QS_COUNT };
+KZG_DEV void quot_arg(fr9_t& v, const FrArg& a, uint32_t* __restrict__ bad, bool check) {
+    uint32_t w[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) w[i] = bswap32(a.w[7 - i]);
+    if (check && fr_words_ge_r(w)) atomicOr(bad, 1u);
+    fr9_from_words(v, w);
+    fr9_to_mont(v, v);
+}
+KZG_DEV void lds_get(fr9_t& v, const uint32_t (*cst)[9], uint32_t j) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) v.l[i] = cst[j][i];
+}
+__global__ void __launch_bounds__(256) k_quot_points(const RowTab rt, const uint32_t* __restrict__ l0, uint32_t* __restrict__ out,
+                                                      int log_n, const QuotArg qa, const uint32_t* __restrict__ tw,
+                                                      const uint32_t* __restrict__ qc, uint32_t* __restrict__ bad) {
+    __shared__ uint32_t cst[QS_COUNT][9];
+    const uint32_t v = threadIdx.x;
+    const bool chk = blockIdx.x == 0;
+    if (v < QS_COUNT) {
+        fr9_t c;
+        bool live = true;
+        if (v < QS_SHIFT) {
+            live = v < qa.n_terms;
+            if (live) quot_arg(c, qa.c[v], bad, chk);
+        } else if (v < QS_BETA) {   // beta s_j
+            live = v - QS_SHIFT < qa.k;
+            if (live) {
+                fr9_t b;
+                quot_arg(c, qa.shift[v - QS_SHIFT], bad, chk);
+                quot_arg(b, qa.beta, bad, false);
+                fr9_mul(c, c, b);
+                fr9_canon(c, c);
+            }
+        } else if (v == QS_BETA) {
+            quot_arg(c, qa.beta, bad, chk);
+        } else if (v == QS_GAMMA) {
+            quot_arg(c, qa.gamma, bad, chk);
+        } else {
+            quot_arg(c, qa.alpha, bad, chk);
+            if (v == QS_ALPHA2) {
+                fr9_mul(c, c, c);
+                fr9_canon(c, c);
+            }
+        }
+        if (!live) fr9_zero(c);
+#pragma unroll
+        for (int i = 0; i < 9; i++) cst[v][i] = c.l[i];
+    }
+    __syncthreads();
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + v;
+    if (i >> log_n) return;
+    const uint64_t n = (uint64_t)1 << log_n, half = n >> 1;
+    fr9_t acc, p, c;
+    fr9_zero(acc);
+    for (uint32_t u = 0; u < qa.n_terms; u++) {
+        lds_get(p, cst, u);
+        const uint32_t len = qa.len[u];
+        for (uint32_t f = 0; f < len; f++) {
+            fr9_load(c, rt.r[qa.row[u][f]] + 8 * i);
+            fr9_mul(p, p, c);
+        }
+        fr9_add(acc, acc, p);
+        fr9_norm(acc, acc);
+    }
+    if (qa.k) {
+        fr9_t x, g, gamma, beta, A, B, z, a, sg, t, fa;
+        // x_i = g w_N^i, kept lazy (a first operand only)
+        fr9_load(g, qc + 8 * QC_G);
+        tw_get(c, tw, i & (half - 1));
+        fr9_mul(x, g, c);
+        if (i >= half) {
+            fr9_zero(t);
+            fr9_sub4(x, t, x);
+        }
+        lds_get(gamma, cst, QS_GAMMA);
+        lds_get(beta, cst, QS_BETA);
+        const uint32_t* zr = rt.r[qa.z_row];
+        fr9_load(z, zr + 8 * i);
+        fr9_load(B, zr + 8 * ((i + ((uint64_t)1 << qa.ext_log)) & (n - 1)));
+        A = z;
+        for (uint32_t j = 0; j < qa.k; j++) {
+            fr9_load(a, rt.r[qa.wire[j]] + 8 * i);
+            fr9_load(sg, rt.r[qa.sigma[j]] + 8 * i);
+            lds_get(c, cst, QS_SHIFT + j);
+            fr9_mul(t, x, c);                 // beta s_j x_i
+            fr9_add(fa, a, gamma);
+            fr9_add(t, t, fa);                // < 4r
+            fr9_norm(t, t);
+            fr9_mul(A, t, A);
+            fr9_mul(t, sg, beta);
+            fr9_add(t, t, fa);
+            fr9_norm(t, t);
+            fr9_mul(B, t, B);
+        }
+        fr9_sub4(A, A, B);                    // P1, < 6r
+        lds_get(c, cst, QS_ALPHA);
+        fr9_mul(t, A, c);
+        fr9_add(acc, acc, t);
+        fr9_norm(acc, acc);
+        // P2 / Z_H = (z - 1) L_0 / Z_H: l0 holds L_0 on the coset, the division is the closing product below
+        fr9_one(c);
+        fr9_sub4(z, z, c);
+        fr9_load(c, l0 + 8 * i);
+        fr9_mul(t, z, c);
+        lds_get(c, cst, QS_ALPHA2);
+        fr9_mul(t, t, c);
+        fr9_add(acc, acc, t);
+        fr9_norm(acc, acc);
+    }
+    fr9_load(c, qc + 8 * (i & ((1u << qa.ext_log) - 1)));
+    fr9_mul(acc, acc, c);
+    fr9_canon(acc, acc);
+    fr9_store(out + 8 * i, acc);
+}
+void launch_quot_points(hipStream_t s, const RowTab& ext_rows, const uint32_t* l0, uint32_t* out, int log_t, const QuotPlan& qp,
+                        const uint32_t* tw_n, const uint32_t* qc, uint32_t* bad) {
+    QuotArg qa;
+    memset(&qa, 0, sizeof(qa));
+    qa.n_terms = qp.n_terms;
+    qa.k = qp.k;
+    qa.z_row = qp.z_row;
+    qa.ext_log = qp.ext_log;
+    for (uint32_t u = 0; u < qp.n_terms; u++) {
+        memcpy(qa.c[u].w, qp.term_coeffs_be32 + 32 * (size_t)u, 32);
+        qa.len[u] = qp.term_len[u];
+        memcpy(qa.row[u], qp.term_row[u], QUOT_MAX_FACTORS);
+    }
+    for (uint32_t j = 0; j < qp.k; j++) {
+        memcpy(qa.shift[j].w, qp.shifts_be32 + 32 * (size_t)j, 32);
+        qa.wire[j] = qp.wire[j];
+        qa.sigma[j] = qp.sigma[j];
+    }
+    if (qp.k) {
+        memcpy(qa.beta.w, qp.beta_be32, 32);
+        memcpy(qa.gamma.w, qp.gamma_be32, 32);
+        memcpy(qa.alpha.w, qp.alpha_be32, 32);
+    }
+    const int log_n = log_t + (int)qp.ext_log;
+    k_quot_points<<<nblk((uint64_t)1 << log_n, 256), 256, 0, s>>>(ext_rows, l0, out, log_n, qa, tw_n, qc, bad);
+}
+
+// ------------------------------------------------------------------------------------------------ back to the pieces
+__global__ void __launch_bounds__(256) k_quot_pieces(const uint32_t* __restrict__ in, uint32_t* __restrict__ dst, int log_n,
+                                                      uint64_t kept, const uint32_t* __restrict__ qc,
+                                                      uint32_t* __restrict__ tail_flag) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >> log_n) return;
+    if (i >= kept) {   // canonical input: zero exactly when every word is
+        const uint4* q = reinterpret_cast<const uint4*>(in + 8 * i);
+        const uint4 a = q[0], b = q[1];
+        if (a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w) atomicOr(tail_flag, 1u);
+        return;
+    }
+    fr9_t p, c;
+    quot_gpow(p, qc, log_n, 1, i);
+    fr9_load(c, in + 8 * i);
+    fr9_mul(p, p, c);
+    fr9_canon(p, p);
+    fr9_store(dst + 8 * i, p);
+}
+void launch_quot_pieces(hipStream_t s, const uint32_t* in, uint32_t* dst, int log_t, int ext_log, uint32_t n_pieces,
+                        const uint32_t* qc, uint32_t* tail_flag) {
+    const int log_n = log_t + ext_log;
+    k_quot_pieces<<<nblk((uint64_t)1 << log_n, 256), 256, 0, s>>>(in, dst, log_n, (uint64_t)n_pieces << log_t, qc, tail_flag);
+}

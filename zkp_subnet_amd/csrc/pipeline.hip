@@ -768,4 +768,100 @@ int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& 
     return KZG_OK;
 }
 
+// the quotient's constants of one (T, E), shared by all lanes like the twiddles: built once under the ctx mutex
+static int ensure_quot_consts(kzg_ctx* ctx, Lane& L, int log_t, int ext_log, const uint32_t* tw_n, const uint32_t** qc) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const int key = log_t * 4 + ext_log;
+    if (!ctx->quot_consts.count(key)) {
+        DevBuf b;
+        HIPCHK(ctx, b.ensure(quot_consts_elems(log_t, ext_log) * 32));
+        launch_quot_consts(L.stream, b.as<uint32_t>(), log_t, ext_log, tw_n);
+        HIPCHK(ctx, hipStreamSynchronize(L.stream));
+        ctx->quot_consts[key] = std::move(b);
+    }
+    *qc = ctx->quot_consts[key].as<uint32_t>();
+    return KZG_OK;
+}
+// The PLONK quotient (kzg_rows_commit_quotient): a set built FROM sets.  Every DISTINCT row the constraints name (by device
+// pointer: a wire is named by the gate and by the permutation) is extended to the coset g H_N, N = E T -- one scaling launch
+// into the lane's staging vector, one forward transform of length N into its own vector of the lane's quotient workspace --
+// and so is L_0 when there is a permutation part; one pointwise launch writes num / Z_H into the staging vector; the inverse
+// transform and the g^-i launch leave the P pieces in the new set's buffer `dst` and OR the coefficients above P T into the
+// record's first evaluation slot; ONE MSM pass of P scalar sets commits.  Workspace: (distinct rows + 2) vectors of N.
+// The flag travels in the record's one copy behind the MSM, so an instance that fails the shape check still pays the MSM
+// before KZG_E_ARG comes back: no set is created, but the error path is not a fast path (a read-back of its own in front of
+// the MSM would cost every good call a synchronisation).
+int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t n_rows, uint64_t T, const QuotPlan& qp,
+                      uint32_t n_pieces, uint32_t* dst, uint8_t* out_c48, bool* out_bad_shape) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const int lg = ilog2_exact(T), ext_log = (int)qp.ext_log, lgn = lg + ext_log;
+    const uint64_t N = T << ext_log, nw = N * 8;   // one extended vector, in words
+    uint32_t *tw = nullptr, *twi = nullptr, *invn = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, lgn, 0, &tw, nullptr)) return rc;
+    if (int rc = ensure_twiddles(ctx, A, lgn, 1, &twi, &invn)) return rc;
+    const uint32_t* qc = nullptr;
+    if (int rc = ensure_quot_consts(ctx, A, lg, ext_log, tw, &qc)) return rc;
+    // the rows in use, one workspace vector per distinct device pointer
+    bool used[POLY_MAX_ROWS] = {};
+    for (uint32_t u = 0; u < qp.n_terms; u++)
+        for (uint32_t f = 0; f < qp.term_len[u]; f++) used[qp.term_row[u][f]] = true;
+    for (uint32_t j = 0; j < qp.k; j++) used[qp.wire[j]] = used[qp.sigma[j]] = true;
+    if (qp.k) used[qp.z_row] = true;
+    int slot[POLY_MAX_ROWS];
+    uint32_t nd = 0;
+    for (uint32_t j = 0; j < n_rows; j++) {
+        slot[j] = -1;
+        if (!used[j]) continue;
+        for (uint32_t e = 0; e < j && slot[j] < 0; e++)
+            if (used[e] && rt.r[e] == rt.r[j]) slot[j] = slot[e];
+        if (slot[j] < 0) slot[j] = (int)nd++;
+    }
+    HIPCHK(ctx, A.qext.ensure((size_t)std::max(nd + (qp.k ? 1u : 0u), 1u) * N * 32));   // (constant terms alone: no row)
+    HIPCHK(ctx, A.qstage.ensure(N * 32));
+    HIPCHK(ctx, A.ntt_mid.ensure(N * 48));
+    uint32_t *ext = A.qext.as<uint32_t>(), *stage = A.qstage.as<uint32_t>(), *mid = A.ntt_mid.as<uint32_t>();
+    RowTab et;
+    memset(&et, 0, sizeof(et));
+    for (uint32_t j = 0, done = 0; j <= n_rows; j++) {   // (j == n_rows: L_0)
+        uint32_t* vec;
+        if (j < n_rows) {
+            if (slot[j] < 0) continue;
+            vec = ext + (uint64_t)slot[j] * nw;
+            et.r[j] = vec;
+            if ((uint32_t)slot[j] < done) continue;   // a repeated row: transformed already
+            done++;
+        } else {
+            if (!qp.k) break;
+            vec = ext + (uint64_t)nd * nw;
+        }
+        {
+            Span sp(ctx, A, KZG_T_POLY);
+            launch_quot_extend(A.stream, j < n_rows ? rt.r[j] : nullptr, stage, lg, ext_log, qc);
+        }
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, stage, vec, lgn, tw, nullptr, mid);
+    }
+    uint8_t* rec = A.brec.as<uint8_t>();
+    HIPCHK(ctx, hipMemsetAsync(rec + MR_EVAL, 0, 32, A.stream));
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_quot_points(A.stream, et, ext + (uint64_t)nd * nw, stage, lg, qp, tw, qc, A.flags());
+    }
+    {
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, stage, ext, lgn, twi, invn, mid);
+    }
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_quot_pieces(A.stream, ext, dst, lg, ext_log, n_pieces, qc, reinterpret_cast<uint32_t*>(rec + MR_EVAL));
+    }
+    uint8_t ev[32];
+    if (int rc = multi_msms_finish(ctx, H, i, T, dst, n_pieces, 0, 1, out_c48, ev, nullptr)) return rc;
+    uint32_t tf;
+    memcpy(&tf, ev, 4);
+    *out_bad_shape = tf != 0;
+    return KZG_OK;
+}
+
 }  // namespace kzg_impl

@@ -889,6 +889,90 @@ int rows_grand_product_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_han
     return KZG_OK;
 }
 
+// kzg_rows_commit_quotient: the lookups of an open (one handle list), the reservation of a commit
+int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                       const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces,
+                       uint8_t* out_commitments48, uint64_t* out_handle) {
+    if (!ctx || !handles || !gate || !out_commitments48 || !out_handle) return KZG_E_ARG;
+    const uint32_t k = perm ? perm->k : 0;
+    if (gate->n_terms && (!gate->coeffs_be32 || !gate->term_lens || !gate->term_rows)) return KZG_E_ARG;
+    if (k && (!perm->wire_rows || !perm->sigma_rows || !perm->shifts_be32 || !perm->beta_be32 || !perm->gamma_be32 ||
+              !perm->alpha_be32))
+        return KZG_E_ARG;
+    if (n_handles == 0 || n_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "quotient: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (ext_log < 1 || ext_log > 3) return fail(ctx, KZG_E_ARG, "quotient: ext_log must be 1, 2 or 3");
+    const uint32_t E = 1u << ext_log;
+    if (n_pieces == 0 || n_pieces > E) return fail(ctx, KZG_E_ARG, "quotient: n_pieces must be in [1, 2^ext_log]");
+    if (gate->n_terms > KZG_MAX_GATE_TERMS) return fail(ctx, KZG_E_ARG, "quotient: more than KZG_MAX_GATE_TERMS gate terms");
+    if (k > E) return fail(ctx, KZG_E_ARG, "quotient: the permutation part has k + 1 factors: k must not exceed 2^ext_log");
+    if (gate->n_terms == 0 && k == 0) return fail(ctx, KZG_E_ARG, "quotient: no gate term and no permutation part");
+    QuotPlan qp;
+    memset(&qp, 0, sizeof(qp));
+    qp.ext_log = ext_log;
+    qp.n_terms = gate->n_terms;
+    qp.k = k;
+    qp.term_coeffs_be32 = gate->coeffs_be32;
+    uint32_t max_row = 0;   // the largest row index named, checked against the rows once they are known
+    bool any_row = false;
+    auto name_row = [&](uint32_t row) {
+        any_row = true;
+        if (row > max_row) max_row = row;
+        return (uint8_t)(row < KZG_MAX_BATCH_OPEN ? row : 0);
+    };
+    for (uint32_t u = 0, at = 0; u < gate->n_terms; u++) {
+        if (!fr_be32_canonical(gate->coeffs_be32 + 32 * (size_t)u))
+            return fail(ctx, KZG_E_ARG, "quotient: term coefficients must be canonical scalars (< r)");
+        if (gate->term_lens[u] > E + 1)
+            return fail(ctx, KZG_E_ARG, "quotient: a gate term has more than 2^ext_log + 1 factors");
+        qp.term_len[u] = (uint8_t)gate->term_lens[u];
+        for (uint32_t f = 0; f < gate->term_lens[u]; f++) qp.term_row[u][f] = name_row(gate->term_rows[at++]);
+    }
+    if (k) {
+        if (!fr_be32_canonical(perm->beta_be32) || !fr_be32_canonical(perm->gamma_be32) || !fr_be32_canonical(perm->alpha_be32))
+            return fail(ctx, KZG_E_ARG, "quotient: beta, gamma and alpha must be canonical scalars (< r)");
+        for (uint32_t j = 0; j < k; j++) {
+            if (!fr_be32_canonical(perm->shifts_be32 + 32 * (size_t)j))
+                return fail(ctx, KZG_E_ARG, "quotient: shifts must be canonical scalars (< r)");
+            qp.wire[j] = name_row(perm->wire_rows[j]);
+            qp.sigma[j] = name_row(perm->sigma_rows[j]);
+        }
+        qp.z_row = name_row(perm->z_row);
+        qp.shifts_be32 = perm->shifts_be32;
+        qp.beta_be32 = perm->beta_be32;
+        qp.gamma_be32 = perm->gamma_be32;
+        qp.alpha_be32 = perm->alpha_be32;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs refs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab rt;
+    uint32_t n = 0, i = 0;
+    uint64_t T = 0;
+    if (int rc = rows_lookup(ctx, "quotient", expect_i, n_handles, handles, refs, rt, &n, &i, &T)) return rc;
+    if (any_row && max_row >= n) return fail(ctx, KZG_E_ARG, "quotient: a row index is not below the number of rows named");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "quotient: the row length must be a power of two");
+    if (int rc2 = rows_reserve(ctx, "quotient", pend, (size_t)n_pieces * T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    bool bad_shape = false;
+    uint8_t c48[48 * 8];
+    rc = rows_quotient_dev(ctx, H, i, rt, n, T, qp, n_pieces, pend.buf.as<uint32_t>(), c48, &bad_shape);
+    if (rc) return rc;
+    if (bad_shape)
+        return fail(ctx, KZG_E_ARG, "quotient: t has a nonzero coefficient at or above n_pieces * T: the constraints do not hold "
+                                    "on the domain, or n_pieces is too small; no set was created");
+    memcpy(out_commitments48, c48, 48 * (size_t)n_pieces);
+    *out_handle = rows_insert(ctx, pend, i, n_pieces, T);
+    return KZG_OK;
+}
+
 int rows_release_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle) {
     if (!ctx) return KZG_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->sets_mu);
@@ -959,6 +1043,11 @@ int kzg_rows_commit_grand_product(kzg_ctx* ctx, uint32_t n_wire_handles, const u
                                   uint8_t out_closing32[32], uint64_t* out_handle) {
     return rows_grand_product_impl(ctx, UINT32_MAX, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
                                    beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle);
+}
+int kzg_rows_commit_quotient(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_gate* gate,
+                             const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,
+                             uint64_t* out_handle) {
+    return rows_quotient_impl(ctx, UINT32_MAX, n_handles, handles, gate, perm, ext_log, n_pieces, out_commitments48, out_handle);
 }
 int kzg_rows_release(kzg_ctx* ctx, uint64_t handle) { return rows_release_impl(ctx, UINT32_MAX, handle); }
 int kzg_rows_stats(kzg_ctx* ctx, uint64_t out_live_sets_bytes[2]) {

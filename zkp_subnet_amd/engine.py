@@ -387,6 +387,59 @@ class HipEngine:
         src = next((x for x in list(wire_sets) + list(sigma_sets) if hasattr(x, "T")), None)
         return RowSet(self, h.value, getattr(src, "i", None), 1, getattr(src, "T", None), [c.raw]), cl.raw
 
+    # ---- a third set built from sets: the PLONK quotient (round 3), computed and committed on the device
+    def commit_quotient(self, sets: Sequence[object], terms: Sequence[Tuple[bytes, Sequence[int]]], perm: Optional[dict] = None,
+                        ext_log: int = 2, n_pieces: int = 3) -> "RowSet":
+        """The pieces of t = (Gate + alpha P1 + alpha^2 P2) / (X^T - 1) of kzg_rows_commit_quotient over the concatenated rows
+        of `sets` (RowSet objects or bare handles), as a new RowSet of n_pieces rows.  terms: (32-byte coefficient, row
+        indices) per gate term; perm: None, or a dict with "wires", "sigmas" (k row indices each), "z" (a row index),
+        "shifts" (k x 32 bytes), "beta", "gamma", "alpha" (32 bytes each); k = 0 (no wire) switches the part off like None.
+        alpha must be drawn after z's commitment is
+        fixed, beta and gamma after the wires.  KZG_E_ARG when t does not fit n_pieces rows (the constraints do not hold on
+        the domain, or n_pieces is too small)."""
+        n, hs = self._handle_array(sets, "commit_quotient")
+        bad = lambda why: KzgError(_native.KZG_E_ARG, "commit_quotient: " + why)   # noqa: E731
+        if ext_log not in (1, 2, 3) or not 1 <= n_pieces <= 1 << ext_log:
+            raise bad("ext_log must be 1, 2 or 3 and n_pieces in [1, 2^ext_log]")
+        E = 1 << ext_log
+        terms = [(bytes(c), [int(j) for j in rows]) for c, rows in terms]
+        if len(terms) > _native.KZG_MAX_GATE_TERMS or any(len(c) != 32 or len(rows) > E + 1 for c, rows in terms):
+            raise bad(f"at most {_native.KZG_MAX_GATE_TERMS} terms of a 32-byte coefficient and at most 2^ext_log + 1 rows")
+        gate_rows = [j for _, rows in terms for j in rows]
+        if any(not 0 <= j < 1 << 32 for j in gate_rows):
+            raise bad("row indices must be non-negative integers below 2^32")
+        lens = (ctypes.c_uint32 * max(len(terms), 1))(*[len(rows) for _, rows in terms])
+        gate = _native.QuotientGate(len(terms), b"".join(c for c, _ in terms), lens, None)
+        pm = None
+        if perm is not None:
+            try:
+                wires, sigmas = [int(j) for j in perm["wires"]], [int(j) for j in perm["sigmas"]]
+                k = len(wires)
+                if k:   # (k == 0 switches the part off, as perm->k == 0 does: nothing else of perm is read)
+                    shifts, z = list(perm["shifts"]), int(perm["z"])
+                    scal = shifts + [perm["beta"], perm["gamma"], perm["alpha"]]
+            except (KeyError, TypeError, ValueError) as e:
+                raise bad(f"malformed permutation part: {e!r}") from e
+            if k:
+                if k > E or len(sigmas) != k or len(shifts) != k or any(len(x) != 32 for x in scal):
+                    raise bad("the permutation part takes at most 2^ext_log wires, as many sigmas and shifts, and 32-byte scalars")
+                if any(not 0 <= j < 1 << 32 for j in wires + sigmas + [z]):
+                    raise bad("row indices must be non-negative integers below 2^32")
+                pm = _native.QuotientPerm(k, z, (ctypes.c_uint32 * k)(*wires), (ctypes.c_uint32 * k)(*sigmas),
+                                          b"".join(shifts), perm["beta"], perm["gamma"], perm["alpha"])
+            elif sigmas:
+                raise bad("the permutation part names sigma rows but no wire")
+        if not terms and pm is None:
+            raise bad("no gate term and no permutation part")
+        rows_arr = (ctypes.c_uint32 * max(len(gate_rows), 1))(*gate_rows)
+        gate.term_rows = ctypes.cast(rows_arr, ctypes.POINTER(ctypes.c_uint32))
+        c, h = ctypes.create_string_buffer(48 * n_pieces), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_quotient(self._h, n, hs, ctypes.byref(gate), ctypes.byref(pm) if pm is not None else None,
+                                                     ext_log, n_pieces, c, ctypes.byref(h)))
+        src = next((x for x in sets if hasattr(x, "T")), None)
+        return RowSet(self, h.value, getattr(src, "i", None), n_pieces, getattr(src, "T", None),
+                      [c.raw[48 * p:48 * p + 48] for p in range(n_pieces)])
+
     def _handle_array(self, sets, what):
         handles = [int(getattr(x, "handle", x)) for x in sets]
         n = len(handles)
