@@ -241,6 +241,38 @@ int kzg_rows_commit_grand_product(kzg_ctx* ctx, uint32_t n_wire_handles, const u
                                   const uint8_t* shifts_be32 /* k*32 */, const uint8_t beta_be32[32],
                                   const uint8_t gamma_be32[32], uint8_t out_commitment48[48], uint8_t out_closing32[32],
                                   uint64_t* out_handle);
+/* A fourth set built FROM sets: the running sum of a log-derivative lookup argument (logUp), computed and committed on the
+ * device from rows that are already resident.  The concatenated rows of the input_handles sets are the L * w rows f_{l,c},
+ * lookup-major (l < L = n_lookups, c < w = width); those of the table_handles sets are the w table columns t_c; mult_handle
+ * names a ONE-row set m, the multiplicities (how many input cells hit table row t).  With w_T the T-th root of unity of
+ * evaluation_form = 1 rows (7^((r-1)/T), natural order) and t in [0, T):
+ *   F_l(w_T^t) = sum_c theta^c f_{l,c}(w_T^t),   Tb(w_T^t) = sum_c theta^c t_c(w_T^t)        (theta unused when w = 1)
+ *   term_t = sum_l 1 / (beta + F_l(w_T^t))  -  m(w_T^t) / (beta + Tb(w_T^t))
+ *   S(w_T^0) = 0,  S(w_T^(t+1)) = S(w_T^t) + term_t  (t < T - 1),   closing = sum_{t<T} term_t.
+ * The call creates a new ONE-ROW set of the same worker and length holding S's coefficients, exactly as if S's T evaluations
+ * had gone through kzg_rows_commit(i, 1, S, T, 1, ..): out_commitment48 equals that call's byte for byte and *out_handle opens,
+ * evaluates, combines, releases, goes stale and counts against KZG_MAX_ROW_SETS (KZG_E_BUSY; KZG_E_NOMEM on a failed
+ * allocation) like any other.  out_closing32 is canonical big-endian: 0 exactly when the sum closes (every looked-up tuple is
+ * in the table with the stated multiplicities, except with probability ~ (L + 1) T / r over beta).  The library does not judge
+ * it.  Nothing row-sized crosses the host link in either direction.
+ * Handle lists follow kzg_rows_open: 1 .. KZG_MAX_BATCH_OPEN handles each, a handle may repeat (also across the lists), unknown /
+ * released / stale -> KZG_E_ARG; 1 <= w, 1 <= L, L * w <= KZG_MAX_BATCH_OPEN; the input concatenation must hold exactly L * w
+ * rows, the table concatenation exactly w rows, the multiplicity set exactly one row; every set named must belong to one
+ * worker and one (power-of-two) T; theta or beta >= r -> KZG_E_ARG.  A zero denominator (beta + F_l = 0 or beta + Tb = 0
+ * somewhere on the domain) leaves S undefined: it is found on the device and answered with KZG_E_ARG and a message that says
+ * so, no set created.  The source sets are only read; a release or an SRS load racing the call follows the rules of
+ * kzg_rows_open.  Thread-safe like every call; after any error the context keeps serving.
+ * SOUNDNESS: theta and beta must be drawn AFTER the commitments of the inputs, the table AND m are fixed (a prover who knows
+ * them before it commits m can make a false lookup close).  The library derives no challenge and adds NO BLINDING (as for the
+ * grand product).  closing = 0 is NOT the argument: the wrap-around relation S(w_T X) - S(X) = term(X) on all of H (which
+ * forces closing = 0) belongs in the caller's quotient.
+ * OUT OF SCOPE: that quotient term (it needs S at X and w_T X inside kzg_rows_commit_quotient, i.e. gate factors with a
+ * rotation); computing m on the device (a join of 32-byte keys); per-row selectors (a caller points inactive rows at a default
+ * table entry); plookup; blinding. */
+int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                               uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
+                               uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32], const uint8_t beta_be32[32],
+                               uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle);
 /* A third set built FROM sets: the PLONK quotient (round 3), computed and committed on the device from rows that are already
  * resident.  The concatenated rows of the handles (as in kzg_rows_open) are f_0 .. f_{n-1}, n <= KZG_MAX_BATCH_OPEN, all of
  * one worker and one power-of-two length T; everything below names a row by its index into that list.  A full standard PLONK
@@ -514,6 +546,12 @@ int kzg_multi_rows_commit_grand_product(kzg_multi* mh, uint32_t i, uint32_t n_wi
                                         uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
                                         const uint8_t* shifts_be32, const uint8_t beta_be32[32], const uint8_t gamma_be32[32],
                                         uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle);
+/* kzg_rows_commit_lookup_sum on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_lookup_sum(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                     uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
+                                     uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32],
+                                     const uint8_t beta_be32[32], uint8_t out_commitment48[48], uint8_t out_closing32[32],
+                                     uint64_t* out_handle);
 /* kzg_rows_commit_quotient on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
 int kzg_multi_rows_commit_quotient(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
                                    const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log,

@@ -14,7 +14,9 @@ extern "C" {
 
 /* ---- unit-op hooks for the parity tests (tests/test_gpu_units.py); not part of the serving surface */
 int kzg_test_field(kzg_ctx* ctx, int field /*0 Fp,1 Fr*/, int op /*0 mul,1 add,2 sub,3 mul(plain C ref),4 sqr; Fr only: 7 a^-1 by the
-                   device-side inversion of the grand-product call, giving 0 for a = 0; 8 that inversion's zero flag, 0 or 1; b unused*/,
+                   device-side inversion of the grand-product call, giving 0 for a = 0; 8 that inversion's zero flag, 0 or 1; 9 a^-1 for all n
+                   elements by the batched inversion of the lookup-sum call (one device-side inversion in all), KZG_E_ARG when
+                   some a = 0; b unused*/,
                    const uint8_t* a_be, const uint8_t* b_be, uint8_t* out_be, uint64_t n);
 int kzg_test_g1(kzg_ctx* ctx, int op /*0 a+b mixed,1 2a+b full,2 2a,3 4a,4 a+20a+20b chain; lane-parallel forms: 5 2a+b,
                                          6 4a, 7 ten rounds r <- 2r+b from a*/, const uint8_t* a_be96,

@@ -75,6 +75,8 @@ SYMBOLS = {
     "kzg_rows_open_lincomb": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _U32, _B, _B, _B, _B]),
     "kzg_rows_commit_grand_product": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _B, _B, _B, _B, _B,
                                            ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_lookup_sum": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B, _B, _B, _B,
+                                        ctypes.POINTER(_U64)]),
     "kzg_rows_commit_quotient": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientGate), ctypes.POINTER(QuotientPerm),
                                       _U32, _U32, _B, ctypes.POINTER(_U64)]),
     "kzg_commit_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B]),
@@ -136,6 +138,8 @@ SYMBOLS = {
     "kzg_multi_rows_open_lincomb": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _U32, _B, _B, _B, _B]),
     "kzg_multi_rows_commit_grand_product": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _B, _B, _B,
                                                  _B, _B, ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_lookup_sum": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B,
+                                              _B, _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_quotient": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientGate),
                                             ctypes.POINTER(QuotientPerm), _U32, _U32, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_commit_open_rows": (_I, [_P, _U32, ctypes.POINTER(_U32), _B, _U64, _I, _B, _B, _B, _B, ctypes.POINTER(_I)]),

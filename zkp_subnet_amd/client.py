@@ -333,6 +333,29 @@ class Client:
                 "closing": codec.be32_to_fr(closing)}
 
     @_guard
+    def worker_commit_lookup_sum(self, input_handles: Sequence[int], table_handles: Sequence[int], mult_handle: int,
+                                 n_lookups: int, width: int, theta: str, beta: str):
+        """Extension: the running sum S of a log-derivative lookup argument over the rows of committed sets (n_lookups *
+        width input rows from input_handles, lookup-major; width table columns from table_handles; the multiplicities in
+        the one-row set mult_handle), computed and committed on the device as a new one-row set.  Returns its handle, its
+        commitment and the closing value (0 when the sum closes).  theta and beta must be drawn after the commitments of
+        the inputs, the table and the multiplicities are fixed."""
+        hi, ht, hm = _handles(input_handles), _handles(table_handles), _handles([mult_handle])[0]
+        try:
+            n_lookups, width = int(n_lookups), int(width)
+        except (TypeError, ValueError) as e:
+            raise codec.CodecError(f"worker_commit_lookup_sum: n_lookups and width must be integers: {e!r}") from e
+        if n_lookups < 1 or width < 1 or n_lookups * width > KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"worker_commit_lookup_sum: n_lookups = {n_lookups}, width = {width}, expected both >= 1 "
+                                   f"and n_lookups * width <= {KZG_MAX_BATCH_OPEN}")
+        sc = [codec.fr_to_be32(x) for x in (theta, beta)]
+        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in sc):
+            raise codec.CodecError("worker_commit_lookup_sum: theta and beta must be canonical scalars (< r)")
+        rs, closing = self.engine.commit_lookup_sum(hi, ht, hm, n_lookups, width, sc[0], sc[1])
+        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]),
+                "closing": codec.be32_to_fr(closing)}
+
+    @_guard
     def worker_commit_quotient(self, handles: Sequence[int], terms, perm=None, ext_log: int = 2, n_pieces: int = 3):
         """Extension: the PLONK quotient t over the rows of committed sets, computed and committed on the device as a new set
         of n_pieces rows.  terms: [coefficient, [row indices]] per gate term; perm: None or {"wires", "sigmas", "z",

@@ -188,6 +188,29 @@ int kzg_test_field(kzg_ctx* ctx, int field, int op, const uint8_t* a_be, const u
     uint32_t blocks = (uint32_t)((n + 255) / 256);
     if (field == 0) k_test_fp<<<blocks, 256, 0, L.stream>>>(op, da, db, L.out_be.as<uint8_t>(), n);
     else if (op == 7 || op == 8) launch_fr_inv_test(L.stream, da, L.out_be.as<uint8_t>(), n, op == 8);   // the device-side inversion alone
+    else if (op == 9) {   // the batched inversion of kzg_rows_commit_lookup_sum alone: n elements, one fr9_inv
+        const uint64_t nchunks = (n + 3) / 4;
+        HIPCHK(ctx, L.coeffA.ensure(n * 32));
+        HIPCHK(ctx, L.coeffB.ensure(n * 32));
+        HIPCHK(ctx, L.hbuf.ensure((nchunks + (nchunks >> 1) + 64) * 32));
+        HIPCHK(ctx, L.hnext.ensure((nchunks + (nchunks >> 1) + 64) * 32));
+        HIPCHK(ctx, L.scal.ensure(64));   // [0, 32) the scan's closing slot (unused), [32] zero flag, [36] range flag (unused)
+        uint32_t* q = L.coeffA.as<uint32_t>();
+        uint32_t* fl = L.scal.as<uint32_t>();
+        HIPCHK(ctx, hipMemsetAsync(fl, 0, 64, L.stream));
+        launch_fr_from_be(L.stream, da, q, n, 1, fl + 9);
+        launch_fr_batch_inv(L.stream, q, L.coeffB.as<uint32_t>(), nullptr, L.coeffB.as<uint32_t>(), n, L.hbuf.as<uint32_t>(),
+                            L.hnext.as<uint32_t>(), L.scal.as<uint8_t>(), fl + 8);
+        launch_fr_to_be(L.stream, L.coeffB.as<uint32_t>(), L.out_be.as<uint8_t>(), n, 1);
+        uint32_t zf = 0;
+        HIPCHK(ctx, hipMemcpyAsync(&zf, fl + 8, 4, hipMemcpyDeviceToHost, L.stream));
+        HIPCHK(ctx, hipMemcpyAsync(out_be, L.out_be.p, n * w, hipMemcpyDeviceToHost, L.stream));
+        HIPCHK(ctx, hipStreamSynchronize(L.stream));
+        HIPCHK(ctx, hipGetLastError());
+        H.clean = true;
+        if (zf) return fail(ctx, KZG_E_ARG, "batched inversion: an element is zero");
+        return KZG_OK;
+    }
     else k_test_fr<<<blocks, 256, 0, L.stream>>>(op, da, db, L.out_be.as<uint8_t>(), n);
     HIPCHK(ctx, hipMemcpyAsync(out_be, L.out_be.p, n * w, hipMemcpyDeviceToHost, L.stream));
     HIPCHK(ctx, hipStreamSynchronize(L.stream));

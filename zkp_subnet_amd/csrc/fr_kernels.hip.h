@@ -95,6 +95,11 @@ void launch_gp_factors(hipStream_t s, const uint32_t* ea, const uint32_t* es, ui
 // prod D == 0 (z undefined, N then holds zeros), else 0
 void launch_gp_scan(hipStream_t s, uint32_t* N, uint32_t* D, uint64_t n, uint32_t* scrN, uint32_t* scrD,
                     uint8_t* closing_be, uint32_t* zero_flag);
+// the scan without its last level (N and D only read; they may be one vector): scrN[g] / scrD[g] <- the exclusive prefix
+// product of N in front of level-0 chunk g / the exclusive suffix product of D behind it times 1 / prod D; closing_be and
+// zero_flag as above.  Returns log2 of the level-0 chunk length.  n > 0
+int launch_gp_scan_upper(hipStream_t s, const uint32_t* N, const uint32_t* D, uint64_t n, uint32_t* scrN, uint32_t* scrD,
+                         uint8_t* closing_be, uint32_t* zero_flag);
 // test hook: out[j] = in[j]^-1 (32 big-endian bytes each, canonical; 0 for in[j] == 0) or, with want_flag, the inversion's
 // zero flag (0 / 1) in the same format
 void launch_fr_inv_test(hipStream_t s, const uint8_t* in_be, uint8_t* out_be, uint64_t n, int want_flag);
@@ -122,3 +127,18 @@ void launch_quot_points(hipStream_t s, const RowTab& ext_rows, const uint32_t* l
 // consecutive); *tail_flag |= 1 when some in[i], i >= n_pieces T, is not zero
 void launch_quot_pieces(hipStream_t s, const uint32_t* in, uint32_t* dst, int log_t, int ext_log, uint32_t n_pieces,
                         const uint32_t* qc, uint32_t* tail_flag);
+// ---- the lookup (logUp) running sum (fr_lookup.hip; kzg_rows_commit_lookup_sum)
+// one transformed column e (n evaluations, Montgomery) folded in: v = acc theta + e (has_acc) or e, then by mode
+//   0: acc <- v    1: Q <- beta + v, P <- -P (P holds m's evaluations)    2: (P, Q) <- (P d + Q, Q d), d = beta + v
+// theta, beta as 32 big-endian HOST bytes, *bad raised when >= r
+void launch_lk_step(hipStream_t s, const uint32_t* e, uint32_t* acc, uint32_t* P, uint32_t* Q, uint64_t n, int mode,
+                    bool has_acc, const uint8_t theta_be32[32], const uint8_t beta_be32[32], uint32_t* bad);
+// The batched inversion: out[t] <- 1 / Q[t], or P[t] / Q[t] when P is given, for n Montgomery elements with ONE fr9_inv:
+// 1 / Q_t = (prod_{u<t} Q_u) (prod_{u>t} Q_u) / prod_u Q_u.  Q is only read; W: n elements of workspace; out may be W or P.
+// scrN, scrD: (n + 3) / 4 * 3 / 2 + 64 elements of scratch each; scratch32 (device): 32 bytes that are overwritten;
+// *zero_flag (device): 1 when some Q[t] == 0 (out then holds zeros), else 0
+void launch_fr_batch_inv(hipStream_t s, const uint32_t* Q, uint32_t* W, const uint32_t* P_or_null, uint32_t* out, uint64_t n,
+                         uint32_t* scrN, uint32_t* scrD, uint8_t* scratch32, uint32_t* zero_flag);
+// v[t] <- sum_{u<t} v[u] in place (n Montgomery elements, canonical); scr: (n + 3) / 4 * 3 / 2 + 64 elements; closing_be
+// (device): sum_u v[u], 32 bytes big-endian
+void launch_lk_sum_scan(hipStream_t s, uint32_t* v, uint64_t n, uint32_t* scr, uint8_t* closing_be);

@@ -281,12 +281,13 @@ __global__ void __launch_bounds__(256) k_gp_final(uint32_t* __restrict__ N, uint
         fr9_mul(p, p, c);
     }
 }
-// N, D (n Montgomery elements each) -> z's evaluations in N (D is consumed).  scrN / scrD: (n + 3) / 4 * 3 / 2 + 64 elements
-// of level scratch each (the sizing of the opening's h / hnext).  Level 0 folds 2^l0 elements per lane (4 for short rows, 16
-// for long ones, as the opening does), every further level 16, until at most GP_TOP_MAX values are left for k_gp_top.
-void launch_gp_scan(hipStream_t s, uint32_t* N, uint32_t* D, uint64_t n, uint32_t* scrN, uint32_t* scrD,
-                    uint8_t* closing_be, uint32_t* zero_flag) {
-    if (!n) return;
+// The scan without its last level: chunk products of N and D up to the top, k_gp_top, the expansions back down to level 1.
+// Leaves in scrN[g] / scrD[g] the exclusive prefix product of N in front of level-0 chunk g and the exclusive suffix product
+// of D behind it (times 1 / prod D); returns the level-0 chunk length's log2.  N and D are only read (they may be one
+// vector: the batched inversion of fr_lookup.hip).  Level 0 folds 2^l0 elements per lane (4 for short rows, 16 for long ones,
+// as the opening does), every further level 16, until at most GP_TOP_MAX values are left for k_gp_top.
+int launch_gp_scan_upper(hipStream_t s, const uint32_t* N, const uint32_t* D, uint64_t n, uint32_t* scrN, uint32_t* scrD,
+                         uint8_t* closing_be, uint32_t* zero_flag) {
     int l0 = 2;
     while (l0 < 4 && (n >> (l0 + 1)) >= 16384) l0++;
     int K = 1, lv_l[16];
@@ -306,5 +307,13 @@ void launch_gp_scan(hipStream_t s, uint32_t* N, uint32_t* D, uint64_t n, uint32_
     for (int k = K - 1; k >= 1; k--)
         k_gp_expand<<<dim3(nblk(lv_n[k + 1], 256), 2), 256, 0, s>>>(scrN + 8 * lv_off[k], scrD + 8 * lv_off[k], lv_n[k], lv_l[k],
                                                                     scrN + 8 * lv_off[k + 1], scrD + 8 * lv_off[k + 1]);
-    k_gp_final<<<nblk(lv_n[1], 256), 256, 0, s>>>(N, D, n, l0, scrN, scrD);
+    return l0;
+}
+// N, D (n Montgomery elements each) -> z's evaluations in N (D is consumed).  scrN / scrD: (n + 3) / 4 * 3 / 2 + 64 elements
+// of level scratch each (the sizing of the opening's h / hnext).
+void launch_gp_scan(hipStream_t s, uint32_t* N, uint32_t* D, uint64_t n, uint32_t* scrN, uint32_t* scrD,
+                    uint8_t* closing_be, uint32_t* zero_flag) {
+    if (!n) return;
+    const int l0 = launch_gp_scan_upper(s, N, D, n, scrN, scrD, closing_be, zero_flag);
+    k_gp_final<<<nblk(((n + ((uint64_t)1 << l0) - 1) >> l0), 256), 256, 0, s>>>(N, D, n, l0, scrN, scrD);
 }

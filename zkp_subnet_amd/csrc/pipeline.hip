@@ -768,6 +768,64 @@ int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& 
     return KZG_OK;
 }
 
+// The lookup running sum (kzg_rows_commit_lookup_sum): a set built FROM sets.  Every named row is transformed into ONE lane
+// buffer and folded in as it arrives: m first (its evaluations start the numerator), the w table columns (Horner in theta from
+// the last column down, the first one closes the chain and writes the fraction -m / (beta + Tb)), then the L lookups the same
+// way, each adding 1 / (beta + F_l) to the running fraction P / Q.  Four vectors of T whatever L and w are (the transform's
+// output, the Horner accumulator, P, Q); the transform's output is dead when the batched inversion needs its workspace.
+// term = P / Q (one inversion), the additive scan turns it into S's evaluations in place, the inverse transform writes S's
+// coefficients straight into the new set's buffer `dst`; one MSM commits.  The record's first two evaluation slots carry the
+// closing value and the zero-denominator flag word.
+int rows_lookup_sum_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& table, const uint32_t* mult,
+                        uint32_t n_lookups, uint32_t width, uint64_t T, const uint8_t* theta_be32, const uint8_t* beta_be32,
+                        uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const int lg = ilog2_exact(T);
+    uint32_t* tw = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
+    const uint64_t nchunks = (T + 3) / 4;
+    HIPCHK(ctx, A.coeffA.ensure(T * 32));
+    HIPCHK(ctx, A.coeffB.ensure(T * 32));
+    HIPCHK(ctx, A.bcomb.ensure(T * 32));
+    HIPCHK(ctx, A.qbuf.ensure(T * 32));
+    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    HIPCHK(ctx, A.hbuf.ensure((nchunks + (nchunks >> 1) + 64) * 32));
+    HIPCHK(ctx, A.hnext.ensure((nchunks + (nchunks >> 1) + 64) * 32));
+    uint32_t *e = A.coeffA.as<uint32_t>(), *acc = A.coeffB.as<uint32_t>();
+    uint32_t *P = A.bcomb.as<uint32_t>(), *Q = A.qbuf.as<uint32_t>(), *mid = A.ntt_mid.as<uint32_t>();
+    uint8_t* rec = A.brec.as<uint8_t>();
+    {
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, mult, P, lg, tw, nullptr, mid);
+    }
+    for (uint32_t l = 0; l <= n_lookups; l++) {   // (l == 0: the table; lookup l - 1 after it)
+        for (uint32_t c = width; c-- > 0;) {
+            {
+                Span sp(ctx, A, KZG_T_NTT);
+                launch_fr_ntt(A.stream, l ? inputs.r[(l - 1) * width + c] : table.r[c], e, lg, tw, nullptr, mid);
+            }
+            Span sp(ctx, A, KZG_T_POLY);
+            launch_lk_step(A.stream, e, acc, P, Q, T, c ? 0 : (l ? 2 : 1), c + 1 < width, theta_be32, beta_be32, A.flags());
+        }
+    }
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        uint32_t* zf = reinterpret_cast<uint32_t*>(rec + MR_EVAL + 32);
+        launch_fr_batch_inv(A.stream, Q, e, P, P, T, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), rec + MR_EVAL, zf);
+        launch_lk_sum_scan(A.stream, P, T, A.hbuf.as<uint32_t>(), rec + MR_EVAL);
+    }
+    const uint32_t* c;
+    if (int rc = row_to_coeffs(ctx, A, P, T, 1, &c, dst)) return rc;
+    uint8_t ev[64];
+    if (int rc = multi_msms_finish(ctx, H, i, T, dst, 1, 0, 2, out_c48, ev, nullptr)) return rc;
+    memcpy(out_closing32, ev, 32);
+    uint32_t zf;
+    memcpy(&zf, ev + 32, 4);
+    *out_zero_den = zf != 0;
+    return KZG_OK;
+}
+
 // the quotient's constants of one (T, E), shared by all lanes like the twiddles: built once under the ctx mutex
 static int ensure_quot_consts(kzg_ctx* ctx, Lane& L, int log_t, int ext_log, const uint32_t* tw_n, const uint32_t** qc) {
     std::lock_guard<std::mutex> lk(ctx->mu);

@@ -889,6 +889,60 @@ int rows_grand_product_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_han
     return KZG_OK;
 }
 
+// kzg_rows_commit_lookup_sum: the lookups of an open (three handle lists), the reservation of a commit
+int rows_lookup_sum_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                         uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
+                         uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint8_t* out_commitment48,
+                         uint8_t* out_closing32, uint64_t* out_handle) {
+    if (!ctx || !input_handles || !table_handles || !theta_be32 || !beta_be32 || !out_commitment48 || !out_closing32 ||
+        !out_handle)
+        return KZG_E_ARG;
+    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN || n_table_handles == 0 || n_table_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "lookup sum: the number of handles in each list must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (n_lookups == 0 || width == 0 || (uint64_t)n_lookups * width > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "lookup sum: n_lookups and width must be at least 1 and n_lookups * width at most "
+                                    "KZG_MAX_BATCH_OPEN");
+    if (!fr_be32_canonical(theta_be32) || !fr_be32_canonical(beta_be32))
+        return fail(ctx, KZG_E_ARG, "lookup sum: theta and beta must be canonical scalars (< r)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs irefs{ctx}, trefs{ctx}, mrefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab it, tt, mt;
+    uint32_t ki = 0, kt = 0, km = 0, i = 0, i2 = 0, i3 = 0;
+    uint64_t T = 0, T2 = 0, T3 = 0;
+    if (int rc = rows_lookup(ctx, "lookup sum (inputs)", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    if (int rc = rows_lookup(ctx, "lookup sum (table)", expect_i, n_table_handles, table_handles, trefs, tt, &kt, &i2, &T2)) return rc;
+    if (int rc = rows_lookup(ctx, "lookup sum (multiplicities)", expect_i, 1, &mult_handle, mrefs, mt, &km, &i3, &T3)) return rc;
+    if (i2 != i || i3 != i || T2 != T || T3 != T)
+        return fail(ctx, KZG_E_ARG, "lookup sum: all sets must belong to one worker and have one row length");
+    if (ki != n_lookups * width || kt != width)
+        return fail(ctx, KZG_E_ARG, "lookup sum: the input sets must hold exactly n_lookups * width rows and the table sets "
+                                    "exactly width rows");
+    if (km != 1) return fail(ctx, KZG_E_ARG, "lookup sum: the multiplicity set must hold exactly one row");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "lookup sum: the row length must be a power of two");
+    if (int rc2 = rows_reserve(ctx, "lookup sum", pend, (size_t)T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    bool zero_den = false;
+    uint8_t c48[48], closing[32];
+    rc = rows_lookup_sum_dev(ctx, H, i, it, tt, mt.r[0], n_lookups, width, T, theta_be32, beta_be32, pend.buf.as<uint32_t>(), c48,
+                             closing, &zero_den);
+    if (rc) return rc;
+    if (zero_den)
+        return fail(ctx, KZG_E_ARG, "lookup sum: zero denominator (some beta + F_l or beta + Tb vanishes on the domain): "
+                                    "S is undefined, no set was created");
+    memcpy(out_commitment48, c48, 48);
+    memcpy(out_closing32, closing, 32);
+    *out_handle = rows_insert(ctx, pend, i, 1, T);
+    return KZG_OK;
+}
+
 // kzg_rows_commit_quotient: the lookups of an open (one handle list), the reservation of a commit
 int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
                        const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces,
@@ -1043,6 +1097,13 @@ int kzg_rows_commit_grand_product(kzg_ctx* ctx, uint32_t n_wire_handles, const u
                                   uint8_t out_closing32[32], uint64_t* out_handle) {
     return rows_grand_product_impl(ctx, UINT32_MAX, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
                                    beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle);
+}
+int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_table_handles,
+                               const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups, uint32_t width,
+                               const uint8_t theta_be32[32], const uint8_t beta_be32[32], uint8_t out_commitment48[48],
+                               uint8_t out_closing32[32], uint64_t* out_handle) {
+    return rows_lookup_sum_impl(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
+                                n_lookups, width, theta_be32, beta_be32, out_commitment48, out_closing32, out_handle);
 }
 int kzg_rows_commit_quotient(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_gate* gate,
                              const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,

@@ -387,6 +387,26 @@ class HipEngine:
         src = next((x for x in list(wire_sets) + list(sigma_sets) if hasattr(x, "T")), None)
         return RowSet(self, h.value, getattr(src, "i", None), 1, getattr(src, "T", None), [c.raw]), cl.raw
 
+    # ---- a fourth set built from sets: the running sum of a logUp lookup argument, computed and committed on the device
+    def commit_lookup_sum(self, input_sets: Sequence[object], table_sets: Sequence[object], mult_set: object, n_lookups: int,
+                          width: int, theta_be32: bytes, beta_be32: bytes) -> Tuple["RowSet", bytes]:
+        """S of kzg_rows_commit_lookup_sum: the n_lookups * width concatenated rows of input_sets (lookup-major) looked up in
+        the width concatenated rows of table_sets with the multiplicities of the one-row mult_set (RowSet objects or bare
+        handles).  Returns (a one-row RowSet holding S, the closing value as 32 bytes big-endian: 0 when the sum closes).
+        theta and beta must be drawn after the commitments of the inputs, the table and the multiplicities are fixed."""
+        ni, hi = self._handle_array(input_sets, "commit_lookup_sum (inputs)")
+        nt, ht = self._handle_array(table_sets, "commit_lookup_sum (table)")
+        _, hm = self._handle_array([mult_set], "commit_lookup_sum (multiplicities)")
+        if n_lookups < 1 or width < 1 or n_lookups * width > _native.KZG_MAX_BATCH_OPEN or len(theta_be32) != 32 \
+                or len(beta_be32) != 32:
+            raise KzgError(_native.KZG_E_ARG, f"commit_lookup_sum: n_lookups, width >= 1, n_lookups * width <= "
+                                              f"{_native.KZG_MAX_BATCH_OPEN}, theta and beta of 32 bytes each")
+        c, cl, h = ctypes.create_string_buffer(48), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_lookup_sum(self._h, ni, hi, nt, ht, hm[0], n_lookups, width, theta_be32, beta_be32,
+                                                       c, cl, ctypes.byref(h)))
+        src = next((x for x in list(input_sets) + list(table_sets) + [mult_set] if hasattr(x, "T")), None)
+        return RowSet(self, h.value, getattr(src, "i", None), 1, getattr(src, "T", None), [c.raw]), cl.raw
+
     # ---- a third set built from sets: the PLONK quotient (round 3), computed and committed on the device
     def commit_quotient(self, sets: Sequence[object], terms: Sequence[Tuple[bytes, Sequence[int]]], perm: Optional[dict] = None,
                         ext_log: int = 2, n_pieces: int = 3) -> "RowSet":
@@ -792,6 +812,11 @@ class HipEngine:
         """The device-side Fr inversion alone (kzg_test_field, Fr ops 7 and 8): (inverses as n x 32 bytes, zero flags)."""
         flags = self.test_field(1, 8, in_be32, in_be32)
         return self.test_field(1, 7, in_be32, in_be32), [flags[32 * j + 31] for j in range(len(in_be32) // 32)]
+
+    def test_fr_batch_inv(self, in_be32: bytes) -> bytes:
+        """The batched inversion of commit_lookup_sum alone (kzg_test_field, Fr op 9): the n inverses as n x 32 bytes;
+        KzgError(KZG_E_ARG) when an element is zero."""
+        return self.test_field(1, 9, in_be32, in_be32)
 
     def test_g1(self, op: int, a_be96: bytes, b_be96: bytes) -> bytes:
         out = ctypes.create_string_buffer(len(a_be96))
