@@ -1,6 +1,7 @@
 """Randomised cross-check of the HIP path against the C oracle (not collected by pytest; needs the GPU; lives under
 tests/ because it uses the oracle):
-MSM (random size / window / scalar distribution / offset), NTT round trips and oracle equality, commit / open /
+MSM (random size / window / scalar distribution / offset; one round in eight over a special-tau SRS of repeated, opposite or
+infinite points), NTT round trips and oracle equality, commit / open /
 commit+open on random rows incl. special alphas, the same through the text path and the row cache (with and without a
 coefficient changed between the two calls), the fused transform + evaluation, and ONE MSM cut over the G contexts of one
 handle (kzg_multi_msm: random G, size, range and scalar distribution against the single-context MSM and the oracle).
@@ -26,13 +27,17 @@ def run(budget=60.0, seed=None, rounds=None, max_log=20, with_comm=False):
     minutes, so that a run cut short by its lease still says how far it got (round 4's hour-long run left only its seed)."""
     seed = int(time.time()) if seed is None else seed
     rnd = random.Random(seed)
+    # the "degenerate" round kind draws from a stream of its own, so that the main stream -- and with it every other choice
+    # of a seeded run -- is what it was before the kind existed
+    rnd_deg = random.Random(seed ^ 0xDE6E4E7A7E)
+    special_taus = (1, o.R - 1, 0, pow(7, (o.R - 1) // 4, o.R))   # all G | G, -G, ... | G, infinities | four points, repeating
     print("seed", seed, flush=True)
     oc.build()
     t_start = time.time()
     t_end = t_start + budget
     t_note = t_start + 120.0
     stats = {"rounds": 0, "msm": 0, "ntt": 0, "kzg": 0, "cache_hits": 0, "cache_misses_after_mutation": 0, "sharded": 0,
-             "segmented": 0}
+             "segmented": 0, "degenerate": 0}
 
     def scalars(n, kind):
         if kind == "uniform":
@@ -62,6 +67,9 @@ def run(budget=60.0, seed=None, rounds=None, max_log=20, with_comm=False):
         if lg <= 14 and rnd.random() < 0.15:
             window = rnd.choice((19, 20, 22, 24))       # the widest windows (what 2^20 .. 2^26 slices use) on small inputs
         tx, ty = rnd.randrange(2, o.R), rnd.randrange(2, o.R)
+        if rnd_deg.randrange(8) == 0:     # one round in eight: repeated, opposite or infinite points (the oracle handles them)
+            tx = rnd_deg.choice(special_taus)
+            stats["degenerate"] += 1
         eng = HipEngine(0, window=window)
         i = rnd.randrange(1 << ms)
         eng.gen_srs(tx, ty, lg, ms, [i])
