@@ -266,8 +266,9 @@ int kzg_rows_commit_grand_product(kzg_ctx* ctx, uint32_t n_wire_handles, const u
  * them before it commits m can make a false lookup close).  The library derives no challenge and adds NO BLINDING (as for the
  * grand product).  closing = 0 is NOT the argument: the wrap-around relation S(w_T X) - S(X) = term(X) on all of H (which
  * forces closing = 0) belongs in the caller's quotient.
- * OUT OF SCOPE: that quotient term (it needs S at X and w_T X inside kzg_rows_commit_quotient, i.e. gate factors with a
- * rotation); computing m on the device (a join of 32-byte keys); per-row selectors (a caller points inactive rows at a default
+ * That quotient term (it needs S at X and w_T X, i.e. gate factors with a rotation) is the lookup part of
+ * kzg_rows_commit_quotient_ext.
+ * OUT OF SCOPE: computing m on the device (a join of 32-byte keys); per-row selectors (a caller points inactive rows at a default
  * table entry); plookup; blinding. */
 int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
                                uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
@@ -325,6 +326,53 @@ typedef struct kzg_quotient_perm {
 int kzg_rows_commit_quotient(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_gate* gate,
                              const kzg_quotient_perm* perm /* NULL: gate only */, uint32_t ext_log, uint32_t n_pieces,
                              uint8_t* out_commitments48 /* n_pieces * 48 */, uint64_t* out_handle);
+/* kzg_rows_commit_quotient with gate factors that may be ROTATED and with the logUp relation of kzg_rows_commit_lookup_sum as a
+ * third part.  Everything not named here follows kzg_rows_commit_quotient: the handle rules, one worker and one power-of-two T,
+ * E = 2^ext_log with ext_log in {1, 2, 3}, the pieces, the SHAPE CHECK when P < E (necessary, not a proof), the new set's life,
+ * thread safety, "after any error the context keeps serving", no blinding, no derived challenge.  With every rotation 0 and
+ * lookup == NULL the call IS kzg_rows_commit_quotient, byte for byte.
+ *   Gate(X) = sum_u c_u prod_f f_{j(u,f)}(w^rot(u,f) X)    term_rots runs beside term_rows (NULL: every rotation 0): on the
+ *             domain factor f reads row j at t + rot (mod T).  Any int32 rot is accepted and reduced mod T (-1 and T - 1, or
+ *             1 and T + 1, give the same bytes).  A term still has at most E + 1 factors.  A rotated factor shares its row's
+ *             extended vector with the unrotated one: no extra transform, no extra workspace.
+ *   D_0     = beta + sum_c theta^c t_c,    D_l = beta + sum_c theta^c f_{l,c}  (l = 1 .. L)        (c < w; the rows f_{l,c} =
+ *             input_rows[(l - 1) w + c], t_c = table_rows[c], m = mult_row, S = sum_row; theta, beta those S was built with)
+ *   LK1(X)  = (S(wX) - S(X)) prod_{l=0..L} D_l  -  [ sum_{l=1..L} prod_{l' != l, l' = 0..L} D_l'  -  m prod_{l=1..L} D_l ]
+ *   LK2(X)  = S(X) L_0(X)
+ *   num     = Gate + alpha P1 + alpha^2 P2 + alpha^3 LK1 + alpha^4 LK2,   t = num / (X^T - 1)
+ * The powers 3 and 4 of alpha are FIXED, whether or not a permutation part is present.  LK1 vanishes on all of H exactly when
+ * the wrap-around relation S(wX) - S(X) = term(X) holds there, which forces closing = 0: this, not the closing value, is the
+ * lookup argument.  LK1 has L + 2 factors, so L <= E - 1; the lookup part alone needs L + 1 pieces.  lookup == NULL: no
+ * lookup part.  perm == NULL or perm->k == 0: no permutation part.
+ * Errors beyond those of kzg_rows_commit_quotient (all KZG_E_ARG): L = 0, w = 0, L > E - 1 or L * w > KZG_MAX_BATCH_OPEN; a
+ * lookup row index >= n; theta, beta or alpha >= r; lookup->alpha_be32 and perm->alpha_be32 (perm->k > 0) unequal in bytes;
+ * no term, no permutation part and no lookup part; a null array inside a part that is present (gate itself must not be NULL;
+ * n_terms = 0 makes it empty).
+ * SOUNDNESS: alpha must be drawn AFTER the commitments of S and z are fixed; theta and beta AFTER the commitments of the
+ * inputs, the table and m (as for kzg_rows_commit_lookup_sum).  Still out of scope: computing m on the device, per-row
+ * selectors, plookup, blinding. */
+typedef struct kzg_quotient_terms {
+    uint32_t n_terms;
+    const uint8_t* coeffs_be32;  /* n_terms * 32 */
+    const uint32_t* term_lens;   /* n_terms */
+    const uint32_t* term_rows;   /* sum of term_lens */
+    const int32_t* term_rots;    /* sum of term_lens; NULL = every rotation 0 */
+} kzg_quotient_terms;
+typedef struct kzg_quotient_lookup {
+    uint32_t n_lookups;          /* L */
+    uint32_t width;              /* w */
+    const uint32_t* input_rows;  /* L * w, lookup-major */
+    const uint32_t* table_rows;  /* w */
+    uint32_t mult_row;           /* m */
+    uint32_t sum_row;            /* S */
+    const uint8_t* theta_be32;   /* 32 */
+    const uint8_t* beta_be32;    /* 32 */
+    const uint8_t* alpha_be32;   /* 32 */
+} kzg_quotient_lookup;
+int kzg_rows_commit_quotient_ext(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
+                                 const kzg_quotient_perm* perm /* NULL: none */,
+                                 const kzg_quotient_lookup* lookup /* NULL: none */, uint32_t ext_log, uint32_t n_pieces,
+                                 uint8_t* out_commitments48 /* n_pieces * 48 */, uint64_t* out_handle);
 /* The UNCHANGED reference miner makes two calls per request with the same row -- worker_commit(i, poly), then
  * worker_open(i, poly, x) (neurons/miner.py:56-61).  These forms take a 128-bit content tag identifying the row's bytes
  * (the host codec computes it while decoding the text); the coefficient vectors of the last four rows stay on the
@@ -556,6 +604,11 @@ int kzg_multi_rows_commit_lookup_sum(kzg_multi* mh, uint32_t i, uint32_t n_input
 int kzg_multi_rows_commit_quotient(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
                                    const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log,
                                    uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle);
+/* kzg_rows_commit_quotient_ext on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_quotient_ext(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                       const kzg_quotient_terms* gate, const kzg_quotient_perm* perm,
+                                       const kzg_quotient_lookup* lookup, uint32_t ext_log, uint32_t n_pieces,
+                                       uint8_t* out_commitments48, uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

@@ -42,6 +42,18 @@ class QuotientPerm(ctypes.Structure):
                 ("shifts_be32", _B), ("beta_be32", _B), ("gamma_be32", _B), ("alpha_be32", _B)]
 
 
+class QuotientTerms(ctypes.Structure):
+    """kzg_quotient_terms"""
+    _fields_ = [("n_terms", _U32), ("coeffs_be32", _B), ("term_lens", ctypes.POINTER(_U32)), ("term_rows", ctypes.POINTER(_U32)),
+                ("term_rots", ctypes.POINTER(ctypes.c_int32))]
+
+
+class QuotientLookup(ctypes.Structure):
+    """kzg_quotient_lookup"""
+    _fields_ = [("n_lookups", _U32), ("width", _U32), ("input_rows", ctypes.POINTER(_U32)), ("table_rows", ctypes.POINTER(_U32)),
+                ("mult_row", _U32), ("sum_row", _U32), ("theta_be32", _B), ("beta_be32", _B), ("alpha_be32", _B)]
+
+
 SYMBOLS = {
     "kzg_create": (_I, [_I, ctypes.POINTER(_P)]),
     "kzg_destroy": (None, [_P]),
@@ -79,6 +91,8 @@ SYMBOLS = {
                                         ctypes.POINTER(_U64)]),
     "kzg_rows_commit_quotient": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientGate), ctypes.POINTER(QuotientPerm),
                                       _U32, _U32, _B, ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_quotient_ext": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms), ctypes.POINTER(QuotientPerm),
+                                          ctypes.POINTER(QuotientLookup), _U32, _U32, _B, ctypes.POINTER(_U64)]),
     "kzg_commit_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B]),
     "kzg_open_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B, _B]),
     "kzg_row_cache_stats": (_I, [_P, ctypes.POINTER(_U64)]),
@@ -142,6 +156,9 @@ SYMBOLS = {
                                               _B, _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_quotient": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientGate),
                                             ctypes.POINTER(QuotientPerm), _U32, _U32, _B, ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_quotient_ext": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms),
+                                                ctypes.POINTER(QuotientPerm), ctypes.POINTER(QuotientLookup), _U32, _U32, _B,
+                                                ctypes.POINTER(_U64)]),
     "kzg_multi_commit_open_rows": (_I, [_P, _U32, ctypes.POINTER(_U32), _B, _U64, _I, _B, _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_upload_fr": (_I, [_P, _I, _B, _U64, _I]),
     "kzg_msm_resident": (_I, [_P, _I, _U64, _U64, _B]),

@@ -379,6 +379,42 @@ class Client:
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments]}
 
     @_guard
+    def worker_commit_quotient_ext(self, handles: Sequence[int], terms, perm=None, lookup=None, ext_log: int = 2,
+                                   n_pieces: int = 3):
+        """Extension: worker_commit_quotient with rotated gate factors and the lookup (logUp) relation.  terms:
+        [coefficient, [factors]] per gate term, a factor being a row index or a [row, rot] pair (the row at t + rot on the
+        domain); perm as in worker_commit_quotient; lookup: None or {"inputs", "table", "mult", "sum", "width", "theta",
+        "beta", "alpha"} (row indices, the tuple width and scalars; theta and beta those of worker_commit_lookup_sum).
+        Returns the new handle and the pieces' commitments.  alpha must be drawn after the commitments of S and z are fixed."""
+        hs = _handles(handles)
+        try:
+            ext_log, n_pieces = int(ext_log), int(n_pieces)
+            tt = [(codec.fr_to_be32(c), [(int(f[0]), int(f[1])) if isinstance(f, (tuple, list)) else (int(f), 0) for f in fs])
+                  for c, fs in terms]
+            if any(isinstance(f, (tuple, list)) and len(f) != 2 for _, fs in terms for f in fs):
+                raise ValueError("a factor is a row index or a [row, rot] pair")
+            pp = None
+            if perm is not None and len(perm["wires"]):   # (no wire: the part is off, as perm->k == 0 in C)
+                pp = {"wires": [int(j) for j in perm["wires"]], "sigmas": [int(j) for j in perm["sigmas"]], "z": int(perm["z"]),
+                      "shifts": [codec.fr_to_be32(x) for x in perm["shifts"]], "beta": codec.fr_to_be32(perm["beta"]),
+                      "gamma": codec.fr_to_be32(perm["gamma"]), "alpha": codec.fr_to_be32(perm["alpha"])}
+            ll = None
+            if lookup is not None:
+                ll = {"inputs": [int(j) for j in lookup["inputs"]], "table": [int(j) for j in lookup["table"]],
+                      "mult": int(lookup["mult"]), "sum": int(lookup["sum"]), "width": int(lookup["width"]),
+                      "theta": codec.fr_to_be32(lookup["theta"]), "beta": codec.fr_to_be32(lookup["beta"]),
+                      "alpha": codec.fr_to_be32(lookup["alpha"])}
+        except (TypeError, ValueError, KeyError, IndexError) as e:
+            raise codec.CodecError(f"worker_commit_quotient_ext: malformed terms, permutation or lookup part: {e!r}") from e
+        scal = [c for c, _ in tt] + (pp["shifts"] + [pp["beta"], pp["gamma"], pp["alpha"]] if pp else []) + \
+            ([ll["theta"], ll["beta"], ll["alpha"]] if ll else [])
+        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in scal):
+            raise codec.CodecError("worker_commit_quotient_ext: coefficients, shifts and challenges must be canonical scalars "
+                                   "(< r)")
+        rs = self.engine.commit_quotient_ext(hs, tt, pp, ll, ext_log, n_pieces)
+        return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments]}
+
+    @_guard
     def worker_release_rows(self, handle: int):
         """Extension: frees a committed row set."""
         self.engine.release_rows(_handles([handle])[0])

@@ -444,6 +444,10 @@ int rows_lookup_sum_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handl
 int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
                        const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces,
                        uint8_t* out_commitments48, uint64_t* out_handle);
+// kzg_rows_commit_quotient_ext; plain: the call came through kzg_rows_commit_quotient (rotations null, no lookup part)
+int rows_quotient_ext_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
+                           uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle, bool plain);
 
 // ---- the collective (comm.hip)
 void comm_teardown(kzg_ctx* ctx);

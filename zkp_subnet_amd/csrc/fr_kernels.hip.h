@@ -112,6 +112,14 @@ struct QuotPlan {
     uint32_t ext_log, n_terms, k, z_row;
     uint8_t term_len[QUOT_MAX_TERMS], term_row[QUOT_MAX_TERMS][QUOT_MAX_FACTORS], wire[QUOT_MAX_WIRES], sigma[QUOT_MAX_WIRES];
     const uint8_t *term_coeffs_be32, *shifts_be32, *beta_be32, *gamma_be32, *alpha_be32;   // (the last four unused when k == 0)
+    // kzg_rows_commit_quotient_ext.  ext == 0: nothing below is read and the plain call's kernel runs.  Gate factor f of term
+    // u is row term_row[u][f] at w^rot X, rot = term_rot[u][f] in [0, T); n_lookups > 0 adds alpha^3 LK1 + alpha^4 LK2 over
+    // the n_lookups * width rows in_row (lookup-major), the width rows tab_row, m = mult_row and S = sum_row, with theta_be32,
+    // lbeta_be32 and alpha_be32 (then read when k == 0 too)
+    uint32_t ext, n_lookups, width, mult_row, sum_row;
+    uint32_t term_rot[QUOT_MAX_TERMS][QUOT_MAX_FACTORS];
+    uint8_t in_row[POLY_MAX_ROWS], tab_row[POLY_MAX_ROWS];
+    const uint8_t *theta_be32, *lbeta_be32;
 };
 // the constants record of one (T, E), in 8-word elements: 1 / Z_H on the coset, 1 / T, g and the power tables of g and 1 / g
 uint64_t quot_consts_elems(int log_t, int ext_log);
@@ -119,8 +127,9 @@ uint64_t quot_consts_elems(int log_t, int ext_log);
 void launch_quot_consts(hipStream_t s, uint32_t* qc, int log_t, int ext_log, const uint32_t* tw_n);
 // ext[i] = g^i f[i] for i < T, 0 for T <= i < N (f: T Montgomery coefficients; null: the coefficients of L_0, all 1 / T)
 void launch_quot_extend(hipStream_t s, const uint32_t* f_or_null, uint32_t* ext, int log_t, int ext_log, const uint32_t* qc);
-// out[i] = (Gate + alpha P1 + alpha^2 P2)(x_i) / Z_H(x_i) over the rows' N coset evaluations ext_rows.r[.] and L_0's l0 (unused
-// when k == 0); out must not alias a row (z is read at i + E).  *bad raised for a scalar >= r
+// out[i] = (Gate + alpha P1 + alpha^2 P2 + alpha^3 LK1 + alpha^4 LK2)(x_i) / Z_H(x_i) over the rows' N coset evaluations
+// ext_rows.r[.] and L_0's l0 (unused when k == 0 and n_lookups == 0); out must not alias a row (z and S are read at i + E, a
+// rotated factor at i + rot E).  *bad raised for a scalar >= r
 void launch_quot_points(hipStream_t s, const RowTab& ext_rows, const uint32_t* l0, uint32_t* out, int log_t, const QuotPlan& qp,
                         const uint32_t* tw_n, const uint32_t* qc, uint32_t* bad);
 // in: the N coefficients of t(g X) (inverse transform, 1 / N applied).  dst[i] = g^-i in[i] for i < n_pieces T (the pieces,

@@ -5,10 +5,12 @@
 //                   two-level power tables g^(+-i) = A[i mod 2^h] B[i >> h]  (h = ceil(log N / 2): two tables of ~sqrt N)
 //   k_quot_extend   ext[i] = g^i f[i] (i < T), 0 above: the input of one forward transform of length N per row; with no row,
 //                   the coefficients of L_0 (all 1 / T)
-//   k_quot_points   one lane per coset point: (Gate + alpha P1 + alpha^2 P2) / Z_H
+//   k_quot_points   one lane per coset point: (Gate + alpha P1 + alpha^2 P2) / Z_H; its second instantiation (kzg_rows_commit_
+//                   quotient_ext) reads a gate factor at a rotation and adds alpha^3 LK1 + alpha^4 LK2, the logUp relation
 //   k_quot_pieces   after the inverse transform: t[i] = g^-i v[i] for i < P T into the new set's buffer, the tail [P T, N)
 //                   ORed into a flag word
-// Z_H(x_i) = g^T w_E^(i mod E) - 1: E inversions per (T, E), none per point.  z(w x_i) = z at index (i + E) mod N.
+// Z_H(x_i) = g^T w_E^(i mod E) - 1: E inversions per (T, E), none per point.  z(w x_i) = z at index (i + E) mod N, and in
+// general f(w^rot x_i) = f's extended vector at index (i + rot E) mod N (w = w_N^E): a rotation costs no transform and no vector.
 #include <cstring>
 
 #include "fr_inv.hip.h"
@@ -152,7 +154,22 @@ struct QuotArg {
     uint32_t n_terms, k, z_row, ext_log;
 };
 static_assert(sizeof(QuotArg) + sizeof(RowTab) + 64 <= 4096, "k_quot_points' arguments must fit in 4 KB");
-enum { QS_SHIFT = QUOT_MAX_TERMS, QS_BETA = QS_SHIFT + QUOT_MAX_WIRES, QS_GAMMA, QS_ALPHA, QS_ALPHA2, QS_COUNT };
+// What kzg_rows_commit_quotient_ext adds (1.8 KB in all): a rotation per gate factor, prepared on the host as (rot mod T) E so
+// that the device does one add and one mask, and the lookup part.  The plain call keeps QuotArg and its own instantiation.
+struct QuotArgX {
+    QuotArg q;
+    FrArg theta, lbeta;
+    uint32_t rot[QUOT_MAX_TERMS][QUOT_MAX_FACTORS];
+    uint8_t in_row[POLY_MAX_ROWS], tab_row[POLY_MAX_ROWS];
+    uint32_t n_lookups, width, mult_row, sum_row;
+};
+static_assert(sizeof(QuotArgX) + sizeof(RowTab) + 64 <= 4096, "k_quot_points' arguments must fit in 4 KB");
+template <bool EXT> struct QuotArgOf { typedef QuotArg type; };
+template <> struct QuotArgOf<true> { typedef QuotArgX type; };
+KZG_DEV const QuotArg& quot_base(const QuotArg& a) { return a; }
+KZG_DEV const QuotArg& quot_base(const QuotArgX& a) { return a.q; }
+enum { QS_SHIFT = QUOT_MAX_TERMS, QS_BETA = QS_SHIFT + QUOT_MAX_WIRES, QS_GAMMA, QS_ALPHA, QS_ALPHA2, QS_COUNT,
+       QX_THETA = QS_COUNT, QX_LBETA, QX_ALPHA3, QX_ALPHA4, QX_COUNT };   // (the QX_ slots: the second instantiation only)
 KZG_DEV void quot_arg(fr9_t& v, const FrArg& a, uint32_t* __restrict__ bad, bool check) {
     uint32_t w[8];
 #pragma unroll
@@ -165,10 +182,37 @@ KZG_DEV void lds_get(fr9_t& v, const uint32_t (*cst)[9], uint32_t j) {
 #pragma unroll
     for (int i = 0; i < 9; i++) v.l[i] = cst[j][i];
 }
+// fr9_sub4 for a subtrahend below 6r (normalised): the value grows by 8r
+KZG_DEV void fr9_sub8(fr9_t& r, const fr9_t& a, const fr9_t& b) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + (fr9_m8(i) - b.l[i]);
+}
+// beta + sum_c theta^c f_c(x_i) over the w rows named by `rows`, Horner from the last column down: w - 1 products.  Every
+// step is (a product, < 2r) + (a canonical row value, < r) < 3r with limbs < 2^30, a legal first operand of the next; the sum
+// with beta stays below 4r (limbs < 2^31) and is normalised: a legal SECOND operand for a first one below 17r.
+KZG_DEV void quot_lk_den(fr9_t& d, const RowTab& rt, const uint8_t* rows, uint32_t w, uint64_t i, const fr9_t& theta,
+                         const fr9_t& beta) {
+    fr9_t c;
+    fr9_load(d, rt.r[rows[w - 1]] + 8 * i);
+    for (uint32_t k = w - 1; k-- > 0;) {
+        fr9_mul(d, d, theta);
+        fr9_load(c, rt.r[rows[k]] + 8 * i);
+        fr9_add(d, d, c);
+    }
+    fr9_add(d, d, beta);
+    fr9_norm(d, d);
+}
+// EXT = false is kzg_rows_commit_quotient's kernel, instruction for instruction what it was before the second instantiation
+// existed; EXT = true adds the rotations and the lookup part.  The lazy-sum bound with the lookup: at most 16 terms + alpha P1 +
+// alpha^2 P2 + alpha^3 LK1 + alpha^4 LK2, each a product's output below 2r and the sum renormalised after each, stay below 40r --
+// still under the 64r the closing product's first operand allows (its second one, 1 / Z_H, is canonical).
+template <bool EXT>
 __global__ void __launch_bounds__(256) k_quot_points(const RowTab rt, const uint32_t* __restrict__ l0, uint32_t* __restrict__ out,
-                                                      int log_n, const QuotArg qa, const uint32_t* __restrict__ tw,
-                                                      const uint32_t* __restrict__ qc, uint32_t* __restrict__ bad) {
-    __shared__ uint32_t cst[QS_COUNT][9];
+                                                      int log_n, const typename QuotArgOf<EXT>::type qx,
+                                                      const uint32_t* __restrict__ tw, const uint32_t* __restrict__ qc,
+                                                      uint32_t* __restrict__ bad) {
+    const QuotArg& qa = quot_base(qx);
+    __shared__ uint32_t cst[EXT ? QX_COUNT : QS_COUNT][9];
     const uint32_t v = threadIdx.x;
     const bool chk = blockIdx.x == 0;
     if (v < QS_COUNT) {
@@ -201,6 +245,25 @@ __global__ void __launch_bounds__(256) k_quot_points(const RowTab rt, const uint
 #pragma unroll
         for (int i = 0; i < 9; i++) cst[v][i] = c.l[i];
     }
+    if constexpr (EXT) {
+        if (v >= QS_COUNT && v < QX_COUNT) {   // theta, the lookup's beta, alpha^3, alpha^4: one lane each
+            fr9_t c;
+            if (v == QX_THETA) {
+                quot_arg(c, qx.theta, bad, chk);
+            } else if (v == QX_LBETA) {
+                quot_arg(c, qx.lbeta, bad, chk);
+            } else {
+                fr9_t a2;
+                quot_arg(c, qa.alpha, bad, false);
+                fr9_mul(a2, c, c);
+                fr9_canon(a2, a2);
+                fr9_mul(c, v == QX_ALPHA3 ? c : a2, a2);
+                fr9_canon(c, c);
+            }
+#pragma unroll
+            for (int i = 0; i < 9; i++) cst[v][i] = c.l[i];
+        }
+    }
     __syncthreads();
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + v;
     if (i >> log_n) return;
@@ -211,7 +274,8 @@ __global__ void __launch_bounds__(256) k_quot_points(const RowTab rt, const uint
         lds_get(p, cst, u);
         const uint32_t len = qa.len[u];
         for (uint32_t f = 0; f < len; f++) {
-            fr9_load(c, rt.r[qa.row[u][f]] + 8 * i);
+            if constexpr (EXT) fr9_load(c, rt.r[qa.row[u][f]] + 8 * ((i + qx.rot[u][f]) & (n - 1)));
+            else fr9_load(c, rt.r[qa.row[u][f]] + 8 * i);
             fr9_mul(p, p, c);
         }
         fr9_add(acc, acc, p);
@@ -262,6 +326,45 @@ __global__ void __launch_bounds__(256) k_quot_points(const RowTab rt, const uint
         fr9_add(acc, acc, t);
         fr9_norm(acc, acc);
     }
+    if constexpr (EXT) {
+        if (qx.n_lookups) {
+            // the running fraction of k_lk_step, point by point and without the inversion: P / Q = sum_l 1 / D_l - m / D_0
+            //   P = -m, Q = D_0;  (P, Q) <- (P D_l + Q, Q D_l) for every l;  LK1 = (S(w x) - S(x)) Q - P
+            // P is 4r - m (< 5r) at first and (a product) + Q < 2r + 4r afterwards: a first operand below 6r against D_l
+            // below 4r.  Q is D_0 and then a product's output: normalised either way.
+            fr9_t theta, beta, P, Q, d, s, t;
+            lds_get(theta, cst, QX_THETA);
+            lds_get(beta, cst, QX_LBETA);
+            quot_lk_den(Q, rt, qx.tab_row, qx.width, i, theta, beta);
+            fr9_load(c, rt.r[qx.mult_row] + 8 * i);
+            fr9_zero(P);
+            fr9_sub4(P, P, c);
+            for (uint32_t l = 0; l < qx.n_lookups; l++) {
+                quot_lk_den(d, rt, qx.in_row + l * qx.width, qx.width, i, theta, beta);
+                fr9_mul(P, P, d);
+                fr9_add(P, P, Q);
+                fr9_mul(Q, Q, d);
+            }
+            const uint32_t* sr = rt.r[qx.sum_row];
+            fr9_load(s, sr + 8 * i);
+            fr9_load(t, sr + 8 * ((i + ((uint64_t)1 << qa.ext_log)) & (n - 1)));
+            fr9_sub4(t, t, s);                // S(w x) - S(x), < 5r
+            fr9_mul(t, t, Q);
+            fr9_norm(P, P);                   // < 6r, normalised: what fr9_sub8 takes
+            fr9_sub8(t, t, P);                // LK1, < 10r
+            lds_get(c, cst, QX_ALPHA3);
+            fr9_mul(t, t, c);
+            fr9_add(acc, acc, t);
+            fr9_norm(acc, acc);
+            // LK2 = S L_0
+            fr9_load(c, l0 + 8 * i);
+            fr9_mul(t, s, c);
+            lds_get(c, cst, QX_ALPHA4);
+            fr9_mul(t, t, c);
+            fr9_add(acc, acc, t);
+            fr9_norm(acc, acc);
+        }
+    }
     fr9_load(c, qc + 8 * (i & ((1u << qa.ext_log) - 1)));
     fr9_mul(acc, acc, c);
     fr9_canon(acc, acc);
@@ -269,8 +372,9 @@ __global__ void __launch_bounds__(256) k_quot_points(const RowTab rt, const uint
 }
 void launch_quot_points(hipStream_t s, const RowTab& ext_rows, const uint32_t* l0, uint32_t* out, int log_t, const QuotPlan& qp,
                         const uint32_t* tw_n, const uint32_t* qc, uint32_t* bad) {
-    QuotArg qa;
-    memset(&qa, 0, sizeof(qa));
+    QuotArgX qx;
+    QuotArg& qa = qx.q;
+    memset(&qx, 0, sizeof(qx));
     qa.n_terms = qp.n_terms;
     qa.k = qp.k;
     qa.z_row = qp.z_row;
@@ -288,10 +392,27 @@ void launch_quot_points(hipStream_t s, const RowTab& ext_rows, const uint32_t* l
     if (qp.k) {
         memcpy(qa.beta.w, qp.beta_be32, 32);
         memcpy(qa.gamma.w, qp.gamma_be32, 32);
-        memcpy(qa.alpha.w, qp.alpha_be32, 32);
     }
+    if (qp.k || qp.n_lookups) memcpy(qa.alpha.w, qp.alpha_be32, 32);
     const int log_n = log_t + (int)qp.ext_log;
-    k_quot_points<<<nblk((uint64_t)1 << log_n, 256), 256, 0, s>>>(ext_rows, l0, out, log_n, qa, tw_n, qc, bad);
+    const dim3 g(nblk((uint64_t)1 << log_n, 256));
+    if (!qp.ext) {
+        k_quot_points<false><<<g, 256, 0, s>>>(ext_rows, l0, out, log_n, qa, tw_n, qc, bad);
+        return;
+    }
+    for (uint32_t u = 0; u < qp.n_terms; u++)
+        for (uint32_t f = 0; f < qp.term_len[u]; f++) qx.rot[u][f] = qp.term_rot[u][f] << qp.ext_log;
+    if (qp.n_lookups) {
+        memcpy(qx.theta.w, qp.theta_be32, 32);
+        memcpy(qx.lbeta.w, qp.lbeta_be32, 32);
+        memcpy(qx.in_row, qp.in_row, sizeof(qx.in_row));
+        memcpy(qx.tab_row, qp.tab_row, sizeof(qx.tab_row));
+        qx.n_lookups = qp.n_lookups;
+        qx.width = qp.width;
+        qx.mult_row = qp.mult_row;
+        qx.sum_row = qp.sum_row;
+    }
+    k_quot_points<true><<<g, 256, 0, s>>>(ext_rows, l0, out, log_n, qx, tw_n, qc, bad);
 }
 
 // ------------------------------------------------------------------------------------------------ back to the pieces

@@ -42,6 +42,9 @@ int rows_lookup_sum_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handl
 int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
                        const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces,
                        uint8_t* out_commitments48, uint64_t* out_handle);
+int rows_quotient_ext_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
+                           uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle, bool plain);
 }  // namespace kzg_impl
 
 namespace {
@@ -468,6 +471,16 @@ int kzg_multi_rows_commit_quotient(kzg_multi* mh, uint32_t i, uint32_t n_handles
     if (int rc = route(mh, i, &c, &s)) return rc;
     return relay(c, kzg_impl::rows_quotient_impl(c, s, n_handles, handles, gate, perm, ext_log, n_pieces, out_commitments48,
                                                  out_handle));
+}
+int kzg_multi_rows_commit_quotient_ext(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                       const kzg_quotient_terms* gate, const kzg_quotient_perm* perm,
+                                       const kzg_quotient_lookup* lookup, uint32_t ext_log, uint32_t n_pieces,
+                                       uint8_t* out_commitments48, uint64_t* out_handle) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_quotient_ext_impl(c, s, n_handles, handles, gate, perm, lookup, ext_log, n_pieces,
+                                                     out_commitments48, out_handle, false));
 }
 int kzg_multi_rows_release(kzg_multi* mh, uint32_t i, uint64_t handle) {
     kzg_ctx* c;

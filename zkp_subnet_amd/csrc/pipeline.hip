@@ -843,7 +843,8 @@ static int ensure_quot_consts(kzg_ctx* ctx, Lane& L, int log_t, int ext_log, con
 // The PLONK quotient (kzg_rows_commit_quotient): a set built FROM sets.  Every DISTINCT row the constraints name (by device
 // pointer: a wire is named by the gate and by the permutation) is extended to the coset g H_N, N = E T -- one scaling launch
 // into the lane's staging vector, one forward transform of length N into its own vector of the lane's quotient workspace --
-// and so is L_0 when there is a permutation part; one pointwise launch writes num / Z_H into the staging vector; the inverse
+// and so is L_0 when there is a permutation or a lookup part (a rotated factor reads the SAME vector at another index: no
+// vector and no transform of its own); one pointwise launch writes num / Z_H into the staging vector; the inverse
 // transform and the g^-i launch leave the P pieces in the new set's buffer `dst` and OR the coefficients above P T into the
 // record's first evaluation slot; ONE MSM pass of P scalar sets commits.  Workspace: (distinct rows + 2) vectors of N.
 // The flag travels in the record's one copy behind the MSM, so an instance that fails the shape check still pays the MSM
@@ -866,6 +867,10 @@ int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, u
         for (uint32_t f = 0; f < qp.term_len[u]; f++) used[qp.term_row[u][f]] = true;
     for (uint32_t j = 0; j < qp.k; j++) used[qp.wire[j]] = used[qp.sigma[j]] = true;
     if (qp.k) used[qp.z_row] = true;
+    for (uint32_t j = 0; j < qp.n_lookups * qp.width; j++) used[qp.in_row[j]] = true;
+    for (uint32_t j = 0; qp.n_lookups && j < qp.width; j++) used[qp.tab_row[j]] = true;
+    if (qp.n_lookups) used[qp.mult_row] = used[qp.sum_row] = true;
+    const bool need_l0 = qp.k || qp.n_lookups;   // P2 and LK2
     int slot[POLY_MAX_ROWS];
     uint32_t nd = 0;
     for (uint32_t j = 0; j < n_rows; j++) {
@@ -875,7 +880,7 @@ int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, u
             if (used[e] && rt.r[e] == rt.r[j]) slot[j] = slot[e];
         if (slot[j] < 0) slot[j] = (int)nd++;
     }
-    HIPCHK(ctx, A.qext.ensure((size_t)std::max(nd + (qp.k ? 1u : 0u), 1u) * N * 32));   // (constant terms alone: no row)
+    HIPCHK(ctx, A.qext.ensure((size_t)std::max(nd + (need_l0 ? 1u : 0u), 1u) * N * 32));   // (constant terms alone: no row)
     HIPCHK(ctx, A.qstage.ensure(N * 32));
     HIPCHK(ctx, A.ntt_mid.ensure(N * 48));
     uint32_t *ext = A.qext.as<uint32_t>(), *stage = A.qstage.as<uint32_t>(), *mid = A.ntt_mid.as<uint32_t>();
@@ -890,7 +895,7 @@ int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, u
             if ((uint32_t)slot[j] < done) continue;   // a repeated row: transformed already
             done++;
         } else {
-            if (!qp.k) break;
+            if (!need_l0) break;
             vec = ext + (uint64_t)nd * nw;
         }
         {

@@ -943,13 +943,16 @@ int rows_lookup_sum_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handl
     return KZG_OK;
 }
 
-// kzg_rows_commit_quotient: the lookups of an open (one handle list), the reservation of a commit
-int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                       const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces,
-                       uint8_t* out_commitments48, uint64_t* out_handle) {
+// kzg_rows_commit_quotient_ext (and, with no rotation and no lookup part, kzg_rows_commit_quotient: `plain`, which only words
+// one message): the lookups of an open (one handle list), the reservation of a commit
+int rows_quotient_ext_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
+                           uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle, bool plain) {
     if (!ctx || !handles || !gate || !out_commitments48 || !out_handle) return KZG_E_ARG;
     const uint32_t k = perm ? perm->k : 0;
     if (gate->n_terms && (!gate->coeffs_be32 || !gate->term_lens || !gate->term_rows)) return KZG_E_ARG;
+    if (lookup && (!lookup->input_rows || !lookup->table_rows || !lookup->theta_be32 || !lookup->beta_be32 || !lookup->alpha_be32))
+        return KZG_E_ARG;
     if (k && (!perm->wire_rows || !perm->sigma_rows || !perm->shifts_be32 || !perm->beta_be32 || !perm->gamma_be32 ||
               !perm->alpha_be32))
         return KZG_E_ARG;
@@ -960,13 +963,30 @@ int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, cons
     if (n_pieces == 0 || n_pieces > E) return fail(ctx, KZG_E_ARG, "quotient: n_pieces must be in [1, 2^ext_log]");
     if (gate->n_terms > KZG_MAX_GATE_TERMS) return fail(ctx, KZG_E_ARG, "quotient: more than KZG_MAX_GATE_TERMS gate terms");
     if (k > E) return fail(ctx, KZG_E_ARG, "quotient: the permutation part has k + 1 factors: k must not exceed 2^ext_log");
-    if (gate->n_terms == 0 && k == 0) return fail(ctx, KZG_E_ARG, "quotient: no gate term and no permutation part");
+    if (gate->n_terms == 0 && k == 0 && !lookup)
+        return fail(ctx, KZG_E_ARG, plain ? "quotient: no gate term and no permutation part"
+                                          : "quotient: no gate term, no permutation part and no lookup part");
+    if (lookup) {
+        const uint32_t L = lookup->n_lookups, w = lookup->width;
+        if (L == 0 || w == 0 || (uint64_t)L * w > KZG_MAX_BATCH_OPEN)
+            return fail(ctx, KZG_E_ARG, "quotient: n_lookups and width must be at least 1 and n_lookups * width at most "
+                                        "KZG_MAX_BATCH_OPEN");
+        if (L > E - 1)
+            return fail(ctx, KZG_E_ARG, "quotient: the lookup part has n_lookups + 2 factors: n_lookups must not exceed "
+                                        "2^ext_log - 1");
+        if (!fr_be32_canonical(lookup->theta_be32) || !fr_be32_canonical(lookup->beta_be32) ||
+            !fr_be32_canonical(lookup->alpha_be32))
+            return fail(ctx, KZG_E_ARG, "quotient: the lookup part's theta, beta and alpha must be canonical scalars (< r)");
+        if (k && memcmp(lookup->alpha_be32, perm->alpha_be32, 32) != 0)
+            return fail(ctx, KZG_E_ARG, "quotient: the permutation part and the lookup part must name one alpha");
+    }
     QuotPlan qp;
     memset(&qp, 0, sizeof(qp));
     qp.ext_log = ext_log;
     qp.n_terms = gate->n_terms;
     qp.k = k;
     qp.term_coeffs_be32 = gate->coeffs_be32;
+    int32_t rots[QUOT_MAX_TERMS][QUOT_MAX_FACTORS] = {};   // as given: reduced mod T once T is known
     uint32_t max_row = 0;   // the largest row index named, checked against the rows once they are known
     bool any_row = false;
     auto name_row = [&](uint32_t row) {
@@ -980,7 +1000,10 @@ int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, cons
         if (gate->term_lens[u] > E + 1)
             return fail(ctx, KZG_E_ARG, "quotient: a gate term has more than 2^ext_log + 1 factors");
         qp.term_len[u] = (uint8_t)gate->term_lens[u];
-        for (uint32_t f = 0; f < gate->term_lens[u]; f++) qp.term_row[u][f] = name_row(gate->term_rows[at++]);
+        for (uint32_t f = 0; f < gate->term_lens[u]; f++, at++) {
+            qp.term_row[u][f] = name_row(gate->term_rows[at]);
+            if (gate->term_rots && gate->term_rots[at]) rots[u][f] = gate->term_rots[at], qp.ext = 1;
+        }
     }
     if (k) {
         if (!fr_be32_canonical(perm->beta_be32) || !fr_be32_canonical(perm->gamma_be32) || !fr_be32_canonical(perm->alpha_be32))
@@ -997,6 +1020,18 @@ int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, cons
         qp.gamma_be32 = perm->gamma_be32;
         qp.alpha_be32 = perm->alpha_be32;
     }
+    if (lookup) {
+        qp.ext = 1;
+        qp.n_lookups = lookup->n_lookups;
+        qp.width = lookup->width;
+        for (uint32_t j = 0; j < qp.n_lookups * qp.width; j++) qp.in_row[j] = name_row(lookup->input_rows[j]);
+        for (uint32_t j = 0; j < qp.width; j++) qp.tab_row[j] = name_row(lookup->table_rows[j]);
+        qp.mult_row = name_row(lookup->mult_row);
+        qp.sum_row = name_row(lookup->sum_row);
+        qp.theta_be32 = lookup->theta_be32;
+        qp.lbeta_be32 = lookup->beta_be32;
+        qp.alpha_be32 = lookup->alpha_be32;
+    }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     RowsPending pend{ctx};
     RowsRefs refs{ctx};
@@ -1011,6 +1046,9 @@ int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, cons
     int rc = check_worker(ctx, i, T);
     if (rc) return rc;
     if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "quotient: the row length must be a power of two");
+    for (uint32_t u = 0; u < qp.n_terms; u++)   // any int32 rotation, reduced into [0, T)
+        for (uint32_t f = 0; f < qp.term_len[u]; f++)
+            qp.term_rot[u][f] = (uint32_t)(((int64_t)rots[u][f] % (int64_t)T + (int64_t)T) % (int64_t)T);
     if (int rc2 = rows_reserve(ctx, "quotient", pend, (size_t)n_pieces * T * 32)) return rc2;
     prof_begin(ctx, L);
     rc = clear_flags(ctx, L);
@@ -1025,6 +1063,16 @@ int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, cons
     memcpy(out_commitments48, c48, 48 * (size_t)n_pieces);
     *out_handle = rows_insert(ctx, pend, i, n_pieces, T);
     return KZG_OK;
+}
+
+// kzg_rows_commit_quotient: the same with every rotation 0 and no lookup part
+int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                       const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces,
+                       uint8_t* out_commitments48, uint64_t* out_handle) {
+    if (!gate) return KZG_E_ARG;
+    const kzg_quotient_terms terms = {gate->n_terms, gate->coeffs_be32, gate->term_lens, gate->term_rows, nullptr};
+    return rows_quotient_ext_impl(ctx, expect_i, n_handles, handles, &terms, perm, nullptr, ext_log, n_pieces, out_commitments48,
+                                  out_handle, true);
 }
 
 int rows_release_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle) {
@@ -1109,6 +1157,12 @@ int kzg_rows_commit_quotient(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* h
                              const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,
                              uint64_t* out_handle) {
     return rows_quotient_impl(ctx, UINT32_MAX, n_handles, handles, gate, perm, ext_log, n_pieces, out_commitments48, out_handle);
+}
+int kzg_rows_commit_quotient_ext(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
+                                 const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup, uint32_t ext_log,
+                                 uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle) {
+    return rows_quotient_ext_impl(ctx, UINT32_MAX, n_handles, handles, gate, perm, lookup, ext_log, n_pieces, out_commitments48,
+                                  out_handle, false);
 }
 int kzg_rows_release(kzg_ctx* ctx, uint64_t handle) { return rows_release_impl(ctx, UINT32_MAX, handle); }
 int kzg_rows_stats(kzg_ctx* ctx, uint64_t out_live_sets_bytes[2]) {

@@ -460,6 +460,89 @@ class HipEngine:
         return RowSet(self, h.value, getattr(src, "i", None), n_pieces, getattr(src, "T", None),
                       [c.raw[48 * p:48 * p + 48] for p in range(n_pieces)])
 
+    # ---- the same with rotated gate factors and the logUp relation (what makes commit_lookup_sum's S an argument)
+    def commit_quotient_ext(self, sets: Sequence[object], terms: Sequence[Tuple[bytes, Sequence[object]]],
+                            perm: Optional[dict] = None, lookup: Optional[dict] = None, ext_log: int = 2,
+                            n_pieces: int = 3) -> "RowSet":
+        """The pieces of t = (Gate + alpha P1 + alpha^2 P2 + alpha^3 LK1 + alpha^4 LK2) / (X^T - 1) of
+        kzg_rows_commit_quotient_ext.  sets, perm, ext_log and n_pieces as in commit_quotient.  terms: (32-byte coefficient,
+        factors) per gate term, a factor being a row index or a (row, rot) pair: the row at w^rot X, i.e. at t + rot on the
+        domain (any int32 rot, reduced mod T).  lookup: None, or a dict with "inputs" (n_lookups * width row indices,
+        lookup-major), "table" (width row indices), "mult", "sum" (row indices of m and S), "width", and "theta", "beta",
+        "alpha" (32 bytes each; theta and beta those S was built with, alpha the one of perm).  n_lookups <= 2^ext_log - 1.
+        alpha must be drawn after the commitments of S and z are fixed."""
+        n, hs = self._handle_array(sets, "commit_quotient_ext")
+        bad = lambda why: KzgError(_native.KZG_E_ARG, "commit_quotient_ext: " + why)   # noqa: E731
+        if ext_log not in (1, 2, 3) or not 1 <= n_pieces <= 1 << ext_log:
+            raise bad("ext_log must be 1, 2 or 3 and n_pieces in [1, 2^ext_log]")
+        E = 1 << ext_log
+        try:
+            tt = []
+            for c, factors in terms:
+                fs = [(int(f[0]), int(f[1])) if isinstance(f, (tuple, list)) else (int(f), 0) for f in factors]
+                if any(isinstance(f, (tuple, list)) and len(f) != 2 for f in factors):
+                    raise ValueError("a factor is a row index or a (row, rot) pair")
+                tt.append((bytes(c), fs))
+        except (TypeError, ValueError) as e:
+            raise bad(f"malformed terms: {e!r}") from e
+        if len(tt) > _native.KZG_MAX_GATE_TERMS or any(len(c) != 32 or len(fs) > E + 1 for c, fs in tt):
+            raise bad(f"at most {_native.KZG_MAX_GATE_TERMS} terms of a 32-byte coefficient and at most 2^ext_log + 1 factors")
+        flat = [f for _, fs in tt for f in fs]
+        if any(not 0 <= j < 1 << 32 or not -(1 << 31) <= rot < 1 << 31 for j, rot in flat):
+            raise bad("row indices must be non-negative integers below 2^32 and rotations must fit an int32")
+        pm = None
+        if perm is not None:
+            try:
+                wires, sigmas = [int(j) for j in perm["wires"]], [int(j) for j in perm["sigmas"]]
+                k = len(wires)
+                if k:
+                    shifts, z = list(perm["shifts"]), int(perm["z"])
+                    scal = shifts + [perm["beta"], perm["gamma"], perm["alpha"]]
+            except (KeyError, TypeError, ValueError) as e:
+                raise bad(f"malformed permutation part: {e!r}") from e
+            if k:
+                if k > E or len(sigmas) != k or len(shifts) != k or any(len(x) != 32 for x in scal):
+                    raise bad("the permutation part takes at most 2^ext_log wires, as many sigmas and shifts, and 32-byte scalars")
+                if any(not 0 <= j < 1 << 32 for j in wires + sigmas + [z]):
+                    raise bad("row indices must be non-negative integers below 2^32")
+                pm = _native.QuotientPerm(k, z, (ctypes.c_uint32 * k)(*wires), (ctypes.c_uint32 * k)(*sigmas),
+                                          b"".join(shifts), perm["beta"], perm["gamma"], perm["alpha"])
+            elif sigmas:
+                raise bad("the permutation part names sigma rows but no wire")
+        lk = None
+        if lookup is not None:
+            try:
+                ins, tab = [int(j) for j in lookup["inputs"]], [int(j) for j in lookup["table"]]
+                w, mrow, srow = int(lookup["width"]), int(lookup["mult"]), int(lookup["sum"])
+                lscal = [bytes(lookup[name]) for name in ("theta", "beta", "alpha")]
+            except (KeyError, TypeError, ValueError) as e:
+                raise bad(f"malformed lookup part: {e!r}") from e
+            if w < 1 or len(tab) != w or not ins or len(ins) % w or len(ins) > _native.KZG_MAX_BATCH_OPEN:
+                raise bad(f"the lookup part takes width >= 1 table rows and n_lookups * width <= {_native.KZG_MAX_BATCH_OPEN} "
+                          "input rows, n_lookups >= 1")
+            if len(ins) // w > E - 1:
+                raise bad("the lookup part has n_lookups + 2 factors: n_lookups must not exceed 2^ext_log - 1")
+            if any(len(x) != 32 for x in lscal) or any(not 0 <= j < 1 << 32 for j in ins + tab + [mrow, srow]):
+                raise bad("the lookup part takes 32-byte scalars and non-negative row indices below 2^32")
+            if pm is not None and lscal[2] != bytes(perm["alpha"]):
+                raise bad("the permutation part and the lookup part must name one alpha")
+            lk = _native.QuotientLookup(len(ins) // w, w, (ctypes.c_uint32 * len(ins))(*ins), (ctypes.c_uint32 * w)(*tab), mrow,
+                                        srow, *lscal)
+        if not tt and pm is None and lk is None:
+            raise bad("no gate term, no permutation part and no lookup part")
+        lens = (ctypes.c_uint32 * max(len(tt), 1))(*[len(fs) for _, fs in tt])
+        rows_arr = (ctypes.c_uint32 * max(len(flat), 1))(*[j for j, _ in flat])
+        rots_arr = (ctypes.c_int32 * max(len(flat), 1))(*[rot for _, rot in flat])
+        gate = _native.QuotientTerms(len(tt), b"".join(c for c, _ in tt), lens, rows_arr, rots_arr)
+        c, h = ctypes.create_string_buffer(48 * n_pieces), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_quotient_ext(self._h, n, hs, ctypes.byref(gate),
+                                                         ctypes.byref(pm) if pm is not None else None,
+                                                         ctypes.byref(lk) if lk is not None else None, ext_log, n_pieces, c,
+                                                         ctypes.byref(h)))
+        src = next((x for x in sets if hasattr(x, "T")), None)
+        return RowSet(self, h.value, getattr(src, "i", None), n_pieces, getattr(src, "T", None),
+                      [c.raw[48 * p:48 * p + 48] for p in range(n_pieces)])
+
     def _handle_array(self, sets, what):
         handles = [int(getattr(x, "handle", x)) for x in sets]
         n = len(handles)

@@ -172,6 +172,15 @@ class MultiDeviceClient:
             self._row_owner[int(r.json()["handle"])] = i
         return r
 
+    def worker_commit_quotient_ext(self, handles: Sequence[int], terms, perm=None, lookup=None, ext_log=2, n_pieces=3):
+        i = self._owner(handles)
+        if i is None:
+            return Response(400, {"error": "worker_commit_quotient_ext: the handles must name live sets of one worker"})
+        r = self._for(i).worker_commit_quotient_ext(handles, terms, perm, lookup, ext_log, n_pieces)
+        if r.status_code == 200:
+            self._row_owner[int(r.json()["handle"])] = i
+        return r
+
     def worker_release_rows(self, handle: int):
         i = self._owner([handle])
         if i is None:
