@@ -268,12 +268,43 @@ int kzg_rows_commit_grand_product(kzg_ctx* ctx, uint32_t n_wire_handles, const u
  * forces closing = 0) belongs in the caller's quotient.
  * That quotient term (it needs S at X and w_T X, i.e. gate factors with a rotation) is the lookup part of
  * kzg_rows_commit_quotient_ext.
- * OUT OF SCOPE: computing m on the device (a join of 32-byte keys); per-row selectors (a caller points inactive rows at a default
- * table entry); plookup; blinding. */
+ * m itself is built and committed on the device by kzg_rows_commit_multiplicities.
+ * OUT OF SCOPE: per-row selectors (a caller points inactive rows at a default table entry); plookup; blinding. */
 int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
                                uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
                                uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32], const uint8_t beta_be32[32],
                                uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle);
+/* A fifth set built FROM sets: the multiplicity row m of the lookup argument above, computed and committed on the device from
+ * rows that are already resident -- a hash join of the looked-up tuples against the table.  Handle lists, L = n_lookups,
+ * w = width, the lookup-major input order, w_T and the natural order are those of kzg_rows_commit_lookup_sum.  Tuples are
+ * compared as w-tuples of elements of Fr, in ALL w columns (no challenge exists yet: m is committed BEFORE theta and beta are
+ * drawn, so the join is on the full tuples, never on a theta-compression):
+ *   in(l, t) = (f_{l,0}(w_T^t), .., f_{l,w-1}(w_T^t)),    tab(t) = (t_0(w_T^t), .., t_{w-1}(w_T^t))
+ *   first(u) = the smallest t with tab(t) = u
+ *   m(w_T^t) = #{ (l, t') : first(in(l, t')) = t },       missing = #{ (l, t') : in(l, t') is no row of the table }
+ * A tuple that occurs several times in the table gets ALL its hits on its first copy; the later copies get 0.  That makes m a
+ * function of its inputs (the same bytes whatever the device's schedule).  (a, b) in the table does not make (b, a) a hit.
+ * The call creates a new ONE-ROW set of the same worker and length holding m's coefficients, exactly as if m's T evaluations
+ * had gone through kzg_rows_commit(i, 1, m, T, 1, ..): out_commitment48 equals that call's byte for byte and *out_handle opens,
+ * evaluates, combines, releases, goes stale and counts against KZG_MAX_ROW_SETS (KZG_E_BUSY; KZG_E_NOMEM on a failed
+ * allocation, the lane's workspace of 2 w T-element vectors included) like any other; it can be passed straight to
+ * kzg_rows_commit_lookup_sum as mult_handle and named as mult_row in kzg_rows_commit_quotient_ext.  *out_missing is 0 exactly
+ * when every looked-up tuple is in the table.  The library does not judge it, as it does not judge a closing value: the set is
+ * created either way and m then counts only the cells that were found (the lookup sum over it does not close).  Nothing
+ * row-sized crosses the host link in either direction.
+ * Errors (all KZG_E_ARG unless said): handle lists as in kzg_rows_open (1 .. KZG_MAX_BATCH_OPEN handles each, a handle may
+ * repeat, also across the lists; unknown / released / stale); w = 0, L = 0 or L * w > KZG_MAX_BATCH_OPEN; an input
+ * concatenation that does not hold exactly L * w rows or a table concatenation that does not hold exactly w; sets of more
+ * than one worker or row length; a row length that is no power of two or exceeds 2^27.  Every walk of the join is bounded by
+ * the slot table's capacity; a walk that reaches the bound (it cannot, with 2 T slots for at most T tuples) is answered with
+ * KZG_E_HIP and no set.  The source sets are only read; a release or an SRS load racing the call follows the rules of
+ * kzg_rows_open.  Thread-safe like every call; after any error the context keeps serving.
+ * SOUNDNESS: nothing here is a proof.  m is prover data like any witness row; the argument is the relation of
+ * kzg_rows_commit_quotient_ext over S, with theta and beta drawn AFTER this call's commitment is fixed.  No blinding.
+ * OUT OF SCOPE: per-row selectors, plookup, blinding (as above). */
+int kzg_rows_commit_multiplicities(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                                   uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
+                                   uint8_t out_commitment48[48], uint64_t* out_missing, uint64_t* out_handle);
 /* A third set built FROM sets: the PLONK quotient (round 3), computed and committed on the device from rows that are already
  * resident.  The concatenated rows of the handles (as in kzg_rows_open) are f_0 .. f_{n-1}, n <= KZG_MAX_BATCH_OPEN, all of
  * one worker and one power-of-two length T; everything below names a row by its index into that list.  A full standard PLONK
@@ -349,8 +380,8 @@ int kzg_rows_commit_quotient(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* h
  * no term, no permutation part and no lookup part; a null array inside a part that is present (gate itself must not be NULL;
  * n_terms = 0 makes it empty).
  * SOUNDNESS: alpha must be drawn AFTER the commitments of S and z are fixed; theta and beta AFTER the commitments of the
- * inputs, the table and m (as for kzg_rows_commit_lookup_sum).  Still out of scope: computing m on the device, per-row
- * selectors, plookup, blinding. */
+ * inputs, the table and m (as for kzg_rows_commit_lookup_sum; kzg_rows_commit_multiplicities builds and commits m on the
+ * device).  Still out of scope: per-row selectors, plookup, blinding. */
 typedef struct kzg_quotient_terms {
     uint32_t n_terms;
     const uint8_t* coeffs_be32;  /* n_terms * 32 */
@@ -600,6 +631,11 @@ int kzg_multi_rows_commit_lookup_sum(kzg_multi* mh, uint32_t i, uint32_t n_input
                                      uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32],
                                      const uint8_t beta_be32[32], uint8_t out_commitment48[48], uint8_t out_closing32[32],
                                      uint64_t* out_handle);
+/* kzg_rows_commit_multiplicities on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_multiplicities(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                         uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups,
+                                         uint32_t width, uint8_t out_commitment48[48], uint64_t* out_missing,
+                                         uint64_t* out_handle);
 /* kzg_rows_commit_quotient on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
 int kzg_multi_rows_commit_quotient(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
                                    const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log,

@@ -89,6 +89,8 @@ SYMBOLS = {
                                            ctypes.POINTER(_U64)]),
     "kzg_rows_commit_lookup_sum": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B, _B, _B, _B,
                                         ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_multiplicities": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _B,
+                                            ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_quotient": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientGate), ctypes.POINTER(QuotientPerm),
                                       _U32, _U32, _B, ctypes.POINTER(_U64)]),
     "kzg_rows_commit_quotient_ext": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms), ctypes.POINTER(QuotientPerm),
@@ -154,6 +156,8 @@ SYMBOLS = {
                                                  _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_lookup_sum": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B,
                                               _B, _B, _B, ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_multiplicities": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32,
+                                                  _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_quotient": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientGate),
                                             ctypes.POINTER(QuotientPerm), _U32, _U32, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_quotient_ext": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms),

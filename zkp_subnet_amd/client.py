@@ -356,6 +356,25 @@ class Client:
                 "closing": codec.be32_to_fr(closing)}
 
     @_guard
+    def worker_commit_multiplicities(self, input_handles: Sequence[int], table_handles: Sequence[int], n_lookups: int,
+                                     width: int):
+        """Extension: the multiplicity row m of a lookup argument over the rows of committed sets (n_lookups * width input
+        rows from input_handles, lookup-major; width table columns from table_handles), joined and committed on the device
+        as a new one-row set.  Returns its handle, its commitment and `missing`, the number of looked-up cells whose tuple is
+        no row of the table (0 when every lookup is satisfied).  The handle goes straight into worker_commit_lookup_sum as
+        mult_handle; theta and beta are drawn after this commitment."""
+        hi, ht = _handles(input_handles), _handles(table_handles)
+        try:
+            n_lookups, width = int(n_lookups), int(width)
+        except (TypeError, ValueError) as e:
+            raise codec.CodecError(f"worker_commit_multiplicities: n_lookups and width must be integers: {e!r}") from e
+        if n_lookups < 1 or width < 1 or n_lookups * width > KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"worker_commit_multiplicities: n_lookups = {n_lookups}, width = {width}, expected both "
+                                   f">= 1 and n_lookups * width <= {KZG_MAX_BATCH_OPEN}")
+        rs, missing = self.engine.commit_multiplicities(hi, ht, n_lookups, width)
+        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]), "missing": int(missing)}
+
+    @_guard
     def worker_commit_quotient(self, handles: Sequence[int], terms, perm=None, ext_log: int = 2, n_pieces: int = 3):
         """Extension: the PLONK quotient t over the rows of committed sets, computed and committed on the device as a new set
         of n_pieces rows.  terms: [coefficient, [row indices]] per gate term; perm: None or {"wires", "sigmas", "z",

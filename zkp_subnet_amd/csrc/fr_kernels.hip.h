@@ -151,3 +151,14 @@ void launch_fr_batch_inv(hipStream_t s, const uint32_t* Q, uint32_t* W, const ui
 // v[t] <- sum_{u<t} v[u] in place (n Montgomery elements, canonical); scr: (n + 3) / 4 * 3 / 2 + 64 elements; closing_be
 // (device): sum_u v[u], 32 bytes big-endian
 void launch_lk_sum_scan(hipStream_t s, uint32_t* v, uint64_t n, uint32_t* scr, uint8_t* closing_be);
+// ---- the hash join of the lookup multiplicities (fr_join.hip; kzg_rows_commit_multiplicities).  tab / in: w columns of T
+// canonical Montgomery elements each, column c at + c * T * 8 words; slots: cap u32 (cap a power of two >= 2 T, all
+// 0xffffffff before the build); *overrun (device) raised when a probe walk reaches its bound of cap steps
+// slot[..] <- the smallest row index of every distinct table tuple
+void launch_join_build(hipStream_t s, const uint32_t* tab, uint64_t T, uint32_t w, uint32_t* slots, uint32_t cap,
+                       uint32_t* overrun);
+// one lookup's T cells: cnt[first(tuple)] += 1 for a cell whose tuple is a table row, *missing += 1 otherwise
+void launch_join_probe(hipStream_t s, const uint32_t* tab, const uint32_t* in, uint64_t T, uint32_t w, const uint32_t* slots,
+                       uint32_t cap, uint32_t* cnt, uint64_t* missing, uint32_t* overrun);
+// out[t] <- cnt[t] as a canonical Montgomery element
+void launch_join_counts(hipStream_t s, const uint32_t* cnt, uint32_t* out, uint64_t T);

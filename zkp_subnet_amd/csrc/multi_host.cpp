@@ -39,6 +39,9 @@ int rows_lookup_sum_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handl
                          uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
                          uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint8_t* out_commitment48,
                          uint8_t* out_closing32, uint64_t* out_handle);
+int rows_multiplicities_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                             uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
+                             uint8_t* out_commitment48, uint64_t* out_missing, uint64_t* out_handle);
 int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
                        const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces,
                        uint8_t* out_commitments48, uint64_t* out_handle);
@@ -462,6 +465,16 @@ int kzg_multi_rows_commit_lookup_sum(kzg_multi* mh, uint32_t i, uint32_t n_input
     return relay(c, kzg_impl::rows_lookup_sum_impl(c, s, n_input_handles, input_handles, n_table_handles, table_handles,
                                                    mult_handle, n_lookups, width, theta_be32, beta_be32, out_commitment48,
                                                    out_closing32, out_handle));
+}
+int kzg_multi_rows_commit_multiplicities(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                         uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups,
+                                         uint32_t width, uint8_t out_commitment48[48], uint64_t* out_missing,
+                                         uint64_t* out_handle) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_multiplicities_impl(c, s, n_input_handles, input_handles, n_table_handles, table_handles,
+                                                       n_lookups, width, out_commitment48, out_missing, out_handle));
 }
 int kzg_multi_rows_commit_quotient(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
                                    const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log,

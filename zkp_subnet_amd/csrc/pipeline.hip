@@ -826,6 +826,66 @@ int rows_lookup_sum_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inp
     return KZG_OK;
 }
 
+// The lookup multiplicities (kzg_rows_commit_multiplicities): a set built FROM sets, and the one row of the lookup argument
+// that needs no challenge.  All w columns of a tuple must be live at once, so the workspace is 2 w vectors of T in the lane's
+// quotient workspace: the w table columns in evaluation form, and the w columns of ONE lookup at a time.  The forward
+// transform ends canonical (fr9_reduce) and a length-1 row is copied from a set's canonical coefficients, so the join
+// (fr_join.hip) compares and hashes the words as they lie.  Build once, probe lookup by lookup into T u32 counters, turn
+// the counters into m's evaluations (in the first input vector, dead by then); the inverse transform writes m's
+// coefficients straight into the new set's buffer `dst`; one MSM commits.  The record's first evaluation slot carries
+// `missing` (8 bytes) and the overrun flag word behind it.
+int rows_multiplicities_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& table, uint32_t n_lookups,
+                            uint32_t width, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_missing,
+                            bool* out_overrun) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const int lg = ilog2_exact(T);
+    uint32_t* tw = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
+    const uint64_t vw = T * 8;                 // one vector, in words
+    const uint32_t cap = (uint32_t)(2 * T);    // slots: a power of two, load <= 1 / 2 (T <= 2^27: the caller)
+    HIPCHK(ctx, A.qext.ensure((size_t)2 * width * T * 32));
+    HIPCHK(ctx, A.qstage.ensure(((size_t)cap + T) * 4));
+    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    uint32_t *tab = A.qext.as<uint32_t>(), *in = tab + (uint64_t)width * vw, *mid = A.ntt_mid.as<uint32_t>();
+    uint32_t *slots = A.qstage.as<uint32_t>(), *cnt = slots + cap;
+    uint8_t* rec = A.brec.as<uint8_t>();
+    uint64_t* missing = reinterpret_cast<uint64_t*>(rec + MR_EVAL);
+    uint32_t* overrun = reinterpret_cast<uint32_t*>(rec + MR_EVAL + 8);
+    for (uint32_t c = 0; c < width; c++) {
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, table.r[c], tab + c * vw, lg, tw, nullptr, mid);
+    }
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        HIPCHK(ctx, hipMemsetAsync(slots, 0xff, (size_t)cap * 4, A.stream));
+        HIPCHK(ctx, hipMemsetAsync(cnt, 0, (size_t)T * 4, A.stream));
+        HIPCHK(ctx, hipMemsetAsync(rec + MR_EVAL, 0, 32, A.stream));
+        launch_join_build(A.stream, tab, T, width, slots, cap, overrun);
+    }
+    for (uint32_t l = 0; l < n_lookups; l++) {
+        for (uint32_t c = 0; c < width; c++) {
+            Span sp(ctx, A, KZG_T_NTT);
+            launch_fr_ntt(A.stream, inputs.r[l * width + c], in + c * vw, lg, tw, nullptr, mid);
+        }
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_join_probe(A.stream, tab, in, T, width, slots, cap, cnt, missing, overrun);
+    }
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_join_counts(A.stream, cnt, in, T);
+    }
+    const uint32_t* c;
+    if (int rc = row_to_coeffs(ctx, A, in, T, 1, &c, dst)) return rc;
+    uint8_t ev[32];
+    if (int rc = multi_msms_finish(ctx, H, i, T, dst, 1, 0, 1, out_c48, ev, nullptr)) return rc;
+    uint32_t of;
+    memcpy(out_missing, ev, 8);
+    memcpy(&of, ev + 8, 4);
+    *out_overrun = of != 0;
+    return KZG_OK;
+}
+
 // the quotient's constants of one (T, E), shared by all lanes like the twiddles: built once under the ctx mutex
 static int ensure_quot_consts(kzg_ctx* ctx, Lane& L, int log_t, int ext_log, const uint32_t* tw_n, const uint32_t** qc) {
     std::lock_guard<std::mutex> lk(ctx->mu);

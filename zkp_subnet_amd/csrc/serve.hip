@@ -943,6 +943,55 @@ int rows_lookup_sum_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handl
     return KZG_OK;
 }
 
+// kzg_rows_commit_multiplicities: the lookups of an open (two handle lists), the reservation of a commit
+int rows_multiplicities_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                             uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
+                             uint8_t* out_commitment48, uint64_t* out_missing, uint64_t* out_handle) {
+    if (!ctx || !input_handles || !table_handles || !out_commitment48 || !out_missing || !out_handle) return KZG_E_ARG;
+    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN || n_table_handles == 0 || n_table_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "multiplicities: the number of handles in each list must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (n_lookups == 0 || width == 0 || (uint64_t)n_lookups * width > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "multiplicities: n_lookups and width must be at least 1 and n_lookups * width at most "
+                                    "KZG_MAX_BATCH_OPEN");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs irefs{ctx}, trefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab it, tt;
+    uint32_t ki = 0, kt = 0, i = 0, i2 = 0;
+    uint64_t T = 0, T2 = 0;
+    if (int rc = rows_lookup(ctx, "multiplicities: inputs", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    if (int rc = rows_lookup(ctx, "multiplicities: table", expect_i, n_table_handles, table_handles, trefs, tt, &kt, &i2, &T2)) return rc;
+    if (i2 != i || T2 != T)
+        return fail(ctx, KZG_E_ARG, "multiplicities: all sets must belong to one worker and have one row length");
+    if (ki != n_lookups * width || kt != width)
+        return fail(ctx, KZG_E_ARG, "multiplicities: the input sets must hold exactly n_lookups * width rows and the table "
+                                    "sets exactly width rows");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "multiplicities: the row length must be a power of two");
+    if (T > ((uint64_t)1 << 27))   // L T additions fit a u32 counter, 2 T slots a u32 index
+        return fail(ctx, KZG_E_ARG, "multiplicities: the row length must be at most 2^27");
+    if (int rc2 = rows_reserve(ctx, "multiplicities", pend, (size_t)T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    bool overrun = false;
+    uint8_t c48[48];
+    uint64_t missing = 0;
+    rc = rows_multiplicities_dev(ctx, H, i, it, tt, n_lookups, width, T, pend.buf.as<uint32_t>(), c48, &missing, &overrun);
+    if (rc) return rc;
+    if (overrun)
+        return fail(ctx, KZG_E_HIP, "multiplicities: a probe walk of the hash join reached its bound (the slot table held no "
+                                    "empty slot): no set was created");
+    memcpy(out_commitment48, c48, 48);
+    *out_missing = missing;
+    *out_handle = rows_insert(ctx, pend, i, 1, T);
+    return KZG_OK;
+}
+
 // kzg_rows_commit_quotient_ext (and, with no rotation and no lookup part, kzg_rows_commit_quotient: `plain`, which only words
 // one message): the lookups of an open (one handle list), the reservation of a commit
 int rows_quotient_ext_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
@@ -1152,6 +1201,12 @@ int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uin
                                uint8_t out_closing32[32], uint64_t* out_handle) {
     return rows_lookup_sum_impl(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
                                 n_lookups, width, theta_be32, beta_be32, out_commitment48, out_closing32, out_handle);
+}
+int kzg_rows_commit_multiplicities(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                                   uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
+                                   uint8_t out_commitment48[48], uint64_t* out_missing, uint64_t* out_handle) {
+    return rows_multiplicities_impl(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups,
+                                    width, out_commitment48, out_missing, out_handle);
 }
 int kzg_rows_commit_quotient(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_gate* gate,
                              const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,

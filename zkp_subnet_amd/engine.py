@@ -407,6 +407,25 @@ class HipEngine:
         src = next((x for x in list(input_sets) + list(table_sets) + [mult_set] if hasattr(x, "T")), None)
         return RowSet(self, h.value, getattr(src, "i", None), 1, getattr(src, "T", None), [c.raw]), cl.raw
 
+    # ---- a fifth set built from sets: the multiplicity row of the lookup argument, joined and committed on the device
+    def commit_multiplicities(self, input_sets: Sequence[object], table_sets: Sequence[object], n_lookups: int,
+                              width: int) -> Tuple["RowSet", int]:
+        """m of kzg_rows_commit_multiplicities: how many of the n_lookups * width concatenated rows' cells (input_sets,
+        lookup-major) hit each row of the width concatenated rows of table_sets, every hit of a repeated table tuple counted
+        on its first copy (RowSet objects or bare handles).  Returns (a one-row RowSet holding m, missing): missing is the
+        number of cells whose tuple is no table row, 0 when every lookup is satisfied.  No challenge is involved: m is
+        committed before theta and beta are drawn."""
+        ni, hi = self._handle_array(input_sets, "commit_multiplicities (inputs)")
+        nt, ht = self._handle_array(table_sets, "commit_multiplicities (table)")
+        if n_lookups < 1 or width < 1 or n_lookups * width > _native.KZG_MAX_BATCH_OPEN:
+            raise KzgError(_native.KZG_E_ARG, f"commit_multiplicities: n_lookups, width >= 1, n_lookups * width <= "
+                                              f"{_native.KZG_MAX_BATCH_OPEN}")
+        c, miss, h = ctypes.create_string_buffer(48), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_multiplicities(self._h, ni, hi, nt, ht, n_lookups, width, c, ctypes.byref(miss),
+                                                           ctypes.byref(h)))
+        src = next((x for x in list(input_sets) + list(table_sets) if hasattr(x, "T")), None)
+        return RowSet(self, h.value, getattr(src, "i", None), 1, getattr(src, "T", None), [c.raw]), int(miss.value)
+
     # ---- a third set built from sets: the PLONK quotient (round 3), computed and committed on the device
     def commit_quotient(self, sets: Sequence[object], terms: Sequence[Tuple[bytes, Sequence[int]]], perm: Optional[dict] = None,
                         ext_log: int = 2, n_pieces: int = 3) -> "RowSet":

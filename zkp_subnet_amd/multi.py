@@ -163,6 +163,18 @@ class MultiDeviceClient:
             self._row_owner[int(r.json()["handle"])] = i
         return r
 
+    def worker_commit_multiplicities(self, input_handles: Sequence[int], table_handles: Sequence[int], n_lookups, width):
+        try:
+            i = self._owner(list(input_handles) + list(table_handles))
+        except TypeError:
+            i = None
+        if i is None:
+            return Response(400, {"error": "worker_commit_multiplicities: the handles must name live sets of one worker"})
+        r = self._for(i).worker_commit_multiplicities(input_handles, table_handles, n_lookups, width)
+        if r.status_code == 200:
+            self._row_owner[int(r.json()["handle"])] = i
+        return r
+
     def worker_commit_quotient(self, handles: Sequence[int], terms, perm=None, ext_log=2, n_pieces=3):
         i = self._owner(handles)
         if i is None:
