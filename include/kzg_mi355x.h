@@ -234,8 +234,8 @@ int kzg_rows_open_lincomb(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* hand
  * serving.
  * SOUNDNESS: beta and gamma must be drawn AFTER the wire commitments are fixed (a prover who knows them before it commits
  * the wires can make a false permutation close).  The library derives no challenge and adds NO BLINDING: a blinded z has
- * degree >= T and does not fit a T-point slice; a caller who blinds pads its circuit below T and adds the blinding rows
- * itself through kzg_rows_open_lincomb. */
+ * degree >= T and does not fit a T-point slice; a caller who blinds pads its circuit below T and calls
+ * kzg_rows_commit_grand_product_zk below, which fills the blinding rows. */
 int kzg_rows_commit_grand_product(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t* wire_handles,
                                   uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
                                   const uint8_t* shifts_be32 /* k*32 */, const uint8_t beta_be32[32],
@@ -269,7 +269,8 @@ int kzg_rows_commit_grand_product(kzg_ctx* ctx, uint32_t n_wire_handles, const u
  * That quotient term (it needs S at X and w_T X, i.e. gate factors with a rotation) is the lookup part of
  * kzg_rows_commit_quotient_ext.
  * m itself is built and committed on the device by kzg_rows_commit_multiplicities.
- * OUT OF SCOPE: per-row selectors (a caller points inactive rows at a default table entry); plookup; blinding. */
+ * OUT OF SCOPE: per-row selectors (a caller points inactive rows at a default table entry); plookup.  Blinding rows:
+ * kzg_rows_commit_lookup_sum_zk below. */
 int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
                                uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
                                uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32], const uint8_t beta_be32[32],
@@ -301,7 +302,7 @@ int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uin
  * kzg_rows_open.  Thread-safe like every call; after any error the context keeps serving.
  * SOUNDNESS: nothing here is a proof.  m is prover data like any witness row; the argument is the relation of
  * kzg_rows_commit_quotient_ext over S, with theta and beta drawn AFTER this call's commitment is fixed.  No blinding.
- * OUT OF SCOPE: per-row selectors, plookup, blinding (as above). */
+ * OUT OF SCOPE: per-row selectors, plookup (as above).  Blinding rows: kzg_rows_commit_multiplicities_zk below. */
 int kzg_rows_commit_multiplicities(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
                                    uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
                                    uint8_t out_commitment48[48], uint64_t* out_missing, uint64_t* out_handle);
@@ -336,7 +337,7 @@ int kzg_rows_commit_multiplicities(kzg_ctx* ctx, uint32_t n_input_handles, const
  * kzg_rows_open.  Thread-safe like every call; after any error the context keeps serving.
  * SOUNDNESS: alpha must be drawn AFTER z's commitment is fixed, and beta, gamma after the wire commitments.  The library
  * derives no challenge and adds NO BLINDING here either: a blinded t or z has degree >= T per piece and does not fit T-point
- * slices; a caller who blinds pads its circuit below T and adds the blinding rows itself through kzg_rows_open_lincomb. */
+ * slices; a caller who blinds pads its circuit below T and uses the blinding-rows layout of kzg_rows_commit_quotient_zk. */
 #define KZG_MAX_GATE_TERMS 16
 typedef struct kzg_quotient_gate {
     uint32_t n_terms;
@@ -381,7 +382,7 @@ int kzg_rows_commit_quotient(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* h
  * n_terms = 0 makes it empty).
  * SOUNDNESS: alpha must be drawn AFTER the commitments of S and z are fixed; theta and beta AFTER the commitments of the
  * inputs, the table and m (as for kzg_rows_commit_lookup_sum; kzg_rows_commit_multiplicities builds and commits m on the
- * device).  Still out of scope: per-row selectors, plookup, blinding. */
+ * device).  Still out of scope: per-row selectors, plookup.  Blinding rows: kzg_rows_commit_quotient_zk below. */
 typedef struct kzg_quotient_terms {
     uint32_t n_terms;
     const uint8_t* coeffs_be32;  /* n_terms * 32 */
@@ -404,6 +405,64 @@ int kzg_rows_commit_quotient_ext(kzg_ctx* ctx, uint32_t n_handles, const uint64_
                                  const kzg_quotient_perm* perm /* NULL: none */,
                                  const kzg_quotient_lookup* lookup /* NULL: none */, uint32_t ext_log, uint32_t n_pieces,
                                  uint8_t* out_commitments48 /* n_pieces * 48 */, uint64_t* out_handle);
+/* BLINDING ROWS: the four builders above for a circuit that hides its witness (the layout of halo2).  With T the row length
+ * and u = usable, 1 <= u <= T - 1 and T - u <= KZG_MAX_BLIND_ROWS:
+ *   rows 0 .. u - 1 carry the circuit; row u is the "last" row, where a running value closes; rows u + 1 .. T - 1 hold random
+ *   values -- in the caller's own rows (wires, which it commits itself) and, for z, S and m, the T - u - 1 canonical scalars of
+ *   tail_be32 (row u + 1 first; NULL exactly when u = T - 1).
+ * The library draws no randomness, as it derives no challenge.  Everything not named here is that of the plain call: handle
+ * rules, worker and T rules, the new set's life, thread safety, "after any error the context keeps serving"; nothing
+ * row-sized crosses the host link (the tail rides in a kernel argument).  The plain calls keep their bytes, their kernels and
+ * their host path.  Errors beyond the plain call's (all KZG_E_ARG): u = 0, u >= T, T - u > KZG_MAX_BLIND_ROWS, a tail scalar
+ * >= r, tail_be32 NULL with u < T - 1.
+ * kzg_rows_commit_grand_product_zk:  z(w^0) = 1,  z(w^(t+1)) = z(w^t) N_t / D_t for t < u, so z(w^u) = prod_{t<u} N_t / D_t =
+ *   closing (1 when the permutation holds on the usable rows);  z(w^t) = tail[t - u - 1] for u < t < T.  Rows t >= u of the
+ *   wires and sigmas do not enter the product: a zero D_t there is no error, one at t < u is the plain call's KZG_E_ARG.  The
+ *   committed row equals kzg_rows_commit(i, 1, z, T, 1, ..) of those T evaluations byte for byte.  One inversion per call and
+ *   the plain call's four-vector workspace.
+ * kzg_rows_commit_lookup_sum_zk:  S(w_T^0) = 0,  S(w_T^(t+1)) = S(w_T^t) + term_t for t < u, S(w_T^u) = sum_{t<u} term_t =
+ *   closing, the tail behind.  term_t is 0 for t >= u whatever the cells hold: a zero denominator there is no error.
+ * kzg_rows_commit_multiplicities_zk:  only table rows t < u are built into the join and only input cells t' < u are probed;
+ *   `missing` counts only those cells;  m(w_T^u) = 0 and m(w_T^t) = tail[t - u - 1] behind it.  The first-copy rule, the
+ *   bounded walks and the overrun answer are the plain call's.
+ * kzg_rows_commit_quotient_zk:  active names a resident row A, the caller's fixed column that is 1 on t < u and 0 elsewhere
+ *   (the library does not judge its contents), which switches the two relations that run along the rows off behind u:
+ *     num = Gate + alpha A P1 + alpha^2 P2 + alpha^3 A LK1 + alpha^4 LK2,   t = num / (X^T - 1)
+ *   A P1 has k + 2 factors, so perm->k <= E - 1; A LK1 has L + 3, so L <= E - 2 (either violated: KZG_E_ARG; so is an
+ *   active_row >= n).  With active == NULL the call IS kzg_rows_commit_quotient_ext, byte for byte.  What remains needs no
+ *   library support: "z = 1 at row u" is (z - 1) L_u and "S = 0 at row u" is S L_u, ordinary gate terms over a caller row L_u
+ *   (1 at row u, 0 elsewhere) with the caller's powers of alpha as coefficients; the gates themselves are switched off on the
+ *   padding rows by the caller's selectors.
+ * SOUNDNESS / HIDING: the library supplies the mechanics only.  How many blinding rows a polynomial needs (at least the number
+ * of points it is opened at, plus one) is the caller's choice, and the random values must be fresh per proof.  The quotient
+ * pieces are opened only through the combination sum_p zeta^(pT) t_p (kzg_rows_open_lincomb), whose value the identity already
+ * fixes.  Challenges are still the caller's and are drawn as before (beta, gamma after the wires; theta, beta after the
+ * inputs, the table and m; alpha after z and S).  Degree-raising blinders (b Z_H) do not fit a T-point slice and stay out of
+ * scope, as do per-row selectors and plookup. */
+#define KZG_MAX_BLIND_ROWS 32
+typedef struct kzg_quotient_active {
+    uint32_t active_row;         /* A */
+} kzg_quotient_active;
+int kzg_rows_commit_grand_product_zk(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                     uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
+                                     const uint8_t* shifts_be32 /* k*32 */, const uint8_t beta_be32[32],
+                                     const uint8_t gamma_be32[32], uint64_t usable,
+                                     const uint8_t* tail_be32 /* (T-usable-1)*32, or NULL */, uint8_t out_commitment48[48],
+                                     uint8_t out_closing32[32], uint64_t* out_handle);
+int kzg_rows_commit_lookup_sum_zk(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                                  uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
+                                  uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32], const uint8_t beta_be32[32],
+                                  uint64_t usable, const uint8_t* tail_be32 /* (T-usable-1)*32, or NULL */,
+                                  uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle);
+int kzg_rows_commit_multiplicities_zk(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                                      uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
+                                      uint64_t usable, const uint8_t* tail_be32 /* (T-usable-1)*32, or NULL */,
+                                      uint8_t out_commitment48[48], uint64_t* out_missing, uint64_t* out_handle);
+int kzg_rows_commit_quotient_zk(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
+                                const kzg_quotient_perm* perm /* NULL: none */,
+                                const kzg_quotient_lookup* lookup /* NULL: none */,
+                                const kzg_quotient_active* active /* NULL: kzg_rows_commit_quotient_ext */, uint32_t ext_log,
+                                uint32_t n_pieces, uint8_t* out_commitments48 /* n_pieces * 48 */, uint64_t* out_handle);
 /* The UNCHANGED reference miner makes two calls per request with the same row -- worker_commit(i, poly), then
  * worker_open(i, poly, x) (neurons/miner.py:56-61).  These forms take a 128-bit content tag identifying the row's bytes
  * (the host codec computes it while decoding the text); the coefficient vectors of the last four rows stay on the
@@ -645,6 +704,25 @@ int kzg_multi_rows_commit_quotient_ext(kzg_multi* mh, uint32_t i, uint32_t n_han
                                        const kzg_quotient_terms* gate, const kzg_quotient_perm* perm,
                                        const kzg_quotient_lookup* lookup, uint32_t ext_log, uint32_t n_pieces,
                                        uint8_t* out_commitments48, uint64_t* out_handle);
+/* the kzg_rows_commit_*_zk builders on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_grand_product_zk(kzg_multi* mh, uint32_t i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                           uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
+                                           const uint8_t* shifts_be32, const uint8_t beta_be32[32], const uint8_t gamma_be32[32],
+                                           uint64_t usable, const uint8_t* tail_be32, uint8_t out_commitment48[48],
+                                           uint8_t out_closing32[32], uint64_t* out_handle);
+int kzg_multi_rows_commit_lookup_sum_zk(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                        uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
+                                        uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32],
+                                        const uint8_t beta_be32[32], uint64_t usable, const uint8_t* tail_be32,
+                                        uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle);
+int kzg_multi_rows_commit_multiplicities_zk(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                            uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups,
+                                            uint32_t width, uint64_t usable, const uint8_t* tail_be32,
+                                            uint8_t out_commitment48[48], uint64_t* out_missing, uint64_t* out_handle);
+int kzg_multi_rows_commit_quotient_zk(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                      const kzg_quotient_terms* gate, const kzg_quotient_perm* perm,
+                                      const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
+                                      uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

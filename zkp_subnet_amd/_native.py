@@ -20,6 +20,7 @@ KZG_MAX_BATCH_OPEN = 16   # include/kzg_mi355x.h
 KZG_MAX_OPEN_POINTS = 4
 KZG_MAX_ROW_SETS = 64
 KZG_MAX_GATE_TERMS = 16   # kzg_rows_commit_quotient
+KZG_MAX_BLIND_ROWS = 32   # kzg_rows_commit_*_zk: T - usable
 KZG_OK, KZG_E_ARG, KZG_E_SCALAR, KZG_E_POINT, KZG_E_HIP, KZG_E_NOMEM, KZG_E_BUSY, KZG_E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
 STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_SCALAR", -3: "E_POINT", -4: "E_HIP", -5: "E_NOMEM", -6: "E_BUSY", -7: "E_COMM"}
 TIMING_NAMES = ["decode", "ntt", "digits", "scan", "scatter", "accumulate", "fixup", "tree", "final", "poly", "total", "collective"]
@@ -52,6 +53,11 @@ class QuotientLookup(ctypes.Structure):
     """kzg_quotient_lookup"""
     _fields_ = [("n_lookups", _U32), ("width", _U32), ("input_rows", ctypes.POINTER(_U32)), ("table_rows", ctypes.POINTER(_U32)),
                 ("mult_row", _U32), ("sum_row", _U32), ("theta_be32", _B), ("beta_be32", _B), ("alpha_be32", _B)]
+
+
+class QuotientActive(ctypes.Structure):
+    """kzg_quotient_active"""
+    _fields_ = [("active_row", _U32)]
 
 
 SYMBOLS = {
@@ -95,6 +101,15 @@ SYMBOLS = {
                                       _U32, _U32, _B, ctypes.POINTER(_U64)]),
     "kzg_rows_commit_quotient_ext": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms), ctypes.POINTER(QuotientPerm),
                                           ctypes.POINTER(QuotientLookup), _U32, _U32, _B, ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_grand_product_zk": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _B, _B, _B, _U64, _B,
+                                              _B, _B, ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_lookup_sum_zk": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B, _B, _U64,
+                                           _B, _B, _B, ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_multiplicities_zk": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _U64, _B, _B,
+                                               ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_quotient_zk": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms), ctypes.POINTER(QuotientPerm),
+                                         ctypes.POINTER(QuotientLookup), ctypes.POINTER(QuotientActive), _U32, _U32, _B,
+                                         ctypes.POINTER(_U64)]),
     "kzg_commit_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B]),
     "kzg_open_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B, _B]),
     "kzg_row_cache_stats": (_I, [_P, ctypes.POINTER(_U64)]),
@@ -163,6 +178,15 @@ SYMBOLS = {
     "kzg_multi_rows_commit_quotient_ext": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms),
                                                 ctypes.POINTER(QuotientPerm), ctypes.POINTER(QuotientLookup), _U32, _U32, _B,
                                                 ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_grand_product_zk": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _B, _B,
+                                                    _B, _U64, _B, _B, _B, ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_lookup_sum_zk": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32,
+                                                 _B, _B, _U64, _B, _B, _B, ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_multiplicities_zk": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32,
+                                                     _U64, _B, _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_quotient_zk": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms),
+                                               ctypes.POINTER(QuotientPerm), ctypes.POINTER(QuotientLookup),
+                                               ctypes.POINTER(QuotientActive), _U32, _U32, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_commit_open_rows": (_I, [_P, _U32, ctypes.POINTER(_U32), _B, _U64, _I, _B, _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_upload_fr": (_I, [_P, _I, _B, _U64, _I]),
     "kzg_msm_resident": (_I, [_P, _I, _U64, _U64, _B]),

@@ -433,6 +433,119 @@ class Client:
         rs = self.engine.commit_quotient_ext(hs, tt, pp, ll, ext_log, n_pieces)
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments]}
 
+    # ---- the builders with blinding rows (kzg_rows_commit_*_zk): rows [0, usable) carry the circuit, row `usable` closes the
+    # running value and rows usable + 1 .. T - 1 take `tail`, the caller's fresh random scalars (T - usable - 1 of them)
+    @staticmethod
+    def _blind(what: str, usable, tail) -> tuple:
+        try:
+            usable = int(usable)
+            tb = [codec.fr_to_be32(x) for x in (tail or [])]
+        except (TypeError, ValueError) as e:
+            raise codec.CodecError(f"{what}: usable must be an integer and the tail a list of scalars: {e!r}") from e
+        if usable < 0 or any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in tb):
+            raise codec.CodecError(f"{what}: usable must not be negative and the tail scalars must be canonical (< r)")
+        return usable, tb
+
+    @_guard
+    def worker_commit_grand_product_zk(self, wire_handles: Sequence[int], sigma_handles: Sequence[int], shifts: Sequence[str],
+                                       beta: str, gamma: str, usable: int, tail: Sequence[str]):
+        """Extension: worker_commit_grand_product over the first `usable` rows only: z(w^usable) is the closing value (1 when
+        the permutation holds on the usable rows) and z's rows behind it are `tail`.  Rows >= usable of the wires and sigmas
+        do not enter the product.  The library draws no randomness: the tail must be fresh per proof."""
+        hw, hs = _handles(wire_handles), _handles(sigma_handles)
+        if not 1 <= len(shifts) <= KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"worker_commit_grand_product_zk: {len(shifts)} shifts, expected 1 .. {KZG_MAX_BATCH_OPEN}")
+        sc = [codec.fr_to_be32(x) for x in list(shifts) + [beta, gamma]]
+        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in sc):
+            raise codec.CodecError("worker_commit_grand_product_zk: shifts, beta and gamma must be canonical scalars (< r)")
+        usable, tb = self._blind("worker_commit_grand_product_zk", usable, tail)
+        rs, closing = self.engine.commit_grand_product_zk(hw, hs, sc[:-2], sc[-2], sc[-1], usable, tb)
+        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]),
+                "closing": codec.be32_to_fr(closing)}
+
+    @_guard
+    def worker_commit_lookup_sum_zk(self, input_handles: Sequence[int], table_handles: Sequence[int], mult_handle: int,
+                                    n_lookups: int, width: int, theta: str, beta: str, usable: int, tail: Sequence[str]):
+        """Extension: worker_commit_lookup_sum over the first `usable` rows only: S(w^usable) is the closing value (0 when
+        the sum closes on the usable rows) and S's rows behind it are `tail`."""
+        hi, ht, hm = _handles(input_handles), _handles(table_handles), _handles([mult_handle])[0]
+        try:
+            n_lookups, width = int(n_lookups), int(width)
+        except (TypeError, ValueError) as e:
+            raise codec.CodecError(f"worker_commit_lookup_sum_zk: n_lookups and width must be integers: {e!r}") from e
+        if n_lookups < 1 or width < 1 or n_lookups * width > KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"worker_commit_lookup_sum_zk: n_lookups = {n_lookups}, width = {width}, expected both >= 1 "
+                                   f"and n_lookups * width <= {KZG_MAX_BATCH_OPEN}")
+        sc = [codec.fr_to_be32(x) for x in (theta, beta)]
+        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in sc):
+            raise codec.CodecError("worker_commit_lookup_sum_zk: theta and beta must be canonical scalars (< r)")
+        usable, tb = self._blind("worker_commit_lookup_sum_zk", usable, tail)
+        rs, closing = self.engine.commit_lookup_sum_zk(hi, ht, hm, n_lookups, width, sc[0], sc[1], usable, tb)
+        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]),
+                "closing": codec.be32_to_fr(closing)}
+
+    @_guard
+    def worker_commit_multiplicities_zk(self, input_handles: Sequence[int], table_handles: Sequence[int], n_lookups: int,
+                                        width: int, usable: int, tail: Sequence[str]):
+        """Extension: worker_commit_multiplicities over the first `usable` table rows and input cells only (`missing` counts
+        those cells alone): m(w^usable) = 0 and m's rows behind it are `tail`."""
+        hi, ht = _handles(input_handles), _handles(table_handles)
+        try:
+            n_lookups, width = int(n_lookups), int(width)
+        except (TypeError, ValueError) as e:
+            raise codec.CodecError(f"worker_commit_multiplicities_zk: n_lookups and width must be integers: {e!r}") from e
+        if n_lookups < 1 or width < 1 or n_lookups * width > KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"worker_commit_multiplicities_zk: n_lookups = {n_lookups}, width = {width}, expected both "
+                                   f">= 1 and n_lookups * width <= {KZG_MAX_BATCH_OPEN}")
+        usable, tb = self._blind("worker_commit_multiplicities_zk", usable, tail)
+        rs, missing = self.engine.commit_multiplicities_zk(hi, ht, n_lookups, width, usable, tb)
+        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]), "missing": int(missing)}
+
+    @_guard
+    def worker_commit_quotient_zk(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None,
+                                  ext_log: int = 2, n_pieces: int = 3):
+        """Extension: worker_commit_quotient_ext with the caller's active column: row active_row (1 on the usable rows, 0
+        elsewhere) multiplies the permutation relation P1 and the lookup relation LK1, so that neither binds the blinding
+        rows.  The permutation part then takes at most 2^ext_log - 1 wires, the lookup part at most 2^ext_log - 2 lookups.
+        active_row = None is worker_commit_quotient_ext."""
+        hs = _handles(handles)
+        try:
+            active_row = None if active_row is None else int(active_row)
+        except (TypeError, ValueError) as e:
+            raise codec.CodecError(f"worker_commit_quotient_zk: active_row must be an integer or None: {e!r}") from e
+        tt, pp, ll, ext_log, n_pieces = self._quotient_ext_parts("worker_commit_quotient_zk", terms, perm, lookup, ext_log,
+                                                                 n_pieces)
+        rs = self.engine.commit_quotient_zk(hs, tt, pp, ll, active_row, ext_log, n_pieces)
+        return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments]}
+
+    @staticmethod
+    def _quotient_ext_parts(what: str, terms, perm, lookup, ext_log, n_pieces):
+        """the wire forms of worker_commit_quotient_ext's arguments -> the engine's (bytes and ints), scalars checked"""
+        try:
+            ext_log, n_pieces = int(ext_log), int(n_pieces)
+            tt = [(codec.fr_to_be32(c), [(int(f[0]), int(f[1])) if isinstance(f, (tuple, list)) else (int(f), 0) for f in fs])
+                  for c, fs in terms]
+            if any(isinstance(f, (tuple, list)) and len(f) != 2 for _, fs in terms for f in fs):
+                raise ValueError("a factor is a row index or a [row, rot] pair")
+            pp = None
+            if perm is not None and len(perm["wires"]):   # (no wire: the part is off, as perm->k == 0 in C)
+                pp = {"wires": [int(j) for j in perm["wires"]], "sigmas": [int(j) for j in perm["sigmas"]], "z": int(perm["z"]),
+                      "shifts": [codec.fr_to_be32(x) for x in perm["shifts"]], "beta": codec.fr_to_be32(perm["beta"]),
+                      "gamma": codec.fr_to_be32(perm["gamma"]), "alpha": codec.fr_to_be32(perm["alpha"])}
+            ll = None
+            if lookup is not None:
+                ll = {"inputs": [int(j) for j in lookup["inputs"]], "table": [int(j) for j in lookup["table"]],
+                      "mult": int(lookup["mult"]), "sum": int(lookup["sum"]), "width": int(lookup["width"]),
+                      "theta": codec.fr_to_be32(lookup["theta"]), "beta": codec.fr_to_be32(lookup["beta"]),
+                      "alpha": codec.fr_to_be32(lookup["alpha"])}
+        except (TypeError, ValueError, KeyError, IndexError) as e:
+            raise codec.CodecError(f"{what}: malformed terms, permutation or lookup part: {e!r}") from e
+        scal = [c for c, _ in tt] + (pp["shifts"] + [pp["beta"], pp["gamma"], pp["alpha"]] if pp else []) + \
+            ([ll["theta"], ll["beta"], ll["alpha"]] if ll else [])
+        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in scal):
+            raise codec.CodecError(f"{what}: coefficients, shifts and challenges must be canonical scalars (< r)")
+        return tt, pp, ll, ext_log, n_pieces
+
     @_guard
     def worker_release_rows(self, handle: int):
         """Extension: frees a committed row set."""

@@ -408,21 +408,29 @@ int rows_eval_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint3
 int rows_lincomb_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t k, uint64_t T, uint32_t m,
                      const uint8_t* points_be32, const uint8_t* coeffs_be32, const uint32_t* masks, uint8_t* out_values32,
                      uint8_t* out_p48);
+// The blinding rows of a kzg_rows_commit_*_zk builder (checked by the caller: 1 <= usable < T, T - usable <=
+// KZG_MAX_BLIND_ROWS, every tail scalar canonical): rows [0, usable) carry the circuit, row `usable` closes the running value
+// and rows usable + 1 .. T - 1 take the T - usable - 1 scalars of tail_be32 (host bytes).  Null: the plain builder.
+struct Blind {
+    uint64_t usable;
+    const uint8_t* tail_be32;
+};
 // the grand product of k wire / sigma row pairs (rows read through the two tables) into a new one-row set's buffer dst:
 // its commitment, the closing value, and whether some denominator was zero (z undefined: the caller creates no set)
 int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& wires, const RowTab& sigmas, uint32_t k,
                            uint64_t T, const uint8_t* shifts_be32, const uint8_t* beta_be32, const uint8_t* gamma_be32,
-                           uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den);
+                           uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den,
+                           const Blind* zk = nullptr);
 // the lookup running sum over n_lookups x width input rows, width table rows and the multiplicity row `mult` into a new one-row
 // set's buffer dst: its commitment, the closing value, and whether some denominator was zero (the caller creates no set)
 int rows_lookup_sum_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& table, const uint32_t* mult,
                         uint32_t n_lookups, uint32_t width, uint64_t T, const uint8_t* theta_be32, const uint8_t* beta_be32,
-                        uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den);
+                        uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den, const Blind* zk = nullptr);
 // the lookup multiplicities of n_lookups x width input rows against width table rows into a new one-row set's buffer dst: its
 // commitment, the number of cells whose tuple is no table row, and whether a probe walk reached its bound (no set then)
 int rows_multiplicities_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& table, uint32_t n_lookups,
                             uint32_t width, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_missing,
-                            bool* out_overrun);
+                            bool* out_overrun, const Blind* zk = nullptr);
 // the quotient pieces of the constraints qp over the n_rows coefficient rows of rt into a new n_pieces-row set's buffer dst:
 // their commitments, and whether a coefficient of t at or above n_pieces T was not zero (the caller creates no set)
 int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t n_rows, uint64_t T, const QuotPlan& qp,
@@ -442,6 +450,23 @@ int rows_grand_product_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_han
                             uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
                             const uint8_t* beta_be32, const uint8_t* gamma_be32, uint8_t* out_commitment48,
                             uint8_t* out_closing32, uint64_t* out_handle);
+// the _zk builders (kzg_rows_commit_*_zk): the plain call's arguments with usable and tail_be32 behind the challenges
+int rows_grand_product_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                               uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
+                               const uint8_t* beta_be32, const uint8_t* gamma_be32, uint64_t usable, const uint8_t* tail_be32,
+                               uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle);
+int rows_lookup_sum_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                            uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
+                            uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint64_t usable,
+                            const uint8_t* tail_be32, uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle);
+int rows_multiplicities_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
+                                uint64_t usable, const uint8_t* tail_be32, uint8_t* out_commitment48, uint64_t* out_missing,
+                                uint64_t* out_handle);
+int rows_quotient_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                          const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
+                          const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,
+                          uint64_t* out_handle);
 int rows_lookup_sum_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
                          uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
                          uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint8_t* out_commitment48,

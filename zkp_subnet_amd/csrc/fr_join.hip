@@ -78,6 +78,23 @@ __global__ void __launch_bounds__(256) k_join_build(const uint32_t* __restrict__
     }
     atomicOr(overrun, 1u);
 }
+// kzg_rows_commit_multiplicities_zk: the table's first `rows` rows only (the columns still lie T apart).  The same walk,
+// kept as a kernel of its own so that the plain call's keeps its instructions.
+__global__ void __launch_bounds__(256) k_join_build_rows(const uint32_t* __restrict__ tab, uint64_t T, uint64_t rows, uint32_t w,
+                                                          uint32_t* slots, uint32_t mask, uint32_t* overrun) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= rows) return;
+    uint32_t s = join_hash(tab, T, w, t) & mask;
+    for (uint32_t step = 0; step <= mask; step++, s = (s + 1) & mask) {
+        const uint32_t cur = atomicCAS(slots + s, JOIN_EMPTY, (uint32_t)t);
+        if (cur == JOIN_EMPTY) return;
+        if (cur < T && join_equal(tab, cur, tab, t, T, w)) {
+            atomicMin(slots + s, (uint32_t)t);
+            return;
+        }
+    }
+    atomicOr(overrun, 1u);
+}
 
 // ------------------------------------------------------------------------------------------------ probe
 // One lane per cell t of one lookup.  The walk of the build: an empty slot ends it with a miss; a slot whose row equals the
@@ -92,6 +109,35 @@ __global__ void __launch_bounds__(256) k_join_probe(const uint32_t* __restrict__
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool miss = false;
     if (t < T) {
+        uint32_t s = join_hash(in, T, w, t) & mask;
+        bool done = false;
+        for (uint32_t step = 0; step <= mask; step++, s = (s + 1) & mask) {
+            const uint32_t q = slots[s];
+            if (q == JOIN_EMPTY) { miss = done = true; break; }
+            if (q < T && join_equal(tab, q, in, t, T, w)) {
+                atomicAdd(cnt + q, 1u);
+                done = true;
+                break;
+            }
+        }
+        if (!done) atomicOr(overrun, 1u);
+    }
+    const unsigned long long b = __ballot(miss);
+    if ((threadIdx.x & 63u) == 0 && b) atomicAdd(&wg_miss, (uint32_t)__popcll(b));
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_miss) atomicAdd(missing, (unsigned long long)wg_miss);
+}
+// kzg_rows_commit_multiplicities_zk: one lookup's first `rows` cells only (a kernel of its own, as for the build)
+__global__ void __launch_bounds__(256) k_join_probe_rows(const uint32_t* __restrict__ tab, const uint32_t* __restrict__ in,
+                                                          uint64_t T, uint64_t rows, uint32_t w,
+                                                          const uint32_t* __restrict__ slots, uint32_t mask, uint32_t* cnt,
+                                                          unsigned long long* missing, uint32_t* overrun) {
+    __shared__ uint32_t wg_miss;
+    if (threadIdx.x == 0) wg_miss = 0;
+    __syncthreads();
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool miss = false;
+    if (t < rows) {
         uint32_t s = join_hash(in, T, w, t) & mask;
         bool done = false;
         for (uint32_t step = 0; step <= mask; step++, s = (s + 1) & mask) {
@@ -134,6 +180,16 @@ void launch_join_probe(hipStream_t s, const uint32_t* tab, const uint32_t* in, u
     if (T)
         k_join_probe<<<nblk(T, 256), 256, 0, s>>>(tab, in, T, w, slots, cap - 1, cnt, reinterpret_cast<unsigned long long*>(missing),
                                                    overrun);
+}
+void launch_join_build_rows(hipStream_t s, const uint32_t* tab, uint64_t T, uint64_t rows, uint32_t w, uint32_t* slots,
+                            uint32_t cap, uint32_t* overrun) {
+    if (rows) k_join_build_rows<<<nblk(rows, 256), 256, 0, s>>>(tab, T, rows, w, slots, cap - 1, overrun);
+}
+void launch_join_probe_rows(hipStream_t s, const uint32_t* tab, const uint32_t* in, uint64_t T, uint64_t rows, uint32_t w,
+                            const uint32_t* slots, uint32_t cap, uint32_t* cnt, uint64_t* missing, uint32_t* overrun) {
+    if (rows)
+        k_join_probe_rows<<<nblk(rows, 256), 256, 0, s>>>(tab, in, T, rows, w, slots, cap - 1, cnt,
+                                                           reinterpret_cast<unsigned long long*>(missing), overrun);
 }
 void launch_join_counts(hipStream_t s, const uint32_t* cnt, uint32_t* out, uint64_t T) {
     if (T) k_join_counts<<<nblk(T, 256), 256, 0, s>>>(cnt, out, T);

@@ -120,6 +120,9 @@ struct QuotPlan {
     uint32_t term_rot[QUOT_MAX_TERMS][QUOT_MAX_FACTORS];
     uint8_t in_row[POLY_MAX_ROWS], tab_row[POLY_MAX_ROWS];
     const uint8_t *theta_be32, *lbeta_be32;
+    // kzg_rows_commit_quotient_zk.  active != 0 (then ext != 0 too): P1 and LK1 are multiplied by row active_row, the caller's
+    // column A that is 1 on the usable rows and 0 elsewhere, and the third instantiation of the kernel runs
+    uint32_t active, active_row;
 };
 // the constants record of one (T, E), in 8-word elements: 1 / Z_H on the coset, 1 / T, g and the power tables of g and 1 / g
 uint64_t quot_consts_elems(int log_t, int ext_log);
@@ -127,7 +130,7 @@ uint64_t quot_consts_elems(int log_t, int ext_log);
 void launch_quot_consts(hipStream_t s, uint32_t* qc, int log_t, int ext_log, const uint32_t* tw_n);
 // ext[i] = g^i f[i] for i < T, 0 for T <= i < N (f: T Montgomery coefficients; null: the coefficients of L_0, all 1 / T)
 void launch_quot_extend(hipStream_t s, const uint32_t* f_or_null, uint32_t* ext, int log_t, int ext_log, const uint32_t* qc);
-// out[i] = (Gate + alpha P1 + alpha^2 P2 + alpha^3 LK1 + alpha^4 LK2)(x_i) / Z_H(x_i) over the rows' N coset evaluations
+// out[i] = (Gate + alpha [A] P1 + alpha^2 P2 + alpha^3 [A] LK1 + alpha^4 LK2)(x_i) / Z_H(x_i) over the rows' N coset evaluations
 // ext_rows.r[.] and L_0's l0 (unused when k == 0 and n_lookups == 0); out must not alias a row (z and S are read at i + E, a
 // rotated factor at i + rot E).  *bad raised for a scalar >= r
 void launch_quot_points(hipStream_t s, const RowTab& ext_rows, const uint32_t* l0, uint32_t* out, int log_t, const QuotPlan& qp,
@@ -162,3 +165,17 @@ void launch_join_probe(hipStream_t s, const uint32_t* tab, const uint32_t* in, u
                        uint32_t cap, uint32_t* cnt, uint64_t* missing, uint32_t* overrun);
 // out[t] <- cnt[t] as a canonical Montgomery element
 void launch_join_counts(hipStream_t s, const uint32_t* cnt, uint32_t* out, uint64_t T);
+// the same join over the first `rows` rows only (kzg_rows_commit_multiplicities_zk): the columns still lie T elements apart,
+// table rows and cells at or above `rows` are neither built nor probed nor counted as missing
+void launch_join_build_rows(hipStream_t s, const uint32_t* tab, uint64_t T, uint64_t rows, uint32_t w, uint32_t* slots,
+                            uint32_t cap, uint32_t* overrun);
+void launch_join_probe_rows(hipStream_t s, const uint32_t* tab, const uint32_t* in, uint64_t T, uint64_t rows, uint32_t w,
+                            const uint32_t* slots, uint32_t cap, uint32_t* cnt, uint64_t* missing, uint32_t* overrun);
+// ---- blinding rows (fr_blind.hip; the kzg_rows_commit_*_zk builders): rows [usable, n) of evaluation vectors of n Montgomery
+// elements, n - usable <= BLIND_MAX_ROWS (= KZG_MAX_BLIND_ROWS)
+#define BLIND_MAX_ROWS 32
+// a[t] <- 1 (a_one) or 0, b[t] <- 1 for usable <= t < n: the neutral operands of the product scan / the running fraction
+void launch_blind_mask(hipStream_t s, uint32_t* a, bool a_one, uint32_t* b, uint64_t n, uint64_t usable);
+// v[usable + 1 + j] <- tail[j], j < n - usable - 1; tail_be32: that many canonical scalars as 32 big-endian HOST bytes each (a
+// kernel argument; not read when usable = n - 1), *bad raised when one is >= r
+void launch_blind_tail(hipStream_t s, uint32_t* v, uint64_t n, uint64_t usable, const uint8_t* tail_be32, uint32_t* bad);

@@ -164,10 +164,22 @@ struct QuotArgX {
     uint32_t n_lookups, width, mult_row, sum_row;
 };
 static_assert(sizeof(QuotArgX) + sizeof(RowTab) + 64 <= 4096, "k_quot_points' arguments must fit in 4 KB");
-template <bool EXT> struct QuotArgOf { typedef QuotArg type; };
-template <> struct QuotArgOf<true> { typedef QuotArgX type; };
+// What kzg_rows_commit_quotient_zk adds: the row of the caller's fixed column A (1 on the usable rows, 0 elsewhere), a factor
+// of P1 and of LK1.  The third instantiation's own argument: the two others keep theirs.
+struct QuotArgA {
+    QuotArgX x;
+    uint32_t active_row;
+};
+static_assert(sizeof(QuotArgA) + sizeof(RowTab) + 64 <= 4096, "k_quot_points' arguments must fit in 4 KB");
+template <bool EXT, bool ACT> struct QuotArgOf { typedef QuotArg type; };
+template <> struct QuotArgOf<true, false> { typedef QuotArgX type; };
+template <> struct QuotArgOf<true, true> { typedef QuotArgA type; };
 KZG_DEV const QuotArg& quot_base(const QuotArg& a) { return a; }
 KZG_DEV const QuotArg& quot_base(const QuotArgX& a) { return a.q; }
+KZG_DEV const QuotArg& quot_base(const QuotArgA& a) { return a.x.q; }
+KZG_DEV const QuotArg& quot_ext(const QuotArg& a) { return a; }
+KZG_DEV const QuotArgX& quot_ext(const QuotArgX& a) { return a; }
+KZG_DEV const QuotArgX& quot_ext(const QuotArgA& a) { return a.x; }
 enum { QS_SHIFT = QUOT_MAX_TERMS, QS_BETA = QS_SHIFT + QUOT_MAX_WIRES, QS_GAMMA, QS_ALPHA, QS_ALPHA2, QS_COUNT,
        QX_THETA = QS_COUNT, QX_LBETA, QX_ALPHA3, QX_ALPHA4, QX_COUNT };   // (the QX_ slots: the second instantiation only)
 KZG_DEV void quot_arg(fr9_t& v, const FrArg& a, uint32_t* __restrict__ bad, bool check) {
@@ -206,12 +218,19 @@ KZG_DEV void quot_lk_den(fr9_t& d, const RowTab& rt, const uint8_t* rows, uint32
 // existed; EXT = true adds the rotations and the lookup part.  The lazy-sum bound with the lookup: at most 16 terms + alpha P1 +
 // alpha^2 P2 + alpha^3 LK1 + alpha^4 LK2, each a product's output below 2r and the sum renormalised after each, stay below 40r --
 // still under the 64r the closing product's first operand allows (its second one, 1 / Z_H, is canonical).
-template <bool EXT>
+// ACT = true (with EXT; kzg_rows_commit_quotient_zk) is the third instantiation: num = Gate + alpha A P1 + alpha^2 P2 + alpha^3 A
+// LK1 + alpha^4 LK2 with A the extended vector of the caller's active column.  A(x_i) is a canonical row value (the forward
+// transform ends in fr9_reduce): a legal SECOND operand.  P1 is below 6r and LK1 below 10r, legal FIRST operands as they are for
+// the products by alpha and alpha^3 that follow; A P1 and A LK1 come out below 2r, so those products and the lazy sum keep the
+// bounds above.  One more 32-byte load and two more products per point; the two other instantiations keep their instructions.
+template <bool EXT, bool ACT = false>
 __global__ void __launch_bounds__(256) k_quot_points(const RowTab rt, const uint32_t* __restrict__ l0, uint32_t* __restrict__ out,
-                                                      int log_n, const typename QuotArgOf<EXT>::type qx,
+                                                      int log_n, const typename QuotArgOf<EXT, ACT>::type qarg,
                                                       const uint32_t* __restrict__ tw, const uint32_t* __restrict__ qc,
                                                       uint32_t* __restrict__ bad) {
-    const QuotArg& qa = quot_base(qx);
+    static_assert(EXT || !ACT, "the active column comes with the extended argument");
+    const auto& qx = quot_ext(qarg);   // (the plain argument itself when !EXT: nothing of it is read through qx then)
+    const QuotArg& qa = quot_base(qarg);
     __shared__ uint32_t cst[EXT ? QX_COUNT : QS_COUNT][9];
     const uint32_t v = threadIdx.x;
     const bool chk = blockIdx.x == 0;
@@ -269,6 +288,10 @@ __global__ void __launch_bounds__(256) k_quot_points(const RowTab rt, const uint
     if (i >> log_n) return;
     const uint64_t n = (uint64_t)1 << log_n, half = n >> 1;
     fr9_t acc, p, c;
+    [[maybe_unused]] fr9_t act;
+    if constexpr (ACT) {
+        if (qa.k || qx.n_lookups) fr9_load(act, rt.r[qarg.active_row] + 8 * i);
+    }
     fr9_zero(acc);
     for (uint32_t u = 0; u < qa.n_terms; u++) {
         lds_get(p, cst, u);
@@ -312,6 +335,7 @@ __global__ void __launch_bounds__(256) k_quot_points(const RowTab rt, const uint
             fr9_mul(B, t, B);
         }
         fr9_sub4(A, A, B);                    // P1, < 6r
+        if constexpr (ACT) fr9_mul(A, A, act);   // A P1, < 2r
         lds_get(c, cst, QS_ALPHA);
         fr9_mul(t, A, c);
         fr9_add(acc, acc, t);
@@ -352,6 +376,7 @@ __global__ void __launch_bounds__(256) k_quot_points(const RowTab rt, const uint
             fr9_mul(t, t, Q);
             fr9_norm(P, P);                   // < 6r, normalised: what fr9_sub8 takes
             fr9_sub8(t, t, P);                // LK1, < 10r
+            if constexpr (ACT) fr9_mul(t, t, act);   // A LK1, < 2r
             lds_get(c, cst, QX_ALPHA3);
             fr9_mul(t, t, c);
             fr9_add(acc, acc, t);
@@ -372,9 +397,10 @@ __global__ void __launch_bounds__(256) k_quot_points(const RowTab rt, const uint
 }
 void launch_quot_points(hipStream_t s, const RowTab& ext_rows, const uint32_t* l0, uint32_t* out, int log_t, const QuotPlan& qp,
                         const uint32_t* tw_n, const uint32_t* qc, uint32_t* bad) {
-    QuotArgX qx;
+    QuotArgA qarg;
+    QuotArgX& qx = qarg.x;
     QuotArg& qa = qx.q;
-    memset(&qx, 0, sizeof(qx));
+    memset(&qarg, 0, sizeof(qarg));
     qa.n_terms = qp.n_terms;
     qa.k = qp.k;
     qa.z_row = qp.z_row;
@@ -412,7 +438,12 @@ void launch_quot_points(hipStream_t s, const RowTab& ext_rows, const uint32_t* l
         qx.mult_row = qp.mult_row;
         qx.sum_row = qp.sum_row;
     }
-    k_quot_points<true><<<g, 256, 0, s>>>(ext_rows, l0, out, log_n, qx, tw_n, qc, bad);
+    if (!qp.active) {
+        k_quot_points<true><<<g, 256, 0, s>>>(ext_rows, l0, out, log_n, qx, tw_n, qc, bad);
+        return;
+    }
+    qarg.active_row = qp.active_row;
+    k_quot_points<true, true><<<g, 256, 0, s>>>(ext_rows, l0, out, log_n, qarg, tw_n, qc, bad);
 }
 
 // ------------------------------------------------------------------------------------------------ back to the pieces

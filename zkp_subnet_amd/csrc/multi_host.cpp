@@ -48,6 +48,22 @@ int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, cons
 int rows_quotient_ext_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
                            const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
                            uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle, bool plain);
+int rows_grand_product_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                               uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
+                               const uint8_t* beta_be32, const uint8_t* gamma_be32, uint64_t usable, const uint8_t* tail_be32,
+                               uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle);
+int rows_lookup_sum_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                            uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
+                            uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint64_t usable,
+                            const uint8_t* tail_be32, uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle);
+int rows_multiplicities_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
+                                uint64_t usable, const uint8_t* tail_be32, uint8_t* out_commitment48, uint64_t* out_missing,
+                                uint64_t* out_handle);
+int rows_quotient_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                          const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
+                          const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,
+                          uint64_t* out_handle);
 }  // namespace kzg_impl
 
 namespace {
@@ -494,6 +510,51 @@ int kzg_multi_rows_commit_quotient_ext(kzg_multi* mh, uint32_t i, uint32_t n_han
     if (int rc = route(mh, i, &c, &s)) return rc;
     return relay(c, kzg_impl::rows_quotient_ext_impl(c, s, n_handles, handles, gate, perm, lookup, ext_log, n_pieces,
                                                      out_commitments48, out_handle, false));
+}
+int kzg_multi_rows_commit_grand_product_zk(kzg_multi* mh, uint32_t i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                           uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
+                                           const uint8_t* shifts_be32, const uint8_t beta_be32[32], const uint8_t gamma_be32[32],
+                                           uint64_t usable, const uint8_t* tail_be32, uint8_t out_commitment48[48],
+                                           uint8_t out_closing32[32], uint64_t* out_handle) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_grand_product_zk_impl(c, s, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k,
+                                                         shifts_be32, beta_be32, gamma_be32, usable, tail_be32, out_commitment48,
+                                                         out_closing32, out_handle));
+}
+int kzg_multi_rows_commit_lookup_sum_zk(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                        uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
+                                        uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32],
+                                        const uint8_t beta_be32[32], uint64_t usable, const uint8_t* tail_be32,
+                                        uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_lookup_sum_zk_impl(c, s, n_input_handles, input_handles, n_table_handles, table_handles,
+                                                      mult_handle, n_lookups, width, theta_be32, beta_be32, usable, tail_be32,
+                                                      out_commitment48, out_closing32, out_handle));
+}
+int kzg_multi_rows_commit_multiplicities_zk(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                            uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups,
+                                            uint32_t width, uint64_t usable, const uint8_t* tail_be32,
+                                            uint8_t out_commitment48[48], uint64_t* out_missing, uint64_t* out_handle) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_multiplicities_zk_impl(c, s, n_input_handles, input_handles, n_table_handles, table_handles,
+                                                          n_lookups, width, usable, tail_be32, out_commitment48, out_missing,
+                                                          out_handle));
+}
+int kzg_multi_rows_commit_quotient_zk(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                      const kzg_quotient_terms* gate, const kzg_quotient_perm* perm,
+                                      const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
+                                      uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_quotient_zk_impl(c, s, n_handles, handles, gate, perm, lookup, active, ext_log, n_pieces,
+                                                    out_commitments48, out_handle));
 }
 int kzg_multi_rows_release(kzg_multi* mh, uint32_t i, uint64_t handle) {
     kzg_ctx* c;

@@ -726,7 +726,7 @@ int rows_lincomb_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, ui
 // MSM commits.  The record's first two evaluation slots carry the closing value and the zero-denominator flag word.
 int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& wires, const RowTab& sigmas, uint32_t k,
                            uint64_t T, const uint8_t* shifts_be32, const uint8_t* beta_be32, const uint8_t* gamma_be32,
-                           uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den) {
+                           uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den, const Blind* zk) {
     Lane& A = H.L();
     if (int rc = ensure_multi_record(ctx, A)) return rc;
     const int lg = ilog2_exact(T);
@@ -754,8 +754,12 @@ int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& 
     }
     {
         Span sp(ctx, A, KZG_T_POLY);
+        // _zk: N_t = D_t = 1 on the rows >= usable (whatever their cells hold, a zero D_t included), so the unchanged scan
+        // leaves z = closing on every one of them; the tail then replaces the rows behind row `usable`
+        if (zk) launch_blind_mask(A.stream, N, true, D, T, zk->usable);
         launch_gp_scan(A.stream, N, D, T, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), rec + MR_EVAL,
                        reinterpret_cast<uint32_t*>(rec + MR_EVAL + 32));
+        if (zk) launch_blind_tail(A.stream, N, T, zk->usable, zk->tail_be32, A.flags());
     }
     const uint32_t* c;
     if (int rc = row_to_coeffs(ctx, A, N, T, 1, &c, dst)) return rc;
@@ -778,7 +782,7 @@ int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& 
 // closing value and the zero-denominator flag word.
 int rows_lookup_sum_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& table, const uint32_t* mult,
                         uint32_t n_lookups, uint32_t width, uint64_t T, const uint8_t* theta_be32, const uint8_t* beta_be32,
-                        uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den) {
+                        uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den, const Blind* zk) {
     Lane& A = H.L();
     if (int rc = ensure_multi_record(ctx, A)) return rc;
     const int lg = ilog2_exact(T);
@@ -812,8 +816,12 @@ int rows_lookup_sum_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inp
     {
         Span sp(ctx, A, KZG_T_POLY);
         uint32_t* zf = reinterpret_cast<uint32_t*>(rec + MR_EVAL + 32);
+        // _zk: term_t = 0 / 1 on the rows >= usable, set in front of the inversion so that a zero denominator there cannot
+        // poison prod Q; the unchanged scan leaves S = closing on every one of them, the tail replaces the rows behind `usable`
+        if (zk) launch_blind_mask(A.stream, P, false, Q, T, zk->usable);
         launch_fr_batch_inv(A.stream, Q, e, P, P, T, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), rec + MR_EVAL, zf);
         launch_lk_sum_scan(A.stream, P, T, A.hbuf.as<uint32_t>(), rec + MR_EVAL);
+        if (zk) launch_blind_tail(A.stream, P, T, zk->usable, zk->tail_be32, A.flags());
     }
     const uint32_t* c;
     if (int rc = row_to_coeffs(ctx, A, P, T, 1, &c, dst)) return rc;
@@ -836,7 +844,7 @@ int rows_lookup_sum_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inp
 // `missing` (8 bytes) and the overrun flag word behind it.
 int rows_multiplicities_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& table, uint32_t n_lookups,
                             uint32_t width, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_missing,
-                            bool* out_overrun) {
+                            bool* out_overrun, const Blind* zk) {
     Lane& A = H.L();
     if (int rc = ensure_multi_record(ctx, A)) return rc;
     const int lg = ilog2_exact(T);
@@ -861,7 +869,9 @@ int rows_multiplicities_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab&
         HIPCHK(ctx, hipMemsetAsync(slots, 0xff, (size_t)cap * 4, A.stream));
         HIPCHK(ctx, hipMemsetAsync(cnt, 0, (size_t)T * 4, A.stream));
         HIPCHK(ctx, hipMemsetAsync(rec + MR_EVAL, 0, 32, A.stream));
-        launch_join_build(A.stream, tab, T, width, slots, cap, overrun);
+        // _zk: only the table rows and the cells below `usable` enter the join; the counters of the rows behind stay 0
+        if (zk) launch_join_build_rows(A.stream, tab, T, zk->usable, width, slots, cap, overrun);
+        else launch_join_build(A.stream, tab, T, width, slots, cap, overrun);
     }
     for (uint32_t l = 0; l < n_lookups; l++) {
         for (uint32_t c = 0; c < width; c++) {
@@ -869,11 +879,13 @@ int rows_multiplicities_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab&
             launch_fr_ntt(A.stream, inputs.r[l * width + c], in + c * vw, lg, tw, nullptr, mid);
         }
         Span sp(ctx, A, KZG_T_POLY);
-        launch_join_probe(A.stream, tab, in, T, width, slots, cap, cnt, missing, overrun);
+        if (zk) launch_join_probe_rows(A.stream, tab, in, T, zk->usable, width, slots, cap, cnt, missing, overrun);
+        else launch_join_probe(A.stream, tab, in, T, width, slots, cap, cnt, missing, overrun);
     }
     {
         Span sp(ctx, A, KZG_T_POLY);
         launch_join_counts(A.stream, cnt, in, T);
+        if (zk) launch_blind_tail(A.stream, in, T, zk->usable, zk->tail_be32, A.flags());
     }
     const uint32_t* c;
     if (int rc = row_to_coeffs(ctx, A, in, T, 1, &c, dst)) return rc;
@@ -930,6 +942,7 @@ int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, u
     for (uint32_t j = 0; j < qp.n_lookups * qp.width; j++) used[qp.in_row[j]] = true;
     for (uint32_t j = 0; qp.n_lookups && j < qp.width; j++) used[qp.tab_row[j]] = true;
     if (qp.n_lookups) used[qp.mult_row] = used[qp.sum_row] = true;
+    if (qp.active && (qp.k || qp.n_lookups)) used[qp.active_row] = true;   // A: one more distinct row (a factor of P1 and LK1)
     const bool need_l0 = qp.k || qp.n_lookups;   // P2 and LK2
     int slot[POLY_MAX_ROWS];
     uint32_t nd = 0;

@@ -837,11 +837,26 @@ int rows_lincomb_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const
     return rows_lincomb_dev(ctx, H, i, rt, k, T, m, points_be32, coeffs_be32, masks, out_values32, out_proofs48);
 }
 
-// kzg_rows_commit_grand_product: the lookups of an open (two handle lists), the reservation of a commit
-int rows_grand_product_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
-                            uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
-                            const uint8_t* beta_be32, const uint8_t* gamma_be32, uint8_t* out_commitment48,
-                            uint8_t* out_closing32, uint64_t* out_handle) {
+// the blinding rows of a _zk builder against the row length, once that is known: 1 <= usable <= T - 1, at most
+// KZG_MAX_BLIND_ROWS rows from `usable` on, T - usable - 1 canonical tail scalars (none: the pointer may be null)
+static_assert(KZG_MAX_BLIND_ROWS == BLIND_MAX_ROWS, "the header's cap is the kernels' cap");
+static int blind_check(kzg_ctx* ctx, const char* what, uint64_t T, const Blind& zk) {
+    auto bad = [&](const char* why) { return fail(ctx, KZG_E_ARG, std::string(what) + why); };
+    if (zk.usable == 0 || zk.usable >= T) return bad(": usable must be in [1, T - 1]");
+    if (T - zk.usable > KZG_MAX_BLIND_ROWS) return bad(": at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
+    const uint64_t n_tail = T - zk.usable - 1;
+    if (n_tail && !zk.tail_be32) return bad(": tail_be32 may be null only when usable = T - 1");
+    for (uint64_t j = 0; j < n_tail; j++)
+        if (!fr_be32_canonical(zk.tail_be32 + 32 * (size_t)j)) return bad(": tail scalars must be canonical (< r)");
+    return KZG_OK;
+}
+
+// kzg_rows_commit_grand_product: the lookups of an open (two handle lists), the reservation of a commit.  zk: the blinding
+// rows of kzg_rows_commit_grand_product_zk (null: the plain call)
+static int rows_grand_product_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                  uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
+                                  const uint8_t* shifts_be32, const uint8_t* beta_be32, const uint8_t* gamma_be32,
+                                  uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle, const Blind* zk) {
     if (!ctx || !wire_handles || !sigma_handles || !shifts_be32 || !beta_be32 || !gamma_be32 || !out_commitment48 ||
         !out_closing32 || !out_handle)
         return KZG_E_ARG;
@@ -871,6 +886,8 @@ int rows_grand_product_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_han
     int rc = check_worker(ctx, i, T);
     if (rc) return rc;
     if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "grand product: the row length must be a power of two");
+    if (zk)
+        if (int rcz = blind_check(ctx, "grand product", T, *zk)) return rcz;
     if (int rc2 = rows_reserve(ctx, "grand product", pend, (size_t)T * 32)) return rc2;
     prof_begin(ctx, L);
     rc = clear_flags(ctx, L);
@@ -878,22 +895,40 @@ int rows_grand_product_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_han
     bool zero_den = false;
     uint8_t c48[48], closing[32];
     rc = rows_grand_product_dev(ctx, H, i, wt, st, k, T, shifts_be32, beta_be32, gamma_be32, pend.buf.as<uint32_t>(), c48, closing,
-                                &zero_den);
+                                &zero_den, zk);
     if (rc) return rc;
     if (zero_den)
-        return fail(ctx, KZG_E_ARG, "grand product: zero denominator (some a_j + beta sigma_j + gamma vanishes on the domain): "
-                                    "z is undefined, no set was created");
+        return fail(ctx, KZG_E_ARG, zk ? "grand product: zero denominator (some a_j + beta sigma_j + gamma vanishes on a usable "
+                                         "row): z is undefined, no set was created"
+                                       : "grand product: zero denominator (some a_j + beta sigma_j + gamma vanishes on the domain): "
+                                         "z is undefined, no set was created");
     memcpy(out_commitment48, c48, 48);
     memcpy(out_closing32, closing, 32);
     *out_handle = rows_insert(ctx, pend, i, 1, T);
     return KZG_OK;
 }
+int rows_grand_product_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                            uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
+                            const uint8_t* beta_be32, const uint8_t* gamma_be32, uint8_t* out_commitment48,
+                            uint8_t* out_closing32, uint64_t* out_handle) {
+    return rows_grand_product_any(ctx, expect_i, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
+                                  beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle, nullptr);
+}
+int rows_grand_product_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                               uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
+                               const uint8_t* beta_be32, const uint8_t* gamma_be32, uint64_t usable, const uint8_t* tail_be32,
+                               uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle) {
+    const Blind zk = {usable, tail_be32};
+    return rows_grand_product_any(ctx, expect_i, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
+                                  beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle, &zk);
+}
 
-// kzg_rows_commit_lookup_sum: the lookups of an open (three handle lists), the reservation of a commit
-int rows_lookup_sum_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                         uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
-                         uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint8_t* out_commitment48,
-                         uint8_t* out_closing32, uint64_t* out_handle) {
+// kzg_rows_commit_lookup_sum: the lookups of an open (three handle lists), the reservation of a commit.  zk: the blinding
+// rows of kzg_rows_commit_lookup_sum_zk (null: the plain call)
+static int rows_lookup_sum_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                               uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
+                               uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint8_t* out_commitment48,
+                               uint8_t* out_closing32, uint64_t* out_handle, const Blind* zk) {
     if (!ctx || !input_handles || !table_handles || !theta_be32 || !beta_be32 || !out_commitment48 || !out_closing32 ||
         !out_handle)
         return KZG_E_ARG;
@@ -925,6 +960,8 @@ int rows_lookup_sum_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handl
     int rc = check_worker(ctx, i, T);
     if (rc) return rc;
     if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "lookup sum: the row length must be a power of two");
+    if (zk)
+        if (int rcz = blind_check(ctx, "lookup sum", T, *zk)) return rcz;
     if (int rc2 = rows_reserve(ctx, "lookup sum", pend, (size_t)T * 32)) return rc2;
     prof_begin(ctx, L);
     rc = clear_flags(ctx, L);
@@ -932,21 +969,39 @@ int rows_lookup_sum_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handl
     bool zero_den = false;
     uint8_t c48[48], closing[32];
     rc = rows_lookup_sum_dev(ctx, H, i, it, tt, mt.r[0], n_lookups, width, T, theta_be32, beta_be32, pend.buf.as<uint32_t>(), c48,
-                             closing, &zero_den);
+                             closing, &zero_den, zk);
     if (rc) return rc;
     if (zero_den)
-        return fail(ctx, KZG_E_ARG, "lookup sum: zero denominator (some beta + F_l or beta + Tb vanishes on the domain): "
-                                    "S is undefined, no set was created");
+        return fail(ctx, KZG_E_ARG, zk ? "lookup sum: zero denominator (some beta + F_l or beta + Tb vanishes on a usable row): "
+                                         "S is undefined, no set was created"
+                                       : "lookup sum: zero denominator (some beta + F_l or beta + Tb vanishes on the domain): "
+                                         "S is undefined, no set was created");
     memcpy(out_commitment48, c48, 48);
     memcpy(out_closing32, closing, 32);
     *out_handle = rows_insert(ctx, pend, i, 1, T);
     return KZG_OK;
 }
+int rows_lookup_sum_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                         uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
+                         uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint8_t* out_commitment48,
+                         uint8_t* out_closing32, uint64_t* out_handle) {
+    return rows_lookup_sum_any(ctx, expect_i, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
+                               n_lookups, width, theta_be32, beta_be32, out_commitment48, out_closing32, out_handle, nullptr);
+}
+int rows_lookup_sum_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                            uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
+                            uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint64_t usable,
+                            const uint8_t* tail_be32, uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle) {
+    const Blind zk = {usable, tail_be32};
+    return rows_lookup_sum_any(ctx, expect_i, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
+                               n_lookups, width, theta_be32, beta_be32, out_commitment48, out_closing32, out_handle, &zk);
+}
 
-// kzg_rows_commit_multiplicities: the lookups of an open (two handle lists), the reservation of a commit
-int rows_multiplicities_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                             uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
-                             uint8_t* out_commitment48, uint64_t* out_missing, uint64_t* out_handle) {
+// kzg_rows_commit_multiplicities: the lookups of an open (two handle lists), the reservation of a commit.  zk: the blinding
+// rows of kzg_rows_commit_multiplicities_zk (null: the plain call)
+static int rows_multiplicities_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                   uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
+                                   uint8_t* out_commitment48, uint64_t* out_missing, uint64_t* out_handle, const Blind* zk) {
     if (!ctx || !input_handles || !table_handles || !out_commitment48 || !out_missing || !out_handle) return KZG_E_ARG;
     if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN || n_table_handles == 0 || n_table_handles > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "multiplicities: the number of handles in each list must be in [1, KZG_MAX_BATCH_OPEN]");
@@ -974,6 +1029,8 @@ int rows_multiplicities_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_h
     if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "multiplicities: the row length must be a power of two");
     if (T > ((uint64_t)1 << 27))   // L T additions fit a u32 counter, 2 T slots a u32 index
         return fail(ctx, KZG_E_ARG, "multiplicities: the row length must be at most 2^27");
+    if (zk)
+        if (int rcz = blind_check(ctx, "multiplicities", T, *zk)) return rcz;
     if (int rc2 = rows_reserve(ctx, "multiplicities", pend, (size_t)T * 32)) return rc2;
     prof_begin(ctx, L);
     rc = clear_flags(ctx, L);
@@ -981,7 +1038,7 @@ int rows_multiplicities_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_h
     bool overrun = false;
     uint8_t c48[48];
     uint64_t missing = 0;
-    rc = rows_multiplicities_dev(ctx, H, i, it, tt, n_lookups, width, T, pend.buf.as<uint32_t>(), c48, &missing, &overrun);
+    rc = rows_multiplicities_dev(ctx, H, i, it, tt, n_lookups, width, T, pend.buf.as<uint32_t>(), c48, &missing, &overrun, zk);
     if (rc) return rc;
     if (overrun)
         return fail(ctx, KZG_E_HIP, "multiplicities: a probe walk of the hash join reached its bound (the slot table held no "
@@ -991,12 +1048,28 @@ int rows_multiplicities_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_h
     *out_handle = rows_insert(ctx, pend, i, 1, T);
     return KZG_OK;
 }
+int rows_multiplicities_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                             uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
+                             uint8_t* out_commitment48, uint64_t* out_missing, uint64_t* out_handle) {
+    return rows_multiplicities_any(ctx, expect_i, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups,
+                                   width, out_commitment48, out_missing, out_handle, nullptr);
+}
+int rows_multiplicities_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
+                                uint64_t usable, const uint8_t* tail_be32, uint8_t* out_commitment48, uint64_t* out_missing,
+                                uint64_t* out_handle) {
+    const Blind zk = {usable, tail_be32};
+    return rows_multiplicities_any(ctx, expect_i, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups,
+                                   width, out_commitment48, out_missing, out_handle, &zk);
+}
 
 // kzg_rows_commit_quotient_ext (and, with no rotation and no lookup part, kzg_rows_commit_quotient: `plain`, which only words
 // one message): the lookups of an open (one handle list), the reservation of a commit
-int rows_quotient_ext_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
-                           uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle, bool plain) {
+// active: the caller's column A of kzg_rows_commit_quotient_zk, a factor of P1 and LK1 (null: neither has it)
+static int rows_quotient_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                             const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
+                             const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces,
+                             uint8_t* out_commitments48, uint64_t* out_handle, bool plain) {
     if (!ctx || !handles || !gate || !out_commitments48 || !out_handle) return KZG_E_ARG;
     const uint32_t k = perm ? perm->k : 0;
     if (gate->n_terms && (!gate->coeffs_be32 || !gate->term_lens || !gate->term_rows)) return KZG_E_ARG;
@@ -1012,6 +1085,9 @@ int rows_quotient_ext_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, 
     if (n_pieces == 0 || n_pieces > E) return fail(ctx, KZG_E_ARG, "quotient: n_pieces must be in [1, 2^ext_log]");
     if (gate->n_terms > KZG_MAX_GATE_TERMS) return fail(ctx, KZG_E_ARG, "quotient: more than KZG_MAX_GATE_TERMS gate terms");
     if (k > E) return fail(ctx, KZG_E_ARG, "quotient: the permutation part has k + 1 factors: k must not exceed 2^ext_log");
+    if (active && k > E - 1)
+        return fail(ctx, KZG_E_ARG, "quotient: with an active column the permutation part has k + 2 factors: k must not exceed "
+                                    "2^ext_log - 1");
     if (gate->n_terms == 0 && k == 0 && !lookup)
         return fail(ctx, KZG_E_ARG, plain ? "quotient: no gate term and no permutation part"
                                           : "quotient: no gate term, no permutation part and no lookup part");
@@ -1023,6 +1099,9 @@ int rows_quotient_ext_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, 
         if (L > E - 1)
             return fail(ctx, KZG_E_ARG, "quotient: the lookup part has n_lookups + 2 factors: n_lookups must not exceed "
                                         "2^ext_log - 1");
+        if (active && L > E - 2)
+            return fail(ctx, KZG_E_ARG, "quotient: with an active column the lookup part has n_lookups + 3 factors: n_lookups "
+                                        "must not exceed 2^ext_log - 2");
         if (!fr_be32_canonical(lookup->theta_be32) || !fr_be32_canonical(lookup->beta_be32) ||
             !fr_be32_canonical(lookup->alpha_be32))
             return fail(ctx, KZG_E_ARG, "quotient: the lookup part's theta, beta and alpha must be canonical scalars (< r)");
@@ -1081,6 +1160,10 @@ int rows_quotient_ext_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, 
         qp.lbeta_be32 = lookup->beta_be32;
         qp.alpha_be32 = lookup->alpha_be32;
     }
+    if (active) {
+        qp.ext = qp.active = 1;
+        qp.active_row = name_row(active->active_row);
+    }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     RowsPending pend{ctx};
     RowsRefs refs{ctx};
@@ -1112,6 +1195,20 @@ int rows_quotient_ext_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, 
     memcpy(out_commitments48, c48, 48 * (size_t)n_pieces);
     *out_handle = rows_insert(ctx, pend, i, n_pieces, T);
     return KZG_OK;
+}
+int rows_quotient_ext_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
+                           uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle, bool plain) {
+    return rows_quotient_any(ctx, expect_i, n_handles, handles, gate, perm, lookup, nullptr, ext_log, n_pieces, out_commitments48,
+                             out_handle, plain);
+}
+// kzg_rows_commit_quotient_zk: active == NULL is kzg_rows_commit_quotient_ext
+int rows_quotient_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                          const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
+                          const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,
+                          uint64_t* out_handle) {
+    return rows_quotient_any(ctx, expect_i, n_handles, handles, gate, perm, lookup, active, ext_log, n_pieces, out_commitments48,
+                             out_handle, false);
 }
 
 // kzg_rows_commit_quotient: the same with every rotation 0 and no lookup part
@@ -1218,6 +1315,37 @@ int kzg_rows_commit_quotient_ext(kzg_ctx* ctx, uint32_t n_handles, const uint64_
                                  uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle) {
     return rows_quotient_ext_impl(ctx, UINT32_MAX, n_handles, handles, gate, perm, lookup, ext_log, n_pieces, out_commitments48,
                                   out_handle, false);
+}
+int kzg_rows_commit_grand_product_zk(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                     uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
+                                     const uint8_t* shifts_be32, const uint8_t beta_be32[32], const uint8_t gamma_be32[32],
+                                     uint64_t usable, const uint8_t* tail_be32, uint8_t out_commitment48[48],
+                                     uint8_t out_closing32[32], uint64_t* out_handle) {
+    return rows_grand_product_zk_impl(ctx, UINT32_MAX, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
+                                      beta_be32, gamma_be32, usable, tail_be32, out_commitment48, out_closing32, out_handle);
+}
+int kzg_rows_commit_lookup_sum_zk(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_table_handles,
+                                  const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups, uint32_t width,
+                                  const uint8_t theta_be32[32], const uint8_t beta_be32[32], uint64_t usable,
+                                  const uint8_t* tail_be32, uint8_t out_commitment48[48], uint8_t out_closing32[32],
+                                  uint64_t* out_handle) {
+    return rows_lookup_sum_zk_impl(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
+                                   n_lookups, width, theta_be32, beta_be32, usable, tail_be32, out_commitment48, out_closing32,
+                                   out_handle);
+}
+int kzg_rows_commit_multiplicities_zk(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                                      uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
+                                      uint64_t usable, const uint8_t* tail_be32, uint8_t out_commitment48[48],
+                                      uint64_t* out_missing, uint64_t* out_handle) {
+    return rows_multiplicities_zk_impl(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups,
+                                       width, usable, tail_be32, out_commitment48, out_missing, out_handle);
+}
+int kzg_rows_commit_quotient_zk(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
+                                const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
+                                const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces,
+                                uint8_t* out_commitments48, uint64_t* out_handle) {
+    return rows_quotient_zk_impl(ctx, UINT32_MAX, n_handles, handles, gate, perm, lookup, active, ext_log, n_pieces,
+                                 out_commitments48, out_handle);
 }
 int kzg_rows_release(kzg_ctx* ctx, uint64_t handle) { return rows_release_impl(ctx, UINT32_MAX, handle); }
 int kzg_rows_stats(kzg_ctx* ctx, uint64_t out_live_sets_bytes[2]) {

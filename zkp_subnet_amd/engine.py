@@ -48,6 +48,7 @@ class HipEngine:
         self.device = device
         self.scale = self.machines_scale = 0
         self.verifier = None          # host-side pairing verifier (zkp_subnet_amd.verifier.Verifier)
+        self._set_len: Dict[int, Tuple[int, int]] = {}   # handle -> (worker, row length) of the live sets made through RowSet
         if window:
             self._chk(self._lib.kzg_set_window(self._h, window))
 
@@ -426,6 +427,74 @@ class HipEngine:
         src = next((x for x in list(input_sets) + list(table_sets) if hasattr(x, "T")), None)
         return RowSet(self, h.value, getattr(src, "i", None), 1, getattr(src, "T", None), [c.raw]), int(miss.value)
 
+    # ---- the three builders above with blinding rows (kzg_rows_commit_*_zk): rows [0, usable) carry the circuit, row `usable`
+    # closes the running value, the rows behind take the caller's random tail (T - usable - 1 scalars of 32 bytes)
+    def _blind_args(self, what: str, sets, usable: int, tail_be32: Sequence[bytes]):
+        """(usable, the tail's bytes or None, worker, T).  The native call reads T - usable - 1 scalars, so the tail's length
+        is checked here against the row length, which a RowSet carries and the engine remembers for a bare handle."""
+        src = next((x for x in sets if getattr(x, "T", None) is not None), None)
+        i, T = (src.i, src.T) if src is not None else next(
+            (self._set_len[int(x)] for x in sets if not hasattr(x, "handle") and int(x) in self._set_len), (None, None))
+        tail = [bytes(x) for x in (tail_be32 or [])]
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: {why}")   # noqa: E731
+        if T is None:
+            raise bad("the row length of the sets is unknown to this engine (they were not committed through it)")
+        if not isinstance(usable, int) or not 0 <= usable < 1 << 64 or any(len(x) != 32 for x in tail):
+            raise bad("usable must be a non-negative integer and the tail scalars of 32 bytes each")
+        if 1 <= usable < T and T - usable <= _native.KZG_MAX_BLIND_ROWS and len(tail) != T - usable - 1:
+            raise bad(f"the tail must hold exactly T - usable - 1 = {T - usable - 1} scalars, not {len(tail)}")
+        return usable, (b"".join(tail) if tail else None), i, T
+
+    def commit_grand_product_zk(self, wire_sets: Sequence[object], sigma_sets: Sequence[object], shifts_be32: Sequence[bytes],
+                                beta_be32: bytes, gamma_be32: bytes, usable: int,
+                                tail_be32: Sequence[bytes] = ()) -> Tuple["RowSet", bytes]:
+        """commit_grand_product over the first `usable` rows (kzg_rows_commit_grand_product_zk): z(w^usable) is the closing
+        value (1 when the permutation holds on the usable rows), rows usable + 1 .. T - 1 of z are tail_be32.  """
+        nw, hw = self._handle_array(wire_sets, "commit_grand_product_zk (wires)")
+        ns, hs = self._handle_array(sigma_sets, "commit_grand_product_zk (sigmas)")
+        k = len(shifts_be32)
+        if k == 0 or k > _native.KZG_MAX_BATCH_OPEN or any(len(x) != 32 for x in list(shifts_be32) + [beta_be32, gamma_be32]):
+            raise KzgError(_native.KZG_E_ARG, f"commit_grand_product_zk: 1 .. {_native.KZG_MAX_BATCH_OPEN} shifts, beta and "
+                                              "gamma of 32 bytes each")
+        usable, tail, wi, T = self._blind_args("commit_grand_product_zk", list(wire_sets) + list(sigma_sets), usable, tail_be32)
+        c, cl, h = ctypes.create_string_buffer(48), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_grand_product_zk(self._h, nw, hw, ns, hs, k, b"".join(shifts_be32), beta_be32,
+                                                             gamma_be32, usable, tail, c, cl, ctypes.byref(h)))
+        return RowSet(self, h.value, wi, 1, T, [c.raw]), cl.raw
+
+    def commit_lookup_sum_zk(self, input_sets: Sequence[object], table_sets: Sequence[object], mult_set: object, n_lookups: int,
+                             width: int, theta_be32: bytes, beta_be32: bytes, usable: int,
+                             tail_be32: Sequence[bytes] = ()) -> Tuple["RowSet", bytes]:
+        """commit_lookup_sum over the first `usable` rows (kzg_rows_commit_lookup_sum_zk): S(w^usable) is the closing value
+        (0 when the sum closes on the usable rows), rows usable + 1 .. T - 1 of S are tail_be32."""
+        ni, hi = self._handle_array(input_sets, "commit_lookup_sum_zk (inputs)")
+        nt, ht = self._handle_array(table_sets, "commit_lookup_sum_zk (table)")
+        _, hm = self._handle_array([mult_set], "commit_lookup_sum_zk (multiplicities)")
+        if n_lookups < 1 or width < 1 or n_lookups * width > _native.KZG_MAX_BATCH_OPEN or len(theta_be32) != 32 \
+                or len(beta_be32) != 32:
+            raise KzgError(_native.KZG_E_ARG, f"commit_lookup_sum_zk: n_lookups, width >= 1, n_lookups * width <= "
+                                              f"{_native.KZG_MAX_BATCH_OPEN}, theta and beta of 32 bytes each")
+        usable, tail, wi, T = self._blind_args("commit_lookup_sum_zk", list(input_sets) + list(table_sets) + [mult_set], usable, tail_be32)
+        c, cl, h = ctypes.create_string_buffer(48), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_lookup_sum_zk(self._h, ni, hi, nt, ht, hm[0], n_lookups, width, theta_be32, beta_be32,
+                                                          usable, tail, c, cl, ctypes.byref(h)))
+        return RowSet(self, h.value, wi, 1, T, [c.raw]), cl.raw
+
+    def commit_multiplicities_zk(self, input_sets: Sequence[object], table_sets: Sequence[object], n_lookups: int, width: int,
+                                 usable: int, tail_be32: Sequence[bytes] = ()) -> Tuple["RowSet", int]:
+        """commit_multiplicities over the first `usable` table rows and input cells (kzg_rows_commit_multiplicities_zk):
+        m(w^usable) = 0, rows usable + 1 .. T - 1 of m are tail_be32; missing counts usable cells only."""
+        ni, hi = self._handle_array(input_sets, "commit_multiplicities_zk (inputs)")
+        nt, ht = self._handle_array(table_sets, "commit_multiplicities_zk (table)")
+        if n_lookups < 1 or width < 1 or n_lookups * width > _native.KZG_MAX_BATCH_OPEN:
+            raise KzgError(_native.KZG_E_ARG, f"commit_multiplicities_zk: n_lookups, width >= 1, n_lookups * width <= "
+                                              f"{_native.KZG_MAX_BATCH_OPEN}")
+        usable, tail, wi, T = self._blind_args("commit_multiplicities_zk", list(input_sets) + list(table_sets), usable, tail_be32)
+        c, miss, h = ctypes.create_string_buffer(48), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_multiplicities_zk(self._h, ni, hi, nt, ht, n_lookups, width, usable, tail, c,
+                                                              ctypes.byref(miss), ctypes.byref(h)))
+        return RowSet(self, h.value, wi, 1, T, [c.raw]), int(miss.value)
+
     # ---- a third set built from sets: the PLONK quotient (round 3), computed and committed on the device
     def commit_quotient(self, sets: Sequence[object], terms: Sequence[Tuple[bytes, Sequence[int]]], perm: Optional[dict] = None,
                         ext_log: int = 2, n_pieces: int = 3) -> "RowSet":
@@ -490,8 +559,22 @@ class HipEngine:
         lookup-major), "table" (width row indices), "mult", "sum" (row indices of m and S), "width", and "theta", "beta",
         "alpha" (32 bytes each; theta and beta those S was built with, alpha the one of perm).  n_lookups <= 2^ext_log - 1.
         alpha must be drawn after the commitments of S and z are fixed."""
-        n, hs = self._handle_array(sets, "commit_quotient_ext")
-        bad = lambda why: KzgError(_native.KZG_E_ARG, "commit_quotient_ext: " + why)   # noqa: E731
+        return self._commit_quotient_ext("commit_quotient_ext", sets, terms, perm, lookup, None, ext_log, n_pieces)
+
+    def commit_quotient_zk(self, sets: Sequence[object], terms: Sequence[Tuple[bytes, Sequence[object]]],
+                           perm: Optional[dict] = None, lookup: Optional[dict] = None, active_row: Optional[int] = None,
+                           ext_log: int = 2, n_pieces: int = 3) -> "RowSet":
+        """commit_quotient_ext with the caller's active column (kzg_rows_commit_quotient_zk): row active_row of the
+        concatenation, 1 on the usable rows and 0 elsewhere, multiplies P1 and LK1, so that neither binds the blinding rows.
+        The permutation part then takes at most 2^ext_log - 1 wires and the lookup part at most 2^ext_log - 2 lookups.
+        active_row = None is commit_quotient_ext."""
+        return self._commit_quotient_ext("commit_quotient_zk", sets, terms, perm, lookup, active_row, ext_log, n_pieces)
+
+    def _commit_quotient_ext(self, what, sets, terms, perm, lookup, active_row, ext_log, n_pieces) -> "RowSet":
+        n, hs = self._handle_array(sets, what)
+        bad = lambda why: KzgError(_native.KZG_E_ARG, what + ": " + why)   # noqa: E731
+        if active_row is not None and (not isinstance(active_row, int) or not 0 <= active_row < 1 << 32):
+            raise bad("active_row must be a non-negative integer below 2^32")
         if ext_log not in (1, 2, 3) or not 1 <= n_pieces <= 1 << ext_log:
             raise bad("ext_log must be 1, 2 or 3 and n_pieces in [1, 2^ext_log]")
         E = 1 << ext_log
@@ -554,10 +637,15 @@ class HipEngine:
         rots_arr = (ctypes.c_int32 * max(len(flat), 1))(*[rot for _, rot in flat])
         gate = _native.QuotientTerms(len(tt), b"".join(c for c, _ in tt), lens, rows_arr, rots_arr)
         c, h = ctypes.create_string_buffer(48 * n_pieces), ctypes.c_uint64(0)
-        self._chk(self._lib.kzg_rows_commit_quotient_ext(self._h, n, hs, ctypes.byref(gate),
-                                                         ctypes.byref(pm) if pm is not None else None,
-                                                         ctypes.byref(lk) if lk is not None else None, ext_log, n_pieces, c,
-                                                         ctypes.byref(h)))
+        pm_ref = ctypes.byref(pm) if pm is not None else None
+        lk_ref = ctypes.byref(lk) if lk is not None else None
+        if active_row is None:
+            self._chk(self._lib.kzg_rows_commit_quotient_ext(self._h, n, hs, ctypes.byref(gate), pm_ref, lk_ref, ext_log,
+                                                             n_pieces, c, ctypes.byref(h)))
+        else:
+            act = _native.QuotientActive(active_row)
+            self._chk(self._lib.kzg_rows_commit_quotient_zk(self._h, n, hs, ctypes.byref(gate), pm_ref, lk_ref, ctypes.byref(act),
+                                                            ext_log, n_pieces, c, ctypes.byref(h)))
         src = next((x for x in sets if hasattr(x, "T")), None)
         return RowSet(self, h.value, getattr(src, "i", None), n_pieces, getattr(src, "T", None),
                       [c.raw[48 * p:48 * p + 48] for p in range(n_pieces)])
@@ -579,6 +667,7 @@ class HipEngine:
     def release_rows(self, handle: int) -> None:
         """Frees a committed set (kzg_rows_release); KzgError(KZG_E_ARG) for an unknown or already released handle."""
         self._chk(self._lib.kzg_rows_release(self._h, int(handle)))
+        self._set_len.pop(int(handle), None)
 
     def rows_stats(self) -> Tuple[int, int]:
         """(live committed sets, device bytes their rows hold)."""
@@ -932,6 +1021,8 @@ class RowSet:
 
     def __init__(self, engine, handle: int, i: int, k: int, T: int, commitments: List[bytes]):
         self.engine, self.handle, self.i, self.k, self.T = engine, handle, i, k, T
+        if T is not None and hasattr(engine, "_set_len"):
+            engine._set_len[int(handle)] = (i, T)   # what a _zk builder needs when it is handed the bare handle
         self.commitments = commitments
         self.released = False
 

@@ -193,6 +193,39 @@ class MultiDeviceClient:
             self._row_owner[int(r.json()["handle"])] = i
         return r
 
+    # the builders with blinding rows: routed like the plain ones
+    def _routed_builder(self, name: str, handles, *args):
+        try:
+            i = self._owner(list(handles))
+        except TypeError:
+            i = None
+        if i is None:
+            return Response(400, {"error": f"{name}: the handles must name live sets of one worker"})
+        r = getattr(self._for(i), name)(*args)
+        if r.status_code == 200:
+            self._row_owner[int(r.json()["handle"])] = i
+        return r
+
+    def worker_commit_grand_product_zk(self, wire_handles: Sequence[int], sigma_handles: Sequence[int], shifts, beta, gamma,
+                                       usable, tail):
+        return self._routed_builder("worker_commit_grand_product_zk", list(wire_handles) + list(sigma_handles), wire_handles,
+                                    sigma_handles, shifts, beta, gamma, usable, tail)
+
+    def worker_commit_lookup_sum_zk(self, input_handles: Sequence[int], table_handles: Sequence[int], mult_handle: int,
+                                    n_lookups, width, theta, beta, usable, tail):
+        return self._routed_builder("worker_commit_lookup_sum_zk", list(input_handles) + list(table_handles) + [mult_handle],
+                                    input_handles, table_handles, mult_handle, n_lookups, width, theta, beta, usable, tail)
+
+    def worker_commit_multiplicities_zk(self, input_handles: Sequence[int], table_handles: Sequence[int], n_lookups, width,
+                                        usable, tail):
+        return self._routed_builder("worker_commit_multiplicities_zk", list(input_handles) + list(table_handles), input_handles,
+                                    table_handles, n_lookups, width, usable, tail)
+
+    def worker_commit_quotient_zk(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None, ext_log=2,
+                                  n_pieces=3):
+        return self._routed_builder("worker_commit_quotient_zk", handles, handles, terms, perm, lookup, active_row, ext_log,
+                                    n_pieces)
+
     def worker_release_rows(self, handle: int):
         i = self._owner([handle])
         if i is None:
