@@ -463,6 +463,64 @@ int kzg_rows_commit_quotient_zk(kzg_ctx* ctx, uint32_t n_handles, const uint64_t
                                 const kzg_quotient_lookup* lookup /* NULL: none */,
                                 const kzg_quotient_active* active /* NULL: kzg_rows_commit_quotient_ext */, uint32_t ext_log,
                                 uint32_t n_pieces, uint8_t* out_commitments48 /* n_pieces * 48 */, uint64_t* out_handle);
+/* THE QUOTIENT IN PARTS, AND CHAINED GRAND PRODUCTS: circuits that fit no single quotient call -- more than 16 rows, more
+ * permuted columns than E (E - 1 with an active column), several permutation or lookup arguments, more than 16 gate terms.
+ * The quotient is linear in its numerator and the division by X^T - 1 is pointwise on the coset g H_N, so the numerator is
+ * summed on the device over several calls, each under the caps above with its own handles and its own row numbering (halo2's
+ * layout: the permutation split into chunks of E - 1 columns with one z_c each, chained by z_c(1) = z_{c-1}(w^u)).
+ * kzg_rows_quotient_part:  computes this part's num_p / Z_H on the coset exactly as kzg_rows_commit_quotient_zk does (handle
+ *   rules, row numbering, the degree rules per part and the scalar checks are that call's; active == NULL and lookup == NULL
+ *   as there), multiplies it by the canonical scalar scale (NULL: 1) and adds it into the accumulator *inout_acc, a device
+ *   vector of N = E T canonical elements.  *inout_acc == 0 creates the accumulator (the part is written, not added) and
+ *   returns its handle there.  The caller keeps parts apart with its own powers of alpha in scale: inside a part, alpha still
+ *   weighs P1, P2, LK1, LK2 as in the single call.
+ *   link != NULL (needs perm->k > 0, else KZG_E_ARG): P2 is (z(X) - f_prev(w^rot X)) L_0(X) instead of (z(X) - 1) L_0(X), with
+ *   f_prev row prev_row of THIS part's concatenation and rot any int32, reduced mod T like a gate rotation and read from the
+ *   same extended vector at index (i + rot E) mod N -- the chain relation z_c(1) = z_{c-1}(w^u) with rot = u.  The last chunk's
+ *   closing relation (z - 1) L_u stays a gate term over the caller's row L_u, as in the single call.
+ * The accumulator is an entry of the set table, not a row set: its handle comes from the same counter, it counts against
+ *   KZG_MAX_ROW_SETS and in kzg_rows_stats (N * 32 bytes), goes stale on an SRS load, is freed by kzg_rows_release and
+ *   kzg_destroy, and its buffer goes through the same free list.  It remembers the worker, T and ext_log of its first part; a
+ *   part that differs in any of them gets KZG_E_ARG.  Naming it in an open, an evaluation, a lincomb or any builder is
+ *   KZG_E_ARG, and so is naming a row set as the accumulator.  Parts added to one accumulator from several threads are
+ *   serialised by the library at the add (the rest of each part overlaps); field addition is exact, so the order changes no byte.
+ *   An error never changes which handles are live: a failed first part creates nothing; a failed later part leaves the
+ *   accumulator as it was (the add is the call's last device step); if the add itself fails with KZG_E_HIP the accumulator
+ *   becomes stale.
+ * kzg_rows_quotient_finish:  the inverse transform, the pieces with the shape check when n_pieces < E, and the one MSM pass --
+ *   the code of the single call.  On KZG_OK the new set of n_pieces rows exists and the accumulator is consumed (its handle is
+ *   dead).  On ANY error, the shape check's KZG_E_ARG included, no set is created and the accumulator stays live for the caller
+ *   to release.  n_pieces outside [1, E], a row-set handle, a released or stale accumulator: KZG_E_ARG.
+ * One part with scale NULL and no link followed by finish equals the single call byte for byte.
+ * kzg_rows_commit_grand_product_chain:  kzg_rows_commit_grand_product_zk with start_be32 in front of the outputs:
+ *   z(w^0) = start, z(w^(t+1)) = z(w^t) N_t / D_t for t < u, so z(w^u) = start * prod N / prod D, returned as closing; the tail
+ *   sits behind it untouched by start.  start >= r or start = 0: KZG_E_ARG.  start = 1 IS the _zk call byte for byte.  The factor
+ *   is folded in at the scan's top level: no pass over T elements.  Only the blinding-rows layout has a row that holds the
+ *   closing value, so there is no plain form.
+ * COST: each part re-extends the rows it names -- a row shared by two parts is transformed twice; that is the price of the caps
+ *   staying where they are.  Workspace per part is the single call's; the accumulator adds N * 32 bytes.
+ * SOUNDNESS: the library supplies the mechanics only.  The scales (and every alpha inside a part) must be drawn after all
+ *   z_c and S are committed; the chunks' z_c must share beta and gamma; the verifier recomputes sum_p scale_p num_p(zeta) from
+ *   the opened values, the link as (z_c(zeta) - z_{c-1}(w^u zeta)) L_0(zeta).
+ * OUT OF SCOPE: an opening over more than 16 rows (a wide circuit opens in several kzg_rows_open_lincomb calls, one proof per
+ *   call and point); sharing extended rows between parts; per-row selectors and plookup; degree-raising blinders; deriving
+ *   challenges or scales (the library still draws nothing). */
+typedef struct kzg_quotient_link {
+    uint32_t prev_row;           /* f_prev: the previous chunk's z */
+    int32_t rot;                 /* read at w^rot X */
+} kzg_quotient_link;
+int kzg_rows_quotient_part(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
+                           const kzg_quotient_perm* perm /* NULL: none */, const kzg_quotient_link* link /* NULL: P2 = (z - 1) L_0 */,
+                           const kzg_quotient_lookup* lookup /* NULL: none */, const kzg_quotient_active* active /* NULL: none */,
+                           uint32_t ext_log, const uint8_t* scale_be32 /* NULL: 1 */, uint64_t* inout_acc /* 0: create */);
+int kzg_rows_quotient_finish(kzg_ctx* ctx, uint64_t acc, uint32_t n_pieces, uint8_t* out_commitments48 /* n_pieces * 48 */,
+                             uint64_t* out_handle);
+int kzg_rows_commit_grand_product_chain(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                        uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
+                                        const uint8_t* shifts_be32 /* k*32 */, const uint8_t beta_be32[32],
+                                        const uint8_t gamma_be32[32], uint64_t usable,
+                                        const uint8_t* tail_be32 /* (T-usable-1)*32, or NULL */, const uint8_t start_be32[32],
+                                        uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle);
 /* The UNCHANGED reference miner makes two calls per request with the same row -- worker_commit(i, poly), then
  * worker_open(i, poly, x) (neurons/miner.py:56-61).  These forms take a 128-bit content tag identifying the row's bytes
  * (the host codec computes it while decoding the text); the coefficient vectors of the last four rows stay on the
@@ -723,6 +781,18 @@ int kzg_multi_rows_commit_quotient_zk(kzg_multi* mh, uint32_t i, uint32_t n_hand
                                       const kzg_quotient_terms* gate, const kzg_quotient_perm* perm,
                                       const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
                                       uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle);
+int kzg_multi_rows_quotient_part(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                 const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                                 const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
+                                 const uint8_t* scale_be32, uint64_t* inout_acc);
+int kzg_multi_rows_quotient_finish(kzg_multi* mh, uint32_t i, uint64_t acc, uint32_t n_pieces, uint8_t* out_commitments48,
+                                   uint64_t* out_handle);
+int kzg_multi_rows_commit_grand_product_chain(kzg_multi* mh, uint32_t i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                              uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
+                                              const uint8_t* shifts_be32, const uint8_t beta_be32[32],
+                                              const uint8_t gamma_be32[32], uint64_t usable, const uint8_t* tail_be32,
+                                              const uint8_t start_be32[32], uint8_t out_commitment48[48],
+                                              uint8_t out_closing32[32], uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

@@ -60,6 +60,11 @@ class QuotientActive(ctypes.Structure):
     _fields_ = [("active_row", _U32)]
 
 
+class QuotientLink(ctypes.Structure):
+    """kzg_quotient_link"""
+    _fields_ = [("prev_row", _U32), ("rot", ctypes.c_int32)]
+
+
 SYMBOLS = {
     "kzg_create": (_I, [_I, ctypes.POINTER(_P)]),
     "kzg_destroy": (None, [_P]),
@@ -110,6 +115,12 @@ SYMBOLS = {
     "kzg_rows_commit_quotient_zk": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms), ctypes.POINTER(QuotientPerm),
                                          ctypes.POINTER(QuotientLookup), ctypes.POINTER(QuotientActive), _U32, _U32, _B,
                                          ctypes.POINTER(_U64)]),
+    "kzg_rows_quotient_part": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms), ctypes.POINTER(QuotientPerm),
+                                    ctypes.POINTER(QuotientLink), ctypes.POINTER(QuotientLookup), ctypes.POINTER(QuotientActive),
+                                    _U32, _B, ctypes.POINTER(_U64)]),
+    "kzg_rows_quotient_finish": (_I, [_P, _U64, _U32, _B, ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_grand_product_chain": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _B, _B, _B, _U64,
+                                                 _B, _B, _B, _B, ctypes.POINTER(_U64)]),
     "kzg_commit_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B]),
     "kzg_open_cached": (_I, [_P, _U32, _B, _U64, _I, _B, _B, _B, _B]),
     "kzg_row_cache_stats": (_I, [_P, ctypes.POINTER(_U64)]),
@@ -187,6 +198,13 @@ SYMBOLS = {
     "kzg_multi_rows_commit_quotient_zk": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms),
                                                ctypes.POINTER(QuotientPerm), ctypes.POINTER(QuotientLookup),
                                                ctypes.POINTER(QuotientActive), _U32, _U32, _B, ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_quotient_part": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms),
+                                          ctypes.POINTER(QuotientPerm), ctypes.POINTER(QuotientLink),
+                                          ctypes.POINTER(QuotientLookup), ctypes.POINTER(QuotientActive), _U32, _B,
+                                          ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_quotient_finish": (_I, [_P, _U32, _U64, _U32, _B, ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_grand_product_chain": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _B,
+                                                       _B, _B, _U64, _B, _B, _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_commit_open_rows": (_I, [_P, _U32, ctypes.POINTER(_U32), _B, _U64, _I, _B, _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_upload_fr": (_I, [_P, _I, _B, _U64, _I]),
     "kzg_msm_resident": (_I, [_P, _I, _U64, _U64, _B]),

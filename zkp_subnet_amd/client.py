@@ -97,6 +97,7 @@ class Client:
         self.synthetic = (seed is not None) if synthetic is None else bool(synthetic)
         self.workers = list(workers) if workers is not None else None
         self.scale = self.machines_scale = 0
+        self._accs: Dict[int, Any] = {}   # live quotient accumulators made through worker_quotient_part, by handle
 
     # ------------------------------------------------------------------ lifecycle (base/miner.py:82-84,155,181)
     def start(self, scale: int = 18, machines_scale: int = 8) -> None:
@@ -546,10 +547,88 @@ class Client:
             raise codec.CodecError(f"{what}: coefficients, shifts and challenges must be canonical scalars (< r)")
         return tt, pp, ll, ext_log, n_pieces
 
+    # ---- the quotient in parts and the chained grand product: circuits that fit no single worker_commit_quotient_zk call
+    @_guard
+    def worker_quotient_part(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None, link=None,
+                             ext_log: int = 2, scale=None, acc=None):
+        """Extension: one part of a quotient summed on the device over several calls.  handles, terms, perm, lookup and
+        active_row as in worker_commit_quotient_zk, with this part's own row numbering; link: None or [prev_row, rot], which
+        turns P2 into (z(X) - f_prev(w^rot X)) L_0(X), the chain relation of a chunked permutation; scale: None (1) or the
+        scalar this part is multiplied by (the caller's power of alpha); acc: None (a new accumulator) or the handle an earlier
+        part returned.  Returns {"acc": handle}.  worker_quotient_finish turns the accumulator into the pieces;
+        worker_release_rows frees one that is not finished."""
+        hs = _handles(handles)
+        try:
+            active_row = None if active_row is None else int(active_row)
+            ln = None if link is None else (int(link[0]), int(link[1]))
+            if link is not None and len(link) != 2:
+                raise ValueError("a link is a [prev_row, rot] pair")
+            sc = None if scale is None else codec.fr_to_be32(scale)
+            ah = None if acc is None else _handles([acc])[0]
+        except (TypeError, ValueError, IndexError, KeyError) as e:
+            raise codec.CodecError(f"worker_quotient_part: active_row, link, scale and acc must be an integer, a [prev_row, rot] "
+                                   f"pair, a scalar and a handle (or None): {e!r}") from e
+        if sc is not None and int.from_bytes(sc, "big") >= codec.R_MODULUS:
+            raise codec.CodecError("worker_quotient_part: scale must be a canonical scalar (< r)")
+        tt, pp, ll, ext_log, _ = self._quotient_ext_parts("worker_quotient_part", terms, perm, lookup, ext_log, 1)
+        if ln is not None and pp is None:
+            raise codec.CodecError("worker_quotient_part: a link needs a permutation part")
+        accs = self._accs
+        a = None
+        if ah is not None:
+            a = accs.get(ah)
+            if a is None:
+                raise codec.CodecError("worker_quotient_part: acc names no live accumulator of this client")
+        out = self.engine.quotient_part(hs, tt, pp, ll, active_row, ln, ext_log, sc, a)
+        accs[int(out.handle)] = out
+        return {"acc": int(out.handle)}
+
+    @_guard
+    def worker_quotient_finish(self, acc: int, n_pieces: int = 3):
+        """Extension: the pieces of the quotient accumulated by worker_quotient_part, committed as a new set of n_pieces rows.
+        Returns the new handle and the pieces' commitments; the accumulator is consumed.  When the quotient does not fit
+        n_pieces rows (the constraints do not hold) nothing is created and the accumulator stays, to be released."""
+        ah = _handles([acc])[0]
+        try:
+            n_pieces = int(n_pieces)
+        except (TypeError, ValueError) as e:
+            raise codec.CodecError(f"worker_quotient_finish: n_pieces must be an integer: {e!r}") from e
+        if not 1 <= n_pieces <= 8:
+            raise codec.CodecError(f"worker_quotient_finish: n_pieces = {n_pieces}, expected 1 .. 2^ext_log")
+        accs = self._accs
+        a = accs.get(ah)
+        if a is None:
+            raise codec.CodecError("worker_quotient_finish: acc names no live accumulator of this client")
+        rs = self.engine.quotient_finish(a, n_pieces)
+        accs.pop(ah, None)
+        return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments]}
+
+    @_guard
+    def worker_commit_grand_product_chain(self, wire_handles: Sequence[int], sigma_handles: Sequence[int], shifts: Sequence[str],
+                                          beta: str, gamma: str, usable: int, tail: Sequence[str], start: str):
+        """Extension: worker_commit_grand_product_zk whose z starts at `start` instead of 1: one chunk of a chained
+        permutation.  The closing value z(w^usable) = start * prod N / prod D is the next chunk's start (1 after the last
+        chunk when the permutation holds); the tail is untouched by start.  start must be canonical and not 0."""
+        hw, hs = _handles(wire_handles), _handles(sigma_handles)
+        if not 1 <= len(shifts) <= KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"worker_commit_grand_product_chain: {len(shifts)} shifts, expected 1 .. {KZG_MAX_BATCH_OPEN}")
+        sc = [codec.fr_to_be32(x) for x in list(shifts) + [beta, gamma, start]]
+        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in sc):
+            raise codec.CodecError("worker_commit_grand_product_chain: shifts, beta, gamma and start must be canonical scalars "
+                                   "(< r)")
+        if int.from_bytes(sc[-1], "big") == 0:
+            raise codec.CodecError("worker_commit_grand_product_chain: start must not be 0")
+        usable, tb = self._blind("worker_commit_grand_product_chain", usable, tail)
+        rs, closing = self.engine.commit_grand_product_chain(hw, hs, sc[:-3], sc[-3], sc[-2], usable, tb, sc[-1])
+        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]),
+                "closing": codec.be32_to_fr(closing)}
+
     @_guard
     def worker_release_rows(self, handle: int):
-        """Extension: frees a committed row set."""
-        self.engine.release_rows(_handles([handle])[0])
+        """Extension: frees a committed row set (or a quotient accumulator that was not finished)."""
+        h = _handles([handle])[0]
+        self.engine.release_rows(h)
+        self._accs.pop(h, None)
         return {"released": True}
 
     @_guard

@@ -267,6 +267,13 @@ struct kzg_ctx {
         int refs = 0;
         bool stale = false;          // committed under an SRS that has since been replaced
         bool released = false;       // handle unlinked; the buffer waits for refs == 0
+        // a quotient accumulator (kzg_rows_quotient_part): an entry of this table like a set -- handle, cap, stats, staleness,
+        // release, free list -- that is NOT a row set: buf holds the N = T << acc_ext_log canonical values of sum_p scale_p
+        // num_p / Z_H on the coset, k is 0, and every call that takes row sets refuses it.  acc_mu serialises the adds of parts
+        // that run on several lanes (taken behind the lane, in front of sets_mu; held from an add's launch to its completion).
+        bool acc = false;
+        uint32_t acc_ext_log = 0;
+        std::unique_ptr<std::mutex> acc_mu;
     };
     std::mutex sets_mu;              // guards everything below
     std::map<uint64_t, RowSet> sets; // by handle: live sets, and released ones that an open still reads
@@ -420,7 +427,7 @@ struct Blind {
 int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& wires, const RowTab& sigmas, uint32_t k,
                            uint64_t T, const uint8_t* shifts_be32, const uint8_t* beta_be32, const uint8_t* gamma_be32,
                            uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den,
-                           const Blind* zk = nullptr);
+                           const Blind* zk = nullptr, const uint8_t* start_be32 = nullptr);
 // the lookup running sum over n_lookups x width input rows, width table rows and the multiplicity row `mult` into a new one-row
 // set's buffer dst: its commitment, the closing value, and whether some denominator was zero (the caller creates no set)
 int rows_lookup_sum_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& table, const uint32_t* mult,
@@ -435,6 +442,15 @@ int rows_multiplicities_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab&
 // their commitments, and whether a coefficient of t at or above n_pieces T was not zero (the caller creates no set)
 int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t n_rows, uint64_t T, const QuotPlan& qp,
                       uint32_t n_pieces, uint32_t* dst, uint8_t* out_c48, bool* out_bad_shape);
+// kzg_rows_quotient_part / _finish: the quotient call cut in two around an accumulator of N = T << ext_log canonical values.
+// front: the part's num / Z_H into the lane's staging vector.  add: acc (+)= scale * that vector as the call's last device
+// step (the caller holds the accumulator's mutex around it).  finish: the inverse transform, the pieces with the shape check
+// and the MSM pass over `src`, which is only read (the accumulator, or the single call's staging vector)
+int rows_quotient_front_dev(kzg_ctx* ctx, LaneHold& H, const RowTab& rt, uint32_t n_rows, uint64_t T, const QuotPlan& qp);
+int rows_quotient_add_dev(kzg_ctx* ctx, LaneHold& H, uint64_t T, uint32_t ext_log, const uint8_t* scale_be32, uint32_t* acc,
+                          bool first);
+int rows_quotient_finish_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, uint64_t T, int ext_log, const uint32_t* acc, uint32_t n_pieces,
+                             uint32_t* dst, uint8_t* out_c48, bool* out_bad_shape);
 // an SRS (re)load is installing a new table (every lane held): marks every live set stale, frees its buffer and the free list
 void rows_invalidate(kzg_ctx* ctx);
 // kzg_rows_open with the extra condition that every set belongs to worker `expect_i` (UINT32_MAX: any; kzg_multi_rows_open)
@@ -477,6 +493,18 @@ int rows_multiplicities_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_h
 int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
                        const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces,
                        uint8_t* out_commitments48, uint64_t* out_handle);
+// kzg_rows_quotient_part / kzg_rows_quotient_finish / kzg_rows_commit_grand_product_chain
+int rows_quotient_part_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                            const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                            const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
+                            const uint8_t* scale_be32, uint64_t* inout_acc);
+int rows_quotient_finish_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t acc, uint32_t n_pieces, uint8_t* out_commitments48,
+                              uint64_t* out_handle);
+int rows_grand_product_chain_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                  uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
+                                  const uint8_t* beta_be32, const uint8_t* gamma_be32, uint64_t usable, const uint8_t* tail_be32,
+                                  const uint8_t* start_be32, uint8_t* out_commitment48, uint8_t* out_closing32,
+                                  uint64_t* out_handle);
 // kzg_rows_commit_quotient_ext; plain: the call came through kzg_rows_commit_quotient (rotations null, no lookup part)
 int rows_quotient_ext_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
                            const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,

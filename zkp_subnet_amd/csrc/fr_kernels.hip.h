@@ -93,13 +93,15 @@ void launch_gp_factors(hipStream_t s, const uint32_t* ea, const uint32_t* es, ui
 // N[t] <- z(w^t) = (prod_{u<t} N_u) (prod_{u>=t} D_u) / prod_u D_u (D is consumed); scrN, scrD: (n + 3) / 4 * 3 / 2 + 64
 // elements of scratch each.  closing_be (device): prod N / prod D, 32 bytes big-endian; *zero_flag (device): 1 when
 // prod D == 0 (z undefined, N then holds zeros), else 0
+// start_be32 (kzg_rows_commit_grand_product_chain; null: 1): every z(w^t) and the closing value are multiplied by it -- 32
+// big-endian HOST bytes, canonical and nonzero (the caller's check), folded into the top level's <= 2048 prefix values
 void launch_gp_scan(hipStream_t s, uint32_t* N, uint32_t* D, uint64_t n, uint32_t* scrN, uint32_t* scrD,
-                    uint8_t* closing_be, uint32_t* zero_flag);
+                    uint8_t* closing_be, uint32_t* zero_flag, const uint8_t* start_be32 = nullptr);
 // the scan without its last level (N and D only read; they may be one vector): scrN[g] / scrD[g] <- the exclusive prefix
 // product of N in front of level-0 chunk g / the exclusive suffix product of D behind it times 1 / prod D; closing_be and
 // zero_flag as above.  Returns log2 of the level-0 chunk length.  n > 0
 int launch_gp_scan_upper(hipStream_t s, const uint32_t* N, const uint32_t* D, uint64_t n, uint32_t* scrN, uint32_t* scrD,
-                         uint8_t* closing_be, uint32_t* zero_flag);
+                         uint8_t* closing_be, uint32_t* zero_flag, const uint8_t* start_be32 = nullptr);
 // test hook: out[j] = in[j]^-1 (32 big-endian bytes each, canonical; 0 for in[j] == 0) or, with want_flag, the inversion's
 // zero flag (0 / 1) in the same format
 void launch_fr_inv_test(hipStream_t s, const uint8_t* in_be, uint8_t* out_be, uint64_t n, int want_flag);
@@ -123,6 +125,9 @@ struct QuotPlan {
     // kzg_rows_commit_quotient_zk.  active != 0 (then ext != 0 too): P1 and LK1 are multiplied by row active_row, the caller's
     // column A that is 1 on the usable rows and 0 elsewhere, and the third instantiation of the kernel runs
     uint32_t active, active_row;
+    // kzg_rows_quotient_part with a link.  link != 0 (then ext != 0 and k > 0): P2 = (z - f_prev(w^rot X)) L_0 with f_prev = row
+    // link_row and rot = link_rot in [0, T), and a linked instantiation of the kernel runs
+    uint32_t link, link_row, link_rot;
 };
 // the constants record of one (T, E), in 8-word elements: 1 / Z_H on the coset, 1 / T, g and the power tables of g and 1 / g
 uint64_t quot_consts_elems(int log_t, int ext_log);
@@ -139,6 +144,10 @@ void launch_quot_points(hipStream_t s, const RowTab& ext_rows, const uint32_t* l
 // consecutive); *tail_flag |= 1 when some in[i], i >= n_pieces T, is not zero
 void launch_quot_pieces(hipStream_t s, const uint32_t* in, uint32_t* dst, int log_t, int ext_log, uint32_t n_pieces,
                         const uint32_t* qc, uint32_t* tail_flag);
+// acc[i] = scale v[i] (first) or acc[i] + scale v[i] over n canonical Montgomery elements, canonical on store; scale: 32
+// big-endian HOST bytes < r (the caller's check), null: 1.  The add of kzg_rows_quotient_part
+void launch_quot_accumulate(hipStream_t s, uint32_t* acc, const uint32_t* v, uint64_t n, const uint8_t* scale_be32_or_null,
+                            bool first);
 // ---- the lookup (logUp) running sum (fr_lookup.hip; kzg_rows_commit_lookup_sum)
 // one transformed column e (n evaluations, Montgomery) folded in: v = acc theta + e (has_acc) or e, then by mode
 //   0: acc <- v    1: Q <- beta + v, P <- -P (P holds m's evaluations)    2: (P, Q) <- (P d + Q, Q d), d = beta + v

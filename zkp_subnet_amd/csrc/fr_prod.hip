@@ -234,6 +234,39 @@ __global__ void __launch_bounds__(512) k_gp_top(uint32_t* __restrict__ vN, uint3
         fr9_mul(p, p, c);
     }
 }
+// kzg_rows_commit_grand_product_chain: between k_gp_top and the expansions, every EXCLUSIVE PREFIX value of the top level (m <=
+// GP_TOP_MAX of them, canonical) is multiplied by the caller's start value, so that every value expanded from this level
+// carries it, and lane 0 multiplies the closing value in the record by it as well.  start is converted to Montgomery form once
+// per workgroup; a canonical value by a canonical one, canonical on store.  At most 8 workgroups: no pass over the row.
+__global__ void __launch_bounds__(256) k_gp_chain_start(uint32_t* __restrict__ vN, uint32_t m, uint8_t* __restrict__ closing_be,
+                                                         const FrArg start) {
+    __shared__ uint32_t cst[9];
+    if (threadIdx.x == 0) {
+        fr9_t c;
+        fr9_from_arg(c, start, nullptr, false);   // (start < r and != 0 is the host's check)
+#pragma unroll
+        for (int i = 0; i < 9; i++) cst[i] = c.l[i];
+    }
+    __syncthreads();
+    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= m) return;
+    fr9_t st, p;
+#pragma unroll
+    for (int i = 0; i < 9; i++) st.l[i] = cst[i];
+    fr9_load(p, vN + 8 * (uint64_t)u);
+    fr9_mul(p, p, st);
+    fr9_canon(p, p);
+    fr9_store(vN + 8 * (uint64_t)u, p);
+    if (u == 0) {
+        uint32_t w[8];
+        limbs_from_be<8>(w, closing_be);
+        fr9_from_words(p, w);
+        fr9_mul(p, p, st);       // canonical (plain) by Montgomery start: the plain product, below 2r
+        fr9_canon(p, p);
+        fr9_to_words(w, p);
+        limbs_to_be<8>(closing_be, w);
+    }
+}
 // One level down, in place: group g of 2^l values of this level starts from the parent's exclusive value ex[g]; N (grid row
 // 0) walks its group upward, D (grid row 1) downward, each value replaced by the exclusive product in front of it.
 __global__ void __launch_bounds__(256) k_gp_expand(uint32_t* __restrict__ vN, uint32_t* __restrict__ vD, uint64_t n, int l,
@@ -287,7 +320,7 @@ __global__ void __launch_bounds__(256) k_gp_final(uint32_t* __restrict__ N, uint
 // vector: the batched inversion of fr_lookup.hip).  Level 0 folds 2^l0 elements per lane (4 for short rows, 16 for long ones,
 // as the opening does), every further level 16, until at most GP_TOP_MAX values are left for k_gp_top.
 int launch_gp_scan_upper(hipStream_t s, const uint32_t* N, const uint32_t* D, uint64_t n, uint32_t* scrN, uint32_t* scrD,
-                         uint8_t* closing_be, uint32_t* zero_flag) {
+                         uint8_t* closing_be, uint32_t* zero_flag, const uint8_t* start_be32) {
     int l0 = 2;
     while (l0 < 4 && (n >> (l0 + 1)) >= 16384) l0++;
     int K = 1, lv_l[16];
@@ -304,6 +337,11 @@ int launch_gp_scan_upper(hipStream_t s, const uint32_t* N, const uint32_t* D, ui
         K++;
     }
     k_gp_top<<<1, 512, 0, s>>>(scrN + 8 * lv_off[K], scrD + 8 * lv_off[K], (uint32_t)lv_n[K], closing_be, zero_flag);
+    if (start_be32) {
+        FrArg st;
+        memcpy(st.w, start_be32, 32);
+        k_gp_chain_start<<<nblk(lv_n[K], 256), 256, 0, s>>>(scrN + 8 * lv_off[K], (uint32_t)lv_n[K], closing_be, st);
+    }
     for (int k = K - 1; k >= 1; k--)
         k_gp_expand<<<dim3(nblk(lv_n[k + 1], 256), 2), 256, 0, s>>>(scrN + 8 * lv_off[k], scrD + 8 * lv_off[k], lv_n[k], lv_l[k],
                                                                     scrN + 8 * lv_off[k + 1], scrD + 8 * lv_off[k + 1]);
@@ -312,8 +350,8 @@ int launch_gp_scan_upper(hipStream_t s, const uint32_t* N, const uint32_t* D, ui
 // N, D (n Montgomery elements each) -> z's evaluations in N (D is consumed).  scrN / scrD: (n + 3) / 4 * 3 / 2 + 64 elements
 // of level scratch each (the sizing of the opening's h / hnext).
 void launch_gp_scan(hipStream_t s, uint32_t* N, uint32_t* D, uint64_t n, uint32_t* scrN, uint32_t* scrD,
-                    uint8_t* closing_be, uint32_t* zero_flag) {
+                    uint8_t* closing_be, uint32_t* zero_flag, const uint8_t* start_be32) {
     if (!n) return;
-    const int l0 = launch_gp_scan_upper(s, N, D, n, scrN, scrD, closing_be, zero_flag);
+    const int l0 = launch_gp_scan_upper(s, N, D, n, scrN, scrD, closing_be, zero_flag, start_be32);
     k_gp_final<<<nblk(((n + ((uint64_t)1 << l0) - 1) >> l0), 256), 256, 0, s>>>(N, D, n, l0, scrN, scrD);
 }

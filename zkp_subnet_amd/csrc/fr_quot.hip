@@ -7,6 +7,8 @@
 //                   the coefficients of L_0 (all 1 / T)
 //   k_quot_points   one lane per coset point: (Gate + alpha P1 + alpha^2 P2) / Z_H; its second instantiation (kzg_rows_commit_
 //                   quotient_ext) reads a gate factor at a rotation and adds alpha^3 LK1 + alpha^4 LK2, the logUp relation
+//                   (kzg_rows_quotient_part with a link: P2 = (z - f_prev(w^rot X)) L_0, two instantiations more)
+//   k_quot_accumulate   acc[i] (+)= scale v[i]: one part's num / Z_H into the accumulator of kzg_rows_quotient_part
 //   k_quot_pieces   after the inverse transform: t[i] = g^-i v[i] for i < P T into the new set's buffer, the tail [P T, N)
 //                   ORed into a flag word
 // Z_H(x_i) = g^T w_E^(i mod E) - 1: E inversions per (T, E), none per point.  z(w x_i) = z at index (i + E) mod N, and in
@@ -171,15 +173,27 @@ struct QuotArgA {
     uint32_t active_row;
 };
 static_assert(sizeof(QuotArgA) + sizeof(RowTab) + 64 <= 4096, "k_quot_points' arguments must fit in 4 KB");
-template <bool EXT, bool ACT> struct QuotArgOf { typedef QuotArg type; };
-template <> struct QuotArgOf<true, false> { typedef QuotArgX type; };
-template <> struct QuotArgOf<true, true> { typedef QuotArgA type; };
+// What a link of kzg_rows_quotient_part adds: the row of f_prev and its rotation, prepared on the host as (rot mod T) E like a
+// gate factor's.  The linked instantiations' own argument: the three others keep theirs.
+struct QuotArgL {
+    QuotArgA a;
+    uint32_t link_row, link_rot;
+};
+static_assert(sizeof(QuotArgL) + sizeof(RowTab) + 64 <= 4096, "k_quot_points' arguments must fit in 4 KB");
+template <bool EXT, bool ACT, bool LINK = false> struct QuotArgOf { typedef QuotArg type; };
+template <> struct QuotArgOf<true, false, false> { typedef QuotArgX type; };
+template <> struct QuotArgOf<true, true, false> { typedef QuotArgA type; };
+template <bool ACT> struct QuotArgOf<true, ACT, true> { typedef QuotArgL type; };
 KZG_DEV const QuotArg& quot_base(const QuotArg& a) { return a; }
 KZG_DEV const QuotArg& quot_base(const QuotArgX& a) { return a.q; }
 KZG_DEV const QuotArg& quot_base(const QuotArgA& a) { return a.x.q; }
+KZG_DEV const QuotArg& quot_base(const QuotArgL& a) { return a.a.x.q; }
 KZG_DEV const QuotArg& quot_ext(const QuotArg& a) { return a; }
 KZG_DEV const QuotArgX& quot_ext(const QuotArgX& a) { return a; }
 KZG_DEV const QuotArgX& quot_ext(const QuotArgA& a) { return a.x; }
+KZG_DEV const QuotArgX& quot_ext(const QuotArgL& a) { return a.a.x; }
+KZG_DEV uint32_t quot_active_row(const QuotArgA& a) { return a.active_row; }
+KZG_DEV uint32_t quot_active_row(const QuotArgL& a) { return a.a.active_row; }
 enum { QS_SHIFT = QUOT_MAX_TERMS, QS_BETA = QS_SHIFT + QUOT_MAX_WIRES, QS_GAMMA, QS_ALPHA, QS_ALPHA2, QS_COUNT,
        QX_THETA = QS_COUNT, QX_LBETA, QX_ALPHA3, QX_ALPHA4, QX_COUNT };   // (the QX_ slots: the second instantiation only)
 KZG_DEV void quot_arg(fr9_t& v, const FrArg& a, uint32_t* __restrict__ bad, bool check) {
@@ -223,12 +237,18 @@ KZG_DEV void quot_lk_den(fr9_t& d, const RowTab& rt, const uint8_t* rows, uint32
 // transform ends in fr9_reduce): a legal SECOND operand.  P1 is below 6r and LK1 below 10r, legal FIRST operands as they are for
 // the products by alpha and alpha^3 that follow; A P1 and A LK1 come out below 2r, so those products and the lazy sum keep the
 // bounds above.  One more 32-byte load and two more products per point; the two other instantiations keep their instructions.
-template <bool EXT, bool ACT = false>
+// LINK = true (with EXT; kzg_rows_quotient_part with a link) replaces the 1 of P2 by f_prev(w^rot x_i), a canonical row value
+// read like a rotated gate factor: z - f_prev through fr9_sub4 is below 5r exactly as z - 1 was, a legal first operand of the
+// product by L_0, so P2 and the lazy sum keep the bounds above.  One more 32-byte load per point, in two instantiations of
+// their own (with and without the active column, whose slot of the argument is simply not read); the three others keep their
+// instructions.
+template <bool EXT, bool ACT = false, bool LINK = false>
 __global__ void __launch_bounds__(256) k_quot_points(const RowTab rt, const uint32_t* __restrict__ l0, uint32_t* __restrict__ out,
-                                                      int log_n, const typename QuotArgOf<EXT, ACT>::type qarg,
+                                                      int log_n, const typename QuotArgOf<EXT, ACT, LINK>::type qarg,
                                                       const uint32_t* __restrict__ tw, const uint32_t* __restrict__ qc,
                                                       uint32_t* __restrict__ bad) {
     static_assert(EXT || !ACT, "the active column comes with the extended argument");
+    static_assert(EXT || !LINK, "the link comes with the extended argument");
     const auto& qx = quot_ext(qarg);   // (the plain argument itself when !EXT: nothing of it is read through qx then)
     const QuotArg& qa = quot_base(qarg);
     __shared__ uint32_t cst[EXT ? QX_COUNT : QS_COUNT][9];
@@ -290,7 +310,7 @@ __global__ void __launch_bounds__(256) k_quot_points(const RowTab rt, const uint
     fr9_t acc, p, c;
     [[maybe_unused]] fr9_t act;
     if constexpr (ACT) {
-        if (qa.k || qx.n_lookups) fr9_load(act, rt.r[qarg.active_row] + 8 * i);
+        if (qa.k || qx.n_lookups) fr9_load(act, rt.r[quot_active_row(qarg)] + 8 * i);
     }
     fr9_zero(acc);
     for (uint32_t u = 0; u < qa.n_terms; u++) {
@@ -341,7 +361,9 @@ __global__ void __launch_bounds__(256) k_quot_points(const RowTab rt, const uint
         fr9_add(acc, acc, t);
         fr9_norm(acc, acc);
         // P2 / Z_H = (z - 1) L_0 / Z_H: l0 holds L_0 on the coset, the division is the closing product below
-        fr9_one(c);
+        // (LINK: z - f_prev(w^rot x_i), the chain relation of a chunked permutation)
+        if constexpr (LINK) fr9_load(c, rt.r[qarg.link_row] + 8 * ((i + qarg.link_rot) & (n - 1)));
+        else fr9_one(c);
         fr9_sub4(z, z, c);
         fr9_load(c, l0 + 8 * i);
         fr9_mul(t, z, c);
@@ -397,10 +419,11 @@ __global__ void __launch_bounds__(256) k_quot_points(const RowTab rt, const uint
 }
 void launch_quot_points(hipStream_t s, const RowTab& ext_rows, const uint32_t* l0, uint32_t* out, int log_t, const QuotPlan& qp,
                         const uint32_t* tw_n, const uint32_t* qc, uint32_t* bad) {
-    QuotArgA qarg;
+    QuotArgL larg;
+    QuotArgA& qarg = larg.a;
     QuotArgX& qx = qarg.x;
     QuotArg& qa = qx.q;
-    memset(&qarg, 0, sizeof(qarg));
+    memset(&larg, 0, sizeof(larg));
     qa.n_terms = qp.n_terms;
     qa.k = qp.k;
     qa.z_row = qp.z_row;
@@ -438,12 +461,63 @@ void launch_quot_points(hipStream_t s, const RowTab& ext_rows, const uint32_t* l
         qx.mult_row = qp.mult_row;
         qx.sum_row = qp.sum_row;
     }
+    if (qp.active) qarg.active_row = qp.active_row;
+    if (qp.link) {
+        larg.link_row = qp.link_row;
+        larg.link_rot = qp.link_rot << qp.ext_log;
+        if (qp.active) k_quot_points<true, true, true><<<g, 256, 0, s>>>(ext_rows, l0, out, log_n, larg, tw_n, qc, bad);
+        else k_quot_points<true, false, true><<<g, 256, 0, s>>>(ext_rows, l0, out, log_n, larg, tw_n, qc, bad);
+        return;
+    }
     if (!qp.active) {
         k_quot_points<true><<<g, 256, 0, s>>>(ext_rows, l0, out, log_n, qx, tw_n, qc, bad);
         return;
     }
-    qarg.active_row = qp.active_row;
     k_quot_points<true, true><<<g, 256, 0, s>>>(ext_rows, l0, out, log_n, qarg, tw_n, qc, bad);
+}
+
+// ------------------------------------------------------------------------------------------------ the accumulator's add
+// acc[i] = scale v[i] (FIRST: the part that creates the accumulator) or acc[i] + scale v[i], canonical on store; v is one part's
+// num / Z_H on the coset (canonical), scale the caller's canonical scalar, converted to Montgomery form once per workgroup.  The
+// product is below 2r and the sum with a canonical acc[i] below 3r: fr9_reduce takes it.  Streaming: one product per element,
+// 64 B in (32 when FIRST), 32 B out.
+template <bool FIRST>
+__global__ void __launch_bounds__(256) k_quot_accumulate(uint32_t* __restrict__ acc, const uint32_t* __restrict__ v, uint64_t n,
+                                                          const FrArg scale) {
+    __shared__ uint32_t cst[9];
+    if (threadIdx.x == 0) {   // (scale < r is the host's check: the add raises no flag, it is the call's last device step)
+        fr9_t c;
+        quot_arg(c, scale, nullptr, false);
+#pragma unroll
+        for (int i = 0; i < 9; i++) cst[i] = c.l[i];
+    }
+    __syncthreads();
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fr9_t sc, p;
+#pragma unroll
+    for (int k = 0; k < 9; k++) sc.l[k] = cst[k];
+    fr9_load(p, v + 8 * i);
+    fr9_mul(p, p, sc);
+    if constexpr (FIRST) {
+        fr9_canon(p, p);
+    } else {
+        fr9_t o;
+        fr9_load(o, acc + 8 * i);
+        fr9_add(p, p, o);
+        fr9_reduce(p, p);
+    }
+    fr9_store(acc + 8 * i, p);
+}
+void launch_quot_accumulate(hipStream_t s, uint32_t* acc, const uint32_t* v, uint64_t n, const uint8_t* scale_be32_or_null,
+                            bool first) {
+    if (!n) return;
+    FrArg sc;
+    memset(&sc, 0, sizeof(sc));
+    if (scale_be32_or_null) memcpy(sc.w, scale_be32_or_null, 32);
+    else reinterpret_cast<uint8_t*>(sc.w)[31] = 1;   // big-endian 1
+    if (first) k_quot_accumulate<true><<<nblk(n, 256), 256, 0, s>>>(acc, v, n, sc);
+    else k_quot_accumulate<false><<<nblk(n, 256), 256, 0, s>>>(acc, v, n, sc);
 }
 
 // ------------------------------------------------------------------------------------------------ back to the pieces

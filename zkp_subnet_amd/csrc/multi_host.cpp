@@ -64,6 +64,17 @@ int rows_quotient_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, c
                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
                           const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,
                           uint64_t* out_handle);
+int rows_quotient_part_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                            const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                            const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
+                            const uint8_t* scale_be32, uint64_t* inout_acc);
+int rows_quotient_finish_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t acc, uint32_t n_pieces, uint8_t* out_commitments48,
+                              uint64_t* out_handle);
+int rows_grand_product_chain_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                  uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
+                                  const uint8_t* beta_be32, const uint8_t* gamma_be32, uint64_t usable, const uint8_t* tail_be32,
+                                  const uint8_t* start_be32, uint8_t* out_commitment48, uint8_t* out_closing32,
+                                  uint64_t* out_handle);
 }  // namespace kzg_impl
 
 namespace {
@@ -555,6 +566,36 @@ int kzg_multi_rows_commit_quotient_zk(kzg_multi* mh, uint32_t i, uint32_t n_hand
     if (int rc = route(mh, i, &c, &s)) return rc;
     return relay(c, kzg_impl::rows_quotient_zk_impl(c, s, n_handles, handles, gate, perm, lookup, active, ext_log, n_pieces,
                                                     out_commitments48, out_handle));
+}
+int kzg_multi_rows_quotient_part(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                 const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                                 const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
+                                 const uint8_t* scale_be32, uint64_t* inout_acc) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_quotient_part_impl(c, s, n_handles, handles, gate, perm, link, lookup, active, ext_log,
+                                                      scale_be32, inout_acc));
+}
+int kzg_multi_rows_quotient_finish(kzg_multi* mh, uint32_t i, uint64_t acc, uint32_t n_pieces, uint8_t* out_commitments48,
+                                   uint64_t* out_handle) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_quotient_finish_impl(c, s, acc, n_pieces, out_commitments48, out_handle));
+}
+int kzg_multi_rows_commit_grand_product_chain(kzg_multi* mh, uint32_t i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                              uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
+                                              const uint8_t* shifts_be32, const uint8_t beta_be32[32],
+                                              const uint8_t gamma_be32[32], uint64_t usable, const uint8_t* tail_be32,
+                                              const uint8_t start_be32[32], uint8_t out_commitment48[48],
+                                              uint8_t out_closing32[32], uint64_t* out_handle) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_grand_product_chain_impl(c, s, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles,
+                                                            k, shifts_be32, beta_be32, gamma_be32, usable, tail_be32, start_be32,
+                                                            out_commitment48, out_closing32, out_handle));
 }
 int kzg_multi_rows_release(kzg_multi* mh, uint32_t i, uint64_t handle) {
     kzg_ctx* c;

@@ -726,7 +726,8 @@ int rows_lincomb_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, ui
 // MSM commits.  The record's first two evaluation slots carry the closing value and the zero-denominator flag word.
 int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& wires, const RowTab& sigmas, uint32_t k,
                            uint64_t T, const uint8_t* shifts_be32, const uint8_t* beta_be32, const uint8_t* gamma_be32,
-                           uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den, const Blind* zk) {
+                           uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den, const Blind* zk,
+                           const uint8_t* start_be32) {
     Lane& A = H.L();
     if (int rc = ensure_multi_record(ctx, A)) return rc;
     const int lg = ilog2_exact(T);
@@ -757,8 +758,10 @@ int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& 
         // _zk: N_t = D_t = 1 on the rows >= usable (whatever their cells hold, a zero D_t included), so the unchanged scan
         // leaves z = closing on every one of them; the tail then replaces the rows behind row `usable`
         if (zk) launch_blind_mask(A.stream, N, true, D, T, zk->usable);
+        // _chain: start_be32 is folded into the scan's top-level prefix values: every row and the closing value carry it, and
+        // the tail below overwrites the rows behind row `usable`
         launch_gp_scan(A.stream, N, D, T, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), rec + MR_EVAL,
-                       reinterpret_cast<uint32_t*>(rec + MR_EVAL + 32));
+                       reinterpret_cast<uint32_t*>(rec + MR_EVAL + 32), start_be32);
         if (zk) launch_blind_tail(A.stream, N, T, zk->usable, zk->tail_be32, A.flags());
     }
     const uint32_t* c;
@@ -922,10 +925,9 @@ static int ensure_quot_consts(kzg_ctx* ctx, Lane& L, int log_t, int ext_log, con
 // The flag travels in the record's one copy behind the MSM, so an instance that fails the shape check still pays the MSM
 // before KZG_E_ARG comes back: no set is created, but the error path is not a fast path (a read-back of its own in front of
 // the MSM would cost every good call a synchronisation).
-int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t n_rows, uint64_t T, const QuotPlan& qp,
-                      uint32_t n_pieces, uint32_t* dst, uint8_t* out_c48, bool* out_bad_shape) {
-    Lane& A = H.L();
-    if (int rc = ensure_multi_record(ctx, A)) return rc;
+// The front half, shared with kzg_rows_quotient_part: the extensions and the pointwise launch, which leaves num / Z_H on the
+// coset (N canonical elements) in the lane's staging vector.
+static int quot_front(kzg_ctx* ctx, Lane& A, const RowTab& rt, uint32_t n_rows, uint64_t T, const QuotPlan& qp) {
     const int lg = ilog2_exact(T), ext_log = (int)qp.ext_log, lgn = lg + ext_log;
     const uint64_t N = T << ext_log, nw = N * 8;   // one extended vector, in words
     uint32_t *tw = nullptr, *twi = nullptr, *invn = nullptr;
@@ -943,6 +945,7 @@ int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, u
     for (uint32_t j = 0; qp.n_lookups && j < qp.width; j++) used[qp.tab_row[j]] = true;
     if (qp.n_lookups) used[qp.mult_row] = used[qp.sum_row] = true;
     if (qp.active && (qp.k || qp.n_lookups)) used[qp.active_row] = true;   // A: one more distinct row (a factor of P1 and LK1)
+    if (qp.link) used[qp.link_row] = true;                                 // f_prev of a linked P2
     const bool need_l0 = qp.k || qp.n_lookups;   // P2 and LK2
     int slot[POLY_MAX_ROWS];
     uint32_t nd = 0;
@@ -978,15 +981,31 @@ int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, u
         Span sp(ctx, A, KZG_T_NTT);
         launch_fr_ntt(A.stream, stage, vec, lgn, tw, nullptr, mid);
     }
+    Span sp(ctx, A, KZG_T_POLY);
+    launch_quot_points(A.stream, et, ext + (uint64_t)nd * nw, stage, lg, qp, tw, qc, A.flags());
+    return KZG_OK;
+}
+// The back half, which is kzg_rows_quotient_finish over the accumulator: `src` (num / Z_H on the coset, N canonical elements, only read) through
+// the inverse transform into the lane's quotient workspace, the g^-i launch with the shape check, the one MSM pass.
+int rows_quotient_finish_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, uint64_t T, int ext_log, const uint32_t* src, uint32_t n_pieces,
+                     uint32_t* dst, uint8_t* out_c48, bool* out_bad_shape) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const int lg = ilog2_exact(T), lgn = lg + ext_log;
+    const uint64_t N = T << ext_log;
+    uint32_t *tw = nullptr, *twi = nullptr, *invn = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, lgn, 0, &tw, nullptr)) return rc;
+    if (int rc = ensure_twiddles(ctx, A, lgn, 1, &twi, &invn)) return rc;
+    const uint32_t* qc = nullptr;
+    if (int rc = ensure_quot_consts(ctx, A, lg, ext_log, tw, &qc)) return rc;
+    HIPCHK(ctx, A.qext.ensure(N * 32));
+    HIPCHK(ctx, A.ntt_mid.ensure(N * 48));
+    uint32_t *ext = A.qext.as<uint32_t>(), *mid = A.ntt_mid.as<uint32_t>();
     uint8_t* rec = A.brec.as<uint8_t>();
     HIPCHK(ctx, hipMemsetAsync(rec + MR_EVAL, 0, 32, A.stream));
     {
-        Span sp(ctx, A, KZG_T_POLY);
-        launch_quot_points(A.stream, et, ext + (uint64_t)nd * nw, stage, lg, qp, tw, qc, A.flags());
-    }
-    {
         Span sp(ctx, A, KZG_T_NTT);
-        launch_fr_ntt(A.stream, stage, ext, lgn, twi, invn, mid);
+        launch_fr_ntt(A.stream, src, ext, lgn, twi, invn, mid);
     }
     {
         Span sp(ctx, A, KZG_T_POLY);
@@ -997,6 +1016,35 @@ int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, u
     uint32_t tf;
     memcpy(&tf, ev, 4);
     *out_bad_shape = tf != 0;
+    return KZG_OK;
+}
+int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t n_rows, uint64_t T, const QuotPlan& qp,
+                      uint32_t n_pieces, uint32_t* dst, uint8_t* out_c48, bool* out_bad_shape) {
+    Lane& A = H.L();
+    if (int rc = quot_front(ctx, A, rt, n_rows, T, qp)) return rc;
+    return rows_quotient_finish_dev(ctx, H, i, T, (int)qp.ext_log, A.qstage.as<uint32_t>(), n_pieces, dst, out_c48, out_bad_shape);
+}
+// kzg_rows_quotient_part in two steps, so that the caller can take the accumulator's mutex between them.  The front half
+// leaves the part's num / Z_H in the lane's staging vector; the add is acc (+)= scale * that vector, the call's LAST device
+// step, and ends the call (the stream is drained on any failure: nothing of this call touches the accumulator afterwards).
+// Every scalar was range-checked on the host, so finish() cannot answer KZG_E_SCALAR here; the caller nevertheless treats any
+// failure behind the add's launch as "contents unknown".
+int rows_quotient_front_dev(kzg_ctx* ctx, LaneHold& H, const RowTab& rt, uint32_t n_rows, uint64_t T, const QuotPlan& qp) {
+    return quot_front(ctx, H.L(), rt, n_rows, T, qp);
+}
+int rows_quotient_add_dev(kzg_ctx* ctx, LaneHold& H, uint64_t T, uint32_t ext_log, const uint8_t* scale_be32, uint32_t* acc,
+                          bool first) {
+    Lane& A = H.L();
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_quot_accumulate(A.stream, acc, A.qstage.as<uint32_t>(), T << ext_log, scale_be32, first);
+    }
+    if (int rc = finish(ctx, A)) {
+        (void)hipStreamSynchronize(A.stream);
+        (void)hipGetLastError();
+        return rc;
+    }
+    H.clean = true;
     return KZG_OK;
 }
 

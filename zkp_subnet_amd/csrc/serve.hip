@@ -715,6 +715,7 @@ static int rows_lookup(kzg_ctx* ctx, const char* what, uint32_t expect_i, uint32
         auto it = ctx->sets.find(handles[t]);
         if (it == ctx->sets.end() || it->second.released) return bad(": unknown or released handle");
         kzg_ctx::RowSet& st = it->second;
+        if (st.acc) return bad(": the handle names a quotient accumulator, not a row set");
         if (st.stale)
             return bad(": the set was committed under an SRS that has since been reloaded (its commitments no longer "
                        "hold): release it and commit its rows again");
@@ -856,10 +857,14 @@ static int blind_check(kzg_ctx* ctx, const char* what, uint64_t T, const Blind& 
 static int rows_grand_product_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
                                   uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
                                   const uint8_t* shifts_be32, const uint8_t* beta_be32, const uint8_t* gamma_be32,
-                                  uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle, const Blind* zk) {
+                                  uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle, const Blind* zk,
+                                  const uint8_t* start_be32 = nullptr) {
     if (!ctx || !wire_handles || !sigma_handles || !shifts_be32 || !beta_be32 || !gamma_be32 || !out_commitment48 ||
         !out_closing32 || !out_handle)
         return KZG_E_ARG;
+    static const uint8_t zero32[32] = {};
+    if (start_be32 && (!fr_be32_canonical(start_be32) || memcmp(start_be32, zero32, 32) == 0))
+        return fail(ctx, KZG_E_ARG, "grand product: start must be a canonical scalar (< r) other than 0");
     if (n_wire_handles == 0 || n_wire_handles > KZG_MAX_BATCH_OPEN || n_sigma_handles == 0 || n_sigma_handles > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "grand product: the number of handles in each list must be in [1, KZG_MAX_BATCH_OPEN]");
     if (k == 0 || k > KZG_MAX_BATCH_OPEN) return fail(ctx, KZG_E_ARG, "grand product: k must be in [1, KZG_MAX_BATCH_OPEN]");
@@ -895,7 +900,7 @@ static int rows_grand_product_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wi
     bool zero_den = false;
     uint8_t c48[48], closing[32];
     rc = rows_grand_product_dev(ctx, H, i, wt, st, k, T, shifts_be32, beta_be32, gamma_be32, pend.buf.as<uint32_t>(), c48, closing,
-                                &zero_den, zk);
+                                &zero_den, zk, start_be32);
     if (rc) return rc;
     if (zero_den)
         return fail(ctx, KZG_E_ARG, zk ? "grand product: zero denominator (some a_j + beta sigma_j + gamma vanishes on a usable "
@@ -921,6 +926,17 @@ int rows_grand_product_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_
     const Blind zk = {usable, tail_be32};
     return rows_grand_product_any(ctx, expect_i, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
                                   beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle, &zk);
+}
+// kzg_rows_commit_grand_product_chain: the _zk call whose z starts at `start` instead of 1
+int rows_grand_product_chain_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                  uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
+                                  const uint8_t* beta_be32, const uint8_t* gamma_be32, uint64_t usable, const uint8_t* tail_be32,
+                                  const uint8_t* start_be32, uint8_t* out_commitment48, uint8_t* out_closing32,
+                                  uint64_t* out_handle) {
+    if (!start_be32) return KZG_E_ARG;
+    const Blind zk = {usable, tail_be32};
+    return rows_grand_product_any(ctx, expect_i, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
+                                  beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle, &zk, start_be32);
 }
 
 // kzg_rows_commit_lookup_sum: the lookups of an open (three handle lists), the reservation of a commit.  zk: the blinding
@@ -1063,14 +1079,18 @@ int rows_multiplicities_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_inpu
                                    width, out_commitment48, out_missing, out_handle, &zk);
 }
 
-// kzg_rows_commit_quotient_ext (and, with no rotation and no lookup part, kzg_rows_commit_quotient: `plain`, which only words
-// one message): the lookups of an open (one handle list), the reservation of a commit
-// active: the caller's column A of kzg_rows_commit_quotient_zk, a factor of P1 and LK1 (null: neither has it)
-static int rows_quotient_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                             const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
-                             const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces,
-                             uint8_t* out_commitments48, uint64_t* out_handle, bool plain) {
-    if (!ctx || !handles || !gate || !out_commitments48 || !out_handle) return KZG_E_ARG;
+// The constraints of a quotient call as the caller gave them, checked and turned into the kernels' plan before any lane is
+// taken (kzg_rows_commit_quotient*, and kzg_rows_quotient_part, which has no n_pieces: null).  `plain` only words one message.
+struct QuotCall {
+    QuotPlan qp;
+    int32_t rots[QUOT_MAX_TERMS][QUOT_MAX_FACTORS];   // as given: reduced mod T once T is known
+    int32_t link_rot;
+    uint32_t max_row;   // the largest row index named, checked against the rows once they are known
+    bool any_row;
+};
+static int quot_plan(kzg_ctx* ctx, const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                     const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
+                     const uint32_t* n_pieces, uint32_t n_handles, bool plain, QuotCall& C) {
     const uint32_t k = perm ? perm->k : 0;
     if (gate->n_terms && (!gate->coeffs_be32 || !gate->term_lens || !gate->term_rows)) return KZG_E_ARG;
     if (lookup && (!lookup->input_rows || !lookup->table_rows || !lookup->theta_be32 || !lookup->beta_be32 || !lookup->alpha_be32))
@@ -1082,12 +1102,13 @@ static int rows_quotient_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles
         return fail(ctx, KZG_E_ARG, "quotient: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
     if (ext_log < 1 || ext_log > 3) return fail(ctx, KZG_E_ARG, "quotient: ext_log must be 1, 2 or 3");
     const uint32_t E = 1u << ext_log;
-    if (n_pieces == 0 || n_pieces > E) return fail(ctx, KZG_E_ARG, "quotient: n_pieces must be in [1, 2^ext_log]");
+    if (n_pieces && (*n_pieces == 0 || *n_pieces > E)) return fail(ctx, KZG_E_ARG, "quotient: n_pieces must be in [1, 2^ext_log]");
     if (gate->n_terms > KZG_MAX_GATE_TERMS) return fail(ctx, KZG_E_ARG, "quotient: more than KZG_MAX_GATE_TERMS gate terms");
     if (k > E) return fail(ctx, KZG_E_ARG, "quotient: the permutation part has k + 1 factors: k must not exceed 2^ext_log");
     if (active && k > E - 1)
         return fail(ctx, KZG_E_ARG, "quotient: with an active column the permutation part has k + 2 factors: k must not exceed "
                                     "2^ext_log - 1");
+    if (link && k == 0) return fail(ctx, KZG_E_ARG, "quotient: a link needs a permutation part (perm->k > 0)");
     if (gate->n_terms == 0 && k == 0 && !lookup)
         return fail(ctx, KZG_E_ARG, plain ? "quotient: no gate term and no permutation part"
                                           : "quotient: no gate term, no permutation part and no lookup part");
@@ -1108,18 +1129,15 @@ static int rows_quotient_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles
         if (k && memcmp(lookup->alpha_be32, perm->alpha_be32, 32) != 0)
             return fail(ctx, KZG_E_ARG, "quotient: the permutation part and the lookup part must name one alpha");
     }
-    QuotPlan qp;
-    memset(&qp, 0, sizeof(qp));
+    memset(&C, 0, sizeof(C));
+    QuotPlan& qp = C.qp;
     qp.ext_log = ext_log;
     qp.n_terms = gate->n_terms;
     qp.k = k;
     qp.term_coeffs_be32 = gate->coeffs_be32;
-    int32_t rots[QUOT_MAX_TERMS][QUOT_MAX_FACTORS] = {};   // as given: reduced mod T once T is known
-    uint32_t max_row = 0;   // the largest row index named, checked against the rows once they are known
-    bool any_row = false;
     auto name_row = [&](uint32_t row) {
-        any_row = true;
-        if (row > max_row) max_row = row;
+        C.any_row = true;
+        if (row > C.max_row) C.max_row = row;
         return (uint8_t)(row < KZG_MAX_BATCH_OPEN ? row : 0);
     };
     for (uint32_t u = 0, at = 0; u < gate->n_terms; u++) {
@@ -1130,7 +1148,7 @@ static int rows_quotient_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles
         qp.term_len[u] = (uint8_t)gate->term_lens[u];
         for (uint32_t f = 0; f < gate->term_lens[u]; f++, at++) {
             qp.term_row[u][f] = name_row(gate->term_rows[at]);
-            if (gate->term_rots && gate->term_rots[at]) rots[u][f] = gate->term_rots[at], qp.ext = 1;
+            if (gate->term_rots && gate->term_rots[at]) C.rots[u][f] = gate->term_rots[at], qp.ext = 1;
         }
     }
     if (k) {
@@ -1164,6 +1182,36 @@ static int rows_quotient_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles
         qp.ext = qp.active = 1;
         qp.active_row = name_row(active->active_row);
     }
+    if (link) {
+        qp.ext = qp.link = 1;
+        qp.link_row = name_row(link->prev_row);
+        C.link_rot = link->rot;
+    }
+    return KZG_OK;
+}
+// ... and against the rows once the lookup has found them: row indices, the worker, the row length, the rotations mod T
+static int quot_plan_rows(kzg_ctx* ctx, QuotCall& C, uint32_t n, uint32_t i, uint64_t T) {
+    if (C.any_row && C.max_row >= n) return fail(ctx, KZG_E_ARG, "quotient: a row index is not below the number of rows named");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "quotient: the row length must be a power of two");
+    auto reduce = [&](int32_t rot) { return (uint32_t)(((int64_t)rot % (int64_t)T + (int64_t)T) % (int64_t)T); };
+    for (uint32_t u = 0; u < C.qp.n_terms; u++)   // any int32 rotation, reduced into [0, T)
+        for (uint32_t f = 0; f < C.qp.term_len[u]; f++) C.qp.term_rot[u][f] = reduce(C.rots[u][f]);
+    C.qp.link_rot = reduce(C.link_rot);
+    return KZG_OK;
+}
+
+// kzg_rows_commit_quotient_ext (and, with no rotation and no lookup part, kzg_rows_commit_quotient: `plain`, which only words
+// one message): the lookups of an open (one handle list), the reservation of a commit
+// active: the caller's column A of kzg_rows_commit_quotient_zk, a factor of P1 and LK1 (null: neither has it)
+static int rows_quotient_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                             const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
+                             const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces,
+                             uint8_t* out_commitments48, uint64_t* out_handle, bool plain) {
+    if (!ctx || !handles || !gate || !out_commitments48 || !out_handle) return KZG_E_ARG;
+    QuotCall C;
+    if (int rc = quot_plan(ctx, gate, perm, nullptr, lookup, active, ext_log, &n_pieces, n_handles, plain, C)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     RowsPending pend{ctx};
     RowsRefs refs{ctx};
@@ -1174,26 +1222,154 @@ static int rows_quotient_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles
     uint32_t n = 0, i = 0;
     uint64_t T = 0;
     if (int rc = rows_lookup(ctx, "quotient", expect_i, n_handles, handles, refs, rt, &n, &i, &T)) return rc;
-    if (any_row && max_row >= n) return fail(ctx, KZG_E_ARG, "quotient: a row index is not below the number of rows named");
-    int rc = check_worker(ctx, i, T);
-    if (rc) return rc;
-    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "quotient: the row length must be a power of two");
-    for (uint32_t u = 0; u < qp.n_terms; u++)   // any int32 rotation, reduced into [0, T)
-        for (uint32_t f = 0; f < qp.term_len[u]; f++)
-            qp.term_rot[u][f] = (uint32_t)(((int64_t)rots[u][f] % (int64_t)T + (int64_t)T) % (int64_t)T);
+    if (int rc = quot_plan_rows(ctx, C, n, i, T)) return rc;
     if (int rc2 = rows_reserve(ctx, "quotient", pend, (size_t)n_pieces * T * 32)) return rc2;
     prof_begin(ctx, L);
-    rc = clear_flags(ctx, L);
+    int rc = clear_flags(ctx, L);
     if (rc) return rc;
     bool bad_shape = false;
     uint8_t c48[48 * 8];
-    rc = rows_quotient_dev(ctx, H, i, rt, n, T, qp, n_pieces, pend.buf.as<uint32_t>(), c48, &bad_shape);
+    rc = rows_quotient_dev(ctx, H, i, rt, n, T, C.qp, n_pieces, pend.buf.as<uint32_t>(), c48, &bad_shape);
     if (rc) return rc;
     if (bad_shape)
         return fail(ctx, KZG_E_ARG, "quotient: t has a nonzero coefficient at or above n_pieces * T: the constraints do not hold "
                                     "on the domain, or n_pieces is too small; no set was created");
     memcpy(out_commitments48, c48, 48 * (size_t)n_pieces);
     *out_handle = rows_insert(ctx, pend, i, n_pieces, T);
+    return KZG_OK;
+}
+
+// ---- the quotient in parts (kzg_rows_quotient_part / kzg_rows_quotient_finish).  The accumulator is an entry of the set table
+// (RowSet::acc): handle, cap, stats, staleness, release and free list are the sets'; rows_lookup refuses it everywhere else.
+// the accumulator `h` for a part or the finish (under sets_mu inside; lane held): one reference into refs
+static int acc_lookup(kzg_ctx* ctx, const char* what, uint32_t expect_i, uint64_t h, RowsRefs& refs, kzg_ctx::RowSet** out) {
+    auto bad = [&](const char* why) { return fail(ctx, KZG_E_ARG, std::string(what) + why); };
+    std::lock_guard<std::mutex> lk(ctx->sets_mu);
+    auto it = ctx->sets.find(h);
+    if (it == ctx->sets.end() || it->second.released) return bad(": unknown, released or consumed accumulator handle");
+    kzg_ctx::RowSet& st = it->second;
+    if (!st.acc) return bad(": the handle names a row set, not a quotient accumulator");
+    if (st.stale)
+        return bad(": the accumulator is stale (the SRS was reloaded, or an add into it failed on the device): release it and "
+                   "add its parts again");
+    if (expect_i != UINT32_MAX && st.i != expect_i) return bad(": the accumulator belongs to another worker");
+    st.refs++;
+    refs.h[refs.n++] = h;
+    *out = &st;   // (map nodes do not move; the reference keeps this one from being erased)
+    return KZG_OK;
+}
+int rows_quotient_part_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                            const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                            const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
+                            const uint8_t* scale_be32, uint64_t* inout_acc) {
+    if (!ctx || !handles || !gate || !inout_acc) return KZG_E_ARG;
+    if (scale_be32 && !fr_be32_canonical(scale_be32))
+        return fail(ctx, KZG_E_ARG, "quotient part: scale must be a canonical scalar (< r)");
+    QuotCall C;
+    if (int rc = quot_plan(ctx, gate, perm, link, lookup, active, ext_log, nullptr, n_handles, false, C)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs refs{ctx}, arefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the buffers under this call)
+    Lane& L = H.L();
+    RowTab rt;
+    uint32_t n = 0, i = 0;
+    uint64_t T = 0;
+    if (int rc = rows_lookup(ctx, "quotient part", expect_i, n_handles, handles, refs, rt, &n, &i, &T)) return rc;
+    if (int rc = quot_plan_rows(ctx, C, n, i, T)) return rc;
+    const bool first = *inout_acc == 0;
+    const uint64_t h = *inout_acc;
+    kzg_ctx::RowSet* acc = nullptr;
+    if (first) {
+        if (int rc = rows_reserve(ctx, "quotient part", pend, ((size_t)T << ext_log) * 32)) return rc;
+    } else {
+        if (int rc = acc_lookup(ctx, "quotient part", expect_i, h, arefs, &acc)) return rc;
+        if (acc->i != i || acc->T != T || acc->acc_ext_log != ext_log)
+            return fail(ctx, KZG_E_ARG, "quotient part: the part's worker, row length and ext_log must be the accumulator's");
+    }
+    prof_begin(ctx, L);
+    int rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    rc = rows_quotient_front_dev(ctx, H, rt, n, T, C.qp);
+    if (rc) return rc;
+    // the add: under the accumulator's mutex from its launch to the end of the call (a first part has no one to wait for).  A
+    // later part looks again once it holds the mutex: a finish or a failed add may have come in between.  Any failure behind
+    // the launch leaves contents nobody can vouch for: the accumulator goes stale (only KZG_E_HIP can happen: every scalar
+    // was checked on the host)
+    std::unique_lock<std::mutex> alk;
+    if (!first) {
+        alk = std::unique_lock<std::mutex>(*acc->acc_mu);
+        std::lock_guard<std::mutex> lk(ctx->sets_mu);
+        if (acc->released || acc->stale)
+            return fail(ctx, KZG_E_ARG, "quotient part: the accumulator was consumed, released or made stale meanwhile");
+    }
+    rc = rows_quotient_add_dev(ctx, H, T, ext_log, scale_be32, first ? pend.buf.as<uint32_t>() : acc->buf.as<uint32_t>(), first);
+    if (rc) {
+        if (!first) {
+            std::lock_guard<std::mutex> lk(ctx->sets_mu);
+            acc->stale = true;
+        }
+        return rc;
+    }
+    if (first) {
+        const uint64_t nh = ++g_row_set_handles;
+        std::lock_guard<std::mutex> lk(ctx->sets_mu);
+        kzg_ctx::RowSet& st = ctx->sets[nh];
+        st.i = i;
+        st.k = 0;
+        st.T = T;
+        st.acc = true;
+        st.acc_ext_log = ext_log;
+        st.acc_mu.reset(new std::mutex);
+        st.buf = std::move(pend.buf);
+        ctx->sets_pending--;
+        pend.reserved = false;
+        *inout_acc = nh;
+    }
+    return KZG_OK;
+}
+int rows_quotient_finish_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t acc_handle, uint32_t n_pieces, uint8_t* out_commitments48,
+                              uint64_t* out_handle) {
+    if (!ctx || !out_commitments48 || !out_handle) return KZG_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs arefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;
+    Lane& L = H.L();
+    kzg_ctx::RowSet* acc = nullptr;
+    if (int rc = acc_lookup(ctx, "quotient finish", expect_i, acc_handle, arefs, &acc)) return rc;
+    const uint32_t i = acc->i, ext_log = acc->acc_ext_log;
+    const uint64_t T = acc->T;
+    if (n_pieces == 0 || n_pieces > (1u << ext_log))
+        return fail(ctx, KZG_E_ARG, "quotient finish: n_pieces must be in [1, 2^ext_log]");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    std::unique_lock<std::mutex> alk(*acc->acc_mu);   // no part is between its add's launch and its end
+    {
+        std::lock_guard<std::mutex> lk(ctx->sets_mu);
+        if (acc->released || acc->stale)
+            return fail(ctx, KZG_E_ARG, "quotient finish: the accumulator was consumed, released or made stale meanwhile");
+    }
+    if (int rc2 = rows_reserve(ctx, "quotient finish", pend, (size_t)n_pieces * T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    bool bad_shape = false;
+    uint8_t c48[48 * 8];
+    rc = rows_quotient_finish_dev(ctx, H, i, T, (int)ext_log, acc->buf.as<uint32_t>(), n_pieces, pend.buf.as<uint32_t>(), c48,
+                                  &bad_shape);
+    if (rc) return rc;
+    if (bad_shape)
+        return fail(ctx, KZG_E_ARG, "quotient finish: t has a nonzero coefficient at or above n_pieces * T: the constraints do not "
+                                    "hold on the domain, or n_pieces is too small; no set was created and the accumulator stays");
+    memcpy(out_commitments48, c48, 48 * (size_t)n_pieces);
+    *out_handle = rows_insert(ctx, pend, i, n_pieces, T);
+    {   // consumed: the handle is unlinked now, the buffer goes to the free list when this call's reference drops
+        std::lock_guard<std::mutex> lk(ctx->sets_mu);
+        acc->released = true;
+    }
     return KZG_OK;
 }
 int rows_quotient_ext_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
@@ -1346,6 +1522,24 @@ int kzg_rows_commit_quotient_zk(kzg_ctx* ctx, uint32_t n_handles, const uint64_t
                                 uint8_t* out_commitments48, uint64_t* out_handle) {
     return rows_quotient_zk_impl(ctx, UINT32_MAX, n_handles, handles, gate, perm, lookup, active, ext_log, n_pieces,
                                  out_commitments48, out_handle);
+}
+int kzg_rows_quotient_part(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
+                           const kzg_quotient_perm* perm, const kzg_quotient_link* link, const kzg_quotient_lookup* lookup,
+                           const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32, uint64_t* inout_acc) {
+    return rows_quotient_part_impl(ctx, UINT32_MAX, n_handles, handles, gate, perm, link, lookup, active, ext_log, scale_be32,
+                                   inout_acc);
+}
+int kzg_rows_quotient_finish(kzg_ctx* ctx, uint64_t acc, uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle) {
+    return rows_quotient_finish_impl(ctx, UINT32_MAX, acc, n_pieces, out_commitments48, out_handle);
+}
+int kzg_rows_commit_grand_product_chain(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                        uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
+                                        const uint8_t* shifts_be32, const uint8_t beta_be32[32], const uint8_t gamma_be32[32],
+                                        uint64_t usable, const uint8_t* tail_be32, const uint8_t start_be32[32],
+                                        uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle) {
+    return rows_grand_product_chain_impl(ctx, UINT32_MAX, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k,
+                                         shifts_be32, beta_be32, gamma_be32, usable, tail_be32, start_be32, out_commitment48,
+                                         out_closing32, out_handle);
 }
 int kzg_rows_release(kzg_ctx* ctx, uint64_t handle) { return rows_release_impl(ctx, UINT32_MAX, handle); }
 int kzg_rows_stats(kzg_ctx* ctx, uint64_t out_live_sets_bytes[2]) {

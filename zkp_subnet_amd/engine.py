@@ -571,11 +571,28 @@ class HipEngine:
         return self._commit_quotient_ext("commit_quotient_zk", sets, terms, perm, lookup, active_row, ext_log, n_pieces)
 
     def _commit_quotient_ext(self, what, sets, terms, perm, lookup, active_row, ext_log, n_pieces) -> "RowSet":
+        n, hs, gate, pm, lk, act = self._quotient_args(what, sets, terms, perm, lookup, active_row, ext_log, n_pieces)
+        c, h = ctypes.create_string_buffer(48 * n_pieces), ctypes.c_uint64(0)
+        pm_ref = ctypes.byref(pm) if pm is not None else None
+        lk_ref = ctypes.byref(lk) if lk is not None else None
+        if act is None:
+            self._chk(self._lib.kzg_rows_commit_quotient_ext(self._h, n, hs, ctypes.byref(gate), pm_ref, lk_ref, ext_log,
+                                                             n_pieces, c, ctypes.byref(h)))
+        else:
+            self._chk(self._lib.kzg_rows_commit_quotient_zk(self._h, n, hs, ctypes.byref(gate), pm_ref, lk_ref, ctypes.byref(act),
+                                                            ext_log, n_pieces, c, ctypes.byref(h)))
+        src = next((x for x in sets if hasattr(x, "T")), None)
+        return RowSet(self, h.value, getattr(src, "i", None), n_pieces, getattr(src, "T", None),
+                      [c.raw[48 * p:48 * p + 48] for p in range(n_pieces)])
+
+    def _quotient_args(self, what, sets, terms, perm, lookup, active_row, ext_log, n_pieces):
+        """The checks and the ctypes forms shared by commit_quotient_ext / _zk and quotient_part (n_pieces None: a part has
+        none): (n, handles, QuotientTerms, QuotientPerm or None, QuotientLookup or None, QuotientActive or None)."""
         n, hs = self._handle_array(sets, what)
         bad = lambda why: KzgError(_native.KZG_E_ARG, what + ": " + why)   # noqa: E731
         if active_row is not None and (not isinstance(active_row, int) or not 0 <= active_row < 1 << 32):
             raise bad("active_row must be a non-negative integer below 2^32")
-        if ext_log not in (1, 2, 3) or not 1 <= n_pieces <= 1 << ext_log:
+        if ext_log not in (1, 2, 3) or (n_pieces is not None and not 1 <= n_pieces <= 1 << ext_log):
             raise bad("ext_log must be 1, 2 or 3 and n_pieces in [1, 2^ext_log]")
         E = 1 << ext_log
         try:
@@ -636,19 +653,83 @@ class HipEngine:
         rows_arr = (ctypes.c_uint32 * max(len(flat), 1))(*[j for j, _ in flat])
         rots_arr = (ctypes.c_int32 * max(len(flat), 1))(*[rot for _, rot in flat])
         gate = _native.QuotientTerms(len(tt), b"".join(c for c, _ in tt), lens, rows_arr, rots_arr)
-        c, h = ctypes.create_string_buffer(48 * n_pieces), ctypes.c_uint64(0)
-        pm_ref = ctypes.byref(pm) if pm is not None else None
-        lk_ref = ctypes.byref(lk) if lk is not None else None
-        if active_row is None:
-            self._chk(self._lib.kzg_rows_commit_quotient_ext(self._h, n, hs, ctypes.byref(gate), pm_ref, lk_ref, ext_log,
-                                                             n_pieces, c, ctypes.byref(h)))
-        else:
-            act = _native.QuotientActive(active_row)
-            self._chk(self._lib.kzg_rows_commit_quotient_zk(self._h, n, hs, ctypes.byref(gate), pm_ref, lk_ref, ctypes.byref(act),
-                                                            ext_log, n_pieces, c, ctypes.byref(h)))
+        gate._keep = (lens, rows_arr, rots_arr)   # the arrays live as long as the structure that points at them
+        return n, hs, gate, pm, lk, (None if active_row is None else _native.QuotientActive(active_row))
+
+    # ---- the quotient in parts: circuits that fit no single call (more than 16 rows, more permuted columns than 2^ext_log - 1,
+    # several permutation or lookup arguments) sum their numerator on the device over several calls
+    def quotient_part(self, sets: Sequence[object], terms: Sequence[Tuple[bytes, Sequence[object]]], perm: Optional[dict] = None,
+                      lookup: Optional[dict] = None, active_row: Optional[int] = None, link: Optional[Tuple[int, int]] = None,
+                      ext_log: int = 2, scale_be32: Optional[bytes] = None, acc: Optional["QuotientAcc"] = None) -> "QuotientAcc":
+        """One part of a quotient (kzg_rows_quotient_part): this part's numerator over the concatenated rows of `sets`, with
+        terms, perm, lookup and active_row as in commit_quotient_zk and its own row numbering, divided by Z_H on the coset,
+        multiplied by scale_be32 (32 bytes, None: 1) and added into `acc` (None: a new accumulator).  link: None, or (prev_row,
+        rot): P2 becomes (z(X) - f_prev(w^rot X)) L_0(X), the chain relation of a chunked permutation (needs perm).  Returns
+        the accumulator (a QuotientAcc; the one passed in, or the new one); quotient_finish turns it into the pieces.  Each part
+        re-extends the rows it names."""
+        n, hs, gate, pm, lk, act = self._quotient_args("quotient_part", sets, terms, perm, lookup, active_row, ext_log, None)
+        bad = lambda why: KzgError(_native.KZG_E_ARG, "quotient_part: " + why)   # noqa: E731
+        ln = None
+        if link is not None:
+            try:
+                prev_row, rot = int(link[0]), int(link[1])
+                if len(link) != 2:
+                    raise ValueError("a link is a (prev_row, rot) pair")
+            except (TypeError, ValueError, IndexError) as e:
+                raise bad(f"malformed link: {e!r}") from e
+            if not 0 <= prev_row < 1 << 32 or not -(1 << 31) <= rot < 1 << 31:
+                raise bad("the link's row must be a non-negative integer below 2^32 and its rotation must fit an int32")
+            if pm is None:
+                raise bad("a link needs a permutation part")
+            ln = _native.QuotientLink(prev_row, rot)
+        if scale_be32 is not None and len(scale_be32) != 32:
+            raise bad("scale must be 32 bytes or None")
+        if acc is not None and not isinstance(acc, QuotientAcc):
+            raise bad("acc must be a QuotientAcc returned by quotient_part, or None")
+        h = ctypes.c_uint64(0 if acc is None else acc.handle)
+        self._chk(self._lib.kzg_rows_quotient_part(self._h, n, hs, ctypes.byref(gate), ctypes.byref(pm) if pm is not None else None,
+                                                   ctypes.byref(ln) if ln is not None else None,
+                                                   ctypes.byref(lk) if lk is not None else None,
+                                                   ctypes.byref(act) if act is not None else None, ext_log, scale_be32,
+                                                   ctypes.byref(h)))
+        if acc is not None:
+            return acc
         src = next((x for x in sets if hasattr(x, "T")), None)
-        return RowSet(self, h.value, getattr(src, "i", None), n_pieces, getattr(src, "T", None),
-                      [c.raw[48 * p:48 * p + 48] for p in range(n_pieces)])
+        i, T = (src.i, src.T) if src is not None else next(
+            (self._set_len[int(x)] for x in sets if not hasattr(x, "handle") and int(x) in self._set_len), (None, None))
+        return QuotientAcc(self, h.value, i, T, ext_log)
+
+    def quotient_finish(self, acc: "QuotientAcc", n_pieces: int = 3) -> "RowSet":
+        """The pieces of the accumulated quotient (kzg_rows_quotient_finish) as a new RowSet of n_pieces rows; the accumulator
+        is consumed.  KzgError(KZG_E_ARG) when t does not fit n_pieces rows (the constraints do not hold, or n_pieces is too
+        small): no set is created then and the accumulator stays live, for the caller to release."""
+        if not isinstance(acc, QuotientAcc):
+            raise KzgError(_native.KZG_E_ARG, "quotient_finish: acc must be a QuotientAcc returned by quotient_part")
+        if not isinstance(n_pieces, int) or not 1 <= n_pieces <= 8:
+            raise KzgError(_native.KZG_E_ARG, "quotient_finish: n_pieces must be in [1, 2^ext_log]")
+        c, h = ctypes.create_string_buffer(48 * n_pieces), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_quotient_finish(self._h, acc.handle, n_pieces, c, ctypes.byref(h)))
+        acc.released = True   # consumed: its handle is dead
+        return RowSet(self, h.value, acc.i, n_pieces, acc.T, [c.raw[48 * p:48 * p + 48] for p in range(n_pieces)])
+
+    def commit_grand_product_chain(self, wire_sets: Sequence[object], sigma_sets: Sequence[object], shifts_be32: Sequence[bytes],
+                                   beta_be32: bytes, gamma_be32: bytes, usable: int, tail_be32: Sequence[bytes],
+                                   start_be32: bytes) -> Tuple["RowSet", bytes]:
+        """commit_grand_product_zk whose z starts at start_be32 instead of 1 (kzg_rows_commit_grand_product_chain): the chunk of
+        a chained permutation.  z(w^usable) = start * prod N / prod D is the closing value, the next chunk's start; the tail is
+        untouched by start.  start must be canonical and not 0."""
+        nw, hw = self._handle_array(wire_sets, "commit_grand_product_chain (wires)")
+        ns, hs = self._handle_array(sigma_sets, "commit_grand_product_chain (sigmas)")
+        k = len(shifts_be32)
+        if k == 0 or k > _native.KZG_MAX_BATCH_OPEN or \
+                any(len(x) != 32 for x in list(shifts_be32) + [beta_be32, gamma_be32, start_be32]):
+            raise KzgError(_native.KZG_E_ARG, f"commit_grand_product_chain: 1 .. {_native.KZG_MAX_BATCH_OPEN} shifts, beta, "
+                                              "gamma and start of 32 bytes each")
+        usable, tail, wi, T = self._blind_args("commit_grand_product_chain", list(wire_sets) + list(sigma_sets), usable, tail_be32)
+        c, cl, h = ctypes.create_string_buffer(48), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_grand_product_chain(self._h, nw, hw, ns, hs, k, b"".join(shifts_be32), beta_be32,
+                                                                gamma_be32, usable, tail, start_be32, c, cl, ctypes.byref(h)))
+        return RowSet(self, h.value, wi, 1, T, [c.raw]), cl.raw
 
     def _handle_array(self, sets, what):
         handles = [int(getattr(x, "handle", x)) for x in sets]
@@ -1040,3 +1121,28 @@ class RowSet:
 
     def __repr__(self) -> str:
         return f"RowSet(handle={self.handle}, i={self.i}, k={self.k}, T={self.T})"
+
+
+class QuotientAcc:
+    """The accumulator of HipEngine.quotient_part: `handle`, worker `i`, row length `T` and `ext_log` of a device vector of
+    T << ext_log field elements.  Not a row set: only quotient_part and quotient_finish take it.  release() frees it (a
+    finished accumulator is consumed and needs none); a `with` block releases on exit."""
+
+    def __init__(self, engine, handle: int, i: int, T: int, ext_log: int):
+        self.engine, self.handle, self.i, self.T, self.ext_log = engine, handle, i, T, ext_log
+        self.released = False
+
+    def release(self) -> None:
+        if not self.released:
+            self.released = True
+            self.engine.release_rows(self.handle)
+
+    def __enter__(self) -> "QuotientAcc":
+        return self
+
+    def __exit__(self, *exc) -> bool:
+        self.release()
+        return False
+
+    def __repr__(self) -> str:
+        return f"QuotientAcc(handle={self.handle}, i={self.i}, T={self.T}, ext_log={self.ext_log})"

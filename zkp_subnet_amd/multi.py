@@ -226,6 +226,37 @@ class MultiDeviceClient:
         return self._routed_builder("worker_commit_quotient_zk", handles, handles, terms, perm, lookup, active_row, ext_log,
                                     n_pieces)
 
+    def worker_quotient_part(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None, link=None, ext_log=2,
+                             scale=None, acc=None):
+        try:
+            i = self._owner(list(handles) + ([acc] if acc is not None else []))
+        except TypeError:
+            i = None
+        if i is None:
+            return Response(400, {"error": "worker_quotient_part: the handles and the accumulator must be live and of one worker"})
+        r = self._for(i).worker_quotient_part(handles, terms, perm, lookup, active_row, link, ext_log, scale, acc)
+        if r.status_code == 200:
+            self._row_owner[int(r.json()["acc"])] = i
+        return r
+
+    def worker_quotient_finish(self, acc: int, n_pieces=3):
+        try:
+            i = self._owner([acc])
+        except TypeError:
+            i = None
+        if i is None:
+            return Response(400, {"error": "worker_quotient_finish: unknown accumulator handle"})
+        r = self._for(i).worker_quotient_finish(acc, n_pieces)
+        if r.status_code == 200:
+            self._row_owner.pop(int(acc), None)
+            self._row_owner[int(r.json()["handle"])] = i
+        return r
+
+    def worker_commit_grand_product_chain(self, wire_handles: Sequence[int], sigma_handles: Sequence[int], shifts, beta, gamma,
+                                          usable, tail, start):
+        return self._routed_builder("worker_commit_grand_product_chain", list(wire_handles) + list(sigma_handles), wire_handles,
+                                    sigma_handles, shifts, beta, gamma, usable, tail, start)
+
     def worker_release_rows(self, handle: int):
         i = self._owner([handle])
         if i is None:
