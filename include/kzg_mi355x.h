@@ -269,8 +269,8 @@ int kzg_rows_commit_grand_product(kzg_ctx* ctx, uint32_t n_wire_handles, const u
  * That quotient term (it needs S at X and w_T X, i.e. gate factors with a rotation) is the lookup part of
  * kzg_rows_commit_quotient_ext.
  * m itself is built and committed on the device by kzg_rows_commit_multiplicities.
- * OUT OF SCOPE: per-row selectors (a caller points inactive rows at a default table entry); plookup.  Blinding rows:
- * kzg_rows_commit_lookup_sum_zk below. */
+ * Per-row selectors (a lookup enabled only on some rows): kzg_rows_commit_lookup_sum_sel below.  OUT OF SCOPE: plookup, a
+ * selector on the table side.  Blinding rows: kzg_rows_commit_lookup_sum_zk below. */
 int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
                                uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
                                uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32], const uint8_t beta_be32[32],
@@ -302,7 +302,8 @@ int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uin
  * kzg_rows_open.  Thread-safe like every call; after any error the context keeps serving.
  * SOUNDNESS: nothing here is a proof.  m is prover data like any witness row; the argument is the relation of
  * kzg_rows_commit_quotient_ext over S, with theta and beta drawn AFTER this call's commitment is fixed.  No blinding.
- * OUT OF SCOPE: per-row selectors, plookup (as above).  Blinding rows: kzg_rows_commit_multiplicities_zk below. */
+ * Per-row selectors: kzg_rows_commit_multiplicities_sel below.  OUT OF SCOPE: plookup, a selector on the table side (as
+ * above).  Blinding rows: kzg_rows_commit_multiplicities_zk below. */
 int kzg_rows_commit_multiplicities(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
                                    uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
                                    uint8_t out_commitment48[48], uint64_t* out_missing, uint64_t* out_handle);
@@ -382,7 +383,8 @@ int kzg_rows_commit_quotient(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* h
  * n_terms = 0 makes it empty).
  * SOUNDNESS: alpha must be drawn AFTER the commitments of S and z are fixed; theta and beta AFTER the commitments of the
  * inputs, the table and m (as for kzg_rows_commit_lookup_sum; kzg_rows_commit_multiplicities builds and commits m on the
- * device).  Still out of scope: per-row selectors, plookup.  Blinding rows: kzg_rows_commit_quotient_zk below. */
+ * device).  Lookups enabled on some rows only: kzg_rows_commit_quotient_sel below.  Still out of scope: plookup, a selector
+ * on the table side.  Blinding rows: kzg_rows_commit_quotient_zk below. */
 typedef struct kzg_quotient_terms {
     uint32_t n_terms;
     const uint8_t* coeffs_be32;  /* n_terms * 32 */
@@ -438,7 +440,8 @@ int kzg_rows_commit_quotient_ext(kzg_ctx* ctx, uint32_t n_handles, const uint64_
  * pieces are opened only through the combination sum_p zeta^(pT) t_p (kzg_rows_open_lincomb), whose value the identity already
  * fixes.  Challenges are still the caller's and are drawn as before (beta, gamma after the wires; theta, beta after the
  * inputs, the table and m; alpha after z and S).  Degree-raising blinders (b Z_H) do not fit a T-point slice and stay out of
- * scope, as do per-row selectors and plookup. */
+ * scope, as do plookup and a selector on the table side.  Lookups enabled on some rows only: the _sel calls below (the
+ * builders take usable and tail like the calls here, the quotient calls take the active column). */
 #define KZG_MAX_BLIND_ROWS 32
 typedef struct kzg_quotient_active {
     uint32_t active_row;         /* A */
@@ -463,6 +466,52 @@ int kzg_rows_commit_quotient_zk(kzg_ctx* ctx, uint32_t n_handles, const uint64_t
                                 const kzg_quotient_lookup* lookup /* NULL: none */,
                                 const kzg_quotient_active* active /* NULL: kzg_rows_commit_quotient_ext */, uint32_t ext_log,
                                 uint32_t n_pieces, uint8_t* out_commitments48 /* n_pieces * 48 */, uint64_t* out_handle);
+/* LOOKUP SELECTORS: the multiplicities and the running sum for lookups that are enabled on some rows only (halo2's q * a).
+ * A selector is an ordinary resident row of the same worker and length, the caller's fixed column q_l.  Each lookup l < L has
+ * either one selector row or KZG_NO_SELECTOR (the constant 1); one row may serve several lookups.  sel_index[l] (L entries)
+ * is KZG_NO_SELECTOR or indexes the concatenated rows of the sel_handles sets (at most KZG_MAX_BATCH_OPEN rows, handle rules of
+ * kzg_rows_open), so a caller names its whole fixed set and picks the rows, without committing the selectors apart;
+ * n_sel_handles = 0 (sel_handles may then be NULL) is legal only when every entry is KZG_NO_SELECTOR.  With q_l = 1 for a
+ * lookup without a selector:
+ *   m(w_T^t) = #{ (l, t') : q_l(w_T^t') != 0 and first(in(l, t')) = t },
+ *   missing  = #{ (l, t') : q_l(w_T^t') != 0 and in(l, t') is no row of the table }
+ *   term_t   = sum_l q_l(w_T^t) / (beta + F_l(w_T^t))  -  m(w_T^t) / (beta + Tb(w_T^t))
+ * Multiplicities: cell (l, t) is probed exactly when q_l(w_T^t) != 0, compared as canonical words like the join's tuples; a
+ * probed cell counts 1 whatever the value of q_l there, and `missing` counts probed cells only.  The table rows are all built as
+ * before; the first-copy rule, the bounded walks and the overrun answer are unchanged.  Running sum: the fraction of lookup l
+ * has the numerator q_l(w_T^t), ANY element of Fr -- per lookup the update is (P, Q) <- (P d + q Q, Q d) with d = beta + F_l.
+ * From the two rules: m and S agree (the sum closes for a satisfied instance) exactly when q_l is 0 or 1 on the rows that
+ * count; the library does not judge q, as it judges no closing value.  A zero denominator is still KZG_E_ARG wherever the
+ * plain or _zk rule reads that row, whether the row is enabled or not (the quotient relation carries D_l on every row, and
+ * beta is random).
+ * Layout: usable and tail_be32 are those of the _zk calls (rows >= usable are neither probed nor summed, row usable closes,
+ * the tail behind); in addition usable == T with tail_be32 == NULL is the plain layout without a closing row.  So there is
+ * ONE _sel builder per stage.  With every entry KZG_NO_SELECTOR each call IS the existing one byte for byte and kernel for
+ * kernel (kzg_rows_commit_multiplicities / _lookup_sum for usable == T, their _zk forms otherwise); an all-ones selector row
+ * gives the same bytes; selectors that are 0 everywhere give m = 0 on the circuit rows, missing = 0, S = 0 and closing 0.
+ * Cost: each DISTINCT selector row is brought to evaluation form once per call (one forward transform and one more T-element
+ * vector of lane workspace, counted in the KZG_E_NOMEM path); a selected lookup's probe reads 32 bytes more per cell and its
+ * step of the running fraction does one product more.  Lookups without a selector launch the existing kernels.
+ * Errors beyond the underlying call's (all KZG_E_ARG): sel_index NULL; sel_handles NULL with n_sel_handles > 0; more than
+ * KZG_MAX_BATCH_OPEN selector handles or rows; an entry that is neither KZG_NO_SELECTOR nor below the number of selector rows
+ * (so any real index with n_sel_handles = 0); a selector set of another worker or row length, or an unknown / released /
+ * stale one.  Everything else -- thread safety, a racing release or SRS load, "after any error the context keeps serving" --
+ * is the underlying call's.
+ * The quotient calls are declared behind kzg_rows_quotient_part below (THE QUOTIENT WITH LOOKUP SELECTORS). */
+#define KZG_NO_SELECTOR 0xffffffffu
+int kzg_rows_commit_multiplicities_sel(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                                       uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_sel_handles,
+                                       const uint64_t* sel_handles, const uint32_t* sel_index /* n_lookups */,
+                                       uint32_t n_lookups, uint32_t width, uint64_t usable,
+                                       const uint8_t* tail_be32 /* (T-usable-1)*32, or NULL */, uint8_t out_commitment48[48],
+                                       uint64_t* out_missing, uint64_t* out_handle);
+int kzg_rows_commit_lookup_sum_sel(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                                   uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
+                                   uint32_t n_sel_handles, const uint64_t* sel_handles,
+                                   const uint32_t* sel_index /* n_lookups */, uint32_t n_lookups, uint32_t width,
+                                   const uint8_t theta_be32[32], const uint8_t beta_be32[32], uint64_t usable,
+                                   const uint8_t* tail_be32 /* (T-usable-1)*32, or NULL */, uint8_t out_commitment48[48],
+                                   uint8_t out_closing32[32], uint64_t* out_handle);
 /* THE QUOTIENT IN PARTS, AND CHAINED GRAND PRODUCTS: circuits that fit no single quotient call -- more than 16 rows, more
  * permuted columns than E (E - 1 with an active column), several permutation or lookup arguments, more than 16 gate terms.
  * The quotient is linear in its numerator and the division by X^T - 1 is pointwise on the coset g H_N, so the numerator is
@@ -503,8 +552,8 @@ int kzg_rows_commit_quotient_zk(kzg_ctx* ctx, uint32_t n_handles, const uint64_t
  *   z_c and S are committed; the chunks' z_c must share beta and gamma; the verifier recomputes sum_p scale_p num_p(zeta) from
  *   the opened values, the link as (z_c(zeta) - z_{c-1}(w^u zeta)) L_0(zeta).
  * OUT OF SCOPE: an opening over more than 16 rows (a wide circuit opens in several kzg_rows_open_lincomb calls, one proof per
- *   call and point); sharing extended rows between parts; per-row selectors and plookup; degree-raising blinders; deriving
- *   challenges or scales (the library still draws nothing). */
+ *   call and point); sharing extended rows between parts; plookup; degree-raising blinders; deriving challenges or scales
+ *   (the library still draws nothing).  Lookup selectors in a part: kzg_rows_quotient_part_sel below. */
 typedef struct kzg_quotient_link {
     uint32_t prev_row;           /* f_prev: the previous chunk's z */
     int32_t rot;                 /* read at w^rot X */
@@ -521,6 +570,34 @@ int kzg_rows_commit_grand_product_chain(kzg_ctx* ctx, uint32_t n_wire_handles, c
                                         const uint8_t gamma_be32[32], uint64_t usable,
                                         const uint8_t* tail_be32 /* (T-usable-1)*32, or NULL */, const uint8_t start_be32[32],
                                         uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle);
+/* THE QUOTIENT WITH LOOKUP SELECTORS: kzg_rows_commit_quotient_zk and kzg_rows_quotient_part for lookups that are enabled on
+ * some rows only.  selectors->selector_rows holds L = lookup->n_lookups entries, each a row index into the call's concatenated
+ * rows (the caller's fixed column q_l, the row that kzg_rows_commit_multiplicities_sel / _lookup_sum_sel read) or
+ * KZG_NO_SELECTOR (the constant 1); one row may serve several lookups.  The selector becomes the numerator of its fraction, at
+ * no cost in degree.  With D_0 = beta + Tb, D_l = beta + F_l for lookup l = 1 .. L and q_l that lookup's selector:
+ *   LK1 = (S(w X) - S(X)) prod_{l=0..L} D_l  -  [ sum_{l=1..L} q_l prod_{l' != l, l'=0..L} D_l'  -  m prod_{l=1..L} D_l ]
+ * q_l prod_{l' != l} D_l' has L + 1 factors, still below the L + 2 of the first product: L <= E - 1 (E - 2 with an active
+ * column) and the piece counts stay as they are.  D_l stands on EVERY row, enabled or not.  A selector row is extended once
+ * like any row the call names and shares its extended vector if it is also a gate factor or the active column; a selected
+ * lookup costs one more 32-byte load and one more product per point.  selectors == NULL, or every entry KZG_NO_SELECTOR, IS
+ * the existing call (kzg_rows_commit_quotient_zk / kzg_rows_quotient_part), byte for byte and kernel for kernel; an all-ones
+ * selector row gives the same bytes.  Errors beyond the existing call's (all KZG_E_ARG): selectors != NULL with lookup ==
+ * NULL; a null selector_rows; a selector row index >= n.  Everything else -- handle rules, the accumulator, thread safety, a
+ * racing release or SRS load, "after any error the context keeps serving" -- is the existing call's. */
+typedef struct kzg_quotient_selectors {
+    const uint32_t* selector_rows;   /* L; row index or KZG_NO_SELECTOR */
+} kzg_quotient_selectors;
+int kzg_rows_commit_quotient_sel(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
+                                 const kzg_quotient_perm* perm /* NULL: none */,
+                                 const kzg_quotient_lookup* lookup /* NULL: none */,
+                                 const kzg_quotient_selectors* selectors /* NULL: kzg_rows_commit_quotient_zk */,
+                                 const kzg_quotient_active* active /* NULL: none */, uint32_t ext_log, uint32_t n_pieces,
+                                 uint8_t* out_commitments48 /* n_pieces * 48 */, uint64_t* out_handle);
+int kzg_rows_quotient_part_sel(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
+                               const kzg_quotient_perm* perm, const kzg_quotient_link* link, const kzg_quotient_lookup* lookup,
+                               const kzg_quotient_selectors* selectors /* NULL: kzg_rows_quotient_part */,
+                               const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32 /* NULL: 1 */,
+                               uint64_t* inout_acc);
 /* The UNCHANGED reference miner makes two calls per request with the same row -- worker_commit(i, poly), then
  * worker_open(i, poly, x) (neurons/miner.py:56-61).  These forms take a 128-bit content tag identifying the row's bytes
  * (the host codec computes it while decoding the text); the coefficient vectors of the last four rows stay on the
@@ -777,6 +854,18 @@ int kzg_multi_rows_commit_multiplicities_zk(kzg_multi* mh, uint32_t i, uint32_t 
                                             uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups,
                                             uint32_t width, uint64_t usable, const uint8_t* tail_be32,
                                             uint8_t out_commitment48[48], uint64_t* out_missing, uint64_t* out_handle);
+/* the kzg_rows_commit_*_sel builders on the device of worker i: every set named, selector sets included, must belong to worker i */
+int kzg_multi_rows_commit_lookup_sum_sel(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                         uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
+                                         uint32_t n_sel_handles, const uint64_t* sel_handles, const uint32_t* sel_index,
+                                         uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32],
+                                         const uint8_t beta_be32[32], uint64_t usable, const uint8_t* tail_be32,
+                                         uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle);
+int kzg_multi_rows_commit_multiplicities_sel(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                             uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_sel_handles,
+                                             const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups,
+                                             uint32_t width, uint64_t usable, const uint8_t* tail_be32,
+                                             uint8_t out_commitment48[48], uint64_t* out_missing, uint64_t* out_handle);
 int kzg_multi_rows_commit_quotient_zk(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
                                       const kzg_quotient_terms* gate, const kzg_quotient_perm* perm,
                                       const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
@@ -785,6 +874,16 @@ int kzg_multi_rows_quotient_part(kzg_multi* mh, uint32_t i, uint32_t n_handles, 
                                  const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
                                  const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
                                  const uint8_t* scale_be32, uint64_t* inout_acc);
+int kzg_multi_rows_commit_quotient_sel(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                       const kzg_quotient_terms* gate, const kzg_quotient_perm* perm,
+                                       const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
+                                       const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces,
+                                       uint8_t* out_commitments48, uint64_t* out_handle);
+int kzg_multi_rows_quotient_part_sel(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                     const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                                     const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
+                                     const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32,
+                                     uint64_t* inout_acc);
 int kzg_multi_rows_quotient_finish(kzg_multi* mh, uint32_t i, uint64_t acc, uint32_t n_pieces, uint8_t* out_commitments48,
                                    uint64_t* out_handle);
 int kzg_multi_rows_commit_grand_product_chain(kzg_multi* mh, uint32_t i, uint32_t n_wire_handles, const uint64_t* wire_handles,

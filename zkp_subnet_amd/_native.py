@@ -21,6 +21,7 @@ KZG_MAX_OPEN_POINTS = 4
 KZG_MAX_ROW_SETS = 64
 KZG_MAX_GATE_TERMS = 16   # kzg_rows_commit_quotient
 KZG_MAX_BLIND_ROWS = 32   # kzg_rows_commit_*_zk: T - usable
+KZG_NO_SELECTOR = 0xffffffff   # kzg_rows_commit_*_sel: a lookup without a selector row
 KZG_OK, KZG_E_ARG, KZG_E_SCALAR, KZG_E_POINT, KZG_E_HIP, KZG_E_NOMEM, KZG_E_BUSY, KZG_E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
 STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_SCALAR", -3: "E_POINT", -4: "E_HIP", -5: "E_NOMEM", -6: "E_BUSY", -7: "E_COMM"}
 TIMING_NAMES = ["decode", "ntt", "digits", "scan", "scatter", "accumulate", "fixup", "tree", "final", "poly", "total", "collective"]
@@ -58,6 +59,11 @@ class QuotientLookup(ctypes.Structure):
 class QuotientActive(ctypes.Structure):
     """kzg_quotient_active"""
     _fields_ = [("active_row", _U32)]
+
+
+class QuotientSelectors(ctypes.Structure):
+    """kzg_quotient_selectors"""
+    _fields_ = [("selector_rows", ctypes.POINTER(_U32))]
 
 
 class QuotientLink(ctypes.Structure):
@@ -112,6 +118,19 @@ SYMBOLS = {
                                            _B, _B, _B, ctypes.POINTER(_U64)]),
     "kzg_rows_commit_multiplicities_zk": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _U64, _B, _B,
                                                ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_lookup_sum_sel": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32,
+                                            ctypes.POINTER(_U64), ctypes.POINTER(_U32), _U32, _U32, _B, _B, _U64, _B, _B, _B,
+                                            ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_multiplicities_sel": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32,
+                                                ctypes.POINTER(_U64), ctypes.POINTER(_U32), _U32, _U32, _U64, _B, _B,
+                                                ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_quotient_sel": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms), ctypes.POINTER(QuotientPerm),
+                                          ctypes.POINTER(QuotientLookup), ctypes.POINTER(QuotientSelectors),
+                                          ctypes.POINTER(QuotientActive), _U32, _U32, _B, ctypes.POINTER(_U64)]),
+    "kzg_rows_quotient_part_sel": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms), ctypes.POINTER(QuotientPerm),
+                                        ctypes.POINTER(QuotientLink), ctypes.POINTER(QuotientLookup),
+                                        ctypes.POINTER(QuotientSelectors), ctypes.POINTER(QuotientActive), _U32, _B,
+                                        ctypes.POINTER(_U64)]),
     "kzg_rows_commit_quotient_zk": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms), ctypes.POINTER(QuotientPerm),
                                          ctypes.POINTER(QuotientLookup), ctypes.POINTER(QuotientActive), _U32, _U32, _B,
                                          ctypes.POINTER(_U64)]),
@@ -195,6 +214,20 @@ SYMBOLS = {
                                                  _B, _B, _U64, _B, _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_multiplicities_zk": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32,
                                                      _U64, _B, _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_lookup_sum_sel": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32,
+                                                  ctypes.POINTER(_U64), ctypes.POINTER(_U32), _U32, _U32, _B, _B, _U64, _B, _B, _B,
+                                                  ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_multiplicities_sel": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32,
+                                                      ctypes.POINTER(_U64), ctypes.POINTER(_U32), _U32, _U32, _U64, _B, _B,
+                                                      ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_quotient_sel": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms),
+                                                ctypes.POINTER(QuotientPerm), ctypes.POINTER(QuotientLookup),
+                                                ctypes.POINTER(QuotientSelectors), ctypes.POINTER(QuotientActive), _U32, _U32, _B,
+                                                ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_quotient_part_sel": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms),
+                                              ctypes.POINTER(QuotientPerm), ctypes.POINTER(QuotientLink),
+                                              ctypes.POINTER(QuotientLookup), ctypes.POINTER(QuotientSelectors),
+                                              ctypes.POINTER(QuotientActive), _U32, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_quotient_zk": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(QuotientTerms),
                                                ctypes.POINTER(QuotientPerm), ctypes.POINTER(QuotientLookup),
                                                ctypes.POINTER(QuotientActive), _U32, _U32, _B, ctypes.POINTER(_U64)]),

@@ -502,6 +502,70 @@ class Client:
         rs, missing = self.engine.commit_multiplicities_zk(hi, ht, n_lookups, width, usable, tb)
         return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]), "missing": int(missing)}
 
+    # ---- the two lookup builders with per-row selectors (kzg_rows_commit_*_sel)
+    @staticmethod
+    def _selectors(what: str, sel_handles, sel_index, n_lookups: int) -> tuple:
+        """sel_handles: [] or row-set handles; sel_index: per lookup None (no selector) or a row of their concatenation"""
+        hs = _handles(sel_handles) if sel_handles else []
+        try:
+            idx = [None if j is None else int(j) for j in sel_index]
+        except (TypeError, ValueError) as e:
+            raise codec.CodecError(f"{what}: sel_index must be a list of row indices or nulls: {e!r}") from e
+        if len(idx) != n_lookups or any(j is not None and not 0 <= j < KZG_MAX_BATCH_OPEN for j in idx):
+            raise codec.CodecError(f"{what}: sel_index must hold n_lookups = {n_lookups} entries, each null or a row index below "
+                                   f"{KZG_MAX_BATCH_OPEN}")
+        if not hs and any(j is not None for j in idx):
+            raise codec.CodecError(f"{what}: sel_index names a row but no selector handle was given")
+        return hs, idx
+
+    @_guard
+    def worker_commit_lookup_sum_sel(self, input_handles: Sequence[int], table_handles: Sequence[int], mult_handle: int,
+                                     sel_handles: Sequence[int], sel_index: Sequence[Optional[int]], n_lookups: int, width: int,
+                                     theta: str, beta: str, usable: Optional[int] = None, tail: Sequence[str] = ()):
+        """Extension: worker_commit_lookup_sum (usable = None) or worker_commit_lookup_sum_zk with per-row selectors: the
+        fraction of lookup l has the numerator q_l, row sel_index[l] of the concatenated rows of the sel_handles sets (null: the
+        constant 1).  The sum closes against worker_commit_multiplicities_sel's m when q_l is 0 or 1 on the rows that count."""
+        hi, ht, hm = _handles(input_handles), _handles(table_handles), _handles([mult_handle])[0]
+        try:
+            n_lookups, width = int(n_lookups), int(width)
+        except (TypeError, ValueError) as e:
+            raise codec.CodecError(f"worker_commit_lookup_sum_sel: n_lookups and width must be integers: {e!r}") from e
+        if n_lookups < 1 or width < 1 or n_lookups * width > KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"worker_commit_lookup_sum_sel: n_lookups = {n_lookups}, width = {width}, expected both >= 1 "
+                                   f"and n_lookups * width <= {KZG_MAX_BATCH_OPEN}")
+        hs, idx = self._selectors("worker_commit_lookup_sum_sel", sel_handles, sel_index, n_lookups)
+        sc = [codec.fr_to_be32(x) for x in (theta, beta)]
+        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in sc):
+            raise codec.CodecError("worker_commit_lookup_sum_sel: theta and beta must be canonical scalars (< r)")
+        tb = []
+        if usable is not None:
+            usable, tb = self._blind("worker_commit_lookup_sum_sel", usable, tail)
+        rs, closing = self.engine.commit_lookup_sum_sel(hi, ht, hm, hs, idx, n_lookups, width, sc[0], sc[1], usable, tb)
+        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]),
+                "closing": codec.be32_to_fr(closing)}
+
+    @_guard
+    def worker_commit_multiplicities_sel(self, input_handles: Sequence[int], table_handles: Sequence[int],
+                                         sel_handles: Sequence[int], sel_index: Sequence[Optional[int]], n_lookups: int,
+                                         width: int, usable: Optional[int] = None, tail: Sequence[str] = ()):
+        """Extension: worker_commit_multiplicities (usable = None) or worker_commit_multiplicities_zk with per-row selectors:
+        cell (l, t) is probed, and can be `missing`, only where row sel_index[l] of the concatenated rows of the sel_handles
+        sets is not zero at t (null: every cell).  A disabled cell may hold anything."""
+        hi, ht = _handles(input_handles), _handles(table_handles)
+        try:
+            n_lookups, width = int(n_lookups), int(width)
+        except (TypeError, ValueError) as e:
+            raise codec.CodecError(f"worker_commit_multiplicities_sel: n_lookups and width must be integers: {e!r}") from e
+        if n_lookups < 1 or width < 1 or n_lookups * width > KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"worker_commit_multiplicities_sel: n_lookups = {n_lookups}, width = {width}, expected both "
+                                   f">= 1 and n_lookups * width <= {KZG_MAX_BATCH_OPEN}")
+        hs, idx = self._selectors("worker_commit_multiplicities_sel", sel_handles, sel_index, n_lookups)
+        tb = []
+        if usable is not None:
+            usable, tb = self._blind("worker_commit_multiplicities_sel", usable, tail)
+        rs, missing = self.engine.commit_multiplicities_sel(hi, ht, hs, idx, n_lookups, width, usable, tb)
+        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]), "missing": int(missing)}
+
     @_guard
     def worker_commit_quotient_zk(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None,
                                   ext_log: int = 2, n_pieces: int = 3):
@@ -517,6 +581,37 @@ class Client:
         tt, pp, ll, ext_log, n_pieces = self._quotient_ext_parts("worker_commit_quotient_zk", terms, perm, lookup, ext_log,
                                                                  n_pieces)
         rs = self.engine.commit_quotient_zk(hs, tt, pp, ll, active_row, ext_log, n_pieces)
+        return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments]}
+
+    @staticmethod
+    def _quotient_selectors(what: str, selectors):
+        """per lookup null (no selector) or the row of the concatenation that holds q_l; None: the call without selectors"""
+        if selectors is None:
+            return None
+        try:
+            sel = [None if j is None else int(j) for j in selectors]
+        except (TypeError, ValueError) as e:
+            raise codec.CodecError(f"{what}: selectors must be a list of row indices or nulls: {e!r}") from e
+        if any(j is not None and not 0 <= j < KZG_MAX_BATCH_OPEN for j in sel):
+            raise codec.CodecError(f"{what}: a selector row index must be below {KZG_MAX_BATCH_OPEN}")
+        return sel
+
+    @_guard
+    def worker_commit_quotient_sel(self, handles: Sequence[int], terms, perm=None, lookup=None, selectors=None, active_row=None,
+                                   ext_log: int = 2, n_pieces: int = 3):
+        """Extension: worker_commit_quotient_zk for lookups that are enabled on some rows only: selectors[l] is the row (of the
+        concatenated sets) that holds q_l, the numerator of lookup l's fraction in the lookup relation, or null (the constant
+        1) -- the rows worker_commit_multiplicities_sel and worker_commit_lookup_sum_sel read.  selectors = None is
+        worker_commit_quotient_zk."""
+        hs = _handles(handles)
+        try:
+            active_row = None if active_row is None else int(active_row)
+        except (TypeError, ValueError) as e:
+            raise codec.CodecError(f"worker_commit_quotient_sel: active_row must be an integer or None: {e!r}") from e
+        sel = self._quotient_selectors("worker_commit_quotient_sel", selectors)
+        tt, pp, ll, ext_log, n_pieces = self._quotient_ext_parts("worker_commit_quotient_sel", terms, perm, lookup, ext_log,
+                                                                 n_pieces)
+        rs = self.engine.commit_quotient_sel(hs, tt, pp, ll, sel, active_row, ext_log, n_pieces)
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments]}
 
     @staticmethod
@@ -549,6 +644,15 @@ class Client:
 
     # ---- the quotient in parts and the chained grand product: circuits that fit no single worker_commit_quotient_zk call
     @_guard
+    def worker_quotient_part_sel(self, handles: Sequence[int], terms, perm=None, lookup=None, selectors=None, active_row=None,
+                                 link=None, ext_log: int = 2, scale=None, acc=None):
+        """Extension: worker_quotient_part with the lookup selectors of worker_commit_quotient_sel (selectors = None is
+        worker_quotient_part)."""
+        return self._quotient_part("worker_quotient_part_sel", handles, terms, perm, lookup,
+                                   self._quotient_selectors("worker_quotient_part_sel", selectors), active_row, link, ext_log,
+                                   scale, acc)
+
+    @_guard
     def worker_quotient_part(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None, link=None,
                              ext_log: int = 2, scale=None, acc=None):
         """Extension: one part of a quotient summed on the device over several calls.  handles, terms, perm, lookup and
@@ -557,6 +661,9 @@ class Client:
         scalar this part is multiplied by (the caller's power of alpha); acc: None (a new accumulator) or the handle an earlier
         part returned.  Returns {"acc": handle}.  worker_quotient_finish turns the accumulator into the pieces;
         worker_release_rows frees one that is not finished."""
+        return self._quotient_part("worker_quotient_part", handles, terms, perm, lookup, None, active_row, link, ext_log, scale, acc)
+
+    def _quotient_part(self, what, handles, terms, perm, lookup, sel, active_row, link, ext_log, scale, acc):
         hs = _handles(handles)
         try:
             active_row = None if active_row is None else int(active_row)
@@ -566,20 +673,23 @@ class Client:
             sc = None if scale is None else codec.fr_to_be32(scale)
             ah = None if acc is None else _handles([acc])[0]
         except (TypeError, ValueError, IndexError, KeyError) as e:
-            raise codec.CodecError(f"worker_quotient_part: active_row, link, scale and acc must be an integer, a [prev_row, rot] "
+            raise codec.CodecError(f"{what}: active_row, link, scale and acc must be an integer, a [prev_row, rot] "
                                    f"pair, a scalar and a handle (or None): {e!r}") from e
         if sc is not None and int.from_bytes(sc, "big") >= codec.R_MODULUS:
-            raise codec.CodecError("worker_quotient_part: scale must be a canonical scalar (< r)")
-        tt, pp, ll, ext_log, _ = self._quotient_ext_parts("worker_quotient_part", terms, perm, lookup, ext_log, 1)
+            raise codec.CodecError(f"{what}: scale must be a canonical scalar (< r)")
+        tt, pp, ll, ext_log, _ = self._quotient_ext_parts(what, terms, perm, lookup, ext_log, 1)
         if ln is not None and pp is None:
-            raise codec.CodecError("worker_quotient_part: a link needs a permutation part")
+            raise codec.CodecError(f"{what}: a link needs a permutation part")
         accs = self._accs
         a = None
         if ah is not None:
             a = accs.get(ah)
             if a is None:
-                raise codec.CodecError("worker_quotient_part: acc names no live accumulator of this client")
-        out = self.engine.quotient_part(hs, tt, pp, ll, active_row, ln, ext_log, sc, a)
+                raise codec.CodecError(f"{what}: acc names no live accumulator of this client")
+        if sel is None:
+            out = self.engine.quotient_part(hs, tt, pp, ll, active_row, ln, ext_log, sc, a)
+        else:
+            out = self.engine.quotient_part_sel(hs, tt, pp, ll, sel, active_row, ln, ext_log, sc, a)
         accs[int(out.handle)] = out
         return {"acc": int(out.handle)}
 

@@ -422,6 +422,15 @@ struct Blind {
     uint64_t usable;
     const uint8_t* tail_be32;
 };
+// The selectors of a kzg_rows_commit_*_sel builder (checked by the caller): the n DISTINCT resident rows the call names
+// (coefficients, like every row of a set) and, per lookup, which of them is its q_l (SEL_NONE: the constant 1, the lookup runs
+// through the kernels of the call without selectors).  Null, or every entry SEL_NONE: the builder without selectors.
+#define SEL_NONE 0xffu
+struct SelPlan {
+    uint32_t n;
+    const uint32_t* row[POLY_MAX_ROWS];
+    uint8_t of[POLY_MAX_ROWS];
+};
 // the grand product of k wire / sigma row pairs (rows read through the two tables) into a new one-row set's buffer dst:
 // its commitment, the closing value, and whether some denominator was zero (z undefined: the caller creates no set)
 int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& wires, const RowTab& sigmas, uint32_t k,
@@ -432,12 +441,13 @@ int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& 
 // set's buffer dst: its commitment, the closing value, and whether some denominator was zero (the caller creates no set)
 int rows_lookup_sum_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& table, const uint32_t* mult,
                         uint32_t n_lookups, uint32_t width, uint64_t T, const uint8_t* theta_be32, const uint8_t* beta_be32,
-                        uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den, const Blind* zk = nullptr);
+                        uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den, const Blind* zk = nullptr,
+                        const SelPlan* sel = nullptr);
 // the lookup multiplicities of n_lookups x width input rows against width table rows into a new one-row set's buffer dst: its
 // commitment, the number of cells whose tuple is no table row, and whether a probe walk reached its bound (no set then)
 int rows_multiplicities_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& table, uint32_t n_lookups,
                             uint32_t width, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_missing,
-                            bool* out_overrun, const Blind* zk = nullptr);
+                            bool* out_overrun, const Blind* zk = nullptr, const SelPlan* sel = nullptr);
 // the quotient pieces of the constraints qp over the n_rows coefficient rows of rt into a new n_pieces-row set's buffer dst:
 // their commitments, and whether a coefficient of t at or above n_pieces T was not zero (the caller creates no set)
 int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t n_rows, uint64_t T, const QuotPlan& qp,
@@ -479,6 +489,26 @@ int rows_multiplicities_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_inpu
                                 uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
                                 uint64_t usable, const uint8_t* tail_be32, uint8_t* out_commitment48, uint64_t* out_missing,
                                 uint64_t* out_handle);
+// the _sel builders (kzg_rows_commit_*_sel): the _zk call's arguments with the selector sets and sel_index behind the table
+int rows_lookup_sum_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                             uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
+                             uint32_t n_sel_handles, const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups,
+                             uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint64_t usable,
+                             const uint8_t* tail_be32, uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle);
+int rows_multiplicities_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                 uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_sel_handles,
+                                 const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups, uint32_t width,
+                                 uint64_t usable, const uint8_t* tail_be32, uint8_t* out_commitment48, uint64_t* out_missing,
+                                 uint64_t* out_handle);
+int rows_quotient_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
+                           const kzg_quotient_selectors* selectors, const kzg_quotient_active* active, uint32_t ext_log,
+                           uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle);
+int rows_quotient_part_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                                const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                                const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
+                                const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32,
+                                uint64_t* inout_acc);
 int rows_quotient_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
                           const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,

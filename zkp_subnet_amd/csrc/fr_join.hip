@@ -4,6 +4,7 @@
 // hashes words).  Column c of a tuple is cols + c * T * 8 words.
 //   build : slot[hash(tab(t)) ...] <- the SMALLEST t with that tuple              (open addressing, linear probing)
 //   probe : cnt[first(in(l, t))] += 1, or missing += 1                            (one launch per lookup)
+//           (_sel: only where the lookup's selector q_l(w^t) is not zero)
 //   counts: cnt[t] -> m(w^t) as a Montgomery element
 // A slot holds a table ROW INDEX or JOIN_EMPTY = 2^32 - 1 (T <= 2^27, so 0 and T - 1 are ordinary values).  No kernel here
 // multiplies (the last one: one product per element); they move bytes and chase one dependent load (slot -> row).
@@ -157,6 +158,43 @@ __global__ void __launch_bounds__(256) k_join_probe_rows(const uint32_t* __restr
     if (threadIdx.x == 0 && wg_miss) atomicAdd(missing, (unsigned long long)wg_miss);
 }
 
+// kzg_rows_commit_multiplicities_sel: the probe of k_join_probe_rows for a lookup with a selector row.  sel holds q_l's T
+// evaluations (canonical Montgomery words like the tuples: 0 is eight zero words): one more 32-byte load per cell, and a lane
+// whose selector is zero neither walks nor counts a miss.  rows = T is the plain layout, rows = usable the _zk one.  A
+// kernel of its own: the two probes above keep their instructions, and a lookup without a selector still launches them.
+__global__ void __launch_bounds__(256) k_join_probe_sel(const uint32_t* __restrict__ tab, const uint32_t* __restrict__ in,
+                                                         const uint32_t* __restrict__ sel, uint64_t T, uint64_t rows, uint32_t w,
+                                                         const uint32_t* __restrict__ slots, uint32_t mask, uint32_t* cnt,
+                                                         unsigned long long* missing, uint32_t* overrun) {
+    __shared__ uint32_t wg_miss;
+    if (threadIdx.x == 0) wg_miss = 0;
+    __syncthreads();
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool miss = false;
+    if (t < rows) {
+        const uint4* sq = reinterpret_cast<const uint4*>(sel + 8 * t);
+        const uint4 s0 = sq[0], s1 = sq[1];
+        if (s0.x | s0.y | s0.z | s0.w | s1.x | s1.y | s1.z | s1.w) {
+            uint32_t s = join_hash(in, T, w, t) & mask;
+            bool done = false;
+            for (uint32_t step = 0; step <= mask; step++, s = (s + 1) & mask) {
+                const uint32_t q = slots[s];
+                if (q == JOIN_EMPTY) { miss = done = true; break; }
+                if (q < T && join_equal(tab, q, in, t, T, w)) {
+                    atomicAdd(cnt + q, 1u);
+                    done = true;
+                    break;
+                }
+            }
+            if (!done) atomicOr(overrun, 1u);
+        }
+    }
+    const unsigned long long b = __ballot(miss);
+    if ((threadIdx.x & 63u) == 0 && b) atomicAdd(&wg_miss, (uint32_t)__popcll(b));
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_miss) atomicAdd(missing, (unsigned long long)wg_miss);
+}
+
 // ------------------------------------------------------------------------------------------------ counters -> Fr
 // m(w^t) = cnt[t] as a canonical Montgomery element: what the inverse transform of row_to_coeffs reads
 __global__ void __launch_bounds__(256) k_join_counts(const uint32_t* __restrict__ cnt, uint32_t* __restrict__ out, uint64_t T) {
@@ -190,6 +228,12 @@ void launch_join_probe_rows(hipStream_t s, const uint32_t* tab, const uint32_t* 
     if (rows)
         k_join_probe_rows<<<nblk(rows, 256), 256, 0, s>>>(tab, in, T, rows, w, slots, cap - 1, cnt,
                                                            reinterpret_cast<unsigned long long*>(missing), overrun);
+}
+void launch_join_probe_sel(hipStream_t s, const uint32_t* tab, const uint32_t* in, const uint32_t* sel, uint64_t T, uint64_t rows,
+                           uint32_t w, const uint32_t* slots, uint32_t cap, uint32_t* cnt, uint64_t* missing, uint32_t* overrun) {
+    if (rows)
+        k_join_probe_sel<<<nblk(rows, 256), 256, 0, s>>>(tab, in, sel, T, rows, w, slots, cap - 1, cnt,
+                                                          reinterpret_cast<unsigned long long*>(missing), overrun);
 }
 void launch_join_counts(hipStream_t s, const uint32_t* cnt, uint32_t* out, uint64_t T) {
     if (T) k_join_counts<<<nblk(T, 256), 256, 0, s>>>(cnt, out, T);

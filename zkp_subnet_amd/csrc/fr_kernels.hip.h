@@ -128,6 +128,10 @@ struct QuotPlan {
     // kzg_rows_quotient_part with a link.  link != 0 (then ext != 0 and k > 0): P2 = (z - f_prev(w^rot X)) L_0 with f_prev = row
     // link_row and rot = link_rot in [0, T), and a linked instantiation of the kernel runs
     uint32_t link, link_row, link_rot;
+    // kzg_rows_commit_quotient_sel / kzg_rows_quotient_part_sel.  sel != 0 (then ext != 0 and n_lookups > 0): lookup l's fraction in
+    // LK1 has the numerator row sel_row[l] (0xff: the constant 1), and a SEL kernel runs.  sel == 0: sel_row is not read
+    uint32_t sel;
+    uint8_t sel_row[POLY_MAX_ROWS];
 };
 // the constants record of one (T, E), in 8-word elements: 1 / Z_H on the coset, 1 / T, g and the power tables of g and 1 / g
 uint64_t quot_consts_elems(int log_t, int ext_log);
@@ -154,6 +158,10 @@ void launch_quot_accumulate(hipStream_t s, uint32_t* acc, const uint32_t* v, uin
 // theta, beta as 32 big-endian HOST bytes, *bad raised when >= r
 void launch_lk_step(hipStream_t s, const uint32_t* e, uint32_t* acc, uint32_t* P, uint32_t* Q, uint64_t n, int mode,
                     bool has_acc, const uint8_t theta_be32[32], const uint8_t beta_be32[32], uint32_t* bad);
+// mode 2 with a numerator (kzg_rows_commit_lookup_sum_sel): (P, Q) <- (P d + q Q, Q d), q = sel[t], n canonical Montgomery
+// elements (the lookup's selector row in evaluation form)
+void launch_lk_step_sel(hipStream_t s, const uint32_t* e, uint32_t* acc, uint32_t* P, uint32_t* Q, const uint32_t* sel,
+                        uint64_t n, bool has_acc, const uint8_t theta_be32[32], const uint8_t beta_be32[32], uint32_t* bad);
 // The batched inversion: out[t] <- 1 / Q[t], or P[t] / Q[t] when P is given, for n Montgomery elements with ONE fr9_inv:
 // 1 / Q_t = (prod_{u<t} Q_u) (prod_{u>t} Q_u) / prod_u Q_u.  Q is only read; W: n elements of workspace; out may be W or P.
 // scrN, scrD: (n + 3) / 4 * 3 / 2 + 64 elements of scratch each; scratch32 (device): 32 bytes that are overwritten;
@@ -180,6 +188,10 @@ void launch_join_build_rows(hipStream_t s, const uint32_t* tab, uint64_t T, uint
                             uint32_t cap, uint32_t* overrun);
 void launch_join_probe_rows(hipStream_t s, const uint32_t* tab, const uint32_t* in, uint64_t T, uint64_t rows, uint32_t w,
                             const uint32_t* slots, uint32_t cap, uint32_t* cnt, uint64_t* missing, uint32_t* overrun);
+// one lookup's first `rows` cells (rows = T: all of them) under a selector (kzg_rows_commit_multiplicities_sel): sel holds T
+// canonical Montgomery elements, a cell whose sel[t] is zero is neither probed nor counted as missing
+void launch_join_probe_sel(hipStream_t s, const uint32_t* tab, const uint32_t* in, const uint32_t* sel, uint64_t T, uint64_t rows,
+                           uint32_t w, const uint32_t* slots, uint32_t cap, uint32_t* cnt, uint64_t* missing, uint32_t* overrun);
 // ---- blinding rows (fr_blind.hip; the kzg_rows_commit_*_zk builders): rows [usable, n) of evaluation vectors of n Montgomery
 // elements, n - usable <= BLIND_MAX_ROWS (= KZG_MAX_BLIND_ROWS)
 #define BLIND_MAX_ROWS 32

@@ -19,11 +19,22 @@ static inline uint32_t nblk(uint64_t n, uint32_t b) { return (uint32_t)((n + b -
 //   LK_HORNER : acc <- v                                     (more columns of this tuple follow)
 //   LK_TABLE  : Q <- beta + v,  P <- -P                      (P holds m's evaluations: the fraction starts as -m / d_T)
 //   LK_INPUT  : (P, Q) <- (P d + Q, Q d) with d = beta + v   (one more 1 / d)
+//   LK_INPUT_SEL : (P, Q) <- (P d + q Q, Q d)                (one more q / d: kzg_rows_commit_lookup_sum_sel, q the
+//                  lookup's selector row in evaluation form, any element of Fr)
 // theta and beta are converted to Montgomery form once per workgroup (two lanes, one product each).  Multiplier-bound at
 // LK_INPUT (2 or 3 products per element, 96 - 128 B in, 64 B out), bandwidth-bound otherwise (0 or 1 product).
-enum { LK_HORNER = 0, LK_TABLE = 1, LK_INPUT = 2 };
+// LK_INPUT_SEL does 3 or 4 products per element and reads 32 B more (q).  Operand classes: p, q and the selector are loaded
+// canonical (the forward transform ends in fr9_reduce, P and Q are stored canonical), d is normalised below 4r: p d and q Q
+// are both products' outputs below 2r, so their sum is below 4r with limbs < 2^30, inside what fr9_reduce takes.  The mode
+// is a kernel of its own, k_lk_step_sel, with an argument struct of its own (the selector's pointer rides there), so the three
+// other modes keep their signature, their names and their instructions; a lookup without a selector still launches LK_INPUT.
+enum { LK_HORNER = 0, LK_TABLE = 1, LK_INPUT = 2, LK_INPUT_SEL = 3 };
 struct LkArg {
     FrArg theta, beta;
+};
+struct LkArgSel {
+    LkArg a;
+    const uint32_t* sel;
 };
 KZG_DEV void lk_from_arg(fr9_t& v, const FrArg& a, uint32_t* __restrict__ bad, bool check) {
     uint32_t w[8];
@@ -99,6 +110,61 @@ void launch_lk_step(hipStream_t s, const uint32_t* e, uint32_t* acc, uint32_t* P
     else if (mode == LK_TABLE) { if (has_acc) LK_GO(LK_TABLE, true); else LK_GO(LK_TABLE, false); }
     else { if (has_acc) LK_GO(LK_INPUT, true); else LK_GO(LK_INPUT, false); }
 #undef LK_GO
+}
+
+// LK_INPUT_SEL: the LK_INPUT step with the numerator q = sel[t].  A kernel of its own (k_lk_step keeps its signature, its names
+// and its instructions); the front is k_lk_step's.
+template <bool HAS_ACC>
+__global__ void __launch_bounds__(256) k_lk_step_sel(const uint32_t* __restrict__ e, uint32_t* __restrict__ acc,
+                                                      uint32_t* __restrict__ P, uint32_t* __restrict__ Q, uint64_t n,
+                                                      const LkArgSel larg, uint32_t* __restrict__ bad) {
+    __shared__ uint32_t cst[2][9];   // theta, beta
+    const uint32_t lane = threadIdx.x;
+    if (lane < 2) {
+        fr9_t c;
+        lk_from_arg(c, lane ? larg.a.beta : larg.a.theta, bad, blockIdx.x == 0);
+#pragma unroll
+        for (int i = 0; i < 9; i++) cst[lane][i] = c.l[i];
+    }
+    __syncthreads();
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + lane;
+    if (t >= n) return;
+    fr9_t v, x, y, beta, d, p, q, s;
+    fr9_load(v, e + 8 * t);
+    if constexpr (HAS_ACC) {
+        fr9_t a, theta;
+#pragma unroll
+        for (int i = 0; i < 9; i++) theta.l[i] = cst[0][i];
+        fr9_load(a, acc + 8 * t);
+        fr9_mul(x, a, theta);
+        fr9_add(v, v, x);                     // < 3r, limbs < 2^30
+    }
+#pragma unroll
+    for (int i = 0; i < 9; i++) beta.l[i] = cst[1][i];
+    fr9_add(d, v, beta);                      // < 4r, limbs < 2^31
+    fr9_norm(d, d);                           // a legal second operand: limbs 0..7 < 2^29, value < 4r
+    fr9_load(p, P + 8 * t);
+    fr9_load(q, Q + 8 * t);
+    fr9_load(s, larg.sel + 8 * t);            // q_l(w^t), canonical
+    fr9_mul(x, p, d);
+    fr9_mul(y, s, q);
+    fr9_add(x, x, y);                         // < 4r, limbs < 2^30
+    fr9_reduce(x, x);
+    fr9_mul(q, q, d);
+    fr9_canon(q, q);
+    fr9_store(P + 8 * t, x);
+    fr9_store(Q + 8 * t, q);
+}
+void launch_lk_step_sel(hipStream_t s, const uint32_t* e, uint32_t* acc, uint32_t* P, uint32_t* Q, const uint32_t* sel,
+                        uint64_t n, bool has_acc, const uint8_t theta_be32[32], const uint8_t beta_be32[32], uint32_t* bad) {
+    if (!n) return;
+    LkArgSel arg;
+    memcpy(arg.a.theta.w, theta_be32, 32);
+    memcpy(arg.a.beta.w, beta_be32, 32);
+    arg.sel = sel;
+    const dim3 g(nblk(n, 256));
+    if (has_acc) k_lk_step_sel<true><<<g, 256, 0, s>>>(e, acc, P, Q, n, arg, bad);
+    else k_lk_step_sel<false><<<g, 256, 0, s>>>(e, acc, P, Q, n, arg, bad);
 }
 
 // ------------------------------------------------------------------------------------------------ batched inversion

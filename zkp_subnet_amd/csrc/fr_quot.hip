@@ -180,6 +180,15 @@ struct QuotArgL {
     uint32_t link_row, link_rot;
 };
 static_assert(sizeof(QuotArgL) + sizeof(RowTab) + 64 <= 4096, "k_quot_points' arguments must fit in 4 KB");
+// What the _sel calls add (kzg_rows_commit_quotient_sel, kzg_rows_quotient_part_sel): per lookup the row of its selector q_l,
+// the numerator of its fraction in LK1, or QUOT_NO_SEL (the constant 1).  The widest argument plus 16 bytes, for the SEL
+// kernel alone: the five others keep theirs.
+#define QUOT_NO_SEL 0xffu
+struct QuotArgS {
+    QuotArgL l;
+    uint8_t sel_row[POLY_MAX_ROWS];
+};
+static_assert(sizeof(QuotArgS) + sizeof(RowTab) + 64 <= 4096, "k_quot_points_sel's arguments must fit in 4 KB");
 template <bool EXT, bool ACT, bool LINK = false> struct QuotArgOf { typedef QuotArg type; };
 template <> struct QuotArgOf<true, false, false> { typedef QuotArgX type; };
 template <> struct QuotArgOf<true, true, false> { typedef QuotArgA type; };
@@ -188,10 +197,13 @@ KZG_DEV const QuotArg& quot_base(const QuotArg& a) { return a; }
 KZG_DEV const QuotArg& quot_base(const QuotArgX& a) { return a.q; }
 KZG_DEV const QuotArg& quot_base(const QuotArgA& a) { return a.x.q; }
 KZG_DEV const QuotArg& quot_base(const QuotArgL& a) { return a.a.x.q; }
+KZG_DEV const QuotArg& quot_base(const QuotArgS& a) { return a.l.a.x.q; }
 KZG_DEV const QuotArg& quot_ext(const QuotArg& a) { return a; }
 KZG_DEV const QuotArgX& quot_ext(const QuotArgX& a) { return a; }
 KZG_DEV const QuotArgX& quot_ext(const QuotArgA& a) { return a.x; }
 KZG_DEV const QuotArgX& quot_ext(const QuotArgL& a) { return a.a.x; }
+KZG_DEV const QuotArgX& quot_ext(const QuotArgS& a) { return a.l.a.x; }
+KZG_DEV uint32_t quot_active_row(const QuotArgS& a) { return a.l.a.active_row; }
 KZG_DEV uint32_t quot_active_row(const QuotArgA& a) { return a.active_row; }
 KZG_DEV uint32_t quot_active_row(const QuotArgL& a) { return a.a.active_row; }
 enum { QS_SHIFT = QUOT_MAX_TERMS, QS_BETA = QS_SHIFT + QUOT_MAX_WIRES, QS_GAMMA, QS_ALPHA, QS_ALPHA2, QS_COUNT,
@@ -417,13 +429,203 @@ __global__ void __launch_bounds__(256) k_quot_points(const RowTab rt, const uint
     fr9_canon(acc, acc);
     fr9_store(out + 8 * i, acc);
 }
+// kzg_rows_commit_quotient_sel / kzg_rows_quotient_part_sel: q_l is the numerator of lookup l's fraction.  Inside the LK1 loop
+// P <- P D_l + q_l Q instead of P D_l + Q, one more 32-byte load and one more product per SELECTED lookup and point, behind a
+// wave-uniform branch on sel_row[l].  q_l(x_i) is a canonical row value and Q is normalised (D_0 below 4r, then products'
+// outputs): q_l Q is a product's output below 2r, so P stays below 2r + 2r, inside the 6r the loop already allows.  A KERNEL OF
+// ITS OWN with a body of its own (k_quot_points above is the text it was before the selectors existed, so that every existing
+// call keeps its instructions), always with the extended argument, in the four <ACT, LINK> combinations the two calls reach.
+template <bool ACT, bool LINK>
+__global__ void __launch_bounds__(256) k_quot_points_sel(const RowTab rt, const uint32_t* __restrict__ l0,
+                                                          uint32_t* __restrict__ out, int log_n, const QuotArgS qarg,
+                                                          const uint32_t* __restrict__ tw, const uint32_t* __restrict__ qc,
+                                                          uint32_t* __restrict__ bad) {
+    constexpr bool EXT = true;   // (the text below is k_quot_points' with the selector in the LK1 loop)
+    static_assert(EXT || !ACT, "the active column comes with the extended argument");
+    static_assert(EXT || !LINK, "the link comes with the extended argument");
+    const auto& qx = quot_ext(qarg);   // (the plain argument itself when !EXT: nothing of it is read through qx then)
+    const QuotArg& qa = quot_base(qarg);
+    __shared__ uint32_t cst[EXT ? QX_COUNT : QS_COUNT][9];
+    const uint32_t v = threadIdx.x;
+    const bool chk = blockIdx.x == 0;
+    if (v < QS_COUNT) {
+        fr9_t c;
+        bool live = true;
+        if (v < QS_SHIFT) {
+            live = v < qa.n_terms;
+            if (live) quot_arg(c, qa.c[v], bad, chk);
+        } else if (v < QS_BETA) {   // beta s_j
+            live = v - QS_SHIFT < qa.k;
+            if (live) {
+                fr9_t b;
+                quot_arg(c, qa.shift[v - QS_SHIFT], bad, chk);
+                quot_arg(b, qa.beta, bad, false);
+                fr9_mul(c, c, b);
+                fr9_canon(c, c);
+            }
+        } else if (v == QS_BETA) {
+            quot_arg(c, qa.beta, bad, chk);
+        } else if (v == QS_GAMMA) {
+            quot_arg(c, qa.gamma, bad, chk);
+        } else {
+            quot_arg(c, qa.alpha, bad, chk);
+            if (v == QS_ALPHA2) {
+                fr9_mul(c, c, c);
+                fr9_canon(c, c);
+            }
+        }
+        if (!live) fr9_zero(c);
+#pragma unroll
+        for (int i = 0; i < 9; i++) cst[v][i] = c.l[i];
+    }
+    if constexpr (EXT) {
+        if (v >= QS_COUNT && v < QX_COUNT) {   // theta, the lookup's beta, alpha^3, alpha^4: one lane each
+            fr9_t c;
+            if (v == QX_THETA) {
+                quot_arg(c, qx.theta, bad, chk);
+            } else if (v == QX_LBETA) {
+                quot_arg(c, qx.lbeta, bad, chk);
+            } else {
+                fr9_t a2;
+                quot_arg(c, qa.alpha, bad, false);
+                fr9_mul(a2, c, c);
+                fr9_canon(a2, a2);
+                fr9_mul(c, v == QX_ALPHA3 ? c : a2, a2);
+                fr9_canon(c, c);
+            }
+#pragma unroll
+            for (int i = 0; i < 9; i++) cst[v][i] = c.l[i];
+        }
+    }
+    __syncthreads();
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + v;
+    if (i >> log_n) return;
+    const uint64_t n = (uint64_t)1 << log_n, half = n >> 1;
+    fr9_t acc, p, c;
+    [[maybe_unused]] fr9_t act;
+    if constexpr (ACT) {
+        if (qa.k || qx.n_lookups) fr9_load(act, rt.r[quot_active_row(qarg)] + 8 * i);
+    }
+    fr9_zero(acc);
+    for (uint32_t u = 0; u < qa.n_terms; u++) {
+        lds_get(p, cst, u);
+        const uint32_t len = qa.len[u];
+        for (uint32_t f = 0; f < len; f++) {
+            if constexpr (EXT) fr9_load(c, rt.r[qa.row[u][f]] + 8 * ((i + qx.rot[u][f]) & (n - 1)));
+            else fr9_load(c, rt.r[qa.row[u][f]] + 8 * i);
+            fr9_mul(p, p, c);
+        }
+        fr9_add(acc, acc, p);
+        fr9_norm(acc, acc);
+    }
+    if (qa.k) {
+        fr9_t x, g, gamma, beta, A, B, z, a, sg, t, fa;
+        // x_i = g w_N^i, kept lazy (a first operand only)
+        fr9_load(g, qc + 8 * QC_G);
+        tw_get(c, tw, i & (half - 1));
+        fr9_mul(x, g, c);
+        if (i >= half) {
+            fr9_zero(t);
+            fr9_sub4(x, t, x);
+        }
+        lds_get(gamma, cst, QS_GAMMA);
+        lds_get(beta, cst, QS_BETA);
+        const uint32_t* zr = rt.r[qa.z_row];
+        fr9_load(z, zr + 8 * i);
+        fr9_load(B, zr + 8 * ((i + ((uint64_t)1 << qa.ext_log)) & (n - 1)));
+        A = z;
+        for (uint32_t j = 0; j < qa.k; j++) {
+            fr9_load(a, rt.r[qa.wire[j]] + 8 * i);
+            fr9_load(sg, rt.r[qa.sigma[j]] + 8 * i);
+            lds_get(c, cst, QS_SHIFT + j);
+            fr9_mul(t, x, c);                 // beta s_j x_i
+            fr9_add(fa, a, gamma);
+            fr9_add(t, t, fa);                // < 4r
+            fr9_norm(t, t);
+            fr9_mul(A, t, A);
+            fr9_mul(t, sg, beta);
+            fr9_add(t, t, fa);
+            fr9_norm(t, t);
+            fr9_mul(B, t, B);
+        }
+        fr9_sub4(A, A, B);                    // P1, < 6r
+        if constexpr (ACT) fr9_mul(A, A, act);   // A P1, < 2r
+        lds_get(c, cst, QS_ALPHA);
+        fr9_mul(t, A, c);
+        fr9_add(acc, acc, t);
+        fr9_norm(acc, acc);
+        // P2 / Z_H = (z - 1) L_0 / Z_H: l0 holds L_0 on the coset, the division is the closing product below
+        // (LINK: z - f_prev(w^rot x_i), the chain relation of a chunked permutation)
+        if constexpr (LINK) fr9_load(c, rt.r[qarg.l.link_row] + 8 * ((i + qarg.l.link_rot) & (n - 1)));
+        else fr9_one(c);
+        fr9_sub4(z, z, c);
+        fr9_load(c, l0 + 8 * i);
+        fr9_mul(t, z, c);
+        lds_get(c, cst, QS_ALPHA2);
+        fr9_mul(t, t, c);
+        fr9_add(acc, acc, t);
+        fr9_norm(acc, acc);
+    }
+    if constexpr (EXT) {
+        if (qx.n_lookups) {
+            // the running fraction of k_lk_step, point by point and without the inversion: P / Q = sum_l 1 / D_l - m / D_0
+            //   P = -m, Q = D_0;  (P, Q) <- (P D_l + Q, Q D_l) for every l;  LK1 = (S(w x) - S(x)) Q - P
+            // P is 4r - m (< 5r) at first and (a product) + Q < 2r + 4r afterwards: a first operand below 6r against D_l
+            // below 4r.  Q is D_0 and then a product's output: normalised either way.
+            fr9_t theta, beta, P, Q, d, s, t;
+            lds_get(theta, cst, QX_THETA);
+            lds_get(beta, cst, QX_LBETA);
+            quot_lk_den(Q, rt, qx.tab_row, qx.width, i, theta, beta);
+            fr9_load(c, rt.r[qx.mult_row] + 8 * i);
+            fr9_zero(P);
+            fr9_sub4(P, P, c);
+            for (uint32_t l = 0; l < qx.n_lookups; l++) {
+                quot_lk_den(d, rt, qx.in_row + l * qx.width, qx.width, i, theta, beta);
+                fr9_mul(P, P, d);
+                const uint32_t sr = qarg.sel_row[l];   // wave-uniform: a kernel argument
+                if (sr != QUOT_NO_SEL) {
+                    fr9_load(c, rt.r[sr] + 8 * i);
+                    fr9_mul(t, c, Q);                 // q_l Q, < 2r
+                    fr9_add(P, P, t);
+                } else {
+                    fr9_add(P, P, Q);
+                }
+                fr9_mul(Q, Q, d);
+            }
+            const uint32_t* sr = rt.r[qx.sum_row];
+            fr9_load(s, sr + 8 * i);
+            fr9_load(t, sr + 8 * ((i + ((uint64_t)1 << qa.ext_log)) & (n - 1)));
+            fr9_sub4(t, t, s);                // S(w x) - S(x), < 5r
+            fr9_mul(t, t, Q);
+            fr9_norm(P, P);                   // < 6r, normalised: what fr9_sub8 takes
+            fr9_sub8(t, t, P);                // LK1, < 10r
+            if constexpr (ACT) fr9_mul(t, t, act);   // A LK1, < 2r
+            lds_get(c, cst, QX_ALPHA3);
+            fr9_mul(t, t, c);
+            fr9_add(acc, acc, t);
+            fr9_norm(acc, acc);
+            // LK2 = S L_0
+            fr9_load(c, l0 + 8 * i);
+            fr9_mul(t, s, c);
+            lds_get(c, cst, QX_ALPHA4);
+            fr9_mul(t, t, c);
+            fr9_add(acc, acc, t);
+            fr9_norm(acc, acc);
+        }
+    }
+    fr9_load(c, qc + 8 * (i & ((1u << qa.ext_log) - 1)));
+    fr9_mul(acc, acc, c);
+    fr9_canon(acc, acc);
+    fr9_store(out + 8 * i, acc);
+}
 void launch_quot_points(hipStream_t s, const RowTab& ext_rows, const uint32_t* l0, uint32_t* out, int log_t, const QuotPlan& qp,
                         const uint32_t* tw_n, const uint32_t* qc, uint32_t* bad) {
-    QuotArgL larg;
+    QuotArgS sarg;
+    QuotArgL& larg = sarg.l;
     QuotArgA& qarg = larg.a;
     QuotArgX& qx = qarg.x;
     QuotArg& qa = qx.q;
-    memset(&larg, 0, sizeof(larg));
+    memset(&sarg, 0, sizeof(sarg));
     qa.n_terms = qp.n_terms;
     qa.k = qp.k;
     qa.z_row = qp.z_row;
@@ -465,6 +667,16 @@ void launch_quot_points(hipStream_t s, const RowTab& ext_rows, const uint32_t* l
     if (qp.link) {
         larg.link_row = qp.link_row;
         larg.link_rot = qp.link_rot << qp.ext_log;
+    }
+    if (qp.sel) {   // (then n_lookups > 0: the host's check)
+        memcpy(sarg.sel_row, qp.sel_row, sizeof(sarg.sel_row));
+#define QS_GO(A, L) k_quot_points_sel<A, L><<<g, 256, 0, s>>>(ext_rows, l0, out, log_n, sarg, tw_n, qc, bad)
+        if (qp.active) { if (qp.link) QS_GO(true, true); else QS_GO(true, false); }
+        else { if (qp.link) QS_GO(false, true); else QS_GO(false, false); }
+#undef QS_GO
+        return;
+    }
+    if (qp.link) {
         if (qp.active) k_quot_points<true, true, true><<<g, 256, 0, s>>>(ext_rows, l0, out, log_n, larg, tw_n, qc, bad);
         else k_quot_points<true, false, true><<<g, 256, 0, s>>>(ext_rows, l0, out, log_n, larg, tw_n, qc, bad);
         return;

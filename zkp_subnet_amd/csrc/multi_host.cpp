@@ -60,6 +60,25 @@ int rows_multiplicities_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_inpu
                                 uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
                                 uint64_t usable, const uint8_t* tail_be32, uint8_t* out_commitment48, uint64_t* out_missing,
                                 uint64_t* out_handle);
+int rows_lookup_sum_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                             uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
+                             uint32_t n_sel_handles, const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups,
+                             uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint64_t usable,
+                             const uint8_t* tail_be32, uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle);
+int rows_multiplicities_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                 uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_sel_handles,
+                                 const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups, uint32_t width,
+                                 uint64_t usable, const uint8_t* tail_be32, uint8_t* out_commitment48, uint64_t* out_missing,
+                                 uint64_t* out_handle);
+int rows_quotient_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
+                           const kzg_quotient_selectors* selectors, const kzg_quotient_active* active, uint32_t ext_log,
+                           uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle);
+int rows_quotient_part_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                                const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                                const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
+                                const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32,
+                                uint64_t* inout_acc);
 int rows_quotient_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
                           const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,
@@ -556,6 +575,54 @@ int kzg_multi_rows_commit_multiplicities_zk(kzg_multi* mh, uint32_t i, uint32_t 
     return relay(c, kzg_impl::rows_multiplicities_zk_impl(c, s, n_input_handles, input_handles, n_table_handles, table_handles,
                                                           n_lookups, width, usable, tail_be32, out_commitment48, out_missing,
                                                           out_handle));
+}
+int kzg_multi_rows_commit_lookup_sum_sel(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                         uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
+                                         uint32_t n_sel_handles, const uint64_t* sel_handles, const uint32_t* sel_index,
+                                         uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32],
+                                         const uint8_t beta_be32[32], uint64_t usable, const uint8_t* tail_be32,
+                                         uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_lookup_sum_sel_impl(c, s, n_input_handles, input_handles, n_table_handles, table_handles,
+                                                       mult_handle, n_sel_handles, sel_handles, sel_index, n_lookups, width,
+                                                       theta_be32, beta_be32, usable, tail_be32, out_commitment48, out_closing32,
+                                                       out_handle));
+}
+int kzg_multi_rows_commit_multiplicities_sel(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                             uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_sel_handles,
+                                             const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups,
+                                             uint32_t width, uint64_t usable, const uint8_t* tail_be32,
+                                             uint8_t out_commitment48[48], uint64_t* out_missing, uint64_t* out_handle) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_multiplicities_sel_impl(c, s, n_input_handles, input_handles, n_table_handles, table_handles,
+                                                           n_sel_handles, sel_handles, sel_index, n_lookups, width, usable,
+                                                           tail_be32, out_commitment48, out_missing, out_handle));
+}
+int kzg_multi_rows_commit_quotient_sel(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                       const kzg_quotient_terms* gate, const kzg_quotient_perm* perm,
+                                       const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
+                                       const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces,
+                                       uint8_t* out_commitments48, uint64_t* out_handle) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_quotient_sel_impl(c, s, n_handles, handles, gate, perm, lookup, selectors, active, ext_log,
+                                                     n_pieces, out_commitments48, out_handle));
+}
+int kzg_multi_rows_quotient_part_sel(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                     const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                                     const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
+                                     const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32,
+                                     uint64_t* inout_acc) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_quotient_part_sel_impl(c, s, n_handles, handles, gate, perm, link, lookup, selectors, active,
+                                                          ext_log, scale_be32, inout_acc));
 }
 int kzg_multi_rows_commit_quotient_zk(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
                                       const kzg_quotient_terms* gate, const kzg_quotient_perm* perm,

@@ -783,9 +783,14 @@ int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& 
 // term = P / Q (one inversion), the additive scan turns it into S's evaluations in place, the inverse transform writes S's
 // coefficients straight into the new set's buffer `dst`; one MSM commits.  The record's first two evaluation slots carry the
 // closing value and the zero-denominator flag word.
+// sel (kzg_rows_commit_lookup_sum_sel): each distinct selector row is transformed ONCE, in front of everything else, into a
+// vector of its own in the lane's quotient workspace (sel->n vectors of T more); the lookups that name one close their Horner
+// chain with LK_INPUT_SEL (numerator q_l), the others with LK_INPUT as without selectors.  Nothing else changes: the _zk mask,
+// the one inversion (a zero denominator is found on every row it reads, enabled or not), the scan, the tail.
 int rows_lookup_sum_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& table, const uint32_t* mult,
                         uint32_t n_lookups, uint32_t width, uint64_t T, const uint8_t* theta_be32, const uint8_t* beta_be32,
-                        uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den, const Blind* zk) {
+                        uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den, const Blind* zk,
+                        const SelPlan* sel) {
     Lane& A = H.L();
     if (int rc = ensure_multi_record(ctx, A)) return rc;
     const int lg = ilog2_exact(T);
@@ -802,6 +807,12 @@ int rows_lookup_sum_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inp
     uint32_t *e = A.coeffA.as<uint32_t>(), *acc = A.coeffB.as<uint32_t>();
     uint32_t *P = A.bcomb.as<uint32_t>(), *Q = A.qbuf.as<uint32_t>(), *mid = A.ntt_mid.as<uint32_t>();
     uint8_t* rec = A.brec.as<uint8_t>();
+    if (sel && sel->n) {
+        HIPCHK(ctx, A.qext.ensure((size_t)sel->n * T * 32));
+        Span sp(ctx, A, KZG_T_NTT);
+        for (uint32_t j = 0; j < sel->n; j++)
+            launch_fr_ntt(A.stream, sel->row[j], A.qext.as<uint32_t>() + (uint64_t)j * T * 8, lg, tw, nullptr, mid);
+    }
     {
         Span sp(ctx, A, KZG_T_NTT);
         launch_fr_ntt(A.stream, mult, P, lg, tw, nullptr, mid);
@@ -813,7 +824,11 @@ int rows_lookup_sum_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inp
                 launch_fr_ntt(A.stream, l ? inputs.r[(l - 1) * width + c] : table.r[c], e, lg, tw, nullptr, mid);
             }
             Span sp(ctx, A, KZG_T_POLY);
-            launch_lk_step(A.stream, e, acc, P, Q, T, c ? 0 : (l ? 2 : 1), c + 1 < width, theta_be32, beta_be32, A.flags());
+            if (sel && l && !c && sel->of[l - 1] != SEL_NONE)
+                launch_lk_step_sel(A.stream, e, acc, P, Q, A.qext.as<uint32_t>() + (uint64_t)sel->of[l - 1] * T * 8, T, c + 1 < width,
+                                   theta_be32, beta_be32, A.flags());
+            else
+                launch_lk_step(A.stream, e, acc, P, Q, T, c ? 0 : (l ? 2 : 1), c + 1 < width, theta_be32, beta_be32, A.flags());
         }
     }
     {
@@ -845,9 +860,12 @@ int rows_lookup_sum_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inp
 // the counters into m's evaluations (in the first input vector, dead by then); the inverse transform writes m's
 // coefficients straight into the new set's buffer `dst`; one MSM commits.  The record's first evaluation slot carries
 // `missing` (8 bytes) and the overrun flag word behind it.
+// sel (kzg_rows_commit_multiplicities_sel): sel->n more vectors behind the 2 w, one per distinct selector row, transformed
+// once; a lookup that names one is probed by k_join_probe_sel (only the cells whose selector is not zero), the others by the
+// probe of the call without selectors.  The build, the counters, the tail and the commit are unchanged.
 int rows_multiplicities_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& table, uint32_t n_lookups,
                             uint32_t width, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_missing,
-                            bool* out_overrun, const Blind* zk) {
+                            bool* out_overrun, const Blind* zk, const SelPlan* sel) {
     Lane& A = H.L();
     if (int rc = ensure_multi_record(ctx, A)) return rc;
     const int lg = ilog2_exact(T);
@@ -855,17 +873,23 @@ int rows_multiplicities_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab&
     if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
     const uint64_t vw = T * 8;                 // one vector, in words
     const uint32_t cap = (uint32_t)(2 * T);    // slots: a power of two, load <= 1 / 2 (T <= 2^27: the caller)
-    HIPCHK(ctx, A.qext.ensure((size_t)2 * width * T * 32));
+    const uint32_t n_sel = sel ? sel->n : 0;
+    HIPCHK(ctx, A.qext.ensure(((size_t)2 * width + n_sel) * T * 32));
     HIPCHK(ctx, A.qstage.ensure(((size_t)cap + T) * 4));
     HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
     uint32_t *tab = A.qext.as<uint32_t>(), *in = tab + (uint64_t)width * vw, *mid = A.ntt_mid.as<uint32_t>();
     uint32_t *slots = A.qstage.as<uint32_t>(), *cnt = slots + cap;
+    uint32_t* selv = in + (uint64_t)width * vw;
     uint8_t* rec = A.brec.as<uint8_t>();
     uint64_t* missing = reinterpret_cast<uint64_t*>(rec + MR_EVAL);
     uint32_t* overrun = reinterpret_cast<uint32_t*>(rec + MR_EVAL + 8);
     for (uint32_t c = 0; c < width; c++) {
         Span sp(ctx, A, KZG_T_NTT);
         launch_fr_ntt(A.stream, table.r[c], tab + c * vw, lg, tw, nullptr, mid);
+    }
+    for (uint32_t j = 0; j < n_sel; j++) {
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, sel->row[j], selv + j * vw, lg, tw, nullptr, mid);
     }
     {
         Span sp(ctx, A, KZG_T_POLY);
@@ -882,7 +906,10 @@ int rows_multiplicities_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab&
             launch_fr_ntt(A.stream, inputs.r[l * width + c], in + c * vw, lg, tw, nullptr, mid);
         }
         Span sp(ctx, A, KZG_T_POLY);
-        if (zk) launch_join_probe_rows(A.stream, tab, in, T, zk->usable, width, slots, cap, cnt, missing, overrun);
+        if (sel && sel->of[l] != SEL_NONE)
+            launch_join_probe_sel(A.stream, tab, in, selv + sel->of[l] * vw, T, zk ? zk->usable : T, width, slots, cap, cnt, missing,
+                                  overrun);
+        else if (zk) launch_join_probe_rows(A.stream, tab, in, T, zk->usable, width, slots, cap, cnt, missing, overrun);
         else launch_join_probe(A.stream, tab, in, T, width, slots, cap, cnt, missing, overrun);
     }
     {
@@ -946,6 +973,8 @@ static int quot_front(kzg_ctx* ctx, Lane& A, const RowTab& rt, uint32_t n_rows, 
     if (qp.n_lookups) used[qp.mult_row] = used[qp.sum_row] = true;
     if (qp.active && (qp.k || qp.n_lookups)) used[qp.active_row] = true;   // A: one more distinct row (a factor of P1 and LK1)
     if (qp.link) used[qp.link_row] = true;                                 // f_prev of a linked P2
+    for (uint32_t l = 0; qp.sel && l < qp.n_lookups; l++)                 // q_l: extended once like any row the part names
+        if (qp.sel_row[l] != 0xffu) used[qp.sel_row[l]] = true;
     const bool need_l0 = qp.k || qp.n_lookups;   // P2 and LK2
     int slot[POLY_MAX_ROWS];
     uint32_t nd = 0;

@@ -939,15 +939,59 @@ int rows_grand_product_chain_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wi
                                   beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle, &zk, start_be32);
 }
 
+// The selector arguments of a _sel builder as the caller gave them (null: the call has none), and their check: sel_index[l] is
+// KZG_NO_SELECTOR or indexes the concatenated rows of the sel_handles sets, which must be of the call's worker and row length.
+// The distinct rows named go into sp (a row that serves several lookups is transformed once).
+struct SelCall {
+    uint32_t n_sel_handles;
+    const uint64_t* sel_handles;
+    const uint32_t* sel_index;
+};
+static int sel_plan(kzg_ctx* ctx, const char* what, uint32_t expect_i, const SelCall& sc, uint32_t n_lookups, uint32_t i, uint64_t T,
+                    RowsRefs& refs, SelPlan& sp) {
+    auto bad = [&](const char* why) { return fail(ctx, KZG_E_ARG, std::string(what) + why); };
+    memset(&sp, 0, sizeof(sp));
+    RowTab st;
+    uint32_t ks = 0;
+    if (sc.n_sel_handles) {
+        uint32_t is = 0;
+        uint64_t Ts = 0;
+        if (int rc = rows_lookup(ctx, (std::string(what) + " (selectors)").c_str(), expect_i, sc.n_sel_handles, sc.sel_handles, refs,
+                                 st, &ks, &is, &Ts))
+            return rc;
+        if (is != i || Ts != T) return bad(": all sets must belong to one worker and have one row length");
+    }
+    uint8_t slot_of[KZG_MAX_BATCH_OPEN];
+    memset(slot_of, SEL_NONE, sizeof(slot_of));
+    for (uint32_t l = 0; l < n_lookups; l++) {
+        const uint32_t j = sc.sel_index[l];
+        sp.of[l] = SEL_NONE;
+        if (j == KZG_NO_SELECTOR) continue;
+        if (j >= ks) return bad(": a sel_index entry must be KZG_NO_SELECTOR or index the concatenated rows of the selector sets");
+        if (slot_of[j] == SEL_NONE) {
+            slot_of[j] = (uint8_t)sp.n;
+            sp.row[sp.n++] = st.r[j];
+        }
+        sp.of[l] = slot_of[j];
+    }
+    return KZG_OK;
+}
+// the layout of a _sel builder once T is known: usable == T with no tail is the plain layout (null), anything else the _zk
+// call's, which blind_check then judges (so usable == T WITH a tail is its "usable must be in [1, T - 1]")
+static const Blind* sel_layout(const Blind* zk, uint64_t T) { return zk->usable == T && !zk->tail_be32 ? nullptr : zk; }
+
 // kzg_rows_commit_lookup_sum: the lookups of an open (three handle lists), the reservation of a commit.  zk: the blinding
 // rows of kzg_rows_commit_lookup_sum_zk (null: the plain call)
 static int rows_lookup_sum_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
                                uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
                                uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint8_t* out_commitment48,
-                               uint8_t* out_closing32, uint64_t* out_handle, const Blind* zk) {
+                               uint8_t* out_closing32, uint64_t* out_handle, const Blind* zk, const SelCall* sc = nullptr) {
     if (!ctx || !input_handles || !table_handles || !theta_be32 || !beta_be32 || !out_commitment48 || !out_closing32 ||
         !out_handle)
         return KZG_E_ARG;
+    if (sc && (!sc->sel_index || (sc->n_sel_handles && !sc->sel_handles))) return KZG_E_ARG;
+    if (sc && sc->n_sel_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "lookup sum: at most KZG_MAX_BATCH_OPEN selector handles");
     if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN || n_table_handles == 0 || n_table_handles > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "lookup sum: the number of handles in each list must be in [1, KZG_MAX_BATCH_OPEN]");
     if (n_lookups == 0 || width == 0 || (uint64_t)n_lookups * width > KZG_MAX_BATCH_OPEN)
@@ -957,7 +1001,7 @@ static int rows_lookup_sum_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input
         return fail(ctx, KZG_E_ARG, "lookup sum: theta and beta must be canonical scalars (< r)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     RowsPending pend{ctx};
-    RowsRefs irefs{ctx}, trefs{ctx}, mrefs{ctx};
+    RowsRefs irefs{ctx}, trefs{ctx}, mrefs{ctx}, srefs{ctx};
     LaneHold H(ctx);
     if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
     Lane& L = H.L();
@@ -976,6 +1020,11 @@ static int rows_lookup_sum_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input
     int rc = check_worker(ctx, i, T);
     if (rc) return rc;
     if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "lookup sum: the row length must be a power of two");
+    SelPlan sp;
+    if (sc) {
+        if (int rcs = sel_plan(ctx, "lookup sum", expect_i, *sc, n_lookups, i, T, srefs, sp)) return rcs;
+        zk = sel_layout(zk, T);
+    }
     if (zk)
         if (int rcz = blind_check(ctx, "lookup sum", T, *zk)) return rcz;
     if (int rc2 = rows_reserve(ctx, "lookup sum", pend, (size_t)T * 32)) return rc2;
@@ -985,7 +1034,7 @@ static int rows_lookup_sum_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input
     bool zero_den = false;
     uint8_t c48[48], closing[32];
     rc = rows_lookup_sum_dev(ctx, H, i, it, tt, mt.r[0], n_lookups, width, T, theta_be32, beta_be32, pend.buf.as<uint32_t>(), c48,
-                             closing, &zero_den, zk);
+                             closing, &zero_den, zk, sc ? &sp : nullptr);
     if (rc) return rc;
     if (zero_den)
         return fail(ctx, KZG_E_ARG, zk ? "lookup sum: zero denominator (some beta + F_l or beta + Tb vanishes on a usable row): "
@@ -1013,12 +1062,28 @@ int rows_lookup_sum_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_ha
                                n_lookups, width, theta_be32, beta_be32, out_commitment48, out_closing32, out_handle, &zk);
 }
 
+// kzg_rows_commit_lookup_sum_sel: one call for both layouts (sel_plan decides once T is known)
+int rows_lookup_sum_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                             uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
+                             uint32_t n_sel_handles, const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups,
+                             uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint64_t usable,
+                             const uint8_t* tail_be32, uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle) {
+    const Blind zk = {usable, tail_be32};
+    const SelCall sc = {n_sel_handles, sel_handles, sel_index};
+    return rows_lookup_sum_any(ctx, expect_i, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
+                               n_lookups, width, theta_be32, beta_be32, out_commitment48, out_closing32, out_handle, &zk, &sc);
+}
+
 // kzg_rows_commit_multiplicities: the lookups of an open (two handle lists), the reservation of a commit.  zk: the blinding
 // rows of kzg_rows_commit_multiplicities_zk (null: the plain call)
 static int rows_multiplicities_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
                                    uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
-                                   uint8_t* out_commitment48, uint64_t* out_missing, uint64_t* out_handle, const Blind* zk) {
+                                   uint8_t* out_commitment48, uint64_t* out_missing, uint64_t* out_handle, const Blind* zk,
+                                   const SelCall* sc = nullptr) {
     if (!ctx || !input_handles || !table_handles || !out_commitment48 || !out_missing || !out_handle) return KZG_E_ARG;
+    if (sc && (!sc->sel_index || (sc->n_sel_handles && !sc->sel_handles))) return KZG_E_ARG;
+    if (sc && sc->n_sel_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "multiplicities: at most KZG_MAX_BATCH_OPEN selector handles");
     if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN || n_table_handles == 0 || n_table_handles > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "multiplicities: the number of handles in each list must be in [1, KZG_MAX_BATCH_OPEN]");
     if (n_lookups == 0 || width == 0 || (uint64_t)n_lookups * width > KZG_MAX_BATCH_OPEN)
@@ -1026,7 +1091,7 @@ static int rows_multiplicities_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_i
                                     "KZG_MAX_BATCH_OPEN");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     RowsPending pend{ctx};
-    RowsRefs irefs{ctx}, trefs{ctx};
+    RowsRefs irefs{ctx}, trefs{ctx}, srefs{ctx};
     LaneHold H(ctx);
     if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
     Lane& L = H.L();
@@ -1045,6 +1110,11 @@ static int rows_multiplicities_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_i
     if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "multiplicities: the row length must be a power of two");
     if (T > ((uint64_t)1 << 27))   // L T additions fit a u32 counter, 2 T slots a u32 index
         return fail(ctx, KZG_E_ARG, "multiplicities: the row length must be at most 2^27");
+    SelPlan sp;
+    if (sc) {
+        if (int rcs = sel_plan(ctx, "multiplicities", expect_i, *sc, n_lookups, i, T, srefs, sp)) return rcs;
+        zk = sel_layout(zk, T);
+    }
     if (zk)
         if (int rcz = blind_check(ctx, "multiplicities", T, *zk)) return rcz;
     if (int rc2 = rows_reserve(ctx, "multiplicities", pend, (size_t)T * 32)) return rc2;
@@ -1054,7 +1124,8 @@ static int rows_multiplicities_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_i
     bool overrun = false;
     uint8_t c48[48];
     uint64_t missing = 0;
-    rc = rows_multiplicities_dev(ctx, H, i, it, tt, n_lookups, width, T, pend.buf.as<uint32_t>(), c48, &missing, &overrun, zk);
+    rc = rows_multiplicities_dev(ctx, H, i, it, tt, n_lookups, width, T, pend.buf.as<uint32_t>(), c48, &missing, &overrun, zk,
+                                 sc ? &sp : nullptr);
     if (rc) return rc;
     if (overrun)
         return fail(ctx, KZG_E_HIP, "multiplicities: a probe walk of the hash join reached its bound (the slot table held no "
@@ -1078,6 +1149,17 @@ int rows_multiplicities_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_inpu
     return rows_multiplicities_any(ctx, expect_i, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups,
                                    width, out_commitment48, out_missing, out_handle, &zk);
 }
+// kzg_rows_commit_multiplicities_sel: one call for both layouts (sel_plan decides once T is known)
+int rows_multiplicities_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                 uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_sel_handles,
+                                 const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups, uint32_t width,
+                                 uint64_t usable, const uint8_t* tail_be32, uint8_t* out_commitment48, uint64_t* out_missing,
+                                 uint64_t* out_handle) {
+    const Blind zk = {usable, tail_be32};
+    const SelCall sc = {n_sel_handles, sel_handles, sel_index};
+    return rows_multiplicities_any(ctx, expect_i, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups,
+                                   width, out_commitment48, out_missing, out_handle, &zk, &sc);
+}
 
 // The constraints of a quotient call as the caller gave them, checked and turned into the kernels' plan before any lane is
 // taken (kzg_rows_commit_quotient*, and kzg_rows_quotient_part, which has no n_pieces: null).  `plain` only words one message.
@@ -1090,8 +1172,11 @@ struct QuotCall {
 };
 static int quot_plan(kzg_ctx* ctx, const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
                      const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
-                     const uint32_t* n_pieces, uint32_t n_handles, bool plain, QuotCall& C) {
+                     const uint32_t* n_pieces, uint32_t n_handles, bool plain, QuotCall& C,
+                     const kzg_quotient_selectors* selectors = nullptr) {
     const uint32_t k = perm ? perm->k : 0;
+    if (selectors && !selectors->selector_rows) return fail(ctx, KZG_E_ARG, "quotient: selectors->selector_rows must not be null");
+    if (selectors && !lookup) return fail(ctx, KZG_E_ARG, "quotient: selectors need a lookup part (lookup != NULL)");
     if (gate->n_terms && (!gate->coeffs_be32 || !gate->term_lens || !gate->term_rows)) return KZG_E_ARG;
     if (lookup && (!lookup->input_rows || !lookup->table_rows || !lookup->theta_be32 || !lookup->beta_be32 || !lookup->alpha_be32))
         return KZG_E_ARG;
@@ -1182,6 +1267,15 @@ static int quot_plan(kzg_ctx* ctx, const kzg_quotient_terms* gate, const kzg_quo
         qp.ext = qp.active = 1;
         qp.active_row = name_row(active->active_row);
     }
+    if (selectors) {   // every entry KZG_NO_SELECTOR: sel stays 0 and the call is the one without selectors
+        for (uint32_t l = 0; l < qp.n_lookups; l++) {
+            const uint32_t r = selectors->selector_rows[l];
+            qp.sel_row[l] = 0xffu;
+            if (r == KZG_NO_SELECTOR) continue;
+            qp.sel_row[l] = name_row(r);
+            qp.sel = 1;
+        }
+    }
     if (link) {
         qp.ext = qp.link = 1;
         qp.link_row = name_row(link->prev_row);
@@ -1208,10 +1302,11 @@ static int quot_plan_rows(kzg_ctx* ctx, QuotCall& C, uint32_t n, uint32_t i, uin
 static int rows_quotient_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
                              const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
                              const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces,
-                             uint8_t* out_commitments48, uint64_t* out_handle, bool plain) {
+                             uint8_t* out_commitments48, uint64_t* out_handle, bool plain,
+                             const kzg_quotient_selectors* selectors = nullptr) {
     if (!ctx || !handles || !gate || !out_commitments48 || !out_handle) return KZG_E_ARG;
     QuotCall C;
-    if (int rc = quot_plan(ctx, gate, perm, nullptr, lookup, active, ext_log, &n_pieces, n_handles, plain, C)) return rc;
+    if (int rc = quot_plan(ctx, gate, perm, nullptr, lookup, active, ext_log, &n_pieces, n_handles, plain, C, selectors)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     RowsPending pend{ctx};
     RowsRefs refs{ctx};
@@ -1258,15 +1353,17 @@ static int acc_lookup(kzg_ctx* ctx, const char* what, uint32_t expect_i, uint64_
     *out = &st;   // (map nodes do not move; the reference keeps this one from being erased)
     return KZG_OK;
 }
-int rows_quotient_part_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                            const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
-                            const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
-                            const uint8_t* scale_be32, uint64_t* inout_acc) {
+// selectors: those of kzg_rows_quotient_part_sel (null: kzg_rows_quotient_part)
+static int rows_quotient_part_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                                  const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                                  const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
+                                  const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32,
+                                  uint64_t* inout_acc) {
     if (!ctx || !handles || !gate || !inout_acc) return KZG_E_ARG;
     if (scale_be32 && !fr_be32_canonical(scale_be32))
         return fail(ctx, KZG_E_ARG, "quotient part: scale must be a canonical scalar (< r)");
     QuotCall C;
-    if (int rc = quot_plan(ctx, gate, perm, link, lookup, active, ext_log, nullptr, n_handles, false, C)) return rc;
+    if (int rc = quot_plan(ctx, gate, perm, link, lookup, active, ext_log, nullptr, n_handles, false, C, selectors)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     RowsPending pend{ctx};
     RowsRefs refs{ctx}, arefs{ctx};
@@ -1329,6 +1426,21 @@ int rows_quotient_part_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles,
     }
     return KZG_OK;
 }
+int rows_quotient_part_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                            const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                            const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
+                            const uint8_t* scale_be32, uint64_t* inout_acc) {
+    return rows_quotient_part_any(ctx, expect_i, n_handles, handles, gate, perm, link, lookup, nullptr, active, ext_log, scale_be32,
+                                  inout_acc);
+}
+int rows_quotient_part_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                                const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                                const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
+                                const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32,
+                                uint64_t* inout_acc) {
+    return rows_quotient_part_any(ctx, expect_i, n_handles, handles, gate, perm, link, lookup, selectors, active, ext_log,
+                                  scale_be32, inout_acc);
+}
 int rows_quotient_finish_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t acc_handle, uint32_t n_pieces, uint8_t* out_commitments48,
                               uint64_t* out_handle) {
     if (!ctx || !out_commitments48 || !out_handle) return KZG_E_ARG;
@@ -1385,6 +1497,14 @@ int rows_quotient_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, c
                           uint64_t* out_handle) {
     return rows_quotient_any(ctx, expect_i, n_handles, handles, gate, perm, lookup, active, ext_log, n_pieces, out_commitments48,
                              out_handle, false);
+}
+// kzg_rows_commit_quotient_sel: selectors == NULL is kzg_rows_commit_quotient_zk
+int rows_quotient_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
+                           const kzg_quotient_selectors* selectors, const kzg_quotient_active* active, uint32_t ext_log,
+                           uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle) {
+    return rows_quotient_any(ctx, expect_i, n_handles, handles, gate, perm, lookup, active, ext_log, n_pieces, out_commitments48,
+                             out_handle, false, selectors);
 }
 
 // kzg_rows_commit_quotient: the same with every rotation 0 and no lookup part
@@ -1508,6 +1628,39 @@ int kzg_rows_commit_lookup_sum_zk(kzg_ctx* ctx, uint32_t n_input_handles, const 
     return rows_lookup_sum_zk_impl(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
                                    n_lookups, width, theta_be32, beta_be32, usable, tail_be32, out_commitment48, out_closing32,
                                    out_handle);
+}
+int kzg_rows_commit_lookup_sum_sel(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_table_handles,
+                                   const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_sel_handles,
+                                   const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups, uint32_t width,
+                                   const uint8_t theta_be32[32], const uint8_t beta_be32[32], uint64_t usable,
+                                   const uint8_t* tail_be32, uint8_t out_commitment48[48], uint8_t out_closing32[32],
+                                   uint64_t* out_handle) {
+    return rows_lookup_sum_sel_impl(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
+                                    n_sel_handles, sel_handles, sel_index, n_lookups, width, theta_be32, beta_be32, usable,
+                                    tail_be32, out_commitment48, out_closing32, out_handle);
+}
+int kzg_rows_commit_multiplicities_sel(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                                       uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_sel_handles,
+                                       const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups, uint32_t width,
+                                       uint64_t usable, const uint8_t* tail_be32, uint8_t out_commitment48[48],
+                                       uint64_t* out_missing, uint64_t* out_handle) {
+    return rows_multiplicities_sel_impl(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles,
+                                        n_sel_handles, sel_handles, sel_index, n_lookups, width, usable, tail_be32,
+                                        out_commitment48, out_missing, out_handle);
+}
+int kzg_rows_commit_quotient_sel(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
+                                 const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
+                                 const kzg_quotient_selectors* selectors, const kzg_quotient_active* active, uint32_t ext_log,
+                                 uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle) {
+    return rows_quotient_sel_impl(ctx, UINT32_MAX, n_handles, handles, gate, perm, lookup, selectors, active, ext_log, n_pieces,
+                                  out_commitments48, out_handle);
+}
+int kzg_rows_quotient_part_sel(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
+                               const kzg_quotient_perm* perm, const kzg_quotient_link* link, const kzg_quotient_lookup* lookup,
+                               const kzg_quotient_selectors* selectors, const kzg_quotient_active* active, uint32_t ext_log,
+                               const uint8_t* scale_be32, uint64_t* inout_acc) {
+    return rows_quotient_part_sel_impl(ctx, UINT32_MAX, n_handles, handles, gate, perm, link, lookup, selectors, active, ext_log,
+                                       scale_be32, inout_acc);
 }
 int kzg_rows_commit_multiplicities_zk(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
                                       uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,

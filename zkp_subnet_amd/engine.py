@@ -495,6 +495,72 @@ class HipEngine:
                                                               ctypes.byref(miss), ctypes.byref(h)))
         return RowSet(self, h.value, wi, 1, T, [c.raw]), int(miss.value)
 
+    # ---- the two lookup builders with per-row selectors (kzg_rows_commit_*_sel): sel_index[l] is None (no selector) or the
+    # index of lookup l's selector row in the concatenated rows of sel_sets; usable = None is the plain layout (no closing row),
+    # anything else the _zk one
+    def _sel_args(self, what: str, sel_sets, sel_index, n_lookups: int):
+        """(n_sel_handles, the handle array or None, the index array)."""
+        sel_sets = list(sel_sets or [])
+        idx = [_native.KZG_NO_SELECTOR if j is None else j for j in sel_index]
+        if len(idx) != n_lookups or any(not isinstance(j, int) or not 0 <= j <= _native.KZG_NO_SELECTOR for j in idx):
+            raise KzgError(_native.KZG_E_ARG, f"{what}: sel_index must hold n_lookups entries, each None or a row index")
+        ns, hs = self._handle_array(sel_sets, f"{what} (selectors)") if sel_sets else (0, None)
+        return ns, hs, (ctypes.c_uint32 * n_lookups)(*idx)
+
+    def commit_lookup_sum_sel(self, input_sets: Sequence[object], table_sets: Sequence[object], mult_set: object,
+                              sel_sets: Sequence[object], sel_index: Sequence[Optional[int]], n_lookups: int, width: int,
+                              theta_be32: bytes, beta_be32: bytes, usable: Optional[int] = None,
+                              tail_be32: Sequence[bytes] = ()) -> Tuple["RowSet", bytes]:
+        """commit_lookup_sum / _zk with the numerator q_l of lookup l read from row sel_index[l] of the concatenated rows of
+        sel_sets (kzg_rows_commit_lookup_sum_sel); None there is the constant 1.  The library does not judge q.  usable =
+        None (the plain layout) needs the row length, which RowSet objects carry and the engine remembers for the handles of
+        sets committed through it: with bare handles of other origin pass usable = T yourself."""
+        ni, hi = self._handle_array(input_sets, "commit_lookup_sum_sel (inputs)")
+        nt, ht = self._handle_array(table_sets, "commit_lookup_sum_sel (table)")
+        _, hm = self._handle_array([mult_set], "commit_lookup_sum_sel (multiplicities)")
+        if n_lookups < 1 or width < 1 or n_lookups * width > _native.KZG_MAX_BATCH_OPEN or len(theta_be32) != 32 \
+                or len(beta_be32) != 32:
+            raise KzgError(_native.KZG_E_ARG, f"commit_lookup_sum_sel: n_lookups, width >= 1, n_lookups * width <= "
+                                              f"{_native.KZG_MAX_BATCH_OPEN}, theta and beta of 32 bytes each")
+        ns, hs, idx = self._sel_args("commit_lookup_sum_sel", sel_sets, sel_index, n_lookups)
+        sets = list(input_sets) + list(table_sets) + [mult_set]
+        usable, tail, wi, T = self._blind_args("commit_lookup_sum_sel", sets, self._sel_usable(sets, usable), tail_be32)
+        c, cl, h = ctypes.create_string_buffer(48), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_lookup_sum_sel(self._h, ni, hi, nt, ht, hm[0], ns, hs, idx, n_lookups, width,
+                                                           theta_be32, beta_be32, usable, tail, c, cl, ctypes.byref(h)))
+        return RowSet(self, h.value, wi, 1, T, [c.raw]), cl.raw
+
+    def commit_multiplicities_sel(self, input_sets: Sequence[object], table_sets: Sequence[object], sel_sets: Sequence[object],
+                                  sel_index: Sequence[Optional[int]], n_lookups: int, width: int, usable: Optional[int] = None,
+                                  tail_be32: Sequence[bytes] = ()) -> Tuple["RowSet", int]:
+        """commit_multiplicities / _zk over the cells whose selector is not zero (kzg_rows_commit_multiplicities_sel):
+        sel_index[l] names lookup l's selector row in the concatenated rows of sel_sets, None probes every cell.  usable =
+        None: as for commit_lookup_sum_sel."""
+        ni, hi = self._handle_array(input_sets, "commit_multiplicities_sel (inputs)")
+        nt, ht = self._handle_array(table_sets, "commit_multiplicities_sel (table)")
+        if n_lookups < 1 or width < 1 or n_lookups * width > _native.KZG_MAX_BATCH_OPEN:
+            raise KzgError(_native.KZG_E_ARG, f"commit_multiplicities_sel: n_lookups, width >= 1, n_lookups * width <= "
+                                              f"{_native.KZG_MAX_BATCH_OPEN}")
+        ns, hs, idx = self._sel_args("commit_multiplicities_sel", sel_sets, sel_index, n_lookups)
+        sets = list(input_sets) + list(table_sets)
+        usable, tail, wi, T = self._blind_args("commit_multiplicities_sel", sets, self._sel_usable(sets, usable), tail_be32)
+        c, miss, h = ctypes.create_string_buffer(48), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_multiplicities_sel(self._h, ni, hi, nt, ht, ns, hs, idx, n_lookups, width, usable,
+                                                               tail, c, ctypes.byref(miss), ctypes.byref(h)))
+        return RowSet(self, h.value, wi, 1, T, [c.raw]), int(miss.value)
+
+    def _sel_usable(self, sets, usable):
+        """usable = None (the plain layout) is the row length, which the native call expects in its place."""
+        if usable is not None:
+            return usable
+        src = next((x for x in sets if getattr(x, "T", None) is not None), None)
+        T = src.T if src is not None else next(
+            (self._set_len[int(x)][1] for x in sets if not hasattr(x, "handle") and int(x) in self._set_len), None)
+        if T is None:
+            raise KzgError(_native.KZG_E_ARG, "commit_*_sel: the row length of the sets is unknown to this engine (they were "
+                                              "not committed through it)")
+        return T
+
     # ---- a third set built from sets: the PLONK quotient (round 3), computed and committed on the device
     def commit_quotient(self, sets: Sequence[object], terms: Sequence[Tuple[bytes, Sequence[int]]], perm: Optional[dict] = None,
                         ext_log: int = 2, n_pieces: int = 3) -> "RowSet":
@@ -569,6 +635,45 @@ class HipEngine:
         The permutation part then takes at most 2^ext_log - 1 wires and the lookup part at most 2^ext_log - 2 lookups.
         active_row = None is commit_quotient_ext."""
         return self._commit_quotient_ext("commit_quotient_zk", sets, terms, perm, lookup, active_row, ext_log, n_pieces)
+
+    def _quotient_selectors(self, what, selectors, lk):
+        """The ctypes form of a selector list (one entry per lookup: None or a row index of the concatenation), or None."""
+        if selectors is None:
+            return None
+        bad = lambda why: KzgError(_native.KZG_E_ARG, what + ": " + why)   # noqa: E731
+        if lk is None:
+            raise bad("selectors need a lookup part")
+        idx = [_native.KZG_NO_SELECTOR if j is None else j for j in selectors]
+        if len(idx) != lk.n_lookups or any(not isinstance(j, int) or not 0 <= j <= _native.KZG_NO_SELECTOR for j in idx):
+            raise bad("selectors must hold n_lookups entries, each None or a row index")
+        arr = (ctypes.c_uint32 * len(idx))(*idx)
+        sel = _native.QuotientSelectors(arr)
+        sel._keep = arr
+        return sel
+
+    def commit_quotient_sel(self, sets: Sequence[object], terms: Sequence[Tuple[bytes, Sequence[object]]],
+                            perm: Optional[dict] = None, lookup: Optional[dict] = None,
+                            selectors: Optional[Sequence[Optional[int]]] = None, active_row: Optional[int] = None,
+                            ext_log: int = 2, n_pieces: int = 3) -> "RowSet":
+        """commit_quotient_zk with per-row lookup selectors (kzg_rows_commit_quotient_sel): selectors[l] is the row of the
+        concatenation that holds q_l, the numerator of lookup l's fraction in LK1, or None (the constant 1).  selectors = None,
+        or all None, is commit_quotient_zk."""
+        what = "commit_quotient_sel"
+        n, hs, gate, pm, lk, act = self._quotient_args(what, sets, terms, perm, lookup, active_row, ext_log, n_pieces)
+        sel = self._quotient_selectors(what, selectors, lk)
+        ref = lambda x: ctypes.byref(x) if x is not None else None   # noqa: E731
+        c, h = ctypes.create_string_buffer(48 * n_pieces), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_quotient_sel(self._h, n, hs, ctypes.byref(gate), ref(pm), ref(lk), ref(sel), ref(act),
+                                                         ext_log, n_pieces, c, ctypes.byref(h)))
+        src = next((x for x in sets if hasattr(x, "T")), None)
+        return RowSet(self, h.value, getattr(src, "i", None), n_pieces, getattr(src, "T", None),
+                      [c.raw[48 * p:48 * p + 48] for p in range(n_pieces)])
+
+    def quotient_part_sel(self, sets, terms, perm=None, lookup=None, selectors=None, active_row=None, link=None, ext_log: int = 2,
+                          scale_be32: Optional[bytes] = None, acc: Optional["QuotientAcc"] = None) -> "QuotientAcc":
+        """quotient_part with per-row lookup selectors (kzg_rows_quotient_part_sel); selectors as in commit_quotient_sel."""
+        return self.quotient_part(sets, terms, perm, lookup, active_row, link, ext_log, scale_be32, acc, _selectors=selectors,
+                                  _what="quotient_part_sel")
 
     def _commit_quotient_ext(self, what, sets, terms, perm, lookup, active_row, ext_log, n_pieces) -> "RowSet":
         n, hs, gate, pm, lk, act = self._quotient_args(what, sets, terms, perm, lookup, active_row, ext_log, n_pieces)
@@ -660,15 +765,17 @@ class HipEngine:
     # several permutation or lookup arguments) sum their numerator on the device over several calls
     def quotient_part(self, sets: Sequence[object], terms: Sequence[Tuple[bytes, Sequence[object]]], perm: Optional[dict] = None,
                       lookup: Optional[dict] = None, active_row: Optional[int] = None, link: Optional[Tuple[int, int]] = None,
-                      ext_log: int = 2, scale_be32: Optional[bytes] = None, acc: Optional["QuotientAcc"] = None) -> "QuotientAcc":
+                      ext_log: int = 2, scale_be32: Optional[bytes] = None, acc: Optional["QuotientAcc"] = None,
+                      _selectors=None, _what: str = "quotient_part") -> "QuotientAcc":
         """One part of a quotient (kzg_rows_quotient_part): this part's numerator over the concatenated rows of `sets`, with
         terms, perm, lookup and active_row as in commit_quotient_zk and its own row numbering, divided by Z_H on the coset,
         multiplied by scale_be32 (32 bytes, None: 1) and added into `acc` (None: a new accumulator).  link: None, or (prev_row,
         rot): P2 becomes (z(X) - f_prev(w^rot X)) L_0(X), the chain relation of a chunked permutation (needs perm).  Returns
         the accumulator (a QuotientAcc; the one passed in, or the new one); quotient_finish turns it into the pieces.  Each part
         re-extends the rows it names."""
-        n, hs, gate, pm, lk, act = self._quotient_args("quotient_part", sets, terms, perm, lookup, active_row, ext_log, None)
-        bad = lambda why: KzgError(_native.KZG_E_ARG, "quotient_part: " + why)   # noqa: E731
+        n, hs, gate, pm, lk, act = self._quotient_args(_what, sets, terms, perm, lookup, active_row, ext_log, None)
+        sel = self._quotient_selectors(_what, _selectors, lk)
+        bad = lambda why: KzgError(_native.KZG_E_ARG, _what + ": " + why)   # noqa: E731
         ln = None
         if link is not None:
             try:
@@ -687,11 +794,13 @@ class HipEngine:
         if acc is not None and not isinstance(acc, QuotientAcc):
             raise bad("acc must be a QuotientAcc returned by quotient_part, or None")
         h = ctypes.c_uint64(0 if acc is None else acc.handle)
-        self._chk(self._lib.kzg_rows_quotient_part(self._h, n, hs, ctypes.byref(gate), ctypes.byref(pm) if pm is not None else None,
-                                                   ctypes.byref(ln) if ln is not None else None,
-                                                   ctypes.byref(lk) if lk is not None else None,
-                                                   ctypes.byref(act) if act is not None else None, ext_log, scale_be32,
-                                                   ctypes.byref(h)))
+        ref = lambda x: ctypes.byref(x) if x is not None else None   # noqa: E731
+        if _selectors is None:
+            self._chk(self._lib.kzg_rows_quotient_part(self._h, n, hs, ctypes.byref(gate), ref(pm), ref(ln), ref(lk), ref(act),
+                                                       ext_log, scale_be32, ctypes.byref(h)))
+        else:
+            self._chk(self._lib.kzg_rows_quotient_part_sel(self._h, n, hs, ctypes.byref(gate), ref(pm), ref(ln), ref(lk), ref(sel),
+                                                           ref(act), ext_log, scale_be32, ctypes.byref(h)))
         if acc is not None:
             return acc
         src = next((x for x in sets if hasattr(x, "T")), None)

@@ -221,10 +221,42 @@ class MultiDeviceClient:
         return self._routed_builder("worker_commit_multiplicities_zk", list(input_handles) + list(table_handles), input_handles,
                                     table_handles, n_lookups, width, usable, tail)
 
+    def worker_commit_lookup_sum_sel(self, input_handles: Sequence[int], table_handles: Sequence[int], mult_handle: int,
+                                     sel_handles, sel_index, n_lookups, width, theta, beta, usable=None, tail=()):
+        return self._routed_builder("worker_commit_lookup_sum_sel",
+                                    list(input_handles) + list(table_handles) + [mult_handle] + list(sel_handles or []),
+                                    input_handles, table_handles, mult_handle, sel_handles, sel_index, n_lookups, width, theta,
+                                    beta, usable, tail)
+
+    def worker_commit_multiplicities_sel(self, input_handles: Sequence[int], table_handles: Sequence[int], sel_handles, sel_index,
+                                         n_lookups, width, usable=None, tail=()):
+        return self._routed_builder("worker_commit_multiplicities_sel",
+                                    list(input_handles) + list(table_handles) + list(sel_handles or []), input_handles,
+                                    table_handles, sel_handles, sel_index, n_lookups, width, usable, tail)
+
     def worker_commit_quotient_zk(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None, ext_log=2,
                                   n_pieces=3):
         return self._routed_builder("worker_commit_quotient_zk", handles, handles, terms, perm, lookup, active_row, ext_log,
                                     n_pieces)
+
+    def worker_commit_quotient_sel(self, handles: Sequence[int], terms, perm=None, lookup=None, selectors=None, active_row=None,
+                                   ext_log=2, n_pieces=3):
+        return self._routed_builder("worker_commit_quotient_sel", handles, handles, terms, perm, lookup, selectors, active_row,
+                                    ext_log, n_pieces)
+
+    def worker_quotient_part_sel(self, handles: Sequence[int], terms, perm=None, lookup=None, selectors=None, active_row=None,
+                                 link=None, ext_log=2, scale=None, acc=None):
+        try:
+            i = self._owner(list(handles) + ([acc] if acc is not None else []))
+        except TypeError:
+            i = None
+        if i is None:
+            return Response(400, {"error": "worker_quotient_part_sel: the handles and the accumulator must be live and of one "
+                                           "worker"})
+        r = self._for(i).worker_quotient_part_sel(handles, terms, perm, lookup, selectors, active_row, link, ext_log, scale, acc)
+        if r.status_code == 200:
+            self._row_owner[int(r.json()["acc"])] = i
+        return r
 
     def worker_quotient_part(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None, link=None, ext_log=2,
                              scale=None, acc=None):
