@@ -215,6 +215,38 @@ int kzg_rows_eval(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uin
 int kzg_rows_open_lincomb(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
                           const uint8_t* points_be32 /* m*32 */, const uint8_t* coeffs_be32 /* m*k*32 */,
                           uint8_t* out_values32 /* m*32 */, uint8_t* out_proofs48 /* m*48 */);
+/* SHPLONK (BDFG20) multi-open over committed sets: ONE proof pair (W, pi) for k rows opened at any number of points, where the
+ * GWC calls above return one proof per point.  Rows f_0 .. f_{k-1}: the concatenated rows of the handles' sets; points
+ * alpha_0 .. alpha_{m-1}, pairwise distinct, P the set of all of them; masks[p] bit j set when row j is opened at alpha_p (the
+ * convention of kzg_rows_eval), S_j = { p : bit j of masks[p] } row j's point set, Z_S = prod_{p in S} (X - alpha_p), r_j the
+ * interpolant of f_j on S_j; c_0 .. c_{k-1} caller scalars (in halo2: products of powers of its challenges y and v).
+ * Round A, kzg_rows_commit_shplonk -- a set built FROM sets:
+ *   h = sum_{j : c_j != 0} c_j (f_j - r_j) / Z_{S_j}
+ * is computed on the device (rows with equal S_j are combined first, then divided by one point after the other; no
+ * evaluation, no interpolation), and committed as a new ONE-ROW set of the same worker and length: out_commitment48 = W
+ * equals kzg_commit of h's coefficients (T of them, evaluation_form = 0) byte for byte, and *out_handle opens, evaluates,
+ * combines, releases, goes stale and counts against KZG_MAX_ROW_SETS (KZG_E_BUSY; KZG_E_NOMEM on a failed allocation) like
+ * any other.  No upload of anything row-sized, no evaluation returned.
+ * Round B is host arithmetic and kzg_rows_open_lincomb: the caller hashes W, draws u outside P, and with
+ *   lambda_j = c_j Z_{P \ S_j}(u)  (j < k),   lambda_k = -Z_P(u)
+ * opens L = sum_j lambda_j f_j + lambda_k h -- the k rows followed by h -- at the single point u.  The call returns
+ *   v = L(u) = sum_j c_j Z_{P \ S_j}(u) r_j(u)   and   pi = [(L - v) / (X - u)].
+ * The proof is (W, pi): 96 bytes, two MSMs and (kzg_vk_verify_open_shplonk) two pairings whatever m is.
+ * Handle rules as kzg_rows_commit_grand_product: a handle may repeat (its rows are numbered twice); unknown / released /
+ * stale handles, mixed workers or lengths -> KZG_E_ARG; the source sets are only read; a release or an SRS load racing the
+ * call behaves as for kzg_rows_open; thread-safe; after any error the context keeps serving.  KZG_E_ARG with a message that
+ * names it: k != the rows of the concatenation; k = 0 or k > KZG_MAX_SHPLONK_ROWS; m = 0 or m > KZG_MAX_SHPLONK_POINTS; a
+ * point or coefficient >= r; two equal points (unlike the GWC calls, where each point keeps its own proof); a mask bit >= k;
+ * a row with c_j != 0 and an empty S_j; all c_j zero; some |S_j| >= T.  A row with c_j = 0 is left out, whatever its mask.
+ * More than KZG_MAX_SHPLONK_ROWS opened rows compose by linearity: several round-A calls with the same points, their W (and
+ * later their pi) summed with kzg_g1_sum_compressed and their v added; the library has no helper for that.
+ * SOUNDNESS: the c_j must be drawn AFTER the commitments AND the evaluations of kzg_rows_eval are fixed, and u AFTER W.  The
+ * library derives no challenge. */
+#define KZG_MAX_SHPLONK_POINTS 8
+#define KZG_MAX_SHPLONK_ROWS   (KZG_MAX_BATCH_OPEN - 1)    /* round B opens k + 1 rows */
+int kzg_rows_commit_shplonk(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
+                            const uint8_t* points_be32 /* m*32 */, const uint32_t* masks /* m */,
+                            const uint8_t* coeffs_be32 /* k*32 */, uint8_t out_commitment48[48], uint64_t* out_handle);
 /* A set built FROM sets: the permutation grand product (PLONK round 2), computed and committed on the device from rows that
  * are already resident.  The wire rows a_0 .. a_{k-1} are the concatenated rows of the wire_handles sets, the permutation rows
  * sigma_0 .. sigma_{k-1} those of the sigma_handles sets.  With w the T-th root of unity of evaluation_form = 1 rows
@@ -672,6 +704,17 @@ int kzg_vk_verify_open_multi(const kzg_vk* vk, uint32_t i, uint32_t k, const uin
 int kzg_vk_verify_open_lincomb(const kzg_vk* vk, uint32_t i, uint32_t k, const uint8_t* commitments48, uint32_t m,
                                const uint8_t* points_be32, const uint8_t* coeffs_be32, const uint8_t* values_be32,
                                const uint8_t* proofs48, int* out_valid);
+/* One SHPLONK opening (kzg_rows_commit_shplonk + kzg_rows_open_lincomb at u) of k rows of slice i at m points.  evals32: the
+ * evaluations y_{j,p} in the point-major layout of kzg_rows_eval for the same points and masks.  The host computes r_j(u) by
+ * Lagrange interpolation over S_j, from them v and the lambda of round B, and runs the check of kzg_vk_verify_open_lincomb on
+ * the k + 1 commitments (C_0 .. C_{k-1}, W) at the one point u with value v and proof pi: two pairings whatever m is.
+ * Malformed, off-curve or non-G1 commitment / W / proof bytes and a well-formed but false proof give *out_ok = 0 (not an
+ * error).  The argument checks of kzg_rows_commit_shplonk (each KZG_E_ARG), u equal to one of the points or i outside the
+ * key -> KZG_E_ARG; an evaluation or u >= r -> KZG_E_SCALAR. */
+int kzg_vk_verify_open_shplonk(const kzg_vk* vk, uint32_t i, uint32_t k, const uint8_t* commitments48 /* k*48 */, uint32_t m,
+                               const uint8_t* points_be32, const uint32_t* masks, const uint8_t* coeffs_be32 /* k*32 */,
+                               const uint8_t* evals32 /* kzg_rows_eval's point-major layout */,
+                               const uint8_t w48[48], const uint8_t u_be32[32], const uint8_t proof48[48], int* out_ok);
 
 /* ---- multi-GPU: each rank reduces its SRS shard to ONE partial sum; the 192-byte partials are exchanged by
  *      the caller (RCCL all_gather over xGMI in zkp_subnet_amd.distributed) and summed on any rank. */
@@ -814,6 +857,10 @@ int kzg_multi_rows_eval(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uin
 int kzg_multi_rows_open_lincomb(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t k,
                                 uint32_t m, const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32,
                                 uint8_t* out_proofs48);
+/* kzg_rows_commit_shplonk on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_shplonk(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
+                                  const uint8_t* points_be32, const uint32_t* masks, const uint8_t* coeffs_be32,
+                                  uint8_t out_commitment48[48], uint64_t* out_handle);
 /* kzg_rows_commit_grand_product on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
 int kzg_multi_rows_commit_grand_product(kzg_multi* mh, uint32_t i, uint32_t n_wire_handles, const uint64_t* wire_handles,
                                         uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,

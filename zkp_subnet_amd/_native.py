@@ -19,6 +19,8 @@ LIB_PATH = os.environ.get("KZG_MI355X_LIB") or os.path.join(HERE, "libkzg_mi355x
 KZG_MAX_BATCH_OPEN = 16   # include/kzg_mi355x.h
 KZG_MAX_OPEN_POINTS = 4
 KZG_MAX_ROW_SETS = 64
+KZG_MAX_SHPLONK_POINTS = 8                      # kzg_rows_commit_shplonk
+KZG_MAX_SHPLONK_ROWS = KZG_MAX_BATCH_OPEN - 1   # round B opens k + 1 rows
 KZG_MAX_GATE_TERMS = 16   # kzg_rows_commit_quotient
 KZG_MAX_BLIND_ROWS = 32   # kzg_rows_commit_*_zk: T - usable
 KZG_NO_SELECTOR = 0xffffffff   # kzg_rows_commit_*_sel: a lookup without a selector row
@@ -102,6 +104,8 @@ SYMBOLS = {
     "kzg_rows_stats": (_I, [_P, ctypes.POINTER(_U64)]),
     "kzg_rows_eval": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _B, ctypes.POINTER(_U32), _B]),
     "kzg_rows_open_lincomb": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _U32, _B, _B, _B, _B]),
+    "kzg_rows_commit_shplonk": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _U32, _B, ctypes.POINTER(_U32), _B, _B,
+                                     ctypes.POINTER(_U64)]),
     "kzg_rows_commit_grand_product": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _B, _B, _B, _B, _B,
                                            ctypes.POINTER(_U64)]),
     "kzg_rows_commit_lookup_sum": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B, _B, _B, _B,
@@ -156,6 +160,8 @@ SYMBOLS = {
     "kzg_vk_verify_open_batch": (_I, [_P, _U32, _U32, _B, _B, _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_vk_verify_open_multi": (_I, [_P, _U32, _U32, _B, _U32, _B, ctypes.POINTER(_U32), _B, _B, _B, ctypes.POINTER(_I)]),
     "kzg_vk_verify_open_lincomb": (_I, [_P, _U32, _U32, _B, _U32, _B, _B, _B, _B, ctypes.POINTER(_I)]),
+    "kzg_vk_verify_open_shplonk": (_I, [_P, _U32, _U32, _B, _U32, _B, ctypes.POINTER(_U32), _B, _B, _B, _B, _B,
+                                        ctypes.POINTER(_I)]),
     "kzg_vk_pairing": (_I, [_B, _B, _B]),
     "kzg_msm_partial": (_I, [_P, _B, _U64, _U64, _B]),
     "kzg_g1_sum": (_I, [_P, _B, _U32, _B]),
@@ -197,6 +203,8 @@ SYMBOLS = {
     "kzg_multi_rows_release": (_I, [_P, _U32, _U64]),
     "kzg_multi_rows_eval": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _B, ctypes.POINTER(_U32), _B]),
     "kzg_multi_rows_open_lincomb": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _U32, _B, _B, _B, _B]),
+    "kzg_multi_rows_commit_shplonk": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _U32, _B, ctypes.POINTER(_U32), _B, _B,
+                                           ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_grand_product": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _B, _B, _B,
                                                  _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_lookup_sum": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B,
@@ -285,6 +293,22 @@ def open_masks(opened, k: int):
         rows = [int(j) for j in rows]
         if not rows or any(b <= a for a, b in zip(rows, rows[1:])) or rows[0] < 0 or rows[-1] >= k:
             raise KzgError(KZG_E_ARG, f"multi-point opening: point {p} opens {rows}, expected increasing rows in [0, {k})")
+        masks[p] = sum(1 << j for j in rows)
+    return masks, sum(len(r) for r in opened)
+
+
+def shplonk_masks(opened, k: int):
+    """The SHPLONK row masks (bit j = row j) from opened[p], the rows opened at point p as a strictly increasing list of
+    indices in [0, k) (it may be empty: the point then only enters Z_P); a (ctypes uint32 array, number of evaluations).
+    KzgError(KZG_E_ARG) for anything else."""
+    m = len(opened)
+    if m == 0 or m > KZG_MAX_SHPLONK_POINTS:
+        raise KzgError(KZG_E_ARG, f"shplonk: {m} points, expected 1 .. {KZG_MAX_SHPLONK_POINTS}")
+    masks = (ctypes.c_uint32 * m)()
+    for p, rows in enumerate(opened):
+        rows = [int(j) for j in rows]
+        if any(b <= a for a, b in zip(rows, rows[1:])) or (rows and (rows[0] < 0 or rows[-1] >= k)):
+            raise KzgError(KZG_E_ARG, f"shplonk: point {p} opens {rows}, expected increasing rows in [0, {k})")
         masks[p] = sum(1 << j for j in rows)
     return masks, sum(len(r) for r in opened)
 

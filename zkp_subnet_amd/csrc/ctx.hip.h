@@ -140,7 +140,8 @@ static_assert(BR_COPY % 4 == 0 && BR_COPY <= 8192, "the batched record is publis
 enum {
     MR_RES = 0, MR_EVAL = MR_RES + MR_SETS * 224, MR_C48 = MR_EVAL + MR_PAIRS * 32, MR_COPY = MR_C48 + MR_SETS * 48,
     MR_Y_M = MR_COPY, MR_ALPHA_M = MR_Y_M + MR_PAIRS * 32, MR_HY_M = MR_ALPHA_M + KZG_MAX_OPEN_POINTS * 32,
-    MR_SIZE = MR_HY_M + KZG_MAX_OPEN_POINTS * 32
+    MR_SH_ALPHA_M = MR_HY_M + KZG_MAX_OPEN_POINTS * 32,   // the points of kzg_rows_commit_shplonk in Montgomery form
+    MR_SIZE = MR_SH_ALPHA_M + KZG_MAX_SHPLONK_POINTS * 32
 };
 static_assert(MR_COPY % 4 == 0 && MR_COPY <= 8192, "the multi-point record is published by words into an 8 KB page");
 static_assert(MR_PAIRS <= POLY_MAX_PAIRS && KZG_MAX_OPEN_POINTS <= POLY_MAX_POINTS, "one evaluation launch holds every pair");
@@ -415,6 +416,16 @@ int rows_eval_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint3
 int rows_lincomb_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t k, uint64_t T, uint32_t m,
                      const uint8_t* points_be32, const uint8_t* coeffs_be32, const uint32_t* masks, uint8_t* out_values32,
                      uint8_t* out_p48);
+// kzg_rows_commit_shplonk: the rows with one point set S form a group (rows: their mask; pt: S, ascending); the caller hands
+// the groups over sorted by descending npts, so that the groups still dividing in pass d are a prefix of every batch.
+// h = sum_groups quot(sum_{j in group} c_j f_j, Z_S) goes into the new one-row set's buffer dst; its commitment to out_c48.
+struct ShGroup {
+    uint32_t rows;
+    uint8_t npts, pt[KZG_MAX_SHPLONK_POINTS];
+};
+int rows_shplonk_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t k, uint64_t T, uint32_t m,
+                     const uint8_t* points_be32, const uint8_t* coeffs_be32, uint32_t n_groups, const ShGroup* groups,
+                     uint32_t* dst, uint8_t* out_c48);
 // The blinding rows of a kzg_rows_commit_*_zk builder (checked by the caller: 1 <= usable < T, T - usable <=
 // KZG_MAX_BLIND_ROWS, every tail scalar canonical): rows [0, usable) carry the circuit, row `usable` closes the running value
 // and rows usable + 1 .. T - 1 take the T - usable - 1 scalars of tail_be32 (host bytes).  Null: the plain builder.
@@ -472,6 +483,9 @@ int rows_eval_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const ui
 int rows_lincomb_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
                       const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32, uint8_t* out_proofs48);
 int rows_release_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle);
+int rows_shplonk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
+                      const uint8_t* points_be32, const uint32_t* masks, const uint8_t* coeffs_be32, uint8_t* out_commitment48,
+                      uint64_t* out_handle);
 int rows_grand_product_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
                             uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
                             const uint8_t* beta_be32, const uint8_t* gamma_be32, uint8_t* out_commitment48,

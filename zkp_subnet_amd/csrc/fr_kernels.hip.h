@@ -64,7 +64,10 @@ void launch_poly_eval_pairs(hipStream_t s, const RowTab& rt, uint64_t n, uint32_
 // (y_be given: y_p also as 32 big-endian bytes at y_be + 32 p)
 void launch_poly_open_points(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t m, const uint32_t* alpha_mont,
                              uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont, uint32_t* q_canon,
-                             uint8_t* y_be = nullptr);
+                             uint8_t* y_be = nullptr, const uint8_t* pts = nullptr, bool q_mont = false);
+// out[t] = (accumulate ? out[t] : 0) + sum_{g < cnt} rt.r[g][t] over n elements (Montgomery in and out, reduced below r):
+// the sum of the groups' final quotients of kzg_rows_commit_shplonk
+void launch_fr_sum_rows(hipStream_t s, const RowTab& rt, uint32_t cnt, uint64_t n, bool accumulate, uint32_t* out_mont);
 // h_p[t] = sum gamma_p^j rt.r[j][t] over the rows j of mask[p] (Montgomery in and out) into out + p * n elements, for
 // p < m in one launch; g[p]: gamma_p's 32 big-endian bytes, *bad raised when one is >= r
 struct CombArg {
@@ -78,6 +81,8 @@ void launch_fr_combine_points(hipStream_t s, const RowTab& rt, uint64_t n, uint3
 // exactly when lambda_{p,j} != 0 (the rows the kernel reads).  Point p (32 big-endian bytes at points_be32 + 32 p) is
 // converted by the launch and left at alpha_mont + 8 p for the openings behind it.  *bad raised for a coefficient or a
 // point >= r.  The launcher packs all of it into ONE kernel argument (2.4 KB at m = 4, k = 16).
+// alpha_mont == null (the group combinations of kzg_rows_commit_shplonk, "point" read as "group of rows with one point
+// set"): no point is converted and points_be32 is not read.
 void launch_fr_lincomb_points(hipStream_t s, const RowTab& rt, uint64_t n, uint32_t m, uint32_t k, const uint8_t* coeffs_be32,
                               const uint32_t* masks, const uint8_t* points_be32, uint32_t* out_mont, uint32_t* alpha_mont,
                               uint32_t* bad);

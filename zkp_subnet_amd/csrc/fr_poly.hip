@@ -184,6 +184,9 @@ __global__ void __launch_bounds__(256) k_poly_chunk_expand(const uint32_t* __res
     poly_chunk_expand(h, nchunks, l2, alpha_mont, sq, hnext2, hnext);
 }
 // q[j-1] = sum_{k>=j} f_k alpha^(k-j), written canonical (ready to be MSM scalars); q has n-1 entries
+// MONT: the entries stay in Montgomery form (reduced below r), the input of a further division: the chained quotients of
+// kzg_rows_commit_shplonk divide by one point after the other.  Same recurrence, only the form of the stored value differs.
+template <bool MONT>
 KZG_DEV void poly_quotient(const uint32_t* __restrict__ f, uint64_t n, int lchunk, const uint32_t* __restrict__ alpha_mont,
                            const uint32_t* __restrict__ hnext, uint32_t* __restrict__ q_canon) {
     uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -199,7 +202,8 @@ KZG_DEV void poly_quotient(const uint32_t* __restrict__ f, uint64_t n, int lchun
         fr9_mul(s, s, a);
         fr9_add(s, s, c);
         if (j >= 1) {
-            fr9_from_mont(o, s);
+            if constexpr (MONT) fr9_reduce(o, s);
+            else fr9_from_mont(o, s);
             fr9_store(q_canon + 8 * (j - 1), o);
         }
     }
@@ -212,7 +216,7 @@ __global__ void __launch_bounds__(256) k_poly_quotient(const uint32_t* __restric
                                                         const uint32_t* __restrict__ alpha_mont,
                                                         const uint32_t* __restrict__ hnext,
                                                         uint32_t* __restrict__ q_canon) {
-    poly_quotient(f, n, lchunk, alpha_mont, hnext, q_canon);
+    poly_quotient<false>(f, n, lchunk, alpha_mont, hnext, q_canon);
 }
 
 // ---- the multi-point opening (kzg_commit_open_multi, kzg_rows_open): grid row y is a PAIR -- row pa.row[y] at point
@@ -247,12 +251,13 @@ __global__ void __launch_bounds__(256) k_poly_pairs_expand(const uint32_t* __res
     const uint32_t y = blockIdx.y;
     poly_chunk_expand(h + y * h_rs, nchunks, l2, alpha_mont + 8 * pa.pt[y], sq, hnext2 + y * h_rs, hnext + y * h_rs);
 }
+template <bool MONT>
 __global__ void __launch_bounds__(256) k_poly_pairs_quotient(const uint32_t* __restrict__ f, uint64_t n, int lchunk,
                                                               const uint32_t* __restrict__ alpha_mont,
                                                               const uint32_t* __restrict__ hnext, uint32_t* __restrict__ q_canon,
                                                               uint64_t f_rs, uint64_t h_rs, const PairArg pa) {
     const uint32_t y = blockIdx.y;
-    poly_quotient(f + y * f_rs, n, lchunk, alpha_mont + 8 * pa.pt[y], hnext + y * h_rs, q_canon + y * f_rs);
+    poly_quotient<MONT>(f + y * f_rs, n, lchunk, alpha_mont + 8 * pa.pt[y], hnext + y * h_rs, q_canon + y * f_rs);
 }
 
 // ---- the batched opening's combination h[t] = sum_j gamma^j c_j[t] over k Montgomery rows at a stride of n elements
@@ -349,7 +354,7 @@ __global__ void __launch_bounds__(256) k_fr_lincomb_points(const RowTab rt, uint
         fr9_to_mont(c, c);
 #pragma unroll
         for (int i = 0; i < 9; i++) lam[v][i] = c.l[i];
-    } else if (v == POLY_MAX_ROWS && blockIdx.x == 0) {   // the point, as the pair kernels' first level publishes it
+    } else if (v == POLY_MAX_ROWS && blockIdx.x == 0 && alpha_mont) {   // the point, as the pair kernels' first level publishes it
         uint32_t w[8];
 #pragma unroll
         for (int i = 0; i < 8; i++) w[i] = bswap32(la.a[p].w[7 - i]);
@@ -383,10 +388,32 @@ void launch_fr_lincomb_points(hipStream_t s, const RowTab& rt, uint64_t n, uint3
     memset(&la, 0, sizeof(la));
     for (uint32_t p = 0; p < m; p++) {
         la.mask[p] = masks[p];
-        memcpy(la.a[p].w, points_be32 + 32 * (size_t)p, 32);
+        if (alpha_mont) memcpy(la.a[p].w, points_be32 + 32 * (size_t)p, 32);
         for (uint32_t j = 0; j < k; j++) memcpy(la.lam[p][j].w, coeffs_be32 + 32 * ((size_t)p * k + j), 32);
     }
     k_fr_lincomb_points<<<dim3(nblk(n, 256), m), 256, 0, s>>>(rt, n, la, out_mont, alpha_mont, bad);
+}
+
+// ---- the sum behind the chained quotients (kzg_rows_commit_shplonk): out[t] = (acc ? out[t] : 0) + sum_{g < cnt} rt.r[g][t],
+// Montgomery in, reduced Montgomery out (what a row set holds).  HBM-bound: (cnt + acc) * 32 bytes in and 32 out per element.
+__global__ void __launch_bounds__(256) k_fr_sum_rows(const RowTab rt, uint32_t cnt, uint64_t n, int acc, uint32_t* out) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    fr9_t s, c;
+    fr9_zero(s);
+    if (acc) fr9_load(s, out + 8 * t);
+    for (uint32_t g = 0; g < cnt; g++) {   // one sum per term, renormalised: < (cnt + 1) r <= 17 r, a legal fr9_reduce input
+        fr9_load(c, rt.r[g] + 8 * t);
+        fr9_add(s, s, c);
+        fr9_norm(s, s);
+    }
+    fr9_reduce(s, s);
+    fr9_store(out + 8 * t, s);
+}
+void launch_fr_sum_rows(hipStream_t s, const RowTab& rt, uint32_t cnt, uint64_t n, bool accumulate, uint32_t* out_mont) {
+    // cnt <= POLY_MAX_ROWS is the caller's to keep (rows_shplonk_dev adds at most KZG_MAX_OPEN_POINTS vectors per launch,
+    // checked there at compile time); the test only keeps a wrong caller from reading past the table
+    if (n && cnt <= POLY_MAX_ROWS) k_fr_sum_rows<<<nblk(n, 256), 256, 0, s>>>(rt, cnt, n, accumulate ? 1 : 0, out_mont);
 }
 
 // ---- long rows (16 coefficients per lane): the quotient (and, as an A/B form, the level-0 fold) with the coefficients
@@ -614,13 +641,20 @@ void launch_poly_eval_pairs(hipStream_t s, const RowTab& rt, uint64_t n, uint32_
 }
 // the levels go up with the pair kernels (pair p = combination p at point p), then back down as in launch_poly_open with
 // grid y = point; long rows' LDS-staged quotient runs once per point
+// pts (the chained divisions of kzg_rows_commit_shplonk): vector p is divided by the point alpha_mont + 8 pts[p] instead of
+// point p, and q_mont keeps the quotients in Montgomery form for the next division (always the strided quotient kernel)
 void launch_poly_open_points(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t m, const uint32_t* alpha_mont,
                              uint32_t* h, uint32_t* hnext, uint64_t h_rs, uint32_t* y_mont, uint32_t* q_canon,
-                             uint8_t* y_be) {
-    if (!n || !m) return;
+                             uint8_t* y_be, const uint8_t* pts, bool q_mont) {
+    // m <= POLY_MAX_POINTS is the caller's to keep (the C-ABI refuses more points; rows_shplonk_dev batches its groups by
+    // KZG_MAX_OPEN_POINTS, checked at compile time); the test only keeps a wrong caller from writing past PairArg
+    if (!n || !m || m > POLY_MAX_POINTS) return;
     PairArg pa;
     memset(&pa, 0, sizeof(pa));
-    for (uint32_t p = 0; p < m; p++) pa.row[p] = pa.pt[p] = (uint8_t)p;
+    for (uint32_t p = 0; p < m; p++) {
+        pa.row[p] = (uint8_t)p;
+        pa.pt[p] = pts ? pts[p] : (uint8_t)p;
+    }
     PolyLevels lv;
     uint32_t* am = const_cast<uint32_t*>(alpha_mont);   // (read only: no point is converted on this path)
     poly_up(s, f_mont, n, m, am, h, hnext, h_rs, y_mont, nullptr, nullptr, y_be, lv, &pa);
@@ -629,12 +663,15 @@ void launch_poly_open_points(hipStream_t s, const uint32_t* f_mont, uint64_t n, 
         k_poly_pairs_expand<<<dim3(nblk(lv.n[k + 1], 256), m), 256, 0, s>>>(h + 8 * lv.off[k], lv.n[k], lv.l[k], alpha_mont,
                                                                             lv.sq[k], hnext + 8 * lv.off[k + 1],
                                                                             hnext + 8 * lv.off[k], h_rs, pa);
-    if (quotient_lds(n, l0)) {
+    if (q_mont) {
+        k_poly_pairs_quotient<true><<<dim3(nblk(lv.n[1], 256), m), 256, 0, s>>>(f_mont, n, l0, alpha_mont, hnext, q_canon, n * 8,
+                                                                                h_rs, pa);
+    } else if (quotient_lds(n, l0)) {
         for (uint32_t p = 0; p < m; p++)
-            k_poly_quotient16_lds<<<(uint32_t)(n >> 10), 64, 0, s>>>(f_mont + p * n * 8, n, alpha_mont + 8 * p, hnext + p * h_rs,
-                                                                    q_canon + p * n * 8);
+            k_poly_quotient16_lds<<<(uint32_t)(n >> 10), 64, 0, s>>>(f_mont + p * n * 8, n, alpha_mont + 8 * pa.pt[p],
+                                                                    hnext + p * h_rs, q_canon + p * n * 8);
     } else {
-        k_poly_pairs_quotient<<<dim3(nblk(lv.n[1], 256), m), 256, 0, s>>>(f_mont, n, l0, alpha_mont, hnext, q_canon, n * 8,
+        k_poly_pairs_quotient<false><<<dim3(nblk(lv.n[1], 256), m), 256, 0, s>>>(f_mont, n, l0, alpha_mont, hnext, q_canon, n * 8,
                                                                           h_rs, pa);
     }
 }

@@ -31,6 +31,9 @@ int rows_eval_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const ui
 int rows_lincomb_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
                       const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32, uint8_t* out_proofs48);
 int rows_release_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle);
+int rows_shplonk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
+                      const uint8_t* points_be32, const uint32_t* masks, const uint8_t* coeffs_be32, uint8_t* out_commitment48,
+                      uint64_t* out_handle);
 int rows_grand_product_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
                             uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
                             const uint8_t* beta_be32, const uint8_t* gamma_be32, uint8_t* out_commitment48,
@@ -488,6 +491,15 @@ int kzg_multi_rows_open_lincomb(kzg_multi* mh, uint32_t i, uint32_t n_handles, c
     if (int rc = route(mh, i, &c, &s)) return rc;
     return relay(c, kzg_impl::rows_lincomb_impl(c, s, n_handles, handles, k, m, points_be32, coeffs_be32, out_values32,
                                                 out_proofs48));
+}
+int kzg_multi_rows_commit_shplonk(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
+                                  const uint8_t* points_be32, const uint32_t* masks, const uint8_t* coeffs_be32,
+                                  uint8_t out_commitment48[48], uint64_t* out_handle) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(mh, i, &c, &s)) return rc;
+    return relay(c, kzg_impl::rows_shplonk_impl(c, s, n_handles, handles, k, m, points_be32, masks, coeffs_be32,
+                                                out_commitment48, out_handle));
 }
 int kzg_multi_rows_commit_grand_product(kzg_multi* mh, uint32_t i, uint32_t n_wire_handles, const uint64_t* wire_handles,
                                         uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,

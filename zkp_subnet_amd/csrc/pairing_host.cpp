@@ -812,6 +812,134 @@ int kzg_vk_verify_open_lincomb(const kzg_vk* vk, uint32_t i, uint32_t k, const u
     }
 }
 
+/* ---- SHPLONK: the verifier's Fr arithmetic beyond sums and products */
+static void fr_sub_mod(u64 out[4], const u64 a[4], const u64 b[4]) {   // out = a - b mod r, a and b < r
+    u64 nb[4];
+    u128 br = 0;
+    for (int w = 0; w < 4; w++) {   // nb = r - b (b = 0: r, which fr_add_mod's conditional subtraction takes out again)
+        const u128 t = (u128)R_ORDER[w] - b[w] - (u64)br;
+        nb[w] = (u64)t;
+        br = (t >> 64) & 1;
+    }
+    u64 s[4] = {a[0], a[1], a[2], a[3]};
+    if ((b[0] | b[1] | b[2] | b[3]) != 0) fr_add_mod(s, nb);
+    memcpy(out, s, sizeof(s));
+}
+static void fr_inv_mod(u64 out[4], const u64 a[4]) {   // a^(r - 2): the one inversion of a verification
+    u64 e[4] = {R_ORDER[0] - 2, R_ORDER[1], R_ORDER[2], R_ORDER[3]}, acc[4] = {1, 0, 0, 0};
+    for (int bit = 255; bit >= 0; bit--) {
+        fr_mul_mod(acc, acc, acc);
+        if ((e[bit / 64] >> (bit % 64)) & 1) fr_mul_mod(acc, acc, a);
+    }
+    memcpy(out, acc, sizeof(acc));
+}
+static void fr_to_be32(uint8_t* b, const u64 k[4]) {
+    for (int w = 0; w < 4; w++)
+        for (int t = 0; t < 8; t++) b[32 - 8 * w - 1 - t] = (uint8_t)(k[w] >> (8 * t));
+}
+/* r_j(u) by Lagrange interpolation over S_j, v = sum_j c_j Z_{P \ S_j}(u) r_j(u), lambda_j = c_j Z_{P \ S_j}(u),
+ * lambda_k = -Z_P(u); then the check of kzg_vk_verify_open_lincomb on (C_0 .. C_{k-1}, W) at the one point u.  The pairwise
+ * differences alpha_p - alpha_q are inverted together (one inversion). */
+int kzg_vk_verify_open_shplonk(const kzg_vk* vk, uint32_t i, uint32_t k, const uint8_t* commitments48, uint32_t m,
+                               const uint8_t* points_be32, const uint32_t* masks, const uint8_t* coeffs_be32,
+                               const uint8_t* evals32, const uint8_t w48[48], const uint8_t u_be32[32],
+                               const uint8_t proof48[48], int* out_ok) {
+    if (!vk || !commitments48 || !points_be32 || !masks || !coeffs_be32 || !evals32 || !w48 || !u_be32 || !proof48 || !out_ok)
+        return KZG_E_ARG;
+    *out_ok = 0;
+    if (k == 0 || k > KZG_MAX_SHPLONK_ROWS || m == 0 || m > KZG_MAX_SHPLONK_POINTS || i >= vk->k.li.size()) return KZG_E_ARG;
+    const uint32_t M = KZG_MAX_SHPLONK_POINTS, K = KZG_MAX_SHPLONK_ROWS;
+    u64 alpha[M][4], c[K][4], u[4];
+    uint32_t first[M], npairs = 0;                           // the point's first evaluation
+    for (uint32_t p = 0; p < m; p++) {
+        if (!fr_from_be32(alpha[p], points_be32 + 32 * (size_t)p)) return KZG_E_ARG;
+        for (uint32_t q = 0; q < p; q++)
+            if (memcmp(alpha[p], alpha[q], sizeof(alpha[p])) == 0) return KZG_E_ARG;
+        if ((masks[p] >> k) != 0) return KZG_E_ARG;
+        first[p] = npairs;
+        npairs += (uint32_t)__builtin_popcount(masks[p]);
+    }
+    bool any = false;
+    for (uint32_t j = 0; j < k; j++) {
+        if (!fr_from_be32(c[j], coeffs_be32 + 32 * (size_t)j)) return KZG_E_ARG;
+        if (!(c[j][0] | c[j][1] | c[j][2] | c[j][3])) continue;
+        any = true;
+        bool opened = false;
+        for (uint32_t p = 0; p < m; p++) opened = opened || ((masks[p] >> j) & 1u);
+        if (!opened) return KZG_E_ARG;
+    }
+    if (!any) return KZG_E_ARG;
+    if (!fr_from_be32(u, u_be32)) return KZG_E_SCALAR;
+    for (uint32_t p = 0; p < m; p++)
+        if (memcmp(u, alpha[p], sizeof(u)) == 0) return KZG_E_ARG;
+    try {
+        std::vector<u64> y(4 * (size_t)std::max<uint32_t>(npairs, 1));
+        for (uint32_t t = 0; t < npairs; t++)
+            if (!fr_from_be32(&y[4 * (size_t)t], evals32 + 32 * (size_t)t)) return KZG_E_SCALAR;
+        // 1 / (alpha_p - alpha_q) for p != q: prefix products, one inversion, back down
+        u64 dinv[M][M][4], ud[M][4];
+        {
+            u64 d[M * M][4], pre[M * M + 1][4] = {{1, 0, 0, 0}}, inv[4];
+            uint32_t n = 0;
+            for (uint32_t p = 0; p < m; p++)
+                for (uint32_t q = 0; q < m; q++)
+                    if (p != q) {
+                        fr_sub_mod(d[n], alpha[p], alpha[q]);
+                        fr_mul_mod(pre[n + 1], pre[n], d[n]);
+                        n++;
+                    }
+            fr_inv_mod(inv, pre[n]);
+            for (uint32_t p = m; p-- > 0;)
+                for (uint32_t q = m; q-- > 0;)
+                    if (p != q) {
+                        n--;
+                        fr_mul_mod(dinv[p][q], inv, pre[n]);
+                        fr_mul_mod(inv, inv, d[n]);
+                    }
+        }
+        for (uint32_t p = 0; p < m; p++) fr_sub_mod(ud[p], u, alpha[p]);
+        u64 v[4] = {0, 0, 0, 0}, zp[4] = {1, 0, 0, 0};
+        for (uint32_t p = 0; p < m; p++) fr_mul_mod(zp, zp, ud[p]);
+        uint8_t lam[(K + 1) * 32], comm[(K + 1) * 48], v_be[32];
+        for (uint32_t j = 0; j < k; j++) {
+            u64 lj[4] = {c[j][0], c[j][1], c[j][2], c[j][3]};
+            if (lj[0] | lj[1] | lj[2] | lj[3]) {
+                u64 rj[4] = {0, 0, 0, 0};
+                for (uint32_t p = 0; p < m; p++) {
+                    if ((masks[p] >> j) & 1u) {          // y_{j,p} prod_{q in S_j, q != p} (u - alpha_q) / (alpha_p - alpha_q)
+                        const uint32_t t = first[p] + (uint32_t)__builtin_popcount(masks[p] & ((1u << j) - 1));
+                        u64 term[4];
+                        memcpy(term, &y[4 * (size_t)t], sizeof(term));
+                        for (uint32_t q = 0; q < m; q++)
+                            if (q != p && ((masks[q] >> j) & 1u)) {
+                                fr_mul_mod(term, term, ud[q]);
+                                fr_mul_mod(term, term, dinv[p][q]);
+                            }
+                        fr_add_mod(rj, term);
+                    } else {
+                        fr_mul_mod(lj, lj, ud[p]);       // lambda_j = c_j Z_{P \ S_j}(u)
+                    }
+                }
+                fr_mul_mod(rj, rj, lj);
+                fr_add_mod(v, rj);
+            }
+            fr_to_be32(lam + 32 * (size_t)j, lj);
+        }
+        {
+            const u64 zero[4] = {0, 0, 0, 0};
+            u64 neg[4];
+            fr_sub_mod(neg, zero, zp);
+            fr_to_be32(lam + 32 * (size_t)k, neg);
+        }
+        fr_to_be32(v_be, v);
+        memcpy(comm, commitments48, 48 * (size_t)k);
+        memcpy(comm + 48 * (size_t)k, w48, 48);
+        return kzg_vk_verify_open_lincomb(vk, i, k + 1, comm, 1, u_be32, lam, v_be, proof48, out_ok);
+    } catch (...) {
+        return KZG_E_NOMEM;
+    }
+}
+
 /* test hook: out = final_exp(miller(P, Q)) as 12 x 48 bytes in tower order
  * (c0.c0.c0, c0.c0.c1, c0.c1.c0, ..., c1.c2.c1); P affine be96, Q uncompressed be192 */
 int kzg_vk_pairing(const uint8_t p_be96[96], const uint8_t q_be192[192], uint8_t out_fp12[576]) {

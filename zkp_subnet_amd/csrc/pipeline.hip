@@ -719,6 +719,64 @@ int rows_lincomb_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, ui
     }
     return multi_msms_finish(ctx, H, i, T, nullptr, 0, m, m, nullptr, out_values32, out_p48);
 }
+// The first SHPLONK round (kzg_rows_commit_shplonk): a set built FROM sets.  h = sum_S quot(g_S, Z_S) over the groups of rows
+// with one point set S, g_S = sum_{j in group} c_j f_j.  Groups run in batches of at most KZG_MAX_OPEN_POINTS: one launch
+// combines the batch's g_S (k_fr_lincomb_points, "point" read as "group"), then pass d divides every group that still has a
+// d-th point by (X - that point) -- the launches of ONE opening, grid y = group, the quotient kept in Montgomery form -- the
+// vectors going back and forth between the two lane buffers of the caller-weighted opening; one launch adds the batch's final
+// quotients into the new set's buffer `dst`; one MSM commits.  The remainders are never looked at: dividing on by the next
+// point drops them.  Workspace: what rows_lincomb_dev holds at m = KZG_MAX_OPEN_POINTS, whatever the number of groups.
+int rows_shplonk_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t k, uint64_t T, uint32_t m,
+                     const uint8_t* points_be32, const uint8_t* coeffs_be32, uint32_t n_groups, const ShGroup* groups,
+                     uint32_t* dst, uint8_t* out_c48) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    hipStream_t s = A.stream;
+    uint8_t* rec = A.brec.as<uint8_t>();
+    uint32_t* alpha_m = reinterpret_cast<uint32_t*>(rec + MR_SH_ALPHA_M);
+    const uint32_t B = KZG_MAX_OPEN_POINTS;   // groups per batch
+    static_assert(KZG_MAX_OPEN_POINTS <= POLY_MAX_POINTS && KZG_MAX_OPEN_POINTS <= POLY_MAX_ROWS,
+                  "a batch is one launch of the combination, of each division and of the sum");
+    const uint64_t nchunks = (T + 3) / 4, words = T * 8;
+    const uint64_t hrow = (nchunks + (nchunks >> 1) + 64) * 8;   // level scratch of one group's division, words
+    HIPCHK(ctx, A.hbuf.ensure(B * hrow * 4));
+    HIPCHK(ctx, A.hnext.ensure(B * hrow * 4));
+    HIPCHK(ctx, A.bcomb.ensure(B * T * 32));
+    HIPCHK(ctx, A.qbuf.ensure(B * T * 32));
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        for (uint32_t p = 0; p < m; p++) launch_fr_from_host32(s, points_be32 + 32 * (size_t)p, alpha_m + 8 * p, 1, A.flags());
+        for (uint32_t g0 = 0; g0 < n_groups; g0 += B) {
+            const uint32_t G = std::min(B, n_groups - g0);
+            uint8_t lam[KZG_MAX_OPEN_POINTS * KZG_MAX_BATCH_OPEN * 32] = {};   // group-major: c_j on the group's rows
+            uint32_t masks[KZG_MAX_OPEN_POINTS] = {};
+            for (uint32_t g = 0; g < G; g++) {
+                masks[g] = groups[g0 + g].rows;
+                for (uint32_t j = 0; j < k; j++)
+                    if ((masks[g] >> j) & 1u) memcpy(lam + 32 * ((size_t)g * k + j), coeffs_be32 + 32 * (size_t)j, 32);
+            }
+            uint32_t *cur = A.bcomb.as<uint32_t>(), *nxt = A.qbuf.as<uint32_t>();
+            launch_fr_lincomb_points(s, rt, T, G, k, lam, masks, nullptr, cur, nullptr, A.flags());
+            RowTab fin;   // where each group's last quotient lies
+            memset(&fin, 0, sizeof(fin));
+            for (uint32_t d = 0; d < groups[g0].npts; d++) {   // (descending npts: the groups with a d-th point are a prefix)
+                uint32_t nact = 0;
+                uint8_t pts[KZG_MAX_OPEN_POINTS] = {};
+                while (nact < G && groups[g0 + nact].npts > d) {
+                    pts[nact] = groups[g0 + nact].pt[d];
+                    nact++;
+                }
+                launch_poly_open_points(s, cur, T, nact, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), hrow,
+                                        reinterpret_cast<uint32_t*>(rec + MR_HY_M), nxt, nullptr, pts, true);
+                for (uint32_t g = 0; g < nact; g++)
+                    if (groups[g0 + g].npts == d + 1) fin.r[g] = nxt + g * words;
+                std::swap(cur, nxt);
+            }
+            launch_fr_sum_rows(s, fin, G, T, g0 != 0, dst);
+        }
+    }
+    return multi_msms_finish(ctx, H, i, T, dst, 1, 0, 0, out_c48, nullptr, nullptr);
+}
 // The permutation grand product (kzg_rows_commit_grand_product): a set built FROM sets.  Per wire / sigma pair two forward
 // transforms of the sets' coefficient rows into two lane buffers and one launch that folds the pair's factors into the
 // running N and D vectors (four vectors of T whatever k is); the product scans and the one inversion turn N into z's

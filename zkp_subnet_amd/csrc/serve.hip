@@ -838,6 +838,71 @@ int rows_lincomb_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const
     return rows_lincomb_dev(ctx, H, i, rt, k, T, m, points_be32, coeffs_be32, masks, out_values32, out_proofs48);
 }
 
+// kzg_rows_commit_shplonk: the argument checks, the rows' point sets grouped (rows with c_j = 0 left out), the lookups of an
+// open and the reservation of a commit
+static_assert(KZG_MAX_SHPLONK_ROWS + 1 <= KZG_MAX_BATCH_OPEN && KZG_MAX_SHPLONK_POINTS <= 8, "round B opens k + 1 rows; a "
+              "point set is a byte");
+int rows_shplonk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
+                      const uint8_t* points_be32, const uint32_t* masks, const uint8_t* coeffs_be32, uint8_t* out_commitment48,
+                      uint64_t* out_handle) {
+    if (!ctx || !handles || !points_be32 || !masks || !coeffs_be32 || !out_commitment48 || !out_handle) return KZG_E_ARG;
+    if (n_handles == 0 || n_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "shplonk: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (k == 0 || k > KZG_MAX_SHPLONK_ROWS) return fail(ctx, KZG_E_ARG, "shplonk: k must be in [1, KZG_MAX_SHPLONK_ROWS]");
+    if (m == 0 || m > KZG_MAX_SHPLONK_POINTS) return fail(ctx, KZG_E_ARG, "shplonk: m must be in [1, KZG_MAX_SHPLONK_POINTS]");
+    static const uint8_t zero[32] = {};
+    for (uint32_t p = 0; p < m; p++) {
+        if (!fr_be32_canonical(points_be32 + 32 * (size_t)p))
+            return fail(ctx, KZG_E_ARG, "shplonk: points must be canonical scalars (< r)");
+        for (uint32_t q = 0; q < p; q++)
+            if (memcmp(points_be32 + 32 * (size_t)p, points_be32 + 32 * (size_t)q, 32) == 0)
+                return fail(ctx, KZG_E_ARG, "shplonk: the points must be pairwise distinct");
+        if ((masks[p] >> k) != 0) return fail(ctx, KZG_E_ARG, "shplonk: a mask names a row >= k");
+    }
+    ShGroup groups[KZG_MAX_SHPLONK_ROWS];
+    uint32_t n_groups = 0, max_pts = 0;
+    for (uint32_t j = 0; j < k; j++) {
+        const uint8_t* c = coeffs_be32 + 32 * (size_t)j;
+        if (!fr_be32_canonical(c)) return fail(ctx, KZG_E_ARG, "shplonk: coefficients must be canonical scalars (< r)");
+        if (memcmp(c, zero, 32) == 0) continue;   // the row is left out, whatever its mask
+        ShGroup g = {};
+        for (uint32_t p = 0; p < m; p++)
+            if ((masks[p] >> j) & 1u) g.pt[g.npts++] = (uint8_t)p;
+        if (!g.npts) return fail(ctx, KZG_E_ARG, "shplonk: a row with a nonzero coefficient is opened at no point");
+        uint32_t t = 0;
+        while (t < n_groups && !(groups[t].npts == g.npts && memcmp(groups[t].pt, g.pt, g.npts) == 0)) t++;
+        if (t == n_groups) groups[n_groups++] = g;
+        groups[t].rows |= 1u << j;
+        max_pts = std::max<uint32_t>(max_pts, g.npts);
+    }
+    if (!n_groups) return fail(ctx, KZG_E_ARG, "shplonk: every coefficient is zero");
+    std::stable_sort(groups, groups + n_groups, [](const ShGroup& a, const ShGroup& b) { return a.npts > b.npts; });
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs refs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookup: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab rt;
+    uint32_t nrows = 0, i = 0;
+    uint64_t T = 0;
+    if (int rc = rows_lookup(ctx, "shplonk", expect_i, n_handles, handles, refs, rt, &nrows, &i, &T)) return rc;
+    if (nrows != k) return fail(ctx, KZG_E_ARG, "shplonk: k must equal the rows of the concatenated sets");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (max_pts >= T) return fail(ctx, KZG_E_ARG, "shplonk: a row is opened at T or more points (its quotient is zero)");
+    if (int rc2 = rows_reserve(ctx, "shplonk", pend, (size_t)T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    uint8_t c48[48];
+    rc = rows_shplonk_dev(ctx, H, i, rt, k, T, m, points_be32, coeffs_be32, n_groups, groups, pend.buf.as<uint32_t>(), c48);
+    if (rc) return rc;
+    memcpy(out_commitment48, c48, 48);
+    *out_handle = rows_insert(ctx, pend, i, 1, T);
+    return KZG_OK;
+}
+
 // the blinding rows of a _zk builder against the row length, once that is known: 1 <= usable <= T - 1, at most
 // KZG_MAX_BLIND_ROWS rows from `usable` on, T - usable - 1 canonical tail scalars (none: the pointer may be null)
 static_assert(KZG_MAX_BLIND_ROWS == BLIND_MAX_ROWS, "the header's cap is the kernels' cap");
@@ -1580,6 +1645,12 @@ int kzg_rows_eval(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uin
 int kzg_rows_open_lincomb(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
                           const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32, uint8_t* out_proofs48) {
     return rows_lincomb_impl(ctx, UINT32_MAX, n_handles, handles, k, m, points_be32, coeffs_be32, out_values32, out_proofs48);
+}
+int kzg_rows_commit_shplonk(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
+                            const uint8_t* points_be32, const uint32_t* masks, const uint8_t* coeffs_be32,
+                            uint8_t out_commitment48[48], uint64_t* out_handle) {
+    return rows_shplonk_impl(ctx, UINT32_MAX, n_handles, handles, k, m, points_be32, masks, coeffs_be32, out_commitment48,
+                             out_handle);
 }
 int kzg_rows_commit_grand_product(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t* wire_handles, uint32_t n_sigma_handles,
                                   const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,

@@ -11,6 +11,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 from . import _native
 from ._native import KzgError
+from .verifier import shplonk_finish_coeffs
 
 R_MODULUS = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 
@@ -369,6 +370,46 @@ class HipEngine:
         self._chk(self._lib.kzg_rows_open_lincomb(self._h, n, hs, k, m, b"".join(points_be32),
                                                   b"".join(c for cs in coeffs for c in cs), vals, pf))
         return [vals.raw[32 * p:32 * p + 32] for p in range(m)], [pf.raw[48 * p:48 * p + 48] for p in range(m)]
+
+    # ---- SHPLONK: one proof pair for any number of points.  Round A commits h on the device as a new one-row set; round B is
+    # host arithmetic (shplonk_finish_coeffs) and open_rows_lincomb over the rows followed by h at the single point u
+    def commit_shplonk(self, sets: Sequence[object], points_be32: Sequence[bytes], opened: Sequence[Sequence[int]],
+                       coeffs_be32: Sequence[bytes]) -> Tuple[bytes, "RowSet"]:
+        """Round A (kzg_rows_commit_shplonk): h = sum_j c_j (f_j - r_j) / Z_{S_j} over the k concatenated rows of committed
+        sets, opened[p] the rows opened at point p (as in eval_rows; up to 8 distinct points), coeffs_be32 the k row scalars
+        c_j (zero leaves a row out).  Returns (W = [h], a one-row RowSet holding h).  The c_j must be drawn after the
+        commitments and the evaluations of eval_rows are fixed."""
+        n, hs = self._handle_array(sets, "commit_shplonk")
+        k, m = len(coeffs_be32), len(points_be32)
+        if k == 0 or k > _native.KZG_MAX_SHPLONK_ROWS:
+            raise KzgError(_native.KZG_E_ARG, f"commit_shplonk: k = {k} outside [1, {_native.KZG_MAX_SHPLONK_ROWS}]")
+        masks, _ = _native.shplonk_masks(opened, k)
+        if len(opened) != m or any(len(x) != 32 for x in list(points_be32) + list(coeffs_be32)):
+            raise KzgError(_native.KZG_E_ARG, "commit_shplonk: one 32-byte point per opened list and k 32-byte coefficients")
+        c, h = ctypes.create_string_buffer(48), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_shplonk(self._h, n, hs, k, m, b"".join(points_be32), masks, b"".join(coeffs_be32),
+                                                    c, ctypes.byref(h)))
+        src = next((x for x in sets if hasattr(x, "T")), None)
+        return c.raw, RowSet(self, h.value, getattr(src, "i", None), 1, getattr(src, "T", None), [c.raw])
+
+    def open_shplonk_finish(self, sets: Sequence[object], h_set: object, points_be32: Sequence[bytes],
+                            opened: Sequence[Sequence[int]], coeffs_be32: Sequence[bytes], u_be32: bytes) -> Tuple[bytes, bytes]:
+        """Round B: (v, pi) of the opening of sum_j lambda_j f_j + lambda_k h at u, lambda from shplonk_finish_coeffs.  u must
+        be drawn after W and must not be one of the points.  The proof is (W, pi)."""
+        try:
+            lam = shplonk_finish_coeffs(points_be32, opened, coeffs_be32, u_be32)
+        except ValueError as e:
+            raise KzgError(_native.KZG_E_ARG, f"open_shplonk_finish: {e}") from e
+        vals, pfs = self.open_rows_lincomb(list(sets) + [h_set], [u_be32], [lam])
+        return vals[0], pfs[0]
+
+    def verify_open_shplonk(self, i: int, commitments48: Sequence[bytes], points32: Sequence[bytes],
+                            opened: Sequence[Sequence[int]], coeffs32: Sequence[bytes], evals32: Sequence[Sequence[bytes]],
+                            w48: bytes, u32: bytes, proof48: bytes) -> bool:
+        """Pairing check of one SHPLONK opening (commit_shplonk + open_shplonk_finish) against resident slice i."""
+        if self.verifier is None:
+            raise NotImplementedError("no verifier key: call set_verifier_key() after load_srs()")
+        return self.verifier.verify_open_shplonk(i, commitments48, points32, opened, coeffs32, evals32, w48, u32, proof48)
 
     # ---- a set built from sets: the permutation grand product (PLONK round 2), computed and committed on the device
     def commit_grand_product(self, wire_sets: Sequence[object], sigma_sets: Sequence[object], shifts_be32: Sequence[bytes],

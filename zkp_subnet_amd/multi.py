@@ -138,6 +138,27 @@ class MultiDeviceClient:
             return Response(400, {"error": "worker_open_rows_lincomb: the handles must name live sets of one worker"})
         return self._for(i).worker_open_rows_lincomb(handles, points, coeffs)
 
+    def worker_commit_shplonk(self, handles: Sequence[int], points, opened, coeffs):
+        try:
+            i = self._owner(handles)
+        except TypeError:
+            i = None
+        if i is None:
+            return Response(400, {"error": "worker_commit_shplonk: the handles must name live sets of one worker"})
+        r = self._for(i).worker_commit_shplonk(handles, points, opened, coeffs)
+        if r.status_code == 200:
+            self._row_owner[int(r.json()["handle"])] = i
+        return r
+
+    def worker_open_shplonk_finish(self, handles: Sequence[int], h_handle: int, points, opened, coeffs, u):
+        try:
+            i = self._owner(list(handles) + [h_handle])
+        except TypeError:
+            i = None
+        if i is None:
+            return Response(400, {"error": "worker_open_shplonk_finish: the handles must name live sets of one worker"})
+        return self._for(i).worker_open_shplonk_finish(handles, h_handle, points, opened, coeffs, u)
+
     def worker_commit_grand_product(self, wire_handles: Sequence[int], sigma_handles: Sequence[int], shifts, beta, gamma):
         try:
             i = self._owner(list(wire_handles) + list(sigma_handles))
@@ -316,6 +337,9 @@ class MultiDeviceClient:
 
     def worker_verify_open_multi(self, i: int, proofs, points, opened, gammas, evals, commitments):
         return self._for(i).worker_verify_open_multi(i, proofs, points, opened, gammas, evals, commitments)
+
+    def worker_verify_open_shplonk(self, i: int, w, proof, u, points, opened, coeffs, evals, commitments):
+        return self._for(i).worker_verify_open_shplonk(i, w, proof, u, points, opened, coeffs, evals, commitments)
 
     def worker_verify_open_lincomb(self, i: int, proofs, points, coeffs, values, commitments):
         return self._for(i).worker_verify_open_lincomb(i, proofs, points, coeffs, values, commitments)

@@ -9,6 +9,37 @@ from . import _native
 from ._native import KzgError
 
 
+R_MODULUS = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+
+
+def shplonk_finish_coeffs(points32: Sequence[bytes], opened: Sequence[Sequence[int]], coeffs32: Sequence[bytes],
+                          u32: bytes) -> list:
+    """The k + 1 scalars of SHPLONK's round B: lambda_j = c_j Z_{P \\ S_j}(u) for the k rows (S_j: the points p with j in
+    opened[p]) and lambda_k = -Z_P(u) for h, the set kzg_rows_commit_shplonk made.  open_rows_lincomb over (rows, h) at the
+    one point u with these proves the opening.  Pure host arithmetic; ValueError for u among the points, unequal lengths or a
+    scalar that is not 32 canonical bytes."""
+    if len(points32) != len(opened) or any(len(x) != 32 for x in list(points32) + list(coeffs32) + [u32]):
+        raise ValueError("shplonk_finish_coeffs: one row list per point; points, coefficients and u of 32 bytes each")
+    a = [int.from_bytes(x, "big") for x in points32]
+    c = [int.from_bytes(x, "big") for x in coeffs32]
+    u = int.from_bytes(u32, "big")
+    if any(x >= R_MODULUS for x in a + c + [u]):
+        raise ValueError("shplonk_finish_coeffs: scalars must be canonical (< r)")
+    if u in a:
+        raise ValueError("shplonk_finish_coeffs: u must not be one of the points")
+    lam = []
+    for j, cj in enumerate(c):
+        for p, ap in enumerate(a):
+            if j not in opened[p]:
+                cj = cj * (u - ap) % R_MODULUS
+        lam.append(cj)
+    zp = 1
+    for ap in a:
+        zp = zp * (u - ap) % R_MODULUS
+    lam.append(-zp % R_MODULUS)
+    return [x.to_bytes(32, "big") for x in lam]
+
+
 class Verifier:
     def __init__(self, handle):
         self._lib = _native.load()
@@ -135,6 +166,33 @@ class Verifier:
                                                   b"".join(flat), b"".join(values32), b"".join(proofs48), ctypes.byref(ok))
         if rc != 0:
             raise KzgError(rc, "kzg_vk_verify_open_lincomb: bad argument (k, m, all-zero point, index or non-canonical scalar)")
+        return bool(ok.value)
+
+    def verify_open_shplonk(self, i: int, commitments48: Sequence[bytes], points32: Sequence[bytes],
+                            opened: Sequence[Sequence[int]], coeffs32: Sequence[bytes], evals32: Sequence[Sequence[bytes]],
+                            w48: bytes, u32: bytes, proof48: bytes) -> bool:
+        """One SHPLONK opening of k rows of slice i (kzg_vk_verify_open_shplonk): opened[p] lists the rows opened at
+        points32[p] (increasing), evals32[p] their evaluations there (eval_rows' shape), coeffs32 the k row scalars c_j,
+        (w48, proof48) the proof pair and u32 the point of round B.  Two pairings whatever the number of points."""
+        k, m = len(commitments48), len(points32)
+        if not (m == len(opened) == len(evals32)) or len(coeffs32) != k:
+            raise ValueError("verify_open_shplonk: one row list and evaluation list per point, one coefficient per commitment")
+        if any(len(e) != len(r) for e, r in zip(evals32, opened)):
+            raise ValueError("verify_open_shplonk: one evaluation per opened row")
+        if k == 0 or k > _native.KZG_MAX_SHPLONK_ROWS:
+            raise KzgError(_native.KZG_E_ARG, f"kzg_vk_verify_open_shplonk: k = {k} outside [1, {_native.KZG_MAX_SHPLONK_ROWS}]")
+        masks, _ = _native.shplonk_masks(opened, k)
+        flat = [e for ev in evals32 for e in ev]
+        if any(len(x) != 32 for x in list(points32) + list(coeffs32) + flat + [u32]):
+            raise KzgError(_native.KZG_E_ARG, "kzg_vk_verify_open_shplonk: points / coefficients / evals / u must be 32 bytes")
+        if any(len(c) != 48 for c in list(commitments48) + [w48, proof48]):
+            return False
+        ok = ctypes.c_int(0)
+        rc = self._lib.kzg_vk_verify_open_shplonk(self._h, i, k, b"".join(commitments48), m, b"".join(points32), masks,
+                                                  b"".join(coeffs32), b"".join(flat), w48, u32, proof48, ctypes.byref(ok))
+        if rc != 0:
+            raise KzgError(rc, "kzg_vk_verify_open_shplonk: bad argument (k, m, equal points, u among the points, a mask, a "
+                               "nonzero coefficient on an unopened row, index or non-canonical scalar)")
         return bool(ok.value)
 
     def close(self) -> None:
