@@ -18,7 +18,7 @@ SOURCES = ["msm_sort.hip", "msm_accumulate.hip", "msm_tree.hip", "g1_kernels.hip
            "pairing_host.cpp", "finish_host.cpp", "rccl_dl.cpp", "multi_host.cpp", "wire_host.cpp"]
 # dev-only prototypes (scripts/proto/), linked only when KZG_WITH_PROTO=1: never part of the shipped library
 PROTO_SOURCES = ["../../scripts/proto/baff_proto.hip"]
-HEADERS = ["bigint.hip.h", "field.hip.h", "fp28.hip.h", "fr29.hip.h", "g1.hip.h", "msm.hip.h", "msm_dev.hip.h", "fr_kernels.hip.h", "fr_inv.hip.h", "fp_lp.hip.h", "fp_host.h", "rccl_dl.h", "lanebook.h", "ctx.hip.h",
+HEADERS = ["bigint.hip.h", "field.hip.h", "fp28.hip.h", "fr29.hip.h", "g1.hip.h", "msm.hip.h", "msm_dev.hip.h", "fr_kernels.hip.h", "fr_inv.hip.h", "fp_lp.hip.h", "fp_host.h", "rccl_dl.h", "lanebook.h", "ctx.hip.h", "rows_impl.h",
            "../../include/kzg_mi355x.h", "../../include/kzg_mi355x_test.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
 

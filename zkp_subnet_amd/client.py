@@ -362,15 +362,58 @@ class Client:
         permutation rows sigma_j from sigma_handles, one shift per row), computed and committed on the device as a new
         one-row set.  Returns its handle, its commitment and the closing value (1 when the permutation holds).  beta and
         gamma must be drawn after the wire commitments are fixed."""
+        hw, hs, sh, ch = self._grand_product_args("worker_commit_grand_product", wire_handles, sigma_handles, shifts,
+                                                  (beta, gamma), "beta and gamma")
+        return self._with_closing(*self.engine.commit_grand_product(hw, hs, sh, *ch))
+
+    # ---- one parser per builder behind its plain, _zk, _sel and _chain forms: `what` is the public method's name
+    @staticmethod
+    def _grand_product_args(what: str, wire_handles, sigma_handles, shifts, challenges, names: str) -> tuple:
+        """(wire handles, sigma handles, the shifts' bytes, the challenges' bytes); `names` words the challenges"""
         hw, hs = _handles(wire_handles), _handles(sigma_handles)
         if not 1 <= len(shifts) <= KZG_MAX_BATCH_OPEN:
-            raise codec.CodecError(f"worker_commit_grand_product: {len(shifts)} shifts, expected 1 .. {KZG_MAX_BATCH_OPEN}")
-        sc = [codec.fr_to_be32(x) for x in list(shifts) + [beta, gamma]]
+            raise codec.CodecError(f"{what}: {len(shifts)} shifts, expected 1 .. {KZG_MAX_BATCH_OPEN}")
+        sc = [codec.fr_to_be32(x) for x in list(shifts) + list(challenges)]
         if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in sc):
-            raise codec.CodecError("worker_commit_grand_product: shifts, beta and gamma must be canonical scalars (< r)")
-        rs, closing = self.engine.commit_grand_product(hw, hs, sc[:-2], sc[-2], sc[-1])
+            raise codec.CodecError(f"{what}: shifts, {names} must be canonical scalars (< r)")
+        return hw, hs, sc[:len(shifts)], sc[len(shifts):]
+
+    @staticmethod
+    def _lookup_shape(what: str, n_lookups, width) -> tuple:
+        try:
+            n_lookups, width = int(n_lookups), int(width)
+        except (TypeError, ValueError) as e:
+            raise codec.CodecError(f"{what}: n_lookups and width must be integers: {e!r}") from e
+        if n_lookups < 1 or width < 1 or n_lookups * width > KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"{what}: n_lookups = {n_lookups}, width = {width}, expected both >= 1 "
+                                   f"and n_lookups * width <= {KZG_MAX_BATCH_OPEN}")
+        return n_lookups, width
+
+    def _lookup_sum_args(self, what: str, input_handles, table_handles, mult_handle, n_lookups, width, theta, beta,
+                         sel=None) -> tuple:
+        """The engine's arguments up to beta; sel = (sel_handles, sel_index) puts the selectors behind the handles (_sel)"""
+        hi, ht, hm = _handles(input_handles), _handles(table_handles), _handles([mult_handle])[0]
+        n_lookups, width = self._lookup_shape(what, n_lookups, width)
+        sel = self._selectors(what, *sel, n_lookups) if sel else ()
+        sc = [codec.fr_to_be32(x) for x in (theta, beta)]
+        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in sc):
+            raise codec.CodecError(f"{what}: theta and beta must be canonical scalars (< r)")
+        return (hi, ht, hm, *sel, n_lookups, width, sc[0], sc[1])
+
+    def _multiplicities_args(self, what: str, input_handles, table_handles, n_lookups, width, sel=None) -> tuple:
+        """The engine's arguments up to width; sel as for _lookup_sum_args"""
+        hi, ht = _handles(input_handles), _handles(table_handles)
+        n_lookups, width = self._lookup_shape(what, n_lookups, width)
+        return (hi, ht, *(self._selectors(what, *sel, n_lookups) if sel else ()), n_lookups, width)
+
+    @staticmethod
+    def _with_closing(rs, closing) -> dict:
         return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]),
                 "closing": codec.be32_to_fr(closing)}
+
+    @staticmethod
+    def _with_missing(rs, missing) -> dict:
+        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]), "missing": int(missing)}
 
     @_guard
     def worker_commit_lookup_sum(self, input_handles: Sequence[int], table_handles: Sequence[int], mult_handle: int,
@@ -380,20 +423,9 @@ class Client:
         the one-row set mult_handle), computed and committed on the device as a new one-row set.  Returns its handle, its
         commitment and the closing value (0 when the sum closes).  theta and beta must be drawn after the commitments of
         the inputs, the table and the multiplicities are fixed."""
-        hi, ht, hm = _handles(input_handles), _handles(table_handles), _handles([mult_handle])[0]
-        try:
-            n_lookups, width = int(n_lookups), int(width)
-        except (TypeError, ValueError) as e:
-            raise codec.CodecError(f"worker_commit_lookup_sum: n_lookups and width must be integers: {e!r}") from e
-        if n_lookups < 1 or width < 1 or n_lookups * width > KZG_MAX_BATCH_OPEN:
-            raise codec.CodecError(f"worker_commit_lookup_sum: n_lookups = {n_lookups}, width = {width}, expected both >= 1 "
-                                   f"and n_lookups * width <= {KZG_MAX_BATCH_OPEN}")
-        sc = [codec.fr_to_be32(x) for x in (theta, beta)]
-        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in sc):
-            raise codec.CodecError("worker_commit_lookup_sum: theta and beta must be canonical scalars (< r)")
-        rs, closing = self.engine.commit_lookup_sum(hi, ht, hm, n_lookups, width, sc[0], sc[1])
-        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]),
-                "closing": codec.be32_to_fr(closing)}
+        args = self._lookup_sum_args("worker_commit_lookup_sum", input_handles, table_handles, mult_handle, n_lookups, width,
+                                     theta, beta)
+        return self._with_closing(*self.engine.commit_lookup_sum(*args))
 
     @_guard
     def worker_commit_multiplicities(self, input_handles: Sequence[int], table_handles: Sequence[int], n_lookups: int,
@@ -403,16 +435,8 @@ class Client:
         as a new one-row set.  Returns its handle, its commitment and `missing`, the number of looked-up cells whose tuple is
         no row of the table (0 when every lookup is satisfied).  The handle goes straight into worker_commit_lookup_sum as
         mult_handle; theta and beta are drawn after this commitment."""
-        hi, ht = _handles(input_handles), _handles(table_handles)
-        try:
-            n_lookups, width = int(n_lookups), int(width)
-        except (TypeError, ValueError) as e:
-            raise codec.CodecError(f"worker_commit_multiplicities: n_lookups and width must be integers: {e!r}") from e
-        if n_lookups < 1 or width < 1 or n_lookups * width > KZG_MAX_BATCH_OPEN:
-            raise codec.CodecError(f"worker_commit_multiplicities: n_lookups = {n_lookups}, width = {width}, expected both "
-                                   f">= 1 and n_lookups * width <= {KZG_MAX_BATCH_OPEN}")
-        rs, missing = self.engine.commit_multiplicities(hi, ht, n_lookups, width)
-        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]), "missing": int(missing)}
+        args = self._multiplicities_args("worker_commit_multiplicities", input_handles, table_handles, n_lookups, width)
+        return self._with_missing(*self.engine.commit_multiplicities(*args))
 
     @_guard
     def worker_commit_quotient(self, handles: Sequence[int], terms, perm=None, ext_log: int = 2, n_pieces: int = 3):
@@ -492,54 +516,29 @@ class Client:
         """Extension: worker_commit_grand_product over the first `usable` rows only: z(w^usable) is the closing value (1 when
         the permutation holds on the usable rows) and z's rows behind it are `tail`.  Rows >= usable of the wires and sigmas
         do not enter the product.  The library draws no randomness: the tail must be fresh per proof."""
-        hw, hs = _handles(wire_handles), _handles(sigma_handles)
-        if not 1 <= len(shifts) <= KZG_MAX_BATCH_OPEN:
-            raise codec.CodecError(f"worker_commit_grand_product_zk: {len(shifts)} shifts, expected 1 .. {KZG_MAX_BATCH_OPEN}")
-        sc = [codec.fr_to_be32(x) for x in list(shifts) + [beta, gamma]]
-        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in sc):
-            raise codec.CodecError("worker_commit_grand_product_zk: shifts, beta and gamma must be canonical scalars (< r)")
+        hw, hs, sh, ch = self._grand_product_args("worker_commit_grand_product_zk", wire_handles, sigma_handles, shifts,
+                                                  (beta, gamma), "beta and gamma")
         usable, tb = self._blind("worker_commit_grand_product_zk", usable, tail)
-        rs, closing = self.engine.commit_grand_product_zk(hw, hs, sc[:-2], sc[-2], sc[-1], usable, tb)
-        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]),
-                "closing": codec.be32_to_fr(closing)}
+        return self._with_closing(*self.engine.commit_grand_product_zk(hw, hs, sh, *ch, usable, tb))
 
     @_guard
     def worker_commit_lookup_sum_zk(self, input_handles: Sequence[int], table_handles: Sequence[int], mult_handle: int,
                                     n_lookups: int, width: int, theta: str, beta: str, usable: int, tail: Sequence[str]):
         """Extension: worker_commit_lookup_sum over the first `usable` rows only: S(w^usable) is the closing value (0 when
         the sum closes on the usable rows) and S's rows behind it are `tail`."""
-        hi, ht, hm = _handles(input_handles), _handles(table_handles), _handles([mult_handle])[0]
-        try:
-            n_lookups, width = int(n_lookups), int(width)
-        except (TypeError, ValueError) as e:
-            raise codec.CodecError(f"worker_commit_lookup_sum_zk: n_lookups and width must be integers: {e!r}") from e
-        if n_lookups < 1 or width < 1 or n_lookups * width > KZG_MAX_BATCH_OPEN:
-            raise codec.CodecError(f"worker_commit_lookup_sum_zk: n_lookups = {n_lookups}, width = {width}, expected both >= 1 "
-                                   f"and n_lookups * width <= {KZG_MAX_BATCH_OPEN}")
-        sc = [codec.fr_to_be32(x) for x in (theta, beta)]
-        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in sc):
-            raise codec.CodecError("worker_commit_lookup_sum_zk: theta and beta must be canonical scalars (< r)")
+        args = self._lookup_sum_args("worker_commit_lookup_sum_zk", input_handles, table_handles, mult_handle, n_lookups, width,
+                                     theta, beta)
         usable, tb = self._blind("worker_commit_lookup_sum_zk", usable, tail)
-        rs, closing = self.engine.commit_lookup_sum_zk(hi, ht, hm, n_lookups, width, sc[0], sc[1], usable, tb)
-        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]),
-                "closing": codec.be32_to_fr(closing)}
+        return self._with_closing(*self.engine.commit_lookup_sum_zk(*args, usable, tb))
 
     @_guard
     def worker_commit_multiplicities_zk(self, input_handles: Sequence[int], table_handles: Sequence[int], n_lookups: int,
                                         width: int, usable: int, tail: Sequence[str]):
         """Extension: worker_commit_multiplicities over the first `usable` table rows and input cells only (`missing` counts
         those cells alone): m(w^usable) = 0 and m's rows behind it are `tail`."""
-        hi, ht = _handles(input_handles), _handles(table_handles)
-        try:
-            n_lookups, width = int(n_lookups), int(width)
-        except (TypeError, ValueError) as e:
-            raise codec.CodecError(f"worker_commit_multiplicities_zk: n_lookups and width must be integers: {e!r}") from e
-        if n_lookups < 1 or width < 1 or n_lookups * width > KZG_MAX_BATCH_OPEN:
-            raise codec.CodecError(f"worker_commit_multiplicities_zk: n_lookups = {n_lookups}, width = {width}, expected both "
-                                   f">= 1 and n_lookups * width <= {KZG_MAX_BATCH_OPEN}")
+        args = self._multiplicities_args("worker_commit_multiplicities_zk", input_handles, table_handles, n_lookups, width)
         usable, tb = self._blind("worker_commit_multiplicities_zk", usable, tail)
-        rs, missing = self.engine.commit_multiplicities_zk(hi, ht, n_lookups, width, usable, tb)
-        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]), "missing": int(missing)}
+        return self._with_missing(*self.engine.commit_multiplicities_zk(*args, usable, tb))
 
     # ---- the two lookup builders with per-row selectors (kzg_rows_commit_*_sel)
     @staticmethod
@@ -564,24 +563,10 @@ class Client:
         """Extension: worker_commit_lookup_sum (usable = None) or worker_commit_lookup_sum_zk with per-row selectors: the
         fraction of lookup l has the numerator q_l, row sel_index[l] of the concatenated rows of the sel_handles sets (null: the
         constant 1).  The sum closes against worker_commit_multiplicities_sel's m when q_l is 0 or 1 on the rows that count."""
-        hi, ht, hm = _handles(input_handles), _handles(table_handles), _handles([mult_handle])[0]
-        try:
-            n_lookups, width = int(n_lookups), int(width)
-        except (TypeError, ValueError) as e:
-            raise codec.CodecError(f"worker_commit_lookup_sum_sel: n_lookups and width must be integers: {e!r}") from e
-        if n_lookups < 1 or width < 1 or n_lookups * width > KZG_MAX_BATCH_OPEN:
-            raise codec.CodecError(f"worker_commit_lookup_sum_sel: n_lookups = {n_lookups}, width = {width}, expected both >= 1 "
-                                   f"and n_lookups * width <= {KZG_MAX_BATCH_OPEN}")
-        hs, idx = self._selectors("worker_commit_lookup_sum_sel", sel_handles, sel_index, n_lookups)
-        sc = [codec.fr_to_be32(x) for x in (theta, beta)]
-        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in sc):
-            raise codec.CodecError("worker_commit_lookup_sum_sel: theta and beta must be canonical scalars (< r)")
-        tb = []
-        if usable is not None:
-            usable, tb = self._blind("worker_commit_lookup_sum_sel", usable, tail)
-        rs, closing = self.engine.commit_lookup_sum_sel(hi, ht, hm, hs, idx, n_lookups, width, sc[0], sc[1], usable, tb)
-        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]),
-                "closing": codec.be32_to_fr(closing)}
+        args = self._lookup_sum_args("worker_commit_lookup_sum_sel", input_handles, table_handles, mult_handle, n_lookups, width,
+                                     theta, beta, (sel_handles, sel_index))
+        usable, tb = (None, []) if usable is None else self._blind("worker_commit_lookup_sum_sel", usable, tail)
+        return self._with_closing(*self.engine.commit_lookup_sum_sel(*args, usable, tb))
 
     @_guard
     def worker_commit_multiplicities_sel(self, input_handles: Sequence[int], table_handles: Sequence[int],
@@ -590,20 +575,10 @@ class Client:
         """Extension: worker_commit_multiplicities (usable = None) or worker_commit_multiplicities_zk with per-row selectors:
         cell (l, t) is probed, and can be `missing`, only where row sel_index[l] of the concatenated rows of the sel_handles
         sets is not zero at t (null: every cell).  A disabled cell may hold anything."""
-        hi, ht = _handles(input_handles), _handles(table_handles)
-        try:
-            n_lookups, width = int(n_lookups), int(width)
-        except (TypeError, ValueError) as e:
-            raise codec.CodecError(f"worker_commit_multiplicities_sel: n_lookups and width must be integers: {e!r}") from e
-        if n_lookups < 1 or width < 1 or n_lookups * width > KZG_MAX_BATCH_OPEN:
-            raise codec.CodecError(f"worker_commit_multiplicities_sel: n_lookups = {n_lookups}, width = {width}, expected both "
-                                   f">= 1 and n_lookups * width <= {KZG_MAX_BATCH_OPEN}")
-        hs, idx = self._selectors("worker_commit_multiplicities_sel", sel_handles, sel_index, n_lookups)
-        tb = []
-        if usable is not None:
-            usable, tb = self._blind("worker_commit_multiplicities_sel", usable, tail)
-        rs, missing = self.engine.commit_multiplicities_sel(hi, ht, hs, idx, n_lookups, width, usable, tb)
-        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]), "missing": int(missing)}
+        args = self._multiplicities_args("worker_commit_multiplicities_sel", input_handles, table_handles, n_lookups, width,
+                                         (sel_handles, sel_index))
+        usable, tb = (None, []) if usable is None else self._blind("worker_commit_multiplicities_sel", usable, tail)
+        return self._with_missing(*self.engine.commit_multiplicities_sel(*args, usable, tb))
 
     @_guard
     def worker_commit_quotient_zk(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None,
@@ -758,19 +733,12 @@ class Client:
         """Extension: worker_commit_grand_product_zk whose z starts at `start` instead of 1: one chunk of a chained
         permutation.  The closing value z(w^usable) = start * prod N / prod D is the next chunk's start (1 after the last
         chunk when the permutation holds); the tail is untouched by start.  start must be canonical and not 0."""
-        hw, hs = _handles(wire_handles), _handles(sigma_handles)
-        if not 1 <= len(shifts) <= KZG_MAX_BATCH_OPEN:
-            raise codec.CodecError(f"worker_commit_grand_product_chain: {len(shifts)} shifts, expected 1 .. {KZG_MAX_BATCH_OPEN}")
-        sc = [codec.fr_to_be32(x) for x in list(shifts) + [beta, gamma, start]]
-        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in sc):
-            raise codec.CodecError("worker_commit_grand_product_chain: shifts, beta, gamma and start must be canonical scalars "
-                                   "(< r)")
-        if int.from_bytes(sc[-1], "big") == 0:
+        hw, hs, sh, ch = self._grand_product_args("worker_commit_grand_product_chain", wire_handles, sigma_handles, shifts,
+                                                  (beta, gamma, start), "beta, gamma and start")
+        if int.from_bytes(ch[2], "big") == 0:
             raise codec.CodecError("worker_commit_grand_product_chain: start must not be 0")
         usable, tb = self._blind("worker_commit_grand_product_chain", usable, tail)
-        rs, closing = self.engine.commit_grand_product_chain(hw, hs, sc[:-3], sc[-3], sc[-2], usable, tb, sc[-1])
-        return {"handle": int(rs.handle), "commitment": codec.g1_to_b64(rs.commitments[0]),
-                "closing": codec.be32_to_fr(closing)}
+        return self._with_closing(*self.engine.commit_grand_product_chain(hw, hs, sh, ch[0], ch[1], usable, tb, ch[2]))
 
     @_guard
     def worker_release_rows(self, handle: int):

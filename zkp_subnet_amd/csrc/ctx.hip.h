@@ -38,6 +38,7 @@
 #include "fp_lp.hip.h"
 #include "rccl_dl.h"
 #include "lanebook.h"
+#include "rows_impl.h"
 
 #define KZG_VERSION "kzg_mi355x 0.6 (gfx950)"
 #define N_SLOTS 4
@@ -426,13 +427,6 @@ struct ShGroup {
 int rows_shplonk_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t k, uint64_t T, uint32_t m,
                      const uint8_t* points_be32, const uint8_t* coeffs_be32, uint32_t n_groups, const ShGroup* groups,
                      uint32_t* dst, uint8_t* out_c48);
-// The blinding rows of a kzg_rows_commit_*_zk builder (checked by the caller: 1 <= usable < T, T - usable <=
-// KZG_MAX_BLIND_ROWS, every tail scalar canonical): rows [0, usable) carry the circuit, row `usable` closes the running value
-// and rows usable + 1 .. T - 1 take the T - usable - 1 scalars of tail_be32 (host bytes).  Null: the plain builder.
-struct Blind {
-    uint64_t usable;
-    const uint8_t* tail_be32;
-};
 // The selectors of a kzg_rows_commit_*_sel builder (checked by the caller): the n DISTINCT resident rows the call names
 // (coefficients, like every row of a set) and, per lookup, which of them is its q_l (SEL_NONE: the constant 1, the lookup runs
 // through the kernels of the call without selectors).  Null, or every entry SEL_NONE: the builder without selectors.
@@ -474,85 +468,7 @@ int rows_quotient_finish_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, uint64_t T, 
                              uint32_t* dst, uint8_t* out_c48, bool* out_bad_shape);
 // an SRS (re)load is installing a new table (every lane held): marks every live set stale, frees its buffer and the free list
 void rows_invalidate(kzg_ctx* ctx);
-// kzg_rows_open with the extra condition that every set belongs to worker `expect_i` (UINT32_MAX: any; kzg_multi_rows_open)
-int rows_open_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
-                   const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
-                   uint8_t* out_proofs48);
-int rows_eval_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
-                   const uint8_t* points_be32, const uint32_t* masks, uint8_t* out_evals32);
-int rows_lincomb_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
-                      const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32, uint8_t* out_proofs48);
-int rows_release_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle);
-int rows_shplonk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
-                      const uint8_t* points_be32, const uint32_t* masks, const uint8_t* coeffs_be32, uint8_t* out_commitment48,
-                      uint64_t* out_handle);
-int rows_grand_product_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
-                            uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
-                            const uint8_t* beta_be32, const uint8_t* gamma_be32, uint8_t* out_commitment48,
-                            uint8_t* out_closing32, uint64_t* out_handle);
-// the _zk builders (kzg_rows_commit_*_zk): the plain call's arguments with usable and tail_be32 behind the challenges
-int rows_grand_product_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
-                               uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
-                               const uint8_t* beta_be32, const uint8_t* gamma_be32, uint64_t usable, const uint8_t* tail_be32,
-                               uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle);
-int rows_lookup_sum_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                            uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
-                            uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint64_t usable,
-                            const uint8_t* tail_be32, uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle);
-int rows_multiplicities_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                                uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
-                                uint64_t usable, const uint8_t* tail_be32, uint8_t* out_commitment48, uint64_t* out_missing,
-                                uint64_t* out_handle);
-// the _sel builders (kzg_rows_commit_*_sel): the _zk call's arguments with the selector sets and sel_index behind the table
-int rows_lookup_sum_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                             uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
-                             uint32_t n_sel_handles, const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups,
-                             uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint64_t usable,
-                             const uint8_t* tail_be32, uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle);
-int rows_multiplicities_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                                 uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_sel_handles,
-                                 const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups, uint32_t width,
-                                 uint64_t usable, const uint8_t* tail_be32, uint8_t* out_commitment48, uint64_t* out_missing,
-                                 uint64_t* out_handle);
-int rows_quotient_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
-                           const kzg_quotient_selectors* selectors, const kzg_quotient_active* active, uint32_t ext_log,
-                           uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle);
-int rows_quotient_part_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                                const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
-                                const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
-                                const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32,
-                                uint64_t* inout_acc);
-int rows_quotient_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                          const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
-                          const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,
-                          uint64_t* out_handle);
-int rows_lookup_sum_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                         uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
-                         uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint8_t* out_commitment48,
-                         uint8_t* out_closing32, uint64_t* out_handle);
-int rows_multiplicities_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                             uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
-                             uint8_t* out_commitment48, uint64_t* out_missing, uint64_t* out_handle);
-int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                       const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces,
-                       uint8_t* out_commitments48, uint64_t* out_handle);
-// kzg_rows_quotient_part / kzg_rows_quotient_finish / kzg_rows_commit_grand_product_chain
-int rows_quotient_part_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                            const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
-                            const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
-                            const uint8_t* scale_be32, uint64_t* inout_acc);
-int rows_quotient_finish_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t acc, uint32_t n_pieces, uint8_t* out_commitments48,
-                              uint64_t* out_handle);
-int rows_grand_product_chain_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
-                                  uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
-                                  const uint8_t* beta_be32, const uint8_t* gamma_be32, uint64_t usable, const uint8_t* tail_be32,
-                                  const uint8_t* start_be32, uint8_t* out_commitment48, uint8_t* out_closing32,
-                                  uint64_t* out_handle);
-// kzg_rows_commit_quotient_ext; plain: the call came through kzg_rows_commit_quotient (rotations null, no lookup part)
-int rows_quotient_ext_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
-                           uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle, bool plain);
+// (the entries behind the kzg_rows_* / kzg_multi_rows_* exports, Blind and SelCall: rows_impl.h)
 
 // ---- the collective (comm.hip)
 void comm_teardown(kzg_ctx* ctx);

@@ -20,84 +20,10 @@
 
 #include "../../include/kzg_mi355x.h"
 
-// the one exception to the public C-ABI: an open / release of committed row sets that also checks the sets' worker
-// (serve.hip; the public forms accept sets of any one worker)
-namespace kzg_impl {
-int rows_open_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
-                   const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
-                   uint8_t* out_proofs48);
-int rows_eval_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
-                   const uint8_t* points_be32, const uint32_t* masks, uint8_t* out_evals32);
-int rows_lincomb_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
-                      const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32, uint8_t* out_proofs48);
-int rows_release_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle);
-int rows_shplonk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
-                      const uint8_t* points_be32, const uint32_t* masks, const uint8_t* coeffs_be32, uint8_t* out_commitment48,
-                      uint64_t* out_handle);
-int rows_grand_product_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
-                            uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
-                            const uint8_t* beta_be32, const uint8_t* gamma_be32, uint8_t* out_commitment48,
-                            uint8_t* out_closing32, uint64_t* out_handle);
-int rows_lookup_sum_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                         uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
-                         uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint8_t* out_commitment48,
-                         uint8_t* out_closing32, uint64_t* out_handle);
-int rows_multiplicities_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                             uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
-                             uint8_t* out_commitment48, uint64_t* out_missing, uint64_t* out_handle);
-int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                       const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces,
-                       uint8_t* out_commitments48, uint64_t* out_handle);
-int rows_quotient_ext_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
-                           uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle, bool plain);
-int rows_grand_product_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
-                               uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
-                               const uint8_t* beta_be32, const uint8_t* gamma_be32, uint64_t usable, const uint8_t* tail_be32,
-                               uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle);
-int rows_lookup_sum_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                            uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
-                            uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint64_t usable,
-                            const uint8_t* tail_be32, uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle);
-int rows_multiplicities_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                                uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
-                                uint64_t usable, const uint8_t* tail_be32, uint8_t* out_commitment48, uint64_t* out_missing,
-                                uint64_t* out_handle);
-int rows_lookup_sum_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                             uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
-                             uint32_t n_sel_handles, const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups,
-                             uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint64_t usable,
-                             const uint8_t* tail_be32, uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle);
-int rows_multiplicities_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                                 uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_sel_handles,
-                                 const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups, uint32_t width,
-                                 uint64_t usable, const uint8_t* tail_be32, uint8_t* out_commitment48, uint64_t* out_missing,
-                                 uint64_t* out_handle);
-int rows_quotient_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
-                           const kzg_quotient_selectors* selectors, const kzg_quotient_active* active, uint32_t ext_log,
-                           uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle);
-int rows_quotient_part_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                                const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
-                                const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
-                                const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32,
-                                uint64_t* inout_acc);
-int rows_quotient_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                          const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
-                          const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,
-                          uint64_t* out_handle);
-int rows_quotient_part_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                            const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
-                            const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
-                            const uint8_t* scale_be32, uint64_t* inout_acc);
-int rows_quotient_finish_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t acc, uint32_t n_pieces, uint8_t* out_commitments48,
-                              uint64_t* out_handle);
-int rows_grand_product_chain_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
-                                  uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
-                                  const uint8_t* beta_be32, const uint8_t* gamma_be32, uint64_t usable, const uint8_t* tail_be32,
-                                  const uint8_t* start_be32, uint8_t* out_commitment48, uint8_t* out_closing32,
-                                  uint64_t* out_handle);
-}  // namespace kzg_impl
+// The row-set calls do not go through the public kzg_rows_* exports but through the internal entries behind them (serve.hip),
+// which take one argument more: expect_i, the slice every set named must belong to.  A handle of a set of ANOTHER worker
+// on the same device is refused there; the public forms accept sets of any one worker.
+#include "rows_impl.h"
 
 namespace {
 enum Layout { LAYOUT_NONE = 0, LAYOUT_ROWS_WHOLE, LAYOUT_ROWS_SLICED, LAYOUT_SEGMENTS };
@@ -182,6 +108,14 @@ int relay(kzg_ctx* ctx, int rc) {      // a per-GPU failure becomes this handle'
     if (rc != KZG_OK) tl_multi_err = kzg_last_error(ctx);
     return rc;
 }
+// a call for worker i: routed to its device, run as call(ctx, slice), its failure relayed
+template <class F>
+int routed(kzg_multi* m, uint32_t i, F call) {
+    kzg_ctx* c;
+    uint32_t s;
+    if (int rc = route(m, i, &c, &s)) return rc;
+    return relay(c, call(c, s));
+}
 void forget(kzg_multi* m) {            // a load is about to replace the devices' SRS: nothing is routable until it has succeeded
     m->layout = LAYOUT_NONE;
     m->total_points = 0;
@@ -199,7 +133,7 @@ int ceil_log2(uint64_t n) {
     return l;
 }
 
-int create_impl(int device_count, const int* device_ids, kzg_multi** out) {
+int create_body(int device_count, const int* device_ids, kzg_multi** out) {
     if (!out) return KZG_E_ARG;
     *out = nullptr;
     if (device_count < 1 || device_count > 64 || !device_ids) return mfail(KZG_E_ARG, "1..64 devices");
@@ -231,7 +165,7 @@ int create_impl(int device_count, const int* device_ids, kzg_multi** out) {
     return KZG_OK;
 }
 
-int load_srs_file_impl(kzg_multi* m, const char* path, int compressed, int scale, int machines_scale) {
+int load_srs_file_body(kzg_multi* m, const char* path, int compressed, int scale, int machines_scale) {
     if (!m || !path || machines_scale < 0 || machines_scale > 30) return mfail(KZG_E_ARG, "bad argument");
     const uint32_t G = (uint32_t)m->ctx.size();
     forget(m);
@@ -246,7 +180,7 @@ int load_srs_file_impl(kzg_multi* m, const char* path, int compressed, int scale
     m->machines_scale = machines_scale;
     return KZG_OK;
 }
-int gen_srs_impl(kzg_multi* m, const uint8_t tau_be32[32], const uint8_t* s0_be32_all, int scale, int machines_scale) {
+int gen_srs_body(kzg_multi* m, const uint8_t tau_be32[32], const uint8_t* s0_be32_all, int scale, int machines_scale) {
     if (!m || !tau_be32 || !s0_be32_all || machines_scale < 0 || machines_scale > 20) return mfail(KZG_E_ARG, "bad argument");
     const uint32_t M = 1u << machines_scale, G = (uint32_t)m->ctx.size();
     forget(m);
@@ -268,7 +202,7 @@ void install_segments(kzg_multi* m, uint64_t n_points) {
     m->machines_scale = 0;
     m->layout = LAYOUT_SEGMENTS;
 }
-int load_segments_impl(kzg_multi* m, const char* path, int compressed, uint64_t n_points) {
+int load_segments_body(kzg_multi* m, const char* path, int compressed, uint64_t n_points) {
     if (!m || !path || !n_points) return mfail(KZG_E_ARG, "bad argument");
     const uint64_t G = m->ctx.size();
     if (n_points < G) return mfail(KZG_E_ARG, "fewer points than devices");
@@ -282,7 +216,7 @@ int load_segments_impl(kzg_multi* m, const char* path, int compressed, uint64_t 
     install_segments(m, n_points);
     return KZG_OK;
 }
-int gen_segments_impl(kzg_multi* m, const uint8_t tau_be32[32], const uint8_t* s0_be32_per_device, uint64_t n_points) {
+int gen_segments_body(kzg_multi* m, const uint8_t tau_be32[32], const uint8_t* s0_be32_per_device, uint64_t n_points) {
     if (!m || !tau_be32 || !s0_be32_per_device || !n_points) return mfail(KZG_E_ARG, "bad argument");
     const uint64_t G = m->ctx.size();
     if (n_points < G) return mfail(KZG_E_ARG, "fewer points than devices");
@@ -335,14 +269,14 @@ int msm_over_segments(kzg_multi* m, uint64_t offset, uint64_t n, uint8_t out48[4
     // a group launch over G streams to save one ~10-us copy); the sum runs on device 0's auxiliary stream
     return relay(m->ctx[0], kzg_g1_sum(m->ctx[0], partials.data(), count, out48));
 }
-int msm_impl(kzg_multi* m, const uint8_t* scalars_be32, uint64_t n, uint64_t srs_offset, uint8_t out48[48]) {
+int msm_body(kzg_multi* m, const uint8_t* scalars_be32, uint64_t n, uint64_t srs_offset, uint8_t out48[48]) {
     if (!out48 || (n && !scalars_be32)) return mfail(KZG_E_ARG, "bad argument");
     if (int rc = need_segments(m, srs_offset, n)) return rc;
     return msm_over_segments(m, srs_offset, n, out48, [&](int g, uint64_t lo, uint64_t cnt, uint8_t* out192) {
         return kzg_msm_partial(m->ctx[g], scalars_be32 + 32 * (size_t)(lo - srs_offset), cnt, lo - m->seg_lo[g], out192);
     });
 }
-int upload_impl(kzg_multi* m, int slot, const uint8_t* scalars_be32, uint64_t n, uint64_t srs_offset) {
+int upload_body(kzg_multi* m, int slot, const uint8_t* scalars_be32, uint64_t n, uint64_t srs_offset) {
     if (slot < 0 || slot >= 4 || (n && !scalars_be32)) return mfail(KZG_E_ARG, "bad argument");
     if (int rc = need_segments(m, srs_offset, n)) return rc;
     m->slot[slot].valid = false;
@@ -357,7 +291,7 @@ int upload_impl(kzg_multi* m, int slot, const uint8_t* scalars_be32, uint64_t n,
     m->slot[slot].valid = true;
     return KZG_OK;
 }
-int msm_resident_impl(kzg_multi* m, int slot, uint8_t out48[48]) {
+int msm_resident_body(kzg_multi* m, int slot, uint8_t out48[48]) {
     if (!m || slot < 0 || slot >= 4 || !out48) return mfail(KZG_E_ARG, "bad argument");
     if (!m->slot[slot].valid) return mfail(KZG_E_ARG, "the slot holds no scalars: kzg_multi_upload_fr first");
     const uint64_t offset = m->slot[slot].offset, n = m->slot[slot].n;
@@ -370,7 +304,7 @@ int msm_resident_impl(kzg_multi* m, int slot, uint8_t out48[48]) {
 // The rows of one challenge, all devices at once: row k (worker index indices[k], T x 32 bytes at rows_be32 + k * T * 32) runs
 // on the device of its index, up to four rows per device in flight (a context has four lanes).  out_status[k] is that row's
 // own status: one bad row never costs the others.  Returns KZG_OK when every row succeeded, else the first failing status.
-int commit_open_rows_impl(kzg_multi* m, uint32_t n_rows, const uint32_t* indices, const uint8_t* rows_be32, uint64_t T,
+int commit_open_rows_body(kzg_multi* m, uint32_t n_rows, const uint32_t* indices, const uint8_t* rows_be32, uint64_t T,
                           int evaluation_form, const uint8_t alpha_be32[32], uint8_t* out_c48, uint8_t* out_e32, uint8_t* out_p48,
                           int* out_status) {
     if (!m || (n_rows && (!indices || !rows_be32 || !alpha_be32 || !out_c48 || !out_e32 || !out_p48 || !out_status)))
@@ -422,246 +356,91 @@ kzg_ctx* kzg_multi_ctx(kzg_multi* m, int k) { return (m && k >= 0 && k < (int)m-
 int kzg_multi_device_of(kzg_multi* m, uint32_t i) { return (m && !m->ctx.empty()) ? m->device[i % m->ctx.size()] : -1; }
 
 int kzg_multi_commit(kzg_multi* m, uint32_t i, const uint8_t* row_be32, uint64_t T, int evaluation_form, uint8_t out48[48]) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(m, i, &c, &s)) return rc;
-    return relay(c, kzg_commit(c, s, row_be32, T, evaluation_form, out48));
+    return routed(m, i, [&](kzg_ctx* c, uint32_t s) { return kzg_commit(c, s, row_be32, T, evaluation_form, out48); });
 }
 int kzg_multi_open(kzg_multi* m, uint32_t i, const uint8_t* row_be32, uint64_t T, int evaluation_form, const uint8_t alpha_be32[32],
                    uint8_t out_eval32[32], uint8_t out_proof48[48]) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(m, i, &c, &s)) return rc;
-    return relay(c, kzg_open(c, s, row_be32, T, evaluation_form, alpha_be32, out_eval32, out_proof48));
+    return routed(m, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_open(c, s, row_be32, T, evaluation_form, alpha_be32, out_eval32, out_proof48);
+    });
 }
 int kzg_multi_commit_open(kzg_multi* m, uint32_t i, const uint8_t* row_be32, uint64_t T, int evaluation_form,
                           const uint8_t alpha_be32[32], uint8_t out48[48], uint8_t out_eval32[32], uint8_t out_proof48[48]) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(m, i, &c, &s)) return rc;
-    return relay(c, kzg_commit_open(c, s, row_be32, T, evaluation_form, alpha_be32, out48, out_eval32, out_proof48));
+    return routed(m, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_commit_open(c, s, row_be32, T, evaluation_form, alpha_be32, out48, out_eval32, out_proof48);
+    });
 }
 int kzg_multi_commit_open_batch(kzg_multi* m, uint32_t i, uint32_t k, const uint8_t* rows_be32, uint64_t T, int evaluation_form,
                                 const uint8_t alpha_be32[32], const uint8_t gamma_be32[32], uint8_t* out_commitments48,
                                 uint8_t* out_evals32, uint8_t out_proof48[48]) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(m, i, &c, &s)) return rc;
-    return relay(c, kzg_commit_open_batch(c, s, k, rows_be32, T, evaluation_form, alpha_be32, gamma_be32, out_commitments48,
-                                          out_evals32, out_proof48));
+    return routed(m, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_commit_open_batch(c, s, k, rows_be32, T, evaluation_form, alpha_be32, gamma_be32, out_commitments48, out_evals32,
+                                     out_proof48);
+    });
 }
 int kzg_multi_commit_open_multi(kzg_multi* mh, uint32_t i, uint32_t k, const uint8_t* rows_be32, uint64_t T,
                                 int evaluation_form, uint32_t m, const uint8_t* points_be32, const uint32_t* masks,
                                 const uint8_t* gammas_be32, uint8_t* out_commitments48, uint8_t* out_evals32,
                                 uint8_t* out_proofs48) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_commit_open_multi(c, s, k, rows_be32, T, evaluation_form, m, points_be32, masks, gammas_be32,
-                                          out_commitments48, out_evals32, out_proofs48));
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_commit_open_multi(c, s, k, rows_be32, T, evaluation_form, m, points_be32, masks, gammas_be32, out_commitments48,
+                                     out_evals32, out_proofs48);
+    });
 }
 int kzg_multi_rows_commit(kzg_multi* mh, uint32_t i, uint32_t k, const uint8_t* rows_be32, uint64_t T, int evaluation_form,
                           uint8_t* out_commitments48, uint64_t* out_handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_rows_commit(c, s, k, rows_be32, T, evaluation_form, out_commitments48, out_handle));
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_rows_commit(c, s, k, rows_be32, T, evaluation_form, out_commitments48, out_handle);
+    });
 }
+// from here on every call is the entry its single-context twin (serve.hip) calls, with the slice as expect_i
 int kzg_multi_rows_open(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
                         const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
                         uint8_t* out_proofs48) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_open_impl(c, s, n_handles, handles, m, points_be32, masks, gammas_be32, out_evals32,
-                                             out_proofs48));
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_open(c, s, n_handles, handles, m, points_be32, masks, gammas_be32, out_evals32, out_proofs48);
+    });
 }
 int kzg_multi_rows_eval(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
                         const uint8_t* points_be32, const uint32_t* masks, uint8_t* out_evals32) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_eval_impl(c, s, n_handles, handles, m, points_be32, masks, out_evals32));
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_eval(c, s, n_handles, handles, m, points_be32, masks, out_evals32);
+    });
 }
 int kzg_multi_rows_open_lincomb(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t k,
                                 uint32_t m, const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32,
                                 uint8_t* out_proofs48) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_lincomb_impl(c, s, n_handles, handles, k, m, points_be32, coeffs_be32, out_values32,
-                                                out_proofs48));
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_lincomb(c, s, n_handles, handles, k, m, points_be32, coeffs_be32, out_values32, out_proofs48);
+    });
 }
 int kzg_multi_rows_commit_shplonk(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
                                   const uint8_t* points_be32, const uint32_t* masks, const uint8_t* coeffs_be32,
                                   uint8_t out_commitment48[48], uint64_t* out_handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_shplonk_impl(c, s, n_handles, handles, k, m, points_be32, masks, coeffs_be32,
-                                                out_commitment48, out_handle));
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_shplonk(c, s, n_handles, handles, k, m, points_be32, masks, coeffs_be32, out_commitment48,
+                                      out_handle);
+    });
 }
 int kzg_multi_rows_commit_grand_product(kzg_multi* mh, uint32_t i, uint32_t n_wire_handles, const uint64_t* wire_handles,
                                         uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
                                         const uint8_t* shifts_be32, const uint8_t beta_be32[32], const uint8_t gamma_be32[32],
                                         uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_grand_product_impl(c, s, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k,
-                                                      shifts_be32, beta_be32, gamma_be32, out_commitment48, out_closing32,
-                                                      out_handle));
-}
-int kzg_multi_rows_commit_lookup_sum(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
-                                     uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
-                                     uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32],
-                                     const uint8_t beta_be32[32], uint8_t out_commitment48[48], uint8_t out_closing32[32],
-                                     uint64_t* out_handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_lookup_sum_impl(c, s, n_input_handles, input_handles, n_table_handles, table_handles,
-                                                   mult_handle, n_lookups, width, theta_be32, beta_be32, out_commitment48,
-                                                   out_closing32, out_handle));
-}
-int kzg_multi_rows_commit_multiplicities(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
-                                         uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups,
-                                         uint32_t width, uint8_t out_commitment48[48], uint64_t* out_missing,
-                                         uint64_t* out_handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_multiplicities_impl(c, s, n_input_handles, input_handles, n_table_handles, table_handles,
-                                                       n_lookups, width, out_commitment48, out_missing, out_handle));
-}
-int kzg_multi_rows_commit_quotient(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
-                                   const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log,
-                                   uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_quotient_impl(c, s, n_handles, handles, gate, perm, ext_log, n_pieces, out_commitments48,
-                                                 out_handle));
-}
-int kzg_multi_rows_commit_quotient_ext(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
-                                       const kzg_quotient_terms* gate, const kzg_quotient_perm* perm,
-                                       const kzg_quotient_lookup* lookup, uint32_t ext_log, uint32_t n_pieces,
-                                       uint8_t* out_commitments48, uint64_t* out_handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_quotient_ext_impl(c, s, n_handles, handles, gate, perm, lookup, ext_log, n_pieces,
-                                                     out_commitments48, out_handle, false));
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_grand_product(c, s, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
+                                            beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle, nullptr, nullptr);
+    });
 }
 int kzg_multi_rows_commit_grand_product_zk(kzg_multi* mh, uint32_t i, uint32_t n_wire_handles, const uint64_t* wire_handles,
                                            uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
                                            const uint8_t* shifts_be32, const uint8_t beta_be32[32], const uint8_t gamma_be32[32],
                                            uint64_t usable, const uint8_t* tail_be32, uint8_t out_commitment48[48],
                                            uint8_t out_closing32[32], uint64_t* out_handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_grand_product_zk_impl(c, s, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k,
-                                                         shifts_be32, beta_be32, gamma_be32, usable, tail_be32, out_commitment48,
-                                                         out_closing32, out_handle));
-}
-int kzg_multi_rows_commit_lookup_sum_zk(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
-                                        uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
-                                        uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32],
-                                        const uint8_t beta_be32[32], uint64_t usable, const uint8_t* tail_be32,
-                                        uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_lookup_sum_zk_impl(c, s, n_input_handles, input_handles, n_table_handles, table_handles,
-                                                      mult_handle, n_lookups, width, theta_be32, beta_be32, usable, tail_be32,
-                                                      out_commitment48, out_closing32, out_handle));
-}
-int kzg_multi_rows_commit_multiplicities_zk(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
-                                            uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups,
-                                            uint32_t width, uint64_t usable, const uint8_t* tail_be32,
-                                            uint8_t out_commitment48[48], uint64_t* out_missing, uint64_t* out_handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_multiplicities_zk_impl(c, s, n_input_handles, input_handles, n_table_handles, table_handles,
-                                                          n_lookups, width, usable, tail_be32, out_commitment48, out_missing,
-                                                          out_handle));
-}
-int kzg_multi_rows_commit_lookup_sum_sel(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
-                                         uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
-                                         uint32_t n_sel_handles, const uint64_t* sel_handles, const uint32_t* sel_index,
-                                         uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32],
-                                         const uint8_t beta_be32[32], uint64_t usable, const uint8_t* tail_be32,
-                                         uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_lookup_sum_sel_impl(c, s, n_input_handles, input_handles, n_table_handles, table_handles,
-                                                       mult_handle, n_sel_handles, sel_handles, sel_index, n_lookups, width,
-                                                       theta_be32, beta_be32, usable, tail_be32, out_commitment48, out_closing32,
-                                                       out_handle));
-}
-int kzg_multi_rows_commit_multiplicities_sel(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
-                                             uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_sel_handles,
-                                             const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups,
-                                             uint32_t width, uint64_t usable, const uint8_t* tail_be32,
-                                             uint8_t out_commitment48[48], uint64_t* out_missing, uint64_t* out_handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_multiplicities_sel_impl(c, s, n_input_handles, input_handles, n_table_handles, table_handles,
-                                                           n_sel_handles, sel_handles, sel_index, n_lookups, width, usable,
-                                                           tail_be32, out_commitment48, out_missing, out_handle));
-}
-int kzg_multi_rows_commit_quotient_sel(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
-                                       const kzg_quotient_terms* gate, const kzg_quotient_perm* perm,
-                                       const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
-                                       const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces,
-                                       uint8_t* out_commitments48, uint64_t* out_handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_quotient_sel_impl(c, s, n_handles, handles, gate, perm, lookup, selectors, active, ext_log,
-                                                     n_pieces, out_commitments48, out_handle));
-}
-int kzg_multi_rows_quotient_part_sel(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
-                                     const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
-                                     const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
-                                     const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32,
-                                     uint64_t* inout_acc) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_quotient_part_sel_impl(c, s, n_handles, handles, gate, perm, link, lookup, selectors, active,
-                                                          ext_log, scale_be32, inout_acc));
-}
-int kzg_multi_rows_commit_quotient_zk(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
-                                      const kzg_quotient_terms* gate, const kzg_quotient_perm* perm,
-                                      const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
-                                      uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_quotient_zk_impl(c, s, n_handles, handles, gate, perm, lookup, active, ext_log, n_pieces,
-                                                    out_commitments48, out_handle));
-}
-int kzg_multi_rows_quotient_part(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
-                                 const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
-                                 const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
-                                 const uint8_t* scale_be32, uint64_t* inout_acc) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_quotient_part_impl(c, s, n_handles, handles, gate, perm, link, lookup, active, ext_log,
-                                                      scale_be32, inout_acc));
-}
-int kzg_multi_rows_quotient_finish(kzg_multi* mh, uint32_t i, uint64_t acc, uint32_t n_pieces, uint8_t* out_commitments48,
-                                   uint64_t* out_handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_quotient_finish_impl(c, s, acc, n_pieces, out_commitments48, out_handle));
+    const kzg_impl::Blind zk = {usable, tail_be32};
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_grand_product(c, s, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
+                                            beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle, &zk, nullptr);
+    });
 }
 int kzg_multi_rows_commit_grand_product_chain(kzg_multi* mh, uint32_t i, uint32_t n_wire_handles, const uint64_t* wire_handles,
                                               uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
@@ -669,34 +448,162 @@ int kzg_multi_rows_commit_grand_product_chain(kzg_multi* mh, uint32_t i, uint32_
                                               const uint8_t gamma_be32[32], uint64_t usable, const uint8_t* tail_be32,
                                               const uint8_t start_be32[32], uint8_t out_commitment48[48],
                                               uint8_t out_closing32[32], uint64_t* out_handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_grand_product_chain_impl(c, s, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles,
-                                                            k, shifts_be32, beta_be32, gamma_be32, usable, tail_be32, start_be32,
-                                                            out_commitment48, out_closing32, out_handle));
+    const kzg_impl::Blind zk = {usable, tail_be32};
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        if (!start_be32) return (int)KZG_E_ARG;   // (to the entry a null start means "not a chain")
+        return kzg_impl::rows_grand_product(c, s, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
+                                            beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle, &zk, start_be32);
+    });
+}
+int kzg_multi_rows_commit_lookup_sum(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                     uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
+                                     uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32],
+                                     const uint8_t beta_be32[32], uint8_t out_commitment48[48], uint8_t out_closing32[32],
+                                     uint64_t* out_handle) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_lookup_sum(c, s, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
+                                         n_lookups, width, theta_be32, beta_be32, out_commitment48, out_closing32, out_handle,
+                                         nullptr, nullptr);
+    });
+}
+int kzg_multi_rows_commit_lookup_sum_zk(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                        uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
+                                        uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32],
+                                        const uint8_t beta_be32[32], uint64_t usable, const uint8_t* tail_be32,
+                                        uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle) {
+    const kzg_impl::Blind zk = {usable, tail_be32};
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_lookup_sum(c, s, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
+                                         n_lookups, width, theta_be32, beta_be32, out_commitment48, out_closing32, out_handle,
+                                         &zk, nullptr);
+    });
+}
+int kzg_multi_rows_commit_lookup_sum_sel(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                         uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
+                                         uint32_t n_sel_handles, const uint64_t* sel_handles, const uint32_t* sel_index,
+                                         uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32],
+                                         const uint8_t beta_be32[32], uint64_t usable, const uint8_t* tail_be32,
+                                         uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle) {
+    const kzg_impl::Blind zk = {usable, tail_be32};
+    const kzg_impl::SelCall sc = {n_sel_handles, sel_handles, sel_index};
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_lookup_sum(c, s, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
+                                         n_lookups, width, theta_be32, beta_be32, out_commitment48, out_closing32, out_handle,
+                                         &zk, &sc);
+    });
+}
+int kzg_multi_rows_commit_multiplicities(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                         uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups,
+                                         uint32_t width, uint8_t out_commitment48[48], uint64_t* out_missing,
+                                         uint64_t* out_handle) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_multiplicities(c, s, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups,
+                                             width, out_commitment48, out_missing, out_handle, nullptr, nullptr);
+    });
+}
+int kzg_multi_rows_commit_multiplicities_zk(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                            uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups,
+                                            uint32_t width, uint64_t usable, const uint8_t* tail_be32,
+                                            uint8_t out_commitment48[48], uint64_t* out_missing, uint64_t* out_handle) {
+    const kzg_impl::Blind zk = {usable, tail_be32};
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_multiplicities(c, s, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups,
+                                             width, out_commitment48, out_missing, out_handle, &zk, nullptr);
+    });
+}
+int kzg_multi_rows_commit_multiplicities_sel(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                             uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_sel_handles,
+                                             const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups,
+                                             uint32_t width, uint64_t usable, const uint8_t* tail_be32,
+                                             uint8_t out_commitment48[48], uint64_t* out_missing, uint64_t* out_handle) {
+    const kzg_impl::Blind zk = {usable, tail_be32};
+    const kzg_impl::SelCall sc = {n_sel_handles, sel_handles, sel_index};
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_multiplicities(c, s, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups,
+                                             width, out_commitment48, out_missing, out_handle, &zk, &sc);
+    });
+}
+int kzg_multi_rows_commit_quotient(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                   const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log,
+                                   uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        if (!gate) return (int)KZG_E_ARG;
+        const kzg_quotient_terms terms = kzg_impl::quotient_plain_terms(gate);
+        return kzg_impl::rows_quotient(c, s, n_handles, handles, &terms, perm, nullptr, nullptr, nullptr, ext_log, n_pieces,
+                                       out_commitments48, out_handle, true);
+    });
+}
+int kzg_multi_rows_commit_quotient_ext(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                       const kzg_quotient_terms* gate, const kzg_quotient_perm* perm,
+                                       const kzg_quotient_lookup* lookup, uint32_t ext_log, uint32_t n_pieces,
+                                       uint8_t* out_commitments48, uint64_t* out_handle) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_quotient(c, s, n_handles, handles, gate, perm, lookup, nullptr, nullptr, ext_log, n_pieces,
+                                       out_commitments48, out_handle, false);
+    });
+}
+int kzg_multi_rows_commit_quotient_zk(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                      const kzg_quotient_terms* gate, const kzg_quotient_perm* perm,
+                                      const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
+                                      uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_quotient(c, s, n_handles, handles, gate, perm, lookup, nullptr, active, ext_log, n_pieces,
+                                       out_commitments48, out_handle, false);
+    });
+}
+int kzg_multi_rows_commit_quotient_sel(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                       const kzg_quotient_terms* gate, const kzg_quotient_perm* perm,
+                                       const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
+                                       const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces,
+                                       uint8_t* out_commitments48, uint64_t* out_handle) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_quotient(c, s, n_handles, handles, gate, perm, lookup, selectors, active, ext_log, n_pieces,
+                                       out_commitments48, out_handle, false);
+    });
+}
+int kzg_multi_rows_quotient_part(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                 const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                                 const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
+                                 const uint8_t* scale_be32, uint64_t* inout_acc) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_quotient_part(c, s, n_handles, handles, gate, perm, link, lookup, nullptr, active, ext_log,
+                                            scale_be32, inout_acc);
+    });
+}
+int kzg_multi_rows_quotient_part_sel(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles,
+                                     const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                                     const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
+                                     const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32,
+                                     uint64_t* inout_acc) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_quotient_part(c, s, n_handles, handles, gate, perm, link, lookup, selectors, active, ext_log,
+                                            scale_be32, inout_acc);
+    });
+}
+int kzg_multi_rows_quotient_finish(kzg_multi* mh, uint32_t i, uint64_t acc, uint32_t n_pieces, uint8_t* out_commitments48,
+                                   uint64_t* out_handle) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_quotient_finish(c, s, acc, n_pieces, out_commitments48, out_handle);
+    });
 }
 int kzg_multi_rows_release(kzg_multi* mh, uint32_t i, uint64_t handle) {
-    kzg_ctx* c;
-    uint32_t s;
-    if (int rc = route(mh, i, &c, &s)) return rc;
-    return relay(c, kzg_impl::rows_release_impl(c, s, handle));
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) { return kzg_impl::rows_release(c, s, handle); });
 }
 
 int kzg_multi_create(int device_count, const int* device_ids, kzg_multi** out) {
-    return guarded("kzg_multi_create", [&] { return create_impl(device_count, device_ids, out); });
+    return guarded("kzg_multi_create", [&] { return create_body(device_count, device_ids, out); });
 }
 int kzg_multi_load_srs_file(kzg_multi* m, const char* path, int compressed, int scale, int machines_scale) {
-    return guarded("kzg_multi_load_srs_file", [&] { return load_srs_file_impl(m, path, compressed, scale, machines_scale); });
+    return guarded("kzg_multi_load_srs_file", [&] { return load_srs_file_body(m, path, compressed, scale, machines_scale); });
 }
 int kzg_multi_gen_srs(kzg_multi* m, const uint8_t tau_be32[32], const uint8_t* s0_be32_all, int scale, int machines_scale) {
-    return guarded("kzg_multi_gen_srs", [&] { return gen_srs_impl(m, tau_be32, s0_be32_all, scale, machines_scale); });
+    return guarded("kzg_multi_gen_srs", [&] { return gen_srs_body(m, tau_be32, s0_be32_all, scale, machines_scale); });
 }
 int kzg_multi_load_srs_file_segments(kzg_multi* m, const char* path, int compressed, uint64_t n_points) {
-    return guarded("kzg_multi_load_srs_file_segments", [&] { return load_segments_impl(m, path, compressed, n_points); });
+    return guarded("kzg_multi_load_srs_file_segments", [&] { return load_segments_body(m, path, compressed, n_points); });
 }
 int kzg_multi_gen_srs_segments(kzg_multi* m, const uint8_t tau_be32[32], const uint8_t* s0_be32_per_device, uint64_t n_points) {
-    return guarded("kzg_multi_gen_srs_segments", [&] { return gen_segments_impl(m, tau_be32, s0_be32_per_device, n_points); });
+    return guarded("kzg_multi_gen_srs_segments", [&] { return gen_segments_body(m, tau_be32, s0_be32_per_device, n_points); });
 }
 int kzg_multi_segment(kzg_multi* m, int g, uint64_t out_first_count[2]) {
     if (!m || !out_first_count || g < 0 || g >= (int)m->ctx.size() || m->layout != LAYOUT_SEGMENTS) return mfail(KZG_E_ARG, "no such segment");
@@ -705,19 +612,19 @@ int kzg_multi_segment(kzg_multi* m, int g, uint64_t out_first_count[2]) {
     return KZG_OK;
 }
 int kzg_multi_msm(kzg_multi* m, const uint8_t* scalars_be32, uint64_t n, uint64_t srs_offset, uint8_t out48[48]) {
-    return guarded("kzg_multi_msm", [&] { return msm_impl(m, scalars_be32, n, srs_offset, out48); });
+    return guarded("kzg_multi_msm", [&] { return msm_body(m, scalars_be32, n, srs_offset, out48); });
 }
 int kzg_multi_upload_fr(kzg_multi* m, int slot, const uint8_t* scalars_be32, uint64_t n, uint64_t srs_offset) {
-    return guarded("kzg_multi_upload_fr", [&] { return upload_impl(m, slot, scalars_be32, n, srs_offset); });
+    return guarded("kzg_multi_upload_fr", [&] { return upload_body(m, slot, scalars_be32, n, srs_offset); });
 }
 int kzg_multi_msm_resident(kzg_multi* m, int slot, uint8_t out48[48]) {
-    return guarded("kzg_multi_msm_resident", [&] { return msm_resident_impl(m, slot, out48); });
+    return guarded("kzg_multi_msm_resident", [&] { return msm_resident_body(m, slot, out48); });
 }
 int kzg_multi_commit_open_rows(kzg_multi* m, uint32_t n_rows, const uint32_t* indices, const uint8_t* rows_be32, uint64_t T,
                                int evaluation_form, const uint8_t alpha_be32[32], uint8_t* out_c48, uint8_t* out_e32, uint8_t* out_p48,
                                int* out_status) {
     return guarded("kzg_multi_commit_open_rows", [&] {
-        return commit_open_rows_impl(m, n_rows, indices, rows_be32, T, evaluation_form, alpha_be32, out_c48, out_e32, out_p48, out_status);
+        return commit_open_rows_body(m, n_rows, indices, rows_be32, T, evaluation_form, alpha_be32, out_c48, out_e32, out_p48, out_status);
     });
 }
 

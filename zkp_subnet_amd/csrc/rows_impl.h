@@ -1,0 +1,72 @@
+// rows_impl.h -- the internal entries behind the row-set exports, declared ONCE for their two callers: serve.hip, which
+// defines them and whose kzg_rows_* exports call them with expect_i = UINT32_MAX, and multi_host.cpp, whose kzg_multi_rows_*
+// exports call them with the routed slice.  Plain C++17 over the public header: no HIP type appears here.
+//
+// Every entry takes the public call's arguments behind (ctx, expect_i).  expect_i is the one thing the public forms lack:
+// every set (and accumulator) named must belong to worker `expect_i`; UINT32_MAX accepts any one worker.  A builder has ONE
+// entry for all its variants: what a variant adds arrives as an optional argument (null: the variant without it).
+#pragma once
+#include "../../include/kzg_mi355x.h"
+
+namespace kzg_impl {
+
+// The blinding rows of a kzg_rows_commit_*_zk builder (checked by the caller: 1 <= usable < T, T - usable <=
+// KZG_MAX_BLIND_ROWS, every tail scalar canonical): rows [0, usable) carry the circuit, row `usable` closes the running value
+// and rows usable + 1 .. T - 1 take the T - usable - 1 scalars of tail_be32 (host bytes).  Null: the plain builder.
+struct Blind {
+    uint64_t usable;
+    const uint8_t* tail_be32;
+};
+// The selector arguments of a _sel builder as the caller gave them (null: the call has none): sel_index[l] is KZG_NO_SELECTOR
+// or indexes the concatenated rows of the sel_handles sets, which must be of the call's worker and row length.  A _sel call
+// always comes with a Blind: usable == T with no tail is the plain layout, decided once T is known.
+struct SelCall {
+    uint32_t n_sel_handles;
+    const uint64_t* sel_handles;
+    const uint32_t* sel_index;
+};
+
+int rows_open(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
+              const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
+              uint8_t* out_proofs48);
+int rows_eval(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
+              const uint8_t* points_be32, const uint32_t* masks, uint8_t* out_evals32);
+int rows_lincomb(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
+                 const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32, uint8_t* out_proofs48);
+int rows_shplonk(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
+                 const uint8_t* points_be32, const uint32_t* masks, const uint8_t* coeffs_be32, uint8_t* out_commitment48,
+                 uint64_t* out_handle);
+int rows_release(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle);
+// zk: the blinding rows of the _zk and _chain calls.  start_be32: the _chain call's start of z (null: not a chain, z starts at 1)
+int rows_grand_product(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                       uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
+                       const uint8_t* beta_be32, const uint8_t* gamma_be32, uint8_t* out_commitment48, uint8_t* out_closing32,
+                       uint64_t* out_handle, const Blind* zk, const uint8_t* start_be32);
+// zk: the blinding rows of the _zk call, the layout of the _sel call.  sc: the selectors of the _sel call
+int rows_lookup_sum(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                    uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
+                    uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint8_t* out_commitment48,
+                    uint8_t* out_closing32, uint64_t* out_handle, const Blind* zk, const SelCall* sc);
+int rows_multiplicities(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                        uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
+                        uint8_t* out_commitment48, uint64_t* out_missing, uint64_t* out_handle, const Blind* zk,
+                        const SelCall* sc);
+// lookup: the _ext call's.  selectors: the _sel call's.  active: the _zk call's column A.  plain: the call came through
+// kzg_rows_commit_quotient (quotient_plain_terms below), which only words one message
+int rows_quotient(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
+                  const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
+                  const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,
+                  uint64_t* out_handle, bool plain);
+int rows_quotient_part(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                       const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                       const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
+                       const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32, uint64_t* inout_acc);
+int rows_quotient_finish(kzg_ctx* ctx, uint32_t expect_i, uint64_t acc, uint32_t n_pieces, uint8_t* out_commitments48,
+                         uint64_t* out_handle);
+
+// kzg_rows_commit_quotient's gate as the terms of the general call: every rotation 0 (the caller has checked gate != NULL)
+inline kzg_quotient_terms quotient_plain_terms(const kzg_quotient_gate* gate) {
+    return {gate->n_terms, gate->coeffs_be32, gate->term_lens, gate->term_rows, nullptr};
+}
+
+}  // namespace kzg_impl

@@ -738,9 +738,9 @@ static int rows_lookup(kzg_ctx* ctx, const char* what, uint32_t expect_i, uint32
     return KZG_OK;
 }
 
-int rows_open_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
-                   const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
-                   uint8_t* out_proofs48) {
+int rows_open(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
+              const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
+              uint8_t* out_proofs48) {
     if (!ctx || !handles || !points_be32 || !masks || !gammas_be32 || !out_evals32 || !out_proofs48) return KZG_E_ARG;
     if (n_handles == 0 || n_handles > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "row-set opening: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
@@ -770,8 +770,8 @@ int rows_open_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const ui
 }
 
 // kzg_rows_eval: the checks and lookup of kzg_rows_open without the gammas
-int rows_eval_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
-                   const uint8_t* points_be32, const uint32_t* masks, uint8_t* out_evals32) {
+int rows_eval(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
+              const uint8_t* points_be32, const uint32_t* masks, uint8_t* out_evals32) {
     if (!ctx || !handles || !points_be32 || !masks || !out_evals32) return KZG_E_ARG;
     if (n_handles == 0 || n_handles > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "row-set evaluation: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
@@ -801,8 +801,8 @@ int rows_eval_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const ui
 }
 
 // kzg_rows_open_lincomb: every coefficient is range-checked here, and each point's mask of nonzero coefficients built
-int rows_lincomb_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
-                      const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32, uint8_t* out_proofs48) {
+int rows_lincomb(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
+                 const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32, uint8_t* out_proofs48) {
     if (!ctx || !handles || !points_be32 || !coeffs_be32 || !out_values32 || !out_proofs48) return KZG_E_ARG;
     if (n_handles == 0 || n_handles > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "row-set lincomb: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
@@ -842,9 +842,9 @@ int rows_lincomb_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const
 // open and the reservation of a commit
 static_assert(KZG_MAX_SHPLONK_ROWS + 1 <= KZG_MAX_BATCH_OPEN && KZG_MAX_SHPLONK_POINTS <= 8, "round B opens k + 1 rows; a "
               "point set is a byte");
-int rows_shplonk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
-                      const uint8_t* points_be32, const uint32_t* masks, const uint8_t* coeffs_be32, uint8_t* out_commitment48,
-                      uint64_t* out_handle) {
+int rows_shplonk(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
+                 const uint8_t* points_be32, const uint32_t* masks, const uint8_t* coeffs_be32, uint8_t* out_commitment48,
+                 uint64_t* out_handle) {
     if (!ctx || !handles || !points_be32 || !masks || !coeffs_be32 || !out_commitment48 || !out_handle) return KZG_E_ARG;
     if (n_handles == 0 || n_handles > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "shplonk: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
@@ -918,12 +918,12 @@ static int blind_check(kzg_ctx* ctx, const char* what, uint64_t T, const Blind& 
 }
 
 // kzg_rows_commit_grand_product: the lookups of an open (two handle lists), the reservation of a commit.  zk: the blinding
-// rows of kzg_rows_commit_grand_product_zk (null: the plain call)
-static int rows_grand_product_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
-                                  uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
-                                  const uint8_t* shifts_be32, const uint8_t* beta_be32, const uint8_t* gamma_be32,
-                                  uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle, const Blind* zk,
-                                  const uint8_t* start_be32 = nullptr) {
+// rows of kzg_rows_commit_grand_product_zk (null: the plain call).  start_be32: kzg_rows_commit_grand_product_chain's start of
+// z instead of 1 (null: not a chain)
+int rows_grand_product(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                       uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
+                       const uint8_t* beta_be32, const uint8_t* gamma_be32, uint8_t* out_commitment48, uint8_t* out_closing32,
+                       uint64_t* out_handle, const Blind* zk, const uint8_t* start_be32) {
     if (!ctx || !wire_handles || !sigma_handles || !shifts_be32 || !beta_be32 || !gamma_be32 || !out_commitment48 ||
         !out_closing32 || !out_handle)
         return KZG_E_ARG;
@@ -977,41 +977,10 @@ static int rows_grand_product_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wi
     *out_handle = rows_insert(ctx, pend, i, 1, T);
     return KZG_OK;
 }
-int rows_grand_product_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
-                            uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
-                            const uint8_t* beta_be32, const uint8_t* gamma_be32, uint8_t* out_commitment48,
-                            uint8_t* out_closing32, uint64_t* out_handle) {
-    return rows_grand_product_any(ctx, expect_i, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
-                                  beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle, nullptr);
-}
-int rows_grand_product_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
-                               uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
-                               const uint8_t* beta_be32, const uint8_t* gamma_be32, uint64_t usable, const uint8_t* tail_be32,
-                               uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle) {
-    const Blind zk = {usable, tail_be32};
-    return rows_grand_product_any(ctx, expect_i, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
-                                  beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle, &zk);
-}
-// kzg_rows_commit_grand_product_chain: the _zk call whose z starts at `start` instead of 1
-int rows_grand_product_chain_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
-                                  uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
-                                  const uint8_t* beta_be32, const uint8_t* gamma_be32, uint64_t usable, const uint8_t* tail_be32,
-                                  const uint8_t* start_be32, uint8_t* out_commitment48, uint8_t* out_closing32,
-                                  uint64_t* out_handle) {
-    if (!start_be32) return KZG_E_ARG;
-    const Blind zk = {usable, tail_be32};
-    return rows_grand_product_any(ctx, expect_i, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
-                                  beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle, &zk, start_be32);
-}
 
-// The selector arguments of a _sel builder as the caller gave them (null: the call has none), and their check: sel_index[l] is
-// KZG_NO_SELECTOR or indexes the concatenated rows of the sel_handles sets, which must be of the call's worker and row length.
-// The distinct rows named go into sp (a row that serves several lookups is transformed once).
-struct SelCall {
-    uint32_t n_sel_handles;
-    const uint64_t* sel_handles;
-    const uint32_t* sel_index;
-};
+// The check of a _sel builder's selector arguments (SelCall, rows_impl.h): sel_index[l] is KZG_NO_SELECTOR or indexes the
+// concatenated rows of the sel_handles sets, which must be of the call's worker and row length.  The distinct rows named go
+// into sp (a row that serves several lookups is transformed once).
 static int sel_plan(kzg_ctx* ctx, const char* what, uint32_t expect_i, const SelCall& sc, uint32_t n_lookups, uint32_t i, uint64_t T,
                     RowsRefs& refs, SelPlan& sp) {
     auto bad = [&](const char* why) { return fail(ctx, KZG_E_ARG, std::string(what) + why); };
@@ -1046,11 +1015,12 @@ static int sel_plan(kzg_ctx* ctx, const char* what, uint32_t expect_i, const Sel
 static const Blind* sel_layout(const Blind* zk, uint64_t T) { return zk->usable == T && !zk->tail_be32 ? nullptr : zk; }
 
 // kzg_rows_commit_lookup_sum: the lookups of an open (three handle lists), the reservation of a commit.  zk: the blinding
-// rows of kzg_rows_commit_lookup_sum_zk (null: the plain call)
-static int rows_lookup_sum_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                               uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
-                               uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint8_t* out_commitment48,
-                               uint8_t* out_closing32, uint64_t* out_handle, const Blind* zk, const SelCall* sc = nullptr) {
+// rows of kzg_rows_commit_lookup_sum_zk (null: the plain call).  sc: the selectors of kzg_rows_commit_lookup_sum_sel, one call
+// for both layouts (sel_layout decides once T is known)
+int rows_lookup_sum(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                    uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
+                    uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint8_t* out_commitment48,
+                    uint8_t* out_closing32, uint64_t* out_handle, const Blind* zk, const SelCall* sc) {
     if (!ctx || !input_handles || !table_handles || !theta_be32 || !beta_be32 || !out_commitment48 || !out_closing32 ||
         !out_handle)
         return KZG_E_ARG;
@@ -1111,40 +1081,13 @@ static int rows_lookup_sum_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input
     *out_handle = rows_insert(ctx, pend, i, 1, T);
     return KZG_OK;
 }
-int rows_lookup_sum_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                         uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
-                         uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint8_t* out_commitment48,
-                         uint8_t* out_closing32, uint64_t* out_handle) {
-    return rows_lookup_sum_any(ctx, expect_i, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
-                               n_lookups, width, theta_be32, beta_be32, out_commitment48, out_closing32, out_handle, nullptr);
-}
-int rows_lookup_sum_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                            uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,
-                            uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint64_t usable,
-                            const uint8_t* tail_be32, uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle) {
-    const Blind zk = {usable, tail_be32};
-    return rows_lookup_sum_any(ctx, expect_i, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
-                               n_lookups, width, theta_be32, beta_be32, out_commitment48, out_closing32, out_handle, &zk);
-}
-
-// kzg_rows_commit_lookup_sum_sel: one call for both layouts (sel_plan decides once T is known)
-int rows_lookup_sum_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                             uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
-                             uint32_t n_sel_handles, const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups,
-                             uint32_t width, const uint8_t* theta_be32, const uint8_t* beta_be32, uint64_t usable,
-                             const uint8_t* tail_be32, uint8_t* out_commitment48, uint8_t* out_closing32, uint64_t* out_handle) {
-    const Blind zk = {usable, tail_be32};
-    const SelCall sc = {n_sel_handles, sel_handles, sel_index};
-    return rows_lookup_sum_any(ctx, expect_i, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
-                               n_lookups, width, theta_be32, beta_be32, out_commitment48, out_closing32, out_handle, &zk, &sc);
-}
 
 // kzg_rows_commit_multiplicities: the lookups of an open (two handle lists), the reservation of a commit.  zk: the blinding
-// rows of kzg_rows_commit_multiplicities_zk (null: the plain call)
-static int rows_multiplicities_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                                   uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
-                                   uint8_t* out_commitment48, uint64_t* out_missing, uint64_t* out_handle, const Blind* zk,
-                                   const SelCall* sc = nullptr) {
+// rows of kzg_rows_commit_multiplicities_zk (null: the plain call).  sc: the selectors of kzg_rows_commit_multiplicities_sel
+int rows_multiplicities(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                        uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
+                        uint8_t* out_commitment48, uint64_t* out_missing, uint64_t* out_handle, const Blind* zk,
+                        const SelCall* sc) {
     if (!ctx || !input_handles || !table_handles || !out_commitment48 || !out_missing || !out_handle) return KZG_E_ARG;
     if (sc && (!sc->sel_index || (sc->n_sel_handles && !sc->sel_handles))) return KZG_E_ARG;
     if (sc && sc->n_sel_handles > KZG_MAX_BATCH_OPEN)
@@ -1199,31 +1142,6 @@ static int rows_multiplicities_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_i
     *out_missing = missing;
     *out_handle = rows_insert(ctx, pend, i, 1, T);
     return KZG_OK;
-}
-int rows_multiplicities_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                             uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
-                             uint8_t* out_commitment48, uint64_t* out_missing, uint64_t* out_handle) {
-    return rows_multiplicities_any(ctx, expect_i, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups,
-                                   width, out_commitment48, out_missing, out_handle, nullptr);
-}
-int rows_multiplicities_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                                uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
-                                uint64_t usable, const uint8_t* tail_be32, uint8_t* out_commitment48, uint64_t* out_missing,
-                                uint64_t* out_handle) {
-    const Blind zk = {usable, tail_be32};
-    return rows_multiplicities_any(ctx, expect_i, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups,
-                                   width, out_commitment48, out_missing, out_handle, &zk);
-}
-// kzg_rows_commit_multiplicities_sel: one call for both layouts (sel_plan decides once T is known)
-int rows_multiplicities_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
-                                 uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_sel_handles,
-                                 const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups, uint32_t width,
-                                 uint64_t usable, const uint8_t* tail_be32, uint8_t* out_commitment48, uint64_t* out_missing,
-                                 uint64_t* out_handle) {
-    const Blind zk = {usable, tail_be32};
-    const SelCall sc = {n_sel_handles, sel_handles, sel_index};
-    return rows_multiplicities_any(ctx, expect_i, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups,
-                                   width, out_commitment48, out_missing, out_handle, &zk, &sc);
 }
 
 // The constraints of a quotient call as the caller gave them, checked and turned into the kernels' plan before any lane is
@@ -1364,11 +1282,11 @@ static int quot_plan_rows(kzg_ctx* ctx, QuotCall& C, uint32_t n, uint32_t i, uin
 // kzg_rows_commit_quotient_ext (and, with no rotation and no lookup part, kzg_rows_commit_quotient: `plain`, which only words
 // one message): the lookups of an open (one handle list), the reservation of a commit
 // active: the caller's column A of kzg_rows_commit_quotient_zk, a factor of P1 and LK1 (null: neither has it)
-static int rows_quotient_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                             const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
-                             const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces,
-                             uint8_t* out_commitments48, uint64_t* out_handle, bool plain,
-                             const kzg_quotient_selectors* selectors = nullptr) {
+// selectors: those of kzg_rows_commit_quotient_sel (null: none)
+int rows_quotient(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
+                  const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
+                  const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,
+                  uint64_t* out_handle, bool plain) {
     if (!ctx || !handles || !gate || !out_commitments48 || !out_handle) return KZG_E_ARG;
     QuotCall C;
     if (int rc = quot_plan(ctx, gate, perm, nullptr, lookup, active, ext_log, &n_pieces, n_handles, plain, C, selectors)) return rc;
@@ -1419,11 +1337,10 @@ static int acc_lookup(kzg_ctx* ctx, const char* what, uint32_t expect_i, uint64_
     return KZG_OK;
 }
 // selectors: those of kzg_rows_quotient_part_sel (null: kzg_rows_quotient_part)
-static int rows_quotient_part_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                                  const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
-                                  const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
-                                  const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32,
-                                  uint64_t* inout_acc) {
+int rows_quotient_part(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
+                       const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
+                       const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
+                       const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32, uint64_t* inout_acc) {
     if (!ctx || !handles || !gate || !inout_acc) return KZG_E_ARG;
     if (scale_be32 && !fr_be32_canonical(scale_be32))
         return fail(ctx, KZG_E_ARG, "quotient part: scale must be a canonical scalar (< r)");
@@ -1491,23 +1408,8 @@ static int rows_quotient_part_any(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_ha
     }
     return KZG_OK;
 }
-int rows_quotient_part_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                            const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
-                            const kzg_quotient_lookup* lookup, const kzg_quotient_active* active, uint32_t ext_log,
-                            const uint8_t* scale_be32, uint64_t* inout_acc) {
-    return rows_quotient_part_any(ctx, expect_i, n_handles, handles, gate, perm, link, lookup, nullptr, active, ext_log, scale_be32,
-                                  inout_acc);
-}
-int rows_quotient_part_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                                const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_link* link,
-                                const kzg_quotient_lookup* lookup, const kzg_quotient_selectors* selectors,
-                                const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32,
-                                uint64_t* inout_acc) {
-    return rows_quotient_part_any(ctx, expect_i, n_handles, handles, gate, perm, link, lookup, selectors, active, ext_log,
-                                  scale_be32, inout_acc);
-}
-int rows_quotient_finish_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t acc_handle, uint32_t n_pieces, uint8_t* out_commitments48,
-                              uint64_t* out_handle) {
+int rows_quotient_finish(kzg_ctx* ctx, uint32_t expect_i, uint64_t acc_handle, uint32_t n_pieces, uint8_t* out_commitments48,
+                         uint64_t* out_handle) {
     if (!ctx || !out_commitments48 || !out_handle) return KZG_E_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     RowsPending pend{ctx};
@@ -1549,40 +1451,8 @@ int rows_quotient_finish_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t acc_hand
     }
     return KZG_OK;
 }
-int rows_quotient_ext_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
-                           uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle, bool plain) {
-    return rows_quotient_any(ctx, expect_i, n_handles, handles, gate, perm, lookup, nullptr, ext_log, n_pieces, out_commitments48,
-                             out_handle, plain);
-}
-// kzg_rows_commit_quotient_zk: active == NULL is kzg_rows_commit_quotient_ext
-int rows_quotient_zk_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                          const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
-                          const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,
-                          uint64_t* out_handle) {
-    return rows_quotient_any(ctx, expect_i, n_handles, handles, gate, perm, lookup, active, ext_log, n_pieces, out_commitments48,
-                             out_handle, false);
-}
-// kzg_rows_commit_quotient_sel: selectors == NULL is kzg_rows_commit_quotient_zk
-int rows_quotient_sel_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                           const kzg_quotient_terms* gate, const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
-                           const kzg_quotient_selectors* selectors, const kzg_quotient_active* active, uint32_t ext_log,
-                           uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle) {
-    return rows_quotient_any(ctx, expect_i, n_handles, handles, gate, perm, lookup, active, ext_log, n_pieces, out_commitments48,
-                             out_handle, false, selectors);
-}
 
-// kzg_rows_commit_quotient: the same with every rotation 0 and no lookup part
-int rows_quotient_impl(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles,
-                       const kzg_quotient_gate* gate, const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces,
-                       uint8_t* out_commitments48, uint64_t* out_handle) {
-    if (!gate) return KZG_E_ARG;
-    const kzg_quotient_terms terms = {gate->n_terms, gate->coeffs_be32, gate->term_lens, gate->term_rows, nullptr};
-    return rows_quotient_ext_impl(ctx, expect_i, n_handles, handles, &terms, perm, nullptr, ext_log, n_pieces, out_commitments48,
-                                  out_handle, true);
-}
-
-int rows_release_impl(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle) {
+int rows_release(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle) {
     if (!ctx) return KZG_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->sets_mu);
     auto it = ctx->sets.find(handle);
@@ -1633,72 +1503,67 @@ int kzg_rows_commit(kzg_ctx* ctx, uint32_t i, uint32_t k, const uint8_t* rows_be
     *out_handle = h;
     return KZG_OK;
 }
+// The exports below are the entries of rows_impl.h for any one worker (UINT32_MAX): what a variant adds goes in as a Blind / SelCall
+// on the stack, what it lacks as null
 int kzg_rows_open(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t m, const uint8_t* points_be32,
                   const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32, uint8_t* out_proofs48) {
-    return rows_open_impl(ctx, UINT32_MAX, n_handles, handles, m, points_be32, masks, gammas_be32, out_evals32,
-                          out_proofs48);
+    return rows_open(ctx, UINT32_MAX, n_handles, handles, m, points_be32, masks, gammas_be32, out_evals32, out_proofs48);
 }
 int kzg_rows_eval(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t m, const uint8_t* points_be32,
                   const uint32_t* masks, uint8_t* out_evals32) {
-    return rows_eval_impl(ctx, UINT32_MAX, n_handles, handles, m, points_be32, masks, out_evals32);
+    return rows_eval(ctx, UINT32_MAX, n_handles, handles, m, points_be32, masks, out_evals32);
 }
 int kzg_rows_open_lincomb(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
                           const uint8_t* points_be32, const uint8_t* coeffs_be32, uint8_t* out_values32, uint8_t* out_proofs48) {
-    return rows_lincomb_impl(ctx, UINT32_MAX, n_handles, handles, k, m, points_be32, coeffs_be32, out_values32, out_proofs48);
+    return rows_lincomb(ctx, UINT32_MAX, n_handles, handles, k, m, points_be32, coeffs_be32, out_values32, out_proofs48);
 }
 int kzg_rows_commit_shplonk(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t k, uint32_t m,
                             const uint8_t* points_be32, const uint32_t* masks, const uint8_t* coeffs_be32,
                             uint8_t out_commitment48[48], uint64_t* out_handle) {
-    return rows_shplonk_impl(ctx, UINT32_MAX, n_handles, handles, k, m, points_be32, masks, coeffs_be32, out_commitment48,
-                             out_handle);
+    return rows_shplonk(ctx, UINT32_MAX, n_handles, handles, k, m, points_be32, masks, coeffs_be32, out_commitment48, out_handle);
 }
 int kzg_rows_commit_grand_product(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t* wire_handles, uint32_t n_sigma_handles,
                                   const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
                                   const uint8_t beta_be32[32], const uint8_t gamma_be32[32], uint8_t out_commitment48[48],
                                   uint8_t out_closing32[32], uint64_t* out_handle) {
-    return rows_grand_product_impl(ctx, UINT32_MAX, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
-                                   beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle);
-}
-int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_table_handles,
-                               const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups, uint32_t width,
-                               const uint8_t theta_be32[32], const uint8_t beta_be32[32], uint8_t out_commitment48[48],
-                               uint8_t out_closing32[32], uint64_t* out_handle) {
-    return rows_lookup_sum_impl(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
-                                n_lookups, width, theta_be32, beta_be32, out_commitment48, out_closing32, out_handle);
-}
-int kzg_rows_commit_multiplicities(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
-                                   uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
-                                   uint8_t out_commitment48[48], uint64_t* out_missing, uint64_t* out_handle) {
-    return rows_multiplicities_impl(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups,
-                                    width, out_commitment48, out_missing, out_handle);
-}
-int kzg_rows_commit_quotient(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_gate* gate,
-                             const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,
-                             uint64_t* out_handle) {
-    return rows_quotient_impl(ctx, UINT32_MAX, n_handles, handles, gate, perm, ext_log, n_pieces, out_commitments48, out_handle);
-}
-int kzg_rows_commit_quotient_ext(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
-                                 const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup, uint32_t ext_log,
-                                 uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle) {
-    return rows_quotient_ext_impl(ctx, UINT32_MAX, n_handles, handles, gate, perm, lookup, ext_log, n_pieces, out_commitments48,
-                                  out_handle, false);
+    return rows_grand_product(ctx, UINT32_MAX, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
+                              beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle, nullptr, nullptr);
 }
 int kzg_rows_commit_grand_product_zk(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t* wire_handles,
                                      uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
                                      const uint8_t* shifts_be32, const uint8_t beta_be32[32], const uint8_t gamma_be32[32],
                                      uint64_t usable, const uint8_t* tail_be32, uint8_t out_commitment48[48],
                                      uint8_t out_closing32[32], uint64_t* out_handle) {
-    return rows_grand_product_zk_impl(ctx, UINT32_MAX, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
-                                      beta_be32, gamma_be32, usable, tail_be32, out_commitment48, out_closing32, out_handle);
+    const Blind zk = {usable, tail_be32};
+    return rows_grand_product(ctx, UINT32_MAX, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
+                              beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle, &zk, nullptr);
+}
+// the _zk call whose z starts at `start` instead of 1 (a null start is refused here: to the entry it means "not a chain")
+int kzg_rows_commit_grand_product_chain(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                        uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
+                                        const uint8_t* shifts_be32, const uint8_t beta_be32[32], const uint8_t gamma_be32[32],
+                                        uint64_t usable, const uint8_t* tail_be32, const uint8_t start_be32[32],
+                                        uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle) {
+    if (!start_be32) return KZG_E_ARG;
+    const Blind zk = {usable, tail_be32};
+    return rows_grand_product(ctx, UINT32_MAX, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
+                              beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle, &zk, start_be32);
+}
+int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_table_handles,
+                               const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups, uint32_t width,
+                               const uint8_t theta_be32[32], const uint8_t beta_be32[32], uint8_t out_commitment48[48],
+                               uint8_t out_closing32[32], uint64_t* out_handle) {
+    return rows_lookup_sum(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle, n_lookups,
+                           width, theta_be32, beta_be32, out_commitment48, out_closing32, out_handle, nullptr, nullptr);
 }
 int kzg_rows_commit_lookup_sum_zk(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_table_handles,
                                   const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups, uint32_t width,
                                   const uint8_t theta_be32[32], const uint8_t beta_be32[32], uint64_t usable,
                                   const uint8_t* tail_be32, uint8_t out_commitment48[48], uint8_t out_closing32[32],
                                   uint64_t* out_handle) {
-    return rows_lookup_sum_zk_impl(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
-                                   n_lookups, width, theta_be32, beta_be32, usable, tail_be32, out_commitment48, out_closing32,
-                                   out_handle);
+    const Blind zk = {usable, tail_be32};
+    return rows_lookup_sum(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle, n_lookups,
+                           width, theta_be32, beta_be32, out_commitment48, out_closing32, out_handle, &zk, nullptr);
 }
 int kzg_rows_commit_lookup_sum_sel(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_table_handles,
                                    const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_sel_handles,
@@ -1706,66 +1571,83 @@ int kzg_rows_commit_lookup_sum_sel(kzg_ctx* ctx, uint32_t n_input_handles, const
                                    const uint8_t theta_be32[32], const uint8_t beta_be32[32], uint64_t usable,
                                    const uint8_t* tail_be32, uint8_t out_commitment48[48], uint8_t out_closing32[32],
                                    uint64_t* out_handle) {
-    return rows_lookup_sum_sel_impl(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle,
-                                    n_sel_handles, sel_handles, sel_index, n_lookups, width, theta_be32, beta_be32, usable,
-                                    tail_be32, out_commitment48, out_closing32, out_handle);
+    const Blind zk = {usable, tail_be32};
+    const SelCall sc = {n_sel_handles, sel_handles, sel_index};
+    return rows_lookup_sum(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, mult_handle, n_lookups,
+                           width, theta_be32, beta_be32, out_commitment48, out_closing32, out_handle, &zk, &sc);
+}
+int kzg_rows_commit_multiplicities(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                                   uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
+                                   uint8_t out_commitment48[48], uint64_t* out_missing, uint64_t* out_handle) {
+    return rows_multiplicities(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups, width,
+                               out_commitment48, out_missing, out_handle, nullptr, nullptr);
+}
+int kzg_rows_commit_multiplicities_zk(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                                      uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
+                                      uint64_t usable, const uint8_t* tail_be32, uint8_t out_commitment48[48],
+                                      uint64_t* out_missing, uint64_t* out_handle) {
+    const Blind zk = {usable, tail_be32};
+    return rows_multiplicities(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups, width,
+                               out_commitment48, out_missing, out_handle, &zk, nullptr);
 }
 int kzg_rows_commit_multiplicities_sel(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
                                        uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_sel_handles,
                                        const uint64_t* sel_handles, const uint32_t* sel_index, uint32_t n_lookups, uint32_t width,
                                        uint64_t usable, const uint8_t* tail_be32, uint8_t out_commitment48[48],
                                        uint64_t* out_missing, uint64_t* out_handle) {
-    return rows_multiplicities_sel_impl(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles,
-                                        n_sel_handles, sel_handles, sel_index, n_lookups, width, usable, tail_be32,
-                                        out_commitment48, out_missing, out_handle);
+    const Blind zk = {usable, tail_be32};
+    const SelCall sc = {n_sel_handles, sel_handles, sel_index};
+    return rows_multiplicities(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups, width,
+                               out_commitment48, out_missing, out_handle, &zk, &sc);
 }
+// the same with every rotation 0 and no lookup part
+int kzg_rows_commit_quotient(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_gate* gate,
+                             const kzg_quotient_perm* perm, uint32_t ext_log, uint32_t n_pieces, uint8_t* out_commitments48,
+                             uint64_t* out_handle) {
+    if (!gate) return KZG_E_ARG;
+    const kzg_quotient_terms terms = quotient_plain_terms(gate);
+    return rows_quotient(ctx, UINT32_MAX, n_handles, handles, &terms, perm, nullptr, nullptr, nullptr, ext_log, n_pieces,
+                         out_commitments48, out_handle, true);
+}
+int kzg_rows_commit_quotient_ext(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
+                                 const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup, uint32_t ext_log,
+                                 uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle) {
+    return rows_quotient(ctx, UINT32_MAX, n_handles, handles, gate, perm, lookup, nullptr, nullptr, ext_log, n_pieces,
+                         out_commitments48, out_handle, false);
+}
+// active == NULL is kzg_rows_commit_quotient_ext
+int kzg_rows_commit_quotient_zk(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
+                                const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
+                                const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces,
+                                uint8_t* out_commitments48, uint64_t* out_handle) {
+    return rows_quotient(ctx, UINT32_MAX, n_handles, handles, gate, perm, lookup, nullptr, active, ext_log, n_pieces,
+                         out_commitments48, out_handle, false);
+}
+// selectors == NULL is kzg_rows_commit_quotient_zk
 int kzg_rows_commit_quotient_sel(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
                                  const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
                                  const kzg_quotient_selectors* selectors, const kzg_quotient_active* active, uint32_t ext_log,
                                  uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle) {
-    return rows_quotient_sel_impl(ctx, UINT32_MAX, n_handles, handles, gate, perm, lookup, selectors, active, ext_log, n_pieces,
-                                  out_commitments48, out_handle);
+    return rows_quotient(ctx, UINT32_MAX, n_handles, handles, gate, perm, lookup, selectors, active, ext_log, n_pieces,
+                         out_commitments48, out_handle, false);
+}
+int kzg_rows_quotient_part(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
+                           const kzg_quotient_perm* perm, const kzg_quotient_link* link, const kzg_quotient_lookup* lookup,
+                           const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32, uint64_t* inout_acc) {
+    return rows_quotient_part(ctx, UINT32_MAX, n_handles, handles, gate, perm, link, lookup, nullptr, active, ext_log, scale_be32,
+                              inout_acc);
 }
 int kzg_rows_quotient_part_sel(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
                                const kzg_quotient_perm* perm, const kzg_quotient_link* link, const kzg_quotient_lookup* lookup,
                                const kzg_quotient_selectors* selectors, const kzg_quotient_active* active, uint32_t ext_log,
                                const uint8_t* scale_be32, uint64_t* inout_acc) {
-    return rows_quotient_part_sel_impl(ctx, UINT32_MAX, n_handles, handles, gate, perm, link, lookup, selectors, active, ext_log,
-                                       scale_be32, inout_acc);
-}
-int kzg_rows_commit_multiplicities_zk(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
-                                      uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_lookups, uint32_t width,
-                                      uint64_t usable, const uint8_t* tail_be32, uint8_t out_commitment48[48],
-                                      uint64_t* out_missing, uint64_t* out_handle) {
-    return rows_multiplicities_zk_impl(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, n_lookups,
-                                       width, usable, tail_be32, out_commitment48, out_missing, out_handle);
-}
-int kzg_rows_commit_quotient_zk(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
-                                const kzg_quotient_perm* perm, const kzg_quotient_lookup* lookup,
-                                const kzg_quotient_active* active, uint32_t ext_log, uint32_t n_pieces,
-                                uint8_t* out_commitments48, uint64_t* out_handle) {
-    return rows_quotient_zk_impl(ctx, UINT32_MAX, n_handles, handles, gate, perm, lookup, active, ext_log, n_pieces,
-                                 out_commitments48, out_handle);
-}
-int kzg_rows_quotient_part(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, const kzg_quotient_terms* gate,
-                           const kzg_quotient_perm* perm, const kzg_quotient_link* link, const kzg_quotient_lookup* lookup,
-                           const kzg_quotient_active* active, uint32_t ext_log, const uint8_t* scale_be32, uint64_t* inout_acc) {
-    return rows_quotient_part_impl(ctx, UINT32_MAX, n_handles, handles, gate, perm, link, lookup, active, ext_log, scale_be32,
-                                   inout_acc);
+    return rows_quotient_part(ctx, UINT32_MAX, n_handles, handles, gate, perm, link, lookup, selectors, active, ext_log,
+                              scale_be32, inout_acc);
 }
 int kzg_rows_quotient_finish(kzg_ctx* ctx, uint64_t acc, uint32_t n_pieces, uint8_t* out_commitments48, uint64_t* out_handle) {
-    return rows_quotient_finish_impl(ctx, UINT32_MAX, acc, n_pieces, out_commitments48, out_handle);
+    return rows_quotient_finish(ctx, UINT32_MAX, acc, n_pieces, out_commitments48, out_handle);
 }
-int kzg_rows_commit_grand_product_chain(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t* wire_handles,
-                                        uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k,
-                                        const uint8_t* shifts_be32, const uint8_t beta_be32[32], const uint8_t gamma_be32[32],
-                                        uint64_t usable, const uint8_t* tail_be32, const uint8_t start_be32[32],
-                                        uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle) {
-    return rows_grand_product_chain_impl(ctx, UINT32_MAX, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k,
-                                         shifts_be32, beta_be32, gamma_be32, usable, tail_be32, start_be32, out_commitment48,
-                                         out_closing32, out_handle);
-}
-int kzg_rows_release(kzg_ctx* ctx, uint64_t handle) { return rows_release_impl(ctx, UINT32_MAX, handle); }
+int kzg_rows_release(kzg_ctx* ctx, uint64_t handle) { return rows_release(ctx, UINT32_MAX, handle); }
 int kzg_rows_stats(kzg_ctx* ctx, uint64_t out_live_sets_bytes[2]) {
     if (!ctx || !out_live_sets_bytes) return KZG_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->sets_mu);

@@ -417,17 +417,24 @@ class HipEngine:
         """z of kzg_rows_commit_grand_product over the k concatenated rows of wire_sets and of sigma_sets (RowSet objects or
         bare handles), one 32-byte shift per row.  Returns (a one-row RowSet holding z, the closing value as 32 bytes
         big-endian: 1 when the permutation holds).  beta and gamma must be drawn after the wire commitments are fixed."""
-        nw, hw = self._handle_array(wire_sets, "commit_grand_product (wires)")
-        ns, hs = self._handle_array(sigma_sets, "commit_grand_product (sigmas)")
-        k = len(shifts_be32)
-        if k == 0 or k > _native.KZG_MAX_BATCH_OPEN or any(len(x) != 32 for x in list(shifts_be32) + [beta_be32, gamma_be32]):
-            raise KzgError(_native.KZG_E_ARG, f"commit_grand_product: 1 .. {_native.KZG_MAX_BATCH_OPEN} shifts, beta and gamma "
-                                              "of 32 bytes each")
+        return self._grand_product("commit_grand_product", wire_sets, sigma_sets, shifts_be32, beta_be32, gamma_be32)
+
+    def _grand_product(self, what, wire_sets, sigma_sets, shifts_be32, beta_be32, gamma_be32, blind=None, start_be32=None):
+        """The one body of commit_grand_product / _zk / _chain: `what` names the public method (and the native export
+        kzg_rows_ + its suffix); blind = (usable, tail_be32) for the _zk and _chain forms, start_be32 for the _chain form."""
+        nw, hw = self._handle_array(wire_sets, f"{what} (wires)")
+        ns, hs = self._handle_array(sigma_sets, f"{what} (sigmas)")
+        k, start = len(shifts_be32), [] if start_be32 is None else [start_be32]
+        if k == 0 or k > _native.KZG_MAX_BATCH_OPEN or \
+                any(len(x) != 32 for x in list(shifts_be32) + [beta_be32, gamma_be32] + start):
+            raise KzgError(_native.KZG_E_ARG, f"{what}: 1 .. {_native.KZG_MAX_BATCH_OPEN} shifts, " +
+                           ("beta, gamma and start" if start else "beta and gamma") + " of 32 bytes each")
+        sets = list(wire_sets) + list(sigma_sets)
+        extra, wi, T = self._layout_args(what, sets, blind)
         c, cl, h = ctypes.create_string_buffer(48), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
-        self._chk(self._lib.kzg_rows_commit_grand_product(self._h, nw, hw, ns, hs, k, b"".join(shifts_be32), beta_be32,
-                                                          gamma_be32, c, cl, ctypes.byref(h)))
-        src = next((x for x in list(wire_sets) + list(sigma_sets) if hasattr(x, "T")), None)
-        return RowSet(self, h.value, getattr(src, "i", None), 1, getattr(src, "T", None), [c.raw]), cl.raw
+        self._chk(getattr(self._lib, "kzg_rows_" + what)(self._h, nw, hw, ns, hs, k, b"".join(shifts_be32), beta_be32, gamma_be32,
+                                                         *extra, *start, c, cl, ctypes.byref(h)))
+        return RowSet(self, h.value, wi, 1, T, [c.raw]), cl.raw
 
     # ---- a fourth set built from sets: the running sum of a logUp lookup argument, computed and committed on the device
     def commit_lookup_sum(self, input_sets: Sequence[object], table_sets: Sequence[object], mult_set: object, n_lookups: int,
@@ -436,18 +443,24 @@ class HipEngine:
         the width concatenated rows of table_sets with the multiplicities of the one-row mult_set (RowSet objects or bare
         handles).  Returns (a one-row RowSet holding S, the closing value as 32 bytes big-endian: 0 when the sum closes).
         theta and beta must be drawn after the commitments of the inputs, the table and the multiplicities are fixed."""
-        ni, hi = self._handle_array(input_sets, "commit_lookup_sum (inputs)")
-        nt, ht = self._handle_array(table_sets, "commit_lookup_sum (table)")
-        _, hm = self._handle_array([mult_set], "commit_lookup_sum (multiplicities)")
+        return self._lookup_sum("commit_lookup_sum", input_sets, table_sets, mult_set, n_lookups, width, theta_be32, beta_be32)
+
+    def _lookup_sum(self, what, input_sets, table_sets, mult_set, n_lookups, width, theta_be32, beta_be32, blind=None, sel=None):
+        """The one body of commit_lookup_sum / _zk / _sel: blind = (usable, tail_be32) for the _zk and _sel forms, sel =
+        (sel_sets, sel_index) for the _sel form."""
+        ni, hi = self._handle_array(input_sets, f"{what} (inputs)")
+        nt, ht = self._handle_array(table_sets, f"{what} (table)")
+        _, hm = self._handle_array([mult_set], f"{what} (multiplicities)")
         if n_lookups < 1 or width < 1 or n_lookups * width > _native.KZG_MAX_BATCH_OPEN or len(theta_be32) != 32 \
                 or len(beta_be32) != 32:
-            raise KzgError(_native.KZG_E_ARG, f"commit_lookup_sum: n_lookups, width >= 1, n_lookups * width <= "
+            raise KzgError(_native.KZG_E_ARG, f"{what}: n_lookups, width >= 1, n_lookups * width <= "
                                               f"{_native.KZG_MAX_BATCH_OPEN}, theta and beta of 32 bytes each")
+        selargs = self._sel_args(what, *sel, n_lookups) if sel else ()
+        extra, wi, T = self._layout_args(what, list(input_sets) + list(table_sets) + [mult_set], blind, sel_usable=bool(sel))
         c, cl, h = ctypes.create_string_buffer(48), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
-        self._chk(self._lib.kzg_rows_commit_lookup_sum(self._h, ni, hi, nt, ht, hm[0], n_lookups, width, theta_be32, beta_be32,
-                                                       c, cl, ctypes.byref(h)))
-        src = next((x for x in list(input_sets) + list(table_sets) + [mult_set] if hasattr(x, "T")), None)
-        return RowSet(self, h.value, getattr(src, "i", None), 1, getattr(src, "T", None), [c.raw]), cl.raw
+        self._chk(getattr(self._lib, "kzg_rows_" + what)(self._h, ni, hi, nt, ht, hm[0], *selargs, n_lookups, width, theta_be32,
+                                                         beta_be32, *extra, c, cl, ctypes.byref(h)))
+        return RowSet(self, h.value, wi, 1, T, [c.raw]), cl.raw
 
     # ---- a fifth set built from sets: the multiplicity row of the lookup argument, joined and committed on the device
     def commit_multiplicities(self, input_sets: Sequence[object], table_sets: Sequence[object], n_lookups: int,
@@ -457,16 +470,21 @@ class HipEngine:
         on its first copy (RowSet objects or bare handles).  Returns (a one-row RowSet holding m, missing): missing is the
         number of cells whose tuple is no table row, 0 when every lookup is satisfied.  No challenge is involved: m is
         committed before theta and beta are drawn."""
-        ni, hi = self._handle_array(input_sets, "commit_multiplicities (inputs)")
-        nt, ht = self._handle_array(table_sets, "commit_multiplicities (table)")
+        return self._multiplicities("commit_multiplicities", input_sets, table_sets, n_lookups, width)
+
+    def _multiplicities(self, what, input_sets, table_sets, n_lookups, width, blind=None, sel=None):
+        """The one body of commit_multiplicities / _zk / _sel: blind and sel as for _lookup_sum."""
+        ni, hi = self._handle_array(input_sets, f"{what} (inputs)")
+        nt, ht = self._handle_array(table_sets, f"{what} (table)")
         if n_lookups < 1 or width < 1 or n_lookups * width > _native.KZG_MAX_BATCH_OPEN:
-            raise KzgError(_native.KZG_E_ARG, f"commit_multiplicities: n_lookups, width >= 1, n_lookups * width <= "
+            raise KzgError(_native.KZG_E_ARG, f"{what}: n_lookups, width >= 1, n_lookups * width <= "
                                               f"{_native.KZG_MAX_BATCH_OPEN}")
+        selargs = self._sel_args(what, *sel, n_lookups) if sel else ()
+        extra, wi, T = self._layout_args(what, list(input_sets) + list(table_sets), blind, sel_usable=bool(sel))
         c, miss, h = ctypes.create_string_buffer(48), ctypes.c_uint64(0), ctypes.c_uint64(0)
-        self._chk(self._lib.kzg_rows_commit_multiplicities(self._h, ni, hi, nt, ht, n_lookups, width, c, ctypes.byref(miss),
-                                                           ctypes.byref(h)))
-        src = next((x for x in list(input_sets) + list(table_sets) if hasattr(x, "T")), None)
-        return RowSet(self, h.value, getattr(src, "i", None), 1, getattr(src, "T", None), [c.raw]), int(miss.value)
+        self._chk(getattr(self._lib, "kzg_rows_" + what)(self._h, ni, hi, nt, ht, *selargs, n_lookups, width, *extra, c,
+                                                         ctypes.byref(miss), ctypes.byref(h)))
+        return RowSet(self, h.value, wi, 1, T, [c.raw]), int(miss.value)
 
     # ---- the three builders above with blinding rows (kzg_rows_commit_*_zk): rows [0, usable) carry the circuit, row `usable`
     # closes the running value, the rows behind take the caller's random tail (T - usable - 1 scalars of 32 bytes)
@@ -486,55 +504,37 @@ class HipEngine:
             raise bad(f"the tail must hold exactly T - usable - 1 = {T - usable - 1} scalars, not {len(tail)}")
         return usable, (b"".join(tail) if tail else None), i, T
 
+    def _layout_args(self, what, sets, blind, sel_usable=False):
+        """((usable, tail) for the native call, worker, T) of a builder over `sets`.  blind = None is the plain form: no extra
+        argument, and bare handles whose row length the engine does not know are accepted (worker and T are None then)."""
+        if blind is None:
+            src = next((x for x in sets if hasattr(x, "T")), None)
+            return (), getattr(src, "i", None), getattr(src, "T", None)
+        usable, tail_be32 = blind
+        usable, tail, wi, T = self._blind_args(what, sets, self._sel_usable(sets, usable) if sel_usable else usable, tail_be32)
+        return (usable, tail), wi, T
+
     def commit_grand_product_zk(self, wire_sets: Sequence[object], sigma_sets: Sequence[object], shifts_be32: Sequence[bytes],
                                 beta_be32: bytes, gamma_be32: bytes, usable: int,
                                 tail_be32: Sequence[bytes] = ()) -> Tuple["RowSet", bytes]:
         """commit_grand_product over the first `usable` rows (kzg_rows_commit_grand_product_zk): z(w^usable) is the closing
         value (1 when the permutation holds on the usable rows), rows usable + 1 .. T - 1 of z are tail_be32.  """
-        nw, hw = self._handle_array(wire_sets, "commit_grand_product_zk (wires)")
-        ns, hs = self._handle_array(sigma_sets, "commit_grand_product_zk (sigmas)")
-        k = len(shifts_be32)
-        if k == 0 or k > _native.KZG_MAX_BATCH_OPEN or any(len(x) != 32 for x in list(shifts_be32) + [beta_be32, gamma_be32]):
-            raise KzgError(_native.KZG_E_ARG, f"commit_grand_product_zk: 1 .. {_native.KZG_MAX_BATCH_OPEN} shifts, beta and "
-                                              "gamma of 32 bytes each")
-        usable, tail, wi, T = self._blind_args("commit_grand_product_zk", list(wire_sets) + list(sigma_sets), usable, tail_be32)
-        c, cl, h = ctypes.create_string_buffer(48), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
-        self._chk(self._lib.kzg_rows_commit_grand_product_zk(self._h, nw, hw, ns, hs, k, b"".join(shifts_be32), beta_be32,
-                                                             gamma_be32, usable, tail, c, cl, ctypes.byref(h)))
-        return RowSet(self, h.value, wi, 1, T, [c.raw]), cl.raw
+        return self._grand_product("commit_grand_product_zk", wire_sets, sigma_sets, shifts_be32, beta_be32, gamma_be32,
+                                   (usable, tail_be32))
 
     def commit_lookup_sum_zk(self, input_sets: Sequence[object], table_sets: Sequence[object], mult_set: object, n_lookups: int,
                              width: int, theta_be32: bytes, beta_be32: bytes, usable: int,
                              tail_be32: Sequence[bytes] = ()) -> Tuple["RowSet", bytes]:
         """commit_lookup_sum over the first `usable` rows (kzg_rows_commit_lookup_sum_zk): S(w^usable) is the closing value
         (0 when the sum closes on the usable rows), rows usable + 1 .. T - 1 of S are tail_be32."""
-        ni, hi = self._handle_array(input_sets, "commit_lookup_sum_zk (inputs)")
-        nt, ht = self._handle_array(table_sets, "commit_lookup_sum_zk (table)")
-        _, hm = self._handle_array([mult_set], "commit_lookup_sum_zk (multiplicities)")
-        if n_lookups < 1 or width < 1 or n_lookups * width > _native.KZG_MAX_BATCH_OPEN or len(theta_be32) != 32 \
-                or len(beta_be32) != 32:
-            raise KzgError(_native.KZG_E_ARG, f"commit_lookup_sum_zk: n_lookups, width >= 1, n_lookups * width <= "
-                                              f"{_native.KZG_MAX_BATCH_OPEN}, theta and beta of 32 bytes each")
-        usable, tail, wi, T = self._blind_args("commit_lookup_sum_zk", list(input_sets) + list(table_sets) + [mult_set], usable, tail_be32)
-        c, cl, h = ctypes.create_string_buffer(48), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
-        self._chk(self._lib.kzg_rows_commit_lookup_sum_zk(self._h, ni, hi, nt, ht, hm[0], n_lookups, width, theta_be32, beta_be32,
-                                                          usable, tail, c, cl, ctypes.byref(h)))
-        return RowSet(self, h.value, wi, 1, T, [c.raw]), cl.raw
+        return self._lookup_sum("commit_lookup_sum_zk", input_sets, table_sets, mult_set, n_lookups, width, theta_be32, beta_be32,
+                                (usable, tail_be32))
 
     def commit_multiplicities_zk(self, input_sets: Sequence[object], table_sets: Sequence[object], n_lookups: int, width: int,
                                  usable: int, tail_be32: Sequence[bytes] = ()) -> Tuple["RowSet", int]:
         """commit_multiplicities over the first `usable` table rows and input cells (kzg_rows_commit_multiplicities_zk):
         m(w^usable) = 0, rows usable + 1 .. T - 1 of m are tail_be32; missing counts usable cells only."""
-        ni, hi = self._handle_array(input_sets, "commit_multiplicities_zk (inputs)")
-        nt, ht = self._handle_array(table_sets, "commit_multiplicities_zk (table)")
-        if n_lookups < 1 or width < 1 or n_lookups * width > _native.KZG_MAX_BATCH_OPEN:
-            raise KzgError(_native.KZG_E_ARG, f"commit_multiplicities_zk: n_lookups, width >= 1, n_lookups * width <= "
-                                              f"{_native.KZG_MAX_BATCH_OPEN}")
-        usable, tail, wi, T = self._blind_args("commit_multiplicities_zk", list(input_sets) + list(table_sets), usable, tail_be32)
-        c, miss, h = ctypes.create_string_buffer(48), ctypes.c_uint64(0), ctypes.c_uint64(0)
-        self._chk(self._lib.kzg_rows_commit_multiplicities_zk(self._h, ni, hi, nt, ht, n_lookups, width, usable, tail, c,
-                                                              ctypes.byref(miss), ctypes.byref(h)))
-        return RowSet(self, h.value, wi, 1, T, [c.raw]), int(miss.value)
+        return self._multiplicities("commit_multiplicities_zk", input_sets, table_sets, n_lookups, width, (usable, tail_be32))
 
     # ---- the two lookup builders with per-row selectors (kzg_rows_commit_*_sel): sel_index[l] is None (no selector) or the
     # index of lookup l's selector row in the concatenated rows of sel_sets; usable = None is the plain layout (no closing row),
@@ -556,20 +556,8 @@ class HipEngine:
         sel_sets (kzg_rows_commit_lookup_sum_sel); None there is the constant 1.  The library does not judge q.  usable =
         None (the plain layout) needs the row length, which RowSet objects carry and the engine remembers for the handles of
         sets committed through it: with bare handles of other origin pass usable = T yourself."""
-        ni, hi = self._handle_array(input_sets, "commit_lookup_sum_sel (inputs)")
-        nt, ht = self._handle_array(table_sets, "commit_lookup_sum_sel (table)")
-        _, hm = self._handle_array([mult_set], "commit_lookup_sum_sel (multiplicities)")
-        if n_lookups < 1 or width < 1 or n_lookups * width > _native.KZG_MAX_BATCH_OPEN or len(theta_be32) != 32 \
-                or len(beta_be32) != 32:
-            raise KzgError(_native.KZG_E_ARG, f"commit_lookup_sum_sel: n_lookups, width >= 1, n_lookups * width <= "
-                                              f"{_native.KZG_MAX_BATCH_OPEN}, theta and beta of 32 bytes each")
-        ns, hs, idx = self._sel_args("commit_lookup_sum_sel", sel_sets, sel_index, n_lookups)
-        sets = list(input_sets) + list(table_sets) + [mult_set]
-        usable, tail, wi, T = self._blind_args("commit_lookup_sum_sel", sets, self._sel_usable(sets, usable), tail_be32)
-        c, cl, h = ctypes.create_string_buffer(48), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
-        self._chk(self._lib.kzg_rows_commit_lookup_sum_sel(self._h, ni, hi, nt, ht, hm[0], ns, hs, idx, n_lookups, width,
-                                                           theta_be32, beta_be32, usable, tail, c, cl, ctypes.byref(h)))
-        return RowSet(self, h.value, wi, 1, T, [c.raw]), cl.raw
+        return self._lookup_sum("commit_lookup_sum_sel", input_sets, table_sets, mult_set, n_lookups, width, theta_be32, beta_be32,
+                                (usable, tail_be32), (sel_sets, sel_index))
 
     def commit_multiplicities_sel(self, input_sets: Sequence[object], table_sets: Sequence[object], sel_sets: Sequence[object],
                                   sel_index: Sequence[Optional[int]], n_lookups: int, width: int, usable: Optional[int] = None,
@@ -577,18 +565,8 @@ class HipEngine:
         """commit_multiplicities / _zk over the cells whose selector is not zero (kzg_rows_commit_multiplicities_sel):
         sel_index[l] names lookup l's selector row in the concatenated rows of sel_sets, None probes every cell.  usable =
         None: as for commit_lookup_sum_sel."""
-        ni, hi = self._handle_array(input_sets, "commit_multiplicities_sel (inputs)")
-        nt, ht = self._handle_array(table_sets, "commit_multiplicities_sel (table)")
-        if n_lookups < 1 or width < 1 or n_lookups * width > _native.KZG_MAX_BATCH_OPEN:
-            raise KzgError(_native.KZG_E_ARG, f"commit_multiplicities_sel: n_lookups, width >= 1, n_lookups * width <= "
-                                              f"{_native.KZG_MAX_BATCH_OPEN}")
-        ns, hs, idx = self._sel_args("commit_multiplicities_sel", sel_sets, sel_index, n_lookups)
-        sets = list(input_sets) + list(table_sets)
-        usable, tail, wi, T = self._blind_args("commit_multiplicities_sel", sets, self._sel_usable(sets, usable), tail_be32)
-        c, miss, h = ctypes.create_string_buffer(48), ctypes.c_uint64(0), ctypes.c_uint64(0)
-        self._chk(self._lib.kzg_rows_commit_multiplicities_sel(self._h, ni, hi, nt, ht, ns, hs, idx, n_lookups, width, usable,
-                                                               tail, c, ctypes.byref(miss), ctypes.byref(h)))
-        return RowSet(self, h.value, wi, 1, T, [c.raw]), int(miss.value)
+        return self._multiplicities("commit_multiplicities_sel", input_sets, table_sets, n_lookups, width, (usable, tail_be32),
+                                    (sel_sets, sel_index))
 
     def _sel_usable(self, sets, usable):
         """usable = None (the plain layout) is the row length, which the native call expects in its place."""
@@ -868,18 +846,8 @@ class HipEngine:
         """commit_grand_product_zk whose z starts at start_be32 instead of 1 (kzg_rows_commit_grand_product_chain): the chunk of
         a chained permutation.  z(w^usable) = start * prod N / prod D is the closing value, the next chunk's start; the tail is
         untouched by start.  start must be canonical and not 0."""
-        nw, hw = self._handle_array(wire_sets, "commit_grand_product_chain (wires)")
-        ns, hs = self._handle_array(sigma_sets, "commit_grand_product_chain (sigmas)")
-        k = len(shifts_be32)
-        if k == 0 or k > _native.KZG_MAX_BATCH_OPEN or \
-                any(len(x) != 32 for x in list(shifts_be32) + [beta_be32, gamma_be32, start_be32]):
-            raise KzgError(_native.KZG_E_ARG, f"commit_grand_product_chain: 1 .. {_native.KZG_MAX_BATCH_OPEN} shifts, beta, "
-                                              "gamma and start of 32 bytes each")
-        usable, tail, wi, T = self._blind_args("commit_grand_product_chain", list(wire_sets) + list(sigma_sets), usable, tail_be32)
-        c, cl, h = ctypes.create_string_buffer(48), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
-        self._chk(self._lib.kzg_rows_commit_grand_product_chain(self._h, nw, hw, ns, hs, k, b"".join(shifts_be32), beta_be32,
-                                                                gamma_be32, usable, tail, start_be32, c, cl, ctypes.byref(h)))
-        return RowSet(self, h.value, wi, 1, T, [c.raw]), cl.raw
+        return self._grand_product("commit_grand_product_chain", wire_sets, sigma_sets, shifts_be32, beta_be32, gamma_be32,
+                                   (usable, tail_be32), start_be32)
 
     def _handle_array(self, sets, what):
         handles = [int(getattr(x, "handle", x)) for x in sets]

@@ -120,204 +120,124 @@ class MultiDeviceClient:
             return None
         return owners.pop() if len(owners) == 1 else None
 
-    def worker_open_rows(self, handles: Sequence[int], points, opened, gammas):
-        i = self._owner(handles)
+    _ONE_WORKER = "the handles must name live sets of one worker"
+
+    def _routed_builder(self, name: str, groups, *args, key: Optional[str] = "handle", forget=None, why: str = _ONE_WORKER):
+        """Client call `name`(*args) on the device that owns every handle of `groups` (handle lists, read here so that a
+        malformed one is the 400 of an unknown one); 400 `why` when no one worker owns them.  On success the new handle
+        answered under `key` is recorded for that worker (None: the call makes none) and `forget` is dropped (key=None,
+        forget=h is the release form; a finish forgets the accumulator and records the new set)."""
+        try:
+            i = self._owner([h for g in groups for h in g])
+        except TypeError:
+            i = None
         if i is None:
-            return Response(400, {"error": "worker_open_rows: the handles must name live sets of one worker"})
-        return self._for(i).worker_open_rows(handles, points, opened, gammas)
+            return Response(400, {"error": f"{name}: {why}"})
+        r = getattr(self._for(i), name)(*args)
+        if r.status_code == 200:
+            if forget is not None:
+                self._row_owner.pop(int(forget), None)
+            if key is not None:
+                self._row_owner[int(r.json()[key])] = i
+        return r
+
+    def worker_open_rows(self, handles: Sequence[int], points, opened, gammas):
+        return self._routed_builder("worker_open_rows", [handles], handles, points, opened, gammas, key=None)
 
     def worker_eval_rows(self, handles: Sequence[int], points, opened):
-        i = self._owner(handles)
-        if i is None:
-            return Response(400, {"error": "worker_eval_rows: the handles must name live sets of one worker"})
-        return self._for(i).worker_eval_rows(handles, points, opened)
+        return self._routed_builder("worker_eval_rows", [handles], handles, points, opened, key=None)
 
     def worker_open_rows_lincomb(self, handles: Sequence[int], points, coeffs):
-        i = self._owner(handles)
-        if i is None:
-            return Response(400, {"error": "worker_open_rows_lincomb: the handles must name live sets of one worker"})
-        return self._for(i).worker_open_rows_lincomb(handles, points, coeffs)
+        return self._routed_builder("worker_open_rows_lincomb", [handles], handles, points, coeffs, key=None)
 
     def worker_commit_shplonk(self, handles: Sequence[int], points, opened, coeffs):
-        try:
-            i = self._owner(handles)
-        except TypeError:
-            i = None
-        if i is None:
-            return Response(400, {"error": "worker_commit_shplonk: the handles must name live sets of one worker"})
-        r = self._for(i).worker_commit_shplonk(handles, points, opened, coeffs)
-        if r.status_code == 200:
-            self._row_owner[int(r.json()["handle"])] = i
-        return r
+        return self._routed_builder("worker_commit_shplonk", [handles], handles, points, opened, coeffs)
 
     def worker_open_shplonk_finish(self, handles: Sequence[int], h_handle: int, points, opened, coeffs, u):
-        try:
-            i = self._owner(list(handles) + [h_handle])
-        except TypeError:
-            i = None
-        if i is None:
-            return Response(400, {"error": "worker_open_shplonk_finish: the handles must name live sets of one worker"})
-        return self._for(i).worker_open_shplonk_finish(handles, h_handle, points, opened, coeffs, u)
+        return self._routed_builder("worker_open_shplonk_finish", [handles, [h_handle]], handles, h_handle, points, opened,
+                                    coeffs, u, key=None)
 
     def worker_commit_grand_product(self, wire_handles: Sequence[int], sigma_handles: Sequence[int], shifts, beta, gamma):
-        try:
-            i = self._owner(list(wire_handles) + list(sigma_handles))
-        except TypeError:
-            i = None
-        if i is None:
-            return Response(400, {"error": "worker_commit_grand_product: the handles must name live sets of one worker"})
-        r = self._for(i).worker_commit_grand_product(wire_handles, sigma_handles, shifts, beta, gamma)
-        if r.status_code == 200:
-            self._row_owner[int(r.json()["handle"])] = i
-        return r
+        return self._routed_builder("worker_commit_grand_product", [wire_handles, sigma_handles], wire_handles, sigma_handles,
+                                    shifts, beta, gamma)
 
     def worker_commit_lookup_sum(self, input_handles: Sequence[int], table_handles: Sequence[int], mult_handle: int,
                                  n_lookups, width, theta, beta):
-        try:
-            i = self._owner(list(input_handles) + list(table_handles) + [mult_handle])
-        except TypeError:
-            i = None
-        if i is None:
-            return Response(400, {"error": "worker_commit_lookup_sum: the handles must name live sets of one worker"})
-        r = self._for(i).worker_commit_lookup_sum(input_handles, table_handles, mult_handle, n_lookups, width, theta, beta)
-        if r.status_code == 200:
-            self._row_owner[int(r.json()["handle"])] = i
-        return r
+        return self._routed_builder("worker_commit_lookup_sum", [input_handles, table_handles, [mult_handle]], input_handles,
+                                    table_handles, mult_handle, n_lookups, width, theta, beta)
 
     def worker_commit_multiplicities(self, input_handles: Sequence[int], table_handles: Sequence[int], n_lookups, width):
-        try:
-            i = self._owner(list(input_handles) + list(table_handles))
-        except TypeError:
-            i = None
-        if i is None:
-            return Response(400, {"error": "worker_commit_multiplicities: the handles must name live sets of one worker"})
-        r = self._for(i).worker_commit_multiplicities(input_handles, table_handles, n_lookups, width)
-        if r.status_code == 200:
-            self._row_owner[int(r.json()["handle"])] = i
-        return r
+        return self._routed_builder("worker_commit_multiplicities", [input_handles, table_handles], input_handles,
+                                    table_handles, n_lookups, width)
 
     def worker_commit_quotient(self, handles: Sequence[int], terms, perm=None, ext_log=2, n_pieces=3):
-        i = self._owner(handles)
-        if i is None:
-            return Response(400, {"error": "worker_commit_quotient: the handles must name live sets of one worker"})
-        r = self._for(i).worker_commit_quotient(handles, terms, perm, ext_log, n_pieces)
-        if r.status_code == 200:
-            self._row_owner[int(r.json()["handle"])] = i
-        return r
+        return self._routed_builder("worker_commit_quotient", [handles], handles, terms, perm, ext_log, n_pieces)
 
     def worker_commit_quotient_ext(self, handles: Sequence[int], terms, perm=None, lookup=None, ext_log=2, n_pieces=3):
-        i = self._owner(handles)
-        if i is None:
-            return Response(400, {"error": "worker_commit_quotient_ext: the handles must name live sets of one worker"})
-        r = self._for(i).worker_commit_quotient_ext(handles, terms, perm, lookup, ext_log, n_pieces)
-        if r.status_code == 200:
-            self._row_owner[int(r.json()["handle"])] = i
-        return r
+        return self._routed_builder("worker_commit_quotient_ext", [handles], handles, terms, perm, lookup, ext_log, n_pieces)
 
-    # the builders with blinding rows: routed like the plain ones
-    def _routed_builder(self, name: str, handles, *args):
-        try:
-            i = self._owner(list(handles))
-        except TypeError:
-            i = None
-        if i is None:
-            return Response(400, {"error": f"{name}: the handles must name live sets of one worker"})
-        r = getattr(self._for(i), name)(*args)
-        if r.status_code == 200:
-            self._row_owner[int(r.json()["handle"])] = i
-        return r
-
+    # the builders with blinding rows, selectors, parts and chains: routed like the plain ones
     def worker_commit_grand_product_zk(self, wire_handles: Sequence[int], sigma_handles: Sequence[int], shifts, beta, gamma,
                                        usable, tail):
-        return self._routed_builder("worker_commit_grand_product_zk", list(wire_handles) + list(sigma_handles), wire_handles,
+        return self._routed_builder("worker_commit_grand_product_zk", [wire_handles, sigma_handles], wire_handles,
                                     sigma_handles, shifts, beta, gamma, usable, tail)
 
     def worker_commit_lookup_sum_zk(self, input_handles: Sequence[int], table_handles: Sequence[int], mult_handle: int,
                                     n_lookups, width, theta, beta, usable, tail):
-        return self._routed_builder("worker_commit_lookup_sum_zk", list(input_handles) + list(table_handles) + [mult_handle],
+        return self._routed_builder("worker_commit_lookup_sum_zk", [input_handles, table_handles, [mult_handle]],
                                     input_handles, table_handles, mult_handle, n_lookups, width, theta, beta, usable, tail)
 
     def worker_commit_multiplicities_zk(self, input_handles: Sequence[int], table_handles: Sequence[int], n_lookups, width,
                                         usable, tail):
-        return self._routed_builder("worker_commit_multiplicities_zk", list(input_handles) + list(table_handles), input_handles,
+        return self._routed_builder("worker_commit_multiplicities_zk", [input_handles, table_handles], input_handles,
                                     table_handles, n_lookups, width, usable, tail)
 
     def worker_commit_lookup_sum_sel(self, input_handles: Sequence[int], table_handles: Sequence[int], mult_handle: int,
                                      sel_handles, sel_index, n_lookups, width, theta, beta, usable=None, tail=()):
         return self._routed_builder("worker_commit_lookup_sum_sel",
-                                    list(input_handles) + list(table_handles) + [mult_handle] + list(sel_handles or []),
-                                    input_handles, table_handles, mult_handle, sel_handles, sel_index, n_lookups, width, theta,
-                                    beta, usable, tail)
+                                    [input_handles, table_handles, [mult_handle], sel_handles or []], input_handles,
+                                    table_handles, mult_handle, sel_handles, sel_index, n_lookups, width, theta, beta, usable, tail)
 
     def worker_commit_multiplicities_sel(self, input_handles: Sequence[int], table_handles: Sequence[int], sel_handles, sel_index,
                                          n_lookups, width, usable=None, tail=()):
-        return self._routed_builder("worker_commit_multiplicities_sel",
-                                    list(input_handles) + list(table_handles) + list(sel_handles or []), input_handles,
-                                    table_handles, sel_handles, sel_index, n_lookups, width, usable, tail)
+        return self._routed_builder("worker_commit_multiplicities_sel", [input_handles, table_handles, sel_handles or []],
+                                    input_handles, table_handles, sel_handles, sel_index, n_lookups, width, usable, tail)
 
     def worker_commit_quotient_zk(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None, ext_log=2,
                                   n_pieces=3):
-        return self._routed_builder("worker_commit_quotient_zk", handles, handles, terms, perm, lookup, active_row, ext_log,
+        return self._routed_builder("worker_commit_quotient_zk", [handles], handles, terms, perm, lookup, active_row, ext_log,
                                     n_pieces)
 
     def worker_commit_quotient_sel(self, handles: Sequence[int], terms, perm=None, lookup=None, selectors=None, active_row=None,
                                    ext_log=2, n_pieces=3):
-        return self._routed_builder("worker_commit_quotient_sel", handles, handles, terms, perm, lookup, selectors, active_row,
-                                    ext_log, n_pieces)
+        return self._routed_builder("worker_commit_quotient_sel", [handles], handles, terms, perm, lookup, selectors,
+                                    active_row, ext_log, n_pieces)
+
+    _PART_ONE_WORKER = "the handles and the accumulator must be live and of one worker"
 
     def worker_quotient_part_sel(self, handles: Sequence[int], terms, perm=None, lookup=None, selectors=None, active_row=None,
                                  link=None, ext_log=2, scale=None, acc=None):
-        try:
-            i = self._owner(list(handles) + ([acc] if acc is not None else []))
-        except TypeError:
-            i = None
-        if i is None:
-            return Response(400, {"error": "worker_quotient_part_sel: the handles and the accumulator must be live and of one "
-                                           "worker"})
-        r = self._for(i).worker_quotient_part_sel(handles, terms, perm, lookup, selectors, active_row, link, ext_log, scale, acc)
-        if r.status_code == 200:
-            self._row_owner[int(r.json()["acc"])] = i
-        return r
+        return self._routed_builder("worker_quotient_part_sel", [handles, [] if acc is None else [acc]], handles, terms, perm,
+                                    lookup, selectors, active_row, link, ext_log, scale, acc, key="acc",
+                                    why=self._PART_ONE_WORKER)
 
     def worker_quotient_part(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None, link=None, ext_log=2,
                              scale=None, acc=None):
-        try:
-            i = self._owner(list(handles) + ([acc] if acc is not None else []))
-        except TypeError:
-            i = None
-        if i is None:
-            return Response(400, {"error": "worker_quotient_part: the handles and the accumulator must be live and of one worker"})
-        r = self._for(i).worker_quotient_part(handles, terms, perm, lookup, active_row, link, ext_log, scale, acc)
-        if r.status_code == 200:
-            self._row_owner[int(r.json()["acc"])] = i
-        return r
+        return self._routed_builder("worker_quotient_part", [handles, [] if acc is None else [acc]], handles, terms, perm,
+                                    lookup, active_row, link, ext_log, scale, acc, key="acc", why=self._PART_ONE_WORKER)
 
     def worker_quotient_finish(self, acc: int, n_pieces=3):
-        try:
-            i = self._owner([acc])
-        except TypeError:
-            i = None
-        if i is None:
-            return Response(400, {"error": "worker_quotient_finish: unknown accumulator handle"})
-        r = self._for(i).worker_quotient_finish(acc, n_pieces)
-        if r.status_code == 200:
-            self._row_owner.pop(int(acc), None)
-            self._row_owner[int(r.json()["handle"])] = i
-        return r
+        return self._routed_builder("worker_quotient_finish", [[acc]], acc, n_pieces, forget=acc,
+                                    why="unknown accumulator handle")
 
     def worker_commit_grand_product_chain(self, wire_handles: Sequence[int], sigma_handles: Sequence[int], shifts, beta, gamma,
                                           usable, tail, start):
-        return self._routed_builder("worker_commit_grand_product_chain", list(wire_handles) + list(sigma_handles), wire_handles,
+        return self._routed_builder("worker_commit_grand_product_chain", [wire_handles, sigma_handles], wire_handles,
                                     sigma_handles, shifts, beta, gamma, usable, tail, start)
 
     def worker_release_rows(self, handle: int):
-        i = self._owner([handle])
-        if i is None:
-            return Response(400, {"error": "worker_release_rows: unknown row-set handle"})
-        r = self._for(i).worker_release_rows(handle)
-        if r.status_code == 200:
-            self._row_owner.pop(int(handle), None)
-        return r
+        return self._routed_builder("worker_release_rows", [[handle]], handle, key=None, forget=handle,
+                                    why="unknown row-set handle")
 
     def commit_and_open_rows(self, indices: Sequence[int], polys: Sequence[Sequence[str]], x: str) -> List[Response]:
         """Pianist rows of one challenge, all devices at once: row k runs on the device of indices[k]; responses in input
