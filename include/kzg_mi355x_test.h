@@ -22,6 +22,24 @@ int kzg_test_g1(kzg_ctx* ctx, int op /*0 a+b mixed,1 2a+b full,2 2a,3 4a,4 a+20a
                                          6 4a, 7 ten rounds r <- 2r+b from a*/, const uint8_t* a_be96,
                 const uint8_t* b_be96, uint8_t* out_be96, uint64_t n);
 
+/* ---- raw-limb hooks (tests/test_gpu_fp_classes.py, reference tests/fp28_ref.py): operands and results are the working limbs
+ * themselves -- 14 words of 28 bits per Fp element (field 0), 9 words of 29 bits per Fr element (field 1) -- with no conversion, no
+ * Montgomery entry or exit and no canonicalisation beyond what the operation does itself, so that a test can place every operand on
+ * the bounds of its representation class.  An operand that the operation does not read may be NULL.
+ *   field 0: 0 fp_mul(a, b), 1 fp_mul_inline, 2 fp_sqr(a), 3 fp_sqr_inline, 4 fp_mul2_inline(a, b, c, d), 5 / 6 / 7 fp_sub4 / fp_sub8 /
+ *            fp_sub16(a, b) then fp_norm, 8 fp_neg8(a), 9 fp_canon, 10 fp_canon_mont, 11 fp_neg_canon, 12 fp_is_zero_n (the answer in
+ *            limb 0, the other limbs zero); lane-parallel, four elements per wave, one per DPP row: 13 lp_mul(a, b), 14 lp_norm of the
+ *            14 lane values a (low words) | b (high words) << 32
+ *   field 1: 0 fr9_mul(a lazy, b), 1 fr9_sub4(a, b), 2 fr9_sub8(a, b) (both as they leave, not normalised), 3 fr9_norm(a),
+ *            4 fr9_reduce(a), 5 fr9_reduce_approx(a) */
+int kzg_test_fp_raw(kzg_ctx* ctx, int field, int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d,
+                    uint32_t* out, uint64_t n);
+/* points on raw XYZZ coordinates: 4 x 14 words per operand (X, Y, ZZ, ZZZ; all zero = infinity); the mixed additions read b's first
+ * 28 words as the canonical affine x, y.  The result is the affine point, 96 big-endian bytes (zeros = infinity).
+ *   0 g1_add<false>, 1 g1_add<true> (inlined products, paired reduction), 2 g1_madd<false>, 3 g1_madd<true>, 4 g1_dbl(a),
+ *   5 lp_add, 6 lp_dbl(a) (one wave per element) */
+int kzg_test_g1_raw(kzg_ctx* ctx, int op, const uint32_t* a_xyzz, const uint32_t* b_xyzz, uint8_t* out_be96, uint64_t n);
+
 /* the host encoder itself (no GPU): 4 x 14 limbs of 28 bits (X, Y, ZZ, ZZZ; lazy limbs < 2^32; residues with
  * R = 2^392) -> 48-byte compressed point / 192-byte partial record.  Test hooks. */
 int kzg_host_xyzz_to_c48(const uint32_t xyzz_limbs28[56], uint8_t out48[48]);

@@ -27,6 +27,19 @@ def value(l):
     return sum(x << (28 * i) for i, x in enumerate(l))
 
 
+def lp_norm(t):
+    """16 lane values (lanes 14 / 15 zero) -> (the same value with lanes 0..12 < 2^28, the number of carry rounds)"""
+    rounds = 0
+    while any(x > MASK for x in t[:13]):
+        hi = [x >> 28 for x in t]
+        lo = [x & MASK for x in t]
+        hi_dn = [0] + hi[:-1]                            # row_shr:1 (lane j <- lane j-1)
+        t = [(lo[j] if j < 13 else t[j]) + (hi_dn[j] if j <= 13 else 0) for j in range(16)]
+        # lane 13 keeps its whole value (top limb holds the excess) and adds the carry of lane 12
+        rounds += 1
+    return t, rounds
+
+
 def lp_mul(a, b, stats):
     """a, b: 16 lanes (limb j in lane j, lanes 14/15 zero), limbs < 2^30 (loose).  Returns 16 lanes, limbs < 2^28 except
     the top one, value = a*b/R + (something) * p < 2p."""
@@ -45,14 +58,7 @@ def lp_mul(a, b, stats):
         t = [hi[j] + lo_up[j] for j in range(16)]        # 64-bit add
     # lanes 0..13 now hold columns 14..27 (each < 2^37); lanes 14, 15 hold zero
     assert t[14] == 0 and t[15] == 0
-    rounds = 0
-    while any(x > MASK for x in t[:13]):
-        hi = [x >> 28 for x in t]
-        lo = [x & MASK for x in t]
-        hi_dn = [0] + hi[:-1]                            # row_shr:1 (lane j <- lane j-1)
-        t = [(lo[j] if j < 13 else t[j]) + (hi_dn[j] if j <= 13 else 0) for j in range(16)]
-        # lane 13 keeps its whole value (top limb holds the excess) and adds the carry of lane 12
-        rounds += 1
+    t, rounds = lp_norm(t)
     stats["max_rounds"] = max(stats["max_rounds"], rounds)
     stats["rounds_hist"][rounds] = stats["rounds_hist"].get(rounds, 0) + 1
     return t

@@ -271,6 +271,8 @@ SYMBOLS = {
     "kzg_b64_encode_fr": (_I, [_B, _U64, _B]),
     "kzg_test_field": (_I, [_P, _I, _I, _B, _B, _B, _U64]),
     "kzg_test_g1": (_I, [_P, _I, _B, _B, _B, _U64]),
+    "kzg_test_fp_raw": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _U64]),
+    "kzg_test_g1_raw": (_I, [_P, _I, _P, _P, _B, _U64]),
 }
 
 _lib = None

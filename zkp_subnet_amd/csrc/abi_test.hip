@@ -143,6 +143,120 @@ __global__ void __launch_bounds__(64) k_test_g1_lp(int op, const uint8_t* a_be, 
     }
 }
 
+// ---- raw-limb test kernels (kzg_test_fp_raw / kzg_test_g1_raw): limbs in as they are, limbs out as they are -- no conversion,
+// no Montgomery entry or exit, no canonicalisation beyond what the operation under test does itself, so that tests/ can put every
+// operand on the bounds of its representation class (tests/fp28_ref.py) and compare every output limb
+KZG_DEV void fp_ld_raw(fp_t& r, const uint32_t* p) {
+#pragma unroll
+    for (int i = 0; i < 14; i++) r.l[i] = p[i];
+}
+template <int OP>
+__global__ void __launch_bounds__(256) k_test_fp_raw(const uint32_t* a_l, const uint32_t* b_l, const uint32_t* c_l,
+                                                      const uint32_t* d_l, uint32_t* out, uint64_t n) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    fp_t a, b, r;
+    fp_ld_raw(a, a_l + 14 * j);
+    fp_ld_raw(b, b_l + 14 * j);
+    if constexpr (OP == 0) fp_mul(r, a, b);
+    else if constexpr (OP == 1) fp_mul_inline(r, a, b);
+    else if constexpr (OP == 2) fp_sqr(r, a);
+    else if constexpr (OP == 3) fp_sqr_inline(r, a);
+    else if constexpr (OP == 4) {
+        fp_t c, d;
+        fp_ld_raw(c, c_l + 14 * j);
+        fp_ld_raw(d, d_l + 14 * j);
+        fp_mul2_inline(r, a, b, c, d);
+    }
+    else if constexpr (OP == 5) { fp_sub4(r, a, b); fp_norm(r, r); }
+    else if constexpr (OP == 6) { fp_sub8(r, a, b); fp_norm(r, r); }
+    else if constexpr (OP == 7) { fp_sub16(r, a, b); fp_norm(r, r); }
+    else if constexpr (OP == 8) fp_neg8(r, a);
+    else if constexpr (OP == 9) fp_canon(r, a);
+    else if constexpr (OP == 10) fp_canon_mont(r, a);
+    else if constexpr (OP == 11) fp_neg_canon(r, a);
+    else {
+        fp_zero(r);
+        r.l[0] = fp_is_zero_n(a) ? 1u : 0u;
+    }
+#pragma unroll
+    for (int i = 0; i < 14; i++) out[14 * j + i] = r.l[i];
+}
+// lane-parallel forms: four independent elements per wave, one per DPP row (element 4 * block + row); rows past n run on zeros.
+// op 13 = lp_mul, 14 = lp_norm on the 64-bit lane values a (low words) | b (high words) << 32
+__global__ void __launch_bounds__(64) k_test_lp_raw(int op, const uint32_t* a_l, const uint32_t* b_l, uint32_t* out, uint64_t n) {
+    const LpLane k = lp_lane();
+    const uint64_t e = 4ull * blockIdx.x + k.row;
+    const bool live = e < n && k.j < 14;
+    const uint32_t x = live ? a_l[14 * e + k.j] : 0u, y = live ? b_l[14 * e + k.j] : 0u;
+    const uint32_t r = op == 13 ? lp_mul(x, y, k) : lp_norm((uint64_t)x | ((uint64_t)y << 32), k);
+    if (live) out[14 * e + k.j] = r;
+}
+__global__ void __launch_bounds__(256) k_test_fr_raw(int op, const uint32_t* a_l, const uint32_t* b_l, uint32_t* out, uint64_t n) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    fr9_t a, b, r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) { a.l[i] = a_l[9 * j + i]; b.l[i] = b_l[9 * j + i]; }
+    if (op == 0) fr9_mul(r, a, b);
+    else if (op == 1) fr9_sub4(r, a, b);
+    else if (op == 2) fr9_sub8(r, a, b);
+    else if (op == 3) fr9_norm(r, a);
+    else if (op == 4) fr9_reduce(r, a);
+    else fr9_reduce_approx(r, a);
+#pragma unroll
+    for (int i = 0; i < 9; i++) out[9 * j + i] = r.l[i];
+}
+// points on raw XYZZ limbs (4 x 14 words per operand; the mixed additions read b's first 28 words as the affine x, y); the result
+// leaves as the affine point, 96 big-endian bytes.  OP 0 / 1 = g1_add<false / true>, 2 / 3 = g1_madd<false / true>, 4 = g1_dbl
+KZG_DEV void xyzz_ld_raw(g1_xyzz_t& p, const uint32_t* w) {
+    fp_ld_raw(p.x, w); fp_ld_raw(p.y, w + 14); fp_ld_raw(p.zz, w + 28); fp_ld_raw(p.zzz, w + 42);
+}
+template <int OP>
+__global__ void __launch_bounds__(64) k_test_g1_raw(const uint32_t* a_l, const uint32_t* b_l, uint8_t* out_be, uint64_t n) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    g1_xyzz_t pa, pb, r;
+    xyzz_ld_raw(pa, a_l + 56 * j);
+    xyzz_ld_raw(pb, b_l + 56 * j);
+    if constexpr (OP == 0) g1_add<false>(r, pa, pb);
+    else if constexpr (OP == 1) g1_add<true>(r, pa, pb);
+    else if constexpr (OP == 2 || OP == 3) {
+        g1_aff28 q;
+        q.x = pb.x; q.y = pb.y;
+        r = pa;
+        g1_madd_checked<OP == 3>(r, q);
+    }
+    else g1_dbl(r, pa);
+    g1_aff28 o;
+    g1_to_aff(o, r);
+    fp_to_be48(out_be + 96 * j, o.x);
+    fp_to_be48(out_be + 96 * j + 48, o.y);
+}
+// op 5 = lp_add, 6 = lp_dbl: one wave per element
+__global__ void __launch_bounds__(64) k_test_g1_lp_raw(int op, const uint32_t* a_l, const uint32_t* b_l, uint8_t* out_be) {
+    __shared__ LpScratch sm;
+    __shared__ g1_xyzz_t pa, pb, r;
+    const uint64_t j = blockIdx.x;
+    const LpLane k = lp_lane();
+    if (threadIdx.x < 56) {
+        reinterpret_cast<uint32_t*>(&pa)[threadIdx.x] = a_l[56 * j + threadIdx.x];
+        reinterpret_cast<uint32_t*>(&pb)[threadIdx.x] = b_l[56 * j + threadIdx.x];
+    }
+    __syncthreads();
+    if (op == 5) lp_add(sm, &r, &pa, &pb, k);
+    else lp_dbl(sm, &r, &pa, k);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        g1_xyzz_t v;
+        load_xyzz(v, &r);
+        g1_aff28 o;
+        g1_to_aff(o, v);
+        fp_to_be48(out_be + 96 * j, o.x);
+        fp_to_be48(out_be + 96 * j + 48, o.y);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -233,6 +347,72 @@ int kzg_test_g1(kzg_ctx* ctx, int op, const uint8_t* a_be96, const uint8_t* b_be
     if (op >= 5) k_test_g1_lp<<<(uint32_t)n, 64, 0, L.stream>>>(op, da, db, L.out_be.as<uint8_t>());
     else k_test_g1<<<(uint32_t)((n + 255) / 256), 256, 0, L.stream>>>(op, da, db, L.out_be.as<uint8_t>(), n);
     HIPCHK(ctx, hipMemcpyAsync(out_be96, L.out_be.p, n * 96, hipMemcpyDeviceToHost, L.stream));
+    HIPCHK(ctx, hipStreamSynchronize(L.stream));
+    HIPCHK(ctx, hipGetLastError());
+    H.clean = true;
+    return KZG_OK;
+}
+
+#define KZG_RAW_MAX_N (1ull << 22)   // elements per raw-hook call (tests pass a few thousand)
+int kzg_test_fp_raw(kzg_ctx* ctx, int field, int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d,
+                    uint32_t* out, uint64_t n) {
+    if (!ctx || !a || !out || !n || n > KZG_RAW_MAX_N || (field != 0 && field != 1) || op < 0 || op > (field == 0 ? 14 : 5))
+        return KZG_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;
+    Lane& L = H.L();
+    const size_t bytes = n * (field == 0 ? 14 : 9) * sizeof(uint32_t);
+    HIPCHK(ctx, L.in_be.ensure(4 * bytes));
+    HIPCHK(ctx, L.out_be.ensure(bytes));
+    const uint32_t* src[4] = {a, b ? b : a, c ? c : a, d ? d : a};     // an operand the operation does not read may be NULL
+    uint32_t* dv[4];
+    for (int i = 0; i < 4; i++) {
+        dv[i] = reinterpret_cast<uint32_t*>(L.in_be.as<uint8_t>() + i * bytes);
+        HIPCHK(ctx, hipMemcpyAsync(dv[i], src[i], bytes, hipMemcpyHostToDevice, L.stream));
+    }
+    uint32_t* dout = L.out_be.as<uint32_t>();
+    const uint32_t blocks = (uint32_t)((n + 255) / 256);
+    if (field == 1) k_test_fr_raw<<<blocks, 256, 0, L.stream>>>(op, dv[0], dv[1], dout, n);
+    else if (op >= 13) k_test_lp_raw<<<(uint32_t)((n + 3) / 4), 64, 0, L.stream>>>(op, dv[0], dv[1], dout, n);
+    else {
+        switch (op) {
+#define FP_RAW_CASE(OP) case OP: k_test_fp_raw<OP><<<blocks, 256, 0, L.stream>>>(dv[0], dv[1], dv[2], dv[3], dout, n); break;
+            FP_RAW_CASE(0) FP_RAW_CASE(1) FP_RAW_CASE(2) FP_RAW_CASE(3) FP_RAW_CASE(4) FP_RAW_CASE(5) FP_RAW_CASE(6)
+            FP_RAW_CASE(7) FP_RAW_CASE(8) FP_RAW_CASE(9) FP_RAW_CASE(10) FP_RAW_CASE(11) FP_RAW_CASE(12)
+#undef FP_RAW_CASE
+        }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, L.stream));
+    HIPCHK(ctx, hipStreamSynchronize(L.stream));
+    HIPCHK(ctx, hipGetLastError());
+    H.clean = true;
+    return KZG_OK;
+}
+int kzg_test_g1_raw(kzg_ctx* ctx, int op, const uint32_t* a_xyzz, const uint32_t* b_xyzz, uint8_t* out_be96, uint64_t n) {
+    if (!ctx || !a_xyzz || !out_be96 || !n || n > KZG_RAW_MAX_N || op < 0 || op > 6) return KZG_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;
+    Lane& L = H.L();
+    const size_t bytes = n * 56 * sizeof(uint32_t);
+    HIPCHK(ctx, L.in_be.ensure(2 * bytes));
+    HIPCHK(ctx, L.out_be.ensure(n * 96));
+    uint32_t* da = L.in_be.as<uint32_t>();
+    uint32_t* db = da + n * 56;
+    HIPCHK(ctx, hipMemcpyAsync(da, a_xyzz, bytes, hipMemcpyHostToDevice, L.stream));
+    HIPCHK(ctx, hipMemcpyAsync(db, b_xyzz ? b_xyzz : a_xyzz, bytes, hipMemcpyHostToDevice, L.stream));   // the doublings read no b
+    uint8_t* dout = L.out_be.as<uint8_t>();
+    const uint32_t blocks = (uint32_t)((n + 63) / 64);
+    switch (op) {
+        case 0: k_test_g1_raw<0><<<blocks, 64, 0, L.stream>>>(da, db, dout, n); break;
+        case 1: k_test_g1_raw<1><<<blocks, 64, 0, L.stream>>>(da, db, dout, n); break;
+        case 2: k_test_g1_raw<2><<<blocks, 64, 0, L.stream>>>(da, db, dout, n); break;
+        case 3: k_test_g1_raw<3><<<blocks, 64, 0, L.stream>>>(da, db, dout, n); break;
+        case 4: k_test_g1_raw<4><<<blocks, 64, 0, L.stream>>>(da, db, dout, n); break;
+        default: k_test_g1_lp_raw<<<(uint32_t)n, 64, 0, L.stream>>>(op, da, db, dout); break;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(out_be96, dout, n * 96, hipMemcpyDeviceToHost, L.stream));
     HIPCHK(ctx, hipStreamSynchronize(L.stream));
     HIPCHK(ctx, hipGetLastError());
     H.clean = true;

@@ -50,6 +50,10 @@ KZG_DEV void fr9_sub4(fr9_t& r, const fr9_t& a, const fr9_t& b) {   // b normali
 #pragma unroll
     for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + (fr9_m4(i) - b.l[i]);
 }
+KZG_DEV void fr9_sub8(fr9_t& r, const fr9_t& a, const fr9_t& b) {   // b normalised, < 6r; value grows by 8r
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + (fr9_m8(i) - b.l[i]);
+}
 // carry propagation: same value, limbs 0..7 < 2^29
 KZG_DEV void fr9_norm(fr9_t& r, const fr9_t& a) {
     uint32_t c = 0;

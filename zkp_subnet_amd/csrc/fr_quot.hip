@@ -220,11 +220,6 @@ KZG_DEV void lds_get(fr9_t& v, const uint32_t (*cst)[9], uint32_t j) {
 #pragma unroll
     for (int i = 0; i < 9; i++) v.l[i] = cst[j][i];
 }
-// fr9_sub4 for a subtrahend below 6r (normalised): the value grows by 8r
-KZG_DEV void fr9_sub8(fr9_t& r, const fr9_t& a, const fr9_t& b) {
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + (fr9_m8(i) - b.l[i]);
-}
 // beta + sum_c theta^c f_c(x_i) over the w rows named by `rows`, Horner from the last column down: w - 1 products.  Every
 // step is (a product, < 2r) + (a canonical row value, < r) < 3r with limbs < 2^30, a legal first operand of the next; the sum
 // with beta stays below 4r (limbs < 2^31) and is normalised: a legal SECOND operand for a first one below 17r.

@@ -1213,6 +1213,39 @@ class HipEngine:
         self._chk(self._lib.kzg_test_g1(self._h, op, a_be96, b_be96, out, len(a_be96) // 96))
         return out.raw
 
+    def test_fp_raw(self, field: int, op: int, *operands) -> List[List[int]]:
+        """One field operation on raw working limbs (kzg_test_fp_raw): up to four operands, each a list of n elements of 14
+        (field 0, Fp) or 9 (field 1, Fr) limbs; the n results, limbs as they leave the operation."""
+        w = 14 if field == 0 else 9
+        n = len(operands[0])
+        arrs = []
+        for elems in operands:
+            flat = [x for e in elems for x in e]
+            if len(elems) != n or len(flat) != n * w:
+                raise ValueError(f"raw operands must be {n} elements of {w} limbs")
+            arrs.append((ctypes.c_uint32 * (n * w))(*flat))
+        arrs += [None] * (4 - len(arrs))
+        out = (ctypes.c_uint32 * (n * w))()
+        self._chk(self._lib.kzg_test_fp_raw(self._h, field, op, *arrs, out, n))
+        out = list(out)
+        return [out[w * j:w * j + w] for j in range(n)]
+
+    def test_g1_raw(self, op: int, a_xyzz: List[List[int]], b_xyzz: List[List[int]] = None) -> bytes:
+        """One point operation on raw XYZZ limbs (kzg_test_g1_raw): n operands of 56 limbs each; n affine points x 96 bytes."""
+        n = len(a_xyzz)
+        arrs = []
+        for pts in (a_xyzz, b_xyzz):
+            if pts is None:
+                arrs.append(None)
+                continue
+            flat = [x for e in pts for x in e]
+            if len(flat) != n * 56:
+                raise ValueError(f"raw points must be {n} records of 56 limbs")
+            arrs.append((ctypes.c_uint32 * (n * 56))(*flat))
+        out = ctypes.create_string_buffer(96 * n)
+        self._chk(self._lib.kzg_test_g1_raw(self._h, op, arrs[0], arrs[1], out, n))
+        return out.raw
+
 
 class RowSet:
     """Rows committed by HipEngine.commit_rows and kept on the device: `handle`, worker `i`, `k` rows of `T` elements and
