@@ -4,19 +4,7 @@ and a builder of real permutation instances (sigma rows of a random permutation 
 cycles)."""
 import random
 
-R = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
-
-
-def be(v):
-    return (v % R).to_bytes(32, "big")
-
-
-def ints(b):
-    return [int.from_bytes(b[i:i + 32], "big") for i in range(0, len(b), 32)]
-
-
-def row_bytes(vals):
-    return b"".join(be(v) for v in vals)
+from tests.gpu_common import R, be, ints, row_bytes  # noqa: F401  (re-exported for the tests)
 
 
 def omega(T):

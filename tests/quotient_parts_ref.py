@@ -184,3 +184,10 @@ class WideInstance:
         coeff = [qr.coeffs_of(r) for r in self.all_rows]
         return [part([coeff[n] for n in names], terms, perm, None, active, link, scale)
                 for names, terms, perm, active, link, scale in self.layout()]
+
+
+# the instances tests/test_gpu_quotient_parts.py runs on the device, as (lg, usable, seed); tests/test_quotient_parts_cpu.py
+# checks their preconditions without one
+GPU_WIDE = [(8, (1 << 8) - 5, 21), (16, (1 << 16) - 6, 23)]
+GPU_CLIENT = (6, 58, 25)     # the round through the Client's text forms
+GPU_SPLIT = [(4, 11, 31), (8, (1 << 8) - 6, 32), (10, (1 << 10) - 6, 33)]     # blinding_ref.Instance, split into three parts

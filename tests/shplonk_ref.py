@@ -6,20 +6,9 @@ Conventions (include/kzg_mi355x.h, kzg_rows_commit_shplonk): rows f_j as lists o
 distinct; opened[p] the rows opened at a_p; S_j = {p : j in opened[p]}; c_j one scalar per row, c_j = 0 leaves the row out."""
 from oracle import bls12_381 as o
 from oracle import cpu as oc
+from tests.gpu_common import be, ints, row_bytes  # noqa: F401  (re-exported for the tests)
 
 R = o.R
-
-
-def be(v):
-    return (v % R).to_bytes(32, "big")
-
-
-def ints(b):
-    return [int.from_bytes(b[32 * t:32 * t + 32], "big") for t in range(len(b) // 32)]
-
-
-def row_bytes(vals):
-    return b"".join(be(v) for v in vals)
 
 
 def coeffs_of(row_be32, ef):

@@ -7,6 +7,7 @@ import pytest
 
 from oracle import bls12_381 as o
 from oracle import cpu as oc
+from tests.gpu_common import be
 from zkp_subnet_amd import _native
 from zkp_subnet_amd.build import build
 from zkp_subnet_amd.client import Client
@@ -15,10 +16,6 @@ from zkp_subnet_amd.engine import lagrange_factor
 from zkp_subnet_amd.verifier import Verifier
 
 R = o.R
-
-
-def be(v):
-    return (v % R).to_bytes(32, "big")
 
 
 def combine(rows, gamma):

@@ -15,20 +15,19 @@ import pytest
 
 from oracle import cpu as oc
 from tests import blinding_ref as br
+from tests import gpu_rows
 from tests import grand_product_ref as gp
 from tests import lookup_ref as lr
 from tests import quotient_ref as qr
-from tests.gpu_common import ints, rand_scalars_bytes
-from tests.test_gpu_quotient import b_perm, check_pieces, commit_sets, release, standard
-from tests.test_gpu_quotient_ext import b_lookup, b_terms, c_args, x_call
+from tests.gpu_common import ints, val
+from tests.gpu_rows import (arg_error, b_lookup, b_perm, b_terms, bt, c_args, check_one_row, check_pieces, commit_sets,
+                            engine_cache, probes_closing, release, srs_cache, standard, tail_of, x_call, zk_call)
 from zkp_subnet_amd import _native, codec
-from zkp_subnet_amd._native import KzgError
 from zkp_subnet_amd.engine import lagrange_factor
 
 pytestmark = pytest.mark.gpu
 R = br.R
 be, row_bytes = br.be, br.row_bytes
-val = lambda b: int.from_bytes(b, "big")   # noqa: E731
 E_ARG = _native.KZG_E_ARG
 SEED_X, SEED_Y = 0xB11D01, 0xB11D02
 SHAPES = [(5, 1), (5, 2), (5, 27), (5, 31), (10, (1 << 10) - 6), (14, (1 << 14) - 32), (14, (1 << 14) - 1)]
@@ -38,68 +37,21 @@ SHAPE_MSG = "the constraints do not hold on the domain, or n_pieces is too small
 
 @pytest.fixture(scope="module")
 def engines(hip):
-    """one context per log2 row length, holding worker 0's slice of a 2^lg-point SRS (machines_scale 0)"""
-    cache = {}
-
-    def get(lg):
-        if lg not in cache:
-            eng = hip()
-            eng.gen_srs(SEED_X + lg, SEED_Y, lg, 0)
-            cache[lg] = eng
-        return cache[lg]
-
-    return get
+    return engine_cache(hip, SEED_X, SEED_Y)
 
 
 @pytest.fixture(scope="module")
 def srs_of():
-    cache = {}
-
-    def get(lg):
-        if lg not in cache:
-            cache[lg] = oc.srs_gen(be(SEED_X + lg), be(SEED_Y), lg, 0, 0)
-        return cache[lg]
-
-    return get
+    return srs_cache(SEED_X, SEED_Y)
 
 
-@functools.lru_cache(maxsize=None)
-def rand_rows(k, T, seed):
-    return [ints(rand_scalars_bytes(T, seed + j)) for j in range(k)]
-
-
-def tail_of(T, u, seed):
-    rnd = random.Random(seed)
-    return [rnd.randrange(R) for _ in range(T - u - 1)]
-
-
-def bt(tail):
-    return [be(v) for v in tail]
-
-
-def _arg_error(fn, why=None, code=E_ARG):
-    with pytest.raises(KzgError) as ei:
-        fn()
-    assert ei.value.code == code, ei.value
-    if why:
-        assert why in str(ei.value), str(ei.value)
+rand_rows = functools.lru_cache(maxsize=None)(gpu_rows.rand_rows)   # the tests share rows and none of them writes to one
 
 
 def check_row(eng, srs, rset, row, u, rnd):
     """the one-row set against the expected evaluations: the oracle's commitment, the values at w^u, w^(u+1), w^(T-1) and
     at a random point"""
-    T = len(row)
-    rb = row_bytes(row)
-    assert (rset.k, rset.i, rset.T, len(rset.commitments)) == (1, 0, T, 1)
-    assert rset.commitments[0] == oc.commit(srs, rb, True)
-    w = gp.omega(T)
-    ts = sorted({0, u - 1, u, min(u + 1, T - 1), T - 1})
-    for t0 in range(0, len(ts), 4):
-        part = ts[t0:t0 + 4]
-        Y = eng.eval_rows([rset], [be(pow(w, t, R)) for t in part], [[0]] * len(part))
-        assert [y[0] for y in Y] == [be(row[t]) for t in part], part
-    x = be(rnd.randrange(R))
-    assert eng.eval_rows([rset], [x], [[0]])[0][0] == oc.fr_eval(oc.fr_ntt(rb, True), x)
+    check_one_row(eng, srs, rset, row, rnd, probes=probes_closing(len(row), u))
 
 
 # ---------------------------------------------------------------------------------------------------- the three builders
@@ -224,11 +176,11 @@ def test_a_zero_denominator_counts_only_on_usable_rows(engines, srs_of):
         for t, usable_row in ((u, False), (T - 1, False), (u - 1, True), (0, True), (517, True)):
             gamma = -(wires[1][t] + beta * sigmas[1][t]) % R          # D_t = 0
             lbeta = -inputs[1][t] % R                                  # beta + F_2(w^t) = 0 (L = 2, w = 1)
-            _arg_error(lambda: eng.commit_grand_product(W, Sg, bs, be(beta), be(gamma)), "zero denominator")
-            _arg_error(lambda: eng.commit_lookup_sum(F, Tb, M[0], 2, 1, be(theta), be(lbeta)), "zero denominator")
+            arg_error(lambda: eng.commit_grand_product(W, Sg, bs, be(beta), be(gamma)), "zero denominator")
+            arg_error(lambda: eng.commit_lookup_sum(F, Tb, M[0], 2, 1, be(theta), be(lbeta)), "zero denominator")
             if usable_row:
-                _arg_error(lambda: eng.commit_grand_product_zk(W, Sg, bs, be(beta), be(gamma), u, bt(zt)), "zero denominator")
-                _arg_error(lambda: eng.commit_lookup_sum_zk(F, Tb, M[0], 2, 1, be(theta), be(lbeta), u, bt(st)),
+                arg_error(lambda: eng.commit_grand_product_zk(W, Sg, bs, be(beta), be(gamma), u, bt(zt)), "zero denominator")
+                arg_error(lambda: eng.commit_lookup_sum_zk(F, Tb, M[0], 2, 1, be(theta), be(lbeta), u, bt(st)),
                            "zero denominator")
                 assert eng.rows_stats() == live                        # no set was created
                 continue
@@ -247,10 +199,6 @@ def test_a_zero_denominator_counts_only_on_usable_rows(engines, srs_of):
 
 
 # ---------------------------------------------------------------------------------------------------- the quotient
-def zk_call(eng, sets, terms, perm=None, lookup=None, active=None, ext_log=2, n_pieces=3):
-    return eng.commit_quotient_zk(sets, b_terms(terms), b_perm(perm), b_lookup(lookup), active, ext_log, n_pieces)
-
-
 def raw_zk(lib, eng, sets, terms, perm, lookup, active, ext_log, P):
     """kzg_rows_commit_quotient_zk itself (active: a row index, or None for a NULL pointer) -> (status, commitments)"""
     hs = (ctypes.c_uint64 * len(sets))(*[s.handle for s in sets])
@@ -331,7 +279,7 @@ def test_the_masked_quotient_bit_exact(engines, srs_of):
             check_pieces(eng, srs, tset, want, rnd)
         finally:
             tset.release()
-        _arg_error(lambda: x_call(eng, S, inst.terms, inst.perm, inst.lookup, 3, 4), SHAPE_MSG)   # unmasked: the padding binds
+        arg_error(lambda: x_call(eng, S, inst.terms, inst.perm, inst.lookup, 3, 4), SHAPE_MSG)   # unmasked: the padding binds
     finally:
         release(S)
     assert eng.rows_stats() == before
@@ -460,9 +408,9 @@ def test_errors_leave_the_context_serving(engines, srs_of):
         assert b"KZG_MAX_BLIND_ROWS" in lib.kzg_last_error(engines(10)._h)
         # the engine checks the tail's length before the library reads it
         bs = [be(1), be(7)]
-        _arg_error(lambda: eng.commit_grand_product_zk(W, Sg, bs, one, one, u, bt(ints(tail))[:-1]), "exactly")
-        _arg_error(lambda: eng.commit_grand_product_zk(W, Sg, bs, one, one, u, []), "exactly")
-        _arg_error(lambda: eng.commit_grand_product_zk([W[0].handle], [Sg[0].handle], bs, one, one, 0, []), "usable")
+        arg_error(lambda: eng.commit_grand_product_zk(W, Sg, bs, one, one, u, bt(ints(tail))[:-1]), "exactly")
+        arg_error(lambda: eng.commit_grand_product_zk(W, Sg, bs, one, one, u, []), "exactly")
+        arg_error(lambda: eng.commit_grand_product_zk([W[0].handle], [Sg[0].handle], bs, one, one, 0, []), "usable")
         fresh_ok()
         assert eng.rows_stats() == live
     finally:

@@ -11,7 +11,9 @@ import pytest
 
 from oracle import cpu as oc
 from tests import grand_product_ref as gp
-from tests.gpu_common import ints, rand_scalars_bytes
+from tests.gpu_common import ints
+from tests.gpu_rows import (arg_error, check_one_row, commit_sets, engine_cache, probes_ends, rand_rows, release,
+                            split_first as split, srs_cache)
 from zkp_subnet_amd import _native
 from zkp_subnet_amd._native import KzgError
 from zkp_subnet_amd.engine import lagrange_factor
@@ -25,55 +27,12 @@ ONE = be(1)
 
 @pytest.fixture(scope="module")
 def engines(hip):
-    """one context per log2 row length, holding worker 0's slice of a 2^lg-point SRS (machines_scale 0)"""
-    cache = {}
-
-    def get(lg):
-        if lg not in cache:
-            eng = hip()
-            eng.gen_srs(SEED_X + lg, SEED_Y, lg, 0)
-            cache[lg] = eng
-        return cache[lg]
-
-    return get
+    return engine_cache(hip, SEED_X, SEED_Y)
 
 
 @pytest.fixture(scope="module")
 def srs_of():
-    cache = {}
-
-    def get(lg):
-        if lg not in cache:
-            cache[lg] = oc.srs_gen(be(SEED_X + lg), be(SEED_Y), lg, 0, 0)
-        return cache[lg]
-
-    return get
-
-
-def rand_rows(k, T, seed):
-    return [ints(rand_scalars_bytes(T, seed + j)) for j in range(k)]
-
-
-def commit_sets(eng, evals, sizes, ef=True, i=0):
-    """rows given by their evaluations, committed in evaluation form or (through the oracle's INTT) in coefficient form"""
-    rows = [row_bytes(v) for v in evals]
-    if not ef:
-        rows = [oc.fr_ntt(r, True) for r in rows]
-    sets, o = [], 0
-    for s in sizes:
-        sets.append(eng.commit_rows(i, rows[o:o + s], ef))
-        o += s
-    assert o == len(rows)
-    return sets
-
-
-def release(sets):
-    for s in sets:
-        s.release()
-
-
-def split(k):
-    return (k,) if k < 3 else (1, k - 1)
+    return srs_cache(SEED_X, SEED_Y)
 
 
 def gp_call(eng, W, S, shifts, beta, gamma):
@@ -81,19 +40,8 @@ def gp_call(eng, W, S, shifts, beta, gamma):
 
 
 def check_against_reference(eng, srs, zset, closing, z, want_closing, rnd):
-    T = len(z)
-    zb = row_bytes(z)
-    assert (zset.k, len(zset.commitments)) == (1, 1)
-    assert zset.commitments[0] == oc.commit(srs, zb, True)
     assert closing == be(want_closing)
-    dom_w = gp.omega(T)
-    ts = sorted({0, 1 % T, T - 1} | {rnd.randrange(T) for _ in range(3)})
-    for t0 in range(0, len(ts), 4):
-        part = ts[t0:t0 + 4]
-        Y = eng.eval_rows([zset], [be(pow(dom_w, t, R)) for t in part], [[0]] * len(part))
-        assert [y[0] for y in Y] == [be(z[t]) for t in part], part
-    x = be(rnd.randrange(R))
-    assert eng.eval_rows([zset], [x], [[0]])[0][0] == oc.fr_eval(oc.fr_ntt(zb, True), x)
+    check_one_row(eng, srs, zset, z, rnd, probes=probes_ends(len(z), rnd))
 
 
 @pytest.mark.parametrize("k", [1, 3, 5])
@@ -240,14 +188,6 @@ def test_edge_values(engines, srs_of):
     assert eng.rows_stats() == before
 
 
-def _arg_error(fn, why=None, code=_native.KZG_E_ARG):
-    with pytest.raises(KzgError) as ei:
-        fn()
-    assert ei.value.code == code, ei.value
-    if why:
-        assert why in str(ei.value), str(ei.value)
-
-
 def test_zero_denominator_is_detected_on_the_device(engines, srs_of):
     lg = 12
     eng, srs, T = engines(lg), srs_of(lg), 1 << lg
@@ -260,7 +200,7 @@ def test_zero_denominator_is_detected_on_the_device(engines, srs_of):
         live = eng.rows_stats()
         for t in (0, 1234, T - 1):
             gamma = -(wires[0][t] + beta * sigmas[0][t]) % R
-            _arg_error(lambda: gp_call(eng, W, S, shifts, beta, gamma), "zero denominator")
+            arg_error(lambda: gp_call(eng, W, S, shifts, beta, gamma), "zero denominator")
             assert eng.rows_stats() == live
         gamma = rnd.randrange(R)
         z, closing = gp.grand_product(wires, sigmas, shifts, beta, gamma)
@@ -293,39 +233,39 @@ def test_errors_leave_the_context_serving(hip):
 
     W, S = commit_sets(eng, wires, (3,)), commit_sets(eng, sigmas, (1, 2))
     fresh_ok(W, S)
-    _arg_error(lambda: gp_call(eng, W, S[:1], shifts, beta, gamma), "exactly k rows")           # 3 wire rows, 1 sigma row
-    _arg_error(lambda: gp_call(eng, W, S, shifts[:2], beta, gamma), "exactly k rows")            # k = 2, 3 rows each
-    _arg_error(lambda: eng.commit_grand_product(W, S, [], be(beta), be(gamma)))                  # k = 0
+    arg_error(lambda: gp_call(eng, W, S[:1], shifts, beta, gamma), "exactly k rows")           # 3 wire rows, 1 sigma row
+    arg_error(lambda: gp_call(eng, W, S, shifts[:2], beta, gamma), "exactly k rows")            # k = 2, 3 rows each
+    arg_error(lambda: eng.commit_grand_product(W, S, [], be(beta), be(gamma)))                  # k = 0
     hw, hs = (ctypes.c_uint64 * 1)(W[0].handle), (ctypes.c_uint64 * 2)(S[0].handle, S[1].handle)
     c, cl, h = ctypes.create_string_buffer(48), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
     lib = _native.load()
     assert lib.kzg_rows_commit_grand_product(eng._h, 1, hw, 2, hs, 0, ONE * 3, ONE, ONE, c, cl, ctypes.byref(h)) == _native.KZG_E_ARG
     assert lib.kzg_rows_commit_grand_product(eng._h, 1, hw, 2, hs, 17, ONE * 17, ONE, ONE, c, cl, ctypes.byref(h)) == _native.KZG_E_ARG
-    _arg_error(lambda: gp_call(eng, W * 6, S, [1] * 16, beta, gamma), "KZG_MAX_BATCH_OPEN rows")  # 18 wire rows
+    arg_error(lambda: gp_call(eng, W * 6, S, [1] * 16, beta, gamma), "KZG_MAX_BATCH_OPEN rows")  # 18 wire rows
     big = R.to_bytes(32, "big")
-    _arg_error(lambda: eng.commit_grand_product(W, S, [be(1), big, be(3)], be(5), be(6)), "canonical")
-    _arg_error(lambda: eng.commit_grand_product(W, S, [be(1)] * 3, big, be(6)), "canonical")
-    _arg_error(lambda: eng.commit_grand_product(W, S, [be(1)] * 3, be(5), b"\xff" * 32), "canonical")
+    arg_error(lambda: eng.commit_grand_product(W, S, [be(1), big, be(3)], be(5), be(6)), "canonical")
+    arg_error(lambda: eng.commit_grand_product(W, S, [be(1)] * 3, big, be(6)), "canonical")
+    arg_error(lambda: eng.commit_grand_product(W, S, [be(1)] * 3, be(5), b"\xff" * 32), "canonical")
     other = commit_sets(eng, sigmas, (3,), i=1)                                                   # another worker
-    _arg_error(lambda: gp_call(eng, W, other, shifts, beta, gamma), "one worker")
+    arg_error(lambda: gp_call(eng, W, other, shifts, beta, gamma), "one worker")
     short = eng.commit_rows(0, [row_bytes(r[:T // 2]) for r in sigmas])                            # another length
-    _arg_error(lambda: gp_call(eng, W, [short], shifts, beta, gamma), "one worker and have one row length")
+    arg_error(lambda: gp_call(eng, W, [short], shifts, beta, gamma), "one worker and have one row length")
     release(other + [short])
     gone = commit_sets(eng, sigmas, (3,))
     release(gone)
-    _arg_error(lambda: gp_call(eng, W, gone, shifts, beta, gamma), "released")
-    _arg_error(lambda: gp_call(eng, [2 ** 40], S, shifts, beta, gamma), "unknown")
+    arg_error(lambda: gp_call(eng, W, gone, shifts, beta, gamma), "released")
+    arg_error(lambda: gp_call(eng, [2 ** 40], S, shifts, beta, gamma), "unknown")
     fresh_ok(W, S)
     # the 65th live set
     fill = [eng.commit_rows(0, [row_bytes(wires[0])]) for _ in range(_native.KZG_MAX_ROW_SETS - 3)]
     assert eng.rows_stats()[0] == _native.KZG_MAX_ROW_SETS
-    _arg_error(lambda: gp_call(eng, W, S, shifts, beta, gamma), "KZG_MAX_ROW_SETS", code=_native.KZG_E_BUSY)
+    arg_error(lambda: gp_call(eng, W, S, shifts, beta, gamma), "KZG_MAX_ROW_SETS", code=_native.KZG_E_BUSY)
     fill.pop().release()
     fresh_ok(W, S)
     release(fill)
     # stale after an SRS load
     eng.gen_srs(SEED_X, SEED_Y, lg + 1, 1)
-    _arg_error(lambda: gp_call(eng, W, S, shifts, beta, gamma), "SRS")
+    arg_error(lambda: gp_call(eng, W, S, shifts, beta, gamma), "SRS")
     release(W + S)
     W, S = commit_sets(eng, wires, (3,)), commit_sets(eng, sigmas, (1, 2))
     fresh_ok(W, S)

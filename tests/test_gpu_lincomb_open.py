@@ -10,21 +10,13 @@ import threading
 import pytest
 
 from oracle import cpu as oc
-from tests.gpu_common import rand_scalars_bytes
+from tests.gpu_common import R, be, rand_scalars_bytes, val as ib
+from tests.gpu_rows import arg_error, commit_sets, engine_cache, release
 from zkp_subnet_amd import _native
-from zkp_subnet_amd._native import KzgError
-from zkp_subnet_amd.engine import R_MODULUS as R, _root_of_unity
+from zkp_subnet_amd.engine import _root_of_unity
 
 pytestmark = pytest.mark.gpu
 SEED_X, SEED_Y = 0x11C0B1, 0x11C0B2
-
-
-def be(v):
-    return (v % R).to_bytes(32, "big")
-
-
-def ib(b):
-    return int.from_bytes(b, "big")
 
 
 def make_rows(T, k, seed):
@@ -37,31 +29,7 @@ def make_rows(T, k, seed):
 
 @pytest.fixture(scope="module")
 def engines(hip):
-    """one context per log2 row length, holding worker 0's slice of a 2^lg-point SRS (machines_scale 0)"""
-    cache = {}
-
-    def get(lg):
-        if lg not in cache:
-            eng = hip()
-            eng.gen_srs(SEED_X + lg, SEED_Y, lg, 0)
-            cache[lg] = eng
-        return cache[lg]
-
-    return get
-
-
-def commit_sets(eng, rows, sizes, ef=True, i=0):
-    sets, o = [], 0
-    for s in sizes:
-        sets.append(eng.commit_rows(i, rows[o:o + s], ef))
-        o += s
-    assert o == len(rows)
-    return sets
-
-
-def release(sets):
-    for s in sets:
-        s.release()
+    return engine_cache(hip, SEED_X, SEED_Y)
 
 
 def gamma_coeffs(k, opened, gammas):
@@ -215,14 +183,6 @@ def test_fiat_shamir_plonk_round(engines):
         release(S)
 
 
-def _arg_error(fn, why=None):
-    with pytest.raises(KzgError) as ei:
-        fn()
-    assert ei.value.code == _native.KZG_E_ARG, ei.value
-    if why:
-        assert why in str(ei.value), str(ei.value)
-
-
 def test_errors_leave_the_context_serving(hip):
     eng = hip()
     lg = 8
@@ -242,25 +202,25 @@ def test_errors_leave_the_context_serving(hip):
 
     rs = eng.commit_rows(0, rows)
     rs.release()
-    _arg_error(lambda: eng.eval_rows([rs], P, opened), "released")
-    _arg_error(lambda: eng.open_rows_lincomb([rs], P, L), "released")
+    arg_error(lambda: eng.eval_rows([rs], P, opened), "released")
+    arg_error(lambda: eng.open_rows_lincomb([rs], P, L), "released")
     fresh_ok()
     with eng.commit_rows(0, rows) as rs:
-        _arg_error(lambda: eng.open_rows_lincomb([rs], P, [L[0], L[1][:3] + [R.to_bytes(32, "big")]]), "canonical")
-        _arg_error(lambda: eng.open_rows_lincomb([rs], P, [L[0], [be(0)] * 4]), "nonzero")
-        _arg_error(lambda: eng.open_rows_lincomb([rs], P, [x[:3] for x in L]), "k must equal")
-        _arg_error(lambda: eng.open_rows_lincomb([rs], [P[0], R.to_bytes(32, "big")], L), "canonical")
-        _arg_error(lambda: eng.eval_rows([rs], [P[0], R.to_bytes(32, "big")], opened), "canonical")
-        _arg_error(lambda: eng.eval_rows([rs], P, [[0, 4], [1]]))
+        arg_error(lambda: eng.open_rows_lincomb([rs], P, [L[0], L[1][:3] + [R.to_bytes(32, "big")]]), "canonical")
+        arg_error(lambda: eng.open_rows_lincomb([rs], P, [L[0], [be(0)] * 4]), "nonzero")
+        arg_error(lambda: eng.open_rows_lincomb([rs], P, [x[:3] for x in L]), "k must equal")
+        arg_error(lambda: eng.open_rows_lincomb([rs], [P[0], R.to_bytes(32, "big")], L), "canonical")
+        arg_error(lambda: eng.eval_rows([rs], [P[0], R.to_bytes(32, "big")], opened), "canonical")
+        arg_error(lambda: eng.eval_rows([rs], P, [[0, 4], [1]]))
         with eng.commit_rows(1, rows[:2]) as other:
-            _arg_error(lambda: eng.eval_rows([rs, other], P[:1], [[0]]), "one worker")
-            _arg_error(lambda: eng.open_rows_lincomb([rs, other], P[:1], [L[0] + L[0][:2]]), "one worker")
+            arg_error(lambda: eng.eval_rows([rs, other], P[:1], [[0]]), "one worker")
+            arg_error(lambda: eng.open_rows_lincomb([rs, other], P[:1], [L[0] + L[0][:2]]), "one worker")
         assert (eng.eval_rows([rs], P, opened), eng.open_rows_lincomb([rs], P, L)) == want
     fresh_ok()
     st = eng.commit_rows(0, rows)
     eng.gen_srs(SEED_X, SEED_Y, lg + 1, 1)
-    _arg_error(lambda: eng.eval_rows([st], P, opened), "SRS")
-    _arg_error(lambda: eng.open_rows_lincomb([st], P, L), "SRS")
+    arg_error(lambda: eng.eval_rows([st], P, opened), "SRS")
+    arg_error(lambda: eng.open_rows_lincomb([st], P, L), "SRS")
     st.release()
     fresh_ok()
     assert eng.rows_stats() == (0, 0)

@@ -18,7 +18,9 @@ from oracle import cpu as oc
 from tests import grand_product_ref as gp
 from tests import lookup_ref as lr
 from tests import lookup_sel_ref as ls
-from tests.gpu_common import ints, rand_scalars_bytes
+from tests.gpu_common import val
+from tests.gpu_rows import (arg_error, bt, check_one_row, commit_sets, engine_cache, probes_closing, rand_rows, release,
+                            srs_cache, tail_of)
 from zkp_subnet_amd import _native, codec
 from zkp_subnet_amd._native import KzgError
 from zkp_subnet_amd.engine import lagrange_factor
@@ -26,7 +28,6 @@ from zkp_subnet_amd.engine import lagrange_factor
 pytestmark = pytest.mark.gpu
 R = ls.R
 be, row_bytes = ls.be, ls.row_bytes
-val = lambda b: int.from_bytes(b, "big")   # noqa: E731
 E_ARG = _native.KZG_E_ARG
 NOSEL = _native.KZG_NO_SELECTOR
 SEED_X, SEED_Y = 0x5E1EC7, 0x5E1EC8
@@ -36,86 +37,18 @@ layout_id = lambda s: f"T2^{s[0]}-u{s[1]}"   # noqa: E731
 
 @pytest.fixture(scope="module")
 def engines(hip):
-    """one context per log2 row length, holding worker 0's slice of a 2^lg-point SRS (machines_scale 0)"""
-    cache = {}
-
-    def get(lg):
-        if lg not in cache:
-            eng = hip()
-            eng.gen_srs(SEED_X + lg, SEED_Y, lg, 0)
-            cache[lg] = eng
-        return cache[lg]
-
-    return get
+    return engine_cache(hip, SEED_X, SEED_Y)
 
 
 @pytest.fixture(scope="module")
 def srs_of():
-    cache = {}
-
-    def get(lg):
-        if lg not in cache:
-            cache[lg] = oc.srs_gen(be(SEED_X + lg), be(SEED_Y), lg, 0, 0)
-        return cache[lg]
-
-    return get
-
-
-def rand_rows(k, T, seed):
-    return [ints(rand_scalars_bytes(T, seed + j)) for j in range(k)]
-
-
-def tail_of(T, u, seed):
-    rnd = random.Random(seed)
-    return [] if u is None else [rnd.randrange(R) for _ in range(T - u - 1)]
-
-
-def bt(tail):
-    return [be(v) for v in tail]
-
-
-def commit_sets(eng, evals, sizes, ef=True, i=0):
-    """rows given by their evaluations, committed in evaluation form or (through the oracle's INTT) in coefficient form"""
-    rows = [row_bytes(v) for v in evals]
-    if not ef:
-        rows = [oc.fr_ntt(r, True) for r in rows]
-    sets, o = [], 0
-    for s in sizes:
-        sets.append(eng.commit_rows(i, rows[o:o + s], ef))
-        o += s
-    assert o == len(rows)
-    return sets
-
-
-def release(sets):
-    for s in sets:
-        s.release()
-
-
-def _arg_error(fn, why=None, code=E_ARG):
-    with pytest.raises(KzgError) as ei:
-        fn()
-    assert ei.value.code == code, ei.value
-    if why:
-        assert why in str(ei.value), str(ei.value)
+    return srs_cache(SEED_X, SEED_Y)
 
 
 def check_row(eng, srs, rset, row, u, rnd):
     """the one-row set against the expected evaluations: the oracle's commitment of the reference's row, the values around
     the closing row and at the ends, and the value at a random point"""
-    T = len(row)
-    rb = row_bytes(row)
-    assert (rset.k, rset.i, rset.T, len(rset.commitments)) == (1, 0, T, 1)
-    assert rset.commitments[0] == oc.commit(srs, rb, True)
-    w = gp.omega(T)
-    u = T - 1 if u is None else u
-    ts = sorted({0, u - 1, u, min(u + 1, T - 1), T - 1})
-    for t0 in range(0, len(ts), 4):
-        part = ts[t0:t0 + 4]
-        Y = eng.eval_rows([rset], [be(pow(w, t, R)) for t in part], [[0]] * len(part))
-        assert [y[0] for y in Y] == [be(row[t]) for t in part], part
-    x = be(rnd.randrange(R))
-    assert eng.eval_rows([rset], [x], [[0]])[0][0] == oc.fr_eval(oc.fr_ntt(rb, True), x)
+    check_one_row(eng, srs, rset, row, rnd, probes=probes_closing(len(row), u))
 
 
 def run(eng, srs, inputs, table, sels, L, w, theta, beta, u, tail, rnd, mult=None):
@@ -362,7 +295,7 @@ def test_a_zero_denominator_on_a_disabled_row_is_an_error(engines, srs_of):
     F, Tb, Q, M = (commit_sets(eng, x, (1,)) for x in (inputs, table, sels, [m]))
     try:
         for layout in ((u, bt(tail)), (None, [])):
-            _arg_error(lambda: eng.commit_lookup_sum_sel(F, Tb, M[0], Q, [0], L, w, be(0), be(-inputs[0][t] % R), *layout),
+            arg_error(lambda: eng.commit_lookup_sum_sel(F, Tb, M[0], Q, [0], L, w, be(0), be(-inputs[0][t] % R), *layout),
                        "zero denominator")
             assert eng.rows_stats()[0] == before[0] + 4
         beta = -inputs[0][u + 1] % R
@@ -406,17 +339,17 @@ def test_errors_leave_the_context_serving(engines, srs_of, hip):
     try:
         good()
         for call in (mul, lks):
-            _arg_error(lambda: call(Q, [0, 2]), "sel_index")            # out of range
-            _arg_error(lambda: call(Q, [0, NOSEL - 1]), "sel_index")
-            _arg_error(lambda: call([], [0, None]), "sel_index")         # a real index with no selector set
-            _arg_error(lambda: call([gone.handle], [0, 1]), "unknown or released")
-            _arg_error(lambda: call([0xDEAD], [0, 1]), "unknown or released")
-            _arg_error(lambda: call(Q, [0]))                             # not n_lookups entries (refused by the binding)
-            _arg_error(lambda: call(Q, [0, 1], T, tb), "usable")         # usable = T goes with no tail only
-            _arg_error(lambda: call(Q, [0, 1], 0, []))
+            arg_error(lambda: call(Q, [0, 2]), "sel_index")            # out of range
+            arg_error(lambda: call(Q, [0, NOSEL - 1]), "sel_index")
+            arg_error(lambda: call([], [0, None]), "sel_index")         # a real index with no selector set
+            arg_error(lambda: call([gone.handle], [0, 1]), "unknown or released")
+            arg_error(lambda: call([0xDEAD], [0, 1]), "unknown or released")
+            arg_error(lambda: call(Q, [0]))                             # not n_lookups entries (refused by the binding)
+            arg_error(lambda: call(Q, [0, 1], T, tb), "usable")         # usable = T goes with no tail only
+            arg_error(lambda: call(Q, [0, 1], 0, []))
             good()
         # a selector set of another row length is a set of another context here: unknown to this one
-        _arg_error(lambda: mul([long_set.handle], [0, 0]), "unknown or released")
+        arg_error(lambda: mul([long_set.handle], [0, 0]), "unknown or released")
         # the C entry points themselves: null sel_index, null sel_handles with a count, too many handles
         c, cl, h, miss = ctypes.create_string_buffer(48), ctypes.create_string_buffer(32), ctypes.c_uint64(0), ctypes.c_uint64(0)
         arr = lambda *xs: (ctypes.c_uint64 * len(xs))(*[int(getattr(x, "handle", x)) for x in xs])   # noqa: E731
@@ -443,9 +376,9 @@ def test_a_selector_of_another_worker(hip):
     F, Tb, Q = (commit_sets(eng, x, (1,)) for x in (inputs, table, sels))
     Q1 = commit_sets(eng, sels, (1,), i=1)
     try:
-        _arg_error(lambda: eng.commit_multiplicities_sel(F, Tb, Q1, [0], L, w), "one worker")
+        arg_error(lambda: eng.commit_multiplicities_sel(F, Tb, Q1, [0], L, w), "one worker")
         mset, miss = eng.commit_multiplicities_sel(F, Tb, Q, [0], L, w)
-        _arg_error(lambda: eng.commit_lookup_sum_sel(F, Tb, mset, Q1, [0], L, w, be(3), be(4)), "one worker")
+        arg_error(lambda: eng.commit_lookup_sum_sel(F, Tb, mset, Q1, [0], L, w, be(3), be(4)), "one worker")
         sset, cl = eng.commit_lookup_sum_sel(F, Tb, mset, Q, [0], L, w, be(3), be(4))
         release([mset, sset])
         assert (miss, cl) == (0, be(0))
@@ -772,8 +705,8 @@ def test_quotient_sel_errors_leave_the_context_serving(engines, srs_of):
 
     try:
         good()
-        _arg_error(lambda: eng.commit_quotient_sel(sets, terms, None, lookup, [n], None, ext_log, P), "row index")
-        _arg_error(lambda: eng.quotient_part_sel(sets, terms, None, lookup, [n + 3], None, None, ext_log), "row index")
+        arg_error(lambda: eng.commit_quotient_sel(sets, terms, None, lookup, [n], None, ext_log, P), "row index")
+        arg_error(lambda: eng.quotient_part_sel(sets, terms, None, lookup, [n + 3], None, None, ext_log), "row index")
         good()
         # the C entry points: selectors without a lookup part, and a null selector_rows
         _, hs, gate, _, lk, _ = eng._quotient_args("t", sets, [(be(1), [0])], None, lookup, None, ext_log, P)

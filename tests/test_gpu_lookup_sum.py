@@ -13,6 +13,8 @@ import pytest
 from oracle import cpu as oc
 from tests import lookup_ref as lk
 from tests.gpu_common import ints, rand_scalars_bytes
+from tests.gpu_rows import (arg_error, check_one_row, commit_sets, engine_cache, probes_ends, rand_rows, release,
+                            split_first as split, srs_cache)
 from zkp_subnet_amd import _native
 from zkp_subnet_amd._native import KzgError
 from zkp_subnet_amd.engine import lagrange_factor
@@ -27,55 +29,12 @@ SHAPES = [(1, 1), (2, 1), (4, 3), (16, 1), (1, 16)]
 
 @pytest.fixture(scope="module")
 def engines(hip):
-    """one context per log2 row length, holding worker 0's slice of a 2^lg-point SRS (machines_scale 0)"""
-    cache = {}
-
-    def get(lg):
-        if lg not in cache:
-            eng = hip()
-            eng.gen_srs(SEED_X + lg, SEED_Y, lg, 0)
-            cache[lg] = eng
-        return cache[lg]
-
-    return get
+    return engine_cache(hip, SEED_X, SEED_Y)
 
 
 @pytest.fixture(scope="module")
 def srs_of():
-    cache = {}
-
-    def get(lg):
-        if lg not in cache:
-            cache[lg] = oc.srs_gen(be(SEED_X + lg), be(SEED_Y), lg, 0, 0)
-        return cache[lg]
-
-    return get
-
-
-def rand_rows(k, T, seed):
-    return [ints(rand_scalars_bytes(T, seed + j)) for j in range(k)]
-
-
-def commit_sets(eng, evals, sizes, ef=True, i=0):
-    """rows given by their evaluations, committed in evaluation form or (through the oracle's INTT) in coefficient form"""
-    rows = [row_bytes(v) for v in evals]
-    if not ef:
-        rows = [oc.fr_ntt(r, True) for r in rows]
-    sets, o = [], 0
-    for s in sizes:
-        sets.append(eng.commit_rows(i, rows[o:o + s], ef))
-        o += s
-    assert o == len(rows)
-    return sets
-
-
-def release(sets):
-    for s in sets:
-        s.release()
-
-
-def split(k):
-    return (k,) if k < 3 else (1, k - 1)
+    return srs_cache(SEED_X, SEED_Y)
 
 
 def lk_call(eng, F, Tb, M, L, w, theta, beta):
@@ -83,19 +42,8 @@ def lk_call(eng, F, Tb, M, L, w, theta, beta):
 
 
 def check_against_reference(eng, srs, sset, closing, S, want_closing, rnd, want_commitment=None):
-    T = len(S)
-    sb = row_bytes(S)
-    assert (sset.k, len(sset.commitments)) == (1, 1)
-    assert sset.commitments[0] == (want_commitment or oc.commit(srs, sb, True))
     assert closing == be(want_closing)
-    dom_w = lk.domain(T)[1 % T]
-    ts = sorted({0, 1 % T, T - 1} | {rnd.randrange(T) for _ in range(3)})
-    for t0 in range(0, len(ts), 4):
-        part = ts[t0:t0 + 4]
-        Y = eng.eval_rows([sset], [be(pow(dom_w, t, R)) for t in part], [[0]] * len(part))
-        assert [y[0] for y in Y] == [be(S[t]) for t in part], part
-    x = be(rnd.randrange(R))
-    assert eng.eval_rows([sset], [x], [[0]])[0][0] == oc.fr_eval(oc.fr_ntt(sb, True), x)
+    check_one_row(eng, srs, sset, S, rnd, probes=probes_ends(len(S), rnd), want_commitment=want_commitment)
 
 
 def run_both_forms(eng, srs, inputs, table, mult, L, w, theta, beta, rnd, closes):
@@ -264,14 +212,6 @@ def test_large_row_through_the_trapdoor(engines):
     assert eng.rows_stats() == before
 
 
-def _arg_error(fn, why=None, code=_native.KZG_E_ARG):
-    with pytest.raises(KzgError) as ei:
-        fn()
-    assert ei.value.code == code, ei.value
-    if why:
-        assert why in str(ei.value), str(ei.value)
-
-
 def test_zero_denominator_is_detected_on_the_device(engines, srs_of):
     lg, L, w = 12, 2, 2
     eng, srs, T = engines(lg), srs_of(lg), 1 << lg
@@ -288,7 +228,7 @@ def test_zero_denominator_is_detected_on_the_device(engines, srs_of):
                 beta = -comp[t] % R
                 with pytest.raises(ZeroDivisionError):
                     lk.lookup_sum(inputs, table, mult, L, w, theta, beta)
-                _arg_error(lambda: lk_call(eng, F, Tb, M[0], L, w, theta, beta), "zero denominator")
+                arg_error(lambda: lk_call(eng, F, Tb, M[0], L, w, theta, beta), "zero denominator")
                 assert eng.rows_stats() == live
         beta = rnd.randrange(R)
         S, closing = lk.lookup_sum(inputs, table, mult, L, w, theta, beta)
@@ -320,12 +260,12 @@ def test_errors_leave_the_context_serving(hip):
 
     F, Tb, M = commit_sets(eng, inputs, (1, 3)), commit_sets(eng, table, (2,)), commit_sets(eng, [mult], (1,))[0]
     fresh_ok(F, Tb, M)
-    _arg_error(lambda: lk_call(eng, F[:1], Tb, M, L, w, theta, beta), "n_lookups * width rows")     # 1 input row for 4
-    _arg_error(lambda: lk_call(eng, F, Tb, M, 4, 1, theta, beta), "width rows")                      # 2 table rows for w = 1
-    _arg_error(lambda: lk_call(eng, F, Tb + Tb, M, L, w, theta, beta), "width rows")                 # 4 table rows for w = 2
-    _arg_error(lambda: lk_call(eng, F, Tb, Tb[0], L, w, theta, beta), "exactly one row")             # a two-row m
-    _arg_error(lambda: lk_call(eng, F, Tb, M, 0, w, theta, beta))                                    # L = 0
-    _arg_error(lambda: lk_call(eng, F, Tb, M, L, 0, theta, beta))                                    # w = 0
+    arg_error(lambda: lk_call(eng, F[:1], Tb, M, L, w, theta, beta), "n_lookups * width rows")     # 1 input row for 4
+    arg_error(lambda: lk_call(eng, F, Tb, M, 4, 1, theta, beta), "width rows")                      # 2 table rows for w = 1
+    arg_error(lambda: lk_call(eng, F, Tb + Tb, M, L, w, theta, beta), "width rows")                 # 4 table rows for w = 2
+    arg_error(lambda: lk_call(eng, F, Tb, Tb[0], L, w, theta, beta), "exactly one row")             # a two-row m
+    arg_error(lambda: lk_call(eng, F, Tb, M, 0, w, theta, beta))                                    # L = 0
+    arg_error(lambda: lk_call(eng, F, Tb, M, L, 0, theta, beta))                                    # w = 0
     hf, ht = (ctypes.c_uint64 * 2)(F[0].handle, F[1].handle), (ctypes.c_uint64 * 1)(Tb[0].handle)
     c, cl, h = ctypes.create_string_buffer(48), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
     lib = _native.load()
@@ -339,33 +279,33 @@ def test_errors_leave_the_context_serving(hip):
     assert f(eng._h, 2, hf, 17, ht, M.handle, 2, 2, ONE, ONE, c, cl, ctypes.byref(h)) == _native.KZG_E_ARG
     assert f(eng._h, 2, hf, 1, ht, M.handle, 2, 2, ONE, ONE, c, cl, ctypes.byref(h)) == 0              # (the same call, in range)
     eng.release_rows(h.value)
-    _arg_error(lambda: lk_call(eng, F * 6, Tb, M, 8, 2, theta, beta), "KZG_MAX_BATCH_OPEN rows")      # 24 input rows
+    arg_error(lambda: lk_call(eng, F * 6, Tb, M, 8, 2, theta, beta), "KZG_MAX_BATCH_OPEN rows")      # 24 input rows
     big = R.to_bytes(32, "big")
-    _arg_error(lambda: eng.commit_lookup_sum(F, Tb, M, L, w, big, be(6)), "canonical")
-    _arg_error(lambda: eng.commit_lookup_sum(F, Tb, M, L, w, be(5), b"\xff" * 32), "canonical")
+    arg_error(lambda: eng.commit_lookup_sum(F, Tb, M, L, w, big, be(6)), "canonical")
+    arg_error(lambda: eng.commit_lookup_sum(F, Tb, M, L, w, be(5), b"\xff" * 32), "canonical")
     other = commit_sets(eng, table, (2,), i=1)                                                        # another worker
-    _arg_error(lambda: lk_call(eng, F, other, M, L, w, theta, beta), "one worker")
+    arg_error(lambda: lk_call(eng, F, other, M, L, w, theta, beta), "one worker")
     other_m = commit_sets(eng, [mult], (1,), i=1)
-    _arg_error(lambda: lk_call(eng, F, Tb, other_m[0], L, w, theta, beta), "one worker")
+    arg_error(lambda: lk_call(eng, F, Tb, other_m[0], L, w, theta, beta), "one worker")
     short = eng.commit_rows(0, [row_bytes(r[:T // 2]) for r in table])                                # another length
-    _arg_error(lambda: lk_call(eng, F, [short], M, L, w, theta, beta), "one worker and have one row length")
+    arg_error(lambda: lk_call(eng, F, [short], M, L, w, theta, beta), "one worker and have one row length")
     release(other + other_m + [short])
     gone = commit_sets(eng, table, (2,))
     release(gone)
-    _arg_error(lambda: lk_call(eng, F, gone, M, L, w, theta, beta), "released")
-    _arg_error(lambda: lk_call(eng, [2 ** 40], Tb, M, L, w, theta, beta), "unknown")
-    _arg_error(lambda: lk_call(eng, F, Tb, 2 ** 40, L, w, theta, beta), "unknown")
+    arg_error(lambda: lk_call(eng, F, gone, M, L, w, theta, beta), "released")
+    arg_error(lambda: lk_call(eng, [2 ** 40], Tb, M, L, w, theta, beta), "unknown")
+    arg_error(lambda: lk_call(eng, F, Tb, 2 ** 40, L, w, theta, beta), "unknown")
     fresh_ok(F, Tb, M)
     # the 65th live set
     fill = [eng.commit_rows(0, [row_bytes(mult)]) for _ in range(_native.KZG_MAX_ROW_SETS - 4)]
     assert eng.rows_stats()[0] == _native.KZG_MAX_ROW_SETS
-    _arg_error(lambda: lk_call(eng, F, Tb, M, L, w, theta, beta), "KZG_MAX_ROW_SETS", code=_native.KZG_E_BUSY)
+    arg_error(lambda: lk_call(eng, F, Tb, M, L, w, theta, beta), "KZG_MAX_ROW_SETS", code=_native.KZG_E_BUSY)
     fill.pop().release()
     fresh_ok(F, Tb, M)
     release(fill)
     # stale after an SRS load
     eng.gen_srs(SEED_X, SEED_Y, lg + 1, 1)
-    _arg_error(lambda: lk_call(eng, F, Tb, M, L, w, theta, beta), "SRS")
+    arg_error(lambda: lk_call(eng, F, Tb, M, L, w, theta, beta), "SRS")
     release(F + Tb + [M])
     F, Tb, M = commit_sets(eng, inputs, (1, 3)), commit_sets(eng, table, (2,)), commit_sets(eng, [mult], (1,))[0]
     fresh_ok(F, Tb, M)
@@ -487,7 +427,7 @@ def test_batched_inversion_hook(hip):
     for n, at in ((1, 0), (300, 0), (300, 299), (5000, 2500)):
         vals = [rnd.randrange(1, R) for _ in range(n)]
         vals[at] = 0
-        _arg_error(lambda: eng.test_fr_batch_inv(b"".join(be(v) for v in vals)), "zero")
+        arg_error(lambda: eng.test_fr_batch_inv(b"".join(be(v) for v in vals)), "zero")
     assert ints(eng.test_fr_batch_inv(be(3) + be(5))) == [pow(3, -1, R), pow(5, -1, R)]    # the context keeps serving
     out, zero = eng.test_fr_inv(be(0) + be(3))                                              # ops 7 / 8 as before
     assert zero == [1, 0] and ints(out) == [0, pow(3, -1, R)]

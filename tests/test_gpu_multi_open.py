@@ -9,16 +9,12 @@ import threading
 import pytest
 
 from oracle import cpu as oc
-from tests.gpu_common import rand_scalars_bytes
+from tests.gpu_common import be, rand_scalars_bytes
 from zkp_subnet_amd import _native
 from zkp_subnet_amd.engine import R_MODULUS as R, _root_of_unity
 
 pytestmark = pytest.mark.gpu
 TH = 16
-
-
-def be(v):
-    return (v % R).to_bytes(32, "big")
 
 
 def combine(rows, gamma):

@@ -13,7 +13,8 @@ import pytest
 
 from oracle import cpu as oc
 from tests import lookup_ref as lk
-from tests.gpu_common import ints, rand_scalars_bytes
+from tests.gpu_rows import (arg_error as rows_arg_error, check_one_row, commit_sets, engine_cache, probes_ends, rand_rows,
+                            release, split_first as split, srs_cache)
 from tests.multiplicities_ref import multiplicities
 from zkp_subnet_amd import _native
 from zkp_subnet_amd._native import KzgError
@@ -28,33 +29,12 @@ SHAPES = [(1, 1), (3, 2), (16, 1), (1, 16), (2, 8)]
 
 @pytest.fixture(scope="module")
 def engines(hip):
-    """one context per log2 row length, holding worker 0's slice of a 2^lg-point SRS (machines_scale 0)"""
-    cache = {}
-
-    def get(lg):
-        if lg not in cache:
-            eng = hip()
-            eng.gen_srs(SEED_X + lg, SEED_Y, lg, 0)
-            cache[lg] = eng
-        return cache[lg]
-
-    return get
+    return engine_cache(hip, SEED_X, SEED_Y)
 
 
 @pytest.fixture(scope="module")
 def srs_of():
-    cache = {}
-
-    def get(lg):
-        if lg not in cache:
-            cache[lg] = oc.srs_gen(be(SEED_X + lg), be(SEED_Y), lg, 0, 0)
-        return cache[lg]
-
-    return get
-
-
-def rand_rows(k, T, seed):
-    return [ints(rand_scalars_bytes(T, seed + j)) for j in range(k)]
+    return srs_cache(SEED_X, SEED_Y)
 
 
 def instance(L, w, T, seed, duplicates=False):
@@ -73,42 +53,9 @@ def instance(L, w, T, seed, duplicates=False):
     return inputs, table
 
 
-def commit_sets(eng, evals, sizes, ef=True, i=0):
-    """rows given by their evaluations, committed in evaluation form or (through the oracle's INTT) in coefficient form"""
-    rows = [row_bytes(v) for v in evals]
-    if not ef:
-        rows = [oc.fr_ntt(r, True) for r in rows]
-    sets, o = [], 0
-    for s in sizes:
-        sets.append(eng.commit_rows(i, rows[o:o + s], ef))
-        o += s
-    assert o == len(rows)
-    return sets
-
-
-def release(sets):
-    for s in sets:
-        s.release()
-
-
-def split(k):
-    return (k,) if k < 3 else (1, k - 1)
-
-
 def check_against_reference(eng, srs, mset, missing, mult, want_missing, rnd, want_commitment=None):
-    T = len(mult)
-    mb = row_bytes(mult)
-    assert (mset.k, len(mset.commitments)) == (1, 1)
     assert missing == want_missing
-    assert mset.commitments[0] == (want_commitment or oc.commit(srs, mb, True))
-    dom_w = pow(7, (R - 1) // T, R)
-    ts = sorted({0, 1 % T, T - 1} | {rnd.randrange(T) for _ in range(3)})
-    for t0 in range(0, len(ts), 4):
-        part = ts[t0:t0 + 4]
-        Y = eng.eval_rows([mset], [be(pow(dom_w, t, R)) for t in part], [[0]] * len(part))
-        assert [int.from_bytes(y[0], "big") for y in Y] == [mult[t] for t in part], part
-    x = be(rnd.randrange(R))
-    assert eng.eval_rows([mset], [x], [[0]])[0][0] == oc.fr_eval(oc.fr_ntt(mb, True), x)
+    check_one_row(eng, srs, mset, mult, rnd, probes=probes_ends(len(mult), rnd), want_commitment=want_commitment)
 
 
 def run_both_forms(eng, srs, inputs, table, L, w, rnd, want=None):
@@ -442,13 +389,9 @@ def test_determinism_in_a_row_and_from_four_threads(engines, srs_of):
     assert eng.rows_stats() == before
 
 
-def _arg_error(fn, why=None, code=_native.KZG_E_ARG):
-    with pytest.raises(KzgError) as ei:
-        fn()
-    assert ei.value.code == code, ei.value
-    assert "multiplicities" in str(ei.value), str(ei.value)
-    if why:
-        assert why in str(ei.value), str(ei.value)
+def arg_error(fn, why=None, code=_native.KZG_E_ARG):
+    """every error of this builder names it"""
+    assert "multiplicities" in str(rows_arg_error(fn, why, code))
 
 
 def test_errors_leave_the_context_serving(hip):
@@ -470,11 +413,11 @@ def test_errors_leave_the_context_serving(hip):
 
     F, Tb = commit_sets(eng, inputs, (1, 3)), commit_sets(eng, table, (2,))
     fresh_ok(F, Tb)
-    _arg_error(lambda: call(F[:1], Tb, L, w), "n_lookups * width rows")             # 1 input row for 4
-    _arg_error(lambda: call(F, Tb, 4, 1), "width rows")                              # 2 table rows for w = 1
-    _arg_error(lambda: call(F, Tb + Tb, L, w), "width rows")                         # 4 table rows for w = 2
-    _arg_error(lambda: call(F, Tb, 0, w))                                            # L = 0
-    _arg_error(lambda: call(F, Tb, L, 0))                                            # w = 0
+    arg_error(lambda: call(F[:1], Tb, L, w), "n_lookups * width rows")             # 1 input row for 4
+    arg_error(lambda: call(F, Tb, 4, 1), "width rows")                              # 2 table rows for w = 1
+    arg_error(lambda: call(F, Tb + Tb, L, w), "width rows")                         # 4 table rows for w = 2
+    arg_error(lambda: call(F, Tb, 0, w))                                            # L = 0
+    arg_error(lambda: call(F, Tb, L, 0))                                            # w = 0
     hf, ht = (ctypes.c_uint64 * 2)(F[0].handle, F[1].handle), (ctypes.c_uint64 * 1)(Tb[0].handle)
     c, ms, h = ctypes.create_string_buffer(48), ctypes.c_uint64(0), ctypes.c_uint64(0)
     lib = _native.load()
@@ -491,32 +434,32 @@ def test_errors_leave_the_context_serving(hip):
     assert f(eng._h, 2, hf, 1, ht, 2, 2, c, ctypes.byref(ms), ctypes.byref(h)) == 0            # (the same call, in range)
     assert (c.raw, ms.value) == want
     eng.release_rows(h.value)
-    _arg_error(lambda: call(F * 6, Tb, 8, 2), "KZG_MAX_BATCH_OPEN rows")             # 24 input rows
+    arg_error(lambda: call(F * 6, Tb, 8, 2), "KZG_MAX_BATCH_OPEN rows")             # 24 input rows
     other = commit_sets(eng, table, (2,), i=1)                                       # another worker
-    _arg_error(lambda: call(F, other, L, w), "one worker")
+    arg_error(lambda: call(F, other, L, w), "one worker")
     short = eng.commit_rows(0, [row_bytes(r[:T // 2]) for r in table])               # another length
-    _arg_error(lambda: call(F, [short], L, w), "one worker and have one row length")
+    arg_error(lambda: call(F, [short], L, w), "one worker and have one row length")
     odd = [eng.commit_rows(0, [row_bytes(r[:T - 1]) for r in table], False), eng.commit_rows(0, [row_bytes(r[:T - 1]) for r in inputs], False)]
-    _arg_error(lambda: call(odd[1:], odd[:1], L, w), "power of two")                 # coefficient rows of length T - 1
+    arg_error(lambda: call(odd[1:], odd[:1], L, w), "power of two")                 # coefficient rows of length T - 1
     release(other + [short] + odd)
     gone = commit_sets(eng, table, (2,))
     release(gone)
-    _arg_error(lambda: call(F, gone, L, w), "released")
-    _arg_error(lambda: call([2 ** 40], Tb, L, w), "unknown")
-    _arg_error(lambda: call(F, [2 ** 40], L, w), "unknown")
+    arg_error(lambda: call(F, gone, L, w), "released")
+    arg_error(lambda: call([2 ** 40], Tb, L, w), "unknown")
+    arg_error(lambda: call(F, [2 ** 40], L, w), "unknown")
     fresh_ok(F, Tb)
     # the 65th live set
     fill = [eng.commit_rows(0, [row_bytes(table[0])]) for _ in range(_native.KZG_MAX_ROW_SETS - 3)]
     assert eng.rows_stats()[0] == _native.KZG_MAX_ROW_SETS
-    _arg_error(lambda: call(F, Tb, L, w), "KZG_MAX_ROW_SETS", code=_native.KZG_E_BUSY)
+    arg_error(lambda: call(F, Tb, L, w), "KZG_MAX_ROW_SETS", code=_native.KZG_E_BUSY)
     fill.pop().release()
     fresh_ok(F, Tb)
     release(fill)
     # stale after an SRS load, the new set with its sources
     keep, _ = call(F, Tb, L, w)
     eng.gen_srs(SEED_X, SEED_Y, lg + 1, 1)
-    _arg_error(lambda: call(F, Tb, L, w), "SRS")
-    _arg_error(lambda: call([keep], [keep], 1, 1), "SRS")
+    arg_error(lambda: call(F, Tb, L, w), "SRS")
+    arg_error(lambda: call([keep], [keep], 1, 1), "SRS")
     release(F + Tb + [keep])
     F, Tb = commit_sets(eng, inputs, (1, 3)), commit_sets(eng, table, (2,))
     fresh_ok(F, Tb)

@@ -5,7 +5,6 @@ and evaluations are compared bit for bit; the whole round opens and verifies and
 shapes, the unsatisfied instance, every documented error, threads, a racing release, the multi-GPU handle and one large row
 through the SRS trapdoor follow.  Each test leaves rows_stats() where it found it."""
 import ctypes
-import functools
 import random
 import threading
 
@@ -14,6 +13,9 @@ import pytest
 from oracle import cpu as oc
 from tests import grand_product_ref as gp
 from tests import quotient_ref as qr
+from tests.gpu_common import val
+from tests.gpu_rows import (arg_error, b_perm, b_terms, check_pieces, commit_sets, engine_cache, q_call, reference_pieces,
+                            release, srs_cache, standard)
 from zkp_subnet_amd import _native
 from zkp_subnet_amd._native import KzgError
 from zkp_subnet_amd.engine import lagrange_factor
@@ -22,97 +24,16 @@ pytestmark = pytest.mark.gpu
 R = gp.R
 be, row_bytes = gp.be, gp.row_bytes
 SEED_X, SEED_Y = 0x7A0D01, 0x7A0D02
-val = lambda b: int.from_bytes(b, "big")   # noqa: E731
 
 
 @pytest.fixture(scope="module")
 def engines(hip):
-    """one context per log2 row length, holding worker 0's slice of a 2^lg-point SRS (machines_scale 0)"""
-    cache = {}
-
-    def get(lg):
-        if lg not in cache:
-            eng = hip()
-            eng.gen_srs(SEED_X + lg, SEED_Y, lg, 0)
-            cache[lg] = eng
-        return cache[lg]
-
-    return get
+    return engine_cache(hip, SEED_X, SEED_Y)
 
 
 @pytest.fixture(scope="module")
 def srs_of():
-    cache = {}
-
-    def get(lg):
-        if lg not in cache:
-            cache[lg] = oc.srs_gen(be(SEED_X + lg), be(SEED_Y), lg, 0, 0)
-        return cache[lg]
-
-    return get
-
-
-def commit_sets(eng, evals, sizes, ef=True, i=0):
-    """rows given by their evaluations, committed in evaluation form or (through the oracle's INTT) in coefficient form"""
-    rows = [row_bytes(v) for v in evals]
-    if not ef:
-        rows = [oc.fr_ntt(r, True) for r in rows]
-    sets, o = [], 0
-    for s in sizes:
-        sets.append(eng.commit_rows(i, rows[o:o + s], ef))
-        o += s
-    assert o == len(rows)
-    return sets
-
-
-def release(sets):
-    for s in sets:
-        s.release()
-
-
-def b_terms(terms):
-    return [(be(c), rows) for c, rows in terms]
-
-
-def b_perm(perm):
-    if perm is None:
-        return None
-    out = dict(perm)
-    out["shifts"] = [be(s) for s in perm["shifts"]]
-    for name in ("beta", "gamma", "alpha"):
-        out[name] = be(perm[name])
-    return out
-
-
-def q_call(eng, sets, terms, perm, ext_log=2, n_pieces=3):
-    return eng.commit_quotient(sets, b_terms(terms), b_perm(perm), ext_log, n_pieces)
-
-
-def reference_pieces(rows, terms, perm, ext_log, P):
-    """the P piece rows of t over the evaluation rows `rows`, from tests/quotient_ref.py; the remainder must vanish"""
-    t, rem = qr.quotient([qr.coeffs_of(r) for r in rows], terms, perm, ext_log)
-    assert not any(rem)
-    return qr.pieces(t, len(rows[0]), P)
-
-
-@functools.lru_cache(maxsize=None)
-def standard(lg, seed=1):
-    rows, terms, perm = qr.standard_instance(1 << lg, seed)
-    return rows, terms, perm, reference_pieces(rows, terms, perm, 2, 3)
-
-
-def check_pieces(eng, srs, tset, want, rnd):
-    """commitments against the oracle's, evaluations at domain points and at a random point against the oracle's"""
-    P, T = len(want), len(want[0])
-    assert (tset.k, len(tset.commitments)) == (P, P)
-    wb = [row_bytes(w) for w in want]
-    for p in range(P):
-        assert tset.commitments[p] == oc.commit(srs, wb[p], False), p
-    w = gp.omega(T)
-    pts = [be(pow(w, t, R)) for t in (0, T - 1, rnd.randrange(T))] + [be(rnd.randrange(R))]
-    Y = eng.eval_rows([tset], pts, [list(range(P))] * len(pts))
-    for x, ys in zip(pts, Y):
-        assert ys == [oc.fr_eval(wb[p], x) for p in range(P)]
+    return srs_cache(SEED_X, SEED_Y)
 
 
 def num_at(vals, terms, perm, x, zw, T):
@@ -227,14 +148,6 @@ def test_other_shapes(engines, srs_of):
     assert eng.rows_stats() == before
 
 
-def _arg_error(fn, why=None, code=_native.KZG_E_ARG):
-    with pytest.raises(KzgError) as ei:
-        fn()
-    assert ei.value.code == code, ei.value
-    if why:
-        assert why in str(ei.value), str(ei.value)
-
-
 def test_unsatisfied_instance_creates_no_set(engines, srs_of):
     lg = 12
     eng, srs, T = engines(lg), srs_of(lg), 1 << lg
@@ -248,12 +161,12 @@ def test_unsatisfied_instance_creates_no_set(engines, srs_of):
         live = eng.rows_stats()
         # ONE message for both causes: the device sees a nonzero coefficient above P T and cannot tell which it is
         msg = "the constraints do not hold on the domain, or n_pieces is too small"
-        _arg_error(lambda: q_call(eng, bad, terms, perm, 2, 3), msg)                 # one qC changed
+        arg_error(lambda: q_call(eng, bad, terms, perm, 2, 3), msg)                 # one qC changed
         assert eng.rows_stats() == live
-        _arg_error(lambda: q_call(eng, good, terms, perm, 2, 2), msg)                # satisfied, but t needs three pieces
+        arg_error(lambda: q_call(eng, good, terms, perm, 2, 2), msg)                # satisfied, but t needs three pieces
         assert eng.rows_stats() == live
         wrong_z = dict(perm, z=qr.A_)                                                # not the accumulator
-        _arg_error(lambda: q_call(eng, good, terms, wrong_z, 2, 3), msg)
+        arg_error(lambda: q_call(eng, good, terms, wrong_z, 2, 3), msg)
         assert eng.rows_stats() == live
         tset = q_call(eng, good, terms, perm, 2, 3)
         try:
@@ -324,33 +237,33 @@ def test_errors_leave_the_context_serving(hip):
     assert raw(terms=bt * 3) == E_ARG                                                # 18 terms
     assert raw() == 0
     # the same through the Python layer, with the messages
-    _arg_error(lambda: call(ext_log=4))
-    _arg_error(lambda: call(n_pieces=5))
-    _arg_error(lambda: call(terms=[(be(1), [13])]), "row index")
-    _arg_error(lambda: call(perm=dict(bp, z=40)), "row index")
-    _arg_error(lambda: call(terms=[(big, [0])]), "canonical")
-    _arg_error(lambda: call(sets=S * 5))                                             # 20 handles
-    _arg_error(lambda: call(sets=S + S[:2]), "KZG_MAX_BATCH_OPEN rows")              # 13 + 3 + 5 rows
+    arg_error(lambda: call(ext_log=4))
+    arg_error(lambda: call(n_pieces=5))
+    arg_error(lambda: call(terms=[(be(1), [13])]), "row index")
+    arg_error(lambda: call(perm=dict(bp, z=40)), "row index")
+    arg_error(lambda: call(terms=[(big, [0])]), "canonical")
+    arg_error(lambda: call(sets=S * 5))                                             # 20 handles
+    arg_error(lambda: call(sets=S + S[:2]), "KZG_MAX_BATCH_OPEN rows")              # 13 + 3 + 5 rows
     other = commit_sets(eng, rows[:3], (3,), i=1)                                    # another worker
-    _arg_error(lambda: call(sets=S[:3] + other), "one worker")
+    arg_error(lambda: call(sets=S[:3] + other), "one worker")
     short = eng.commit_rows(0, [row_bytes(r[:T // 2]) for r in rows[:2]])            # another length
-    _arg_error(lambda: call(sets=S[:3] + [short]), "one worker and have one row length")
+    arg_error(lambda: call(sets=S[:3] + [short]), "one worker and have one row length")
     release(other + [short])
     gone = commit_sets(eng, rows[11:], (2,))
     release(gone)
-    _arg_error(lambda: call(sets=S[:3] + gone), "released")
-    _arg_error(lambda: call(sets=S[:3] + [2 ** 40]), "unknown")
+    arg_error(lambda: call(sets=S[:3] + gone), "released")
+    arg_error(lambda: call(sets=S[:3] + [2 ** 40]), "unknown")
     fresh_ok(S)
     # the 65th live set
     fill = [eng.commit_rows(0, [row_bytes(rows[0])]) for _ in range(_native.KZG_MAX_ROW_SETS - 4)]
     assert eng.rows_stats()[0] == _native.KZG_MAX_ROW_SETS
-    _arg_error(lambda: call(), "KZG_MAX_ROW_SETS", code=_native.KZG_E_BUSY)
+    arg_error(lambda: call(), "KZG_MAX_ROW_SETS", code=_native.KZG_E_BUSY)
     fill.pop().release()
     fresh_ok(S)
     release(fill)
     # stale after an SRS load
     eng.gen_srs(SEED_X, SEED_Y, lg + 1, 1)
-    _arg_error(lambda: call(), "SRS")
+    arg_error(lambda: call(), "SRS")
     release(S)
     S = commit_sets(eng, rows, (13,))
     fresh_ok(S)

@@ -17,61 +17,28 @@ from tests import grand_product_ref as gp
 from tests import lookup_ref as lr
 from tests import quotient_ext_ref as qx
 from tests import quotient_ref as qr
-from tests.test_gpu_quotient import (SEED_X, SEED_Y, _arg_error, b_perm, check_pieces, commit_sets, engines,  # noqa: F401
-                                     q_call, release, srs_of, standard)
+from tests.gpu_common import val
+from tests.gpu_rows import (arg_error, b_lookup, b_perm, b_terms, c_args, check_pieces, commit_sets, engine_cache, q_call,
+                            reference_pieces_ext as reference_pieces, release, srs_cache, standard, x_call)
 from zkp_subnet_amd import _native
 from zkp_subnet_amd.engine import lagrange_factor
 
 pytestmark = pytest.mark.gpu
 R = gp.R
 be, row_bytes = gp.be, gp.row_bytes
-val = lambda b: int.from_bytes(b, "big")   # noqa: E731
 E_ARG = _native.KZG_E_ARG
+SEED_X, SEED_Y = 0x7A0D01, 0x7A0D02         # those of tests/test_gpu_quotient.py: the two modules' contexts hold the same SRS
 SHAPE_MSG = "the constraints do not hold on the domain, or n_pieces is too small"
 
 
-def b_terms(terms):
-    return [(be(c), fs) for c, fs in terms]
+@pytest.fixture(scope="module")
+def engines(hip):
+    return engine_cache(hip, SEED_X, SEED_Y)
 
 
-def b_lookup(lookup):
-    if lookup is None:
-        return None
-    out = dict(lookup)
-    for name in ("theta", "beta", "alpha"):
-        out[name] = be(lookup[name])
-    return out
-
-
-def x_call(eng, sets, terms, perm=None, lookup=None, ext_log=2, n_pieces=3):
-    return eng.commit_quotient_ext(sets, b_terms(terms), b_perm(perm), b_lookup(lookup), ext_log, n_pieces)
-
-
-def c_args(terms, perm, lookup, rots=True):
-    """the three argument structs from byte-valued parts (and everything that must outlive the call)"""
-    lens = (ctypes.c_uint32 * max(len(terms), 1))(*[len(fs) for _, fs in terms])
-    flat = [qx.factor(f) for _, fs in terms for f in fs]
-    tr = (ctypes.c_uint32 * max(len(flat), 1))(*[j for j, _ in flat])
-    ro = (ctypes.c_int32 * max(len(flat), 1))(*[rot for _, rot in flat]) if rots else None
-    gate = _native.QuotientTerms(len(terms), b"".join(c for c, _ in terms), lens, tr, ro)
-    pm = lk = None
-    if perm:
-        pm = _native.QuotientPerm(len(perm["wires"]), perm["z"], (ctypes.c_uint32 * 16)(*perm["wires"]),
-                                  (ctypes.c_uint32 * 16)(*perm["sigmas"]), b"".join(perm["shifts"]), perm["beta"], perm["gamma"],
-                                  perm["alpha"])
-    if lookup:
-        w = lookup["width"]
-        lk = _native.QuotientLookup(lookup.get("L", len(lookup["inputs"]) // max(w, 1)), w,
-                                    (ctypes.c_uint32 * 32)(*lookup["inputs"]), (ctypes.c_uint32 * 32)(*lookup["table"]),
-                                    lookup["mult"], lookup["sum"], lookup["theta"], lookup["beta"], lookup["alpha"])
-    ref = lambda x: ctypes.byref(x) if x is not None else None   # noqa: E731
-    return ref(gate), ref(pm), ref(lk), (gate, pm, lk, lens, tr, ro)
-
-
-def reference_pieces(rows, terms, perm, lookup, ext_log, P):
-    t, rem = qx.quotient([qr.coeffs_of(r) for r in rows], terms, perm, lookup, ext_log)
-    assert not any(rem)
-    return qr.pieces(t, len(rows[0]), P)
+@pytest.fixture(scope="module")
+def srs_of():
+    return srs_cache(SEED_X, SEED_Y)
 
 
 # ---------------------------------------------------------------------------------------------------- equivalence
@@ -269,7 +236,7 @@ def test_unsatisfied_instances_create_no_set(engines):
                 ts = x_call(eng, [src, tset, mset, s_set], [], None, lookup, 2, 2)
                 ts.release()
             else:
-                _arg_error(lambda: x_call(eng, [src, tset, mset, s_set], [], None, lookup, 2, 2), SHAPE_MSG)
+                arg_error(lambda: x_call(eng, [src, tset, mset, s_set], [], None, lookup, 2, 2), SHAPE_MSG)
             assert eng.rows_stats() == live
         # a next-row gate broken in row T - 1 only: the row that reads rows 0 and 1 through the wrap
         rows = qx.next_row_instance(T, 33)
@@ -277,7 +244,7 @@ def test_unsatisfied_instances_create_no_set(engines):
         sets = commit_sets(eng, rows, (4,))
         made += sets
         live = eng.rows_stats()
-        _arg_error(lambda: x_call(eng, sets, qx.next_row_terms(), None, None, 2, 1), SHAPE_MSG)
+        arg_error(lambda: x_call(eng, sets, qx.next_row_terms(), None, None, 2, 1), SHAPE_MSG)
         assert eng.rows_stats() == live
     finally:
         release([good, bad, tset, mset] + made)
@@ -350,27 +317,27 @@ def test_errors_leave_the_context_serving(hip):
     # through the Python layer, with the messages
     call = lambda **kw: eng.commit_quotient_ext(kw.get("sets", S), kw.get("terms", bt), kw.get("perm", bp),   # noqa: E731
                                                 kw.get("lookup", bl), kw.get("ext_log", 2), kw.get("n_pieces", 3))
-    _arg_error(lambda: call(lookup=dict(bl, sum=40)), "row index")
-    _arg_error(lambda: call(terms=[(be(1), [(13, -1), (16, 0)])]), "row index")
-    _arg_error(lambda: call(lookup=dict(bl, theta=big)), "canonical")
-    _arg_error(lambda: call(lookup=dict(bl, alpha=be(1))), "one alpha")
-    _arg_error(lambda: call(lookup=dict(bl, inputs=[2] * 4)), "n_lookups")
-    _arg_error(lambda: call(lookup=dict(bl, sum=qr.A_)), SHAPE_MSG)                   # not the running sum
-    _arg_error(lambda: call(n_pieces=2), SHAPE_MSG)
+    arg_error(lambda: call(lookup=dict(bl, sum=40)), "row index")
+    arg_error(lambda: call(terms=[(be(1), [(13, -1), (16, 0)])]), "row index")
+    arg_error(lambda: call(lookup=dict(bl, theta=big)), "canonical")
+    arg_error(lambda: call(lookup=dict(bl, alpha=be(1))), "one alpha")
+    arg_error(lambda: call(lookup=dict(bl, inputs=[2] * 4)), "n_lookups")
+    arg_error(lambda: call(lookup=dict(bl, sum=qr.A_)), SHAPE_MSG)                   # not the running sum
+    arg_error(lambda: call(n_pieces=2), SHAPE_MSG)
     other = commit_sets(eng, rows[:3], (3,), i=1)                                     # another worker
-    _arg_error(lambda: call(sets=S[:4] + other), "one worker")
+    arg_error(lambda: call(sets=S[:4] + other), "one worker")
     short = eng.commit_rows(0, [row_bytes(r[:T // 2]) for r in rows[:3]])             # another length
-    _arg_error(lambda: call(sets=S[:4] + [short]), "one worker and have one row length")
+    arg_error(lambda: call(sets=S[:4] + [short]), "one worker and have one row length")
     release(other + [short])
     gone = commit_sets(eng, rows[13:], (3,))
     release(gone)
-    _arg_error(lambda: call(sets=S[:4] + gone), "released")
-    _arg_error(lambda: call(sets=S[:4] + [2 ** 40]), "unknown")
-    _arg_error(lambda: call(sets=S + S[:1]), "KZG_MAX_BATCH_OPEN rows")
+    arg_error(lambda: call(sets=S[:4] + gone), "released")
+    arg_error(lambda: call(sets=S[:4] + [2 ** 40]), "unknown")
+    arg_error(lambda: call(sets=S + S[:1]), "KZG_MAX_BATCH_OPEN rows")
     fresh_ok()
     # stale after an SRS load
     eng.gen_srs(SEED_X, SEED_Y, lg + 1, 1)
-    _arg_error(lambda: call(), "SRS")
+    arg_error(lambda: call(), "SRS")
     release(S)
     S = commit_sets(eng, rows, (16,))
     fresh_ok()

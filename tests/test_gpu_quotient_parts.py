@@ -17,32 +17,33 @@ from tests import blinding_ref as br
 from tests import grand_product_ref as gp
 from tests import quotient_parts_ref as qp
 from tests import quotient_ref as qr
-from tests.test_gpu_blinding import bt, engines, srs_of, zk_call  # noqa: F401  (module fixtures)
-from tests.test_gpu_quotient import b_perm, check_pieces, commit_sets, q_call, release, standard
-from tests.test_gpu_quotient_ext import b_lookup, b_terms, c_args, x_call
-from tests.test_quotient_parts_cpu import GPU_CLIENT, GPU_SPLIT, GPU_WIDE
+from tests.gpu_common import val
+from tests.gpu_rows import (arg_error, b_lookup, b_perm, b_terms, bt, c_args, check_pieces, commit_sets, engine_cache, q_call,
+                            release, srs_cache, standard, x_call, zk_call)
+from tests.quotient_parts_ref import GPU_CLIENT, GPU_SPLIT, GPU_WIDE
 from zkp_subnet_amd import _native, codec
-from zkp_subnet_amd._native import KzgError
 from zkp_subnet_amd.engine import QuotientAcc, lagrange_factor
 
 pytestmark = pytest.mark.gpu
 R = qp.R
 be, row_bytes = qp.be, qp.row_bytes
-val = lambda b: int.from_bytes(b, "big")   # noqa: E731
 E_ARG, E_BUSY = _native.KZG_E_ARG, _native.KZG_E_BUSY
+SEED_X, SEED_Y = 0xB11D01, 0xB11D02         # those of tests/test_gpu_blinding.py: the two modules' contexts hold the same SRS
+
+
+@pytest.fixture(scope="module")
+def engines(hip):
+    return engine_cache(hip, SEED_X, SEED_Y)
+
+
+@pytest.fixture(scope="module")
+def srs_of():
+    return srs_cache(SEED_X, SEED_Y)
 
 
 def part_call(eng, sets, terms, perm=None, lookup=None, active=None, link=None, ext_log=2, scale=None, acc=None):
     return eng.quotient_part(sets, b_terms(terms), b_perm(perm), b_lookup(lookup), active, link, ext_log,
                              None if scale is None else be(scale), acc)
-
-
-def _arg_error(fn, why=None, code=E_ARG):
-    with pytest.raises(KzgError) as ei:
-        fn()
-    assert ei.value.code == code, ei.value
-    if why:
-        assert why in str(ei.value), str(ei.value)
 
 
 def evals_at(eng, tset, x):
@@ -97,7 +98,7 @@ def test_one_part_and_finish_equal_the_single_call(engines, lg):
             try:
                 assert (tset.commitments, evals_at(eng, tset, zeta)) == want and (tset.k, tset.T) == (P, T)
                 assert eng.rows_stats()[0] == live[0]        # the accumulator is consumed, the piece set is live
-                _arg_error(lambda: eng.release_rows(acc.handle))
+                arg_error(lambda: eng.release_rows(acc.handle))
             finally:
                 tset.release()
     finally:
@@ -330,7 +331,7 @@ def test_broken_wide_instances_fail_the_finish_and_keep_the_accumulator(engines,
         acc = wide_parts(eng, w, S, 3)
         live = eng.rows_stats()
         assert live[0] == before[0] + len(S) + 1
-        _arg_error(lambda: eng.quotient_finish(acc, 4), "the constraints do not hold")
+        arg_error(lambda: eng.quotient_finish(acc, 4), "the constraints do not hold")
         assert eng.rows_stats() == live and not acc.released      # no set was created, the accumulator is still there
         acc.release()
         assert eng.rows_stats()[0] == live[0] - 1
@@ -385,26 +386,26 @@ def test_errors_leave_the_context_serving(hip, engines):
         acc = part_call(eng, A, terms)
         live = eng.rows_stats()
         assert live[0] == before[0] + 3 and live[1] - before[1] >= 2 * 3 * T * 32 + 4 * T * 32     # counted, with its N * 32 bytes
-        _arg_error(lambda: part_call(eng, B, terms, acc=acc), "worker")                     # another worker
-        _arg_error(lambda: part_call(eng, A, terms, ext_log=3, acc=acc), "ext_log")         # another ext_log
-        _arg_error(lambda: part_call(eng, A, terms, link=(0, 1)))                           # a link without a permutation
+        arg_error(lambda: part_call(eng, B, terms, acc=acc), "worker")                     # another worker
+        arg_error(lambda: part_call(eng, A, terms, ext_log=3, acc=acc), "ext_log")         # another ext_log
+        arg_error(lambda: part_call(eng, A, terms, link=(0, 1)))                           # a link without a permutation
         gate, pm, lk, _keep = c_args(b_terms(terms), None, None)
         hs = (ctypes.c_uint64 * 1)(A[0].handle)
         ln, h = _native.QuotientLink(0, 1), ctypes.c_uint64(acc.handle)
         assert lib.kzg_rows_quotient_part(eng._h, 1, hs, gate, None, ctypes.byref(ln), None, None, 2, None, ctypes.byref(h)) == E_ARG
         assert lib.kzg_rows_quotient_part(eng._h, 1, hs, gate, None, None, None, None, 2, bad_r, ctypes.byref(h)) == E_ARG
-        _arg_error(lambda: eng.quotient_part(A, b_terms(terms), None, None, None, None, 2, bad_r, acc), "scale")   # scale >= r
+        arg_error(lambda: eng.quotient_part(A, b_terms(terms), None, None, None, None, 2, bad_r, acc), "scale")   # scale >= r
         # start of 0 or >= r
         for start in (bytes(32), bad_r):
-            _arg_error(lambda: eng.commit_grand_product_chain(A[:1], A[:1], [be(1)] * 3, be(3), be(5), T - 3, bt([1, 2]), start))
+            arg_error(lambda: eng.commit_grand_product_chain(A[:1], A[:1], [be(1)] * 3, be(3), be(5), T - 3, bt([1, 2]), start))
         # an accumulator is no row set, and a row set no accumulator
-        _arg_error(lambda: eng.eval_rows([acc], [be(5)], [[0]]), "accumulator")
-        _arg_error(lambda: eng.open_rows([acc], [be(5)], [[0]], [be(1)]), "accumulator")
-        _arg_error(lambda: eng.commit_grand_product_zk([acc], A[:1], [be(1)], be(3), be(5), T - 3, bt([1, 2])))
-        _arg_error(lambda: part_call(eng, [acc], terms), "accumulator")
+        arg_error(lambda: eng.eval_rows([acc], [be(5)], [[0]]), "accumulator")
+        arg_error(lambda: eng.open_rows([acc], [be(5)], [[0]], [be(1)]), "accumulator")
+        arg_error(lambda: eng.commit_grand_product_zk([acc], A[:1], [be(1)], be(3), be(5), T - 3, bt([1, 2])))
+        arg_error(lambda: part_call(eng, [acc], terms), "accumulator")
         fake = QuotientAcc(eng, A[0].handle, 0, T, 2)
-        _arg_error(lambda: part_call(eng, A, terms, acc=fake), "row set")
-        _arg_error(lambda: eng.quotient_finish(fake, 2), "row set")
+        arg_error(lambda: part_call(eng, A, terms, acc=fake), "row set")
+        arg_error(lambda: eng.quotient_finish(fake, 2), "row set")
         fake.released = True
         # n_pieces outside [1, E]
         c, hh = ctypes.create_string_buffer(48 * 8), ctypes.c_uint64(0)
@@ -415,25 +416,25 @@ def test_errors_leave_the_context_serving(hip, engines):
         H8 = commit_sets(eng, [[1] * 8], (1,))
         O = commit_sets(other, [[1] * 32], (1,))
         try:
-            _arg_error(lambda: part_call(eng, H8, [(1, [0])], acc=acc), "row length")
-            _arg_error(lambda: part_call(other, O, [(1, [0])], acc=QuotientAcc(other, acc.handle, 0, 32, 2)))
+            arg_error(lambda: part_call(eng, H8, [(1, [0])], acc=acc), "row length")
+            arg_error(lambda: part_call(other, O, [(1, [0])], acc=QuotientAcc(other, acc.handle, 0, 32, 2)))
         finally:
             release(H8 + O)
         assert eng.rows_stats() == live
         # a released accumulator
         acc.release()
-        _arg_error(lambda: part_call(eng, A, terms, acc=QuotientAcc(eng, acc.handle, 0, T, 2)), "accumulator")
+        arg_error(lambda: part_call(eng, A, terms, acc=QuotientAcc(eng, acc.handle, 0, T, 2)), "accumulator")
         assert lib.kzg_rows_quotient_finish(eng._h, acc.handle, 2, c, ctypes.byref(hh)) == E_ARG
         # the 65th live object
         fill = []
         while eng.rows_stats()[0] < _native.KZG_MAX_ROW_SETS:
             fill += commit_sets(eng, rows[:1], (1,))
-        _arg_error(lambda: part_call(eng, A, terms), code=E_BUSY)
+        arg_error(lambda: part_call(eng, A, terms), code=E_BUSY)
         release(fill)
         # an accumulator made stale by an SRS reload
         acc = part_call(eng, A, terms, perm)
         eng.gen_srs(0xE46, 0xE47, 5, 1)
-        _arg_error(lambda: eng.quotient_finish(acc, 4), "stale")
+        arg_error(lambda: eng.quotient_finish(acc, 4), "stale")
         acc.release()
         # ... and the context keeps serving
         A2 = commit_sets(eng, rows, (3,))

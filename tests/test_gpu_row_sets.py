@@ -9,18 +9,15 @@ import threading
 import pytest
 
 from oracle import cpu as oc
-from tests.gpu_common import rand_scalars_bytes
+from tests.gpu_common import R, be, rand_scalars_bytes
+from tests.gpu_rows import arg_error, commit_sets, engine_cache, release
 from zkp_subnet_amd import _native
 from zkp_subnet_amd._native import KzgError
-from zkp_subnet_amd.engine import R_MODULUS as R, _root_of_unity
+from zkp_subnet_amd.engine import _root_of_unity
 
 pytestmark = pytest.mark.gpu
 TH = 16
 SEED_X, SEED_Y = 0x5EED01, 0x5EED02
-
-
-def be(v):
-    return (v % R).to_bytes(32, "big")
 
 
 def make_rows(T, k, seed):
@@ -33,35 +30,11 @@ def make_rows(T, k, seed):
 
 @pytest.fixture(scope="module")
 def engines(hip):
-    """one context per log2 row length, holding worker 0's slice of a 2^lg-point SRS (machines_scale 0)"""
-    cache = {}
-
-    def get(lg):
-        if lg not in cache:
-            eng = hip()
-            eng.gen_srs(SEED_X + lg, SEED_Y, lg, 0)
-            cache[lg] = eng
-        return cache[lg]
-
-    return get
+    return engine_cache(hip, SEED_X, SEED_Y)
 
 
 def chalk(rnd, m):
     return [be(rnd.randrange(R)) for _ in range(m)], [be(rnd.randrange(R)) for _ in range(m)]
-
-
-def commit_sets(eng, rows, sizes, ef, i=0):
-    sets, o = [], 0
-    for s in sizes:
-        sets.append(eng.commit_rows(i, rows[o:o + s], ef))
-        o += s
-    assert o == len(rows)
-    return sets
-
-
-def release(sets):
-    for s in sets:
-        s.release()
 
 
 def opened_for(k, m):
@@ -183,14 +156,6 @@ def test_long_rows_two_lane_commit(engines):
         assert eng.open_rows([rs], P, opened, G) == (Y, Pf)
 
 
-def _arg_error(fn, why=None):
-    with pytest.raises(KzgError) as ei:
-        fn()
-    assert ei.value.code == _native.KZG_E_ARG, ei.value
-    if why:
-        assert why in str(ei.value), str(ei.value)
-
-
 def test_lifecycle(hip):
     eng = hip()
     lg = 8
@@ -209,9 +174,9 @@ def test_lifecycle(hip):
     # open after release, double release
     rs = eng.commit_rows(0, rows)
     rs.release()
-    _arg_error(lambda: eng.open_rows([rs], P, opened, G))
-    _arg_error(lambda: eng.release_rows(rs.handle))
-    _arg_error(lambda: eng.release_rows(0))
+    arg_error(lambda: eng.open_rows([rs], P, opened, G))
+    arg_error(lambda: eng.release_rows(rs.handle))
+    arg_error(lambda: eng.release_rows(0))
     fresh_ok()
     # handles are not reused
     a = eng.commit_rows(0, rows[:1])
@@ -221,23 +186,23 @@ def test_lifecycle(hip):
     b.release()
     # sets of two workers, sets of two lengths
     s0, s1 = eng.commit_rows(0, rows[:2]), eng.commit_rows(1, rows[2:])
-    _arg_error(lambda: eng.open_rows([s0, s1], P, opened, G), "one worker")
+    arg_error(lambda: eng.open_rows([s0, s1], P, opened, G), "one worker")
     short = eng.commit_rows(0, [r[:32 * (T // 2)] for r in rows[2:]])
-    _arg_error(lambda: eng.open_rows([s0, short], P, opened, G), "one row length")
+    arg_error(lambda: eng.open_rows([s0, short], P, opened, G), "one row length")
     release([s0, s1, short])
     fresh_ok()
     # more than 16 rows in all
     big = [eng.commit_rows(0, make_rows(T, 9, 1)), eng.commit_rows(0, make_rows(T, 8, 2))]
-    _arg_error(lambda: eng.open_rows(big, P[:1], [[0]], G[:1]), "KZG_MAX_BATCH_OPEN")
+    arg_error(lambda: eng.open_rows(big, P[:1], [[0]], G[:1]), "KZG_MAX_BATCH_OPEN")
     # a mask past the concatenated rows; the single set still opens
-    _arg_error(lambda: eng.open_rows(big[1:], P[:1], [[8]], G[:1]))
+    arg_error(lambda: eng.open_rows(big[1:], P[:1], [[8]], G[:1]))
     release(big)
     fresh_ok()
     # argument checks of the commit
-    _arg_error(lambda: eng.commit_rows(2, rows))                               # worker outside the SRS
-    _arg_error(lambda: eng.commit_rows(0, make_rows(T, 17, 3)))                # k = 17
-    _arg_error(lambda: eng.commit_rows(0, [r + r for r in rows]))             # longer than the slice
-    _arg_error(lambda: eng.commit_rows(0, [r[:32 * 3] for r in rows]))        # evaluation form of length 3
+    arg_error(lambda: eng.commit_rows(2, rows))                               # worker outside the SRS
+    arg_error(lambda: eng.commit_rows(0, make_rows(T, 17, 3)))                # k = 17
+    arg_error(lambda: eng.commit_rows(0, [r + r for r in rows]))             # longer than the slice
+    arg_error(lambda: eng.commit_rows(0, [r[:32 * 3] for r in rows]))        # evaluation form of length 3
     fresh_ok()
     # the cap: KZG_MAX_ROW_SETS live sets, then KZG_E_BUSY until one is released
     cap = []
@@ -260,7 +225,7 @@ def test_lifecycle(hip):
     # an SRS reload makes every live set stale; its release still succeeds
     st = eng.commit_rows(0, rows)
     eng.gen_srs(SEED_X, SEED_Y, lg + 1, 1)
-    _arg_error(lambda: eng.open_rows([st], P, opened, G), "SRS")
+    arg_error(lambda: eng.open_rows([st], P, opened, G), "SRS")
     assert eng.rows_stats()[0] == 1
     st.release()
     assert eng.rows_stats() == (0, 0)

@@ -11,14 +11,14 @@ import pytest
 
 from oracle import cpu as oc
 from tests import shplonk_ref as ref
-from tests.gpu_common import rand_scalars_bytes
+from tests.gpu_common import R, be, rand_scalars_bytes, val as ib
+from tests.gpu_rows import arg_error, commit_sets, engine_cache, release, split_halves as split, srs_cache
 from zkp_subnet_amd import _native
 from zkp_subnet_amd._native import KzgError
-from zkp_subnet_amd.engine import R_MODULUS as R, _root_of_unity, lagrange_factor
+from zkp_subnet_amd.engine import _root_of_unity, lagrange_factor
 
 pytestmark = pytest.mark.gpu
 SEED_X, SEED_Y = 0x5A9107, 0x5A9108
-be, ib = ref.be, lambda b: int.from_bytes(b, "big")
 INF = bytes([0xC0]) + bytes(47)
 
 # more than four groups (a second batch on the device): six rows, six different point sets over three points
@@ -29,44 +29,10 @@ SPECIAL = (8, [[0, 1, 2, 3, 4, 5, 6, 7], [3, 4, 5, 6], [5, 6], [7]])
 
 @pytest.fixture(scope="module")
 def engines(hip):
-    """one context per log2 row length, holding worker 0's slice of a 2^lg-point SRS (machines_scale 0)"""
-    cache = {}
-
-    def get(lg):
-        if lg not in cache:
-            eng = hip()
-            eng.gen_srs(SEED_X + lg, SEED_Y, lg, 0)
-            cache[lg] = eng
-        return cache[lg]
-
-    return get
+    return engine_cache(hip, SEED_X, SEED_Y)
 
 
-_SRS = {}
-
-
-def oracle_srs(lg):
-    if lg not in _SRS:
-        _SRS[lg] = oc.srs_gen(be(SEED_X + lg), be(SEED_Y), lg, 0, 0)
-    return _SRS[lg]
-
-
-def commit_sets(eng, rows, sizes, ef=True, i=0):
-    sets, o = [], 0
-    for s in sizes:
-        sets.append(eng.commit_rows(i, rows[o:o + s], ef))
-        o += s
-    assert o == len(rows)
-    return sets
-
-
-def release(sets):
-    for s in sets:
-        s.release()
-
-
-def split(k):
-    return (k,) if k < 3 else (k // 2, k - k // 2)
+oracle_srs = srs_cache(SEED_X, SEED_Y)
 
 
 def points_for(rnd, T, m, special=False):
@@ -233,14 +199,6 @@ def test_one_group_with_gamma_powers_is_the_gwc_proof(engines, lg):
 
 
 # ------------------------------------------------------------------------------------- 4. errors
-def _arg_error(fn, needle=None):
-    with pytest.raises(KzgError) as ei:
-        fn()
-    assert ei.value.code == _native.KZG_E_ARG, ei.value
-    if needle:
-        assert needle in str(ei.value), ei.value
-
-
 def test_errors_leave_the_context_serving(hip):
     eng = hip()
     lg = 4
@@ -279,16 +237,16 @@ def test_errors_leave_the_context_serving(hip):
     small = hip()
     small.gen_srs(SEED_X, SEED_Y, 2, 0)
     with small.commit_rows(0, [rand_scalars_bytes(4, 1)], False) as tiny:
-        _arg_error(lambda: small.commit_shplonk([tiny], [be(1), be(2), be(3), be(4)], [[0]] * 4, [be(1)]), "T or more")
+        arg_error(lambda: small.commit_shplonk([tiny], [be(1), be(2), be(3), be(4)], [[0]] * 4, [be(1)]), "T or more")
         w, h = small.commit_shplonk([tiny], [be(1), be(2), be(3)], [[0]] * 3, [be(1)])   # three points: a constant h
         h.release()
     # handles: released, another worker, mixed workers
     gone = eng.commit_rows(0, rows)
     gone.release()
-    _arg_error(lambda: eng.commit_shplonk([gone], P, opened, C), "released")
+    arg_error(lambda: eng.commit_shplonk([gone], P, opened, C), "released")
     good()
     with eng.commit_rows(1, rows[:2]) as other:
-        _arg_error(lambda: eng.commit_shplonk([rs, other], P, [[0, 1, 2, 3, 4, 5], [3]], C + [be(1), be(2)]), "one worker")
+        arg_error(lambda: eng.commit_shplonk([rs, other], P, [[0, 1, 2, 3, 4, 5], [3]], C + [be(1), be(2)]), "one worker")
     good()
     # KZG_E_BUSY at the 65th set
     held = [eng.commit_rows(0, rows[:1]) for _ in range(_native.KZG_MAX_ROW_SETS - 1)]
@@ -299,7 +257,7 @@ def test_errors_leave_the_context_serving(hip):
     good()
     # a source set made stale by an SRS load
     eng.gen_srs(SEED_X, SEED_Y, lg + 1, 1)
-    _arg_error(lambda: eng.commit_shplonk([rs], P, opened, C), "SRS")
+    arg_error(lambda: eng.commit_shplonk([rs], P, opened, C), "SRS")
     rs.release()
     rs = eng.commit_rows(0, rows)
     good()

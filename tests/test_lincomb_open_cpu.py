@@ -14,6 +14,7 @@ import pytest
 
 from oracle import bls12_381 as o
 from oracle import cpu as oc
+from tests.gpu_common import be
 from zkp_subnet_amd import MultiDeviceClient, _native, codec
 from zkp_subnet_amd.build import build
 from zkp_subnet_amd.client import Client
@@ -24,10 +25,6 @@ from zkp_subnet_amd.verifier import Verifier
 R = o.R
 E_ARG = _native.KZG_E_ARG
 _HANDLES = itertools.count(1)
-
-
-def be(v):
-    return (v % R).to_bytes(32, "big")
 
 
 @pytest.fixture(scope="module")

@@ -13,6 +13,7 @@ import pytest
 from tests import blinding_ref as br
 from tests import quotient_parts_ref as qp
 from tests import quotient_ref as qr
+from tests.quotient_parts_ref import GPU_CLIENT, GPU_SPLIT, GPU_WIDE
 from zkp_subnet_amd import MultiDeviceClient, _native
 from zkp_subnet_amd.client import Client
 from zkp_subnet_amd.codec import be32_to_fr
@@ -22,10 +23,6 @@ R = qp.R
 E_ARG = _native.KZG_E_ARG
 _HANDLES = itertools.count(1)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# the wide instances of tests/test_gpu_quotient_parts.py: (lg, usable, seed)
-GPU_WIDE = [(8, (1 << 8) - 5, 21), (16, (1 << 16) - 6, 23)]
-GPU_CLIENT = (6, 58, 25)     # the round through the Client's text forms
-GPU_SPLIT = [(4, 11, 31), (8, (1 << 8) - 6, 32), (10, (1 << 10) - 6, 33)]
 
 
 def split_three(inst):
