@@ -602,6 +602,63 @@ int kzg_rows_commit_grand_product_chain(kzg_ctx* ctx, uint32_t n_wire_handles, c
                                         const uint8_t gamma_be32[32], uint64_t usable,
                                         const uint8_t* tail_be32 /* (T-usable-1)*32, or NULL */, const uint8_t start_be32[32],
                                         uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle);
+/* THE SHUFFLE: a set built FROM sets, the running product of a shuffle argument ("the tuples of these columns are, as a
+ * multiset over the rows, the tuples of those columns": memory consistency, sorted-column range checks, data handed between
+ * regions), computed and committed on the device from rows that are already resident.  It has no table and no
+ * multiplicities.  The concatenated rows of the input_handles sets are the G * w rows a_{g,c}, group-major (g < G = n_groups,
+ * c < w = width, the order of the lookups' inputs); those of the shuffle_handles sets are the G * w rows b_{g,c}.  With w_T
+ * the T-th root of unity of evaluation_form = 1 rows (7^((r-1)/T), natural order) and t in [0, T):
+ *   A_g(w_T^t) = sum_c theta^c a_{g,c}(w_T^t),   B_g(w_T^t) = sum_c theta^c b_{g,c}(w_T^t)       (theta unused when w = 1)
+ *   nf_g = gamma + A_g                    df_g = gamma + B_g                    (no selector on that side of group g)
+ *   nf_g = 1 + q_g (gamma + A_g - 1)      df_g = 1 + q'_g (gamma + B_g - 1)     (with a selector row q_g / q'_g)
+ *   N_t = prod_g nf_g(w_T^t),   D_t = prod_g df_g(w_T^t)
+ *   z(w_T^0) = 1,  z(w_T^(t+1)) = z(w_T^t) N_t / D_t  (t < T - 1),   closing = prod_t N_t / prod_t D_t.
+ * The call creates a new ONE-ROW set of the same worker and length holding z's coefficients, exactly as if z's T evaluations
+ * had gone through kzg_rows_commit(i, 1, z, T, 1, ..): out_commitment48 equals that call's byte for byte and *out_handle opens,
+ * evaluates, combines, releases, goes stale and counts against KZG_MAX_ROW_SETS (KZG_E_BUSY; KZG_E_NOMEM on a failed
+ * allocation -- the lane's workspace is the grand product's four T-element vectors and scan scratch plus ONE more T-element
+ * vector when a selector is named, whatever G and w are) like any other.  out_closing32 is canonical big-endian: 1 exactly
+ * when the product closes.  The library does not judge it.  Nothing row-sized crosses the host link in either direction (the
+ * tail rides in a kernel argument).
+ * opts (NULL: no selectors, plain layout):
+ *   Selectors are ordinary resident rows of the same worker and length, the caller's fixed columns, addressed as in the _sel
+ *   calls: input_sel[g] / shuffle_sel[g] (G entries each; a NULL list: none on that side) is KZG_NO_SELECTOR or indexes the
+ *   concatenated rows of the sel_handles sets; one row may serve several places.  A disabled cell (q = 0) contributes the
+ *   factor 1 whatever it holds; with boolean selectors the product closes exactly when the enabled input tuples are a
+ *   permutation of the enabled shuffle tuples.  The library does not judge a selector's contents, as it does not judge the
+ *   active column; an all-ones selector row gives the bytes of the call without it.
+ *   usable = 0 is the plain layout.  Anything else is the layout of kzg_rows_commit_grand_product_zk with u = usable:
+ *   N_t = D_t = 1 on the rows t >= u (a zero df there is no error), z(w_T^u) = closing, z(w_T^t) = tail[t - u - 1] behind it;
+ *   1 <= u <= T - 1, T - u <= KZG_MAX_BLIND_ROWS, tail_be32 NULL exactly when u = T - 1.
+ *   With opts == NULL, or usable == 0 and every entry KZG_NO_SELECTOR, exactly the plain path runs.
+ * Handle lists follow kzg_rows_open: 1 .. KZG_MAX_BATCH_OPEN handles each, a handle may repeat (also across the lists), unknown /
+ * released / stale -> KZG_E_ARG; every set named must belong to one worker and one (power-of-two) T.  KZG_E_ARG with a message
+ * that names the cause: G = 0, w = 0 or G * w > KZG_MAX_BATCH_OPEN; an input or shuffle concatenation that does not hold
+ * exactly G * w rows; a selector index that is neither KZG_NO_SELECTOR nor below the number of selector rows; selector indices
+ * given with no selector handles; theta, gamma or a tail scalar >= r; u >= T, T - u > KZG_MAX_BLIND_ROWS, tail_be32 NULL with
+ * u < T - 1, or a tail with usable = 0.  A zero denominator (some D_t = 0 on a row that counts) leaves z undefined: it is found
+ * on the device and answered with KZG_E_ARG "zero denominator", no set created.  The source sets are only read; a release or an
+ * SRS load racing the call follows the rules of kzg_rows_open.  Thread-safe like every call; after any error the context keeps
+ * serving.
+ * SOUNDNESS: theta and gamma must be drawn AFTER the commitments of all input and shuffle rows are fixed.  closing = 1 is NOT
+ * the argument: the relation z(w_T X) prod_g df_g(X) = z(X) prod_g nf_g(X) on the rows that count belongs in the caller's
+ * quotient, where it is a sum of products of rows at rotations 0 and 1 -- gate terms of kzg_rows_commit_quotient_ext / _zk /
+ * kzg_rows_quotient_part, no new quotient call.  "z = 1 at row 0" and, under blinding, "z = 1 at row u" stay ordinary gate terms
+ * over a caller row L_0 / L_u, as for the permutation.  There is NO BLINDING beyond the rows the caller passes, and the library
+ * derives no challenge. */
+typedef struct kzg_shuffle_opts {
+    uint32_t n_sel_handles;
+    const uint64_t* sel_handles;
+    const uint32_t* input_sel;     /* G entries, KZG_NO_SELECTOR = none; NULL = none at all */
+    const uint32_t* shuffle_sel;   /* the same for the shuffle side */
+    uint64_t usable;               /* 0: plain layout; else the _zk layout */
+    const uint8_t* tail_be32;      /* (T - usable - 1) * 32, or NULL */
+} kzg_shuffle_opts;
+int kzg_rows_commit_shuffle(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                            uint32_t n_shuffle_handles, const uint64_t* shuffle_handles, uint32_t n_groups, uint32_t width,
+                            const uint8_t theta_be32[32], const uint8_t gamma_be32[32],
+                            const kzg_shuffle_opts* opts /* NULL: no selectors, plain layout */, uint8_t out_commitment48[48],
+                            uint8_t out_closing32[32], uint64_t* out_handle);
 /* THE QUOTIENT WITH LOOKUP SELECTORS: kzg_rows_commit_quotient_zk and kzg_rows_quotient_part for lookups that are enabled on
  * some rows only.  selectors->selector_rows holds L = lookup->n_lookups entries, each a row index into the call's concatenated
  * rows (the caller's fixed column q_l, the row that kzg_rows_commit_multiplicities_sel / _lookup_sum_sel read) or
@@ -939,6 +996,11 @@ int kzg_multi_rows_commit_grand_product_chain(kzg_multi* mh, uint32_t i, uint32_
                                               const uint8_t gamma_be32[32], uint64_t usable, const uint8_t* tail_be32,
                                               const uint8_t start_be32[32], uint8_t out_commitment48[48],
                                               uint8_t out_closing32[32], uint64_t* out_handle);
+/* kzg_rows_commit_shuffle on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_shuffle(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                  uint32_t n_shuffle_handles, const uint64_t* shuffle_handles, uint32_t n_groups, uint32_t width,
+                                  const uint8_t theta_be32[32], const uint8_t gamma_be32[32], const kzg_shuffle_opts* opts,
+                                  uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

@@ -68,6 +68,12 @@ class QuotientSelectors(ctypes.Structure):
     _fields_ = [("selector_rows", ctypes.POINTER(_U32))]
 
 
+class ShuffleOpts(ctypes.Structure):
+    """kzg_shuffle_opts"""
+    _fields_ = [("n_sel_handles", _U32), ("sel_handles", ctypes.POINTER(_U64)), ("input_sel", ctypes.POINTER(_U32)),
+                ("shuffle_sel", ctypes.POINTER(_U32)), ("usable", _U64), ("tail_be32", _B)]
+
+
 class QuotientLink(ctypes.Structure):
     """kzg_quotient_link"""
     _fields_ = [("prev_row", _U32), ("rot", ctypes.c_int32)]
@@ -108,6 +114,8 @@ SYMBOLS = {
                                      ctypes.POINTER(_U64)]),
     "kzg_rows_commit_grand_product": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _B, _B, _B, _B, _B,
                                            ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_shuffle": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _B, _B,
+                                     ctypes.POINTER(ShuffleOpts), _B, _B, ctypes.POINTER(_U64)]),
     "kzg_rows_commit_lookup_sum": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B, _B, _B, _B,
                                         ctypes.POINTER(_U64)]),
     "kzg_rows_commit_multiplicities": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _B,
@@ -207,6 +215,8 @@ SYMBOLS = {
                                            ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_grand_product": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _B, _B, _B,
                                                  _B, _B, ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_shuffle": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _B, _B,
+                                           ctypes.POINTER(ShuffleOpts), _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_lookup_sum": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B,
                                               _B, _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_multiplicities": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32,

@@ -580,6 +580,54 @@ class Client:
         usable, tb = (None, []) if usable is None else self._blind("worker_commit_multiplicities_sel", usable, tail)
         return self._with_missing(*self.engine.commit_multiplicities_sel(*args, usable, tb))
 
+    # ---- the shuffle: ONE call for its plain, selector and blinding-rows forms
+    def _shuffle_args(self, what: str, input_handles, shuffle_handles, n_groups, width, theta, gamma, sel_handles, input_sel,
+                      shuffle_sel, usable, tail) -> tuple:
+        """The engine's arguments, in its order"""
+        hi, hs = _handles(input_handles), _handles(shuffle_handles)
+        n_groups, width = self._lookup_shape(what, n_groups, width)
+        hq, sides = _handles(sel_handles) if sel_handles else [], []
+        for idx in (input_sel, shuffle_sel):
+            sides.append(None if idx is None else self._selectors(what, hq, idx, n_groups)[1])
+        sc = [codec.fr_to_be32(x) for x in (theta, gamma)]
+        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in sc):
+            raise codec.CodecError(f"{what}: theta and gamma must be canonical scalars (< r)")
+        usable, tb = (None, []) if usable is None else self._blind(what, usable, tail)
+        return (hi, hs, n_groups, width, sc[0], sc[1], hq, sides[0], sides[1], usable, tb)
+
+    @_guard
+    def worker_commit_shuffle(self, input_handles: Sequence[int], shuffle_handles: Sequence[int], n_groups: int, width: int,
+                              theta: str, gamma: str, sel_handles: Optional[Sequence[int]] = None,
+                              input_sel: Optional[Sequence[Optional[int]]] = None,
+                              shuffle_sel: Optional[Sequence[Optional[int]]] = None, usable: Optional[int] = None,
+                              tail: Sequence[str] = ()):
+        """Extension: the running product z of a shuffle argument over the rows of committed sets (n_groups * width input
+        rows from input_handles, group-major, against as many shuffle rows from shuffle_handles), computed and committed on
+        the device as a new one-row set.  input_sel / shuffle_sel: null, or per group null or that side's selector row in the
+        concatenated rows of the sel_handles sets (a disabled cell contributes the factor 1).  usable = null is the plain
+        layout; otherwise z(w^usable) is the closing value and z's rows behind it are `tail`, as for
+        worker_commit_grand_product_zk.  Returns its handle, its commitment and the closing value (1 when the product
+        closes).  theta and gamma must be drawn after the commitments of all input and shuffle rows are fixed; the argument is
+        the relation of shuffle_quotient_terms in the caller's quotient, not the closing value."""
+        args = self._shuffle_args("worker_commit_shuffle", input_handles, shuffle_handles, n_groups, width, theta, gamma,
+                                  sel_handles, input_sel, shuffle_sel, usable, tail)
+        return self._with_closing(*self.engine.commit_shuffle(*args))
+
+    @staticmethod
+    def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: Sequence[int], n_groups: int, width: int,
+                               theta: str, gamma: str, coeff: str, active_row: Optional[int] = None,
+                               input_sel: Optional[Sequence[Optional[int]]] = None,
+                               shuffle_sel: Optional[Sequence[Optional[int]]] = None, ext_log: int = 2) -> list:
+        """engine.shuffle_quotient_terms in the text form of worker_commit_quotient_ext / _zk / worker_quotient_part: the
+        relation coeff * A * [z(wX) prod_g df_g - z(X) prod_g nf_g] as [coefficient, [[row, rot], ..]] terms.  The relations
+        "z = 1 at row 0" and "z = 1 at row usable" stay the caller's gate terms over its rows L_0 / L_u."""
+        from .engine import shuffle_quotient_terms
+
+        terms = shuffle_quotient_terms(z_row, input_rows, shuffle_rows, n_groups, width, codec.fr_to_be32(theta),
+                                       codec.fr_to_be32(gamma), codec.fr_to_be32(coeff), active_row, input_sel, shuffle_sel,
+                                       ext_log)
+        return [[codec.be32_to_fr(c), [[row, rot] for row, rot in fs]] for c, fs in terms]
+
     @_guard
     def worker_commit_quotient_zk(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None,
                                   ext_log: int = 2, n_pieces: int = 3):

@@ -442,6 +442,16 @@ int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& 
                            uint64_t T, const uint8_t* shifts_be32, const uint8_t* beta_be32, const uint8_t* gamma_be32,
                            uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den,
                            const Blind* zk = nullptr, const uint8_t* start_be32 = nullptr);
+// The selectors of kzg_rows_commit_shuffle (checked by the caller): per group the resident row (coefficients) that is q_g on
+// the input side and q'_g on the shuffle side; null: the side has no selector there
+struct ShuffleSel {
+    const uint32_t *in[POLY_MAX_ROWS], *sh[POLY_MAX_ROWS];
+};
+// the shuffle grand product of n_groups x width input rows against as many shuffle rows into a new one-row set's buffer dst:
+// its commitment, the closing value, and whether some denominator was zero (z undefined: the caller creates no set)
+int rows_shuffle_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& shuffles, uint32_t n_groups,
+                     uint32_t width, uint64_t T, const uint8_t* theta_be32, const uint8_t* gamma_be32, uint32_t* dst,
+                     uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den, const Blind* zk, const ShuffleSel* sel);
 // the lookup running sum over n_lookups x width input rows, width table rows and the multiplicity row `mult` into a new one-row
 // set's buffer dst: its commitment, the closing value, and whether some denominator was zero (the caller creates no set)
 int rows_lookup_sum_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& table, const uint32_t* mult,

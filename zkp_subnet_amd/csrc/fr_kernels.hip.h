@@ -95,6 +95,11 @@ void launch_words_differ(hipStream_t s, const uint32_t* a, const uint32_t* b, ui
 void launch_gp_factors(hipStream_t s, const uint32_t* ea, const uint32_t* es, uint32_t* N, uint32_t* D, uint64_t n,
                        const uint32_t* tw, const uint8_t beta_be32[32], const uint8_t gamma_be32[32],
                        const uint8_t shift_be32[32], bool first, uint32_t* bad);
+// kzg_rows_commit_shuffle: one side of one group folded into its running vector: with v = acc theta + e (acc given) or e,
+// V[t] (*)= gamma + v, or 1 + sel[t] (gamma + v - 1) when sel is given (first: written instead of multiplied).  e, acc, sel: n
+// canonical Montgomery elements each; theta, gamma as 32 big-endian HOST bytes, *bad raised when >= r
+void launch_sh_factor(hipStream_t s, const uint32_t* e, const uint32_t* acc_or_null, uint32_t* V, const uint32_t* sel_or_null,
+                      uint64_t n, const uint8_t theta_be32[32], const uint8_t gamma_be32[32], bool first, uint32_t* bad);
 // N[t] <- z(w^t) = (prod_{u<t} N_u) (prod_{u>=t} D_u) / prod_u D_u (D is consumed); scrN, scrD: (n + 3) / 4 * 3 / 2 + 64
 // elements of scratch each.  closing_be (device): prod N / prod D, 32 bytes big-endian; *zero_flag (device): 1 when
 // prod D == 0 (z undefined, N then holds zeros), else 0

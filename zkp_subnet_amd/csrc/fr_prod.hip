@@ -3,6 +3,7 @@
 // with the monoid "multiply") and the library's one device-side Fr inversion.
 //   N_t = prod_j (a_j(w^t) + beta s_j w^t + gamma),  D_t = prod_j (a_j(w^t) + beta sigma_j(w^t) + gamma)
 //   z(w^t) = (prod_{u<t} N_u) (prod_{u>=t} D_u) (prod_u D_u)^-1        -- ONE inversion per call, no batch inversion
+// kzg_rows_commit_shuffle feeds the same scans: its N and D come from k_sh_factor (one group and side per launch) instead.
 // Every kernel is a chain of fr9_mul: running values stay in the product's output class and are canonicalised on store.
 #include <cstring>
 
@@ -133,6 +134,87 @@ void launch_gp_factors(hipStream_t s, const uint32_t* ea, const uint32_t* es, ui
     memcpy(arg.shift.w, shift_be32, 32);
     if (first) k_gp_factors<true><<<nblk(n, 256), 256, 0, s>>>(ea, es, N, D, n, tw, arg, bad);
     else k_gp_factors<false><<<nblk(n, 256), 256, 0, s>>>(ea, es, N, D, n, tw, arg, bad);
+}
+
+// ------------------------------------------------------------------------------------------------ shuffle factors
+// kzg_rows_commit_shuffle: one side of one group closes its Horner chain in theta and enters its running vector V (N for the
+// input side, D for the shuffle side).  e holds the group's column 0 (n evaluations, Montgomery, natural order), acc the chain
+// over the columns behind it (HAS_ACC; those steps are fr_lookup.hip's LK_HORNER).  With v = acc theta + e, or e alone:
+//   V[t] (*)= gamma + v                         (no selector)
+//   V[t] (*)= 1 + q[t] (gamma + v - 1)          (HAS_SEL: q the side's selector row in evaluation form, ANY element of Fr)
+// theta and gamma (gamma - 1 under HAS_SEL) are converted to Montgomery form once per workgroup (two lanes).  FIRST: the
+// vector is written, not multiplied.  Multiplier-bound: one product each for HAS_ACC, HAS_SEL and !FIRST, so 0 .. 3 per
+// element, 32 - 128 B in, 32 B out.  Operand classes: e, acc, q and V are loaded canonical; acc theta is a product's output
+// below 2r, so gamma + v stays below 4r with limbs < 2^31, a legal FIRST operand; q (gamma + v - 1) + 1 is below 3r.
+struct ShArg {
+    FrArg theta, gamma;
+    const uint32_t* sel;
+};
+template <bool FIRST, bool HAS_ACC, bool HAS_SEL>
+__global__ void __launch_bounds__(256) k_sh_factor(const uint32_t* __restrict__ e, const uint32_t* __restrict__ acc,
+                                                    uint32_t* __restrict__ V, uint64_t n, const ShArg arg,
+                                                    uint32_t* __restrict__ bad) {
+    __shared__ uint32_t cst[2][9];   // theta, gamma (HAS_SEL: gamma - 1)
+    const uint32_t lane = threadIdx.x;
+    if (lane < 2) {
+        fr9_t c;
+        fr9_from_arg(c, lane ? arg.gamma : arg.theta, bad, blockIdx.x == 0);
+        if (HAS_SEL && lane) {
+            fr9_t one;
+            fr9_one(one);
+            fr9_sub4(c, c, one);              // gamma + 4r - 1
+            fr9_reduce(c, c);
+        }
+#pragma unroll
+        for (int i = 0; i < 9; i++) cst[lane][i] = c.l[i];
+    }
+    __syncthreads();
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + lane;
+    if (t >= n) return;
+    fr9_t v, x, g;
+    fr9_load(v, e + 8 * t);
+    if constexpr (HAS_ACC) {
+        fr9_t a, theta;
+#pragma unroll
+        for (int i = 0; i < 9; i++) theta.l[i] = cst[0][i];
+        fr9_load(a, acc + 8 * t);
+        fr9_mul(x, a, theta);
+        fr9_add(v, v, x);                     // < 3r, limbs < 2^30
+    }
+#pragma unroll
+    for (int i = 0; i < 9; i++) g.l[i] = cst[1][i];
+    fr9_add(v, v, g);                         // < 4r, limbs < 2^31
+    if constexpr (HAS_SEL) {
+        fr9_t q;
+        fr9_load(q, arg.sel + 8 * t);         // canonical
+        fr9_mul(x, v, q);
+        fr9_one(g);
+        fr9_add(v, x, g);                     // < 3r, limbs < 2^30
+    }
+    if constexpr (FIRST) {
+        fr9_reduce(v, v);
+    } else {
+        fr9_t o;
+        fr9_load(o, V + 8 * t);
+        fr9_mul(v, v, o);
+        fr9_canon(v, v);
+    }
+    fr9_store(V + 8 * t, v);
+}
+void launch_sh_factor(hipStream_t s, const uint32_t* e, const uint32_t* acc_or_null, uint32_t* V, const uint32_t* sel_or_null,
+                      uint64_t n, const uint8_t theta_be32[32], const uint8_t gamma_be32[32], bool first, uint32_t* bad) {
+    if (!n) return;
+    ShArg arg;
+    memcpy(arg.theta.w, theta_be32, 32);
+    memcpy(arg.gamma.w, gamma_be32, 32);
+    arg.sel = sel_or_null;
+    const dim3 g(nblk(n, 256));
+#define SH_GO(F, A, S) k_sh_factor<F, A, S><<<g, 256, 0, s>>>(e, acc_or_null, V, n, arg, bad)
+#define SH_SEL(F, A) do { if (sel_or_null) SH_GO(F, A, true); else SH_GO(F, A, false); } while (0)
+    if (first) { if (acc_or_null) SH_SEL(true, true); else SH_SEL(true, false); }
+    else { if (acc_or_null) SH_SEL(false, true); else SH_SEL(false, false); }
+#undef SH_SEL
+#undef SH_GO
 }
 
 // ------------------------------------------------------------------------------------------------ product scans

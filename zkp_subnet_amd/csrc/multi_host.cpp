@@ -455,6 +455,15 @@ int kzg_multi_rows_commit_grand_product_chain(kzg_multi* mh, uint32_t i, uint32_
                                             beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle, &zk, start_be32);
     });
 }
+int kzg_multi_rows_commit_shuffle(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                  uint32_t n_shuffle_handles, const uint64_t* shuffle_handles, uint32_t n_groups, uint32_t width,
+                                  const uint8_t theta_be32[32], const uint8_t gamma_be32[32], const kzg_shuffle_opts* opts,
+                                  uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_shuffle(c, s, n_input_handles, input_handles, n_shuffle_handles, shuffle_handles, n_groups, width,
+                                      theta_be32, gamma_be32, opts, out_commitment48, out_closing32, out_handle);
+    });
+}
 int kzg_multi_rows_commit_lookup_sum(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                      uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
                                      uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32],

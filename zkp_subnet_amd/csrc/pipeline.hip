@@ -777,6 +777,36 @@ int rows_shplonk_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, ui
     }
     return multi_msms_finish(ctx, H, i, T, dst, 1, 0, 0, out_c48, nullptr, nullptr);
 }
+// The back half of a grand product, the permutation's and the shuffle's alike: the running vectors N and D (T factors each,
+// in the lane's bcomb / qbuf) become z's evaluations through the product scans and the one inversion (fr_prod.hip); the inverse
+// transform writes z's coefficients straight into the new set's buffer `dst`; one MSM commits.  The record's first two
+// evaluation slots carry the closing value and the zero-denominator flag word.
+static int grand_product_finish_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, uint32_t* N, uint32_t* D, uint64_t T, uint32_t* dst,
+                                    uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den, const Blind* zk,
+                                    const uint8_t* start_be32) {
+    Lane& A = H.L();
+    uint8_t* rec = A.brec.as<uint8_t>();
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        // _zk: N_t = D_t = 1 on the rows >= usable (whatever their cells hold, a zero D_t included), so the unchanged scan
+        // leaves z = closing on every one of them; the tail then replaces the rows behind row `usable`
+        if (zk) launch_blind_mask(A.stream, N, true, D, T, zk->usable);
+        // _chain: start_be32 is folded into the scan's top-level prefix values: every row and the closing value carry it, and
+        // the tail below overwrites the rows behind row `usable`
+        launch_gp_scan(A.stream, N, D, T, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), rec + MR_EVAL,
+                       reinterpret_cast<uint32_t*>(rec + MR_EVAL + 32), start_be32);
+        if (zk) launch_blind_tail(A.stream, N, T, zk->usable, zk->tail_be32, A.flags());
+    }
+    const uint32_t* c;
+    if (int rc = row_to_coeffs(ctx, A, N, T, 1, &c, dst)) return rc;
+    uint8_t ev[64];
+    if (int rc = multi_msms_finish(ctx, H, i, T, dst, 1, 0, 2, out_c48, ev, nullptr)) return rc;
+    memcpy(out_closing32, ev, 32);
+    uint32_t zf;
+    memcpy(&zf, ev + 32, 4);
+    *out_zero_den = zf != 0;
+    return KZG_OK;
+}
 // The permutation grand product (kzg_rows_commit_grand_product): a set built FROM sets.  Per wire / sigma pair two forward
 // transforms of the sets' coefficient rows into two lane buffers and one launch that folds the pair's factors into the
 // running N and D vectors (four vectors of T whatever k is); the product scans and the one inversion turn N into z's
@@ -801,7 +831,6 @@ int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& 
     HIPCHK(ctx, A.hnext.ensure((nchunks + (nchunks >> 1) + 64) * 32));
     uint32_t *ea = A.coeffA.as<uint32_t>(), *es = A.coeffB.as<uint32_t>();
     uint32_t *N = A.bcomb.as<uint32_t>(), *D = A.qbuf.as<uint32_t>();
-    uint8_t* rec = A.brec.as<uint8_t>();
     for (uint32_t j = 0; j < k; j++) {
         {
             Span sp(ctx, A, KZG_T_NTT);
@@ -811,26 +840,60 @@ int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& 
         Span sp(ctx, A, KZG_T_POLY);
         launch_gp_factors(A.stream, ea, es, N, D, T, tw, beta_be32, gamma_be32, shifts_be32 + 32 * (size_t)j, j == 0, A.flags());
     }
-    {
-        Span sp(ctx, A, KZG_T_POLY);
-        // _zk: N_t = D_t = 1 on the rows >= usable (whatever their cells hold, a zero D_t included), so the unchanged scan
-        // leaves z = closing on every one of them; the tail then replaces the rows behind row `usable`
-        if (zk) launch_blind_mask(A.stream, N, true, D, T, zk->usable);
-        // _chain: start_be32 is folded into the scan's top-level prefix values: every row and the closing value carry it, and
-        // the tail below overwrites the rows behind row `usable`
-        launch_gp_scan(A.stream, N, D, T, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), rec + MR_EVAL,
-                       reinterpret_cast<uint32_t*>(rec + MR_EVAL + 32), start_be32);
-        if (zk) launch_blind_tail(A.stream, N, T, zk->usable, zk->tail_be32, A.flags());
+    return grand_product_finish_dev(ctx, H, i, N, D, T, dst, out_c48, out_closing32, out_zero_den, zk, start_be32);
+}
+
+// The shuffle grand product (kzg_rows_commit_shuffle): a set built FROM sets.  Per group, the input side and then the shuffle
+// side: every row of the side is transformed into ONE lane buffer and folded in as it arrives, by Horner in theta from the last
+// column down (fr_lookup.hip's LK_HORNER); column 0 closes the chain with k_sh_factor, which multiplies gamma + A_g (or the
+// selected form) into N, gamma + B_g into D.  A side's selector row is transformed into one further vector just in front of
+// that launch (kept when the next side names the same row).  Workspace: the grand product's four vectors of T (the
+// transform's output, the Horner accumulator, N, D) and its scan scratch, plus one vector of T when a selector is named --
+// whatever n_groups and width are.  From N and D on, the call is the grand product's.
+int rows_shuffle_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& shuffles, uint32_t n_groups,
+                     uint32_t width, uint64_t T, const uint8_t* theta_be32, const uint8_t* gamma_be32, uint32_t* dst,
+                     uint8_t* out_c48, uint8_t* out_closing32, bool* out_zero_den, const Blind* zk, const ShuffleSel* sel) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const int lg = ilog2_exact(T);
+    uint32_t* tw = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
+    const uint64_t nchunks = (T + 3) / 4;
+    HIPCHK(ctx, A.coeffA.ensure(T * 32));
+    HIPCHK(ctx, A.coeffB.ensure(T * 32));
+    HIPCHK(ctx, A.bcomb.ensure(T * 32));
+    HIPCHK(ctx, A.qbuf.ensure(T * 32));
+    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    HIPCHK(ctx, A.hbuf.ensure((nchunks + (nchunks >> 1) + 64) * 32));
+    HIPCHK(ctx, A.hnext.ensure((nchunks + (nchunks >> 1) + 64) * 32));
+    if (sel) HIPCHK(ctx, A.qext.ensure(T * 32));
+    uint32_t *e = A.coeffA.as<uint32_t>(), *acc = A.coeffB.as<uint32_t>(), *mid = A.ntt_mid.as<uint32_t>();
+    uint32_t *N = A.bcomb.as<uint32_t>(), *D = A.qbuf.as<uint32_t>();
+    const uint32_t* sel_in_q = nullptr;   // the selector row whose evaluations lie in qext
+    for (uint32_t g = 0; g < n_groups; g++) {
+        for (int side = 0; side < 2; side++) {
+            const RowTab& rt = side ? shuffles : inputs;
+            const uint32_t* q = sel ? (side ? sel->sh[g] : sel->in[g]) : nullptr;
+            for (uint32_t c = width; c-- > 0;) {
+                {
+                    Span sp(ctx, A, KZG_T_NTT);
+                    launch_fr_ntt(A.stream, rt.r[g * width + c], e, lg, tw, nullptr, mid);
+                    if (!c && q && q != sel_in_q) {
+                        launch_fr_ntt(A.stream, q, A.qext.as<uint32_t>(), lg, tw, nullptr, mid);
+                        sel_in_q = q;
+                    }
+                }
+                Span sp(ctx, A, KZG_T_POLY);
+                const bool has_acc = c + 1 < width;
+                if (c)   // (LK_HORNER touches neither P nor Q, and only checks its second scalar)
+                    launch_lk_step(A.stream, e, acc, nullptr, nullptr, T, 0, has_acc, theta_be32, gamma_be32, A.flags());
+                else
+                    launch_sh_factor(A.stream, e, has_acc ? acc : nullptr, side ? D : N, q ? A.qext.as<uint32_t>() : nullptr, T,
+                                     theta_be32, gamma_be32, g == 0, A.flags());
+            }
+        }
     }
-    const uint32_t* c;
-    if (int rc = row_to_coeffs(ctx, A, N, T, 1, &c, dst)) return rc;
-    uint8_t ev[64];
-    if (int rc = multi_msms_finish(ctx, H, i, T, dst, 1, 0, 2, out_c48, ev, nullptr)) return rc;
-    memcpy(out_closing32, ev, 32);
-    uint32_t zf;
-    memcpy(&zf, ev + 32, 4);
-    *out_zero_den = zf != 0;
-    return KZG_OK;
+    return grand_product_finish_dev(ctx, H, i, N, D, T, dst, out_c48, out_closing32, out_zero_den, zk, nullptr);
 }
 
 // The lookup running sum (kzg_rows_commit_lookup_sum): a set built FROM sets.  Every named row is transformed into ONE lane

@@ -42,6 +42,11 @@ int rows_grand_product(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles,
                        uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,
                        const uint8_t* beta_be32, const uint8_t* gamma_be32, uint8_t* out_commitment48, uint8_t* out_closing32,
                        uint64_t* out_handle, const Blind* zk, const uint8_t* start_be32);
+// opts: the selectors and the blinding rows as the public call takes them (null: neither)
+int rows_shuffle(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                 uint32_t n_shuffle_handles, const uint64_t* shuffle_handles, uint32_t n_groups, uint32_t width,
+                 const uint8_t* theta_be32, const uint8_t* gamma_be32, const kzg_shuffle_opts* opts, uint8_t* out_commitment48,
+                 uint8_t* out_closing32, uint64_t* out_handle);
 // zk: the blinding rows of the _zk call, the layout of the _sel call.  sc: the selectors of the _sel call
 int rows_lookup_sum(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
                     uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,

@@ -978,6 +978,94 @@ int rows_grand_product(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles,
     return KZG_OK;
 }
 
+// kzg_rows_commit_shuffle: the lookups of an open (two handle lists, and the selectors' when opts names some), the
+// reservation of a commit.  opts == NULL, or usable == 0 and no selector index list: the plain call
+int rows_shuffle(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                 uint32_t n_shuffle_handles, const uint64_t* shuffle_handles, uint32_t n_groups, uint32_t width,
+                 const uint8_t* theta_be32, const uint8_t* gamma_be32, const kzg_shuffle_opts* opts, uint8_t* out_commitment48,
+                 uint8_t* out_closing32, uint64_t* out_handle) {
+    if (!ctx || !input_handles || !shuffle_handles || !theta_be32 || !gamma_be32 || !out_commitment48 || !out_closing32 ||
+        !out_handle)
+        return KZG_E_ARG;
+    const bool has_sel = opts && (opts->input_sel || opts->shuffle_sel);
+    if (opts && opts->n_sel_handles && !opts->sel_handles) return KZG_E_ARG;
+    if (opts && opts->n_sel_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "shuffle: at most KZG_MAX_BATCH_OPEN selector handles");
+    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN || n_shuffle_handles == 0 ||
+        n_shuffle_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "shuffle: the number of handles in each list must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (n_groups == 0 || width == 0 || (uint64_t)n_groups * width > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "shuffle: n_groups and width must be at least 1 and n_groups * width at most "
+                                    "KZG_MAX_BATCH_OPEN");
+    if (!fr_be32_canonical(theta_be32) || !fr_be32_canonical(gamma_be32))
+        return fail(ctx, KZG_E_ARG, "shuffle: theta and gamma must be canonical scalars (< r)");
+    if (has_sel && !opts->n_sel_handles)
+        for (uint32_t g = 0; g < n_groups; g++)
+            if ((opts->input_sel && opts->input_sel[g] != KZG_NO_SELECTOR) ||
+                (opts->shuffle_sel && opts->shuffle_sel[g] != KZG_NO_SELECTOR))
+                return fail(ctx, KZG_E_ARG, "shuffle: a selector index was given but no selector handles");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs irefs{ctx}, srefs{ctx}, qrefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab it, st, qt;
+    uint32_t ki = 0, ks = 0, kq = 0, i = 0, i2 = 0;
+    uint64_t T = 0, T2 = 0;
+    if (int rc = rows_lookup(ctx, "shuffle (inputs)", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    if (int rc = rows_lookup(ctx, "shuffle (shuffles)", expect_i, n_shuffle_handles, shuffle_handles, srefs, st, &ks, &i2, &T2))
+        return rc;
+    if (i2 != i || T2 != T) return fail(ctx, KZG_E_ARG, "shuffle: all sets must belong to one worker and have one row length");
+    if (opts && opts->n_sel_handles) {
+        if (int rc = rows_lookup(ctx, "shuffle (selectors)", expect_i, opts->n_sel_handles, opts->sel_handles, qrefs, qt, &kq, &i2, &T2))
+            return rc;
+        if (i2 != i || T2 != T) return fail(ctx, KZG_E_ARG, "shuffle: all sets must belong to one worker and have one row length");
+    }
+    if (ki != n_groups * width || ks != n_groups * width)
+        return fail(ctx, KZG_E_ARG, "shuffle: the input sets and the shuffle sets must each hold exactly n_groups * width rows");
+    ShuffleSel sel;
+    memset(&sel, 0, sizeof(sel));
+    bool any_sel = false;   // (every entry KZG_NO_SELECTOR: the call without selectors)
+    for (uint32_t g = 0; has_sel && g < n_groups; g++) {
+        const uint32_t ji = opts->input_sel ? opts->input_sel[g] : KZG_NO_SELECTOR;
+        const uint32_t js = opts->shuffle_sel ? opts->shuffle_sel[g] : KZG_NO_SELECTOR;
+        if ((ji != KZG_NO_SELECTOR && ji >= kq) || (js != KZG_NO_SELECTOR && js >= kq))
+            return fail(ctx, KZG_E_ARG, "shuffle: an input_sel / shuffle_sel entry must be KZG_NO_SELECTOR or index the "
+                                        "concatenated rows of the selector sets");
+        if (ji != KZG_NO_SELECTOR) sel.in[g] = qt.r[ji];
+        if (js != KZG_NO_SELECTOR) sel.sh[g] = qt.r[js];
+        any_sel = any_sel || sel.in[g] || sel.sh[g];
+    }
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "shuffle: the row length must be a power of two");
+    const Blind zk = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
+    if (zk.usable) {
+        if (int rcz = blind_check(ctx, "shuffle", T, zk)) return rcz;
+    } else if (zk.tail_be32) {
+        return fail(ctx, KZG_E_ARG, "shuffle: tail_be32 must be null in the plain layout (usable = 0)");
+    }
+    if (int rc2 = rows_reserve(ctx, "shuffle", pend, (size_t)T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    bool zero_den = false;
+    uint8_t c48[48], closing[32];
+    rc = rows_shuffle_dev(ctx, H, i, it, st, n_groups, width, T, theta_be32, gamma_be32, pend.buf.as<uint32_t>(), c48, closing,
+                          &zero_den, zk.usable ? &zk : nullptr, any_sel ? &sel : nullptr);
+    if (rc) return rc;
+    if (zero_den)
+        return fail(ctx, KZG_E_ARG, zk.usable ? "shuffle: zero denominator (some shuffle-side factor vanishes on a usable row): z is "
+                                                "undefined, no set was created"
+                                              : "shuffle: zero denominator (some shuffle-side factor vanishes on the domain): z is "
+                                                "undefined, no set was created");
+    memcpy(out_commitment48, c48, 48);
+    memcpy(out_closing32, closing, 32);
+    *out_handle = rows_insert(ctx, pend, i, 1, T);
+    return KZG_OK;
+}
+
 // The check of a _sel builder's selector arguments (SelCall, rows_impl.h): sel_index[l] is KZG_NO_SELECTOR or indexes the
 // concatenated rows of the sel_handles sets, which must be of the call's worker and row length.  The distinct rows named go
 // into sp (a row that serves several lookups is transformed once).
@@ -1548,6 +1636,13 @@ int kzg_rows_commit_grand_product_chain(kzg_ctx* ctx, uint32_t n_wire_handles, c
     const Blind zk = {usable, tail_be32};
     return rows_grand_product(ctx, UINT32_MAX, n_wire_handles, wire_handles, n_sigma_handles, sigma_handles, k, shifts_be32,
                               beta_be32, gamma_be32, out_commitment48, out_closing32, out_handle, &zk, start_be32);
+}
+int kzg_rows_commit_shuffle(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_shuffle_handles,
+                            const uint64_t* shuffle_handles, uint32_t n_groups, uint32_t width, const uint8_t theta_be32[32],
+                            const uint8_t gamma_be32[32], const kzg_shuffle_opts* opts, uint8_t out_commitment48[48],
+                            uint8_t out_closing32[32], uint64_t* out_handle) {
+    return rows_shuffle(ctx, UINT32_MAX, n_input_handles, input_handles, n_shuffle_handles, shuffle_handles, n_groups, width,
+                        theta_be32, gamma_be32, opts, out_commitment48, out_closing32, out_handle);
 }
 int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_table_handles,
                                const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups, uint32_t width,

@@ -34,6 +34,59 @@ def lagrange_factor(i: int, machines_scale: int, tau_y: int) -> int:
     return wi * inv(m) % R_MODULUS * num % R_MODULUS * inv(tau_y - wi) % R_MODULUS
 
 
+def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: Sequence[int], n_groups: int, width: int,
+                           theta_be32: bytes, gamma_be32: bytes, coeff_be32: bytes, active_row: Optional[int] = None,
+                           input_sel: Optional[Sequence[Optional[int]]] = None,
+                           shuffle_sel: Optional[Sequence[Optional[int]]] = None,
+                           ext_log: int = 2) -> List[Tuple[bytes, List[Tuple[int, int]]]]:
+    """The relation that makes commit_shuffle's z an argument, as gate terms for commit_quotient_ext / _zk / quotient_part:
+        coeff * A * [ z(wX) prod_g df_g(X)  -  z(X) prod_g nf_g(X) ]
+    multiplied out over the groups into (32-byte coefficient, [(row, rot), ..]) terms.  Every argument names a row of the
+    quotient call's concatenation: z, the n_groups * width input and shuffle rows (group-major), the optional active column A
+    and, per group, None or the selector row of that side (input_sel / shuffle_sel, None: no selector at all); theta and gamma
+    are those z was built with, coeff the caller's power of alpha.  Terms with the same factors are added up and nothing
+    else is merged.  Raises CodecError when the expansion needs more than KZG_MAX_GATE_TERMS terms or a term more than
+    2^ext_log + 1 factors: such a relation goes through quotient_part in slices of this list, or needs a larger ext_log.
+    "z = 1 at row 0" and, under blinding, "z = 1 at row u" are not written here: they stay the ordinary gate terms (z - 1) L_0
+    and (z - 1) L_u over a caller row L_0 / L_u, as for the permutation.  Pure host arithmetic on a few scalars."""
+    from . import codec
+
+    G, w = int(n_groups), int(width)
+    if G < 1 or w < 1 or len(input_rows) != G * w or len(shuffle_rows) != G * w:
+        raise codec.CodecError(f"shuffle_quotient_terms: n_groups, width >= 1 and n_groups * width = {G * w} input and shuffle "
+                               f"rows each, not {len(input_rows)} and {len(shuffle_rows)}")
+    sels = [[None] * G if s is None else list(s) for s in (input_sel, shuffle_sel)]
+    if any(len(s) != G for s in sels):
+        raise codec.CodecError(f"shuffle_quotient_terms: input_sel and shuffle_sel hold one entry per group ({G}) or are None")
+    if any(len(x) != 32 or int.from_bytes(x, "big") >= R_MODULUS for x in (theta_be32, gamma_be32, coeff_be32)):
+        raise codec.CodecError("shuffle_quotient_terms: theta, gamma and coeff must be canonical scalars (< r) of 32 bytes")
+    theta, gamma, coeff = (int.from_bytes(x, "big") for x in (theta_be32, gamma_be32, coeff_be32))
+
+    def factor(rows, q):   # gamma + sum_c theta^c row_c, or 1 + q (gamma - 1) + sum_c theta^c q row_c, as {factors: coefficient}
+        head = [] if q is None else [(int(q), 0)]
+        mono = [((), 1), (tuple(head), gamma - 1)] if head else [((), gamma)]
+        return mono + [(tuple(head + [(int(rows[c]), 0)]), pow(theta, c, R_MODULUS)) for c in range(w)]
+
+    out: Dict[tuple, int] = {}
+    front = [] if active_row is None else [(int(active_row), 0)]
+    for side, rows, rot, sign in ((1, shuffle_rows, 1, 1), (0, input_rows, 0, -1)):
+        prod = [(tuple(front + [(int(z_row), rot)]), sign * coeff % R_MODULUS)]
+        for g in range(G):
+            f = factor(rows[g * w:(g + 1) * w], sels[side][g])
+            prod = [(fa + fb, ca * cb % R_MODULUS) for fa, ca in prod for fb, cb in f]
+        for fs, c in prod:
+            key = tuple(sorted(fs))
+            out[key] = (out.get(key, 0) + c) % R_MODULUS
+    E = 1 << int(ext_log)
+    if len(out) > _native.KZG_MAX_GATE_TERMS:
+        raise codec.CodecError(f"shuffle_quotient_terms: the relation expands into {len(out)} terms, more than "
+                               f"KZG_MAX_GATE_TERMS = {_native.KZG_MAX_GATE_TERMS}")
+    deepest = max(len(fs) for fs in out)
+    if deepest > E + 1:
+        raise codec.CodecError(f"shuffle_quotient_terms: a term has {deepest} factors, more than 2^ext_log + 1 = {E + 1}")
+    return [(c.to_bytes(32, "big"), list(fs)) for fs, c in out.items()]
+
+
 class HipEngine:
     # rows from this length up are decoded and uploaded tile by tile (see _Staged); KZG_STREAM_MIN_LOG moves the threshold
     STREAM_MIN = 1 << int(os.environ.get("KZG_STREAM_MIN_LOG", "19"))
@@ -579,6 +632,48 @@ class HipEngine:
             raise KzgError(_native.KZG_E_ARG, "commit_*_sel: the row length of the sets is unknown to this engine (they were "
                                               "not committed through it)")
         return T
+
+    # ---- a set built from sets: the running product of a shuffle argument.  ONE call for every form: selectors and blinding
+    # rows are optional arguments (kzg_shuffle_opts)
+    def commit_shuffle(self, input_sets: Sequence[object], shuffle_sets: Sequence[object], n_groups: int, width: int,
+                       theta_be32: bytes, gamma_be32: bytes, sel_sets: Optional[Sequence[object]] = None,
+                       input_sel: Optional[Sequence[Optional[int]]] = None,
+                       shuffle_sel: Optional[Sequence[Optional[int]]] = None, usable: Optional[int] = None,
+                       tail: Sequence[bytes] = ()) -> Tuple["RowSet", bytes]:
+        """z of kzg_rows_commit_shuffle: the n_groups * width concatenated rows of input_sets (group-major) against as many of
+        shuffle_sets (RowSet objects or bare handles).  input_sel / shuffle_sel: None, or one entry per group, None or the
+        index of that side's selector row in the concatenated rows of sel_sets.  usable = None is the plain layout, anything
+        else that of commit_grand_product_zk with its tail.  Returns (a one-row RowSet holding z, the closing value as 32
+        bytes big-endian: 1 when the product closes).  theta and gamma must be drawn after the commitments of all input and
+        shuffle rows are fixed; the argument is the relation shuffle_quotient_terms writes, not the closing value."""
+        what = "commit_shuffle"
+        ni, hi = self._handle_array(input_sets, f"{what} (inputs)")
+        ns, hs = self._handle_array(shuffle_sets, f"{what} (shuffles)")
+        if n_groups < 1 or width < 1 or n_groups * width > _native.KZG_MAX_BATCH_OPEN or len(theta_be32) != 32 \
+                or len(gamma_be32) != 32:
+            raise KzgError(_native.KZG_E_ARG, f"{what}: n_groups, width >= 1, n_groups * width <= "
+                                              f"{_native.KZG_MAX_BATCH_OPEN}, theta and gamma of 32 bytes each")
+        if usable == 0:   # (the C call reads 0 as "plain layout"; here that is None, and 0 is the _zk calls' range error)
+            raise KzgError(_native.KZG_E_ARG, f"{what}: usable must be in [1, T - 1] (None: the plain layout)")
+        opts = None
+        if sel_sets or input_sel is not None or shuffle_sel is not None or usable is not None:
+            opts = _native.ShuffleOpts()
+            # (keep: the arrays must outlive the call)
+            keep = [self._sel_args(what, sel_sets, [None] * n_groups if idx is None else idx, n_groups)
+                    for idx in (input_sel, shuffle_sel)]
+            opts.n_sel_handles, opts.sel_handles = keep[0][0], keep[0][1]
+            if input_sel is not None:
+                opts.input_sel = keep[0][2]
+            if shuffle_sel is not None:
+                opts.shuffle_sel = keep[1][2]
+        blind = None if usable is None else (usable, tail)
+        extra, wi, T = self._layout_args(what, list(input_sets) + list(shuffle_sets), blind)
+        if extra:
+            opts.usable, opts.tail_be32 = extra
+        c, cl, h = ctypes.create_string_buffer(48), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_shuffle(self._h, ni, hi, ns, hs, n_groups, width, theta_be32, gamma_be32,
+                                                    ctypes.byref(opts) if opts is not None else None, c, cl, ctypes.byref(h)))
+        return RowSet(self, h.value, wi, 1, T, [c.raw]), cl.raw
 
     # ---- a third set built from sets: the PLONK quotient (round 3), computed and committed on the device
     def commit_quotient(self, sets: Sequence[object], terms: Sequence[Tuple[bytes, Sequence[int]]], perm: Optional[dict] = None,

@@ -203,6 +203,12 @@ class MultiDeviceClient:
         return self._routed_builder("worker_commit_multiplicities_sel", [input_handles, table_handles, sel_handles or []],
                                     input_handles, table_handles, sel_handles, sel_index, n_lookups, width, usable, tail)
 
+    def worker_commit_shuffle(self, input_handles: Sequence[int], shuffle_handles: Sequence[int], n_groups, width, theta, gamma,
+                              sel_handles=None, input_sel=None, shuffle_sel=None, usable=None, tail=()):
+        return self._routed_builder("worker_commit_shuffle", [input_handles, shuffle_handles, sel_handles or []], input_handles,
+                                    shuffle_handles, n_groups, width, theta, gamma, sel_handles, input_sel, shuffle_sel, usable,
+                                    tail)
+
     def worker_commit_quotient_zk(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None, ext_log=2,
                                   n_pieces=3):
         return self._routed_builder("worker_commit_quotient_zk", [handles], handles, terms, perm, lookup, active_row, ext_log,
