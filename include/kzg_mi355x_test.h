@@ -40,6 +40,22 @@ int kzg_test_fp_raw(kzg_ctx* ctx, int field, int op, const uint32_t* a, const ui
  *   5 lp_add, 6 lp_dbl(a) (one wave per element) */
 int kzg_test_g1_raw(kzg_ctx* ctx, int op, const uint32_t* a_xyzz, const uint32_t* b_xyzz, uint8_t* out_be96, uint64_t n);
 
+/* ---- the NTT's pass plans (tests/test_ntt_plans_cpu.py, tests/test_gpu_ntt_plans.py, reference tests/ntt_ref.py).  A transform
+ * of 2^log_n elements is `passes` launches of one kernel form; pass p runs S[p] butterfly stages on tiles of 2^S[p] rows x
+ * 2^logC[p] columns.
+ * kzg_test_ntt_plan_of: the plan the library itself runs, host only, no context.  kernel -1: the form it picks for this size
+ * (radix-2 below 2^18, or everywhere under KZG_NTT_RADIX2=1), 0: the register-blocked form, 1: the radix-2 form, whatever the
+ * size; tile_log 0: the tile it uses (KZG_NTT_TILE_LOG, or 10), 8 .. 11: that tile (the radix-2 form has one tile, 10).
+ * log_n in [1, 31].  out_S, out_logC: room for 8 passes.  Returns the form (0 register-blocked, 1 radix-2) or KZG_E_ARG.
+ * kzg_test_ntt_run: kzg_ntt's path (upload, twiddles, scratch, launches, download) with the CALLER'S plan in place of the
+ * library's; kernel 0 or 1, log_n in [1, 22], at most 8 passes.  The plan is checked against the kernels' preconditions before
+ * anything is launched (and before the context is looked at), KZG_E_ARG with the reason in kzg_last_error otherwise:
+ *   sum S = log_n, every S >= 1; radix-2: S <= 8 and S + logC <= 10; register-blocked: S <= 9 and S + logC <= 11;
+ *   logC >= 0; first pass: logC <= log_n - S; later passes: logC <= s0 = the sum of the earlier S */
+int kzg_test_ntt_plan_of(int log_n, int kernel, int tile_log, int* out_S, int* out_logC, int* out_passes);
+int kzg_test_ntt_run(kzg_ctx* ctx, uint8_t* inout_be32, int log_n, int inverse, int kernel, int passes, const int* S,
+                     const int* logC);
+
 /* the host encoder itself (no GPU): 4 x 14 limbs of 28 bits (X, Y, ZZ, ZZZ; lazy limbs < 2^32; residues with
  * R = 2^392) -> 48-byte compressed point / 192-byte partial record.  Test hooks. */
 int kzg_host_xyzz_to_c48(const uint32_t xyzz_limbs28[56], uint8_t out48[48]);

@@ -283,6 +283,8 @@ SYMBOLS = {
     "kzg_test_g1": (_I, [_P, _I, _B, _B, _B, _U64]),
     "kzg_test_fp_raw": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _U64]),
     "kzg_test_g1_raw": (_I, [_P, _I, _P, _P, _B, _U64]),
+    "kzg_test_ntt_plan_of": (_I, [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "kzg_test_ntt_run": (_I, [_P, _P, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
 }
 
 _lib = None

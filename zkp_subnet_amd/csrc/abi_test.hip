@@ -419,4 +419,65 @@ int kzg_test_g1_raw(kzg_ctx* ctx, int op, const uint32_t* a_xyzz, const uint32_t
     return KZG_OK;
 }
 
+// ---- the NTT's pass plans (tests/test_ntt_plans_cpu.py, tests/test_gpu_ntt_plans.py)
+int kzg_test_ntt_plan_of(int log_n, int kernel, int tile_log, int* out_S, int* out_logC, int* out_passes) {
+    if (!out_S || !out_logC || !out_passes) return fail(nullptr, KZG_E_ARG, "ntt plan: null output");
+    if (log_n < 1 || log_n > 31 || kernel < -1 || kernel > 1 || (tile_log != 0 && (tile_log < 8 || tile_log > 11)))
+        return fail(nullptr, KZG_E_ARG, "ntt plan: log_n in [1, 31], kernel in {-1, 0, 1}, tile_log 0 or in [8, 11]");
+    const NttPlan pl = ntt_plan_for(log_n, kernel, tile_log);
+    for (int p = 0; p < pl.passes; p++) {
+        out_S[p] = pl.S[p];
+        out_logC[p] = pl.logC[p];
+    }
+    *out_passes = pl.passes;
+    return pl.radix2;
+}
+#define KZG_TEST_NTT_MAX_LOG 22      // elements per plan-hook call (as KZG_RAW_MAX_N)
+int kzg_test_ntt_run(kzg_ctx* ctx, uint8_t* inout_be32, int log_n, int inverse, int kernel, int passes, const int* S,
+                     const int* logC) {
+    // the plan is judged first, with no context and no device: nothing invalid reaches a kernel
+    if (!S || !logC || passes < 1 || passes > NTT_MAX_PASSES) return fail(ctx, KZG_E_ARG, "ntt plan: number of passes outside [1, 8]");
+    if (kernel != 0 && kernel != 1) return fail(ctx, KZG_E_ARG, "ntt plan: kernel must be 0 (register-blocked) or 1 (radix-2)");
+    if (log_n < 1 || log_n > KZG_TEST_NTT_MAX_LOG) return fail(ctx, KZG_E_ARG, "ntt plan: log_n outside [1, 22]");
+    NttPlan pl;
+    memset(&pl, 0, sizeof pl);
+    pl.radix2 = kernel;
+    pl.passes = passes;
+    for (int p = 0; p < passes; p++) {
+        pl.S[p] = S[p];
+        pl.logC[p] = logC[p];
+    }
+    if (const char* why = ntt_plan_invalid(log_n, pl)) return fail(ctx, KZG_E_ARG, why);
+    if (!ctx || !inout_be32) return fail(ctx, KZG_E_ARG, "ntt plan: no context or no data");
+    // from here on: kzg_ntt's path (serve.hip), with the caller's plan in place of the production one
+    const uint64_t n = (uint64_t)1 << log_n;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;
+    Lane& L = H.L();
+    prof_begin(ctx, L);
+    int rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    HIPCHK(ctx, L.coeffA.ensure(n * 32));
+    HIPCHK(ctx, L.coeffB.ensure(n * 32));
+    HIPCHK(ctx, L.out_be.ensure(n * 32));
+    rc = upload_fr(ctx, L, inout_be32, n, L.coeffA.as<uint32_t>(), 1);
+    if (rc) return rc;
+    uint32_t *tw = nullptr, *invn = nullptr;
+    rc = ensure_twiddles(ctx, L, log_n, inverse, &tw, inverse ? &invn : nullptr);
+    if (rc) return rc;
+    HIPCHK(ctx, L.ntt_mid.ensure(n * 48));
+    {
+        Span sp(ctx, L, KZG_T_NTT);
+        run_fr_ntt_plan(L.stream, L.coeffA.as<uint32_t>(), L.coeffB.as<uint32_t>(), log_n, tw, inverse ? invn : nullptr,
+                        L.ntt_mid.as<uint32_t>(), pl);
+    }
+    launch_fr_to_be(L.stream, L.coeffB.as<uint32_t>(), L.out_be.as<uint8_t>(), n, 1);
+    rc = finish(ctx, L);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpy(inout_be32, L.out_be.p, n * 32, hipMemcpyDeviceToHost));
+    H.clean = true;
+    return KZG_OK;
+}
+
 }  // extern "C"

@@ -19,6 +19,22 @@ void launch_fr_inv_pow2(hipStream_t s, uint32_t* out, int log_n);
 // scratch (the vector between passes, same slot format); unused when log_n <= 8 (one pass)
 void launch_fr_ntt(hipStream_t s, const uint32_t* in, uint32_t* out, int log_n, const uint32_t* tw,
                    const uint32_t* scale_or_null, uint32_t* mid);
+// launch_fr_ntt is "plan, then run" (fr_ntt.hip).  A plan: the kernel form and, per pass, the stages S and the log2 of the
+// tile's columns; ntt_plan is the launcher's arithmetic as a pure host function, ntt_production_plan what launch_fr_ntt
+// picks (the 2^18 switch, KZG_NTT_RADIX2, KZG_NTT_TILE_LOG), ntt_plan_invalid the kernels' preconditions (null: valid),
+// run_fr_ntt_plan the launches of a valid plan (arguments as launch_fr_ntt, log_n >= 1).
+#define NTT_MAX_PASSES 8
+struct NttPlan {
+    int radix2, passes;
+    int S[NTT_MAX_PASSES], logC[NTT_MAX_PASSES];
+};
+NttPlan ntt_plan(int log_n, bool radix2, int tile_log);
+// kernel -1 / 0 / 1: the production choice / register-blocked / radix-2; tile_log 0: the production tile, 8 .. 11: that one
+NttPlan ntt_plan_for(int log_n, int kernel, int tile_log);
+NttPlan ntt_production_plan(int log_n);
+const char* ntt_plan_invalid(int log_n, const NttPlan& pl);
+void run_fr_ntt_plan(hipStream_t s, const uint32_t* in, uint32_t* out, int log_n, const uint32_t* tw,
+                     const uint32_t* scale_or_null, uint32_t* mid, const NttPlan& pl);
 // y = f(alpha) (Montgomery) and, if q is given, the n-1 canonical coefficients of (f - y)/(X - alpha)
 // h, hnext: ceil(n/4) * 3/2 + 64 Fr scratch each (level arrays stacked; the chunk length shrinks to 4 for small rows)
 // alpha_be32_host given: alpha arrives as 32 big-endian HOST bytes (a kernel argument of the first kernel), its

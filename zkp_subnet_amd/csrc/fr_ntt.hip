@@ -579,28 +579,32 @@ void launch_fr_twiddles(hipStream_t s, uint32_t* tw, int log_n, int inverse) {
     k_fr_twiddles<<<nblk((half + 63) / 64, 256), 256, 0, s>>>(tw, log_n, inverse);
 }
 void launch_fr_inv_pow2(hipStream_t s, uint32_t* out, int log_n) { k_fr_inv_pow2<<<1, 64, 0, s>>>(out, log_n); }
-static void launch_fr_ntt_radix2(hipStream_t s, const uint32_t* in, uint32_t* out, int log_n, const uint32_t* tw,
-                                 const uint32_t* scale_or_null, uint32_t* mid) {
-    const uint64_t n = (uint64_t)1 << log_n;
-    // split log_n into ceil(log_n / 8) passes of near-equal depth (22 -> 8 + 7 + 7)
-    const int passes = (log_n + NTT_PASS_LOG - 1) / NTT_PASS_LOG;
+// ---- the pass plan.  A transform is `passes` launches; pass p runs S[p] stages on tiles of 2^S[p] rows x 2^logC[p] columns.
+// ntt_plan is the arithmetic of the launcher and nothing else (pure, host only): tests read it through kzg_test_ntt_plan_of.
+//   radix-2 (k_fr_ntt_pass):          ceil(log_n / 8) passes of near-equal depth (22 -> 8 + 7 + 7), 1024-element tiles
+//   register-blocked (k_fr_ntt_pass4): ceil(log_n / (tile_log - 2)) passes, 2^tile_log-element tiles (tile_log 8 .. 11)
+// columns: as many as the tile allows, bounded by what exists (tiles in the first pass, the low-bit range s0 later), and
+// the first pass takes at most 4 tiles (128 B source rows), which keeps the tiles' stores long.
+NttPlan ntt_plan(int log_n, bool radix2, int tile_log) {
+    NttPlan pl;
+    memset(&pl, 0, sizeof pl);
+    pl.radix2 = radix2 ? 1 : 0;
+    if (log_n < 1) return pl;
+    const int tl = radix2 ? 10 : tile_log;
+    const int max_s = radix2 ? NTT_PASS_LOG : tile_log - 2;
+    pl.passes = (log_n + max_s - 1) / max_s;
     int s0 = 0;
-    for (int p = 0; p < passes; p++) {
-        const int S = (log_n - s0 + (passes - p) - 1) / (passes - p);
-        // columns: as many as the 1024-element tile allows, bounded by what exists (tiles / low-bit range)
-        int logC = 10 - S;
+    for (int p = 0; p < pl.passes; p++) {
+        const int S = (log_n - s0 + (pl.passes - p) - 1) / (pl.passes - p);
+        int logC = tl - S;
         const int avail = p == 0 ? log_n - S : s0;
         if (logC > avail) logC = avail;
-        if (p == 0 && logC > 2) logC = 2;  // first pass: 4 tiles (128 B source rows) keep the tiles' stores long
-        const uint32_t blocks = (uint32_t)(n >> (S + logC));
-        const bool last = p == passes - 1;
-        const bool big = (1u << (S + logC)) >= 1024;
-        if (big && last) k_fr_ntt_pass<512, true><<<blocks, 512, 0, s>>>(in, out, mid, log_n, s0, S, logC, tw, scale_or_null);
-        else if (big) k_fr_ntt_pass<512, false><<<blocks, 512, 0, s>>>(in, out, mid, log_n, s0, S, logC, tw, nullptr);
-        else if (last) k_fr_ntt_pass<256, true><<<blocks, 256, 0, s>>>(in, out, mid, log_n, s0, S, logC, tw, scale_or_null);
-        else k_fr_ntt_pass<256, false><<<blocks, 256, 0, s>>>(in, out, mid, log_n, s0, S, logC, tw, nullptr);
+        if (p == 0 && logC > 2) logC = 2;
+        pl.S[p] = S;
+        pl.logC[p] = logC;
         s0 += S;
     }
+    return pl;
 }
 // KZG_NTT_RADIX2=1 selects the round-2 kernel (one stage per LDS round trip, 1024-element tiles) for same-box A/B runs
 static int ntt_use_radix2() {
@@ -610,13 +614,18 @@ static int ntt_use_radix2() {
     }();
     return v;
 }
-void launch_fr_ntt(hipStream_t s, const uint32_t* in, uint32_t* out, int log_n, const uint32_t* tw,
-                   const uint32_t* scale_or_null, uint32_t* mid) {
-    const uint64_t n = (uint64_t)1 << log_n;
-    if (log_n == 0) {  // length 1: the transform is the identity (1/1 = 1)
-        (void)hipMemcpyAsync(out, in, 32, hipMemcpyDeviceToDevice, s);
-        return;
-    }
+// KZG_NTT_TILE_LOG=8 .. 11: the tile of the register-blocked kernel (anything else: 10)
+static int ntt_env_tile_log() {
+    static const int tile_log = [] {
+        const char* e = getenv("KZG_NTT_TILE_LOG");
+        const int v = e ? atoi(e) : 10;
+        return v >= 8 && v <= 11 ? v : 10;
+    }();
+    return tile_log;
+}
+// kernel -1: the form launch_fr_ntt picks for 2^log_n elements, 0 / 1: the register-blocked / the radix-2 form whatever the
+// size (as KZG_NTT_RADIX2 does); tile_log 0: the tile launch_fr_ntt uses (KZG_NTT_TILE_LOG, or 10), 8 .. 11: that tile
+NttPlan ntt_plan_for(int log_n, int kernel, int tile_log) {
     // Same-box A/B of the two kernels (profiles/r03_ab_ntt_radix4.log; NTT time inside a commit+open, ms):
     //   size   radix-2 (1024-tile)   radix-2^2, 2048-element tiles   radix-2^2, 1024-element tiles
     //   2^22   0.554 / 0.561         0.580 / 0.585                   0.540 / 0.539
@@ -629,37 +638,73 @@ void launch_fr_ntt(hipStream_t s, const uint32_t* in, uint32_t* out, int log_n, 
     // 2^22, ~0.25 ms at the bandwidth such tiles reach), which only partly overlap.  Larger tiles lose (two workgroups per
     // CU instead of four hide less of the load / store phases).  So: the register-blocked kernel with 1024-element tiles
     // from 2^18 up, the radix-2 kernel (one butterfly per lane: more lanes for the latency-bound short rows) below.
-    if (ntt_use_radix2() || log_n < 18) {
-        launch_fr_ntt_radix2(s, in, out, log_n, tw, scale_or_null, mid);
-        return;
-    }
-    static const int tile_log = [] {
-        const char* e = getenv("KZG_NTT_TILE_LOG");
-        const int v = e ? atoi(e) : 10;
-        return v >= 8 && v <= 11 ? v : 10;
-    }();
-    const int max_s = tile_log - 2;
-    const int passes = (log_n + max_s - 1) / max_s;
+    const bool radix2 = kernel < 0 ? (ntt_use_radix2() || log_n < 18) : kernel == 1;
+    return ntt_plan(log_n, radix2, radix2 ? 10 : (tile_log ? tile_log : ntt_env_tile_log()));
+}
+// what launch_fr_ntt runs for 2^log_n elements
+NttPlan ntt_production_plan(int log_n) { return ntt_plan_for(log_n, -1, 0); }
+// The kernels' own preconditions on a plan -- everything they index with is derived from (log_n, s0, S, logC), and they
+// check none of it:
+//   * 1 <= passes <= NTT_MAX_PASSES, every S >= 1 and sum S = log_n (pass p runs stages s0 .. s0 + S - 1, s0 = the sum
+//     of the earlier S; the twiddle index k << (log_n - s - 1) stays below n / 2 only for s < log_n);
+//   * radix-2: S <= 8 and S + logC <= 10 (NttTile holds 1024 elements); register-blocked: S <= 9 and S + logC <= 11
+//     (the largest instantiation stages 4 x 512 = 2048 elements);
+//   * logC >= 0; first pass: logC <= log_n - S (a workgroup takes 2^logC of the n / 2^S tiles); later passes:
+//     logC <= s0 (the columns are adjacent values of the s0 low bits: 2^s0 / 2^logC column groups, at least one).
+// With these, blocks = n >> (S + logC) >= 1 workgroups cover every element exactly once and no index leaves the vector,
+// the n / 2-entry twiddle table or the tile.  Null: the plan is valid; otherwise what is wrong with it.
+const char* ntt_plan_invalid(int log_n, const NttPlan& pl) {
+    if (log_n < 1 || log_n > 31) return "ntt plan: log_n outside [1, 31]";
+    if (pl.passes < 1 || pl.passes > NTT_MAX_PASSES) return "ntt plan: number of passes outside [1, 8]";
+    const int max_s = pl.radix2 ? NTT_PASS_LOG : NTT4_PASS_LOG, tile = pl.radix2 ? 10 : 11;
     int s0 = 0;
-    for (int p = 0; p < passes; p++) {
-        const int S = (log_n - s0 + (passes - p) - 1) / (passes - p);
-        int logC = tile_log - S;
-        const int avail = p == 0 ? log_n - S : s0;
-        if (logC > avail) logC = avail;
-        if (p == 0 && logC > 2) logC = 2;  // first pass: 4 tiles (128 B source rows) keep the tiles' stores long
+    for (int p = 0; p < pl.passes; p++) {
+        const int S = pl.S[p], logC = pl.logC[p];
+        if (S < 1 || S > max_s) return "ntt plan: a pass has fewer than 1 or more stages than its kernel admits";
+        if (logC < 0 || S + logC > tile) return "ntt plan: a pass does not fit the tile";
+        if (S > log_n - s0) return "ntt plan: the stages do not sum to log_n";
+        if (p == 0 ? logC > log_n - S : logC > s0) return "ntt plan: more columns than the pass has";
+        s0 += S;
+    }
+    if (s0 != log_n) return "ntt plan: the stages do not sum to log_n";
+    return nullptr;
+}
+// runs a VALID plan (ntt_plan_invalid is the caller's business: launch_fr_ntt runs its own plans, the test hook checks)
+void run_fr_ntt_plan(hipStream_t s, const uint32_t* in, uint32_t* out, int log_n, const uint32_t* tw,
+                     const uint32_t* scale_or_null, uint32_t* mid, const NttPlan& pl) {
+    const uint64_t n = (uint64_t)1 << log_n;
+    int s0 = 0;
+    for (int p = 0; p < pl.passes; p++) {
+        const int S = pl.S[p], logC = pl.logC[p];
         const uint32_t blocks = (uint32_t)(n >> (S + logC));
-        const bool last = p == passes - 1;
-        const uint32_t quads = (1u << (S + logC)) >> 2;     // one lane per four elements (the tile is sized 4 x lanes)
+        const bool last = p == pl.passes - 1;
+        if (pl.radix2) {
+            const bool big = (1u << (S + logC)) >= 1024;
+            if (big && last) k_fr_ntt_pass<512, true><<<blocks, 512, 0, s>>>(in, out, mid, log_n, s0, S, logC, tw, scale_or_null);
+            else if (big) k_fr_ntt_pass<512, false><<<blocks, 512, 0, s>>>(in, out, mid, log_n, s0, S, logC, tw, nullptr);
+            else if (last) k_fr_ntt_pass<256, true><<<blocks, 256, 0, s>>>(in, out, mid, log_n, s0, S, logC, tw, scale_or_null);
+            else k_fr_ntt_pass<256, false><<<blocks, 256, 0, s>>>(in, out, mid, log_n, s0, S, logC, tw, nullptr);
+        } else {
+            const uint32_t quads = (1u << (S + logC)) >> 2;     // one lane per four elements (the tile is sized 4 x lanes)
 #define NTT4_LAUNCH(NT)                                                                                                      \
     do {                                                                                                                     \
         if (last) k_fr_ntt_pass4<NT, true><<<blocks, NT, 0, s>>>(in, out, mid, log_n, s0, S, logC, tw, scale_or_null);      \
         else k_fr_ntt_pass4<NT, false><<<blocks, NT, 0, s>>>(in, out, mid, log_n, s0, S, logC, tw, nullptr);               \
     } while (0)
-        if (quads > 256) NTT4_LAUNCH(512);
-        else if (quads > 128) NTT4_LAUNCH(256);
-        else if (quads > 64) NTT4_LAUNCH(128);
-        else NTT4_LAUNCH(64);
+            if (quads > 256) NTT4_LAUNCH(512);
+            else if (quads > 128) NTT4_LAUNCH(256);
+            else if (quads > 64) NTT4_LAUNCH(128);
+            else NTT4_LAUNCH(64);
 #undef NTT4_LAUNCH
+        }
         s0 += S;
     }
+}
+void launch_fr_ntt(hipStream_t s, const uint32_t* in, uint32_t* out, int log_n, const uint32_t* tw,
+                   const uint32_t* scale_or_null, uint32_t* mid) {
+    if (log_n == 0) {  // length 1: the transform is the identity (1/1 = 1)
+        (void)hipMemcpyAsync(out, in, 32, hipMemcpyDeviceToDevice, s);
+        return;
+    }
+    run_fr_ntt_plan(s, in, out, log_n, tw, scale_or_null, mid, ntt_production_plan(log_n));
 }

@@ -1341,6 +1341,30 @@ class HipEngine:
         self._chk(self._lib.kzg_test_g1_raw(self._h, op, arrs[0], arrs[1], out, n))
         return out.raw
 
+    def test_ntt_run(self, vals_be32: bytes, inverse: bool, kernel: int, S: Sequence[int], logC: Sequence[int]) -> bytes:
+        """The transform of 2^log_n elements by the CALLER'S pass plan (kzg_test_ntt_run): kernel 0 register-blocked, 1 radix-2;
+        pass p runs S[p] stages on tiles of 2^logC[p] columns.  KzgError(KZG_E_ARG) for a plan the kernels do not admit."""
+        n = len(vals_be32) // 32
+        if n < 2 or n & (n - 1) or len(S) != len(logC):
+            raise KzgError(_native.KZG_E_ARG, "ntt plan: 2^log_n elements with log_n >= 1, one logC per S")
+        buf = ctypes.create_string_buffer(vals_be32, len(vals_be32))
+        arr_s, arr_c = (ctypes.c_int * max(1, len(S)))(*S), (ctypes.c_int * max(1, len(S)))(*logC)
+        self._chk(self._lib.kzg_test_ntt_run(self._h, ctypes.addressof(buf), n.bit_length() - 1, int(inverse), kernel, len(S),
+                                             arr_s, arr_c))
+        return buf.raw
+
+
+def ntt_plan_of(log_n: int, kernel: int = -1, tile_log: int = 0) -> Tuple[int, List[Tuple[int, int]]]:
+    """The pass plan the library runs for 2^log_n elements (kzg_test_ntt_plan_of; no context, no device): (form, [(S, logC)
+    per pass]) with form 0 register-blocked / 1 radix-2.  kernel -1: the library's choice, 0 / 1: that form; tile_log 0: the
+    library's tile, 8 .. 11: that tile."""
+    lib = _native.load()
+    arr_s, arr_c, passes = (ctypes.c_int * 8)(), (ctypes.c_int * 8)(), ctypes.c_int(0)
+    form = lib.kzg_test_ntt_plan_of(log_n, kernel, tile_log, arr_s, arr_c, ctypes.byref(passes))
+    if form < 0:
+        raise KzgError(form, lib.kzg_last_error(None).decode(errors="replace"))
+    return form, [(arr_s[p], arr_c[p]) for p in range(passes.value)]
+
 
 class RowSet:
     """Rows committed by HipEngine.commit_rows and kept on the device: `handle`, worker `i`, `k` rows of `T` elements and
