@@ -56,6 +56,12 @@ int kzg_test_ntt_plan_of(int log_n, int kernel, int tile_log, int* out_S, int* o
 int kzg_test_ntt_run(kzg_ctx* ctx, uint8_t* inout_be32, int log_n, int inverse, int kernel, int passes, const int* S,
                      const int* logC);
 
+/* ---- the MSM passes of a multi-row call (tests/test_msm_passes_cpu.py): how the library splits k row sets + m tail sets (what
+ * the openings divide out, one scalar set per point) at window c (2^(c-1) buckets per set) into passes of its Pippenger pipeline; long_rows: rows past the
+ * length up to which sets share a pass (2^18).  Host only, no context.  out5: 5 words per pass, room for k + m passes -- first
+ * row, rows, first tail set, tail sets, lane (0 the call's own, 1 its second).  c in [4, 24], k <= 16, m <= 4, else KZG_E_ARG. */
+int kzg_test_msm_passes(int c, int long_rows, uint32_t k, uint32_t m, uint32_t* out5, int* out_passes);
+
 /* the host encoder itself (no GPU): 4 x 14 limbs of 28 bits (X, Y, ZZ, ZZZ; lazy limbs < 2^32; residues with
  * R = 2^392) -> 48-byte compressed point / 192-byte partial record.  Test hooks. */
 int kzg_host_xyzz_to_c48(const uint32_t xyzz_limbs28[56], uint8_t out48[48]);

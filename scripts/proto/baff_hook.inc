@@ -47,8 +47,8 @@ int kzg_proto_baff(kzg_ctx* ctx, int slot, uint64_t n, uint64_t srs_offset, uint
     for (auto& e : ev) HIPCHK(ctx, hipEventCreate(&e));
     HIPCHK(ctx, hipMemsetAsync(L.bufA.p, 0, B * sizeof(g1_xyzz_t), s));
     HIPCHK(ctx, hipEventRecord(ev[0], s));
-    launch_msm_sort(s, sh, ctx->slot[slot].as<uint32_t>(), ctx->slot_mont[slot], nullptr, 0, L.hist.as<uint32_t>(), false,
-                    L.rank.as<uint2>(), L.offsets.as<uint32_t>(), L.sorted.as<uint32_t>(), L.flags() + 2, false, L.flags() + 3);
+    launch_msm_sort(s, sh, ScalarSets::one(ctx->slot[slot].as<uint32_t>(), ctx->slot_mont[slot]), L.hist.as<uint32_t>(), false,
+                    L.rank.as<uint2>(), L.offsets.as<uint32_t>(), L.sorted.as<uint32_t>(), L.flags() + 2, false, L.flags() + 3, nullptr);
     HIPCHK(ctx, hipEventRecord(ev[1], s));
     uint32_t entries = 0;
     HIPCHK(ctx, hipMemcpyAsync(&entries, L.offsets.as<uint32_t>() + B, 4, hipMemcpyDeviceToHost, s));

@@ -285,6 +285,7 @@ SYMBOLS = {
     "kzg_test_g1_raw": (_I, [_P, _I, _P, _P, _B, _U64]),
     "kzg_test_ntt_plan_of": (_I, [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "kzg_test_ntt_run": (_I, [_P, _P, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "kzg_test_msm_passes": (_I, [_I, _I, _U32, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_I)]),
 }
 
 _lib = None

@@ -303,11 +303,10 @@ int kzg_test_field(kzg_ctx* ctx, int field, int op, const uint8_t* a_be, const u
     if (field == 0) k_test_fp<<<blocks, 256, 0, L.stream>>>(op, da, db, L.out_be.as<uint8_t>(), n);
     else if (op == 7 || op == 8) launch_fr_inv_test(L.stream, da, L.out_be.as<uint8_t>(), n, op == 8);   // the device-side inversion alone
     else if (op == 9) {   // the batched inversion of kzg_rows_commit_lookup_sum alone: n elements, one fr9_inv
-        const uint64_t nchunks = (n + 3) / 4;
         HIPCHK(ctx, L.coeffA.ensure(n * 32));
         HIPCHK(ctx, L.coeffB.ensure(n * 32));
-        HIPCHK(ctx, L.hbuf.ensure((nchunks + (nchunks >> 1) + 64) * 32));
-        HIPCHK(ctx, L.hnext.ensure((nchunks + (nchunks >> 1) + 64) * 32));
+        HIPCHK(ctx, L.hbuf.ensure(poly_level_words(n) * 4));
+        HIPCHK(ctx, L.hnext.ensure(poly_level_words(n) * 4));
         HIPCHK(ctx, L.scal.ensure(64));   // [0, 32) the scan's closing slot (unused), [32] zero flag, [36] range flag (unused)
         uint32_t* q = L.coeffA.as<uint32_t>();
         uint32_t* fl = L.scal.as<uint32_t>();
@@ -477,6 +476,20 @@ int kzg_test_ntt_run(kzg_ctx* ctx, uint8_t* inout_be32, int log_n, int inverse, 
     if (rc) return rc;
     HIPCHK(ctx, hipMemcpy(inout_be32, L.out_be.p, n * 32, hipMemcpyDeviceToHost));
     H.clean = true;
+    return KZG_OK;
+}
+
+// ---- the MSM passes of a multi-row call (tests/test_msm_passes_cpu.py)
+int kzg_test_msm_passes(int c, int long_rows, uint32_t k, uint32_t m, uint32_t* out5, int* out_passes) {
+    if (!out5 || !out_passes) return fail(nullptr, KZG_E_ARG, "msm passes: null output");
+    if (c < 4 || c > 24 || k > KZG_MAX_BATCH_OPEN || m > KZG_MAX_OPEN_POINTS)
+        return fail(nullptr, KZG_E_ARG, "msm passes: c in [4, 24], k <= 16 rows, m <= 4 tail sets");
+    MsmPass pass[MR_SETS];
+    *out_passes = (int)plan_msm_passes(c, 1u << (c - 1), long_rows != 0, k, m, pass);
+    for (int p = 0; p < *out_passes; p++) {
+        const uint32_t w[5] = {pass[p].row0, pass[p].nrows, pass[p].tail0, pass[p].ntail, pass[p].lane};
+        memcpy(out5 + 5 * p, w, sizeof w);
+    }
     return KZG_OK;
 }
 

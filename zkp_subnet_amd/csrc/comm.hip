@@ -162,7 +162,7 @@ int kzg_msm_sharded_begin(kzg_ctx* ctx, int slot, uint64_t n, uint64_t srs_offse
     // while the lane's MSM may still be running (hipFree synchronises the whole device)
     if (!rc && L.gather.ensure((size_t)(KZG_MAX_GATHER + 2) * sizeof(g1_xyzz_t)) != hipSuccess)
         rc = fail(ctx, KZG_E_NOMEM, "gather buffer");
-    if (!rc) rc = msm_core(ctx, L, ctx->slot[slot].as<uint32_t>(), ctx->slot_mont[slot], n, srs_offset, L.res());
+    if (!rc) rc = msm_core(ctx, L, ScalarSets::one(ctx->slot[slot].as<uint32_t>(), ctx->slot_mont[slot]), n, srs_offset, L.res());
     if (!rc) {
         launch_xyzz_pack(L.stream, L.res(), reinterpret_cast<uint32_t*>(dev_out_xyzz192), 1);
         hipError_t e = hipEventRecord(L.ev_ext, L.stream);
@@ -532,7 +532,7 @@ int kzg_msm_sharded(kzg_ctx* ctx, int slot, uint64_t n, uint64_t srs_offset, uin
     prof_begin(ctx, L);
     rc = clear_flags(ctx, L);
     if (rc) return rc;
-    rc = msm_core(ctx, L, ctx->slot[slot].as<uint32_t>(), ctx->slot_mont[slot], n, srs_offset, L.res());
+    rc = msm_core(ctx, L, ScalarSets::one(ctx->slot[slot].as<uint32_t>(), ctx->slot_mont[slot]), n, srs_offset, L.res());
     if (rc) return rc;
     {
         Span sp(ctx, L, KZG_T_COLLECTIVE);

@@ -125,17 +125,11 @@ enum {
     TB_COPY = 832,
     TB_ALPHA_M = 832, TB_Y_M = 864, TB_ALPHA_BE = 896, TB_SIZE = 1024
 };
-// the batched opening's record (kzg_commit_open_batch; device Lane::brec, pinned Lane::bpin): k + 1 result points in the
-// XYZZ working form (C_0 .. C_{k-1}, pi), k evaluations big-endian, the GPU-side encodings (host_finish off); [0, BR_COPY)
-// comes back to the host page in one copy before the lane's ordinary record
-enum {
-    BR_RES = 0, BR_EVAL = BR_RES + MSM_MAX_SETS * 224, BR_C48 = BR_EVAL + KZG_MAX_BATCH_OPEN * 32,
-    BR_COPY = BR_C48 + MSM_MAX_SETS * 48, BR_Y_M = BR_COPY, BR_SIZE = BR_Y_M + KZG_MAX_BATCH_OPEN * 32
-};
-static_assert(BR_COPY % 4 == 0 && BR_COPY <= 8192, "the batched record is published by words into an 8 KB page");
-// the multi-point opening's record (kzg_commit_open_multi; the same Lane::brec / bpin): k + m result points (C_0 .. C_{k-1},
-// pi_0 .. pi_{m-1}), the evaluations of up to 64 (row, point) pairs big-endian, the GPU-side encodings -- [0, MR_COPY) is
-// published -- then the pairs' Montgomery evaluations, the points' Montgomery forms and the combinations' h_p(alpha_p)
+// the multi-row record (every call that ends in multi_msms_finish: the batched and multi-point openings, the row sets; device
+// Lane::brec, pinned Lane::bpin): k + m result points in the XYZZ working form (C_0 .. C_{k-1}, pi_0 .. pi_{m-1}), the
+// evaluations of up to 64 (row, point) pairs big-endian, the GPU-side encodings (host_finish off) -- [0, MR_COPY) comes back
+// to the host page in one copy before the lane's ordinary record -- then the pairs' Montgomery evaluations, the points'
+// Montgomery forms and the combinations' h_p(alpha_p)
 #define MR_SETS (KZG_MAX_BATCH_OPEN + KZG_MAX_OPEN_POINTS)
 #define MR_PAIRS (KZG_MAX_BATCH_OPEN * KZG_MAX_OPEN_POINTS)
 enum {
@@ -144,7 +138,7 @@ enum {
     MR_SH_ALPHA_M = MR_HY_M + KZG_MAX_OPEN_POINTS * 32,   // the points of kzg_rows_commit_shplonk in Montgomery form
     MR_SIZE = MR_SH_ALPHA_M + KZG_MAX_SHPLONK_POINTS * 32
 };
-static_assert(MR_COPY % 4 == 0 && MR_COPY <= 8192, "the multi-point record is published by words into an 8 KB page");
+static_assert(MR_COPY % 4 == 0 && MR_COPY <= 8192, "the multi-row record is published by words into an 8 KB page");
 static_assert(MR_PAIRS <= POLY_MAX_PAIRS && KZG_MAX_OPEN_POINTS <= POLY_MAX_POINTS, "one evaluation launch holds every pair");
 #define PIN_MAXLEN 1024           // offset of the fold-depth read-back inside the lane's pinned page
 #define PIN_SEQ 2048              // sequence word of the last published record (polled by finish())
@@ -173,8 +167,9 @@ struct Lane {
     hipEvent_t ev_verify = nullptr;  // beside the request's own kernels (the lane's publish waits for this event)
     DevBuf vbuf;
     bool partial = false;         // outstanding ticket wants the 192-byte partial
-    // kzg_commit_open_batch: its record (BR_*; device + an 8 KB pinned, mapped page), the rows' coefficients and their
-    // gamma-combination -- allocated by the first batched call on the lane
+    // the multi-row calls: their record (MR_*; device brec + the 8 KB pinned, mapped page bpin below), the coefficients of rows
+    // that arrived in evaluation form, and the openings' combinations h_p (the builders: a scratch vector) -- allocated by the
+    // first such call on the lane
     DevBuf brec, bcoef, bcomb;
     // kzg_rows_commit_quotient: the rows' (and L_0's) evaluations on the coset, one vector of E T elements each, and the
     // staging vector the extensions and the pointwise result pass through -- allocated by the first quotient call on the lane
@@ -377,8 +372,16 @@ inline int ilog2_exact(uint64_t n) {
     return l;
 }
 int pick_chunk(uint64_t entries);
-int msm_core(kzg_ctx* ctx, Lane& L, const uint32_t* scalars, int mont, uint64_t n, uint64_t srs_offset, g1_xyzz_t* out_xyzz,
-             const uint32_t* scalars2 = nullptr, int mont2 = 0, int nrows = 1, uint64_t row_stride = 0, int ntail = 1);
+// sc's MSMs over points [srs_offset, srs_offset + n) as one pass on lane L -> out_xyzz[0 .. sc.nsets()); KZG_E_ARG, with
+// nothing queued, for a malformed sc: no sets, a count without scalars, more sets than min(MSM_MAX_SETS, msm_sort_max_sets(c))
+int msm_core(kzg_ctx* ctx, Lane& L, const ScalarSets& sc, uint64_t n, uint64_t srs_offset, g1_xyzz_t* out_xyzz);
+// how a multi-row call's k row sets + m tail sets (its quotients) go through msm_core: pass p takes rows [row0, row0 + nrows)
+// and tail sets [tail0, tail0 + ntail), on the call's lane (lane 0) or its second one.  Pure: window c, nbuckets per set,
+// long_rows = past KZG_BATCHED_ROW_MAX.  out: room for k + m passes; returns their number.
+struct MsmPass {
+    uint32_t row0, nrows, tail0, ntail, lane;
+};
+uint32_t plan_msm_passes(int c, uint32_t nbuckets, bool long_rows, uint32_t k, uint32_t m, MsmPass* out);
 int ensure_twiddles(kzg_ctx* ctx, Lane& L, int log_n, int inverse, uint32_t** tw, uint32_t** invn);
 int row_to_coeffs(kzg_ctx* ctx, Lane& L, const uint32_t* row_dev, uint64_t T, int evaluation_form, const uint32_t** coeffs,
                   uint32_t* dst = nullptr);

@@ -27,19 +27,32 @@ struct MsmShape {
     WinLayout lay;
     uint32_t nbuckets;   // 2^(c-1) per MSM; nbatch MSMs over the same points use nbatch consecutive bucket sets
     uint64_t n;          // number of (scalar, point) pairs in each MSM of the batch
-    int nbatch;          // 1 .. MSM_MAX_SETS MSMs as ONE pass (scalar set b -> bucket set b), see launch_msm_sort
+    int nbatch;          // 1 .. MSM_MAX_SETS MSMs as ONE pass (scalar set b -> bucket set b), see ScalarSets
     uint64_t srs_offset; // first point of the slice inside the resident SRS
     uint64_t srs_stride; // points per window table (= total resident SRS points)
     int chunk;           // sorted entries per lane in msm_accumulate
 };
 
+// What one pass sorts: nrows sets at rows + b * stride words (Montgomery form when rows_mont), then ntail more at
+// tail + b * stride (the openings' quotients, canonical: tail_mont = 0).  Every set has the pass's n scalars; scalar set b
+// goes to bucket set b and root b, rows first.  A base may be null only where its count is 0.
+struct ScalarSets {
+    const uint32_t* rows;
+    int rows_mont, nrows;
+    const uint32_t* tail;
+    int tail_mont, ntail;
+    uint64_t stride;
+    int nsets() const { return nrows + ntail; }
+    static ScalarSets one(const uint32_t* scalars, int mont) { return {scalars, mont, 1, nullptr, 0, 0, 0}; }
+    static ScalarSets rows_tail(const uint32_t* rows, int nrows, const uint32_t* tail, int ntail, uint64_t stride) {
+        return {rows, 1, nrows, tail, 0, ntail, stride};
+    }
+};
 // signed-digit recode + two-level counting sort: fills offsets[0..nbuckets] and sorted[0..entries).
 // part_ws: 16384 u32 scratch; parted: one uint2 per entry
-// With sh.nbatch == S > 1 scalar sets (same length, same points) set b is sorted into bucket set b: sets 0 .. nrows-1 lie at
-// scalars + b * set_stride words (Montgomery form scalars_mont), sets nrows .. S-1 at scalars2 + (b - nrows) * set_stride
-// (scalars2_mont); nrows < 0 means S - 1 (one trailing set).  The key gets
-// ceil(log2 S) more high bits (key = set << (c-1) | digit - 1, at most 24 bits: msm_sort_max_sets), everything downstream
-// just sees S * nbuckets buckets; partitions of the key space beyond the last set are not launched.
+// sc: the sh.nbatch scalar sets.  With S > 1 sets the key gets ceil(log2 S) more high bits (key = set << (c-1) | digit - 1,
+// at most 24 bits: msm_sort_max_sets), everything downstream just sees S * nbuckets buckets; partitions of the key space
+// beyond the last set are not launched.
 // part_ws_clean: the partition counts / cursors are known to be zero (a completed sort leaves them so); max_len_word: the
 // MSM's fold-depth word, reset here (launch_fold_maxlen accumulates into it).  fast: no count pass, fixed-capacity
 // partition regions (parted must hold msm_sort_parted_entries(sh, true) entries); when a region overflows,
@@ -55,10 +68,9 @@ struct SortTail {
     uint32_t* seq_word;      // the page's sequence word
     uint32_t seq;
 };
-void launch_msm_sort(hipStream_t s, const MsmShape& sh, const uint32_t* scalars, int scalars_mont,
-                     const uint32_t* scalars2, int scalars2_mont, uint32_t* part_ws, bool part_ws_clean, uint2* parted,
-                     uint32_t* offsets, uint32_t* sorted, uint32_t* max_len_word, bool fast, uint32_t* overflow_word,
-                     const SortTail* tail = nullptr, uint64_t set_stride = 0, int nrows = -1);
+void launch_msm_sort(hipStream_t s, const MsmShape& sh, const ScalarSets& sc, uint32_t* part_ws, bool part_ws_clean,
+                     uint2* parted, uint32_t* offsets, uint32_t* sorted, uint32_t* max_len_word, bool fast,
+                     uint32_t* overflow_word, const SortTail* tail);
 // scalar sets per MSM (one sort, one bucket tree with nbatch roots); KZG_MAX_BATCH_OPEN rows + the batched opening's quotient
 #define MSM_MAX_SETS 17
 // how many scalar sets one pass of window c can carry: the sort's key (set bits + c - 1 digit bits) has at most 24 bits

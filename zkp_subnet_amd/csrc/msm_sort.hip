@@ -28,7 +28,7 @@ struct SortShape {
     uint64_t n, total, srs_offset, srs_stride;  // n scalars per set, total = n * sets
     const uint32_t* scalars2;                   // the trailing sets nrows .. nsets-1 of a batch of nsets > 1 MSMs
     uint64_t stride;                            // words between consecutive sets (rows at `scalars`, trailing at scalars2)
-    int nsets, nrows;                           // nrows: sets at the kernels' `scalars` (nsets - 1 unless set otherwise)
+    int nsets, nrows;                           // nrows: sets at the kernels' `scalars` (sort_shape)
     int mont, mont2, keybits, hbits, lbits;     // key = set << keybits | digit magnitude - 1 = (part << lbits) | low
     uint32_t spb;                               // scalars per workgroup in the two level-1 kernels
 };
@@ -650,13 +650,12 @@ int msm_sort_max_sets(int c) {
     const int room = 24 - (c - 1);   // key bits left for the set index
     return room >= 5 ? MSM_MAX_SETS : 1 << room;
 }
-static void sort_shape(const MsmShape& sh, const uint32_t* scalars2, int scalars_mont, int scalars2_mont, SortShape& ss,
-                       uint64_t set_stride = 0, int nrows = -1) {
+// the geometry of a sort of sh.nbatch sets (everything but where the scalars lie: sort_shape)
+static void sort_geometry(const MsmShape& sh, SortShape& ss) {
     const int setbits = set_bits(sh.nbatch);
     const int keybits = sh.c - 1 + setbits;
     ss.n = sh.n; ss.total = sh.n * (uint64_t)sh.nbatch; ss.srs_offset = sh.srs_offset; ss.srs_stride = sh.srs_stride;
-    ss.mont = scalars_mont; ss.scalars2 = scalars2; ss.mont2 = scalars2_mont; ss.keybits = sh.c - 1;
-    ss.stride = set_stride; ss.nsets = sh.nbatch; ss.nrows = nrows < 0 ? sh.nbatch - 1 : nrows;
+    ss.keybits = sh.c - 1; ss.nsets = sh.nbatch;
     // 1024 partitions (level 2 runs one workgroup per partition), up to 4096 when that brings a partition down to what
     // level 2 can stage in LDS (SORT_STAGE entries; ~13 k on average at 2^20 / 1024, ~27 k at 2^22 / 2048 and 2^23 / 4096)
     const uint64_t entries = ss.total * (uint64_t)sh.nwin;
@@ -674,13 +673,26 @@ static void sort_shape(const MsmShape& sh, const uint32_t* scalars2, int scalars
     ss.lbits = keybits - hbits;
     ss.spb = ss.total >= (1u << 21) ? 4096u : 1024u;
 }
+// Where the kernels find set b: sets 0 .. ss.nrows - 1 at the kernel argument `scalars` (returned), the rest at ss.scalars2,
+// both at ss.stride; the one- and two-set kernels read set 0 at `scalars` and set 1 at ss.scalars2 whatever ss.nrows says.
+// So a pass of more than two sets splits where sc does, a shorter one behind its first set.
+static const uint32_t* sort_shape(const MsmShape& sh, const ScalarSets& sc, SortShape& ss) {
+    sort_geometry(sh, ss);
+    auto base = [&](int b) { return b < sc.nrows ? sc.rows + b * sc.stride : sc.tail + (b - sc.nrows) * sc.stride; };
+    auto mont = [&](int b) { return b < sc.nrows ? sc.rows_mont : sc.tail_mont; };
+    const int split = sh.nbatch > 2 ? sc.nrows : 1;
+    const bool rest = split < sh.nbatch;
+    ss.stride = sc.stride; ss.nrows = split; ss.mont = mont(0);
+    ss.scalars2 = rest ? base(split) : nullptr; ss.mont2 = rest ? mont(split) : 0;
+    return base(0);
+}
 // the partitions that hold keys: nbatch sets of 2^(c-1) buckets (all 2^hbits of them unless nbatch is not a power of two)
 static uint32_t sort_npart_used(const SortShape& ss) { return (uint32_t)ss.nsets << (ss.hbits - set_bits(ss.nsets)); }
 uint64_t msm_sort_parted_entries(const MsmShape& sh, bool fast) {  // capacity of `parted`, in entries
     const uint64_t entries = (uint64_t)sh.n * sh.nbatch * sh.nwin;
     if (!fast) return entries;
     SortShape ss;
-    sort_shape(sh, nullptr, 0, 0, ss);
+    sort_geometry(sh, ss);
     return msm_sort_region_cap(entries, sort_npart_used(ss)) * sort_npart_used(ss);
 }
 // rounds per workgroup of the staged level-1 partition (A/B knob KZG_SORT_ROUNDS = 1 | 2): two from 2^20 scalars up
@@ -719,19 +731,14 @@ static void launch_partition_staged(hipStream_t s, const uint32_t* scalars, cons
 // the cursors, level 2 reads the regions.  If a region overflows (skewed scalars) *overflow_word is raised, the offsets
 // come out all zero (the queued accumulate sees an empty MSM) and the caller reruns in EXACT mode: count pass, exact
 // bases, no overflow possible.  Both leave the partition counts / cursors zero for the next sort.
-void launch_msm_sort(hipStream_t s, const MsmShape& sh, const uint32_t* scalars, int scalars_mont,
-                     const uint32_t* scalars2, int scalars2_mont, uint32_t* part_ws, bool part_ws_clean, uint2* parted,
-                     uint32_t* offsets, uint32_t* sorted, uint32_t* max_len_word, bool fast, uint32_t* overflow_word,
-                     const SortTail* tail, uint64_t set_stride, int nrows) {
+void launch_msm_sort(hipStream_t s, const MsmShape& sh, const ScalarSets& sc, uint32_t* part_ws, bool part_ws_clean,
+                     uint2* parted, uint32_t* offsets, uint32_t* sorted, uint32_t* max_len_word, bool fast,
+                     uint32_t* overflow_word, const SortTail* tail) {
     SortTail tl{0u, nullptr, nullptr, nullptr, 0u};
     if (tail) tl = *tail;
     uint32_t* done = part_ws + 3 * SORT_MAXPART + 16;   // k_sort_buckets' ticket counter (zero between sorts)
-    if (!scalars2 && sh.nbatch > 1) {   // every set at the stride: the last one too
-        scalars2 = scalars + (uint64_t)(sh.nbatch - 1) * set_stride;
-        scalars2_mont = scalars_mont;
-    }
     SortShape ss;
-    sort_shape(sh, scalars2, scalars_mont, scalars2_mont, ss, set_stride, nrows);
+    const uint32_t* scalars = sort_shape(sh, sc, ss);
     const uint64_t entries = ss.total * (uint64_t)sh.nwin;
     const uint32_t npart = 1u << ss.hbits;
     // level 2 runs over the partitions that hold keys only: the bucket arrays downstream hold exactly nbatch * 2^(c-1) buckets

@@ -28,14 +28,6 @@ int pick_chunk(uint64_t entries) {
     const uint64_t k = (entries + lanes * rounds - 1) / (lanes * rounds);
     return (int)k;
 }
-// ---- the MSM pipeline on device-resident scalars -> one XYZZ point at out_xyzz (device), on lane L.
-// With scalars2 != null: TWO MSMs over the same n points in one pass (the commitment and the opening of one row):
-// set b is sorted into bucket set b, the sort / accumulate / fold / tree kernels simply see twice the buckets, the
-// tree stops at two roots and out_xyzz[0..1] receive the two sums.  One kernel sequence, one latency-bound tail.
-// nrows > 1 (the batched opening): sets 0 .. nrows-1 lie at scalars + b * row_stride words, scalars2 (if given) is set
-// nrows; nrows + 1 <= msm_sort_max_sets(c) sets, nrows + 1 roots at out_xyzz[0 ..].  ntail > 1 (the multi-point opening):
-// scalars2 holds ntail sets at the same stride (its quotients), sets nrows .. nrows + ntail - 1.
-// The only host wait inside is on the 4-byte fold-depth read-back; the calling thread holds no lock meanwhile.
 // The bucket tree on stream s: merges level arrays until `stop` nodes are left.  Three buffers in rotation (a level reads its
 // own array and the P array of the level below, writes the next) plus a fourth for the two-level launches.  On return b.in is
 // the last level array, b.prev the level below it, b.out a buffer nothing reads any more.
@@ -65,11 +57,17 @@ static void run_tree(hipStream_t s, TreeBufs& b, uint32_t n_in, uint32_t stop) {
         n_in >>= 1;
     }
 }
-int msm_core(kzg_ctx* ctx, Lane& L, const uint32_t* scalars, int mont, uint64_t n, uint64_t srs_offset,
-             g1_xyzz_t* out_xyzz, const uint32_t* scalars2, int mont2, int nrows, uint64_t row_stride, int ntail) {
+// ---- the MSM pipeline on device-resident scalars, on lane L: the S = sc.nsets() MSMs of sc's scalar sets over the same n
+// points in ONE pass -- set b is sorted into bucket set b, the sort / accumulate / fold / tree kernels simply see S times the
+// buckets, the tree stops at S roots and out_xyzz[0 .. S-1] (device, XYZZ) receive the sums.  One kernel sequence, one
+// latency-bound tail.  The only host wait inside is on the 4-byte fold-depth read-back; the calling thread holds no lock
+// meanwhile.
+int msm_core(kzg_ctx* ctx, Lane& L, const ScalarSets& sc, uint64_t n, uint64_t srs_offset, g1_xyzz_t* out_xyzz) {
     hipStream_t s = L.stream;
-    const int nbatch = nrows + (scalars2 ? ntail : 0);
-    if (nrows < 1 || nbatch > std::min(MSM_MAX_SETS, msm_sort_max_sets(ctx->c)))
+    const int nbatch = sc.nsets();
+    if (sc.nrows < 0 || sc.ntail < 0 || nbatch < 1 || (sc.nrows && !sc.rows) || (sc.ntail && !sc.tail))
+        return fail(ctx, KZG_E_ARG, "MSM pass without scalar sets, or with a count and no scalars");
+    if (nbatch > std::min(MSM_MAX_SETS, msm_sort_max_sets(ctx->c)))
         return fail(ctx, KZG_E_ARG, "MSM pass with more scalar sets than the sort's key can carry");
     if (n == 0) {
         HIPCHK(ctx, hipMemsetAsync(out_xyzz, 0, nbatch * sizeof(g1_xyzz_t), s));
@@ -114,9 +112,8 @@ int msm_core(kzg_ctx* ctx, Lane& L, const uint32_t* scalars, int mont, uint64_t 
     auto sort_and_publish = [&](bool fast_mode, bool ws_clean) {
         const SortTail tail{(uint32_t)sh.chunk, L.bufA.as<g1_xyzz_t>(), reinterpret_cast<uint32_t*>(L.pin_dev + PIN_MAXLEN),
                             reinterpret_cast<uint32_t*>(L.pin_dev + PIN_SEQ_SORT), ++L.sort_seq};
-        launch_msm_sort(s, sh, scalars, mont, scalars2, mont2, L.hist.as<uint32_t>(), ws_clean, L.rank.as<uint2>(),
-                        L.offsets.as<uint32_t>(), L.sorted.as<uint32_t>(), max_len_d, fast_mode, max_len_d + 1,
-                        &tail, row_stride, scalars2 ? nrows : -1);
+        launch_msm_sort(s, sh, sc, L.hist.as<uint32_t>(), ws_clean, L.rank.as<uint2>(), L.offsets.as<uint32_t>(),
+                        L.sorted.as<uint32_t>(), max_len_d, fast_mode, max_len_d + 1, &tail);
     };
     {
         Span sp(ctx, L, KZG_T_DIGITS);
@@ -231,6 +228,16 @@ int row_to_coeffs(kzg_ctx* ctx, Lane& L, const uint32_t* row_dev, uint64_t T, in
     *coeffs = dst;
     return KZG_OK;
 }
+// k rows (k x T elements at rows_dev) in evaluation form: the inverse transform of each into dst (k x T); rows that are
+// coefficients already stay where they are
+static int rows_to_coeffs(kzg_ctx* ctx, Lane& L, const uint32_t* rows_dev, uint32_t k, uint64_t T, int evaluation_form,
+                          uint32_t* dst) {
+    for (uint32_t j = 0; evaluation_form && T > 1 && j < k; j++) {
+        const uint32_t* c;
+        if (int rc = row_to_coeffs(ctx, L, rows_dev + j * T * 8, T, 1, &c, dst + j * T * 8)) return rc;
+    }
+    return KZG_OK;
+}
 int check_worker(kzg_ctx* ctx, uint32_t i, uint64_t T) {
     int rc = need_srs(ctx);
     if (rc) return rc;
@@ -312,15 +319,14 @@ int commit_open_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* row_d
         HIPCHK(ctx, hipStreamWaitEvent(so, A.ev_coeffs, 0));
     }
     if (out_c48 && !batched) {
-        rc = msm_core(ctx, A, coeffs, 1, T, offset, res);
+        rc = msm_core(ctx, A, ScalarSets::one(coeffs, 1), T, offset, res);
         if (rc) return rc;
     }
     if (out_p48) {
         uint32_t* alpha_m = reinterpret_cast<uint32_t*>(A.tail + TB_ALPHA_M);
         uint32_t* y_m = reinterpret_cast<uint32_t*>(A.tail + TB_Y_M);
-        const uint64_t nchunks = (T + 3) / 4;
-        HIPCHK(ctx, O.hbuf.ensure((nchunks + (nchunks >> 1) + 64) * 32));
-        HIPCHK(ctx, O.hnext.ensure((nchunks + (nchunks >> 1) + 64) * 32));
+        HIPCHK(ctx, O.hbuf.ensure(poly_level_words(T) * 4));
+        HIPCHK(ctx, O.hnext.ensure(poly_level_words(T) * 4));
         HIPCHK(ctx, O.qbuf.ensure(T * 32));
         {
             Span sp(ctx, A, KZG_T_POLY, so);
@@ -331,9 +337,9 @@ int commit_open_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* row_d
         if (batched) {
             // the quotient has T - 1 coefficients; k_poly_quotient leaves a zero in slot T - 1, so it rides as a second
             // length-T scalar set
-            rc = msm_core(ctx, A, coeffs, 1, T, offset, res, O.qbuf.as<uint32_t>(), 0);
+            rc = msm_core(ctx, A, ScalarSets::rows_tail(coeffs, 1, O.qbuf.as<uint32_t>(), 1, 0), T, offset, res);
         } else {
-            rc = msm_core(ctx, O, O.qbuf.as<uint32_t>(), 0, T - 1, offset, res + 1);
+            rc = msm_core(ctx, O, ScalarSets::one(O.qbuf.as<uint32_t>(), 0), T - 1, offset, res + 1);
         }
         if (rc) return rc;
         if (B) {
@@ -374,120 +380,7 @@ int commit_open_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* row_d
 }
 
 
-// ---- the batched opening (kzg_commit_open_batch): k rows f_j of worker i, one point alpha, one challenge gamma.
-//   INTT of each row -> the k evaluations y_j = f_j(alpha) side by side (launch_poly_eval_rows: the launches of ONE
-//   evaluation) -> h = sum_j gamma^j f_j (launch_fr_combine_rows) -> the opening of h (launch_poly_open: its quotient
-//   lands in the proof's scalar set) -> the k + 1 MSMs over the slice U_i.
-//  * rows up to KZG_BATCHED_ROW_MAX (latency-bound): ONE msm_core pass with k + 1 scalar sets -- one sort, one accumulate,
-//    one bucket tree with k + 1 roots -- as far as the window leaves the sort's key room (msm_sort_max_sets); beyond that
-//    as few passes as fit; bucket memory caps a pass at 2^22 buckets;
-//  * longer rows (throughput-bound: a multi-set pass there only adds buckets to a sort that is no longer latency): k + 1
-//    single MSMs alternating between this lane and a second one when one is free, as commit_open_dev spreads its two --
-//    k + 1 MSMs where k single-row calls run 2k.
-#ifndef KZG_BATCH_PASS_SETS
-#define KZG_BATCH_PASS_SETS MSM_MAX_SETS   // (A/B knob: a smaller cap splits a batch into more passes)
-#endif
-int commit_open_batch_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* rows_dev, uint32_t k, uint64_t T,
-                          int evaluation_form, const uint8_t* alpha_be32, const uint8_t* gamma_be32, uint8_t* out_c48,
-                          uint8_t* out_evals32, uint8_t* out_p48) {
-    Lane& A = H.L();
-    hipStream_t s = A.stream;
-    HIPCHK(ctx, A.brec.ensure(BR_SIZE));
-    if (!A.bpin) {
-        uint8_t* p = nullptr;
-        HIPCHK(ctx, hipHostMalloc((void**)&p, 8192, hipHostMallocMapped | hipHostMallocCoherent));
-        A.bpin = p;
-        HIPCHK(ctx, hipHostGetDevicePointer((void**)&A.bpin_dev, A.bpin, 0));
-    }
-    const uint64_t words = T * 8;   // one row, in words
-    const uint32_t* coef = rows_dev;
-    if (evaluation_form && T > 1) {
-        HIPCHK(ctx, A.bcoef.ensure(k * T * 32));
-        for (uint32_t j = 0; j < k; j++) {
-            const uint32_t* c;
-            int rc = row_to_coeffs(ctx, A, rows_dev + j * words, T, 1, &c, A.bcoef.as<uint32_t>() + j * words);
-            if (rc) return rc;
-        }
-        coef = A.bcoef.as<uint32_t>();
-    }
-    uint8_t* rec = A.brec.as<uint8_t>();
-    g1_xyzz_t* res = reinterpret_cast<g1_xyzz_t*>(rec + BR_RES);
-    uint32_t* alpha_m = reinterpret_cast<uint32_t*>(A.tail + TB_ALPHA_M);
-    uint32_t* y_m = reinterpret_cast<uint32_t*>(A.tail + TB_Y_M);
-    const uint64_t nchunks = (T + 3) / 4;
-    const uint64_t hrow = (nchunks + (nchunks >> 1) + 64) * 8;   // level scratch of one row, words
-    HIPCHK(ctx, A.hbuf.ensure(k * hrow * 4));
-    HIPCHK(ctx, A.hnext.ensure(k * hrow * 4));
-    HIPCHK(ctx, A.bcomb.ensure(T * 32));
-    HIPCHK(ctx, A.qbuf.ensure(T * 32));
-    uint32_t* hcomb = A.bcomb.as<uint32_t>();
-    uint32_t* q = A.qbuf.as<uint32_t>();
-    {
-        Span sp(ctx, A, KZG_T_POLY);
-        // alpha rides in as an argument of the evaluations' first kernel, gamma as one of the combination's
-        launch_poly_eval_rows(s, coef, T, k, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), hrow,
-                              reinterpret_cast<uint32_t*>(rec + BR_Y_M), alpha_be32, A.flags(), rec + BR_EVAL);
-        launch_fr_combine_rows(s, coef, T, k, gamma_be32, hcomb, A.flags());
-        // k_poly_quotient leaves a zero in slot T - 1: the quotient rides as one more length-T scalar set
-        launch_poly_open(s, hcomb, T, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), y_m, q);
-    }
-    const uint64_t offset = (uint64_t)i * ctx->T;
-    const bool batched = T <= KZG_BATCHED_ROW_MAX;
-    // sets per pass: what the sort's key carries (msm_sort_max_sets), at most 2^22 buckets; long rows one set per pass
-    int per = std::min(KZG_BATCH_PASS_SETS, msm_sort_max_sets(ctx->c));
-    while (per > 2 && (uint64_t)per * ctx->nbuckets > ((uint64_t)1 << 22)) per--;
-    if (!batched) per = 1;
-    const uint32_t sets = k + 1, passes = (sets + per - 1) / per;   // set k is the quotient
-    Lane* B = (!batched && passes > 1) ? H.second() : nullptr;
-    if (B) {
-        HIPCHK(ctx, hipEventRecord(A.ev_coeffs, s));
-        HIPCHK(ctx, hipStreamWaitEvent(B->stream, A.ev_coeffs, 0));
-    }
-    for (uint32_t p = 0; p < passes; p++) {
-        Lane& L = (B && (p & 1)) ? *B : A;
-        const uint32_t a = p * per, b = std::min(sets, a + per);
-        const uint32_t m = std::min(b, k) - std::min(a, k);   // rows in this pass
-        const bool with_q = b == sets;
-        int rc = m ? msm_core(ctx, L, coef + (uint64_t)a * words, 1, T, offset, res + a, with_q ? q : nullptr, 0, (int)m, words)
-                   : msm_core(ctx, L, q, 0, T, offset, res + k);
-        if (rc) return rc;
-    }
-    if (B) {
-        HIPCHK(ctx, hipEventRecord(B->ev_done, B->stream));
-        HIPCHK(ctx, hipStreamWaitEvent(s, B->ev_done, 0));
-    }
-    if (!ctx->host_finish) {
-        Span sp(ctx, A, KZG_T_FINAL);
-        for (uint32_t p = 0; p + 1 < sets; p += 2)
-            launch_g1_compress_pair(s, res + p, res + p + 1, rec + BR_C48 + 48 * p, rec + BR_C48 + 48 * (p + 1));
-        if (sets & 1) launch_g1_compress(s, res + k, rec + BR_C48 + 48 * k);
-    }
-    launch_publish(s, rec, A.bpin_dev, BR_COPY);   // stream-ordered ahead of finish()'s record and its sequence word
-    int rc = finish(ctx, A);
-    if (rc) return rc;
-    if (ctx->host_finish) {
-        uint8_t enc[MSM_MAX_SETS * 48];
-        kzg_host::xyzz_batch_to_c48(reinterpret_cast<const uint32_t*>(A.bpin + BR_RES), sets, enc);
-        memcpy(out_c48, enc, 48 * (size_t)k);
-        memcpy(out_p48, enc + 48 * (size_t)k, 48);
-    } else {
-        memcpy(out_c48, A.bpin + BR_C48, 48 * (size_t)k);
-        memcpy(out_p48, A.bpin + BR_C48 + 48 * (size_t)k, 48);
-    }
-    memcpy(out_evals32, A.bpin + BR_EVAL, 32 * (size_t)k);
-    H.clean = true;
-    return KZG_OK;
-}
-
-// ---- the multi-point opening (kzg_commit_open_multi): k rows f_j of worker i, m points alpha_p, point p opening the rows of
-// masks[p] with its own challenge gamma_p.
-//   INTT of each row (once) -> every masked (row, point) pair evaluated side by side (launch_poly_eval_pairs: the launches
-//   of ONE evaluation; rows past KZG_BATCHED_ROW_MAX in groups of KZG_MAX_BATCH_OPEN pairs, whose level scratch is large)
-//   -> the m combinations h_p in one launch (launch_fr_combine_points) -> their m openings side by side
-//   (launch_poly_open_points: the quotients land in m consecutive length-T scalar sets) -> the k + m MSMs over U_i, split
-//   into passes exactly as commit_open_batch_dev splits its k + 1 (one pass while the sort's key and 2^22 buckets allow).
-// The committed row sets (kzg_rows_commit / kzg_rows_open) run the two halves of the same sequence: the commit its INTT and
-// k MSMs, the open its pairs, combinations, quotients and m MSMs, reading the rows through the same table of row pointers.
+// ---- the back half of every multi-row call: k row sets + m quotient sets -> passes of msm_core -> the record -> the host.
 
 // the multi-row record (MR_*) and its pinned page, allocated by the first multi-row call on the lane
 static int ensure_multi_record(kzg_ctx* ctx, Lane& A) {
@@ -500,6 +393,123 @@ static int ensure_multi_record(kzg_ctx* ctx, Lane& A) {
     }
     return KZG_OK;
 }
+#ifndef KZG_BATCH_PASS_SETS
+#define KZG_BATCH_PASS_SETS MSM_MAX_SETS   // (A/B knob: a smaller cap splits a batch into more passes)
+#endif
+// Sets 0 .. k-1 are the rows, k .. k+m-1 the quotients; consecutive sets share a pass.
+//  * rows up to KZG_BATCHED_ROW_MAX (latency-bound): as many sets per pass as the sort's key carries (msm_sort_max_sets);
+//    bucket memory caps a pass of more than two sets at 2^22 buckets;
+//  * longer rows (throughput-bound: a multi-set pass there only adds buckets to a sort that is no longer latency): one set
+//    per pass, alternating between the call's lane and a second one (when one is free), as commit_open_dev spreads its two.
+uint32_t plan_msm_passes(int c, uint32_t nbuckets, bool long_rows, uint32_t k, uint32_t m, MsmPass* out) {
+    uint32_t per = (uint32_t)std::min(KZG_BATCH_PASS_SETS, msm_sort_max_sets(c));
+    while (per > 2 && (uint64_t)per * nbuckets > ((uint64_t)1 << 22)) per--;
+    if (long_rows) per = 1;
+    uint32_t passes = 0;
+    for (uint32_t a = 0; a < k + m; a += per, passes++) {
+        const uint32_t b = std::min(k + m, a + per), ra = std::min(a, k), rb = std::min(b, k);
+        out[passes] = MsmPass{ra, rb - ra, a - ra, (b - a) - (rb - ra), long_rows ? passes & 1u : 0u};
+    }
+    return passes;
+}
+// the MSMs over U_i and the end of a multi-row call: the k rows (Montgomery, consecutive at coef) and the m quotients in
+// A.qbuf, in the passes of plan_msm_passes.  Writes the k commitments, the npairs evaluations of the record and the m proofs
+// (each output unused when its count is 0).
+static int multi_msms_finish(kzg_ctx* ctx, LaneHold& H, uint32_t i, uint64_t T, const uint32_t* coef, uint32_t k,
+                             uint32_t m, uint32_t npairs, uint8_t* out_c48, uint8_t* out_evals32, uint8_t* out_p48) {
+    Lane& A = H.L();
+    hipStream_t s = A.stream;
+    const uint64_t words = T * 8;   // one row, in words
+    uint8_t* rec = A.brec.as<uint8_t>();
+    g1_xyzz_t* res = reinterpret_cast<g1_xyzz_t*>(rec + MR_RES);
+    const uint32_t* q = A.qbuf.as<uint32_t>();
+    MsmPass pass[MR_SETS];
+    const uint32_t sets = k + m, passes = plan_msm_passes(ctx->c, ctx->nbuckets, T > KZG_BATCHED_ROW_MAX, k, m, pass);
+    Lane* B = (passes > 1 && pass[1].lane) ? H.second() : nullptr;
+    if (B) {
+        HIPCHK(ctx, hipEventRecord(A.ev_coeffs, s));
+        HIPCHK(ctx, hipStreamWaitEvent(B->stream, A.ev_coeffs, 0));
+    }
+    for (uint32_t p = 0; p < passes; p++) {
+        const MsmPass& P = pass[p];
+        const ScalarSets sc = ScalarSets::rows_tail(P.nrows ? coef + P.row0 * words : nullptr, (int)P.nrows,
+                                                    P.ntail ? q + P.tail0 * words : nullptr, (int)P.ntail, words);
+        if (int rc = msm_core(ctx, (B && P.lane) ? *B : A, sc, T, (uint64_t)i * ctx->T, res + P.row0 + P.tail0)) return rc;
+    }
+    if (B) {
+        HIPCHK(ctx, hipEventRecord(B->ev_done, B->stream));
+        HIPCHK(ctx, hipStreamWaitEvent(s, B->ev_done, 0));
+    }
+    if (!ctx->host_finish) {
+        Span sp(ctx, A, KZG_T_FINAL);
+        for (uint32_t p = 0; p + 1 < sets; p += 2)
+            launch_g1_compress_pair(s, res + p, res + p + 1, rec + MR_C48 + 48 * p, rec + MR_C48 + 48 * (p + 1));
+        if (sets & 1) launch_g1_compress(s, res + sets - 1, rec + MR_C48 + 48 * (sets - 1));
+    }
+    launch_publish(s, rec, A.bpin_dev, MR_COPY);   // stream-ordered ahead of finish()'s record and its sequence word
+    int rc = finish(ctx, A);
+    if (rc) return rc;
+    if (ctx->host_finish) {
+        uint8_t enc[MR_SETS * 48];
+        kzg_host::xyzz_batch_to_c48(reinterpret_cast<const uint32_t*>(A.bpin + MR_RES), sets, enc);
+        if (k) memcpy(out_c48, enc, 48 * (size_t)k);
+        if (m) memcpy(out_p48, enc + 48 * (size_t)k, 48 * (size_t)m);
+    } else {
+        if (k) memcpy(out_c48, A.bpin + MR_C48, 48 * (size_t)k);
+        if (m) memcpy(out_p48, A.bpin + MR_C48 + 48 * (size_t)k, 48 * (size_t)m);
+    }
+    if (npairs) memcpy(out_evals32, A.bpin + MR_EVAL, 32 * (size_t)npairs);
+    H.clean = true;
+    return KZG_OK;
+}
+
+// ---- the batched opening (kzg_commit_open_batch): k rows f_j of worker i, one point alpha, one challenge gamma.
+//   INTT of each row -> the k evaluations y_j = f_j(alpha) side by side (launch_poly_eval_rows: the launches of ONE
+//   evaluation) -> h = sum_j gamma^j f_j (launch_fr_combine_rows) -> the opening of h (launch_poly_open: its quotient
+//   lands in the proof's scalar set) -> the k + 1 MSMs over the slice U_i (multi_msms_finish with one quotient): one pass
+//   for short rows while the window leaves the sort's key room, k + 1 MSMs where k single-row calls run 2k.
+int commit_open_batch_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* rows_dev, uint32_t k, uint64_t T,
+                          int evaluation_form, const uint8_t* alpha_be32, const uint8_t* gamma_be32, uint8_t* out_c48,
+                          uint8_t* out_evals32, uint8_t* out_p48) {
+    Lane& A = H.L();
+    hipStream_t s = A.stream;
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const bool intt = evaluation_form && T > 1;
+    if (intt) HIPCHK(ctx, A.bcoef.ensure(k * T * 32));
+    const uint32_t* coef = intt ? A.bcoef.as<uint32_t>() : rows_dev;
+    if (int rc = rows_to_coeffs(ctx, A, rows_dev, k, T, evaluation_form, A.bcoef.as<uint32_t>())) return rc;
+    uint8_t* rec = A.brec.as<uint8_t>();   // (alpha and y of the combination's opening: the lane's own tail record)
+    uint32_t* alpha_m = reinterpret_cast<uint32_t*>(A.tail + TB_ALPHA_M);
+    uint32_t* y_m = reinterpret_cast<uint32_t*>(A.tail + TB_Y_M);
+    const uint64_t hrow = poly_level_words(T);   // level scratch of one row
+    HIPCHK(ctx, A.hbuf.ensure(k * hrow * 4));
+    HIPCHK(ctx, A.hnext.ensure(k * hrow * 4));
+    HIPCHK(ctx, A.bcomb.ensure(T * 32));
+    HIPCHK(ctx, A.qbuf.ensure(T * 32));
+    uint32_t* hcomb = A.bcomb.as<uint32_t>();
+    uint32_t* q = A.qbuf.as<uint32_t>();
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        // alpha rides in as an argument of the evaluations' first kernel, gamma as one of the combination's
+        launch_poly_eval_rows(s, coef, T, k, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), hrow,
+                              reinterpret_cast<uint32_t*>(rec + MR_Y_M), alpha_be32, A.flags(), rec + MR_EVAL);
+        launch_fr_combine_rows(s, coef, T, k, gamma_be32, hcomb, A.flags());
+        // k_poly_quotient leaves a zero in slot T - 1: the quotient rides as one more length-T scalar set
+        launch_poly_open(s, hcomb, T, alpha_m, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), y_m, q);
+    }
+    return multi_msms_finish(ctx, H, i, T, coef, k, 1, k, out_c48, out_evals32, out_p48);
+}
+
+// ---- the multi-point opening (kzg_commit_open_multi): k rows f_j of worker i, m points alpha_p, point p opening the rows of
+// masks[p] with its own challenge gamma_p.
+//   INTT of each row (once) -> every masked (row, point) pair evaluated side by side (launch_poly_eval_pairs: the launches
+//   of ONE evaluation; rows past KZG_BATCHED_ROW_MAX in groups of KZG_MAX_BATCH_OPEN pairs, whose level scratch is large)
+//   -> the m combinations h_p in one launch (launch_fr_combine_points) -> their m openings side by side
+//   (launch_poly_open_points: the quotients land in m consecutive length-T scalar sets) -> the k + m MSMs over U_i
+//   (multi_msms_finish: one pass while the sort's key and 2^22 buckets allow).
+// The committed row sets (kzg_rows_commit / kzg_rows_open) run the two halves of the same sequence: the commit its INTT and
+// k MSMs, the open its pairs, combinations, quotients and m MSMs, reading the rows through the same table of row pointers.
+
 // the masked (row, point) pairs of nrows rows at m points, point-major, ascending rows inside a point (the order of
 // out_evals32), with the points as the evaluations' kernel argument; rows past KZG_BATCHED_ROW_MAX are evaluated in groups
 // of KZG_MAX_BATCH_OPEN pairs (their level scratch is large)
@@ -520,8 +530,7 @@ static void plan_pairs(PairPlan& pp, uint32_t nrows, uint64_t T, uint32_t m, con
                 pp.pa.pt[pp.npairs++] = (uint8_t)p;
             }
     }
-    const uint64_t nchunks = (T + 3) / 4;
-    pp.hrow = (nchunks + (nchunks >> 1) + 64) * 8;
+    pp.hrow = poly_level_words(T);
     pp.group = T <= KZG_BATCHED_ROW_MAX ? pp.npairs : std::min<uint32_t>(pp.npairs, KZG_MAX_BATCH_OPEN);
 }
 // every pair evaluated (rows read at rt.r[j]): the evaluations land in the record (MR_EVAL big-endian, MR_Y_M Montgomery),
@@ -569,85 +578,18 @@ static int multi_open_poly(kzg_ctx* ctx, Lane& A, const RowTab& rt, uint32_t nro
     *out_npairs = npairs;
     return KZG_OK;
 }
-// the MSMs over U_i and the end of a multi-row call: sets 0 .. k-1 are the rows (Montgomery, consecutive at coef), sets
-// k .. k+m-1 the quotients in A.qbuf.  Rows up to KZG_BATCHED_ROW_MAX share passes of as many sets as the sort's key carries
-// (at most 2^22 buckets); longer rows run one set per pass, alternating with a second lane when one is free.  Writes the k
-// commitments, the npairs evaluations of the record and the m proofs (each output unused when its count is 0).
-static int multi_msms_finish(kzg_ctx* ctx, LaneHold& H, uint32_t i, uint64_t T, const uint32_t* coef, uint32_t k,
-                             uint32_t m, uint32_t npairs, uint8_t* out_c48, uint8_t* out_evals32, uint8_t* out_p48) {
-    Lane& A = H.L();
-    hipStream_t s = A.stream;
-    const uint64_t words = T * 8;   // one row, in words
-    uint8_t* rec = A.brec.as<uint8_t>();
-    g1_xyzz_t* res = reinterpret_cast<g1_xyzz_t*>(rec + MR_RES);
-    const uint32_t* q = A.qbuf.as<uint32_t>();
-    const bool batched = T <= KZG_BATCHED_ROW_MAX;
-    const uint64_t offset = (uint64_t)i * ctx->T;
-    // sets per pass: what the sort's key carries (msm_sort_max_sets), at most 2^22 buckets; long rows one set per pass
-    int per = std::min(KZG_BATCH_PASS_SETS, msm_sort_max_sets(ctx->c));
-    while (per > 2 && (uint64_t)per * ctx->nbuckets > ((uint64_t)1 << 22)) per--;
-    if (!batched) per = 1;
-    const uint32_t sets = k + m, passes = (sets + per - 1) / per;   // sets k .. k + m - 1 are the quotients
-    Lane* B = (!batched && passes > 1) ? H.second() : nullptr;
-    if (B) {
-        HIPCHK(ctx, hipEventRecord(A.ev_coeffs, s));
-        HIPCHK(ctx, hipStreamWaitEvent(B->stream, A.ev_coeffs, 0));
-    }
-    for (uint32_t p = 0; p < passes; p++) {
-        Lane& L = (B && (p & 1)) ? *B : A;
-        const uint32_t a = p * per, b = std::min(sets, a + per);
-        const uint32_t nr = std::min(b, k) - std::min(a, k);   // rows in this pass
-        const uint32_t q0 = std::max(a, k) - k, nq = b > k ? b - std::max(a, k) : 0;   // quotients in this pass
-        int rc = nr ? msm_core(ctx, L, coef + (uint64_t)a * words, 1, T, offset, res + a, nq ? q + q0 * words : nullptr, 0,
-                               (int)nr, words, (int)nq)
-                    : msm_core(ctx, L, q + q0 * words, 0, T, offset, res + a, nullptr, 0, (int)nq, words);
-        if (rc) return rc;
-    }
-    if (B) {
-        HIPCHK(ctx, hipEventRecord(B->ev_done, B->stream));
-        HIPCHK(ctx, hipStreamWaitEvent(s, B->ev_done, 0));
-    }
-    if (!ctx->host_finish) {
-        Span sp(ctx, A, KZG_T_FINAL);
-        for (uint32_t p = 0; p + 1 < sets; p += 2)
-            launch_g1_compress_pair(s, res + p, res + p + 1, rec + MR_C48 + 48 * p, rec + MR_C48 + 48 * (p + 1));
-        if (sets & 1) launch_g1_compress(s, res + sets - 1, rec + MR_C48 + 48 * (sets - 1));
-    }
-    launch_publish(s, rec, A.bpin_dev, MR_COPY);   // stream-ordered ahead of finish()'s record and its sequence word
-    int rc = finish(ctx, A);
-    if (rc) return rc;
-    if (ctx->host_finish) {
-        uint8_t enc[MR_SETS * 48];
-        kzg_host::xyzz_batch_to_c48(reinterpret_cast<const uint32_t*>(A.bpin + MR_RES), sets, enc);
-        if (k) memcpy(out_c48, enc, 48 * (size_t)k);
-        if (m) memcpy(out_p48, enc + 48 * (size_t)k, 48 * (size_t)m);
-    } else {
-        if (k) memcpy(out_c48, A.bpin + MR_C48, 48 * (size_t)k);
-        if (m) memcpy(out_p48, A.bpin + MR_C48 + 48 * (size_t)k, 48 * (size_t)m);
-    }
-    if (npairs) memcpy(out_evals32, A.bpin + MR_EVAL, 32 * (size_t)npairs);
-    H.clean = true;
-    return KZG_OK;
-}
 int commit_open_multi_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* rows_dev, uint32_t k, uint64_t T,
                           int evaluation_form, uint32_t m, const uint8_t* points_be32, const uint32_t* masks,
                           const uint8_t* gammas_be32, uint8_t* out_c48, uint8_t* out_evals32, uint8_t* out_p48) {
     Lane& A = H.L();
     if (int rc = ensure_multi_record(ctx, A)) return rc;
-    const uint64_t words = T * 8;   // one row, in words
-    const uint32_t* coef = rows_dev;
-    if (evaluation_form && T > 1) {
-        HIPCHK(ctx, A.bcoef.ensure(k * T * 32));
-        for (uint32_t j = 0; j < k; j++) {
-            const uint32_t* c;
-            int rc = row_to_coeffs(ctx, A, rows_dev + j * words, T, 1, &c, A.bcoef.as<uint32_t>() + j * words);
-            if (rc) return rc;
-        }
-        coef = A.bcoef.as<uint32_t>();
-    }
+    const bool intt = evaluation_form && T > 1;
+    if (intt) HIPCHK(ctx, A.bcoef.ensure(k * T * 32));
+    const uint32_t* coef = intt ? A.bcoef.as<uint32_t>() : rows_dev;
+    if (int rc = rows_to_coeffs(ctx, A, rows_dev, k, T, evaluation_form, A.bcoef.as<uint32_t>())) return rc;
     RowTab rt;
     memset(&rt, 0, sizeof(rt));
-    for (uint32_t j = 0; j < k; j++) rt.r[j] = coef + j * words;
+    for (uint32_t j = 0; j < k; j++) rt.r[j] = coef + j * T * 8;
     uint32_t npairs = 0;
     if (int rc = multi_open_poly(ctx, A, rt, k, T, m, points_be32, masks, gammas_be32, &npairs)) return rc;
     return multi_msms_finish(ctx, H, i, T, coef, k, m, npairs, out_c48, out_evals32, out_p48);
@@ -659,12 +601,7 @@ int rows_commit_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const uint32_t* rows_
                     int evaluation_form, uint32_t* dst, uint8_t* out_c48) {
     Lane& A = H.L();
     if (int rc = ensure_multi_record(ctx, A)) return rc;
-    const uint64_t words = T * 8;
-    for (uint32_t j = 0; evaluation_form && T > 1 && j < k; j++) {
-        const uint32_t* c;
-        int rc = row_to_coeffs(ctx, A, rows_dev + j * words, T, 1, &c, dst + j * words);
-        if (rc) return rc;
-    }
+    if (int rc = rows_to_coeffs(ctx, A, rows_dev, k, T, evaluation_form, dst)) return rc;
     return multi_msms_finish(ctx, H, i, T, dst, k, 0, 0, out_c48, nullptr, nullptr);
 }
 // The open: the coefficient rows of committed sets (row j at rt.r[j], read in place) at m points -> the m proofs.
@@ -704,8 +641,7 @@ int rows_lincomb_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, ui
     if (int rc = ensure_multi_record(ctx, A)) return rc;
     uint8_t* rec = A.brec.as<uint8_t>();
     uint32_t* alpha_m = reinterpret_cast<uint32_t*>(rec + MR_ALPHA_M);
-    const uint64_t nchunks = (T + 3) / 4;
-    const uint64_t hrow = (nchunks + (nchunks >> 1) + 64) * 8;   // level scratch of one point's combination, words
+    const uint64_t hrow = poly_level_words(T);   // level scratch of one point's combination
     HIPCHK(ctx, A.hbuf.ensure(m * hrow * 4));
     HIPCHK(ctx, A.hnext.ensure(m * hrow * 4));
     HIPCHK(ctx, A.bcomb.ensure(m * T * 32));
@@ -737,8 +673,8 @@ int rows_shplonk_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, ui
     const uint32_t B = KZG_MAX_OPEN_POINTS;   // groups per batch
     static_assert(KZG_MAX_OPEN_POINTS <= POLY_MAX_POINTS && KZG_MAX_OPEN_POINTS <= POLY_MAX_ROWS,
                   "a batch is one launch of the combination, of each division and of the sum");
-    const uint64_t nchunks = (T + 3) / 4, words = T * 8;
-    const uint64_t hrow = (nchunks + (nchunks >> 1) + 64) * 8;   // level scratch of one group's division, words
+    const uint64_t words = T * 8;
+    const uint64_t hrow = poly_level_words(T);   // level scratch of one group's division
     HIPCHK(ctx, A.hbuf.ensure(B * hrow * 4));
     HIPCHK(ctx, A.hnext.ensure(B * hrow * 4));
     HIPCHK(ctx, A.bcomb.ensure(B * T * 32));
@@ -821,14 +757,13 @@ int rows_grand_product_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& 
     const int lg = ilog2_exact(T);
     uint32_t* tw = nullptr;
     if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
-    const uint64_t nchunks = (T + 3) / 4;
     HIPCHK(ctx, A.coeffA.ensure(T * 32));
     HIPCHK(ctx, A.coeffB.ensure(T * 32));
     HIPCHK(ctx, A.bcomb.ensure(T * 32));
     HIPCHK(ctx, A.qbuf.ensure(T * 32));
     HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
-    HIPCHK(ctx, A.hbuf.ensure((nchunks + (nchunks >> 1) + 64) * 32));
-    HIPCHK(ctx, A.hnext.ensure((nchunks + (nchunks >> 1) + 64) * 32));
+    HIPCHK(ctx, A.hbuf.ensure(poly_level_words(T) * 4));
+    HIPCHK(ctx, A.hnext.ensure(poly_level_words(T) * 4));
     uint32_t *ea = A.coeffA.as<uint32_t>(), *es = A.coeffB.as<uint32_t>();
     uint32_t *N = A.bcomb.as<uint32_t>(), *D = A.qbuf.as<uint32_t>();
     for (uint32_t j = 0; j < k; j++) {
@@ -858,14 +793,13 @@ int rows_shuffle_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs
     const int lg = ilog2_exact(T);
     uint32_t* tw = nullptr;
     if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
-    const uint64_t nchunks = (T + 3) / 4;
     HIPCHK(ctx, A.coeffA.ensure(T * 32));
     HIPCHK(ctx, A.coeffB.ensure(T * 32));
     HIPCHK(ctx, A.bcomb.ensure(T * 32));
     HIPCHK(ctx, A.qbuf.ensure(T * 32));
     HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
-    HIPCHK(ctx, A.hbuf.ensure((nchunks + (nchunks >> 1) + 64) * 32));
-    HIPCHK(ctx, A.hnext.ensure((nchunks + (nchunks >> 1) + 64) * 32));
+    HIPCHK(ctx, A.hbuf.ensure(poly_level_words(T) * 4));
+    HIPCHK(ctx, A.hnext.ensure(poly_level_words(T) * 4));
     if (sel) HIPCHK(ctx, A.qext.ensure(T * 32));
     uint32_t *e = A.coeffA.as<uint32_t>(), *acc = A.coeffB.as<uint32_t>(), *mid = A.ntt_mid.as<uint32_t>();
     uint32_t *N = A.bcomb.as<uint32_t>(), *D = A.qbuf.as<uint32_t>();
@@ -917,14 +851,13 @@ int rows_lookup_sum_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inp
     const int lg = ilog2_exact(T);
     uint32_t* tw = nullptr;
     if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
-    const uint64_t nchunks = (T + 3) / 4;
     HIPCHK(ctx, A.coeffA.ensure(T * 32));
     HIPCHK(ctx, A.coeffB.ensure(T * 32));
     HIPCHK(ctx, A.bcomb.ensure(T * 32));
     HIPCHK(ctx, A.qbuf.ensure(T * 32));
     HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
-    HIPCHK(ctx, A.hbuf.ensure((nchunks + (nchunks >> 1) + 64) * 32));
-    HIPCHK(ctx, A.hnext.ensure((nchunks + (nchunks >> 1) + 64) * 32));
+    HIPCHK(ctx, A.hbuf.ensure(poly_level_words(T) * 4));
+    HIPCHK(ctx, A.hnext.ensure(poly_level_words(T) * 4));
     uint32_t *e = A.coeffA.as<uint32_t>(), *acc = A.coeffB.as<uint32_t>();
     uint32_t *P = A.bcomb.as<uint32_t>(), *Q = A.qbuf.as<uint32_t>(), *mid = A.ntt_mid.as<uint32_t>();
     uint8_t* rec = A.brec.as<uint8_t>();

@@ -22,7 +22,7 @@ static int msm_host_common(kzg_ctx* ctx, const uint8_t* scalars_be32, uint64_t n
     HIPCHK(ctx, L.scal.ensure(n * 32 + 32));
     rc = upload_fr(ctx, L, scalars_be32, n, L.scal.as<uint32_t>(), 0);
     if (rc) return rc;
-    rc = msm_core(ctx, L, L.scal.as<uint32_t>(), 0, n, srs_offset, L.res());
+    rc = msm_core(ctx, L, ScalarSets::one(L.scal.as<uint32_t>(), 0), n, srs_offset, L.res());
     if (rc) return rc;
     if (partial) queue_pack(ctx, L);
     else queue_encode(ctx, L, true, false);
@@ -333,9 +333,8 @@ int kzg_eval(kzg_ctx* ctx, const uint8_t* coeffs_be32, uint64_t n, const uint8_t
     int rc = clear_flags(ctx, L);
     if (rc) return rc;
     HIPCHK(ctx, L.coeffA.ensure(n * 32));
-    const uint64_t nchunks = (n + 3) / 4;
-    HIPCHK(ctx, L.hbuf.ensure((nchunks + (nchunks >> 1) + 64) * 32));
-    HIPCHK(ctx, L.hnext.ensure((nchunks + (nchunks >> 1) + 64) * 32));
+    HIPCHK(ctx, L.hbuf.ensure(poly_level_words(n) * 4));
+    HIPCHK(ctx, L.hnext.ensure(poly_level_words(n) * 4));
     rc = upload_fr(ctx, L, coeffs_be32, n, L.coeffA.as<uint32_t>(), 1);
     if (rc) return rc;
     uint32_t* x_m = reinterpret_cast<uint32_t*>(L.tail + TB_ALPHA_M);
@@ -367,9 +366,8 @@ int kzg_ntt_eval(kzg_ctx* ctx, const uint8_t* vals_be32, uint64_t n, int inverse
     HIPCHK(ctx, L.coeffA.ensure(n * 32));
     HIPCHK(ctx, L.coeffB.ensure(n * 32));
     HIPCHK(ctx, L.ntt_mid.ensure(n * 48));
-    const uint64_t nchunks = (n + 3) / 4;
-    HIPCHK(ctx, L.hbuf.ensure((nchunks + (nchunks >> 1) + 64) * 32));
-    HIPCHK(ctx, L.hnext.ensure((nchunks + (nchunks >> 1) + 64) * 32));
+    HIPCHK(ctx, L.hbuf.ensure(poly_level_words(n) * 4));
+    HIPCHK(ctx, L.hnext.ensure(poly_level_words(n) * 4));
     rc = upload_fr(ctx, L, vals_be32, n, L.coeffA.as<uint32_t>(), 1);
     if (rc) return rc;
     const uint32_t* coeffs = L.coeffA.as<uint32_t>();
@@ -428,7 +426,7 @@ static int msm_resident_common(kzg_ctx* ctx, int slot, uint64_t n, uint64_t srs_
     prof_begin(ctx, L);
     rc = clear_flags(ctx, L);
     if (rc) return rc;
-    rc = msm_core(ctx, L, ctx->slot[slot].as<uint32_t>(), ctx->slot_mont[slot], n, srs_offset, L.res());
+    rc = msm_core(ctx, L, ScalarSets::one(ctx->slot[slot].as<uint32_t>(), ctx->slot_mont[slot]), n, srs_offset, L.res());
     if (rc) return rc;
     if (dev_out) launch_xyzz_pack(L.stream, L.res(), reinterpret_cast<uint32_t*>(dev_out), 1);
     else if (partial) queue_pack(ctx, L);
@@ -471,7 +469,7 @@ int kzg_msm_submit(kzg_ctx* ctx, int slot, uint64_t n, uint64_t srs_offset, int 
     }
     prof_begin(ctx, L);
     rc = clear_flags(ctx, L);
-    if (!rc) rc = msm_core(ctx, L, ctx->slot[slot].as<uint32_t>(), ctx->slot_mont[slot], n, srs_offset, L.res());
+    if (!rc) rc = msm_core(ctx, L, ScalarSets::one(ctx->slot[slot].as<uint32_t>(), ctx->slot_mont[slot]), n, srs_offset, L.res());
     if (!rc) {
         L.partial = partial != 0;
         if (partial) queue_pack(ctx, L);

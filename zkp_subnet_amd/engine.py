@@ -1366,6 +1366,17 @@ def ntt_plan_of(log_n: int, kernel: int = -1, tile_log: int = 0) -> Tuple[int, L
     return form, [(arr_s[p], arr_c[p]) for p in range(passes.value)]
 
 
+def msm_passes_of(c: int, long_rows: bool, k: int, m: int) -> List[Tuple[int, int, int, int, int]]:
+    """The MSM passes the library runs for a multi-row call's k row sets + m tail sets (the openings' quotients) at window c
+    (kzg_test_msm_passes; no context, no device): per pass (first row, rows, first tail set, tail sets, lane)."""
+    lib = _native.load()
+    out, passes = (ctypes.c_uint32 * (5 * max(1, k + m)))(), ctypes.c_int(0)
+    rc = lib.kzg_test_msm_passes(c, int(long_rows), k, m, out, ctypes.byref(passes))
+    if rc != _native.KZG_OK:
+        raise KzgError(rc, lib.kzg_last_error(None).decode(errors="replace"))
+    return [tuple(out[5 * p:5 * p + 5]) for p in range(passes.value)]
+
+
 class RowSet:
     """Rows committed by HipEngine.commit_rows and kept on the device: `handle`, worker `i`, `k` rows of `T` elements and
     their `commitments` (48-byte compressed G1 each).  release() frees the device copy; a `with` block releases on exit."""
