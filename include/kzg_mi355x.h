@@ -659,6 +659,44 @@ int kzg_rows_commit_shuffle(kzg_ctx* ctx, uint32_t n_input_handles, const uint64
                             const uint8_t theta_be32[32], const uint8_t gamma_be32[32],
                             const kzg_shuffle_opts* opts /* NULL: no selectors, plain layout */, uint8_t out_commitment48[48],
                             uint8_t out_closing32[32], uint64_t* out_handle);
+/* THE SORTED COLUMNS: a set built FROM sets, the second side of a shuffle whose first side is a group of columns and whose second
+ * side is the same tuples SORTED (memory consistency: (addr, time | value) ordered by address then time; sorted-column range
+ * checks), sorted and committed on the device from rows that are already resident.  The concatenated rows of the input_handles
+ * sets are the w = width columns c_0 .. c_{w-1}, 1 <= w <= KZG_MAX_BATCH_OPEN.  With w_T the T-th root of unity of
+ * evaluation_form = 1 rows (natural order), row t carries the tuple u_t = (c_0(w_T^t), .., c_{w-1}(w_T^t)).  Every entry is taken
+ * as its CANONICAL INTEGER in [0, r) -- not as its Montgomery representative, whose words do not order like the values.  The
+ * call creates a new set of w rows of the same worker and length whose evaluations are the tuples of rows [0, n), STABLY sorted:
+ * ascending, lexicographic on the first n_keys columns (1 <= n_keys <= w), column 0 most significant, ties by ascending source
+ * row t; the columns behind the keys travel with their row as payload.  The output is a function of the input bytes alone,
+ * whatever the device's schedule.  out_commitments48[c] equals kzg_rows_commit(i, w, sorted rows, T, 1, ..)[c] byte for byte,
+ * and *out_handle opens, evaluates, combines, releases, goes stale and counts against KZG_MAX_ROW_SETS (KZG_E_BUSY; KZG_E_NOMEM
+ * on a failed allocation, the lane's workspace included: w + n_keys + 1 T-element vectors and about a third of one more for the
+ * permutations and counts) like any other.
+ * opts (NULL: plain layout):
+ *   usable = 0 is the plain layout: n = T, all rows are sorted, tail_be32 must be NULL.  Otherwise n = usable, 1 <= usable <=
+ *   T - 1 and T - usable <= KZG_MAX_BLIND_ROWS: source rows t >= usable are never read into the sort (they may hold anything),
+ *   and output row usable + s of column c takes tail_be32[c * (T - usable) + s], column-major canonical scalars.  Unlike the
+ *   _zk builders there is NO closing row: all T - usable rows behind are the caller's.  The tail (at most 16 KB) rides in kernel
+ *   arguments; nothing row-sized crosses the host link in either direction.
+ * The cost follows the significant bytes of the keys, not 255 bits: a key byte that is the same in all n rows costs nothing
+ * (a column of 16-bit values costs 2 radix passes of the 32 a full-width column costs).
+ * Handle lists follow kzg_rows_open: 1 .. KZG_MAX_BATCH_OPEN handles, a handle may repeat (two equal columns), unknown /
+ * released / stale -> KZG_E_ARG; every set named must belong to one worker and one (power-of-two) T.  KZG_E_ARG with a message
+ * that names the cause: w = 0 or w > KZG_MAX_BATCH_OPEN; n_keys = 0 or n_keys > w; a concatenation that does not hold exactly w
+ * rows; T > 2^27; usable >= T; T - usable > KZG_MAX_BLIND_ROWS; a tail with usable = 0, or none with usable > 0; a tail scalar
+ * >= r.  The source sets are only read; a release or an SRS load racing the call follows the rules of kzg_rows_open.
+ * Thread-safe like every call; after any error the context keeps serving.
+ * OUT OF SCOPE: selectors (the caller compacts the enabled rows itself), descending order, and returning the permutation.
+ * SOUNDNESS: nothing here is a proof.  The sorted rows are prover data; the argument is the shuffle relation
+ * (kzg_rows_commit_shuffle over the inputs and this set, theta and gamma drawn AFTER these commitments are fixed) plus the
+ * caller's adjacent-row gate.  The library derives no challenge. */
+typedef struct kzg_sorted_opts {
+    uint64_t usable;           /* 0: plain layout (all T rows are sorted); else only rows [0, usable) */
+    const uint8_t* tail_be32;  /* width * (T - usable) * 32, column-major; NULL exactly when usable == 0 */
+} kzg_sorted_opts;
+int kzg_rows_commit_sorted(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                           uint32_t width, uint32_t n_keys, const kzg_sorted_opts* opts /* NULL: plain */,
+                           uint8_t* out_commitments48 /* width * 48 */, uint64_t* out_handle);
 /* THE QUOTIENT WITH LOOKUP SELECTORS: kzg_rows_commit_quotient_zk and kzg_rows_quotient_part for lookups that are enabled on
  * some rows only.  selectors->selector_rows holds L = lookup->n_lookups entries, each a row index into the call's concatenated
  * rows (the caller's fixed column q_l, the row that kzg_rows_commit_multiplicities_sel / _lookup_sum_sel read) or
@@ -1001,6 +1039,10 @@ int kzg_multi_rows_commit_shuffle(kzg_multi* mh, uint32_t i, uint32_t n_input_ha
                                   uint32_t n_shuffle_handles, const uint64_t* shuffle_handles, uint32_t n_groups, uint32_t width,
                                   const uint8_t theta_be32[32], const uint8_t gamma_be32[32], const kzg_shuffle_opts* opts,
                                   uint8_t out_commitment48[48], uint8_t out_closing32[32], uint64_t* out_handle);
+/* kzg_rows_commit_sorted on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_sorted(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                 uint32_t width, uint32_t n_keys, const kzg_sorted_opts* opts, uint8_t* out_commitments48,
+                                 uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

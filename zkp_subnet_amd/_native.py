@@ -74,6 +74,11 @@ class ShuffleOpts(ctypes.Structure):
                 ("shuffle_sel", ctypes.POINTER(_U32)), ("usable", _U64), ("tail_be32", _B)]
 
 
+class SortedOpts(ctypes.Structure):
+    """kzg_sorted_opts"""
+    _fields_ = [("usable", _U64), ("tail_be32", _B)]
+
+
 class QuotientLink(ctypes.Structure):
     """kzg_quotient_link"""
     _fields_ = [("prev_row", _U32), ("rot", ctypes.c_int32)]
@@ -116,6 +121,8 @@ SYMBOLS = {
                                            ctypes.POINTER(_U64)]),
     "kzg_rows_commit_shuffle": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _B, _B,
                                      ctypes.POINTER(ShuffleOpts), _B, _B, ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_sorted": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _U32, ctypes.POINTER(SortedOpts), _B,
+                                    ctypes.POINTER(_U64)]),
     "kzg_rows_commit_lookup_sum": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B, _B, _B, _B,
                                         ctypes.POINTER(_U64)]),
     "kzg_rows_commit_multiplicities": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _B,
@@ -217,6 +224,8 @@ SYMBOLS = {
                                                  _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_shuffle": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _B, _B,
                                            ctypes.POINTER(ShuffleOpts), _B, _B, ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_sorted": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _U32, ctypes.POINTER(SortedOpts), _B,
+                                          ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_lookup_sum": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B,
                                               _B, _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_multiplicities": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32,

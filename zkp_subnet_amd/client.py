@@ -613,6 +613,37 @@ class Client:
                                   sel_handles, input_sel, shuffle_sel, usable, tail)
         return self._with_closing(*self.engine.commit_shuffle(*args))
 
+    # ---- the sorted side of a shuffle: the columns of committed sets, sorted as tuples on the device
+    @_guard
+    def worker_commit_sorted(self, input_handles: Sequence[int], width: int, n_keys: Optional[int] = None,
+                             usable: Optional[int] = None, tail: Sequence[str] = ()):
+        """Extension: the `width` rows of the input_handles sets, read as the columns of one tuple per row, stably sorted on the
+        device and committed as a new set of `width` rows: ascending by the canonical integers of the first n_keys columns
+        (null: all), column 0 most significant, ties by source row; the other columns travel as payload.  usable = null sorts
+        all T rows; otherwise only rows [0, usable) are sorted (the source rows behind are not read) and row usable + s of
+        column c is tail[c * (T - usable) + s] -- there is no closing row.  Returns the handle and the `width` commitments.
+        Nothing here is a proof: the argument is worker_commit_shuffle over the inputs and this set plus the caller's
+        adjacent-row gate, with theta and gamma drawn after these commitments are fixed."""
+        what = "worker_commit_sorted"
+        hs = _handles(input_handles)
+        try:
+            width = int(width)
+            n_keys = width if n_keys is None else int(n_keys)
+        except (TypeError, ValueError) as e:
+            raise codec.CodecError(f"{what}: width and n_keys must be integers: {e!r}") from e
+        if not 1 <= width <= KZG_MAX_BATCH_OPEN or not 1 <= n_keys <= width:
+            raise codec.CodecError(f"{what}: width must be in [1, {KZG_MAX_BATCH_OPEN}] and n_keys in [1, width]")
+        if usable is None:
+            if tail:
+                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are sorted)")
+            tb = []
+        else:
+            usable, tb = self._blind(what, usable, tail)
+            if usable == 0:
+                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are sorted)")
+        rs = self.engine.commit_sorted(hs, width, n_keys, usable, tb)
+        return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments]}
+
     @staticmethod
     def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: Sequence[int], n_groups: int, width: int,
                                theta: str, gamma: str, coeff: str, active_row: Optional[int] = None,

@@ -466,6 +466,11 @@ int rows_lookup_sum_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inp
 int rows_multiplicities_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& table, uint32_t n_lookups,
                             uint32_t width, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_missing,
                             bool* out_overrun, const Blind* zk = nullptr, const SelPlan* sel = nullptr);
+// the `width` input rows, stably sorted as tuples by their first n_keys columns, into a new width-row set's buffer dst: their
+// commitments.  lay (null: all T rows are sorted): rows [0, usable) are sorted, rows usable + s of column c take
+// tail_be32[c * (T - usable) + s] (checked by the caller: 1 <= usable < T, T - usable <= KZG_MAX_BLIND_ROWS, canonical scalars)
+int rows_sorted_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t width, uint32_t n_keys, uint64_t T,
+                    uint32_t* dst, uint8_t* out_c48, const Blind* lay);
 // the quotient pieces of the constraints qp over the n_rows coefficient rows of rt into a new n_pieces-row set's buffer dst:
 // their commitments, and whether a coefficient of t at or above n_pieces T was not zero (the caller creates no set)
 int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t n_rows, uint64_t T, const QuotPlan& qp,

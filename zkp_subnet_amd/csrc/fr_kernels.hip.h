@@ -223,6 +223,24 @@ void launch_join_probe_rows(hipStream_t s, const uint32_t* tab, const uint32_t* 
 // canonical Montgomery elements, a cell whose sel[t] is zero is neither probed nor counted as missing
 void launch_join_probe_sel(hipStream_t s, const uint32_t* tab, const uint32_t* in, const uint32_t* sel, uint64_t T, uint64_t rows,
                            uint32_t w, const uint32_t* slots, uint32_t cap, uint32_t* cnt, uint64_t* missing, uint32_t* overrun);
+// ---- the stable sort of kzg_rows_commit_sorted (fr_sort.hip).  ev: the columns as evaluation vectors of T canonical Montgomery
+// elements, column c at + c * T * 8 words; rows [0, n) are sorted by the canonical integers of columns 0 .. n_keys - 1 (column 0
+// most significant), ties by ascending row.  keys: n_keys vectors of T elements; ws: fr_sort_ws_words(n, n_keys) words
+uint64_t fr_sort_ws_words(uint64_t n, uint32_t n_keys);
+uint32_t fr_sort_tile();   // positions per workgroup of the per-pass kernels
+// the keys' canonical integers into `keys` and the digit histograms of all 32 n_keys passes; returns the DEVICE address of the
+// passes' skip words (32 n_keys x u32, 1: one bin holds all n rows, the pass moves nothing)
+const uint32_t* launch_sort_front(hipStream_t s, const uint32_t* ev, uint64_t T, uint64_t n, uint32_t n_keys, uint32_t* keys,
+                                  uint32_t* ws);
+// the passes whose skip word (HOST copy) is 0; returns the final permutation (n x u32 inside ws; row perm[t] of the source is
+// row t of the result), or null when no pass ran: the identity
+const uint32_t* launch_sort_passes(hipStream_t s, const uint32_t* keys, uint64_t T, uint64_t n, uint32_t n_keys,
+                                   const uint32_t* skip_host, uint32_t* ws);
+// out[t] = col[perm[t]] for t < n (perm null: the identity); col and out must not overlap
+void launch_sort_gather(hipStream_t s, const uint32_t* col, const uint32_t* perm, uint32_t* out, uint64_t n);
+// v[usable + j] <- tail[j], j < n - usable <= BLIND_MAX_ROWS (no closing row, unlike launch_blind_tail); tail_be32: canonical
+// scalars as 32 big-endian HOST bytes each (a kernel argument), *bad raised when one is >= r
+void launch_sort_tail(hipStream_t s, uint32_t* v, uint64_t n, uint64_t usable, const uint8_t* tail_be32, uint32_t* bad);
 // ---- blinding rows (fr_blind.hip; the kzg_rows_commit_*_zk builders): rows [usable, n) of evaluation vectors of n Montgomery
 // elements, n - usable <= BLIND_MAX_ROWS (= KZG_MAX_BLIND_ROWS)
 #define BLIND_MAX_ROWS 32

@@ -982,6 +982,62 @@ int rows_multiplicities_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab&
     return KZG_OK;
 }
 
+// The sorted columns (kzg_rows_commit_sorted): a set built FROM sets, the second side of a shuffle whose first side is these
+// columns.  All w columns of a row travel together, so the w columns are transformed into w vectors of T in the lane's quotient
+// workspace; behind them lie the n_keys key vectors (the key columns' canonical integers: fr_sort.hip) and, in the staging
+// buffer, the sort's own workspace of about 0.3 vectors (two u32 permutations, a byte per row, the per-tile counts, 8 KB of
+// histograms per key column).  The front pass leaves one skip word per radix pass; their read-back (at most 2 KB, into the
+// lane's pinned page) is the call's one wait before the MSM: only the passes that move something are launched after it.
+// Each column is then gathered through the final permutation into one more vector (with the caller's tail behind `usable`),
+// whose inverse transform writes the column's coefficients straight into the new set's buffer `dst`; ONE MSM pass of w scalar
+// sets commits.  Workspace: w + n_keys + 1 vectors of T and the 0.3 above.
+int rows_sorted_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t width, uint32_t n_keys, uint64_t T,
+                    uint32_t* dst, uint8_t* out_c48, const Blind* lay) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const int lg = ilog2_exact(T);
+    uint32_t* tw = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
+    const uint64_t vw = T * 8;                        // one vector, in words
+    const uint64_t n = lay ? lay->usable : T;         // the rows that are sorted
+    const uint32_t passes = 32 * n_keys;
+    static_assert(32 * KZG_MAX_BATCH_OPEN * 4 <= 8192, "the skip words of every pass fit the lane's pinned page");
+    HIPCHK(ctx, A.qext.ensure(((size_t)width + n_keys) * T * 32));
+    HIPCHK(ctx, A.qstage.ensure(fr_sort_ws_words(n, n_keys) * 4));
+    HIPCHK(ctx, A.coeffA.ensure(T * 32));
+    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    uint32_t *ev = A.qext.as<uint32_t>(), *keys = ev + (uint64_t)width * vw, *mid = A.ntt_mid.as<uint32_t>();
+    uint32_t *ws = A.qstage.as<uint32_t>(), *out = A.coeffA.as<uint32_t>();
+    for (uint32_t c = 0; c < width; c++) {
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, inputs.r[c], ev + c * vw, lg, tw, nullptr, mid);
+    }
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        const uint32_t* skip_dev = launch_sort_front(A.stream, ev, T, n, n_keys, keys, ws);
+        HIPCHK(ctx, hipMemcpyAsync(A.bpin, skip_dev, (size_t)passes * 4, hipMemcpyDeviceToHost, A.stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(A.stream));
+    uint32_t skip[32 * KZG_MAX_BATCH_OPEN];
+    memcpy(skip, A.bpin, (size_t)passes * 4);
+    const uint32_t* perm;
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        perm = launch_sort_passes(A.stream, keys, T, n, n_keys, skip, ws);
+    }
+    for (uint32_t c = 0; c < width; c++) {
+        {
+            Span sp(ctx, A, KZG_T_POLY);
+            launch_sort_gather(A.stream, ev + c * vw, perm, out, n);
+            if (lay) launch_sort_tail(A.stream, out, T, n, lay->tail_be32 + 32 * (size_t)c * (T - n), A.flags());
+        }
+        const uint32_t* cf;
+        if (int rc = row_to_coeffs(ctx, A, out, T, 1, &cf, dst + c * vw)) return rc;
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return multi_msms_finish(ctx, H, i, T, dst, width, 0, 0, out_c48, nullptr, nullptr);
+}
+
 // the quotient's constants of one (T, E), shared by all lanes like the twiddles: built once under the ctx mutex
 static int ensure_quot_consts(kzg_ctx* ctx, Lane& L, int log_t, int ext_log, const uint32_t* tw_n, const uint32_t** qc) {
     std::lock_guard<std::mutex> lk(ctx->mu);

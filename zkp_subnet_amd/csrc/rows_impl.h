@@ -47,6 +47,9 @@ int rows_shuffle(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, cons
                  uint32_t n_shuffle_handles, const uint64_t* shuffle_handles, uint32_t n_groups, uint32_t width,
                  const uint8_t* theta_be32, const uint8_t* gamma_be32, const kzg_shuffle_opts* opts, uint8_t* out_commitment48,
                  uint8_t* out_closing32, uint64_t* out_handle);
+// opts: the usable layout and its tail as the public call takes them (null: all T rows are sorted)
+int rows_sorted(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t width,
+                uint32_t n_keys, const kzg_sorted_opts* opts, uint8_t* out_commitments48, uint64_t* out_handle);
 // zk: the blinding rows of the _zk call, the layout of the _sel call.  sc: the selectors of the _sel call
 int rows_lookup_sum(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
                     uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,

@@ -1064,6 +1064,55 @@ int rows_shuffle(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, cons
     return KZG_OK;
 }
 
+// kzg_rows_commit_sorted: the lookups of an open (one handle list), the reservation of a commit of `width` rows.  opts == NULL,
+// or usable == 0: all T rows are sorted
+int rows_sorted(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t width,
+                uint32_t n_keys, const kzg_sorted_opts* opts, uint8_t* out_commitments48, uint64_t* out_handle) {
+    if (!ctx || !input_handles || !out_commitments48 || !out_handle) return KZG_E_ARG;
+    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "sorted: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (width == 0 || width > KZG_MAX_BATCH_OPEN) return fail(ctx, KZG_E_ARG, "sorted: width must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (n_keys == 0 || n_keys > width) return fail(ctx, KZG_E_ARG, "sorted: n_keys must be in [1, width]");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs irefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab it;
+    uint32_t ki = 0, i = 0;
+    uint64_t T = 0;
+    if (int rc = rows_lookup(ctx, "sorted", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    if (ki != width) return fail(ctx, KZG_E_ARG, "sorted: the input sets must hold exactly width rows");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "sorted: the row length must be a power of two");
+    if (T > ((uint64_t)1 << 27))   // row indices and slot offsets are u32, 256 counts per tile of the passes
+        return fail(ctx, KZG_E_ARG, "sorted: the row length must be at most 2^27");
+    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
+    if (lay.usable) {
+        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "sorted: usable must be in [1, T - 1] (0: all T rows are sorted)");
+        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
+            return fail(ctx, KZG_E_ARG, "sorted: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
+        if (!lay.tail_be32) return fail(ctx, KZG_E_ARG, "sorted: tail_be32 must be given when usable > 0");
+        for (uint64_t j = 0; j < (uint64_t)width * (T - lay.usable); j++)
+            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
+                return fail(ctx, KZG_E_ARG, "sorted: tail scalars must be canonical (< r)");
+    } else if (lay.tail_be32) {
+        return fail(ctx, KZG_E_ARG, "sorted: tail_be32 must be null in the plain layout (usable = 0)");
+    }
+    if (int rc2 = rows_reserve(ctx, "sorted", pend, (size_t)width * T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    rc = rows_sorted_dev(ctx, H, i, it, width, n_keys, T, pend.buf.as<uint32_t>(), c48, lay.usable ? &lay : nullptr);
+    if (rc) return rc;
+    memcpy(out_commitments48, c48, 48 * (size_t)width);
+    *out_handle = rows_insert(ctx, pend, i, width, T);
+    return KZG_OK;
+}
+
 // The check of a _sel builder's selector arguments (SelCall, rows_impl.h): sel_index[l] is KZG_NO_SELECTOR or indexes the
 // concatenated rows of the sel_handles sets, which must be of the call's worker and row length.  The distinct rows named go
 // into sp (a row that serves several lookups is transformed once).
@@ -1641,6 +1690,10 @@ int kzg_rows_commit_shuffle(kzg_ctx* ctx, uint32_t n_input_handles, const uint64
                             uint8_t out_closing32[32], uint64_t* out_handle) {
     return rows_shuffle(ctx, UINT32_MAX, n_input_handles, input_handles, n_shuffle_handles, shuffle_handles, n_groups, width,
                         theta_be32, gamma_be32, opts, out_commitment48, out_closing32, out_handle);
+}
+int kzg_rows_commit_sorted(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t width, uint32_t n_keys,
+                           const kzg_sorted_opts* opts, uint8_t* out_commitments48, uint64_t* out_handle) {
+    return rows_sorted(ctx, UINT32_MAX, n_input_handles, input_handles, width, n_keys, opts, out_commitments48, out_handle);
 }
 int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_table_handles,
                                const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups, uint32_t width,

@@ -675,6 +675,47 @@ class HipEngine:
                                                     ctypes.byref(opts) if opts is not None else None, c, cl, ctypes.byref(h)))
         return RowSet(self, h.value, wi, 1, T, [c.raw]), cl.raw
 
+    # ---- a set built from sets: the columns of committed sets, stably sorted as tuples on the device (the second side of a
+    # shuffle whose first side is those columns)
+    def commit_sorted(self, input_sets: Sequence[object], width: int, n_keys: Optional[int] = None, usable: Optional[int] = None,
+                      tail: Sequence[bytes] = ()) -> "RowSet":
+        """kzg_rows_commit_sorted: the `width` concatenated rows of input_sets (RowSet objects or bare handles) are the columns
+        of one tuple per row; the new RowSet of `width` rows holds the tuples sorted ascending by the canonical integers of the
+        first n_keys columns (None: all of them), column 0 most significant, ties by source row.  usable = None sorts all T
+        rows; otherwise only rows [0, usable) are sorted and row usable + s of column c takes tail[c * (T - usable) + s] (32
+        bytes each, column-major; there is no closing row)."""
+        what = "commit_sorted"
+        ni, hi = self._handle_array(input_sets, what)
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: {why}")   # noqa: E731
+        if n_keys is None:
+            n_keys = width
+        if not isinstance(width, int) or not 1 <= width <= _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"width must be in [1, {_native.KZG_MAX_BATCH_OPEN}]")
+        if not isinstance(n_keys, int) or not 1 <= n_keys <= width:
+            raise bad("n_keys must be in [1, width]")
+        tail = [bytes(x) for x in (tail or [])]
+        src = next((x for x in input_sets if getattr(x, "T", None) is not None), None)
+        wi, T = (src.i, src.T) if src is not None else next(
+            (self._set_len[int(x)] for x in input_sets if not hasattr(x, "handle") and int(x) in self._set_len), (None, None))
+        opts = None
+        if usable is None:
+            if tail:
+                raise bad("a tail needs usable (None: all T rows are sorted)")
+        else:
+            if not isinstance(usable, int) or not 1 <= usable < 1 << 64:   # (the C call reads 0 as "plain layout": here None)
+                raise bad("usable must be in [1, T - 1] (None: all T rows are sorted)")
+            if any(len(x) != 32 for x in tail):
+                raise bad("the tail scalars must be of 32 bytes each")
+            if T is None:
+                raise bad("the row length of the sets is unknown to this engine (they were not committed through it)")
+            if usable < T and T - usable <= _native.KZG_MAX_BLIND_ROWS and len(tail) != width * (T - usable):
+                raise bad(f"the tail must hold exactly width * (T - usable) = {width * (T - usable)} scalars, not {len(tail)}")
+            opts = _native.SortedOpts(usable, b"".join(tail) if tail else None)
+        c, h = ctypes.create_string_buffer(48 * width), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_sorted(self._h, ni, hi, width, n_keys, ctypes.byref(opts) if opts is not None else None,
+                                                   c, ctypes.byref(h)))
+        return RowSet(self, h.value, wi, width, T, [c.raw[48 * p:48 * p + 48] for p in range(width)])
+
     # ---- a third set built from sets: the PLONK quotient (round 3), computed and committed on the device
     def commit_quotient(self, sets: Sequence[object], terms: Sequence[Tuple[bytes, Sequence[int]]], perm: Optional[dict] = None,
                         ext_log: int = 2, n_pieces: int = 3) -> "RowSet":
