@@ -56,6 +56,38 @@ int kzg_test_ntt_plan_of(int log_n, int kernel, int tile_log, int* out_S, int* o
 int kzg_test_ntt_run(kzg_ctx* ctx, uint8_t* inout_be32, int log_n, int inverse, int kernel, int passes, const int* S,
                      const int* logC);
 
+/* ---- the opening scan's plans (tests/test_poly_plans_cpu.py, tests/test_gpu_poly_plans.py, reference tests/poly_ref.py).
+ * y = f(alpha) and q = (f - y) / (X - alpha) over n coefficients run as a ladder of levels: level 0 folds chunks of 2^l0
+ * coefficients, every level above it chunks of 16 values of the level below, until at most scan_max values are left for one
+ * workgroup of scan_nt lanes; the suffix values then go back down level by level and the division kernel (strided, or with
+ * lds = 1 the LDS-staged one) writes q.  l0 = scan_max = scan_nt = lds = -1: the plan the library picks for n (l0 = 2 below 2^17,
+ * 3 below 2^18, else 4; 2048; 1024 lanes for a top level of more than 1024 values; the LDS-staged division from 2^21 on multiples of
+ * 1024, as KZG_POLY_NO_LDS / KZG_POLY_LDS_MIN_LOG move it).  Anything else: the CALLER'S plan, every parameter as given.
+ * A plan is checked against the kernels' preconditions first, KZG_E_ARG with the reason in kzg_last_error otherwise:
+ *   n >= 1; l0 in 2 .. 4; scan_max >= 1; scan_nt 256 or 1024; at most 14 levels; lds only with l0 = 4, n >= 1024 and
+ *   n % 1024 == 0; the stacked level arrays inside the scratch the library allocates for n (ceil(n / 4) * 3 / 2 + 64 elements)
+ * kzg_test_poly_plan_of: host only, no context.  out_K: the levels K; out_l, out_sq, out_n, out_off: room for 16 entries, K + 1
+ * are filled -- level k folds chunks of 2^l[k] of its n[k] values, each weighing alpha^(2^sq[k]), kept from entry off[k] of the
+ * scratch (level 0: the coefficients themselves; level K: what the scan takes, l = 0); out_scan_nt, out_lds: as run.
+ * kzg_test_poly_run: upload, the plan through the library's own launcher, download -- no SRS, no MSM.  The plan (and then the
+ * other arguments) are judged before the context is looked at.  f_be32: rows x n scalars, 32 big-endian bytes each; f_mont != 0:
+ * they are Montgomery residues already and are stored as they are.  alphas_be32: nalphas points.  out_y_be32: one evaluation of 32
+ * bytes per row (form 3: per pair).  out_q_words (forms 0, 4, 5): rows x n x 8 words, the buffer of q as the kernel left it
+ * over a fill pattern -- n - 1 coefficients and the zero of slot n - 1 per row.  rows * n <= 2^22.  form:
+ *   0 launch_poly_open, alpha as the first kernel's argument, q written         1 alpha read from memory, no q (rows = 1)
+ *   2 launch_poly_eval_rows: rows <= 16 rows side by side at one point
+ *   3 launch_poly_eval_pairs: pair t = row pair_row[t] at point pair_pt[t], npairs <= 64 point-major pairs over rows <= 16 rows that
+ *     the hook lays out apart from each other and in descending order, nalphas <= 4 points
+ *   4 launch_poly_open_points: rows <= 4 vectors, vector p at point p (nalphas = rows), canonical q
+ *   5 the same with vector p at point pts[p] and q left in Montgomery form (the chained division of
+ *     kzg_rows_commit_shplonk; always the strided kernel) */
+int kzg_test_poly_plan_of(uint64_t n, int l0, int64_t scan_max, int scan_nt, int lds, int* out_K, int* out_l, int* out_sq,
+                          uint64_t* out_n, uint64_t* out_off, int* out_scan_nt, int* out_lds);
+int kzg_test_poly_run(kzg_ctx* ctx, int form, int l0, int64_t scan_max, int scan_nt, int lds, const uint8_t* f_be32, uint64_t n,
+                      uint32_t rows, int f_mont, const uint8_t* pair_row, const uint8_t* pair_pt, uint32_t npairs,
+                      const uint8_t* pts, const uint8_t* alphas_be32, uint32_t nalphas, uint8_t* out_y_be32,
+                      uint32_t* out_q_words);
+
 /* ---- the MSM passes of a multi-row call (tests/test_msm_passes_cpu.py): how the library splits k row sets + m tail sets (what
  * the openings divide out, one scalar set per point) at window c (2^(c-1) buckets per set) into passes of its Pippenger pipeline; long_rows: rows past the
  * length up to which sets share a pass (2^18).  Host only, no context.  out5: 5 words per pass, room for k + m passes -- first

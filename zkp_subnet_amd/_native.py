@@ -295,6 +295,9 @@ SYMBOLS = {
     "kzg_test_ntt_plan_of": (_I, [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "kzg_test_ntt_run": (_I, [_P, _P, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "kzg_test_msm_passes": (_I, [_I, _I, _U32, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_I)]),
+    "kzg_test_poly_plan_of": (_I, [_U64, _I, ctypes.c_int64, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I),
+                                   ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "kzg_test_poly_run": (_I, [_P, _I, _I, ctypes.c_int64, _I, _I, _P, _U64, _U32, _I, _P, _P, _U32, _P, _P, _U32, _P, _P]),
 }
 
 _lib = None

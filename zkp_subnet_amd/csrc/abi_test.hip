@@ -479,6 +479,126 @@ int kzg_test_ntt_run(kzg_ctx* ctx, uint8_t* inout_be32, int log_n, int inverse, 
     return KZG_OK;
 }
 
+// ---- the opening scan's plans (tests/test_poly_plans_cpu.py, tests/test_gpu_poly_plans.py)
+// all four parameters -1: the plan the launchers pick themselves; otherwise the caller's, every parameter taken as given
+static const char* poly_plan_from(uint64_t n, int l0, int64_t scan_max, int scan_nt, int lds, PolyPlan* pl) {
+    if (!n) return "poly plan: no coefficients";
+    if (l0 == -1 && scan_max == -1 && scan_nt == -1 && lds == -1) *pl = poly_plan(n);
+    else {
+        if (lds != 0 && lds != 1) return "poly plan: lds must be 0 or 1";
+        *pl = poly_plan_levels(n, l0, scan_max < 0 ? 0 : (uint64_t)scan_max, scan_nt, lds != 0);
+    }
+    return poly_plan_invalid(*pl, n);
+}
+int kzg_test_poly_plan_of(uint64_t n, int l0, int64_t scan_max, int scan_nt, int lds, int* out_K, int* out_l, int* out_sq,
+                          uint64_t* out_n, uint64_t* out_off, int* out_scan_nt, int* out_lds) {
+    if (!out_K || !out_l || !out_sq || !out_n || !out_off || !out_scan_nt || !out_lds)
+        return fail(nullptr, KZG_E_ARG, "poly plan: null output");
+    PolyPlan pl;
+    if (const char* why = poly_plan_from(n, l0, scan_max, scan_nt, lds, &pl)) return fail(nullptr, KZG_E_ARG, why);
+    for (int k = 0; k <= pl.K; k++) {
+        out_l[k] = k < pl.K ? pl.l[k] : 0;    // (level K is the scan's: it folds nothing into a further level)
+        out_sq[k] = pl.sq[k];
+        out_n[k] = pl.n[k];
+        out_off[k] = pl.off[k];
+    }
+    *out_K = pl.K;
+    *out_scan_nt = pl.scan_nt;
+    *out_lds = pl.lds;
+    return KZG_OK;
+}
+#define KZG_TEST_POLY_MAX_N ((uint64_t)1 << 22)   // coefficients per plan-hook call, all rows together (as KZG_RAW_MAX_N)
+int kzg_test_poly_run(kzg_ctx* ctx, int form, int l0, int64_t scan_max, int scan_nt, int lds, const uint8_t* f_be32, uint64_t n,
+                      uint32_t rows, int f_mont, const uint8_t* pair_row, const uint8_t* pair_pt, uint32_t npairs,
+                      const uint8_t* pts, const uint8_t* alphas_be32, uint32_t nalphas, uint8_t* out_y_be32,
+                      uint32_t* out_q_words) {
+    // the plan is judged first, with no context and no device: nothing invalid reaches a kernel
+    PolyPlan pl;
+    if (const char* why = poly_plan_from(n, l0, scan_max, scan_nt, lds, &pl)) return fail(ctx, KZG_E_ARG, why);
+    if (form < 0 || form > 5) return fail(ctx, KZG_E_ARG, "poly run: form outside [0, 5]");
+    const bool quot = form == 0 || form >= 4, pairs = form == 3, points = form >= 4;
+    const uint32_t max_rows = form <= 1 ? 1 : points ? POLY_MAX_POINTS : POLY_MAX_ROWS;
+    if (!rows || rows > max_rows || n > KZG_TEST_POLY_MAX_N / rows)
+        return fail(ctx, KZG_E_ARG, "poly run: 1 row (forms 0, 1), up to 16 (2, 3) or 4 (4, 5), at most 2^22 coefficients in all");
+    if (!nalphas || nalphas > (form <= 2 ? 1u : (uint32_t)POLY_MAX_POINTS) || (form == 4 && nalphas != rows))
+        return fail(ctx, KZG_E_ARG, "poly run: one point (forms 0 - 2), up to 4 (3, 5), one per vector (4)");
+    if (pairs) {
+        if (!pair_row || !pair_pt || !npairs || npairs > POLY_MAX_PAIRS) return fail(ctx, KZG_E_ARG, "poly run: 1 .. 64 pairs");
+        for (uint32_t y = 0; y < npairs; y++)
+            if (pair_row[y] >= rows || pair_pt[y] >= nalphas || (y && pair_pt[y] < pair_pt[y - 1]))
+                return fail(ctx, KZG_E_ARG, "poly run: a pair names no row or no point, or the pairs are not point-major");
+    }
+    if (form == 5) {
+        if (!pts) return fail(ctx, KZG_E_ARG, "poly run: form 5 takes a map of points");
+        for (uint32_t p = 0; p < rows; p++)
+            if (pts[p] >= nalphas) return fail(ctx, KZG_E_ARG, "poly run: the map names no point");
+    }
+    if (!ctx || !f_be32 || !alphas_be32 || !out_y_be32 || (quot && !out_q_words))
+        return fail(ctx, KZG_E_ARG, "poly run: no context or no data");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;
+    Lane& L = H.L();
+    prof_begin(ctx, L);
+    int rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    hipStream_t s = L.stream;
+    const uint32_t nout = pairs ? npairs : rows;          // evaluations, and rows of level scratch
+    const uint64_t hrow = poly_level_words(n);
+    const uint64_t stride = pairs ? n + 3 : n;            // form 3: the rows lie apart and in descending order
+    HIPCHK(ctx, L.coeffA.ensure(rows * stride * 32));
+    HIPCHK(ctx, L.coeffB.ensure(rows * n * 32));
+    HIPCHK(ctx, L.hbuf.ensure(nout * hrow * 4));
+    HIPCHK(ctx, L.hnext.ensure(nout * hrow * 4));
+    HIPCHK(ctx, L.scal.ensure(POLY_MAX_POINTS * 32 + POLY_MAX_PAIRS * 64));
+    if (quot) HIPCHK(ctx, L.qbuf.ensure(rows * n * 32));
+    uint32_t* f = pairs ? L.coeffB.as<uint32_t>() : L.coeffA.as<uint32_t>();
+    uint32_t* alpha_m = L.scal.as<uint32_t>();                         // POLY_MAX_POINTS x 8 words
+    uint32_t* y_m = alpha_m + POLY_MAX_POINTS * 8;                     // POLY_MAX_PAIRS x 8 words
+    uint8_t* y_be = L.scal.as<uint8_t>() + POLY_MAX_POINTS * 32 + POLY_MAX_PAIRS * 32;
+    rc = upload_fr(ctx, L, f_be32, rows * n, f, f_mont ? 0 : 1);
+    if (rc) return rc;
+    // whatever a kernel fails to write must show: the quotient and the suffix values start from a pattern that is no result
+    HIPCHK(ctx, hipMemsetAsync(L.hnext.p, 0xa5, nout * hrow * 4, s));
+    if (quot) HIPCHK(ctx, hipMemsetAsync(L.qbuf.p, 0xa5, rows * n * 32, s));
+    uint32_t* h = L.hbuf.as<uint32_t>();
+    uint32_t* hn = L.hnext.as<uint32_t>();
+    uint32_t* q = L.qbuf.as<uint32_t>();
+    {
+        Span sp(ctx, L, KZG_T_POLY);
+        if (form == 0) launch_poly_open(s, pl, f, n, alpha_m, h, hn, y_m, q, alphas_be32, L.flags(), y_be);
+        else if (form == 1) {
+            launch_fr_from_host32(s, alphas_be32, alpha_m, 1, L.flags());
+            launch_poly_open(s, pl, f, n, alpha_m, h, hn, y_m, nullptr, nullptr, nullptr, y_be);
+        } else if (form == 2) launch_poly_eval_rows(s, pl, f, n, rows, alpha_m, h, hn, hrow, y_m, alphas_be32, L.flags(), y_be);
+        else if (form == 3) {
+            RowTab rt;
+            memset(&rt, 0, sizeof rt);
+            PairArg pa;
+            memset(&pa, 0, sizeof pa);
+            for (uint32_t j = 0; j < rows; j++) {
+                uint32_t* dst = L.coeffA.as<uint32_t>() + (uint64_t)(rows - 1 - j) * stride * 8;
+                HIPCHK(ctx, hipMemcpyAsync(dst, f + (uint64_t)j * n * 8, n * 32, hipMemcpyDeviceToDevice, s));
+                rt.r[j] = dst;
+            }
+            for (uint32_t p = 0; p < nalphas; p++) memcpy(pa.a[p].w, alphas_be32 + 32 * (size_t)p, 32);
+            memcpy(pa.row, pair_row, npairs);
+            memcpy(pa.pt, pair_pt, npairs);
+            launch_poly_eval_pairs(s, pl, rt, n, npairs, pa, alpha_m, h, hn, hrow, y_m, L.flags(), y_be);
+        } else {
+            for (uint32_t p = 0; p < nalphas; p++)
+                launch_fr_from_host32(s, alphas_be32 + 32 * (size_t)p, alpha_m + 8 * p, 1, L.flags());
+            launch_poly_open_points(s, pl, f, n, rows, alpha_m, h, hn, hrow, y_m, q, y_be, form == 5 ? pts : nullptr, form == 5);
+        }
+    }
+    rc = finish(ctx, L);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpy(out_y_be32, y_be, nout * 32, hipMemcpyDeviceToHost));
+    if (quot) HIPCHK(ctx, hipMemcpy(out_q_words, q, rows * n * 32, hipMemcpyDeviceToHost));
+    H.clean = true;
+    return KZG_OK;
+}
+
 // ---- the MSM passes of a multi-row call (tests/test_msm_passes_cpu.py)
 int kzg_test_msm_passes(int c, int long_rows, uint32_t k, uint32_t m, uint32_t* out5, int* out_passes) {
     if (!out5 || !out_passes) return fail(nullptr, KZG_E_ARG, "msm passes: null output");

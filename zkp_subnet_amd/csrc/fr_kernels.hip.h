@@ -48,11 +48,37 @@ inline uint64_t poly_level_words(uint64_t n) {
 void launch_poly_open(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t* alpha_mont, uint32_t* h,
                       uint32_t* hnext, uint32_t* y_mont, uint32_t* q_canon_or_null,
                       const uint8_t* alpha_be32_host = nullptr, uint32_t* bad = nullptr, uint8_t* y_be_or_null = nullptr);
+// The four opening launchers are "plan, then run" (fr_poly.hip).  A plan: the level-0 chunk 2^l0, the chunk 2^lup of every
+// level above it, the most values the single-workgroup scan is left with, the scan's lanes, whether the quotient is the
+// LDS-staged one, and the level table these give for n coefficients: level k folds chunks of 2^l[k] of its n[k] values
+// (level 0: the coefficients) into level k + 1, whose values weigh alpha^(2^sq[k + 1]) each and start at entry off[k + 1]
+// of h / hnext; level K goes to the scan.  poly_plan is what the launchers pick (l0 by length, 2048, 1024 lanes for a top
+// level of more than 1024 values, KZG_POLY_NO_LDS / KZG_POLY_LDS_MIN_LOG -- read nowhere else); poly_plan_levels a
+// caller's choice; poly_plan_invalid the kernels' preconditions (null: valid): l0 in 2 .. 4, scan_max >= 1, at most
+// POLY_MAX_LEVELS levels, 256 or 1024 lanes, the LDS quotient only with l0 = 4 on whole blocks of 1024 coefficients, and
+// the stacked levels inside poly_level_words(n).  The overloads that take a plan run it unchecked.
+#define POLY_MAX_LEVELS 14
+struct PolyPlan {
+    int l0, lup, scan_nt, lds;
+    uint64_t scan_max;
+    int K;
+    int l[16], sq[16];
+    uint64_t n[16], off[16];
+};
+PolyPlan poly_plan(uint64_t n);
+PolyPlan poly_plan_levels(uint64_t n, int l0, uint64_t scan_max, int scan_nt, bool lds);
+const char* poly_plan_invalid(const PolyPlan& pl, uint64_t n);
+void launch_poly_open(hipStream_t s, const PolyPlan& pl, const uint32_t* f_mont, uint64_t n, uint32_t* alpha_mont, uint32_t* h,
+                      uint32_t* hnext, uint32_t* y_mont, uint32_t* q_canon_or_null, const uint8_t* alpha_be32_host,
+                      uint32_t* bad, uint8_t* y_be_or_null);
 // the batched opening: y_r = f_r(alpha) for `rows` rows of n Montgomery coefficients at a stride of n elements, in the
 // launches of ONE evaluation (row index in the grid).  h, hnext: rows x h_row_words words of scratch each (h_row_words >=
 // 8 x the single-row size above); y_mont: rows x 8 words; y_be: rows x 32 bytes; alpha as in launch_poly_open
 void launch_poly_eval_rows(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t rows, uint32_t* alpha_mont,
                            uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont,
+                           const uint8_t* alpha_be32_host, uint32_t* bad, uint8_t* y_be);
+void launch_poly_eval_rows(hipStream_t s, const PolyPlan& pl, const uint32_t* f_mont, uint64_t n, uint32_t rows,
+                           uint32_t* alpha_mont, uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont,
                            const uint8_t* alpha_be32_host, uint32_t* bad, uint8_t* y_be);
 // out[t] = sum_j gamma^j rows[j * n + t] (Montgomery in and out), j < k <= 16; gamma as 32 big-endian HOST bytes (a kernel
 // argument), *bad raised when it is >= r
@@ -80,12 +106,18 @@ struct RowTab {
 void launch_poly_eval_pairs(hipStream_t s, const RowTab& rt, uint64_t n, uint32_t npairs, const PairArg& pa,
                             uint32_t* alpha_mont, uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont,
                             uint32_t* bad, uint8_t* y_be);
+void launch_poly_eval_pairs(hipStream_t s, const PolyPlan& pl, const RowTab& rt, uint64_t n, uint32_t npairs, const PairArg& pa,
+                            uint32_t* alpha_mont, uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont,
+                            uint32_t* bad, uint8_t* y_be);
 // m openings side by side: f_p = f_mont + p * n elements at the point alpha_mont + 8 p (Montgomery, already in memory):
 // y_p at y_mont + 8 p and the n-1 canonical quotient coefficients (slot n - 1 zero) at q_canon + p * n elements
 // (y_be given: y_p also as 32 big-endian bytes at y_be + 32 p)
 void launch_poly_open_points(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t m, const uint32_t* alpha_mont,
                              uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont, uint32_t* q_canon,
                              uint8_t* y_be = nullptr, const uint8_t* pts = nullptr, bool q_mont = false);
+void launch_poly_open_points(hipStream_t s, const PolyPlan& pl, const uint32_t* f_mont, uint64_t n, uint32_t m,
+                             const uint32_t* alpha_mont, uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont,
+                             uint32_t* q_canon, uint8_t* y_be, const uint8_t* pts, bool q_mont);
 // out[t] = (accumulate ? out[t] : 0) + sum_{g < cnt} rt.r[g][t] over n elements (Montgomery in and out, reduced below r):
 // the sum of the groups' final quotients of kzg_rows_commit_shplonk
 void launch_fr_sum_rows(hipStream_t s, const RowTab& rt, uint32_t cnt, uint64_t n, bool accumulate, uint32_t* out_mont);

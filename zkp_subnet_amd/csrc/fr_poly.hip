@@ -529,16 +529,58 @@ static bool quotient_lds(uint64_t n, int l0) {
     // (the level-0 fold gains nothing from LDS staging: 53 against 49 us, profiles/r04_ab_opening_lds_staging.log -- strided)
     return !no_lds && l0 == 4 && (n & 1023) == 0 && n >= ((uint64_t)1 << lds_min_log);
 }
-struct PolyLevels {
-    int K;
-    int l[16], sq[16];
-    uint64_t n[16], off[16];
-};
+// ---- the plan: everything the launchers below decide before they launch, as pure host arithmetic (fr_kernels.hip.h).
+// Level k folds chunks of 2^l[k] of its n[k] values into the n[k + 1] values of level k + 1, whose unit is alpha^(2^sq[k + 1]);
+// levels are added while the top one holds more than scan_max values (and the tables have room).
+PolyPlan poly_plan_levels(uint64_t n, int l0, uint64_t scan_max, int scan_nt, bool lds) {
+    PolyPlan pl;
+    memset(&pl, 0, sizeof pl);
+    pl.l0 = l0;
+    pl.lup = 4;   // log2 chunk of the levels above the first (4-long chunks + more levels measured no faster on short rows)
+    pl.scan_max = scan_max;
+    pl.scan_nt = scan_nt;
+    pl.lds = lds ? 1 : 0;
+    if (l0 < 2 || l0 > 4 || scan_max < 1) return pl;   // (no level table: poly_plan_invalid names the parameter)
+    const int lup = pl.lup;
+    int K = 1;
+    pl.l[0] = l0; pl.sq[0] = 0; pl.n[0] = n; pl.off[0] = 0;           // level 0 = f itself (offset unused)
+    pl.n[1] = (n + ((uint64_t)1 << l0) - 1) >> l0; pl.sq[1] = l0; pl.off[1] = 0;
+    while (pl.n[K] > scan_max && K < POLY_MAX_LEVELS) {
+        pl.l[K] = lup;
+        pl.n[K + 1] = (pl.n[K] + ((uint64_t)1 << lup) - 1) >> lup;
+        pl.sq[K + 1] = pl.sq[K] + lup;
+        pl.off[K + 1] = pl.off[K] + pl.n[K];
+        K++;
+    }
+    pl.K = K;
+    return pl;
+}
+PolyPlan poly_plan(uint64_t n) {
+    const int l0 = poly_lchunk(n);
+    PolyPlan pl = poly_plan_levels(n, l0, 2048, 256, quotient_lds(n, l0));
+    // the scan is one workgroup of dependent Fr products: 256 lanes (one wave per SIMD, <= 8 values each) run the chain
+    // at a lone wave's issue rate; 1024 lanes (four waves per SIMD) only when there is more than that to fold
+    if (pl.n[pl.K] > 1024) pl.scan_nt = 1024;
+    return pl;
+}
+const char* poly_plan_invalid(const PolyPlan& pl, uint64_t n) {
+    if (!n) return "poly plan: no coefficients";
+    if (pl.l0 < 2 || pl.l0 > 4) return "poly plan: level-0 chunk outside 2^2 .. 2^4";
+    if (pl.scan_max < 1) return "poly plan: the scan must be left at least one value";
+    if (pl.scan_nt != 256 && pl.scan_nt != 1024) return "poly plan: the scan runs 256 or 1024 lanes";
+    if (pl.K < 1 || pl.K > POLY_MAX_LEVELS || pl.n[pl.K] > pl.scan_max) return "poly plan: more than 14 levels";
+    // k_poly_quotient16_lds: 16 coefficients per lane, whole workgroups of 1024 coefficients, no bounds test of its own
+    if (pl.lds && (pl.l0 != 4 || (n & 1023) != 0 || n < 1024))
+        return "poly plan: the LDS-staged quotient needs 16-long chunks and whole blocks of 1024 coefficients";
+    if (pl.n[0] != n || (pl.off[pl.K] + pl.n[pl.K]) * 8 > poly_level_words(n))
+        return "poly plan: the stacked levels do not fit poly_level_words(n)";
+    return nullptr;
+}
 // pa given (the multi-point opening): the rows are pairs, each at its own point (k_poly_pairs_*); ARG then stands for
 // alpha_be32_host != null, the points coming from pa.a and the pairs' rows from the table *rt (f_mont unused)
 static void poly_up(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t rows, uint32_t* alpha_mont, uint32_t* h,
                     uint32_t* hnext, uint64_t h_rs, uint32_t* y_mont, const uint8_t* alpha_be32_host, uint32_t* bad,
-                    uint8_t* y_be_or_null, PolyLevels& lv, const PairArg* pa = nullptr, const RowTab* rt = nullptr) {
+                    uint8_t* y_be_or_null, const PolyPlan& lv, const PairArg* pa = nullptr, const RowTab* rt = nullptr) {
     RowTab none;
     memset(&none, 0, sizeof(none));
     const RowTab& tab = rt ? *rt : none;
@@ -546,15 +588,10 @@ static void poly_up(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t 
     memset(&arg, 0, sizeof(arg));
     if (alpha_be32_host) memcpy(arg.w, alpha_be32_host, 32);
     const uint64_t f_rs = rows > 1 ? n * 8 : 0;
-    const int l0 = poly_lchunk(n);
-    const int lup = 4;   // log2 chunk of the levels above the first (4-long chunks + more levels measured no faster on short rows)
-    int* lv_l = lv.l;
-    int* lv_sq = lv.sq;
-    uint64_t* lv_n = lv.n;
-    uint64_t* lv_off = lv.off;
-    int K = 1;
-    lv_l[0] = l0; lv_sq[0] = 0; lv_n[0] = n; lv_off[0] = 0;           // level 0 = f itself (offset unused)
-    lv_n[1] = (n + ((uint64_t)1 << l0) - 1) >> l0; lv_sq[1] = l0; lv_off[1] = 0;
+    const int l0 = lv.l0, lup = lv.lup, K = lv.K;
+    const int* lv_sq = lv.sq;
+    const uint64_t* lv_n = lv.n;
+    const uint64_t* lv_off = lv.off;
     if (pa) {
         if (alpha_be32_host)
             k_poly_pairs_eval<true><<<dim3(nblk(lv_n[1], 256), rows), 256, 0, s>>>(f_mont, n, l0, alpha_mont, 0, h, *pa, bad,
@@ -568,53 +605,51 @@ static void poly_up(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t 
     else
         k_poly_chunk_eval<false><<<dim3(nblk(lv_n[1], 256), rows), 256, 0, s>>>(f_mont, n, l0, alpha_mont, 0, h, arg, nullptr,
                                                                             nullptr, f_rs, h_rs);
-    while (lv_n[K] > 2048 && K < 14) {
-        lv_l[K] = lup;
-        lv_n[K + 1] = (lv_n[K] + ((uint64_t)1 << lup) - 1) >> lup;
-        lv_sq[K + 1] = lv_sq[K] + lup;
-        lv_off[K + 1] = lv_off[K] + lv_n[K];
+    for (int k = 1; k < K; k++) {
         if (pa)
-            k_poly_pairs_eval<false><<<dim3(nblk(lv_n[K + 1], 256), rows), 256, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lup,
-                                                                                    alpha_mont, lv_sq[K], h + 8 * lv_off[K + 1],
+            k_poly_pairs_eval<false><<<dim3(nblk(lv_n[k + 1], 256), rows), 256, 0, s>>>(h + 8 * lv_off[k], lv_n[k], lup,
+                                                                                    alpha_mont, lv_sq[k], h + 8 * lv_off[k + 1],
                                                                                     *pa, nullptr, h_rs, h_rs, tab);
         else
-            k_poly_chunk_eval<false><<<dim3(nblk(lv_n[K + 1], 256), rows), 256, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lup,
-                                                                                    alpha_mont, lv_sq[K], h + 8 * lv_off[K + 1],
+            k_poly_chunk_eval<false><<<dim3(nblk(lv_n[k + 1], 256), rows), 256, 0, s>>>(h + 8 * lv_off[k], lv_n[k], lup,
+                                                                                    alpha_mont, lv_sq[k], h + 8 * lv_off[k + 1],
                                                                                     arg, nullptr, nullptr, h_rs, h_rs);
-        K++;
     }
-    // the scan is one workgroup of dependent Fr products: 256 lanes (one wave per SIMD, <= 8 values each) run the chain
-    // at a lone wave's issue rate; 1024 lanes (four waves per SIMD) only when there is more than that to fold
     if (pa) {
-        if (lv_n[K] <= 1024)
+        if (lv.scan_nt == 256)
             k_poly_pairs_scan<256><<<rows, 256, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lv_sq[K], alpha_mont, hnext + 8 * lv_off[K],
                                                         y_mont, y_be_or_null, h_rs, *pa);
         else
             k_poly_pairs_scan<1024><<<rows, 1024, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lv_sq[K], alpha_mont,
                                                           hnext + 8 * lv_off[K], y_mont, y_be_or_null, h_rs, *pa);
-    } else if (lv_n[K] <= 1024)
+    } else if (lv.scan_nt == 256)
         k_poly_chunk_scan<256><<<rows, 256, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lv_sq[K], alpha_mont, hnext + 8 * lv_off[K],
                                                     y_mont, y_be_or_null, h_rs);
     else
         k_poly_chunk_scan<1024><<<rows, 1024, 0, s>>>(h + 8 * lv_off[K], lv_n[K], lv_sq[K], alpha_mont, hnext + 8 * lv_off[K],
                                                       y_mont, y_be_or_null, h_rs);
-    lv.K = K;
 }
+// (every launcher: the plan is the caller's to have checked with poly_plan_invalid; poly_plan's own always pass)
 void launch_poly_open(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t* alpha_mont, uint32_t* h,
+                      uint32_t* hnext, uint32_t* y_mont, uint32_t* q_canon_or_null, const uint8_t* alpha_be32_host,
+                      uint32_t* bad, uint8_t* y_be_or_null) {
+    launch_poly_open(s, poly_plan(n), f_mont, n, alpha_mont, h, hnext, y_mont, q_canon_or_null, alpha_be32_host, bad,
+                     y_be_or_null);
+}
+void launch_poly_open(hipStream_t s, const PolyPlan& lv, const uint32_t* f_mont, uint64_t n, uint32_t* alpha_mont, uint32_t* h,
                       uint32_t* hnext, uint32_t* y_mont, uint32_t* q_canon_or_null, const uint8_t* alpha_be32_host,
                       uint32_t* bad, uint8_t* y_be_or_null) {
     if (!n) {
         if (alpha_be32_host) launch_fr_from_host32(s, alpha_be32_host, alpha_mont, 1, bad);
         return;
     }
-    PolyLevels lv;
     poly_up(s, f_mont, n, 1, alpha_mont, h, hnext, 0, y_mont, alpha_be32_host, bad, y_be_or_null, lv);
     const int l0 = lv.l[0], K = lv.K;
     const int* lv_l = lv.l;
     const int* lv_sq = lv.sq;
     const uint64_t* lv_n = lv.n;
     const uint64_t* lv_off = lv.off;
-    const bool lds = quotient_lds(n, l0);
+    const bool lds = lv.lds != 0;
     for (int k = K - 1; k >= 1; k--)
         k_poly_chunk_expand<<<nblk(lv_n[k + 1], 256), 256, 0, s>>>(h + 8 * lv_off[k], lv_n[k], lv_l[k], alpha_mont,
                                                                    lv_sq[k], hnext + 8 * lv_off[k + 1],
@@ -627,15 +662,26 @@ void launch_poly_open(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_
 void launch_poly_eval_rows(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t rows, uint32_t* alpha_mont,
                            uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont,
                            const uint8_t* alpha_be32_host, uint32_t* bad, uint8_t* y_be) {
-    PolyLevels lv;
+    if (n && rows)
+        launch_poly_eval_rows(s, poly_plan(n), f_mont, n, rows, alpha_mont, h, hnext, h_row_words, y_mont, alpha_be32_host, bad,
+                              y_be);
+}
+void launch_poly_eval_rows(hipStream_t s, const PolyPlan& lv, const uint32_t* f_mont, uint64_t n, uint32_t rows,
+                           uint32_t* alpha_mont, uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont,
+                           const uint8_t* alpha_be32_host, uint32_t* bad, uint8_t* y_be) {
     if (n && rows) poly_up(s, f_mont, n, rows, alpha_mont, h, hnext, h_row_words, y_mont, alpha_be32_host, bad, y_be, lv);
 }
 
 void launch_poly_eval_pairs(hipStream_t s, const RowTab& rt, uint64_t n, uint32_t npairs, const PairArg& pa,
                             uint32_t* alpha_mont, uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont,
                             uint32_t* bad, uint8_t* y_be) {
+    if (n && npairs)
+        launch_poly_eval_pairs(s, poly_plan(n), rt, n, npairs, pa, alpha_mont, h, hnext, h_row_words, y_mont, bad, y_be);
+}
+void launch_poly_eval_pairs(hipStream_t s, const PolyPlan& lv, const RowTab& rt, uint64_t n, uint32_t npairs, const PairArg& pa,
+                            uint32_t* alpha_mont, uint32_t* h, uint32_t* hnext, uint64_t h_row_words, uint32_t* y_mont,
+                            uint32_t* bad, uint8_t* y_be) {
     static const uint8_t ARG_MARK[32] = {};   // (non-null: the first kernel converts the points of pa.a)
-    PolyLevels lv;
     if (n && npairs)
         poly_up(s, nullptr, n, npairs, alpha_mont, h, hnext, h_row_words, y_mont, ARG_MARK, bad, y_be, lv, &pa, &rt);
 }
@@ -646,6 +692,12 @@ void launch_poly_eval_pairs(hipStream_t s, const RowTab& rt, uint64_t n, uint32_
 void launch_poly_open_points(hipStream_t s, const uint32_t* f_mont, uint64_t n, uint32_t m, const uint32_t* alpha_mont,
                              uint32_t* h, uint32_t* hnext, uint64_t h_rs, uint32_t* y_mont, uint32_t* q_canon,
                              uint8_t* y_be, const uint8_t* pts, bool q_mont) {
+    if (!n || !m || m > POLY_MAX_POINTS) return;
+    launch_poly_open_points(s, poly_plan(n), f_mont, n, m, alpha_mont, h, hnext, h_rs, y_mont, q_canon, y_be, pts, q_mont);
+}
+void launch_poly_open_points(hipStream_t s, const PolyPlan& lv, const uint32_t* f_mont, uint64_t n, uint32_t m,
+                             const uint32_t* alpha_mont, uint32_t* h, uint32_t* hnext, uint64_t h_rs, uint32_t* y_mont,
+                             uint32_t* q_canon, uint8_t* y_be, const uint8_t* pts, bool q_mont) {
     // m <= POLY_MAX_POINTS is the caller's to keep (the C-ABI refuses more points; rows_shplonk_dev batches its groups by
     // KZG_MAX_OPEN_POINTS, checked at compile time); the test only keeps a wrong caller from writing past PairArg
     if (!n || !m || m > POLY_MAX_POINTS) return;
@@ -655,7 +707,6 @@ void launch_poly_open_points(hipStream_t s, const uint32_t* f_mont, uint64_t n, 
         pa.row[p] = (uint8_t)p;
         pa.pt[p] = pts ? pts[p] : (uint8_t)p;
     }
-    PolyLevels lv;
     uint32_t* am = const_cast<uint32_t*>(alpha_mont);   // (read only: no point is converted on this path)
     poly_up(s, f_mont, n, m, am, h, hnext, h_rs, y_mont, nullptr, nullptr, y_be, lv, &pa);
     const int l0 = lv.l[0], K = lv.K;
@@ -666,7 +717,7 @@ void launch_poly_open_points(hipStream_t s, const uint32_t* f_mont, uint64_t n, 
     if (q_mont) {
         k_poly_pairs_quotient<true><<<dim3(nblk(lv.n[1], 256), m), 256, 0, s>>>(f_mont, n, l0, alpha_mont, hnext, q_canon, n * 8,
                                                                                 h_rs, pa);
-    } else if (quotient_lds(n, l0)) {
+    } else if (lv.lds) {
         for (uint32_t p = 0; p < m; p++)
             k_poly_quotient16_lds<<<(uint32_t)(n >> 10), 64, 0, s>>>(f_mont + p * n * 8, n, alpha_mont + 8 * pa.pt[p],
                                                                     hnext + p * h_rs, q_canon + p * n * 8);

@@ -1394,6 +1394,25 @@ class HipEngine:
                                              arr_s, arr_c))
         return buf.raw
 
+    def test_poly_run(self, form: int, f_be32: bytes, n: int, alphas_be32: bytes, plan: Sequence[int] = (-1, -1, -1, -1),
+                      rows: int = 1, pairs: Sequence[Tuple[int, int]] = (), pts: Optional[Sequence[int]] = None,
+                      f_mont: bool = False) -> Tuple[bytes, bytes]:
+        """The opening scan of rows x n coefficients by the CALLER'S plan (kzg_test_poly_run; no SRS, no MSM): plan = (l0,
+        scan_max, scan_nt, lds), all -1 for the library's own.  form 0 open (alpha as kernel argument), 1 evaluate (alpha from
+        memory), 2 rows side by side, 3 (row, point) pairs, 4 vectors at their points, 5 the chained division (vector p at point
+        pts[p], Montgomery quotients).  Returns (the evaluations, 32 bytes each; the raw quotient buffer of rows x n x 8
+        little-endian words, empty for forms 1 - 3).  KzgError(KZG_E_ARG) for a plan the kernels do not admit."""
+        l0, scan_max, scan_nt, lds = plan
+        nout = len(pairs) if form == 3 else rows
+        y = ctypes.create_string_buffer(32 * max(1, nout))
+        quot = form in (0, 4, 5)
+        q = (ctypes.c_uint32 * (8 * rows * n))() if quot else None
+        pr, pp = bytes(r for r, _ in pairs), bytes(p for _, p in pairs)
+        self._chk(self._lib.kzg_test_poly_run(self._h, form, l0, scan_max, scan_nt, lds, f_be32, n, rows, int(f_mont), pr, pp,
+                                              len(pairs), bytes(pts) if pts is not None else None, alphas_be32,
+                                              len(alphas_be32) // 32, ctypes.addressof(y), ctypes.addressof(q) if quot else None))
+        return y.raw[:32 * nout], bytes(q) if quot else b""
+
 
 def ntt_plan_of(log_n: int, kernel: int = -1, tile_log: int = 0) -> Tuple[int, List[Tuple[int, int]]]:
     """The pass plan the library runs for 2^log_n elements (kzg_test_ntt_plan_of; no context, no device): (form, [(S, logC)
@@ -1405,6 +1424,22 @@ def ntt_plan_of(log_n: int, kernel: int = -1, tile_log: int = 0) -> Tuple[int, L
     if form < 0:
         raise KzgError(form, lib.kzg_last_error(None).decode(errors="replace"))
     return form, [(arr_s[p], arr_c[p]) for p in range(passes.value)]
+
+
+def poly_plan_of(n: int, l0: int = -1, scan_max: int = -1, scan_nt: int = -1, lds: int = -1) -> Dict[str, object]:
+    """The level plan of the opening scan for n coefficients (kzg_test_poly_plan_of; no context, no device): with every
+    parameter -1 the plan the library runs, otherwise the caller's.  {"K", "l", "sq", "n", "off" (K + 1 entries each), "scan_nt",
+    "lds"}; KzgError(KZG_E_ARG) with the reason for a plan outside the kernels' preconditions."""
+    lib = _native.load()
+    K, nt, ld = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    al, asq, an, aoff = (ctypes.c_int * 16)(), (ctypes.c_int * 16)(), (ctypes.c_uint64 * 16)(), (ctypes.c_uint64 * 16)()
+    rc = lib.kzg_test_poly_plan_of(n, l0, scan_max, scan_nt, lds, ctypes.byref(K), al, asq, an, aoff, ctypes.byref(nt),
+                                   ctypes.byref(ld))
+    if rc != _native.KZG_OK:
+        raise KzgError(rc, lib.kzg_last_error(None).decode(errors="replace"))
+    k = K.value + 1
+    return {"K": K.value, "l": list(al[:k]), "sq": list(asq[:k]), "n": list(an[:k]), "off": list(aoff[:k]), "scan_nt": nt.value,
+            "lds": ld.value}
 
 
 def msm_passes_of(c: int, long_rows: bool, k: int, m: int) -> List[Tuple[int, int, int, int, int]]:
