@@ -697,6 +697,59 @@ typedef struct kzg_sorted_opts {
 int kzg_rows_commit_sorted(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
                            uint32_t width, uint32_t n_keys, const kzg_sorted_opts* opts /* NULL: plain */,
                            uint8_t* out_commitments48 /* width * 48 */, uint64_t* out_handle);
+/* THE DERIVED COLUMNS: a set built FROM sets, the two helper columns of range checks and zero tests, each a pure function of ONE
+ * column that is already resident.  The concatenated rows of the input_handles sets (as in kzg_rows_open) are the source
+ * columns; with w_T the T-th root of unity of evaluation_form = 1 rows, cell t of a column is its value at w_T^t, taken as its
+ * CANONICAL INTEGER x_t in [0, r) -- not as its Montgomery representative.  Each of the n_ops ops names one source row and
+ * yields `count` output rows; the outputs follow the order of ops, and inside one op the order given here:
+ *   KZG_DERIVE_INV0 (bits = 0; count 1 or 2): inv0_t = x_t^-1 in the field, or 0 where x_t = 0 (the IsZero / "a != b" gadget);
+ *     with count = 2 a second row follows, 1 where x_t = 0 and 0 elsewhere (the bit 1 - x inv0).  out_counts[op] is the number
+ *     of zero cells among the rows read.  A zero is never an error.  All INV0 ops of one call share ONE batched inversion
+ *     over n_inv * T elements: one field inversion per call, three to four products per cell.
+ *   KZG_DERIVE_LIMBS (bits = b in [1, 32]; count = L in [1, KZG_MAX_BATCH_OPEN], b * L <= 256): limb_l,t = (x_t >> (b l)) & (2^b - 1)
+ *     for l < L, least significant first: the rows a 2^b-entry table is looked up with (kzg_rows_commit_multiplicities ->
+ *     kzg_rows_commit_lookup_sum) and the gate x = sum_l 2^(b l) limb_l ties back to x (kzg_rows_commit_quotient).
+ *     out_counts[op] is the number of cells read with x_t >= 2^(b L) -- the part `missing` plays in the multiplicities call;
+ *     the low limbs are still written for such cells and the call still succeeds.
+ * n_out = sum of the counts, 1 <= n_out <= KZG_MAX_BATCH_OPEN.  The call creates a new set of n_out rows of the same worker and
+ * length.  out_commitments48[c] equals kzg_rows_commit(i, n_out, derived rows, T, 1, ..)[c] byte for byte, and *out_handle
+ * opens, evaluates, combines, releases, goes stale and counts against KZG_MAX_ROW_SETS (KZG_E_BUSY; KZG_E_NOMEM on a failed
+ * allocation, the lane's workspace included: one T-element vector per DISTINCT source row, which is transformed once however
+ * many ops name it, one per INV0 op, and max(number of INV0 ops, largest count) more) like any other.
+ * opts (NULL: plain layout) follows kzg_sorted_opts:
+ *   usable = 0 is the plain layout: all T rows are read, tail_be32 must be NULL.  Otherwise 1 <= usable <= T - 1 and T - usable
+ *   <= KZG_MAX_BLIND_ROWS: source rows t >= usable are never read or counted (they may hold anything), and output row usable + s
+ *   of output column c takes tail_be32[c * (T - usable) + s], column-major canonical scalars over the n_out columns.  There is
+ *   NO closing row.  The tail rides in kernel arguments; nothing row-sized crosses the host link in either direction.
+ * Handle lists follow kzg_rows_open: 1 .. KZG_MAX_BATCH_OPEN handles, a handle may repeat, unknown / released / stale ->
+ * KZG_E_ARG; every set named must belong to one worker and one (power-of-two) T.  KZG_E_ARG with a message that begins
+ * "derived:" and names the cause: n_ops = 0; n_out = 0 or n_out > KZG_MAX_BATCH_OPEN; an unknown kind; a row at or beyond the
+ * concatenation; bits outside [1, 32], count outside [1, KZG_MAX_BATCH_OPEN] or b * L > 256 on LIMBS; bits != 0 or count
+ * outside {1, 2} on INV0; usable >= T; T - usable > KZG_MAX_BLIND_ROWS; a tail with usable = 0, or none with usable > 0; a tail
+ * scalar >= r.  The source sets are only read; a release or an SRS load racing the call follows the rules of kzg_rows_open.
+ * Thread-safe like every call; after any error the context keeps serving.
+ * OUT OF SCOPE: per-row selectors; signed limbs or limbs in a base that is no power of two; halo2's running-sum decomposition
+ * along the rows; general expression rows (sum_u c_u prod rows[rot] committed as a column).
+ * SOUNDNESS: nothing here is a proof.  The derived rows are prover data; the argument is the caller's gates (x inv0 = 1 - bit
+ * and x bit = 0; x = sum_l 2^(b l) limb_l) and the lookup of the limbs, with every challenge drawn AFTER these commitments are
+ * fixed.  The library derives no challenge and draws no randomness: the tail must be fresh per proof. */
+#define KZG_DERIVE_INV0  1
+#define KZG_DERIVE_LIMBS 2
+typedef struct kzg_derive_op {
+    uint32_t kind;   /* KZG_DERIVE_* */
+    uint32_t row;    /* source row, index into the concatenated rows of input_handles */
+    uint32_t bits;   /* LIMBS: b in [1, 32]; INV0: must be 0 */
+    uint32_t count;  /* output rows of this op -- INV0: 1 (inv0) or 2 (inv0, then the is-zero bit);
+                        LIMBS: L in [1, KZG_MAX_BATCH_OPEN], b * L <= 256 */
+} kzg_derive_op;
+typedef struct kzg_derive_opts {
+    uint64_t usable;           /* 0: plain layout (all T rows are read); else only rows [0, usable) */
+    const uint8_t* tail_be32;  /* n_out * (T - usable) * 32, column-major; NULL exactly when usable == 0 */
+} kzg_derive_opts;
+int kzg_rows_commit_derived(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                            uint32_t n_ops, const kzg_derive_op* ops, const kzg_derive_opts* opts /* NULL: plain */,
+                            uint8_t* out_commitments48 /* n_out * 48 */, uint64_t* out_counts /* n_ops */,
+                            uint64_t* out_handle);
 /* THE QUOTIENT WITH LOOKUP SELECTORS: kzg_rows_commit_quotient_zk and kzg_rows_quotient_part for lookups that are enabled on
  * some rows only.  selectors->selector_rows holds L = lookup->n_lookups entries, each a row index into the call's concatenated
  * rows (the caller's fixed column q_l, the row that kzg_rows_commit_multiplicities_sel / _lookup_sum_sel read) or
@@ -1043,6 +1096,10 @@ int kzg_multi_rows_commit_shuffle(kzg_multi* mh, uint32_t i, uint32_t n_input_ha
 int kzg_multi_rows_commit_sorted(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                  uint32_t width, uint32_t n_keys, const kzg_sorted_opts* opts, uint8_t* out_commitments48,
                                  uint64_t* out_handle);
+/* kzg_rows_commit_derived on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_derived(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                  uint32_t n_ops, const kzg_derive_op* ops, const kzg_derive_opts* opts,
+                                  uint8_t* out_commitments48, uint64_t* out_counts, uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

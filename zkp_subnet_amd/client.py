@@ -644,6 +644,48 @@ class Client:
         rs = self.engine.commit_sorted(hs, width, n_keys, usable, tb)
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments]}
 
+    # ---- the helper columns of zero tests and range checks: functions of one resident column, built on the device
+    @_guard
+    def worker_commit_derived(self, input_handles: Sequence[int], ops: Sequence[Sequence], usable: Optional[int] = None,
+                              tail: Sequence[str] = ()):
+        """Extension: helper columns of the rows of the input_handles sets, computed and committed on the device as one new set.
+        ops: ["inv0", row] gives the row 1 / x with 0 where x = 0 (the IsZero gadget), ["inv0", row, true] also the bit row
+        behind it (1 where x = 0); ["limbs", row, bits, count] the `count` limbs of `bits` bits of x's canonical integer, least
+        significant first (range checks: the limbs go into worker_commit_multiplicities against a 2^bits table).  usable = null
+        reads all T rows; otherwise only rows [0, usable) are read and row usable + s of output column c is
+        tail[c * (T - usable) + s] -- there is no closing row.  Returns the handle, the commitments of all output rows in the
+        order of ops, and one count per op: the zero cells of an inv0 op, the cells at or above 2^(bits * count) of a limbs op
+        (0 when the range check can hold).  Nothing here is a proof: the argument is the caller's gates and lookups over these
+        rows, with every challenge drawn after these commitments are fixed."""
+        what = "worker_commit_derived"
+        hs = _handles(input_handles)
+        try:
+            recs = []
+            for op in ops:
+                name = op[0]
+                if name == "inv0" and len(op) in (2, 3):
+                    recs.append(("inv0", int(op[1]), bool(op[2])) if len(op) == 3 else ("inv0", int(op[1])))
+                elif name == "limbs" and len(op) == 4:
+                    recs.append(("limbs", int(op[1]), int(op[2]), int(op[3])))
+                else:
+                    raise ValueError(f"unknown op {op!r}")
+        except (TypeError, ValueError, IndexError, KeyError) as e:
+            raise codec.CodecError(f'{what}: ops must be a list of ["inv0", row], ["inv0", row, with_bit] or '
+                                   f'["limbs", row, bits, count]: {e!r}') from e
+        if not recs:
+            raise codec.CodecError(f"{what}: ops must not be empty")
+        if usable is None:
+            if tail:
+                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
+            tb = []
+        else:
+            usable, tb = self._blind(what, usable, tail)
+            if usable == 0:
+                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        rs, counts = self.engine.commit_derived(hs, recs, usable, tb)
+        return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
+                "counts": [int(v) for v in counts]}
+
     @staticmethod
     def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: Sequence[int], n_groups: int, width: int,
                                theta: str, gamma: str, coeff: str, active_row: Optional[int] = None,

@@ -6,6 +6,7 @@
 //   srs.hip       setup loaders (memory, file, per-device slices), synthetic SRS, window tables, read-back
 //   pipeline.hip  the host-side sequencing of the kernels: one MSM (msm_core), a row's commit / open (commit_open_dev)
 //   serve.hip     the serving entry points: commit / open / msm / ntt / eval, resident slots, tickets, sums
+//   fr_derive.hip the kernels of kzg_rows_commit_derived: inverse-or-zero around the batched inversion, limb decomposition
 //   comm.hip      the library's own RCCL collective (kzg_comm_*, kzg_msm_sharded, the stream-chained pair)
 //   abi_test.hip  unit-op test hooks (include/kzg_mi355x_test.h)
 // No CPU arithmetic fallback exists anywhere here: if HIP fails, the call fails.
@@ -471,6 +472,11 @@ int rows_multiplicities_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab&
 // tail_be32[c * (T - usable) + s] (checked by the caller: 1 <= usable < T, T - usable <= KZG_MAX_BLIND_ROWS, canonical scalars)
 int rows_sorted_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t width, uint32_t n_keys, uint64_t T,
                     uint32_t* dst, uint8_t* out_c48, const Blind* lay);
+// the n_out helper rows of the n_ops ops (checked by the caller: kinds, rows inside `inputs`, bits and counts in range, the
+// counts summing to n_out) into a new n_out-row set's buffer dst: their commitments and one count per op (zero cells of an
+// inv0 op, cells at or above 2^(bits count) of a limbs op).  lay: as for rows_sorted_dev, the tail column-major over n_out
+int rows_derived_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_ops, const kzg_derive_op* ops,
+                     uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_counts, const Blind* lay);
 // the quotient pieces of the constraints qp over the n_rows coefficient rows of rt into a new n_pieces-row set's buffer dst:
 // their commitments, and whether a coefficient of t at or above n_pieces T was not zero (the caller creates no set)
 int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t n_rows, uint64_t T, const QuotPlan& qp,

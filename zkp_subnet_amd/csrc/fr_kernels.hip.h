@@ -273,6 +273,20 @@ void launch_sort_gather(hipStream_t s, const uint32_t* col, const uint32_t* perm
 // v[usable + j] <- tail[j], j < n - usable <= BLIND_MAX_ROWS (no closing row, unlike launch_blind_tail); tail_be32: canonical
 // scalars as 32 big-endian HOST bytes each (a kernel argument), *bad raised when one is >= r
 void launch_sort_tail(hipStream_t s, uint32_t* v, uint64_t n, uint64_t usable, const uint8_t* tail_be32, uint32_t* bad);
+// ---- the helper columns of kzg_rows_commit_derived (fr_derive.hip).  A source is an evaluation vector of T canonical Montgomery
+// elements of which rows [0, n) are read; counts are u64 words in device memory that the launches add to
+// the words of one op's zero mask (1 bit per cell, 32 cells per u32 word)
+uint32_t inv0_mask_words(uint64_t T);
+// the n_inv <= POLY_MAX_ROWS inv0 ops side by side: Q[j T + t] <- src.r[j][t], or Montgomery 1 where that is zero or t >= n (no
+// zero is left for launch_fr_batch_inv); mask[j inv0_mask_words(T) ..] <- the zero cells of op j; counts[slot[j]] += their number
+void launch_inv0_prepare(hipStream_t s, const RowTab& src, const uint32_t* slot, uint32_t n_inv, uint32_t* Q, uint32_t* mask,
+                         uint64_t T, uint64_t n, uint64_t* counts);
+// one op behind the inversion: inv[t] <- 0 under the op's mask; bit (null: none) <- Montgomery 1 under the mask, 0 elsewhere
+void launch_inv0_finish(hipStream_t s, uint32_t* inv, const uint32_t* mask, uint64_t T, uint32_t* bit_or_null);
+// out[l T + t] <- limb l of src[t]'s canonical integer x, (x >> (bits l)) & (2^bits - 1), as a canonical Montgomery element, for
+// l < count and t < n (1 <= bits <= 32, bits count <= 256); *over += the cells with x >= 2^(bits count).  out: count vectors of T
+void launch_limbs(hipStream_t s, const uint32_t* src, uint32_t* out, uint64_t T, uint64_t n, uint32_t bits, uint32_t count,
+                  uint64_t* over);
 // ---- blinding rows (fr_blind.hip; the kzg_rows_commit_*_zk builders): rows [usable, n) of evaluation vectors of n Montgomery
 // elements, n - usable <= BLIND_MAX_ROWS (= KZG_MAX_BLIND_ROWS)
 #define BLIND_MAX_ROWS 32

@@ -1038,6 +1038,105 @@ int rows_sorted_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs,
     return multi_msms_finish(ctx, H, i, T, dst, width, 0, 0, out_c48, nullptr, nullptr);
 }
 
+// The helper columns (kzg_rows_commit_derived): a set built FROM sets, every output row a pure function of ONE source row.
+// Each DISTINCT source row (by device pointer: two ops, or two indices of a repeated handle, may name one row) is transformed
+// once into its own vector of the lane's quotient workspace.  All inv0 ops share ONE batched inversion: k_inv0_prepare lays
+// their sources side by side with Montgomery 1 in place of every zero (and of the rows >= usable), so launch_fr_batch_inv runs
+// unchanged over n_inv T elements with its one fr9_inv and nothing to flag; k_inv0_finish then writes the zeros back (and the
+// bit row).  k_limbs cuts one source into its L vectors.  Every output vector takes the caller's tail behind `usable`
+// (launch_sort_tail: no closing row) and is transformed straight into the new set's buffer `dst`; ONE MSM pass of n_out scalar
+// sets commits.  The ops' counts are u64 words behind the first two evaluation slots of the record (which the inversion uses as
+// its scratch and flag) and come back in the copy behind the MSM: the call never waits on its own.
+// Workspace: distinct sources + n_inv + max(n_inv, longest op) vectors of T -- the prepared vector Q is dead behind the
+// inversion, so the limb vectors and the bit row reuse it -- and T / 8 bytes of zero mask per inv0 op in the staging buffer.
+int rows_derived_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_ops, const kzg_derive_op* ops,
+                     uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_counts, const Blind* lay) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const int lg = ilog2_exact(T);
+    uint32_t* tw = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
+    const uint64_t vw = T * 8;                        // one vector, in words
+    const uint64_t n = lay ? lay->usable : T;         // the rows that are read
+    constexpr uint32_t CNT_OFF = 64;                  // the counts in the record: behind the inversion's scratch and flag
+    static_assert(CNT_OFF + 8 * KZG_MAX_BATCH_OPEN <= MR_PAIRS * 32 && KZG_MAX_BATCH_OPEN <= POLY_MAX_ROWS,
+                  "the counts of every op fit the record's evaluation slots");
+    const uint32_t* distinct[POLY_MAX_ROWS];
+    uint32_t slot[POLY_MAX_ROWS], inv_op[POLY_MAX_ROWS], nd = 0, n_inv = 0, longest = 0;
+    for (uint32_t o = 0; o < n_ops; o++) {
+        const uint32_t* p = inputs.r[ops[o].row];
+        uint32_t d = 0;
+        while (d < nd && distinct[d] != p) d++;
+        if (d == nd) distinct[nd++] = p;
+        slot[o] = d;
+        if (ops[o].kind == KZG_DERIVE_INV0) inv_op[n_inv++] = o;
+        longest = std::max(longest, ops[o].kind == KZG_DERIVE_INV0 ? ops[o].count - 1 : ops[o].count);
+    }
+    const uint32_t mw = inv0_mask_words(T), n_scratch = std::max(n_inv, longest);
+    HIPCHK(ctx, A.qext.ensure(((size_t)nd + n_inv + n_scratch) * T * 32));
+    HIPCHK(ctx, A.qstage.ensure(((size_t)n_inv * mw + 4) * 4));
+    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    if (n_inv) {
+        HIPCHK(ctx, A.hbuf.ensure(poly_level_words(n_inv * T) * 4));
+        HIPCHK(ctx, A.hnext.ensure(poly_level_words(n_inv * T) * 4));
+    }
+    uint32_t *src = A.qext.as<uint32_t>(), *W = src + nd * vw, *Q = W + n_inv * vw, *scratch = Q;
+    uint32_t *mask = A.qstage.as<uint32_t>(), *mid = A.ntt_mid.as<uint32_t>();
+    uint8_t* rec = A.brec.as<uint8_t>();
+    uint64_t* cnt = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF);
+    for (uint32_t d = 0; d < nd; d++) {
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, distinct[d], src + d * vw, lg, tw, nullptr, mid);
+    }
+    HIPCHK(ctx, hipMemsetAsync(rec + MR_EVAL, 0, CNT_OFF + 8 * (size_t)n_ops, A.stream));
+    if (n_inv) {
+        Span sp(ctx, A, KZG_T_POLY);
+        RowTab st;
+        for (uint32_t j = 0; j < n_inv; j++) st.r[j] = src + slot[inv_op[j]] * vw;
+        launch_inv0_prepare(A.stream, st, inv_op, n_inv, Q, mask, T, n, cnt);
+        launch_fr_batch_inv(A.stream, Q, W, nullptr, W, n_inv * T, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), rec + MR_EVAL,
+                            reinterpret_cast<uint32_t*>(rec + MR_EVAL + 32));
+    }
+    uint32_t c = 0;   // the next output column
+    auto emit = [&](uint32_t* v) -> int {
+        if (lay) {
+            Span sp(ctx, A, KZG_T_POLY);
+            launch_sort_tail(A.stream, v, T, n, lay->tail_be32 + 32 * (size_t)c * (T - n), A.flags());
+        }
+        const uint32_t* cf;
+        return row_to_coeffs(ctx, A, v, T, 1, &cf, dst + (c++) * vw);
+    };
+    for (uint32_t o = 0, j = 0; o < n_ops; o++) {
+        if (ops[o].kind == KZG_DERIVE_INV0) {
+            uint32_t *inv = W + j * vw, *bit = ops[o].count == 2 ? scratch : nullptr;
+            {
+                Span sp(ctx, A, KZG_T_POLY);
+                launch_inv0_finish(A.stream, inv, mask + (uint64_t)j * mw, T, bit);
+            }
+            if (int rc = emit(inv)) return rc;
+            if (bit)
+                if (int rc = emit(bit)) return rc;
+            j++;
+        } else {
+            {
+                Span sp(ctx, A, KZG_T_POLY);
+                launch_limbs(A.stream, src + slot[o] * vw, scratch, T, n, ops[o].bits, ops[o].count, cnt + o);
+            }
+            for (uint32_t l = 0; l < ops[o].count; l++)
+                if (int rc = emit(scratch + l * vw)) return rc;
+        }
+    }
+    HIPCHK(ctx, hipGetLastError());
+    uint8_t ev[CNT_OFF + 8 * KZG_MAX_BATCH_OPEN + 32];
+    const uint32_t npairs = (CNT_OFF + 8 * n_ops + 31) / 32;
+    if (int rc = multi_msms_finish(ctx, H, i, T, dst, n_out, 0, npairs, out_c48, ev, nullptr)) return rc;
+    uint32_t zf;
+    memcpy(&zf, ev + 32, 4);
+    if (zf) return fail(ctx, KZG_E_HIP, "derived: the batched inversion met a zero behind k_inv0_prepare");
+    memcpy(out_counts, ev + CNT_OFF, 8 * (size_t)n_ops);
+    return KZG_OK;
+}
+
 // the quotient's constants of one (T, E), shared by all lanes like the twiddles: built once under the ctx mutex
 static int ensure_quot_consts(kzg_ctx* ctx, Lane& L, int log_t, int ext_log, const uint32_t* tw_n, const uint32_t** qc) {
     std::lock_guard<std::mutex> lk(ctx->mu);

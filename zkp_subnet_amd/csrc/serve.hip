@@ -1113,6 +1113,76 @@ int rows_sorted(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const
     return KZG_OK;
 }
 
+// kzg_rows_commit_derived: the lookups of an open (one handle list), the reservation of a commit of n_out rows.  opts == NULL,
+// or usable == 0: all T rows are read
+int rows_derived(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
+                 const kzg_derive_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_counts,
+                 uint64_t* out_handle) {
+    if (!ctx || !input_handles || !out_commitments48 || !out_counts || !out_handle) return KZG_E_ARG;
+    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "derived: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (n_ops == 0 || !ops) return fail(ctx, KZG_E_ARG, "derived: n_ops must be at least 1");
+    uint64_t n_out = 0;
+    for (uint32_t o = 0; o < n_ops && n_out <= KZG_MAX_BATCH_OPEN; o++) {
+        const kzg_derive_op& op = ops[o];
+        if (op.kind == KZG_DERIVE_INV0) {
+            if (op.bits != 0) return fail(ctx, KZG_E_ARG, "derived: bits must be 0 on an INV0 op");
+            if (op.count != 1 && op.count != 2)
+                return fail(ctx, KZG_E_ARG, "derived: count must be 1 or 2 on an INV0 op (inv0, then the is-zero bit)");
+        } else if (op.kind == KZG_DERIVE_LIMBS) {
+            if (op.bits == 0 || op.bits > 32) return fail(ctx, KZG_E_ARG, "derived: bits must be in [1, 32] on a LIMBS op");
+            if (op.count == 0 || op.count > KZG_MAX_BATCH_OPEN)
+                return fail(ctx, KZG_E_ARG, "derived: count must be in [1, KZG_MAX_BATCH_OPEN] on a LIMBS op");
+            if ((uint64_t)op.bits * op.count > 256) return fail(ctx, KZG_E_ARG, "derived: bits * count must be at most 256");
+        } else {
+            return fail(ctx, KZG_E_ARG, "derived: unknown kind (KZG_DERIVE_INV0 or KZG_DERIVE_LIMBS)");
+        }
+        n_out += op.count;
+    }
+    if (n_out > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "derived: n_out, the sum of the counts, must be in [1, KZG_MAX_BATCH_OPEN]");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs irefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab it;
+    uint32_t ki = 0, i = 0;
+    uint64_t T = 0;
+    if (int rc = rows_lookup(ctx, "derived", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    for (uint32_t o = 0; o < n_ops; o++)
+        if (ops[o].row >= ki) return fail(ctx, KZG_E_ARG, "derived: a row must index the concatenated rows of the input sets");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "derived: the row length must be a power of two");
+    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
+    if (lay.usable) {
+        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "derived: usable must be in [1, T - 1] (0: all T rows are read)");
+        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
+            return fail(ctx, KZG_E_ARG, "derived: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
+        if (!lay.tail_be32) return fail(ctx, KZG_E_ARG, "derived: tail_be32 must be given when usable > 0");
+        for (uint64_t j = 0; j < n_out * (T - lay.usable); j++)
+            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
+                return fail(ctx, KZG_E_ARG, "derived: tail scalars must be canonical (< r)");
+    } else if (lay.tail_be32) {
+        return fail(ctx, KZG_E_ARG, "derived: tail_be32 must be null in the plain layout (usable = 0)");
+    }
+    if (int rc2 = rows_reserve(ctx, "derived", pend, (size_t)n_out * T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    uint64_t counts[KZG_MAX_BATCH_OPEN];
+    rc = rows_derived_dev(ctx, H, i, it, n_ops, ops, (uint32_t)n_out, T, pend.buf.as<uint32_t>(), c48, counts,
+                          lay.usable ? &lay : nullptr);
+    if (rc) return rc;
+    memcpy(out_commitments48, c48, 48 * (size_t)n_out);
+    memcpy(out_counts, counts, 8 * (size_t)n_ops);
+    *out_handle = rows_insert(ctx, pend, i, (uint32_t)n_out, T);
+    return KZG_OK;
+}
+
 // The check of a _sel builder's selector arguments (SelCall, rows_impl.h): sel_index[l] is KZG_NO_SELECTOR or indexes the
 // concatenated rows of the sel_handles sets, which must be of the call's worker and row length.  The distinct rows named go
 // into sp (a row that serves several lookups is transformed once).
@@ -1694,6 +1764,12 @@ int kzg_rows_commit_shuffle(kzg_ctx* ctx, uint32_t n_input_handles, const uint64
 int kzg_rows_commit_sorted(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t width, uint32_t n_keys,
                            const kzg_sorted_opts* opts, uint8_t* out_commitments48, uint64_t* out_handle) {
     return rows_sorted(ctx, UINT32_MAX, n_input_handles, input_handles, width, n_keys, opts, out_commitments48, out_handle);
+}
+int kzg_rows_commit_derived(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
+                            const kzg_derive_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48,
+                            uint64_t* out_counts, uint64_t* out_handle) {
+    return rows_derived(ctx, UINT32_MAX, n_input_handles, input_handles, n_ops, ops, opts, out_commitments48, out_counts,
+                        out_handle);
 }
 int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_table_handles,
                                const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups, uint32_t width,

@@ -693,28 +693,79 @@ class HipEngine:
             raise bad(f"width must be in [1, {_native.KZG_MAX_BATCH_OPEN}]")
         if not isinstance(n_keys, int) or not 1 <= n_keys <= width:
             raise bad("n_keys must be in [1, width]")
-        tail = [bytes(x) for x in (tail or [])]
-        src = next((x for x in input_sets if getattr(x, "T", None) is not None), None)
-        wi, T = (src.i, src.T) if src is not None else next(
-            (self._set_len[int(x)] for x in input_sets if not hasattr(x, "handle") and int(x) in self._set_len), (None, None))
-        opts = None
-        if usable is None:
-            if tail:
-                raise bad("a tail needs usable (None: all T rows are sorted)")
-        else:
-            if not isinstance(usable, int) or not 1 <= usable < 1 << 64:   # (the C call reads 0 as "plain layout": here None)
-                raise bad("usable must be in [1, T - 1] (None: all T rows are sorted)")
-            if any(len(x) != 32 for x in tail):
-                raise bad("the tail scalars must be of 32 bytes each")
-            if T is None:
-                raise bad("the row length of the sets is unknown to this engine (they were not committed through it)")
-            if usable < T and T - usable <= _native.KZG_MAX_BLIND_ROWS and len(tail) != width * (T - usable):
-                raise bad(f"the tail must hold exactly width * (T - usable) = {width * (T - usable)} scalars, not {len(tail)}")
-            opts = _native.SortedOpts(usable, b"".join(tail) if tail else None)
+        wi, T, lay = self._column_layout(what, input_sets, width, "width", "sorted", usable, tail)
+        opts = _native.SortedOpts(*lay) if lay else None
         c, h = ctypes.create_string_buffer(48 * width), ctypes.c_uint64(0)
         self._chk(self._lib.kzg_rows_commit_sorted(self._h, ni, hi, width, n_keys, ctypes.byref(opts) if opts is not None else None,
                                                    c, ctypes.byref(h)))
         return RowSet(self, h.value, wi, width, T, [c.raw[48 * p:48 * p + 48] for p in range(width)])
+
+    def _column_layout(self, what: str, input_sets, n_cols: int, cols_name: str, verb: str, usable, tail):
+        """The usable layout WITHOUT a closing row (kzg_sorted_opts, kzg_derive_opts) of a builder with n_cols output columns:
+        (worker, T, None for the plain layout or (usable, the column-major tail's bytes or None)); worker and T are None for
+        bare handles of sets this engine did not commit, which only the plain layout accepts."""
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: {why}")   # noqa: E731
+        tail = [bytes(x) for x in (tail or [])]
+        src = next((x for x in input_sets if getattr(x, "T", None) is not None), None)
+        wi, T = (src.i, src.T) if src is not None else next(
+            (self._set_len[int(x)] for x in input_sets if not hasattr(x, "handle") and int(x) in self._set_len), (None, None))
+        if usable is None:
+            if tail:
+                raise bad(f"a tail needs usable (None: all T rows are {verb})")
+            return wi, T, None
+        if not isinstance(usable, int) or not 1 <= usable < 1 << 64:   # (the C call reads 0 as "plain layout": here None)
+            raise bad(f"usable must be in [1, T - 1] (None: all T rows are {verb})")
+        if any(len(x) != 32 for x in tail):
+            raise bad("the tail scalars must be of 32 bytes each")
+        if T is None:
+            raise bad("the row length of the sets is unknown to this engine (they were not committed through it)")
+        if usable < T and T - usable <= _native.KZG_MAX_BLIND_ROWS and len(tail) != n_cols * (T - usable):
+            raise bad(f"the tail must hold exactly {cols_name} * (T - usable) = {n_cols * (T - usable)} scalars, not {len(tail)}")
+        return wi, T, (usable, b"".join(tail) if tail else None)
+
+    # ---- a set built from sets: the helper columns of zero tests and range checks, each a function of one resident column
+    def commit_derived(self, input_sets: Sequence[object], ops: Sequence[tuple], usable: Optional[int] = None,
+                       tail: Sequence[bytes] = ()) -> Tuple["RowSet", List[int]]:
+        """kzg_rows_commit_derived over the concatenated rows of input_sets (RowSet objects or bare handles).  ops: ("inv0", row)
+        gives the row 1 / x, 0 where x = 0; ("inv0", row, True) also the bit row behind it (1 where x = 0); ("limbs", row, bits,
+        count) the `count` limbs of `bits` bits of x's canonical integer, least significant first.  Returns (the new RowSet of
+        all output rows in the order of ops, one count per op: the zero cells of an inv0 op, the cells at or above 2^(bits *
+        count) of a limbs op).  usable = None reads all T rows; otherwise only rows [0, usable) are read and row usable + s of
+        output column c takes tail[c * (T - usable) + s] (32 bytes each, column-major; there is no closing row)."""
+        what = "commit_derived"
+        ni, hi = self._handle_array(input_sets, what)
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: {why}")   # noqa: E731
+        ops = list(ops) if isinstance(ops, (list, tuple)) else None
+        if not ops:
+            raise bad("ops must be a non-empty list")
+        recs = []
+        for op in ops:
+            if not isinstance(op, (list, tuple)) or not op or op[0] not in ("inv0", "limbs"):
+                raise bad('an op is ("inv0", row), ("inv0", row, True) or ("limbs", row, bits, count)')
+            if op[0] == "inv0":
+                if len(op) not in (2, 3) or (len(op) == 3 and not isinstance(op[2], bool)):
+                    raise bad('an inv0 op is ("inv0", row) or ("inv0", row, with_bit)')
+                kind, nums, count = _native.KZG_DERIVE_INV0, [op[1], 0], 2 if len(op) == 3 and op[2] else 1
+            else:
+                if len(op) != 4:
+                    raise bad('a limbs op is ("limbs", row, bits, count)')
+                kind, nums, count = _native.KZG_DERIVE_LIMBS, [op[1], op[2]], op[3]
+            if any(not isinstance(v, int) or isinstance(v, bool) or not 0 <= v < 1 << 32 for v in nums + [count]):
+                raise bad("row, bits and count must be integers in [0, 2^32)")
+            if kind == _native.KZG_DERIVE_LIMBS and (not 1 <= nums[1] <= 32 or not 1 <= count <= _native.KZG_MAX_BATCH_OPEN
+                                                     or nums[1] * count > 256):
+                raise bad(f"bits must be in [1, 32], count in [1, {_native.KZG_MAX_BATCH_OPEN}] and bits * count at most 256")
+            recs.append((kind, nums[0], nums[1], count))
+        n_out = sum(r[3] for r in recs)
+        if n_out > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"the ops give {n_out} output rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+        wi, T, lay = self._column_layout(what, input_sets, n_out, "n_out", "read", usable, tail)
+        opts = _native.DeriveOpts(*lay) if lay else None
+        arr =(_native.DeriveOp * len(recs))(*[_native.DeriveOp(*r) for r in recs])
+        c, h, cnt = ctypes.create_string_buffer(48 * n_out), ctypes.c_uint64(0), (ctypes.c_uint64 * len(recs))()
+        self._chk(self._lib.kzg_rows_commit_derived(self._h, ni, hi, len(recs), arr, ctypes.byref(opts) if opts is not None else None,
+                                                    c, cnt, ctypes.byref(h)))
+        return RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]), [int(v) for v in cnt]
 
     # ---- a third set built from sets: the PLONK quotient (round 3), computed and committed on the device
     def commit_quotient(self, sets: Sequence[object], terms: Sequence[Tuple[bytes, Sequence[int]]], perm: Optional[dict] = None,

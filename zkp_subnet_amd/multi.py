@@ -212,6 +212,9 @@ class MultiDeviceClient:
     def worker_commit_sorted(self, input_handles: Sequence[int], width, n_keys=None, usable=None, tail=()):
         return self._routed_builder("worker_commit_sorted", [input_handles], input_handles, width, n_keys, usable, tail)
 
+    def worker_commit_derived(self, input_handles: Sequence[int], ops, usable=None, tail=()):
+        return self._routed_builder("worker_commit_derived", [input_handles], input_handles, ops, usable, tail)
+
     def worker_commit_quotient_zk(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None, ext_log=2,
                                   n_pieces=3):
         return self._routed_builder("worker_commit_quotient_zk", [handles], handles, terms, perm, lookup, active_row, ext_log,
