@@ -729,7 +729,7 @@ int kzg_rows_commit_sorted(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_
  * scalar >= r.  The source sets are only read; a release or an SRS load racing the call follows the rules of kzg_rows_open.
  * Thread-safe like every call; after any error the context keeps serving.
  * OUT OF SCOPE: per-row selectors; signed limbs or limbs in a base that is no power of two; halo2's running-sum decomposition
- * along the rows; general expression rows (sum_u c_u prod rows[rot] committed as a column).
+ * along the rows.  (General expression rows, sum_u c_u prod rows[rot] committed as a column: kzg_rows_commit_expr below.)
  * SOUNDNESS: nothing here is a proof.  The derived rows are prover data; the argument is the caller's gates (x inv0 = 1 - bit
  * and x bit = 0; x = sum_l 2^(b l) limb_l) and the lookup of the limbs, with every challenge drawn AFTER these commitments are
  * fixed.  The library derives no challenge and draws no randomness: the tail must be fresh per proof. */
@@ -750,6 +750,61 @@ int kzg_rows_commit_derived(kzg_ctx* ctx, uint32_t n_input_handles, const uint64
                             uint32_t n_ops, const kzg_derive_op* ops, const kzg_derive_opts* opts /* NULL: plain */,
                             uint8_t* out_commitments48 /* n_out * 48 */, uint64_t* out_counts /* n_ops */,
                             uint64_t* out_handle);
+/* THE EXPRESSION COLUMNS: a set built FROM sets, every output column plain arithmetic in columns that are already resident --
+ * c = a b + q d, a theta-compressed tuple, the next row of a running value, the left side of any custom gate.  The concatenated
+ * rows of the input_handles sets (as in kzg_rows_commit_derived) are the source columns; cell t of a column is its value at
+ * w_T^t.  Expression e is a list of terms in the format of kzg_rows_commit_quotient_ext's gate (kzg_quotient_terms), evaluated on
+ * H itself, not on the extended coset: for every row t < n, with n = usable, or n = T in the plain layout,
+ *   v_e[t] = sum_u c_u prod_f col_{j(u,f)}[(t + rot(u,f)) mod T]
+ * with 1 <= n_terms <= KZG_MAX_GATE_TERMS terms of 0 .. KZG_MAX_EXPR_FACTORS factors each; a term with no factors is the
+ * constant c_u.  term_rots runs beside term_rows (NULL: every rotation 0); any int32 rotation is accepted and reduced mod T (-1
+ * and T - 1, or 0 and T, give the same bytes).  A rotated factor of a row t < n reads the source cell it lands on, even at or
+ * behind `usable`, as the quotient does; no source cell is read on behalf of a row t >= n.
+ * flags = 0: the expression is COMMITTED.  The n_out committed expressions become, in their order, the rows of ONE new set of
+ * the same worker and length; out_commitments48[c] equals kzg_rows_commit(i, n_out, the T evaluations, T, 1, ..)[c] byte for
+ * byte, and *out_handle opens, evaluates, combines, releases, goes stale and counts against KZG_MAX_ROW_SETS (KZG_E_BUSY;
+ * KZG_E_NOMEM on a failed allocation, the lane's workspace included: one T-element vector per DISTINCT source row that some
+ * term names -- transformed once however many factors name it; a row no term names is not transformed -- and one more) like
+ * any other.  flags = KZG_EXPR_CHECK: the expression is evaluated and counted only -- no row, no commitment: a device-side
+ * "mock prover" for a gate, which the quotient would refuse only after all its work and without a row index.
+ * out_nonzero[e] is the number of rows t < n with v_e[t] != 0 and out_first[e] the smallest such t, or KZG_EXPR_NONE; both are
+ * filled for EVERY expression, committed or not.  If every expression is a check (n_out = 0) the call creates no set:
+ * *out_handle = 0, out_commitments48 may be NULL, no reservation is made, nothing counts against KZG_MAX_ROW_SETS, and neither
+ * an inverse transform nor an MSM runs.
+ * opts (NULL: plain layout) is kzg_derive_opts in layout and refusals: usable = 0 is the plain layout, tail_be32 must be NULL.
+ * Otherwise 1 <= usable <= T - 1, T - usable <= KZG_MAX_BLIND_ROWS, and output row usable + s of committed column c takes
+ * tail_be32[c * (T - usable) + s], column-major canonical scalars over the n_out COMMITTED columns (with n_out = 0 the tail is
+ * empty: tail_be32 is not read and may be NULL).  There is NO closing row.
+ * Handle rules, the worker and T rules, the life of the new set, thread safety and "after any error the context keeps
+ * serving" are those of kzg_rows_commit_derived.  KZG_E_ARG with a message that begins "expr:" and names the cause: n_exprs
+ * outside [1, KZG_MAX_BATCH_OPEN]; n_terms outside [1, KZG_MAX_GATE_TERMS]; a term of more than KZG_MAX_EXPR_FACTORS factors;
+ * flags other than 0 or KZG_EXPR_CHECK; a row index at or beyond the concatenation; a coefficient >= r (checked on the HOST,
+ * before any lane is taken: an argument error, not a queued failure); a NULL array inside an expression (coeffs_be32,
+ * term_lens, or term_rows when some term has a factor); T > 2^32 (the prepared rotations are 32-bit words); and the usable and
+ * tail refusals of kzg_rows_commit_derived.
+ * OUT OF SCOPE: division or an inverse inside an expression (compose with KZG_DERIVE_INV0); per-row selectors other than as an
+ * ordinary factor; more than KZG_MAX_GATE_TERMS terms (split the expression and add the parts with a further call); the
+ * running-sum decomposition along the rows (row t + 1 of the OUTPUT depending on row t of the output).
+ * SOUNDNESS: nothing here is a proof.  An expression column is prover data: the argument is the caller's gate in the quotient
+ * (kzg_rows_commit_quotient*), with every challenge that enters a coefficient drawn after the commitments it depends on are
+ * fixed.  A zero count of a check is a convenience for the prover -- it tells where a witness is wrong before the quotient
+ * is paid -- and convinces no verifier.  The library derives no challenge and draws no randomness: the tail must be fresh
+ * per proof. */
+#define KZG_MAX_EXPR_FACTORS 8
+#define KZG_EXPR_CHECK 1u                   /* flags: evaluate and count only; no row, no commitment */
+#define KZG_EXPR_NONE  0xffffffffffffffffull
+typedef struct kzg_expr {
+    kzg_quotient_terms terms;               /* coeffs_be32, term_lens, term_rows, term_rots (NULL: all 0) */
+    uint32_t flags;                         /* 0 or KZG_EXPR_CHECK */
+} kzg_expr;
+typedef struct kzg_expr_opts {
+    uint64_t usable;           /* 0: plain layout (all T rows are evaluated); else only rows [0, usable) */
+    const uint8_t* tail_be32;  /* n_out * (T - usable) * 32, column-major; NULL when usable == 0 (and, if wished, when n_out == 0) */
+} kzg_expr_opts;
+int kzg_rows_commit_expr(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                         uint32_t n_exprs, const kzg_expr* exprs, const kzg_expr_opts* opts /* NULL: plain */,
+                         uint8_t* out_commitments48 /* n_out * 48 */, uint64_t* out_nonzero /* n_exprs */,
+                         uint64_t* out_first /* n_exprs */, uint64_t* out_handle);
 /* THE QUOTIENT WITH LOOKUP SELECTORS: kzg_rows_commit_quotient_zk and kzg_rows_quotient_part for lookups that are enabled on
  * some rows only.  selectors->selector_rows holds L = lookup->n_lookups entries, each a row index into the call's concatenated
  * rows (the caller's fixed column q_l, the row that kzg_rows_commit_multiplicities_sel / _lookup_sum_sel read) or
@@ -1100,6 +1155,10 @@ int kzg_multi_rows_commit_sorted(kzg_multi* mh, uint32_t i, uint32_t n_input_han
 int kzg_multi_rows_commit_derived(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                   uint32_t n_ops, const kzg_derive_op* ops, const kzg_derive_opts* opts,
                                   uint8_t* out_commitments48, uint64_t* out_counts, uint64_t* out_handle);
+/* kzg_rows_commit_expr on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_expr(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                               uint32_t n_exprs, const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48,
+                               uint64_t* out_nonzero, uint64_t* out_first, uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

@@ -25,6 +25,9 @@ KZG_MAX_GATE_TERMS = 16   # kzg_rows_commit_quotient
 KZG_MAX_BLIND_ROWS = 32   # kzg_rows_commit_*_zk: T - usable
 KZG_NO_SELECTOR = 0xffffffff   # kzg_rows_commit_*_sel: a lookup without a selector row
 KZG_DERIVE_INV0, KZG_DERIVE_LIMBS = 1, 2   # kzg_rows_commit_derived: kzg_derive_op.kind
+KZG_MAX_EXPR_FACTORS = 8   # kzg_rows_commit_expr: factors of one term
+KZG_EXPR_CHECK = 1   # kzg_expr.flags: evaluate and count only
+KZG_EXPR_NONE = 0xffffffffffffffff   # out_first: no non-zero cell
 KZG_OK, KZG_E_ARG, KZG_E_SCALAR, KZG_E_POINT, KZG_E_HIP, KZG_E_NOMEM, KZG_E_BUSY, KZG_E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
 STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_SCALAR", -3: "E_POINT", -4: "E_HIP", -5: "E_NOMEM", -6: "E_BUSY", -7: "E_COMM"}
 TIMING_NAMES = ["decode", "ntt", "digits", "scan", "scatter", "accumulate", "fixup", "tree", "final", "poly", "total", "collective"]
@@ -90,6 +93,16 @@ class DeriveOpts(ctypes.Structure):
     _fields_ = [("usable", _U64), ("tail_be32", _B)]
 
 
+class Expr(ctypes.Structure):
+    """kzg_expr"""
+    _fields_ = [("terms", QuotientTerms), ("flags", _U32)]
+
+
+class ExprOpts(ctypes.Structure):
+    """kzg_expr_opts"""
+    _fields_ = [("usable", _U64), ("tail_be32", _B)]
+
+
 class QuotientLink(ctypes.Structure):
     """kzg_quotient_link"""
     _fields_ = [("prev_row", _U32), ("rot", ctypes.c_int32)]
@@ -136,6 +149,8 @@ SYMBOLS = {
                                     ctypes.POINTER(_U64)]),
     "kzg_rows_commit_derived": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp), ctypes.POINTER(DeriveOpts), _B,
                                      ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_expr": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,
+                                  ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_lookup_sum": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B, _B, _B, _B,
                                         ctypes.POINTER(_U64)]),
     "kzg_rows_commit_multiplicities": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _B,
@@ -241,6 +256,8 @@ SYMBOLS = {
                                           ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_derived": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp),
                                            ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_expr": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,
+                                        ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_lookup_sum": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B,
                                               _B, _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_multiplicities": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32,

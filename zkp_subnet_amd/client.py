@@ -686,6 +686,51 @@ class Client:
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
                 "counts": [int(v) for v in counts]}
 
+    # ---- columns that are plain arithmetic in resident columns, and gates checked row by row, on the device
+    @_guard
+    def worker_commit_expr(self, input_handles: Sequence[int], exprs: Sequence[Sequence], usable: Optional[int] = None,
+                           tail: Sequence[str] = ()):
+        """Extension: expression columns over the rows of the input_handles sets, evaluated on the device: v[t] = sum_u c_u
+        prod_f row[(t + rot) mod T].  exprs: a list whose entries are [terms] (the column is committed) or [terms, true] (a
+        check: evaluated and counted only); terms as in worker_commit_quotient_ext: [coefficient, [factors]] per term, a factor
+        a row index or a [row, rot] pair, at most 8 factors per term and 16 terms.  The committed expressions become, in their
+        order, the rows of ONE new set.  usable = null evaluates all T rows; otherwise only rows [0, usable) and row usable + s
+        of committed column c is tail[c * (T - usable) + s] -- there is no closing row.  Returns the handle (null when every
+        entry is a check), the commitments, and per entry `nonzero`, the number of non-zero cells among the rows evaluated,
+        and `first`, the smallest such row (null: none).  Nothing here is a proof: a committed column is prover data and the
+        argument is the caller's gate in the quotient; a zero count only tells the prover that the gate holds."""
+        what = "worker_commit_expr"
+        hs = _handles(input_handles)
+        try:
+            recs = []
+            for ent in exprs:
+                if isinstance(ent, (str, bytes)) or len(ent) not in (1, 2) or (len(ent) == 2 and not isinstance(ent[1], bool)):
+                    raise ValueError(f"an entry is [terms] or [terms, check]: {ent!r}")
+                if any(isinstance(f, (tuple, list)) and len(f) != 2 for _, fs in ent[0] for f in fs):
+                    raise ValueError("a factor is a row index or a [row, rot] pair")
+                tt = [(codec.fr_to_be32(c), [(int(f[0]), int(f[1])) if isinstance(f, (tuple, list)) else (int(f), 0) for f in fs])
+                      for c, fs in ent[0]]
+                recs.append((tt, len(ent) == 2 and ent[1]))
+        except (TypeError, ValueError, IndexError, KeyError) as e:
+            raise codec.CodecError(f"{what}: exprs must be a list of [terms] or [terms, check] with terms a list of "
+                                   f"[coefficient, [factors]]: {e!r}") from e
+        if not recs:
+            raise codec.CodecError(f"{what}: exprs must not be empty")
+        if any(int.from_bytes(c, "big") >= codec.R_MODULUS for tt, _ in recs for c, _ in tt):
+            raise codec.CodecError(f"{what}: coefficients must be canonical scalars (< r)")
+        if usable is None:
+            if tail:
+                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are evaluated)")
+            tb = []
+        else:
+            usable, tb = self._blind(what, usable, tail)
+            if usable == 0:
+                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are evaluated)")
+        rs, nonzero, first = self.engine.commit_expr(hs, recs, usable, tb)
+        return {"handle": None if rs is None else int(rs.handle),
+                "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments],
+                "nonzero": nonzero, "first": first}
+
     @staticmethod
     def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: Sequence[int], n_groups: int, width: int,
                                theta: str, gamma: str, coeff: str, active_row: Optional[int] = None,

@@ -7,6 +7,7 @@
 //   pipeline.hip  the host-side sequencing of the kernels: one MSM (msm_core), a row's commit / open (commit_open_dev)
 //   serve.hip     the serving entry points: commit / open / msm / ntt / eval, resident slots, tickets, sums
 //   fr_derive.hip the kernels of kzg_rows_commit_derived: inverse-or-zero around the batched inversion, limb decomposition
+//   fr_expr.hip   the kernel of kzg_rows_commit_expr: sums of products of rotated resident columns on H, counted and stored
 //   comm.hip      the library's own RCCL collective (kzg_comm_*, kzg_msm_sharded, the stream-chained pair)
 //   abi_test.hip  unit-op test hooks (include/kzg_mi355x_test.h)
 // No CPU arithmetic fallback exists anywhere here: if HIP fails, the call fails.
@@ -477,6 +478,14 @@ int rows_sorted_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs,
 // inv0 op, cells at or above 2^(bits count) of a limbs op).  lay: as for rows_sorted_dev, the tail column-major over n_out
 int rows_derived_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_ops, const kzg_derive_op* ops,
                      uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_counts, const Blind* lay);
+// the n_out committed ones of the n_exprs expressions (checked by the caller: term counts and lengths in range, rows inside
+// `inputs`, rotations reduced into [0, T), canonical coefficients; is_check[e] != 0: expression e is only counted) into a new
+// n_out-row set's buffer dst (null when n_out = 0: then no transform back and no MSM runs): their commitments, and per
+// expression the number of non-zero cells among the rows evaluated and the smallest such row (KZG_EXPR_NONE: none).  lay: as
+// for rows_sorted_dev, the tail column-major over the n_out committed columns
+int rows_expr_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_exprs, const ExprPlan* exprs,
+                  const uint8_t* is_check, uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_nonzero,
+                  uint64_t* out_first, const Blind* lay);
 // the quotient pieces of the constraints qp over the n_rows coefficient rows of rt into a new n_pieces-row set's buffer dst:
 // their commitments, and whether a coefficient of t at or above n_pieces T was not zero (the caller creates no set)
 int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t n_rows, uint64_t T, const QuotPlan& qp,

@@ -21,17 +21,7 @@
 
 static inline uint32_t nblk(uint64_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
 
-// the workgroup's count of flagged lanes added to *total: one ballot and one LDS add per wave, one global add per workgroup.
-// Called by every lane of the workgroup (uniform control flow).
-KZG_DEV void derive_count(bool flagged, unsigned long long* __restrict__ total) {
-    __shared__ uint32_t wg_cnt;
-    if (threadIdx.x == 0) wg_cnt = 0;
-    __syncthreads();
-    const unsigned long long b = __ballot(flagged);
-    if ((threadIdx.x & 63u) == 0 && b) atomicAdd(&wg_cnt, (uint32_t)__popcll(b));
-    __syncthreads();
-    if (threadIdx.x == 0 && wg_cnt) atomicAdd(total, (unsigned long long)wg_cnt);
-}
+// (derive_count, the workgroup's count of flagged lanes, lives in fr_kernels.hip.h: fr_expr.hip counts with it too)
 
 // ------------------------------------------------------------------------------------------------ inverse-or-zero
 // grid (blocks over T, n_inv): op j = blockIdx.y reads src[j] (two ops may name one vector) and adds to counts[slot[j]]

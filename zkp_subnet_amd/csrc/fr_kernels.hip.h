@@ -287,6 +287,32 @@ void launch_inv0_finish(hipStream_t s, uint32_t* inv, const uint32_t* mask, uint
 // l < count and t < n (1 <= bits <= 32, bits count <= 256); *over += the cells with x >= 2^(bits count).  out: count vectors of T
 void launch_limbs(hipStream_t s, const uint32_t* src, uint32_t* out, uint64_t T, uint64_t n, uint32_t bits, uint32_t count,
                   uint64_t* over);
+// the workgroup's count of flagged lanes added to *total: one ballot and one LDS add per wave, one global add per workgroup.
+// Called by every lane of the workgroup (uniform control flow).  Shared by the kernels of fr_derive.hip and fr_expr.hip
+KZG_DEV void derive_count(bool flagged, unsigned long long* __restrict__ total) {
+    __shared__ uint32_t wg_cnt;
+    if (threadIdx.x == 0) wg_cnt = 0;
+    __syncthreads();
+    const unsigned long long b = __ballot(flagged);
+    if ((threadIdx.x & 63u) == 0 && b) atomicAdd(&wg_cnt, (uint32_t)__popcll(b));
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_cnt) atomicAdd(total, (unsigned long long)wg_cnt);
+}
+// ---- the expression columns of kzg_rows_commit_expr (fr_expr.hip): v[t] = sum_u c_u prod_f src.r[row[u][f]][(t + rot[u][f]) mod T]
+// for t < n <= T over evaluation vectors of T canonical Montgomery elements (T a power of two, at most 2^32)
+#define EXPR_MAX_TERMS 16
+#define EXPR_MAX_FACTORS 8
+struct ExprPlan {
+    uint32_t n_terms;                                   // 1 .. EXPR_MAX_TERMS
+    const uint8_t* coeffs_be32;                         // n_terms canonical scalars, 32 big-endian HOST bytes each (the caller's check)
+    uint8_t term_len[EXPR_MAX_TERMS];                   // 0 .. EXPR_MAX_FACTORS
+    uint8_t term_row[EXPR_MAX_TERMS][EXPR_MAX_FACTORS]; // index into src
+    uint32_t term_rot[EXPR_MAX_TERMS][EXPR_MAX_FACTORS];// in [0, T)
+};
+// out (null: a check, nothing is stored) [t] <- v[t], canonical, for t < n; *nonzero += the cells t < n with v[t] != 0;
+// *first <- min(*first, the smallest such t).  out must not alias a source (a rotated factor reads other cells)
+void launch_expr(hipStream_t s, const RowTab& src, const ExprPlan& ep, uint32_t* out_or_null, uint64_t T, uint64_t n,
+                 uint64_t* nonzero, uint64_t* first);
 // ---- blinding rows (fr_blind.hip; the kzg_rows_commit_*_zk builders): rows [usable, n) of evaluation vectors of n Montgomery
 // elements, n - usable <= BLIND_MAX_ROWS (= KZG_MAX_BLIND_ROWS)
 #define BLIND_MAX_ROWS 32

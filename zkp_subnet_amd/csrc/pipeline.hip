@@ -1137,6 +1137,85 @@ int rows_derived_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs
     return KZG_OK;
 }
 
+// The expression columns (kzg_rows_commit_expr): a set built FROM sets, every output row plain arithmetic in source rows.
+// Each DISTINCT source row (by device pointer: two indices of a repeated handle name one row) that some term names is
+// transformed forward once into its own vector of the lane's quotient workspace; a row no term names is not transformed.
+//   step                      launches                         per call
+//   forward transforms        launch_fr_ntt                    one per distinct source row named
+//   evaluate + count          launch_expr (k_expr)             one per expression; a check stores nothing
+//   tail                      launch_sort_tail                 one per committed expression, with `usable` only
+//   inverse transform         row_to_coeffs                    one per committed expression, straight into dst
+//   commit                    multi_msms_finish                ONE pass of n_out scalar sets
+// A committed expression is evaluated into ONE scratch vector, takes the caller's tail behind `usable` (no closing row) and is
+// transformed straight into the new set's buffer `dst`; the scratch vector is reused, the stream orders the work.  The counts
+// and first indices are u64 words behind the first two evaluation slots of the record (the inversion's slots of the derived
+// call, so that the layouts agree) and come back in the copy behind the MSM: the call never waits on its own.  With n_out = 0
+// nothing is transformed back and no MSM runs: the record's one copy and its synchronisation are all that is left.
+// Workspace: distinct sources + 1 vectors of T.
+int rows_expr_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_exprs, const ExprPlan* exprs,
+                  const uint8_t* is_check, uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_nonzero,
+                  uint64_t* out_first, const Blind* lay) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const int lg = ilog2_exact(T);
+    uint32_t* tw = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
+    const uint64_t vw = T * 8;                        // one vector, in words
+    const uint64_t n = lay ? lay->usable : T;         // the rows that are evaluated
+    constexpr uint32_t CNT_OFF = 64;                  // the counts in the record, then the first indices
+    static_assert(CNT_OFF + 16 * KZG_MAX_BATCH_OPEN <= MR_PAIRS * 32 && KZG_MAX_BATCH_OPEN <= POLY_MAX_ROWS,
+                  "the count and the first index of every expression fit the record's evaluation slots");
+    static_assert(KZG_MAX_GATE_TERMS == EXPR_MAX_TERMS && KZG_MAX_EXPR_FACTORS == EXPR_MAX_FACTORS, "the header's caps are the kernel's");
+    const uint32_t* distinct[POLY_MAX_ROWS];
+    uint32_t nd = 0;
+    ExprPlan plan[KZG_MAX_BATCH_OPEN];
+    for (uint32_t e = 0; e < n_exprs; e++) {
+        plan[e] = exprs[e];
+        for (uint32_t u = 0; u < plan[e].n_terms; u++)
+            for (uint32_t f = 0; f < plan[e].term_len[u]; f++) {
+                const uint32_t* p = inputs.r[plan[e].term_row[u][f]];
+                uint32_t d = 0;
+                while (d < nd && distinct[d] != p) d++;
+                if (d == nd) distinct[nd++] = p;
+                plan[e].term_row[u][f] = (uint8_t)d;
+            }
+    }
+    HIPCHK(ctx, A.qext.ensure(((size_t)nd + 1) * T * 32));
+    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    uint32_t *src = A.qext.as<uint32_t>(), *scratch = src + nd * vw, *mid = A.ntt_mid.as<uint32_t>();
+    uint8_t* rec = A.brec.as<uint8_t>();
+    uint64_t *cnt = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF), *first = cnt + n_exprs;
+    RowTab st;
+    memset(&st, 0, sizeof(st));
+    for (uint32_t d = 0; d < nd; d++) {
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, distinct[d], src + d * vw, lg, tw, nullptr, mid);
+        st.r[d] = src + d * vw;
+    }
+    HIPCHK(ctx, hipMemsetAsync(cnt, 0, 8 * (size_t)n_exprs, A.stream));
+    HIPCHK(ctx, hipMemsetAsync(first, 0xff, 8 * (size_t)n_exprs, A.stream));   // KZG_EXPR_NONE
+    for (uint32_t e = 0, c = 0; e < n_exprs; e++) {
+        {
+            Span sp(ctx, A, KZG_T_POLY);
+            launch_expr(A.stream, st, plan[e], is_check[e] ? nullptr : scratch, T, n, cnt + e, first + e);
+        }
+        if (is_check[e]) continue;
+        if (lay) {
+            Span sp(ctx, A, KZG_T_POLY);
+            launch_sort_tail(A.stream, scratch, T, n, lay->tail_be32 + 32 * (size_t)c * (T - n), A.flags());
+        }
+        const uint32_t* cf;
+        if (int rc = row_to_coeffs(ctx, A, scratch, T, 1, &cf, dst + (c++) * vw)) return rc;
+    }
+    HIPCHK(ctx, hipGetLastError());
+    uint8_t ev[CNT_OFF + 16 * KZG_MAX_BATCH_OPEN + 32];
+    const uint32_t npairs = (CNT_OFF + 16 * n_exprs + 31) / 32;
+    if (int rc = multi_msms_finish(ctx, H, i, T, dst, n_out, 0, npairs, out_c48, ev, nullptr)) return rc;
+    memcpy(out_nonzero, ev + CNT_OFF, 8 * (size_t)n_exprs);
+    memcpy(out_first, ev + CNT_OFF + 8 * (size_t)n_exprs, 8 * (size_t)n_exprs);
+    return KZG_OK;
+}
+
 // the quotient's constants of one (T, E), shared by all lanes like the twiddles: built once under the ctx mutex
 static int ensure_quot_consts(kzg_ctx* ctx, Lane& L, int log_t, int ext_log, const uint32_t* tw_n, const uint32_t** qc) {
     std::lock_guard<std::mutex> lk(ctx->mu);

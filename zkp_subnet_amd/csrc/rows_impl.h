@@ -54,6 +54,10 @@ int rows_sorted(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const
 int rows_derived(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
                  const kzg_derive_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_counts,
                  uint64_t* out_handle);
+// opts: the usable layout and its tail as the public call takes them (null: all T rows are evaluated)
+int rows_expr(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
+              const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48, uint64_t* out_nonzero,
+              uint64_t* out_first, uint64_t* out_handle);
 // zk: the blinding rows of the _zk call, the layout of the _sel call.  sc: the selectors of the _sel call
 int rows_lookup_sum(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
                     uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,

@@ -1183,6 +1183,97 @@ int rows_derived(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, cons
     return KZG_OK;
 }
 
+// kzg_rows_commit_expr: the lookups of an open (one handle list), the reservation of a commit of n_out rows -- none when every
+// expression is a check.  opts == NULL, or usable == 0: all T rows are evaluated.  Coefficients are checked here, on the host
+int rows_expr(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
+              const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48, uint64_t* out_nonzero,
+              uint64_t* out_first, uint64_t* out_handle) {
+    if (!ctx || !input_handles || !out_nonzero || !out_first || !out_handle) return KZG_E_ARG;
+    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "expr: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (n_exprs == 0 || n_exprs > KZG_MAX_BATCH_OPEN || !exprs)
+        return fail(ctx, KZG_E_ARG, "expr: n_exprs must be in [1, KZG_MAX_BATCH_OPEN]");
+    ExprPlan plan[KZG_MAX_BATCH_OPEN];
+    int32_t rots[KZG_MAX_BATCH_OPEN][EXPR_MAX_TERMS][EXPR_MAX_FACTORS];   // as given: reduced mod T once T is known
+    uint8_t is_check[KZG_MAX_BATCH_OPEN];
+    uint32_t n_out = 0, max_row = 0;
+    memset(plan, 0, sizeof(plan));
+    memset(rots, 0, sizeof(rots));
+    for (uint32_t e = 0; e < n_exprs; e++) {
+        const kzg_quotient_terms& g = exprs[e].terms;
+        if (exprs[e].flags & ~KZG_EXPR_CHECK) return fail(ctx, KZG_E_ARG, "expr: flags must be 0 or KZG_EXPR_CHECK");
+        is_check[e] = exprs[e].flags == KZG_EXPR_CHECK;
+        n_out += !is_check[e];
+        if (g.n_terms == 0 || g.n_terms > KZG_MAX_GATE_TERMS)
+            return fail(ctx, KZG_E_ARG, "expr: n_terms must be in [1, KZG_MAX_GATE_TERMS]");
+        if (!g.coeffs_be32 || !g.term_lens)
+            return fail(ctx, KZG_E_ARG, "expr: coeffs_be32 and term_lens must not be null inside an expression");
+        plan[e].n_terms = g.n_terms;
+        plan[e].coeffs_be32 = g.coeffs_be32;
+        for (uint32_t u = 0, at = 0; u < g.n_terms; u++) {
+            if (!fr_be32_canonical(g.coeffs_be32 + 32 * (size_t)u))
+                return fail(ctx, KZG_E_ARG, "expr: term coefficients must be canonical scalars (< r)");
+            if (g.term_lens[u] > KZG_MAX_EXPR_FACTORS)
+                return fail(ctx, KZG_E_ARG, "expr: a term has more than KZG_MAX_EXPR_FACTORS factors");
+            if (g.term_lens[u] && !g.term_rows)
+                return fail(ctx, KZG_E_ARG, "expr: term_rows must not be null inside an expression that has a factor");
+            plan[e].term_len[u] = (uint8_t)g.term_lens[u];
+            for (uint32_t f = 0; f < g.term_lens[u]; f++, at++) {
+                max_row = std::max(max_row, g.term_rows[at]);
+                plan[e].term_row[u][f] = (uint8_t)(g.term_rows[at] < KZG_MAX_BATCH_OPEN ? g.term_rows[at] : 0);
+                if (g.term_rots) rots[e][u][f] = g.term_rots[at];
+            }
+        }
+    }
+    if (n_out && !out_commitments48) return KZG_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs irefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab it;
+    uint32_t ki = 0, i = 0;
+    uint64_t T = 0;
+    if (int rc = rows_lookup(ctx, "expr", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    if (max_row >= ki) return fail(ctx, KZG_E_ARG, "expr: a row must index the concatenated rows of the input sets");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "expr: the row length must be a power of two");
+    if (T > ((uint64_t)1 << 32)) return fail(ctx, KZG_E_ARG, "expr: the row length must be at most 2^32");
+    for (uint32_t e = 0; e < n_exprs; e++)   // any int32 rotation, reduced into [0, T)
+        for (uint32_t u = 0; u < plan[e].n_terms; u++)
+            for (uint32_t f = 0; f < plan[e].term_len[u]; f++)
+                plan[e].term_rot[u][f] = (uint32_t)(((int64_t)rots[e][u][f] % (int64_t)T + (int64_t)T) % (int64_t)T);
+    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
+    if (lay.usable) {
+        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "expr: usable must be in [1, T - 1] (0: all T rows are evaluated)");
+        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
+            return fail(ctx, KZG_E_ARG, "expr: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
+        if (n_out && !lay.tail_be32) return fail(ctx, KZG_E_ARG, "expr: tail_be32 must be given when usable > 0");
+        for (uint64_t j = 0; j < n_out * (T - lay.usable); j++)
+            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
+                return fail(ctx, KZG_E_ARG, "expr: tail scalars must be canonical (< r)");
+    } else if (lay.tail_be32) {
+        return fail(ctx, KZG_E_ARG, "expr: tail_be32 must be null in the plain layout (usable = 0)");
+    }
+    if (n_out)
+        if (int rc2 = rows_reserve(ctx, "expr", pend, (size_t)n_out * T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    uint64_t nonzero[KZG_MAX_BATCH_OPEN], first[KZG_MAX_BATCH_OPEN];
+    rc = rows_expr_dev(ctx, H, i, it, n_exprs, plan, is_check, n_out, T, n_out ? pend.buf.as<uint32_t>() : nullptr, c48, nonzero,
+                       first, lay.usable ? &lay : nullptr);
+    if (rc) return rc;
+    if (n_out) memcpy(out_commitments48, c48, 48 * (size_t)n_out);
+    memcpy(out_nonzero, nonzero, 8 * (size_t)n_exprs);
+    memcpy(out_first, first, 8 * (size_t)n_exprs);
+    *out_handle = n_out ? rows_insert(ctx, pend, i, n_out, T) : 0;
+    return KZG_OK;
+}
+
 // The check of a _sel builder's selector arguments (SelCall, rows_impl.h): sel_index[l] is KZG_NO_SELECTOR or indexes the
 // concatenated rows of the sel_handles sets, which must be of the call's worker and row length.  The distinct rows named go
 // into sp (a row that serves several lookups is transformed once).
@@ -1770,6 +1861,12 @@ int kzg_rows_commit_derived(kzg_ctx* ctx, uint32_t n_input_handles, const uint64
                             uint64_t* out_counts, uint64_t* out_handle) {
     return rows_derived(ctx, UINT32_MAX, n_input_handles, input_handles, n_ops, ops, opts, out_commitments48, out_counts,
                         out_handle);
+}
+int kzg_rows_commit_expr(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
+                         const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48, uint64_t* out_nonzero,
+                         uint64_t* out_first, uint64_t* out_handle) {
+    return rows_expr(ctx, UINT32_MAX, n_input_handles, input_handles, n_exprs, exprs, opts, out_commitments48, out_nonzero,
+                     out_first, out_handle);
 }
 int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_table_handles,
                                const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups, uint32_t width,

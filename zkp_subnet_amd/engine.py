@@ -767,6 +767,60 @@ class HipEngine:
                                                     c, cnt, ctypes.byref(h)))
         return RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]), [int(v) for v in cnt]
 
+    # ---- a set built from sets: columns that are plain arithmetic in resident columns, and gates checked row by row
+    def commit_expr(self, input_sets: Sequence[object], exprs: Sequence[Sequence], usable: Optional[int] = None,
+                    tail: Sequence[bytes] = ()) -> Tuple[Optional["RowSet"], List[int], List[Optional[int]]]:
+        """kzg_rows_commit_expr over the concatenated rows of input_sets (RowSet objects or bare handles).  exprs: a list of
+        (terms,) or (terms, check) entries; terms as in commit_quotient_ext: (32-byte coefficient, factors) per term, a factor a
+        row index or a (row, rot) pair, at most KZG_MAX_EXPR_FACTORS per term; v[t] = sum_u c_u prod_f col[(t + rot) mod T].  An
+        entry with check = True is evaluated and counted only.  Returns (the new RowSet of the committed expressions in their
+        order, or None when every entry is a check; per entry the number of non-zero cells among the rows evaluated; per
+        entry the smallest such row, or None).  usable = None evaluates all T rows; otherwise only rows [0, usable) and row
+        usable + s of committed column c takes tail[c * (T - usable) + s] (32 bytes each, column-major; no closing row)."""
+        what = "commit_expr"
+        ni, hi = self._handle_array(input_sets, what)
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: {why}")   # noqa: E731
+        exprs = list(exprs) if isinstance(exprs, (list, tuple)) else None
+        if not exprs or len(exprs) > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"exprs must be a list of 1 .. {_native.KZG_MAX_BATCH_OPEN} entries")
+        arr, keep, checks = (_native.Expr * len(exprs))(), [], []
+        for e, ent in enumerate(exprs):
+            if not isinstance(ent, (list, tuple)) or len(ent) not in (1, 2) or (len(ent) == 2 and not isinstance(ent[1], bool)):
+                raise bad("an entry of exprs is (terms,) or (terms, check) with check a bool")
+            try:
+                tt = []
+                for c, factors in ent[0]:
+                    if any(isinstance(f, (tuple, list)) and len(f) != 2 for f in factors):
+                        raise ValueError("a factor is a row index or a (row, rot) pair")
+                    tt.append((bytes(c), [(int(f[0]), int(f[1])) if isinstance(f, (tuple, list)) else (int(f), 0) for f in factors]))
+            except (TypeError, ValueError) as ex:
+                raise bad(f"malformed terms: {ex!r}") from ex
+            if not 1 <= len(tt) <= _native.KZG_MAX_GATE_TERMS or any(
+                    len(c) != 32 or len(fs) > _native.KZG_MAX_EXPR_FACTORS for c, fs in tt):
+                raise bad(f"an expression has 1 .. {_native.KZG_MAX_GATE_TERMS} terms of a 32-byte coefficient and at most "
+                          f"{_native.KZG_MAX_EXPR_FACTORS} factors")
+            flat = [f for _, fs in tt for f in fs]
+            if any(not 0 <= j < 1 << 32 or not -(1 << 31) <= rot < 1 << 31 for j, rot in flat):
+                raise bad("row indices must be non-negative integers below 2^32 and rotations must fit an int32")
+            lens = (ctypes.c_uint32 * len(tt))(*[len(fs) for _, fs in tt])
+            rows_arr = (ctypes.c_uint32 * max(len(flat), 1))(*[j for j, _ in flat])
+            rots_arr = (ctypes.c_int32 * max(len(flat), 1))(*[rot for _, rot in flat])
+            check = len(ent) == 2 and ent[1]
+            arr[e] = _native.Expr(_native.QuotientTerms(len(tt), b"".join(c for c, _ in tt), lens, rows_arr, rots_arr),
+                                  _native.KZG_EXPR_CHECK if check else 0)
+            keep.append((lens, rows_arr, rots_arr))   # the arrays live as long as the structures that point at them
+            checks.append(check)
+        n_out = checks.count(False)
+        wi, T, lay = self._column_layout(what, input_sets, n_out, "n_out", "evaluated", usable, tail)
+        opts = _native.ExprOpts(*lay) if lay else None
+        c, h = ctypes.create_string_buffer(48 * max(n_out, 1)), ctypes.c_uint64(0)
+        nz, first = (ctypes.c_uint64 * len(exprs))(), (ctypes.c_uint64 * len(exprs))()
+        self._chk(self._lib.kzg_rows_commit_expr(self._h, ni, hi, len(exprs), arr, ctypes.byref(opts) if opts is not None else None,
+                                                 c if n_out else None, nz, first, ctypes.byref(h)))
+        del keep
+        rs = RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]) if n_out else None
+        return rs, [int(v) for v in nz], [None if int(v) == _native.KZG_EXPR_NONE else int(v) for v in first]
+
     # ---- a third set built from sets: the PLONK quotient (round 3), computed and committed on the device
     def commit_quotient(self, sets: Sequence[object], terms: Sequence[Tuple[bytes, Sequence[int]]], perm: Optional[dict] = None,
                         ext_log: int = 2, n_pieces: int = 3) -> "RowSet":
