@@ -728,8 +728,9 @@ int kzg_rows_commit_sorted(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_
  * outside {1, 2} on INV0; usable >= T; T - usable > KZG_MAX_BLIND_ROWS; a tail with usable = 0, or none with usable > 0; a tail
  * scalar >= r.  The source sets are only read; a release or an SRS load racing the call follows the rules of kzg_rows_open.
  * Thread-safe like every call; after any error the context keeps serving.
- * OUT OF SCOPE: per-row selectors; signed limbs or limbs in a base that is no power of two; halo2's running-sum decomposition
- * along the rows.  (General expression rows, sum_u c_u prod rows[rot] committed as a column: kzg_rows_commit_expr below.)
+ * OUT OF SCOPE: per-row selectors; signed limbs or limbs in a base that is no power of two.  (halo2's running-sum decomposition
+ * along the rows: kzg_rows_commit_recurrence below, z' = (z - k) 2^-K as a recurrence.  General expression rows, sum_u c_u prod
+ * rows[rot] committed as a column: kzg_rows_commit_expr below.)
  * SOUNDNESS: nothing here is a proof.  The derived rows are prover data; the argument is the caller's gates (x inv0 = 1 - bit
  * and x bit = 0; x = sum_l 2^(b l) limb_l) and the lookup of the limbs, with every challenge drawn AFTER these commitments are
  * fixed.  The library derives no challenge and draws no randomness: the tail must be fresh per proof. */
@@ -783,8 +784,9 @@ int kzg_rows_commit_derived(kzg_ctx* ctx, uint32_t n_input_handles, const uint64
  * term_lens, or term_rows when some term has a factor); T > 2^32 (the prepared rotations are 32-bit words); and the usable and
  * tail refusals of kzg_rows_commit_derived.
  * OUT OF SCOPE: division or an inverse inside an expression (compose with KZG_DERIVE_INV0); per-row selectors other than as an
- * ordinary factor; more than KZG_MAX_GATE_TERMS terms (split the expression and add the parts with a further call); the
- * running-sum decomposition along the rows (row t + 1 of the OUTPUT depending on row t of the output).
+ * ordinary factor; more than KZG_MAX_GATE_TERMS terms (split the expression and add the parts with a further call).  (The
+ * running-sum decomposition along the rows, row t + 1 of the OUTPUT depending on row t of the output: kzg_rows_commit_recurrence
+ * below.)
  * SOUNDNESS: nothing here is a proof.  An expression column is prover data: the argument is the caller's gate in the quotient
  * (kzg_rows_commit_quotient*), with every challenge that enters a coefficient drawn after the commitments it depends on are
  * fixed.  A zero count of a check is a convenience for the prover -- it tells where a witness is wrong before the quotient
@@ -805,6 +807,61 @@ int kzg_rows_commit_expr(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t*
                          uint32_t n_exprs, const kzg_expr* exprs, const kzg_expr_opts* opts /* NULL: plain */,
                          uint8_t* out_commitments48 /* n_out * 48 */, uint64_t* out_nonzero /* n_exprs */,
                          uint64_t* out_first /* n_exprs */, uint64_t* out_handle);
+/* THE RECURRENCE COLUMNS: a set built FROM sets, every output column a running value along the rows whose step is plain
+ * arithmetic in columns that are already resident -- the running-sum range decomposition z' = (z - k) 2^-K, a random-linear-
+ * combination or Horner accumulator acc' = acc r + byte, a running count or sum, a custom running product, and, where a selector
+ * makes the multiplier 0, any of these restarted per segment.  The concatenated rows of the input_handles sets are the source
+ * columns, with the handle, worker and T rules of kzg_rows_commit_expr.  Recurrence e has a multiplier expression mul, an addend
+ * expression add and a start; mul and add are kzg_quotient_terms in exactly the format and with the caps of an expression of
+ * kzg_rows_commit_expr (at most KZG_MAX_GATE_TERMS terms of at most KZG_MAX_EXPR_FACTORS factors, term_rots NULL: every
+ * rotation 0), except that n_terms = 0 is allowed: an empty mul is A = 1, an empty add is B = 0; both empty is refused.  With
+ * n = T in the plain layout and n = usable otherwise,
+ *   v[0] = start,   v[t + 1] = A[t] v[t] + B[t]   for 0 <= t < n,
+ * A[t] and B[t] the values of the two expressions at row t as kzg_rows_commit_expr defines them: a rotated factor reads the
+ * source cell it lands on, also at or behind `usable`; nothing is read on behalf of a row t >= n.  A zero multiplier is never
+ * an error: the value restarts at the addend.  Any start below r is legal, 0 included.
+ * PLAIN LAYOUT (opts NULL, or usable = 0; tail_be32 must be NULL): rows 0 .. T - 1 hold v[0] .. v[T - 1]; out_closings32[e] is
+ * v[T], the wrap-around value, 32 big-endian bytes.  It equals start exactly when the cyclic relation v(w X) = A v + B holds on
+ * all of H.
+ * USABLE LAYOUT (that of the _zk builders, not of kzg_rows_commit_derived / _expr: a running value needs its closing row):
+ * 1 <= usable <= T - 1 and T - usable <= KZG_MAX_BLIND_ROWS; rows 0 .. usable hold v[0] .. v[usable]; row `usable` is the
+ * closing row and its value is also returned; row usable + 1 + s of column e takes tail_be32[e * (T - usable - 1) + s],
+ * canonical scalars, column-major over the recurrences; tail_be32 may be NULL only when usable = T - 1.
+ * The n_recs recurrences form, in their order, the rows of ONE new set of the same worker and length; out_commitments48[e]
+ * equals kzg_rows_commit(i, n_recs, the T evaluations, T, 1, ..)[e] byte for byte, and *out_handle opens, evaluates, combines,
+ * releases, goes stale and counts against KZG_MAX_ROW_SETS (KZG_E_BUSY; KZG_E_NOMEM on a failed allocation, the lane's
+ * workspace included) like any other.  A recurrence cannot name another recurrence's output of the same call: compose with a
+ * second call.  Each distinct source row named is transformed forward once; nothing row-sized crosses the host link: starts
+ * and tails ride in kernel arguments, the closings come back in the copy behind the MSM.
+ * WORKSPACE per call: (distinct source rows named + 3) vectors of T elements (A, B and one output vector, reused by every
+ * recurrence) and 2 (ceil(n / 4) 3 / 2 + 64) elements for the stacked levels of the scan, 32 bytes per element.
+ * Thread safety and "after any error the context keeps serving" are those of kzg_rows_commit_expr.  KZG_E_ARG with a message
+ * that begins "recur:" and names the cause: n_recs outside [1, KZG_MAX_BATCH_OPEN]; both expressions of a recurrence empty;
+ * n_terms above KZG_MAX_GATE_TERMS; a term of more than KZG_MAX_EXPR_FACTORS factors; a row index at or beyond the
+ * concatenation; a coefficient or a start >= r (checked on the HOST, before any lane is taken: an argument error, not a queued
+ * failure); a NULL array (start_be32; coeffs_be32 or term_lens of a non-empty expression; term_rows when some term has a
+ * factor); T > 2^32; and the usable and tail refusals of the _zk builders.
+ * OUT OF SCOPE: second-order recurrences (v[t + 2] from v[t + 1] and v[t]; carry the pair in two columns of a later call, or
+ * on the host); a recurrence that runs across calls other than by handing the closing value on as the next `start`; division
+ * or an inverse inside a step (compose with KZG_DERIVE_INV0).
+ * SOUNDNESS: nothing here is a proof.  The column is prover data: the argument is the caller's gate v(w X) - A v - B in the
+ * quotient (kzg_rows_commit_quotient_ext with a rotated factor), restricted to the usable rows where there are blinding rows,
+ * plus the boundary gate L_0 (v - start), with every challenge that enters a coefficient drawn after the commitments it depends
+ * on are fixed.  A closing value is a convenience for the prover and convinces no verifier.  The library derives no challenge
+ * and draws no randomness: the tail must be fresh per proof. */
+typedef struct kzg_recurrence {
+    kzg_quotient_terms mul;                 /* the multiplier A; n_terms = 0: A = 1 */
+    kzg_quotient_terms add;                 /* the addend B; n_terms = 0: B = 0 */
+    const uint8_t* start_be32;              /* v[0]: one canonical scalar, 32 bytes */
+} kzg_recurrence;
+typedef struct kzg_recurrence_opts {
+    uint64_t usable;           /* 0: plain layout; else rows 0 .. usable hold v[0] .. v[usable] */
+    const uint8_t* tail_be32;  /* n_recs * (T - usable - 1) * 32, column-major; NULL when usable == 0 or usable == T - 1 */
+} kzg_recurrence_opts;
+int kzg_rows_commit_recurrence(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                               uint32_t n_recs, const kzg_recurrence* recs, const kzg_recurrence_opts* opts /* NULL: plain */,
+                               uint8_t* out_commitments48 /* n_recs * 48 */, uint8_t* out_closings32 /* n_recs * 32 */,
+                               uint64_t* out_handle);
 /* THE QUOTIENT WITH LOOKUP SELECTORS: kzg_rows_commit_quotient_zk and kzg_rows_quotient_part for lookups that are enabled on
  * some rows only.  selectors->selector_rows holds L = lookup->n_lookups entries, each a row index into the call's concatenated
  * rows (the caller's fixed column q_l, the row that kzg_rows_commit_multiplicities_sel / _lookup_sum_sel read) or
@@ -1159,6 +1216,10 @@ int kzg_multi_rows_commit_derived(kzg_multi* mh, uint32_t i, uint32_t n_input_ha
 int kzg_multi_rows_commit_expr(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                uint32_t n_exprs, const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48,
                                uint64_t* out_nonzero, uint64_t* out_first, uint64_t* out_handle);
+/* kzg_rows_commit_recurrence on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_recurrence(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                     uint32_t n_recs, const kzg_recurrence* recs, const kzg_recurrence_opts* opts,
+                                     uint8_t* out_commitments48, uint8_t* out_closings32, uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

@@ -115,4 +115,6 @@ int kzg_vk_pairing(const uint8_t p_be96[96], const uint8_t q_be192[192], uint8_t
 #ifdef __cplusplus
 }
 #endif
+/* the plan hooks of the recurrence scan (csrc/fr_recur.hip), declared in a file of their own */
+#include "kzg_mi355x_recur_test.h"
 #endif /* KZG_MI355X_TEST_H */

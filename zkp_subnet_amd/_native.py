@@ -103,6 +103,16 @@ class ExprOpts(ctypes.Structure):
     _fields_ = [("usable", _U64), ("tail_be32", _B)]
 
 
+class Recurrence(ctypes.Structure):
+    """kzg_recurrence"""
+    _fields_ = [("mul", QuotientTerms), ("add", QuotientTerms), ("start_be32", _B)]
+
+
+class RecurrenceOpts(ctypes.Structure):
+    """kzg_recurrence_opts"""
+    _fields_ = [("usable", _U64), ("tail_be32", _B)]
+
+
 class QuotientLink(ctypes.Structure):
     """kzg_quotient_link"""
     _fields_ = [("prev_row", _U32), ("rot", ctypes.c_int32)]
@@ -151,6 +161,8 @@ SYMBOLS = {
                                      ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_expr": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,
                                   ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_recurrence": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Recurrence),
+                                        ctypes.POINTER(RecurrenceOpts), _B, _B, ctypes.POINTER(_U64)]),
     "kzg_rows_commit_lookup_sum": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B, _B, _B, _B,
                                         ctypes.POINTER(_U64)]),
     "kzg_rows_commit_multiplicities": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _B,
@@ -258,6 +270,8 @@ SYMBOLS = {
                                            ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_expr": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,
                                         ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_recurrence": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Recurrence),
+                                              ctypes.POINTER(RecurrenceOpts), _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_lookup_sum": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B,
                                               _B, _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_multiplicities": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32,
@@ -332,6 +346,13 @@ SYMBOLS = {
     "kzg_test_poly_run": (_I, [_P, _I, _I, ctypes.c_int64, _I, _I, _P, _U64, _U32, _I, _P, _P, _U32, _P, _P, _U32, _P, _P]),
 }
 
+# the plan hooks of the recurrence scan (include/kzg_mi355x_recur_test.h, which kzg_mi355x_test.h includes): bound like SYMBOLS
+RECUR_HOOKS = {
+    "kzg_test_recur_plan_of": (_I, [_U64, _I, ctypes.c_int64, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_U64),
+                                    ctypes.POINTER(_U64)]),
+    "kzg_test_recur_run": (_I, [_P, _I, ctypes.c_int64, _P, _P, _P, _U64, _P, _P]),
+}
+
 _lib = None
 
 
@@ -386,7 +407,7 @@ def load() -> ctypes.CDLL:
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback."
             )
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(RECUR_HOOKS.items()):
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -731,6 +731,55 @@ class Client:
                 "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments],
                 "nonzero": nonzero, "first": first}
 
+    # ---- running values along the rows, v[t + 1] = A[t] v[t] + B[t] with A and B expressions in resident columns, on the device
+    @_guard
+    def worker_commit_recurrence(self, input_handles: Sequence[int], recs: Sequence[Sequence], usable: Optional[int] = None,
+                                 tail: Sequence[str] = ()):
+        """Extension: first-order recurrence columns over the rows of the input_handles sets, built on the device: v[0] = start,
+        v[t + 1] = A[t] v[t] + B[t].  recs: a list of [mul_terms, add_terms, start] entries; both term lists as in
+        worker_commit_expr ([coefficient, [factors]] per term, a factor a row index or a [row, rot] pair, at most 8 factors per
+        term and 16 terms); an empty mul_terms is A = 1, an empty add_terms is B = 0, both empty is refused.  A zero multiplier
+        restarts the value at the addend.  The recurrences become, in their order, the rows of ONE new set.  usable = null: rows
+        0 .. T - 1 hold v[0] .. v[T - 1] and `closings` holds v[T], which equals start exactly when the relation holds cyclically;
+        otherwise rows 0 .. usable hold v[0] .. v[usable], the last of them the closing value, and row usable + 1 + s of column c
+        is tail[c * (T - usable - 1) + s].  Returns the handle, the commitments and the closings.  Nothing here is a proof: the
+        column is prover data and the argument is the caller's gate v(wX) - A v - B in the quotient plus the boundary gate."""
+        what = "worker_commit_recurrence"
+        hs = _handles(input_handles)
+
+        def side(terms):
+            if any(isinstance(f, (tuple, list)) and len(f) != 2 for _, fs in terms for f in fs):
+                raise ValueError("a factor is a row index or a [row, rot] pair")
+            return [(codec.fr_to_be32(c), [(int(f[0]), int(f[1])) if isinstance(f, (tuple, list)) else (int(f), 0) for f in fs])
+                    for c, fs in terms]
+        try:
+            rr = []
+            for ent in recs:
+                if isinstance(ent, (str, bytes)) or len(ent) != 3:
+                    raise ValueError(f"an entry is [mul_terms, add_terms, start]: {ent!r}")
+                rr.append((side(ent[0]), side(ent[1]), codec.fr_to_be32(ent[2])))
+        except (TypeError, ValueError, IndexError, KeyError) as e:
+            raise codec.CodecError(f"{what}: recs must be a list of [mul_terms, add_terms, start] with terms a list of "
+                                   f"[coefficient, [factors]]: {e!r}") from e
+        if not rr:
+            raise codec.CodecError(f"{what}: recs must not be empty")
+        if any(not m and not a for m, a, _ in rr):
+            raise codec.CodecError(f"{what}: mul_terms and add_terms must not both be empty")
+        if any(int.from_bytes(c, "big") >= codec.R_MODULUS for m, a, _ in rr for c, _ in m + a) or any(
+                int.from_bytes(st, "big") >= codec.R_MODULUS for _, _, st in rr):
+            raise codec.CodecError(f"{what}: coefficients and starts must be canonical scalars (< r)")
+        if usable is None:
+            if tail:
+                raise codec.CodecError(f"{what}: a tail needs usable (null: the plain layout)")
+            tb = []
+        else:
+            usable, tb = self._blind(what, usable, tail)
+            if usable == 0:
+                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: the plain layout)")
+        rs, closings = self.engine.commit_recurrence(hs, rr, usable, tb)
+        return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
+                "closings": [codec.be32_to_fr(c) for c in closings]}
+
     @staticmethod
     def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: Sequence[int], n_groups: int, width: int,
                                theta: str, gamma: str, coeff: str, active_row: Optional[int] = None,

@@ -599,6 +599,78 @@ int kzg_test_poly_run(kzg_ctx* ctx, int form, int l0, int64_t scan_max, int scan
     return KZG_OK;
 }
 
+// ---- the recurrence scan's plans (tests/test_recurrence_cpu.py, tests/test_gpu_recur_plans.py)
+// both parameters -1: the plan the launcher picks itself; otherwise the caller's, both taken as given
+static const char* recur_plan_from(uint64_t n, int l0, int64_t top_max, RecurPlan* pl) {
+    if (!n) return "recur plan: no rows";
+    if (l0 == -1 && top_max == -1) *pl = recur_plan(n);
+    else *pl = recur_plan_levels(n, l0, top_max < 0 ? 0 : (uint64_t)top_max);
+    return recur_plan_invalid(*pl, n);
+}
+int kzg_test_recur_plan_of(uint64_t n, int l0, int64_t top_max, int* out_K, int* out_l, uint64_t* out_n, uint64_t* out_off) {
+    if (!out_K || !out_l || !out_n || !out_off) return fail(nullptr, KZG_E_ARG, "recur plan: null output");
+    RecurPlan pl;
+    if (const char* why = recur_plan_from(n, l0, top_max, &pl)) return fail(nullptr, KZG_E_ARG, why);
+    for (int k = 0; k <= pl.K; k++) {
+        out_l[k] = k < pl.K ? pl.l[k] : 0;    // (level K is the top kernel's: it folds nothing into a further level)
+        out_n[k] = pl.n[k];
+        out_off[k] = pl.off[k];
+    }
+    *out_K = pl.K;
+    return KZG_OK;
+}
+#define KZG_TEST_RECUR_MAX_N ((uint64_t)1 << 22)   // steps per plan-hook call (as KZG_TEST_POLY_MAX_N)
+int kzg_test_recur_run(kzg_ctx* ctx, int l0, int64_t top_max, const uint8_t* a_be32, const uint8_t* b_be32,
+                       const uint8_t start_be32[32], uint64_t n, uint8_t* out_v_be32, uint8_t* out_closing_be32) {
+    // the plan is judged first, with no context and no device: nothing invalid reaches a kernel
+    RecurPlan pl;
+    if (const char* why = recur_plan_from(n, l0, top_max, &pl)) return fail(ctx, KZG_E_ARG, why);
+    if (n > KZG_TEST_RECUR_MAX_N) return fail(ctx, KZG_E_ARG, "recur run: at most 2^22 steps");
+    if (!ctx || !a_be32 || !b_be32 || !start_be32 || !out_v_be32 || !out_closing_be32)
+        return fail(ctx, KZG_E_ARG, "recur run: no context or no data");
+    static const uint8_t R_BE[32] = {0x73, 0xED, 0xA7, 0x53, 0x29, 0x9D, 0x7D, 0x48, 0x33, 0x39, 0xD8, 0x08, 0x09, 0xA1, 0xD8, 0x05,
+                                     0x53, 0xBD, 0xA4, 0x02, 0xFF, 0xFE, 0x5B, 0xFE, 0xFF, 0xFF, 0xFF, 0xFF, 0x00, 0x00, 0x00, 0x01};
+    if (memcmp(start_be32, R_BE, 32) >= 0)   // (the serving call checks its starts on the host too; the kernel takes them as canonical)
+        return fail(ctx, KZG_E_ARG, "recur run: start must be canonical (< r)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;
+    Lane& L = H.L();
+    prof_begin(ctx, L);
+    int rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    hipStream_t s = L.stream;
+    HIPCHK(ctx, L.coeffA.ensure(n * 32));
+    HIPCHK(ctx, L.coeffB.ensure(n * 32));
+    HIPCHK(ctx, L.qbuf.ensure(n * 32));
+    HIPCHK(ctx, L.hbuf.ensure(recur_level_elems(n) * 32));
+    HIPCHK(ctx, L.hnext.ensure(recur_level_elems(n) * 32));
+    HIPCHK(ctx, L.scal.ensure(64));
+    HIPCHK(ctx, L.out_be.ensure(n * 32));
+    uint32_t *a = L.coeffA.as<uint32_t>(), *b = L.coeffB.as<uint32_t>(), *v = L.qbuf.as<uint32_t>();
+    rc = upload_fr(ctx, L, a_be32, n, a, 1);
+    if (rc) return rc;
+    rc = upload_fr(ctx, L, b_be32, n, b, 1);
+    if (rc) return rc;
+    // whatever a kernel fails to write must show: the values and the level scratch start from a pattern that is no result
+    HIPCHK(ctx, hipMemsetAsync(L.qbuf.p, 0xff, n * 32, s));
+    HIPCHK(ctx, hipMemsetAsync(L.hbuf.p, 0xff, recur_level_elems(n) * 32, s));
+    HIPCHK(ctx, hipMemsetAsync(L.hnext.p, 0xff, recur_level_elems(n) * 32, s));
+    {
+        Span sp(ctx, L, KZG_T_POLY);
+        launch_recur_scan(s, pl, a, b, n, L.hbuf.as<uint32_t>(), L.hnext.as<uint32_t>(), start_be32, v, L.scal.as<uint8_t>(), nullptr);
+    }
+    // the words as the kernels left them, taken out of Montgomery form WITHOUT a reduction check: an unwritten cell (all ones)
+    // comes back as a value that no reference holds
+    launch_fr_to_be(s, v, L.out_be.as<uint8_t>(), n, 1);
+    rc = finish(ctx, L);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpy(out_v_be32, L.out_be.p, n * 32, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(out_closing_be32, L.scal.p, 32, hipMemcpyDeviceToHost));
+    H.clean = true;
+    return KZG_OK;
+}
+
 // ---- the MSM passes of a multi-row call (tests/test_msm_passes_cpu.py)
 int kzg_test_msm_passes(int c, int long_rows, uint32_t k, uint32_t m, uint32_t* out5, int* out_passes) {
     if (!out5 || !out_passes) return fail(nullptr, KZG_E_ARG, "msm passes: null output");

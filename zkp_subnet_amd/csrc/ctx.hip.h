@@ -8,6 +8,7 @@
 //   serve.hip     the serving entry points: commit / open / msm / ntt / eval, resident slots, tickets, sums
 //   fr_derive.hip the kernels of kzg_rows_commit_derived: inverse-or-zero around the batched inversion, limb decomposition
 //   fr_expr.hip   the kernel of kzg_rows_commit_expr: sums of products of rotated resident columns on H, counted and stored
+//   fr_recur.hip  the scan of kzg_rows_commit_recurrence: v[t + 1] = A[t] v[t] + B[t] as a ladder over affine maps
 //   comm.hip      the library's own RCCL collective (kzg_comm_*, kzg_msm_sharded, the stream-chained pair)
 //   abi_test.hip  unit-op test hooks (include/kzg_mi355x_test.h)
 // No CPU arithmetic fallback exists anywhere here: if HIP fails, the call fails.
@@ -486,6 +487,18 @@ int rows_derived_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs
 int rows_expr_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_exprs, const ExprPlan* exprs,
                   const uint8_t* is_check, uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_nonzero,
                   uint64_t* out_first, const Blind* lay);
+// one recurrence of kzg_rows_commit_recurrence: v[0] = start, v[t + 1] = mul[t] v[t] + add[t]; a side with n_terms = 0 is empty
+// (mul: the constant 1, add: the constant 0); the rest of each side as the caller of rows_expr_dev checks an expression
+struct RecurSpec {
+    ExprPlan mul, add;
+    const uint8_t* start_be32;   // a canonical scalar, 32 big-endian HOST bytes
+};
+// the n_recs recurrences into a new n_recs-row set's buffer dst: their commitments and closing values (32 big-endian bytes
+// each).  lay (null: rows 0 .. T - 1 hold v[0] .. v[T - 1] and the closing value is v[T]): the _zk layout -- rows 0 .. usable
+// hold v[0] .. v[usable], the last of them the closing value, and row usable + 1 + s of column c takes
+// tail_be32[c * (T - usable - 1) + s] (checked by the caller as blind_check does, over n_recs columns)
+int rows_recur_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_recs, const RecurSpec* recs, uint64_t T,
+                   uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, const Blind* lay);
 // the quotient pieces of the constraints qp over the n_rows coefficient rows of rt into a new n_pieces-row set's buffer dst:
 // their commitments, and whether a coefficient of t at or above n_pieces T was not zero (the caller creates no set)
 int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t n_rows, uint64_t T, const QuotPlan& qp,

@@ -313,6 +313,35 @@ struct ExprPlan {
 // *first <- min(*first, the smallest such t).  out must not alias a source (a rotated factor reads other cells)
 void launch_expr(hipStream_t s, const RowTab& src, const ExprPlan& ep, uint32_t* out_or_null, uint64_t T, uint64_t n,
                  uint64_t* nonzero, uint64_t* first);
+// ---- the first-order recurrence columns of kzg_rows_commit_recurrence (fr_recur.hip): v[0] = start, v[t + 1] = A[t] v[t] + B[t]
+// for t < n over two vectors of canonical Montgomery elements, as a scan of affine maps.  "Plan, then run", as the opening scan:
+// level 0 is the vectors themselves, level k folds chunks of 2^l[k] of its n[k] maps (2^l0 at level 0, 16 above) into level
+// k + 1, which starts at element off[k + 1] of BOTH scratch arrays, until at most top_max maps are left for the one workgroup of
+// the top kernel (K = 0: the vectors go to it directly).  recur_plan is what the launcher picks (l0 = 2 below 2^17, 3 below
+// 2^18, else 4; RECUR_TOP_MAX), recur_plan_levels a caller's choice, recur_plan_invalid the kernels' preconditions (null:
+// valid): l0 in 2 .. 4, 1 <= top_max <= RECUR_TOP_MAX, at most RECUR_MAX_LEVELS levels, the stacked levels inside
+// recur_level_elems(n).  The overload that takes a plan runs it unchecked.
+#define RECUR_TOP_MAX 2048
+#define RECUR_MAX_LEVELS 14
+struct RecurPlan {
+    int l0, lup, K;
+    uint64_t top_max;
+    int l[16];
+    uint64_t n[16], off[16];
+};
+// elements of EACH of the two scratch arrays: the stacked levels above level 0, sized as the other scans size theirs
+inline uint64_t recur_level_elems(uint64_t n) { return poly_level_words(n) / 8; }
+RecurPlan recur_plan(uint64_t n);
+RecurPlan recur_plan_levels(uint64_t n, int l0, uint64_t top_max);
+const char* recur_plan_invalid(const RecurPlan& pl, uint64_t n);
+// out[t] <- v[t] for t < n (canonical; out must not alias A or B); closing_be (device) <- v[n] as 32 big-endian bytes;
+// close_row (device, null: none) <- v[n] as a canonical Montgomery element.  A and B are only read; scrA, scrB:
+// recur_level_elems(n) elements each; start_be32: a canonical scalar as 32 big-endian HOST bytes (the caller's check; a kernel
+// argument).  1 <= n <= 2^32
+void launch_recur_scan(hipStream_t s, const uint32_t* A, const uint32_t* B, uint64_t n, uint32_t* scrA, uint32_t* scrB,
+                       const uint8_t start_be32[32], uint32_t* out, uint8_t* closing_be, uint32_t* close_row);
+void launch_recur_scan(hipStream_t s, const RecurPlan& pl, const uint32_t* A, const uint32_t* B, uint64_t n, uint32_t* scrA,
+                       uint32_t* scrB, const uint8_t start_be32[32], uint32_t* out, uint8_t* closing_be, uint32_t* close_row);
 // ---- blinding rows (fr_blind.hip; the kzg_rows_commit_*_zk builders): rows [usable, n) of evaluation vectors of n Montgomery
 // elements, n - usable <= BLIND_MAX_ROWS (= KZG_MAX_BLIND_ROWS)
 #define BLIND_MAX_ROWS 32

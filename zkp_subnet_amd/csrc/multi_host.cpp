@@ -486,6 +486,14 @@ int kzg_multi_rows_commit_expr(kzg_multi* mh, uint32_t i, uint32_t n_input_handl
                                    out_first, out_handle);
     });
 }
+int kzg_multi_rows_commit_recurrence(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                     uint32_t n_recs, const kzg_recurrence* recs, const kzg_recurrence_opts* opts,
+                                     uint8_t* out_commitments48, uint8_t* out_closings32, uint64_t* out_handle) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_recurrence(c, s, n_input_handles, input_handles, n_recs, recs, opts, out_commitments48,
+                                         out_closings32, out_handle);
+    });
+}
 int kzg_multi_rows_commit_lookup_sum(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                      uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
                                      uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32],

@@ -1216,6 +1216,88 @@ int rows_expr_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, u
     return KZG_OK;
 }
 
+// The first-order recurrence columns (kzg_rows_commit_recurrence): a set built FROM sets, every output column a running value
+// v[t + 1] = A[t] v[t] + B[t] whose multiplier A and addend B are expressions in source rows.  Sources as in rows_expr_dev: each
+// DISTINCT source row that some term names is transformed forward once.
+//   step                      launches                         per call
+//   forward transforms        launch_fr_ntt                    one per distinct source row named
+//   A and B                   launch_expr (k_expr, unchanged)  two per recurrence; an empty side is the constant 1 / 0
+//   the scan                  launch_recur_scan                K folds, one top kernel, K walks per recurrence
+//   tail                      launch_blind_tail                one per recurrence, with `usable` < T - 1 only
+//   inverse transform         row_to_coeffs                    one per recurrence, straight into dst
+//   commit                    multi_msms_finish                ONE pass of n_recs scalar sets
+// A, B and the output are three scratch vectors that every recurrence reuses; the stream orders the work.  The scan writes the
+// closing value of recurrence c into evaluation slot c of the record (and, in the usable layout, into row `usable` of the
+// output); the closings come back in the record's copy behind the MSM: the call never waits on its own.  launch_expr's two
+// counters go to two spare words behind the last closing slot and are not read.
+// Workspace: distinct sources + 3 vectors of T, and 2 recur_level_elems(n) elements of level scratch.
+int rows_recur_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_recs, const RecurSpec* recs, uint64_t T,
+                   uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, const Blind* lay) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const int lg = ilog2_exact(T);
+    uint32_t* tw = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
+    const uint64_t vw = T * 8;                        // one vector, in words
+    const uint64_t n = lay ? lay->usable : T;         // the steps of the recurrence: rows 0 .. n - 1 are v[0] .. v[n - 1]
+    constexpr uint32_t DUMP_OFF = 32 * KZG_MAX_BATCH_OPEN;   // launch_expr's counters, behind the closings
+    static_assert(DUMP_OFF + 16 <= MR_PAIRS * 32 && KZG_MAX_BATCH_OPEN <= POLY_MAX_ROWS,
+                  "the closing of every recurrence and the two spare words fit the record's evaluation slots");
+    static_assert(KZG_MAX_GATE_TERMS == EXPR_MAX_TERMS && KZG_MAX_EXPR_FACTORS == EXPR_MAX_FACTORS, "the header's caps are the kernel's");
+    static const uint8_t ONE_BE[32] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
+    static const uint8_t ZERO_BE[32] = {};
+    const uint32_t* distinct[POLY_MAX_ROWS];
+    uint32_t nd = 0;
+    ExprPlan plan[KZG_MAX_BATCH_OPEN][2];
+    for (uint32_t e = 0; e < n_recs; e++)
+        for (int side = 0; side < 2; side++) {
+            ExprPlan& pl = plan[e][side];
+            pl = side ? recs[e].add : recs[e].mul;
+            if (pl.n_terms == 0) {   // the empty side: the constant 1 (A) or 0 (B), one term without factors
+                memset(&pl, 0, sizeof pl);
+                pl.n_terms = 1;
+                pl.coeffs_be32 = side ? ZERO_BE : ONE_BE;
+            }
+            for (uint32_t u = 0; u < pl.n_terms; u++)
+                for (uint32_t f = 0; f < pl.term_len[u]; f++) {
+                    const uint32_t* p = inputs.r[pl.term_row[u][f]];
+                    uint32_t d = 0;
+                    while (d < nd && distinct[d] != p) d++;
+                    if (d == nd) distinct[nd++] = p;
+                    pl.term_row[u][f] = (uint8_t)d;
+                }
+        }
+    HIPCHK(ctx, A.qext.ensure(((size_t)nd + 3) * T * 32));
+    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    HIPCHK(ctx, A.hbuf.ensure(recur_level_elems(n) * 32));
+    HIPCHK(ctx, A.hnext.ensure(recur_level_elems(n) * 32));
+    uint32_t *src = A.qext.as<uint32_t>(), *va = src + nd * vw, *vb = va + vw, *out = vb + vw, *mid = A.ntt_mid.as<uint32_t>();
+    uint8_t* rec = A.brec.as<uint8_t>();
+    uint64_t* dump = reinterpret_cast<uint64_t*>(rec + MR_EVAL + DUMP_OFF);
+    RowTab st;
+    memset(&st, 0, sizeof(st));
+    for (uint32_t d = 0; d < nd; d++) {
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, distinct[d], src + d * vw, lg, tw, nullptr, mid);
+        st.r[d] = src + d * vw;
+    }
+    HIPCHK(ctx, hipMemsetAsync(dump, 0, 16, A.stream));
+    for (uint32_t e = 0; e < n_recs; e++) {
+        {
+            Span sp(ctx, A, KZG_T_POLY);
+            launch_expr(A.stream, st, plan[e][0], va, T, n, dump, dump + 1);
+            launch_expr(A.stream, st, plan[e][1], vb, T, n, dump, dump + 1);
+            launch_recur_scan(A.stream, va, vb, n, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), recs[e].start_be32, out,
+                              rec + MR_EVAL + 32 * e, lay ? out + 8 * n : nullptr);
+            if (lay) launch_blind_tail(A.stream, out, T, n, lay->tail_be32 + 32 * (size_t)e * (T - n - 1), A.flags());
+        }
+        const uint32_t* cf;
+        if (int rc = row_to_coeffs(ctx, A, out, T, 1, &cf, dst + e * vw)) return rc;
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return multi_msms_finish(ctx, H, i, T, dst, n_recs, 0, n_recs, out_c48, out_closing32, nullptr);
+}
+
 // the quotient's constants of one (T, E), shared by all lanes like the twiddles: built once under the ctx mutex
 static int ensure_quot_consts(kzg_ctx* ctx, Lane& L, int log_t, int ext_log, const uint32_t* tw_n, const uint32_t** qc) {
     std::lock_guard<std::mutex> lk(ctx->mu);

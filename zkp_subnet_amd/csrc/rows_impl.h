@@ -58,6 +58,10 @@ int rows_derived(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, cons
 int rows_expr(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
               const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48, uint64_t* out_nonzero,
               uint64_t* out_first, uint64_t* out_handle);
+// opts: the usable layout (with a closing row) and its tail as the public call takes them (null: the plain layout)
+int rows_recurrence(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_recs,
+                    const kzg_recurrence* recs, const kzg_recurrence_opts* opts, uint8_t* out_commitments48,
+                    uint8_t* out_closings32, uint64_t* out_handle);
 // zk: the blinding rows of the _zk call, the layout of the _sel call.  sc: the selectors of the _sel call
 int rows_lookup_sum(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
                     uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,

@@ -1274,6 +1274,103 @@ int rows_expr(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const u
     return KZG_OK;
 }
 
+// kzg_rows_commit_recurrence: the lookups of an open (one handle list), the reservation of a commit of n_recs rows.  Each side
+// of a recurrence is checked as rows_expr checks an expression, except that it may be empty (not both).  Coefficients and
+// starts are checked here, on the host, before a lane is taken.  opts == NULL, or usable == 0: the plain layout
+int rows_recurrence(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_recs,
+                    const kzg_recurrence* recs, const kzg_recurrence_opts* opts, uint8_t* out_commitments48,
+                    uint8_t* out_closings32, uint64_t* out_handle) {
+    if (!ctx || !input_handles || !out_commitments48 || !out_closings32 || !out_handle) return KZG_E_ARG;
+    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "recur: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (n_recs == 0 || n_recs > KZG_MAX_BATCH_OPEN || !recs)
+        return fail(ctx, KZG_E_ARG, "recur: n_recs must be in [1, KZG_MAX_BATCH_OPEN]");
+    std::vector<RecurSpec> spec(n_recs);
+    std::vector<int32_t> rots((size_t)n_recs * 2 * EXPR_MAX_TERMS * EXPR_MAX_FACTORS, 0);   // as given: reduced mod T once T is known
+    auto rot_at = [&](uint32_t e, int side, uint32_t u, uint32_t f) -> int32_t& {
+        return rots[(((size_t)e * 2 + side) * EXPR_MAX_TERMS + u) * EXPR_MAX_FACTORS + f];
+    };
+    uint32_t max_row = 0;
+    for (uint32_t e = 0; e < n_recs; e++) {
+        memset(&spec[e], 0, sizeof(RecurSpec));
+        if (recs[e].mul.n_terms == 0 && recs[e].add.n_terms == 0)
+            return fail(ctx, KZG_E_ARG, "recur: mul and add must not both be empty (v would be the constant start)");
+        if (!recs[e].start_be32) return fail(ctx, KZG_E_ARG, "recur: start_be32 must not be null");
+        if (!fr_be32_canonical(recs[e].start_be32)) return fail(ctx, KZG_E_ARG, "recur: start must be a canonical scalar (< r)");
+        spec[e].start_be32 = recs[e].start_be32;
+        for (int side = 0; side < 2; side++) {
+            const kzg_quotient_terms& g = side ? recs[e].add : recs[e].mul;
+            ExprPlan& pl = side ? spec[e].add : spec[e].mul;
+            if (g.n_terms > KZG_MAX_GATE_TERMS) return fail(ctx, KZG_E_ARG, "recur: n_terms must be in [0, KZG_MAX_GATE_TERMS]");
+            if (g.n_terms == 0) continue;
+            if (!g.coeffs_be32 || !g.term_lens)
+                return fail(ctx, KZG_E_ARG, "recur: coeffs_be32 and term_lens must not be null inside an expression");
+            pl.n_terms = g.n_terms;
+            pl.coeffs_be32 = g.coeffs_be32;
+            for (uint32_t u = 0, at = 0; u < g.n_terms; u++) {
+                if (!fr_be32_canonical(g.coeffs_be32 + 32 * (size_t)u))
+                    return fail(ctx, KZG_E_ARG, "recur: term coefficients must be canonical scalars (< r)");
+                if (g.term_lens[u] > KZG_MAX_EXPR_FACTORS)
+                    return fail(ctx, KZG_E_ARG, "recur: a term has more than KZG_MAX_EXPR_FACTORS factors");
+                if (g.term_lens[u] && !g.term_rows)
+                    return fail(ctx, KZG_E_ARG, "recur: term_rows must not be null inside an expression that has a factor");
+                pl.term_len[u] = (uint8_t)g.term_lens[u];
+                for (uint32_t f = 0; f < g.term_lens[u]; f++, at++) {
+                    max_row = std::max(max_row, g.term_rows[at]);
+                    pl.term_row[u][f] = (uint8_t)(g.term_rows[at] < KZG_MAX_BATCH_OPEN ? g.term_rows[at] : 0);
+                    if (g.term_rots) rot_at(e, side, u, f) = g.term_rots[at];
+                }
+            }
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs irefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab it;
+    uint32_t ki = 0, i = 0;
+    uint64_t T = 0;
+    if (int rc = rows_lookup(ctx, "recur", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    if (max_row >= ki) return fail(ctx, KZG_E_ARG, "recur: a row must index the concatenated rows of the input sets");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "recur: the row length must be a power of two");
+    if (T > ((uint64_t)1 << 32)) return fail(ctx, KZG_E_ARG, "recur: the row length must be at most 2^32");
+    for (uint32_t e = 0; e < n_recs; e++)   // any int32 rotation, reduced into [0, T)
+        for (int side = 0; side < 2; side++) {
+            ExprPlan& pl = side ? spec[e].add : spec[e].mul;
+            for (uint32_t u = 0; u < pl.n_terms; u++)
+                for (uint32_t f = 0; f < pl.term_len[u]; f++)
+                    pl.term_rot[u][f] = (uint32_t)(((int64_t)rot_at(e, side, u, f) % (int64_t)T + (int64_t)T) % (int64_t)T);
+        }
+    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
+    if (lay.usable) {   // the _zk layout over n_recs columns: blind_check's refusals, the tail column-major
+        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "recur: usable must be in [1, T - 1] (0: the plain layout)");
+        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
+            return fail(ctx, KZG_E_ARG, "recur: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
+        const uint64_t n_tail = (uint64_t)n_recs * (T - lay.usable - 1);
+        if (n_tail && !lay.tail_be32) return fail(ctx, KZG_E_ARG, "recur: tail_be32 may be null only when usable = T - 1");
+        for (uint64_t j = 0; j < n_tail; j++)
+            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
+                return fail(ctx, KZG_E_ARG, "recur: tail scalars must be canonical (< r)");
+    } else if (lay.tail_be32) {
+        return fail(ctx, KZG_E_ARG, "recur: tail_be32 must be null in the plain layout (usable = 0)");
+    }
+    if (int rc2 = rows_reserve(ctx, "recur", pend, (size_t)n_recs * T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    uint8_t c48[KZG_MAX_BATCH_OPEN * 48], closing[KZG_MAX_BATCH_OPEN * 32];
+    rc = rows_recur_dev(ctx, H, i, it, n_recs, spec.data(), T, pend.buf.as<uint32_t>(), c48, closing, lay.usable ? &lay : nullptr);
+    if (rc) return rc;
+    memcpy(out_commitments48, c48, 48 * (size_t)n_recs);
+    memcpy(out_closings32, closing, 32 * (size_t)n_recs);
+    *out_handle = rows_insert(ctx, pend, i, n_recs, T);
+    return KZG_OK;
+}
+
 // The check of a _sel builder's selector arguments (SelCall, rows_impl.h): sel_index[l] is KZG_NO_SELECTOR or indexes the
 // concatenated rows of the sel_handles sets, which must be of the call's worker and row length.  The distinct rows named go
 // into sp (a row that serves several lookups is transformed once).
@@ -1867,6 +1964,12 @@ int kzg_rows_commit_expr(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t*
                          uint64_t* out_first, uint64_t* out_handle) {
     return rows_expr(ctx, UINT32_MAX, n_input_handles, input_handles, n_exprs, exprs, opts, out_commitments48, out_nonzero,
                      out_first, out_handle);
+}
+int kzg_rows_commit_recurrence(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_recs,
+                               const kzg_recurrence* recs, const kzg_recurrence_opts* opts, uint8_t* out_commitments48,
+                               uint8_t* out_closings32, uint64_t* out_handle) {
+    return rows_recurrence(ctx, UINT32_MAX, n_input_handles, input_handles, n_recs, recs, opts, out_commitments48,
+                           out_closings32, out_handle);
 }
 int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_table_handles,
                                const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups, uint32_t width,

@@ -821,6 +821,87 @@ class HipEngine:
         rs = RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]) if n_out else None
         return rs, [int(v) for v in nz], [None if int(v) == _native.KZG_EXPR_NONE else int(v) for v in first]
 
+    # ---- a set built from sets: running values along the rows, v[t + 1] = A[t] v[t] + B[t] with A and B expressions
+    def commit_recurrence(self, input_sets: Sequence[object], recs: Sequence[Sequence], usable: Optional[int] = None,
+                          tail: Sequence[bytes] = ()) -> Tuple["RowSet", List[bytes]]:
+        """kzg_rows_commit_recurrence over the concatenated rows of input_sets (RowSet objects or bare handles).  recs: a list of
+        (mul_terms, add_terms, start_be32) entries; both term lists as in commit_expr ((32-byte coefficient, factors) per term, a
+        factor a row index or a (row, rot) pair), an empty mul_terms standing for A = 1 and an empty add_terms for B = 0 (not
+        both); v[0] = start, v[t + 1] = A[t] v[t] + B[t].  Returns (the new RowSet of the recurrences in their order, the closing
+        value of each as 32 bytes).  usable = None: rows 0 .. T - 1 hold v[0] .. v[T - 1] and the closing value is v[T];
+        otherwise rows 0 .. usable hold v[0] .. v[usable], the last of them the closing value, and row usable + 1 + s of column c
+        takes tail[c * (T - usable - 1) + s] (32 bytes each, column-major)."""
+        what = "commit_recurrence"
+        ni, hi = self._handle_array(input_sets, what)
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: {why}")   # noqa: E731
+        recs = list(recs) if isinstance(recs, (list, tuple)) else None
+        if not recs or len(recs) > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"recs must be a list of 1 .. {_native.KZG_MAX_BATCH_OPEN} entries")
+        arr, keep = (_native.Recurrence * len(recs))(), []
+
+        def side(terms):
+            try:
+                tt = []
+                for c, factors in terms:
+                    if any(isinstance(f, (tuple, list)) and len(f) != 2 for f in factors):
+                        raise ValueError("a factor is a row index or a (row, rot) pair")
+                    tt.append((bytes(c), [(int(f[0]), int(f[1])) if isinstance(f, (tuple, list)) else (int(f), 0) for f in factors]))
+            except (TypeError, ValueError) as ex:
+                raise bad(f"malformed terms: {ex!r}") from ex
+            if len(tt) > _native.KZG_MAX_GATE_TERMS or any(len(c) != 32 or len(fs) > _native.KZG_MAX_EXPR_FACTORS for c, fs in tt):
+                raise bad(f"an expression has at most {_native.KZG_MAX_GATE_TERMS} terms of a 32-byte coefficient and at most "
+                          f"{_native.KZG_MAX_EXPR_FACTORS} factors")
+            flat = [f for _, fs in tt for f in fs]
+            if any(not 0 <= j < 1 << 32 or not -(1 << 31) <= rot < 1 << 31 for j, rot in flat):
+                raise bad("row indices must be non-negative integers below 2^32 and rotations must fit an int32")
+            if not tt:
+                return _native.QuotientTerms(0, None, None, None, None)
+            lens = (ctypes.c_uint32 * len(tt))(*[len(fs) for _, fs in tt])
+            rows_arr = (ctypes.c_uint32 * max(len(flat), 1))(*[j for j, _ in flat])
+            rots_arr = (ctypes.c_int32 * max(len(flat), 1))(*[rot for _, rot in flat])
+            keep.append((lens, rows_arr, rots_arr))   # the arrays live as long as the structures that point at them
+            return _native.QuotientTerms(len(tt), b"".join(c for c, _ in tt), lens, rows_arr, rots_arr)
+
+        for e, ent in enumerate(recs):
+            if not isinstance(ent, (list, tuple)) or len(ent) != 3 or not isinstance(ent[2], (bytes, bytearray)) or len(ent[2]) != 32:
+                raise bad("an entry of recs is (mul_terms, add_terms, start) with start of 32 bytes")
+            mul, add = side(ent[0]), side(ent[1])
+            if mul.n_terms == 0 and add.n_terms == 0:
+                raise bad("mul_terms and add_terms must not both be empty")
+            arr[e] = _native.Recurrence(mul, add, bytes(ent[2]))
+        wi, T, lay = self._recurrence_layout(what, input_sets, len(recs), usable, tail)
+        opts = _native.RecurrenceOpts(*lay) if lay else None
+        c, cl, h = ctypes.create_string_buffer(48 * len(recs)), ctypes.create_string_buffer(32 * len(recs)), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_recurrence(self._h, ni, hi, len(recs), arr, ctypes.byref(opts) if opts is not None else None,
+                                                       c, cl, ctypes.byref(h)))
+        del keep
+        k = len(recs)
+        return (RowSet(self, h.value, wi, k, T, [c.raw[48 * p:48 * p + 48] for p in range(k)]),
+                [cl.raw[32 * p:32 * p + 32] for p in range(k)])
+
+    def _recurrence_layout(self, what: str, input_sets, n_cols: int, usable, tail):
+        """The usable layout WITH a closing row over n_cols columns (kzg_recurrence_opts): (worker, T, None for the plain layout or
+        (usable, the column-major tail's bytes or None)); worker and T are None for bare handles of sets this engine did not
+        commit, which only the plain layout accepts."""
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: {why}")   # noqa: E731
+        tail = [bytes(x) for x in (tail or [])]
+        src = next((x for x in input_sets if getattr(x, "T", None) is not None), None)
+        wi, T = (src.i, src.T) if src is not None else next(
+            (self._set_len[int(x)] for x in input_sets if not hasattr(x, "handle") and int(x) in self._set_len), (None, None))
+        if usable is None:
+            if tail:
+                raise bad("a tail needs usable (None: the plain layout)")
+            return wi, T, None
+        if not isinstance(usable, int) or not 1 <= usable < 1 << 64:   # (the C call reads 0 as "plain layout": here None)
+            raise bad("usable must be in [1, T - 1] (None: the plain layout)")
+        if any(len(x) != 32 for x in tail):
+            raise bad("the tail scalars must be of 32 bytes each")
+        if T is None:
+            raise bad("the row length of the sets is unknown to this engine (they were not committed through it)")
+        if usable < T and T - usable <= _native.KZG_MAX_BLIND_ROWS and len(tail) != n_cols * (T - usable - 1):
+            raise bad(f"the tail must hold exactly n_recs * (T - usable - 1) = {n_cols * (T - usable - 1)} scalars, not {len(tail)}")
+        return wi, T, (usable, b"".join(tail) if tail else None)
+
     # ---- a third set built from sets: the PLONK quotient (round 3), computed and committed on the device
     def commit_quotient(self, sets: Sequence[object], terms: Sequence[Tuple[bytes, Sequence[int]]], perm: Optional[dict] = None,
                         ext_log: int = 2, n_pieces: int = 3) -> "RowSet":
@@ -1518,6 +1599,17 @@ class HipEngine:
                                               len(alphas_be32) // 32, ctypes.addressof(y), ctypes.addressof(q) if quot else None))
         return y.raw[:32 * nout], bytes(q) if quot else b""
 
+    def test_recur_run(self, a_be32: bytes, b_be32: bytes, start_be32: bytes, n: int,
+                       plan: Sequence[int] = (-1, -1)) -> Tuple[bytes, bytes]:
+        """v[0] = start, v[t + 1] = a[t] v[t] + b[t] over n steps by the CALLER'S plan (kzg_test_recur_run; no SRS, no MSM): plan =
+        (l0, top_max), both -1 for the library's own.  Returns (v[0] .. v[n - 1] as n x 32 bytes, the closing value v[n]).
+        KzgError(KZG_E_ARG) for a plan the kernels do not admit."""
+        l0, top_max = plan
+        v, cl = ctypes.create_string_buffer(32 * max(1, n)), ctypes.create_string_buffer(32)
+        self._chk(self._lib.kzg_test_recur_run(self._h, l0, top_max, a_be32, b_be32, start_be32, n, ctypes.addressof(v),
+                                               ctypes.addressof(cl)))
+        return v.raw[:32 * n], cl.raw
+
 
 def ntt_plan_of(log_n: int, kernel: int = -1, tile_log: int = 0) -> Tuple[int, List[Tuple[int, int]]]:
     """The pass plan the library runs for 2^log_n elements (kzg_test_ntt_plan_of; no context, no device): (form, [(S, logC)
@@ -1545,6 +1637,20 @@ def poly_plan_of(n: int, l0: int = -1, scan_max: int = -1, scan_nt: int = -1, ld
     k = K.value + 1
     return {"K": K.value, "l": list(al[:k]), "sq": list(asq[:k]), "n": list(an[:k]), "off": list(aoff[:k]), "scan_nt": nt.value,
             "lds": ld.value}
+
+
+def recur_plan_of(n: int, l0: int = -1, top_max: int = -1) -> Dict[str, object]:
+    """The level plan of the recurrence scan for n steps (kzg_test_recur_plan_of; no context, no device): with both parameters
+    -1 the plan the library runs, otherwise the caller's.  {"K", "l", "n", "off" (K + 1 entries each)}; KzgError(KZG_E_ARG) with
+    the reason for a plan outside the kernels' preconditions."""
+    lib = _native.load()
+    K = ctypes.c_int(0)
+    al, an, aoff = (ctypes.c_int * 16)(), (ctypes.c_uint64 * 16)(), (ctypes.c_uint64 * 16)()
+    rc = lib.kzg_test_recur_plan_of(n, l0, top_max, ctypes.byref(K), al, an, aoff)
+    if rc != _native.KZG_OK:
+        raise KzgError(rc, lib.kzg_last_error(None).decode(errors="replace"))
+    k = K.value + 1
+    return {"K": K.value, "l": list(al[:k]), "n": list(an[:k]), "off": list(aoff[:k])}
 
 
 def msm_passes_of(c: int, long_rows: bool, k: int, m: int) -> List[Tuple[int, int, int, int, int]]:

@@ -221,6 +221,9 @@ class MultiDeviceClient:
             self._row_owner[int(r.json()["handle"])] = self._owner(list(input_handles))
         return r
 
+    def worker_commit_recurrence(self, input_handles: Sequence[int], recs, usable=None, tail=()):
+        return self._routed_builder("worker_commit_recurrence", [input_handles], input_handles, recs, usable, tail)
+
     def worker_commit_quotient_zk(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None, ext_log=2,
                                   n_pieces=3):
         return self._routed_builder("worker_commit_quotient_zk", [handles], handles, terms, perm, lookup, active_row, ext_log,
