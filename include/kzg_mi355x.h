@@ -686,7 +686,8 @@ int kzg_rows_commit_shuffle(kzg_ctx* ctx, uint32_t n_input_handles, const uint64
  * rows; T > 2^27; usable >= T; T - usable > KZG_MAX_BLIND_ROWS; a tail with usable = 0, or none with usable > 0; a tail scalar
  * >= r.  The source sets are only read; a release or an SRS load racing the call follows the rules of kzg_rows_open.
  * Thread-safe like every call; after any error the context keeps serving.
- * OUT OF SCOPE: selectors (the caller compacts the enabled rows itself), descending order, and returning the permutation.
+ * OUT OF SCOPE: selectors (the caller compacts the enabled rows itself) and descending order.  (The permutation and its
+ * inverse: carry the row number as a payload column, then kzg_rows_commit_fetch below by it.)
  * SOUNDNESS: nothing here is a proof.  The sorted rows are prover data; the argument is the shuffle relation
  * (kzg_rows_commit_shuffle over the inputs and this set, theta and gamma drawn AFTER these commitments are fixed) plus the
  * caller's adjacent-row gate.  The library derives no challenge. */
@@ -862,6 +863,59 @@ int kzg_rows_commit_recurrence(kzg_ctx* ctx, uint32_t n_input_handles, const uin
                                uint32_t n_recs, const kzg_recurrence* recs, const kzg_recurrence_opts* opts /* NULL: plain */,
                                uint8_t* out_commitments48 /* n_recs * 48 */, uint8_t* out_closings32 /* n_recs * 32 */,
                                uint64_t* out_handle);
+/* THE FETCHED COLUMNS: a set built FROM sets, every output cell READ OUT OF A TABLE that is already resident -- c = a XOR b from
+ * the table (a, b, a ^ b), an S-box output, an opcode's decode flags, any ROM read, no polynomial expression of a and b; the
+ * value of a memory read back in program order from the sorted columns (carry the row number through kzg_rows_commit_sorted as
+ * a payload column, then fetch by it: the un-sort); v[t] = table[idx[t]].  The concatenated rows of the table_handles sets are
+ * the w_tab columns of the table: the first n_keys are the KEY, the n_pay = w_tab - n_keys behind them the PAYLOAD.  The
+ * concatenated rows of the input_handles sets are n_reads reads, read-major like the lookups of kzg_rows_commit_multiplicities:
+ * read l owns rows l n_keys .. l n_keys + n_keys - 1.  Every cell is a column's value at w_T^t, a canonical field element, as in
+ * the sorted and derived calls.
+ *   BY KEY (n_keys >= 1): for cell t of read l let q be the SMALLEST table row whose key tuple equals the read's tuple at t in all
+ *     n_keys columns.  Output column p of the read takes table[n_keys + p][q].  With flags = KZG_FETCH_INDEX one more column
+ *     leads the read's outputs and holds q itself as a field element.  A cell with no such row is a MISS: it gets 0 in every
+ *     output column of its read and is counted.
+ *   BY ROW INDEX (n_keys = 0): each read owns ONE input row, the address; q is its canonical integer and all w_tab table columns
+ *     are payload.  A cell is a miss when q >= the number of addressable table rows; the comparison is on the whole 255-bit
+ *     integer (2^32 + 3 or 2^64 is a miss, not row 3 or row 0).  KZG_FETCH_INDEX is refused: the address is the index.
+ * The outputs form ONE new set of n_out = n_reads (n_pay + index) rows of the same worker and length, in read order; inside a
+ * read the index first, then the payload in table order.  out_commitments48[c] equals kzg_rows_commit(i, n_out, the fetched
+ * rows, T, 1, ..)[c] byte for byte, and *out_handle opens, evaluates, combines, releases, goes stale and counts against
+ * KZG_MAX_ROW_SETS (KZG_E_BUSY; KZG_E_NOMEM on a failed allocation, the lane's workspace included) like any other.
+ * out_missing[l] is the number of misses of read l and out_first_missing[l] the smallest missing row, or KZG_FETCH_NONE -- the
+ * mechanism and meaning of out_first of kzg_rows_commit_expr.  A miss is never an error.  The output is a function of the input
+ * bytes alone, whatever the device's schedule: a repeated table key answers with its first copy, as the multiplicities call
+ * counts on it.
+ * opts (NULL: plain layout) is kzg_derive_opts, in layout and refusals: usable = 0 reads all T cells and all T table rows are
+ * addressable, tail_be32 must be NULL.  Otherwise 1 <= usable <= T - 1 and T - usable <= KZG_MAX_BLIND_ROWS: cells and table
+ * rows at or behind `usable` are never read or matched (as in kzg_rows_commit_multiplicities_zk; by row index an address >=
+ * usable is a miss), and output row usable + s of output column c takes tail_be32[c * (T - usable) + s], column-major canonical
+ * scalars over the n_out columns.  There is NO closing row.  The tail rides in kernel arguments, the counts come back in the
+ * copy behind the MSM; nothing row-sized crosses the host link in either direction.
+ * WORKSPACE per call: w_tab + max(n_keys, 1) + n_pay + index vectors of T elements of 32 bytes (the table columns, ONE read's
+ * input columns, ONE read's output columns; the reads reuse the last two groups) and, by key, 2 T slots of 4 bytes.
+ * Handle lists follow kzg_rows_commit_multiplicities: 1 .. KZG_MAX_BATCH_OPEN handles per list, a handle may repeat and may
+ * stand in both lists (the table and the input may be one set), unknown / released / stale -> KZG_E_ARG; every set named must
+ * belong to one worker and one (power-of-two) T.  KZG_E_ARG with a message that begins "fetch:" and names the cause: n_reads = 0;
+ * n_keys > w_tab; n_pay = 0 without KZG_FETCH_INDEX (nothing to output); an unknown flag; KZG_FETCH_INDEX with n_keys = 0; more
+ * than KZG_MAX_BATCH_OPEN table rows, input rows or output rows; an input concatenation that does not hold exactly n_reads
+ * max(n_keys, 1) rows; T > 2^27; and the usable and tail refusals of kzg_rows_commit_derived.  The source sets are only read; a
+ * release or an SRS load racing the call follows the rules of kzg_rows_open.  Thread-safe like every call; after any error the
+ * context keeps serving.
+ * OUT OF SCOPE: per-read selectors (a disabled cell is a counted miss that reads 0: multiply by the selector with
+ * kzg_rows_commit_expr afterwards); a default value other than 0; the LAST matching row instead of the first; tables longer or
+ * shorter than the input rows.
+ * SOUNDNESS: nothing here is a proof.  The fetched rows are prover data; the argument is the lookup of the tuple (key, payload)
+ * in the table (kzg_rows_commit_multiplicities -> kzg_rows_commit_lookup_sum -> the quotient's logUp relation), with theta and
+ * beta drawn AFTER these commitments are fixed.  A zero miss count is a convenience for the prover and convinces no verifier.
+ * The library derives no challenge and draws no randomness: the tail must be fresh per proof. */
+#define KZG_FETCH_INDEX 1u                  /* flags: lead every read's outputs with the matching row number */
+#define KZG_FETCH_NONE  0xffffffffffffffffull
+int kzg_rows_commit_fetch(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                          uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_reads, uint32_t n_keys,
+                          uint32_t flags /* 0 or KZG_FETCH_INDEX */, const kzg_derive_opts* opts /* NULL: plain */,
+                          uint8_t* out_commitments48 /* n_out * 48 */, uint64_t* out_missing /* n_reads */,
+                          uint64_t* out_first_missing /* n_reads */, uint64_t* out_handle);
 /* THE QUOTIENT WITH LOOKUP SELECTORS: kzg_rows_commit_quotient_zk and kzg_rows_quotient_part for lookups that are enabled on
  * some rows only.  selectors->selector_rows holds L = lookup->n_lookups entries, each a row index into the call's concatenated
  * rows (the caller's fixed column q_l, the row that kzg_rows_commit_multiplicities_sel / _lookup_sum_sel read) or
@@ -1220,6 +1274,11 @@ int kzg_multi_rows_commit_expr(kzg_multi* mh, uint32_t i, uint32_t n_input_handl
 int kzg_multi_rows_commit_recurrence(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                      uint32_t n_recs, const kzg_recurrence* recs, const kzg_recurrence_opts* opts,
                                      uint8_t* out_commitments48, uint8_t* out_closings32, uint64_t* out_handle);
+/* kzg_rows_commit_fetch on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_fetch(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_reads, uint32_t n_keys,
+                                uint32_t flags, const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_missing,
+                                uint64_t* out_first_missing, uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

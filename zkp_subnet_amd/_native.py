@@ -28,6 +28,8 @@ KZG_DERIVE_INV0, KZG_DERIVE_LIMBS = 1, 2   # kzg_rows_commit_derived: kzg_derive
 KZG_MAX_EXPR_FACTORS = 8   # kzg_rows_commit_expr: factors of one term
 KZG_EXPR_CHECK = 1   # kzg_expr.flags: evaluate and count only
 KZG_EXPR_NONE = 0xffffffffffffffff   # out_first: no non-zero cell
+KZG_FETCH_INDEX = 1   # kzg_rows_commit_fetch flags: lead every read's outputs with the matching row number
+KZG_FETCH_NONE = 0xffffffffffffffff   # out_first_missing: no miss
 KZG_OK, KZG_E_ARG, KZG_E_SCALAR, KZG_E_POINT, KZG_E_HIP, KZG_E_NOMEM, KZG_E_BUSY, KZG_E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
 STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_SCALAR", -3: "E_POINT", -4: "E_HIP", -5: "E_NOMEM", -6: "E_BUSY", -7: "E_COMM"}
 TIMING_NAMES = ["decode", "ntt", "digits", "scan", "scatter", "accumulate", "fixup", "tree", "final", "poly", "total", "collective"]
@@ -163,6 +165,8 @@ SYMBOLS = {
                                   ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_recurrence": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Recurrence),
                                         ctypes.POINTER(RecurrenceOpts), _B, _B, ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_fetch": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _U32,
+                                   ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_lookup_sum": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B, _B, _B, _B,
                                         ctypes.POINTER(_U64)]),
     "kzg_rows_commit_multiplicities": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _B,
@@ -272,6 +276,9 @@ SYMBOLS = {
                                         ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_recurrence": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Recurrence),
                                               ctypes.POINTER(RecurrenceOpts), _B, _B, ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_fetch": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _U32,
+                                         ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64),
+                                         ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_lookup_sum": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B,
                                               _B, _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_multiplicities": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32,

@@ -780,6 +780,41 @@ class Client:
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
                 "closings": [codec.be32_to_fr(c) for c in closings]}
 
+    # ---- columns read out of a resident table, by key or by row index, on the device
+    @_guard
+    def worker_commit_fetch(self, input_handles: Sequence[int], table_handles: Sequence[int], n_reads: int, n_keys: int,
+                            with_index: bool = False, usable: Optional[int] = None, tail: Sequence[str] = ()):
+        """Extension: columns fetched from a table that is already resident.  The rows of the table_handles sets are the
+        table's columns, the first n_keys the key and the others the payload; the rows of the input_handles sets are n_reads
+        reads of n_keys rows each (read-major).  Every cell takes the payload of the SMALLEST table row whose key equals the
+        cell's key in all n_keys columns (with_index: that row number leads the read's columns), or zeros where there is
+        none: c = a XOR b from the table (a, b, a ^ b), a ROM read, the value of a sorted memory back in program order.  With
+        n_keys = 0 a read is ONE row of row indices, every table column is payload and an index at or beyond the table's
+        rows is a miss.  All outputs form ONE new set in read order.  usable = null reads all T rows; otherwise only cells and
+        table rows [0, usable) take part and row usable + s of output column c is tail[c * (T - usable) + s] -- there is no
+        closing row.  Returns the handle, the commitments, and per read `missing`, the number of cells without a table row,
+        and `first_missing`, the smallest such cell (null: none).  A miss is no error.  Nothing here is a proof: the fetched
+        rows are prover data and the argument is the lookup of (key, payload) in the table."""
+        what = "worker_commit_fetch"
+        hi, ht = _handles(input_handles), _handles(table_handles)
+        if any(isinstance(v, bool) or not isinstance(v, int) for v in (n_reads, n_keys)) or not isinstance(with_index, bool):
+            raise codec.CodecError(f"{what}: n_reads and n_keys must be integers and with_index a boolean")
+        if n_reads < 1 or n_keys < 0 or n_reads * max(n_keys, 1) > KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"{what}: n_reads >= 1, n_keys >= 0 and n_reads * max(n_keys, 1) <= {KZG_MAX_BATCH_OPEN}")
+        if with_index and n_keys == 0:
+            raise codec.CodecError(f"{what}: with_index needs n_keys >= 1 (by row index the input row is the index)")
+        if usable is None:
+            if tail:
+                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
+            tb = []
+        else:
+            usable, tb = self._blind(what, usable, tail)
+            if usable == 0:
+                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        rs, missing, first = self.engine.commit_fetch(hi, ht, n_reads, n_keys, with_index, usable, tb)
+        return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
+                "missing": [int(v) for v in missing], "first_missing": first}
+
     @staticmethod
     def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: Sequence[int], n_groups: int, width: int,
                                theta: str, gamma: str, coeff: str, active_row: Optional[int] = None,

@@ -9,6 +9,7 @@
 //   fr_derive.hip the kernels of kzg_rows_commit_derived: inverse-or-zero around the batched inversion, limb decomposition
 //   fr_expr.hip   the kernel of kzg_rows_commit_expr: sums of products of rotated resident columns on H, counted and stored
 //   fr_recur.hip  the scan of kzg_rows_commit_recurrence: v[t + 1] = A[t] v[t] + B[t] as a ladder over affine maps
+//   fr_join.hip   the hash join of kzg_rows_commit_multiplicities, and the fetch of kzg_rows_commit_fetch that walks it
 //   comm.hip      the library's own RCCL collective (kzg_comm_*, kzg_msm_sharded, the stream-chained pair)
 //   abi_test.hip  unit-op test hooks (include/kzg_mi355x_test.h)
 // No CPU arithmetic fallback exists anywhere here: if HIP fails, the call fails.
@@ -499,6 +500,14 @@ struct RecurSpec {
 // tail_be32[c * (T - usable - 1) + s] (checked by the caller as blind_check does, over n_recs columns)
 int rows_recur_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_recs, const RecurSpec* recs, uint64_t T,
                    uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, const Blind* lay);
+// the n_reads reads of kzg_rows_commit_fetch (checked by the caller: n_keys <= w_tab rows in `table`, n_reads max(n_keys, 1)
+// rows in `inputs`, n_reads (w_tab - n_keys + index) in [1, KZG_MAX_BATCH_OPEN], no index with n_keys = 0, T <= 2^27) into a
+// new set's buffer dst: their commitments, per read the number of cells without a table row and the smallest such cell
+// (KZG_FETCH_NONE: none), and whether a walk of the join reached its bound (the caller creates no set).  lay: as for
+// rows_sorted_dev, the tail column-major over all output columns; cells and table rows at or behind `usable` do not take part
+int rows_fetch_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& table, uint32_t n_reads,
+                   uint32_t n_keys, uint32_t w_tab, bool index, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_missing,
+                   uint64_t* out_first, bool* out_overrun, const Blind* lay);
 // the quotient pieces of the constraints qp over the n_rows coefficient rows of rt into a new n_pieces-row set's buffer dst:
 // their commitments, and whether a coefficient of t at or above n_pieces T was not zero (the caller creates no set)
 int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t n_rows, uint64_t T, const QuotPlan& qp,

@@ -6,6 +6,8 @@
 //   probe : cnt[first(in(l, t))] += 1, or missing += 1                            (one launch per lookup)
 //           (_sel: only where the lookup's selector q_l(w^t) is not zero)
 //   counts: cnt[t] -> m(w^t) as a Montgomery element
+//   fetch : out[p][t] <- tab[n_keys + p][first(in(l, t))], or 0 and missing += 1    (kzg_rows_commit_fetch; one launch per read;
+//           k_fetch_index: the row is the cell's canonical integer instead of a walk)
 // A slot holds a table ROW INDEX or JOIN_EMPTY = 2^32 - 1 (T <= 2^27, so 0 and T - 1 are ordinary values).  No kernel here
 // multiplies (the last one: one product per element); they move bytes and chase one dependent load (slot -> row).
 #include "fr_kernels.hip.h"
@@ -209,6 +211,109 @@ __global__ void __launch_bounds__(256) k_join_counts(const uint32_t* __restrict_
     fr9_store(out + 8 * t, v);
 }
 
+// ------------------------------------------------------------------------------------------------ fetch
+// kzg_rows_commit_fetch: the probe that copies.  The misses of a workgroup and its smallest missing cell: one ballot per wave,
+// an LDS sum and an LDS minimum (the lowest set bit of the ballot), one atomicAdd and one atomicMin on u64 words per workgroup
+// -- a sum and a minimum of minima, whatever the order in which the atomics return.  Called by every lane of the workgroup
+// (uniform control flow); lane v stands for cell blockIdx.x * blockDim.x + v
+KZG_DEV void fetch_tally(bool miss, unsigned long long* __restrict__ missing, unsigned long long* __restrict__ first) {
+    __shared__ uint32_t wg_miss, wg_first;
+    if (threadIdx.x == 0) {
+        wg_miss = 0;
+        wg_first = 0xffffffffu;
+    }
+    __syncthreads();
+    const unsigned long long b = __ballot(miss);
+    if ((threadIdx.x & 63u) == 0 && b) {
+        atomicAdd(&wg_miss, (uint32_t)__popcll(b));
+        atomicMin(&wg_first, threadIdx.x + (uint32_t)__ffsll(b) - 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_miss) {
+        atomicAdd(missing, (unsigned long long)wg_miss);
+        atomicMin(first, (unsigned long long)blockIdx.x * blockDim.x + wg_first);
+    }
+}
+// cell t of the n_out = index + n_pay output vectors (T elements apart) of one read: on a hit at table row q the index column
+// (if any) takes q as a canonical Montgomery element, as k_join_counts converts a counter, and payload column p the 32 bytes of
+// pay[p T + q] (two 16-byte loads, the gather; two 16-byte stores, coalesced); on a miss every column takes 0.  Vector stores only
+KZG_DEV void fetch_emit(const uint32_t* __restrict__ pay, uint32_t* __restrict__ out, uint64_t T, uint64_t t, bool hit, uint32_t q,
+                        uint32_t n_pay, bool index) {
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    if (index) {
+        if (hit) {
+            fr9_t v;
+            fr9_zero(v);
+            v.l[0] = q & FR9_MASK;
+            v.l[1] = q >> 29;
+            fr9_to_mont(v, v);
+            fr9_store(out + 8 * t, v);
+        } else {
+            uint4* o = reinterpret_cast<uint4*>(out + 8 * t);
+            o[0] = z;
+            o[1] = z;
+        }
+        out += T * 8;
+    }
+    for (uint32_t p = 0; p < n_pay; p++) {
+        uint4 a = z, b = z;
+        if (hit) {
+            const uint4* g = reinterpret_cast<const uint4*>(pay + ((uint64_t)p * T + q) * 8);
+            a = g[0];
+            b = g[1];
+        }
+        uint4* o = reinterpret_cast<uint4*>(out + ((uint64_t)p * T + t) * 8);
+        o[0] = a;
+        o[1] = b;
+    }
+}
+// One lane per cell t < rows of one read; the walk of k_join_probe_rows over a join built on the table's first w = n_keys
+// columns and its first `rows` rows (rows = T: all of them).  A slot's row q is below `rows` (the build wrote it), so every
+// gather stays inside the table's vectors; the payload columns are the table's vectors n_keys .. n_keys + n_pay - 1.  A walk
+// that reaches its bound raises *overrun and writes the zeros of a miss (the caller fails the call).  Lanes t >= rows read and
+// store nothing; they still walk the reduction.
+__global__ void __launch_bounds__(256) k_join_fetch(const uint32_t* __restrict__ tab, const uint32_t* __restrict__ in, uint64_t T,
+                                                     uint64_t rows, uint32_t w, uint32_t n_pay, uint32_t index,
+                                                     const uint32_t* __restrict__ slots, uint32_t mask, uint32_t* __restrict__ out,
+                                                     unsigned long long* __restrict__ missing,
+                                                     unsigned long long* __restrict__ first, uint32_t* overrun) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool miss = false;
+    if (t < rows) {
+        uint32_t s = join_hash(in, T, w, t) & mask, q = 0;
+        bool hit = false, done = false;
+        for (uint32_t step = 0; step <= mask; step++, s = (s + 1) & mask) {
+            q = slots[s];
+            if (q == JOIN_EMPTY) { miss = done = true; break; }
+            if (q < rows && join_equal(tab, q, in, t, T, w)) { hit = done = true; break; }
+        }
+        if (!done) atomicOr(overrun, 1u);
+        fetch_emit(tab + (uint64_t)w * T * 8, out, T, t, hit, q, n_pay, index != 0);
+    }
+    fetch_tally(miss, missing, first);
+}
+// n_keys = 0: the cell is the ADDRESS.  It is decoded from Montgomery form to its canonical integer as k_limbs decodes a cell;
+// the range test reads all eight words (2^32 + 3 or 2^64 is a miss, not row 3 or row 0), so a hit's q is below rows <= T and
+// every gather stays inside the table's vectors, which are all payload.
+__global__ void __launch_bounds__(256) k_fetch_index(const uint32_t* __restrict__ tab, const uint32_t* __restrict__ addr, uint64_t T,
+                                                      uint64_t rows, uint32_t n_pay, uint32_t* __restrict__ out,
+                                                      unsigned long long* __restrict__ missing,
+                                                      unsigned long long* __restrict__ first) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool miss = false;
+    if (t < rows) {
+        uint32_t w[8];
+        fr9_t v;
+        fr9_load(v, addr + t * 8);
+        fr9_from_mont(v, v);
+        fr9_to_words(w, v);
+        const bool hit = (w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) == 0 && w[0] < rows;
+        miss = !hit;
+        fetch_emit(tab, out, T, t, hit, hit ? w[0] : 0u, n_pay, false);
+    }
+    fetch_tally(miss, missing, first);
+}
+
 void launch_join_build(hipStream_t s, const uint32_t* tab, uint64_t T, uint32_t w, uint32_t* slots, uint32_t cap,
                        uint32_t* overrun) {
     if (T) k_join_build<<<nblk(T, 256), 256, 0, s>>>(tab, T, w, slots, cap - 1, overrun);
@@ -237,4 +342,18 @@ void launch_join_probe_sel(hipStream_t s, const uint32_t* tab, const uint32_t* i
 }
 void launch_join_counts(hipStream_t s, const uint32_t* cnt, uint32_t* out, uint64_t T) {
     if (T) k_join_counts<<<nblk(T, 256), 256, 0, s>>>(cnt, out, T);
+}
+void launch_join_fetch(hipStream_t s, const uint32_t* tab, const uint32_t* in, uint64_t T, uint64_t rows, uint32_t n_keys,
+                       uint32_t n_pay, bool index, const uint32_t* slots, uint32_t cap, uint32_t* out, uint64_t* missing,
+                       uint64_t* first, uint32_t* overrun) {
+    if (!rows || rows > T || T > ((uint64_t)1 << 27) || n_keys == 0 || (n_pay == 0 && !index)) return;
+    k_join_fetch<<<nblk(rows, 256), 256, 0, s>>>(tab, in, T, rows, n_keys, n_pay, index ? 1u : 0u, slots, cap - 1, out,
+                                                  reinterpret_cast<unsigned long long*>(missing),
+                                                  reinterpret_cast<unsigned long long*>(first), overrun);
+}
+void launch_fetch_index(hipStream_t s, const uint32_t* tab, const uint32_t* addr, uint64_t T, uint64_t rows, uint32_t n_pay,
+                        uint32_t* out, uint64_t* missing, uint64_t* first) {
+    if (!rows || rows > T || T > ((uint64_t)1 << 27) || n_pay == 0) return;
+    k_fetch_index<<<nblk(rows, 256), 256, 0, s>>>(tab, addr, T, rows, n_pay, out, reinterpret_cast<unsigned long long*>(missing),
+                                                   reinterpret_cast<unsigned long long*>(first));
 }

@@ -255,6 +255,19 @@ void launch_join_probe_rows(hipStream_t s, const uint32_t* tab, const uint32_t* 
 // canonical Montgomery elements, a cell whose sel[t] is zero is neither probed nor counted as missing
 void launch_join_probe_sel(hipStream_t s, const uint32_t* tab, const uint32_t* in, const uint32_t* sel, uint64_t T, uint64_t rows,
                            uint32_t w, const uint32_t* slots, uint32_t cap, uint32_t* cnt, uint64_t* missing, uint32_t* overrun);
+// ---- the fetch of kzg_rows_commit_fetch (fr_join.hip).  tab: n_keys + n_pay columns of T canonical Montgomery elements, the
+// first n_keys of them the key that launch_join_build(_rows) was called with (w = n_keys, the same `rows`); in: the n_keys
+// columns of one read; out: index + n_pay vectors of T, of which cells [0, rows) are written.  Cell t takes the payload of the
+// smallest table row below `rows` whose key equals the cell's (with index: that row number first, as a canonical Montgomery
+// element), or zeros; *missing += the cells without such a row, *first <- min(*first, the smallest such cell).  out must not
+// overlap tab or in.  rows <= T <= 2^27
+void launch_join_fetch(hipStream_t s, const uint32_t* tab, const uint32_t* in, uint64_t T, uint64_t rows, uint32_t n_keys,
+                       uint32_t n_pay, bool index, const uint32_t* slots, uint32_t cap, uint32_t* out, uint64_t* missing,
+                       uint64_t* first, uint32_t* overrun);
+// the fetch by row index: cell t < rows of the n_pay vectors of out takes tab[p T + q], q the canonical integer of addr[t], or
+// zeros where q >= rows (all 255 bits are compared); the counts as above.  tab: n_pay columns, all payload
+void launch_fetch_index(hipStream_t s, const uint32_t* tab, const uint32_t* addr, uint64_t T, uint64_t rows, uint32_t n_pay,
+                        uint32_t* out, uint64_t* missing, uint64_t* first);
 // ---- the stable sort of kzg_rows_commit_sorted (fr_sort.hip).  ev: the columns as evaluation vectors of T canonical Montgomery
 // elements, column c at + c * T * 8 words; rows [0, n) are sorted by the canonical integers of columns 0 .. n_keys - 1 (column 0
 // most significant), ties by ascending row.  keys: n_keys vectors of T elements; ws: fr_sort_ws_words(n, n_keys) words

@@ -494,6 +494,15 @@ int kzg_multi_rows_commit_recurrence(kzg_multi* mh, uint32_t i, uint32_t n_input
                                          out_closings32, out_handle);
     });
 }
+int kzg_multi_rows_commit_fetch(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_reads, uint32_t n_keys,
+                                uint32_t flags, const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_missing,
+                                uint64_t* out_first_missing, uint64_t* out_handle) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_fetch(c, s, n_input_handles, input_handles, n_table_handles, table_handles, n_reads, n_keys, flags,
+                                    opts, out_commitments48, out_missing, out_first_missing, out_handle);
+    });
+}
 int kzg_multi_rows_commit_lookup_sum(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                      uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle,
                                      uint32_t n_lookups, uint32_t width, const uint8_t theta_be32[32],

@@ -1298,6 +1298,90 @@ int rows_recur_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, 
     return multi_msms_finish(ctx, H, i, T, dst, n_recs, 0, n_recs, out_c48, out_closing32, nullptr);
 }
 
+// The fetched columns (kzg_rows_commit_fetch): a set built FROM sets, every output cell a table cell READ by the key (or the
+// row index) that the input columns hold.  The w_tab table columns are transformed forward once into w_tab vectors of the
+// lane's quotient workspace; with n_keys >= 1 the join of rows_multiplicities_dev is built over the first n_keys of them
+// (launch_join_build / _rows with w = n_keys, unchanged), the others are the payload.
+//   step                      launches                               per call
+//   forward transforms        launch_fr_ntt                          w_tab, then max(n_keys, 1) per read
+//   build                     launch_join_build(_rows)               one (n_keys >= 1)
+//   fetch + count             launch_join_fetch / launch_fetch_index one per read, into n_per = index + n_pay vectors
+//   tail                      launch_sort_tail                       one per output column, with `usable` only
+//   inverse transform         row_to_coeffs                          one per output column, straight into dst
+//   commit                    multi_msms_finish                      ONE pass of n_reads n_per scalar sets
+// The input vectors and the n_per output vectors are reused by every read; the stream orders the work.  The counts and first
+// indices are u64 words behind the first two evaluation slots of the record (the layout of rows_expr_dev), the join's overrun
+// word lies in the second slot; all come back in the copy behind the MSM: the call never waits on its own.
+// Workspace: w_tab + max(n_keys, 1) + n_per vectors of T, and 2 T u32 slots in the staging buffer (n_keys >= 1).
+int rows_fetch_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& table, uint32_t n_reads,
+                   uint32_t n_keys, uint32_t w_tab, bool index, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_missing,
+                   uint64_t* out_first, bool* out_overrun, const Blind* lay) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const int lg = ilog2_exact(T);
+    uint32_t* tw = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
+    const uint64_t vw = T * 8;                        // one vector, in words
+    const uint64_t n = lay ? lay->usable : T;         // the cells that are read and the table rows that can answer
+    const uint32_t n_in = n_keys ? n_keys : 1, n_pay = w_tab - n_keys, n_per = n_pay + (index ? 1u : 0u), n_out = n_reads * n_per;
+    const uint32_t cap = (uint32_t)(2 * T);           // slots: a power of two, load <= 1 / 2 (T <= 2^27: the caller)
+    constexpr uint32_t CNT_OFF = 64, OVR_OFF = 32;    // the counts in the record, then the first indices; the overrun word
+    static_assert(CNT_OFF + 16 * KZG_MAX_BATCH_OPEN <= MR_PAIRS * 32 && KZG_MAX_BATCH_OPEN <= POLY_MAX_ROWS,
+                  "the count and the first index of every read fit the record's evaluation slots");
+    HIPCHK(ctx, A.qext.ensure(((size_t)w_tab + n_in + n_per) * T * 32));
+    if (n_keys) HIPCHK(ctx, A.qstage.ensure((size_t)cap * 4));
+    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    uint32_t *tab = A.qext.as<uint32_t>(), *in = tab + (uint64_t)w_tab * vw, *out = in + (uint64_t)n_in * vw;
+    uint32_t *mid = A.ntt_mid.as<uint32_t>(), *slots = n_keys ? A.qstage.as<uint32_t>() : nullptr;
+    uint8_t* rec = A.brec.as<uint8_t>();
+    uint64_t *cnt = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF), *first = cnt + n_reads;
+    uint32_t* overrun = reinterpret_cast<uint32_t*>(rec + MR_EVAL + OVR_OFF);
+    for (uint32_t c = 0; c < w_tab; c++) {
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, table.r[c], tab + c * vw, lg, tw, nullptr, mid);
+    }
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        HIPCHK(ctx, hipMemsetAsync(rec + MR_EVAL, 0, CNT_OFF + 8 * (size_t)n_reads, A.stream));
+        HIPCHK(ctx, hipMemsetAsync(first, 0xff, 8 * (size_t)n_reads, A.stream));   // KZG_FETCH_NONE
+        if (n_keys) {
+            HIPCHK(ctx, hipMemsetAsync(slots, 0xff, (size_t)cap * 4, A.stream));
+            // usable: only the table rows below it enter the join, so no row at or behind it can answer
+            if (lay) launch_join_build_rows(A.stream, tab, T, n, n_keys, slots, cap, overrun);
+            else launch_join_build(A.stream, tab, T, n_keys, slots, cap, overrun);
+        }
+    }
+    for (uint32_t l = 0, c = 0; l < n_reads; l++) {
+        for (uint32_t k = 0; k < n_in; k++) {
+            Span sp(ctx, A, KZG_T_NTT);
+            launch_fr_ntt(A.stream, inputs.r[l * n_in + k], in + k * vw, lg, tw, nullptr, mid);
+        }
+        {
+            Span sp(ctx, A, KZG_T_POLY);
+            if (n_keys) launch_join_fetch(A.stream, tab, in, T, n, n_keys, n_pay, index, slots, cap, out, cnt + l, first + l, overrun);
+            else launch_fetch_index(A.stream, tab, in, T, n, n_pay, out, cnt + l, first + l);
+        }
+        for (uint32_t p = 0; p < n_per; p++, c++) {
+            if (lay) {
+                Span sp(ctx, A, KZG_T_POLY);
+                launch_sort_tail(A.stream, out + p * vw, T, n, lay->tail_be32 + 32 * (size_t)c * (T - n), A.flags());
+            }
+            const uint32_t* cf;
+            if (int rc = row_to_coeffs(ctx, A, out + p * vw, T, 1, &cf, dst + c * vw)) return rc;
+        }
+    }
+    HIPCHK(ctx, hipGetLastError());
+    uint8_t ev[CNT_OFF + 16 * KZG_MAX_BATCH_OPEN + 32];
+    const uint32_t npairs = (CNT_OFF + 16 * n_reads + 31) / 32;
+    if (int rc = multi_msms_finish(ctx, H, i, T, dst, n_out, 0, npairs, out_c48, ev, nullptr)) return rc;
+    uint32_t of;
+    memcpy(&of, ev + OVR_OFF, 4);
+    *out_overrun = of != 0;
+    memcpy(out_missing, ev + CNT_OFF, 8 * (size_t)n_reads);
+    memcpy(out_first, ev + CNT_OFF + 8 * (size_t)n_reads, 8 * (size_t)n_reads);
+    return KZG_OK;
+}
+
 // the quotient's constants of one (T, E), shared by all lanes like the twiddles: built once under the ctx mutex
 static int ensure_quot_consts(kzg_ctx* ctx, Lane& L, int log_t, int ext_log, const uint32_t* tw_n, const uint32_t** qc) {
     std::lock_guard<std::mutex> lk(ctx->mu);

@@ -62,6 +62,10 @@ int rows_expr(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const u
 int rows_recurrence(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_recs,
                     const kzg_recurrence* recs, const kzg_recurrence_opts* opts, uint8_t* out_commitments48,
                     uint8_t* out_closings32, uint64_t* out_handle);
+// flags: 0 or KZG_FETCH_INDEX.  opts: the usable layout and its tail as the public call takes them (null: all T rows are read)
+int rows_fetch(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_table_handles,
+               const uint64_t* table_handles, uint32_t n_reads, uint32_t n_keys, uint32_t flags, const kzg_derive_opts* opts,
+               uint8_t* out_commitments48, uint64_t* out_missing, uint64_t* out_first_missing, uint64_t* out_handle);
 // zk: the blinding rows of the _zk call, the layout of the _sel call.  sc: the selectors of the _sel call
 int rows_lookup_sum(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
                     uint32_t n_table_handles, const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups,

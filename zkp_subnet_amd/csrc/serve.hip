@@ -1371,6 +1371,81 @@ int rows_recurrence(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, c
     return KZG_OK;
 }
 
+// kzg_rows_commit_fetch: the lookups of an open (two handle lists, as rows_multiplicities), the reservation of a commit of
+// n_out = n_reads (n_pay + index) rows.  What needs no set is refused before a lane is taken; w_tab is what the table sets hold.
+// opts == NULL, or usable == 0: all T cells are read and all T table rows can answer
+int rows_fetch(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_table_handles,
+               const uint64_t* table_handles, uint32_t n_reads, uint32_t n_keys, uint32_t flags, const kzg_derive_opts* opts,
+               uint8_t* out_commitments48, uint64_t* out_missing, uint64_t* out_first_missing, uint64_t* out_handle) {
+    if (!ctx || !input_handles || !table_handles || !out_commitments48 || !out_missing || !out_first_missing || !out_handle)
+        return KZG_E_ARG;
+    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN || n_table_handles == 0 || n_table_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "fetch: the number of handles in each list must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (n_reads == 0) return fail(ctx, KZG_E_ARG, "fetch: n_reads must be at least 1");
+    if (flags & ~KZG_FETCH_INDEX) return fail(ctx, KZG_E_ARG, "fetch: flags must be 0 or KZG_FETCH_INDEX");
+    const bool index = flags == KZG_FETCH_INDEX;
+    if (index && n_keys == 0)
+        return fail(ctx, KZG_E_ARG, "fetch: KZG_FETCH_INDEX needs n_keys >= 1 (by row index the address column is the index)");
+    const uint64_t n_in = (uint64_t)n_reads * (n_keys ? n_keys : 1);
+    if (n_in > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "fetch: n_reads * max(n_keys, 1) input rows must be at most KZG_MAX_BATCH_OPEN");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs irefs{ctx}, trefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab it, tt;
+    uint32_t ki = 0, w_tab = 0, i = 0, i2 = 0;
+    uint64_t T = 0, T2 = 0;
+    if (int rc = rows_lookup(ctx, "fetch: inputs", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    if (int rc = rows_lookup(ctx, "fetch: table", expect_i, n_table_handles, table_handles, trefs, tt, &w_tab, &i2, &T2)) return rc;
+    if (i2 != i || T2 != T) return fail(ctx, KZG_E_ARG, "fetch: all sets must belong to one worker and have one row length");
+    if (n_keys > w_tab) return fail(ctx, KZG_E_ARG, "fetch: n_keys must be at most the number of table rows");
+    const uint32_t n_per = w_tab - n_keys + (index ? 1u : 0u);
+    if (n_per == 0)
+        return fail(ctx, KZG_E_ARG, "fetch: nothing to output: every table row is a key and KZG_FETCH_INDEX is not set");
+    const uint64_t n_out = (uint64_t)n_reads * n_per;
+    if (n_out > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "fetch: n_reads * (payload rows + index) output rows must be at most KZG_MAX_BATCH_OPEN");
+    if (ki != n_in) return fail(ctx, KZG_E_ARG, "fetch: the input sets must hold exactly n_reads * max(n_keys, 1) rows");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "fetch: the row length must be a power of two");
+    if (T > ((uint64_t)1 << 27))   // a slot holds a u32 row index, 2 T slots a u32 offset
+        return fail(ctx, KZG_E_ARG, "fetch: the row length must be at most 2^27");
+    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
+    if (lay.usable) {
+        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "fetch: usable must be in [1, T - 1] (0: all T rows are read)");
+        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
+            return fail(ctx, KZG_E_ARG, "fetch: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
+        if (!lay.tail_be32) return fail(ctx, KZG_E_ARG, "fetch: tail_be32 must be given when usable > 0");
+        for (uint64_t j = 0; j < n_out * (T - lay.usable); j++)
+            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
+                return fail(ctx, KZG_E_ARG, "fetch: tail scalars must be canonical (< r)");
+    } else if (lay.tail_be32) {
+        return fail(ctx, KZG_E_ARG, "fetch: tail_be32 must be null in the plain layout (usable = 0)");
+    }
+    if (int rc2 = rows_reserve(ctx, "fetch", pend, (size_t)n_out * T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    bool overrun = false;
+    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    uint64_t missing[KZG_MAX_BATCH_OPEN], first[KZG_MAX_BATCH_OPEN];
+    rc = rows_fetch_dev(ctx, H, i, it, tt, n_reads, n_keys, w_tab, index, T, pend.buf.as<uint32_t>(), c48, missing, first, &overrun,
+                        lay.usable ? &lay : nullptr);
+    if (rc) return rc;
+    if (overrun)
+        return fail(ctx, KZG_E_HIP, "fetch: a probe walk of the hash join reached its bound (the slot table held no empty "
+                                    "slot): no set was created");
+    memcpy(out_commitments48, c48, 48 * (size_t)n_out);
+    memcpy(out_missing, missing, 8 * (size_t)n_reads);
+    memcpy(out_first_missing, first, 8 * (size_t)n_reads);
+    *out_handle = rows_insert(ctx, pend, i, (uint32_t)n_out, T);
+    return KZG_OK;
+}
+
 // The check of a _sel builder's selector arguments (SelCall, rows_impl.h): sel_index[l] is KZG_NO_SELECTOR or indexes the
 // concatenated rows of the sel_handles sets, which must be of the call's worker and row length.  The distinct rows named go
 // into sp (a row that serves several lookups is transformed once).
@@ -1970,6 +2045,13 @@ int kzg_rows_commit_recurrence(kzg_ctx* ctx, uint32_t n_input_handles, const uin
                                uint8_t* out_closings32, uint64_t* out_handle) {
     return rows_recurrence(ctx, UINT32_MAX, n_input_handles, input_handles, n_recs, recs, opts, out_commitments48,
                            out_closings32, out_handle);
+}
+int kzg_rows_commit_fetch(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_table_handles,
+                          const uint64_t* table_handles, uint32_t n_reads, uint32_t n_keys, uint32_t flags,
+                          const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_missing,
+                          uint64_t* out_first_missing, uint64_t* out_handle) {
+    return rows_fetch(ctx, UINT32_MAX, n_input_handles, input_handles, n_table_handles, table_handles, n_reads, n_keys, flags, opts,
+                      out_commitments48, out_missing, out_first_missing, out_handle);
 }
 int kzg_rows_commit_lookup_sum(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_table_handles,
                                const uint64_t* table_handles, uint64_t mult_handle, uint32_t n_lookups, uint32_t width,

@@ -103,6 +103,7 @@ class HipEngine:
         self.scale = self.machines_scale = 0
         self.verifier = None          # host-side pairing verifier (zkp_subnet_amd.verifier.Verifier)
         self._set_len: Dict[int, Tuple[int, int]] = {}   # handle -> (worker, row length) of the live sets made through RowSet
+        self._set_rows: Dict[int, int] = {}   # handle -> rows of those sets (commit_fetch: the table's width sizes its output)
         if window:
             self._chk(self._lib.kzg_set_window(self._h, window))
 
@@ -902,6 +903,48 @@ class HipEngine:
             raise bad(f"the tail must hold exactly n_recs * (T - usable - 1) = {n_cols * (T - usable - 1)} scalars, not {len(tail)}")
         return wi, T, (usable, b"".join(tail) if tail else None)
 
+    # ---- a set built from sets: columns read out of a resident table, by key or by row index
+    def commit_fetch(self, input_sets: Sequence[object], table_sets: Sequence[object], n_reads: int, n_keys: int,
+                     with_index: bool = False, usable: Optional[int] = None,
+                     tail: Sequence[bytes] = ()) -> Tuple["RowSet", List[int], List[Optional[int]]]:
+        """kzg_rows_commit_fetch.  The concatenated rows of table_sets are the table's columns: the first n_keys the key, the
+        others the payload.  The concatenated rows of input_sets are n_reads reads of n_keys rows each (read-major); with n_keys
+        = 0 a read is ONE row of row indices and every table column is payload.  Each cell takes the payload of the smallest
+        table row whose key equals the cell's key (with_index: that row number first), or zeros where there is none.  Returns
+        (the new RowSet of n_reads * (payload columns + with_index) rows in read order, per read the number of cells without a
+        table row, per read the smallest such cell or None).  usable = None reads all T rows; otherwise only cells and table
+        rows [0, usable) take part and row usable + s of output column c takes tail[c * (T - usable) + s] (32 bytes each,
+        column-major; there is no closing row)."""
+        what = "commit_fetch"
+        ni, hi = self._handle_array(input_sets, f"{what} (inputs)")
+        nt, ht = self._handle_array(table_sets, f"{what} (table)")
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: {why}")   # noqa: E731
+        cap = _native.KZG_MAX_BATCH_OPEN
+        if any(isinstance(v, bool) or not isinstance(v, int) for v in (n_reads, n_keys)) or not isinstance(with_index, bool):
+            raise bad("n_reads and n_keys must be integers and with_index a bool")
+        if not 1 <= n_reads <= cap or not 0 <= n_keys <= cap or n_reads * max(n_keys, 1) > cap:
+            raise bad(f"n_reads >= 1, n_keys >= 0, n_reads * max(n_keys, 1) <= {cap}")
+        if with_index and n_keys == 0:
+            raise bad("with_index needs n_keys >= 1 (by row index the address column is the index)")
+        widths = [x.k if hasattr(x, "handle") else self._set_rows.get(int(x)) for x in table_sets]
+        if any(k is None for k in widths):   # (n_out sizes the tail and the RowSet that is returned)
+            raise bad("the row count of the table sets is unknown to this engine (they were not committed through it)")
+        w_tab = sum(widths)
+        if n_keys > w_tab:
+            raise bad(f"n_keys = {n_keys} exceeds the {w_tab} table rows")
+        n_out = n_reads * (w_tab - n_keys + int(with_index))
+        if not 1 <= n_out <= cap:
+            raise bad(f"n_reads * (payload rows + with_index) = {n_out} output rows must be in [1, {cap}]")
+        wi, T, lay = self._column_layout(what, list(input_sets) + list(table_sets), n_out, "n_out", "read", usable, tail)
+        opts = _native.DeriveOpts(*lay) if lay else None
+        c, h = ctypes.create_string_buffer(48 * cap), ctypes.c_uint64(0)
+        miss, first = (ctypes.c_uint64 * n_reads)(), (ctypes.c_uint64 * n_reads)()
+        self._chk(self._lib.kzg_rows_commit_fetch(self._h, ni, hi, nt, ht, n_reads, n_keys,
+                                                  _native.KZG_FETCH_INDEX if with_index else 0,
+                                                  ctypes.byref(opts) if opts is not None else None, c, miss, first, ctypes.byref(h)))
+        return (RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]), [int(v) for v in miss],
+                [None if int(v) == _native.KZG_FETCH_NONE else int(v) for v in first])
+
     # ---- a third set built from sets: the PLONK quotient (round 3), computed and committed on the device
     def commit_quotient(self, sets: Sequence[object], terms: Sequence[Tuple[bytes, Sequence[int]]], perm: Optional[dict] = None,
                         ext_log: int = 2, n_pieces: int = 3) -> "RowSet":
@@ -1189,6 +1232,7 @@ class HipEngine:
         """Frees a committed set (kzg_rows_release); KzgError(KZG_E_ARG) for an unknown or already released handle."""
         self._chk(self._lib.kzg_rows_release(self._h, int(handle)))
         self._set_len.pop(int(handle), None)
+        getattr(self, "_set_rows", {}).pop(int(handle), None)
 
     def rows_stats(self) -> Tuple[int, int]:
         """(live committed sets, device bytes their rows hold)."""
@@ -1672,6 +1716,8 @@ class RowSet:
         self.engine, self.handle, self.i, self.k, self.T = engine, handle, i, k, T
         if T is not None and hasattr(engine, "_set_len"):
             engine._set_len[int(handle)] = (i, T)   # what a _zk builder needs when it is handed the bare handle
+        if hasattr(engine, "_set_rows"):
+            engine._set_rows[int(handle)] = k
         self.commitments = commitments
         self.released = False
 

@@ -224,6 +224,11 @@ class MultiDeviceClient:
     def worker_commit_recurrence(self, input_handles: Sequence[int], recs, usable=None, tail=()):
         return self._routed_builder("worker_commit_recurrence", [input_handles], input_handles, recs, usable, tail)
 
+    def worker_commit_fetch(self, input_handles: Sequence[int], table_handles: Sequence[int], n_reads, n_keys, with_index=False,
+                            usable=None, tail=()):
+        return self._routed_builder("worker_commit_fetch", [input_handles, table_handles], input_handles, table_handles,
+                                    n_reads, n_keys, with_index, usable, tail)
+
     def worker_commit_quotient_zk(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None, ext_log=2,
                                   n_pieces=3):
         return self._routed_builder("worker_commit_quotient_zk", [handles], handles, terms, perm, lookup, active_row, ext_log,
