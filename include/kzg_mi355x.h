@@ -192,6 +192,33 @@ int kzg_rows_open(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uin
                   uint8_t* out_evals32 /* sum popcount(masks)*32 */, uint8_t* out_proofs48 /* m*48 */);
 int kzg_rows_release(kzg_ctx* ctx, uint64_t handle);
 int kzg_rows_stats(kzg_ctx* ctx, uint64_t out_live_sets_bytes[2]);
+/* Typed columns in, cells of resident rows back out: the two ends of a witness that otherwise never leaves the device.
+ * kzg_rows_commit_typed: kzg_rows_commit whose k rows arrive one column each, as integers of their natural width instead of 32
+ * big-endian bytes per cell.  Column c holds cols[c].count <= T cells at cols[c].data (host memory, any alignment; native
+ * little-endian for the integer kinds, 32 big-endian bytes per cell for KZG_COL_BE32); cells [count, T) take fill_be32 (null:
+ * 0).  A negative cell x of a signed kind is r - |x|.  The set, its handle, commitments, buffer contents and kzg_rows_stats
+ * accounting are those of kzg_rows_commit on the same values written as be32 rows; only k * count * width bytes cross the
+ * host link.  The checks of kzg_rows_commit on i, T and evaluation_form apply; k outside [1, KZG_MAX_BATCH_OPEN], an unknown
+ * kind, count > T, a null data with count > 0, a KZG_COL_BE32 cell or a fill >= r: KZG_E_ARG, and no set is left behind.
+ * kzg_rows_read: cells [first, first + count) of row `row` of the concatenated sets (numbered as in kzg_rows_open), as the
+ * values on the domain (evaluation_form = 1: what was uploaded or built; T must be a power of two) or the coefficients
+ * (evaluation_form = 0).  `kind` chooses the output: KZG_COL_BE32 writes 32 big-endian bytes per cell, an integer kind
+ * native little-endian integers of its width, where a value >= r - 2^(w-1) reads as negative for the signed kinds.  A cell
+ * that does not fit the kind is written as 0 and counted: out_overflow[0] = how many, out_overflow[1] = the smallest such
+ * row index (UINT64_MAX: none); that is no error.  first + count > T, a row outside the concatenation, a quotient accumulator,
+ * an unknown, released or stale handle: KZG_E_ARG.  count = 0 succeeds and writes nothing.  The sets are unchanged; reads
+ * run beside opens of the same set, under the rules of kzg_rows_open for a release or an SRS load that races them. */
+enum { KZG_COL_BE32 = 0, KZG_COL_U8, KZG_COL_U16, KZG_COL_U32, KZG_COL_U64, KZG_COL_I32, KZG_COL_I64 };
+typedef struct {
+    const void* data;         /* `count` cells */
+    uint64_t count;           /* <= T */
+    uint32_t kind;            /* KZG_COL_* */
+    const uint8_t* fill_be32; /* 32 bytes, canonical; NULL: 0 */
+} kzg_col;
+int kzg_rows_commit_typed(kzg_ctx* ctx, uint32_t i, uint32_t k, const kzg_col* cols /* k */, uint64_t T, int evaluation_form,
+                          uint8_t* out_commitments48 /* k*48 */, uint64_t* out_handle);
+int kzg_rows_read(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t row, uint64_t first, uint64_t count,
+                  uint32_t kind, int evaluation_form, void* out /* count * width */, uint64_t out_overflow[2]);
 /* Evaluate first, then open caller-weighted combinations: the two calls of a Fiat-Shamir opening round (PLONK round 5).
  *   1. kzg_rows_commit the sets; hash the commitments, derive zeta.
  *   2. kzg_rows_eval; hash the evaluations, derive v.
@@ -1166,6 +1193,10 @@ int kzg_multi_rows_open(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uin
                         const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
                         uint8_t* out_proofs48);
 int kzg_multi_rows_release(kzg_multi* mh, uint32_t i, uint64_t handle);
+int kzg_multi_rows_commit_typed(kzg_multi* mh, uint32_t i, uint32_t k, const kzg_col* cols, uint64_t T, int evaluation_form,
+                                uint8_t* out_commitments48, uint64_t* out_handle);
+int kzg_multi_rows_read(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t row, uint64_t first,
+                        uint64_t count, uint32_t kind, int evaluation_form, void* out, uint64_t out_overflow[2]);
 int kzg_multi_rows_eval(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
                         const uint8_t* points_be32, const uint32_t* masks, uint8_t* out_evals32);
 int kzg_multi_rows_open_lincomb(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t k,

@@ -30,6 +30,13 @@ KZG_EXPR_CHECK = 1   # kzg_expr.flags: evaluate and count only
 KZG_EXPR_NONE = 0xffffffffffffffff   # out_first: no non-zero cell
 KZG_FETCH_INDEX = 1   # kzg_rows_commit_fetch flags: lead every read's outputs with the matching row number
 KZG_FETCH_NONE = 0xffffffffffffffff   # out_first_missing: no miss
+KZG_COL_BE32, KZG_COL_U8, KZG_COL_U16, KZG_COL_U32, KZG_COL_U64, KZG_COL_I32, KZG_COL_I64 = range(7)   # kzg_col.kind
+KZG_READ_NONE = 0xffffffffffffffff   # kzg_rows_read out_overflow[1]: no cell overflowed
+# kind -> (cell width in bytes, signed); name -> kind for the text client
+COL_KINDS = {KZG_COL_BE32: (32, False), KZG_COL_U8: (1, False), KZG_COL_U16: (2, False), KZG_COL_U32: (4, False),
+             KZG_COL_U64: (8, False), KZG_COL_I32: (4, True), KZG_COL_I64: (8, True)}
+COL_DTYPES = {"fr": KZG_COL_BE32, "u8": KZG_COL_U8, "u16": KZG_COL_U16, "u32": KZG_COL_U32, "u64": KZG_COL_U64,
+              "i32": KZG_COL_I32, "i64": KZG_COL_I64}
 KZG_OK, KZG_E_ARG, KZG_E_SCALAR, KZG_E_POINT, KZG_E_HIP, KZG_E_NOMEM, KZG_E_BUSY, KZG_E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
 STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_SCALAR", -3: "E_POINT", -4: "E_HIP", -5: "E_NOMEM", -6: "E_BUSY", -7: "E_COMM"}
 TIMING_NAMES = ["decode", "ntt", "digits", "scan", "scatter", "accumulate", "fixup", "tree", "final", "poly", "total", "collective"]
@@ -90,6 +97,11 @@ class DeriveOp(ctypes.Structure):
     _fields_ = [("kind", _U32), ("row", _U32), ("bits", _U32), ("count", _U32)]
 
 
+class Col(ctypes.Structure):
+    """kzg_col"""
+    _fields_ = [("data", ctypes.c_void_p), ("count", ctypes.c_uint64), ("kind", ctypes.c_uint32), ("fill_be32", ctypes.c_char_p)]
+
+
 class DeriveOpts(ctypes.Structure):
     """kzg_derive_opts"""
     _fields_ = [("usable", _U64), ("tail_be32", _B)]
@@ -148,6 +160,8 @@ SYMBOLS = {
     "kzg_rows_commit": (_I, [_P, _U32, _U32, _B, _U64, _I, _B, ctypes.POINTER(_U64)]),
     "kzg_rows_open": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _B, ctypes.POINTER(_U32), _B, _B, _B]),
     "kzg_rows_release": (_I, [_P, _U64]),
+    "kzg_rows_commit_typed": (_I, [_P, _U32, _U32, ctypes.POINTER(Col), _U64, _I, _B, ctypes.POINTER(_U64)]),
+    "kzg_rows_read": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _U64, _U64, _U32, _I, ctypes.c_void_p, ctypes.POINTER(_U64)]),
     "kzg_rows_stats": (_I, [_P, ctypes.POINTER(_U64)]),
     "kzg_rows_eval": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _B, ctypes.POINTER(_U32), _B]),
     "kzg_rows_open_lincomb": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _U32, _B, _B, _B, _B]),
@@ -260,6 +274,9 @@ SYMBOLS = {
     "kzg_multi_rows_commit": (_I, [_P, _U32, _U32, _B, _U64, _I, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_open": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _B, ctypes.POINTER(_U32), _B, _B, _B]),
     "kzg_multi_rows_release": (_I, [_P, _U32, _U64]),
+    "kzg_multi_rows_commit_typed": (_I, [_P, _U32, _U32, ctypes.POINTER(Col), _U64, _I, _B, ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_read": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _U64, _U64, _U32, _I, ctypes.c_void_p,
+                                 ctypes.POINTER(_U64)]),
     "kzg_multi_rows_eval": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _B, ctypes.POINTER(_U32), _B]),
     "kzg_multi_rows_open_lincomb": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _U32, _B, _B, _B, _B]),
     "kzg_multi_rows_commit_shplonk": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _U32, _B, ctypes.POINTER(_U32), _B, _B,

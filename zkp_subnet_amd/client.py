@@ -15,10 +15,11 @@ from __future__ import annotations
 import logging
 import os
 import secrets
+import struct
 from typing import Any, Dict, List, Optional, Sequence
 
 from . import codec
-from ._native import (KZG_E_ARG, KZG_E_POINT, KZG_E_SCALAR, KZG_MAX_BATCH_OPEN, KZG_MAX_OPEN_POINTS, KZG_MAX_SHPLONK_POINTS,
+from ._native import (COL_DTYPES, COL_KINDS, KZG_E_ARG, KZG_E_POINT, KZG_E_SCALAR, KZG_MAX_BATCH_OPEN, KZG_MAX_OPEN_POINTS, KZG_MAX_SHPLONK_POINTS,
                       KZG_MAX_SHPLONK_ROWS, KzgError, open_masks, shplonk_masks)
 
 R_MODULUS = codec.R_MODULUS
@@ -270,6 +271,55 @@ class Client:
             raise codec.CodecError("worker_commit_rows: rows of unequal length")
         rs = self.engine.commit_rows(self._slice(i), [codec.fr_list_to_be32(p) for p in polys], True)
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments]}
+
+    @_guard
+    def worker_commit_rows_typed(self, i: int, columns: Sequence[object], fills: Optional[Sequence[Optional[str]]] = None,
+                                 T: Optional[int] = None):
+        """Extension: worker_commit_rows whose columns arrive as integers of their natural width.  A column is a C-contiguous
+        one-dimensional buffer of u8, u16, u32, u64, i32 or i64 (a numpy array, an array.array), bytes of 32 big-endian bytes
+        per cell, or the wire list of strings of worker_commit_rows, which goes through the codec as there: one call can mix
+        an Fr column with typed ones.  T defaults to the longest column; a shorter column's cells behind its end take fills[c]
+        (a wire string; null, or no fills at all: 0).  A negative cell x is r - |x|.  Returns what worker_commit_rows returns
+        for the same values: the set is an ordinary one."""
+        what = "worker_commit_rows_typed"
+        k = len(columns)
+        if k == 0 or k > KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"{what}: {k} columns, expected 1 .. {KZG_MAX_BATCH_OPEN}")
+        if fills is not None and len(fills) != k:
+            raise codec.CodecError(f"{what}: {len(fills)} fills for {k} columns (one each, or none at all)")
+        if T is not None and (isinstance(T, bool) or not isinstance(T, int) or T < 1):
+            raise codec.CodecError(f"{what}: T must be a positive integer or null")
+        cols = []
+        for c, col in enumerate(columns):
+            if isinstance(col, (list, tuple)):
+                col = codec.fr_list_to_be32(col)
+            fill = None if fills is None or fills[c] is None else codec.fr_to_be32(fills[c])
+            cols.append((col, fill))
+        rs = self.engine.commit_rows_typed(self._slice(i), cols, True, T)
+        return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments]}
+
+    @_guard
+    def worker_read_rows(self, handles: Sequence[int], row: int, first: int, count: int, dtype: str = "fr"):
+        """Extension: cells [first, first + count) of row `row` of committed sets (rows numbered as in worker_open_rows), as
+        the values on the domain: what was uploaded, or what a builder wrote.  dtype "fr" returns wire strings; "u8", "u16",
+        "u32", "u64", "i32" and "i64" return Python integers, where a value >= r - 2^(w-1) reads as negative for the signed
+        ones.  A cell that does not fit the dtype reads 0 and is counted: `overflow`, and `first_overflow`, the smallest such
+        row index (null: none).  The sets are unchanged."""
+        what = "worker_read_rows"
+        hs = _handles(handles)
+        if not isinstance(dtype, str) or dtype not in COL_DTYPES:
+            raise codec.CodecError(f"{what}: dtype must be one of {sorted(COL_DTYPES)}")
+        if any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in (row, first, count)):
+            raise codec.CodecError(f"{what}: row, first and count must be non-negative integers")
+        kind = COL_DTYPES[dtype]
+        raw, overflow, first_overflow = self.engine.read_rows(hs, row, first, count, kind, True)
+        if dtype == "fr":
+            cells = codec.be32_to_fr_list(raw)
+        else:
+            width, signed = COL_KINDS[kind]
+            code = {1: "B", 2: "H", 4: "I", 8: "Q"}[width]
+            cells = list(struct.unpack(f"<{count}{code.lower() if signed else code}", raw))
+        return {"cells": cells, "overflow": int(overflow), "first_overflow": first_overflow}
 
     @_guard
     def worker_open_rows(self, handles: Sequence[int], points: Sequence[str], opened: Sequence[Sequence[int]],

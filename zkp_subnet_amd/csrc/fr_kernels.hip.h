@@ -11,6 +11,27 @@ void launch_fr_from_be(hipStream_t s, const uint8_t* be, uint32_t* out, uint64_t
 void launch_fr_from_host32(hipStream_t s, const uint8_t be32[32], uint32_t* out, int to_mont, uint32_t* bad);
 void launch_fr_to_be(hipStream_t s, const uint32_t* in, uint8_t* be, uint64_t n, int from_mont);
 void launch_fr_from_mont(hipStream_t s, const uint32_t* in, uint32_t* out, uint64_t n);
+// typed columns (kzg_rows_commit_typed): the integer columns of one call, packed into one device buffer (each starting on a
+// 16-byte boundary and padded to one), decoded into rows of T Montgomery elements by ONE launch whose argument is this table.
+// Column c: `count` cells of `kind` (a KZG_COL_* integer kind) at packed + off -> out + row * T * 8; cells [count, T) take
+// `fill` (canonical little-endian words); cells [0, skip) are left alone (a be32 column: skip = count, its cells are
+// k_fr_from_be's and the launch writes the fill behind them only).
+#define FR_TYPED_MAX_COLS 16
+struct TypedCol {
+    uint64_t off, count, skip;
+    uint32_t kind, row;
+    uint32_t fill[8];
+};
+struct TypedTab {
+    TypedCol c[FR_TYPED_MAX_COLS];
+};
+static_assert(sizeof(TypedTab) + 64 <= 4096, "the column table rides as a kernel argument");
+void launch_fr_from_typed(hipStream_t s, const uint8_t* packed, const TypedTab& tab, uint32_t ncols, uint32_t* out, uint64_t T);
+// cells [first, first + count) of the Montgomery row `in` narrowed to `kind` (kzg_rows_read): KZG_COL_BE32 writes 32 big-endian
+// bytes per cell, an integer kind its width; ovf[0] counts the cells that do not fit (written as 0), ovf[1] holds
+// UINT64_MAX - the smallest such cell (0: none).  The caller zeroes ovf.
+void launch_fr_narrow(hipStream_t s, const uint32_t* in, uint64_t first, uint64_t count, uint32_t kind, uint8_t* out,
+                      uint64_t* ovf);
 // tw: 2^(log_n-1) Montgomery-form powers of w_n (inverse: of w_n^-1), 12 words each (nine limbs + padding)
 void launch_fr_twiddles(hipStream_t s, uint32_t* tw, int log_n, int inverse);
 void launch_fr_inv_pow2(hipStream_t s, uint32_t* out, int log_n);

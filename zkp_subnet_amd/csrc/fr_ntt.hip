@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "../../include/kzg_mi355x.h"   // the KZG_COL_* kinds of the typed columns
 #include "fr_kernels.hip.h"
 
 static inline uint32_t nblk(uint64_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
@@ -59,6 +60,141 @@ __global__ void __launch_bounds__(256) k_fr_from_mont(const uint32_t* __restrict
     fr9_load(v, in + 8 * j);
     fr9_from_mont(v, v);
     fr9_store(out + 8 * j, v);
+}
+
+// ---- typed columns (kzg_rows_commit_typed / kzg_rows_read): integers of their natural width <-> Montgomery elements
+// x * 2^261 mod r for x < 2^64, below 2r: x has three limbs, so a Montgomery product of radix 2^87 by 2^(261 + 87) mod r
+// does it -- 27 + 24 mads where fr9_to_mont spends 81 + 72.  (x C + q r) / 2^87 < (2^64 + 2^87) r / 2^87 < 2r; a column sum
+// is at most six products below 2^58.  Modelled limb by limb against x * 2^261 % r over the edges and 2 x 10^4 random x.
+FR9_TABLE(fr9_2_348, 0x1c74a235u, 0x1cebd299u, 0x0150fcf8u, 0x18886c4cu, 0x162c0a9du, 0x06cbaa5fu, 0x17bd1efeu, 0x06f2bf4bu, 0x0032f10cu)
+KZG_DEV void fr9_mont_from_u64(fr9_t& r, uint64_t x) {
+    const uint32_t a[3] = {(uint32_t)x & FR9_MASK, (uint32_t)(x >> 29) & FR9_MASK, (uint32_t)(x >> 58)};
+    uint32_t q[3];
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 11; k++) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            const int j = k - i;
+            if (j >= 0 && j < 9) acc += (uint64_t)a[i] * fr9_2_348(j);
+        }
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            const int j = k - i;
+            if (i < k && j >= 1 && j < 9) acc += (uint64_t)q[i] * fr9_r(j);
+        }
+        if (k < 3) {
+            q[k] = (0u - (uint32_t)acc) & FR9_MASK;
+            acc += q[k];
+        } else {
+            r.l[k - 3] = (uint32_t)acc & FR9_MASK;
+        }
+        acc >>= 29;
+    }
+    r.l[8] = (uint32_t)acc;
+}
+// r - a for a canonical a != 0
+KZG_DEV void fr9_neg_canon(fr9_t& r, const fr9_t& a) {
+    int32_t br = 0;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        const int32_t v = (int32_t)fr9_r(i) - (int32_t)a.l[i] + br;
+        br = v >> 29;
+        r.l[i] = (i < 8) ? ((uint32_t)v & FR9_MASK) : (uint32_t)v;
+    }
+}
+// One launch decodes every typed column of a call: grid y = entry of the table, one lane per cell.  A lane reads the aligned
+// dword (qword for the 64-bit kinds) that holds its cell -- every column starts on a 16-byte boundary of `packed` and is
+// padded to one, so the dword of a column's last odd bytes lies inside the buffer -- and writes its element in two 16-byte
+// stores.  Cells at or behind the column's count take the fill (canonical words in the table); cells below its `skip` belong
+// to another decoder and are not touched.
+__global__ void __launch_bounds__(256) k_fr_from_typed(const uint8_t* __restrict__ packed, const TypedTab tab,
+                                                        uint32_t* __restrict__ out, uint64_t T) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T) return;
+    const TypedCol& c = tab.c[blockIdx.y];
+    if (t < c.skip) return;
+    uint32_t* dst = out + 8 * ((uint64_t)c.row * T + t);
+    fr9_t v;
+    if (t >= c.count) {
+        fr9_from_words(v, c.fill);
+        fr9_to_mont(v, v);
+        fr9_store(dst, v);
+        return;
+    }
+    const uint8_t* col = packed + c.off;
+    uint64_t x;
+    bool neg = false;
+    if (c.kind == KZG_COL_U64 || c.kind == KZG_COL_I64) {
+        x = reinterpret_cast<const uint64_t*>(col)[t];
+        if (c.kind == KZG_COL_I64 && (int64_t)x < 0) { neg = true; x = 0 - x; }
+    } else if (c.kind == KZG_COL_U32 || c.kind == KZG_COL_I32) {
+        const uint32_t w = reinterpret_cast<const uint32_t*>(col)[t];
+        x = w;
+        if (c.kind == KZG_COL_I32 && (int32_t)w < 0) { neg = true; x = 0u - w; }
+    } else if (c.kind == KZG_COL_U16) {
+        x = (reinterpret_cast<const uint32_t*>(col)[t >> 1] >> (16 * (uint32_t)(t & 1))) & 0xffffu;
+    } else {
+        x = (reinterpret_cast<const uint32_t*>(col)[t >> 2] >> (8 * (uint32_t)(t & 3))) & 0xffu;
+    }
+    fr9_mont_from_u64(v, x);
+    fr9_canon(v, v);
+    if (neg) fr9_neg_canon(v, v);   // (|x| is in [1, 2^63]: its residue is not zero)
+    fr9_store(dst, v);
+}
+// cells [first, first + count) of a Montgomery row -> the caller's kind: 32 big-endian bytes, or integers of the kind's width
+// (a value >= r - 2^(w-1) is negative for the signed kinds).  A value that does not fit is written as 0 and counted, per wave:
+// ovf[0] += how many, ovf[1] = max(UINT64_MAX - t) over such cells t (0: none; the host turns it back into the smallest t).
+__global__ void __launch_bounds__(256) k_fr_narrow(const uint32_t* __restrict__ in, uint64_t first, uint64_t count, uint32_t kind,
+                                                    uint8_t* __restrict__ out, unsigned long long* __restrict__ ovf) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    const uint64_t t = first + j;
+    fr9_t v;
+    fr9_load(v, in + 8 * t);
+    fr9_from_mont(v, v);
+    uint32_t w[8];
+    fr9_to_words(w, v);
+    if (kind == KZG_COL_BE32) {
+        limbs_to_be<8>(out + 32 * j, w);
+        return;
+    }
+    const bool is_signed = kind == KZG_COL_I32 || kind == KZG_COL_I64;
+    const int bits = kind == KZG_COL_U8 ? 8 : kind == KZG_COL_U16 ? 16 : (kind == KZG_COL_U32 || kind == KZG_COL_I32) ? 32 : 64;
+    uint64_t x = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+    bool high = false;
+#pragma unroll
+    for (int i = 2; i < 8; i++) high |= w[i] != 0;
+    bool fits;
+    if (!is_signed) {
+        fits = !high && (bits == 64 || (x >> bits) == 0);
+    } else {
+        fits = !high && (x >> (bits - 1)) == 0;
+        if (!fits) {   // d = r - value: negative when 1 <= d <= 2^(w-1)
+            fr9_t d;
+            fr9_neg_canon(d, v);
+            fr9_to_words(w, d);
+            const uint64_t m = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+            bool dh = false;
+#pragma unroll
+            for (int i = 2; i < 8; i++) dh |= w[i] != 0;
+            if (!dh && m != 0 && m <= ((uint64_t)1 << (bits - 1))) {
+                fits = true;
+                x = 0 - m;
+            }
+        }
+    }
+    if (!fits) x = 0;
+    // one pair of atomics per wave: the lanes that are here hold ascending t, so the lowest set bit is the wave's smallest
+    const unsigned long long m = __ballot(!fits);
+    if (m && (threadIdx.x & 63) == (uint32_t)__ffsll((long long)m) - 1) {
+        atomicAdd(ovf, (unsigned long long)__popcll(m));
+        atomicMax(ovf + 1, ~0ull - (unsigned long long)t);
+    }
+    if (bits == 8) out[j] = (uint8_t)x;
+    else if (bits == 16) reinterpret_cast<uint16_t*>(out)[j] = (uint16_t)x;
+    else if (bits == 32) reinterpret_cast<uint32_t*>(out)[j] = (uint32_t)x;
+    else reinterpret_cast<uint64_t*>(out)[j] = x;
 }
 
 // ------------------------------------------------------------------------------------------------ twiddles
@@ -572,6 +708,14 @@ void launch_fr_to_be(hipStream_t s, const uint32_t* in, uint8_t* be, uint64_t n,
 }
 void launch_fr_from_mont(hipStream_t s, const uint32_t* in, uint32_t* out, uint64_t n) {
     if (n) k_fr_from_mont<<<nblk(n, 256), 256, 0, s>>>(in, out, n);
+}
+void launch_fr_from_typed(hipStream_t s, const uint8_t* packed, const TypedTab& tab, uint32_t ncols, uint32_t* out, uint64_t T) {
+    if (ncols && T) k_fr_from_typed<<<dim3(nblk(T, 256), ncols), 256, 0, s>>>(packed, tab, out, T);
+}
+void launch_fr_narrow(hipStream_t s, const uint32_t* in, uint64_t first, uint64_t count, uint32_t kind, uint8_t* out,
+                      uint64_t* ovf) {
+    if (count)
+        k_fr_narrow<<<nblk(count, 256), 256, 0, s>>>(in, first, count, kind, out, reinterpret_cast<unsigned long long*>(ovf));
 }
 void launch_fr_twiddles(hipStream_t s, uint32_t* tw, int log_n, int inverse) {
     if (log_n < 1) return;

@@ -393,7 +393,19 @@ int kzg_multi_rows_commit(kzg_multi* mh, uint32_t i, uint32_t k, const uint8_t* 
         return kzg_rows_commit(c, s, k, rows_be32, T, evaluation_form, out_commitments48, out_handle);
     });
 }
+int kzg_multi_rows_commit_typed(kzg_multi* mh, uint32_t i, uint32_t k, const kzg_col* cols, uint64_t T, int evaluation_form,
+                                uint8_t* out_commitments48, uint64_t* out_handle) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_rows_commit_typed(c, s, k, cols, T, evaluation_form, out_commitments48, out_handle);
+    });
+}
 // from here on every call is the entry its single-context twin (serve.hip) calls, with the slice as expect_i
+int kzg_multi_rows_read(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t row, uint64_t first,
+                        uint64_t count, uint32_t kind, int evaluation_form, void* out, uint64_t out_overflow[2]) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_read(c, s, n_handles, handles, row, first, count, kind, evaluation_form, out, out_overflow);
+    });
+}
 int kzg_multi_rows_open(kzg_multi* mh, uint32_t i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
                         const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
                         uint8_t* out_proofs48) {

@@ -37,6 +37,8 @@ int rows_shplonk(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint
                  const uint8_t* points_be32, const uint32_t* masks, const uint8_t* coeffs_be32, uint8_t* out_commitment48,
                  uint64_t* out_handle);
 int rows_release(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle);
+int rows_read(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t row, uint64_t first,
+              uint64_t count, uint32_t kind, int evaluation_form, void* out, uint64_t* out_overflow);
 // zk: the blinding rows of the _zk and _chain calls.  start_be32: the _chain call's start of z (null: not a chain, z starts at 1)
 int rows_grand_product(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
                        uint32_t n_sigma_handles, const uint64_t* sigma_handles, uint32_t k, const uint8_t* shifts_be32,

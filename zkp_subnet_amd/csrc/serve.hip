@@ -1933,6 +1933,82 @@ int rows_release(kzg_ctx* ctx, uint32_t expect_i, uint64_t handle) {
     return KZG_OK;
 }
 
+
+// width in bytes of a typed column's cell (0: no such kind)
+static uint32_t col_width(uint32_t kind) {
+    switch (kind) {
+        case KZG_COL_BE32: return 32;
+        case KZG_COL_U8: return 1;
+        case KZG_COL_U16: return 2;
+        case KZG_COL_U32: case KZG_COL_I32: return 4;
+        case KZG_COL_U64: case KZG_COL_I64: return 8;
+    }
+    return 0;
+}
+// kzg_rows_read: the lookup of an open; the row is read in place under the call's reference (a read changes nothing, so it
+// runs beside opens of the same set), transformed forward into lane scratch when the domain values are asked for, narrowed
+// into the lane's output buffer and copied out once the lane's record -- which carries the two overflow words -- is back
+int rows_read(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t row, uint64_t first,
+              uint64_t count, uint32_t kind, int evaluation_form, void* out, uint64_t* out_overflow) {
+    if (!ctx || !handles || !out_overflow || (count && !out)) return KZG_E_ARG;
+    if (n_handles == 0 || n_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "row-set read: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    const uint32_t width = col_width(kind);
+    if (!width) return fail(ctx, KZG_E_ARG, "row-set read: unknown kind");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsRefs refs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;
+    Lane& L = H.L();
+    RowTab rt;
+    uint32_t k = 0, i = 0;
+    uint64_t T = 0;
+    if (int rc = rows_lookup(ctx, "row-set read", expect_i, n_handles, handles, refs, rt, &k, &i, &T)) return rc;
+    if (row >= k) return fail(ctx, KZG_E_ARG, "row-set read: row outside the concatenated sets");
+    if (first > T || count > T - first) return fail(ctx, KZG_E_ARG, "row-set read: first + count exceeds the row length");
+    const int lg = ilog2_exact(T);
+    if (evaluation_form && lg < 0)
+        return fail(ctx, KZG_E_ARG, "row-set read: the values on the domain need a row length that is a power of two");
+    out_overflow[0] = 0;
+    out_overflow[1] = UINT64_MAX;
+    if (count == 0) {
+        H.clean = true;
+        return KZG_OK;
+    }
+    prof_begin(ctx, L);
+    int rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    const uint32_t* src = rt.r[row];
+    if (evaluation_form && lg > 0) {
+        uint32_t* tw = nullptr;
+        rc = ensure_twiddles(ctx, L, lg, 0, &tw, nullptr);
+        if (rc) return rc;
+        HIPCHK(ctx, L.coeffB.ensure(T * 32));
+        HIPCHK(ctx, L.ntt_mid.ensure(T * 48));
+        Span sp(ctx, L, KZG_T_NTT);
+        launch_fr_ntt(L.stream, src, L.coeffB.as<uint32_t>(), lg, tw, nullptr, L.ntt_mid.as<uint32_t>());
+        src = L.coeffB.as<uint32_t>();
+    }
+    const uint64_t bytes = count * width;
+    HIPCHK(ctx, L.out_be.ensure(bytes));
+    uint64_t* ovf = reinterpret_cast<uint64_t*>(L.tail + TB_EVAL);   // comes back with the lane's record
+    {
+        Span sp(ctx, L, KZG_T_DECODE);
+        HIPCHK(ctx, hipMemsetAsync(ovf, 0, 16, L.stream));
+        launch_fr_narrow(L.stream, src, first, count, kind, L.out_be.as<uint8_t>(), ovf);
+    }
+    L.expect_short = true;   // one transform and one pass over a row, no MSM: finish() may poll for the record
+    rc = finish(ctx, L);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpy(out, L.out_be.p, bytes, hipMemcpyDeviceToHost));
+    uint64_t rec[2];
+    memcpy(rec, L.pin + TB_EVAL, 16);
+    out_overflow[0] = rec[0];
+    out_overflow[1] = rec[1] ? UINT64_MAX - rec[1] : UINT64_MAX;
+    H.clean = true;
+    return KZG_OK;
+}
+
 }  // namespace kzg_impl
 
 extern "C" {
@@ -1970,6 +2046,85 @@ int kzg_rows_commit(kzg_ctx* ctx, uint32_t i, uint32_t k, const uint8_t* rows_be
     const uint64_t h = rows_insert(ctx, pend, i, k, T);
     *out_handle = h;
     return KZG_OK;
+}
+// kzg_rows_commit with the rows as typed columns: everything but the upload and decode in front of rows_commit_dev is that
+// call's.  The integer columns are packed into the lane's input buffer (each on a 16-byte boundary, one copy per column) and
+// decoded by one launch; be32 columns go through the decoder of upload_fr, whose flag a cell >= r raises
+int kzg_rows_commit_typed(kzg_ctx* ctx, uint32_t i, uint32_t k, const kzg_col* cols, uint64_t T, int evaluation_form,
+                          uint8_t* out_commitments48, uint64_t* out_handle) {
+    if (!ctx || !cols || !out_commitments48 || !out_handle) return KZG_E_ARG;
+    if (k == 0 || k > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "typed row-set commit: k must be in [1, KZG_MAX_BATCH_OPEN]");
+    static_assert(KZG_MAX_BATCH_OPEN <= FR_TYPED_MAX_COLS, "one table holds every column of a call");
+    TypedTab tab;
+    memset(&tab, 0, sizeof(tab));
+    uint64_t off[KZG_MAX_BATCH_OPEN], packed = 0;
+    uint32_t n_typed = 0;
+    for (uint32_t c = 0; c < k; c++) {
+        const kzg_col& col = cols[c];
+        const uint32_t width = col_width(col.kind);
+        if (!width) return fail(ctx, KZG_E_ARG, "typed row-set commit: unknown column kind");
+        if (col.count > T) return fail(ctx, KZG_E_ARG, "typed row-set commit: a column holds more than T cells");
+        if (col.count && !col.data) return fail(ctx, KZG_E_ARG, "typed row-set commit: a column with cells has no data");
+        if (col.fill_be32 && !fr_be32_canonical(col.fill_be32))
+            return fail(ctx, KZG_E_ARG, "typed row-set commit: a fill must be a canonical scalar (< r)");
+        off[c] = packed;
+        packed += (col.count * width + 15) & ~(uint64_t)15;
+        if (col.kind == KZG_COL_BE32 && col.count == T) continue;   // all cells through the be32 decoder: no fill to write
+        TypedCol& e = tab.c[n_typed++];
+        e.off = off[c];
+        e.count = col.count;
+        e.skip = col.kind == KZG_COL_BE32 ? col.count : 0;           // (a short be32 column: the launch writes its fill only)
+        e.kind = col.kind;
+        e.row = c;
+        for (int w = 0; col.fill_be32 && w < 8; w++) {
+            uint32_t be;
+            memcpy(&be, col.fill_be32 + 4 * (7 - w), 4);
+            e.fill[w] = __builtin_bswap32(be);
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;
+    Lane& L = H.L();
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (evaluation_form && T > 1 && ilog2_exact(T) < 0)
+        return fail(ctx, KZG_E_ARG, "evaluation-form row length must be a power of two");
+    const size_t bytes = (size_t)k * T * 32;
+    if (int rc2 = rows_reserve(ctx, "typed row-set commit", pend, bytes)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    uint32_t* dst = pend.buf.as<uint32_t>();
+    uint32_t* up = dst;
+    if (evaluation_form && T > 1) {
+        HIPCHK(ctx, L.coeffA.ensure(bytes));
+        up = L.coeffA.as<uint32_t>();
+    }
+    {
+        Span sp(ctx, L, KZG_T_DECODE);
+        HIPCHK(ctx, L.in_be.ensure(packed + 16));
+        uint8_t* in = L.in_be.as<uint8_t>();
+        for (uint32_t c = 0; c < k; c++)
+            if (cols[c].count)
+                HIPCHK(ctx, hipMemcpyAsync(in + off[c], cols[c].data, cols[c].count * col_width(cols[c].kind),
+                                           hipMemcpyHostToDevice, L.stream));
+        launch_fr_from_typed(L.stream, in, tab, n_typed, up, T);
+        for (uint32_t c = 0; c < k; c++)   // (the launch above wrote a be32 column's cells at or behind `count` only)
+            if (cols[c].kind == KZG_COL_BE32)
+                launch_fr_from_be(L.stream, in + off[c], up + (uint64_t)c * T * 8, cols[c].count, 1, L.flags());
+    }
+    rc = rows_commit_dev(ctx, H, i, up, k, T, evaluation_form, dst, out_commitments48);
+    if (rc == KZG_E_SCALAR) return fail(ctx, KZG_E_ARG, "typed row-set commit: a be32 cell is not a canonical scalar (< r)");
+    if (rc) return rc;
+    *out_handle = rows_insert(ctx, pend, i, k, T);
+    return KZG_OK;
+}
+int kzg_rows_read(kzg_ctx* ctx, uint32_t n_handles, const uint64_t* handles, uint32_t row, uint64_t first, uint64_t count,
+                  uint32_t kind, int evaluation_form, void* out, uint64_t out_overflow[2]) {
+    return rows_read(ctx, UINT32_MAX, n_handles, handles, row, first, count, kind, evaluation_form, out, out_overflow);
 }
 // The exports below are the entries of rows_impl.h for any one worker (UINT32_MAX): what a variant adds goes in as a Blind / SelCall
 // on the stack, what it lacks as null

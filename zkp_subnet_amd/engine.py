@@ -87,6 +87,40 @@ def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: 
     return [(c.to_bytes(32, "big"), list(fs)) for fs, c in out.items()]
 
 
+_TYPED_FORMATS = {("B", 1): _native.KZG_COL_U8, ("H", 2): _native.KZG_COL_U16, ("I", 4): _native.KZG_COL_U32,
+                  ("L", 8): _native.KZG_COL_U64, ("Q", 8): _native.KZG_COL_U64, ("i", 4): _native.KZG_COL_I32,
+                  ("l", 8): _native.KZG_COL_I64, ("q", 8): _native.KZG_COL_I64}
+
+
+def typed_column(col, what: str = "commit_rows_typed"):
+    """One column of commit_rows_typed as (kind, cells, memoryview of its bytes, fill or None).  `col` is a buffer or a
+    (buffer, fill_be32_or_None) pair.  bytes / bytearray of 32 * cells are 32-byte big-endian scalars (KZG_COL_BE32); any other
+    object with the buffer protocol (numpy arrays, array.array, memoryviews) must be one-dimensional and C-contiguous with the
+    native format B, H, I, L / Q, i or l / q at item size 1, 2, 4, 8, 4, 8.  Nothing is copied here; commit_rows_typed hands the
+    library the buffer's own memory when it is writable or a whole bytes object, and one copy of a read-only view otherwise.
+    Raises KzgError(KZG_E_ARG)."""
+    bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: {why}")   # noqa: E731
+    buf, fill = col if isinstance(col, tuple) and len(col) == 2 else (col, None)
+    if fill is not None and (not isinstance(fill, (bytes, bytearray)) or len(fill) != 32):
+        raise bad("a fill is None or 32 big-endian bytes")
+    if isinstance(buf, (bytes, bytearray)):
+        if len(buf) % 32:
+            raise bad("a bytes column holds 32 bytes per cell")
+        return _native.KZG_COL_BE32, len(buf) // 32, memoryview(buf), fill
+    try:
+        mv = memoryview(buf)
+    except TypeError:
+        raise bad(f"a column is bytes or an object with the buffer protocol, not {type(buf).__name__}") from None
+    if mv.ndim != 1 or not mv.c_contiguous:
+        raise bad("a column must be one-dimensional and C-contiguous")
+    fmt = mv.format[1:] if mv.format[:1] in "@=<" and len(mv.format) > 1 else mv.format
+    kind = _TYPED_FORMATS.get((fmt, mv.itemsize))
+    if kind is None:
+        raise bad(f"unsupported buffer format {mv.format!r} with item size {mv.itemsize}: expected B, H, I, L/Q, i or l/q "
+                  f"(u8, u16, u32, u64, i32, i64)")
+    return kind, mv.shape[0], mv, fill
+
+
 class HipEngine:
     # rows from this length up are decoded and uploaded tile by tile (see _Staged); KZG_STREAM_MIN_LOG moves the threshold
     STREAM_MIN = 1 << int(os.environ.get("KZG_STREAM_MIN_LOG", "19"))
@@ -356,6 +390,78 @@ class HipEngine:
         c, h = ctypes.create_string_buffer(48 * k), ctypes.c_uint64(0)
         self._chk(self._lib.kzg_rows_commit(self._h, i, k, rows, T, int(evaluation_form), c, ctypes.byref(h)))
         return RowSet(self, h.value, i, k, T, [c.raw[48 * j:48 * j + 48] for j in range(k)])
+
+    # ---- typed columns in, cells of resident rows back out
+    def commit_rows_typed(self, i: int, columns: Sequence[object], evaluation_form: bool = True,
+                          T: Optional[int] = None) -> "RowSet":
+        """commit_rows whose rows arrive as integer columns of their natural width (kzg_rows_commit_typed): each of the k <=
+        16 columns is a buffer or a (buffer, fill_be32_or_None) pair -- see typed_column for the buffers taken; a bytes column
+        holds 32-byte big-endian scalars, so one call can mix kinds.  T defaults to the longest column; a shorter column's
+        cells [len, T) take its fill (None: 0).  A negative cell x of a signed column is r - |x|.  The set is the one
+        commit_rows makes of the same values; only len * width bytes per column cross the host link."""
+        what = "commit_rows_typed"
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: {why}")   # noqa: E731
+        k = len(columns)
+        if k == 0 or k > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"k = {k} outside [1, {_native.KZG_MAX_BATCH_OPEN}]")
+        cols = [typed_column(c, what) for c in columns]
+        longest = max(n for _, n, _, _ in cols)
+        if T is None:
+            T = longest
+        if isinstance(T, bool) or not isinstance(T, int) or T < 1:
+            raise bad("T must be a positive integer (default: the longest column, which must not be empty)")
+        if longest > T:
+            raise bad(f"a column holds {longest} cells, more than T = {T}")
+        arr, keep = (_native.Col * k)(), []
+        for c, (kind, n, mv, fill) in enumerate(cols):
+            if n == 0:
+                ptr = None
+            elif mv.readonly:   # ctypes takes no address of a read-only buffer: bytes that the view covers whole, else a copy
+                whole = isinstance(mv.obj, bytes) and mv.nbytes == len(mv.obj)
+                raw = mv.obj if whole else mv.tobytes()
+                keep.append(raw)
+                ptr = ctypes.cast(ctypes.c_char_p(raw), ctypes.c_void_p)
+            else:
+                keep.append(mv)
+                ptr = ctypes.c_void_p(ctypes.addressof(ctypes.c_char.from_buffer(mv)))
+            arr[c].data, arr[c].count, arr[c].kind = ptr, n, kind
+            arr[c].fill_be32 = None if fill is None else bytes(fill)
+        c48, h = ctypes.create_string_buffer(48 * k), ctypes.c_uint64(0)
+        self._chk(self._lib.kzg_rows_commit_typed(self._h, i, k, arr, T, int(bool(evaluation_form)), c48, ctypes.byref(h)))
+        del keep
+        return RowSet(self, h.value, i, k, T, [c48.raw[48 * j:48 * j + 48] for j in range(k)])
+
+    def read_rows(self, sets: Sequence[object], row: int, first: int, count: int, kind,
+                  evaluation_form: bool = True) -> Tuple[bytes, int, Optional[int]]:
+        """Cells [first, first + count) of row `row` of the concatenated sets (kzg_rows_read), as the values on the domain
+        (evaluation_form, the default: what was uploaded or built) or the coefficients.  kind: a KZG_COL_* value or its name
+        ("fr", "u8", "u16", "u32", "u64", "i32", "i64").  Returns (bytes, overflow, first_overflow): 32 big-endian bytes per cell
+        for "fr", else native little-endian integers of the kind's width; a value >= r - 2^(w-1) reads as negative for the
+        signed kinds; a cell that does not fit reads 0 and is counted in `overflow`, first_overflow being the smallest such row
+        index (None: none).  The sets are unchanged."""
+        what = "read_rows"
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: {why}")   # noqa: E731
+        kind = _native.COL_DTYPES.get(kind, kind) if isinstance(kind, str) else kind
+        if isinstance(kind, bool) or kind not in _native.COL_KINDS:
+            raise bad(f"kind must be a KZG_COL_* value or one of {sorted(_native.COL_DTYPES)}")
+        if any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 1 << 64 for v in (first, count)):
+            raise bad("first and count must be integers in [0, 2^64)")
+        if isinstance(row, bool) or not isinstance(row, int) or not 0 <= row < _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"row must be an integer in [0, {_native.KZG_MAX_BATCH_OPEN})")
+        n, hs = self._handle_array(sets, what)
+        known = [self._set_len.get(int(getattr(x, "handle", x))) for x in sets]
+        if all(v is not None for v in known) and first + count > min(v[1] for v in known):
+            raise bad("first + count exceeds the row length")   # (before the output buffer is sized by a caller's count)
+        width = _native.COL_KINDS[kind][0]
+        if count > 1 << 32:   # (no row is that long: refused here, before a caller's count sizes the output buffer)
+            raise bad("first + count exceeds the row length")
+        try:
+            out = ctypes.create_string_buffer(max(count * width, 1))
+        except (MemoryError, OverflowError):
+            raise bad(f"no room for {count} cells of {width} bytes: count exceeds any row this host can hold") from None
+        ovf = (ctypes.c_uint64 * 2)()
+        self._chk(self._lib.kzg_rows_read(self._h, n, hs, row, first, count, kind, int(bool(evaluation_form)), out, ovf))
+        return out.raw[:count * width], int(ovf[0]), None if int(ovf[1]) == _native.KZG_READ_NONE else int(ovf[1])
 
     def open_rows(self, sets: Sequence[object], points_be32: Sequence[bytes], opened: Sequence[Sequence[int]],
                   gammas_be32: Sequence[bytes]) -> Tuple[List[List[bytes]], List[bytes]]:

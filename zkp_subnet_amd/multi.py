@@ -113,6 +113,12 @@ class MultiDeviceClient:
             self._row_owner[int(r.json()["handle"])] = int(i)
         return r
 
+    def worker_commit_rows_typed(self, i: int, columns, fills=None, T=None):
+        r = self._for(i).worker_commit_rows_typed(i, columns, fills, T)
+        if r.status_code == 200:
+            self._row_owner[int(r.json()["handle"])] = int(i)
+        return r
+
     def _owner(self, handles) -> Optional[int]:
         try:
             owners = {self._row_owner.get(int(h)) for h in handles}
@@ -143,6 +149,9 @@ class MultiDeviceClient:
 
     def worker_open_rows(self, handles: Sequence[int], points, opened, gammas):
         return self._routed_builder("worker_open_rows", [handles], handles, points, opened, gammas, key=None)
+
+    def worker_read_rows(self, handles: Sequence[int], row, first, count, dtype="fr"):
+        return self._routed_builder("worker_read_rows", [handles], handles, row, first, count, dtype, key=None)
 
     def worker_eval_rows(self, handles: Sequence[int], points, opened):
         return self._routed_builder("worker_eval_rows", [handles], handles, points, opened, key=None)
