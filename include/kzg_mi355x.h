@@ -943,6 +943,58 @@ int kzg_rows_commit_fetch(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t
                           uint32_t flags /* 0 or KZG_FETCH_INDEX */, const kzg_derive_opts* opts /* NULL: plain */,
                           uint8_t* out_commitments48 /* n_out * 48 */, uint64_t* out_missing /* n_reads */,
                           uint64_t* out_first_missing /* n_reads */, uint64_t* out_handle);
+/* THE SIGMA COLUMNS: a set built FROM sets, the permutation rows that kzg_rows_commit_grand_product* takes as "already
+ * resident", built on the device from VARIABLE LABELS -- the shape in which every frontend holds its copy constraints: one id
+ * per wire slot, where a copy constraint is "same id" (commit the ids with kzg_rows_commit_typed).  The concatenated rows of the
+ * label_handles sets are k label columns l_0 .. l_{k-1}, 1 <= k <= KZG_MAX_BATCH_OPEN.  With w_T = 7^((r-1)/T), natural order --
+ * exactly the convention of kzg_rows_commit_grand_product -- cell (c, t) carries the label l_c(w_T^t), taken as its CANONICAL
+ * INTEGER in [0, r); any field element is a label.  Cells with equal labels are one copy class.
+ * Let n = opts->usable, or n = T for the plain layout.  The cells with t < n take part; their flat index is j = c T + t.  The
+ * call builds the permutation sigma in which each class is ONE CYCLE IN ASCENDING FLAT INDEX: a cell maps to the next larger
+ * flat index of its class, the largest to the smallest; and writes sigma_c(w_T^t) = shifts[c'] w_T^t' for the image (c', t').
+ * Two kinds of cell map to themselves:
+ *   FREE CELLS: a participating cell whose label equals opts->free_label_be32 (NULL: no such label) maps to itself, whatever
+ *     else carries that label.  With KZG_COL_I32 label columns the natural choice is -1, which is r - 1.
+ *   ROWS t >= n: sigma_c(w_T^t) = shifts[c] w_T^t.  Their labels are never read.  sigma is a public fixed column: there is no
+ *     tail and no closing row, and therefore no bound T - usable <= KZG_MAX_BLIND_ROWS as the _zk builders have.
+ * The result is a new set of k rows of the same worker and length: out_commitments48[c] equals kzg_rows_commit(i, k, the sigma
+ * evaluations, T, 1, ..)[c] byte for byte, and *out_handle opens, evaluates, combines, releases, goes stale and counts against
+ * KZG_MAX_ROW_SETS (KZG_E_BUSY; KZG_E_NOMEM on a failed allocation, the lane's workspace included: 2 k + 1 T-element vectors
+ * and about a third of k more for the sort) like any other.  out_stats[0] is the number of classes (distinct non-free labels
+ * among the participating cells), out_stats[1] the number of participating cells that map to themselves (free cells and
+ * singletons).  The output is a function of the input bytes alone, whatever the device's schedule.  The shifts ride in kernel
+ * arguments and the stats come back in the copy behind the MSM; nothing row-sized crosses the host link in either direction.
+ * Handle lists follow kzg_rows_commit_sorted: 1 .. KZG_MAX_BATCH_OPEN handles, a handle may repeat (two equal label columns),
+ * unknown / released / stale -> KZG_E_ARG.  KZG_E_ARG with a message that names the cause: k = 0 or k > KZG_MAX_BATCH_OPEN; a
+ * concatenation that does not hold exactly k rows; sets of several workers or several T; usable >= T; a shift or the free
+ * label >= r; k n > 2^27 (the sort's bound: positions are 32-bit).  The source sets are only read; a release or an SRS load
+ * racing the call follows the rules of kzg_rows_open.  Thread-safe like every call; after any error the context keeps serving.
+ * OUT OF SCOPE: building the wire columns from a variable vector (a = w[id] with more variables than rows: see
+ * kzg_rows_commit_fetch by row index for up to T variables); labels that arrive as typed host buffers without a set; copy
+ * constraints given as equality pairs (union-find); one permutation chained across more than KZG_MAX_BATCH_OPEN columns in one
+ * call (label per chunk and use kzg_rows_commit_grand_product_chain).
+ * SOUNDNESS: nothing here is a proof.  sigma is a fixed column of the circuit, part of the verifying key; the copy argument is
+ * the grand product over it (kzg_rows_commit_grand_product*, beta and gamma drawn AFTER the wire commitments are fixed).  The
+ * shifts must put the k cosets shifts[c] H apart (1, 7, 49, .. do), which the library does not check. */
+typedef struct kzg_sigma_opts {
+    uint64_t usable;                 /* 0: all T rows take part; else rows [0, usable), 1 <= usable <= T - 1 */
+    const uint8_t* free_label_be32;  /* NULL: none */
+} kzg_sigma_opts;
+int kzg_rows_commit_sigma(kzg_ctx* ctx, uint32_t n_label_handles, const uint64_t* label_handles, uint32_t k,
+                          const uint8_t* shifts_be32 /* k*32 */, const kzg_sigma_opts* opts /* NULL: plain, no free label */,
+                          uint8_t* out_commitments48 /* k*48 */, uint64_t out_stats[2], uint64_t* out_handle);
+/* THE COPY CHECK: "does this witness respect its copy constraints?", answered cell by cell on the device.  The label arguments
+ * and opts are those of kzg_rows_commit_sigma; the concatenated rows of the wire_handles sets are the k wire columns, cell for
+ * cell beside the labels.  A participating, non-free cell is a VIOLATION when its value differs from the value of its class's
+ * smallest-flat-index cell.  out[0] is the number of violations, out[1] the smallest violating flat index c T + t, or
+ * UINT64_MAX if there is none.  No set is created and no inverse transform or MSM runs (as a kzg_rows_commit_expr call made of
+ * checks alone).  The two handle lists follow kzg_rows_commit_fetch (a handle may stand in both); the refusals are those of
+ * kzg_rows_commit_sigma, with both concatenations holding exactly k rows of one worker and one T.
+ * SOUNDNESS: a violation count is a convenience for the prover and convinces no verifier.  The argument is the grand product
+ * over the sigma of kzg_rows_commit_sigma. */
+int kzg_rows_check_copies(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t* wire_handles, uint32_t n_label_handles,
+                          const uint64_t* label_handles, uint32_t k, const kzg_sigma_opts* opts /* NULL: plain, no free label */,
+                          uint64_t out[2]);
 /* THE QUOTIENT WITH LOOKUP SELECTORS: kzg_rows_commit_quotient_zk and kzg_rows_quotient_part for lookups that are enabled on
  * some rows only.  selectors->selector_rows holds L = lookup->n_lookups entries, each a row index into the call's concatenated
  * rows (the caller's fixed column q_l, the row that kzg_rows_commit_multiplicities_sel / _lookup_sum_sel read) or
@@ -1310,6 +1362,14 @@ int kzg_multi_rows_commit_fetch(kzg_multi* mh, uint32_t i, uint32_t n_input_hand
                                 uint32_t n_table_handles, const uint64_t* table_handles, uint32_t n_reads, uint32_t n_keys,
                                 uint32_t flags, const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_missing,
                                 uint64_t* out_first_missing, uint64_t* out_handle);
+/* kzg_rows_commit_sigma / kzg_rows_check_copies on the device of worker i: every set named must belong to worker i, else
+ * KZG_E_ARG */
+int kzg_multi_rows_commit_sigma(kzg_multi* mh, uint32_t i, uint32_t n_label_handles, const uint64_t* label_handles, uint32_t k,
+                                const uint8_t* shifts_be32, const kzg_sigma_opts* opts, uint8_t* out_commitments48,
+                                uint64_t out_stats[2], uint64_t* out_handle);
+int kzg_multi_rows_check_copies(kzg_multi* mh, uint32_t i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                uint32_t n_label_handles, const uint64_t* label_handles, uint32_t k, const kzg_sigma_opts* opts,
+                                uint64_t out[2]);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

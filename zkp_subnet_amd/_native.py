@@ -92,6 +92,11 @@ class SortedOpts(ctypes.Structure):
     _fields_ = [("usable", _U64), ("tail_be32", _B)]
 
 
+class SigmaOpts(ctypes.Structure):
+    """kzg_sigma_opts"""
+    _fields_ = [("usable", _U64), ("free_label_be32", _B)]
+
+
 class DeriveOp(ctypes.Structure):
     """kzg_derive_op"""
     _fields_ = [("kind", _U32), ("row", _U32), ("bits", _U32), ("count", _U32)]
@@ -181,6 +186,10 @@ SYMBOLS = {
                                         ctypes.POINTER(RecurrenceOpts), _B, _B, ctypes.POINTER(_U64)]),
     "kzg_rows_commit_fetch": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _U32,
                                    ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_sigma": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _B, ctypes.POINTER(SigmaOpts), _B, ctypes.POINTER(_U64),
+                                   ctypes.POINTER(_U64)]),
+    "kzg_rows_check_copies": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(SigmaOpts),
+                                   ctypes.POINTER(_U64)]),
     "kzg_rows_commit_lookup_sum": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B, _B, _B, _B,
                                         ctypes.POINTER(_U64)]),
     "kzg_rows_commit_multiplicities": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _B,
@@ -296,6 +305,10 @@ SYMBOLS = {
     "kzg_multi_rows_commit_fetch": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32, _U32,
                                          ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64),
                                          ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_sigma": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _B, ctypes.POINTER(SigmaOpts), _B,
+                                         ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_check_copies": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32,
+                                         ctypes.POINTER(SigmaOpts), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_lookup_sum": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U64, _U32, _U32, _B,
                                               _B, _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_multiplicities": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(_U64), _U32, _U32,

@@ -865,6 +865,55 @@ class Client:
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
                 "missing": [int(v) for v in missing], "first_missing": first}
 
+    # ---- the permutation's sigma columns from variable labels, and the copy check over the same labels
+    @staticmethod
+    def _sigma_args(what: str, usable, free_label) -> tuple:
+        """(usable or None, the free label's bytes or None)"""
+        if usable is not None:
+            if isinstance(usable, bool) or not isinstance(usable, int) or usable < 1:
+                raise codec.CodecError(f"{what}: usable must be an integer in [1, T - 1] (null: all rows take part)")
+        fl = None
+        if free_label is not None:
+            fl = codec.fr_to_be32(free_label)
+            if int.from_bytes(fl, "big") >= codec.R_MODULUS:
+                raise codec.CodecError(f"{what}: the free label must be a canonical scalar (< r)")
+        return usable, fl
+
+    @_guard
+    def worker_commit_sigma(self, label_handles: Sequence[int], shifts: Sequence[str], usable: Optional[int] = None,
+                            free_label: Optional[str] = None):
+        """Extension: the permutation rows sigma_0 .. sigma_{k-1} that worker_commit_grand_product takes, built on the device
+        from variable labels.  The rows of the label_handles sets are k = len(shifts) label columns (commit them with
+        worker_commit_rows_typed); cells with equal labels are one copy class, and sigma runs through every class as one
+        cycle in ascending flat index column * T + row.  usable = null: all T rows take part; otherwise rows [0, usable) do
+        and the rows behind map to themselves.  A cell whose label is free_label (null: no such label) maps to itself.
+        Returns the handle, the k commitments, `classes` (distinct non-free labels among the participating cells) and `fixed`
+        (participating cells that map to themselves).  sigma is a fixed column of the circuit, no proof of anything."""
+        what = "worker_commit_sigma"
+        hl = _handles(label_handles)
+        if not 1 <= len(shifts) <= KZG_MAX_BATCH_OPEN:
+            raise codec.CodecError(f"{what}: {len(shifts)} shifts, expected 1 .. {KZG_MAX_BATCH_OPEN}")
+        sh = [codec.fr_to_be32(x) for x in shifts]
+        if any(int.from_bytes(x, "big") >= codec.R_MODULUS for x in sh):
+            raise codec.CodecError(f"{what}: the shifts must be canonical scalars (< r)")
+        usable, fl = self._sigma_args(what, usable, free_label)
+        commitments, rs, stats = self.engine.commit_sigma(hl, sh, usable, fl)
+        return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in commitments],
+                "classes": int(stats["classes"]), "fixed": int(stats["fixed"])}
+
+    @_guard
+    def worker_check_copies(self, wire_handles: Sequence[int], label_handles: Sequence[int], usable: Optional[int] = None,
+                            free_label: Optional[str] = None):
+        """Extension: the copy constraints of worker_commit_sigma's labels checked against the wire columns, cell by cell on
+        the device.  A participating, non-free cell is a violation when its value differs from that of its class's smallest
+        cell.  Returns `violations` and `first`, the [column, row] of the smallest violating flat index (null: none).  No set
+        is created and no MSM runs.  A count convinces no verifier: the argument is the grand product over sigma."""
+        what = "worker_check_copies"
+        hw, hl = _handles(wire_handles), _handles(label_handles)
+        usable, fl = self._sigma_args(what, usable, free_label)
+        res = self.engine.check_copies(hw, hl, usable, fl)
+        return {"violations": int(res["violations"]), "first": None if res["first"] is None else [int(v) for v in res["first"]]}
+
     @staticmethod
     def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: Sequence[int], n_groups: int, width: int,
                                theta: str, gamma: str, coeff: str, active_row: Optional[int] = None,

@@ -10,6 +10,7 @@
 //   fr_expr.hip   the kernel of kzg_rows_commit_expr: sums of products of rotated resident columns on H, counted and stored
 //   fr_recur.hip  the scan of kzg_rows_commit_recurrence: v[t + 1] = A[t] v[t] + B[t] as a ladder over affine maps
 //   fr_join.hip   the hash join of kzg_rows_commit_multiplicities, and the fetch of kzg_rows_commit_fetch that walks it
+//   fr_sigma.hip  the link of kzg_rows_commit_sigma over the sorted labels, and the check of kzg_rows_check_copies
 //   comm.hip      the library's own RCCL collective (kzg_comm_*, kzg_msm_sharded, the stream-chained pair)
 //   abi_test.hip  unit-op test hooks (include/kzg_mi355x_test.h)
 // No CPU arithmetic fallback exists anywhere here: if HIP fails, the call fails.
@@ -508,6 +509,15 @@ int rows_recur_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, 
 int rows_fetch_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const RowTab& table, uint32_t n_reads,
                    uint32_t n_keys, uint32_t w_tab, bool index, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_missing,
                    uint64_t* out_first, bool* out_overrun, const Blind* lay);
+// the sigma columns of the k label rows (checked by the caller: k in [1, KZG_MAX_BATCH_OPEN], 1 <= n <= T, k n <= 2^27, canonical
+// shifts and free label; n < T: rows [n, T) map to themselves and their labels are not read) into a new k-row set's buffer dst:
+// their commitments, the number of classes and the number of cells t < n that map to themselves.  free_be32 null: no free label
+int rows_sigma_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& labels, uint32_t k, uint64_t T, uint64_t n,
+                   const uint8_t* shifts_be32, const uint8_t* free_be32, uint32_t* dst, uint8_t* out_c48, uint64_t* out_stats);
+// the copy constraints of the same labels checked against the k wire rows: out[0] the cells whose value differs from that of
+// their class's smallest cell, out[1] the smallest such flat index c T + t (UINT64_MAX: none).  No set, no MSM
+int rows_check_copies_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& wires, const RowTab& labels, uint32_t k, uint64_t T,
+                          uint64_t n, const uint8_t* free_be32, uint64_t* out);
 // the quotient pieces of the constraints qp over the n_rows coefficient rows of rt into a new n_pieces-row set's buffer dst:
 // their commitments, and whether a coefficient of t at or above n_pieces T was not zero (the caller creates no set)
 int rows_quotient_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& rt, uint32_t n_rows, uint64_t T, const QuotPlan& qp,

@@ -307,6 +307,25 @@ void launch_sort_gather(hipStream_t s, const uint32_t* col, const uint32_t* perm
 // v[usable + j] <- tail[j], j < n - usable <= BLIND_MAX_ROWS (no closing row, unlike launch_blind_tail); tail_be32: canonical
 // scalars as 32 big-endian HOST bytes each (a kernel argument), *bad raised when one is >= r
 void launch_sort_tail(hipStream_t s, uint32_t* v, uint64_t n, uint64_t usable, const uint8_t* tail_be32, uint32_t* bad);
+// ---- the sigma columns of kzg_rows_commit_sigma and the check of kzg_rows_check_copies (fr_sigma.hip).  The k <= SIGMA_MAX_COLS
+// label columns are sorted as ONE vector of N = k n <= 2^27 cells in flat-index order (cell c n + t: column c, row t < n <= T)
+// by launch_sort_front / launch_sort_passes with n_keys = 1: keys holds the cells' canonical integers, perm the sorted order
+// (null: the identity).  Cells with equal keys are one class; a cell whose key is free_be32 (null: none) stands alone.
+#define SIGMA_MAX_COLS POLY_MAX_ROWS
+// sig[c T + t] <- shift[c'] w_T^t' (canonical Montgomery) for every cell (c, t), t < n, where (c', t') is the next larger cell of
+// its class, or the smallest one behind the largest; stats[0] += the classes, stats[1] += the cells that map to themselves.
+// tw: the forward twiddle table of T (launch_fr_twiddles; not read at T = 1); shifts_be32: k scalars as 32 big-endian HOST
+// bytes each, free_be32 likewise (kernel arguments), *bad raised when one is >= r.  sig: k vectors of T elements
+void launch_sigma_link(hipStream_t s, const uint32_t* keys, const uint32_t* perm, uint64_t N, uint64_t n, uint64_t T, uint32_t k,
+                       const uint32_t* tw, const uint8_t* shifts_be32, const uint8_t* free_be32, uint32_t* sig, uint64_t* stats,
+                       uint32_t* bad);
+// sig[c T + t] <- shift[c] w_T^t for n <= t < T: the rows that take no part
+void launch_sigma_identity(hipStream_t s, uint64_t n, uint64_t T, uint32_t k, const uint32_t* tw, const uint8_t* shifts_be32,
+                           uint32_t* sig, uint32_t* bad);
+// out[0] += the non-free cells whose value in wires.r[c][t] (canonical Montgomery, T elements per column) differs from that of
+// their class's smallest cell, out[1] <- min(out[1], the smallest such flat index c T + t)
+void launch_copy_check(hipStream_t s, const uint32_t* keys, const uint32_t* perm, uint64_t N, uint64_t n, uint64_t T, uint32_t k,
+                       const RowTab& wires, const uint8_t* free_be32, uint64_t* out);
 // ---- the helper columns of kzg_rows_commit_derived (fr_derive.hip).  A source is an evaluation vector of T canonical Montgomery
 // elements of which rows [0, n) are read; counts are u64 words in device memory that the launches add to
 // the words of one op's zero mask (1 bit per cell, 32 cells per u32 word)

@@ -482,6 +482,21 @@ int kzg_multi_rows_commit_sorted(kzg_multi* mh, uint32_t i, uint32_t n_input_han
         return kzg_impl::rows_sorted(c, s, n_input_handles, input_handles, width, n_keys, opts, out_commitments48, out_handle);
     });
 }
+int kzg_multi_rows_commit_sigma(kzg_multi* mh, uint32_t i, uint32_t n_label_handles, const uint64_t* label_handles, uint32_t k,
+                                const uint8_t* shifts_be32, const kzg_sigma_opts* opts, uint8_t* out_commitments48,
+                                uint64_t out_stats[2], uint64_t* out_handle) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_sigma(c, s, n_label_handles, label_handles, k, shifts_be32, opts, out_commitments48, out_stats,
+                                    out_handle);
+    });
+}
+int kzg_multi_rows_check_copies(kzg_multi* mh, uint32_t i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                                uint32_t n_label_handles, const uint64_t* label_handles, uint32_t k, const kzg_sigma_opts* opts,
+                                uint64_t out[2]) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_check_copies(c, s, n_wire_handles, wire_handles, n_label_handles, label_handles, k, opts, out);
+    });
+}
 int kzg_multi_rows_commit_derived(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                   uint32_t n_ops, const kzg_derive_op* ops, const kzg_derive_opts* opts,
                                   uint8_t* out_commitments48, uint64_t* out_counts, uint64_t* out_handle) {

@@ -1038,6 +1038,139 @@ int rows_sorted_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs,
     return multi_msms_finish(ctx, H, i, T, dst, width, 0, 0, out_c48, nullptr, nullptr);
 }
 
+// The front of kzg_rows_commit_sigma and kzg_rows_check_copies: the k label columns as ONE sorted vector.  Each DISTINCT label
+// row (by device pointer: two indices of a repeated handle name one row) is transformed forward once; cells [0, n) of column c
+// land at cells [c n, c n + n) of `packed` (straight from the transform when n = T, through the one vector `tmp` otherwise, by
+// a device copy for a repeated row), so that the flat-index order is the vector's own.  The unchanged sort then runs with
+// n_keys = 1 over N = k n cells: launch_sort_front, the read-back of its 32 skip words (the call's one wait before the end),
+// launch_sort_passes.  *perm: the sorted order inside ws, or null (the identity) when no pass moved anything.
+static int sigma_sort_dev(kzg_ctx* ctx, Lane& A, const RowTab& labels, uint32_t k, uint64_t T, uint64_t n, const uint32_t* tw,
+                          uint32_t* packed, uint32_t* tmp, uint32_t* keys, uint32_t* ws, const uint32_t** perm) {
+    const int lg = ilog2_exact(T);
+    const uint64_t N = (uint64_t)k * n;
+    uint32_t* mid = A.ntt_mid.as<uint32_t>();
+    for (uint32_t c = 0; c < k; c++) {
+        uint32_t first = 0;
+        while (labels.r[first] != labels.r[c]) first++;
+        uint32_t* at = packed + (uint64_t)c * n * 8;
+        if (first < c) {
+            HIPCHK(ctx, hipMemcpyAsync(at, packed + (uint64_t)first * n * 8, n * 32, hipMemcpyDeviceToDevice, A.stream));
+            continue;
+        }
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, labels.r[c], n == T ? at : tmp, lg, tw, nullptr, mid);
+        if (n != T) HIPCHK(ctx, hipMemcpyAsync(at, tmp, n * 32, hipMemcpyDeviceToDevice, A.stream));
+    }
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        const uint32_t* skip_dev = launch_sort_front(A.stream, packed, N, N, 1, keys, ws);
+        HIPCHK(ctx, hipMemcpyAsync(A.bpin, skip_dev, 32 * 4, hipMemcpyDeviceToHost, A.stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(A.stream));
+    uint32_t skip[32];
+    memcpy(skip, A.bpin, sizeof(skip));
+    Span sp(ctx, A, KZG_T_POLY);
+    *perm = launch_sort_passes(A.stream, keys, N, N, 1, skip, ws);
+    return KZG_OK;
+}
+
+// The sigma columns (kzg_rows_commit_sigma): a set built FROM sets, the permutation whose cycles are the classes of equal labels.
+//   step                      launches                              per call
+//   forward transforms        launch_fr_ntt                         one per distinct label row
+//   sort                      launch_sort_front / _passes           n_keys = 1 over k n cells (sigma_sort_dev)
+//   link + count              launch_sigma_link                     one: every cell t < n of every column
+//   identity                  launch_sigma_identity                 one, with `usable` only: rows t >= n
+//   inverse transform         row_to_coeffs                         one per column, straight into dst
+//   commit                    multi_msms_finish                     ONE pass of k scalar sets
+// The packed labels are dead once the front pass has written the keys, so the k sigma vectors take their place.  The two counts
+// are u64 words behind the first two evaluation slots of the record (the layout of rows_expr_dev) and come back in the copy
+// behind the MSM.  Workspace: 2 k + 1 vectors of T (sigma / packed labels, keys, one transform target; k n cells of keys and
+// no target when n < T resp. n = T) and the sort's 0.3 k n elements in the staging buffer.
+int rows_sigma_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& labels, uint32_t k, uint64_t T, uint64_t n,
+                   const uint8_t* shifts_be32, const uint8_t* free_be32, uint32_t* dst, uint8_t* out_c48, uint64_t* out_stats) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    uint32_t* tw = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, ilog2_exact(T), 0, &tw, nullptr)) return rc;
+    const uint64_t vw = T * 8, N = (uint64_t)k * n;
+    constexpr uint32_t CNT_OFF = 64;
+    static_assert(CNT_OFF + 16 <= MR_PAIRS * 32 && KZG_MAX_BATCH_OPEN <= SIGMA_MAX_COLS, "the counts fit the record");
+    HIPCHK(ctx, A.qext.ensure(((size_t)k * T + N + (n != T ? T : 0)) * 32));
+    HIPCHK(ctx, A.qstage.ensure(fr_sort_ws_words(N, 1) * 4));
+    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    uint32_t *sig = A.qext.as<uint32_t>(), *keys = sig + (uint64_t)k * vw, *tmp = keys + N * 8, *ws = A.qstage.as<uint32_t>();
+    uint8_t* rec = A.brec.as<uint8_t>();
+    uint64_t* cnt = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF);
+    const uint32_t* perm = nullptr;
+    if (int rc = sigma_sort_dev(ctx, A, labels, k, T, n, tw, sig, tmp, keys, ws, &perm)) return rc;
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        HIPCHK(ctx, hipMemsetAsync(rec + MR_EVAL, 0, CNT_OFF + 16, A.stream));
+        launch_sigma_link(A.stream, keys, perm, N, n, T, k, tw, shifts_be32, free_be32, sig, cnt, A.flags());
+        launch_sigma_identity(A.stream, n, T, k, tw, shifts_be32, sig, A.flags());
+    }
+    for (uint32_t c = 0; c < k; c++) {
+        const uint32_t* cf;
+        if (int rc = row_to_coeffs(ctx, A, sig + c * vw, T, 1, &cf, dst + c * vw)) return rc;
+    }
+    HIPCHK(ctx, hipGetLastError());
+    uint8_t ev[CNT_OFF + 32];
+    if (int rc = multi_msms_finish(ctx, H, i, T, dst, k, 0, (CNT_OFF + 16 + 31) / 32, out_c48, ev, nullptr)) return rc;
+    memcpy(out_stats, ev + CNT_OFF, 16);
+    return KZG_OK;
+}
+
+// The copy check (kzg_rows_check_copies): the front of rows_sigma_dev, then ONE launch_copy_check over the k wire columns, each
+// DISTINCT wire row transformed forward once.  Nothing is transformed back and no MSM runs (as a rows_expr_dev call made of
+// checks alone): the record's one copy and its synchronisation end the call.  out: the violations and the smallest violating
+// flat index (UINT64_MAX: none).  Workspace: 2 k n cells (packed labels, keys), the distinct wire rows and one transform
+// target in vectors of T, and the sort's own.
+int rows_check_copies_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& wires, const RowTab& labels, uint32_t k, uint64_t T,
+                          uint64_t n, const uint8_t* free_be32, uint64_t* out) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const int lg = ilog2_exact(T);
+    uint32_t* tw = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
+    const uint64_t vw = T * 8, N = (uint64_t)k * n;
+    constexpr uint32_t CNT_OFF = 64;
+    const uint32_t* distinct[POLY_MAX_ROWS];
+    uint32_t slot[POLY_MAX_ROWS], nd = 0;
+    for (uint32_t c = 0; c < k; c++) {
+        uint32_t d = 0;
+        while (d < nd && distinct[d] != wires.r[c]) d++;
+        if (d == nd) distinct[nd++] = wires.r[c];
+        slot[c] = d;
+    }
+    HIPCHK(ctx, A.qext.ensure((2 * N + ((size_t)nd + (n != T ? 1 : 0)) * T) * 32));
+    HIPCHK(ctx, A.qstage.ensure(fr_sort_ws_words(N, 1) * 4));
+    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    uint32_t *packed = A.qext.as<uint32_t>(), *keys = packed + N * 8, *wv = keys + N * 8, *tmp = wv + (uint64_t)nd * vw;
+    uint32_t *ws = A.qstage.as<uint32_t>(), *mid = A.ntt_mid.as<uint32_t>();
+    uint8_t* rec = A.brec.as<uint8_t>();
+    uint64_t* cnt = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF);
+    RowTab wt;
+    memset(&wt, 0, sizeof(wt));
+    for (uint32_t d = 0; d < nd; d++) {
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, distinct[d], wv + d * vw, lg, tw, nullptr, mid);
+    }
+    for (uint32_t c = 0; c < k; c++) wt.r[c] = wv + slot[c] * vw;
+    const uint32_t* perm = nullptr;
+    if (int rc = sigma_sort_dev(ctx, A, labels, k, T, n, tw, packed, tmp, keys, ws, &perm)) return rc;
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        HIPCHK(ctx, hipMemsetAsync(rec + MR_EVAL, 0, CNT_OFF + 8, A.stream));
+        HIPCHK(ctx, hipMemsetAsync(cnt + 1, 0xff, 8, A.stream));   // UINT64_MAX: no violation
+        launch_copy_check(A.stream, keys, perm, N, n, T, k, wt, free_be32, cnt);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    uint8_t ev[CNT_OFF + 32];
+    if (int rc = multi_msms_finish(ctx, H, i, T, nullptr, 0, 0, (CNT_OFF + 16 + 31) / 32, nullptr, ev, nullptr)) return rc;
+    memcpy(out, ev + CNT_OFF, 16);
+    return KZG_OK;
+}
+
 // The helper columns (kzg_rows_commit_derived): a set built FROM sets, every output row a pure function of ONE source row.
 // Each DISTINCT source row (by device pointer: two ops, or two indices of a repeated handle, may name one row) is transformed
 // once into its own vector of the lane's quotient workspace.  All inv0 ops share ONE batched inversion: k_inv0_prepare lays

@@ -52,6 +52,13 @@ int rows_shuffle(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, cons
 // opts: the usable layout and its tail as the public call takes them (null: all T rows are sorted)
 int rows_sorted(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t width,
                 uint32_t n_keys, const kzg_sorted_opts* opts, uint8_t* out_commitments48, uint64_t* out_handle);
+// opts: the usable layout and the free label as the public call takes them (null: all T rows take part, no free label)
+int rows_sigma(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_label_handles, const uint64_t* label_handles, uint32_t k,
+               const uint8_t* shifts_be32, const kzg_sigma_opts* opts, uint8_t* out_commitments48, uint64_t* out_stats,
+               uint64_t* out_handle);
+int rows_check_copies(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                      uint32_t n_label_handles, const uint64_t* label_handles, uint32_t k, const kzg_sigma_opts* opts,
+                      uint64_t* out);
 // opts: the usable layout and its tail as the public call takes them (null: all T rows are read)
 int rows_derived(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
                  const kzg_derive_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_counts,

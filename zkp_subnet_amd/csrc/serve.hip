@@ -1113,6 +1113,96 @@ int rows_sorted(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const
     return KZG_OK;
 }
 
+// what kzg_rows_commit_sigma and kzg_rows_check_copies ask of their opts once T is known: *n <- the rows that take part
+static int sigma_layout(kzg_ctx* ctx, const char* what, const kzg_sigma_opts* opts, uint32_t k, uint64_t T, uint64_t* n) {
+    const char* why = nullptr;
+    *n = opts && opts->usable ? opts->usable : T;
+    if (ilog2_exact(T) < 0) why = "the row length must be a power of two";
+    else if (*n >= T && opts && opts->usable) why = "usable must be in [1, T - 1] (0: all T rows take part)";
+    else if (opts && opts->free_label_be32 && !fr_be32_canonical(opts->free_label_be32))
+        why = "the free label must be a canonical scalar (< r)";
+    else if (*n > ((uint64_t)1 << 27) || (uint64_t)k * *n > ((uint64_t)1 << 27))   // positions of the sort are u32
+        why = "k * n cells take part, which must be at most 2^27";
+    return why ? fail(ctx, KZG_E_ARG, std::string(what) + ": " + why) : KZG_OK;
+}
+
+// kzg_rows_commit_sigma: the lookups of an open (one handle list), the reservation of a commit of k rows.  opts == NULL: plain
+// layout, no free label.  The shifts and the free label are checked here, on the host (the kernels check them again)
+int rows_sigma(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_label_handles, const uint64_t* label_handles, uint32_t k,
+               const uint8_t* shifts_be32, const kzg_sigma_opts* opts, uint8_t* out_commitments48, uint64_t* out_stats,
+               uint64_t* out_handle) {
+    if (!ctx || !label_handles || !shifts_be32 || !out_commitments48 || !out_stats || !out_handle) return KZG_E_ARG;
+    if (n_label_handles == 0 || n_label_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "sigma: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (k == 0 || k > KZG_MAX_BATCH_OPEN) return fail(ctx, KZG_E_ARG, "sigma: k must be in [1, KZG_MAX_BATCH_OPEN]");
+    for (uint32_t c = 0; c < k; c++)
+        if (!fr_be32_canonical(shifts_be32 + 32 * (size_t)c))
+            return fail(ctx, KZG_E_ARG, "sigma: the shifts must be canonical scalars (< r)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs lrefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab lt;
+    uint32_t kl = 0, i = 0;
+    uint64_t T = 0, n = 0;
+    if (int rc = rows_lookup(ctx, "sigma", expect_i, n_label_handles, label_handles, lrefs, lt, &kl, &i, &T)) return rc;
+    if (kl != k) return fail(ctx, KZG_E_ARG, "sigma: the label sets must hold exactly k rows");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (int rc2 = sigma_layout(ctx, "sigma", opts, k, T, &n)) return rc2;
+    if (int rc2 = rows_reserve(ctx, "sigma", pend, (size_t)k * T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    uint64_t stats[2];
+    rc = rows_sigma_dev(ctx, H, i, lt, k, T, n, shifts_be32, opts ? opts->free_label_be32 : nullptr, pend.buf.as<uint32_t>(), c48,
+                        stats);
+    if (rc) return rc;
+    memcpy(out_commitments48, c48, 48 * (size_t)k);
+    out_stats[0] = stats[0];
+    out_stats[1] = stats[1];
+    *out_handle = rows_insert(ctx, pend, i, k, T);
+    return KZG_OK;
+}
+
+// kzg_rows_check_copies: the lookups of an open (two handle lists, as rows_fetch); no reservation, no set
+int rows_check_copies(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_wire_handles, const uint64_t* wire_handles,
+                      uint32_t n_label_handles, const uint64_t* label_handles, uint32_t k, const kzg_sigma_opts* opts,
+                      uint64_t* out) {
+    if (!ctx || !wire_handles || !label_handles || !out) return KZG_E_ARG;
+    if (n_wire_handles == 0 || n_wire_handles > KZG_MAX_BATCH_OPEN || n_label_handles == 0 || n_label_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "check_copies: the number of handles in each list must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (k == 0 || k > KZG_MAX_BATCH_OPEN) return fail(ctx, KZG_E_ARG, "check_copies: k must be in [1, KZG_MAX_BATCH_OPEN]");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsRefs wrefs{ctx}, lrefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab wt, lt;
+    uint32_t kw = 0, kl = 0, i = 0, i2 = 0;
+    uint64_t T = 0, T2 = 0, n = 0;
+    if (int rc = rows_lookup(ctx, "check_copies: wires", expect_i, n_wire_handles, wire_handles, wrefs, wt, &kw, &i, &T)) return rc;
+    if (int rc = rows_lookup(ctx, "check_copies: labels", expect_i, n_label_handles, label_handles, lrefs, lt, &kl, &i2, &T2))
+        return rc;
+    if (i2 != i || T2 != T) return fail(ctx, KZG_E_ARG, "check_copies: all sets must belong to one worker and have one row length");
+    if (kw != k || kl != k) return fail(ctx, KZG_E_ARG, "check_copies: the wire sets and the label sets must hold exactly k rows each");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (int rc2 = sigma_layout(ctx, "check_copies", opts, k, T, &n)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    uint64_t res[2];
+    rc = rows_check_copies_dev(ctx, H, i, wt, lt, k, T, n, opts ? opts->free_label_be32 : nullptr, res);
+    if (rc) return rc;
+    out[0] = res[0];
+    out[1] = res[1];
+    return KZG_OK;
+}
+
 // kzg_rows_commit_derived: the lookups of an open (one handle list), the reservation of a commit of n_out rows.  opts == NULL,
 // or usable == 0: all T rows are read
 int rows_derived(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
@@ -2182,6 +2272,16 @@ int kzg_rows_commit_shuffle(kzg_ctx* ctx, uint32_t n_input_handles, const uint64
 int kzg_rows_commit_sorted(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t width, uint32_t n_keys,
                            const kzg_sorted_opts* opts, uint8_t* out_commitments48, uint64_t* out_handle) {
     return rows_sorted(ctx, UINT32_MAX, n_input_handles, input_handles, width, n_keys, opts, out_commitments48, out_handle);
+}
+int kzg_rows_commit_sigma(kzg_ctx* ctx, uint32_t n_label_handles, const uint64_t* label_handles, uint32_t k,
+                          const uint8_t* shifts_be32, const kzg_sigma_opts* opts, uint8_t* out_commitments48, uint64_t out_stats[2],
+                          uint64_t* out_handle) {
+    return rows_sigma(ctx, UINT32_MAX, n_label_handles, label_handles, k, shifts_be32, opts, out_commitments48, out_stats,
+                      out_handle);
+}
+int kzg_rows_check_copies(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t* wire_handles, uint32_t n_label_handles,
+                          const uint64_t* label_handles, uint32_t k, const kzg_sigma_opts* opts, uint64_t out[2]) {
+    return rows_check_copies(ctx, UINT32_MAX, n_wire_handles, wire_handles, n_label_handles, label_handles, k, opts, out);
 }
 int kzg_rows_commit_derived(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
                             const kzg_derive_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48,

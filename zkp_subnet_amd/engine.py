@@ -807,6 +807,67 @@ class HipEngine:
                                                    c, ctypes.byref(h)))
         return RowSet(self, h.value, wi, width, T, [c.raw[48 * p:48 * p + 48] for p in range(width)])
 
+    # ---- a set built from sets: the permutation's sigma columns from variable labels, and the copy check over the same labels
+    def _sigma_opts(self, what: str, usable, free_label):
+        """kzg_sigma_opts (None for the plain layout without a free label) and the object that keeps its bytes alive"""
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: {why}")   # noqa: E731
+        if usable is not None and (isinstance(usable, bool) or not isinstance(usable, int) or not 1 <= usable < 1 << 64):
+            raise bad("usable must be in [1, T - 1] (None: all T rows take part)")   # (the C call reads 0 as "plain layout")
+        if free_label is not None:
+            free_label = bytes(free_label)
+            if len(free_label) != 32:
+                raise bad("the free label must be of 32 bytes")
+        if usable is None and free_label is None:
+            return None
+        return _native.SigmaOpts(usable or 0, free_label)
+
+    def commit_sigma(self, label_sets: Sequence[object], shifts_be32: Sequence[bytes], usable: Optional[int] = None,
+                     free_label: Optional[bytes] = None) -> Tuple[List[bytes], "RowSet", Dict[str, int]]:
+        """kzg_rows_commit_sigma.  The concatenated rows of label_sets (RowSet objects or bare handles) are k = len(shifts_be32)
+        label columns; cells with equal labels (as canonical integers) are one copy class.  The new RowSet of k rows holds the
+        permutation in which every class is one cycle in ascending flat index c * T + t: sigma_c(w^t) = shifts[c'] * w^t' for
+        the image (c', t').  usable = None: all T rows take part; otherwise rows [0, usable) do and the rows behind map to
+        themselves, their labels unread.  A cell whose label is free_label (32 bytes; None: no such label) maps to itself.
+        Returns (the k commitments, the RowSet -- the handle of the new set --, {"classes": distinct non-free labels among the
+        participating cells, "fixed": participating cells that map to themselves})."""
+        what = "commit_sigma"
+        nl, hl = self._handle_array(label_sets, what)
+        shifts = [bytes(x) for x in shifts_be32]
+        k = len(shifts)
+        if not 1 <= k <= _native.KZG_MAX_BATCH_OPEN or any(len(x) != 32 for x in shifts):
+            raise KzgError(_native.KZG_E_ARG, f"{what}: 1 .. {_native.KZG_MAX_BATCH_OPEN} shifts of 32 bytes each")
+        opts = self._sigma_opts(what, usable, free_label)
+        wi, T, _ = self._column_layout(what, label_sets, k, "k", "linked", None, ())
+        c, h, st = ctypes.create_string_buffer(48 * k), ctypes.c_uint64(0), (ctypes.c_uint64 * 2)()
+        self._chk(self._lib.kzg_rows_commit_sigma(self._h, nl, hl, k, b"".join(shifts), ctypes.byref(opts) if opts is not None else None,
+                                                  c, st, ctypes.byref(h)))
+        rs = RowSet(self, h.value, wi, k, T, [c.raw[48 * p:48 * p + 48] for p in range(k)])
+        return list(rs.commitments), rs, {"classes": int(st[0]), "fixed": int(st[1])}
+
+    def check_copies(self, wire_sets: Sequence[object], label_sets: Sequence[object], usable: Optional[int] = None,
+                     free_label: Optional[bytes] = None) -> Dict[str, object]:
+        """kzg_rows_check_copies: the wire columns (the concatenated rows of wire_sets) against the copy classes of the label
+        columns of commit_sigma, cell by cell on the device; both concatenations hold the same k rows, which must be known to
+        this engine (sets committed through it).  A participating, non-free cell is a violation when its value differs from
+        that of its class's smallest cell.  Returns {"violations": their number, "first": the (column, row) of the smallest
+        violating flat index or None}.  Creates no set and runs no MSM; a count convinces no verifier."""
+        what = "check_copies"
+        nw, hw = self._handle_array(wire_sets, f"{what} (wires)")
+        nl, hl = self._handle_array(label_sets, f"{what} (labels)")
+        widths = [x.k if hasattr(x, "handle") else self._set_rows.get(int(x)) for x in label_sets]
+        wi, T, _ = self._column_layout(what, list(label_sets) + list(wire_sets), 0, "k", "checked", None, ())
+        if any(w is None for w in widths) or T is None:   # (k is an argument of the C call; T splits the flat index)
+            raise KzgError(_native.KZG_E_ARG, f"{what}: the row count or length of the label sets is unknown to this engine "
+                                              "(they were not committed through it)")
+        k = sum(widths)
+        if not 1 <= k <= _native.KZG_MAX_BATCH_OPEN:
+            raise KzgError(_native.KZG_E_ARG, f"{what}: the label sets hold {k} rows, expected 1 .. {_native.KZG_MAX_BATCH_OPEN}")
+        opts = self._sigma_opts(what, usable, free_label)
+        out = (ctypes.c_uint64 * 2)()
+        self._chk(self._lib.kzg_rows_check_copies(self._h, nw, hw, nl, hl, k, ctypes.byref(opts) if opts is not None else None, out))
+        first = None if int(out[1]) == 0xffffffffffffffff else (int(out[1]) // T, int(out[1]) % T)
+        return {"violations": int(out[0]), "first": first}
+
     def _column_layout(self, what: str, input_sets, n_cols: int, cols_name: str, verb: str, usable, tail):
         """The usable layout WITHOUT a closing row (kzg_sorted_opts, kzg_derive_opts) of a builder with n_cols output columns:
         (worker, T, None for the plain layout or (usable, the column-major tail's bytes or None)); worker and T are None for

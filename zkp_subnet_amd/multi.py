@@ -238,6 +238,13 @@ class MultiDeviceClient:
         return self._routed_builder("worker_commit_fetch", [input_handles, table_handles], input_handles, table_handles,
                                     n_reads, n_keys, with_index, usable, tail)
 
+    def worker_commit_sigma(self, label_handles: Sequence[int], shifts, usable=None, free_label=None):
+        return self._routed_builder("worker_commit_sigma", [label_handles], label_handles, shifts, usable, free_label)
+
+    def worker_check_copies(self, wire_handles: Sequence[int], label_handles: Sequence[int], usable=None, free_label=None):
+        return self._routed_builder("worker_check_copies", [wire_handles, label_handles], wire_handles, label_handles, usable,
+                                    free_label, key=None)
+
     def worker_commit_quotient_zk(self, handles: Sequence[int], terms, perm=None, lookup=None, active_row=None, ext_log=2,
                                   n_pieces=3):
         return self._routed_builder("worker_commit_quotient_zk", [handles], handles, terms, perm, lookup, active_row, ext_log,
