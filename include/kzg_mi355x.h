@@ -758,7 +758,8 @@ int kzg_rows_commit_sorted(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_
  * Thread-safe like every call; after any error the context keeps serving.
  * OUT OF SCOPE: per-row selectors; signed limbs or limbs in a base that is no power of two.  (halo2's running-sum decomposition
  * along the rows: kzg_rows_commit_recurrence below, z' = (z - k) 2^-K as a recurrence.  General expression rows, sum_u c_u prod
- * rows[rot] committed as a column: kzg_rows_commit_expr below.)
+ * rows[rot] committed as a column: kzg_rows_commit_expr below.  Machine-word arithmetic on the canonical integers -- bitwise
+ * ops, carries, borrows, high products, quotients and remainders, shifts: kzg_rows_commit_int below.)
  * SOUNDNESS: nothing here is a proof.  The derived rows are prover data; the argument is the caller's gates (x inv0 = 1 - bit
  * and x bit = 0; x = sum_l 2^(b l) limb_l) and the lookup of the limbs, with every challenge drawn AFTER these commitments are
  * fixed.  The library derives no challenge and draws no randomness: the tail must be fresh per proof. */
@@ -931,7 +932,8 @@ int kzg_rows_commit_recurrence(kzg_ctx* ctx, uint32_t n_input_handles, const uin
  * context keeps serving.
  * OUT OF SCOPE: per-read selectors (a disabled cell is a counted miss that reads 0: multiply by the selector with
  * kzg_rows_commit_expr afterwards); a default value other than 0; the LAST matching row instead of the first; tables longer or
- * shorter than the input rows.
+ * shorter than the input rows.  (A bitwise or arithmetic operation on machine words needs no 2^(2b)-row table to be COMPUTED:
+ * kzg_rows_commit_int below builds the witness column directly; the table stays the caller's argument for it.)
  * SOUNDNESS: nothing here is a proof.  The fetched rows are prover data; the argument is the lookup of the tuple (key, payload)
  * in the table (kzg_rows_commit_multiplicities -> kzg_rows_commit_lookup_sum -> the quotient's logUp relation), with theta and
  * beta drawn AFTER these commitments are fixed.  A zero miss count is a convenience for the prover and convinces no verifier.
@@ -995,6 +997,73 @@ int kzg_rows_commit_sigma(kzg_ctx* ctx, uint32_t n_label_handles, const uint64_t
 int kzg_rows_check_copies(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t* wire_handles, uint32_t n_label_handles,
                           const uint64_t* label_handles, uint32_t k, const kzg_sigma_opts* opts /* NULL: plain, no free label */,
                           uint64_t out[2]);
+/* THE INTEGER ALU COLUMNS: a set built FROM sets, the witness columns of machine-word arithmetic -- what a zkVM-style execution
+ * trace holds beside its field arithmetic (kzg_rows_commit_expr): bitwise results, carries, borrows, high products, quotients
+ * and remainders, shifted halves.  The concatenated rows of the input_handles sets (as in kzg_rows_open) are the source
+ * columns; cell t of a column is its value at w_T^t, taken as its CANONICAL INTEGER in [0, r), exactly as in
+ * kzg_rows_commit_derived.  Each of the n_ops ops has a kind, a width w in [1, 64] with M = 2^w, a first operand row a, a second
+ * operand that is the row b or, with KZG_INT_IMM in flags, the 64-bit immediate imm, and `count`, its number of output rows.
+ * READING AN OPERAND: an operand cell x >= 2^w is OUT OF RANGE: the op uses x mod 2^w, its low w bits.  Such a cell is counted
+ * once in out_counts[op], however many of its operands are out of range, and out_first[op] is the smallest such row, or
+ * KZG_INT_NONE.  An out-of-range cell is never an error; the output rows are still written.  An immediate >= 2^w (SPLIT: an
+ * immediate > w) is KZG_E_ARG.  The output rows of an op, in this order (count selects the first one or both):
+ *   KZG_INT_AND, _OR, _XOR (count 1)   a op b
+ *   KZG_INT_ADD    (count 1 or 2)      (a + b) mod M;  the carry (a + b) >> w, 0 or 1
+ *   KZG_INT_SUB    (count 1 or 2)      (a - b) mod M;  the borrow, 1 where a < b and else 0 (the unsigned less-than bit)
+ *   KZG_INT_MUL    (count 1 or 2)      (a b) mod M;    (a b) >> w
+ *   KZG_INT_DIVMOD (count 1 or 2)      floor(a / b), M - 1 where b = 0;  a mod b, a where b = 0 (the RISC-V convention; a zero
+ *                                      divisor is neither counted nor an error)
+ *   KZG_INT_SPLIT  (count 1 or 2)      a >> s;  a mod 2^s.  The second operand is the shift s: an immediate in [0, w], or a row
+ *                                      whose cell is s; a cell with s > w is out of range and is taken as s = w.  Every shift and
+ *                                      rotation follows by composition: shl = lo 2^s, rotr = lo 2^(w - s) + hi through
+ *                                      kzg_rows_commit_expr.
+ * A row may serve as both operands of one op.  n_ops <= KZG_MAX_BATCH_OPEN and n_out = sum of the counts, 1 <= n_out <=
+ * KZG_MAX_BATCH_OPEN.  All outputs of a call form ONE new set of the same worker and length, in the order of ops:
+ * out_commitments48[c] equals kzg_rows_commit(i, n_out, these rows, T, 1, ..)[c] byte for byte, and *out_handle opens,
+ * evaluates, combines, releases, goes stale and counts against KZG_MAX_ROW_SETS (KZG_E_BUSY; KZG_E_NOMEM on a failed allocation,
+ * the lane's workspace included: one T-element vector per DISTINCT source row, which is transformed once however many ops name
+ * it, and one per output row) like any other.  ONE kernel launch computes every op of the call; the counts and first rows come
+ * back in the copy behind the MSM; nothing row-sized crosses the host link in either direction.
+ * opts (NULL: plain layout) is kzg_derive_opts, exactly as kzg_rows_commit_derived reads it: source rows t >= usable are never
+ * read or counted, output row usable + s of output column c takes tail_be32[c * (T - usable) + s], there is NO closing row.
+ * Handle lists follow kzg_rows_open.  KZG_E_ARG with a message that begins "int:" and names the cause: n_ops = 0 or n_ops >
+ * KZG_MAX_BATCH_OPEN; n_out > KZG_MAX_BATCH_OPEN; an unknown kind; an unknown flag; w outside [1, 64]; count outside the kind's
+ * set; a row at or beyond the concatenation; an immediate that does not fit; the usable and tail refusals of
+ * kzg_rows_commit_derived; the handle refusals of kzg_rows_open.  The source sets are only read; a release or an SRS load racing
+ * the call follows the rules of kzg_rows_open.  Thread-safe like every call; after any error the context keeps serving.
+ * OUT OF SCOPE: signed variants (sra, mulh, signed div / rem, slt: the caller adds the bias 2^(w-1) and corrects with
+ * kzg_rows_commit_expr); widths above 64; three-operand ops (a b + c, funnel shifts); per-row selectors (an op-code column
+ * choosing the kind per row: build every candidate and select with kzg_rows_commit_expr); a separate count of zero divisors.
+ * SOUNDNESS: nothing here is a proof.  The rows are prover data; the argument is the caller's gates plus the range lookups of
+ * the outputs (kzg_rows_commit_derived LIMBS -> kzg_rows_commit_multiplicities -> kzg_rows_commit_lookup_sum): a + b = s + carry M;
+ * a - b = d - borrow M; a b = lo + hi M; a = q b + rem with rem < b shown through the borrow of a SUB (and the b = 0 case
+ * through an is-zero bit); a = hi 2^s + lo with lo < 2^s, where for a per-row s the power 2^s is fetched from a table
+ * (kzg_rows_commit_fetch); a bitwise op through its 2^(2b)-row table on the limbs.  Every challenge is drawn AFTER these
+ * commitments are fixed.  A zero out-of-range count is a convenience for the prover and convinces no verifier.  The library
+ * derives no challenge and draws no randomness: the tail must be fresh per proof. */
+#define KZG_INT_AND    1
+#define KZG_INT_OR     2
+#define KZG_INT_XOR    3
+#define KZG_INT_ADD    4
+#define KZG_INT_SUB    5
+#define KZG_INT_MUL    6
+#define KZG_INT_DIVMOD 7
+#define KZG_INT_SPLIT  8
+#define KZG_INT_IMM    1u                   /* flags: the second operand is `imm`, not row b */
+#define KZG_INT_NONE   0xffffffffffffffffull
+typedef struct kzg_int_op {
+    uint32_t kind;   /* KZG_INT_* */
+    uint32_t width;  /* w in [1, 64] */
+    uint32_t a;      /* first operand: a row, index into the concatenated rows of input_handles */
+    uint32_t b;      /* second operand: a row (a SPLIT's shift column); must be 0 with KZG_INT_IMM */
+    uint64_t imm;    /* second operand with KZG_INT_IMM: below 2^w (SPLIT: at most w); must be 0 without */
+    uint32_t flags;  /* 0 or KZG_INT_IMM */
+    uint32_t count;  /* output rows: 1, or 2 where the kind has a second row */
+} kzg_int_op;
+int kzg_rows_commit_int(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
+                        const kzg_int_op* ops, const kzg_derive_opts* opts /* NULL: plain */,
+                        uint8_t* out_commitments48 /* n_out * 48 */, uint64_t* out_counts /* n_ops */,
+                        uint64_t* out_first /* n_ops */, uint64_t* out_handle);
 /* THE QUOTIENT WITH LOOKUP SELECTORS: kzg_rows_commit_quotient_zk and kzg_rows_quotient_part for lookups that are enabled on
  * some rows only.  selectors->selector_rows holds L = lookup->n_lookups entries, each a row index into the call's concatenated
  * rows (the caller's fixed column q_l, the row that kzg_rows_commit_multiplicities_sel / _lookup_sum_sel read) or
@@ -1370,6 +1439,10 @@ int kzg_multi_rows_commit_sigma(kzg_multi* mh, uint32_t i, uint32_t n_label_hand
 int kzg_multi_rows_check_copies(kzg_multi* mh, uint32_t i, uint32_t n_wire_handles, const uint64_t* wire_handles,
                                 uint32_t n_label_handles, const uint64_t* label_handles, uint32_t k, const kzg_sigma_opts* opts,
                                 uint64_t out[2]);
+/* kzg_rows_commit_int on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_int(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
+                              const kzg_int_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48,
+                              uint64_t* out_counts, uint64_t* out_first, uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

@@ -25,6 +25,10 @@ KZG_MAX_GATE_TERMS = 16   # kzg_rows_commit_quotient
 KZG_MAX_BLIND_ROWS = 32   # kzg_rows_commit_*_zk: T - usable
 KZG_NO_SELECTOR = 0xffffffff   # kzg_rows_commit_*_sel: a lookup without a selector row
 KZG_DERIVE_INV0, KZG_DERIVE_LIMBS = 1, 2   # kzg_rows_commit_derived: kzg_derive_op.kind
+# kzg_rows_commit_int: kzg_int_op.kind, the immediate flag, out_first without an out-of-range cell
+KZG_INT_AND, KZG_INT_OR, KZG_INT_XOR, KZG_INT_ADD, KZG_INT_SUB, KZG_INT_MUL, KZG_INT_DIVMOD, KZG_INT_SPLIT = range(1, 9)
+KZG_INT_IMM = 1
+KZG_INT_NONE = 0xffffffffffffffff
 KZG_MAX_EXPR_FACTORS = 8   # kzg_rows_commit_expr: factors of one term
 KZG_EXPR_CHECK = 1   # kzg_expr.flags: evaluate and count only
 KZG_EXPR_NONE = 0xffffffffffffffff   # out_first: no non-zero cell
@@ -100,6 +104,11 @@ class SigmaOpts(ctypes.Structure):
 class DeriveOp(ctypes.Structure):
     """kzg_derive_op"""
     _fields_ = [("kind", _U32), ("row", _U32), ("bits", _U32), ("count", _U32)]
+
+
+class IntOp(ctypes.Structure):
+    """kzg_int_op"""
+    _fields_ = [("kind", _U32), ("width", _U32), ("a", _U32), ("b", _U32), ("imm", _U64), ("flags", _U32), ("count", _U32)]
 
 
 class Col(ctypes.Structure):
@@ -178,6 +187,8 @@ SYMBOLS = {
                                      ctypes.POINTER(ShuffleOpts), _B, _B, ctypes.POINTER(_U64)]),
     "kzg_rows_commit_sorted": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, _U32, ctypes.POINTER(SortedOpts), _B,
                                     ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_int": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(IntOp), ctypes.POINTER(DeriveOpts), _B,
+                                 ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_derived": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp), ctypes.POINTER(DeriveOpts), _B,
                                      ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_expr": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,
@@ -296,6 +307,9 @@ SYMBOLS = {
                                            ctypes.POINTER(ShuffleOpts), _B, _B, ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_sorted": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, _U32, ctypes.POINTER(SortedOpts), _B,
                                           ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_int": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(IntOp),
+                                       ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64),
+                                       ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_derived": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp),
                                            ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_expr": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,

@@ -914,6 +914,51 @@ class Client:
         res = self.engine.check_copies(hw, hl, usable, fl)
         return {"violations": int(res["violations"]), "first": None if res["first"] is None else [int(v) for v in res["first"]]}
 
+    # ---- machine-word arithmetic on resident columns: bitwise ops, carries, high products, quotients, shifts, on the device
+    @_guard
+    def worker_commit_int(self, input_handles: Sequence[int], ops: Sequence[Sequence], usable: Optional[int] = None,
+                          tail: Sequence[str] = ()):
+        """Extension: integer ALU columns of the rows of the input_handles sets, computed and committed on the device as one new
+        set.  ops: [kind, w, a, b] or [kind, w, a, b, count] with kind one of "and" "or" "xor" "add" "sub" "mul" "divmod"
+        "split", w the width in [1, 64], a a row, b a row or ["imm", value], count 1 or 2.  The operands are the cells'
+        canonical integers reduced to their low w bits; the rows of an op, in this order: a op b; the sum and its carry; the
+        difference and its borrow (1 where a < b); the low and the high word of the product; the quotient and the remainder
+        (2^w - 1 and a where b = 0); a >> s and a mod 2^s with the shift s as second operand.  usable = null reads all T rows;
+        otherwise only rows [0, usable) are read and row usable + s of output column c is tail[c * (T - usable) + s] -- there is
+        no closing row.  Returns the handle, the commitments of all output rows in the order of ops, and per op `counts`, the
+        cells read with an operand at or above 2^w (a shift cell: above w), and `first`, the smallest such row (null: none).
+        Nothing here is a proof: the rows are prover data and the argument is the caller's gates and range lookups over them."""
+        what = "worker_commit_int"
+        hs = _handles(input_handles)
+        try:
+            recs = []
+            for op in ops:
+                if isinstance(op, (str, bytes)) or len(op) not in (4, 5):
+                    raise ValueError(f"an op is [kind, w, a, b] or [kind, w, a, b, count]: {op!r}")
+                b = op[3]
+                if isinstance(b, (list, tuple)):
+                    if len(b) != 2 or b[0] != "imm":
+                        raise ValueError(f'an immediate is ["imm", value]: {b!r}')
+                    b = ("imm", int(b[1]))
+                else:
+                    b = int(b)
+                recs.append((str(op[0]), int(op[1]), int(op[2]), b) + ((int(op[4]),) if len(op) == 5 else ()))
+        except (TypeError, ValueError, IndexError, KeyError) as e:
+            raise codec.CodecError(f"{what}: ops must be a list of [kind, w, a, b] or [kind, w, a, b, count]: {e!r}") from e
+        if not recs:
+            raise codec.CodecError(f"{what}: ops must not be empty")
+        if usable is None:
+            if tail:
+                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
+            tb = []
+        else:
+            usable, tb = self._blind(what, usable, tail)
+            if usable == 0:
+                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        rs, counts, first = self.engine.commit_int(hs, recs, usable, tb)
+        return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
+                "counts": counts, "first": first}
+
     @staticmethod
     def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: Sequence[int], n_groups: int, width: int,
                                theta: str, gamma: str, coeff: str, active_row: Optional[int] = None,

@@ -7,6 +7,7 @@
 //   pipeline.hip  the host-side sequencing of the kernels: one MSM (msm_core), a row's commit / open (commit_open_dev)
 //   serve.hip     the serving entry points: commit / open / msm / ntt / eval, resident slots, tickets, sums
 //   fr_derive.hip the kernels of kzg_rows_commit_derived: inverse-or-zero around the batched inversion, limb decomposition
+//   fr_int.hip    the kernel of kzg_rows_commit_int: machine-word arithmetic on the canonical integers of resident columns
 //   fr_expr.hip   the kernel of kzg_rows_commit_expr: sums of products of rotated resident columns on H, counted and stored
 //   fr_recur.hip  the scan of kzg_rows_commit_recurrence: v[t + 1] = A[t] v[t] + B[t] as a ladder over affine maps
 //   fr_join.hip   the hash join of kzg_rows_commit_multiplicities, and the fetch of kzg_rows_commit_fetch that walks it
@@ -481,6 +482,11 @@ int rows_sorted_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs,
 // inv0 op, cells at or above 2^(bits count) of a limbs op).  lay: as for rows_sorted_dev, the tail column-major over n_out
 int rows_derived_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_ops, const kzg_derive_op* ops,
                      uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_counts, const Blind* lay);
+// the n_out rows of the n_ops integer ops (checked by the caller: kinds, widths, counts summing to n_out, rows inside `inputs`,
+// immediates that fit) into a new n_out-row set's buffer dst: their commitments and, per op, the number of cells read with an
+// operand out of range and the smallest such row (KZG_INT_NONE: none).  lay: as for rows_derived_dev
+int rows_int_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_ops, const kzg_int_op* ops, uint32_t n_out,
+                 uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_counts, uint64_t* out_first, const Blind* lay);
 // the n_out committed ones of the n_exprs expressions (checked by the caller: term counts and lengths in range, rows inside
 // `inputs`, rotations reduced into [0, T), canonical coefficients; is_check[e] != 0: expression e is only counted) into a new
 // n_out-row set's buffer dst (null when n_out = 0: then no transform back and no MSM runs): their commitments, and per

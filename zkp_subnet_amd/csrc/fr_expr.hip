@@ -32,19 +32,7 @@ struct ExprArg {
 static_assert(sizeof(ExprArg) + sizeof(RowTab) + 64 <= 4096, "k_expr's arguments must fit in 4 KB");
 static_assert(EXPR_MAX_FACTORS <= 255 && POLY_MAX_ROWS <= 256, "lengths and row indices ride in bytes");
 
-// the workgroup's smallest flagged cell folded into *first: the lowest set bit of each wave's ballot, one LDS minimum per wave,
-// one global minimum per workgroup.  Called by every lane of the workgroup (uniform control flow); lane v stands for cell
-// blockIdx.x * blockDim.x + v
-KZG_DEV void expr_first(bool flagged, unsigned long long* __restrict__ first) {
-    __shared__ uint32_t wg_first;
-    if (threadIdx.x == 0) wg_first = 0xffffffffu;
-    __syncthreads();
-    const unsigned long long b = __ballot(flagged);
-    if ((threadIdx.x & 63u) == 0 && b) atomicMin(&wg_first, threadIdx.x + (uint32_t)__ffsll(b) - 1u);
-    __syncthreads();
-    if (threadIdx.x == 0 && wg_first != 0xffffffffu)
-        atomicMin(first, (unsigned long long)blockIdx.x * blockDim.x + wg_first);
-}
+// (expr_first, the workgroup's smallest flagged cell, lives in fr_kernels.hip.h beside derive_count: fr_int.hip uses it too)
 
 // T a power of two, n <= T, every rot below T, every row below POLY_MAX_ROWS and its pointer set (the launcher's and its
 // caller's checks).  Lanes t >= n read nothing and store nothing; they still walk the two reductions.

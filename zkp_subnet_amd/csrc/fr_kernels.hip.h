@@ -351,6 +351,37 @@ KZG_DEV void derive_count(bool flagged, unsigned long long* __restrict__ total) 
     __syncthreads();
     if (threadIdx.x == 0 && wg_cnt) atomicAdd(total, (unsigned long long)wg_cnt);
 }
+// the workgroup's smallest flagged cell folded into *first: the lowest set bit of each wave's ballot, one LDS minimum per wave,
+// one global minimum per workgroup.  Called by every lane of the workgroup (uniform control flow); lane v stands for cell
+// blockIdx.x * blockDim.x + v.  Shared by the kernels of fr_expr.hip and fr_int.hip
+KZG_DEV void expr_first(bool flagged, unsigned long long* __restrict__ first) {
+    __shared__ uint32_t wg_first;
+    if (threadIdx.x == 0) wg_first = 0xffffffffu;
+    __syncthreads();
+    const unsigned long long b = __ballot(flagged);
+    if ((threadIdx.x & 63u) == 0 && b) atomicMin(&wg_first, threadIdx.x + (uint32_t)__ffsll(b) - 1u);
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_first != 0xffffffffu)
+        atomicMin(first, (unsigned long long)blockIdx.x * blockDim.x + wg_first);
+}
+// ---- the integer ALU columns of kzg_rows_commit_int (fr_int.hip): every output cell a function of the canonical integers of one
+// or two source cells, reduced to their low w bits.  An op reads a[t] and b[t] (b null: the immediate imm) for t < n and writes
+// `count` vectors of T elements at out (row 0, then row 1 at out + 8 T words), canonical Montgomery.  kind: a KZG_INT_* kind
+#define INT_MAX_OPS POLY_MAX_ROWS
+struct IntOp {
+    const uint32_t *a, *b;
+    uint64_t imm;
+    uint32_t* out;
+    uint32_t kind, w, count, pad;
+};
+struct IntTab {
+    IntOp op[INT_MAX_OPS];
+};
+static_assert(sizeof(IntTab) + 64 <= 4096, "the op table rides as a kernel argument");
+// ONE launch for the n_ops <= INT_MAX_OPS ops of tab; counts[o] += the cells t < n of op o with an operand at or above 2^w
+// (a SPLIT's shift cell: above w), first[o] <- min(first[o], the smallest such t).  a and b are only read and may be one
+// vector; out must not overlap a source.  1 <= w <= 64, an immediate below 2^w (SPLIT: at most w): the caller's checks
+void launch_int(hipStream_t s, const IntTab& tab, uint32_t n_ops, uint64_t T, uint64_t n, uint64_t* counts, uint64_t* first);
 // ---- the expression columns of kzg_rows_commit_expr (fr_expr.hip): v[t] = sum_u c_u prod_f src.r[row[u][f]][(t + rot[u][f]) mod T]
 // for t < n <= T over evaluation vectors of T canonical Montgomery elements (T a power of two, at most 2^32)
 #define EXPR_MAX_TERMS 16

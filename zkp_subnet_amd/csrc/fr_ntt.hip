@@ -8,6 +8,7 @@
 
 #include "../../include/kzg_mi355x.h"   // the KZG_COL_* kinds of the typed columns
 #include "fr_kernels.hip.h"
+#include "fr_u64.hip.h"
 
 static inline uint32_t nblk(uint64_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
 
@@ -63,36 +64,7 @@ __global__ void __launch_bounds__(256) k_fr_from_mont(const uint32_t* __restrict
 }
 
 // ---- typed columns (kzg_rows_commit_typed / kzg_rows_read): integers of their natural width <-> Montgomery elements
-// x * 2^261 mod r for x < 2^64, below 2r: x has three limbs, so a Montgomery product of radix 2^87 by 2^(261 + 87) mod r
-// does it -- 27 + 24 mads where fr9_to_mont spends 81 + 72.  (x C + q r) / 2^87 < (2^64 + 2^87) r / 2^87 < 2r; a column sum
-// is at most six products below 2^58.  Modelled limb by limb against x * 2^261 % r over the edges and 2 x 10^4 random x.
-FR9_TABLE(fr9_2_348, 0x1c74a235u, 0x1cebd299u, 0x0150fcf8u, 0x18886c4cu, 0x162c0a9du, 0x06cbaa5fu, 0x17bd1efeu, 0x06f2bf4bu, 0x0032f10cu)
-KZG_DEV void fr9_mont_from_u64(fr9_t& r, uint64_t x) {
-    const uint32_t a[3] = {(uint32_t)x & FR9_MASK, (uint32_t)(x >> 29) & FR9_MASK, (uint32_t)(x >> 58)};
-    uint32_t q[3];
-    uint64_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < 11; k++) {
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const int j = k - i;
-            if (j >= 0 && j < 9) acc += (uint64_t)a[i] * fr9_2_348(j);
-        }
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const int j = k - i;
-            if (i < k && j >= 1 && j < 9) acc += (uint64_t)q[i] * fr9_r(j);
-        }
-        if (k < 3) {
-            q[k] = (0u - (uint32_t)acc) & FR9_MASK;
-            acc += q[k];
-        } else {
-            r.l[k - 3] = (uint32_t)acc & FR9_MASK;
-        }
-        acc >>= 29;
-    }
-    r.l[8] = (uint32_t)acc;
-}
+// (fr9_mont_from_u64, x * 2^261 mod r for x < 2^64 below 2r, lives in fr_u64.hip.h: fr_int.hip encodes with it too)
 // r - a for a canonical a != 0
 KZG_DEV void fr9_neg_canon(fr9_t& r, const fr9_t& a) {
     int32_t br = 0;

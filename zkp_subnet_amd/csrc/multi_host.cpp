@@ -505,6 +505,14 @@ int kzg_multi_rows_commit_derived(kzg_multi* mh, uint32_t i, uint32_t n_input_ha
                                       out_handle);
     });
 }
+int kzg_multi_rows_commit_int(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
+                              const kzg_int_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48,
+                              uint64_t* out_counts, uint64_t* out_first, uint64_t* out_handle) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_int(c, s, n_input_handles, input_handles, n_ops, ops, opts, out_commitments48, out_counts,
+                                  out_first, out_handle);
+    });
+}
 int kzg_multi_rows_commit_expr(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                uint32_t n_exprs, const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48,
                                uint64_t* out_nonzero, uint64_t* out_first, uint64_t* out_handle) {

@@ -1270,6 +1270,88 @@ int rows_derived_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs
     return KZG_OK;
 }
 
+// The integer ALU columns (kzg_rows_commit_int): a set built FROM sets, every output row a pure function of the canonical
+// integers of ONE or TWO source rows.  Each DISTINCT source row (by device pointer: several ops, both operands of one op, or two
+// indices of a repeated handle, may name one row) is transformed forward once into its own vector of the lane's quotient
+// workspace.
+//   step                      launches                         per call
+//   forward transforms        launch_fr_ntt                    one per distinct source row named
+//   every op                  launch_int (k_fr_int)            ONE, grid y = op
+//   tail                      launch_sort_tail                 one per output row, with `usable` only
+//   inverse transform         row_to_coeffs                    one per output row, straight into dst
+//   commit                    multi_msms_finish                ONE pass of n_out scalar sets
+// The outputs lie side by side behind the sources in the order of the set (op by op, row 0 then row 1), so output row c is
+// vector c.  The counts and first rows are u64 words behind the first two evaluation slots of the record (the layout of the
+// expression call) and come back in the copy behind the MSM: the call never waits on its own.
+// Workspace: distinct sources + n_out vectors of T.
+int rows_int_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_ops, const kzg_int_op* ops, uint32_t n_out,
+                 uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_counts, uint64_t* out_first, const Blind* lay) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const int lg = ilog2_exact(T);
+    uint32_t* tw = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
+    const uint64_t vw = T * 8;                        // one vector, in words
+    const uint64_t n = lay ? lay->usable : T;         // the rows that are read
+    constexpr uint32_t CNT_OFF = 64;                  // the counts in the record, then the first rows
+    static_assert(CNT_OFF + 16 * KZG_MAX_BATCH_OPEN <= MR_PAIRS * 32 && KZG_MAX_BATCH_OPEN <= INT_MAX_OPS,
+                  "the count and the first row of every op fit the record's evaluation slots");
+    const uint32_t* distinct[POLY_MAX_ROWS];
+    uint32_t sa[INT_MAX_OPS], sb[INT_MAX_OPS], nd = 0;
+    auto slot_of = [&](const uint32_t* p) {
+        uint32_t d = 0;
+        while (d < nd && distinct[d] != p) d++;
+        if (d == nd) distinct[nd++] = p;
+        return d;
+    };
+    for (uint32_t o = 0; o < n_ops; o++) {
+        sa[o] = slot_of(inputs.r[ops[o].a]);
+        sb[o] = (ops[o].flags & KZG_INT_IMM) ? UINT32_MAX : slot_of(inputs.r[ops[o].b]);
+    }
+    HIPCHK(ctx, A.qext.ensure(((size_t)nd + n_out) * T * 32));
+    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + nd * vw, *mid = A.ntt_mid.as<uint32_t>();
+    uint8_t* rec = A.brec.as<uint8_t>();
+    uint64_t *cnt = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF), *first = cnt + n_ops;
+    for (uint32_t d = 0; d < nd; d++) {
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, distinct[d], src + d * vw, lg, tw, nullptr, mid);
+    }
+    HIPCHK(ctx, hipMemsetAsync(cnt, 0, 8 * (size_t)n_ops, A.stream));
+    HIPCHK(ctx, hipMemsetAsync(first, 0xff, 8 * (size_t)n_ops, A.stream));   // KZG_INT_NONE
+    IntTab tab;
+    memset(&tab, 0, sizeof(tab));
+    for (uint32_t o = 0, c = 0; o < n_ops; c += ops[o++].count) {
+        IntOp& op = tab.op[o];
+        op.a = src + sa[o] * vw;
+        op.b = sb[o] == UINT32_MAX ? nullptr : src + sb[o] * vw;
+        op.imm = ops[o].imm;
+        op.out = outv + c * vw;
+        op.kind = ops[o].kind;
+        op.w = ops[o].width;
+        op.count = ops[o].count;
+    }
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_int(A.stream, tab, n_ops, T, n, cnt, first);
+    }
+    for (uint32_t c = 0; c < n_out; c++) {
+        if (lay) {
+            Span sp(ctx, A, KZG_T_POLY);
+            launch_sort_tail(A.stream, outv + c * vw, T, n, lay->tail_be32 + 32 * (size_t)c * (T - n), A.flags());
+        }
+        const uint32_t* cf;
+        if (int rc = row_to_coeffs(ctx, A, outv + c * vw, T, 1, &cf, dst + c * vw)) return rc;
+    }
+    HIPCHK(ctx, hipGetLastError());
+    uint8_t ev[CNT_OFF + 16 * KZG_MAX_BATCH_OPEN + 32];
+    const uint32_t npairs = (CNT_OFF + 16 * n_ops + 31) / 32;
+    if (int rc = multi_msms_finish(ctx, H, i, T, dst, n_out, 0, npairs, out_c48, ev, nullptr)) return rc;
+    memcpy(out_counts, ev + CNT_OFF, 8 * (size_t)n_ops);
+    memcpy(out_first, ev + CNT_OFF + 8 * (size_t)n_ops, 8 * (size_t)n_ops);
+    return KZG_OK;
+}
+
 // The expression columns (kzg_rows_commit_expr): a set built FROM sets, every output row plain arithmetic in source rows.
 // Each DISTINCT source row (by device pointer: two indices of a repeated handle name one row) that some term names is
 // transformed forward once into its own vector of the lane's quotient workspace; a row no term names is not transformed.

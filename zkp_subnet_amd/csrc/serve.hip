@@ -1273,6 +1273,80 @@ int rows_derived(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, cons
     return KZG_OK;
 }
 
+// kzg_rows_commit_int: the lookups of an open (one handle list), the reservation of a commit of n_out rows.  opts == NULL, or
+// usable == 0: all T rows are read.  Kinds, widths, counts and immediates are checked here, on the host, before a lane is taken
+int rows_int(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
+             const kzg_int_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_counts,
+             uint64_t* out_first, uint64_t* out_handle) {
+    if (!ctx || !input_handles || !out_commitments48 || !out_counts || !out_first || !out_handle) return KZG_E_ARG;
+    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "int: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (n_ops == 0 || n_ops > KZG_MAX_BATCH_OPEN || !ops)
+        return fail(ctx, KZG_E_ARG, "int: n_ops must be in [1, KZG_MAX_BATCH_OPEN]");
+    uint32_t n_out = 0;
+    for (uint32_t o = 0; o < n_ops; o++) {
+        const kzg_int_op& op = ops[o];
+        if (op.kind < KZG_INT_AND || op.kind > KZG_INT_SPLIT)
+            return fail(ctx, KZG_E_ARG, "int: unknown kind (KZG_INT_AND .. KZG_INT_SPLIT)");
+        if (op.flags & ~KZG_INT_IMM) return fail(ctx, KZG_E_ARG, "int: flags must be 0 or KZG_INT_IMM");
+        if (op.width == 0 || op.width > 64) return fail(ctx, KZG_E_ARG, "int: the width must be in [1, 64]");
+        if (op.count != 1 && !(op.count == 2 && op.kind >= KZG_INT_ADD))
+            return fail(ctx, KZG_E_ARG, "int: count must be 1 on AND, OR and XOR, and 1 or 2 on the other kinds");
+        if (op.flags & KZG_INT_IMM) {
+            if (op.b != 0) return fail(ctx, KZG_E_ARG, "int: the row b must be 0 beside an immediate");
+            if (op.kind == KZG_INT_SPLIT ? op.imm > op.width : op.width < 64 && (op.imm >> op.width) != 0)
+                return fail(ctx, KZG_E_ARG, "int: an immediate must be below 2^width (SPLIT: a shift of at most width)");
+        } else if (op.imm != 0) {
+            return fail(ctx, KZG_E_ARG, "int: the immediate must be 0 without KZG_INT_IMM");
+        }
+        n_out += op.count;
+    }
+    if (n_out > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "int: n_out, the sum of the counts, must be in [1, KZG_MAX_BATCH_OPEN]");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs irefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab it;
+    uint32_t ki = 0, i = 0;
+    uint64_t T = 0;
+    if (int rc = rows_lookup(ctx, "int", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    for (uint32_t o = 0; o < n_ops; o++)
+        if (ops[o].a >= ki || ops[o].b >= ki)
+            return fail(ctx, KZG_E_ARG, "int: a row must index the concatenated rows of the input sets");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "int: the row length must be a power of two");
+    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
+    if (lay.usable) {
+        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "int: usable must be in [1, T - 1] (0: all T rows are read)");
+        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
+            return fail(ctx, KZG_E_ARG, "int: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
+        if (!lay.tail_be32) return fail(ctx, KZG_E_ARG, "int: tail_be32 must be given when usable > 0");
+        for (uint64_t j = 0; j < n_out * (T - lay.usable); j++)
+            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
+                return fail(ctx, KZG_E_ARG, "int: tail scalars must be canonical (< r)");
+    } else if (lay.tail_be32) {
+        return fail(ctx, KZG_E_ARG, "int: tail_be32 must be null in the plain layout (usable = 0)");
+    }
+    if (int rc2 = rows_reserve(ctx, "int", pend, (size_t)n_out * T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    uint64_t counts[KZG_MAX_BATCH_OPEN], first[KZG_MAX_BATCH_OPEN];
+    rc = rows_int_dev(ctx, H, i, it, n_ops, ops, n_out, T, pend.buf.as<uint32_t>(), c48, counts, first,
+                      lay.usable ? &lay : nullptr);
+    if (rc) return rc;
+    memcpy(out_commitments48, c48, 48 * (size_t)n_out);
+    memcpy(out_counts, counts, 8 * (size_t)n_ops);
+    memcpy(out_first, first, 8 * (size_t)n_ops);
+    *out_handle = rows_insert(ctx, pend, i, n_out, T);
+    return KZG_OK;
+}
+
 // kzg_rows_commit_expr: the lookups of an open (one handle list), the reservation of a commit of n_out rows -- none when every
 // expression is a check.  opts == NULL, or usable == 0: all T rows are evaluated.  Coefficients are checked here, on the host
 int rows_expr(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
@@ -2288,6 +2362,12 @@ int kzg_rows_commit_derived(kzg_ctx* ctx, uint32_t n_input_handles, const uint64
                             uint64_t* out_counts, uint64_t* out_handle) {
     return rows_derived(ctx, UINT32_MAX, n_input_handles, input_handles, n_ops, ops, opts, out_commitments48, out_counts,
                         out_handle);
+}
+int kzg_rows_commit_int(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
+                        const kzg_int_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_counts,
+                        uint64_t* out_first, uint64_t* out_handle) {
+    return rows_int(ctx, UINT32_MAX, n_input_handles, input_handles, n_ops, ops, opts, out_commitments48, out_counts, out_first,
+                    out_handle);
 }
 int kzg_rows_commit_expr(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
                          const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48, uint64_t* out_nonzero,

@@ -935,6 +935,74 @@ class HipEngine:
                                                     c, cnt, ctypes.byref(h)))
         return RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]), [int(v) for v in cnt]
 
+    # ---- a set built from sets: machine-word arithmetic on the canonical integers of one or two resident columns
+    _INT_KINDS = {"and": _native.KZG_INT_AND, "or": _native.KZG_INT_OR, "xor": _native.KZG_INT_XOR, "add": _native.KZG_INT_ADD,
+                  "sub": _native.KZG_INT_SUB, "mul": _native.KZG_INT_MUL, "divmod": _native.KZG_INT_DIVMOD,
+                  "split": _native.KZG_INT_SPLIT}
+
+    @classmethod
+    def int_ops(cls, ops, what: str = "commit_int") -> List[tuple]:
+        """The kzg_int_op fields (kind, width, a, b, imm, flags, count) of a list of ops (kind, w, a, b) or (kind, w, a, b,
+        count): kind one of "and" "or" "xor" "add" "sub" "mul" "divmod" "split", w in [1, 64], a a row index, b a row index or
+        ("imm", value), count 1 or, except on the bitwise kinds, 2 (default 1).  Raises KzgError(KZG_E_ARG) with the cause."""
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: int: {why}")   # noqa: E731
+        ops = list(ops) if isinstance(ops, (list, tuple)) else None
+        if not ops or len(ops) > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"ops must be a list of 1 .. {_native.KZG_MAX_BATCH_OPEN} entries (n_ops)")
+        is_u = lambda v, top: isinstance(v, int) and not isinstance(v, bool) and 0 <= v < top   # noqa: E731
+        recs = []
+        for op in ops:
+            if not isinstance(op, (list, tuple)) or len(op) not in (4, 5):
+                raise bad("an op is (kind, w, a, b) or (kind, w, a, b, count)")
+            name, w, a, b = op[:4]
+            count = op[4] if len(op) == 5 else 1
+            if not isinstance(name, str) or name not in cls._INT_KINDS:
+                raise bad(f"unknown kind {name!r} (one of {', '.join(cls._INT_KINDS)})")
+            kind = cls._INT_KINDS[name]
+            if not is_u(w, 65) or w == 0:
+                raise bad("the width must be an integer in [1, 64]")
+            if not is_u(count, 3) or count == 0 or (count == 2 and kind < _native.KZG_INT_ADD):
+                raise bad("count must be 1 on and, or and xor, and 1 or 2 on the other kinds")
+            if not is_u(a, 1 << 32):
+                raise bad("a row must be an integer in [0, 2^32)")
+            if isinstance(b, (list, tuple)):
+                if len(b) != 2 or b[0] != "imm" or not is_u(b[1], 1 << 64):
+                    raise bad('an immediate is ("imm", value) with value an integer in [0, 2^64)')
+                if b[1] > w if kind == _native.KZG_INT_SPLIT else b[1] >> w:
+                    raise bad("an immediate must be below 2^width (split: a shift of at most width)")
+                recs.append((kind, w, a, 0, b[1], _native.KZG_INT_IMM, count))
+            elif is_u(b, 1 << 32):
+                recs.append((kind, w, a, b, 0, 0, count))
+            else:
+                raise bad('the second operand is a row, an integer in [0, 2^32), or ("imm", value)')
+        if sum(r[6] for r in recs) > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"n_out: the ops give {sum(r[6] for r in recs)} output rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+        return recs
+
+    def commit_int(self, input_sets: Sequence[object], ops: Sequence[tuple], usable: Optional[int] = None,
+                   tail: Sequence[bytes] = ()) -> Tuple["RowSet", List[int], List[Optional[int]]]:
+        """kzg_rows_commit_int over the concatenated rows of input_sets (RowSet objects or bare handles).  ops: see int_ops; the
+        operands are the cells' canonical integers reduced to their low w bits, the output rows of an op in this order: and /
+        or / xor: a op b; add: the sum mod 2^w, the carry; sub: the difference mod 2^w, the borrow (1 where a < b); mul: the low
+        word, the high word; divmod: the quotient (2^w - 1 where b = 0), the remainder (a where b = 0); split: a >> s, a mod 2^s
+        with s the second operand, at most w.  Returns (the new RowSet of all output rows in the order of ops; per op the number
+        of cells read with an operand at or above 2^w (a split's shift cell: above w); per op the smallest such row, or None).
+        usable = None reads all T rows; otherwise only rows [0, usable) are read and row usable + s of output column c takes
+        tail[c * (T - usable) + s] (32 bytes each, column-major; there is no closing row)."""
+        what = "commit_int"
+        ni, hi = self._handle_array(input_sets, what)
+        recs = self.int_ops(ops, what)
+        n_out = sum(r[6] for r in recs)
+        wi, T, lay = self._column_layout(what, input_sets, n_out, "n_out", "read", usable, tail)
+        opts = _native.DeriveOpts(*lay) if lay else None
+        arr = (_native.IntOp * len(recs))(*[_native.IntOp(*r) for r in recs])
+        c, h = ctypes.create_string_buffer(48 * n_out), ctypes.c_uint64(0)
+        cnt, first = (ctypes.c_uint64 * len(recs))(), (ctypes.c_uint64 * len(recs))()
+        self._chk(self._lib.kzg_rows_commit_int(self._h, ni, hi, len(recs), arr, ctypes.byref(opts) if opts is not None else None,
+                                                c, cnt, first, ctypes.byref(h)))
+        return (RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]), [int(v) for v in cnt],
+                [None if int(v) == _native.KZG_INT_NONE else int(v) for v in first])
+
     # ---- a set built from sets: columns that are plain arithmetic in resident columns, and gates checked row by row
     def commit_expr(self, input_sets: Sequence[object], exprs: Sequence[Sequence], usable: Optional[int] = None,
                     tail: Sequence[bytes] = ()) -> Tuple[Optional["RowSet"], List[int], List[Optional[int]]]:
