@@ -1034,6 +1034,7 @@ int kzg_rows_check_copies(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t*
  * OUT OF SCOPE: signed variants (sra, mulh, signed div / rem, slt: the caller adds the bias 2^(w-1) and corrects with
  * kzg_rows_commit_expr); widths above 64; three-operand ops (a b + c, funnel shifts); per-row selectors (an op-code column
  * choosing the kind per row: build every candidate and select with kzg_rows_commit_expr); a separate count of zero divisors.
+ * (Both in ONE call, the signed kinds and a kind chosen per row by an op-code column: kzg_rows_commit_alu below.)
  * SOUNDNESS: nothing here is a proof.  The rows are prover data; the argument is the caller's gates plus the range lookups of
  * the outputs (kzg_rows_commit_derived LIMBS -> kzg_rows_commit_multiplicities -> kzg_rows_commit_lookup_sum): a + b = s + carry M;
  * a - b = d - borrow M; a b = lo + hi M; a = q b + rem with rem < b shown through the borrow of a SUB (and the b = 0 case
@@ -1064,6 +1065,115 @@ int kzg_rows_commit_int(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* 
                         const kzg_int_op* ops, const kzg_derive_opts* opts /* NULL: plain */,
                         uint8_t* out_commitments48 /* n_out * 48 */, uint64_t* out_counts /* n_ops */,
                         uint64_t* out_first /* n_ops */, uint64_t* out_handle);
+/* THE ALU COLUMN WITH AN OP-CODE COLUMN: kzg_rows_commit_int with the kind chosen PER ROW, the shape of a CPU table in a zkVM
+ * trace -- one result column, and an op-code column that says per row whether the row is an add, an sltu, an sra or a mulh.
+ * `program` has n_entries <= KZG_ALU_MAX_PROGRAM entries and the entry's index is the op-code.  An entry is idle (kind
+ * KZG_ALU_IDLE, every other field 0) or gives a kind, a width w in [1, 64] with M = 2^w, and, with KZG_ALU_IMM in flags, an
+ * immediate second operand imm.  Each of the n_units <= KZG_ALU_MAX_UNITS units names three rows of the concatenated rows of
+ * the input_handles sets (as in kzg_rows_open) -- the op-code column op_row and the operand columns a and b; one row may serve
+ * several roles, one program serves all units -- and `count`, 1 or 2, its number of output rows.  Cells are CANONICAL INTEGERS
+ * as in kzg_rows_commit_int.  Per cell t, with c the integer of op_row[t]:
+ *   c >= n_entries (a cell at or above 2^32 included)   UNKNOWN: the outputs are 0; counted in out_unknown[unit], the smallest
+ *                                                       such row in out_first_unknown[unit] (KZG_ALU_NONE: none)
+ *   program[c] idle                                     the outputs are 0; nothing else is read, nothing is counted (the row of a
+ *                                                       load or a branch in a CPU table)
+ *   otherwise                                           a and b are reduced to their low w bits exactly as in kzg_rows_commit_int:
+ *                                                       a cell with an operand at or above 2^w is counted ONCE in
+ *                                                       out_counts[unit], the smallest such row is out_first[unit] (KZG_ALU_NONE:
+ *                                                       none); it is never an error.  With KZG_ALU_IMM the second operand is imm
+ *                                                       and column b is neither read nor counted for that row
+ * The output rows (count selects row 0 alone or both), with sgn(x) = x - M [x >= M / 2] and, for the five shifts and
+ * rotations, s = b mod w (the RISC-V rule at w = 32 and 64: a shift amount is never out of range on its own):
+ *   KZG_ALU_AND .. KZG_ALU_SPLIT   the numbers and the exact rows of KZG_INT_AND .. KZG_INT_SPLIT, SPLIT's clamp-and-count of a
+ *                                  shift above w included; row 1 of AND, OR and XOR, which have none there, is 0
+ *   KZG_ALU_LTU      [a < b];                                   (a - b) mod M
+ *   KZG_ALU_LT       [sgn a < sgn b];                           (a - b) mod M
+ *   KZG_ALU_EQ       [a = b];                                   (a - b) mod M
+ *   KZG_ALU_SLL      (a 2^s) mod M;                             a >> (w - s), 0 where s = 0
+ *   KZG_ALU_SRL      a >> s;                                    a mod 2^s
+ *   KZG_ALU_SRA      floor(sgn a / 2^s) mod M;                  a mod 2^s
+ *   KZG_ALU_ROTL     SLL's row 0 + SLL's row 1;                 a >> (w - s), 0 where s = 0
+ *   KZG_ALU_ROTR     (a >> s) + (a mod 2^s) 2^(w - s), a where s = 0;   a mod 2^s
+ *   KZG_ALU_MULHU    (a b) >> w;                                (a b) mod M
+ *   KZG_ALU_MULH     floor(sgn a sgn b / M) mod M;              (a b) mod M
+ *   KZG_ALU_MULHSU   floor(sgn a b / M) mod M;                  (a b) mod M
+ *   KZG_ALU_DIV      q = trunc(sgn a / sgn b) mod M;            (sgn a - q sgn b) mod M.  The RISC-V convention: b = 0 gives M - 1
+ *                                                               and a; a = M / 2 with b = M - 1 (the overflow) gives M / 2 and 0;
+ *                                                               neither is counted, neither is an error
+ *   KZG_ALU_REM      DIV's row 1;                               DIV's row 0
+ *   KZG_ALU_REMU     a mod b, a where b = 0;                    floor(a / b), M - 1 where b = 0
+ *   KZG_ALU_SEXT     the low f bits of a sign-extended to w bits;   bit f - 1 of a.  f is the second operand: a column cell of 0
+ *                                                               or above w is out of range, taken as w and counted
+ * All of it is defined at w = 1 (sgn 1 = -1, s = 0).  An immediate must be below 2^w; SPLIT's and SEXT's at most w, SEXT's not 0.
+ * count = 2 needs an entry whose kind has a second row (a program of AND, OR and XOR entries alone refuses it).  n_out = the sum
+ * of the counts <= KZG_MAX_BATCH_OPEN.  All outputs form ONE new set of the same worker and length, unit by unit, row 0 then
+ * row 1: out_commitments48[c] equals kzg_rows_commit(i, n_out, these rows, T, 1, ..)[c] byte for byte.  ONE kernel launch
+ * computes every unit; each DISTINCT source row is transformed once; the four statistics of every unit come back in the copy
+ * behind the MSM; nothing row-sized crosses the host link.  opts (usable / tail), the handle rules, staleness,
+ * KZG_MAX_ROW_SETS, KZG_E_BUSY / KZG_E_NOMEM and thread safety are exactly those of kzg_rows_commit_int.  KZG_E_ARG with a
+ * message that begins "alu:" and names the cause: n_entries outside [1, KZG_ALU_MAX_PROGRAM]; n_units outside [1,
+ * KZG_ALU_MAX_UNITS]; an unknown kind; an unknown flag; an idle entry with a field set; w outside [1, 64]; an immediate that
+ * does not fit, or one given without KZG_ALU_IMM; count outside {1, 2}, or 2
+ * without a two-row kind; n_out > KZG_MAX_BATCH_OPEN; a row at or beyond the concatenation; the usable, tail and handle refusals
+ * of kzg_rows_commit_int.  After any error the context keeps serving.
+ * OUT OF SCOPE: widths above 64; three-operand ops; a per-row width column (the width comes from the program entry); a per-row
+ * count; Zbb-style bit counts (clz, ctz, popcount) and min / max; more than KZG_ALU_MAX_PROGRAM op-codes or KZG_ALU_MAX_UNITS
+ * units per call; a separate count of zero divisors or overflows; any proof.
+ * SOUNDNESS: nothing here is a proof.  The rows are prover data; the argument is the caller's gates, each multiplied by the
+ * selector of its op-code, plus the range lookups of the outputs (as for kzg_rows_commit_int): LTU, LT, EQ: a - b = d - borrow M
+ * with the sign bits of a and b split off for LT, and d inv0(d) for EQ; SLL, ROTL: a 2^s = hi M + lo; SRL, SPLIT, ROTR: a = hi
+ * 2^s + lo with lo < 2^s; SRA: sgn(hi) 2^s + lo = sgn a; MULHU: a b = hi M + lo; MULH: sgn a sgn b = sgn(hi) M + lo; MULHSU:
+ * sgn a b = sgn(hi) M + lo; DIV, REM: sgn a = sgn q sgn b + sgn r with |r| < |b| and r = 0 or of a's sign, the zero divisor and
+ * the overflow through their is-zero bits; REMU: a = q b + r with r < b; SEXT: x = lo + bit (M - 2^f) with lo < 2^f and bit its
+ * top bit; 2^s for a per-row s fetched from a table (kzg_rows_commit_fetch).  Every challenge is drawn AFTER these commitments
+ * are fixed.  Zero counts are a convenience for the prover and convince no verifier.  The library derives no challenge and
+ * draws no randomness: the tail must be fresh per proof. */
+#define KZG_ALU_IDLE   0
+#define KZG_ALU_AND    1
+#define KZG_ALU_OR     2
+#define KZG_ALU_XOR    3
+#define KZG_ALU_ADD    4
+#define KZG_ALU_SUB    5
+#define KZG_ALU_MUL    6
+#define KZG_ALU_DIVMOD 7
+#define KZG_ALU_SPLIT  8
+#define KZG_ALU_LTU    9
+#define KZG_ALU_LT     10
+#define KZG_ALU_EQ     11
+#define KZG_ALU_SLL    12
+#define KZG_ALU_SRL    13
+#define KZG_ALU_SRA    14
+#define KZG_ALU_ROTL   15
+#define KZG_ALU_ROTR   16
+#define KZG_ALU_MULHU  17
+#define KZG_ALU_MULH   18
+#define KZG_ALU_MULHSU 19
+#define KZG_ALU_DIV    20
+#define KZG_ALU_REM    21
+#define KZG_ALU_REMU   22
+#define KZG_ALU_SEXT   23
+#define KZG_ALU_IMM    1u                   /* flags: the entry's second operand is `imm`, not column b */
+#define KZG_ALU_NONE   0xffffffffffffffffull
+#define KZG_ALU_MAX_PROGRAM 64
+#define KZG_ALU_MAX_UNITS   8
+typedef struct kzg_alu_entry {
+    uint32_t kind;   /* KZG_ALU_IDLE or a kind KZG_ALU_AND .. KZG_ALU_SEXT */
+    uint32_t width;  /* w in [1, 64]; 0 on an idle entry */
+    uint64_t imm;    /* second operand with KZG_ALU_IMM: below 2^w (SPLIT, SEXT: at most w; SEXT: not 0); must be 0 without */
+    uint32_t flags;  /* 0 or KZG_ALU_IMM */
+    uint32_t pad;    /* must be 0 */
+} kzg_alu_entry;
+typedef struct kzg_alu_unit {
+    uint32_t op_row; /* the op-code column: a row, index into the concatenated rows of input_handles */
+    uint32_t a;      /* first operand column */
+    uint32_t b;      /* second operand column (read only on rows whose entry has no immediate) */
+    uint32_t count;  /* output rows: 1 or 2 */
+} kzg_alu_unit;
+int kzg_rows_commit_alu(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_entries,
+                        const kzg_alu_entry* program, uint32_t n_units, const kzg_alu_unit* units,
+                        const kzg_derive_opts* opts /* NULL: plain */, uint8_t* out_commitments48 /* n_out * 48 */,
+                        uint64_t* out_counts /* n_units */, uint64_t* out_first /* n_units */, uint64_t* out_unknown /* n_units */,
+                        uint64_t* out_first_unknown /* n_units */, uint64_t* out_handle);
 /* THE QUOTIENT WITH LOOKUP SELECTORS: kzg_rows_commit_quotient_zk and kzg_rows_quotient_part for lookups that are enabled on
  * some rows only.  selectors->selector_rows holds L = lookup->n_lookups entries, each a row index into the call's concatenated
  * rows (the caller's fixed column q_l, the row that kzg_rows_commit_multiplicities_sel / _lookup_sum_sel read) or
@@ -1443,6 +1553,11 @@ int kzg_multi_rows_check_copies(kzg_multi* mh, uint32_t i, uint32_t n_wire_handl
 int kzg_multi_rows_commit_int(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
                               const kzg_int_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48,
                               uint64_t* out_counts, uint64_t* out_first, uint64_t* out_handle);
+/* kzg_rows_commit_alu on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_alu(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                              uint32_t n_entries, const kzg_alu_entry* program, uint32_t n_units, const kzg_alu_unit* units,
+                              const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_counts, uint64_t* out_first,
+                              uint64_t* out_unknown, uint64_t* out_first_unknown, uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

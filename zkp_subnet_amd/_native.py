@@ -29,6 +29,14 @@ KZG_DERIVE_INV0, KZG_DERIVE_LIMBS = 1, 2   # kzg_rows_commit_derived: kzg_derive
 KZG_INT_AND, KZG_INT_OR, KZG_INT_XOR, KZG_INT_ADD, KZG_INT_SUB, KZG_INT_MUL, KZG_INT_DIVMOD, KZG_INT_SPLIT = range(1, 9)
 KZG_INT_IMM = 1
 KZG_INT_NONE = 0xffffffffffffffff
+# kzg_rows_commit_alu: kzg_alu_entry.kind (the first eight are the KZG_INT_* kinds), the immediate flag, the sentinel, the limits
+(KZG_ALU_AND, KZG_ALU_OR, KZG_ALU_XOR, KZG_ALU_ADD, KZG_ALU_SUB, KZG_ALU_MUL, KZG_ALU_DIVMOD, KZG_ALU_SPLIT, KZG_ALU_LTU,
+ KZG_ALU_LT, KZG_ALU_EQ, KZG_ALU_SLL, KZG_ALU_SRL, KZG_ALU_SRA, KZG_ALU_ROTL, KZG_ALU_ROTR, KZG_ALU_MULHU, KZG_ALU_MULH,
+ KZG_ALU_MULHSU, KZG_ALU_DIV, KZG_ALU_REM, KZG_ALU_REMU, KZG_ALU_SEXT) = range(1, 24)
+KZG_ALU_IDLE = 0
+KZG_ALU_IMM = 1
+KZG_ALU_NONE = 0xffffffffffffffff
+KZG_ALU_MAX_PROGRAM, KZG_ALU_MAX_UNITS = 64, 8
 KZG_MAX_EXPR_FACTORS = 8   # kzg_rows_commit_expr: factors of one term
 KZG_EXPR_CHECK = 1   # kzg_expr.flags: evaluate and count only
 KZG_EXPR_NONE = 0xffffffffffffffff   # out_first: no non-zero cell
@@ -111,6 +119,16 @@ class IntOp(ctypes.Structure):
     _fields_ = [("kind", _U32), ("width", _U32), ("a", _U32), ("b", _U32), ("imm", _U64), ("flags", _U32), ("count", _U32)]
 
 
+class AluEntry(ctypes.Structure):
+    """kzg_alu_entry"""
+    _fields_ = [("kind", _U32), ("width", _U32), ("imm", _U64), ("flags", _U32), ("pad", _U32)]
+
+
+class AluUnit(ctypes.Structure):
+    """kzg_alu_unit"""
+    _fields_ = [("op_row", _U32), ("a", _U32), ("b", _U32), ("count", _U32)]
+
+
 class Col(ctypes.Structure):
     """kzg_col"""
     _fields_ = [("data", ctypes.c_void_p), ("count", ctypes.c_uint64), ("kind", ctypes.c_uint32), ("fill_be32", ctypes.c_char_p)]
@@ -189,6 +207,9 @@ SYMBOLS = {
                                     ctypes.POINTER(_U64)]),
     "kzg_rows_commit_int": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(IntOp), ctypes.POINTER(DeriveOpts), _B,
                                  ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_alu": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(AluEntry), _U32, ctypes.POINTER(AluUnit),
+                                 ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64),
+                                 ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_derived": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp), ctypes.POINTER(DeriveOpts), _B,
                                      ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_expr": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,
@@ -310,6 +331,9 @@ SYMBOLS = {
     "kzg_multi_rows_commit_int": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(IntOp),
                                        ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64),
                                        ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_alu": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(AluEntry), _U32,
+                                       ctypes.POINTER(AluUnit), ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64),
+                                       ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_derived": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp),
                                            ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_expr": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,

@@ -959,6 +959,62 @@ class Client:
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
                 "counts": counts, "first": first}
 
+    # ---- the same arithmetic and its signed kinds with the kind chosen per row: the ALU column of a CPU table
+    @_guard
+    def worker_commit_alu(self, input_handles: Sequence[int], program: Sequence, units: Sequence[Sequence],
+                          usable: Optional[int] = None, tail: Sequence[str] = ()):
+        """Extension: ALU columns whose KIND an op-code column picks per row, computed and committed on the device as one new
+        set.  program: at most 64 entries, the index the op-code, each null (idle), [kind, w] or [kind, w, ["imm", value]]
+        with kind one of "and" "or" "xor" "add" "sub" "mul" "divmod" "split" "ltu" "lt" "eq" "sll" "srl" "sra" "rotl" "rotr"
+        "mulhu" "mulh" "mulhsu" "div" "rem" "remu" "sext" and w the width in [1, 64].  units: 1 to 8 entries [op_row, a, b] or
+        [op_row, a, b, count], rows of the concatenated input sets, count 1 or 2, at most 16 output rows in all.  Per cell, c is
+        the integer of op_row: c beyond the program gives 0 and is counted as unknown; a null entry gives 0 and reads nothing;
+        otherwise the entry's kind acts on a and b (or the entry's immediate, and then b is neither read nor counted) reduced to
+        their low w bits, as in worker_commit_int, and writes row 0 and row 1 of that kind (include/kzg_mi355x.h lists them).
+        usable and tail: as for worker_commit_int.  Returns the handle, the commitments of all output rows unit by unit, and
+        per unit `counts` (cells read with an operand out of range), `first` (the smallest such row, null: none), `unknown`
+        and `first_unknown` (the same for unknown op-codes).  Nothing here is a proof: the rows are prover data."""
+        what = "worker_commit_alu"
+        hs = _handles(input_handles)
+        try:
+            prog = []
+            for en in program:
+                if en is None:
+                    prog.append(None)
+                    continue
+                if isinstance(en, (str, bytes)) or len(en) not in (2, 3):
+                    raise ValueError(f'an entry is null, [kind, w] or [kind, w, ["imm", value]]: {en!r}')
+                rec = (str(en[0]), int(en[1]))
+                if len(en) == 3:
+                    imm = en[2]
+                    if not isinstance(imm, (list, tuple)) or len(imm) != 2 or imm[0] != "imm":
+                        raise ValueError(f'an immediate is ["imm", value]: {imm!r}')
+                    rec += (("imm", int(imm[1])),)
+                prog.append(rec)
+            us = []
+            for un in units:
+                if isinstance(un, (str, bytes)) or len(un) not in (3, 4):
+                    raise ValueError(f"a unit is [op_row, a, b] or [op_row, a, b, count]: {un!r}")
+                us.append(tuple(int(v) for v in un))
+        except (TypeError, ValueError, IndexError, KeyError) as e:
+            raise codec.CodecError(f"{what}: program must be a list of null, [kind, w] or [kind, w, [\"imm\", value]] and units "
+                                   f"a list of [op_row, a, b] or [op_row, a, b, count]: {e!r}") from e
+        if not prog or len(prog) > 64:
+            raise codec.CodecError(f"{what}: program must hold 1 to 64 entries")
+        if not us or len(us) > 8:
+            raise codec.CodecError(f"{what}: units must hold 1 to 8 entries")
+        if usable is None:
+            if tail:
+                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
+            tb = []
+        else:
+            usable, tb = self._blind(what, usable, tail)
+            if usable == 0:
+                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        rs, st = self.engine.commit_alu(hs, prog, us, usable, tb)
+        return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
+                "counts": st["counts"], "first": st["first"], "unknown": st["unknown"], "first_unknown": st["first_unknown"]}
+
     @staticmethod
     def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: Sequence[int], n_groups: int, width: int,
                                theta: str, gamma: str, coeff: str, active_row: Optional[int] = None,

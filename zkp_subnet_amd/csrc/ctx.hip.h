@@ -8,6 +8,7 @@
 //   serve.hip     the serving entry points: commit / open / msm / ntt / eval, resident slots, tickets, sums
 //   fr_derive.hip the kernels of kzg_rows_commit_derived: inverse-or-zero around the batched inversion, limb decomposition
 //   fr_int.hip    the kernel of kzg_rows_commit_int: machine-word arithmetic on the canonical integers of resident columns
+//   fr_alu.hip    the kernel of kzg_rows_commit_alu: the same arithmetic and its signed kinds, the kind chosen per cell by an op-code column
 //   fr_expr.hip   the kernel of kzg_rows_commit_expr: sums of products of rotated resident columns on H, counted and stored
 //   fr_recur.hip  the scan of kzg_rows_commit_recurrence: v[t + 1] = A[t] v[t] + B[t] as a ladder over affine maps
 //   fr_join.hip   the hash join of kzg_rows_commit_multiplicities, and the fetch of kzg_rows_commit_fetch that walks it
@@ -487,6 +488,13 @@ int rows_derived_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs
 // operand out of range and the smallest such row (KZG_INT_NONE: none).  lay: as for rows_derived_dev
 int rows_int_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_ops, const kzg_int_op* ops, uint32_t n_out,
                  uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_counts, uint64_t* out_first, const Blind* lay);
+// the n_out rows of the n_units units over one program of n_entries entries (checked by the caller: kinds, widths, immediates,
+// counts summing to n_out, rows inside `inputs`) into a new n_out-row set's buffer dst: their commitments and, per unit, four
+// words in out_stats: [u] the cells with an operand out of range, [n_units + u] the cells with an unknown op-code, [2 n_units
+// + u] and [3 n_units + u] the smallest such rows (KZG_ALU_NONE: none).  lay: as for rows_derived_dev
+int rows_alu_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_entries, const kzg_alu_entry* program,
+                 uint32_t n_units, const kzg_alu_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48,
+                 uint64_t* out_stats, const Blind* lay);
 // the n_out committed ones of the n_exprs expressions (checked by the caller: term counts and lengths in range, rows inside
 // `inputs`, rotations reduced into [0, T), canonical coefficients; is_check[e] != 0: expression e is only counted) into a new
 // n_out-row set's buffer dst (null when n_out = 0: then no transform back and no MSM runs): their commitments, and per

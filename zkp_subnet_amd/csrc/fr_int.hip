@@ -25,22 +25,7 @@
 
 static inline uint32_t nblk(uint64_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
 
-// the canonical integer of the cell at p: its low 64 bits; *high <- whether a bit at or above 2^64 is set
-KZG_DEV uint64_t int_load(const uint32_t* p, bool* high) {
-    fr9_t v;
-    uint32_t w[8];
-    fr9_load(v, p);
-    fr9_from_mont(v, v);
-    fr9_to_words(w, v);
-    *high = (w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) != 0;
-    return ((uint64_t)w[1] << 32) | w[0];
-}
-KZG_DEV void int_store(uint32_t* p, uint64_t x) {
-    fr9_t v;
-    fr9_mont_from_u64(v, x);
-    fr9_canon(v, v);
-    fr9_store(p, v);
-}
+// (int_load and int_store, a cell's canonical integer in and a machine word out, live in fr_u64.hip.h: fr_alu.hip uses them too)
 
 __global__ void __launch_bounds__(256) k_fr_int(const IntTab tab, uint64_t T, uint64_t n, unsigned long long* __restrict__ counts,
                                                  unsigned long long* __restrict__ first) {

@@ -382,6 +382,31 @@ static_assert(sizeof(IntTab) + 64 <= 4096, "the op table rides as a kernel argum
 // (a SPLIT's shift cell: above w), first[o] <- min(first[o], the smallest such t).  a and b are only read and may be one
 // vector; out must not overlap a source.  1 <= w <= 64, an immediate below 2^w (SPLIT: at most w): the caller's checks
 void launch_int(hipStream_t s, const IntTab& tab, uint32_t n_ops, uint64_t T, uint64_t n, uint64_t* counts, uint64_t* first);
+// ---- the ALU column of kzg_rows_commit_alu (fr_alu.hip): the kind of every CELL comes from an op-code column.  Cell t < n of
+// unit u reads c = op[t]; c >= n_prog (or no machine word at all): unknown, the outputs are 0; prog[c].kind == 0: idle, the
+// outputs are 0; else the kind, the width and the optional immediate of prog[c] act on a[t] and b[t] as a KZG_ALU_* kind says.
+// A unit writes `count` vectors of T elements at out (row 0, then row 1 at out + 8 T words), canonical Montgomery
+#define ALU_MAX_PROG 64
+#define ALU_MAX_UNITS 8
+struct AluEnt {   // 16 B: one ds_read_b128 per lane
+    uint64_t imm;
+    uint32_t kind, w_imm;   // kind: 0 idle, or KZG_ALU_*; w_imm: the width in the low byte, bit 8 set: the second operand is imm
+};
+struct AluUnit {
+    const uint32_t *op, *a, *b;   // b null: every entry of the program has an immediate
+    uint32_t* out;
+    uint32_t count, pad;
+};
+struct AluTab {
+    AluEnt prog[ALU_MAX_PROG];
+    AluUnit unit[ALU_MAX_UNITS];
+};
+static_assert(sizeof(AluEnt) == 16 && sizeof(AluTab) + 64 <= 4096, "the program and the units ride as a kernel argument");
+// ONE launch for the n_units <= ALU_MAX_UNITS units of tab over one program of n_prog <= ALU_MAX_PROG entries.  stats: four
+// runs of n_units words: [u] += the cells with an operand out of range, [n_units + u] += the cells with an unknown op-code,
+// [2 n_units + u] <- min(., the smallest out-of-range row), [3 n_units + u] <- min(., the smallest unknown row).  Sources are
+// only read and may coincide; out must not overlap a source.  Widths, immediates and kinds: the caller's checks
+void launch_alu(hipStream_t s, const AluTab& tab, uint32_t n_prog, uint32_t n_units, uint64_t T, uint64_t n, uint64_t* stats);
 // ---- the expression columns of kzg_rows_commit_expr (fr_expr.hip): v[t] = sum_u c_u prod_f src.r[row[u][f]][(t + rot[u][f]) mod T]
 // for t < n <= T over evaluation vectors of T canonical Montgomery elements (T a power of two, at most 2^32)
 #define EXPR_MAX_TERMS 16

@@ -1,5 +1,5 @@
 // The Montgomery form of a machine word: shared by the typed-column decoder (fr_ntt.hip, k_fr_from_typed) and the integer ALU
-// columns (fr_int.hip, k_fr_int), so that both translation units encode with one body.
+// columns (fr_int.hip, k_fr_int; fr_alu.hip, k_fr_alu), so that every translation unit encodes with one body.
 #pragma once
 #include "fr29.hip.h"
 
@@ -32,4 +32,22 @@ KZG_DEV void fr9_mont_from_u64(fr9_t& r, uint64_t x) {
         acc >>= 29;
     }
     r.l[8] = (uint32_t)acc;
+}
+
+// ---- a cell in, a machine word out: the two ends of every integer ALU kernel (fr_int.hip, fr_alu.hip)
+// the canonical integer of the cell at p: its low 64 bits; *high <- whether a bit at or above 2^64 is set
+KZG_DEV uint64_t int_load(const uint32_t* p, bool* high) {
+    fr9_t v;
+    uint32_t w[8];
+    fr9_load(v, p);
+    fr9_from_mont(v, v);
+    fr9_to_words(w, v);
+    *high = (w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) != 0;
+    return ((uint64_t)w[1] << 32) | w[0];
+}
+KZG_DEV void int_store(uint32_t* p, uint64_t x) {
+    fr9_t v;
+    fr9_mont_from_u64(v, x);
+    fr9_canon(v, v);
+    fr9_store(p, v);
 }

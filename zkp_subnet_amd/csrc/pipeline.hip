@@ -1352,6 +1352,93 @@ int rows_int_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, ui
     return KZG_OK;
 }
 
+// The ALU column with an op-code column (kzg_rows_commit_alu): the frame of rows_int_dev.  Each DISTINCT source row (by device
+// pointer: the op-code column and both operands of one unit, or rows of several units, may be one row) is transformed forward
+// once; column b of a unit is not transformed when every entry of the program has an immediate.
+//   step                      launches                         per call
+//   forward transforms        launch_fr_ntt                    one per distinct source row named
+//   every unit                launch_alu (k_fr_alu)            ONE, grid y = unit
+//   tail                      launch_sort_tail                 one per output row, with `usable` only
+//   inverse transform         row_to_coeffs                    one per output row, straight into dst
+//   commit                    multi_msms_finish                ONE pass of n_out scalar sets
+// The outputs lie side by side behind the sources, unit by unit, row 0 then row 1.  The four u64 statistics of every unit lie
+// in the record's evaluation slots where rows_int_dev keeps its two (at most 8 units x 32 B = the 256 B of 16 ops x 16 B) and
+// come back in the copy behind the MSM.  Workspace: distinct sources + n_out vectors of T.
+int rows_alu_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_entries, const kzg_alu_entry* program,
+                 uint32_t n_units, const kzg_alu_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48,
+                 uint64_t* out_stats, const Blind* lay) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const int lg = ilog2_exact(T);
+    uint32_t* tw = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
+    const uint64_t vw = T * 8;                        // one vector, in words
+    const uint64_t n = lay ? lay->usable : T;         // the rows that are read
+    constexpr uint32_t CNT_OFF = 64;                  // the statistics in the record: counts, unknown, first, first unknown
+    static_assert(CNT_OFF + 32 * KZG_ALU_MAX_UNITS <= MR_PAIRS * 32 && 32 * KZG_ALU_MAX_UNITS == 16 * KZG_MAX_BATCH_OPEN &&
+                      KZG_ALU_MAX_UNITS == ALU_MAX_UNITS && KZG_ALU_MAX_PROGRAM == ALU_MAX_PROG,
+                  "the four statistics of every unit fit the record's evaluation slots, where rows_int_dev keeps two per op");
+    bool needs_b = false;
+    for (uint32_t e = 0; e < n_entries; e++) needs_b |= program[e].kind != KZG_ALU_IDLE && !(program[e].flags & KZG_ALU_IMM);
+    const uint32_t* distinct[3 * ALU_MAX_UNITS];
+    uint32_t so[ALU_MAX_UNITS], sa[ALU_MAX_UNITS], sb[ALU_MAX_UNITS], nd = 0;
+    auto slot_of = [&](const uint32_t* p) {
+        uint32_t d = 0;
+        while (d < nd && distinct[d] != p) d++;
+        if (d == nd) distinct[nd++] = p;
+        return d;
+    };
+    for (uint32_t u = 0; u < n_units; u++) {
+        so[u] = slot_of(inputs.r[units[u].op_row]);
+        sa[u] = slot_of(inputs.r[units[u].a]);
+        sb[u] = needs_b ? slot_of(inputs.r[units[u].b]) : UINT32_MAX;
+    }
+    HIPCHK(ctx, A.qext.ensure(((size_t)nd + n_out) * T * 32));
+    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + nd * vw, *mid = A.ntt_mid.as<uint32_t>();
+    uint8_t* rec = A.brec.as<uint8_t>();
+    uint64_t* st = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF);
+    for (uint32_t d = 0; d < nd; d++) {
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, distinct[d], src + d * vw, lg, tw, nullptr, mid);
+    }
+    HIPCHK(ctx, hipMemsetAsync(st, 0, 16 * (size_t)n_units, A.stream));
+    HIPCHK(ctx, hipMemsetAsync(st + 2 * n_units, 0xff, 16 * (size_t)n_units, A.stream));   // KZG_ALU_NONE
+    AluTab tab;
+    memset(&tab, 0, sizeof(tab));
+    for (uint32_t e = 0; e < n_entries; e++) {
+        tab.prog[e].imm = program[e].imm;
+        tab.prog[e].kind = program[e].kind;
+        tab.prog[e].w_imm = program[e].width | ((program[e].flags & KZG_ALU_IMM) ? 0x100u : 0u);
+    }
+    for (uint32_t u = 0, c = 0; u < n_units; c += units[u++].count) {
+        AluUnit& un = tab.unit[u];
+        un.op = src + so[u] * vw;
+        un.a = src + sa[u] * vw;
+        un.b = sb[u] == UINT32_MAX ? nullptr : src + sb[u] * vw;
+        un.out = outv + c * vw;
+        un.count = units[u].count;
+    }
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_alu(A.stream, tab, n_entries, n_units, T, n, st);
+    }
+    for (uint32_t c = 0; c < n_out; c++) {
+        if (lay) {
+            Span sp(ctx, A, KZG_T_POLY);
+            launch_sort_tail(A.stream, outv + c * vw, T, n, lay->tail_be32 + 32 * (size_t)c * (T - n), A.flags());
+        }
+        const uint32_t* cf;
+        if (int rc = row_to_coeffs(ctx, A, outv + c * vw, T, 1, &cf, dst + c * vw)) return rc;
+    }
+    HIPCHK(ctx, hipGetLastError());
+    uint8_t ev[CNT_OFF + 32 * KZG_ALU_MAX_UNITS + 32];
+    const uint32_t npairs = (CNT_OFF + 32 * n_units + 31) / 32;
+    if (int rc = multi_msms_finish(ctx, H, i, T, dst, n_out, 0, npairs, out_c48, ev, nullptr)) return rc;
+    memcpy(out_stats, ev + CNT_OFF, 32 * (size_t)n_units);
+    return KZG_OK;
+}
+
 // The expression columns (kzg_rows_commit_expr): a set built FROM sets, every output row plain arithmetic in source rows.
 // Each DISTINCT source row (by device pointer: two indices of a repeated handle name one row) that some term names is
 // transformed forward once into its own vector of the lane's quotient workspace; a row no term names is not transformed.

@@ -1347,6 +1347,96 @@ int rows_int(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const ui
     return KZG_OK;
 }
 
+// kzg_rows_commit_alu: the frame of rows_int.  The program and the units are checked here, on the host, before a lane is taken
+int rows_alu(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_entries,
+             const kzg_alu_entry* program, uint32_t n_units, const kzg_alu_unit* units, const kzg_derive_opts* opts,
+             uint8_t* out_commitments48, uint64_t* out_counts, uint64_t* out_first, uint64_t* out_unknown,
+             uint64_t* out_first_unknown, uint64_t* out_handle) {
+    if (!ctx || !input_handles || !out_commitments48 || !out_counts || !out_first || !out_unknown || !out_first_unknown ||
+        !out_handle)
+        return KZG_E_ARG;
+    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "alu: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (n_entries == 0 || n_entries > KZG_ALU_MAX_PROGRAM || !program)
+        return fail(ctx, KZG_E_ARG, "alu: n_entries must be in [1, KZG_ALU_MAX_PROGRAM]");
+    if (n_units == 0 || n_units > KZG_ALU_MAX_UNITS || !units)
+        return fail(ctx, KZG_E_ARG, "alu: n_units must be in [1, KZG_ALU_MAX_UNITS]");
+    bool two_rows = false;
+    for (uint32_t e = 0; e < n_entries; e++) {
+        const kzg_alu_entry& en = program[e];
+        if (en.kind > KZG_ALU_SEXT) return fail(ctx, KZG_E_ARG, "alu: unknown kind (KZG_ALU_IDLE, KZG_ALU_AND .. KZG_ALU_SEXT)");
+        if (en.pad != 0) return fail(ctx, KZG_E_ARG, "alu: an entry's pad must be 0");
+        if (en.kind == KZG_ALU_IDLE) {
+            if (en.width != 0 || en.imm != 0 || en.flags != 0)
+                return fail(ctx, KZG_E_ARG, "alu: an idle entry must have width, imm and flags 0");
+            continue;
+        }
+        if (en.flags & ~KZG_ALU_IMM) return fail(ctx, KZG_E_ARG, "alu: flags must be 0 or KZG_ALU_IMM");
+        if (en.width == 0 || en.width > 64) return fail(ctx, KZG_E_ARG, "alu: the width must be in [1, 64]");
+        if (en.flags & KZG_ALU_IMM) {
+            const bool field = en.kind == KZG_ALU_SPLIT || en.kind == KZG_ALU_SEXT;
+            if (field ? en.imm > en.width || (en.kind == KZG_ALU_SEXT && en.imm == 0) : en.width < 64 && (en.imm >> en.width) != 0)
+                return fail(ctx, KZG_E_ARG,
+                            "alu: an immediate must be below 2^width (SPLIT, SEXT: at most width; SEXT: at least 1)");
+        } else if (en.imm != 0) {
+            return fail(ctx, KZG_E_ARG, "alu: the immediate must be 0 without KZG_ALU_IMM");
+        }
+        two_rows |= en.kind > KZG_ALU_XOR;
+    }
+    uint32_t n_out = 0;
+    for (uint32_t u = 0; u < n_units; u++) {
+        if (units[u].count != 1 && !(units[u].count == 2 && two_rows))
+            return fail(ctx, KZG_E_ARG, "alu: count must be 1 or 2, and 1 where no entry's kind has a second row (AND, OR, XOR)");
+        n_out += units[u].count;
+    }
+    if (n_out > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "alu: n_out, the sum of the counts, must be in [1, KZG_MAX_BATCH_OPEN]");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs irefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab it;
+    uint32_t ki = 0, i = 0;
+    uint64_t T = 0;
+    if (int rc = rows_lookup(ctx, "alu", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    for (uint32_t u = 0; u < n_units; u++)
+        if (units[u].op_row >= ki || units[u].a >= ki || units[u].b >= ki)
+            return fail(ctx, KZG_E_ARG, "alu: a row must index the concatenated rows of the input sets");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "alu: the row length must be a power of two");
+    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
+    if (lay.usable) {
+        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "alu: usable must be in [1, T - 1] (0: all T rows are read)");
+        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
+            return fail(ctx, KZG_E_ARG, "alu: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
+        if (!lay.tail_be32) return fail(ctx, KZG_E_ARG, "alu: tail_be32 must be given when usable > 0");
+        for (uint64_t j = 0; j < n_out * (T - lay.usable); j++)
+            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
+                return fail(ctx, KZG_E_ARG, "alu: tail scalars must be canonical (< r)");
+    } else if (lay.tail_be32) {
+        return fail(ctx, KZG_E_ARG, "alu: tail_be32 must be null in the plain layout (usable = 0)");
+    }
+    if (int rc2 = rows_reserve(ctx, "alu", pend, (size_t)n_out * T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    uint64_t stats[4 * KZG_ALU_MAX_UNITS];
+    rc = rows_alu_dev(ctx, H, i, it, n_entries, program, n_units, units, n_out, T, pend.buf.as<uint32_t>(), c48, stats,
+                      lay.usable ? &lay : nullptr);
+    if (rc) return rc;
+    memcpy(out_commitments48, c48, 48 * (size_t)n_out);
+    memcpy(out_counts, stats, 8 * (size_t)n_units);
+    memcpy(out_unknown, stats + n_units, 8 * (size_t)n_units);
+    memcpy(out_first, stats + 2 * n_units, 8 * (size_t)n_units);
+    memcpy(out_first_unknown, stats + 3 * n_units, 8 * (size_t)n_units);
+    *out_handle = rows_insert(ctx, pend, i, n_out, T);
+    return KZG_OK;
+}
+
 // kzg_rows_commit_expr: the lookups of an open (one handle list), the reservation of a commit of n_out rows -- none when every
 // expression is a check.  opts == NULL, or usable == 0: all T rows are evaluated.  Coefficients are checked here, on the host
 int rows_expr(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
@@ -2368,6 +2458,13 @@ int kzg_rows_commit_int(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* 
                         uint64_t* out_first, uint64_t* out_handle) {
     return rows_int(ctx, UINT32_MAX, n_input_handles, input_handles, n_ops, ops, opts, out_commitments48, out_counts, out_first,
                     out_handle);
+}
+int kzg_rows_commit_alu(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_entries,
+                        const kzg_alu_entry* program, uint32_t n_units, const kzg_alu_unit* units, const kzg_derive_opts* opts,
+                        uint8_t* out_commitments48, uint64_t* out_counts, uint64_t* out_first, uint64_t* out_unknown,
+                        uint64_t* out_first_unknown, uint64_t* out_handle) {
+    return rows_alu(ctx, UINT32_MAX, n_input_handles, input_handles, n_entries, program, n_units, units, opts,
+                    out_commitments48, out_counts, out_first, out_unknown, out_first_unknown, out_handle);
 }
 int kzg_rows_commit_expr(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
                          const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48, uint64_t* out_nonzero,

@@ -1003,6 +1003,105 @@ class HipEngine:
         return (RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]), [int(v) for v in cnt],
                 [None if int(v) == _native.KZG_INT_NONE else int(v) for v in first])
 
+    # ---- a set built from sets: the same arithmetic and its signed kinds, the kind chosen per row by an op-code column
+    _ALU_KINDS = {name: num for num, name in enumerate(
+        ("and", "or", "xor", "add", "sub", "mul", "divmod", "split", "ltu", "lt", "eq", "sll", "srl", "sra", "rotl", "rotr",
+         "mulhu", "mulh", "mulhsu", "div", "rem", "remu", "sext"), 1)}
+
+    @classmethod
+    def alu_program(cls, program, what: str = "commit_alu") -> List[tuple]:
+        """The kzg_alu_entry fields (kind, width, imm, flags, pad) of a program: a list of 1 .. 64 entries, the index the
+        op-code, each None (idle), (kind, w) or (kind, w, ("imm", value)) with kind one of "and" "or" "xor" "add" "sub" "mul"
+        "divmod" "split" "ltu" "lt" "eq" "sll" "srl" "sra" "rotl" "rotr" "mulhu" "mulh" "mulhsu" "div" "rem" "remu" "sext" and w
+        in [1, 64].  An immediate is below 2^w; split's and sext's at most w, sext's not 0.  Raises KzgError(KZG_E_ARG)."""
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: alu: {why}")   # noqa: E731
+        program = list(program) if isinstance(program, (list, tuple)) else None
+        if not program or len(program) > _native.KZG_ALU_MAX_PROGRAM:
+            raise bad(f"the program must be a list of 1 .. {_native.KZG_ALU_MAX_PROGRAM} entries (n_entries)")
+        is_u = lambda v, top: isinstance(v, int) and not isinstance(v, bool) and 0 <= v < top   # noqa: E731
+        recs = []
+        for en in program:
+            if en is None:
+                recs.append((_native.KZG_ALU_IDLE, 0, 0, 0, 0))
+                continue
+            if not isinstance(en, (list, tuple)) or len(en) not in (2, 3):
+                raise bad('an entry is None, (kind, w) or (kind, w, ("imm", value))')
+            name, w = en[:2]
+            if not isinstance(name, str) or name not in cls._ALU_KINDS:
+                raise bad(f"unknown kind {name!r} (one of {', '.join(cls._ALU_KINDS)})")
+            kind = cls._ALU_KINDS[name]
+            if not is_u(w, 65) or w == 0:
+                raise bad("the width must be an integer in [1, 64]")
+            if len(en) == 2:
+                recs.append((kind, w, 0, 0, 0))
+                continue
+            imm = en[2]
+            if not isinstance(imm, (list, tuple)) or len(imm) != 2 or imm[0] != "imm" or not is_u(imm[1], 1 << 64):
+                raise bad('an immediate is ("imm", value) with value an integer in [0, 2^64)')
+            v = imm[1]
+            if (v > w or (name == "sext" and v == 0)) if name in ("split", "sext") else v >> w:
+                raise bad("an immediate must be below 2^width (split, sext: at most width; sext: at least 1)")
+            recs.append((kind, w, v, _native.KZG_ALU_IMM, 0))
+        return recs
+
+    @classmethod
+    def alu_units(cls, units, recs, what: str = "commit_alu") -> List[tuple]:
+        """The kzg_alu_unit fields (op_row, a, b, count) of 1 .. 8 units (op_row, a, b) or (op_row, a, b, count), rows of the
+        concatenated input sets, count 1 or 2 (default 1); recs: the program's fields from alu_program -- count 2 needs an entry
+        whose kind has a second row.  Raises KzgError(KZG_E_ARG) with the cause."""
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: alu: {why}")   # noqa: E731
+        units = list(units) if isinstance(units, (list, tuple)) else None
+        if not units or len(units) > _native.KZG_ALU_MAX_UNITS:
+            raise bad(f"units must be a list of 1 .. {_native.KZG_ALU_MAX_UNITS} entries (n_units)")
+        is_u = lambda v, top: isinstance(v, int) and not isinstance(v, bool) and 0 <= v < top   # noqa: E731
+        two_rows = any(r[0] > _native.KZG_ALU_XOR for r in recs)
+        out = []
+        for un in units:
+            if not isinstance(un, (list, tuple)) or len(un) not in (3, 4):
+                raise bad("a unit is (op_row, a, b) or (op_row, a, b, count)")
+            count = un[3] if len(un) == 4 else 1
+            if not all(is_u(v, 1 << 32) for v in un[:3]):
+                raise bad("a row must be an integer in [0, 2^32)")
+            if not is_u(count, 3) or count == 0 or (count == 2 and not two_rows):
+                raise bad("count must be 1 or 2, and 1 where no entry's kind has a second row (and, or, xor)")
+            out.append((un[0], un[1], un[2], count))
+        if sum(u[3] for u in out) > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"n_out: the units give {sum(u[3] for u in out)} output rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+        return out
+
+    def commit_alu(self, input_sets: Sequence[object], program: Sequence, units: Sequence[tuple], usable: Optional[int] = None,
+                   tail: Sequence[bytes] = ()) -> Tuple["RowSet", dict]:
+        """kzg_rows_commit_alu over the concatenated rows of input_sets (RowSet objects or bare handles): the machine-word
+        arithmetic of commit_int with the kind chosen PER ROW.  program: see alu_program; units: see alu_units.  Cell t of a unit
+        takes c, the canonical integer of op_row[t]: c beyond the program is unknown (outputs 0, counted), program[c] None is idle
+        (outputs 0, nothing read or counted), otherwise the entry's kind acts on a[t] and b[t] (or the entry's immediate) reduced
+        to their low w bits.  The rows of the kinds commit_int lacks, row 0 then row 1, with s = b mod w: ltu / lt / eq: the bit,
+        (a - b) mod 2^w; sll: the low word, the bits shifted out; srl / sra: the shifted word, a mod 2^s; rotl / rotr: the
+        rotated word, the wrapped bits; mulhu / mulh / mulhsu: the high word, the low word; div: quotient, remainder (RISC-V);
+        rem: remainder, quotient; remu: remainder, quotient; sext: the low f bits sign-extended, bit f - 1.  Returns (the new
+        RowSet of all output rows, unit by unit; {"counts", "first", "unknown", "first_unknown"}, per unit the cells read with an
+        operand out of range and the cells with an unknown op-code, and the smallest such rows or None).  usable and tail: as
+        for commit_int."""
+        what = "commit_alu"
+        ni, hi = self._handle_array(input_sets, what)
+        recs = self.alu_program(program, what)
+        urecs = self.alu_units(units, recs, what)
+        n_out = sum(u[3] for u in urecs)
+        wi, T, lay = self._column_layout(what, input_sets, n_out, "n_out", "read", usable, tail)
+        opts = _native.DeriveOpts(*lay) if lay else None
+        prog = (_native.AluEntry * len(recs))(*[_native.AluEntry(*r) for r in recs])
+        arr = (_native.AluUnit * len(urecs))(*[_native.AluUnit(*u) for u in urecs])
+        c, h = ctypes.create_string_buffer(48 * n_out), ctypes.c_uint64(0)
+        nu = len(urecs)
+        cnt, first, unk, funk = [(ctypes.c_uint64 * nu)() for _ in range(4)]
+        self._chk(self._lib.kzg_rows_commit_alu(self._h, ni, hi, len(recs), prog, nu, arr,
+                                                ctypes.byref(opts) if opts is not None else None, c, cnt, first, unk, funk,
+                                                ctypes.byref(h)))
+        none = lambda vs: [None if int(v) == _native.KZG_ALU_NONE else int(v) for v in vs]   # noqa: E731
+        return (RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]),
+                {"counts": [int(v) for v in cnt], "first": none(first), "unknown": [int(v) for v in unk],
+                 "first_unknown": none(funk)})
+
     # ---- a set built from sets: columns that are plain arithmetic in resident columns, and gates checked row by row
     def commit_expr(self, input_sets: Sequence[object], exprs: Sequence[Sequence], usable: Optional[int] = None,
                     tail: Sequence[bytes] = ()) -> Tuple[Optional["RowSet"], List[int], List[Optional[int]]]:
