@@ -1035,6 +1035,7 @@ int kzg_rows_check_copies(kzg_ctx* ctx, uint32_t n_wire_handles, const uint64_t*
  * kzg_rows_commit_expr); widths above 64; three-operand ops (a b + c, funnel shifts); per-row selectors (an op-code column
  * choosing the kind per row: build every candidate and select with kzg_rows_commit_expr); a separate count of zero divisors.
  * (Both in ONE call, the signed kinds and a kind chosen per row by an op-code column: kzg_rows_commit_alu below.)
+ * (Widths above 64 as limbs, and a b + c mod m: kzg_rows_commit_wide below.)
  * SOUNDNESS: nothing here is a proof.  The rows are prover data; the argument is the caller's gates plus the range lookups of
  * the outputs (kzg_rows_commit_derived LIMBS -> kzg_rows_commit_multiplicities -> kzg_rows_commit_lookup_sum): a + b = s + carry M;
  * a - b = d - borrow M; a b = lo + hi M; a = q b + rem with rem < b shown through the borrow of a SUB (and the b = 0 case
@@ -1174,6 +1175,90 @@ int kzg_rows_commit_alu(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* 
                         const kzg_derive_opts* opts /* NULL: plain */, uint8_t* out_commitments48 /* n_out * 48 */,
                         uint64_t* out_counts /* n_units */, uint64_t* out_first /* n_units */, uint64_t* out_unknown /* n_units */,
                         uint64_t* out_first_unknown /* n_units */, uint64_t* out_handle);
+/* THE MULTI-LIMB INTEGER COLUMNS: a set built FROM sets, the witness columns of 256-bit, 384-bit and 512-bit arithmetic -- uint256
+ * mul / div, a b + c mod p over the base fields of secp256k1, bn254 and BLS12-381 -- which kzg_rows_commit_int and
+ * kzg_rows_commit_alu leave out (widths above 64, three operands).  The concatenated rows of the input_handles sets (as in
+ * kzg_rows_open) are the source columns.  A WIDE VALUE is L consecutive rows of them: limb l is row first + l, little-endian,
+ * the order in which kzg_rows_commit_derived's LIMBS writes its rows.  Cell t of a limb row is taken as its CANONICAL INTEGER in
+ * [0, r) and reduced to its low b bits; the value at row t is sum_l limb_l[t] 2^(b l).  1 <= b <= 64, 1 <= L <= 8, W = b L <=
+ * 512.  A limb cell at or above 2^b is OUT OF RANGE: it is reduced, never refused; a row t with such a limb in any operand is
+ * counted ONCE in out_counts[op], and out_first[op] is the smallest such row, or KZG_INT_NONE.  An immediate (imm_be64, m_be64)
+ * is a big-endian integer of 64 bytes and must be below 2^W.  An operand field holds the first row of the value, or
+ * KZG_WIDE_ABSENT.  The output rows of an op, in this order (count selects the first part or all):
+ *   KZG_WIDE_ADD    (count L or L + 1)  (a + b) mod 2^W as L limbs; the carry, 0 or 1
+ *   KZG_WIDE_SUB    (count L or L + 1)  (a - b) mod 2^W as L limbs; the borrow, 1 where a < b
+ *   KZG_WIDE_MUL    (count L or 2 L)    the low L limbs of a b; the high L limbs
+ *   KZG_WIDE_DIVMOD (count L or 2 L)    floor(a / b) as L limbs; a mod b as L limbs.  Where b = 0: 2^W - 1 and a, the convention
+ *                                       of kzg_rows_commit_int, neither counted nor an error
+ *   KZG_WIDE_MULMOD (count L or 2 L)    with t = a b + d and the modulus m = m_be64, 1 <= m < 2^W: r = t mod m as L limbs; q =
+ *                                       floor(t / m) as L limbs.  b is a wide row, the immediate imm_be64 (KZG_WIDE_IMM_B), or
+ *                                       absent (then 1).  d = 0 without an operand c, d = c with one.  With KZG_WIDE_NEG_C: d = m -
+ *                                       (c mod m), which is m where c = 0 or there is no c, and a row with c > m is counted out of
+ *                                       range: the caller's gate is a b + m - c = q m + r, and q is never negative.  A row with q
+ *                                       >= 2^W (operands not reduced against a small m) writes the low W bits of q and is counted
+ *                                       in out_qover[op], the smallest such row in out_first_qover[op] (or KZG_INT_NONE)
+ *   KZG_WIDE_CARRY  (count 2 L - 1)     the carry columns of the limb identity of a MULMOD whose q and r are resident: operands
+ *                                       a, b, c as for MULMOD, q, r (wide rows) and m; the limbs of m and d come from the integers
+ *                                       m and d cut into b-bit limbs.  For k = 0 .. 2 L - 1:
+ *                                         s_k = sum_{i + j = k} (A_i B_j - Q_i M_j) + [k < L] (D_k - R_k) + carry_(k-1),
+ *                                         carry_(-1) = 0, carry_k = floor(s_k / 2^b), rounding towards minus infinity.
+ *                                       The rows are carry_0 .. carry_(2L-2); a negative carry x is the cell r - |x|, the
+ *                                       convention of the typed i64 columns.  b <= 56, so every carry fits a signed 64-bit word.
+ *                                       A row where some s_k is no multiple of 2^b, or carry_(2L-1) != 0, is INEXACT: counted in
+ *                                       out_qover[op] / out_first_qover[op]; its rows are still written
+ * The other kinds take b as a row or an immediate and no c, q, r or m (all zero bytes).  A row may serve several operands of one
+ * op.  1 <= n_ops <= KZG_WIDE_MAX_OPS and n_out = the sum of the counts, 1 <= n_out <= KZG_MAX_BATCH_OPEN.  All outputs of a call
+ * form ONE new set of the same worker and length, in the order of ops: out_commitments48[c] equals kzg_rows_commit(i, n_out,
+ * these rows, T, 1, ..)[c] byte for byte, and *out_handle opens, evaluates, combines, releases, goes stale and counts against
+ * KZG_MAX_ROW_SETS (KZG_E_BUSY; KZG_E_NOMEM on a failed allocation, the lane's workspace included: one T-element vector per
+ * DISTINCT source row named and one per output row) like any other.  ONE kernel launch computes every op of the call; the four
+ * statistics come back in the copy behind the MSM; nothing row-sized crosses the host link in either direction.
+ * opts (NULL: plain layout) is kzg_derive_opts, exactly as kzg_rows_commit_derived reads it: source rows t >= usable are never
+ * read or counted, output row usable + s of output column c takes tail_be32[c * (T - usable) + s], there is NO closing row.
+ * Handle lists follow kzg_rows_open.  KZG_E_ARG with a message that begins "wide:" and names the cause: n_ops outside [1,
+ * KZG_WIDE_MAX_OPS]; n_out outside [1, KZG_MAX_BATCH_OPEN]; an unknown kind; an unknown flag; b outside [1, 64] (CARRY: [1, 56]),
+ * L outside [1, 8], W above 512; a count outside the kind's set; an operand whose L rows reach beyond the concatenation; an
+ * operand, immediate, modulus or flag that the kind does not take, or a missing one that it needs; an immediate or a modulus at
+ * or above 2^W; m = 0; the usable and tail refusals of kzg_rows_commit_derived; the handle refusals of kzg_rows_open.  The
+ * source sets are only read; a release or an SRS load racing the call follows the rules of kzg_rows_open.  Thread-safe like
+ * every call; after any error the context keeps serving.
+ * OUT OF SCOPE: L > 8 (regroup 8-bit or 16-bit limbs into wider ones with kzg_rows_commit_expr, or cut the outputs again with
+ * kzg_rows_commit_derived); a per-row modulus; modular inversion and division; signed operands; an op-code column; operands
+ * on DISTINCT rows beyond the KZG_MAX_BATCH_OPEN concatenated rows a call reads: the limit counts rows, not L, and a row may
+ * serve several operands, so a CARRY runs at any L <= 8, but with a, q and r on three distinct runs of rows it has L <= 5 (L <=
+ * 4 with b as a fourth).  A 256-bit or 384-bit carry chain over distinct a, q, r is therefore not to be had in one call.
+ * SOUNDNESS: nothing here is a proof.  The rows are prover data; the argument is the caller's gates over the limbs plus the
+ * range lookups of every output limb and carry: the limb identity s_k = carry_k 2^b for k < 2 L (kzg_rows_commit_expr over the
+ * operand, quotient, remainder and carry columns), r < m through a SUB and its borrow, and for a modular statement W large
+ * enough that the integer identity cannot wrap in the field.  Every challenge is drawn AFTER these commitments are fixed.  Zero
+ * counts are a convenience for the prover and convince no verifier.  The library derives no challenge and draws no randomness:
+ * the tail must be fresh per proof. */
+#define KZG_WIDE_ADD    1
+#define KZG_WIDE_SUB    2
+#define KZG_WIDE_MUL    3
+#define KZG_WIDE_DIVMOD 4
+#define KZG_WIDE_MULMOD 5
+#define KZG_WIDE_CARRY  6
+#define KZG_WIDE_IMM_B  1u                  /* flags: operand b is imm_be64 */
+#define KZG_WIDE_NEG_C  2u                  /* flags (MULMOD, CARRY): d = m - (c mod m) */
+#define KZG_WIDE_ABSENT 0xffffffffu         /* an operand field without a row */
+#define KZG_WIDE_MAX_OPS 8
+#define KZG_WIDE_MAX_LIMBS 8
+typedef struct kzg_wide_op {
+    uint32_t kind;          /* KZG_WIDE_* */
+    uint32_t bits;          /* b in [1, 64]; CARRY: [1, 56] */
+    uint32_t limbs;         /* L in [1, 8], b L <= 512 */
+    uint32_t count;         /* output rows: see the kinds */
+    uint32_t flags;         /* 0, KZG_WIDE_IMM_B, KZG_WIDE_NEG_C or both */
+    uint32_t a, b, c, q, r; /* the first row of each operand in the concatenated rows of input_handles, or KZG_WIDE_ABSENT */
+    uint8_t imm_be64[64];   /* operand b with KZG_WIDE_IMM_B: below 2^W; all zero without */
+    uint8_t m_be64[64];     /* the modulus of MULMOD and CARRY: in [1, 2^W); all zero on the other kinds */
+} kzg_wide_op;
+int kzg_rows_commit_wide(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
+                         const kzg_wide_op* ops, const kzg_derive_opts* opts /* NULL: plain */,
+                         uint8_t* out_commitments48 /* n_out * 48 */, uint64_t* out_counts /* n_ops */,
+                         uint64_t* out_first /* n_ops */, uint64_t* out_qover /* n_ops */, uint64_t* out_first_qover /* n_ops */,
+                         uint64_t* out_handle);
 /* THE QUOTIENT WITH LOOKUP SELECTORS: kzg_rows_commit_quotient_zk and kzg_rows_quotient_part for lookups that are enabled on
  * some rows only.  selectors->selector_rows holds L = lookup->n_lookups entries, each a row index into the call's concatenated
  * rows (the caller's fixed column q_l, the row that kzg_rows_commit_multiplicities_sel / _lookup_sum_sel read) or
@@ -1558,6 +1643,11 @@ int kzg_multi_rows_commit_alu(kzg_multi* mh, uint32_t i, uint32_t n_input_handle
                               uint32_t n_entries, const kzg_alu_entry* program, uint32_t n_units, const kzg_alu_unit* units,
                               const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_counts, uint64_t* out_first,
                               uint64_t* out_unknown, uint64_t* out_first_unknown, uint64_t* out_handle);
+/* kzg_rows_commit_wide on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_wide(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
+                               const kzg_wide_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48,
+                               uint64_t* out_counts, uint64_t* out_first, uint64_t* out_qover, uint64_t* out_first_qover,
+                               uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

@@ -37,6 +37,11 @@ KZG_ALU_IDLE = 0
 KZG_ALU_IMM = 1
 KZG_ALU_NONE = 0xffffffffffffffff
 KZG_ALU_MAX_PROGRAM, KZG_ALU_MAX_UNITS = 64, 8
+# kzg_rows_commit_wide: kzg_wide_op.kind, the flags, an operand field without a row, the limits
+KZG_WIDE_ADD, KZG_WIDE_SUB, KZG_WIDE_MUL, KZG_WIDE_DIVMOD, KZG_WIDE_MULMOD, KZG_WIDE_CARRY = range(1, 7)
+KZG_WIDE_IMM_B, KZG_WIDE_NEG_C = 1, 2
+KZG_WIDE_ABSENT = 0xffffffff
+KZG_WIDE_MAX_OPS, KZG_WIDE_MAX_LIMBS = 8, 8
 KZG_MAX_EXPR_FACTORS = 8   # kzg_rows_commit_expr: factors of one term
 KZG_EXPR_CHECK = 1   # kzg_expr.flags: evaluate and count only
 KZG_EXPR_NONE = 0xffffffffffffffff   # out_first: no non-zero cell
@@ -129,6 +134,12 @@ class AluUnit(ctypes.Structure):
     _fields_ = [("op_row", _U32), ("a", _U32), ("b", _U32), ("count", _U32)]
 
 
+class WideOp(ctypes.Structure):
+    """kzg_wide_op"""
+    _fields_ = [("kind", _U32), ("bits", _U32), ("limbs", _U32), ("count", _U32), ("flags", _U32), ("a", _U32), ("b", _U32),
+                ("c", _U32), ("q", _U32), ("r", _U32), ("imm_be64", ctypes.c_uint8 * 64), ("m_be64", ctypes.c_uint8 * 64)]
+
+
 class Col(ctypes.Structure):
     """kzg_col"""
     _fields_ = [("data", ctypes.c_void_p), ("count", ctypes.c_uint64), ("kind", ctypes.c_uint32), ("fill_be32", ctypes.c_char_p)]
@@ -210,6 +221,9 @@ SYMBOLS = {
     "kzg_rows_commit_alu": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(AluEntry), _U32, ctypes.POINTER(AluUnit),
                                  ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64),
                                  ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_wide": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(WideOp), ctypes.POINTER(DeriveOpts), _B,
+                                  ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64),
+                                  ctypes.POINTER(_U64)]),
     "kzg_rows_commit_derived": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp), ctypes.POINTER(DeriveOpts), _B,
                                      ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_expr": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,
@@ -334,6 +348,9 @@ SYMBOLS = {
     "kzg_multi_rows_commit_alu": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(AluEntry), _U32,
                                        ctypes.POINTER(AluUnit), ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64),
                                        ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_wide": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(WideOp),
+                                        ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64),
+                                        ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_derived": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp),
                                            ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_expr": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,

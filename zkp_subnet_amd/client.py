@@ -1015,6 +1015,48 @@ class Client:
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
                 "counts": st["counts"], "first": st["first"], "unknown": st["unknown"], "first_unknown": st["first_unknown"]}
 
+    # ---- multi-limb integers: uint256 arithmetic and a b + c mod p over runs of limb rows, with the carries of the limb identity
+    @_guard
+    def worker_commit_wide(self, input_handles: Sequence[int], ops: Sequence[dict], usable: Optional[int] = None,
+                           tail: Sequence[str] = ()):
+        """Extension: multi-limb integer columns of the rows of the input_handles sets, computed and committed on the device as
+        one new set.  A wide value is L consecutive rows, limb l in row first + l (little-endian), each cell reduced to its low
+        b bits; 1 <= b <= 64, 1 <= L <= 8, b L <= 512.  ops: 1 to 8 objects {"kind", "bits", "limbs", "a", "b", "c", "q", "r",
+        "m", "neg_c", "count"}: kind one of "add" "sub" "mul" "divmod" "mulmod" "carry"; a, c, q, r first rows (or null); b a
+        first row, ["imm", value] or null; m the modulus; integers above 2^53 may be sent as decimal or 0x strings; count
+        defaults to L (carry: 2 L - 1).  The rows of an op: add / sub: L limbs, then the carry / borrow; mul: low L limbs, high
+        L limbs; divmod: quotient, remainder (2^W - 1 and a where b = 0); mulmod: r = (a b + d) mod m, then q, with d = c (or 0),
+        or m - (c mod m) with neg_c; carry: the 2 L - 1 carries of the limb identity of that mulmod (b <= 56), a negative one
+        as r_field - |x|.  usable and tail: as for worker_commit_int.  Returns the handle, the commitments, and per op
+        `counts` / `first` (rows with a limb at or above 2^b) and `qover` / `first_qover` (mulmod: q at or above 2^W; carry:
+        an inexact row).  Nothing here is a proof: the rows are prover data."""
+        what = "worker_commit_wide"
+        hs = _handles(input_handles)
+        try:
+            recs = []
+            for op in ops:
+                if not isinstance(op, dict):
+                    raise ValueError(f"an op is an object: {op!r}")
+                rec = dict(op)
+                if isinstance(rec.get("b"), (list, tuple)):
+                    rec["b"] = tuple(rec["b"])
+                recs.append(rec)
+        except (TypeError, ValueError, IndexError, KeyError) as e:
+            raise codec.CodecError(f"{what}: ops must be a list of objects: {e!r}") from e
+        if not recs:
+            raise codec.CodecError(f"{what}: ops must not be empty")
+        if usable is None:
+            if tail:
+                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
+            tb = []
+        else:
+            usable, tb = self._blind(what, usable, tail)
+            if usable == 0:
+                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        rs, st = self.engine.commit_wide(hs, recs, usable, tb)
+        return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
+                "counts": st["counts"], "first": st["first"], "qover": st["qover"], "first_qover": st["first_qover"]}
+
     @staticmethod
     def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: Sequence[int], n_groups: int, width: int,
                                theta: str, gamma: str, coeff: str, active_row: Optional[int] = None,

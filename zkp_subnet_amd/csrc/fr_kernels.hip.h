@@ -407,6 +407,38 @@ static_assert(sizeof(AluEnt) == 16 && sizeof(AluTab) + 64 <= 4096, "the program 
 // [2 n_units + u] <- min(., the smallest out-of-range row), [3 n_units + u] <- min(., the smallest unknown row).  Sources are
 // only read and may coincide; out must not overlap a source.  Widths, immediates and kinds: the caller's checks
 void launch_alu(hipStream_t s, const AluTab& tab, uint32_t n_prog, uint32_t n_units, uint64_t T, uint64_t n, uint64_t* stats);
+// ---- the multi-limb integer columns of kzg_rows_commit_wide (fr_wide.hip).  A wide operand is `limbs` vectors of T elements
+// among the source vectors at src: limb l of operand w is vector slot[w][l] (src + slot T 8 words).  An op reads its operands
+// at rows t < n and writes `count` vectors of T elements at out, side by side, canonical Montgomery.  kind: a KZG_WIDE_* kind;
+// flags: KZG_WIDE_NEG_C and the three bits below; imm: operand b where it is no row (absent: 1), m: the modulus, both as 16
+// little-endian 32-bit words
+#define WIDE_MAX_OPS 8
+#define WIDE_MAX_LIMBS 8
+#define WIDE_A 0
+#define WIDE_B 1
+#define WIDE_C 2
+#define WIDE_Q 3
+#define WIDE_R 4
+#define WIDE_F_ROW_B 0x100u   // operand b is a run of rows
+#define WIDE_F_ROW_C 0x200u   // there is an operand c
+#define WIDE_F_B_IS_A 0x400u  // every limb of b is the vector of that limb of a
+struct WideOp {
+    uint32_t* out;
+    uint32_t kind, bits, limbs, count, flags, pad;
+    uint8_t slot[5][WIDE_MAX_LIMBS];
+    uint32_t imm[16], m[16];
+};
+struct WideTab {
+    WideOp op[WIDE_MAX_OPS];
+    const uint32_t* src;
+};
+static_assert(sizeof(WideTab) + 64 <= 4096 && POLY_MAX_ROWS <= 256, "the op table rides as a kernel argument; slots ride in bytes");
+// ONE launch for the n_ops <= WIDE_MAX_OPS ops of tab, instantiated on the widest b limbs of the call.  stats: four runs of
+// n_ops words: [o] += the rows t < n of op o with a limb at or above 2^b (or c > m under KZG_WIDE_NEG_C), [n_ops + o] += the rows
+// whose quotient does not fit W bits (mulmod) or whose limb identity is inexact (carry), [2 n_ops + o] <- min(., the smallest
+// row of the first kind), [3 n_ops + o] <- min(., of the second).  Sources are only read and may coincide; out must not overlap
+// a source.  1 <= b <= 64 (carry: 56), 1 <= L <= 8, b L <= 512, immediates below 2^(b L), m != 0: the caller's checks
+void launch_wide(hipStream_t s, const WideTab& tab, uint32_t n_ops, uint64_t T, uint64_t n, uint64_t* stats);
 // ---- the expression columns of kzg_rows_commit_expr (fr_expr.hip): v[t] = sum_u c_u prod_f src.r[row[u][f]][(t + rot[u][f]) mod T]
 // for t < n <= T over evaluation vectors of T canonical Montgomery elements (T a power of two, at most 2^32)
 #define EXPR_MAX_TERMS 16

@@ -51,3 +51,18 @@ KZG_DEV void int_store(uint32_t* p, uint64_t x) {
     fr9_canon(v, v);
     fr9_store(p, v);
 }
+// int_store with a sign: the cell of x, or where neg (then x is in [1, 2^64)) of -x, which is r - x: the convention of the typed
+// i64 columns (fr_wide.hip's carries).  One encoder; the negation acts on the canonical element before the store
+KZG_DEV void int_store_signed(uint32_t* p, uint64_t x, bool neg) {
+    fr9_t v;
+    fr9_mont_from_u64(v, x);
+    fr9_canon(v, v);
+    int32_t br = 0;   // (the residue of x is not zero: r - v is canonical)
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        const int32_t d = (int32_t)fr9_r(i) - (int32_t)v.l[i] + br;
+        br = d >> 29;
+        v.l[i] = neg ? ((i < 8) ? ((uint32_t)d & FR9_MASK) : (uint32_t)d) : v.l[i];
+    }
+    fr9_store(p, v);
+}

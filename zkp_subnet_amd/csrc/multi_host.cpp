@@ -522,6 +522,15 @@ int kzg_multi_rows_commit_alu(kzg_multi* mh, uint32_t i, uint32_t n_input_handle
                                   out_commitments48, out_counts, out_first, out_unknown, out_first_unknown, out_handle);
     });
 }
+int kzg_multi_rows_commit_wide(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
+                               const kzg_wide_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48,
+                               uint64_t* out_counts, uint64_t* out_first, uint64_t* out_qover, uint64_t* out_first_qover,
+                               uint64_t* out_handle) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_wide(c, s, n_input_handles, input_handles, n_ops, ops, opts, out_commitments48, out_counts,
+                                   out_first, out_qover, out_first_qover, out_handle);
+    });
+}
 int kzg_multi_rows_commit_expr(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                uint32_t n_exprs, const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48,
                                uint64_t* out_nonzero, uint64_t* out_first, uint64_t* out_handle) {

@@ -1439,6 +1439,98 @@ int rows_alu_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, ui
     return KZG_OK;
 }
 
+// The multi-limb integer columns (kzg_rows_commit_wide): the frame of rows_int_dev.  Each DISTINCT source row (by device
+// pointer) among the limb rows that some operand names is transformed forward once; an operand is the list of its limbs' slots.
+//   step                      launches                         per call
+//   forward transforms        launch_fr_ntt                    one per distinct source row named
+//   every op                  launch_wide (k_fr_wide<N>)       ONE, grid y = op
+//   tail                      launch_sort_tail                 one per output row, with `usable` only
+//   inverse transform         row_to_coeffs                    one per output row, straight into dst
+//   commit                    multi_msms_finish                ONE pass of n_out scalar sets
+// The four u64 statistics of every op lie in the record's evaluation slots where rows_alu_dev keeps its four and come back in
+// the copy behind the MSM.  Workspace: distinct sources + n_out vectors of T.
+static void wide_words(uint32_t w[16], const uint8_t be64[64]) {
+    for (int i = 0; i < 16; i++)
+        w[i] = ((uint32_t)be64[60 - 4 * i] << 24) | ((uint32_t)be64[61 - 4 * i] << 16) | ((uint32_t)be64[62 - 4 * i] << 8) |
+               be64[63 - 4 * i];
+}
+int rows_wide_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_ops, const kzg_wide_op* ops,
+                  uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_stats, const Blind* lay) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const int lg = ilog2_exact(T);
+    uint32_t* tw = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
+    const uint64_t vw = T * 8;                        // one vector, in words
+    const uint64_t n = lay ? lay->usable : T;         // the rows that are read
+    constexpr uint32_t CNT_OFF = 64;                  // the statistics in the record: counts, qover, first, first qover
+    static_assert(CNT_OFF + 32 * KZG_WIDE_MAX_OPS <= MR_PAIRS * 32 && KZG_WIDE_MAX_OPS == WIDE_MAX_OPS &&
+                      KZG_WIDE_MAX_LIMBS == WIDE_MAX_LIMBS,
+                  "the four statistics of every op fit the record's evaluation slots");
+    const uint32_t* distinct[POLY_MAX_ROWS];
+    uint32_t nd = 0;
+    auto slot_of = [&](const uint32_t* p) {
+        uint32_t d = 0;
+        while (d < nd && distinct[d] != p) d++;
+        if (d == nd) distinct[nd++] = p;
+        return d;
+    };
+    WideTab tab;
+    memset(&tab, 0, sizeof(tab));
+    for (uint32_t o = 0; o < n_ops; o++) {
+        const kzg_wide_op& in = ops[o];
+        WideOp& op = tab.op[o];
+        const uint32_t first[5] = {in.a, in.b, in.c, in.q, in.r};
+        for (int w = 0; w < 5; w++)
+            for (uint32_t l = 0; l < in.limbs && first[w] != KZG_WIDE_ABSENT; l++)
+                op.slot[w][l] = (uint8_t)slot_of(inputs.r[first[w] + l]);
+        op.kind = in.kind;
+        op.bits = in.bits;
+        op.limbs = in.limbs;
+        op.count = in.count;
+        op.flags = in.flags & KZG_WIDE_NEG_C;
+        if (in.b != KZG_WIDE_ABSENT) {
+            op.flags |= WIDE_F_ROW_B;
+            if (memcmp(op.slot[WIDE_A], op.slot[WIDE_B], in.limbs) == 0) op.flags |= WIDE_F_B_IS_A;
+        }
+        if (in.c != KZG_WIDE_ABSENT) op.flags |= WIDE_F_ROW_C;
+        wide_words(op.imm, in.imm_be64);
+        if (in.b == KZG_WIDE_ABSENT && !(in.flags & KZG_WIDE_IMM_B)) op.imm[0] = 1;   // no b: a times 1
+        wide_words(op.m, in.m_be64);
+    }
+    HIPCHK(ctx, A.qext.ensure(((size_t)nd + n_out) * T * 32));
+    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + nd * vw, *mid = A.ntt_mid.as<uint32_t>();
+    uint8_t* rec = A.brec.as<uint8_t>();
+    uint64_t* st = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF);
+    for (uint32_t d = 0; d < nd; d++) {
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, distinct[d], src + d * vw, lg, tw, nullptr, mid);
+    }
+    HIPCHK(ctx, hipMemsetAsync(st, 0, 16 * (size_t)n_ops, A.stream));
+    HIPCHK(ctx, hipMemsetAsync(st + 2 * n_ops, 0xff, 16 * (size_t)n_ops, A.stream));   // KZG_INT_NONE
+    tab.src = src;
+    for (uint32_t o = 0, c = 0; o < n_ops; c += ops[o++].count) tab.op[o].out = outv + c * vw;
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_wide(A.stream, tab, n_ops, T, n, st);
+    }
+    for (uint32_t c = 0; c < n_out; c++) {
+        if (lay) {
+            Span sp(ctx, A, KZG_T_POLY);
+            launch_sort_tail(A.stream, outv + c * vw, T, n, lay->tail_be32 + 32 * (size_t)c * (T - n), A.flags());
+        }
+        const uint32_t* cf;
+        if (int rc = row_to_coeffs(ctx, A, outv + c * vw, T, 1, &cf, dst + c * vw)) return rc;
+    }
+    HIPCHK(ctx, hipGetLastError());
+    uint8_t ev[CNT_OFF + 32 * KZG_WIDE_MAX_OPS + 32];
+    const uint32_t npairs = (CNT_OFF + 32 * n_ops + 31) / 32;
+    if (int rc = multi_msms_finish(ctx, H, i, T, dst, n_out, 0, npairs, out_c48, ev, nullptr)) return rc;
+    memcpy(out_stats, ev + CNT_OFF, 32 * (size_t)n_ops);
+    return KZG_OK;
+}
+
 // The expression columns (kzg_rows_commit_expr): a set built FROM sets, every output row plain arithmetic in source rows.
 // Each DISTINCT source row (by device pointer: two indices of a repeated handle name one row) that some term names is
 // transformed forward once into its own vector of the lane's quotient workspace; a row no term names is not transformed.

@@ -72,6 +72,10 @@ int rows_alu(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const ui
              const kzg_alu_entry* program, uint32_t n_units, const kzg_alu_unit* units, const kzg_derive_opts* opts,
              uint8_t* out_commitments48, uint64_t* out_counts, uint64_t* out_first, uint64_t* out_unknown,
              uint64_t* out_first_unknown, uint64_t* out_handle);
+// opts: as for rows_derived
+int rows_wide(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
+              const kzg_wide_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_counts,
+              uint64_t* out_first, uint64_t* out_qover, uint64_t* out_first_qover, uint64_t* out_handle);
 // opts: the usable layout and its tail as the public call takes them (null: all T rows are evaluated)
 int rows_expr(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
               const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48, uint64_t* out_nonzero,

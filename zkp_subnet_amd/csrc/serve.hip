@@ -1437,6 +1437,117 @@ int rows_alu(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const ui
     return KZG_OK;
 }
 
+// kzg_rows_commit_wide: the frame of rows_int.  Kinds, b, L, counts, operands, immediates and moduli are checked here, on the
+// host, before a lane is taken
+static bool wide_be64_zero(const uint8_t* v) {
+    for (int j = 0; j < 64; j++)
+        if (v[j]) return false;
+    return true;
+}
+static bool wide_be64_fits(const uint8_t* v, uint32_t W) {   // below 2^W, W <= 512
+    for (uint32_t k = W; k < 512; k++)
+        if (v[63 - k / 8] >> (k % 8) & 1) return false;
+    return true;
+}
+int rows_wide(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
+              const kzg_wide_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_counts,
+              uint64_t* out_first, uint64_t* out_qover, uint64_t* out_first_qover, uint64_t* out_handle) {
+    if (!ctx || !input_handles || !out_commitments48 || !out_counts || !out_first || !out_qover || !out_first_qover || !out_handle)
+        return KZG_E_ARG;
+    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "wide: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (n_ops == 0 || n_ops > KZG_WIDE_MAX_OPS || !ops) return fail(ctx, KZG_E_ARG, "wide: n_ops must be in [1, KZG_WIDE_MAX_OPS]");
+    uint32_t n_out = 0;
+    for (uint32_t o = 0; o < n_ops; o++) {
+        const kzg_wide_op& op = ops[o];
+        const uint32_t L = op.limbs, W = op.bits * L;
+        const bool modular = op.kind == KZG_WIDE_MULMOD || op.kind == KZG_WIDE_CARRY;
+        if (op.kind < KZG_WIDE_ADD || op.kind > KZG_WIDE_CARRY)
+            return fail(ctx, KZG_E_ARG, "wide: unknown kind (KZG_WIDE_ADD .. KZG_WIDE_CARRY)");
+        if (op.flags & ~(KZG_WIDE_IMM_B | KZG_WIDE_NEG_C))
+            return fail(ctx, KZG_E_ARG, "wide: flags must be a combination of KZG_WIDE_IMM_B and KZG_WIDE_NEG_C");
+        if (op.bits == 0 || op.bits > 64) return fail(ctx, KZG_E_ARG, "wide: the limb width b must be in [1, 64]");
+        if (L == 0 || L > KZG_WIDE_MAX_LIMBS) return fail(ctx, KZG_E_ARG, "wide: the number of limbs L must be in [1, 8]");
+        if (W > 512) return fail(ctx, KZG_E_ARG, "wide: the width W = b L must be at most 512");
+        if (op.kind == KZG_WIDE_CARRY && op.bits > 56)
+            return fail(ctx, KZG_E_ARG, "wide: the limb width b of a CARRY must be at most 56");
+        const bool count_ok = op.kind == KZG_WIDE_CARRY ? op.count == 2 * L - 1
+                              : op.kind <= KZG_WIDE_SUB ? op.count == L || op.count == L + 1
+                                                        : op.count == L || op.count == 2 * L;
+        if (!count_ok)
+            return fail(ctx, KZG_E_ARG, "wide: count must be L or L + 1 on ADD and SUB, L or 2 L on MUL, DIVMOD and MULMOD, 2 L - 1 on CARRY");
+        if (op.a == KZG_WIDE_ABSENT) return fail(ctx, KZG_E_ARG, "wide: operand a must be given");
+        if (op.flags & KZG_WIDE_IMM_B) {
+            if (op.b != KZG_WIDE_ABSENT) return fail(ctx, KZG_E_ARG, "wide: operand b must be KZG_WIDE_ABSENT beside KZG_WIDE_IMM_B");
+            if (!wide_be64_fits(op.imm_be64, W)) return fail(ctx, KZG_E_ARG, "wide: the immediate must be below 2^W");
+        } else {
+            if (!wide_be64_zero(op.imm_be64)) return fail(ctx, KZG_E_ARG, "wide: the immediate must be 0 without KZG_WIDE_IMM_B");
+            if (op.b == KZG_WIDE_ABSENT && !modular)
+                return fail(ctx, KZG_E_ARG, "wide: operand b must be given (a row or an immediate) on ADD, SUB, MUL and DIVMOD");
+        }
+        if (!modular) {
+            if (op.c != KZG_WIDE_ABSENT || (op.flags & KZG_WIDE_NEG_C) || !wide_be64_zero(op.m_be64))
+                return fail(ctx, KZG_E_ARG, "wide: an operand the kind does not take: c, KZG_WIDE_NEG_C and m belong to MULMOD and CARRY");
+        } else {
+            if (wide_be64_zero(op.m_be64)) return fail(ctx, KZG_E_ARG, "wide: the modulus m must not be 0");
+            if (!wide_be64_fits(op.m_be64, W)) return fail(ctx, KZG_E_ARG, "wide: the modulus m must be below 2^W");
+        }
+        if (op.kind == KZG_WIDE_CARRY) {
+            if (op.q == KZG_WIDE_ABSENT || op.r == KZG_WIDE_ABSENT)
+                return fail(ctx, KZG_E_ARG, "wide: operands q and r must be given on CARRY");
+        } else if (op.q != KZG_WIDE_ABSENT || op.r != KZG_WIDE_ABSENT) {
+            return fail(ctx, KZG_E_ARG, "wide: an operand the kind does not take: q and r belong to CARRY");
+        }
+        n_out += op.count;
+    }
+    if (n_out > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "wide: n_out, the sum of the counts, must be in [1, KZG_MAX_BATCH_OPEN]");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs irefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab it;
+    uint32_t ki = 0, i = 0;
+    uint64_t T = 0;
+    if (int rc = rows_lookup(ctx, "wide", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    for (uint32_t o = 0; o < n_ops; o++)
+        for (uint32_t first : {ops[o].a, ops[o].b, ops[o].c, ops[o].q, ops[o].r})
+            if (first != KZG_WIDE_ABSENT && (first >= ki || ops[o].limbs > ki - first))
+                return fail(ctx, KZG_E_ARG, "wide: the L rows of an operand must lie inside the concatenated rows of the input sets");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "wide: the row length must be a power of two");
+    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
+    if (lay.usable) {
+        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "wide: usable must be in [1, T - 1] (0: all T rows are read)");
+        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
+            return fail(ctx, KZG_E_ARG, "wide: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
+        if (!lay.tail_be32) return fail(ctx, KZG_E_ARG, "wide: tail_be32 must be given when usable > 0");
+        for (uint64_t j = 0; j < n_out * (T - lay.usable); j++)
+            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
+                return fail(ctx, KZG_E_ARG, "wide: tail scalars must be canonical (< r)");
+    } else if (lay.tail_be32) {
+        return fail(ctx, KZG_E_ARG, "wide: tail_be32 must be null in the plain layout (usable = 0)");
+    }
+    if (int rc2 = rows_reserve(ctx, "wide", pend, (size_t)n_out * T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    uint64_t stats[4 * KZG_WIDE_MAX_OPS];
+    rc = rows_wide_dev(ctx, H, i, it, n_ops, ops, n_out, T, pend.buf.as<uint32_t>(), c48, stats, lay.usable ? &lay : nullptr);
+    if (rc) return rc;
+    memcpy(out_commitments48, c48, 48 * (size_t)n_out);
+    memcpy(out_counts, stats, 8 * (size_t)n_ops);
+    memcpy(out_qover, stats + n_ops, 8 * (size_t)n_ops);
+    memcpy(out_first, stats + 2 * n_ops, 8 * (size_t)n_ops);
+    memcpy(out_first_qover, stats + 3 * n_ops, 8 * (size_t)n_ops);
+    *out_handle = rows_insert(ctx, pend, i, n_out, T);
+    return KZG_OK;
+}
+
 // kzg_rows_commit_expr: the lookups of an open (one handle list), the reservation of a commit of n_out rows -- none when every
 // expression is a check.  opts == NULL, or usable == 0: all T rows are evaluated.  Coefficients are checked here, on the host
 int rows_expr(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
@@ -2465,6 +2576,12 @@ int kzg_rows_commit_alu(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* 
                         uint64_t* out_first_unknown, uint64_t* out_handle) {
     return rows_alu(ctx, UINT32_MAX, n_input_handles, input_handles, n_entries, program, n_units, units, opts,
                     out_commitments48, out_counts, out_first, out_unknown, out_first_unknown, out_handle);
+}
+int kzg_rows_commit_wide(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_ops,
+                         const kzg_wide_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_counts,
+                         uint64_t* out_first, uint64_t* out_qover, uint64_t* out_first_qover, uint64_t* out_handle) {
+    return rows_wide(ctx, UINT32_MAX, n_input_handles, input_handles, n_ops, ops, opts, out_commitments48, out_counts, out_first,
+                     out_qover, out_first_qover, out_handle);
 }
 int kzg_rows_commit_expr(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
                          const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48, uint64_t* out_nonzero,

@@ -1102,6 +1102,144 @@ class HipEngine:
                 {"counts": [int(v) for v in cnt], "first": none(first), "unknown": [int(v) for v in unk],
                  "first_unknown": none(funk)})
 
+    # ---- a set built from sets: multi-limb integers (256, 384, 512 bits) and a b + c mod m over runs of limb rows
+    _WIDE_KINDS = {"add": _native.KZG_WIDE_ADD, "sub": _native.KZG_WIDE_SUB, "mul": _native.KZG_WIDE_MUL,
+                   "divmod": _native.KZG_WIDE_DIVMOD, "mulmod": _native.KZG_WIDE_MULMOD, "carry": _native.KZG_WIDE_CARRY}
+    _WIDE_KEYS = ("kind", "bits", "limbs", "a", "b", "c", "q", "r", "m", "neg_c", "count")
+
+    @classmethod
+    def wide_ops(cls, ops, what: str = "commit_wide") -> List[tuple]:
+        """The kzg_wide_op fields (kind, bits, limbs, count, flags, a, b, c, q, r, imm_be64, m_be64) of a list of ops.  An op is
+        a mapping: kind ("add" "sub" "mul" "divmod" "mulmod" "carry"), bits (b in [1, 64]; carry: 56), limbs (L in [1, 8], b L
+        <= 512), a (the first row of operand a), b (a first row, ("imm", value) or None), and where the kind takes them c, q, r
+        (first rows or None), m (the modulus), neg_c (bool), count (default: L; carry: 2 L - 1).  An integer may be given as
+        a Python int or as a decimal or 0x string.  Raises KzgError(KZG_E_ARG) with the cause."""
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: wide: {why}")   # noqa: E731
+        ops = list(ops) if isinstance(ops, (list, tuple)) else None
+        if not ops or len(ops) > _native.KZG_WIDE_MAX_OPS:
+            raise bad(f"ops must be a list of 1 .. {_native.KZG_WIDE_MAX_OPS} entries (n_ops)")
+        is_u = lambda v, top: isinstance(v, int) and not isinstance(v, bool) and 0 <= v < top   # noqa: E731
+
+        def big(v, name):
+            if isinstance(v, str):
+                try:
+                    v = int(v, 0)
+                except ValueError:
+                    raise bad(f"{name} must be an integer, or a decimal or 0x string") from None
+            if not isinstance(v, int) or isinstance(v, bool) or v < 0:
+                raise bad(f"{name} must be a non-negative integer")
+            return v
+
+        recs = []
+        for op in ops:
+            if not isinstance(op, dict) or "kind" not in op or "a" not in op:
+                raise bad("an op is a mapping with kind, bits, limbs, a and the operands of its kind")
+            extra = set(op) - set(cls._WIDE_KEYS)
+            if extra:
+                raise bad(f"unknown field {sorted(extra)[0]!r} (the fields are {', '.join(cls._WIDE_KEYS)})")
+            name = op["kind"]
+            if not isinstance(name, str) or name not in cls._WIDE_KINDS:
+                raise bad(f"unknown kind {name!r} (one of {', '.join(cls._WIDE_KINDS)})")
+            kind = cls._WIDE_KINDS[name]
+            modular = name in ("mulmod", "carry")
+            b, L = op.get("bits"), op.get("limbs")
+            if not is_u(b, 65) or b == 0:
+                raise bad("the limb width b (bits) must be an integer in [1, 64]")
+            if not is_u(L, _native.KZG_WIDE_MAX_LIMBS + 1) or L == 0:
+                raise bad(f"the number of limbs L (limbs) must be an integer in [1, {_native.KZG_WIDE_MAX_LIMBS}]")
+            W = b * L
+            if W > 512:
+                raise bad("the width W = b L must be at most 512")
+            if name == "carry" and b > 56:
+                raise bad("the limb width b of a carry must be at most 56")
+            counts = (2 * L - 1,) if name == "carry" else (L, L + 1) if name in ("add", "sub") else (L, 2 * L)
+            count = op.get("count", counts[0])
+            if not is_u(count, 17) or count not in counts:
+                raise bad("count must be L or L + 1 on add and sub, L or 2 L on mul, divmod and mulmod, 2 L - 1 on carry")
+            rows = {}
+            for f in ("a", "b", "c", "q", "r"):
+                v = op.get(f)
+                if f == "b" and isinstance(v, (list, tuple)):
+                    continue
+                if v is None:
+                    rows[f] = _native.KZG_WIDE_ABSENT
+                elif is_u(v, _native.KZG_WIDE_ABSENT):
+                    rows[f] = v
+                else:
+                    raise bad(f"operand {f} must be a first row, an integer in [0, 2^32 - 1), or None")
+            if rows["a"] == _native.KZG_WIDE_ABSENT:
+                raise bad("operand a must be given")
+            flags, imm = 0, 0
+            vb = op.get("b")
+            if isinstance(vb, (list, tuple)):
+                if len(vb) != 2 or vb[0] != "imm":
+                    raise bad('an immediate is ("imm", value)')
+                imm = big(vb[1], "an immediate")
+                if imm >> W:
+                    raise bad("the immediate must be below 2^W")
+                flags |= _native.KZG_WIDE_IMM_B
+                rows["b"] = _native.KZG_WIDE_ABSENT
+            elif vb is None and not modular:
+                raise bad("operand b must be given (a row or an immediate) on add, sub, mul and divmod")
+            m = 0
+            if modular:
+                if op.get("m") is None:
+                    raise bad("the modulus m must be given on mulmod and carry")
+                m = big(op["m"], "the modulus m")
+                if m == 0:
+                    raise bad("the modulus m must not be 0")
+                if m >> W:
+                    raise bad("the modulus m must be below 2^W")
+                if not isinstance(op.get("neg_c", False), bool):
+                    raise bad("neg_c must be a boolean")
+                if op.get("neg_c", False):
+                    flags |= _native.KZG_WIDE_NEG_C
+            elif op.get("c") is not None or op.get("m") is not None or op.get("neg_c"):
+                raise bad(f"an operand the kind does not take: c, neg_c and m belong to mulmod and carry, not to {name}")
+            if name == "carry":
+                if op.get("q") is None or op.get("r") is None:
+                    raise bad("operands q and r must be given on carry")
+            elif op.get("q") is not None or op.get("r") is not None:
+                raise bad(f"an operand the kind does not take: q and r belong to carry, not to {name}")
+            recs.append((kind, b, L, count, flags, rows["a"], rows["b"], rows["c"], rows["q"], rows["r"],
+                         imm.to_bytes(64, "big"), m.to_bytes(64, "big")))
+        n_out = sum(r[3] for r in recs)
+        if n_out > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"n_out: the ops give {n_out} output rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+        return recs
+
+    @staticmethod
+    def wide_op_struct(rec) -> "_native.WideOp":
+        u8x64 = ctypes.c_uint8 * 64
+        return _native.WideOp(*rec[:10], u8x64(*rec[10]), u8x64(*rec[11]))
+
+    def commit_wide(self, input_sets: Sequence[object], ops: Sequence[dict], usable: Optional[int] = None,
+                    tail: Sequence[bytes] = ()) -> Tuple["RowSet", dict]:
+        """kzg_rows_commit_wide over the concatenated rows of input_sets (RowSet objects or bare handles).  ops: see wide_ops.
+        A wide value is L consecutive rows, limb l in row first + l, each cell reduced to its low b bits.  The output rows of an
+        op, in this order: add: L limbs of (a + b) mod 2^W, the carry; sub: L limbs of (a - b) mod 2^W, the borrow; mul: the low
+        L limbs of a b, the high L limbs; divmod: L limbs of floor(a / b), L limbs of a mod b (2^W - 1 and a where b = 0);
+        mulmod: with t = a b + d, L limbs of t mod m, L limbs of floor(t / m) (d = c, or m - (c mod m) with neg_c); carry: the
+        2 L - 1 carry rows of the limb identity of that mulmod.  Returns (the new RowSet of all output rows in the order of ops;
+        {"counts", "first", "qover", "first_qover"}: per op the rows with an out-of-range limb and the smallest such row or None,
+        and the same for rows whose quotient passes 2^W (mulmod) or whose limb identity is inexact (carry)).  usable and tail:
+        as for commit_int."""
+        what = "commit_wide"
+        ni, hi = self._handle_array(input_sets, what)
+        recs = self.wide_ops(ops, what)
+        n_out = sum(r[3] for r in recs)
+        wi, T, lay = self._column_layout(what, input_sets, n_out, "n_out", "read", usable, tail)
+        opts = _native.DeriveOpts(*lay) if lay else None
+        arr = (_native.WideOp * len(recs))(*[self.wide_op_struct(r) for r in recs])
+        c, h = ctypes.create_string_buffer(48 * n_out), ctypes.c_uint64(0)
+        st = [(ctypes.c_uint64 * len(recs))() for _ in range(4)]
+        self._chk(self._lib.kzg_rows_commit_wide(self._h, ni, hi, len(recs), arr, ctypes.byref(opts) if opts is not None else None,
+                                                 c, st[0], st[1], st[2], st[3], ctypes.byref(h)))
+        none = lambda vs: [None if int(v) == _native.KZG_INT_NONE else int(v) for v in vs]   # noqa: E731
+        return (RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]),
+                {"counts": [int(v) for v in st[0]], "first": none(st[1]), "qover": [int(v) for v in st[2]],
+                 "first_qover": none(st[3])})
+
     # ---- a set built from sets: columns that are plain arithmetic in resident columns, and gates checked row by row
     def commit_expr(self, input_sets: Sequence[object], exprs: Sequence[Sequence], usable: Optional[int] = None,
                     tail: Sequence[bytes] = ()) -> Tuple[Optional["RowSet"], List[int], List[Optional[int]]]:
