@@ -88,6 +88,29 @@ int kzg_test_poly_run(kzg_ctx* ctx, int form, int l0, int64_t scan_max, int scan
                       const uint8_t* pts, const uint8_t* alphas_be32, uint32_t nalphas, uint8_t* out_y_be32,
                       uint32_t* out_q_words);
 
+/* ---- the hash join alone (tests/test_join_cpu.py, tests/test_gpu_join.py, reference tests/join_ref.py): the open-addressing
+ * table behind kzg_rows_commit_multiplicities, _zk, _sel and kzg_rows_commit_fetch, through the library's own launchers, with the
+ * CALLER'S capacity in place of the builders' 2 T -- no SRS, no transform, no MSM.  The cells are canonical 32-byte big-endian
+ * scalars, column-major, and are laid out as the builders lay them out (T elements of 8 canonical Montgomery words per column):
+ *   tab_be32: (w + n_pay) x T, the w key columns first; in_be32: w x T, the cells of ONE lookup or read; sel_be32: T, the lookup's
+ *   selector column (walk 2, NULL otherwise)
+ *   build 0 launch_join_build, 1 launch_join_build_rows; walk 0 launch_join_probe, 1 _probe_rows, 2 _probe_sel, 3 launch_join_fetch
+ * The arguments are judged before the context is looked at, KZG_E_ARG with the reason in kzg_last_error otherwise:
+ *   1 <= rows <= T <= 2^12, rows = T for build 0 and for walk 0 (they take every row); cap a power of two, rows <= cap <= 2^12;
+ *   w >= 1, w + n_pay <= 16; index 0 or 1 and only with walk 3, which needs n_pay + index >= 1; sel_be32 with walk 2 and only then
+ * cap = rows with rows distinct tuples is a FULL table: a walk for an absent tuple then ends at its bound of cap steps, raises
+ * *out_overrun and counts no miss (the builders turn that word into an error; cap = 2 T never gets there).
+ * out_slots: the cap slot words after the build (a table row, or 2^32 - 1 for an empty slot); out_home: 2 T words, the slot at
+ * which the walk of table row t starts, then that of cell t; out_cnt: the T counters (all zero after walk 3); out_fetch_be32 (walk
+ * 3): (index + n_pay) x T cells, the index column first, cells at and behind `rows` as an unwritten fill pattern reads;
+ * out_missing, out_first (2^64 - 1: none; walk 3 only), out_overrun: the walks' status words.
+ * kzg_test_join_counts: launch_join_counts over n <= 2^12 caller-given counter words; out_be32: n canonical scalars. */
+int kzg_test_join(kzg_ctx* ctx, int build, int walk, const uint8_t* tab_be32, const uint8_t* in_be32, const uint8_t* sel_be32,
+                  uint64_t T, uint64_t rows, uint32_t w, uint32_t n_pay, int index, uint32_t cap, uint32_t* out_slots,
+                  uint32_t* out_home, uint32_t* out_cnt, uint8_t* out_fetch_be32, uint64_t* out_missing, uint64_t* out_first,
+                  uint32_t* out_overrun);
+int kzg_test_join_counts(kzg_ctx* ctx, const uint32_t* cnt, uint64_t n, uint8_t* out_be32);
+
 /* ---- the MSM passes of a multi-row call (tests/test_msm_passes_cpu.py): how the library splits k row sets + m tail sets (what
  * the openings divide out, one scalar set per point) at window c (2^(c-1) buckets per set) into passes of its Pippenger pipeline; long_rows: rows past the
  * length up to which sets share a pass (2^18).  Host only, no context.  out5: 5 words per pass, room for k + m passes -- first

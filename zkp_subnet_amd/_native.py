@@ -436,6 +436,9 @@ SYMBOLS = {
     "kzg_test_poly_plan_of": (_I, [_U64, _I, ctypes.c_int64, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I),
                                    ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "kzg_test_poly_run": (_I, [_P, _I, _I, ctypes.c_int64, _I, _I, _P, _U64, _U32, _I, _P, _P, _U32, _P, _P, _U32, _P, _P]),
+    "kzg_test_join": (_I, [_P, _I, _I, _P, _P, _P, _U64, _U64, _U32, _U32, _I, _U32, _P, _P, _P, _P, ctypes.POINTER(_U64),
+                           ctypes.POINTER(_U64), ctypes.POINTER(_U32)]),
+    "kzg_test_join_counts": (_I, [_P, _P, _U64, _P]),
 }
 
 # the plan hooks of the recurrence scan (include/kzg_mi355x_recur_test.h, which kzg_mi355x_test.h includes): bound like SYMBOLS

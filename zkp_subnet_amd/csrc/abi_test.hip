@@ -671,6 +671,116 @@ int kzg_test_recur_run(kzg_ctx* ctx, int l0, int64_t top_max, const uint8_t* a_b
     return KZG_OK;
 }
 
+// ---- the hash join alone (tests/test_join_cpu.py, tests/test_gpu_join.py, reference tests/join_ref.py)
+#define KZG_TEST_JOIN_MAX 4096u      // rows and slots per join-hook call
+static const char* join_args_invalid(int build, int walk, uint64_t T, uint64_t rows, uint32_t w, uint32_t n_pay, int index,
+                                     uint32_t cap, bool has_sel) {
+    if (build != 0 && build != 1) return "join: build must be 0 (launch_join_build) or 1 (launch_join_build_rows)";
+    if (walk < 0 || walk > 3) return "join: walk must be 0 (probe), 1 (probe_rows), 2 (probe_sel) or 3 (fetch)";
+    if (!T || T > KZG_TEST_JOIN_MAX) return "join: T outside [1, 2^12]";
+    if (!rows || rows > T) return "join: rows outside [1, T]";
+    if ((build == 0 || walk == 0) && rows != T) return "join: launch_join_build and launch_join_probe take every row, rows must be T";
+    if (!cap || (cap & (cap - 1)) || cap < rows || cap > KZG_TEST_JOIN_MAX) return "join: cap must be a power of two in [rows, 2^12]";
+    if (!w || n_pay > KZG_MAX_BATCH_OPEN || w + n_pay > KZG_MAX_BATCH_OPEN) return "join: w >= 1 and w + n_pay <= 16 table columns";
+    if (index != 0 && index != 1) return "join: index must be 0 or 1";
+    if (index && walk != 3) return "join: the index column goes with the fetch only";
+    if (walk == 3 && n_pay + (uint32_t)index == 0) return "join: a fetch needs a payload column or the index";
+    if (has_sel != (walk == 2)) return "join: a selector column goes with launch_join_probe_sel, and only with it";
+    return nullptr;
+}
+int kzg_test_join(kzg_ctx* ctx, int build, int walk, const uint8_t* tab_be32, const uint8_t* in_be32, const uint8_t* sel_be32,
+                  uint64_t T, uint64_t rows, uint32_t w, uint32_t n_pay, int index, uint32_t cap, uint32_t* out_slots,
+                  uint32_t* out_home, uint32_t* out_cnt, uint8_t* out_fetch_be32, uint64_t* out_missing, uint64_t* out_first,
+                  uint32_t* out_overrun) {
+    // the arguments are judged first, with no context and no device: nothing invalid reaches a kernel
+    if (const char* why = join_args_invalid(build, walk, T, rows, w, n_pay, index, cap, sel_be32 != nullptr)) return fail(ctx, KZG_E_ARG, why);
+    if (!ctx || !tab_be32 || !in_be32 || !out_slots || !out_home || !out_cnt || !out_missing || !out_first || !out_overrun ||
+        (walk == 3 && !out_fetch_be32))
+        return fail(ctx, KZG_E_ARG, "join: no context or no data");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;
+    Lane& L = H.L();
+    prof_begin(ctx, L);
+    int rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    hipStream_t s = L.stream;
+    // the builders' layout: every column a vector of T canonical Montgomery elements, the table's w + n_pay first, then the w
+    // columns of the one lookup or read, the selector, the fetched columns; slots, counters and homes in the staging buffer
+    const uint64_t vw = T * 8;
+    const uint32_t w_tab = w + n_pay, n_out = walk == 3 ? n_pay + (uint32_t)index : 0;
+    HIPCHK(ctx, L.qext.ensure(((size_t)w_tab + w + 1 + n_out) * T * 32));
+    HIPCHK(ctx, L.qstage.ensure(((size_t)cap + 3 * T) * 4));
+    HIPCHK(ctx, L.scal.ensure(64));
+    HIPCHK(ctx, L.out_be.ensure((size_t)(n_out ? n_out : 1) * T * 32));
+    uint32_t *tab = L.qext.as<uint32_t>(), *in = tab + (uint64_t)w_tab * vw, *sel = in + (uint64_t)w * vw, *out = sel + vw;
+    uint32_t *slots = L.qstage.as<uint32_t>(), *cnt = slots + cap, *home = cnt + T;
+    uint64_t *missing = L.scal.as<uint64_t>(), *first = missing + 1;       // [0, 8) missing, [8, 16) first, [16, 20) overrun
+    uint32_t* overrun = L.scal.as<uint32_t>() + 4;
+    rc = upload_fr(ctx, L, tab_be32, (uint64_t)w_tab * T, tab, 1);
+    if (rc) return rc;
+    rc = upload_fr(ctx, L, in_be32, (uint64_t)w * T, in, 1);
+    if (rc) return rc;
+    if (walk == 2) {
+        rc = upload_fr(ctx, L, sel_be32, T, sel, 1);
+        if (rc) return rc;
+    }
+    HIPCHK(ctx, hipMemsetAsync(slots, 0xff, (size_t)cap * 4, s));
+    HIPCHK(ctx, hipMemsetAsync(cnt, 0, (size_t)T * 4, s));
+    HIPCHK(ctx, hipMemsetAsync(missing, 0, 64, s));
+    HIPCHK(ctx, hipMemsetAsync(first, 0xff, 8, s));                        // KZG_FETCH_NONE
+    // whatever the fetch fails to write must show: its columns start from a pattern that is no result
+    if (n_out) HIPCHK(ctx, hipMemsetAsync(out, 0xff, (size_t)n_out * T * 32, s));
+    launch_join_home(s, tab, T, w, T, cap, home);
+    launch_join_home(s, in, T, w, T, cap, home + T);
+    {
+        Span sp(ctx, L, KZG_T_POLY);
+        if (build == 0) launch_join_build(s, tab, T, w, slots, cap, overrun);
+        else launch_join_build_rows(s, tab, T, rows, w, slots, cap, overrun);
+        if (walk == 0) launch_join_probe(s, tab, in, T, w, slots, cap, cnt, missing, overrun);
+        else if (walk == 1) launch_join_probe_rows(s, tab, in, T, rows, w, slots, cap, cnt, missing, overrun);
+        else if (walk == 2) launch_join_probe_sel(s, tab, in, sel, T, rows, w, slots, cap, cnt, missing, overrun);
+        else launch_join_fetch(s, tab, in, T, rows, w, n_pay, index != 0, slots, cap, out, missing, first, overrun);
+    }
+    // the fetched words as the kernel left them, taken out of Montgomery form without a reduction check (as kzg_test_recur_run)
+    if (n_out) launch_fr_to_be(s, out, L.out_be.as<uint8_t>(), (uint64_t)n_out * T, 1);
+    rc = finish(ctx, L);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpy(out_slots, slots, (size_t)cap * 4, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(out_cnt, cnt, (size_t)T * 4, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(out_home, home, (size_t)2 * T * 4, hipMemcpyDeviceToHost));
+    if (n_out) HIPCHK(ctx, hipMemcpy(out_fetch_be32, L.out_be.p, (size_t)n_out * T * 32, hipMemcpyDeviceToHost));
+    uint64_t tally[3];
+    HIPCHK(ctx, hipMemcpy(tally, missing, sizeof tally, hipMemcpyDeviceToHost));
+    *out_missing = tally[0];
+    *out_first = tally[1];
+    *out_overrun = (uint32_t)tally[2];
+    H.clean = true;
+    return KZG_OK;
+}
+int kzg_test_join_counts(kzg_ctx* ctx, const uint32_t* cnt, uint64_t n, uint8_t* out_be32) {
+    if (!n || n > KZG_TEST_JOIN_MAX) return fail(ctx, KZG_E_ARG, "join counts: n outside [1, 2^12]");
+    if (!ctx || !cnt || !out_be32) return fail(ctx, KZG_E_ARG, "join counts: no context or no data");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;
+    Lane& L = H.L();
+    prof_begin(ctx, L);
+    int rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    HIPCHK(ctx, L.qstage.ensure(n * 4));
+    HIPCHK(ctx, L.coeffA.ensure(n * 32));
+    HIPCHK(ctx, L.out_be.ensure(n * 32));
+    HIPCHK(ctx, hipMemcpyAsync(L.qstage.p, cnt, n * 4, hipMemcpyHostToDevice, L.stream));
+    launch_join_counts(L.stream, L.qstage.as<uint32_t>(), L.coeffA.as<uint32_t>(), n);
+    launch_fr_to_be(L.stream, L.coeffA.as<uint32_t>(), L.out_be.as<uint8_t>(), n, 1);
+    rc = finish(ctx, L);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpy(out_be32, L.out_be.p, n * 32, hipMemcpyDeviceToHost));
+    H.clean = true;
+    return KZG_OK;
+}
+
 // ---- the MSM passes of a multi-row call (tests/test_msm_passes_cpu.py)
 int kzg_test_msm_passes(int c, int long_rows, uint32_t k, uint32_t m, uint32_t* out5, int* out_passes) {
     if (!out5 || !out_passes) return fail(nullptr, KZG_E_ARG, "msm passes: null output");

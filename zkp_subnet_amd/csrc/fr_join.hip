@@ -314,6 +314,16 @@ __global__ void __launch_bounds__(256) k_fetch_index(const uint32_t* __restrict_
     fetch_tally(miss, missing, first);
 }
 
+// test hook (kzg_test_join): the home slot of tuple t < n, the slot at which every walk above starts
+__global__ void __launch_bounds__(256) k_join_home(const uint32_t* __restrict__ cols, uint64_t T, uint32_t w, uint64_t n,
+                                                    uint32_t mask, uint32_t* __restrict__ home) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n) home[t] = join_hash(cols, T, w, t) & mask;
+}
+void launch_join_home(hipStream_t s, const uint32_t* cols, uint64_t T, uint32_t w, uint64_t n, uint32_t cap, uint32_t* home) {
+    if (n && n <= T) k_join_home<<<nblk(n, 256), 256, 0, s>>>(cols, T, w, n, cap - 1, home);
+}
+
 void launch_join_build(hipStream_t s, const uint32_t* tab, uint64_t T, uint32_t w, uint32_t* slots, uint32_t cap,
                        uint32_t* overrun) {
     if (T) k_join_build<<<nblk(T, 256), 256, 0, s>>>(tab, T, w, slots, cap - 1, overrun);

@@ -276,6 +276,8 @@ void launch_join_probe_rows(hipStream_t s, const uint32_t* tab, const uint32_t* 
 // canonical Montgomery elements, a cell whose sel[t] is zero is neither probed nor counted as missing
 void launch_join_probe_sel(hipStream_t s, const uint32_t* tab, const uint32_t* in, const uint32_t* sel, uint64_t T, uint64_t rows,
                            uint32_t w, const uint32_t* slots, uint32_t cap, uint32_t* cnt, uint64_t* missing, uint32_t* overrun);
+// test hook (kzg_test_join): home[t] <- the slot at which the walk of tuple t < n <= T of cols starts, hash & (cap - 1)
+void launch_join_home(hipStream_t s, const uint32_t* cols, uint64_t T, uint32_t w, uint64_t n, uint32_t cap, uint32_t* home);
 // ---- the fetch of kzg_rows_commit_fetch (fr_join.hip).  tab: n_keys + n_pay columns of T canonical Montgomery elements, the
 // first n_keys of them the key that launch_join_build(_rows) was called with (w = n_keys, the same `rows`); in: the n_keys
 // columns of one read; out: index + n_pay vectors of T, of which cells [0, rows) are written.  Cell t takes the payload of the

@@ -2126,6 +2126,36 @@ class HipEngine:
                                                ctypes.addressof(cl)))
         return v.raw[:32 * n], cl.raw
 
+    def test_join(self, build: int, walk: int, tab_be32: bytes, in_be32: bytes, T: int, rows: int, w: int, cap: int,
+                  n_pay: int = 0, index: bool = False, sel_be32: Optional[bytes] = None) -> Dict[str, object]:
+        """The hash join alone through the library's own launchers at the CALLER'S capacity (kzg_test_join; no SRS, no MSM):
+        build 0 launch_join_build, 1 _build_rows; walk 0 launch_join_probe, 1 _probe_rows, 2 _probe_sel (sel_be32: the selector
+        column), 3 launch_join_fetch.  tab_be32: (w + n_pay) x T canonical cells, column-major; in_be32: w x T.  Returns {"slots":
+        the cap slot words (2^32 - 1: empty), "home_tab", "home_in": the T home slots of the table rows and of the cells, "cnt":
+        the T counters, "fetched": the index + n_pay fetched columns as bytes (walk 3), "missing", "first" (None: no miss),
+        "overrun"}.  KzgError(KZG_E_ARG) for arguments outside the kernels' preconditions."""
+        if len(tab_be32) != 32 * (w + n_pay) * T or len(in_be32) != 32 * w * T or (sel_be32 is not None and len(sel_be32) != 32 * T):
+            raise KzgError(_native.KZG_E_ARG, "join: (w + n_pay) x T table cells, w x T input cells, T selector cells")
+        n_out = n_pay + int(index) if walk == 3 else 0
+        slots, home = (ctypes.c_uint32 * max(1, cap))(), (ctypes.c_uint32 * max(1, 2 * T))()
+        cnt, fetched = (ctypes.c_uint32 * max(1, T))(), ctypes.create_string_buffer(32 * max(1, n_out * T))
+        missing, first, overrun = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+        self._chk(self._lib.kzg_test_join(self._h, build, walk, tab_be32, in_be32, sel_be32, T, rows, w, n_pay, int(index), cap,
+                                          ctypes.addressof(slots), ctypes.addressof(home), ctypes.addressof(cnt),
+                                          ctypes.addressof(fetched), ctypes.byref(missing), ctypes.byref(first),
+                                          ctypes.byref(overrun)))
+        home = list(home)
+        return {"slots": list(slots), "home_tab": home[:T], "home_in": home[T:], "cnt": list(cnt),
+                "fetched": [fetched.raw[32 * T * c:32 * T * (c + 1)] for c in range(n_out)], "missing": missing.value,
+                "first": None if first.value == (1 << 64) - 1 else first.value, "overrun": overrun.value}
+
+    def test_join_counts(self, counters: Sequence[int]) -> bytes:
+        """launch_join_counts over caller-given counter words (kzg_test_join_counts): 32 canonical big-endian bytes each."""
+        n = len(counters)
+        out = ctypes.create_string_buffer(32 * max(1, n))
+        self._chk(self._lib.kzg_test_join_counts(self._h, (ctypes.c_uint32 * max(1, n))(*counters), n, ctypes.addressof(out)))
+        return out.raw[:32 * n]
+
 
 def ntt_plan_of(log_n: int, kernel: int = -1, tile_log: int = 0) -> Tuple[int, List[Tuple[int, int]]]:
     """The pass plan the library runs for 2^log_n elements (kzg_test_ntt_plan_of; no context, no device): (form, [(S, logC)
