@@ -1259,6 +1259,82 @@ int kzg_rows_commit_wide(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t*
                          uint8_t* out_commitments48 /* n_out * 48 */, uint64_t* out_counts /* n_ops */,
                          uint64_t* out_first /* n_ops */, uint64_t* out_qover /* n_ops */, uint64_t* out_first_qover /* n_ops */,
                          uint64_t* out_handle);
+/* THE POSEIDON PERMUTATION COLUMNS: a set built FROM sets, the columns of the hash chip -- Merkle nodes, page commitments,
+ * in-circuit Fiat-Shamir -- which kzg_rows_commit_expr (no row-to-row dependence) and kzg_rows_commit_recurrence (affine in the
+ * running value) cannot express.  The library generates NO constants: the caller supplies the state width t, 2 <= t <= 8, the
+ * number of full rounds R_F (even, 2 <= R_F <= 16) and of partial rounds R_P (0 <= R_P <= 128), the t R round constants rc
+ * (round-major, R = R_F + R_P) and the t x t matrix M (row-major), all canonical scalars of 32 big-endian bytes.  The S-box is
+ * x -> x^5.  THE PERMUTATION of a state s, for each round rho = 0 .. R - 1:
+ *   1. s_i += rc[rho t + i] for every i;
+ *   2. s_i <- s_i^5 for every i where rho < R_F / 2 or rho >= R_F / 2 + R_P (a full round), else for i = 0 only;
+ *   3. s <- M s, that is s'_i = sum_j M[i t + j] s_j.
+ * This is the plain (unoptimised) Hades schedule.  The concatenated rows of the input_handles sets (as in kzg_rows_open) are the
+ * source columns.  A call has 1 <= n_units <= KZG_POSEIDON_MAX_UNITS units that share params.  in[j], j < t, is the source row of
+ * state element j, or KZG_POSEIDON_IMM: then the element is imm_be32[j] on every row (a domain tag, the capacity element,
+ * padding), canonical; imm_be32[j] is all zero beside a row.  One row may serve several slots.  With n = opts->usable, or T in
+ * the plain layout:
+ *   KZG_POSEIDON_ROW     for every row t' < n the state is (in_0[t'], .., in_{t-1}[t']); output column c, c < n_out, holds state
+ *                        element out[c] after the permutation; 1 <= n_out <= t, the out[c] distinct and below t.  With the flag
+ *                        KZG_POSEIDON_CHECK the unit commits NOTHING: expect[c] is the source row that column c is compared
+ *                        with, out_mismatch[u] is the number of rows t' < n where some expected cell differs from the computed
+ *                        one and out_first_mismatch[u] the smallest such row, or KZG_POSEIDON_NONE
+ *   KZG_POSEIDON_ROUNDS  the round trace with the period P = period >= R + 1: block b = 0 .. floor(n / P) - 1 occupies rows
+ *                        [b P, b P + P); its input is read at row b P of the in entries; output column j (n_out = t, out[j] = j)
+ *                        holds at row b P + rho state element j BEFORE round rho, rho = 0 .. R, so row b P is the input and row
+ *                        b P + R the permutation's output; rows b P + R + 1 .. b P + P - 1 and the rows from floor(n / P) P to
+ *                        n - 1 are 0.  No source cell is read other than at the rows b P of existing blocks; a block cut by n is
+ *                        not started.  KZG_POSEIDON_CHECK is refused
+ * out_perms[u] is the number of permutations unit u ran: n for a ROW unit, floor(n / P) for a ROUNDS unit; out_mismatch[u] = 0
+ * and out_first_mismatch[u] = KZG_POSEIDON_NONE on a unit that commits.  All committed columns of a call form ONE new set of the
+ * same worker and length, in the order of units, then of out: out_commitments48[c] equals kzg_rows_commit(i, n_out, these rows,
+ * T, 1, ..)[c] byte for byte, and *out_handle opens, evaluates, combines, releases, goes stale and counts against
+ * KZG_MAX_ROW_SETS like any other.  A call made of checks alone creates no set (*out_handle = 0, out_commitments48 may be null),
+ * runs no inverse transform and no MSM and counts nothing against KZG_MAX_ROW_SETS: the convention of kzg_rows_commit_expr's
+ * checks and of kzg_rows_check_copies.  ONE kernel launch computes every unit; the constants reach the device through a buffer
+ * of the lane; nothing row-sized crosses the host link.  A call reads at most KZG_MAX_BATCH_OPEN distinct rows and commits at
+ * most KZG_MAX_BATCH_OPEN.  opts (NULL: plain layout) is kzg_derive_opts as kzg_rows_commit_derived reads it: source rows t' >=
+ * usable are never read, compared or counted, output row usable + s of committed column c takes tail_be32[c * (T - usable) + s],
+ * there is NO closing row.  Handle lists, worker, T, staleness and threads follow kzg_rows_commit_expr.  KZG_E_ARG with a message
+ * that begins "poseidon:" and names the cause: t, R_F (an odd one included), R_P, a period below R + 1 or n_units outside their
+ * ranges; more than KZG_MAX_BATCH_OPEN output rows or distinct input rows; a constant, matrix entry or immediate at or above r
+ * (checked on the host before a lane is taken); an unknown mode or flag; n_out outside [1, t], an out index at or above t or a
+ * repeated one; KZG_POSEIDON_CHECK on a ROUNDS unit; a row index beyond the concatenation; T above 2^32; the usable and tail
+ * refusals of kzg_rows_commit_derived; the handle refusals of kzg_rows_open.  After any error the context keeps serving.
+ * OUT OF SCOPE: generating constants (the Grain LFSR); other exponents and the inverse S-box; the optimised partial-round form
+ * (sparse matrices, pre-folded constants); sponge chaining of one block's output into the next block's input, which is
+ * sequential along the column (a Merkle path is a ROW unit, a kzg_rows_commit_fetch and another ROW unit); Poseidon2.
+ * SOUNDNESS: nothing here is a proof.  The columns are prover data; the argument is the caller's round gate over the trace
+ * columns, in the quotient, under the caller's fixed rc and selector columns.  A zero mismatch count convinces no verifier. */
+#define KZG_POSEIDON_ROW    1
+#define KZG_POSEIDON_ROUNDS 2
+#define KZG_POSEIDON_CHECK  1u               /* flags (ROW): compare with expect, commit nothing */
+#define KZG_POSEIDON_IMM    0xffffffffu      /* in[j]: the element is imm_be32[j] */
+#define KZG_POSEIDON_NONE   0xffffffffffffffffull   /* out_first_mismatch: no mismatch */
+#define KZG_POSEIDON_MIN_T 2
+#define KZG_POSEIDON_MAX_T 8
+#define KZG_POSEIDON_MAX_FULL 16
+#define KZG_POSEIDON_MAX_PARTIAL 128
+#define KZG_POSEIDON_MAX_UNITS 8
+typedef struct kzg_poseidon_params {
+    uint32_t t, full, partial;   /* t in [2, 8]; R_F even in [2, 16]; R_P in [0, 128] */
+    const uint8_t* rc_be32;      /* t (full + partial) scalars, round-major */
+    const uint8_t* mds_be32;     /* t t scalars, row-major */
+} kzg_poseidon_params;
+typedef struct kzg_poseidon_unit {
+    uint32_t mode;               /* KZG_POSEIDON_ROW or KZG_POSEIDON_ROUNDS */
+    uint32_t flags;              /* 0 or KZG_POSEIDON_CHECK */
+    uint32_t n_out;              /* ROW: 1 .. t; ROUNDS: t */
+    uint32_t period;             /* ROUNDS: P >= R + 1; ROW: 0 */
+    uint32_t in[KZG_POSEIDON_MAX_T];       /* [j < t] a row of the concatenated rows of input_handles, or KZG_POSEIDON_IMM */
+    uint32_t out[KZG_POSEIDON_MAX_T];      /* [c < n_out] the state element of output column c */
+    uint32_t expect[KZG_POSEIDON_MAX_T];   /* [c < n_out] with KZG_POSEIDON_CHECK: the row that column c is compared with */
+    uint8_t imm_be32[KZG_POSEIDON_MAX_T][32];   /* [j] the element where in[j] = KZG_POSEIDON_IMM; all zero beside a row */
+} kzg_poseidon_unit;
+int kzg_rows_commit_poseidon(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                             const kzg_poseidon_params* params, uint32_t n_units, const kzg_poseidon_unit* units,
+                             const kzg_derive_opts* opts /* NULL: plain */, uint8_t* out_commitments48 /* n_out * 48 */,
+                             uint64_t* out_perms /* n_units */, uint64_t* out_mismatch /* n_units */,
+                             uint64_t* out_first_mismatch /* n_units */, uint64_t* out_handle);
 /* THE QUOTIENT WITH LOOKUP SELECTORS: kzg_rows_commit_quotient_zk and kzg_rows_quotient_part for lookups that are enabled on
  * some rows only.  selectors->selector_rows holds L = lookup->n_lookups entries, each a row index into the call's concatenated
  * rows (the caller's fixed column q_l, the row that kzg_rows_commit_multiplicities_sel / _lookup_sum_sel read) or
@@ -1648,6 +1724,11 @@ int kzg_multi_rows_commit_wide(kzg_multi* mh, uint32_t i, uint32_t n_input_handl
                                const kzg_wide_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48,
                                uint64_t* out_counts, uint64_t* out_first, uint64_t* out_qover, uint64_t* out_first_qover,
                                uint64_t* out_handle);
+/* kzg_rows_commit_poseidon on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_poseidon(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                   const kzg_poseidon_params* params, uint32_t n_units, const kzg_poseidon_unit* units,
+                                   const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_perms,
+                                   uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

@@ -42,6 +42,13 @@ KZG_WIDE_ADD, KZG_WIDE_SUB, KZG_WIDE_MUL, KZG_WIDE_DIVMOD, KZG_WIDE_MULMOD, KZG_
 KZG_WIDE_IMM_B, KZG_WIDE_NEG_C = 1, 2
 KZG_WIDE_ABSENT = 0xffffffff
 KZG_WIDE_MAX_OPS, KZG_WIDE_MAX_LIMBS = 8, 8
+# kzg_rows_commit_poseidon: kzg_poseidon_unit.mode, the flag, a slot that holds an immediate, "no mismatch", the limits
+KZG_POSEIDON_ROW, KZG_POSEIDON_ROUNDS = 1, 2
+KZG_POSEIDON_CHECK = 1
+KZG_POSEIDON_IMM = 0xffffffff
+KZG_POSEIDON_NONE = 0xffffffffffffffff
+KZG_POSEIDON_MIN_T, KZG_POSEIDON_MAX_T = 2, 8
+KZG_POSEIDON_MAX_FULL, KZG_POSEIDON_MAX_PARTIAL, KZG_POSEIDON_MAX_UNITS = 16, 128, 8
 KZG_MAX_EXPR_FACTORS = 8   # kzg_rows_commit_expr: factors of one term
 KZG_EXPR_CHECK = 1   # kzg_expr.flags: evaluate and count only
 KZG_EXPR_NONE = 0xffffffffffffffff   # out_first: no non-zero cell
@@ -140,6 +147,17 @@ class WideOp(ctypes.Structure):
                 ("c", _U32), ("q", _U32), ("r", _U32), ("imm_be64", ctypes.c_uint8 * 64), ("m_be64", ctypes.c_uint8 * 64)]
 
 
+class PoseidonParams(ctypes.Structure):
+    """kzg_poseidon_params"""
+    _fields_ = [("t", _U32), ("full", _U32), ("partial", _U32), ("rc_be32", ctypes.c_char_p), ("mds_be32", ctypes.c_char_p)]
+
+
+class PoseidonUnit(ctypes.Structure):
+    """kzg_poseidon_unit"""
+    _fields_ = [("mode", _U32), ("flags", _U32), ("n_out", _U32), ("period", _U32), ("in_", _U32 * 8), ("out", _U32 * 8),
+                ("expect", _U32 * 8), ("imm_be32", (ctypes.c_uint8 * 32) * 8)]
+
+
 class Col(ctypes.Structure):
     """kzg_col"""
     _fields_ = [("data", ctypes.c_void_p), ("count", ctypes.c_uint64), ("kind", ctypes.c_uint32), ("fill_be32", ctypes.c_char_p)]
@@ -224,6 +242,9 @@ SYMBOLS = {
     "kzg_rows_commit_wide": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(WideOp), ctypes.POINTER(DeriveOpts), _B,
                                   ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64),
                                   ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_poseidon": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(PoseidonParams), _U32,
+                                      ctypes.POINTER(PoseidonUnit), ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64),
+                                      ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_derived": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp), ctypes.POINTER(DeriveOpts), _B,
                                      ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_expr": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,
@@ -351,6 +372,9 @@ SYMBOLS = {
     "kzg_multi_rows_commit_wide": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(WideOp),
                                         ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64),
                                         ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_poseidon": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(PoseidonParams), _U32,
+                                            ctypes.POINTER(PoseidonUnit), ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64),
+                                            ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_derived": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp),
                                            ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_expr": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,

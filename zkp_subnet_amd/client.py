@@ -1057,6 +1057,54 @@ class Client:
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
                 "counts": st["counts"], "first": st["first"], "qover": st["qover"], "first_qover": st["first_qover"]}
 
+    # ---- the hash chip: the Poseidon permutation (x^5, the caller's constants) per row, as a check, or as a round trace
+    @_guard
+    def worker_commit_poseidon(self, input_handles: Sequence[int], params: dict, units: Sequence[dict],
+                               usable: Optional[int] = None, tail: Sequence[str] = ()):
+        """Extension: Poseidon permutation columns of the rows of the input_handles sets, computed and committed on the device
+        as one new set.  params: {"t", "full", "partial", "rc", "mds"}: the width t in [2, 8], R_F full rounds (even, 2 .. 16),
+        R_P partial rounds (0 .. 128), the t (R_F + R_P) round constants round-major and the t x t matrix row-major; scalars
+        below r as integers or decimal / 0x strings.  The library generates no constants.  Per round: s_i += rc[rho t + i]; s_i
+        <- s_i^5 for every i in a full round (rho < R_F / 2 or rho >= R_F / 2 + R_P), for i = 0 only in a partial one; s <- M s.
+        units: 1 to 8 objects.  {"mode": "row", "in": [t entries], "out": [state indices]} hashes every row t' < n (n = usable,
+        or T) and commits one column per entry of out; with "expect": [rows] in place of the commitment it commits nothing and
+        reports `mismatch`, the rows where an expected cell differs, and `first_mismatch`.  {"mode": "rounds", "in": [...],
+        "period": P} with P >= R + 1 commits the t columns of the round trace: block b occupies rows [b P, b P + P), row b P +
+        rho holds the state before round rho, row b P + R the output, the rest is 0.  An entry of in is a row index or ["imm",
+        value].  usable and tail: as for worker_commit_derived.  Returns the handle (null when every unit is a check), the
+        commitments, and per unit `perms`, `mismatch`, `first_mismatch`.  Nothing here is a proof: the columns are prover data
+        and the argument is the caller's round gate in the quotient."""
+        what = "worker_commit_poseidon"
+        hs = _handles(input_handles)
+        try:
+            if not isinstance(params, dict):
+                raise ValueError(f"params is an object: {params!r}")
+            par = dict(params)
+            recs = []
+            for un in units:
+                if not isinstance(un, dict):
+                    raise ValueError(f"a unit is an object: {un!r}")
+                rec = dict(un)
+                if isinstance(rec.get("in"), (list, tuple)):
+                    rec["in"] = [tuple(v) if isinstance(v, (list, tuple)) else v for v in rec["in"]]
+                recs.append(rec)
+        except (TypeError, ValueError, IndexError, KeyError) as e:
+            raise codec.CodecError(f"{what}: params must be an object and units a list of objects: {e!r}") from e
+        if not recs:
+            raise codec.CodecError(f"{what}: units must not be empty")
+        if usable is None:
+            if tail:
+                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
+            tb = []
+        else:
+            usable, tb = self._blind(what, usable, tail)
+            if usable == 0:
+                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        rs, st = self.engine.commit_poseidon(hs, par, recs, usable, tb)
+        return {"handle": None if rs is None else int(rs.handle),
+                "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments],
+                "perms": st["perms"], "mismatch": st["mismatch"], "first_mismatch": st["first_mismatch"]}
+
     @staticmethod
     def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: Sequence[int], n_groups: int, width: int,
                                theta: str, gamma: str, coeff: str, active_row: Optional[int] = None,

@@ -441,6 +441,37 @@ static_assert(sizeof(WideTab) + 64 <= 4096 && POLY_MAX_ROWS <= 256, "the op tabl
 // row of the first kind), [3 n_ops + o] <- min(., of the second).  Sources are only read and may coincide; out must not overlap
 // a source.  1 <= b <= 64 (carry: 56), 1 <= L <= 8, b L <= 512, immediates below 2^(b L), m != 0: the caller's checks
 void launch_wide(hipStream_t s, const WideTab& tab, uint32_t n_ops, uint64_t T, uint64_t n, uint64_t* stats);
+// ---- the Poseidon permutation columns of kzg_rows_commit_poseidon (fr_poseidon.hip).  The state of a unit is t elements, element
+// j read from source vector slot[j] (src + slot T 8 words) or, at POS_IMM, the unit's immediate j.  A ROW unit runs one
+// permutation per row t' < n and writes state element i to vector col[i] of out (POS_NO_COL: not written); with out null it is a
+// check and compares that element with source vector exp[col[i]] instead.  A ROUNDS unit runs one permutation per block of
+// `period` rows and writes the state before every round and behind the last into the t vectors at out, which the caller has
+// zeroed.  cst: the constants as 8 little-endian 32-bit words of a canonical integer each: t R round constants, t t matrix
+// entries, then t immediates per unit
+#define POS_MAX_T 8
+#define POS_MAX_UNITS 8
+#define POS_MAX_ROUNDS 144
+#define POS_ROW 1
+#define POS_ROUNDS 2
+#define POS_IMM 0xffu
+#define POS_NO_COL 0xffu
+struct PosUnit {
+    uint32_t* out;
+    uint32_t mode, period;
+    uint8_t slot[POS_MAX_T], col[POS_MAX_T], exp[POS_MAX_T];
+};
+struct PosTab {
+    PosUnit u[POS_MAX_UNITS];
+    const uint32_t *src, *cst;
+    uint32_t t, full, partial, n_units;
+};
+static_assert(sizeof(PosTab) + 64 <= 4096 && POLY_MAX_ROWS < POS_IMM, "the unit table rides as a kernel argument; slots ride in bytes");
+// the words of cst that a call of n_units units needs, and ONE launch for all of them, instantiated on t.  stats: two runs of
+// n_units words: [u] += the rows of check u with a cell that differs, [n_units + u] <- min(., the smallest such row).  Sources are
+// only read and may coincide; out must not overlap a source.  2 <= t <= 8, full even, full + partial <= POS_MAX_ROUNDS, period >=
+// full + partial + 1, canonical constants: the caller's checks
+uint32_t poseidon_cst_words(uint32_t t, uint32_t rounds, uint32_t n_units);
+void launch_poseidon(hipStream_t s, const PosTab& tab, uint64_t T, uint64_t n, uint64_t* stats);
 // ---- the expression columns of kzg_rows_commit_expr (fr_expr.hip): v[t] = sum_u c_u prod_f src.r[row[u][f]][(t + rot[u][f]) mod T]
 // for t < n <= T over evaluation vectors of T canonical Montgomery elements (T a power of two, at most 2^32)
 #define EXPR_MAX_TERMS 16

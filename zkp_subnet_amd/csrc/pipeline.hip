@@ -1531,6 +1531,114 @@ int rows_wide_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, u
     return KZG_OK;
 }
 
+// The Poseidon permutation columns (kzg_rows_commit_poseidon): the frame of rows_wide_dev, with the checks of rows_expr_dev.
+// Each DISTINCT source row (by device pointer) that some unit reads or expects is transformed forward once.
+//   step                      launches                         per call
+//   forward transforms        launch_fr_ntt                    one per distinct source row named
+//   constants                 one host-to-device copy          rc, M and the immediates as words, behind the vectors
+//   zero the trace columns    hipMemsetAsync                   one per ROUNDS unit
+//   every unit                launch_poseidon (k_fr_poseidon<t>) ONE, grid y = unit
+//   tail                      launch_sort_tail                 one per output row, with `usable` only
+//   inverse transform         row_to_coeffs                    one per output row, straight into dst
+//   commit                    multi_msms_finish                ONE pass of n_out scalar sets
+// The mismatch count and the first mismatching row of every unit are u64 words behind the first two evaluation slots of the
+// record (the layout of rows_expr_dev) and come back in the copy behind the MSM.  With n_out = 0 (checks alone) nothing is
+// transformed back and no MSM runs.  Workspace: distinct sources + n_out vectors of T, and the constants.
+static void poseidon_words(uint32_t w[8], const uint8_t* be32) {
+    for (int i = 0; i < 8; i++)
+        w[i] = ((uint32_t)be32[28 - 4 * i] << 24) | ((uint32_t)be32[29 - 4 * i] << 16) | ((uint32_t)be32[30 - 4 * i] << 8) |
+               be32[31 - 4 * i];
+}
+int rows_poseidon_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const kzg_poseidon_params* params,
+                      uint32_t n_units, const kzg_poseidon_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst,
+                      uint8_t* out_c48, uint64_t* out_stats, const Blind* lay) {
+    Lane& A = H.L();
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    const int lg = ilog2_exact(T);
+    uint32_t* tw = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
+    const uint64_t vw = T * 8;                        // one vector, in words
+    const uint64_t n = lay ? lay->usable : T;         // the rows that are read
+    constexpr uint32_t CNT_OFF = 64;                  // the statistics in the record: mismatches, then the first rows
+    static_assert(CNT_OFF + 16 * KZG_POSEIDON_MAX_UNITS <= MR_PAIRS * 32 && KZG_POSEIDON_MAX_UNITS == POS_MAX_UNITS &&
+                      KZG_POSEIDON_MAX_T == POS_MAX_T && KZG_POSEIDON_MAX_FULL + KZG_POSEIDON_MAX_PARTIAL == POS_MAX_ROUNDS &&
+                      KZG_POSEIDON_ROW == POS_ROW && KZG_POSEIDON_ROUNDS == POS_ROUNDS,
+                  "the two statistics of every unit fit the record's evaluation slots; the header's caps are the kernel's");
+    const uint32_t t = params->t, R = params->full + params->partial;
+    const uint32_t* distinct[POLY_MAX_ROWS];
+    uint32_t nd = 0;
+    auto slot_of = [&](const uint32_t* p) {
+        uint32_t d = 0;
+        while (d < nd && distinct[d] != p) d++;
+        if (d == nd) distinct[nd++] = p;
+        return d;
+    };
+    PosTab tab;
+    memset(&tab, 0, sizeof(tab));
+    tab.t = t;
+    tab.full = params->full;
+    tab.partial = params->partial;
+    tab.n_units = n_units;
+    const uint32_t cw = poseidon_cst_words(t, R, n_units);
+    std::vector<uint32_t> cst(cw, 0);                 // (lives until multi_msms_finish has waited for the stream)
+    for (uint32_t k = 0; k < t * R; k++) poseidon_words(&cst[8 * k], params->rc_be32 + 32 * (size_t)k);
+    for (uint32_t k = 0; k < t * t; k++) poseidon_words(&cst[8 * (t * R + k)], params->mds_be32 + 32 * (size_t)k);
+    for (uint32_t u = 0; u < n_units; u++) {
+        const kzg_poseidon_unit& in = units[u];
+        PosUnit& U = tab.u[u];
+        const bool check = in.flags & KZG_POSEIDON_CHECK;
+        U.mode = in.mode;
+        U.period = in.period;
+        memset(U.col, POS_NO_COL, sizeof(U.col));
+        for (uint32_t j = 0; j < t; j++) {
+            U.slot[j] = in.in[j] == KZG_POSEIDON_IMM ? (uint8_t)POS_IMM : (uint8_t)slot_of(inputs.r[in.in[j]]);
+            poseidon_words(&cst[8 * (t * R + t * t + u * t + j)], in.imm_be32[j]);
+        }
+        for (uint32_t c = 0; c < in.n_out; c++) {
+            U.col[in.out[c]] = (uint8_t)c;
+            if (check) U.exp[c] = (uint8_t)slot_of(inputs.r[in.expect[c]]);
+        }
+    }
+    HIPCHK(ctx, A.qext.ensure(((size_t)nd + n_out) * T * 32 + (size_t)cw * 4));
+    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + nd * vw, *cdev = outv + n_out * vw, *mid = A.ntt_mid.as<uint32_t>();
+    uint8_t* rec = A.brec.as<uint8_t>();
+    uint64_t* st = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF);
+    for (uint32_t d = 0; d < nd; d++) {
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, distinct[d], src + d * vw, lg, tw, nullptr, mid);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(cdev, cst.data(), (size_t)cw * 4, hipMemcpyHostToDevice, A.stream));
+    HIPCHK(ctx, hipMemsetAsync(st, 0, 8 * (size_t)n_units, A.stream));
+    HIPCHK(ctx, hipMemsetAsync(st + n_units, 0xff, 8 * (size_t)n_units, A.stream));   // KZG_POSEIDON_NONE
+    tab.src = src;
+    tab.cst = cdev;
+    for (uint32_t u = 0, c = 0; u < n_units; u++) {
+        if (units[u].flags & KZG_POSEIDON_CHECK) continue;
+        tab.u[u].out = outv + c * vw;
+        if (units[u].mode == KZG_POSEIDON_ROUNDS) HIPCHK(ctx, hipMemsetAsync(outv + c * vw, 0, (size_t)t * T * 32, A.stream));
+        c += units[u].n_out;
+    }
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_poseidon(A.stream, tab, T, n, st);
+    }
+    for (uint32_t c = 0; c < n_out; c++) {
+        if (lay) {
+            Span sp(ctx, A, KZG_T_POLY);
+            launch_sort_tail(A.stream, outv + c * vw, T, n, lay->tail_be32 + 32 * (size_t)c * (T - n), A.flags());
+        }
+        const uint32_t* cf;
+        if (int rc = row_to_coeffs(ctx, A, outv + c * vw, T, 1, &cf, dst + c * vw)) return rc;
+    }
+    HIPCHK(ctx, hipGetLastError());
+    uint8_t ev[CNT_OFF + 16 * KZG_POSEIDON_MAX_UNITS + 32];
+    const uint32_t npairs = (CNT_OFF + 16 * n_units + 31) / 32;
+    if (int rc = multi_msms_finish(ctx, H, i, T, dst, n_out, 0, npairs, out_c48, ev, nullptr)) return rc;
+    memcpy(out_stats, ev + CNT_OFF, 16 * (size_t)n_units);
+    return KZG_OK;
+}
+
 // The expression columns (kzg_rows_commit_expr): a set built FROM sets, every output row plain arithmetic in source rows.
 // Each DISTINCT source row (by device pointer: two indices of a repeated handle name one row) that some term names is
 // transformed forward once into its own vector of the lane's quotient workspace; a row no term names is not transformed.

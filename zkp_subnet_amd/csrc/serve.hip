@@ -1548,6 +1548,120 @@ int rows_wide(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const u
     return KZG_OK;
 }
 
+// kzg_rows_commit_poseidon: the frame of rows_wide with the checks of rows_expr (no reservation and no set when every unit is a
+// check).  The parameters, the constants and immediates, modes, flags and out lists are checked here, on the host, before a
+// lane is taken
+int rows_poseidon(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                  const kzg_poseidon_params* params, uint32_t n_units, const kzg_poseidon_unit* units, const kzg_derive_opts* opts,
+                  uint8_t* out_commitments48, uint64_t* out_perms, uint64_t* out_mismatch, uint64_t* out_first_mismatch,
+                  uint64_t* out_handle) {
+    if (!ctx || !input_handles || !out_perms || !out_mismatch || !out_first_mismatch || !out_handle) return KZG_E_ARG;
+    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "poseidon: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (!params || !params->rc_be32 || !params->mds_be32)
+        return fail(ctx, KZG_E_ARG, "poseidon: params, rc_be32 and mds_be32 must not be null");
+    const uint32_t t = params->t, R = params->full + params->partial;
+    if (t < KZG_POSEIDON_MIN_T || t > KZG_POSEIDON_MAX_T) return fail(ctx, KZG_E_ARG, "poseidon: the width t must be in [2, 8]");
+    if (params->full < 2 || params->full > KZG_POSEIDON_MAX_FULL || (params->full & 1))
+        return fail(ctx, KZG_E_ARG, "poseidon: the number of full rounds R_F must be even and in [2, 16]");
+    if (params->partial > KZG_POSEIDON_MAX_PARTIAL)
+        return fail(ctx, KZG_E_ARG, "poseidon: the number of partial rounds R_P must be in [0, 128]");
+    if (n_units == 0 || n_units > KZG_POSEIDON_MAX_UNITS || !units)
+        return fail(ctx, KZG_E_ARG, "poseidon: n_units must be in [1, KZG_POSEIDON_MAX_UNITS]");
+    for (uint32_t k = 0; k < t * R; k++)
+        if (!fr_be32_canonical(params->rc_be32 + 32 * (size_t)k))
+            return fail(ctx, KZG_E_ARG, "poseidon: round constants must be canonical scalars (< r)");
+    for (uint32_t k = 0; k < t * t; k++)
+        if (!fr_be32_canonical(params->mds_be32 + 32 * (size_t)k))
+            return fail(ctx, KZG_E_ARG, "poseidon: matrix entries must be canonical scalars (< r)");
+    uint32_t n_out = 0, max_row = 0, n_seen = 0, seen[2 * KZG_POSEIDON_MAX_T * KZG_POSEIDON_MAX_UNITS];
+    auto see = [&](uint32_t row) {
+        max_row = std::max(max_row, row);
+        uint32_t d = 0;
+        while (d < n_seen && seen[d] != row) d++;
+        if (d == n_seen) seen[n_seen++] = row;
+    };
+    for (uint32_t u = 0; u < n_units; u++) {
+        const kzg_poseidon_unit& U = units[u];
+        if (U.mode != KZG_POSEIDON_ROW && U.mode != KZG_POSEIDON_ROUNDS)
+            return fail(ctx, KZG_E_ARG, "poseidon: unknown mode (KZG_POSEIDON_ROW or KZG_POSEIDON_ROUNDS)");
+        if (U.flags & ~KZG_POSEIDON_CHECK) return fail(ctx, KZG_E_ARG, "poseidon: flags must be 0 or KZG_POSEIDON_CHECK");
+        const bool rounds = U.mode == KZG_POSEIDON_ROUNDS, check = U.flags == KZG_POSEIDON_CHECK;
+        if (rounds && check) return fail(ctx, KZG_E_ARG, "poseidon: expect (KZG_POSEIDON_CHECK) belongs to ROW units, not to ROUNDS");
+        if (rounds ? U.period <= R : U.period != 0)
+            return fail(ctx, KZG_E_ARG, "poseidon: the period P of a ROUNDS unit must be at least R + 1 (0 on a ROW unit)");
+        if (rounds ? U.n_out != t : (U.n_out == 0 || U.n_out > t))
+            return fail(ctx, KZG_E_ARG, "poseidon: n_out must be in [1, t] on a ROW unit and t on a ROUNDS unit");
+        uint32_t taken = 0;
+        for (uint32_t c = 0; c < U.n_out; c++) {
+            if (U.out[c] >= t || (rounds && U.out[c] != c))
+                return fail(ctx, KZG_E_ARG, "poseidon: an out index must be below t (ROUNDS: out[j] = j)");
+            if (taken >> U.out[c] & 1) return fail(ctx, KZG_E_ARG, "poseidon: an out index is repeated");
+            taken |= 1u << U.out[c];
+            if (check) see(U.expect[c]);
+        }
+        for (uint32_t j = 0; j < t; j++) {
+            if (U.in[j] != KZG_POSEIDON_IMM) {
+                see(U.in[j]);
+                for (int b = 0; b < 32; b++)
+                    if (U.imm_be32[j][b]) return fail(ctx, KZG_E_ARG, "poseidon: the immediate must be 0 beside a row");
+            } else if (!fr_be32_canonical(U.imm_be32[j])) {
+                return fail(ctx, KZG_E_ARG, "poseidon: immediates must be canonical scalars (< r)");
+            }
+        }
+        if (n_seen > KZG_MAX_BATCH_OPEN)
+            return fail(ctx, KZG_E_ARG, "poseidon: a call reads at most KZG_MAX_BATCH_OPEN distinct input rows");
+        n_out += check ? 0 : U.n_out;
+    }
+    if (n_out > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "poseidon: n_out, the committed columns of all units, must be at most KZG_MAX_BATCH_OPEN");
+    if (n_out && !out_commitments48) return KZG_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RowsPending pend{ctx};
+    RowsRefs irefs{ctx};
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
+    Lane& L = H.L();
+    RowTab it;
+    uint32_t ki = 0, i = 0;
+    uint64_t T = 0;
+    if (int rc = rows_lookup(ctx, "poseidon", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    if (n_seen && max_row >= ki) return fail(ctx, KZG_E_ARG, "poseidon: a row must index the concatenated rows of the input sets");
+    int rc = check_worker(ctx, i, T);
+    if (rc) return rc;
+    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "poseidon: the row length must be a power of two");
+    if (T > ((uint64_t)1 << 32)) return fail(ctx, KZG_E_ARG, "poseidon: the row length must be at most 2^32");
+    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
+    if (lay.usable) {
+        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "poseidon: usable must be in [1, T - 1] (0: all T rows are read)");
+        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
+            return fail(ctx, KZG_E_ARG, "poseidon: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
+        if (n_out && !lay.tail_be32) return fail(ctx, KZG_E_ARG, "poseidon: tail_be32 must be given when usable > 0");
+        for (uint64_t j = 0; j < n_out * (T - lay.usable); j++)
+            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
+                return fail(ctx, KZG_E_ARG, "poseidon: tail scalars must be canonical (< r)");
+    } else if (lay.tail_be32) {
+        return fail(ctx, KZG_E_ARG, "poseidon: tail_be32 must be null in the plain layout (usable = 0)");
+    }
+    if (n_out)
+        if (int rc2 = rows_reserve(ctx, "poseidon", pend, (size_t)n_out * T * 32)) return rc2;
+    prof_begin(ctx, L);
+    rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    uint64_t stats[2 * KZG_POSEIDON_MAX_UNITS];
+    rc = rows_poseidon_dev(ctx, H, i, it, params, n_units, units, n_out, T, n_out ? pend.buf.as<uint32_t>() : nullptr, c48, stats,
+                           lay.usable ? &lay : nullptr);
+    if (rc) return rc;
+    if (n_out) memcpy(out_commitments48, c48, 48 * (size_t)n_out);
+    const uint64_t n = lay.usable ? lay.usable : T;
+    for (uint32_t u = 0; u < n_units; u++) out_perms[u] = units[u].mode == KZG_POSEIDON_ROUNDS ? n / units[u].period : n;
+    memcpy(out_mismatch, stats, 8 * (size_t)n_units);
+    memcpy(out_first_mismatch, stats + n_units, 8 * (size_t)n_units);
+    *out_handle = n_out ? rows_insert(ctx, pend, i, n_out, T) : 0;
+    return KZG_OK;
+}
+
 // kzg_rows_commit_expr: the lookups of an open (one handle list), the reservation of a commit of n_out rows -- none when every
 // expression is a check.  opts == NULL, or usable == 0: all T rows are evaluated.  Coefficients are checked here, on the host
 int rows_expr(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
@@ -2582,6 +2696,13 @@ int kzg_rows_commit_wide(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t*
                          uint64_t* out_first, uint64_t* out_qover, uint64_t* out_first_qover, uint64_t* out_handle) {
     return rows_wide(ctx, UINT32_MAX, n_input_handles, input_handles, n_ops, ops, opts, out_commitments48, out_counts, out_first,
                      out_qover, out_first_qover, out_handle);
+}
+int kzg_rows_commit_poseidon(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                             const kzg_poseidon_params* params, uint32_t n_units, const kzg_poseidon_unit* units,
+                             const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_perms, uint64_t* out_mismatch,
+                             uint64_t* out_first_mismatch, uint64_t* out_handle) {
+    return rows_poseidon(ctx, UINT32_MAX, n_input_handles, input_handles, params, n_units, units, opts, out_commitments48,
+                         out_perms, out_mismatch, out_first_mismatch, out_handle);
 }
 int kzg_rows_commit_expr(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
                          const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48, uint64_t* out_nonzero,

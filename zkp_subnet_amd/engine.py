@@ -1240,6 +1240,160 @@ class HipEngine:
                 {"counts": [int(v) for v in st[0]], "first": none(st[1]), "qover": [int(v) for v in st[2]],
                  "first_qover": none(st[3])})
 
+    # ---- a set built from sets: the Poseidon permutation (x^5, caller's constants) per row, as a check, or as a round trace
+    _POSEIDON_PARAM_KEYS = ("t", "full", "partial", "rc", "mds")
+    _POSEIDON_UNIT_KEYS = ("mode", "in", "out", "expect", "period")
+
+    @classmethod
+    def poseidon_call(cls, params, units, what: str = "commit_poseidon") -> Tuple[tuple, List[tuple]]:
+        """The kzg_poseidon_params fields (t, full, partial, rc bytes, mds bytes) and per unit the kzg_poseidon_unit fields
+        (mode, flags, n_out, period, in[8], out[8], expect[8], imm[8] of 32 bytes) of a call.  params: a mapping with t (2 .. 8),
+        full (R_F, even, 2 .. 16), partial (R_P, 0 .. 128), rc (t (R_F + R_P) scalars, round-major) and mds (t t scalars,
+        row-major).  A unit is a mapping: mode "row" with in (t entries), out (1 .. t distinct state indices) and, for a check,
+        expect (one row per entry of out); or mode "rounds" with in and period (at least R_F + R_P + 1).  An entry of in is a row
+        index or ("imm", value).  A scalar is an int, a decimal or 0x string, or 32 big-endian bytes, below r.  Raises
+        KzgError(KZG_E_ARG) with the cause; needs no device."""
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: poseidon: {why}")   # noqa: E731
+        is_u = lambda v, top: isinstance(v, int) and not isinstance(v, bool) and 0 <= v < top   # noqa: E731
+        r_mod = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
+
+        def scalar(v, name):
+            if isinstance(v, (bytes, bytearray)):
+                if len(v) != 32:
+                    raise bad(f"{name} given as bytes must be of 32 bytes")
+                v = int.from_bytes(v, "big")
+            elif isinstance(v, str):
+                try:
+                    v = int(v, 0)
+                except ValueError:
+                    raise bad(f"{name} must be an integer, a decimal or 0x string, or 32 bytes") from None
+            if not isinstance(v, int) or isinstance(v, bool) or v < 0:
+                raise bad(f"{name} must be a non-negative integer")
+            if v >= r_mod:
+                raise bad(f"{name} must be a canonical scalar (< r)")
+            return v.to_bytes(32, "big")
+
+        if not isinstance(params, dict) or set(params) != set(cls._POSEIDON_PARAM_KEYS):
+            raise bad(f"params is a mapping with exactly {', '.join(cls._POSEIDON_PARAM_KEYS)}")
+        t, full, partial = params["t"], params["full"], params["partial"]
+        if not is_u(t, _native.KZG_POSEIDON_MAX_T + 1) or t < _native.KZG_POSEIDON_MIN_T:
+            raise bad(f"the width t must be an integer in [{_native.KZG_POSEIDON_MIN_T}, {_native.KZG_POSEIDON_MAX_T}]")
+        if not is_u(full, _native.KZG_POSEIDON_MAX_FULL + 1) or full < 2 or full % 2:
+            raise bad(f"the number of full rounds R_F must be even and in [2, {_native.KZG_POSEIDON_MAX_FULL}]")
+        if not is_u(partial, _native.KZG_POSEIDON_MAX_PARTIAL + 1):
+            raise bad(f"the number of partial rounds R_P must be in [0, {_native.KZG_POSEIDON_MAX_PARTIAL}]")
+        R = full + partial
+        rc, mds = params["rc"], params["mds"]
+        if not isinstance(rc, (list, tuple)) or len(rc) != t * R:
+            raise bad(f"rc must be a list of t (R_F + R_P) = {t * R} scalars, round-major")
+        if not isinstance(mds, (list, tuple)) or len(mds) != t * t:
+            raise bad(f"mds must be a list of t t = {t * t} scalars, row-major")
+        rc_b = b"".join(scalar(v, "a round constant") for v in rc)
+        mds_b = b"".join(scalar(v, "a matrix entry") for v in mds)
+        units = list(units) if isinstance(units, (list, tuple)) else None
+        if not units or len(units) > _native.KZG_POSEIDON_MAX_UNITS:
+            raise bad(f"units must be a list of 1 .. {_native.KZG_POSEIDON_MAX_UNITS} entries (n_units)")
+        recs, seen = [], set()
+        for un in units:
+            if not isinstance(un, dict) or "mode" not in un or "in" not in un:
+                raise bad("a unit is a mapping with mode, in and the fields of its mode")
+            extra = set(un) - set(cls._POSEIDON_UNIT_KEYS)
+            if extra:
+                raise bad(f"unknown field {sorted(extra)[0]!r} (the fields are {', '.join(cls._POSEIDON_UNIT_KEYS)})")
+            mode = un["mode"]
+            if mode not in ("row", "rounds"):
+                raise bad(f'unknown mode {mode!r} (one of "row", "rounds")')
+            ins = un["in"]
+            if not isinstance(ins, (list, tuple)) or len(ins) != t:
+                raise bad(f"in must hold t = {t} entries, each a row index or (\"imm\", value)")
+            rows, imms = [], []
+            for v in ins:
+                if isinstance(v, (list, tuple)):
+                    if len(v) != 2 or v[0] != "imm":
+                        raise bad('an immediate is ("imm", value)')
+                    rows.append(_native.KZG_POSEIDON_IMM)
+                    imms.append(scalar(v[1], "an immediate"))
+                elif is_u(v, _native.KZG_POSEIDON_IMM):
+                    rows.append(v)
+                    imms.append(bytes(32))
+                    seen.add(v)
+                else:
+                    raise bad('an entry of in must be a row index, an integer in [0, 2^32 - 1), or ("imm", value)')
+            flags, period, expect = 0, 0, []
+            if mode == "rounds":
+                if un.get("expect") is not None:
+                    raise bad("expect belongs to row units, not to rounds")
+                if un.get("out") is not None:
+                    raise bad("out belongs to row units: a rounds unit commits all t columns")
+                period = un.get("period")
+                if not is_u(period, 1 << 32) or period < R + 1:
+                    raise bad(f"the period P of a rounds unit must be an integer in [R + 1, 2^32), R + 1 = {R + 1}")
+                out = list(range(t))
+            else:
+                if un.get("period") is not None:
+                    raise bad("period belongs to rounds units, not to row")
+                out = un.get("out")
+                if not isinstance(out, (list, tuple)) or not 1 <= len(out) <= t:
+                    raise bad(f"out must hold 1 .. t = {t} state indices")
+                if any(not is_u(j, t) for j in out):
+                    raise bad(f"an out index must be an integer below t = {t}")
+                if len(set(out)) != len(out):
+                    raise bad("an out index is repeated")
+                out = list(out)
+                if un.get("expect") is not None:
+                    expect = un["expect"]
+                    if not isinstance(expect, (list, tuple)) or len(expect) != len(out):
+                        raise bad("expect must hold one row per entry of out")
+                    if any(not is_u(j, _native.KZG_POSEIDON_IMM) for j in expect):
+                        raise bad("an entry of expect must be a row index, an integer in [0, 2^32 - 1)")
+                    expect = list(expect)
+                    seen.update(expect)
+                    flags = _native.KZG_POSEIDON_CHECK
+            pad = lambda xs: list(xs) + [0] * (8 - len(xs))   # noqa: E731
+            recs.append((_native.KZG_POSEIDON_ROW if mode == "row" else _native.KZG_POSEIDON_ROUNDS, flags, len(out), period,
+                         pad(rows), pad(out), pad(expect), imms + [bytes(32)] * (8 - t)))
+        if len(seen) > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"the units read {len(seen)} distinct input rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+        n_out = sum(r[2] for r in recs if not r[1])
+        if n_out > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"n_out: the units give {n_out} output rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+        return (t, full, partial, rc_b, mds_b), recs
+
+    @staticmethod
+    def poseidon_unit_struct(rec) -> "_native.PoseidonUnit":
+        u = _native.PoseidonUnit(rec[0], rec[1], rec[2], rec[3], (ctypes.c_uint32 * 8)(*rec[4]), (ctypes.c_uint32 * 8)(*rec[5]),
+                                 (ctypes.c_uint32 * 8)(*rec[6]))
+        for j, b in enumerate(rec[7]):
+            u.imm_be32[j][:] = list(b)
+        return u
+
+    def commit_poseidon(self, input_sets: Sequence[object], params: dict, units: Sequence[dict], usable: Optional[int] = None,
+                        tail: Sequence[bytes] = ()) -> Tuple[Optional["RowSet"], dict]:
+        """kzg_rows_commit_poseidon over the concatenated rows of input_sets (RowSet objects or bare handles).  params and units:
+        see poseidon_call.  The permutation is the plain Hades schedule with the S-box x^5: per round s_i += rc[rho t + i]; s_i
+        <- s_i^5 for every i in a full round, for i = 0 in a partial one; s <- M s.  A row unit hashes every row t' < n (n =
+        usable, or T) and commits one column per entry of out -- or, with expect, commits nothing and counts the rows whose
+        expected cells differ; a rounds unit commits the t columns of the round trace, one block of `period` rows per
+        permutation.  Returns (the new RowSet of all committed columns in unit order, or None when every unit is a check;
+        {"perms", "mismatch", "first_mismatch"} per unit).  usable and tail: as for commit_derived, the tail column-major over
+        the committed columns."""
+        what = "commit_poseidon"
+        ni, hi = self._handle_array(input_sets, what)
+        par, recs = self.poseidon_call(params, units, what)
+        n_out = sum(r[2] for r in recs if not r[1])
+        wi, T, lay = self._column_layout(what, input_sets, n_out, "n_out", "read", usable, tail)
+        opts = _native.DeriveOpts(*lay) if lay else None
+        pp = _native.PoseidonParams(*par)
+        arr = (_native.PoseidonUnit * len(recs))(*[self.poseidon_unit_struct(r) for r in recs])
+        c, h = ctypes.create_string_buffer(48 * max(n_out, 1)), ctypes.c_uint64(0)
+        st = [(ctypes.c_uint64 * len(recs))() for _ in range(3)]
+        self._chk(self._lib.kzg_rows_commit_poseidon(self._h, ni, hi, ctypes.byref(pp), len(recs), arr,
+                                                     ctypes.byref(opts) if opts is not None else None, c if n_out else None,
+                                                     st[0], st[1], st[2], ctypes.byref(h)))
+        rs = RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]) if n_out else None
+        return rs, {"perms": [int(v) for v in st[0]], "mismatch": [int(v) for v in st[1]],
+                    "first_mismatch": [None if int(v) == _native.KZG_POSEIDON_NONE else int(v) for v in st[2]]}
+
     # ---- a set built from sets: columns that are plain arithmetic in resident columns, and gates checked row by row
     def commit_expr(self, input_sets: Sequence[object], exprs: Sequence[Sequence], usable: Optional[int] = None,
                     tail: Sequence[bytes] = ()) -> Tuple[Optional["RowSet"], List[int], List[Optional[int]]]:

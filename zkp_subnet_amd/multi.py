@@ -233,6 +233,12 @@ class MultiDeviceClient:
     def worker_commit_wide(self, input_handles: Sequence[int], ops, usable=None, tail=()):
         return self._routed_builder("worker_commit_wide", [input_handles], input_handles, ops, usable, tail)
 
+    def worker_commit_poseidon(self, input_handles: Sequence[int], params, units, usable=None, tail=()):
+        r = self._routed_builder("worker_commit_poseidon", [input_handles], input_handles, params, units, usable, tail, key=None)
+        if r.status_code == 200 and r.json()["handle"] is not None:   # (a call of checks alone makes no set)
+            self._row_owner[int(r.json()["handle"])] = self._owner(list(input_handles))
+        return r
+
     def worker_commit_expr(self, input_handles: Sequence[int], exprs, usable=None, tail=()):
         r = self._routed_builder("worker_commit_expr", [input_handles], input_handles, exprs, usable, tail, key=None)
         if r.status_code == 200 and r.json()["handle"] is not None:   # (a call of checks alone makes no set)
