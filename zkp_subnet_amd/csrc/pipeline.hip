@@ -982,6 +982,86 @@ int rows_multiplicities_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab&
     return KZG_OK;
 }
 
+// ---- the device frame of the column builders (rows_sorted_dev, rows_derived_dev .. rows_fetch_dev): what every builder
+// does around the kernels of its own.  cols_begin -- [Sources: slot_of, transform] -- the builder's kernels -- emit_column per
+// output column -- stats_finish.
+
+// The statistics of a call are u64 words in the record's evaluation slots, behind the first two (which the derived call's
+// inversion uses as scratch and flag, the fetch call's join for its overrun word), and come back in the copy behind the MSM.
+constexpr uint32_t CNT_OFF = 64;
+constexpr uint32_t STATS_MAX = 16 * KZG_MAX_BATCH_OPEN;   // the largest user: a count and a first row for each of 16 ops
+static_assert(CNT_OFF + STATS_MAX <= MR_PAIRS * 32, "the statistics of the largest builder fit the record's evaluation slots");
+// what a builder's call works with: the lane's record, the forward twiddles and the transforms' scratch of T, the layout
+struct Cols {
+    uint64_t T, vw, n;    // the row length; one vector, in words; the rows that are read (usable, or T)
+    int lg;
+    uint32_t *tw, *mid, *dst;
+    uint8_t* rec;
+    const Blind* lay;
+    uint8_t ev[CNT_OFF + STATS_MAX + 32];   // the record's evaluation slots as stats_finish read them back
+};
+static int cols_begin(kzg_ctx* ctx, Lane& A, uint64_t T, const Blind* lay, uint32_t* dst, Cols& F) {
+    if (int rc = ensure_multi_record(ctx, A)) return rc;
+    F.T = T;
+    F.vw = T * 8;
+    F.n = lay ? lay->usable : T;
+    F.lg = ilog2_exact(T);
+    F.tw = nullptr;
+    if (int rc = ensure_twiddles(ctx, A, F.lg, 0, &F.tw, nullptr)) return rc;
+    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    F.mid = A.ntt_mid.as<uint32_t>();
+    F.dst = dst;
+    F.rec = A.brec.as<uint8_t>();
+    F.lay = lay;
+    return KZG_OK;
+}
+// The DISTINCT source rows of a call, by device pointer: several ops, both operands of one op, or two indices of a repeated
+// handle, may name one row, which is transformed once.  (Capacity: what the callers of the builders let through.)
+struct Sources {
+    static constexpr uint32_t CAP = 3 * ALU_MAX_UNITS;
+    static_assert(CAP >= POLY_MAX_ROWS && POLY_MAX_ROWS >= KZG_MAX_BATCH_OPEN, "every builder's distinct rows fit");
+    const uint32_t* distinct[CAP];
+    uint32_t nd = 0;
+    uint32_t slot_of(const uint32_t* p) {
+        uint32_t d = 0;
+        while (d < nd && distinct[d] != p) d++;
+        if (d == nd) distinct[nd++] = p;
+        return d;
+    }
+};
+// the forward transforms of the nd rows into the consecutive vectors at src
+static void sources_transform(kzg_ctx* ctx, Lane& A, const Cols& F, const Sources& S, uint32_t* src) {
+    for (uint32_t d = 0; d < S.nd; d++) {
+        Span sp(ctx, A, KZG_T_NTT);
+        launch_fr_ntt(A.stream, S.distinct[d], src + d * F.vw, F.lg, F.tw, nullptr, F.mid);
+    }
+}
+// the rows a plan's factors name, as indices into `inputs`, become slots of S
+static void plan_sources(ExprPlan& pl, const RowTab& inputs, Sources& S) {
+    for (uint32_t u = 0; u < pl.n_terms; u++)
+        for (uint32_t f = 0; f < pl.term_len[u]; f++) pl.term_row[u][f] = (uint8_t)S.slot_of(inputs.r[pl.term_row[u][f]]);
+}
+// output column c from the vector v: the caller's tail behind `usable` (launch_sort_tail: no closing row), then the inverse
+// transform straight into the new set's buffer
+static int emit_column(kzg_ctx* ctx, Lane& A, const Cols& F, uint32_t* v, uint32_t c) {
+    if (F.lay) {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_sort_tail(A.stream, v, F.T, F.n, F.lay->tail_be32 + 32 * (size_t)c * (F.T - F.n), A.flags());
+    }
+    const uint32_t* cf;
+    return row_to_coeffs(ctx, A, v, F.T, 1, &cf, F.dst + c * F.vw);
+}
+// The end of a call with `bytes` bytes of statistics: ONE MSM pass of n_out scalar sets (none for n_out = 0: the record's one
+// copy and its synchronisation are all that is left).  *stats: the bytes behind CNT_OFF; F.ev: the slots in front of them
+static int stats_finish(kzg_ctx* ctx, LaneHold& H, uint32_t i, Cols& F, uint32_t n_out, uint32_t bytes, uint8_t* out_c48,
+                        const uint8_t** stats) {
+    HIPCHK(ctx, hipGetLastError());
+    const uint32_t npairs = (CNT_OFF + bytes + 31) / 32;
+    if (int rc = multi_msms_finish(ctx, H, i, F.T, F.dst, n_out, 0, npairs, out_c48, F.ev, nullptr)) return rc;
+    *stats = F.ev + CNT_OFF;
+    return KZG_OK;
+}
+
 // The sorted columns (kzg_rows_commit_sorted): a set built FROM sets, the second side of a shuffle whose first side is these
 // columns.  All w columns of a row travel together, so the w columns are transformed into w vectors of T in the lane's quotient
 // workspace; behind them lie the n_keys key vectors (the key columns' canonical integers: fr_sort.hip) and, in the staging
@@ -994,23 +1074,19 @@ int rows_multiplicities_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab&
 int rows_sorted_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t width, uint32_t n_keys, uint64_t T,
                     uint32_t* dst, uint8_t* out_c48, const Blind* lay) {
     Lane& A = H.L();
-    if (int rc = ensure_multi_record(ctx, A)) return rc;
-    const int lg = ilog2_exact(T);
-    uint32_t* tw = nullptr;
-    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
-    const uint64_t vw = T * 8;                        // one vector, in words
-    const uint64_t n = lay ? lay->usable : T;         // the rows that are sorted
+    Cols F;
+    if (int rc = cols_begin(ctx, A, T, lay, dst, F)) return rc;
+    const uint64_t vw = F.vw, n = F.n;
     const uint32_t passes = 32 * n_keys;
     static_assert(32 * KZG_MAX_BATCH_OPEN * 4 <= 8192, "the skip words of every pass fit the lane's pinned page");
     HIPCHK(ctx, A.qext.ensure(((size_t)width + n_keys) * T * 32));
     HIPCHK(ctx, A.qstage.ensure(fr_sort_ws_words(n, n_keys) * 4));
     HIPCHK(ctx, A.coeffA.ensure(T * 32));
-    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
-    uint32_t *ev = A.qext.as<uint32_t>(), *keys = ev + (uint64_t)width * vw, *mid = A.ntt_mid.as<uint32_t>();
+    uint32_t *ev = A.qext.as<uint32_t>(), *keys = ev + (uint64_t)width * vw;
     uint32_t *ws = A.qstage.as<uint32_t>(), *out = A.coeffA.as<uint32_t>();
     for (uint32_t c = 0; c < width; c++) {
         Span sp(ctx, A, KZG_T_NTT);
-        launch_fr_ntt(A.stream, inputs.r[c], ev + c * vw, lg, tw, nullptr, mid);
+        launch_fr_ntt(A.stream, inputs.r[c], ev + c * vw, F.lg, F.tw, nullptr, F.mid);
     }
     {
         Span sp(ctx, A, KZG_T_POLY);
@@ -1093,8 +1169,7 @@ int rows_sigma_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& labels, 
     uint32_t* tw = nullptr;
     if (int rc = ensure_twiddles(ctx, A, ilog2_exact(T), 0, &tw, nullptr)) return rc;
     const uint64_t vw = T * 8, N = (uint64_t)k * n;
-    constexpr uint32_t CNT_OFF = 64;
-    static_assert(CNT_OFF + 16 <= MR_PAIRS * 32 && KZG_MAX_BATCH_OPEN <= SIGMA_MAX_COLS, "the counts fit the record");
+    static_assert(16 <= STATS_MAX && KZG_MAX_BATCH_OPEN <= SIGMA_MAX_COLS, "the counts fit the record");
     HIPCHK(ctx, A.qext.ensure(((size_t)k * T + N + (n != T ? T : 0)) * 32));
     HIPCHK(ctx, A.qstage.ensure(fr_sort_ws_words(N, 1) * 4));
     HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
@@ -1133,7 +1208,6 @@ int rows_check_copies_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& w
     uint32_t* tw = nullptr;
     if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
     const uint64_t vw = T * 8, N = (uint64_t)k * n;
-    constexpr uint32_t CNT_OFF = 64;
     const uint32_t* distinct[POLY_MAX_ROWS];
     uint32_t slot[POLY_MAX_ROWS], nd = 0;
     for (uint32_t c = 0; c < k; c++) {
@@ -1185,42 +1259,30 @@ int rows_check_copies_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& w
 int rows_derived_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_ops, const kzg_derive_op* ops,
                      uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_counts, const Blind* lay) {
     Lane& A = H.L();
-    if (int rc = ensure_multi_record(ctx, A)) return rc;
-    const int lg = ilog2_exact(T);
-    uint32_t* tw = nullptr;
-    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
-    const uint64_t vw = T * 8;                        // one vector, in words
-    const uint64_t n = lay ? lay->usable : T;         // the rows that are read
-    constexpr uint32_t CNT_OFF = 64;                  // the counts in the record: behind the inversion's scratch and flag
-    static_assert(CNT_OFF + 8 * KZG_MAX_BATCH_OPEN <= MR_PAIRS * 32 && KZG_MAX_BATCH_OPEN <= POLY_MAX_ROWS,
-                  "the counts of every op fit the record's evaluation slots");
-    const uint32_t* distinct[POLY_MAX_ROWS];
-    uint32_t slot[POLY_MAX_ROWS], inv_op[POLY_MAX_ROWS], nd = 0, n_inv = 0, longest = 0;
+    Cols F;
+    if (int rc = cols_begin(ctx, A, T, lay, dst, F)) return rc;
+    const uint64_t vw = F.vw, n = F.n;
+    static_assert(8 * KZG_MAX_BATCH_OPEN <= STATS_MAX && KZG_MAX_BATCH_OPEN <= POLY_MAX_ROWS,
+                  "the counts of every op (behind the inversion's scratch and flag) fit the record's evaluation slots");
+    Sources S;
+    uint32_t slot[POLY_MAX_ROWS], inv_op[POLY_MAX_ROWS], n_inv = 0, longest = 0;
     for (uint32_t o = 0; o < n_ops; o++) {
-        const uint32_t* p = inputs.r[ops[o].row];
-        uint32_t d = 0;
-        while (d < nd && distinct[d] != p) d++;
-        if (d == nd) distinct[nd++] = p;
-        slot[o] = d;
+        slot[o] = S.slot_of(inputs.r[ops[o].row]);
         if (ops[o].kind == KZG_DERIVE_INV0) inv_op[n_inv++] = o;
         longest = std::max(longest, ops[o].kind == KZG_DERIVE_INV0 ? ops[o].count - 1 : ops[o].count);
     }
     const uint32_t mw = inv0_mask_words(T), n_scratch = std::max(n_inv, longest);
-    HIPCHK(ctx, A.qext.ensure(((size_t)nd + n_inv + n_scratch) * T * 32));
+    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_inv + n_scratch) * T * 32));
     HIPCHK(ctx, A.qstage.ensure(((size_t)n_inv * mw + 4) * 4));
-    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
     if (n_inv) {
         HIPCHK(ctx, A.hbuf.ensure(poly_level_words(n_inv * T) * 4));
         HIPCHK(ctx, A.hnext.ensure(poly_level_words(n_inv * T) * 4));
     }
-    uint32_t *src = A.qext.as<uint32_t>(), *W = src + nd * vw, *Q = W + n_inv * vw, *scratch = Q;
-    uint32_t *mask = A.qstage.as<uint32_t>(), *mid = A.ntt_mid.as<uint32_t>();
-    uint8_t* rec = A.brec.as<uint8_t>();
+    uint32_t *src = A.qext.as<uint32_t>(), *W = src + S.nd * vw, *Q = W + n_inv * vw, *scratch = Q;
+    uint32_t* mask = A.qstage.as<uint32_t>();
+    uint8_t* rec = F.rec;
     uint64_t* cnt = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF);
-    for (uint32_t d = 0; d < nd; d++) {
-        Span sp(ctx, A, KZG_T_NTT);
-        launch_fr_ntt(A.stream, distinct[d], src + d * vw, lg, tw, nullptr, mid);
-    }
+    sources_transform(ctx, A, F, S, src);
     HIPCHK(ctx, hipMemsetAsync(rec + MR_EVAL, 0, CNT_OFF + 8 * (size_t)n_ops, A.stream));
     if (n_inv) {
         Span sp(ctx, A, KZG_T_POLY);
@@ -1231,14 +1293,7 @@ int rows_derived_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs
                             reinterpret_cast<uint32_t*>(rec + MR_EVAL + 32));
     }
     uint32_t c = 0;   // the next output column
-    auto emit = [&](uint32_t* v) -> int {
-        if (lay) {
-            Span sp(ctx, A, KZG_T_POLY);
-            launch_sort_tail(A.stream, v, T, n, lay->tail_be32 + 32 * (size_t)c * (T - n), A.flags());
-        }
-        const uint32_t* cf;
-        return row_to_coeffs(ctx, A, v, T, 1, &cf, dst + (c++) * vw);
-    };
+    auto emit = [&](uint32_t* v) { return emit_column(ctx, A, F, v, c++); };
     for (uint32_t o = 0, j = 0; o < n_ops; o++) {
         if (ops[o].kind == KZG_DERIVE_INV0) {
             uint32_t *inv = W + j * vw, *bit = ops[o].count == 2 ? scratch : nullptr;
@@ -1259,14 +1314,12 @@ int rows_derived_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs
                 if (int rc = emit(scratch + l * vw)) return rc;
         }
     }
-    HIPCHK(ctx, hipGetLastError());
-    uint8_t ev[CNT_OFF + 8 * KZG_MAX_BATCH_OPEN + 32];
-    const uint32_t npairs = (CNT_OFF + 8 * n_ops + 31) / 32;
-    if (int rc = multi_msms_finish(ctx, H, i, T, dst, n_out, 0, npairs, out_c48, ev, nullptr)) return rc;
+    const uint8_t* st;
+    if (int rc = stats_finish(ctx, H, i, F, n_out, 8 * n_ops, out_c48, &st)) return rc;
     uint32_t zf;
-    memcpy(&zf, ev + 32, 4);
+    memcpy(&zf, F.ev + 32, 4);
     if (zf) return fail(ctx, KZG_E_HIP, "derived: the batched inversion met a zero behind k_inv0_prepare");
-    memcpy(out_counts, ev + CNT_OFF, 8 * (size_t)n_ops);
+    memcpy(out_counts, st, 8 * (size_t)n_ops);
     return KZG_OK;
 }
 
@@ -1287,36 +1340,22 @@ int rows_derived_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs
 int rows_int_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_ops, const kzg_int_op* ops, uint32_t n_out,
                  uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_counts, uint64_t* out_first, const Blind* lay) {
     Lane& A = H.L();
-    if (int rc = ensure_multi_record(ctx, A)) return rc;
-    const int lg = ilog2_exact(T);
-    uint32_t* tw = nullptr;
-    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
-    const uint64_t vw = T * 8;                        // one vector, in words
-    const uint64_t n = lay ? lay->usable : T;         // the rows that are read
-    constexpr uint32_t CNT_OFF = 64;                  // the counts in the record, then the first rows
-    static_assert(CNT_OFF + 16 * KZG_MAX_BATCH_OPEN <= MR_PAIRS * 32 && KZG_MAX_BATCH_OPEN <= INT_MAX_OPS,
+    Cols F;
+    if (int rc = cols_begin(ctx, A, T, lay, dst, F)) return rc;
+    const uint64_t vw = F.vw, n = F.n;
+    static_assert(16 * KZG_MAX_BATCH_OPEN <= STATS_MAX && KZG_MAX_BATCH_OPEN <= INT_MAX_OPS,
                   "the count and the first row of every op fit the record's evaluation slots");
-    const uint32_t* distinct[POLY_MAX_ROWS];
-    uint32_t sa[INT_MAX_OPS], sb[INT_MAX_OPS], nd = 0;
-    auto slot_of = [&](const uint32_t* p) {
-        uint32_t d = 0;
-        while (d < nd && distinct[d] != p) d++;
-        if (d == nd) distinct[nd++] = p;
-        return d;
-    };
+    Sources S;
+    uint32_t sa[INT_MAX_OPS], sb[INT_MAX_OPS];
     for (uint32_t o = 0; o < n_ops; o++) {
-        sa[o] = slot_of(inputs.r[ops[o].a]);
-        sb[o] = (ops[o].flags & KZG_INT_IMM) ? UINT32_MAX : slot_of(inputs.r[ops[o].b]);
+        sa[o] = S.slot_of(inputs.r[ops[o].a]);
+        sb[o] = (ops[o].flags & KZG_INT_IMM) ? UINT32_MAX : S.slot_of(inputs.r[ops[o].b]);
     }
-    HIPCHK(ctx, A.qext.ensure(((size_t)nd + n_out) * T * 32));
-    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
-    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + nd * vw, *mid = A.ntt_mid.as<uint32_t>();
-    uint8_t* rec = A.brec.as<uint8_t>();
+    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_out) * T * 32));
+    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + S.nd * vw;
+    uint8_t* rec = F.rec;
     uint64_t *cnt = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF), *first = cnt + n_ops;
-    for (uint32_t d = 0; d < nd; d++) {
-        Span sp(ctx, A, KZG_T_NTT);
-        launch_fr_ntt(A.stream, distinct[d], src + d * vw, lg, tw, nullptr, mid);
-    }
+    sources_transform(ctx, A, F, S, src);
     HIPCHK(ctx, hipMemsetAsync(cnt, 0, 8 * (size_t)n_ops, A.stream));
     HIPCHK(ctx, hipMemsetAsync(first, 0xff, 8 * (size_t)n_ops, A.stream));   // KZG_INT_NONE
     IntTab tab;
@@ -1335,24 +1374,16 @@ int rows_int_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, ui
         Span sp(ctx, A, KZG_T_POLY);
         launch_int(A.stream, tab, n_ops, T, n, cnt, first);
     }
-    for (uint32_t c = 0; c < n_out; c++) {
-        if (lay) {
-            Span sp(ctx, A, KZG_T_POLY);
-            launch_sort_tail(A.stream, outv + c * vw, T, n, lay->tail_be32 + 32 * (size_t)c * (T - n), A.flags());
-        }
-        const uint32_t* cf;
-        if (int rc = row_to_coeffs(ctx, A, outv + c * vw, T, 1, &cf, dst + c * vw)) return rc;
-    }
-    HIPCHK(ctx, hipGetLastError());
-    uint8_t ev[CNT_OFF + 16 * KZG_MAX_BATCH_OPEN + 32];
-    const uint32_t npairs = (CNT_OFF + 16 * n_ops + 31) / 32;
-    if (int rc = multi_msms_finish(ctx, H, i, T, dst, n_out, 0, npairs, out_c48, ev, nullptr)) return rc;
-    memcpy(out_counts, ev + CNT_OFF, 8 * (size_t)n_ops);
-    memcpy(out_first, ev + CNT_OFF + 8 * (size_t)n_ops, 8 * (size_t)n_ops);
+    for (uint32_t c = 0; c < n_out; c++)
+        if (int rc = emit_column(ctx, A, F, outv + c * vw, c)) return rc;
+    const uint8_t* st;
+    if (int rc = stats_finish(ctx, H, i, F, n_out, 16 * n_ops, out_c48, &st)) return rc;
+    memcpy(out_counts, st, 8 * (size_t)n_ops);
+    memcpy(out_first, st + 8 * (size_t)n_ops, 8 * (size_t)n_ops);
     return KZG_OK;
 }
 
-// The ALU column with an op-code column (kzg_rows_commit_alu): the frame of rows_int_dev.  Each DISTINCT source row (by device
+// The ALU column with an op-code column (kzg_rows_commit_alu), in the builders' frame.  Each DISTINCT source row (by device
 // pointer: the op-code column and both operands of one unit, or rows of several units, may be one row) is transformed forward
 // once; column b of a unit is not transformed when every entry of the program has an immediate.
 //   step                      launches                         per call
@@ -1368,40 +1399,26 @@ int rows_alu_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, ui
                  uint32_t n_units, const kzg_alu_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48,
                  uint64_t* out_stats, const Blind* lay) {
     Lane& A = H.L();
-    if (int rc = ensure_multi_record(ctx, A)) return rc;
-    const int lg = ilog2_exact(T);
-    uint32_t* tw = nullptr;
-    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
-    const uint64_t vw = T * 8;                        // one vector, in words
-    const uint64_t n = lay ? lay->usable : T;         // the rows that are read
-    constexpr uint32_t CNT_OFF = 64;                  // the statistics in the record: counts, unknown, first, first unknown
-    static_assert(CNT_OFF + 32 * KZG_ALU_MAX_UNITS <= MR_PAIRS * 32 && 32 * KZG_ALU_MAX_UNITS == 16 * KZG_MAX_BATCH_OPEN &&
-                      KZG_ALU_MAX_UNITS == ALU_MAX_UNITS && KZG_ALU_MAX_PROGRAM == ALU_MAX_PROG,
-                  "the four statistics of every unit fit the record's evaluation slots, where rows_int_dev keeps two per op");
+    Cols F;
+    if (int rc = cols_begin(ctx, A, T, lay, dst, F)) return rc;
+    const uint64_t vw = F.vw, n = F.n;
+    static_assert(32 * KZG_ALU_MAX_UNITS <= STATS_MAX && KZG_ALU_MAX_UNITS == ALU_MAX_UNITS && KZG_ALU_MAX_PROGRAM == ALU_MAX_PROG,
+                  "the four statistics of every unit (counts, unknown, first, first unknown) fit the record's evaluation slots");
     bool needs_b = false;
     for (uint32_t e = 0; e < n_entries; e++) needs_b |= program[e].kind != KZG_ALU_IDLE && !(program[e].flags & KZG_ALU_IMM);
-    const uint32_t* distinct[3 * ALU_MAX_UNITS];
-    uint32_t so[ALU_MAX_UNITS], sa[ALU_MAX_UNITS], sb[ALU_MAX_UNITS], nd = 0;
-    auto slot_of = [&](const uint32_t* p) {
-        uint32_t d = 0;
-        while (d < nd && distinct[d] != p) d++;
-        if (d == nd) distinct[nd++] = p;
-        return d;
-    };
+    static_assert(3 * ALU_MAX_UNITS <= Sources::CAP, "the op-code column and both operands of every unit");
+    Sources S;
+    uint32_t so[ALU_MAX_UNITS], sa[ALU_MAX_UNITS], sb[ALU_MAX_UNITS];
     for (uint32_t u = 0; u < n_units; u++) {
-        so[u] = slot_of(inputs.r[units[u].op_row]);
-        sa[u] = slot_of(inputs.r[units[u].a]);
-        sb[u] = needs_b ? slot_of(inputs.r[units[u].b]) : UINT32_MAX;
+        so[u] = S.slot_of(inputs.r[units[u].op_row]);
+        sa[u] = S.slot_of(inputs.r[units[u].a]);
+        sb[u] = needs_b ? S.slot_of(inputs.r[units[u].b]) : UINT32_MAX;
     }
-    HIPCHK(ctx, A.qext.ensure(((size_t)nd + n_out) * T * 32));
-    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
-    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + nd * vw, *mid = A.ntt_mid.as<uint32_t>();
-    uint8_t* rec = A.brec.as<uint8_t>();
+    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_out) * T * 32));
+    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + S.nd * vw;
+    uint8_t* rec = F.rec;
     uint64_t* st = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF);
-    for (uint32_t d = 0; d < nd; d++) {
-        Span sp(ctx, A, KZG_T_NTT);
-        launch_fr_ntt(A.stream, distinct[d], src + d * vw, lg, tw, nullptr, mid);
-    }
+    sources_transform(ctx, A, F, S, src);
     HIPCHK(ctx, hipMemsetAsync(st, 0, 16 * (size_t)n_units, A.stream));
     HIPCHK(ctx, hipMemsetAsync(st + 2 * n_units, 0xff, 16 * (size_t)n_units, A.stream));   // KZG_ALU_NONE
     AluTab tab;
@@ -1423,23 +1440,15 @@ int rows_alu_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, ui
         Span sp(ctx, A, KZG_T_POLY);
         launch_alu(A.stream, tab, n_entries, n_units, T, n, st);
     }
-    for (uint32_t c = 0; c < n_out; c++) {
-        if (lay) {
-            Span sp(ctx, A, KZG_T_POLY);
-            launch_sort_tail(A.stream, outv + c * vw, T, n, lay->tail_be32 + 32 * (size_t)c * (T - n), A.flags());
-        }
-        const uint32_t* cf;
-        if (int rc = row_to_coeffs(ctx, A, outv + c * vw, T, 1, &cf, dst + c * vw)) return rc;
-    }
-    HIPCHK(ctx, hipGetLastError());
-    uint8_t ev[CNT_OFF + 32 * KZG_ALU_MAX_UNITS + 32];
-    const uint32_t npairs = (CNT_OFF + 32 * n_units + 31) / 32;
-    if (int rc = multi_msms_finish(ctx, H, i, T, dst, n_out, 0, npairs, out_c48, ev, nullptr)) return rc;
-    memcpy(out_stats, ev + CNT_OFF, 32 * (size_t)n_units);
+    for (uint32_t c = 0; c < n_out; c++)
+        if (int rc = emit_column(ctx, A, F, outv + c * vw, c)) return rc;
+    const uint8_t* stats;
+    if (int rc = stats_finish(ctx, H, i, F, n_out, 32 * n_units, out_c48, &stats)) return rc;
+    memcpy(out_stats, stats, 32 * (size_t)n_units);
     return KZG_OK;
 }
 
-// The multi-limb integer columns (kzg_rows_commit_wide): the frame of rows_int_dev.  Each DISTINCT source row (by device
+// The multi-limb integer columns (kzg_rows_commit_wide), in the builders' frame.  Each DISTINCT source row (by device
 // pointer) among the limb rows that some operand names is transformed forward once; an operand is the list of its limbs' slots.
 //   step                      launches                         per call
 //   forward transforms        launch_fr_ntt                    one per distinct source row named
@@ -1457,24 +1466,12 @@ static void wide_words(uint32_t w[16], const uint8_t be64[64]) {
 int rows_wide_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_ops, const kzg_wide_op* ops,
                   uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_stats, const Blind* lay) {
     Lane& A = H.L();
-    if (int rc = ensure_multi_record(ctx, A)) return rc;
-    const int lg = ilog2_exact(T);
-    uint32_t* tw = nullptr;
-    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
-    const uint64_t vw = T * 8;                        // one vector, in words
-    const uint64_t n = lay ? lay->usable : T;         // the rows that are read
-    constexpr uint32_t CNT_OFF = 64;                  // the statistics in the record: counts, qover, first, first qover
-    static_assert(CNT_OFF + 32 * KZG_WIDE_MAX_OPS <= MR_PAIRS * 32 && KZG_WIDE_MAX_OPS == WIDE_MAX_OPS &&
-                      KZG_WIDE_MAX_LIMBS == WIDE_MAX_LIMBS,
-                  "the four statistics of every op fit the record's evaluation slots");
-    const uint32_t* distinct[POLY_MAX_ROWS];
-    uint32_t nd = 0;
-    auto slot_of = [&](const uint32_t* p) {
-        uint32_t d = 0;
-        while (d < nd && distinct[d] != p) d++;
-        if (d == nd) distinct[nd++] = p;
-        return d;
-    };
+    Cols F;
+    if (int rc = cols_begin(ctx, A, T, lay, dst, F)) return rc;
+    const uint64_t vw = F.vw, n = F.n;
+    static_assert(32 * KZG_WIDE_MAX_OPS <= STATS_MAX && KZG_WIDE_MAX_OPS == WIDE_MAX_OPS && KZG_WIDE_MAX_LIMBS == WIDE_MAX_LIMBS,
+                  "the four statistics of every op (counts, qover, first, first qover) fit the record's evaluation slots");
+    Sources S;
     WideTab tab;
     memset(&tab, 0, sizeof(tab));
     for (uint32_t o = 0; o < n_ops; o++) {
@@ -1483,7 +1480,7 @@ int rows_wide_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, u
         const uint32_t first[5] = {in.a, in.b, in.c, in.q, in.r};
         for (int w = 0; w < 5; w++)
             for (uint32_t l = 0; l < in.limbs && first[w] != KZG_WIDE_ABSENT; l++)
-                op.slot[w][l] = (uint8_t)slot_of(inputs.r[first[w] + l]);
+                op.slot[w][l] = (uint8_t)S.slot_of(inputs.r[first[w] + l]);
         op.kind = in.kind;
         op.bits = in.bits;
         op.limbs = in.limbs;
@@ -1498,15 +1495,11 @@ int rows_wide_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, u
         if (in.b == KZG_WIDE_ABSENT && !(in.flags & KZG_WIDE_IMM_B)) op.imm[0] = 1;   // no b: a times 1
         wide_words(op.m, in.m_be64);
     }
-    HIPCHK(ctx, A.qext.ensure(((size_t)nd + n_out) * T * 32));
-    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
-    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + nd * vw, *mid = A.ntt_mid.as<uint32_t>();
-    uint8_t* rec = A.brec.as<uint8_t>();
+    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_out) * T * 32));
+    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + S.nd * vw;
+    uint8_t* rec = F.rec;
     uint64_t* st = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF);
-    for (uint32_t d = 0; d < nd; d++) {
-        Span sp(ctx, A, KZG_T_NTT);
-        launch_fr_ntt(A.stream, distinct[d], src + d * vw, lg, tw, nullptr, mid);
-    }
+    sources_transform(ctx, A, F, S, src);
     HIPCHK(ctx, hipMemsetAsync(st, 0, 16 * (size_t)n_ops, A.stream));
     HIPCHK(ctx, hipMemsetAsync(st + 2 * n_ops, 0xff, 16 * (size_t)n_ops, A.stream));   // KZG_INT_NONE
     tab.src = src;
@@ -1515,23 +1508,15 @@ int rows_wide_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, u
         Span sp(ctx, A, KZG_T_POLY);
         launch_wide(A.stream, tab, n_ops, T, n, st);
     }
-    for (uint32_t c = 0; c < n_out; c++) {
-        if (lay) {
-            Span sp(ctx, A, KZG_T_POLY);
-            launch_sort_tail(A.stream, outv + c * vw, T, n, lay->tail_be32 + 32 * (size_t)c * (T - n), A.flags());
-        }
-        const uint32_t* cf;
-        if (int rc = row_to_coeffs(ctx, A, outv + c * vw, T, 1, &cf, dst + c * vw)) return rc;
-    }
-    HIPCHK(ctx, hipGetLastError());
-    uint8_t ev[CNT_OFF + 32 * KZG_WIDE_MAX_OPS + 32];
-    const uint32_t npairs = (CNT_OFF + 32 * n_ops + 31) / 32;
-    if (int rc = multi_msms_finish(ctx, H, i, T, dst, n_out, 0, npairs, out_c48, ev, nullptr)) return rc;
-    memcpy(out_stats, ev + CNT_OFF, 32 * (size_t)n_ops);
+    for (uint32_t c = 0; c < n_out; c++)
+        if (int rc = emit_column(ctx, A, F, outv + c * vw, c)) return rc;
+    const uint8_t* stats;
+    if (int rc = stats_finish(ctx, H, i, F, n_out, 32 * n_ops, out_c48, &stats)) return rc;
+    memcpy(out_stats, stats, 32 * (size_t)n_ops);
     return KZG_OK;
 }
 
-// The Poseidon permutation columns (kzg_rows_commit_poseidon): the frame of rows_wide_dev, with the checks of rows_expr_dev.
+// The Poseidon permutation columns (kzg_rows_commit_poseidon), in the builders' frame, with checks as rows_expr_dev has them.
 // Each DISTINCT source row (by device pointer) that some unit reads or expects is transformed forward once.
 //   step                      launches                         per call
 //   forward transforms        launch_fr_ntt                    one per distinct source row named
@@ -1553,26 +1538,16 @@ int rows_poseidon_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& input
                       uint32_t n_units, const kzg_poseidon_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst,
                       uint8_t* out_c48, uint64_t* out_stats, const Blind* lay) {
     Lane& A = H.L();
-    if (int rc = ensure_multi_record(ctx, A)) return rc;
-    const int lg = ilog2_exact(T);
-    uint32_t* tw = nullptr;
-    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
-    const uint64_t vw = T * 8;                        // one vector, in words
-    const uint64_t n = lay ? lay->usable : T;         // the rows that are read
-    constexpr uint32_t CNT_OFF = 64;                  // the statistics in the record: mismatches, then the first rows
-    static_assert(CNT_OFF + 16 * KZG_POSEIDON_MAX_UNITS <= MR_PAIRS * 32 && KZG_POSEIDON_MAX_UNITS == POS_MAX_UNITS &&
+    Cols F;
+    if (int rc = cols_begin(ctx, A, T, lay, dst, F)) return rc;
+    const uint64_t vw = F.vw, n = F.n;
+    static_assert(16 * KZG_POSEIDON_MAX_UNITS <= STATS_MAX && KZG_POSEIDON_MAX_UNITS == POS_MAX_UNITS &&
                       KZG_POSEIDON_MAX_T == POS_MAX_T && KZG_POSEIDON_MAX_FULL + KZG_POSEIDON_MAX_PARTIAL == POS_MAX_ROUNDS &&
                       KZG_POSEIDON_ROW == POS_ROW && KZG_POSEIDON_ROUNDS == POS_ROUNDS,
-                  "the two statistics of every unit fit the record's evaluation slots; the header's caps are the kernel's");
+                  "the two statistics of every unit (mismatches, then the first rows) fit the record's evaluation slots; the "
+                  "header's caps are the kernel's");
     const uint32_t t = params->t, R = params->full + params->partial;
-    const uint32_t* distinct[POLY_MAX_ROWS];
-    uint32_t nd = 0;
-    auto slot_of = [&](const uint32_t* p) {
-        uint32_t d = 0;
-        while (d < nd && distinct[d] != p) d++;
-        if (d == nd) distinct[nd++] = p;
-        return d;
-    };
+    Sources S;
     PosTab tab;
     memset(&tab, 0, sizeof(tab));
     tab.t = t;
@@ -1591,23 +1566,19 @@ int rows_poseidon_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& input
         U.period = in.period;
         memset(U.col, POS_NO_COL, sizeof(U.col));
         for (uint32_t j = 0; j < t; j++) {
-            U.slot[j] = in.in[j] == KZG_POSEIDON_IMM ? (uint8_t)POS_IMM : (uint8_t)slot_of(inputs.r[in.in[j]]);
+            U.slot[j] = in.in[j] == KZG_POSEIDON_IMM ? (uint8_t)POS_IMM : (uint8_t)S.slot_of(inputs.r[in.in[j]]);
             poseidon_words(&cst[8 * (t * R + t * t + u * t + j)], in.imm_be32[j]);
         }
         for (uint32_t c = 0; c < in.n_out; c++) {
             U.col[in.out[c]] = (uint8_t)c;
-            if (check) U.exp[c] = (uint8_t)slot_of(inputs.r[in.expect[c]]);
+            if (check) U.exp[c] = (uint8_t)S.slot_of(inputs.r[in.expect[c]]);
         }
     }
-    HIPCHK(ctx, A.qext.ensure(((size_t)nd + n_out) * T * 32 + (size_t)cw * 4));
-    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
-    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + nd * vw, *cdev = outv + n_out * vw, *mid = A.ntt_mid.as<uint32_t>();
-    uint8_t* rec = A.brec.as<uint8_t>();
+    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_out) * T * 32 + (size_t)cw * 4));
+    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + S.nd * vw, *cdev = outv + n_out * vw;
+    uint8_t* rec = F.rec;
     uint64_t* st = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF);
-    for (uint32_t d = 0; d < nd; d++) {
-        Span sp(ctx, A, KZG_T_NTT);
-        launch_fr_ntt(A.stream, distinct[d], src + d * vw, lg, tw, nullptr, mid);
-    }
+    sources_transform(ctx, A, F, S, src);
     HIPCHK(ctx, hipMemcpyAsync(cdev, cst.data(), (size_t)cw * 4, hipMemcpyHostToDevice, A.stream));
     HIPCHK(ctx, hipMemsetAsync(st, 0, 8 * (size_t)n_units, A.stream));
     HIPCHK(ctx, hipMemsetAsync(st + n_units, 0xff, 8 * (size_t)n_units, A.stream));   // KZG_POSEIDON_NONE
@@ -1623,19 +1594,11 @@ int rows_poseidon_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& input
         Span sp(ctx, A, KZG_T_POLY);
         launch_poseidon(A.stream, tab, T, n, st);
     }
-    for (uint32_t c = 0; c < n_out; c++) {
-        if (lay) {
-            Span sp(ctx, A, KZG_T_POLY);
-            launch_sort_tail(A.stream, outv + c * vw, T, n, lay->tail_be32 + 32 * (size_t)c * (T - n), A.flags());
-        }
-        const uint32_t* cf;
-        if (int rc = row_to_coeffs(ctx, A, outv + c * vw, T, 1, &cf, dst + c * vw)) return rc;
-    }
-    HIPCHK(ctx, hipGetLastError());
-    uint8_t ev[CNT_OFF + 16 * KZG_POSEIDON_MAX_UNITS + 32];
-    const uint32_t npairs = (CNT_OFF + 16 * n_units + 31) / 32;
-    if (int rc = multi_msms_finish(ctx, H, i, T, dst, n_out, 0, npairs, out_c48, ev, nullptr)) return rc;
-    memcpy(out_stats, ev + CNT_OFF, 16 * (size_t)n_units);
+    for (uint32_t c = 0; c < n_out; c++)
+        if (int rc = emit_column(ctx, A, F, outv + c * vw, c)) return rc;
+    const uint8_t* stats;
+    if (int rc = stats_finish(ctx, H, i, F, n_out, 16 * n_units, out_c48, &stats)) return rc;
+    memcpy(out_stats, stats, 16 * (size_t)n_units);
     return KZG_OK;
 }
 
@@ -1658,42 +1621,25 @@ int rows_expr_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, u
                   const uint8_t* is_check, uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_nonzero,
                   uint64_t* out_first, const Blind* lay) {
     Lane& A = H.L();
-    if (int rc = ensure_multi_record(ctx, A)) return rc;
-    const int lg = ilog2_exact(T);
-    uint32_t* tw = nullptr;
-    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
-    const uint64_t vw = T * 8;                        // one vector, in words
-    const uint64_t n = lay ? lay->usable : T;         // the rows that are evaluated
-    constexpr uint32_t CNT_OFF = 64;                  // the counts in the record, then the first indices
-    static_assert(CNT_OFF + 16 * KZG_MAX_BATCH_OPEN <= MR_PAIRS * 32 && KZG_MAX_BATCH_OPEN <= POLY_MAX_ROWS,
+    Cols F;
+    if (int rc = cols_begin(ctx, A, T, lay, dst, F)) return rc;
+    const uint64_t vw = F.vw, n = F.n;
+    static_assert(16 * KZG_MAX_BATCH_OPEN <= STATS_MAX && KZG_MAX_BATCH_OPEN <= POLY_MAX_ROWS,
                   "the count and the first index of every expression fit the record's evaluation slots");
     static_assert(KZG_MAX_GATE_TERMS == EXPR_MAX_TERMS && KZG_MAX_EXPR_FACTORS == EXPR_MAX_FACTORS, "the header's caps are the kernel's");
-    const uint32_t* distinct[POLY_MAX_ROWS];
-    uint32_t nd = 0;
+    Sources S;
     ExprPlan plan[KZG_MAX_BATCH_OPEN];
     for (uint32_t e = 0; e < n_exprs; e++) {
         plan[e] = exprs[e];
-        for (uint32_t u = 0; u < plan[e].n_terms; u++)
-            for (uint32_t f = 0; f < plan[e].term_len[u]; f++) {
-                const uint32_t* p = inputs.r[plan[e].term_row[u][f]];
-                uint32_t d = 0;
-                while (d < nd && distinct[d] != p) d++;
-                if (d == nd) distinct[nd++] = p;
-                plan[e].term_row[u][f] = (uint8_t)d;
-            }
+        plan_sources(plan[e], inputs, S);
     }
-    HIPCHK(ctx, A.qext.ensure(((size_t)nd + 1) * T * 32));
-    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
-    uint32_t *src = A.qext.as<uint32_t>(), *scratch = src + nd * vw, *mid = A.ntt_mid.as<uint32_t>();
-    uint8_t* rec = A.brec.as<uint8_t>();
-    uint64_t *cnt = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF), *first = cnt + n_exprs;
+    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + 1) * T * 32));
+    uint32_t *src = A.qext.as<uint32_t>(), *scratch = src + S.nd * vw;
+    uint64_t *cnt = reinterpret_cast<uint64_t*>(F.rec + MR_EVAL + CNT_OFF), *first = cnt + n_exprs;
     RowTab st;
     memset(&st, 0, sizeof(st));
-    for (uint32_t d = 0; d < nd; d++) {
-        Span sp(ctx, A, KZG_T_NTT);
-        launch_fr_ntt(A.stream, distinct[d], src + d * vw, lg, tw, nullptr, mid);
-        st.r[d] = src + d * vw;
-    }
+    sources_transform(ctx, A, F, S, src);
+    for (uint32_t d = 0; d < S.nd; d++) st.r[d] = src + d * vw;
     HIPCHK(ctx, hipMemsetAsync(cnt, 0, 8 * (size_t)n_exprs, A.stream));
     HIPCHK(ctx, hipMemsetAsync(first, 0xff, 8 * (size_t)n_exprs, A.stream));   // KZG_EXPR_NONE
     for (uint32_t e = 0, c = 0; e < n_exprs; e++) {
@@ -1702,19 +1648,12 @@ int rows_expr_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, u
             launch_expr(A.stream, st, plan[e], is_check[e] ? nullptr : scratch, T, n, cnt + e, first + e);
         }
         if (is_check[e]) continue;
-        if (lay) {
-            Span sp(ctx, A, KZG_T_POLY);
-            launch_sort_tail(A.stream, scratch, T, n, lay->tail_be32 + 32 * (size_t)c * (T - n), A.flags());
-        }
-        const uint32_t* cf;
-        if (int rc = row_to_coeffs(ctx, A, scratch, T, 1, &cf, dst + (c++) * vw)) return rc;
+        if (int rc = emit_column(ctx, A, F, scratch, c++)) return rc;
     }
-    HIPCHK(ctx, hipGetLastError());
-    uint8_t ev[CNT_OFF + 16 * KZG_MAX_BATCH_OPEN + 32];
-    const uint32_t npairs = (CNT_OFF + 16 * n_exprs + 31) / 32;
-    if (int rc = multi_msms_finish(ctx, H, i, T, dst, n_out, 0, npairs, out_c48, ev, nullptr)) return rc;
-    memcpy(out_nonzero, ev + CNT_OFF, 8 * (size_t)n_exprs);
-    memcpy(out_first, ev + CNT_OFF + 8 * (size_t)n_exprs, 8 * (size_t)n_exprs);
+    const uint8_t* stats;
+    if (int rc = stats_finish(ctx, H, i, F, n_out, 16 * n_exprs, out_c48, &stats)) return rc;
+    memcpy(out_nonzero, stats, 8 * (size_t)n_exprs);
+    memcpy(out_first, stats + 8 * (size_t)n_exprs, 8 * (size_t)n_exprs);
     return KZG_OK;
 }
 
@@ -1736,20 +1675,16 @@ int rows_expr_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, u
 int rows_recur_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_recs, const RecurSpec* recs, uint64_t T,
                    uint32_t* dst, uint8_t* out_c48, uint8_t* out_closing32, const Blind* lay) {
     Lane& A = H.L();
-    if (int rc = ensure_multi_record(ctx, A)) return rc;
-    const int lg = ilog2_exact(T);
-    uint32_t* tw = nullptr;
-    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
-    const uint64_t vw = T * 8;                        // one vector, in words
-    const uint64_t n = lay ? lay->usable : T;         // the steps of the recurrence: rows 0 .. n - 1 are v[0] .. v[n - 1]
+    Cols F;
+    if (int rc = cols_begin(ctx, A, T, lay, dst, F)) return rc;
+    const uint64_t vw = F.vw, n = F.n;   // n: the steps of the recurrence, rows 0 .. n - 1 are v[0] .. v[n - 1]
     constexpr uint32_t DUMP_OFF = 32 * KZG_MAX_BATCH_OPEN;   // launch_expr's counters, behind the closings
     static_assert(DUMP_OFF + 16 <= MR_PAIRS * 32 && KZG_MAX_BATCH_OPEN <= POLY_MAX_ROWS,
                   "the closing of every recurrence and the two spare words fit the record's evaluation slots");
     static_assert(KZG_MAX_GATE_TERMS == EXPR_MAX_TERMS && KZG_MAX_EXPR_FACTORS == EXPR_MAX_FACTORS, "the header's caps are the kernel's");
     static const uint8_t ONE_BE[32] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
     static const uint8_t ZERO_BE[32] = {};
-    const uint32_t* distinct[POLY_MAX_ROWS];
-    uint32_t nd = 0;
+    Sources S;
     ExprPlan plan[KZG_MAX_BATCH_OPEN][2];
     for (uint32_t e = 0; e < n_recs; e++)
         for (int side = 0; side < 2; side++) {
@@ -1760,29 +1695,18 @@ int rows_recur_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, 
                 pl.n_terms = 1;
                 pl.coeffs_be32 = side ? ZERO_BE : ONE_BE;
             }
-            for (uint32_t u = 0; u < pl.n_terms; u++)
-                for (uint32_t f = 0; f < pl.term_len[u]; f++) {
-                    const uint32_t* p = inputs.r[pl.term_row[u][f]];
-                    uint32_t d = 0;
-                    while (d < nd && distinct[d] != p) d++;
-                    if (d == nd) distinct[nd++] = p;
-                    pl.term_row[u][f] = (uint8_t)d;
-                }
+            plan_sources(pl, inputs, S);
         }
-    HIPCHK(ctx, A.qext.ensure(((size_t)nd + 3) * T * 32));
-    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
+    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + 3) * T * 32));
     HIPCHK(ctx, A.hbuf.ensure(recur_level_elems(n) * 32));
     HIPCHK(ctx, A.hnext.ensure(recur_level_elems(n) * 32));
-    uint32_t *src = A.qext.as<uint32_t>(), *va = src + nd * vw, *vb = va + vw, *out = vb + vw, *mid = A.ntt_mid.as<uint32_t>();
-    uint8_t* rec = A.brec.as<uint8_t>();
+    uint32_t *src = A.qext.as<uint32_t>(), *va = src + S.nd * vw, *vb = va + vw, *out = vb + vw;
+    uint8_t* rec = F.rec;
     uint64_t* dump = reinterpret_cast<uint64_t*>(rec + MR_EVAL + DUMP_OFF);
     RowTab st;
     memset(&st, 0, sizeof(st));
-    for (uint32_t d = 0; d < nd; d++) {
-        Span sp(ctx, A, KZG_T_NTT);
-        launch_fr_ntt(A.stream, distinct[d], src + d * vw, lg, tw, nullptr, mid);
-        st.r[d] = src + d * vw;
-    }
+    sources_transform(ctx, A, F, S, src);
+    for (uint32_t d = 0; d < S.nd; d++) st.r[d] = src + d * vw;
     HIPCHK(ctx, hipMemsetAsync(dump, 0, 16, A.stream));
     for (uint32_t e = 0; e < n_recs; e++) {
         {
@@ -1819,28 +1743,24 @@ int rows_fetch_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, 
                    uint32_t n_keys, uint32_t w_tab, bool index, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_missing,
                    uint64_t* out_first, bool* out_overrun, const Blind* lay) {
     Lane& A = H.L();
-    if (int rc = ensure_multi_record(ctx, A)) return rc;
-    const int lg = ilog2_exact(T);
-    uint32_t* tw = nullptr;
-    if (int rc = ensure_twiddles(ctx, A, lg, 0, &tw, nullptr)) return rc;
-    const uint64_t vw = T * 8;                        // one vector, in words
-    const uint64_t n = lay ? lay->usable : T;         // the cells that are read and the table rows that can answer
+    Cols F;
+    if (int rc = cols_begin(ctx, A, T, lay, dst, F)) return rc;
+    const uint64_t vw = F.vw, n = F.n;   // n: the cells that are read and the table rows that can answer
     const uint32_t n_in = n_keys ? n_keys : 1, n_pay = w_tab - n_keys, n_per = n_pay + (index ? 1u : 0u), n_out = n_reads * n_per;
     const uint32_t cap = (uint32_t)(2 * T);           // slots: a power of two, load <= 1 / 2 (T <= 2^27: the caller)
-    constexpr uint32_t CNT_OFF = 64, OVR_OFF = 32;    // the counts in the record, then the first indices; the overrun word
-    static_assert(CNT_OFF + 16 * KZG_MAX_BATCH_OPEN <= MR_PAIRS * 32 && KZG_MAX_BATCH_OPEN <= POLY_MAX_ROWS,
+    constexpr uint32_t OVR_OFF = 32;                  // the overrun word, in front of the counts and the first indices
+    static_assert(16 * KZG_MAX_BATCH_OPEN <= STATS_MAX && KZG_MAX_BATCH_OPEN <= POLY_MAX_ROWS,
                   "the count and the first index of every read fit the record's evaluation slots");
     HIPCHK(ctx, A.qext.ensure(((size_t)w_tab + n_in + n_per) * T * 32));
     if (n_keys) HIPCHK(ctx, A.qstage.ensure((size_t)cap * 4));
-    HIPCHK(ctx, A.ntt_mid.ensure(T * 48));
     uint32_t *tab = A.qext.as<uint32_t>(), *in = tab + (uint64_t)w_tab * vw, *out = in + (uint64_t)n_in * vw;
-    uint32_t *mid = A.ntt_mid.as<uint32_t>(), *slots = n_keys ? A.qstage.as<uint32_t>() : nullptr;
-    uint8_t* rec = A.brec.as<uint8_t>();
+    uint32_t* slots = n_keys ? A.qstage.as<uint32_t>() : nullptr;
+    uint8_t* rec = F.rec;
     uint64_t *cnt = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF), *first = cnt + n_reads;
     uint32_t* overrun = reinterpret_cast<uint32_t*>(rec + MR_EVAL + OVR_OFF);
     for (uint32_t c = 0; c < w_tab; c++) {
         Span sp(ctx, A, KZG_T_NTT);
-        launch_fr_ntt(A.stream, table.r[c], tab + c * vw, lg, tw, nullptr, mid);
+        launch_fr_ntt(A.stream, table.r[c], tab + c * vw, F.lg, F.tw, nullptr, F.mid);
     }
     {
         Span sp(ctx, A, KZG_T_POLY);
@@ -1856,31 +1776,23 @@ int rows_fetch_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, 
     for (uint32_t l = 0, c = 0; l < n_reads; l++) {
         for (uint32_t k = 0; k < n_in; k++) {
             Span sp(ctx, A, KZG_T_NTT);
-            launch_fr_ntt(A.stream, inputs.r[l * n_in + k], in + k * vw, lg, tw, nullptr, mid);
+            launch_fr_ntt(A.stream, inputs.r[l * n_in + k], in + k * vw, F.lg, F.tw, nullptr, F.mid);
         }
         {
             Span sp(ctx, A, KZG_T_POLY);
             if (n_keys) launch_join_fetch(A.stream, tab, in, T, n, n_keys, n_pay, index, slots, cap, out, cnt + l, first + l, overrun);
             else launch_fetch_index(A.stream, tab, in, T, n, n_pay, out, cnt + l, first + l);
         }
-        for (uint32_t p = 0; p < n_per; p++, c++) {
-            if (lay) {
-                Span sp(ctx, A, KZG_T_POLY);
-                launch_sort_tail(A.stream, out + p * vw, T, n, lay->tail_be32 + 32 * (size_t)c * (T - n), A.flags());
-            }
-            const uint32_t* cf;
-            if (int rc = row_to_coeffs(ctx, A, out + p * vw, T, 1, &cf, dst + c * vw)) return rc;
-        }
+        for (uint32_t p = 0; p < n_per; p++, c++)
+            if (int rc = emit_column(ctx, A, F, out + p * vw, c)) return rc;
     }
-    HIPCHK(ctx, hipGetLastError());
-    uint8_t ev[CNT_OFF + 16 * KZG_MAX_BATCH_OPEN + 32];
-    const uint32_t npairs = (CNT_OFF + 16 * n_reads + 31) / 32;
-    if (int rc = multi_msms_finish(ctx, H, i, T, dst, n_out, 0, npairs, out_c48, ev, nullptr)) return rc;
+    const uint8_t* stats;
+    if (int rc = stats_finish(ctx, H, i, F, n_out, 16 * n_reads, out_c48, &stats)) return rc;
     uint32_t of;
-    memcpy(&of, ev + OVR_OFF, 4);
+    memcpy(&of, F.ev + OVR_OFF, 4);
     *out_overrun = of != 0;
-    memcpy(out_missing, ev + CNT_OFF, 8 * (size_t)n_reads);
-    memcpy(out_first, ev + CNT_OFF + 8 * (size_t)n_reads, 8 * (size_t)n_reads);
+    memcpy(out_missing, stats, 8 * (size_t)n_reads);
+    memcpy(out_first, stats + 8 * (size_t)n_reads, 8 * (size_t)n_reads);
     return KZG_OK;
 }
 

@@ -736,6 +736,87 @@ static int rows_lookup(kzg_ctx* ctx, const char* what, uint32_t expect_i, uint32
     return KZG_OK;
 }
 
+// ---- the call frame of the column builders (sorted, derived, int, alu, wide, poseidon, expr, recurrence, fetch): a set
+// built FROM sets, whose columns may carry the caller's tail behind row `usable`.
+
+// What differs between the builders' `usable` / `tail_be32` layouts: what usable = 0 means, in the words of the first refusal,
+// and whether row `usable` closes a running value (recurrence), so that a column takes T - usable - 1 tail scalars, not T - usable
+struct LayoutKind {
+    const char* zero_means;
+    uint32_t closing;
+};
+static const LayoutKind LAY_READ = {"all T rows are read", 0}, LAY_SORTED = {"all T rows are sorted", 0},
+                        LAY_EVALUATED = {"all T rows are evaluated", 0}, LAY_CLOSING = {"the plain layout", 1};
+// the layout `lay` as the caller gave it against the row length, over n_cols committed columns.  The tail may be null when it
+// holds no scalar (nothing is committed, or usable = T - 1 before a closing row).  *out: what to pass down, null for usable = 0
+static int layout_check(kzg_ctx* ctx, const char* what, const Blind& lay, uint64_t T, uint32_t n_cols, const LayoutKind& kind,
+                        const Blind** out) {
+    auto bad = [&](const std::string& why) { return fail(ctx, KZG_E_ARG, std::string(what) + why); };
+    *out = lay.usable ? &lay : nullptr;
+    if (!lay.usable) return lay.tail_be32 ? bad(": tail_be32 must be null in the plain layout (usable = 0)") : KZG_OK;
+    if (lay.usable >= T) return bad(std::string(": usable must be in [1, T - 1] (0: ") + kind.zero_means + ")");
+    if (T - lay.usable > KZG_MAX_BLIND_ROWS) return bad(": at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
+    const uint64_t n_tail = (uint64_t)n_cols * (T - lay.usable - kind.closing);
+    if (n_tail && !lay.tail_be32)
+        return bad(kind.closing ? ": tail_be32 may be null only when usable = T - 1" : ": tail_be32 must be given when usable > 0");
+    for (uint64_t j = 0; j < n_tail; j++)
+        if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j)) return bad(": tail scalars must be canonical (< r)");
+    return KZG_OK;
+}
+
+// One call of a column builder: begin() -- the builder's checks on row indices -- ready() -- the device call -- commit().
+struct BuilderCall {
+    kzg_ctx* ctx;
+    const char* what;       // prefixes the messages
+    // The order of these three is load-bearing: members are destroyed in reverse, so the LaneHold drains the lane of a failed
+    // call BEFORE the references are dropped and the reserved buffer returns to the free list -- kernels may still write it.
+    RowsPending pend;
+    RowsRefs refs[3];       // one per handle list
+    LaneHold H;
+    uint32_t n_lists = 0, i = 0, n_out = 0;
+    uint64_t T = 0;
+    Blind lay = {0, nullptr};
+    const Blind* blind = nullptr;   // the layout to pass down, set by ready()
+    BuilderCall(kzg_ctx* c, const char* w) : ctx(c), what(w), pend{c}, refs{{c}, {c}, {c}}, H(c) {}
+    // a further handle list (`list` prefixes its messages): its rows into rt, their number into *k; every list of the call
+    // must be of one worker and one row length
+    int lookup(const char* list, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, RowTab& rt, uint32_t* k) {
+        uint32_t i2 = 0;
+        uint64_t T2 = 0;
+        if (int rc = rows_lookup(ctx, list, expect_i, n_handles, handles, refs[n_lists], rt, k, &i2, &T2)) return rc;
+        if (n_lists++ == 0) {
+            i = i2;
+            T = T2;
+        } else if (i2 != i || T2 != T) {
+            return fail(ctx, KZG_E_ARG, std::string(what) + ": all sets must belong to one worker and have one row length");
+        }
+        return KZG_OK;
+    }
+    // the device, the lane (before the lookups: an SRS load cannot free the sets' buffers under this call), the first list
+    int begin(const char* list, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, RowTab& rt, uint32_t* k) {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        if (int rc = H.take()) return rc;
+        return lookup(list, expect_i, n_handles, handles, rt, k);
+    }
+    // the worker, the row length (a power of two, at most 2^max_log_t where the builder has a cap: 0 for none), the layout
+    // `asked` over the n_cols columns to commit, their reservation (none for n_cols = 0), then the call's profile and flags
+    int ready(uint32_t n_cols, int max_log_t, const Blind& asked, const LayoutKind& kind) {
+        if (int rc = check_worker(ctx, i, T)) return rc;
+        if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, std::string(what) + ": the row length must be a power of two");
+        if (max_log_t && T > ((uint64_t)1 << max_log_t))
+            return fail(ctx, KZG_E_ARG, std::string(what) + ": the row length must be at most 2^" + std::to_string(max_log_t));
+        lay = asked;
+        n_out = n_cols;
+        if (int rc = layout_check(ctx, what, lay, T, n_cols, kind, &blind)) return rc;
+        if (n_out)
+            if (int rc = rows_reserve(ctx, what, pend, (size_t)n_out * T * 32)) return rc;
+        prof_begin(ctx, H.L());
+        return clear_flags(ctx, H.L());
+    }
+    uint32_t* dst() { return n_out ? pend.buf.as<uint32_t>() : nullptr; }   // the new set's buffer
+    uint64_t commit() { return n_out ? rows_insert(ctx, pend, i, n_out, T) : 0; }   // the new set's handle; 0: nothing committed
+};
+
 int rows_open(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
               const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
               uint8_t* out_proofs48) {
@@ -1073,43 +1154,17 @@ int rows_sorted(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const
         return fail(ctx, KZG_E_ARG, "sorted: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
     if (width == 0 || width > KZG_MAX_BATCH_OPEN) return fail(ctx, KZG_E_ARG, "sorted: width must be in [1, KZG_MAX_BATCH_OPEN]");
     if (n_keys == 0 || n_keys > width) return fail(ctx, KZG_E_ARG, "sorted: n_keys must be in [1, width]");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    RowsPending pend{ctx};
-    RowsRefs irefs{ctx};
-    LaneHold H(ctx);
-    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
-    Lane& L = H.L();
+    BuilderCall C(ctx, "sorted");
     RowTab it;
-    uint32_t ki = 0, i = 0;
-    uint64_t T = 0;
-    if (int rc = rows_lookup(ctx, "sorted", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    uint32_t ki = 0;
+    if (int rc = C.begin("sorted", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
     if (ki != width) return fail(ctx, KZG_E_ARG, "sorted: the input sets must hold exactly width rows");
-    int rc = check_worker(ctx, i, T);
-    if (rc) return rc;
-    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "sorted: the row length must be a power of two");
-    if (T > ((uint64_t)1 << 27))   // row indices and slot offsets are u32, 256 counts per tile of the passes
-        return fail(ctx, KZG_E_ARG, "sorted: the row length must be at most 2^27");
-    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
-    if (lay.usable) {
-        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "sorted: usable must be in [1, T - 1] (0: all T rows are sorted)");
-        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
-            return fail(ctx, KZG_E_ARG, "sorted: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
-        if (!lay.tail_be32) return fail(ctx, KZG_E_ARG, "sorted: tail_be32 must be given when usable > 0");
-        for (uint64_t j = 0; j < (uint64_t)width * (T - lay.usable); j++)
-            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
-                return fail(ctx, KZG_E_ARG, "sorted: tail scalars must be canonical (< r)");
-    } else if (lay.tail_be32) {
-        return fail(ctx, KZG_E_ARG, "sorted: tail_be32 must be null in the plain layout (usable = 0)");
-    }
-    if (int rc2 = rows_reserve(ctx, "sorted", pend, (size_t)width * T * 32)) return rc2;
-    prof_begin(ctx, L);
-    rc = clear_flags(ctx, L);
-    if (rc) return rc;
+    // (2^27: row indices and slot offsets are u32, 256 counts per tile of the passes)
+    if (int rc = C.ready(width, 27, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_SORTED)) return rc;
     uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
-    rc = rows_sorted_dev(ctx, H, i, it, width, n_keys, T, pend.buf.as<uint32_t>(), c48, lay.usable ? &lay : nullptr);
-    if (rc) return rc;
+    if (int rc = rows_sorted_dev(ctx, C.H, C.i, it, width, n_keys, C.T, C.dst(), c48, C.blind)) return rc;
     memcpy(out_commitments48, c48, 48 * (size_t)width);
-    *out_handle = rows_insert(ctx, pend, i, width, T);
+    *out_handle = C.commit();
     return KZG_OK;
 }
 
@@ -1231,45 +1286,19 @@ int rows_derived(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, cons
     }
     if (n_out > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "derived: n_out, the sum of the counts, must be in [1, KZG_MAX_BATCH_OPEN]");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    RowsPending pend{ctx};
-    RowsRefs irefs{ctx};
-    LaneHold H(ctx);
-    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
-    Lane& L = H.L();
+    BuilderCall C(ctx, "derived");
     RowTab it;
-    uint32_t ki = 0, i = 0;
-    uint64_t T = 0;
-    if (int rc = rows_lookup(ctx, "derived", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    uint32_t ki = 0;
+    if (int rc = C.begin("derived", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
     for (uint32_t o = 0; o < n_ops; o++)
         if (ops[o].row >= ki) return fail(ctx, KZG_E_ARG, "derived: a row must index the concatenated rows of the input sets");
-    int rc = check_worker(ctx, i, T);
-    if (rc) return rc;
-    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "derived: the row length must be a power of two");
-    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
-    if (lay.usable) {
-        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "derived: usable must be in [1, T - 1] (0: all T rows are read)");
-        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
-            return fail(ctx, KZG_E_ARG, "derived: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
-        if (!lay.tail_be32) return fail(ctx, KZG_E_ARG, "derived: tail_be32 must be given when usable > 0");
-        for (uint64_t j = 0; j < n_out * (T - lay.usable); j++)
-            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
-                return fail(ctx, KZG_E_ARG, "derived: tail scalars must be canonical (< r)");
-    } else if (lay.tail_be32) {
-        return fail(ctx, KZG_E_ARG, "derived: tail_be32 must be null in the plain layout (usable = 0)");
-    }
-    if (int rc2 = rows_reserve(ctx, "derived", pend, (size_t)n_out * T * 32)) return rc2;
-    prof_begin(ctx, L);
-    rc = clear_flags(ctx, L);
-    if (rc) return rc;
+    if (int rc = C.ready((uint32_t)n_out, 0, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ)) return rc;
     uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
     uint64_t counts[KZG_MAX_BATCH_OPEN];
-    rc = rows_derived_dev(ctx, H, i, it, n_ops, ops, (uint32_t)n_out, T, pend.buf.as<uint32_t>(), c48, counts,
-                          lay.usable ? &lay : nullptr);
-    if (rc) return rc;
+    if (int rc = rows_derived_dev(ctx, C.H, C.i, it, n_ops, ops, C.n_out, C.T, C.dst(), c48, counts, C.blind)) return rc;
     memcpy(out_commitments48, c48, 48 * (size_t)n_out);
     memcpy(out_counts, counts, 8 * (size_t)n_ops);
-    *out_handle = rows_insert(ctx, pend, i, (uint32_t)n_out, T);
+    *out_handle = C.commit();
     return KZG_OK;
 }
 
@@ -1303,51 +1332,25 @@ int rows_int(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const ui
     }
     if (n_out > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "int: n_out, the sum of the counts, must be in [1, KZG_MAX_BATCH_OPEN]");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    RowsPending pend{ctx};
-    RowsRefs irefs{ctx};
-    LaneHold H(ctx);
-    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
-    Lane& L = H.L();
+    BuilderCall C(ctx, "int");
     RowTab it;
-    uint32_t ki = 0, i = 0;
-    uint64_t T = 0;
-    if (int rc = rows_lookup(ctx, "int", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    uint32_t ki = 0;
+    if (int rc = C.begin("int", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
     for (uint32_t o = 0; o < n_ops; o++)
         if (ops[o].a >= ki || ops[o].b >= ki)
             return fail(ctx, KZG_E_ARG, "int: a row must index the concatenated rows of the input sets");
-    int rc = check_worker(ctx, i, T);
-    if (rc) return rc;
-    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "int: the row length must be a power of two");
-    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
-    if (lay.usable) {
-        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "int: usable must be in [1, T - 1] (0: all T rows are read)");
-        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
-            return fail(ctx, KZG_E_ARG, "int: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
-        if (!lay.tail_be32) return fail(ctx, KZG_E_ARG, "int: tail_be32 must be given when usable > 0");
-        for (uint64_t j = 0; j < n_out * (T - lay.usable); j++)
-            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
-                return fail(ctx, KZG_E_ARG, "int: tail scalars must be canonical (< r)");
-    } else if (lay.tail_be32) {
-        return fail(ctx, KZG_E_ARG, "int: tail_be32 must be null in the plain layout (usable = 0)");
-    }
-    if (int rc2 = rows_reserve(ctx, "int", pend, (size_t)n_out * T * 32)) return rc2;
-    prof_begin(ctx, L);
-    rc = clear_flags(ctx, L);
-    if (rc) return rc;
+    if (int rc = C.ready(n_out, 0, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ)) return rc;
     uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
     uint64_t counts[KZG_MAX_BATCH_OPEN], first[KZG_MAX_BATCH_OPEN];
-    rc = rows_int_dev(ctx, H, i, it, n_ops, ops, n_out, T, pend.buf.as<uint32_t>(), c48, counts, first,
-                      lay.usable ? &lay : nullptr);
-    if (rc) return rc;
+    if (int rc = rows_int_dev(ctx, C.H, C.i, it, n_ops, ops, n_out, C.T, C.dst(), c48, counts, first, C.blind)) return rc;
     memcpy(out_commitments48, c48, 48 * (size_t)n_out);
     memcpy(out_counts, counts, 8 * (size_t)n_ops);
     memcpy(out_first, first, 8 * (size_t)n_ops);
-    *out_handle = rows_insert(ctx, pend, i, n_out, T);
+    *out_handle = C.commit();
     return KZG_OK;
 }
 
-// kzg_rows_commit_alu: the frame of rows_int.  The program and the units are checked here, on the host, before a lane is taken
+// kzg_rows_commit_alu: a BuilderCall around its own checks.  The program and the units are checked here, on the host, before a lane is taken
 int rows_alu(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_entries,
              const kzg_alu_entry* program, uint32_t n_units, const kzg_alu_unit* units, const kzg_derive_opts* opts,
              uint8_t* out_commitments48, uint64_t* out_counts, uint64_t* out_first, uint64_t* out_unknown,
@@ -1391,53 +1394,28 @@ int rows_alu(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const ui
     }
     if (n_out > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "alu: n_out, the sum of the counts, must be in [1, KZG_MAX_BATCH_OPEN]");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    RowsPending pend{ctx};
-    RowsRefs irefs{ctx};
-    LaneHold H(ctx);
-    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
-    Lane& L = H.L();
+    BuilderCall C(ctx, "alu");
     RowTab it;
-    uint32_t ki = 0, i = 0;
-    uint64_t T = 0;
-    if (int rc = rows_lookup(ctx, "alu", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    uint32_t ki = 0;
+    if (int rc = C.begin("alu", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
     for (uint32_t u = 0; u < n_units; u++)
         if (units[u].op_row >= ki || units[u].a >= ki || units[u].b >= ki)
             return fail(ctx, KZG_E_ARG, "alu: a row must index the concatenated rows of the input sets");
-    int rc = check_worker(ctx, i, T);
-    if (rc) return rc;
-    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "alu: the row length must be a power of two");
-    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
-    if (lay.usable) {
-        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "alu: usable must be in [1, T - 1] (0: all T rows are read)");
-        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
-            return fail(ctx, KZG_E_ARG, "alu: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
-        if (!lay.tail_be32) return fail(ctx, KZG_E_ARG, "alu: tail_be32 must be given when usable > 0");
-        for (uint64_t j = 0; j < n_out * (T - lay.usable); j++)
-            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
-                return fail(ctx, KZG_E_ARG, "alu: tail scalars must be canonical (< r)");
-    } else if (lay.tail_be32) {
-        return fail(ctx, KZG_E_ARG, "alu: tail_be32 must be null in the plain layout (usable = 0)");
-    }
-    if (int rc2 = rows_reserve(ctx, "alu", pend, (size_t)n_out * T * 32)) return rc2;
-    prof_begin(ctx, L);
-    rc = clear_flags(ctx, L);
-    if (rc) return rc;
+    if (int rc = C.ready(n_out, 0, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ)) return rc;
     uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
     uint64_t stats[4 * KZG_ALU_MAX_UNITS];
-    rc = rows_alu_dev(ctx, H, i, it, n_entries, program, n_units, units, n_out, T, pend.buf.as<uint32_t>(), c48, stats,
-                      lay.usable ? &lay : nullptr);
-    if (rc) return rc;
+    if (int rc = rows_alu_dev(ctx, C.H, C.i, it, n_entries, program, n_units, units, n_out, C.T, C.dst(), c48, stats, C.blind))
+        return rc;
     memcpy(out_commitments48, c48, 48 * (size_t)n_out);
     memcpy(out_counts, stats, 8 * (size_t)n_units);
     memcpy(out_unknown, stats + n_units, 8 * (size_t)n_units);
     memcpy(out_first, stats + 2 * n_units, 8 * (size_t)n_units);
     memcpy(out_first_unknown, stats + 3 * n_units, 8 * (size_t)n_units);
-    *out_handle = rows_insert(ctx, pend, i, n_out, T);
+    *out_handle = C.commit();
     return KZG_OK;
 }
 
-// kzg_rows_commit_wide: the frame of rows_int.  Kinds, b, L, counts, operands, immediates and moduli are checked here, on the
+// kzg_rows_commit_wide: a BuilderCall around its own checks.  Kinds, b, L, counts, operands, immediates and moduli are checked here, on the
 // host, before a lane is taken
 static bool wide_be64_zero(const uint8_t* v) {
     for (int j = 0; j < 64; j++)
@@ -1502,54 +1480,29 @@ int rows_wide(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const u
     }
     if (n_out > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "wide: n_out, the sum of the counts, must be in [1, KZG_MAX_BATCH_OPEN]");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    RowsPending pend{ctx};
-    RowsRefs irefs{ctx};
-    LaneHold H(ctx);
-    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
-    Lane& L = H.L();
+    BuilderCall C(ctx, "wide");
     RowTab it;
-    uint32_t ki = 0, i = 0;
-    uint64_t T = 0;
-    if (int rc = rows_lookup(ctx, "wide", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    uint32_t ki = 0;
+    if (int rc = C.begin("wide", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
     for (uint32_t o = 0; o < n_ops; o++)
         for (uint32_t first : {ops[o].a, ops[o].b, ops[o].c, ops[o].q, ops[o].r})
             if (first != KZG_WIDE_ABSENT && (first >= ki || ops[o].limbs > ki - first))
                 return fail(ctx, KZG_E_ARG, "wide: the L rows of an operand must lie inside the concatenated rows of the input sets");
-    int rc = check_worker(ctx, i, T);
-    if (rc) return rc;
-    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "wide: the row length must be a power of two");
-    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
-    if (lay.usable) {
-        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "wide: usable must be in [1, T - 1] (0: all T rows are read)");
-        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
-            return fail(ctx, KZG_E_ARG, "wide: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
-        if (!lay.tail_be32) return fail(ctx, KZG_E_ARG, "wide: tail_be32 must be given when usable > 0");
-        for (uint64_t j = 0; j < n_out * (T - lay.usable); j++)
-            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
-                return fail(ctx, KZG_E_ARG, "wide: tail scalars must be canonical (< r)");
-    } else if (lay.tail_be32) {
-        return fail(ctx, KZG_E_ARG, "wide: tail_be32 must be null in the plain layout (usable = 0)");
-    }
-    if (int rc2 = rows_reserve(ctx, "wide", pend, (size_t)n_out * T * 32)) return rc2;
-    prof_begin(ctx, L);
-    rc = clear_flags(ctx, L);
-    if (rc) return rc;
+    if (int rc = C.ready(n_out, 0, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ)) return rc;
     uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
     uint64_t stats[4 * KZG_WIDE_MAX_OPS];
-    rc = rows_wide_dev(ctx, H, i, it, n_ops, ops, n_out, T, pend.buf.as<uint32_t>(), c48, stats, lay.usable ? &lay : nullptr);
-    if (rc) return rc;
+    if (int rc = rows_wide_dev(ctx, C.H, C.i, it, n_ops, ops, n_out, C.T, C.dst(), c48, stats, C.blind)) return rc;
     memcpy(out_commitments48, c48, 48 * (size_t)n_out);
     memcpy(out_counts, stats, 8 * (size_t)n_ops);
     memcpy(out_qover, stats + n_ops, 8 * (size_t)n_ops);
     memcpy(out_first, stats + 2 * n_ops, 8 * (size_t)n_ops);
     memcpy(out_first_qover, stats + 3 * n_ops, 8 * (size_t)n_ops);
-    *out_handle = rows_insert(ctx, pend, i, n_out, T);
+    *out_handle = C.commit();
     return KZG_OK;
 }
 
-// kzg_rows_commit_poseidon: the frame of rows_wide with the checks of rows_expr (no reservation and no set when every unit is a
-// check).  The parameters, the constants and immediates, modes, flags and out lists are checked here, on the host, before a
+// kzg_rows_commit_poseidon: a BuilderCall around its own checks; as in rows_expr, no reservation and no set when every unit is
+// a check.  The parameters, the constants and immediates, modes, flags and out lists are checked here, on the host, before a
 // lane is taken
 int rows_poseidon(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
                   const kzg_poseidon_params* params, uint32_t n_units, const kzg_poseidon_unit* units, const kzg_derive_opts* opts,
@@ -1616,50 +1569,57 @@ int rows_poseidon(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, con
     if (n_out > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "poseidon: n_out, the committed columns of all units, must be at most KZG_MAX_BATCH_OPEN");
     if (n_out && !out_commitments48) return KZG_E_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    RowsPending pend{ctx};
-    RowsRefs irefs{ctx};
-    LaneHold H(ctx);
-    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
-    Lane& L = H.L();
+    BuilderCall C(ctx, "poseidon");
     RowTab it;
-    uint32_t ki = 0, i = 0;
-    uint64_t T = 0;
-    if (int rc = rows_lookup(ctx, "poseidon", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    uint32_t ki = 0;
+    if (int rc = C.begin("poseidon", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
     if (n_seen && max_row >= ki) return fail(ctx, KZG_E_ARG, "poseidon: a row must index the concatenated rows of the input sets");
-    int rc = check_worker(ctx, i, T);
-    if (rc) return rc;
-    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "poseidon: the row length must be a power of two");
-    if (T > ((uint64_t)1 << 32)) return fail(ctx, KZG_E_ARG, "poseidon: the row length must be at most 2^32");
-    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
-    if (lay.usable) {
-        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "poseidon: usable must be in [1, T - 1] (0: all T rows are read)");
-        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
-            return fail(ctx, KZG_E_ARG, "poseidon: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
-        if (n_out && !lay.tail_be32) return fail(ctx, KZG_E_ARG, "poseidon: tail_be32 must be given when usable > 0");
-        for (uint64_t j = 0; j < n_out * (T - lay.usable); j++)
-            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
-                return fail(ctx, KZG_E_ARG, "poseidon: tail scalars must be canonical (< r)");
-    } else if (lay.tail_be32) {
-        return fail(ctx, KZG_E_ARG, "poseidon: tail_be32 must be null in the plain layout (usable = 0)");
-    }
-    if (n_out)
-        if (int rc2 = rows_reserve(ctx, "poseidon", pend, (size_t)n_out * T * 32)) return rc2;
-    prof_begin(ctx, L);
-    rc = clear_flags(ctx, L);
-    if (rc) return rc;
+    if (int rc = C.ready(n_out, 32, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ)) return rc;
     uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
     uint64_t stats[2 * KZG_POSEIDON_MAX_UNITS];
-    rc = rows_poseidon_dev(ctx, H, i, it, params, n_units, units, n_out, T, n_out ? pend.buf.as<uint32_t>() : nullptr, c48, stats,
-                           lay.usable ? &lay : nullptr);
-    if (rc) return rc;
+    if (int rc = rows_poseidon_dev(ctx, C.H, C.i, it, params, n_units, units, n_out, C.T, C.dst(), c48, stats, C.blind)) return rc;
     if (n_out) memcpy(out_commitments48, c48, 48 * (size_t)n_out);
-    const uint64_t n = lay.usable ? lay.usable : T;
+    const uint64_t n = C.blind ? C.blind->usable : C.T;
     for (uint32_t u = 0; u < n_units; u++) out_perms[u] = units[u].mode == KZG_POSEIDON_ROUNDS ? n / units[u].period : n;
     memcpy(out_mismatch, stats, 8 * (size_t)n_units);
     memcpy(out_first_mismatch, stats + n_units, 8 * (size_t)n_units);
-    *out_handle = n_out ? rows_insert(ctx, pend, i, n_out, T) : 0;
+    *out_handle = C.commit();
     return KZG_OK;
+}
+
+// The terms of an expression as rows_expr_dev takes them: a kzg_quotient_terms checked (counts, lengths, canonical
+// coefficients) and copied into the zeroed plan `pl`, its rotations as given into `rots` -- they are reduced by expr_reduce once
+// T is known -- and the largest row it names into *max_row.  may_be_empty: n_terms = 0 is accepted and leaves pl empty
+struct ExprRots {
+    int32_t r[EXPR_MAX_TERMS][EXPR_MAX_FACTORS];
+};
+static int expr_decode(kzg_ctx* ctx, const char* what, const kzg_quotient_terms& g, bool may_be_empty, ExprPlan& pl, ExprRots& rots,
+                       uint32_t* max_row) {
+    auto bad = [&](const char* why) { return fail(ctx, KZG_E_ARG, std::string(what) + why); };
+    if (g.n_terms > KZG_MAX_GATE_TERMS || (g.n_terms == 0 && !may_be_empty))
+        return bad(may_be_empty ? ": n_terms must be in [0, KZG_MAX_GATE_TERMS]" : ": n_terms must be in [1, KZG_MAX_GATE_TERMS]");
+    if (g.n_terms == 0) return KZG_OK;
+    if (!g.coeffs_be32 || !g.term_lens) return bad(": coeffs_be32 and term_lens must not be null inside an expression");
+    pl.n_terms = g.n_terms;
+    pl.coeffs_be32 = g.coeffs_be32;
+    for (uint32_t u = 0, at = 0; u < g.n_terms; u++) {
+        if (!fr_be32_canonical(g.coeffs_be32 + 32 * (size_t)u)) return bad(": term coefficients must be canonical scalars (< r)");
+        if (g.term_lens[u] > KZG_MAX_EXPR_FACTORS) return bad(": a term has more than KZG_MAX_EXPR_FACTORS factors");
+        if (g.term_lens[u] && !g.term_rows) return bad(": term_rows must not be null inside an expression that has a factor");
+        pl.term_len[u] = (uint8_t)g.term_lens[u];
+        for (uint32_t f = 0; f < g.term_lens[u]; f++, at++) {
+            *max_row = std::max(*max_row, g.term_rows[at]);
+            pl.term_row[u][f] = (uint8_t)(g.term_rows[at] < KZG_MAX_BATCH_OPEN ? g.term_rows[at] : 0);
+            if (g.term_rots) rots.r[u][f] = g.term_rots[at];
+        }
+    }
+    return KZG_OK;
+}
+// any int32 rotation, reduced into [0, T)
+static void expr_reduce(ExprPlan& pl, const ExprRots& rots, uint64_t T) {
+    for (uint32_t u = 0; u < pl.n_terms; u++)
+        for (uint32_t f = 0; f < pl.term_len[u]; f++)
+            pl.term_rot[u][f] = (uint32_t)(((int64_t)rots.r[u][f] % (int64_t)T + (int64_t)T) % (int64_t)T);
 }
 
 // kzg_rows_commit_expr: the lookups of an open (one handle list), the reservation of a commit of n_out rows -- none when every
@@ -1673,83 +1633,33 @@ int rows_expr(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const u
     if (n_exprs == 0 || n_exprs > KZG_MAX_BATCH_OPEN || !exprs)
         return fail(ctx, KZG_E_ARG, "expr: n_exprs must be in [1, KZG_MAX_BATCH_OPEN]");
     ExprPlan plan[KZG_MAX_BATCH_OPEN];
-    int32_t rots[KZG_MAX_BATCH_OPEN][EXPR_MAX_TERMS][EXPR_MAX_FACTORS];   // as given: reduced mod T once T is known
+    ExprRots rots[KZG_MAX_BATCH_OPEN];   // as given: reduced mod T once T is known
     uint8_t is_check[KZG_MAX_BATCH_OPEN];
     uint32_t n_out = 0, max_row = 0;
     memset(plan, 0, sizeof(plan));
     memset(rots, 0, sizeof(rots));
     for (uint32_t e = 0; e < n_exprs; e++) {
-        const kzg_quotient_terms& g = exprs[e].terms;
         if (exprs[e].flags & ~KZG_EXPR_CHECK) return fail(ctx, KZG_E_ARG, "expr: flags must be 0 or KZG_EXPR_CHECK");
         is_check[e] = exprs[e].flags == KZG_EXPR_CHECK;
         n_out += !is_check[e];
-        if (g.n_terms == 0 || g.n_terms > KZG_MAX_GATE_TERMS)
-            return fail(ctx, KZG_E_ARG, "expr: n_terms must be in [1, KZG_MAX_GATE_TERMS]");
-        if (!g.coeffs_be32 || !g.term_lens)
-            return fail(ctx, KZG_E_ARG, "expr: coeffs_be32 and term_lens must not be null inside an expression");
-        plan[e].n_terms = g.n_terms;
-        plan[e].coeffs_be32 = g.coeffs_be32;
-        for (uint32_t u = 0, at = 0; u < g.n_terms; u++) {
-            if (!fr_be32_canonical(g.coeffs_be32 + 32 * (size_t)u))
-                return fail(ctx, KZG_E_ARG, "expr: term coefficients must be canonical scalars (< r)");
-            if (g.term_lens[u] > KZG_MAX_EXPR_FACTORS)
-                return fail(ctx, KZG_E_ARG, "expr: a term has more than KZG_MAX_EXPR_FACTORS factors");
-            if (g.term_lens[u] && !g.term_rows)
-                return fail(ctx, KZG_E_ARG, "expr: term_rows must not be null inside an expression that has a factor");
-            plan[e].term_len[u] = (uint8_t)g.term_lens[u];
-            for (uint32_t f = 0; f < g.term_lens[u]; f++, at++) {
-                max_row = std::max(max_row, g.term_rows[at]);
-                plan[e].term_row[u][f] = (uint8_t)(g.term_rows[at] < KZG_MAX_BATCH_OPEN ? g.term_rows[at] : 0);
-                if (g.term_rots) rots[e][u][f] = g.term_rots[at];
-            }
-        }
+        if (int rc = expr_decode(ctx, "expr", exprs[e].terms, false, plan[e], rots[e], &max_row)) return rc;
     }
     if (n_out && !out_commitments48) return KZG_E_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    RowsPending pend{ctx};
-    RowsRefs irefs{ctx};
-    LaneHold H(ctx);
-    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
-    Lane& L = H.L();
+    BuilderCall C(ctx, "expr");
     RowTab it;
-    uint32_t ki = 0, i = 0;
-    uint64_t T = 0;
-    if (int rc = rows_lookup(ctx, "expr", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    uint32_t ki = 0;
+    if (int rc = C.begin("expr", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
     if (max_row >= ki) return fail(ctx, KZG_E_ARG, "expr: a row must index the concatenated rows of the input sets");
-    int rc = check_worker(ctx, i, T);
-    if (rc) return rc;
-    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "expr: the row length must be a power of two");
-    if (T > ((uint64_t)1 << 32)) return fail(ctx, KZG_E_ARG, "expr: the row length must be at most 2^32");
-    for (uint32_t e = 0; e < n_exprs; e++)   // any int32 rotation, reduced into [0, T)
-        for (uint32_t u = 0; u < plan[e].n_terms; u++)
-            for (uint32_t f = 0; f < plan[e].term_len[u]; f++)
-                plan[e].term_rot[u][f] = (uint32_t)(((int64_t)rots[e][u][f] % (int64_t)T + (int64_t)T) % (int64_t)T);
-    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
-    if (lay.usable) {
-        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "expr: usable must be in [1, T - 1] (0: all T rows are evaluated)");
-        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
-            return fail(ctx, KZG_E_ARG, "expr: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
-        if (n_out && !lay.tail_be32) return fail(ctx, KZG_E_ARG, "expr: tail_be32 must be given when usable > 0");
-        for (uint64_t j = 0; j < n_out * (T - lay.usable); j++)
-            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
-                return fail(ctx, KZG_E_ARG, "expr: tail scalars must be canonical (< r)");
-    } else if (lay.tail_be32) {
-        return fail(ctx, KZG_E_ARG, "expr: tail_be32 must be null in the plain layout (usable = 0)");
-    }
-    if (n_out)
-        if (int rc2 = rows_reserve(ctx, "expr", pend, (size_t)n_out * T * 32)) return rc2;
-    prof_begin(ctx, L);
-    rc = clear_flags(ctx, L);
-    if (rc) return rc;
+    if (int rc = C.ready(n_out, 32, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_EVALUATED)) return rc;
+    for (uint32_t e = 0; e < n_exprs; e++) expr_reduce(plan[e], rots[e], C.T);
     uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
     uint64_t nonzero[KZG_MAX_BATCH_OPEN], first[KZG_MAX_BATCH_OPEN];
-    rc = rows_expr_dev(ctx, H, i, it, n_exprs, plan, is_check, n_out, T, n_out ? pend.buf.as<uint32_t>() : nullptr, c48, nonzero,
-                       first, lay.usable ? &lay : nullptr);
-    if (rc) return rc;
+    if (int rc = rows_expr_dev(ctx, C.H, C.i, it, n_exprs, plan, is_check, n_out, C.T, C.dst(), c48, nonzero, first, C.blind))
+        return rc;
     if (n_out) memcpy(out_commitments48, c48, 48 * (size_t)n_out);
     memcpy(out_nonzero, nonzero, 8 * (size_t)n_exprs);
     memcpy(out_first, first, 8 * (size_t)n_exprs);
-    *out_handle = n_out ? rows_insert(ctx, pend, i, n_out, T) : 0;
+    *out_handle = C.commit();
     return KZG_OK;
 }
 
@@ -1765,10 +1675,7 @@ int rows_recurrence(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, c
     if (n_recs == 0 || n_recs > KZG_MAX_BATCH_OPEN || !recs)
         return fail(ctx, KZG_E_ARG, "recur: n_recs must be in [1, KZG_MAX_BATCH_OPEN]");
     std::vector<RecurSpec> spec(n_recs);
-    std::vector<int32_t> rots((size_t)n_recs * 2 * EXPR_MAX_TERMS * EXPR_MAX_FACTORS, 0);   // as given: reduced mod T once T is known
-    auto rot_at = [&](uint32_t e, int side, uint32_t u, uint32_t f) -> int32_t& {
-        return rots[(((size_t)e * 2 + side) * EXPR_MAX_TERMS + u) * EXPR_MAX_FACTORS + f];
-    };
+    std::vector<ExprRots> rots((size_t)n_recs * 2);   // mul, add of every recurrence, as given: reduced mod T once T is known
     uint32_t max_row = 0;
     for (uint32_t e = 0; e < n_recs; e++) {
         memset(&spec[e], 0, sizeof(RecurSpec));
@@ -1777,76 +1684,25 @@ int rows_recurrence(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, c
         if (!recs[e].start_be32) return fail(ctx, KZG_E_ARG, "recur: start_be32 must not be null");
         if (!fr_be32_canonical(recs[e].start_be32)) return fail(ctx, KZG_E_ARG, "recur: start must be a canonical scalar (< r)");
         spec[e].start_be32 = recs[e].start_be32;
-        for (int side = 0; side < 2; side++) {
-            const kzg_quotient_terms& g = side ? recs[e].add : recs[e].mul;
-            ExprPlan& pl = side ? spec[e].add : spec[e].mul;
-            if (g.n_terms > KZG_MAX_GATE_TERMS) return fail(ctx, KZG_E_ARG, "recur: n_terms must be in [0, KZG_MAX_GATE_TERMS]");
-            if (g.n_terms == 0) continue;
-            if (!g.coeffs_be32 || !g.term_lens)
-                return fail(ctx, KZG_E_ARG, "recur: coeffs_be32 and term_lens must not be null inside an expression");
-            pl.n_terms = g.n_terms;
-            pl.coeffs_be32 = g.coeffs_be32;
-            for (uint32_t u = 0, at = 0; u < g.n_terms; u++) {
-                if (!fr_be32_canonical(g.coeffs_be32 + 32 * (size_t)u))
-                    return fail(ctx, KZG_E_ARG, "recur: term coefficients must be canonical scalars (< r)");
-                if (g.term_lens[u] > KZG_MAX_EXPR_FACTORS)
-                    return fail(ctx, KZG_E_ARG, "recur: a term has more than KZG_MAX_EXPR_FACTORS factors");
-                if (g.term_lens[u] && !g.term_rows)
-                    return fail(ctx, KZG_E_ARG, "recur: term_rows must not be null inside an expression that has a factor");
-                pl.term_len[u] = (uint8_t)g.term_lens[u];
-                for (uint32_t f = 0; f < g.term_lens[u]; f++, at++) {
-                    max_row = std::max(max_row, g.term_rows[at]);
-                    pl.term_row[u][f] = (uint8_t)(g.term_rows[at] < KZG_MAX_BATCH_OPEN ? g.term_rows[at] : 0);
-                    if (g.term_rots) rot_at(e, side, u, f) = g.term_rots[at];
-                }
-            }
-        }
+        if (int rc = expr_decode(ctx, "recur", recs[e].mul, true, spec[e].mul, rots[2 * e], &max_row)) return rc;
+        if (int rc = expr_decode(ctx, "recur", recs[e].add, true, spec[e].add, rots[2 * e + 1], &max_row)) return rc;
     }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    RowsPending pend{ctx};
-    RowsRefs irefs{ctx};
-    LaneHold H(ctx);
-    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
-    Lane& L = H.L();
+    BuilderCall C(ctx, "recur");
     RowTab it;
-    uint32_t ki = 0, i = 0;
-    uint64_t T = 0;
-    if (int rc = rows_lookup(ctx, "recur", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
+    uint32_t ki = 0;
+    if (int rc = C.begin("recur", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
     if (max_row >= ki) return fail(ctx, KZG_E_ARG, "recur: a row must index the concatenated rows of the input sets");
-    int rc = check_worker(ctx, i, T);
-    if (rc) return rc;
-    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "recur: the row length must be a power of two");
-    if (T > ((uint64_t)1 << 32)) return fail(ctx, KZG_E_ARG, "recur: the row length must be at most 2^32");
-    for (uint32_t e = 0; e < n_recs; e++)   // any int32 rotation, reduced into [0, T)
-        for (int side = 0; side < 2; side++) {
-            ExprPlan& pl = side ? spec[e].add : spec[e].mul;
-            for (uint32_t u = 0; u < pl.n_terms; u++)
-                for (uint32_t f = 0; f < pl.term_len[u]; f++)
-                    pl.term_rot[u][f] = (uint32_t)(((int64_t)rot_at(e, side, u, f) % (int64_t)T + (int64_t)T) % (int64_t)T);
-        }
-    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
-    if (lay.usable) {   // the _zk layout over n_recs columns: blind_check's refusals, the tail column-major
-        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "recur: usable must be in [1, T - 1] (0: the plain layout)");
-        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
-            return fail(ctx, KZG_E_ARG, "recur: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
-        const uint64_t n_tail = (uint64_t)n_recs * (T - lay.usable - 1);
-        if (n_tail && !lay.tail_be32) return fail(ctx, KZG_E_ARG, "recur: tail_be32 may be null only when usable = T - 1");
-        for (uint64_t j = 0; j < n_tail; j++)
-            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
-                return fail(ctx, KZG_E_ARG, "recur: tail scalars must be canonical (< r)");
-    } else if (lay.tail_be32) {
-        return fail(ctx, KZG_E_ARG, "recur: tail_be32 must be null in the plain layout (usable = 0)");
+    // (the _zk layout over n_recs columns: blind_check's refusals, the tail column-major)
+    if (int rc = C.ready(n_recs, 32, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_CLOSING)) return rc;
+    for (uint32_t e = 0; e < n_recs; e++) {
+        expr_reduce(spec[e].mul, rots[2 * e], C.T);
+        expr_reduce(spec[e].add, rots[2 * e + 1], C.T);
     }
-    if (int rc2 = rows_reserve(ctx, "recur", pend, (size_t)n_recs * T * 32)) return rc2;
-    prof_begin(ctx, L);
-    rc = clear_flags(ctx, L);
-    if (rc) return rc;
     uint8_t c48[KZG_MAX_BATCH_OPEN * 48], closing[KZG_MAX_BATCH_OPEN * 32];
-    rc = rows_recur_dev(ctx, H, i, it, n_recs, spec.data(), T, pend.buf.as<uint32_t>(), c48, closing, lay.usable ? &lay : nullptr);
-    if (rc) return rc;
+    if (int rc = rows_recur_dev(ctx, C.H, C.i, it, n_recs, spec.data(), C.T, C.dst(), c48, closing, C.blind)) return rc;
     memcpy(out_commitments48, c48, 48 * (size_t)n_recs);
     memcpy(out_closings32, closing, 32 * (size_t)n_recs);
-    *out_handle = rows_insert(ctx, pend, i, n_recs, T);
+    *out_handle = C.commit();
     return KZG_OK;
 }
 
@@ -1868,18 +1724,11 @@ int rows_fetch(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const 
     const uint64_t n_in = (uint64_t)n_reads * (n_keys ? n_keys : 1);
     if (n_in > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "fetch: n_reads * max(n_keys, 1) input rows must be at most KZG_MAX_BATCH_OPEN");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    RowsPending pend{ctx};
-    RowsRefs irefs{ctx}, trefs{ctx};
-    LaneHold H(ctx);
-    if (int rc = H.take()) return rc;   // (before the lookups: an SRS load cannot free the sets' buffers under this call)
-    Lane& L = H.L();
+    BuilderCall C(ctx, "fetch");
     RowTab it, tt;
-    uint32_t ki = 0, w_tab = 0, i = 0, i2 = 0;
-    uint64_t T = 0, T2 = 0;
-    if (int rc = rows_lookup(ctx, "fetch: inputs", expect_i, n_input_handles, input_handles, irefs, it, &ki, &i, &T)) return rc;
-    if (int rc = rows_lookup(ctx, "fetch: table", expect_i, n_table_handles, table_handles, trefs, tt, &w_tab, &i2, &T2)) return rc;
-    if (i2 != i || T2 != T) return fail(ctx, KZG_E_ARG, "fetch: all sets must belong to one worker and have one row length");
+    uint32_t ki = 0, w_tab = 0;
+    if (int rc = C.begin("fetch: inputs", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
+    if (int rc = C.lookup("fetch: table", expect_i, n_table_handles, table_handles, tt, &w_tab)) return rc;
     if (n_keys > w_tab) return fail(ctx, KZG_E_ARG, "fetch: n_keys must be at most the number of table rows");
     const uint32_t n_per = w_tab - n_keys + (index ? 1u : 0u);
     if (n_per == 0)
@@ -1888,40 +1737,21 @@ int rows_fetch(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const 
     if (n_out > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "fetch: n_reads * (payload rows + index) output rows must be at most KZG_MAX_BATCH_OPEN");
     if (ki != n_in) return fail(ctx, KZG_E_ARG, "fetch: the input sets must hold exactly n_reads * max(n_keys, 1) rows");
-    int rc = check_worker(ctx, i, T);
-    if (rc) return rc;
-    if (ilog2_exact(T) < 0) return fail(ctx, KZG_E_ARG, "fetch: the row length must be a power of two");
-    if (T > ((uint64_t)1 << 27))   // a slot holds a u32 row index, 2 T slots a u32 offset
-        return fail(ctx, KZG_E_ARG, "fetch: the row length must be at most 2^27");
-    const Blind lay = {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr};
-    if (lay.usable) {
-        if (lay.usable >= T) return fail(ctx, KZG_E_ARG, "fetch: usable must be in [1, T - 1] (0: all T rows are read)");
-        if (T - lay.usable > KZG_MAX_BLIND_ROWS)
-            return fail(ctx, KZG_E_ARG, "fetch: at most KZG_MAX_BLIND_ROWS rows may lie at or behind row `usable`");
-        if (!lay.tail_be32) return fail(ctx, KZG_E_ARG, "fetch: tail_be32 must be given when usable > 0");
-        for (uint64_t j = 0; j < n_out * (T - lay.usable); j++)
-            if (!fr_be32_canonical(lay.tail_be32 + 32 * (size_t)j))
-                return fail(ctx, KZG_E_ARG, "fetch: tail scalars must be canonical (< r)");
-    } else if (lay.tail_be32) {
-        return fail(ctx, KZG_E_ARG, "fetch: tail_be32 must be null in the plain layout (usable = 0)");
-    }
-    if (int rc2 = rows_reserve(ctx, "fetch", pend, (size_t)n_out * T * 32)) return rc2;
-    prof_begin(ctx, L);
-    rc = clear_flags(ctx, L);
-    if (rc) return rc;
+    // (2^27: a slot holds a u32 row index, 2 T slots a u32 offset)
+    if (int rc = C.ready((uint32_t)n_out, 27, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ)) return rc;
     bool overrun = false;
     uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
     uint64_t missing[KZG_MAX_BATCH_OPEN], first[KZG_MAX_BATCH_OPEN];
-    rc = rows_fetch_dev(ctx, H, i, it, tt, n_reads, n_keys, w_tab, index, T, pend.buf.as<uint32_t>(), c48, missing, first, &overrun,
-                        lay.usable ? &lay : nullptr);
-    if (rc) return rc;
+    if (int rc = rows_fetch_dev(ctx, C.H, C.i, it, tt, n_reads, n_keys, w_tab, index, C.T, C.dst(), c48, missing, first, &overrun,
+                                C.blind))
+        return rc;
     if (overrun)
         return fail(ctx, KZG_E_HIP, "fetch: a probe walk of the hash join reached its bound (the slot table held no empty "
                                     "slot): no set was created");
     memcpy(out_commitments48, c48, 48 * (size_t)n_out);
     memcpy(out_missing, missing, 8 * (size_t)n_reads);
     memcpy(out_first_missing, first, 8 * (size_t)n_reads);
-    *out_handle = rows_insert(ctx, pend, i, (uint32_t)n_out, T);
+    *out_handle = C.commit();
     return KZG_OK;
 }
 
