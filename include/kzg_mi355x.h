@@ -1335,6 +1335,115 @@ int kzg_rows_commit_poseidon(kzg_ctx* ctx, uint32_t n_input_handles, const uint6
                              const kzg_derive_opts* opts /* NULL: plain */, uint8_t* out_commitments48 /* n_out * 48 */,
                              uint64_t* out_perms /* n_units */, uint64_t* out_mismatch /* n_units */,
                              uint64_t* out_first_mismatch /* n_units */, uint64_t* out_handle);
+/* THE SHA-256 COMPRESSION COLUMNS: a set built FROM sets, the columns of the bit-oriented hash chip -- Merkle nodes over 32-byte
+ * digests, Bitcoin and Ethereum precompile traces, beacon-chain roots.  A round is no polynomial expression (kzg_rows_commit_expr)
+ * and depends non-linearly on the four rows before it (kzg_rows_commit_recurrence); composed from kzg_rows_commit_alu it takes
+ * more than a hundred calls per column.  There are NO parameters: the 64 round constants K and the standard initial value of
+ * FIPS 180-4 are built in.  ALL VALUES ARE 32-BIT WORDS.  A source cell is read as its canonical integer and reduced to its low
+ * 32 bits; a cell at or above 2^32 is reduced, never refused, counted once per cell in out_counts[u], and the smallest row of
+ * such a cell is out_first[u] (KZG_SHA256_NONE: none): the convention of kzg_rows_commit_int.  Output cells are the words as
+ * kzg_rows_commit_int stores them.  The concatenated rows of the input_handles sets (as in kzg_rows_open) are the source
+ * columns.  A call has 1 <= n_units <= KZG_SHA256_MAX_UNITS units.  A SLOT is a source row, or KZG_SHA256_IMM: then the word is
+ * the slot's immediate on every row, neither read nor counted; the immediate is 0 beside a row.  One row may serve several
+ * slots; a unit of immediates alone is legal.  With n = opts->usable, or T in the plain layout:
+ *   KZG_SHA256_ROW     for every row t' < n ONE compression of the block msg[0 .. 15] from the chaining value state[0 .. 7] (with
+ *                      KZG_SHA256_STD_IV: from the standard initial value; then every state entry is KZG_SHA256_IMM with the
+ *                      immediate 0); output column c < n_out holds word out[c] of the new chaining value, feed-forward
+ *                      included; 1 <= n_out <= 8, the out[c] distinct and below 8.  With KZG_SHA256_CHECK the unit commits
+ *                      NOTHING: expect[c] is the source row that column c is compared with, out_mismatch[u] the number of rows
+ *                      t' < n where some expected cell differs from the computed word and out_first_mismatch[u] the smallest
+ *                      such row, or KZG_SHA256_NONE.  A 2-to-1 hash of 32-byte nodes is two calls: the first with
+ *                      KZG_SHA256_STD_IV and 16 rows, the second with state = the first call's eight output rows and msg = the
+ *                      16 padding words as immediates
+ *   KZG_SHA256_ROUNDS  the round trace, which is what a prover commits, with the period P = period >= KZG_SHA256_MIN_PERIOD:
+ *                      block b = 0 .. floor(n / P) - 1 occupies rows [b P, b P + P); a block cut by n is not started.  msg[0]
+ *                      is the row of the message column, start the row of the start column or KZG_SHA256_ABSENT; out[c] < 12,
+ *                      distinct, names the column (KZG_SHA256_COL_*) of output column c, 1 <= n_out <= 12.  With W, A, E the
+ *                      three main columns of a block, rows counted from the block's first, and H its incoming chaining value:
+ *                        rows j = 0 .. 3       A[j] = H[3 - j], E[j] = H[7 - j]: the working variables d, c, b, a and h, g, f, e
+ *                        rows q = 4 + t, t < 64  W[q] = W_t: for t < 16 the msg cell at that same row, else sigma1(W[q - 2]) + W[q - 7]
+ *                                              + sigma0(W[q - 15]) + W[q - 16] mod 2^32; with (a, b, c, d) = A[q - 1 .. q - 4] and
+ *                                              (e, f, g, h) = E[q - 1 .. q - 4]: T1 = h + Sigma1(e) + Ch(e, f, g) + K_t + W[q], T2 =
+ *                                              Sigma0(a) + Maj(a, b, c), A[q] = T1 + T2 and E[q] = d + T1 mod 2^32
+ *                        rows 68 + j, j < 4    the feed-forward A[68 + j] = A[j] + A[64 + j], E[68 + j] = E[j] + E[64 + j] mod 2^32;
+ *                                              the outgoing chaining value is (A[71], A[70], A[69], A[68], E[71], .., E[68])
+ *                        rows 72 .. P - 1, and the rows floor(n / P) P .. n - 1: 0 in every column
+ *                      so that every gate relates a row to the rows at rotations -1 .. -16.  The columns: W, A, E on all block
+ *                      rows (W is 0 outside the rows q); CW the carry floor(. / 2^32) of the schedule sum (rows q, t >= 16); CA
+ *                      the carry of T1 + T2 summed in full (rows q) and of the A feed-forward (rows 68 + j); CE the carry of d
+ *                      + T1 summed in full (rows q) and of the E feed-forward; SIG0, SIG1 = sigma0(W[q - 15]), sigma1(W[q - 2])
+ *                      (rows q, t >= 16); SUM0, MAJ = Sigma0(A[q - 1]), Maj(A[q - 1], A[q - 2], A[q - 3]) and SUM1, CH =
+ *                      Sigma1(E[q - 1]), Ch(E[q - 1], E[q - 2], E[q - 3]) (rows q).  A column is 0 on every row not listed for
+ *                      it; the carries are at most 3 / 6 / 5.  CHAINING: block b starts a message when b = 0, when start is
+ *                      absent, or when the start cell at row b P is not zero (reduced like every cell); its H is then the
+ *                      standard initial value (KZG_SHA256_STD_IV) or state_imm[0 .. 7]; else H is the outgoing chaining
+ *                      value of block b - 1, so that rows 0 .. 3 repeat rows 68 .. 71 of the block before.  Start cells are
+ *                      read at the rows b P of existing blocks only, msg cells at the rows b P + 4 .. b P + 19 only.
+ *                      Every state entry is KZG_SHA256_IMM; msg[1 .. 15] and msg_imm are 0; KZG_SHA256_CHECK is refused
+ * out_blocks[u] is the number of compressions unit u ran: n for a ROW unit, floor(n / P) for a ROUNDS unit; out_messages[u] the
+ * blocks that started a message (0 on a ROW unit); out_mismatch[u] = 0 and out_first_mismatch[u] = KZG_SHA256_NONE on a unit
+ * that commits.  All committed columns of a call form ONE new set of the same worker and length, in the order of units, then
+ * of out: out_commitments48[c] equals kzg_rows_commit(i, n_out, these rows, T, 1, ..)[c] byte for byte, and *out_handle opens,
+ * evaluates, combines, releases, goes stale and counts against KZG_MAX_ROW_SETS like any other.  A call made of checks alone
+ * creates no set (*out_handle = 0, out_commitments48 may be null), runs no inverse transform and no MSM.  ONE kernel launch
+ * computes every unit; nothing row-sized crosses the host link.  A call reads at most KZG_MAX_BATCH_OPEN distinct rows and
+ * commits at most KZG_MAX_BATCH_OPEN.  opts (NULL: plain layout) is kzg_derive_opts as kzg_rows_commit_derived reads it: source
+ * rows t' >= usable are never read, compared or counted, output row usable + s of committed column c takes tail_be32[c * (T -
+ * usable) + s], there is NO closing row.  Handle lists, worker, T, staleness and threads follow kzg_rows_commit_expr.  KZG_E_ARG
+ * with a message that begins "sha256:" and names the cause: n_units outside its range; an unknown mode or flag;
+ * KZG_SHA256_CHECK on a ROUNDS unit; a period below 72 (not 0 on a ROW unit); n_out outside its range, an out index at or above
+ * 8 (a column id at or above 12) or a repeated one; a state entry, immediate, msg entry or start the mode does not take; more
+ * than KZG_MAX_BATCH_OPEN output rows or distinct input rows; a row index beyond the concatenation; T above 2^32; the usable
+ * and tail refusals of kzg_rows_commit_derived; the handle refusals of kzg_rows_open.  (An immediate or initial-value word at
+ * or above 2^32 does not fit the struct; the Python layer refuses it.)  All but the last five are checked on the host before a
+ * lane is taken.  After any error the context keeps serving and no set or buffer leaks.
+ * OUT OF SCOPE: padding, and packing bytes into words (compose with kzg_rows_commit_alu / kzg_rows_commit_expr); bit columns
+ * and spread-table forms of the words (kzg_rows_commit_derived's limbs and the lookups cover them); SHA-512, Keccak, Blake;
+ * periods below 72; more than one start convention.  A single message that fills the whole column runs on one lane of the
+ * device: correct, and slow.
+ * SOUNDNESS: nothing here is a proof.  The columns are prover data; the argument is the caller's gates over these columns plus
+ * the range lookups of words and carries.  A zero mismatch count convinces no verifier. */
+#define KZG_SHA256_ROW    1
+#define KZG_SHA256_ROUNDS 2
+#define KZG_SHA256_CHECK  1u               /* flags (ROW): compare with expect, commit nothing */
+#define KZG_SHA256_STD_IV 2u               /* flags: the chaining value (ROW) / a message's first one (ROUNDS) is the standard one */
+#define KZG_SHA256_IMM    0xffffffffu      /* a slot: the word is the slot's immediate */
+#define KZG_SHA256_ABSENT 0xffffffffu      /* start (ROUNDS): every block starts a message */
+#define KZG_SHA256_NONE   0xffffffffffffffffull   /* out_first, out_first_mismatch: none */
+#define KZG_SHA256_MAX_UNITS 4
+#define KZG_SHA256_MIN_PERIOD 72
+#define KZG_SHA256_N_COLS 12
+#define KZG_SHA256_COL_W 0
+#define KZG_SHA256_COL_A 1
+#define KZG_SHA256_COL_E 2
+#define KZG_SHA256_COL_CW 3
+#define KZG_SHA256_COL_CA 4
+#define KZG_SHA256_COL_CE 5
+#define KZG_SHA256_COL_SIG0 6
+#define KZG_SHA256_COL_SIG1 7
+#define KZG_SHA256_COL_SUM0 8
+#define KZG_SHA256_COL_MAJ 9
+#define KZG_SHA256_COL_SUM1 10
+#define KZG_SHA256_COL_CH 11
+typedef struct kzg_sha256_unit {
+    uint32_t mode;               /* KZG_SHA256_ROW or KZG_SHA256_ROUNDS */
+    uint32_t flags;              /* a combination of KZG_SHA256_CHECK (ROW) and KZG_SHA256_STD_IV */
+    uint32_t n_out;              /* ROW: 1 .. 8; ROUNDS: 1 .. 12 */
+    uint32_t period;             /* ROUNDS: P >= 72; ROW: 0 */
+    uint32_t start;              /* ROUNDS: the row of the start column, or KZG_SHA256_ABSENT; ROW: KZG_SHA256_ABSENT */
+    uint32_t state[8];           /* ROW: [j] the slot of chaining word j; ROUNDS: KZG_SHA256_IMM */
+    uint32_t state_imm[8];       /* [j] the word where state[j] = KZG_SHA256_IMM; 0 beside a row and with KZG_SHA256_STD_IV */
+    uint32_t msg[16];            /* ROW: [j] the slot of block word j; ROUNDS: msg[0] the row of the message column, the rest 0 */
+    uint32_t msg_imm[16];        /* ROW: [j] the word where msg[j] = KZG_SHA256_IMM; 0 beside a row; ROUNDS: 0 */
+    uint32_t out[12];            /* [c < n_out] ROW: the chaining word of output column c; ROUNDS: its KZG_SHA256_COL_* */
+    uint32_t expect[8];          /* [c < n_out] with KZG_SHA256_CHECK: the row that column c is compared with */
+} kzg_sha256_unit;
+int kzg_rows_commit_sha256(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_units,
+                           const kzg_sha256_unit* units, const kzg_derive_opts* opts /* NULL: plain */,
+                           uint8_t* out_commitments48 /* n_out * 48 */, uint64_t* out_blocks /* n_units */,
+                           uint64_t* out_messages /* n_units */, uint64_t* out_counts /* n_units */,
+                           uint64_t* out_first /* n_units */, uint64_t* out_mismatch /* n_units */,
+                           uint64_t* out_first_mismatch /* n_units */, uint64_t* out_handle);
 /* THE QUOTIENT WITH LOOKUP SELECTORS: kzg_rows_commit_quotient_zk and kzg_rows_quotient_part for lookups that are enabled on
  * some rows only.  selectors->selector_rows holds L = lookup->n_lookups entries, each a row index into the call's concatenated
  * rows (the caller's fixed column q_l, the row that kzg_rows_commit_multiplicities_sel / _lookup_sum_sel read) or
@@ -1729,6 +1838,11 @@ int kzg_multi_rows_commit_poseidon(kzg_multi* mh, uint32_t i, uint32_t n_input_h
                                    const kzg_poseidon_params* params, uint32_t n_units, const kzg_poseidon_unit* units,
                                    const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_perms,
                                    uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_handle);
+/* kzg_rows_commit_sha256 on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_sha256(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                 uint32_t n_units, const kzg_sha256_unit* units, const kzg_derive_opts* opts,
+                                 uint8_t* out_commitments48, uint64_t* out_blocks, uint64_t* out_messages, uint64_t* out_counts,
+                                 uint64_t* out_first, uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

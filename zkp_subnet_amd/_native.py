@@ -49,6 +49,15 @@ KZG_POSEIDON_IMM = 0xffffffff
 KZG_POSEIDON_NONE = 0xffffffffffffffff
 KZG_POSEIDON_MIN_T, KZG_POSEIDON_MAX_T = 2, 8
 KZG_POSEIDON_MAX_FULL, KZG_POSEIDON_MAX_PARTIAL, KZG_POSEIDON_MAX_UNITS = 16, 128, 8
+# kzg_rows_commit_sha256: kzg_sha256_unit.mode, the flags, a slot that holds an immediate, "no start column", "none", the limits,
+# and the column ids of a rounds unit in the order of KZG_SHA256_COL_W .. KZG_SHA256_COL_CH
+KZG_SHA256_ROW, KZG_SHA256_ROUNDS = 1, 2
+KZG_SHA256_CHECK, KZG_SHA256_STD_IV = 1, 2
+KZG_SHA256_IMM = 0xffffffff
+KZG_SHA256_ABSENT = 0xffffffff
+KZG_SHA256_NONE = 0xffffffffffffffff
+KZG_SHA256_MAX_UNITS, KZG_SHA256_MIN_PERIOD, KZG_SHA256_N_COLS = 4, 72, 12
+KZG_SHA256_COLS = ("w", "a", "e", "cw", "ca", "ce", "sig0", "sig1", "sum0", "maj", "sum1", "ch")
 KZG_MAX_EXPR_FACTORS = 8   # kzg_rows_commit_expr: factors of one term
 KZG_EXPR_CHECK = 1   # kzg_expr.flags: evaluate and count only
 KZG_EXPR_NONE = 0xffffffffffffffff   # out_first: no non-zero cell
@@ -158,6 +167,12 @@ class PoseidonUnit(ctypes.Structure):
                 ("expect", _U32 * 8), ("imm_be32", (ctypes.c_uint8 * 32) * 8)]
 
 
+class Sha256Unit(ctypes.Structure):
+    """kzg_sha256_unit"""
+    _fields_ = [("mode", _U32), ("flags", _U32), ("n_out", _U32), ("period", _U32), ("start", _U32), ("state", _U32 * 8),
+                ("state_imm", _U32 * 8), ("msg", _U32 * 16), ("msg_imm", _U32 * 16), ("out", _U32 * 12), ("expect", _U32 * 8)]
+
+
 class Col(ctypes.Structure):
     """kzg_col"""
     _fields_ = [("data", ctypes.c_void_p), ("count", ctypes.c_uint64), ("kind", ctypes.c_uint32), ("fill_be32", ctypes.c_char_p)]
@@ -245,6 +260,8 @@ SYMBOLS = {
     "kzg_rows_commit_poseidon": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(PoseidonParams), _U32,
                                       ctypes.POINTER(PoseidonUnit), ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64),
                                       ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_sha256": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Sha256Unit), ctypes.POINTER(DeriveOpts),
+                                    _B] + [ctypes.POINTER(_U64)] * 7),
     "kzg_rows_commit_derived": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp), ctypes.POINTER(DeriveOpts), _B,
                                      ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_expr": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,
@@ -375,6 +392,8 @@ SYMBOLS = {
     "kzg_multi_rows_commit_poseidon": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(PoseidonParams), _U32,
                                             ctypes.POINTER(PoseidonUnit), ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64),
                                             ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_sha256": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Sha256Unit),
+                                          ctypes.POINTER(DeriveOpts), _B] + [ctypes.POINTER(_U64)] * 7),
     "kzg_multi_rows_commit_derived": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp),
                                            ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_expr": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,

@@ -1105,6 +1105,52 @@ class Client:
                 "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments],
                 "perms": st["perms"], "mismatch": st["mismatch"], "first_mismatch": st["first_mismatch"]}
 
+    # ---- the bit-oriented hash chip: the SHA-256 compression per row, as a check, or as a chained round trace
+    @_guard
+    def worker_commit_sha256(self, input_handles: Sequence[int], units: Sequence[dict], usable: Optional[int] = None,
+                             tail: Sequence[str] = ()):
+        """Extension: SHA-256 compression columns of the rows of the input_handles sets, computed and committed on the device as
+        one new set.  All values are 32-bit words: a source cell is its canonical integer reduced to its low 32 bits; a cell at
+        or above 2^32 is reduced and counted (`counts`, `first`).  K and the standard initial value are built in.  units: 1 to 4
+        objects.  {"mode": "row", "state": "iv" or [8 slots], "msg": [16 slots], "out": [word indices]} runs one compression per
+        row t' < n (n = usable, or T) and commits word out[c] of the new chaining value as column c; with "expect": [rows] it
+        commits nothing and reports `mismatch` and `first_mismatch`.  {"mode": "rounds", "msg": row, "start": row or null,
+        "period": P >= 72, "iv": null or [8 words], "cols": [names]} commits the named columns (w, a, e, cw, ca, ce, sig0, sig1,
+        sum0, maj, sum1, ch) of the round trace: block b occupies rows [b P, b P + P); rows 0 .. 3 hold the incoming chaining
+        value, rows 4 .. 67 the 64 rounds with the schedule word read from msg at rows 4 .. 19, rows 68 .. 71 the feed-forward;
+        a block starts a message when b = 0, start is null or its start cell at row b P is not zero, and continues the block
+        before otherwise.  A slot is a row index or ["imm", v] with v < 2^32.  Padding is the caller's job.  usable and tail:
+        as for worker_commit_derived.  Returns the handle (null when every unit is a check), the commitments, and per unit
+        `blocks`, `messages`, `counts`, `first`, `mismatch`, `first_mismatch`.  Nothing here is a proof: the columns are prover
+        data and the argument is the caller's gates plus the range lookups of words and carries."""
+        what = "worker_commit_sha256"
+        hs = _handles(input_handles)
+        try:
+            recs = []
+            for un in units:
+                if not isinstance(un, dict):
+                    raise ValueError(f"a unit is an object: {un!r}")
+                rec = dict(un)
+                for name in ("state", "msg"):
+                    if isinstance(rec.get(name), (list, tuple)):
+                        rec[name] = [tuple(v) if isinstance(v, (list, tuple)) else v for v in rec[name]]
+                recs.append(rec)
+        except (TypeError, ValueError, IndexError, KeyError) as e:
+            raise codec.CodecError(f"{what}: units must be a list of objects: {e!r}") from e
+        if not recs:
+            raise codec.CodecError(f"{what}: units must not be empty")
+        if usable is None:
+            if tail:
+                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
+            tb = []
+        else:
+            usable, tb = self._blind(what, usable, tail)
+            if usable == 0:
+                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        rs, st = self.engine.commit_sha256(hs, recs, usable, tb)
+        return {"handle": None if rs is None else int(rs.handle),
+                "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments], **st}
+
     @staticmethod
     def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: Sequence[int], n_groups: int, width: int,
                                theta: str, gamma: str, coeff: str, active_row: Optional[int] = None,

@@ -472,6 +472,41 @@ static_assert(sizeof(PosTab) + 64 <= 4096 && POLY_MAX_ROWS < POS_IMM, "the unit 
 // full + partial + 1, canonical constants: the caller's checks
 uint32_t poseidon_cst_words(uint32_t t, uint32_t rounds, uint32_t n_units);
 void launch_poseidon(hipStream_t s, const PosTab& tab, uint64_t T, uint64_t n, uint64_t* stats);
+// ---- the SHA-256 compression columns of kzg_rows_commit_sha256 (fr_sha256.hip).  Every value is a 32-bit word: the low 32 bits
+// of a source cell's canonical integer in, int_store's cell out.  Source vector d lies at src + d T 8 words.  A ROW unit runs one
+// compression per row t' < n: slot j < 8 is word j of the chaining value, slot 8 + j word j of the block; slot[j] is an index
+// into the unit's list ld of n_ld DISTINCT source vectors (each cell is loaded once) or SHA_IMM: then the word is imm[j].  It
+// writes word col[c] of the new chaining value to vector c < n_out of out; with out null it is a check and compares that word
+// with the cell of source vector exp[c].  A ROUNDS unit walks the blocks of `period` rows: ld[0] is the message vector, ld[1]
+// the start vector (SHA_IMM: every block starts a message), imm[0 .. 7] the chaining value a message starts from; it writes
+// column id col[c] (SHA_COL_*) to vector c < n_out of out, which the caller has zeroed
+#define SHA_MAX_UNITS 4
+#define SHA_ROW 1
+#define SHA_ROUNDS 2
+#define SHA_IMM 0xffu
+#define SHA_MIN_PERIOD 72
+#define SHA_N_COLS 12
+#define SHA_LANE_WORDS 36   // LDS words per lane: ROUNDS: 16 of the window, 8 of H, 12 of a row; ROW: up to 16 loaded words
+enum { SHA_COL_W, SHA_COL_A, SHA_COL_E, SHA_COL_CW, SHA_COL_CA, SHA_COL_CE, SHA_COL_SIG0, SHA_COL_SIG1, SHA_COL_SUM0, SHA_COL_MAJ,
+       SHA_COL_SUM1, SHA_COL_CH };
+struct ShaUnit {
+    uint32_t* out;
+    uint32_t mode, period, n_out, n_ld;
+    uint32_t imm[24];
+    uint8_t slot[24], ld[24], col[SHA_N_COLS], exp[8];
+};
+struct ShaTab {
+    ShaUnit u[SHA_MAX_UNITS];
+    const uint32_t* src;
+    uint32_t n_units;
+};
+static_assert(sizeof(ShaTab) + 64 <= 4096 && POLY_MAX_ROWS < SHA_IMM && POLY_MAX_ROWS <= SHA_LANE_WORDS,
+              "the unit table rides as a kernel argument; slots ride in bytes; a row's distinct cells fit the lane's words");
+// ONE launch for the n_units units of tab.  stats: five runs of n_units words: [u] += the source cells read at or above 2^32,
+// [n_units + u] += the rows of check u with a cell that differs, [2 n_units + u] += the messages started, [3 n_units + u] <-
+// min(., the smallest row of the first kind), [4 n_units + u] <- min(., of the second).  Sources are only read and may
+// coincide; out must not overlap a source.  Returns without a launch on a table that the caller's checks should have refused
+void launch_sha256(hipStream_t s, const ShaTab& tab, uint64_t T, uint64_t n, uint64_t* stats);
 // ---- the expression columns of kzg_rows_commit_expr (fr_expr.hip): v[t] = sum_u c_u prod_f src.r[row[u][f]][(t + rot[u][f]) mod T]
 // for t < n <= T over evaluation vectors of T canonical Montgomery elements (T a power of two, at most 2^32)
 #define EXPR_MAX_TERMS 16

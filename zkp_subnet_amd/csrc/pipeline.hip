@@ -1602,6 +1602,89 @@ int rows_poseidon_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& input
     return KZG_OK;
 }
 
+// The SHA-256 compression columns (kzg_rows_commit_sha256), in the builders' frame, with checks as rows_poseidon_dev has them.
+// Each DISTINCT source row (by device pointer) that some unit reads or expects is transformed forward once.
+//   step                      launches                         per call
+//   forward transforms        launch_fr_ntt                    one per distinct source row named
+//   zero the trace columns    hipMemsetAsync                   one per ROUNDS unit
+//   every unit                launch_sha256 (k_fr_sha256)      ONE, grid y = unit
+//   tail                      launch_sort_tail                 one per output row, with `usable` only
+//   inverse transform         row_to_coeffs                    one per output row, straight into dst
+//   commit                    multi_msms_finish                ONE pass of n_out scalar sets
+// The five statistics of every unit are u64 words behind the first two evaluation slots of the record and come back in the copy
+// behind the MSM.  With n_out = 0 (checks alone) nothing is transformed back and no MSM runs.  The standard initial value is
+// written into the unit's immediates here.  Workspace: distinct sources + n_out vectors of T.
+int rows_sha256_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_units, const kzg_sha256_unit* units,
+                    uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_stats, const Blind* lay) {
+    Lane& A = H.L();
+    Cols F;
+    if (int rc = cols_begin(ctx, A, T, lay, dst, F)) return rc;
+    const uint64_t vw = F.vw, n = F.n;
+    static_assert(40 * KZG_SHA256_MAX_UNITS <= STATS_MAX && KZG_SHA256_MAX_UNITS == SHA_MAX_UNITS && KZG_SHA256_ROW == SHA_ROW &&
+                      KZG_SHA256_ROUNDS == SHA_ROUNDS && KZG_SHA256_MIN_PERIOD == SHA_MIN_PERIOD && KZG_SHA256_N_COLS == SHA_N_COLS &&
+                      KZG_SHA256_COL_W == SHA_COL_W && KZG_SHA256_COL_CE == SHA_COL_CE && KZG_SHA256_COL_CH == SHA_COL_CH,
+                  "the five statistics of every unit fit the record's evaluation slots; the header's caps and column ids are the "
+                  "kernel's");
+    static const uint32_t std_iv[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+    Sources S;
+    ShaTab tab;
+    memset(&tab, 0, sizeof(tab));
+    tab.n_units = n_units;
+    for (uint32_t u = 0; u < n_units; u++) {
+        const kzg_sha256_unit& in = units[u];
+        ShaUnit& U = tab.u[u];
+        const bool rounds = in.mode == KZG_SHA256_ROUNDS;
+        U.mode = in.mode;
+        U.period = in.period;
+        U.n_out = in.n_out;
+        for (uint32_t j = 0; j < 8; j++) U.imm[j] = (in.flags & KZG_SHA256_STD_IV) ? std_iv[j] : in.state_imm[j];
+        for (uint32_t c = 0; c < in.n_out; c++) {
+            U.col[c] = (uint8_t)in.out[c];
+            if (in.flags & KZG_SHA256_CHECK) U.exp[c] = (uint8_t)S.slot_of(inputs.r[in.expect[c]]);
+        }
+        memset(U.slot, SHA_IMM, sizeof(U.slot));
+        if (rounds) {
+            U.ld[0] = (uint8_t)S.slot_of(inputs.r[in.msg[0]]);
+            U.ld[1] = in.start == KZG_SHA256_ABSENT ? (uint8_t)SHA_IMM : (uint8_t)S.slot_of(inputs.r[in.start]);
+            continue;
+        }
+        for (uint32_t j = 0; j < 24; j++) {   // the unit's own list of distinct vectors: a cell is loaded and counted once
+            const uint32_t row = j < 8 ? in.state[j] : in.msg[j - 8];
+            if (j >= 8) U.imm[j] = in.msg_imm[j - 8];
+            if (row == KZG_SHA256_IMM) continue;
+            const uint8_t d = (uint8_t)S.slot_of(inputs.r[row]);
+            uint32_t k = 0;
+            while (k < U.n_ld && U.ld[k] != d) k++;
+            if (k == U.n_ld) U.ld[U.n_ld++] = d;
+            U.slot[j] = (uint8_t)k;
+        }
+    }
+    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_out) * T * 32 + 32));   // (+ 32: a call of immediates alone and checks has no vector)
+    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + S.nd * vw;
+    uint64_t* st = reinterpret_cast<uint64_t*>(F.rec + MR_EVAL + CNT_OFF);
+    sources_transform(ctx, A, F, S, src);
+    HIPCHK(ctx, hipMemsetAsync(st, 0, 24 * (size_t)n_units, A.stream));
+    HIPCHK(ctx, hipMemsetAsync(st + 3 * n_units, 0xff, 16 * (size_t)n_units, A.stream));   // KZG_SHA256_NONE
+    tab.src = src;
+    for (uint32_t u = 0, c = 0; u < n_units; u++) {
+        if (units[u].flags & KZG_SHA256_CHECK) continue;
+        tab.u[u].out = outv + c * vw;
+        if (units[u].mode == KZG_SHA256_ROUNDS)
+            HIPCHK(ctx, hipMemsetAsync(outv + c * vw, 0, (size_t)units[u].n_out * T * 32, A.stream));
+        c += units[u].n_out;
+    }
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_sha256(A.stream, tab, T, n, st);
+    }
+    for (uint32_t c = 0; c < n_out; c++)
+        if (int rc = emit_column(ctx, A, F, outv + c * vw, c)) return rc;
+    const uint8_t* stats;
+    if (int rc = stats_finish(ctx, H, i, F, n_out, 40 * n_units, out_c48, &stats)) return rc;
+    memcpy(out_stats, stats, 40 * (size_t)n_units);
+    return KZG_OK;
+}
+
 // The expression columns (kzg_rows_commit_expr): a set built FROM sets, every output row plain arithmetic in source rows.
 // Each DISTINCT source row (by device pointer: two indices of a repeated handle name one row) that some term names is
 // transformed forward once into its own vector of the lane's quotient workspace; a row no term names is not transformed.
