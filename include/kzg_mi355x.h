@@ -1398,8 +1398,8 @@ int kzg_rows_commit_poseidon(kzg_ctx* ctx, uint32_t n_input_handles, const uint6
  * or above 2^32 does not fit the struct; the Python layer refuses it.)  All but the last five are checked on the host before a
  * lane is taken.  After any error the context keeps serving and no set or buffer leaks.
  * OUT OF SCOPE: padding, and packing bytes into words (compose with kzg_rows_commit_alu / kzg_rows_commit_expr); bit columns
- * and spread-table forms of the words (kzg_rows_commit_derived's limbs and the lookups cover them); SHA-512, Keccak, Blake;
- * periods below 72; more than one start convention.  A single message that fills the whole column runs on one lane of the
+ * and spread-table forms of the words (kzg_rows_commit_derived's limbs and the lookups cover them); SHA-512, Keccak, Blake
+ * (Keccak-f[1600] has its own call, kzg_rows_commit_keccak); periods below 72; more than one start convention.  A single message that fills the whole column runs on one lane of the
  * device: correct, and slow.
  * SOUNDNESS: nothing here is a proof.  The columns are prover data; the argument is the caller's gates over these columns plus
  * the range lookups of words and carries.  A zero mismatch count convinces no verifier. */
@@ -1441,6 +1441,102 @@ typedef struct kzg_sha256_unit {
 int kzg_rows_commit_sha256(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_units,
                            const kzg_sha256_unit* units, const kzg_derive_opts* opts /* NULL: plain */,
                            uint8_t* out_commitments48 /* n_out * 48 */, uint64_t* out_blocks /* n_units */,
+                           uint64_t* out_messages /* n_units */, uint64_t* out_counts /* n_units */,
+                           uint64_t* out_first /* n_units */, uint64_t* out_mismatch /* n_units */,
+                           uint64_t* out_first_mismatch /* n_units */, uint64_t* out_handle);
+/* THE KECCAK-F[1600] PERMUTATION COLUMNS: a set built FROM sets, the columns of the Keccak chip -- storage and account tries, code
+ * hashes, the KECCAK256 opcode, SHA-3 and SHAKE.  A round is no polynomial expression (kzg_rows_commit_expr), it is not affine
+ * (kzg_rows_commit_recurrence) and it is no 32-bit compression (kzg_rows_commit_sha256); composed from kzg_rows_commit_alu it
+ * takes several hundred calls per block.  There are NO parameters: the 24 round constants RC and the rotation offsets r[x][y] of
+ * FIPS 202 are built in.  ALL VALUES ARE 64-BIT LANES.  A source cell is read as its canonical integer and reduced to its low
+ * 64 bits; a cell at or above 2^64 is reduced, never refused, counted once per cell in out_counts[u], and the smallest row of
+ * such a cell is out_first[u] (KZG_KECCAK_NONE: none): the convention of kzg_rows_commit_int.  Output cells are the lanes as
+ * kzg_rows_commit_int stores a 64-bit word.  Lane (x, y) of a state has the flat index x + 5 y, the lane order of FIPS 202.  The
+ * library deals in integers only; byte order is the caller's: a lane is the little-endian word of 8 message bytes.  The
+ * concatenated rows of the input_handles sets (as in kzg_rows_open) are the source columns.  A call has 1 <= n_units <=
+ * KZG_KECCAK_MAX_UNITS units.  A SLOT is a source row, or KZG_KECCAK_IMM: then the lane is the slot's immediate on every row,
+ * neither read nor counted; the immediate is 0 beside a row.  One row may serve several slots.  With n = opts->usable, or T in
+ * the plain layout:
+ *   KZG_KECCAK_ROW     for every row t' < n ONE permutation Keccak-f[1600] of the state in[0 .. 24]; output column c < n_out holds
+ *                      lane out[c] of the result; 1 <= n_out <= KZG_KECCAK_MAX_OUT, the out[c] distinct and below 25.  A call
+ *                      reads at most KZG_MAX_BATCH_OPEN distinct rows, so at least 9 slots are immediates: the shape of hashing
+ *                      a short message.  Keccak-256 of two 32-byte nodes is 8 rows, the immediate 0x01 in lane 8, 2^63 in lane
+ *                      16, zeros in the capacity, out = 0, 1, 2, 3: ONE call.  With KZG_KECCAK_CHECK the unit commits NOTHING:
+ *                      expect[c] is the source row that column c is compared with, out_mismatch[u] the number of rows t' < n
+ *                      where some expected cell differs from the computed lane and out_first_mismatch[u] the smallest such
+ *                      row, or KZG_KECCAK_NONE.  period and rate are 0, start is KZG_KECCAK_ABSENT
+ *   KZG_KECCAK_ROUNDS  the round trace, which is what a prover commits, with the period P = period >= KZG_KECCAK_MIN_PERIOD and
+ *                      the rate 1 <= rate <= 24 lanes (17: Keccak-256 and SHA3-256, 9: SHA3-512, 21: SHAKE128): block b = 0 ..
+ *                      floor(n / P) - 1 occupies rows [b P, b P + P); a block cut by n is not started.  in[0 .. 4] are the rows
+ *                      of the five message columns (in[5 .. 24] and every immediate are 0), start the row of the start column
+ *                      or KZG_KECCAK_ABSENT; out[c] < 25, distinct, names the column (KZG_KECCAK_COL_*) of output column c.  Rows
+ *                      are counted from the block's first.  With S the block's incoming state, the absorbed state is A_0[x][y]
+ *                      = S[x][y] XOR m, m the cell of row in[x] at block row y (reduced and counted) where x + 5 y < rate, else
+ *                      0: that cell is then neither read nor counted.
+ *                        rows 5 q + y, q < 24, y < 5   round q, plane y: a_x = A[x][y], the state before round q; p_x = A[x][0] ^
+ *                                                      .. ^ A[x][y], the running column parity, whose value at y = 4 is C[x];
+ *                                                      d_x = D[x] = C[x - 1] ^ rotl(C[x + 1], 1), repeated on the five rows of
+ *                                                      the round; t_x = rotl(A[x][y] ^ D[x], r[x][y]): theta and rho at the
+ *                                                      source position; b_x = B[x][y], the lane after pi: B[y'][(2 x' + 3 y')
+ *                                                      mod 5] = t of (x', y')
+ *                        rows 120 + y, y < 5           the outgoing state in the a columns; p, d, t and b are 0
+ *                        rows 125 .. P - 1, and the rows floor(n / P) P .. n - 1: 0 in every column
+ *                      so that chi and iota are row-local: a_x at row + 5 equals b_x ^ (~b_(x + 1) & b_(x + 2)), XOR RC[q] where
+ *                      x = y = 0.  CHAINING: block b starts a message when b = 0, when start is absent, or when the start cell
+ *                      at row b P is not zero (reduced like every cell); its S is then all zero; else S is the outgoing state
+ *                      of block b - 1.  Start cells are read at the rows b P of existing blocks only.  KZG_KECCAK_CHECK is
+ *                      refused.  Padding, domain suffixes and squeezing beyond one block are the caller's
+ * out_perms[u] is the number of permutations unit u ran: n for a ROW unit, floor(n / P) for a ROUNDS unit; out_messages[u] the
+ * blocks that started a message (0 on a ROW unit); out_mismatch[u] = 0 and out_first_mismatch[u] = KZG_KECCAK_NONE on a unit
+ * that commits.  All committed columns of a call form ONE new set of the same worker and length, in the order of units, then
+ * of out: out_commitments48[c] equals kzg_rows_commit(i, n_out, these rows, T, 1, ..)[c] byte for byte, and *out_handle opens,
+ * evaluates, combines, releases, goes stale and counts against KZG_MAX_ROW_SETS like any other.  A call made of checks alone
+ * creates no set (*out_handle = 0, out_commitments48 may be null), runs no inverse transform and no MSM.  ONE kernel launch
+ * computes every unit; nothing row-sized crosses the host link.  A call reads at most KZG_MAX_BATCH_OPEN distinct rows and
+ * commits at most KZG_MAX_BATCH_OPEN; more columns of a trace take a second unit or call.  opts, handle lists, worker, T,
+ * staleness and threads: as for kzg_rows_commit_sha256.  KZG_E_ARG with a message that begins "keccak:" and names the cause:
+ * n_units outside its range; an unknown mode or flag; KZG_KECCAK_CHECK on a ROUNDS unit; a period below 125 (not 0 on a ROW
+ * unit); a rate outside 1 .. 24 (not 0 on a ROW unit); n_out outside its range, a lane index or column id at or above 25 or a
+ * repeated one; an immediate, in entry or start the mode does not take; more than KZG_MAX_BATCH_OPEN output rows or distinct
+ * input rows; a row index beyond the concatenation; T above 2^32; the usable and tail refusals of kzg_rows_commit_derived; the
+ * handle refusals of kzg_rows_open.  (An immediate at or above 2^64 does not fit the struct; the Python layer refuses it.)  All
+ * but the last five are checked on the host before a lane is taken.  After any error the context keeps serving and no set or
+ * buffer leaks.
+ * OUT OF SCOPE: padding and byte packing; bit columns and spread-table forms of the lanes (kzg_rows_commit_derived's limbs and
+ * the lookups cover them); Keccak-f[800] and smaller widths; squeezing more than one block; typed inputs.  A ROUNDS unit runs
+ * one lane of the device per message: a single message that fills the whole column is correct, and slow.
+ * SOUNDNESS: nothing here is a proof.  The columns are prover data; the argument is the caller's gates over these columns plus
+ * the range lookups of the lanes.  A zero mismatch count convinces no verifier. */
+#define KZG_KECCAK_ROW    1
+#define KZG_KECCAK_ROUNDS 2
+#define KZG_KECCAK_CHECK  1u               /* flags (ROW): compare with expect, commit nothing */
+#define KZG_KECCAK_IMM    0xffffffffu      /* a slot: the lane is the slot's immediate */
+#define KZG_KECCAK_ABSENT 0xffffffffu      /* start (ROUNDS): every block starts a message */
+#define KZG_KECCAK_NONE   0xffffffffffffffffull   /* out_first, out_first_mismatch: none */
+#define KZG_KECCAK_MAX_UNITS 4
+#define KZG_KECCAK_MIN_PERIOD 125
+#define KZG_KECCAK_MAX_OUT 16
+#define KZG_KECCAK_N_COLS 25
+#define KZG_KECCAK_COL_A 0                 /* a0 .. a4: KZG_KECCAK_COL_A + x, and so for the four below */
+#define KZG_KECCAK_COL_P 5
+#define KZG_KECCAK_COL_D 10
+#define KZG_KECCAK_COL_T 15
+#define KZG_KECCAK_COL_B 20
+typedef struct kzg_keccak_unit {
+    uint32_t mode;               /* KZG_KECCAK_ROW or KZG_KECCAK_ROUNDS */
+    uint32_t flags;              /* 0 or KZG_KECCAK_CHECK (ROW) */
+    uint32_t n_out;              /* 1 .. KZG_KECCAK_MAX_OUT */
+    uint32_t period;             /* ROUNDS: P >= 125; ROW: 0 */
+    uint32_t rate;               /* ROUNDS: 1 .. 24 lanes; ROW: 0 */
+    uint32_t start;              /* ROUNDS: the row of the start column, or KZG_KECCAK_ABSENT; ROW: KZG_KECCAK_ABSENT */
+    uint64_t imm[25];            /* ROW: [j] the lane where in[j] = KZG_KECCAK_IMM; 0 beside a row; ROUNDS: 0 */
+    uint32_t in[25];             /* ROW: [j] the slot of state lane j = x + 5 y; ROUNDS: in[x < 5] the row of message column x, the rest 0 */
+    uint32_t out[16];            /* [c < n_out] ROW: the lane of output column c; ROUNDS: its KZG_KECCAK_COL_* */
+    uint32_t expect[16];         /* [c < n_out] with KZG_KECCAK_CHECK: the row that column c is compared with */
+} kzg_keccak_unit;
+int kzg_rows_commit_keccak(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_units,
+                           const kzg_keccak_unit* units, const kzg_derive_opts* opts /* NULL: plain */,
+                           uint8_t* out_commitments48 /* n_out * 48 */, uint64_t* out_perms /* n_units */,
                            uint64_t* out_messages /* n_units */, uint64_t* out_counts /* n_units */,
                            uint64_t* out_first /* n_units */, uint64_t* out_mismatch /* n_units */,
                            uint64_t* out_first_mismatch /* n_units */, uint64_t* out_handle);
@@ -1842,6 +1938,11 @@ int kzg_multi_rows_commit_poseidon(kzg_multi* mh, uint32_t i, uint32_t n_input_h
 int kzg_multi_rows_commit_sha256(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                  uint32_t n_units, const kzg_sha256_unit* units, const kzg_derive_opts* opts,
                                  uint8_t* out_commitments48, uint64_t* out_blocks, uint64_t* out_messages, uint64_t* out_counts,
+                                 uint64_t* out_first, uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_handle);
+/* kzg_rows_commit_keccak on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_keccak(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                 uint32_t n_units, const kzg_keccak_unit* units, const kzg_derive_opts* opts,
+                                 uint8_t* out_commitments48, uint64_t* out_perms, uint64_t* out_messages, uint64_t* out_counts,
                                  uint64_t* out_first, uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).

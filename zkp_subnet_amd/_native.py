@@ -58,6 +58,15 @@ KZG_SHA256_ABSENT = 0xffffffff
 KZG_SHA256_NONE = 0xffffffffffffffff
 KZG_SHA256_MAX_UNITS, KZG_SHA256_MIN_PERIOD, KZG_SHA256_N_COLS = 4, 72, 12
 KZG_SHA256_COLS = ("w", "a", "e", "cw", "ca", "ce", "sig0", "sig1", "sum0", "maj", "sum1", "ch")
+# kzg_rows_commit_keccak: kzg_keccak_unit.mode, the flag, a slot that holds an immediate, "no start column", "none", the limits,
+# and the column names of a rounds unit in the order of their ids: KZG_KECCAK_COL_A + x, _P, _D, _T, _B
+KZG_KECCAK_ROW, KZG_KECCAK_ROUNDS = 1, 2
+KZG_KECCAK_CHECK = 1
+KZG_KECCAK_IMM = 0xffffffff
+KZG_KECCAK_ABSENT = 0xffffffff
+KZG_KECCAK_NONE = 0xffffffffffffffff
+KZG_KECCAK_MAX_UNITS, KZG_KECCAK_MIN_PERIOD, KZG_KECCAK_MAX_OUT, KZG_KECCAK_N_COLS = 4, 125, 16, 25
+KZG_KECCAK_COLS = tuple(f"{k}{x}" for k in "apdtb" for x in range(5))
 KZG_MAX_EXPR_FACTORS = 8   # kzg_rows_commit_expr: factors of one term
 KZG_EXPR_CHECK = 1   # kzg_expr.flags: evaluate and count only
 KZG_EXPR_NONE = 0xffffffffffffffff   # out_first: no non-zero cell
@@ -173,6 +182,12 @@ class Sha256Unit(ctypes.Structure):
                 ("state_imm", _U32 * 8), ("msg", _U32 * 16), ("msg_imm", _U32 * 16), ("out", _U32 * 12), ("expect", _U32 * 8)]
 
 
+class KeccakUnit(ctypes.Structure):
+    """kzg_keccak_unit"""
+    _fields_ = [("mode", _U32), ("flags", _U32), ("n_out", _U32), ("period", _U32), ("rate", _U32), ("start", _U32),
+                ("imm", _U64 * 25), ("in_", _U32 * 25), ("out", _U32 * 16), ("expect", _U32 * 16)]
+
+
 class Col(ctypes.Structure):
     """kzg_col"""
     _fields_ = [("data", ctypes.c_void_p), ("count", ctypes.c_uint64), ("kind", ctypes.c_uint32), ("fill_be32", ctypes.c_char_p)]
@@ -261,6 +276,8 @@ SYMBOLS = {
                                       ctypes.POINTER(PoseidonUnit), ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64),
                                       ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_sha256": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Sha256Unit), ctypes.POINTER(DeriveOpts),
+                                    _B] + [ctypes.POINTER(_U64)] * 7),
+    "kzg_rows_commit_keccak": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(KeccakUnit), ctypes.POINTER(DeriveOpts),
                                     _B] + [ctypes.POINTER(_U64)] * 7),
     "kzg_rows_commit_derived": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp), ctypes.POINTER(DeriveOpts), _B,
                                      ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
@@ -393,6 +410,8 @@ SYMBOLS = {
                                             ctypes.POINTER(PoseidonUnit), ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64),
                                             ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_sha256": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Sha256Unit),
+                                          ctypes.POINTER(DeriveOpts), _B] + [ctypes.POINTER(_U64)] * 7),
+    "kzg_multi_rows_commit_keccak": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(KeccakUnit),
                                           ctypes.POINTER(DeriveOpts), _B] + [ctypes.POINTER(_U64)] * 7),
     "kzg_multi_rows_commit_derived": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp),
                                            ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),

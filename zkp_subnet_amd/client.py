@@ -1151,6 +1151,52 @@ class Client:
         return {"handle": None if rs is None else int(rs.handle),
                 "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments], **st}
 
+    # ---- the Keccak chip: Keccak-f[1600] per row, as a check, or as a chained round trace of 64-bit lanes
+    @_guard
+    def worker_commit_keccak(self, input_handles: Sequence[int], units: Sequence[dict], usable: Optional[int] = None,
+                             tail: Sequence[str] = ()):
+        """Extension: Keccak-f[1600] permutation columns of the rows of the input_handles sets, computed and committed on the
+        device as one new set.  All values are 64-bit lanes: a source cell is its canonical integer reduced to its low 64 bits;
+        a cell at or above 2^64 is reduced and counted (`counts`, `first`).  The round constants and rotation offsets of FIPS
+        202 are built in; lane (x, y) has the index x + 5 y, and a lane is the little-endian word of 8 message bytes.  units: 1
+        to 4 objects.  {"mode": "row", "in": [25 slots], "out": [lane indices]} runs one permutation per row t' < n (n = usable,
+        or T) and commits lane out[c] of the result as column c; with "expect": [rows] it commits nothing and reports `mismatch`
+        and `first_mismatch`.  {"mode": "rounds", "msg": [5 rows], "rate": 1 .. 24, "start": row or null, "period": P >= 125,
+        "cols": [names]} commits the named columns (a0 .. a4, p0 .. p4, d0 .. d4, t0 .. t4, b0 .. b4) of the round trace: block b
+        occupies rows [b P, b P + P); rows 5 q + y hold round q, plane y, rows 120 .. 124 the outgoing state in the a columns;
+        lane x + 5 y < rate absorbs the cell of msg[x] at block row y; a block starts a message when b = 0, start is null or its
+        start cell at row b P is not zero, and continues the block before otherwise.  A slot is a row index or ["imm", v] with
+        v < 2^64.  Padding is the caller's job.  usable and tail: as for worker_commit_derived.  Returns the handle (null when
+        every unit is a check), the commitments, and per unit `perms`, `messages`, `counts`, `first`, `mismatch`,
+        `first_mismatch`.  Nothing here is a proof: the columns are prover data and the argument is the caller's gates plus the
+        range lookups of the lanes."""
+        what = "worker_commit_keccak"
+        hs = _handles(input_handles)
+        try:
+            recs = []
+            for un in units:
+                if not isinstance(un, dict):
+                    raise ValueError(f"a unit is an object: {un!r}")
+                rec = dict(un)
+                if isinstance(rec.get("in"), (list, tuple)):
+                    rec["in"] = [tuple(v) if isinstance(v, (list, tuple)) else v for v in rec["in"]]
+                recs.append(rec)
+        except (TypeError, ValueError, IndexError, KeyError) as e:
+            raise codec.CodecError(f"{what}: units must be a list of objects: {e!r}") from e
+        if not recs:
+            raise codec.CodecError(f"{what}: units must not be empty")
+        if usable is None:
+            if tail:
+                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
+            tb = []
+        else:
+            usable, tb = self._blind(what, usable, tail)
+            if usable == 0:
+                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        rs, st = self.engine.commit_keccak(hs, recs, usable, tb)
+        return {"handle": None if rs is None else int(rs.handle),
+                "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments], **st}
+
     @staticmethod
     def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: Sequence[int], n_groups: int, width: int,
                                theta: str, gamma: str, coeff: str, active_row: Optional[int] = None,

@@ -12,6 +12,7 @@
 //   fr_wide.hip   the kernel of kzg_rows_commit_wide: multi-limb add, sub, mul, divmod, mulmod and the carries of its limb identity
 //   fr_poseidon.hip the kernel of kzg_rows_commit_poseidon: the Hades permutation with x^5 per row, as a check, or as a round trace
 //   fr_sha256.hip the kernel of kzg_rows_commit_sha256: the SHA-256 compression per row, as a check, or as a chained round trace
+//   fr_keccak.hip the kernel of kzg_rows_commit_keccak: Keccak-f[1600] per row, as a check, or as a chained round trace of 64-bit lanes
 //   fr_expr.hip   the kernel of kzg_rows_commit_expr: sums of products of rotated resident columns on H, counted and stored
 //   fr_recur.hip  the scan of kzg_rows_commit_recurrence: v[t + 1] = A[t] v[t] + B[t] as a ladder over affine maps
 //   fr_join.hip   the hash join of kzg_rows_commit_multiplicities, and the fetch of kzg_rows_commit_fetch that walks it
@@ -516,6 +517,12 @@ int rows_poseidon_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& input
 // commitments and five runs of n_units statistics (over-range cells, mismatching rows, messages, then the smallest row of the
 // first and of the second kind, KZG_SHA256_NONE: none).  lay: as for rows_derived_dev
 int rows_sha256_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_units, const kzg_sha256_unit* units,
+                    uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_stats, const Blind* lay);
+// the n_out committed columns of the n_units Keccak units (checked by the caller: modes, flags, periods, rates, out lists, rows
+// inside `inputs`) into a new n_out-row set's buffer dst (null when n_out = 0: then no transform back and no MSM runs): their
+// commitments and five runs of n_units statistics (over-range cells, mismatching rows, messages, then the smallest row of the
+// first and of the second kind, KZG_KECCAK_NONE: none).  lay: as for rows_derived_dev
+int rows_keccak_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_units, const kzg_keccak_unit* units,
                     uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_stats, const Blind* lay);
 // the n_out committed ones of the n_exprs expressions (checked by the caller: term counts and lengths in range, rows inside
 // `inputs`, rotations reduced into [0, T), canonical coefficients; is_check[e] != 0: expression e is only counted) into a new

@@ -507,6 +507,44 @@ static_assert(sizeof(ShaTab) + 64 <= 4096 && POLY_MAX_ROWS < SHA_IMM && POLY_MAX
 // min(., the smallest row of the first kind), [4 n_units + u] <- min(., of the second).  Sources are only read and may
 // coincide; out must not overlap a source.  Returns without a launch on a table that the caller's checks should have refused
 void launch_sha256(hipStream_t s, const ShaTab& tab, uint64_t T, uint64_t n, uint64_t* stats);
+// ---- the Keccak-f[1600] permutation columns of kzg_rows_commit_keccak (fr_keccak.hip).  Every value is a 64-bit lane: the low 64
+// bits of a source cell's canonical integer in, int_store's cell out; lane (x, y) of a state has the flat index x + 5 y.  Source
+// vector d lies at src + d T 8 words.  A ROW unit runs one permutation per row t' < n: slot[j] of state lane j is an index into
+// the unit's list ld of n_ld DISTINCT source vectors (each cell is loaded once) or KEC_IMM: then the lane is imm[j].  It writes
+// lane col[c] of the permuted state to vector c < n_out of out; with out null it is a check and compares that lane with the cell
+// of source vector exp[c].  A ROUNDS unit walks the blocks of `period` rows: ld[0 .. 4] are the message vectors (lane x + 5 y <
+// rate of a block absorbs the cell of ld[x] at block row y), ld[5] the start vector (KEC_IMM: every block starts a message);
+// bit i of nocount: the cell of absorbed lane i is counted by another reader of the same cell (an earlier lane of the same
+// vector, or the start cell); it writes column id col[c] (KEC_COL_A + x, .., KEC_COL_B + x) to vector c < n_out of out, which
+// the caller has zeroed
+#define KEC_MAX_UNITS 4
+#define KEC_ROW 1
+#define KEC_ROUNDS 2
+#define KEC_IMM 0xffu
+#define KEC_MIN_PERIOD 125
+#define KEC_N_COLS 25
+#define KEC_MAX_OUT 16
+#define KEC_LANE_WORDS 50   // LDS words per lane: 25 values of 64 bits: a ROW unit's loaded cells, then its permuted state; a
+                            // ROUNDS unit's absorbed cells, then the 25 values of a stage
+enum { KEC_COL_A = 0, KEC_COL_P = 5, KEC_COL_D = 10, KEC_COL_T = 15, KEC_COL_B = 20 };
+struct KecUnit {
+    uint32_t* out;
+    uint32_t mode, period, n_out, n_ld, rate, nocount;
+    uint64_t imm[25];
+    uint8_t slot[25], ld[POLY_MAX_ROWS], col[KEC_MAX_OUT], exp[KEC_MAX_OUT];
+};
+struct KecTab {
+    KecUnit u[KEC_MAX_UNITS];
+    const uint32_t* src;
+    uint32_t n_units;
+};
+static_assert(sizeof(KecTab) + 64 <= 4096 && POLY_MAX_ROWS < KEC_IMM && 2 * POLY_MAX_ROWS <= KEC_LANE_WORDS && POLY_MAX_ROWS >= 6,
+              "the unit table rides as a kernel argument; slots ride in bytes; a row's distinct cells fit the lane's words");
+// ONE launch for the n_units units of tab.  stats: five runs of n_units words: [u] += the source cells read at or above 2^64,
+// [n_units + u] += the rows of check u with a cell that differs, [2 n_units + u] += the messages started, [3 n_units + u] <-
+// min(., the smallest row of the first kind), [4 n_units + u] <- min(., of the second).  Sources are only read and may
+// coincide; out must not overlap a source.  Returns without a launch on a table that the caller's checks should have refused
+void launch_keccak(hipStream_t s, const KecTab& tab, uint64_t T, uint64_t n, uint64_t* stats);
 // ---- the expression columns of kzg_rows_commit_expr (fr_expr.hip): v[t] = sum_u c_u prod_f src.r[row[u][f]][(t + rot[u][f]) mod T]
 // for t < n <= T over evaluation vectors of T canonical Montgomery elements (T a power of two, at most 2^32)
 #define EXPR_MAX_TERMS 16

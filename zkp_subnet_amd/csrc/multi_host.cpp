@@ -549,6 +549,15 @@ int kzg_multi_rows_commit_sha256(kzg_multi* mh, uint32_t i, uint32_t n_input_han
                                      out_messages, out_counts, out_first, out_mismatch, out_first_mismatch, out_handle);
     });
 }
+int kzg_multi_rows_commit_keccak(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                 uint32_t n_units, const kzg_keccak_unit* units, const kzg_derive_opts* opts,
+                                 uint8_t* out_commitments48, uint64_t* out_perms, uint64_t* out_messages, uint64_t* out_counts,
+                                 uint64_t* out_first, uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_handle) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_keccak(c, s, n_input_handles, input_handles, n_units, units, opts, out_commitments48, out_perms,
+                                     out_messages, out_counts, out_first, out_mismatch, out_first_mismatch, out_handle);
+    });
+}
 int kzg_multi_rows_commit_expr(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                uint32_t n_exprs, const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48,
                                uint64_t* out_nonzero, uint64_t* out_first, uint64_t* out_handle) {

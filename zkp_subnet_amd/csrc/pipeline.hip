@@ -1685,6 +1685,94 @@ int rows_sha256_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs,
     return KZG_OK;
 }
 
+// The Keccak-f[1600] permutation columns (kzg_rows_commit_keccak), in the builders' frame, step for step as rows_sha256_dev:
+//   step                      launches                         per call
+//   forward transforms        launch_fr_ntt                    one per distinct source row named
+//   zero the trace columns    hipMemsetAsync                   one per ROUNDS unit
+//   every unit                launch_keccak (k_fr_keccak)      ONE, grid y = unit
+//   tail                      launch_sort_tail                 one per output row, with `usable` only
+//   inverse transform         row_to_coeffs                    one per output row, straight into dst
+//   commit                    multi_msms_finish                ONE pass of n_out scalar sets
+// The five statistics of every unit are u64 words behind the first two evaluation slots of the record and come back in the copy
+// behind the MSM.  With n_out = 0 (checks alone) nothing is transformed back and no MSM runs.  A cell that several absorbed
+// lanes of a ROUNDS unit read (a repeated message row, the start column among the message rows) is marked here so that one
+// reader counts it.  Workspace: distinct sources + n_out vectors of T.
+int rows_keccak_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t n_units, const kzg_keccak_unit* units,
+                    uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_stats, const Blind* lay) {
+    Lane& A = H.L();
+    Cols F;
+    if (int rc = cols_begin(ctx, A, T, lay, dst, F)) return rc;
+    const uint64_t vw = F.vw, n = F.n;
+    static_assert(40 * KZG_KECCAK_MAX_UNITS <= STATS_MAX && KZG_KECCAK_MAX_UNITS == KEC_MAX_UNITS && KZG_KECCAK_ROW == KEC_ROW &&
+                      KZG_KECCAK_ROUNDS == KEC_ROUNDS && KZG_KECCAK_MIN_PERIOD == KEC_MIN_PERIOD && KZG_KECCAK_N_COLS == KEC_N_COLS &&
+                      KZG_KECCAK_MAX_OUT == KEC_MAX_OUT && KZG_KECCAK_COL_A == KEC_COL_A && KZG_KECCAK_COL_P == KEC_COL_P &&
+                      KZG_KECCAK_COL_D == KEC_COL_D && KZG_KECCAK_COL_T == KEC_COL_T && KZG_KECCAK_COL_B == KEC_COL_B,
+                  "the five statistics of every unit fit the record's evaluation slots; the header's caps and column ids are the "
+                  "kernel's");
+    Sources S;
+    KecTab tab;
+    memset(&tab, 0, sizeof(tab));
+    tab.n_units = n_units;
+    for (uint32_t u = 0; u < n_units; u++) {
+        const kzg_keccak_unit& in = units[u];
+        KecUnit& U = tab.u[u];
+        const bool rounds = in.mode == KZG_KECCAK_ROUNDS;
+        U.mode = in.mode;
+        U.period = in.period;
+        U.rate = in.rate;
+        U.n_out = in.n_out;
+        for (uint32_t c = 0; c < in.n_out; c++) {
+            U.col[c] = (uint8_t)in.out[c];
+            if (in.flags & KZG_KECCAK_CHECK) U.exp[c] = (uint8_t)S.slot_of(inputs.r[in.expect[c]]);
+        }
+        memset(U.slot, KEC_IMM, sizeof(U.slot));
+        if (rounds) {
+            for (uint32_t x = 0; x < 5; x++) U.ld[x] = (uint8_t)S.slot_of(inputs.r[in.in[x]]);
+            U.ld[5] = in.start == KZG_KECCAK_ABSENT ? (uint8_t)KEC_IMM : (uint8_t)S.slot_of(inputs.r[in.start]);
+            for (uint32_t l = 0; l < in.rate; l++) {
+                const uint32_t x = l % 5;
+                bool counted = l < 5 && U.ld[x] == U.ld[5];
+                for (uint32_t k = 0; k < x; k++) counted |= U.ld[k] == U.ld[x];
+                U.nocount |= (uint32_t)counted << l;
+            }
+            continue;
+        }
+        for (uint32_t j = 0; j < 25; j++) {   // the unit's own list of distinct vectors: a cell is loaded and counted once
+            U.imm[j] = in.imm[j];
+            if (in.in[j] == KZG_KECCAK_IMM) continue;
+            const uint8_t d = (uint8_t)S.slot_of(inputs.r[in.in[j]]);
+            uint32_t k = 0;
+            while (k < U.n_ld && U.ld[k] != d) k++;
+            if (k == U.n_ld) U.ld[U.n_ld++] = d;
+            U.slot[j] = (uint8_t)k;
+        }
+    }
+    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_out) * T * 32 + 32));   // (+ 32: a call of immediates alone and checks has no vector)
+    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + S.nd * vw;
+    uint64_t* st = reinterpret_cast<uint64_t*>(F.rec + MR_EVAL + CNT_OFF);
+    sources_transform(ctx, A, F, S, src);
+    HIPCHK(ctx, hipMemsetAsync(st, 0, 24 * (size_t)n_units, A.stream));
+    HIPCHK(ctx, hipMemsetAsync(st + 3 * n_units, 0xff, 16 * (size_t)n_units, A.stream));   // KZG_KECCAK_NONE
+    tab.src = src;
+    for (uint32_t u = 0, c = 0; u < n_units; u++) {
+        if (units[u].flags & KZG_KECCAK_CHECK) continue;
+        tab.u[u].out = outv + c * vw;
+        if (units[u].mode == KZG_KECCAK_ROUNDS)
+            HIPCHK(ctx, hipMemsetAsync(outv + c * vw, 0, (size_t)units[u].n_out * T * 32, A.stream));
+        c += units[u].n_out;
+    }
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_keccak(A.stream, tab, T, n, st);
+    }
+    for (uint32_t c = 0; c < n_out; c++)
+        if (int rc = emit_column(ctx, A, F, outv + c * vw, c)) return rc;
+    const uint8_t* stats;
+    if (int rc = stats_finish(ctx, H, i, F, n_out, 40 * n_units, out_c48, &stats)) return rc;
+    memcpy(out_stats, stats, 40 * (size_t)n_units);
+    return KZG_OK;
+}
+
 // The expression columns (kzg_rows_commit_expr): a set built FROM sets, every output row plain arithmetic in source rows.
 // Each DISTINCT source row (by device pointer: two indices of a repeated handle name one row) that some term names is
 // transformed forward once into its own vector of the lane's quotient workspace; a row no term names is not transformed.

@@ -1683,6 +1683,92 @@ int rows_sha256(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const
     return KZG_OK;
 }
 
+// kzg_rows_commit_keccak: a BuilderCall around its own checks; as in rows_sha256, no reservation and no set when every unit is a
+// check.  Modes, flags, periods, rates, out lists and the entries a mode does not take are checked here, on the host, before a
+// lane is taken
+int rows_keccak(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_units,
+                const kzg_keccak_unit* units, const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_perms,
+                uint64_t* out_messages, uint64_t* out_counts, uint64_t* out_first, uint64_t* out_mismatch,
+                uint64_t* out_first_mismatch, uint64_t* out_handle) {
+    if (!ctx || !input_handles || !out_perms || !out_messages || !out_counts || !out_first || !out_mismatch ||
+        !out_first_mismatch || !out_handle)
+        return KZG_E_ARG;
+    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "keccak: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (n_units == 0 || n_units > KZG_KECCAK_MAX_UNITS || !units)
+        return fail(ctx, KZG_E_ARG, "keccak: n_units must be in [1, KZG_KECCAK_MAX_UNITS]");
+    uint32_t n_out = 0, max_row = 0, n_seen = 0, seen[(25 + KZG_KECCAK_MAX_OUT + 1) * KZG_KECCAK_MAX_UNITS];
+    auto see = [&](uint32_t row) {
+        max_row = std::max(max_row, row);
+        uint32_t d = 0;
+        while (d < n_seen && seen[d] != row) d++;
+        if (d == n_seen) seen[n_seen++] = row;
+    };
+    for (uint32_t u = 0; u < n_units; u++) {
+        const kzg_keccak_unit& U = units[u];
+        if (U.mode != KZG_KECCAK_ROW && U.mode != KZG_KECCAK_ROUNDS)
+            return fail(ctx, KZG_E_ARG, "keccak: unknown mode (KZG_KECCAK_ROW or KZG_KECCAK_ROUNDS)");
+        if (U.flags & ~KZG_KECCAK_CHECK) return fail(ctx, KZG_E_ARG, "keccak: flags must be 0 or KZG_KECCAK_CHECK");
+        const bool rounds = U.mode == KZG_KECCAK_ROUNDS, check = U.flags & KZG_KECCAK_CHECK;
+        if (rounds && check) return fail(ctx, KZG_E_ARG, "keccak: expect (KZG_KECCAK_CHECK) belongs to ROW units, not to ROUNDS");
+        if (rounds ? U.period < KZG_KECCAK_MIN_PERIOD : U.period != 0)
+            return fail(ctx, KZG_E_ARG, "keccak: the period P of a ROUNDS unit must be at least 125 (0 on a ROW unit)");
+        if (rounds ? U.rate == 0 || U.rate > 24 : U.rate != 0)
+            return fail(ctx, KZG_E_ARG, "keccak: the rate of a ROUNDS unit must be in [1, 24] lanes (0 on a ROW unit)");
+        if (U.n_out == 0 || U.n_out > KZG_KECCAK_MAX_OUT)
+            return fail(ctx, KZG_E_ARG, "keccak: n_out must be in [1, KZG_KECCAK_MAX_OUT]");
+        uint32_t taken = 0;
+        for (uint32_t c = 0; c < U.n_out; c++) {
+            if (U.out[c] >= KZG_KECCAK_N_COLS)
+                return fail(ctx, KZG_E_ARG, "keccak: a lane index must be below 25 (ROUNDS: a column id below KZG_KECCAK_N_COLS)");
+            if (taken >> U.out[c] & 1) return fail(ctx, KZG_E_ARG, "keccak: a lane index or column id is repeated");
+            taken |= 1u << U.out[c];
+            if (check) see(U.expect[c]);
+        }
+        for (uint32_t j = 0; j < 25; j++) {
+            if (rounds) {
+                if (j < 5 && U.in[j] == KZG_KECCAK_IMM)
+                    return fail(ctx, KZG_E_ARG, "keccak: the message columns of a ROUNDS unit are rows, not immediates");
+                if ((j >= 5 && U.in[j]) || U.imm[j])
+                    return fail(ctx, KZG_E_ARG, "keccak: in[5 .. 24] and imm must be 0 on a ROUNDS unit");
+                if (j < 5) see(U.in[j]);
+            } else if (U.in[j] != KZG_KECCAK_IMM) {
+                if (U.imm[j]) return fail(ctx, KZG_E_ARG, "keccak: the immediate must be 0 beside a row");
+                see(U.in[j]);
+            }
+        }
+        if (U.start != KZG_KECCAK_ABSENT) {
+            if (!rounds) return fail(ctx, KZG_E_ARG, "keccak: start belongs to ROUNDS units (KZG_KECCAK_ABSENT on a ROW unit)");
+            see(U.start);
+        }
+        if (n_seen > KZG_MAX_BATCH_OPEN)
+            return fail(ctx, KZG_E_ARG, "keccak: a call reads at most KZG_MAX_BATCH_OPEN distinct input rows");
+        n_out += check ? 0 : U.n_out;
+    }
+    if (n_out > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "keccak: n_out, the committed columns of all units, must be at most KZG_MAX_BATCH_OPEN");
+    if (n_out && !out_commitments48) return KZG_E_ARG;
+    BuilderCall C(ctx, "keccak");
+    RowTab it;
+    uint32_t ki = 0;
+    if (int rc = C.begin("keccak", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
+    if (n_seen && max_row >= ki) return fail(ctx, KZG_E_ARG, "keccak: a row must index the concatenated rows of the input sets");
+    if (int rc = C.ready(n_out, 32, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ)) return rc;
+    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    uint64_t stats[5 * KZG_KECCAK_MAX_UNITS];
+    if (int rc = rows_keccak_dev(ctx, C.H, C.i, it, n_units, units, n_out, C.T, C.dst(), c48, stats, C.blind)) return rc;
+    if (n_out) memcpy(out_commitments48, c48, 48 * (size_t)n_out);
+    const uint64_t n = C.blind ? C.blind->usable : C.T;
+    for (uint32_t u = 0; u < n_units; u++) out_perms[u] = units[u].mode == KZG_KECCAK_ROUNDS ? n / units[u].period : n;
+    memcpy(out_counts, stats, 8 * (size_t)n_units);
+    memcpy(out_mismatch, stats + n_units, 8 * (size_t)n_units);
+    memcpy(out_messages, stats + 2 * n_units, 8 * (size_t)n_units);
+    memcpy(out_first, stats + 3 * n_units, 8 * (size_t)n_units);
+    memcpy(out_first_mismatch, stats + 4 * n_units, 8 * (size_t)n_units);
+    *out_handle = C.commit();
+    return KZG_OK;
+}
+
 // The terms of an expression as rows_expr_dev takes them: a kzg_quotient_terms checked (counts, lengths, canonical
 // coefficients) and copied into the zeroed plan `pl`, its rotations as given into `rots` -- they are reduced by expr_reduce once
 // T is known -- and the largest row it names into *max_row.  may_be_empty: n_terms = 0 is accepted and leaves pl empty
@@ -2635,6 +2721,13 @@ int kzg_rows_commit_sha256(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_
                            uint64_t* out_blocks, uint64_t* out_messages, uint64_t* out_counts, uint64_t* out_first,
                            uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_handle) {
     return rows_sha256(ctx, UINT32_MAX, n_input_handles, input_handles, n_units, units, opts, out_commitments48, out_blocks,
+                       out_messages, out_counts, out_first, out_mismatch, out_first_mismatch, out_handle);
+}
+int kzg_rows_commit_keccak(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_units,
+                           const kzg_keccak_unit* units, const kzg_derive_opts* opts, uint8_t* out_commitments48,
+                           uint64_t* out_perms, uint64_t* out_messages, uint64_t* out_counts, uint64_t* out_first,
+                           uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_handle) {
+    return rows_keccak(ctx, UINT32_MAX, n_input_handles, input_handles, n_units, units, opts, out_commitments48, out_perms,
                        out_messages, out_counts, out_first, out_mismatch, out_first_mismatch, out_handle);
 }
 int kzg_rows_commit_expr(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,

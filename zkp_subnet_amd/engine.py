@@ -1547,6 +1547,142 @@ class HipEngine:
         return rs, {"blocks": [int(v) for v in st[0]], "messages": [int(v) for v in st[1]], "counts": [int(v) for v in st[2]],
                     "first": none(st[3]), "mismatch": [int(v) for v in st[4]], "first_mismatch": none(st[5])}
 
+    # ---- a set built from sets: Keccak-f[1600] per row, as a check, or as a chained round trace of 64-bit lanes
+    _KECCAK_ROW_KEYS = ("mode", "in", "out", "expect")
+    _KECCAK_ROUNDS_KEYS = ("mode", "msg", "rate", "start", "period", "cols")
+
+    @classmethod
+    def keccak_call(cls, units, what: str = "commit_keccak") -> List[tuple]:
+        """Per unit the kzg_keccak_unit fields (mode, flags, n_out, period, rate, start, imm[25], in[25], out[16], expect[16])
+        of a call.  A unit is a mapping.  {"mode": "row", "in": 25 slots, "out": 1 .. 16 distinct lane indices below 25} and,
+        for a check, "expect": one row per entry of out.  {"mode": "rounds", "msg": 5 rows, "rate": 1 .. 24, "start": row or
+        None, "period": P >= 125, "cols": 1 .. 16 distinct names of _native.KZG_KECCAK_COLS}.  A slot is a row index or ("imm",
+        v) with v < 2^64; lane (x, y) is slot x + 5 y.  Raises KzgError(KZG_E_ARG) with the cause; needs no device."""
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: keccak: {why}")   # noqa: E731
+        is_u = lambda v, top: isinstance(v, int) and not isinstance(v, bool) and 0 <= v < top   # noqa: E731
+        IMM, TOP = _native.KZG_KECCAK_IMM, _native.KZG_KECCAK_MAX_OUT
+        units = list(units) if isinstance(units, (list, tuple)) else None
+        if not units or len(units) > _native.KZG_KECCAK_MAX_UNITS:
+            raise bad(f"units must be a list of 1 .. {_native.KZG_KECCAK_MAX_UNITS} entries (n_units)")
+        seen = set()
+        recs = []
+        for un in units:
+            if not isinstance(un, dict) or "mode" not in un:
+                raise bad("a unit is a mapping with mode and the fields of its mode")
+            mode = un["mode"]
+            if mode not in ("row", "rounds"):
+                raise bad(f'unknown mode {mode!r} (one of "row", "rounds")')
+            keys = cls._KECCAK_ROW_KEYS if mode == "row" else cls._KECCAK_ROUNDS_KEYS
+            extra = set(un) - set(keys)
+            if extra:
+                if mode == "rounds" and "expect" in extra:
+                    raise bad("expect belongs to row units, not to rounds")
+                raise bad(f"unknown field {sorted(extra)[0]!r} (the fields of a {mode} unit are {', '.join(keys)})")
+            flags, period, rate, start, expect = 0, 0, 0, _native.KZG_KECCAK_ABSENT, []
+            if mode == "row":
+                v = un.get("in")
+                if not isinstance(v, (list, tuple)) or len(v) != 25:
+                    raise bad('in must hold 25 slots, each a row index or ("imm", value)')
+                rows, imms = [], []
+                for s in v:
+                    if isinstance(s, (list, tuple)):
+                        if len(s) != 2 or s[0] != "imm":
+                            raise bad('an immediate is ("imm", value)')
+                        if not is_u(s[1], 1 << 64):
+                            raise bad("an immediate must be an integer below 2^64")
+                        rows.append(IMM)
+                        imms.append(s[1])
+                    elif is_u(s, IMM):
+                        rows.append(s)
+                        imms.append(0)
+                        seen.add(s)
+                    else:
+                        raise bad('a slot must be a row index, an integer in [0, 2^32 - 1), or ("imm", value)')
+                out = un.get("out")
+                if not isinstance(out, (list, tuple)) or not 1 <= len(out) <= TOP:
+                    raise bad(f"out must hold 1 .. {TOP} lane indices (n_out)")
+                if any(not is_u(j, 25) for j in out):
+                    raise bad("a lane index must be an integer below 25")
+                if len(set(out)) != len(out):
+                    raise bad("a lane index is repeated")
+                out = list(out)
+                if un.get("expect") is not None:
+                    expect = un["expect"]
+                    if not isinstance(expect, (list, tuple)) or len(expect) != len(out):
+                        raise bad("expect must hold one row per entry of out")
+                    if any(not is_u(j, IMM) for j in expect):
+                        raise bad("an entry of expect must be a row index, an integer in [0, 2^32 - 1)")
+                    expect = list(expect)
+                    seen.update(expect)
+                    flags |= _native.KZG_KECCAK_CHECK
+            else:
+                msg = un.get("msg")
+                if not isinstance(msg, (list, tuple)) or len(msg) != 5 or any(not is_u(r, IMM) for r in msg):
+                    raise bad("the msg of a rounds unit must hold 5 row indices, integers in [0, 2^32 - 1)")
+                seen.update(msg)
+                rows, imms = list(msg) + [0] * 20, [0] * 25
+                rate = un.get("rate")
+                if not is_u(rate, 25) or rate < 1:
+                    raise bad("the rate of a rounds unit must be an integer in [1, 24] lanes")
+                if un.get("start") is not None:
+                    start = un["start"]
+                    if not is_u(start, IMM):
+                        raise bad("start must be a row index, an integer in [0, 2^32 - 1), or None")
+                    seen.add(start)
+                period = un.get("period")
+                if not is_u(period, 1 << 32) or period < _native.KZG_KECCAK_MIN_PERIOD:
+                    raise bad(f"the period P of a rounds unit must be an integer in [{_native.KZG_KECCAK_MIN_PERIOD}, 2^32)")
+                cols = un.get("cols")
+                if not isinstance(cols, (list, tuple)) or not 1 <= len(cols) <= TOP:
+                    raise bad(f"cols must hold 1 .. {TOP} column names (n_out)")
+                for name in cols:
+                    if name not in _native.KZG_KECCAK_COLS:
+                        raise bad(f"unknown column name {name!r} (the names are {', '.join(_native.KZG_KECCAK_COLS)})")
+                if len(set(cols)) != len(cols):
+                    raise bad("a column name is repeated")
+                out = [_native.KZG_KECCAK_COLS.index(name) for name in cols]
+            pad = lambda xs, k: list(xs) + [0] * (k - len(xs))   # noqa: E731
+            recs.append((_native.KZG_KECCAK_ROW if mode == "row" else _native.KZG_KECCAK_ROUNDS, flags, len(out), period, rate,
+                         start, imms, rows, pad(out, 16), pad(expect, 16)))
+        if len(seen) > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"the units read {len(seen)} distinct input rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+        n_out = sum(r[2] for r in recs if not r[1] & _native.KZG_KECCAK_CHECK)
+        if n_out > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"n_out: the units give {n_out} output rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+        return recs
+
+    @staticmethod
+    def keccak_unit_struct(rec) -> "_native.KeccakUnit":
+        A = lambda k, xs: (ctypes.c_uint32 * k)(*xs)   # noqa: E731
+        return _native.KeccakUnit(rec[0], rec[1], rec[2], rec[3], rec[4], rec[5], (ctypes.c_uint64 * 25)(*rec[6]), A(25, rec[7]),
+                                  A(16, rec[8]), A(16, rec[9]))
+
+    def commit_keccak(self, input_sets: Sequence[object], units: Sequence[dict], usable: Optional[int] = None,
+                      tail: Sequence[bytes] = ()) -> Tuple[Optional["RowSet"], dict]:
+        """kzg_rows_commit_keccak over the concatenated rows of input_sets (RowSet objects or bare handles).  units: see
+        keccak_call.  All values are 64-bit lanes: a source cell is its canonical integer reduced to its low 64 bits, and a
+        cell at or above 2^64 is counted.  A row unit runs one Keccak-f[1600] per row t' < n (n = usable, or T) and commits one
+        column per entry of out -- or, with expect, commits nothing and counts the rows whose expected cells differ; a rounds
+        unit commits the named columns of the round trace in blocks of `period` rows, chained along the start column.
+        Returns (the new RowSet of all committed columns in unit order, or None when every unit is a check; {"perms",
+        "messages", "counts", "first", "mismatch", "first_mismatch"} per unit).  usable and tail: as for commit_derived, the
+        tail column-major over the committed columns."""
+        what = "commit_keccak"
+        ni, hi = self._handle_array(input_sets, what)
+        recs = self.keccak_call(units, what)
+        n_out = sum(r[2] for r in recs if not r[1] & _native.KZG_KECCAK_CHECK)
+        wi, T, lay = self._column_layout(what, input_sets, n_out, "n_out", "read", usable, tail)
+        opts = _native.DeriveOpts(*lay) if lay else None
+        arr = (_native.KeccakUnit * len(recs))(*[self.keccak_unit_struct(r) for r in recs])
+        c, h = ctypes.create_string_buffer(48 * max(n_out, 1)), ctypes.c_uint64(0)
+        st = [(ctypes.c_uint64 * len(recs))() for _ in range(6)]
+        self._chk(self._lib.kzg_rows_commit_keccak(self._h, ni, hi, len(recs), arr, ctypes.byref(opts) if opts is not None else None,
+                                                   c if n_out else None, *st, ctypes.byref(h)))
+        rs = RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]) if n_out else None
+        none = lambda xs: [None if int(v) == _native.KZG_KECCAK_NONE else int(v) for v in xs]   # noqa: E731
+        return rs, {"perms": [int(v) for v in st[0]], "messages": [int(v) for v in st[1]], "counts": [int(v) for v in st[2]],
+                    "first": none(st[3]), "mismatch": [int(v) for v in st[4]], "first_mismatch": none(st[5])}
+
     # ---- a set built from sets: columns that are plain arithmetic in resident columns, and gates checked row by row
     def commit_expr(self, input_sets: Sequence[object], exprs: Sequence[Sequence], usable: Optional[int] = None,
                     tail: Sequence[bytes] = ()) -> Tuple[Optional["RowSet"], List[int], List[Optional[int]]]:
