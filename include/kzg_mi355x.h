@@ -1223,7 +1223,8 @@ int kzg_rows_commit_alu(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* 
  * source sets are only read; a release or an SRS load racing the call follows the rules of kzg_rows_open.  Thread-safe like
  * every call; after any error the context keeps serving.
  * OUT OF SCOPE: L > 8 (regroup 8-bit or 16-bit limbs into wider ones with kzg_rows_commit_expr, or cut the outputs again with
- * kzg_rows_commit_derived); a per-row modulus; modular inversion and division; signed operands; an op-code column; operands
+ * kzg_rows_commit_derived); a per-row modulus; modular inversion and division (no longer missing: they have their own call, the DIV unit of
+ * kzg_rows_commit_ec, for an odd modulus of up to 256 bits); signed operands; an op-code column; operands
  * on DISTINCT rows beyond the KZG_MAX_BATCH_OPEN concatenated rows a call reads: the limit counts rows, not L, and a row may
  * serve several operands, so a CARRY runs at any L <= 8, but with a, q and r on three distinct runs of rows it has L <= 5 (L <=
  * 4 with b as a fourth).  A 256-bit or 384-bit carry chain over distinct a, q, r is therefore not to be had in one call.
@@ -1540,6 +1541,104 @@ int kzg_rows_commit_keccak(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_
                            uint64_t* out_messages /* n_units */, uint64_t* out_counts /* n_units */,
                            uint64_t* out_first /* n_units */, uint64_t* out_mismatch /* n_units */,
                            uint64_t* out_first_mismatch /* n_units */, uint64_t* out_handle);
+/* THE NON-NATIVE ELLIPTIC-CURVE COLUMNS: a set built FROM sets, the columns of the chip that does curve arithmetic over a FOREIGN
+ * field -- ecrecover and ECDSA over secp256k1, the bn254 precompiles, P-256.  The slope of a point addition is a modular
+ * division, which kzg_rows_commit_wide leaves out; a scalar multiplication is a chain whose accumulator feeds the next row
+ * non-linearly, which neither kzg_rows_commit_expr (no dependence from row to row) nor kzg_rows_commit_recurrence (affine)
+ * expresses.  VALUES follow kzg_rows_commit_wide: a wide value is L = curve->limbs consecutive limb rows of b = curve->bits bits,
+ * little-endian, 1 <= b <= 64, 1 <= L <= KZG_EC_MAX_LIMBS, W = b L <= 256; a cell is read as its canonical integer and reduced
+ * to its low b bits.  THE CURVE is one per call: p = curve->p (four little-endian 64-bit words), ODD, 3 <= p < 2^W, not
+ * necessarily prime, and a = curve->a < p, the coefficient of y^2 = x^3 + a x + c; c is never needed and not taken.  An operand
+ * at or above p is reduced mod p, never refused.  A row with a limb at or above 2^b or an operand at or above p is counted ONCE
+ * per unit in out_counts[u], the smallest such row is out_first[u] (KZG_EC_NONE: none).  The concatenated rows of the
+ * input_handles sets (as in kzg_rows_open) are the source columns; an operand is named by its FIRST row and runs over L rows;
+ * one row may serve several operands.  A call has 1 <= n_units <= KZG_EC_MAX_UNITS units.  With n = opts->usable, or T in the
+ * plain layout, and every row t' < n on its own:
+ *   KZG_EC_DIV    r = a b^-1 mod p, L output rows; in[0] = a, in[1] = b, or with KZG_EC_IMM_B in[1] = KZG_EC_ABSENT and b = imm
+ *                 on every row (below 2^W; reduced mod p like a row, not counted).  Where gcd(b mod p, p) != 1 (b = 0 mod p
+ *                 included) r = 0 and the row is counted in out_singular[u], the smallest such row in out_first_singular[u].
+ *                 cols is KZG_EC_R.  The caller's gate is kzg_rows_commit_wide's MULMOD / CARRY of r b = a + q p.
+ *   KZG_EC_ADD    in[0 .. 3] = x1, y1, x2, y2, all reduced mod p.  x1 != x2: lambda = (y2 - y1) / (x2 - x1); x1 = x2, y1 = y2 and
+ *                 gcd(2 y1, p) = 1: lambda = (3 x1^2 + a) / (2 y1), the doubling (name the same rows twice to double a
+ *                 column); any other row -- opposite points, a point of order two, a denominator without an inverse under a
+ *                 composite p -- is EXCEPTIONAL: lambda = x3 = y3 = 0, counted in out_singular[u] / out_first_singular[u].
+ *                 x3 = lambda^2 - x1 - x2, y3 = lambda (x1 - x3) - y1.  cols picks among KZG_EC_LAM, KZG_EC_X3, KZG_EC_Y3; the
+ *                 output rows come in that order, L rows each.  There is no point at infinity and no on-curve check: the unit
+ *                 is arithmetic on pairs of integers.
+ *   KZG_EC_CHECK  (a flag on DIV and ADD) the unit commits NOTHING: expect[k] is the first row of the L rows that name k of cols
+ *                 is compared with (DIV: expect[0]; ADD: expect[0 .. 2] for lambda, x3, y3; KZG_EC_ABSENT beside a name that is
+ *                 not in cols); out_mismatch[u] is the number of rows t' < n where some expected cell differs from the computed
+ *                 limb, out_first_mismatch[u] the smallest such row.
+ *   KZG_EC_CHAIN  the accumulator trace of a double-and-add or of a multi-scalar sum: in[0] = px, in[1] = py, op the row of the
+ *                 op-code column (ONE row, compared as a whole integer); cols picks among KZG_EC_AX, KZG_EC_AY, KZG_EC_LAM, in
+ *                 that order.  The accumulator is a pair of integers mod p, (0, 0) before row 0.  Row t holds the accumulator
+ *                 BEFORE the step in ax, ay and the step's lambda in lam (0 where there is none); then op[t] acts: 0 hold; 1
+ *                 load, acc <- (px[t], py[t]); 2 acc <- acc + (px[t], py[t]) by the rule of ADD, the doubling included; 3 acc
+ *                 <- 2 acc; any other code holds and is counted in out_unknown[u] / out_first_unknown[u].  An exceptional step
+ *                 leaves acc = (0, 0) and is counted in out_singular[u].  px and py are neither read nor counted on rows whose
+ *                 op is 0, 3 or unknown.  A SEGMENT begins at row 0 and at every load; out_segments[u] is their number.  The
+ *                 chain stops at n; there is no closing row: a caller that wants the last result ends on a hold row.
+ *                 KZG_EC_CHECK is refused.
+ * Statistics a mode does not have are 0 and KZG_EC_NONE.  All committed rows of a call form ONE new set of the same worker and
+ * length, in the order of units, then of names, then of limbs: out_commitments48[c] equals kzg_rows_commit(i, n_out, these rows,
+ * T, 1, ..)[c] byte for byte, and *out_handle opens, evaluates, combines, releases, goes stale and counts against
+ * KZG_MAX_ROW_SETS like any other.  A call made of checks alone creates no set (*out_handle = 0, out_commitments48 may be
+ * null), runs no inverse transform and no MSM.  ONE kernel launch computes every unit; nothing row-sized crosses the host link.
+ * A call reads at most KZG_MAX_BATCH_OPEN distinct rows (two points of L = 4 are 16) and commits at most KZG_MAX_BATCH_OPEN.
+ * opts, handle lists, worker, T, staleness and threads: as for kzg_rows_commit_keccak.  KZG_E_ARG with a message that begins
+ * "ec:" and names the cause: n_units outside its range; b, L or W outside their ranges; p even, below 3 or at or above 2^W;
+ * a >= p; an unknown mode or flag, KZG_EC_CHECK on a CHAIN unit, KZG_EC_IMM_B beside a mode other than DIV; cols empty or with a
+ * name the mode does not have; an operand, op, expect entry or immediate the mode does not take, or a missing one; an
+ * immediate at or above 2^W; an operand run that reaches beyond the concatenation; more than KZG_MAX_BATCH_OPEN output rows
+ * or distinct input rows; T above 2^32; the usable and tail refusals of kzg_rows_commit_derived; the handle refusals of
+ * kzg_rows_open.  All but the last four are checked on the host before a lane is taken.  After any error the context keeps
+ * serving and no set or buffer leaks.
+ * OUT OF SCOPE: L > 4 (BLS12-381's Fp); Edwards and Montgomery forms; projective coordinates; the point at infinity; an
+ * on-curve check; subtraction or negation ops; per-row moduli; an even modulus; the quotient and carry columns of the gates
+ * (kzg_rows_commit_wide over these outputs gives them).  A CHAIN unit runs one lane of the device per segment: one segment that
+ * fills the whole column is correct, and slow.
+ * SOUNDNESS: nothing here is a proof.  The columns are prover data; the argument is the caller's MULMOD / CARRY gates over
+ * lambda, x3 and y3 (lambda (x2 - x1) = y2 - y1, and so on, mod p) plus the range lookups of every limb.  Zero counts convince
+ * no verifier. */
+#define KZG_EC_DIV   1
+#define KZG_EC_ADD   2
+#define KZG_EC_CHAIN 3
+#define KZG_EC_CHECK 1u                /* flags (DIV, ADD): compare with expect, commit nothing */
+#define KZG_EC_IMM_B 2u                /* flags (DIV): operand b is imm */
+#define KZG_EC_R     1u                /* cols (DIV) */
+#define KZG_EC_LAM   1u                /* cols (ADD): lambda, x3, y3 */
+#define KZG_EC_X3    2u
+#define KZG_EC_Y3    4u
+#define KZG_EC_AX    1u                /* cols (CHAIN): ax, ay, lam */
+#define KZG_EC_AY    2u
+#define KZG_EC_CLAM  4u
+#define KZG_EC_ABSENT 0xffffffffu      /* an operand, op or expect entry the unit does not have */
+#define KZG_EC_NONE   0xffffffffffffffffull   /* out_first*: none */
+#define KZG_EC_MAX_UNITS 4
+#define KZG_EC_MAX_LIMBS 4
+typedef struct kzg_ec_curve {
+    uint32_t bits;               /* b: 1 .. 64 */
+    uint32_t limbs;              /* L: 1 .. KZG_EC_MAX_LIMBS, b L <= 256 */
+    uint64_t p[4];               /* the modulus, little-endian words: odd, 3 <= p < 2^(b L) */
+    uint64_t a[4];               /* the coefficient a < p */
+} kzg_ec_curve;
+typedef struct kzg_ec_unit {
+    uint32_t mode;               /* KZG_EC_DIV, KZG_EC_ADD or KZG_EC_CHAIN */
+    uint32_t flags;              /* KZG_EC_CHECK, KZG_EC_IMM_B */
+    uint32_t cols;               /* the names that are committed (or compared), a mask of the mode's KZG_EC_* names */
+    uint32_t op;                 /* CHAIN: the row of the op-code column; else KZG_EC_ABSENT */
+    uint32_t in[4];              /* first rows.  DIV: a, b; ADD: x1, y1, x2, y2; CHAIN: px, py; KZG_EC_ABSENT beyond */
+    uint32_t expect[3];          /* with KZG_EC_CHECK: [k] the first row name k is compared with; else KZG_EC_ABSENT */
+    uint32_t reserved;           /* 0 */
+    uint64_t imm[4];             /* with KZG_EC_IMM_B: b, little-endian words; else 0 */
+} kzg_ec_unit;
+int kzg_rows_commit_ec(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, const kzg_ec_curve* curve,
+                       uint32_t n_units, const kzg_ec_unit* units, const kzg_derive_opts* opts /* NULL: plain */,
+                       uint8_t* out_commitments48 /* n_out * 48 */, uint64_t* out_counts /* n_units */,
+                       uint64_t* out_first /* n_units */, uint64_t* out_singular /* n_units */,
+                       uint64_t* out_first_singular /* n_units */, uint64_t* out_mismatch /* n_units */,
+                       uint64_t* out_first_mismatch /* n_units */, uint64_t* out_unknown /* n_units */,
+                       uint64_t* out_first_unknown /* n_units */, uint64_t* out_segments /* n_units */, uint64_t* out_handle);
 /* THE QUOTIENT WITH LOOKUP SELECTORS: kzg_rows_commit_quotient_zk and kzg_rows_quotient_part for lookups that are enabled on
  * some rows only.  selectors->selector_rows holds L = lookup->n_lookups entries, each a row index into the call's concatenated
  * rows (the caller's fixed column q_l, the row that kzg_rows_commit_multiplicities_sel / _lookup_sum_sel read) or
@@ -1944,6 +2043,12 @@ int kzg_multi_rows_commit_keccak(kzg_multi* mh, uint32_t i, uint32_t n_input_han
                                  uint32_t n_units, const kzg_keccak_unit* units, const kzg_derive_opts* opts,
                                  uint8_t* out_commitments48, uint64_t* out_perms, uint64_t* out_messages, uint64_t* out_counts,
                                  uint64_t* out_first, uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_handle);
+/* kzg_rows_commit_ec on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_ec(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                             const kzg_ec_curve* curve, uint32_t n_units, const kzg_ec_unit* units, const kzg_derive_opts* opts,
+                             uint8_t* out_commitments48, uint64_t* out_counts, uint64_t* out_first, uint64_t* out_singular,
+                             uint64_t* out_first_singular, uint64_t* out_mismatch, uint64_t* out_first_mismatch,
+                             uint64_t* out_unknown, uint64_t* out_first_unknown, uint64_t* out_segments, uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

@@ -67,6 +67,15 @@ KZG_KECCAK_ABSENT = 0xffffffff
 KZG_KECCAK_NONE = 0xffffffffffffffff
 KZG_KECCAK_MAX_UNITS, KZG_KECCAK_MIN_PERIOD, KZG_KECCAK_MAX_OUT, KZG_KECCAK_N_COLS = 4, 125, 16, 25
 KZG_KECCAK_COLS = tuple(f"{k}{x}" for k in "apdtb" for x in range(5))
+# kzg_rows_commit_ec: kzg_ec_unit.mode, the flags, "no such operand", "none", the limits, and the names of a unit's columns in
+# the order of their bits in kzg_ec_unit.cols
+KZG_EC_DIV, KZG_EC_ADD, KZG_EC_CHAIN = 1, 2, 3
+KZG_EC_CHECK, KZG_EC_IMM_B = 1, 2
+KZG_EC_ABSENT = 0xffffffff
+KZG_EC_NONE = 0xffffffffffffffff
+KZG_EC_MAX_UNITS, KZG_EC_MAX_LIMBS = 4, 4
+KZG_EC_ADD_NAMES = ("lam", "x3", "y3")
+KZG_EC_CHAIN_NAMES = ("ax", "ay", "lam")
 KZG_MAX_EXPR_FACTORS = 8   # kzg_rows_commit_expr: factors of one term
 KZG_EXPR_CHECK = 1   # kzg_expr.flags: evaluate and count only
 KZG_EXPR_NONE = 0xffffffffffffffff   # out_first: no non-zero cell
@@ -188,6 +197,17 @@ class KeccakUnit(ctypes.Structure):
                 ("imm", _U64 * 25), ("in_", _U32 * 25), ("out", _U32 * 16), ("expect", _U32 * 16)]
 
 
+class EcCurve(ctypes.Structure):
+    """kzg_ec_curve"""
+    _fields_ = [("bits", _U32), ("limbs", _U32), ("p", _U64 * 4), ("a", _U64 * 4)]
+
+
+class EcUnit(ctypes.Structure):
+    """kzg_ec_unit"""
+    _fields_ = [("mode", _U32), ("flags", _U32), ("cols", _U32), ("op", _U32), ("in_", _U32 * 4), ("expect", _U32 * 3),
+                ("reserved", _U32), ("imm", _U64 * 4)]
+
+
 class Col(ctypes.Structure):
     """kzg_col"""
     _fields_ = [("data", ctypes.c_void_p), ("count", ctypes.c_uint64), ("kind", ctypes.c_uint32), ("fill_be32", ctypes.c_char_p)]
@@ -279,6 +299,8 @@ SYMBOLS = {
                                     _B] + [ctypes.POINTER(_U64)] * 7),
     "kzg_rows_commit_keccak": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(KeccakUnit), ctypes.POINTER(DeriveOpts),
                                     _B] + [ctypes.POINTER(_U64)] * 7),
+    "kzg_rows_commit_ec": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(EcCurve), _U32, ctypes.POINTER(EcUnit),
+                                ctypes.POINTER(DeriveOpts), _B] + [ctypes.POINTER(_U64)] * 10),
     "kzg_rows_commit_derived": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp), ctypes.POINTER(DeriveOpts), _B,
                                      ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_expr": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,
@@ -413,6 +435,8 @@ SYMBOLS = {
                                           ctypes.POINTER(DeriveOpts), _B] + [ctypes.POINTER(_U64)] * 7),
     "kzg_multi_rows_commit_keccak": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(KeccakUnit),
                                           ctypes.POINTER(DeriveOpts), _B] + [ctypes.POINTER(_U64)] * 7),
+    "kzg_multi_rows_commit_ec": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(EcCurve), _U32, ctypes.POINTER(EcUnit),
+                                      ctypes.POINTER(DeriveOpts), _B] + [ctypes.POINTER(_U64)] * 10),
     "kzg_multi_rows_commit_derived": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp),
                                            ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_expr": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,

@@ -1197,6 +1197,55 @@ class Client:
         return {"handle": None if rs is None else int(rs.handle),
                 "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments], **st}
 
+    # ---- the non-native elliptic-curve chip: a / b mod p, affine point addition with the doubling, accumulator chains
+    @_guard
+    def worker_commit_ec(self, input_handles: Sequence[int], curve: dict, units: Sequence[dict], usable: Optional[int] = None,
+                         tail: Sequence[str] = ()):
+        """Extension: columns of elliptic-curve arithmetic over a foreign field, computed from the rows of the input_handles
+        sets and committed on the device as one new set.  curve: {"bits": b, "limbs": L, "p": the odd modulus, 3 <= p < 2^(b L),
+        b L <= 256, "a": the coefficient of y^2 = x^3 + a x + c, below p}; integers may be decimal or 0x strings.  A wide value
+        is L consecutive rows of b bits, little-endian, named by its first row; an operand at or above p is reduced mod p; a
+        row with a limb at or above 2^b or such an operand is counted (`counts`, `first`).  units: 1 to 4 objects.  {"mode":
+        "div", "a": row, "b": row or ["imm", v], "out": true} commits a b^-1 mod p (0 and `singular` where b has no inverse).
+        {"mode": "add", "x1", "y1", "x2", "y2": rows, "out": [names among lam, x3, y3]} commits the named values of the affine
+        addition, the doubling where the points are equal; an exceptional row (opposite points, order two, no inverse) gives
+        zeros and is counted in `singular`.  Either with "expect": [first rows] in place of out (add: three entries for lam, x3,
+        y3, null: not compared) commits nothing and reports `mismatch` and `first_mismatch`.  {"mode": "chain", "px", "py":
+        rows, "op": row, "cols": [names among ax, ay, lam]} commits the accumulator before each row's step and the step's
+        lambda: op 0 holds, 1 loads (px, py), 2 adds it, 3 doubles, any other code holds and is counted in `unknown`; the
+        accumulator is (0, 0) before row 0 and after an exceptional step; `segments` counts row 0 and the loads.  usable and
+        tail: as for worker_commit_derived.  Returns the handle (null when every unit is a check), the commitments and the
+        statistics per unit.  Nothing here is a proof: the columns are prover data and the argument is the caller's mulmod and
+        carry gates over them plus the range lookups of the limbs."""
+        what = "worker_commit_ec"
+        hs = _handles(input_handles)
+        try:
+            recs = []
+            for un in units:
+                if not isinstance(un, dict):
+                    raise ValueError(f"a unit is an object: {un!r}")
+                rec = dict(un)
+                if isinstance(rec.get("b"), list):
+                    rec["b"] = tuple(rec["b"])
+                recs.append(rec)
+        except (TypeError, ValueError, IndexError, KeyError) as e:
+            raise codec.CodecError(f"{what}: units must be a list of objects: {e!r}") from e
+        if not recs:
+            raise codec.CodecError(f"{what}: units must not be empty")
+        if not isinstance(curve, dict):
+            raise codec.CodecError(f"{what}: curve must be an object with bits, limbs, p and a")
+        if usable is None:
+            if tail:
+                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
+            tb = []
+        else:
+            usable, tb = self._blind(what, usable, tail)
+            if usable == 0:
+                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        rs, st = self.engine.commit_ec(hs, dict(curve), recs, usable, tb)
+        return {"handle": None if rs is None else int(rs.handle),
+                "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments], **st}
+
     @staticmethod
     def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: Sequence[int], n_groups: int, width: int,
                                theta: str, gamma: str, coeff: str, active_row: Optional[int] = None,

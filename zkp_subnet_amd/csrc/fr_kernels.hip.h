@@ -545,6 +545,40 @@ static_assert(sizeof(KecTab) + 64 <= 4096 && POLY_MAX_ROWS < KEC_IMM && 2 * POLY
 // min(., the smallest row of the first kind), [4 n_units + u] <- min(., of the second).  Sources are only read and may
 // coincide; out must not overlap a source.  Returns without a launch on a table that the caller's checks should have refused
 void launch_keccak(hipStream_t s, const KecTab& tab, uint64_t T, uint64_t n, uint64_t* stats);
+// ---- the non-native elliptic-curve columns of kzg_rows_commit_ec (fr_ec.hip).  A wide value is `limbs` source vectors of `bits`
+// bits each, little-endian, as in fr_wide.hip, at most 256 bits: EC_WORDS 32-bit words.  The curve is uniform over the call: the
+// odd modulus p, the coefficient a < p, and what the Montgomery products of radix 2^256 need: n0inv = -p^-1 mod 2^32 and r2 =
+// 2^512 mod p (the caller computes both).  Source vector d lies at src + d T 8 words.  slot[w][l]: the vector of limb l of operand
+// w (DIV: a, b; ADD: x1, y1, x2, y2; CHAIN: px, py); opv: the vector of a CHAIN unit's op-code column.  cols: bit k set: name k
+// (DIV: r; ADD: lam, x3, y3; CHAIN: ax, ay, lam) is an output, `limbs` vectors each, side by side at out in the order of the
+// names.  out null: a check (DIV, ADD): limb l of name k is compared with the cell of source vector exp[k][l]
+#define EC_MAX_UNITS 4
+#define EC_MAX_LIMBS 4
+#define EC_WORDS 8
+#define EC_DIV 1
+#define EC_ADD 2
+#define EC_CHAIN 3
+#define EC_F_IMM_B 0x100u   // DIV: operand b is imm
+struct EcUnit {
+    uint32_t* out;
+    uint32_t mode, cols, flags, opv;
+    uint8_t slot[4][EC_MAX_LIMBS], exp[3][EC_MAX_LIMBS];
+    uint32_t imm[EC_WORDS];
+};
+struct EcTab {
+    EcUnit u[EC_MAX_UNITS];
+    const uint32_t* src;
+    uint32_t n_units, bits, limbs, n0inv;
+    uint32_t p[EC_WORDS], a[EC_WORDS], r2[EC_WORDS];
+};
+static_assert(sizeof(EcTab) + 64 <= 4096 && POLY_MAX_ROWS <= 256, "the unit table rides as a kernel argument; slots ride in bytes");
+// ONE launch for the n_units units of tab.  stats: seven runs of n_units words: [u] += the rows with a limb at or above 2^bits
+// or an operand at or above p, [n_units + u] += the exceptional (singular) rows, [2 n_units + u] += the rows of a check with a
+// cell that differs, on a CHAIN unit the rows with an unknown op-code, [3 n_units + u] += the segments of a CHAIN unit, [4 n_units
+// + u], [5 n_units + u], [6 n_units + u] <- min(., the smallest row of the first, second and third kind).  Sources are only read
+// and may coincide; out must not overlap a source.  Returns without a launch on a table that the caller's checks should have
+// refused (p even or below 3, a >= p, bits or limbs out of range, an unknown mode, no name)
+void launch_ec(hipStream_t s, const EcTab& tab, uint64_t T, uint64_t n, uint64_t* stats);
 // ---- the expression columns of kzg_rows_commit_expr (fr_expr.hip): v[t] = sum_u c_u prod_f src.r[row[u][f]][(t + rot[u][f]) mod T]
 // for t < n <= T over evaluation vectors of T canonical Montgomery elements (T a power of two, at most 2^32)
 #define EXPR_MAX_TERMS 16

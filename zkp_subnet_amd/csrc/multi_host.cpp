@@ -558,6 +558,18 @@ int kzg_multi_rows_commit_keccak(kzg_multi* mh, uint32_t i, uint32_t n_input_han
                                      out_messages, out_counts, out_first, out_mismatch, out_first_mismatch, out_handle);
     });
 }
+int kzg_multi_rows_commit_ec(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                             const kzg_ec_curve* curve, uint32_t n_units, const kzg_ec_unit* units, const kzg_derive_opts* opts,
+                             uint8_t* out_commitments48, uint64_t* out_counts, uint64_t* out_first, uint64_t* out_singular,
+                             uint64_t* out_first_singular, uint64_t* out_mismatch, uint64_t* out_first_mismatch,
+                             uint64_t* out_unknown, uint64_t* out_first_unknown, uint64_t* out_segments, uint64_t* out_handle) {
+    uint64_t* const st[9] = {out_counts,         out_first,   out_singular,      out_first_singular, out_mismatch,
+                             out_first_mismatch, out_unknown, out_first_unknown, out_segments};
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_ec(c, s, n_input_handles, input_handles, curve, n_units, units, opts, out_commitments48, st,
+                                 out_handle);
+    });
+}
 int kzg_multi_rows_commit_expr(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                uint32_t n_exprs, const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48,
                                uint64_t* out_nonzero, uint64_t* out_first, uint64_t* out_handle) {

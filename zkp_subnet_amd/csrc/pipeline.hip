@@ -1773,6 +1773,103 @@ int rows_keccak_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs,
     return KZG_OK;
 }
 
+// The non-native elliptic-curve columns (kzg_rows_commit_ec), in the builders' frame, step for step as rows_keccak_dev:
+//   step                      launches                         per call
+//   forward transforms        launch_fr_ntt                    one per distinct source row named
+//   every unit                launch_ec (k_fr_ec)              ONE, grid y = unit
+//   tail                      launch_sort_tail                 one per output row, with `usable` only
+//   inverse transform         row_to_coeffs                    one per output row, straight into dst
+//   commit                    multi_msms_finish                ONE pass of n_out scalar sets
+// The seven statistics of every unit are u64 words behind the first two evaluation slots of the record and come back in the
+// copy behind the MSM.  With n_out = 0 (checks alone) nothing is transformed back and no MSM runs.  The curve's two derived
+// constants are computed here, on the host, once per call: -p^-1 mod 2^32 by Newton's iteration and 2^512 mod p by 512
+// doublings.  Every row t < n of a committed column is written by the kernel (a CHAIN unit's rows by the lane of their
+// segment), so nothing is zeroed first.  Workspace: distinct sources + n_out vectors of T.
+int rows_ec_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const kzg_ec_curve* curve, uint32_t n_units,
+                const kzg_ec_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_stats,
+                const Blind* lay) {
+    Lane& A = H.L();
+    Cols F;
+    if (int rc = cols_begin(ctx, A, T, lay, dst, F)) return rc;
+    const uint64_t vw = F.vw, n = F.n;
+    static_assert(56 * KZG_EC_MAX_UNITS <= STATS_MAX && KZG_EC_MAX_UNITS == EC_MAX_UNITS && KZG_EC_MAX_LIMBS == EC_MAX_LIMBS &&
+                      KZG_EC_DIV == EC_DIV && KZG_EC_ADD == EC_ADD && KZG_EC_CHAIN == EC_CHAIN &&
+                      4 * KZG_EC_MAX_LIMBS <= POLY_MAX_ROWS,
+                  "the seven statistics of every unit fit the record's evaluation slots; the header's caps and modes are the "
+                  "kernel's");
+    Sources S;
+    EcTab tab;
+    memset(&tab, 0, sizeof(tab));
+    const uint32_t L = curve->limbs;
+    tab.n_units = n_units;
+    tab.bits = curve->bits;
+    tab.limbs = L;
+    for (uint32_t w = 0; w < 4; w++) {
+        tab.p[2 * w] = (uint32_t)curve->p[w];
+        tab.p[2 * w + 1] = (uint32_t)(curve->p[w] >> 32);
+        tab.a[2 * w] = (uint32_t)curve->a[w];
+        tab.a[2 * w + 1] = (uint32_t)(curve->a[w] >> 32);
+    }
+    uint32_t inv = 1;   // p[0]^-1 mod 2^32: every round doubles the correct low bits (p odd: one is right at the start)
+    for (int k = 0; k < 5; k++) inv *= 2u - tab.p[0] * inv;
+    tab.n0inv = 0u - inv;
+    tab.r2[0] = 1;
+    for (int k = 0; k < 64 * EC_WORDS; k++) {   // r2 <- 2 r2 mod p
+        uint32_t c = 0, br = 0, d[EC_WORDS];
+        for (int j = 0; j < EC_WORDS; j++) {
+            const uint32_t top = tab.r2[j] >> 31;
+            tab.r2[j] = (tab.r2[j] << 1) | c;
+            c = top;
+        }
+        for (int j = 0; j < EC_WORDS; j++) {
+            const uint64_t x = (uint64_t)tab.r2[j] - tab.p[j] - br;
+            d[j] = (uint32_t)x;
+            br = (uint32_t)(x >> 32) & 1u;
+        }
+        if (c || !br) memcpy(tab.r2, d, sizeof(d));
+    }
+    for (uint32_t u = 0; u < n_units; u++) {
+        const kzg_ec_unit& in = units[u];
+        EcUnit& U = tab.u[u];
+        U.mode = in.mode;
+        U.cols = in.cols;
+        U.flags = in.flags & KZG_EC_IMM_B ? EC_F_IMM_B : 0u;
+        for (uint32_t w = 0; w < 4; w++) {
+            U.imm[2 * w] = (uint32_t)in.imm[w];
+            U.imm[2 * w + 1] = (uint32_t)(in.imm[w] >> 32);
+            if (in.in[w] == KZG_EC_ABSENT) continue;
+            for (uint32_t l = 0; l < L; l++) U.slot[w][l] = (uint8_t)S.slot_of(inputs.r[in.in[w] + l]);
+        }
+        if (in.mode == KZG_EC_CHAIN) U.opv = S.slot_of(inputs.r[in.op]);
+        if (in.flags & KZG_EC_CHECK)
+            for (uint32_t k = 0; k < 3; k++)
+                if (in.cols >> k & 1u)
+                    for (uint32_t l = 0; l < L; l++) U.exp[k][l] = (uint8_t)S.slot_of(inputs.r[in.expect[k] + l]);
+    }
+    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_out) * T * 32 + 32));
+    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + S.nd * vw;
+    uint64_t* st = reinterpret_cast<uint64_t*>(F.rec + MR_EVAL + CNT_OFF);
+    sources_transform(ctx, A, F, S, src);
+    HIPCHK(ctx, hipMemsetAsync(st, 0, 32 * (size_t)n_units, A.stream));
+    HIPCHK(ctx, hipMemsetAsync(st + 4 * n_units, 0xff, 24 * (size_t)n_units, A.stream));   // KZG_EC_NONE
+    tab.src = src;
+    for (uint32_t u = 0, c = 0; u < n_units; u++) {
+        if (units[u].flags & KZG_EC_CHECK) continue;
+        tab.u[u].out = outv + c * vw;
+        c += (uint32_t)__builtin_popcount(units[u].cols) * L;
+    }
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_ec(A.stream, tab, T, n, st);
+    }
+    for (uint32_t c = 0; c < n_out; c++)
+        if (int rc = emit_column(ctx, A, F, outv + c * vw, c)) return rc;
+    const uint8_t* stats;
+    if (int rc = stats_finish(ctx, H, i, F, n_out, 56 * n_units, out_c48, &stats)) return rc;
+    memcpy(out_stats, stats, 56 * (size_t)n_units);
+    return KZG_OK;
+}
+
 // The expression columns (kzg_rows_commit_expr): a set built FROM sets, every output row plain arithmetic in source rows.
 // Each DISTINCT source row (by device pointer: two indices of a repeated handle name one row) that some term names is
 // transformed forward once into its own vector of the lane's quotient workspace; a row no term names is not transformed.

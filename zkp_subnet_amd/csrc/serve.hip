@@ -1769,6 +1769,125 @@ int rows_keccak(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const
     return KZG_OK;
 }
 
+// kzg_rows_commit_ec: a BuilderCall around its own checks; as in rows_keccak, no reservation and no set when every unit is a
+// check.  The curve, modes, flags, names and the entries a mode does not take are checked here, on the host, before a lane is
+// taken
+int rows_ec(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, const kzg_ec_curve* curve,
+            uint32_t n_units, const kzg_ec_unit* units, const kzg_derive_opts* opts, uint8_t* out_commitments48,
+            uint64_t* const out_stats[9], uint64_t* out_handle) {
+    if (!ctx || !input_handles || !out_stats || !out_handle) return KZG_E_ARG;
+    for (int k = 0; k < 9; k++)
+        if (!out_stats[k]) return KZG_E_ARG;
+    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "ec: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (n_units == 0 || n_units > KZG_EC_MAX_UNITS || !units)
+        return fail(ctx, KZG_E_ARG, "ec: n_units must be in [1, KZG_EC_MAX_UNITS]");
+    if (!curve) return fail(ctx, KZG_E_ARG, "ec: the curve must be given");
+    const uint32_t b = curve->bits, L = curve->limbs;
+    if (b == 0 || b > 64) return fail(ctx, KZG_E_ARG, "ec: the limb width b (bits) must be in [1, 64]");
+    if (L == 0 || L > KZG_EC_MAX_LIMBS) return fail(ctx, KZG_E_ARG, "ec: the number of limbs L (limbs) must be in [1, KZG_EC_MAX_LIMBS]");
+    const uint32_t W = b * L;
+    if (W > 256) return fail(ctx, KZG_E_ARG, "ec: the width W = b L must be at most 256");
+    // x < 2^W; x < y; as little-endian words
+    auto fits = [&](const uint64_t* x) {
+        for (uint32_t w = 0; w < 4; w++) {
+            const uint32_t lo = 64 * w;
+            if (lo >= W ? x[w] != 0 : (W - lo < 64 && (x[w] >> (W - lo)) != 0)) return false;
+        }
+        return true;
+    };
+    auto below = [](const uint64_t* x, const uint64_t* y) {
+        for (int w = 3; w >= 0; w--)
+            if (x[w] != y[w]) return x[w] < y[w];
+        return false;
+    };
+    const bool p_small = !curve->p[1] && !curve->p[2] && !curve->p[3] && curve->p[0] < 3;
+    if (!(curve->p[0] & 1u) || p_small) return fail(ctx, KZG_E_ARG, "ec: the modulus p must be odd and at least 3");
+    if (!fits(curve->p)) return fail(ctx, KZG_E_ARG, "ec: the modulus p must be below 2^W");
+    if (!below(curve->a, curve->p)) return fail(ctx, KZG_E_ARG, "ec: the coefficient a must be below p");
+    uint32_t n_out = 0, max_row = 0, n_seen = 0, seen[8 * KZG_EC_MAX_LIMBS * KZG_EC_MAX_UNITS];
+    bool too_many = false;
+    auto see = [&](uint32_t first, uint32_t count) {   // (first < 2^32 - 1: first + l cannot wrap past a uint64)
+        for (uint32_t l = 0; l < count; l++) {
+            const uint64_t row = (uint64_t)first + l;
+            if (row >= 0xffffffffull) {
+                max_row = 0xffffffffu;
+                return;
+            }
+            max_row = std::max(max_row, (uint32_t)row);
+            uint32_t d = 0;
+            while (d < n_seen && seen[d] != (uint32_t)row) d++;
+            if (d == n_seen) {
+                if (n_seen == sizeof(seen) / sizeof(seen[0])) {
+                    too_many = true;
+                    return;
+                }
+                seen[n_seen++] = (uint32_t)row;
+            }
+        }
+    };
+    for (uint32_t u = 0; u < n_units; u++) {
+        const kzg_ec_unit& U = units[u];
+        if (U.mode != KZG_EC_DIV && U.mode != KZG_EC_ADD && U.mode != KZG_EC_CHAIN)
+            return fail(ctx, KZG_E_ARG, "ec: unknown mode (KZG_EC_DIV, KZG_EC_ADD or KZG_EC_CHAIN)");
+        if (U.flags & ~(KZG_EC_CHECK | KZG_EC_IMM_B) || U.reserved)
+            return fail(ctx, KZG_E_ARG, "ec: flags must be made of KZG_EC_CHECK and KZG_EC_IMM_B, reserved must be 0");
+        const bool check = U.flags & KZG_EC_CHECK, imm_b = U.flags & KZG_EC_IMM_B;
+        if (check && U.mode == KZG_EC_CHAIN) return fail(ctx, KZG_E_ARG, "ec: expect (KZG_EC_CHECK) belongs to DIV and ADD units, not to CHAIN");
+        if (imm_b && U.mode != KZG_EC_DIV) return fail(ctx, KZG_E_ARG, "ec: an immediate (KZG_EC_IMM_B) belongs to DIV units");
+        const uint32_t names = U.mode == KZG_EC_DIV ? KZG_EC_R : 7u, n_in = U.mode == KZG_EC_ADD ? 4u : 2u;
+        if (!U.cols || (U.cols & ~names)) return fail(ctx, KZG_E_ARG, "ec: cols must name at least one column, and only columns of the unit's mode");
+        for (uint32_t w = 0; w < 4; w++) {
+            const bool takes = w < n_in && !(w == 1 && imm_b);
+            if (takes != (U.in[w] != KZG_EC_ABSENT))
+                return fail(ctx, KZG_E_ARG, "ec: an operand the mode does not take, or a missing one (KZG_EC_ABSENT beside the mode's operands)");
+            if (takes) see(U.in[w], L);
+            if (!imm_b && U.imm[w]) return fail(ctx, KZG_E_ARG, "ec: the immediate must be 0 without KZG_EC_IMM_B");
+        }
+        if (imm_b && !fits(U.imm)) return fail(ctx, KZG_E_ARG, "ec: the immediate must be below 2^W");
+        if ((U.mode == KZG_EC_CHAIN) != (U.op != KZG_EC_ABSENT))
+            return fail(ctx, KZG_E_ARG, "ec: op belongs to CHAIN units, and a CHAIN unit must have one (KZG_EC_ABSENT elsewhere)");
+        if (U.mode == KZG_EC_CHAIN) see(U.op, 1);
+        for (uint32_t k = 0; k < 3; k++) {
+            const bool takes = check && (U.cols >> k & 1u);
+            if (takes != (U.expect[k] != KZG_EC_ABSENT))
+                return fail(ctx, KZG_E_ARG, "ec: expect must hold one first row per name of cols under KZG_EC_CHECK, KZG_EC_ABSENT elsewhere");
+            if (takes) see(U.expect[k], L);
+        }
+        if (too_many || n_seen > KZG_MAX_BATCH_OPEN)
+            return fail(ctx, KZG_E_ARG, "ec: a call reads at most KZG_MAX_BATCH_OPEN distinct input rows");
+        n_out += check ? 0 : (uint32_t)__builtin_popcount(U.cols) * L;
+    }
+    if (n_out > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "ec: n_out, the committed rows of all units, must be at most KZG_MAX_BATCH_OPEN");
+    if (n_out && !out_commitments48) return KZG_E_ARG;
+    BuilderCall C(ctx, "ec");
+    RowTab it;
+    uint32_t ki = 0;
+    if (int rc = C.begin("ec", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
+    if (max_row >= ki) return fail(ctx, KZG_E_ARG, "ec: an operand run must lie inside the concatenated rows of the input sets");
+    if (int rc = C.ready(n_out, 32, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ)) return rc;
+    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    uint64_t stats[7 * KZG_EC_MAX_UNITS];
+    if (int rc = rows_ec_dev(ctx, C.H, C.i, it, curve, n_units, units, n_out, C.T, C.dst(), c48, stats, C.blind)) return rc;
+    if (n_out) memcpy(out_commitments48, c48, 48 * (size_t)n_out);
+    // the device's runs: counts, singular, mismatch or unknown, segments, first, first_singular, first of the third
+    for (uint32_t u = 0; u < n_units; u++) {
+        const bool chain = units[u].mode == KZG_EC_CHAIN;
+        out_stats[0][u] = stats[u];
+        out_stats[1][u] = stats[4 * n_units + u];
+        out_stats[2][u] = stats[n_units + u];
+        out_stats[3][u] = stats[5 * n_units + u];
+        out_stats[4][u] = chain ? 0 : stats[2 * n_units + u];
+        out_stats[5][u] = chain ? KZG_EC_NONE : stats[6 * n_units + u];
+        out_stats[6][u] = chain ? stats[2 * n_units + u] : 0;
+        out_stats[7][u] = chain ? stats[6 * n_units + u] : KZG_EC_NONE;
+        out_stats[8][u] = stats[3 * n_units + u];
+    }
+    *out_handle = C.commit();
+    return KZG_OK;
+}
+
 // The terms of an expression as rows_expr_dev takes them: a kzg_quotient_terms checked (counts, lengths, canonical
 // coefficients) and copied into the zeroed plan `pl`, its rotations as given into `rots` -- they are reduced by expr_reduce once
 // T is known -- and the largest row it names into *max_row.  may_be_empty: n_terms = 0 is accepted and leaves pl empty
@@ -2729,6 +2848,15 @@ int kzg_rows_commit_keccak(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_
                            uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_handle) {
     return rows_keccak(ctx, UINT32_MAX, n_input_handles, input_handles, n_units, units, opts, out_commitments48, out_perms,
                        out_messages, out_counts, out_first, out_mismatch, out_first_mismatch, out_handle);
+}
+int kzg_rows_commit_ec(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, const kzg_ec_curve* curve,
+                       uint32_t n_units, const kzg_ec_unit* units, const kzg_derive_opts* opts, uint8_t* out_commitments48,
+                       uint64_t* out_counts, uint64_t* out_first, uint64_t* out_singular, uint64_t* out_first_singular,
+                       uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_unknown, uint64_t* out_first_unknown,
+                       uint64_t* out_segments, uint64_t* out_handle) {
+    uint64_t* const st[9] = {out_counts,         out_first,   out_singular,      out_first_singular, out_mismatch,
+                             out_first_mismatch, out_unknown, out_first_unknown, out_segments};
+    return rows_ec(ctx, UINT32_MAX, n_input_handles, input_handles, curve, n_units, units, opts, out_commitments48, st, out_handle);
 }
 int kzg_rows_commit_expr(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
                          const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48, uint64_t* out_nonzero,

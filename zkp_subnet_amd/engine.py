@@ -1683,6 +1683,191 @@ class HipEngine:
         return rs, {"perms": [int(v) for v in st[0]], "messages": [int(v) for v in st[1]], "counts": [int(v) for v in st[2]],
                     "first": none(st[3]), "mismatch": [int(v) for v in st[4]], "first_mismatch": none(st[5])}
 
+    # ---- a set built from sets: arithmetic of an elliptic curve over a foreign field: a / b mod p, point addition, chains
+    _EC_CURVE_KEYS = ("bits", "limbs", "p", "a")
+    _EC_KEYS = {"div": ("mode", "a", "b", "out", "expect"), "add": ("mode", "x1", "y1", "x2", "y2", "out", "expect"),
+                "chain": ("mode", "px", "py", "op", "cols")}
+    _EC_MODES = {"div": _native.KZG_EC_DIV, "add": _native.KZG_EC_ADD, "chain": _native.KZG_EC_CHAIN}
+
+    @classmethod
+    def ec_call(cls, curve, units, what: str = "commit_ec", n_rows: Optional[int] = None) -> Tuple[tuple, List[tuple]]:
+        """The kzg_ec_curve fields (bits, limbs, p, a) and per unit the kzg_ec_unit fields (mode, flags, cols, op, in[4],
+        expect[3], imm) of a call.  curve: a mapping with bits (b in [1, 64]), limbs (L in [1, 4], W = b L <= 256), p (odd, 3 <=
+        p < 2^W) and a (below p).  A unit is a mapping.  {"mode": "div", "a": first row, "b": first row or ("imm", v), "out":
+        True}; {"mode": "add", "x1", "y1", "x2", "y2": first rows, "out": names among lam, x3, y3}; either with "expect" in
+        place of out is a check: one first row for div, three entries for add (lam, x3, y3; None: that name is not compared).
+        {"mode": "chain", "px", "py": first rows, "op": row, "cols": names among ax, ay, lam}.  An integer may be given as a
+        Python int or as a decimal or 0x string.  n_rows: the number of concatenated input rows, where known: an operand run
+        must lie inside.  Raises KzgError(KZG_E_ARG) with the cause; needs no device."""
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: ec: {why}")   # noqa: E731
+        is_u = lambda v, top: isinstance(v, int) and not isinstance(v, bool) and 0 <= v < top   # noqa: E731
+        ABSENT = _native.KZG_EC_ABSENT
+
+        def big(v, name):
+            if isinstance(v, str):
+                try:
+                    v = int(v, 0)
+                except ValueError:
+                    raise bad(f"{name} must be an integer, or a decimal or 0x string") from None
+            if not isinstance(v, int) or isinstance(v, bool) or v < 0:
+                raise bad(f"{name} must be a non-negative integer")
+            return v
+
+        if not isinstance(curve, dict):
+            raise bad("the curve is a mapping with bits, limbs, p and a")
+        extra = set(curve) - set(cls._EC_CURVE_KEYS)
+        if extra:
+            raise bad(f"unknown field {sorted(extra)[0]!r} of the curve (the fields are {', '.join(cls._EC_CURVE_KEYS)})")
+        b, L = curve.get("bits"), curve.get("limbs")
+        if not is_u(b, 65) or b == 0:
+            raise bad("the limb width b (bits) must be an integer in [1, 64]")
+        if not is_u(L, _native.KZG_EC_MAX_LIMBS + 1) or L == 0:
+            raise bad(f"the number of limbs L (limbs) must be an integer in [1, {_native.KZG_EC_MAX_LIMBS}]")
+        W = b * L
+        if W > 256:
+            raise bad("the width W = b L must be at most 256")
+        if curve.get("p") is None or curve.get("a") is None:
+            raise bad("the curve must give the modulus p and the coefficient a")
+        p, a = big(curve["p"], "the modulus p"), big(curve["a"], "the coefficient a")
+        if p % 2 == 0 or p < 3:
+            raise bad("the modulus p must be odd and at least 3")
+        if p >> W:
+            raise bad("the modulus p must be below 2^W")
+        if a >= p:
+            raise bad("the coefficient a must be below p")
+        units = list(units) if isinstance(units, (list, tuple)) else None
+        if not units or len(units) > _native.KZG_EC_MAX_UNITS:
+            raise bad(f"units must be a list of 1 .. {_native.KZG_EC_MAX_UNITS} entries (n_units)")
+        seen, recs, n_out = set(), [], 0
+
+        def run(v, name, count=L):
+            if not is_u(v, ABSENT):
+                raise bad(f"{name} must be a first row, an integer in [0, 2^32 - 1)")
+            if n_rows is not None and v + count > n_rows:
+                raise bad(f"the operand run of {name} reaches beyond the {n_rows} concatenated rows of the input sets")
+            seen.update(range(v, v + count))
+            return v
+
+        for un in units:
+            if not isinstance(un, dict) or "mode" not in un:
+                raise bad("a unit is a mapping with mode and the fields of its mode")
+            mode = un["mode"]
+            if not isinstance(mode, str) or mode not in cls._EC_MODES:
+                raise bad(f'unknown mode {mode!r} (one of "div", "add", "chain")')
+            keys = cls._EC_KEYS[mode]
+            extra = set(un) - set(keys)
+            if extra:
+                if mode == "chain" and "expect" in extra:
+                    raise bad("expect belongs to div and add units, not to chain")
+                raise bad(f"unknown field {sorted(extra)[0]!r} (the fields of a {mode} unit are {', '.join(keys)})")
+            flags, cols, op, imm, ins, expect = 0, 0, ABSENT, 0, [ABSENT] * 4, [ABSENT] * 3
+            if mode == "chain":
+                names = _native.KZG_EC_CHAIN_NAMES
+                ins[0], ins[1] = run(un.get("px"), "px"), run(un.get("py"), "py")
+                op = run(un.get("op"), "op", 1)
+                picked = un.get("cols")
+                if not isinstance(picked, (list, tuple)) or not picked:
+                    raise bad(f"cols must hold 1 .. 3 column names among {', '.join(names)}")
+            else:
+                names = ("r",) if mode == "div" else _native.KZG_EC_ADD_NAMES
+                if mode == "div":
+                    ins[0] = run(un.get("a"), "a")
+                    vb = un.get("b")
+                    if isinstance(vb, (list, tuple)):
+                        if len(vb) != 2 or vb[0] != "imm":
+                            raise bad('an immediate is ("imm", value)')
+                        imm = big(vb[1], "an immediate")
+                        if imm >> W:
+                            raise bad("the immediate must be below 2^W")
+                        flags |= _native.KZG_EC_IMM_B
+                    else:
+                        ins[1] = run(vb, "b")
+                else:
+                    ins = [run(un.get(k), k) for k in ("x1", "y1", "x2", "y2")]
+                has_out, has_exp = un.get("out") is not None, un.get("expect") is not None
+                if has_out and has_exp:
+                    raise bad("out together with expect: a unit commits, or it is a check")
+                if not has_out and not has_exp:
+                    raise bad("a unit needs out, or expect for a check")
+                if has_exp:
+                    ex = un["expect"]
+                    if not isinstance(ex, (list, tuple)) or len(ex) != len(names):
+                        raise bad("a wrong number of expect rows: one first row for div, three entries (lam, x3, y3; None: not "
+                                  "compared) for add")
+                    picked = [k for k, v in zip(names, ex) if v is not None]
+                    if not picked:
+                        raise bad("expect must name at least one first row")
+                    for j, v in enumerate(ex):
+                        if v is not None:
+                            expect[j] = run(v, "an entry of expect")
+                    flags |= _native.KZG_EC_CHECK
+                elif mode == "div":
+                    if un["out"] is not True:
+                        raise bad("the out of a div unit is True")
+                    picked = ["r"]
+                else:
+                    picked = un["out"]
+                    if not isinstance(picked, (list, tuple)) or not picked:
+                        raise bad(f"out must hold 1 .. 3 names among {', '.join(names)}")
+            for name in picked:
+                if name not in names:
+                    raise bad(f"unknown name {name!r} (the names of a {mode} unit are {', '.join(names)})")
+            if len(set(picked)) != len(picked):
+                raise bad("a name is repeated")
+            for name in picked:
+                cols |= 1 << names.index(name)
+            if not flags & _native.KZG_EC_CHECK:
+                n_out += len(picked) * L
+            recs.append((cls._EC_MODES[mode], flags, cols, op, ins, expect, imm))
+        if len(seen) > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"the units read {len(seen)} distinct input rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+        if n_out > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"n_out: the units give {n_out} output rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+        return (b, L, p, a), recs
+
+    @staticmethod
+    def ec_structs(cv, recs) -> Tuple["_native.EcCurve", object]:
+        w64 = lambda v: (ctypes.c_uint64 * 4)(*[(v >> (64 * k)) & 0xffffffffffffffff for k in range(4)])   # noqa: E731
+        curve = _native.EcCurve(cv[0], cv[1], w64(cv[2]), w64(cv[3]))
+        arr = (_native.EcUnit * len(recs))(*[_native.EcUnit(r[0], r[1], r[2], r[3], (ctypes.c_uint32 * 4)(*r[4]),
+                                                            (ctypes.c_uint32 * 3)(*r[5]), 0, w64(r[6])) for r in recs])
+        return curve, arr
+
+    @staticmethod
+    def ec_n_out(cv, recs) -> int:
+        return sum(bin(r[2]).count("1") * cv[1] for r in recs if not r[1] & _native.KZG_EC_CHECK)
+
+    def commit_ec(self, input_sets: Sequence[object], curve: dict, units: Sequence[dict], usable: Optional[int] = None,
+                  tail: Sequence[bytes] = ()) -> Tuple[Optional["RowSet"], dict]:
+        """kzg_rows_commit_ec over the concatenated rows of input_sets (RowSet objects or bare handles).  curve and units: see
+        ec_call.  A wide value is L consecutive rows of b bits; an operand at or above p is reduced mod p and its row counted.
+        A div unit commits the L rows of a b^-1 mod p (0 and `singular` where b has no inverse); an add unit the named ones of
+        lam, x3, y3 of (x1, y1) + (x2, y2), the doubling where the points are equal, zeros and `singular` on an exceptional
+        row; either with expect commits nothing and counts the rows whose expected cells differ; a chain unit commits the named
+        ones of ax, ay, lam: the accumulator before each row's step and the step's lambda, for the op-codes 0 hold, 1 load, 2
+        add (px, py), 3 double.  Returns (the new RowSet of all committed rows in unit order, or None when every unit is a
+        check; {"counts", "first", "singular", "first_singular", "mismatch", "first_mismatch", "unknown", "first_unknown",
+        "segments"} per unit).  usable and tail: as for commit_derived, the tail column-major over the committed rows."""
+        what = "commit_ec"
+        ni, hi = self._handle_array(input_sets, what)
+        ks = [getattr(x, "k", None) for x in input_sets]
+        cv, recs = self.ec_call(curve, units, what, None if any(k is None for k in ks) else sum(ks))
+        n_out = self.ec_n_out(cv, recs)
+        wi, T, lay = self._column_layout(what, input_sets, n_out, "n_out", "read", usable, tail)
+        opts = _native.DeriveOpts(*lay) if lay else None
+        cs, arr = self.ec_structs(cv, recs)
+        c, h = ctypes.create_string_buffer(48 * max(n_out, 1)), ctypes.c_uint64(0)
+        st = [(ctypes.c_uint64 * len(recs))() for _ in range(9)]
+        self._chk(self._lib.kzg_rows_commit_ec(self._h, ni, hi, ctypes.byref(cs), len(recs), arr,
+                                               ctypes.byref(opts) if opts is not None else None, c if n_out else None, *st,
+                                               ctypes.byref(h)))
+        rs = RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]) if n_out else None
+        none = lambda xs: [None if int(v) == _native.KZG_EC_NONE else int(v) for v in xs]   # noqa: E731
+        ints = lambda xs: [int(v) for v in xs]   # noqa: E731
+        return rs, {"counts": ints(st[0]), "first": none(st[1]), "singular": ints(st[2]), "first_singular": none(st[3]),
+                    "mismatch": ints(st[4]), "first_mismatch": none(st[5]), "unknown": ints(st[6]), "first_unknown": none(st[7]),
+                    "segments": ints(st[8])}
+
     # ---- a set built from sets: columns that are plain arithmetic in resident columns, and gates checked row by row
     def commit_expr(self, input_sets: Sequence[object], exprs: Sequence[Sequence], usable: Optional[int] = None,
                     tail: Sequence[bytes] = ()) -> Tuple[Optional["RowSet"], List[int], List[Optional[int]]]:
