@@ -1596,7 +1596,9 @@ int kzg_rows_commit_keccak(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_
  * OUT OF SCOPE: L > 4 (BLS12-381's Fp); Edwards and Montgomery forms; projective coordinates; the point at infinity; an
  * on-curve check; subtraction or negation ops; per-row moduli; an even modulus; the quotient and carry columns of the gates
  * (kzg_rows_commit_wide over these outputs gives them).  A CHAIN unit runs one lane of the device per segment: one segment that
- * fills the whole column is correct, and slow.
+ * fills the whole column is correct, and slow.  (Twisted Edwards curves over the scalar field ITSELF -- Jubjub,
+ * Bandersnatch -- are not foreign and have their own call, kzg_rows_commit_edwards, whose chain walks in projective coordinates
+ * with no inversion per step.)
  * SOUNDNESS: nothing here is a proof.  The columns are prover data; the argument is the caller's MULMOD / CARRY gates over
  * lambda, x3 and y3 (lambda (x2 - x1) = y2 - y1, and so on, mod p) plus the range lookups of every limb.  Zero counts convince
  * no verifier. */
@@ -1639,6 +1641,95 @@ int kzg_rows_commit_ec(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* i
                        uint64_t* out_first_singular /* n_units */, uint64_t* out_mismatch /* n_units */,
                        uint64_t* out_first_mismatch /* n_units */, uint64_t* out_unknown /* n_units */,
                        uint64_t* out_first_unknown /* n_units */, uint64_t* out_segments /* n_units */, uint64_t* out_handle);
+/* THE NATIVE TWISTED-EDWARDS COLUMNS: a set built FROM sets, the columns of the chip that does curve arithmetic on a twisted
+ * Edwards curve defined over the scalar field Fr ITSELF -- Jubjub (RedJubjub signatures and Pedersen hashes of Zcash Sapling),
+ * Bandersnatch (the Pedersen vector commitments of Ethereum's Verkle tries).  A coordinate is ONE cell of ONE resident row, read
+ * as the field element it is: no limbs, no range counts.  The accumulator trace of a scalar multiplication depends on the row
+ * before it non-linearly, which neither kzg_rows_commit_expr (no dependence from row to row) nor kzg_rows_commit_recurrence
+ * (affine) expresses, and kzg_rows_commit_ec works on limbs over a foreign field with no Edwards form.  THE CURVE is one per
+ * call: A x^2 + y^2 = 1 + D x^2 y^2 with A = curve->a_be32 and D = curve->d_be32, canonical scalars, A != 0, D != 0, A != D.  The
+ * library generates no curve and ships no constant.  THE LAW is arithmetic on pairs of field elements, with no on-curve check;
+ * the neutral element is (0, 1).  With tau = D x1 x2 y1 y2:
+ *     x3 = (x1 y2 + y1 x2) / (1 + tau)          y3 = (y1 y2 - A x1 x2) / (1 - tau)
+ * and the doubling is this same formula with both operands equal (a dedicated doubling that substitutes the curve equation
+ * differs on off-curve pairs and is not used).  A row or step with tau = 1 or tau = -1 is EXCEPTIONAL.  The concatenated rows of
+ * the input_handles sets (as in kzg_rows_open) are the source columns.  An operand slot in[w] is a row index, or
+ * KZG_EDWARDS_IMM: then the operand is imm_be32[w] on every row (canonical; a constant point, a fixed base, the neutral
+ * element); imm_be32[w] is 0 beside a row.  A call has 1 <= n_units <= KZG_EDWARDS_MAX_UNITS units.  With n = opts->usable, or
+ * T in the plain layout:
+ *   KZG_EDWARDS_ADD    in[0 .. 3] = x1, y1, x2, y2; one addition per row t' < n.  cols picks among KZG_EDWARDS_X3 and
+ *                      KZG_EDWARDS_Y3; out_order[0 .. n_cols) lists the picked names (0: x3, 1: y3) in the order of their output
+ *                      rows (KZG_EDWARDS_ABSENT beyond).  An exceptional row writes x3 = y3 = 0, is counted in out_singular[u],
+ *                      and the smallest such row is out_first_singular[u] (KZG_EDWARDS_NONE: none).  Name the same rows twice to
+ *                      double a column.
+ *   KZG_EDWARDS_CHECK  (a flag on ADD) the unit commits NOTHING: expect[k] is the row that name k of cols is compared with
+ *                      (KZG_EDWARDS_ABSENT beside a name that is not in cols; out_order is all KZG_EDWARDS_ABSENT);
+ *                      out_mismatch[u] is the number of rows t' < n where an expected cell differs from the computed one (an
+ *                      exceptional row computes 0), out_first_mismatch[u] the smallest such row.  No inversion runs: the
+ *                      device compares expect (1 +- tau) with the numerator.
+ *   KZG_EDWARDS_CHAIN  the accumulator trace of a double-and-add or of a multi-scalar sum: in[0] = px, in[1] = py, op the row of
+ *                      the op-code column (compared as a whole 255-bit integer); cols picks among KZG_EDWARDS_AX and
+ *                      KZG_EDWARDS_AY, out_order as above (0: ax, 1: ay).  The accumulator is (0, 1) before row 0.  Row t holds
+ *                      the accumulator BEFORE the step; then op[t] acts: 0 hold; 1 load, acc <- (px[t], py[t]); 2 acc <- acc +
+ *                      (px[t], py[t]); 3 acc <- acc + acc; 4 acc <- acc + (-px[t], py[t]); any other value (2^32 + 2 is one)
+ *                      holds and is counted in out_unknown[u] / out_first_unknown[u].  An exceptional step leaves acc = (0, 1)
+ *                      and is counted in out_singular[u].  px and py are not read where op is 0, 3 or unknown.  A SEGMENT
+ *                      begins at row 0 and at every load; out_segments[u] is their number.  The chain stops at n; there is no
+ *                      closing row.  KZG_EDWARDS_CHECK is refused.
+ * Statistics a mode does not have are 0 and KZG_EDWARDS_NONE.  All committed rows of a call form ONE new set of the same worker
+ * and length, in the order of units, then of out_order: out_commitments48[c] equals kzg_rows_commit(i, n_out, these rows, T, 1,
+ * ..)[c] byte for byte, and *out_handle opens, evaluates, combines, releases, goes stale and counts against KZG_MAX_ROW_SETS
+ * like any other.  A call made of checks alone creates no set (*out_handle = 0, out_commitments48 may be null), runs no inverse
+ * transform and no MSM.  ON THE DEVICE: one launch computes every unit WITHOUT a field inversion -- an ADD unit leaves the
+ * numerators (x1 y2 + y1 x2)(1 - tau), (y1 y2 - A x1 x2)(1 + tau) and the denominator 1 - tau^2; a CHAIN unit walks its
+ * segments in projective coordinates (X : Y : Z) with the unified mixed addition and leaves X, Y and Z per row -- then ONE
+ * batched inversion over the denominators of every unit, then one launch that multiplies through.  Nothing row-sized crosses
+ * the host link.  A call reads at most KZG_MAX_BATCH_OPEN distinct rows and commits at most KZG_MAX_BATCH_OPEN.  opts, handle
+ * lists, worker, T, staleness and threads: as for kzg_rows_commit_ec.  KZG_E_ARG with a message that begins "edwards:" and
+ * names the cause: n_units outside its range; A, D or an immediate not canonical; A = 0, D = 0 or A = D; an unknown mode or
+ * flag, KZG_EDWARDS_CHECK on a CHAIN unit; cols empty or with a name the mode does not have; an out_order that is not the
+ * picked names once each; an operand, op or expect entry the mode does not take, or a missing one; a non-zero immediate beside
+ * a row; a row beyond the concatenation; more than KZG_MAX_BATCH_OPEN output rows or distinct input rows; T above 2^32; the
+ * usable and tail refusals of kzg_rows_commit_derived; the handle refusals of kzg_rows_open.  All but the last four are
+ * checked on the host before a lane is taken.  After any error the context keeps serving and no set or buffer leaks.
+ * OUT OF SCOPE: Montgomery and short-Weierstrass forms over Fr; a per-row scalar multiplication (a chain segment gives it, with
+ * its trace); a helper column for tau (an expression column: kzg_rows_commit_expr); on-curve and subgroup checks; windowed or
+ * signed-digit op-codes beyond 4; parallelism inside one segment: a CHAIN unit runs one lane of the device per segment.
+ * SOUNDNESS: nothing here is a proof.  The columns are prover data; the argument is the caller's two addition gates, x3 (1 +
+ * D x1 x2 y1 y2) = x1 y2 + y1 x2 and y3 (1 - D x1 x2 y1 y2) = y1 y2 - A x1 x2, under the op-code's selector.  Zero counts
+ * convince no verifier. */
+#define KZG_EDWARDS_ADD   1
+#define KZG_EDWARDS_CHAIN 2
+#define KZG_EDWARDS_CHECK 1u                /* flags (ADD): compare with expect, commit nothing */
+#define KZG_EDWARDS_X3    1u                /* cols (ADD): x3, y3 */
+#define KZG_EDWARDS_Y3    2u
+#define KZG_EDWARDS_AX    1u                /* cols (CHAIN): ax, ay */
+#define KZG_EDWARDS_AY    2u
+#define KZG_EDWARDS_IMM    0xfffffffeu      /* in[w]: the operand is imm_be32[w] */
+#define KZG_EDWARDS_ABSENT 0xffffffffu      /* an operand, op, expect or out_order entry the unit does not have */
+#define KZG_EDWARDS_NONE   0xffffffffffffffffull   /* out_first*: none */
+#define KZG_EDWARDS_MAX_UNITS 4
+typedef struct kzg_edwards_curve {
+    uint8_t a_be32[32];          /* A: canonical, not 0 */
+    uint8_t d_be32[32];          /* D: canonical, not 0, not A */
+} kzg_edwards_curve;
+typedef struct kzg_edwards_unit {
+    uint32_t mode;               /* KZG_EDWARDS_ADD or KZG_EDWARDS_CHAIN */
+    uint32_t flags;              /* KZG_EDWARDS_CHECK */
+    uint32_t cols;               /* the names that are committed (or compared), a mask of the mode's KZG_EDWARDS_* names */
+    uint32_t op;                 /* CHAIN: the row of the op-code column; else KZG_EDWARDS_ABSENT */
+    uint32_t in[4];              /* rows or KZG_EDWARDS_IMM.  ADD: x1, y1, x2, y2; CHAIN: px, py; KZG_EDWARDS_ABSENT beyond */
+    uint32_t expect[2];          /* with KZG_EDWARDS_CHECK: [k] the row name k is compared with; else KZG_EDWARDS_ABSENT */
+    uint32_t out_order[2];       /* the picked names (0 or 1) in the order of their output rows; KZG_EDWARDS_ABSENT beyond */
+    uint8_t imm_be32[4][32];     /* [w]: the operand where in[w] is KZG_EDWARDS_IMM; else 0 */
+} kzg_edwards_unit;
+int kzg_rows_commit_edwards(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                            const kzg_edwards_curve* curve, uint32_t n_units, const kzg_edwards_unit* units,
+                            const kzg_derive_opts* opts /* NULL: plain */, uint8_t* out_commitments48 /* n_out * 48 */,
+                            uint64_t* out_singular /* n_units */, uint64_t* out_first_singular /* n_units */,
+                            uint64_t* out_mismatch /* n_units */, uint64_t* out_first_mismatch /* n_units */,
+                            uint64_t* out_unknown /* n_units */, uint64_t* out_first_unknown /* n_units */,
+                            uint64_t* out_segments /* n_units */, uint64_t* out_handle);
 /* THE QUOTIENT WITH LOOKUP SELECTORS: kzg_rows_commit_quotient_zk and kzg_rows_quotient_part for lookups that are enabled on
  * some rows only.  selectors->selector_rows holds L = lookup->n_lookups entries, each a row index into the call's concatenated
  * rows (the caller's fixed column q_l, the row that kzg_rows_commit_multiplicities_sel / _lookup_sum_sel read) or
@@ -2049,6 +2140,13 @@ int kzg_multi_rows_commit_ec(kzg_multi* mh, uint32_t i, uint32_t n_input_handles
                              uint8_t* out_commitments48, uint64_t* out_counts, uint64_t* out_first, uint64_t* out_singular,
                              uint64_t* out_first_singular, uint64_t* out_mismatch, uint64_t* out_first_mismatch,
                              uint64_t* out_unknown, uint64_t* out_first_unknown, uint64_t* out_segments, uint64_t* out_handle);
+/* kzg_rows_commit_edwards on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_edwards(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                  const kzg_edwards_curve* curve, uint32_t n_units, const kzg_edwards_unit* units,
+                                  const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_singular,
+                                  uint64_t* out_first_singular, uint64_t* out_mismatch, uint64_t* out_first_mismatch,
+                                  uint64_t* out_unknown, uint64_t* out_first_unknown, uint64_t* out_segments,
+                                  uint64_t* out_handle);
 
 /* ---- device-resident inputs (what a serving loop and bench.py use: inputs already in HBM when timing starts).
  *      slot in [0, 4).  to_mont=1 stores Montgomery form (rows for commit/open), 0 canonical (MSM scalars). */

@@ -76,6 +76,16 @@ KZG_EC_NONE = 0xffffffffffffffff
 KZG_EC_MAX_UNITS, KZG_EC_MAX_LIMBS = 4, 4
 KZG_EC_ADD_NAMES = ("lam", "x3", "y3")
 KZG_EC_CHAIN_NAMES = ("ax", "ay", "lam")
+# kzg_rows_commit_edwards: kzg_edwards_unit.mode, the flag, a slot that holds an immediate, "no such entry", "none", the limit, and
+# the names of a unit's columns in the order of their bits in kzg_edwards_unit.cols
+KZG_EDWARDS_ADD, KZG_EDWARDS_CHAIN = 1, 2
+KZG_EDWARDS_CHECK = 1
+KZG_EDWARDS_IMM = 0xfffffffe
+KZG_EDWARDS_ABSENT = 0xffffffff
+KZG_EDWARDS_NONE = 0xffffffffffffffff
+KZG_EDWARDS_MAX_UNITS = 4
+KZG_EDWARDS_ADD_NAMES = ("x3", "y3")
+KZG_EDWARDS_CHAIN_NAMES = ("ax", "ay")
 KZG_MAX_EXPR_FACTORS = 8   # kzg_rows_commit_expr: factors of one term
 KZG_EXPR_CHECK = 1   # kzg_expr.flags: evaluate and count only
 KZG_EXPR_NONE = 0xffffffffffffffff   # out_first: no non-zero cell
@@ -208,6 +218,17 @@ class EcUnit(ctypes.Structure):
                 ("reserved", _U32), ("imm", _U64 * 4)]
 
 
+class EdwardsCurve(ctypes.Structure):
+    """kzg_edwards_curve"""
+    _fields_ = [("a_be32", ctypes.c_uint8 * 32), ("d_be32", ctypes.c_uint8 * 32)]
+
+
+class EdwardsUnit(ctypes.Structure):
+    """kzg_edwards_unit"""
+    _fields_ = [("mode", _U32), ("flags", _U32), ("cols", _U32), ("op", _U32), ("in_", _U32 * 4), ("expect", _U32 * 2),
+                ("out_order", _U32 * 2), ("imm_be32", (ctypes.c_uint8 * 32) * 4)]
+
+
 class Col(ctypes.Structure):
     """kzg_col"""
     _fields_ = [("data", ctypes.c_void_p), ("count", ctypes.c_uint64), ("kind", ctypes.c_uint32), ("fill_be32", ctypes.c_char_p)]
@@ -301,6 +322,8 @@ SYMBOLS = {
                                     _B] + [ctypes.POINTER(_U64)] * 7),
     "kzg_rows_commit_ec": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(EcCurve), _U32, ctypes.POINTER(EcUnit),
                                 ctypes.POINTER(DeriveOpts), _B] + [ctypes.POINTER(_U64)] * 10),
+    "kzg_rows_commit_edwards": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(EdwardsCurve), _U32,
+                                     ctypes.POINTER(EdwardsUnit), ctypes.POINTER(DeriveOpts), _B] + [ctypes.POINTER(_U64)] * 8),
     "kzg_rows_commit_derived": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp), ctypes.POINTER(DeriveOpts), _B,
                                      ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_expr": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,
@@ -437,6 +460,9 @@ SYMBOLS = {
                                           ctypes.POINTER(DeriveOpts), _B] + [ctypes.POINTER(_U64)] * 7),
     "kzg_multi_rows_commit_ec": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(EcCurve), _U32, ctypes.POINTER(EcUnit),
                                       ctypes.POINTER(DeriveOpts), _B] + [ctypes.POINTER(_U64)] * 10),
+    "kzg_multi_rows_commit_edwards": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(EdwardsCurve), _U32,
+                                           ctypes.POINTER(EdwardsUnit), ctypes.POINTER(DeriveOpts), _B]
+                                      + [ctypes.POINTER(_U64)] * 8),
     "kzg_multi_rows_commit_derived": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(DeriveOp),
                                            ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_expr": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Expr), ctypes.POINTER(ExprOpts), _B,

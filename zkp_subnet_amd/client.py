@@ -1246,6 +1246,54 @@ class Client:
         return {"handle": None if rs is None else int(rs.handle),
                 "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments], **st}
 
+    # ---- the native twisted-Edwards chip: point addition on a curve over the scalar field itself, accumulator chains
+    @_guard
+    def worker_commit_edwards(self, input_handles: Sequence[int], curve: dict, units: Sequence[dict],
+                              usable: Optional[int] = None, tail: Sequence[str] = ()):
+        """Extension: columns of arithmetic on a twisted Edwards curve over the scalar field itself (Jubjub, Bandersnatch),
+        computed from the rows of the input_handles sets and committed on the device as one new set.  curve: {"a": A, "d": D},
+        the coefficients of A x^2 + y^2 = 1 + D x^2 y^2, scalars below r as integers or decimal / 0x strings, not 0, not equal.
+        The library generates no curve and ships no constant.  A coordinate is one cell; a slot is a row index or ["imm",
+        value].  The law, with tau = D x1 x2 y1 y2: x3 = (x1 y2 + y1 x2) / (1 + tau), y3 = (y1 y2 - A x1 x2) / (1 - tau); the
+        neutral element is (0, 1); there is no on-curve check; a row with tau = 1 or -1 is exceptional.  units: 1 to 4 objects.
+        {"mode": "add", "x1", "y1", "x2", "y2": slots, "out": [names among x3, y3]} commits one row per name, in that order;
+        an exceptional row gives zeros and is counted in `singular`.  With "expect": [row or null, row or null] in place of out
+        it commits nothing and reports `mismatch` and `first_mismatch`.  {"mode": "chain", "px", "py": slots, "op": row,
+        "cols": [names among ax, ay]} commits the accumulator before each row's step: op 0 holds, 1 loads (px, py), 2 adds it,
+        3 doubles, 4 subtracts it, any other value holds and is counted in `unknown`; the accumulator is (0, 1) before row 0
+        and after an exceptional step; `segments` counts row 0 and the loads.  usable and tail: as for worker_commit_derived.
+        Returns the handle (null when every unit is a check), the commitments and the statistics per unit.  Nothing here is a
+        proof: the columns are prover data and the argument is the caller's two addition gates under the op-code's selector."""
+        what = "worker_commit_edwards"
+        hs = _handles(input_handles)
+        try:
+            recs = []
+            for un in units:
+                if not isinstance(un, dict):
+                    raise ValueError(f"a unit is an object: {un!r}")
+                rec = dict(un)
+                for k in ("x1", "y1", "x2", "y2", "px", "py"):
+                    if isinstance(rec.get(k), list):
+                        rec[k] = tuple(rec[k])
+                recs.append(rec)
+        except (TypeError, ValueError, IndexError, KeyError) as e:
+            raise codec.CodecError(f"{what}: units must be a list of objects: {e!r}") from e
+        if not recs:
+            raise codec.CodecError(f"{what}: units must not be empty")
+        if not isinstance(curve, dict):
+            raise codec.CodecError(f"{what}: curve must be an object with a and d")
+        if usable is None:
+            if tail:
+                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
+            tb = []
+        else:
+            usable, tb = self._blind(what, usable, tail)
+            if usable == 0:
+                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        rs, st = self.engine.commit_edwards(hs, dict(curve), recs, usable, tb)
+        return {"handle": None if rs is None else int(rs.handle),
+                "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments], **st}
+
     @staticmethod
     def shuffle_quotient_terms(z_row: int, input_rows: Sequence[int], shuffle_rows: Sequence[int], n_groups: int, width: int,
                                theta: str, gamma: str, coeff: str, active_row: Optional[int] = None,

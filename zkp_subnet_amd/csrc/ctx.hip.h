@@ -14,6 +14,7 @@
 //   fr_sha256.hip the kernel of kzg_rows_commit_sha256: the SHA-256 compression per row, as a check, or as a chained round trace
 //   fr_keccak.hip the kernel of kzg_rows_commit_keccak: Keccak-f[1600] per row, as a check, or as a chained round trace of 64-bit lanes
 //   fr_ec.hip     the kernel of kzg_rows_commit_ec: a b^-1 mod an odd p, affine point addition and doubling, the accumulator trace of a chain
+//   fr_edwards.hip the kernels of kzg_rows_commit_edwards: twisted-Edwards addition over Fr itself as numerators and a denominator, the projective chain
 //   fr_expr.hip   the kernel of kzg_rows_commit_expr: sums of products of rotated resident columns on H, counted and stored
 //   fr_recur.hip  the scan of kzg_rows_commit_recurrence: v[t + 1] = A[t] v[t] + B[t] as a ladder over affine maps
 //   fr_join.hip   the hash join of kzg_rows_commit_multiplicities, and the fetch of kzg_rows_commit_fetch that walks it
@@ -533,6 +534,14 @@ int rows_keccak_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs,
 int rows_ec_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const kzg_ec_curve* curve, uint32_t n_units,
                 const kzg_ec_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48, uint64_t* out_stats,
                 const Blind* lay);
+// the n_out committed rows of the n_units twisted-Edwards units over `curve` (checked by the caller: the curve, canonical
+// immediates, modes, flags, names, out orders, rows inside `inputs`) into a new n_out-row set's buffer dst (null when n_out =
+// 0: then no inversion, no transform back and no MSM runs): their commitments and five runs of n_units statistics (exceptional
+// rows or steps, mismatching rows or on a CHAIN unit unknown op-codes, segments, then the smallest row of the first two kinds,
+// KZG_EDWARDS_NONE: none).  lay: as for rows_derived_dev
+int rows_edwards_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const kzg_edwards_curve* curve,
+                     uint32_t n_units, const kzg_edwards_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48,
+                     uint64_t* out_stats, const Blind* lay);
 // the n_out committed ones of the n_exprs expressions (checked by the caller: term counts and lengths in range, rows inside
 // `inputs`, rotations reduced into [0, T), canonical coefficients; is_check[e] != 0: expression e is only counted) into a new
 // n_out-row set's buffer dst (null when n_out = 0: then no transform back and no MSM runs): their commitments, and per

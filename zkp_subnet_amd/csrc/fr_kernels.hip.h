@@ -579,6 +579,42 @@ static_assert(sizeof(EcTab) + 64 <= 4096 && POLY_MAX_ROWS <= 256, "the unit tabl
 // and may coincide; out must not overlap a source.  Returns without a launch on a table that the caller's checks should have
 // refused (p even or below 3, a >= p, bits or limbs out of range, an unknown mode, no name)
 void launch_ec(hipStream_t s, const EcTab& tab, uint64_t T, uint64_t n, uint64_t* stats);
+// ---- the native twisted-Edwards columns of kzg_rows_commit_edwards (fr_edwards.hip).  A coordinate is one cell of source vector
+// slot[w] (src + slot T 8 words; ADD: x1, y1, x2, y2; CHAIN: px, py) or, at EDW_IMM, the unit's immediate imm[w]; opv: the vector
+// of a CHAIN unit's op-code column.  a, d and imm are canonical integers as 8 little-endian 32-bit words.  cols: bit k set: name k
+// (ADD: x3, y3; CHAIN: ax, ay) is computed; out[k]: the vector it is written to (null: not written); q: the unit's slice of the
+// denominator vector.  q null: a check (ADD): name k is compared with the cell of source vector exp[k]
+#define EDW_MAX_UNITS 4
+#define EDW_ADD 1
+#define EDW_CHAIN 2
+#define EDW_IMM 0xffu
+struct EdwUnit {
+    uint32_t *out[2], *q;
+    uint32_t mode, cols, opv, reserved;
+    uint8_t slot[4], exp[2], pad[2];
+    uint32_t imm[4][8];
+};
+struct EdwTab {
+    EdwUnit u[EDW_MAX_UNITS];
+    const uint32_t* src;
+    uint32_t n_units, reserved;
+    uint32_t a[8], d[8];
+};
+static_assert(sizeof(EdwTab) + 64 <= 4096 && POLY_MAX_ROWS < EDW_IMM, "the unit table rides as a kernel argument; slots ride in bytes");
+// ONE launch for the n_units units of tab, over all T rows: a committing unit leaves its numerators (ADD) or projective X, Y
+// (CHAIN) in out[k] on the rows t < n and its denominators in q on ALL T rows, never zero (Montgomery 1 on an exceptional row
+// and on the rows >= n).  stats: five runs of n_units words: [u] += the exceptional rows or steps, [n_units + u] += the rows of a
+// check with a cell that differs, on a CHAIN unit the rows with an unknown op-code, [2 n_units + u] += the segments of a CHAIN
+// unit, [3 n_units + u], [4 n_units + u] <- min(., the smallest row of the first and second kind).  Sources are only read and may
+// coincide; out and q must not overlap a source.  Returns without a launch on a table that the caller's checks should have refused
+void launch_edwards(hipStream_t s, const EdwTab& tab, uint64_t T, uint64_t n, uint64_t* stats);
+// behind the inversion of the denominators: out[c T + t] <- out[c T + t] W[wq[c] T + t], canonical, for c < n_out and t < n
+struct EdwFin {
+    uint32_t* out;
+    const uint32_t* W;
+    uint8_t wq[POLY_MAX_ROWS];
+};
+void launch_edwards_finish(hipStream_t s, const EdwFin& fin, uint32_t n_out, uint64_t T, uint64_t n);
 // ---- the expression columns of kzg_rows_commit_expr (fr_expr.hip): v[t] = sum_u c_u prod_f src.r[row[u][f]][(t + rot[u][f]) mod T]
 // for t < n <= T over evaluation vectors of T canonical Montgomery elements (T a power of two, at most 2^32)
 #define EXPR_MAX_TERMS 16

@@ -570,6 +570,19 @@ int kzg_multi_rows_commit_ec(kzg_multi* mh, uint32_t i, uint32_t n_input_handles
                                  out_handle);
     });
 }
+int kzg_multi_rows_commit_edwards(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                  const kzg_edwards_curve* curve, uint32_t n_units, const kzg_edwards_unit* units,
+                                  const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_singular,
+                                  uint64_t* out_first_singular, uint64_t* out_mismatch, uint64_t* out_first_mismatch,
+                                  uint64_t* out_unknown, uint64_t* out_first_unknown, uint64_t* out_segments,
+                                  uint64_t* out_handle) {
+    uint64_t* const st[7] = {out_singular, out_first_singular, out_mismatch, out_first_mismatch,
+                             out_unknown,  out_first_unknown,  out_segments};
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_edwards(c, s, n_input_handles, input_handles, curve, n_units, units, opts, out_commitments48, st,
+                                      out_handle);
+    });
+}
 int kzg_multi_rows_commit_expr(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                uint32_t n_exprs, const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48,
                                uint64_t* out_nonzero, uint64_t* out_first, uint64_t* out_handle) {

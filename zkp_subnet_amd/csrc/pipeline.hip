@@ -1870,6 +1870,115 @@ int rows_ec_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, con
     return KZG_OK;
 }
 
+// The native twisted-Edwards columns (kzg_rows_commit_edwards), in the builders' frame:
+//   step                      launches                         per call
+//   forward transforms        launch_fr_ntt                    one per distinct source row named
+//   every unit, phase 1       launch_edwards (k_edwards)       ONE, grid y = unit: numerators or projective X, Y, and Q
+//   the denominators          launch_fr_batch_inv              ONE, over the (units with output) T elements of Q
+//   finish                    launch_edwards_finish            ONE, grid y = output row: out <- out W
+//   tail                      launch_sort_tail                 one per output row, with `usable` only
+//   inverse transform         row_to_coeffs                    one per output row, straight into dst
+//   commit                    multi_msms_finish                ONE pass of n_out scalar sets
+// The outputs lie side by side behind the sources in the order of the set (unit by unit, then the unit's out order), so output
+// row c is vector c; behind them the denominators Q, one slice of T per unit with output, and the inversion's result W of the
+// same shape.  k_edwards writes every element of Q (Montgomery 1 on an exceptional row and on the rows >= n), so the inversion
+// meets no zero; its flag is read back with the statistics all the same.  The five statistics of every unit are u64 words
+// behind the first two evaluation slots of the record (the inversion's scratch and flag) and come back in the copy behind the
+// MSM.  With n_out = 0 (checks alone) nothing is inverted or transformed back and no MSM runs.
+// Workspace: distinct sources + n_out + 2 (units with output) vectors of T, and the inversion's scan scratch in hbuf and hnext.
+int rows_edwards_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const kzg_edwards_curve* curve,
+                     uint32_t n_units, const kzg_edwards_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48,
+                     uint64_t* out_stats, const Blind* lay) {
+    Lane& A = H.L();
+    Cols F;
+    if (int rc = cols_begin(ctx, A, T, lay, dst, F)) return rc;
+    const uint64_t vw = F.vw, n = F.n;
+    static_assert(40 * KZG_EDWARDS_MAX_UNITS <= STATS_MAX && KZG_EDWARDS_MAX_UNITS == EDW_MAX_UNITS && KZG_EDWARDS_ADD == EDW_ADD &&
+                      KZG_EDWARDS_CHAIN == EDW_CHAIN,
+                  "the five statistics of every unit fit the record's evaluation slots; the header's caps and modes are the "
+                  "kernel's");
+    Sources S;
+    EdwTab tab;
+    EdwFin fin;
+    memset(&tab, 0, sizeof(tab));
+    memset(&fin, 0, sizeof(fin));
+    auto words = [](uint32_t* w, const uint8_t* be32) {   // 8 little-endian words of a 32-byte big-endian integer
+        for (int k = 0; k < 8; k++)
+            w[k] = (uint32_t)be32[31 - 4 * k] | (uint32_t)be32[30 - 4 * k] << 8 | (uint32_t)be32[29 - 4 * k] << 16 |
+                   (uint32_t)be32[28 - 4 * k] << 24;
+    };
+    tab.n_units = n_units;
+    words(tab.a, curve->a_be32);
+    words(tab.d, curve->d_be32);
+    uint32_t n_q = 0, col[EDW_MAX_UNITS][2] = {}, qof[EDW_MAX_UNITS] = {};
+    bool commits[EDW_MAX_UNITS] = {};
+    for (uint32_t u = 0, c = 0; u < n_units; u++) {
+        const kzg_edwards_unit& in = units[u];
+        EdwUnit& U = tab.u[u];
+        U.mode = in.mode;
+        U.cols = in.cols;
+        const uint32_t n_in = in.mode == KZG_EDWARDS_ADD ? 4u : 2u;
+        for (uint32_t w = 0; w < n_in; w++) {
+            if (in.in[w] == KZG_EDWARDS_IMM) {
+                U.slot[w] = EDW_IMM;
+                words(U.imm[w], in.imm_be32[w]);
+            } else {
+                U.slot[w] = (uint8_t)S.slot_of(inputs.r[in.in[w]]);
+            }
+        }
+        if (in.mode == KZG_EDWARDS_CHAIN) U.opv = S.slot_of(inputs.r[in.op]);
+        if (in.flags & KZG_EDWARDS_CHECK) {
+            for (uint32_t k = 0; k < 2; k++)
+                if (in.cols >> k & 1u) U.exp[k] = (uint8_t)S.slot_of(inputs.r[in.expect[k]]);
+            continue;
+        }
+        commits[u] = true;
+        qof[u] = n_q++;
+        for (uint32_t j = 0; j < 2 && in.out_order[j] != KZG_EDWARDS_ABSENT; j++) {
+            fin.wq[c] = (uint8_t)qof[u];
+            col[u][in.out_order[j]] = c++ + 1;   // (0: the name is not an output)
+        }
+    }
+    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_out + 2 * n_q) * T * 32 + 32));
+    if (n_q) {
+        HIPCHK(ctx, A.hbuf.ensure(poly_level_words(n_q * T) * 4));
+        HIPCHK(ctx, A.hnext.ensure(poly_level_words(n_q * T) * 4));
+    }
+    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + S.nd * vw, *Q = outv + n_out * vw, *W = Q + n_q * vw;
+    uint8_t* rec = F.rec;
+    uint64_t* st = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF);
+    sources_transform(ctx, A, F, S, src);
+    HIPCHK(ctx, hipMemsetAsync(rec + MR_EVAL, 0, CNT_OFF + 24 * (size_t)n_units, A.stream));
+    HIPCHK(ctx, hipMemsetAsync(st + 3 * n_units, 0xff, 16 * (size_t)n_units, A.stream));   // KZG_EDWARDS_NONE
+    tab.src = src;
+    for (uint32_t u = 0; u < n_units; u++) {
+        if (!commits[u]) continue;
+        tab.u[u].q = Q + qof[u] * vw;
+        for (uint32_t k = 0; k < 2; k++)
+            if (col[u][k]) tab.u[u].out[k] = outv + (col[u][k] - 1) * vw;
+    }
+    fin.out = outv;
+    fin.W = W;
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_edwards(A.stream, tab, T, n, st);
+        if (n_q) {
+            launch_fr_batch_inv(A.stream, Q, W, nullptr, W, n_q * T, A.hbuf.as<uint32_t>(), A.hnext.as<uint32_t>(), rec + MR_EVAL,
+                                reinterpret_cast<uint32_t*>(rec + MR_EVAL + 32));
+            launch_edwards_finish(A.stream, fin, n_out, T, n);
+        }
+    }
+    for (uint32_t c = 0; c < n_out; c++)
+        if (int rc = emit_column(ctx, A, F, outv + c * vw, c)) return rc;
+    const uint8_t* stats;
+    if (int rc = stats_finish(ctx, H, i, F, n_out, 40 * n_units, out_c48, &stats)) return rc;
+    uint32_t zf;
+    memcpy(&zf, F.ev + 32, 4);
+    if (n_q && zf) return fail(ctx, KZG_E_HIP, "edwards: the batched inversion met a zero behind k_edwards");
+    memcpy(out_stats, stats, 40 * (size_t)n_units);
+    return KZG_OK;
+}
+
 // The expression columns (kzg_rows_commit_expr): a set built FROM sets, every output row plain arithmetic in source rows.
 // Each DISTINCT source row (by device pointer: two indices of a repeated handle name one row) that some term names is
 // transformed forward once into its own vector of the lane's quotient workspace; a row no term names is not transformed.

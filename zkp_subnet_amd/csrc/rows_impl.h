@@ -95,6 +95,10 @@ int rows_keccak(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const
 int rows_ec(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, const kzg_ec_curve* curve,
             uint32_t n_units, const kzg_ec_unit* units, const kzg_derive_opts* opts, uint8_t* out_commitments48,
             uint64_t* const out_stats[9], uint64_t* out_handle);
+// opts: as for rows_derived.  out_stats: the seven statistics arrays of kzg_rows_commit_edwards in the order of its arguments
+int rows_edwards(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                 const kzg_edwards_curve* curve, uint32_t n_units, const kzg_edwards_unit* units, const kzg_derive_opts* opts,
+                 uint8_t* out_commitments48, uint64_t* const out_stats[7], uint64_t* out_handle);
 // opts: the usable layout and its tail as the public call takes them (null: all T rows are evaluated)
 int rows_expr(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
               const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48, uint64_t* out_nonzero,

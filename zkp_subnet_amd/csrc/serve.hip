@@ -1888,6 +1888,106 @@ int rows_ec(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uin
     return KZG_OK;
 }
 
+// kzg_rows_commit_edwards: a BuilderCall around its own checks; as in rows_ec, no reservation and no set when every unit is a
+// check.  The curve, the immediates, modes, flags, names, out orders and the entries a mode does not take are checked here, on
+// the host, before a lane is taken
+int rows_edwards(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                 const kzg_edwards_curve* curve, uint32_t n_units, const kzg_edwards_unit* units, const kzg_derive_opts* opts,
+                 uint8_t* out_commitments48, uint64_t* const out_stats[7], uint64_t* out_handle) {
+    if (!ctx || !input_handles || !out_stats || !out_handle) return KZG_E_ARG;
+    for (int k = 0; k < 7; k++)
+        if (!out_stats[k]) return KZG_E_ARG;
+    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "edwards: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (n_units == 0 || n_units > KZG_EDWARDS_MAX_UNITS || !units)
+        return fail(ctx, KZG_E_ARG, "edwards: n_units must be in [1, KZG_EDWARDS_MAX_UNITS]");
+    if (!curve) return fail(ctx, KZG_E_ARG, "edwards: the curve must be given");
+    static const uint8_t zero32[32] = {0};
+    if (!fr_be32_canonical(curve->a_be32) || !fr_be32_canonical(curve->d_be32))
+        return fail(ctx, KZG_E_ARG, "edwards: the coefficients A and D must be canonical scalars (< r)");
+    if (!memcmp(curve->a_be32, zero32, 32) || !memcmp(curve->d_be32, zero32, 32))
+        return fail(ctx, KZG_E_ARG, "edwards: the coefficients A and D must not be 0");
+    if (!memcmp(curve->a_be32, curve->d_be32, 32)) return fail(ctx, KZG_E_ARG, "edwards: the coefficients A and D must differ");
+    uint32_t n_out = 0, max_row = 0, n_seen = 0, seen[7 * KZG_EDWARDS_MAX_UNITS];
+    auto see = [&](uint32_t row) {
+        max_row = std::max(max_row, row);
+        uint32_t d = 0;
+        while (d < n_seen && seen[d] != row) d++;
+        if (d == n_seen) seen[n_seen++] = row;
+    };
+    for (uint32_t u = 0; u < n_units; u++) {
+        const kzg_edwards_unit& U = units[u];
+        if (U.mode != KZG_EDWARDS_ADD && U.mode != KZG_EDWARDS_CHAIN)
+            return fail(ctx, KZG_E_ARG, "edwards: unknown mode (KZG_EDWARDS_ADD or KZG_EDWARDS_CHAIN)");
+        if (U.flags & ~KZG_EDWARDS_CHECK) return fail(ctx, KZG_E_ARG, "edwards: flags must be 0 or KZG_EDWARDS_CHECK");
+        const bool check = U.flags & KZG_EDWARDS_CHECK, chain = U.mode == KZG_EDWARDS_CHAIN;
+        if (check && chain) return fail(ctx, KZG_E_ARG, "edwards: expect (KZG_EDWARDS_CHECK) belongs to ADD units, not to CHAIN");
+        if (!U.cols || (U.cols & ~3u))
+            return fail(ctx, KZG_E_ARG, "edwards: cols must name at least one column, and only columns of the unit's mode");
+        const uint32_t n_in = chain ? 2u : 4u;
+        for (uint32_t w = 0; w < 4; w++) {
+            const bool takes = w < n_in, imm = U.in[w] == KZG_EDWARDS_IMM;
+            if (takes != (U.in[w] != KZG_EDWARDS_ABSENT))
+                return fail(ctx, KZG_E_ARG, "edwards: an operand the mode does not take, or a missing one (KZG_EDWARDS_ABSENT beside the mode's operands)");
+            if (takes && imm) {
+                if (!fr_be32_canonical(U.imm_be32[w])) return fail(ctx, KZG_E_ARG, "edwards: immediates must be canonical scalars (< r)");
+            } else {
+                if (memcmp(U.imm_be32[w], zero32, 32)) return fail(ctx, KZG_E_ARG, "edwards: the immediate must be 0 beside a row");
+                if (takes) see(U.in[w]);
+            }
+        }
+        if (chain != (U.op != KZG_EDWARDS_ABSENT))
+            return fail(ctx, KZG_E_ARG, "edwards: op belongs to CHAIN units, and a CHAIN unit must have one (KZG_EDWARDS_ABSENT elsewhere)");
+        if (chain) {
+            if (U.op == KZG_EDWARDS_IMM) return fail(ctx, KZG_E_ARG, "edwards: op must be a row, not an immediate");
+            see(U.op);
+        }
+        uint32_t ordered = 0;
+        for (uint32_t k = 0; k < 2; k++) {
+            const bool takes = check && (U.cols >> k & 1u);
+            if (takes != (U.expect[k] != KZG_EDWARDS_ABSENT) || U.expect[k] == KZG_EDWARDS_IMM)
+                return fail(ctx, KZG_E_ARG, "edwards: expect must hold one row per name of cols under KZG_EDWARDS_CHECK, KZG_EDWARDS_ABSENT elsewhere");
+            if (takes) see(U.expect[k]);
+            const uint32_t o = U.out_order[k];
+            if (o == KZG_EDWARDS_ABSENT) continue;
+            if (check || o > 1 || (ordered >> o & 1u) || (k == 1 && U.out_order[0] == KZG_EDWARDS_ABSENT))
+                return fail(ctx, KZG_E_ARG, "edwards: out_order must list the names of cols once each (KZG_EDWARDS_ABSENT beyond, and in a check)");
+            ordered |= 1u << o;
+        }
+        if (!check && ordered != U.cols)
+            return fail(ctx, KZG_E_ARG, "edwards: out_order must list the names of cols once each (KZG_EDWARDS_ABSENT beyond, and in a check)");
+        if (n_seen > KZG_MAX_BATCH_OPEN)
+            return fail(ctx, KZG_E_ARG, "edwards: a call reads at most KZG_MAX_BATCH_OPEN distinct input rows");
+        n_out += check ? 0 : (uint32_t)__builtin_popcount(U.cols);
+    }
+    if (n_out > KZG_MAX_BATCH_OPEN)
+        return fail(ctx, KZG_E_ARG, "edwards: n_out, the committed rows of all units, must be at most KZG_MAX_BATCH_OPEN");
+    if (n_out && !out_commitments48) return KZG_E_ARG;
+    BuilderCall C(ctx, "edwards");
+    RowTab it;
+    uint32_t ki = 0;
+    if (int rc = C.begin("edwards", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
+    if (n_seen && max_row >= ki) return fail(ctx, KZG_E_ARG, "edwards: a row must index the concatenated rows of the input sets");
+    if (int rc = C.ready(n_out, 32, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ)) return rc;
+    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    uint64_t stats[5 * KZG_EDWARDS_MAX_UNITS];
+    if (int rc = rows_edwards_dev(ctx, C.H, C.i, it, curve, n_units, units, n_out, C.T, C.dst(), c48, stats, C.blind)) return rc;
+    if (n_out) memcpy(out_commitments48, c48, 48 * (size_t)n_out);
+    // the device's runs: singular, mismatch or unknown, segments, first_singular, first of the second
+    for (uint32_t u = 0; u < n_units; u++) {
+        const bool chain = units[u].mode == KZG_EDWARDS_CHAIN;
+        out_stats[0][u] = stats[u];
+        out_stats[1][u] = stats[3 * n_units + u];
+        out_stats[2][u] = chain ? 0 : stats[n_units + u];
+        out_stats[3][u] = chain ? KZG_EDWARDS_NONE : stats[4 * n_units + u];
+        out_stats[4][u] = chain ? stats[n_units + u] : 0;
+        out_stats[5][u] = chain ? stats[4 * n_units + u] : KZG_EDWARDS_NONE;
+        out_stats[6][u] = stats[2 * n_units + u];
+    }
+    *out_handle = C.commit();
+    return KZG_OK;
+}
+
 // The terms of an expression as rows_expr_dev takes them: a kzg_quotient_terms checked (counts, lengths, canonical
 // coefficients) and copied into the zeroed plan `pl`, its rotations as given into `rots` -- they are reduced by expr_reduce once
 // T is known -- and the largest row it names into *max_row.  may_be_empty: n_terms = 0 is accepted and leaves pl empty
@@ -2857,6 +2957,16 @@ int kzg_rows_commit_ec(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* i
     uint64_t* const st[9] = {out_counts,         out_first,   out_singular,      out_first_singular, out_mismatch,
                              out_first_mismatch, out_unknown, out_first_unknown, out_segments};
     return rows_ec(ctx, UINT32_MAX, n_input_handles, input_handles, curve, n_units, units, opts, out_commitments48, st, out_handle);
+}
+int kzg_rows_commit_edwards(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, const kzg_edwards_curve* curve,
+                            uint32_t n_units, const kzg_edwards_unit* units, const kzg_derive_opts* opts,
+                            uint8_t* out_commitments48, uint64_t* out_singular, uint64_t* out_first_singular,
+                            uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_unknown,
+                            uint64_t* out_first_unknown, uint64_t* out_segments, uint64_t* out_handle) {
+    uint64_t* const st[7] = {out_singular, out_first_singular, out_mismatch, out_first_mismatch,
+                             out_unknown,  out_first_unknown,  out_segments};
+    return rows_edwards(ctx, UINT32_MAX, n_input_handles, input_handles, curve, n_units, units, opts, out_commitments48, st,
+                        out_handle);
 }
 int kzg_rows_commit_expr(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
                          const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48, uint64_t* out_nonzero,

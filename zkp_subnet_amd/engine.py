@@ -1868,6 +1868,180 @@ class HipEngine:
                     "mismatch": ints(st[4]), "first_mismatch": none(st[5]), "unknown": ints(st[6]), "first_unknown": none(st[7]),
                     "segments": ints(st[8])}
 
+    # ---- a set built from sets: arithmetic of a twisted Edwards curve over the scalar field itself: point addition, chains
+    _EDWARDS_CURVE_KEYS = ("a", "d")
+    _EDWARDS_KEYS = {"add": ("mode", "x1", "y1", "x2", "y2", "out", "expect"), "chain": ("mode", "px", "py", "op", "cols")}
+    _EDWARDS_MODES = {"add": _native.KZG_EDWARDS_ADD, "chain": _native.KZG_EDWARDS_CHAIN}
+
+    @classmethod
+    def edwards_call(cls, curve, units, what: str = "commit_edwards", n_rows: Optional[int] = None) -> Tuple[tuple, List[tuple]]:
+        """The kzg_edwards_curve fields (a, d as 32 big-endian bytes) and per unit the kzg_edwards_unit fields (mode, flags,
+        cols, op, in[4], expect[2], out_order[2], imm[4] of 32 bytes) of a call.  curve: a mapping with a and d, the
+        coefficients of A x^2 + y^2 = 1 + D x^2 y^2: canonical scalars, not 0, not equal.  A unit is a mapping.  {"mode": "add",
+        "x1", "y1", "x2", "y2": slots, "out": names among x3, y3}, the output rows in the order of the names; with "expect":
+        [row or None, row or None] (for x3, y3) in place of out it is a check.  {"mode": "chain", "px", "py": slots, "op": row,
+        "cols": names among ax, ay}.  A slot is a row index or ("imm", value).  A scalar is an int, a decimal or 0x string, or
+        32 big-endian bytes, below r.  n_rows: the number of concatenated input rows, where known: a row must lie inside.
+        Raises KzgError(KZG_E_ARG) with the cause; needs no device."""
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: edwards: {why}")   # noqa: E731
+        is_u = lambda v, top: isinstance(v, int) and not isinstance(v, bool) and 0 <= v < top   # noqa: E731
+        ABSENT, IMM = _native.KZG_EDWARDS_ABSENT, _native.KZG_EDWARDS_IMM
+        r_mod = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
+
+        def scalar(v, name):
+            if isinstance(v, (bytes, bytearray)):
+                if len(v) != 32:
+                    raise bad(f"{name} given as bytes must be of 32 bytes")
+                v = int.from_bytes(v, "big")
+            elif isinstance(v, str):
+                try:
+                    v = int(v, 0)
+                except ValueError:
+                    raise bad(f"{name} must be an integer, a decimal or 0x string, or 32 bytes") from None
+            if not isinstance(v, int) or isinstance(v, bool) or v < 0:
+                raise bad(f"{name} must be a non-negative integer")
+            if v >= r_mod:
+                raise bad(f"{name} must be a canonical scalar (< r)")
+            return v.to_bytes(32, "big")
+
+        if not isinstance(curve, dict) or set(curve) != set(cls._EDWARDS_CURVE_KEYS):
+            raise bad("the curve is a mapping with exactly a and d")
+        a_b, d_b = scalar(curve["a"], "the coefficient A"), scalar(curve["d"], "the coefficient D")
+        if a_b == bytes(32) or d_b == bytes(32):
+            raise bad("the coefficients A and D must not be 0")
+        if a_b == d_b:
+            raise bad("the coefficients A and D must differ")
+        units = list(units) if isinstance(units, (list, tuple)) else None
+        if not units or len(units) > _native.KZG_EDWARDS_MAX_UNITS:
+            raise bad(f"units must be a list of 1 .. {_native.KZG_EDWARDS_MAX_UNITS} entries (n_units)")
+        seen, recs, n_out = set(), [], 0
+
+        def row(v, name):
+            if not is_u(v, IMM):
+                raise bad(f"{name} must be a row, an integer in [0, 2^32 - 2)")
+            if n_rows is not None and v >= n_rows:
+                raise bad(f"{name} reaches beyond the {n_rows} concatenated rows of the input sets")
+            seen.add(v)
+            return v
+
+        def slot(v, name):
+            if isinstance(v, (list, tuple)):
+                if len(v) != 2 or v[0] != "imm":
+                    raise bad('an immediate is ("imm", value)')
+                return IMM, scalar(v[1], "an immediate")
+            if v is None or isinstance(v, bool) or not isinstance(v, int):
+                raise bad(f'{name} must be a row index, an integer in [0, 2^32 - 2), or ("imm", value)')
+            return row(v, name), bytes(32)
+
+        for un in units:
+            if not isinstance(un, dict) or "mode" not in un:
+                raise bad("a unit is a mapping with mode and the fields of its mode")
+            mode = un["mode"]
+            if not isinstance(mode, str) or mode not in cls._EDWARDS_MODES:
+                raise bad(f'unknown mode {mode!r} (one of "add", "chain")')
+            keys = cls._EDWARDS_KEYS[mode]
+            extra = set(un) - set(keys)
+            if extra:
+                if mode == "chain" and "expect" in extra:
+                    raise bad("expect belongs to add units, not to chain: a chain is never a check")
+                raise bad(f"unknown field {sorted(extra)[0]!r} (the fields of a {mode} unit are {', '.join(keys)})")
+            flags, op, ins, imms, expect = 0, ABSENT, [ABSENT] * 4, [bytes(32)] * 4, [ABSENT] * 2
+            if mode == "chain":
+                names = _native.KZG_EDWARDS_CHAIN_NAMES
+                for j, k in enumerate(("px", "py")):
+                    ins[j], imms[j] = slot(un.get(k), k)
+                op = row(un.get("op"), "op")
+                picked = un.get("cols")
+                if not isinstance(picked, (list, tuple)) or not picked:
+                    raise bad(f"cols must hold 1 .. 2 column names among {', '.join(names)}")
+            else:
+                names = _native.KZG_EDWARDS_ADD_NAMES
+                for j, k in enumerate(("x1", "y1", "x2", "y2")):
+                    ins[j], imms[j] = slot(un.get(k), k)
+                has_out, has_exp = un.get("out") is not None, un.get("expect") is not None
+                if has_out and has_exp:
+                    raise bad("out together with expect: a unit commits, or it is a check")
+                if not has_out and not has_exp:
+                    raise bad("a unit needs out, or expect for a check")
+                if has_exp:
+                    ex = un["expect"]
+                    if not isinstance(ex, (list, tuple)) or len(ex) != 2:
+                        raise bad("expect must hold two entries (x3, y3; None: not compared)")
+                    picked = [k for k, v in zip(names, ex) if v is not None]
+                    if not picked:
+                        raise bad("expect must name at least one row")
+                    for j, v in enumerate(ex):
+                        if v is not None:
+                            expect[j] = row(v, "an entry of expect")
+                    flags |= _native.KZG_EDWARDS_CHECK
+                else:
+                    picked = un["out"]
+                    if not isinstance(picked, (list, tuple)) or not picked:
+                        raise bad(f"out must hold 1 .. 2 names among {', '.join(names)}")
+            for name in picked:
+                if name not in names:
+                    raise bad(f"unknown name {name!r} (the names of a {mode} unit are {', '.join(names)})")
+            if len(set(picked)) != len(picked):
+                raise bad("a name is repeated")
+            cols, order = 0, [ABSENT] * 2
+            for j, name in enumerate(picked):
+                cols |= 1 << names.index(name)
+                if not flags:
+                    order[j] = names.index(name)
+            if not flags:
+                n_out += len(picked)
+            recs.append((cls._EDWARDS_MODES[mode], flags, cols, op, ins, expect, order, imms))
+        if len(seen) > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"the units read {len(seen)} distinct input rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+        if n_out > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"n_out: the units give {n_out} output rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+        return (a_b, d_b), recs
+
+    @staticmethod
+    def edwards_structs(cv, recs) -> Tuple["_native.EdwardsCurve", object]:
+        curve = _native.EdwardsCurve((ctypes.c_uint8 * 32)(*cv[0]), (ctypes.c_uint8 * 32)(*cv[1]))
+        arr = (_native.EdwardsUnit * len(recs))()
+        for u, r in zip(arr, recs):
+            u.mode, u.flags, u.cols, u.op = r[0], r[1], r[2], r[3]
+            u.in_[:], u.expect[:], u.out_order[:] = r[4], r[5], r[6]
+            for j, b in enumerate(r[7]):
+                u.imm_be32[j][:] = list(b)
+        return curve, arr
+
+    @staticmethod
+    def edwards_n_out(recs) -> int:
+        return sum(bin(r[2]).count("1") for r in recs if not r[1] & _native.KZG_EDWARDS_CHECK)
+
+    def commit_edwards(self, input_sets: Sequence[object], curve: dict, units: Sequence[dict], usable: Optional[int] = None,
+                       tail: Sequence[bytes] = ()) -> Tuple[Optional["RowSet"], dict]:
+        """kzg_rows_commit_edwards over the concatenated rows of input_sets (RowSet objects or bare handles).  curve and units:
+        see edwards_call.  A coordinate is one cell.  With tau = D x1 x2 y1 y2 an add unit commits the named ones of x3 = (x1
+        y2 + y1 x2) / (1 + tau) and y3 = (y1 y2 - A x1 x2) / (1 - tau), zeros and `singular` on an exceptional row (tau = 1 or
+        -1); with expect it commits nothing and counts the rows whose expected cells differ; a chain unit commits the named ones
+        of ax, ay: the accumulator before each row's step, (0, 1) before row 0 and after an exceptional step, for the op-codes 0
+        hold, 1 load, 2 add (px, py), 3 double, 4 subtract (px, py).  Returns (the new RowSet of all committed rows in unit
+        order, or None when every unit is a check; {"singular", "first_singular", "mismatch", "first_mismatch", "unknown",
+        "first_unknown", "segments"} per unit).  usable and tail: as for commit_derived, the tail column-major over the
+        committed rows."""
+        what = "commit_edwards"
+        ni, hi = self._handle_array(input_sets, what)
+        ks = [getattr(x, "k", None) for x in input_sets]
+        cv, recs = self.edwards_call(curve, units, what, None if any(k is None for k in ks) else sum(ks))
+        n_out = self.edwards_n_out(recs)
+        wi, T, lay = self._column_layout(what, input_sets, n_out, "n_out", "read", usable, tail)
+        opts = _native.DeriveOpts(*lay) if lay else None
+        cs, arr = self.edwards_structs(cv, recs)
+        c, h = ctypes.create_string_buffer(48 * max(n_out, 1)), ctypes.c_uint64(0)
+        st = [(ctypes.c_uint64 * len(recs))() for _ in range(7)]
+        self._chk(self._lib.kzg_rows_commit_edwards(self._h, ni, hi, ctypes.byref(cs), len(recs), arr,
+                                                    ctypes.byref(opts) if opts is not None else None, c if n_out else None, *st,
+                                                    ctypes.byref(h)))
+        rs = RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]) if n_out else None
+        none = lambda xs: [None if int(v) == _native.KZG_EDWARDS_NONE else int(v) for v in xs]   # noqa: E731
+        ints = lambda xs: [int(v) for v in xs]   # noqa: E731
+        return rs, {"singular": ints(st[0]), "first_singular": none(st[1]), "mismatch": ints(st[2]), "first_mismatch": none(st[3]),
+                    "unknown": ints(st[4]), "first_unknown": none(st[5]), "segments": ints(st[6])}
+
     # ---- a set built from sets: columns that are plain arithmetic in resident columns, and gates checked row by row
     def commit_expr(self, input_sets: Sequence[object], exprs: Sequence[Sequence], usable: Optional[int] = None,
                     tail: Sequence[bytes] = ()) -> Tuple[Optional["RowSet"], List[int], List[Optional[int]]]:

@@ -257,6 +257,12 @@ class MultiDeviceClient:
             self._row_owner[int(r.json()["handle"])] = self._owner(list(input_handles))
         return r
 
+    def worker_commit_edwards(self, input_handles: Sequence[int], curve, units, usable=None, tail=()):
+        r = self._routed_builder("worker_commit_edwards", [input_handles], input_handles, curve, units, usable, tail, key=None)
+        if r.status_code == 200 and r.json()["handle"] is not None:   # (a call of checks alone makes no set)
+            self._row_owner[int(r.json()["handle"])] = self._owner(list(input_handles))
+        return r
+
     def worker_commit_expr(self, input_handles: Sequence[int], exprs, usable=None, tail=()):
         r = self._routed_builder("worker_commit_expr", [input_handles], input_handles, exprs, usable, tail, key=None)
         if r.status_code == 200 and r.json()["handle"] is not None:   # (a call of checks alone makes no set)
