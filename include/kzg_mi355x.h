@@ -1304,6 +1304,7 @@ int kzg_rows_commit_wide(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t*
  * OUT OF SCOPE: generating constants (the Grain LFSR); other exponents and the inverse S-box; the optimised partial-round form
  * (sparse matrices, pre-folded constants); sponge chaining of one block's output into the next block's input, which is
  * sequential along the column (a Merkle path is a ROW unit, a kzg_rows_commit_fetch and another ROW unit); Poseidon2.
+ * (Sponge chaining and Merkle paths along the column have their own call, kzg_rows_commit_poseidon_chain, below.)
  * SOUNDNESS: nothing here is a proof.  The columns are prover data; the argument is the caller's round gate over the trace
  * columns, in the quotient, under the caller's fixed rc and selector columns.  A zero mismatch count convinces no verifier. */
 #define KZG_POSEIDON_ROW    1
@@ -1336,6 +1337,90 @@ int kzg_rows_commit_poseidon(kzg_ctx* ctx, uint32_t n_input_handles, const uint6
                              const kzg_derive_opts* opts /* NULL: plain */, uint8_t* out_commitments48 /* n_out * 48 */,
                              uint64_t* out_perms /* n_units */, uint64_t* out_mismatch /* n_units */,
                              uint64_t* out_first_mismatch /* n_units */, uint64_t* out_handle);
+/* THE POSEIDON SPONGE AND MERKLE-PATH CHAINS: a set built FROM sets, the two uses of the hash chip that kzg_rows_commit_poseidon
+ * leaves out because one block's input depends on the block before through the permutation: a sponge over a message longer than
+ * the rate, and a Merkle path.  params is kzg_poseidon_params exactly as kzg_rows_commit_poseidon reads and checks it (t in
+ * [2, 8], R_F even, R_P <= 128, the caller's rc and M, S-box x^5, the plain Hades schedule; NO constants are generated).  The
+ * concatenated rows of the input_handles sets are the source columns.  A call has 1 <= n_units <= KZG_POSEIDON_CHAIN_MAX_UNITS
+ * units that share params.  A SLOT is a source row, or KZG_POSEIDON_IMM: then the value is the slot's imm_be32 on every row,
+ * canonical; imm_be32 is all zero beside a row.  With n = opts->usable, or T in the plain layout, every unit is a CHAIN OVER
+ * BLOCKS of P = period rows: block b = 0 .. floor(n / P) - 1 occupies rows [b P, b P + P); a block cut by n is not started and
+ * its rows are 0.  Block b STARTS A SEGMENT when b = 0, when start is KZG_POSEIDON_CHAIN_ABSENT, or when the start cell at row
+ * b P is not zero; otherwise it CONTINUES block b - 1, whose output is out_prev.
+ *   KZG_POSEIDON_CHAIN_SPONGE  in[j], j < t, is the slot of state element j.  A starting block's state is (in_0[b P], ..,
+ *                              in_{t-1}[b P]), as a ROUNDS unit reads it.  A continuing block's state is state_j = out_prev_j +
+ *                              in_j[b P] mod r where in[j] is a row and state_j = out_prev_j where it is an immediate: a tag or
+ *                              capacity immediate enters once per message; a continuing block whose rows hold zeros squeezes.
+ *                              With start absent the unit IS kzg_rows_commit_poseidon's ROUNDS unit, byte for byte
+ *   KZG_POSEIDON_CHAIN_PATH    t >= 3, the arity is a = t - 1.  in[0] is the slot `cap` of state element 0, in[1] the slot `leaf`,
+ *                              in[2 + k], k < t - 2, the ROW of sibling k.  State elements 1 .. a are the children: the child at
+ *                              position p is cur, the other a - 1 children are the sibling cells of row b P in their order; p is
+ *                              the cell of row `pos` at row b P read as a WHOLE canonical integer: a cell at or above a is
+ *                              position 0 and is counted once per block in out_bad_pos[u], the smallest such row in
+ *                              out_first_bad_pos[u] (2^32 + 1 is bad, not position 1); cur is the leaf cell on a starting block
+ *                              and out_prev[digest] on a continuing one.  cap, leaf, the siblings and pos are read at the rows
+ *                              b P only
+ * layout (a unit that commits): KZG_POSEIDON_CHAIN_TRACE needs P >= R + 1 and commits t columns laid out as a ROUNDS unit lays
+ * them out (n_out = t, out[j] = j): row b P + rho holds the state before round rho (row b P the arranged state), row b P + R the
+ * output.  KZG_POSEIDON_CHAIN_FLAT takes any P >= 1 and commits the 1 <= n_out <= 2 t distinct columns out[c] names:
+ * KZG_POSEIDON_CHAIN_COL_IN + j is element j of the arranged state, KZG_POSEIDON_CHAIN_COL_OUT + j element j of the output, both at
+ * row b P only; flat with P = 1 is the one-row-per-level Merkle chip that looks its hashes up in a Poseidon table.  Rows of a
+ * block that hold nothing are 0.  With the flag KZG_POSEIDON_CHAIN_CHECK (either mode; layout = 0, n_out = 0) the unit commits
+ * NOTHING: at the LAST block of each segment out[digest] is compared with the cell of row `expect` at that block's first row --
+ * does every path reach its root, is every message's hash the claimed one -- out_mismatch[u] counts the segments that differ and
+ * out_first_mismatch[u] is the smallest such row, or KZG_POSEIDON_NONE.  digest < t is needed by a PATH unit and by a check and
+ * is KZG_POSEIDON_CHAIN_ABSENT elsewhere.  out_blocks[u] = floor(n / P), out_segments[u] the blocks that started a segment.
+ * All committed columns of a call form ONE new set of the same worker and length, in unit order: out_commitments48[c] equals
+ * kzg_rows_commit(i, n_out, these rows, T, 1, ..)[c] byte for byte.  A call of checks alone creates no set (*out_handle = 0,
+ * out_commitments48 may be null), reserves nothing and runs no inverse transform and no MSM.  A call reads at most
+ * KZG_MAX_BATCH_OPEN distinct rows and commits at most KZG_MAX_BATCH_OPEN.  opts: as for kzg_rows_commit_poseidon, NO closing
+ * row.  ONE kernel launch computes every unit, one lane per block; the lane of a segment's first block walks the segment.  A
+ * SEGMENT IS SERIAL: it costs its length times one permutation's latency (at t = 3, (8, 57): 0.5 ms measured on one long
+ * segment, 1.5 to 1.9 ms in calls of many short ones) whatever the number of segments up to the device's lanes, so
+ * a depth-32 path is some 50 ms and ONE message over a whole 2^20-row column at P = 128 took 4.5 s: correct, and slow,
+ * like the chains of kzg_rows_commit_sha256 and kzg_rows_commit_keccak.
+ * KZG_E_ARG with a message that begins "poseidon_chain: " and names the cause: everything kzg_rows_commit_poseidon refuses about
+ * params; n_units outside [1, 4]; an unknown mode, flag or layout; a field the mode does not take (pos on a SPONGE); t = 2 with
+ * PATH; an immediate among the siblings, pos, start or expect; digest at or above t, missing where needed, given where not; a
+ * TRACE period at or below R, a period of 0; an unknown or repeated column id, n_out = 0 on a FLAT unit; layout or n_out beside
+ * KZG_POSEIDON_CHAIN_CHECK; a 17th distinct input row; more than 16 output rows; a row index beyond the concatenation; an
+ * immediate at or above r or not zero beside a row; the usable and tail refusals of kzg_rows_commit_derived; the handle refusals
+ * of kzg_rows_open.  All but the last four are checked on the host before a lane is taken.
+ * OUT OF SCOPE: t cooperating lanes per segment (the follow-up already listed for traces); t above 8, arity-8 trees included;
+ * Poseidon2; padding and domain-tag conventions (immediates and the message cells are the caller's); building whole trees level
+ * by level (ROW units of kzg_rows_commit_poseidon plus kzg_rows_commit_fetch); a carry across calls.
+ * SOUNDNESS: nothing here is a proof.  The columns are prover data; the argument is the caller's gates. */
+#define KZG_POSEIDON_CHAIN_SPONGE 1
+#define KZG_POSEIDON_CHAIN_PATH   2
+#define KZG_POSEIDON_CHAIN_CHECK  1u               /* flags: compare the digest of every segment with expect, commit nothing */
+#define KZG_POSEIDON_CHAIN_TRACE  1
+#define KZG_POSEIDON_CHAIN_FLAT   2
+#define KZG_POSEIDON_CHAIN_ABSENT 0xffffffffu      /* start, pos, digest, expect: none */
+#define KZG_POSEIDON_CHAIN_COL_IN  0               /* out[c] (FLAT): + j: element j of the arranged state */
+#define KZG_POSEIDON_CHAIN_COL_OUT 8               /* out[c] (FLAT): + j: element j of the block's output */
+#define KZG_POSEIDON_CHAIN_MAX_UNITS 4
+typedef struct kzg_poseidon_chain_unit {
+    uint32_t mode;               /* KZG_POSEIDON_CHAIN_SPONGE or KZG_POSEIDON_CHAIN_PATH */
+    uint32_t flags;              /* 0 or KZG_POSEIDON_CHAIN_CHECK */
+    uint32_t layout;             /* KZG_POSEIDON_CHAIN_TRACE or KZG_POSEIDON_CHAIN_FLAT; 0 with KZG_POSEIDON_CHAIN_CHECK */
+    uint32_t period;             /* P >= 1; TRACE: P >= R + 1 */
+    uint32_t start;              /* the row of the start column, or KZG_POSEIDON_CHAIN_ABSENT: every block starts a segment */
+    uint32_t pos;                /* PATH: the row of the position column; SPONGE: KZG_POSEIDON_CHAIN_ABSENT */
+    uint32_t digest;             /* PATH, CHECK: a state index below t; else KZG_POSEIDON_CHAIN_ABSENT */
+    uint32_t expect;             /* CHECK: the row the digest is compared with; else KZG_POSEIDON_CHAIN_ABSENT */
+    uint32_t n_out;              /* TRACE: t; FLAT: 1 .. 2 t; CHECK: 0 */
+    uint32_t reserved;           /* 0 */
+    uint32_t in[KZG_POSEIDON_MAX_T];        /* SPONGE: [j < t] the slot of element j; PATH: cap, leaf, then t - 2 sibling rows */
+    uint32_t out[2 * KZG_POSEIDON_MAX_T];   /* [c < n_out] TRACE: c; FLAT: a column id KZG_POSEIDON_CHAIN_COL_IN / _OUT + j, j < t */
+    uint8_t imm_be32[KZG_POSEIDON_MAX_T][32];   /* [j] the value where in[j] = KZG_POSEIDON_IMM; all zero beside a row */
+} kzg_poseidon_chain_unit;
+int kzg_rows_commit_poseidon_chain(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                                   const kzg_poseidon_params* params, uint32_t n_units, const kzg_poseidon_chain_unit* units,
+                                   const kzg_derive_opts* opts /* NULL: plain */, uint8_t* out_commitments48 /* n_out * 48 */,
+                                   uint64_t* out_blocks /* n_units */, uint64_t* out_segments /* n_units */,
+                                   uint64_t* out_bad_pos /* n_units */, uint64_t* out_first_bad_pos /* n_units */,
+                                   uint64_t* out_mismatch /* n_units */, uint64_t* out_first_mismatch /* n_units */,
+                                   uint64_t* out_handle);
 /* THE SHA-256 COMPRESSION COLUMNS: a set built FROM sets, the columns of the bit-oriented hash chip -- Merkle nodes over 32-byte
  * digests, Bitcoin and Ethereum precompile traces, beacon-chain roots.  A round is no polynomial expression (kzg_rows_commit_expr)
  * and depends non-linearly on the four rows before it (kzg_rows_commit_recurrence); composed from kzg_rows_commit_alu it takes
@@ -2119,6 +2204,13 @@ int kzg_multi_rows_commit_wide(kzg_multi* mh, uint32_t i, uint32_t n_input_handl
                                const kzg_wide_op* ops, const kzg_derive_opts* opts, uint8_t* out_commitments48,
                                uint64_t* out_counts, uint64_t* out_first, uint64_t* out_qover, uint64_t* out_first_qover,
                                uint64_t* out_handle);
+/* kzg_rows_commit_poseidon_chain on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_poseidon_chain(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                         const kzg_poseidon_params* params, uint32_t n_units,
+                                         const kzg_poseidon_chain_unit* units, const kzg_derive_opts* opts,
+                                         uint8_t* out_commitments48, uint64_t* out_blocks, uint64_t* out_segments,
+                                         uint64_t* out_bad_pos, uint64_t* out_first_bad_pos, uint64_t* out_mismatch,
+                                         uint64_t* out_first_mismatch, uint64_t* out_handle);
 /* kzg_rows_commit_poseidon on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
 int kzg_multi_rows_commit_poseidon(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                    const kzg_poseidon_params* params, uint32_t n_units, const kzg_poseidon_unit* units,

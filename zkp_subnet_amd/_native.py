@@ -49,6 +49,14 @@ KZG_POSEIDON_IMM = 0xffffffff
 KZG_POSEIDON_NONE = 0xffffffffffffffff
 KZG_POSEIDON_MIN_T, KZG_POSEIDON_MAX_T = 2, 8
 KZG_POSEIDON_MAX_FULL, KZG_POSEIDON_MAX_PARTIAL, KZG_POSEIDON_MAX_UNITS = 16, 128, 8
+# kzg_rows_commit_poseidon_chain: kzg_poseidon_chain_unit.mode, the flag, the layouts, "no such entry", the column ids of a flat
+# unit (in_j, out_j), the limit; immediates and "none" are KZG_POSEIDON_IMM and KZG_POSEIDON_NONE
+KZG_POSEIDON_CHAIN_SPONGE, KZG_POSEIDON_CHAIN_PATH = 1, 2
+KZG_POSEIDON_CHAIN_CHECK = 1
+KZG_POSEIDON_CHAIN_TRACE, KZG_POSEIDON_CHAIN_FLAT = 1, 2
+KZG_POSEIDON_CHAIN_ABSENT = 0xffffffff
+KZG_POSEIDON_CHAIN_COL_IN, KZG_POSEIDON_CHAIN_COL_OUT = 0, 8
+KZG_POSEIDON_CHAIN_MAX_UNITS = 4
 # kzg_rows_commit_sha256: kzg_sha256_unit.mode, the flags, a slot that holds an immediate, "no start column", "none", the limits,
 # and the column ids of a rounds unit in the order of KZG_SHA256_COL_W .. KZG_SHA256_COL_CH
 KZG_SHA256_ROW, KZG_SHA256_ROUNDS = 1, 2
@@ -195,6 +203,13 @@ class PoseidonUnit(ctypes.Structure):
                 ("expect", _U32 * 8), ("imm_be32", (ctypes.c_uint8 * 32) * 8)]
 
 
+class PoseidonChainUnit(ctypes.Structure):
+    """kzg_poseidon_chain_unit"""
+    _fields_ = [("mode", _U32), ("flags", _U32), ("layout", _U32), ("period", _U32), ("start", _U32), ("pos", _U32),
+                ("digest", _U32), ("expect", _U32), ("n_out", _U32), ("reserved", _U32), ("in_", _U32 * 8), ("out", _U32 * 16),
+                ("imm_be32", (ctypes.c_uint8 * 32) * 8)]
+
+
 class Sha256Unit(ctypes.Structure):
     """kzg_sha256_unit"""
     _fields_ = [("mode", _U32), ("flags", _U32), ("n_out", _U32), ("period", _U32), ("start", _U32), ("state", _U32 * 8),
@@ -316,6 +331,9 @@ SYMBOLS = {
     "kzg_rows_commit_poseidon": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(PoseidonParams), _U32,
                                       ctypes.POINTER(PoseidonUnit), ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64),
                                       ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_poseidon_chain": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(PoseidonParams), _U32,
+                                            ctypes.POINTER(PoseidonChainUnit), ctypes.POINTER(DeriveOpts), _B]
+                                       + [ctypes.POINTER(_U64)] * 7),
     "kzg_rows_commit_sha256": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Sha256Unit), ctypes.POINTER(DeriveOpts),
                                     _B] + [ctypes.POINTER(_U64)] * 7),
     "kzg_rows_commit_keccak": (_I, [_P, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(KeccakUnit), ctypes.POINTER(DeriveOpts),
@@ -454,6 +472,9 @@ SYMBOLS = {
     "kzg_multi_rows_commit_poseidon": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(PoseidonParams), _U32,
                                             ctypes.POINTER(PoseidonUnit), ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64),
                                             ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_poseidon_chain": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(PoseidonParams), _U32,
+                                                  ctypes.POINTER(PoseidonChainUnit), ctypes.POINTER(DeriveOpts), _B]
+                                             + [ctypes.POINTER(_U64)] * 7),
     "kzg_multi_rows_commit_sha256": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(Sha256Unit),
                                           ctypes.POINTER(DeriveOpts), _B] + [ctypes.POINTER(_U64)] * 7),
     "kzg_multi_rows_commit_keccak": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), _U32, ctypes.POINTER(KeccakUnit),

@@ -1105,6 +1105,63 @@ class Client:
                 "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments],
                 "perms": st["perms"], "mismatch": st["mismatch"], "first_mismatch": st["first_mismatch"]}
 
+    # ---- the hash chip's chains: a Poseidon sponge over a long message, a Merkle path, block after block along the column
+    @_guard
+    def worker_commit_poseidon_chain(self, input_handles: Sequence[int], params: dict, units: Sequence[dict],
+                                     usable: Optional[int] = None, tail: Sequence[str] = ()):
+        """Extension: Poseidon sponge and Merkle-path columns of the rows of the input_handles sets, computed and committed on
+        the device as one new set.  params: as for worker_commit_poseidon (the caller's constants; none are generated).  units: 1
+        to 4 objects, each a chain over blocks of P = period rows, b < floor(n / P) with n = usable, or T; a block cut by n is
+        not started and its rows are 0.  Block b starts a segment when b = 0, when start is null, or when the start cell at row
+        b P is not zero; otherwise it continues the block before.  {"mode": "sponge", "in": [t slots], "start": row or null,
+        "period": P, "layout": ...}: a starting block's state is the slots at row b P; a continuing block's state is the output
+        before it plus the cell where a slot is a row, and that output alone where it is an immediate, so a tag or capacity
+        immediate enters once per message; with start null this is worker_commit_poseidon's rounds unit.  {"mode": "path",
+        "cap": slot, "leaf": slot, "sib": [t - 2 rows], "pos": row, "digest": j, "start": row or null, "period": P, "layout":
+        ...} (t >= 3, arity a = t - 1): state element 0 is cap, the child at position pos (the cell's whole integer; at or above
+        a: position 0, counted in `bad_pos`) is the leaf on a starting block and element digest of the output before on a
+        continuing one, the other children are the sib cells of row b P in their order.  "layout": "trace" (P >= R + 1) commits t
+        columns laid out as a rounds unit lays them out; "flat" with "cols": [names among in0 .. in{t-1}, out0 .. out{t-1}]
+        commits the named elements of the arranged state and of the output at row b P only (P = 1: one row per Merkle level).
+        With "expect": row and "digest" in place of layout and cols a unit commits nothing: at the last block of each segment
+        the digest is compared with the expect cell of that block's first row (`mismatch`, `first_mismatch`).  A slot is a row
+        index or ["imm", value].  A segment is serial: it costs its length times one permutation's latency whatever the number
+        of segments.  usable and tail: as for worker_commit_derived.  Returns the handle (null when every unit is a check), the
+        commitments, and per unit `blocks`, `segments`, `bad_pos`, `first_bad_pos`, `mismatch`, `first_mismatch`.  Nothing here
+        is a proof: the columns are prover data and the argument is the caller's gates."""
+        what = "worker_commit_poseidon_chain"
+        hs = _handles(input_handles)
+        try:
+            if not isinstance(params, dict):
+                raise ValueError(f"params is an object: {params!r}")
+            par = dict(params)
+            recs = []
+            for un in units:
+                if not isinstance(un, dict):
+                    raise ValueError(f"a unit is an object: {un!r}")
+                rec = dict(un)
+                if isinstance(rec.get("in"), (list, tuple)):
+                    rec["in"] = [tuple(v) if isinstance(v, (list, tuple)) else v for v in rec["in"]]
+                for name in ("cap", "leaf"):
+                    if isinstance(rec.get(name), (list, tuple)):
+                        rec[name] = tuple(rec[name])
+                recs.append(rec)
+        except (TypeError, ValueError, IndexError, KeyError) as e:
+            raise codec.CodecError(f"{what}: params must be an object and units a list of objects: {e!r}") from e
+        if not recs:
+            raise codec.CodecError(f"{what}: units must not be empty")
+        if usable is None:
+            if tail:
+                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
+            tb = []
+        else:
+            usable, tb = self._blind(what, usable, tail)
+            if usable == 0:
+                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        rs, st = self.engine.commit_poseidon_chain(hs, par, recs, usable, tb)
+        return {"handle": None if rs is None else int(rs.handle),
+                "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments], **st}
+
     # ---- the bit-oriented hash chip: the SHA-256 compression per row, as a check, or as a chained round trace
     @_guard
     def worker_commit_sha256(self, input_handles: Sequence[int], units: Sequence[dict], usable: Optional[int] = None,

@@ -11,6 +11,7 @@
 //   fr_alu.hip    the kernel of kzg_rows_commit_alu: the same arithmetic and its signed kinds, the kind chosen per cell by an op-code column
 //   fr_wide.hip   the kernel of kzg_rows_commit_wide: multi-limb add, sub, mul, divmod, mulmod and the carries of its limb identity
 //   fr_poseidon.hip the kernel of kzg_rows_commit_poseidon: the Hades permutation with x^5 per row, as a check, or as a round trace
+//   fr_poseidon_chain.hip the kernel of kzg_rows_commit_poseidon_chain: sponge and Merkle-path chains over blocks, one lane walking each segment
 //   fr_sha256.hip the kernel of kzg_rows_commit_sha256: the SHA-256 compression per row, as a check, or as a chained round trace
 //   fr_keccak.hip the kernel of kzg_rows_commit_keccak: Keccak-f[1600] per row, as a check, or as a chained round trace of 64-bit lanes
 //   fr_ec.hip     the kernel of kzg_rows_commit_ec: a b^-1 mod an odd p, affine point addition and doubling, the accumulator trace of a chain
@@ -542,6 +543,14 @@ int rows_ec_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, con
 int rows_edwards_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const kzg_edwards_curve* curve,
                      uint32_t n_units, const kzg_edwards_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48,
                      uint64_t* out_stats, const Blind* lay);
+// the n_out committed columns of the n_units Poseidon chain units (checked by the caller: params as for rows_poseidon_dev, modes,
+// layouts, periods, column ids, digests, canonical immediates, rows inside `inputs`) into a new n_out-row set's buffer dst (null
+// when n_out = 0: then no transform back and no MSM runs): their commitments and five runs of n_units statistics (segments, bad
+// positions, mismatching segments, then the smallest row of the last two kinds, KZG_POSEIDON_NONE: none).  lay: as for
+// rows_derived_dev
+int rows_poseidon_chain_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const kzg_poseidon_params* params,
+                            uint32_t n_units, const kzg_poseidon_chain_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst,
+                            uint8_t* out_c48, uint64_t* out_stats, const Blind* lay);
 // the n_out committed ones of the n_exprs expressions (checked by the caller: term counts and lengths in range, rows inside
 // `inputs`, rotations reduced into [0, T), canonical coefficients; is_check[e] != 0: expression e is only counted) into a new
 // n_out-row set's buffer dst (null when n_out = 0: then no transform back and no MSM runs): their commitments, and per

@@ -472,6 +472,41 @@ static_assert(sizeof(PosTab) + 64 <= 4096 && POLY_MAX_ROWS < POS_IMM, "the unit 
 // full + partial + 1, canonical constants: the caller's checks
 uint32_t poseidon_cst_words(uint32_t t, uint32_t rounds, uint32_t n_units);
 void launch_poseidon(hipStream_t s, const PosTab& tab, uint64_t T, uint64_t n, uint64_t* stats);
+// ---- the Poseidon sponge and Merkle-path chains of kzg_rows_commit_poseidon_chain (fr_poseidon_chain.hip).  t, full, partial and
+// cst are PosTab's (t immediates per unit).  A unit walks the blocks of `period` rows, b < floor(n / period); block b starts a
+// segment where b = 0, `start` is PCH_NONE or the cell of source vector `start` at the block's first row is not zero, and
+// continues the block before otherwise.  SPONGE: slot[j] is the source vector of state element j or POS_IMM; a continuing block
+// adds its cells to the output before it and leaves an immediate's element as it is.  PATH (t >= 3): slot[0] is the cap (element
+// 0), slot[1] the leaf, both a vector or POS_IMM, slot[2 + k], k < t - 2, the vector of sibling k; `pos` the vector of the child
+// position; the child at that position is the leaf (a starting block) or element `digest` of the output before.  layout
+// PCH_TRACE: the state before every round and behind the last into the t vectors at out; PCH_FLAT: at the block's first row
+// only, arranged state element j into vector col[j] of out and output element j into vector col[POS_MAX_T + j] (PCH_NONE: not
+// written); out was zeroed by the caller.  out null, layout 0, exp a source vector: a check: element `digest` of the output of a
+// segment's LAST block is compared with the cell of vector exp at that block's first row
+#define PCH_MAX_UNITS 4
+#define PCH_SPONGE 1
+#define PCH_PATH 2
+#define PCH_TRACE 1
+#define PCH_FLAT 2
+#define PCH_NONE 0xffu
+struct PchUnit {
+    uint32_t* out;
+    uint32_t mode, layout, period, pad;
+    uint8_t slot[POS_MAX_T], col[2 * POS_MAX_T];
+    uint8_t start, pos, digest, exp;
+};
+struct PchTab {
+    PchUnit u[PCH_MAX_UNITS];
+    const uint32_t *src, *cst;
+    uint32_t t, full, partial, n_units;
+};
+static_assert(sizeof(PchTab) + 64 <= 4096 && PCH_NONE == POS_IMM, "the unit table rides as a kernel argument; one escape value");
+// ONE launch for all units, instantiated on t.  stats: five runs of n_units words: [u] += the segments started, [n_units + u] +=
+// the blocks whose pos cell is at or above t - 1 (read as position 0), [2 n_units + u] += the segments of a check whose digest
+// differs, [3 n_units + u] <- min(., the smallest row of the second kind), [4 n_units + u] <- min(., of the third).  Sources are
+// only read and may coincide; out must not overlap a source.  Returns without a launch on a table that the caller's checks
+// should have refused
+void launch_poseidon_chain(hipStream_t s, const PchTab& tab, uint64_t T, uint64_t n, uint64_t* stats);
 // ---- the SHA-256 compression columns of kzg_rows_commit_sha256 (fr_sha256.hip).  Every value is a 32-bit word: the low 32 bits
 // of a source cell's canonical integer in, int_store's cell out.  Source vector d lies at src + d T 8 words.  A ROW unit runs one
 // compression per row t' < n: slot j < 8 is word j of the chaining value, slot 8 + j word j of the block; slot[j] is an index

@@ -540,6 +540,18 @@ int kzg_multi_rows_commit_poseidon(kzg_multi* mh, uint32_t i, uint32_t n_input_h
                                        out_perms, out_mismatch, out_first_mismatch, out_handle);
     });
 }
+int kzg_multi_rows_commit_poseidon_chain(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                         const kzg_poseidon_params* params, uint32_t n_units,
+                                         const kzg_poseidon_chain_unit* units, const kzg_derive_opts* opts,
+                                         uint8_t* out_commitments48, uint64_t* out_blocks, uint64_t* out_segments,
+                                         uint64_t* out_bad_pos, uint64_t* out_first_bad_pos, uint64_t* out_mismatch,
+                                         uint64_t* out_first_mismatch, uint64_t* out_handle) {
+    uint64_t* const st[6] = {out_blocks, out_segments, out_bad_pos, out_first_bad_pos, out_mismatch, out_first_mismatch};
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_poseidon_chain(c, s, n_input_handles, input_handles, params, n_units, units, opts, out_commitments48,
+                                             st, out_handle);
+    });
+}
 int kzg_multi_rows_commit_sha256(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                  uint32_t n_units, const kzg_sha256_unit* units, const kzg_derive_opts* opts,
                                  uint8_t* out_commitments48, uint64_t* out_blocks, uint64_t* out_messages, uint64_t* out_counts,

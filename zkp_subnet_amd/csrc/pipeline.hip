@@ -1602,6 +1602,91 @@ int rows_poseidon_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& input
     return KZG_OK;
 }
 
+// The Poseidon sponge and Merkle-path chains (kzg_rows_commit_poseidon_chain), in the builders' frame, with checks as
+// rows_poseidon_dev has them.  Each DISTINCT source row (by device pointer) that some unit reads is transformed forward once.
+//   step                      launches                         per call
+//   forward transforms        launch_fr_ntt                    one per distinct source row named
+//   constants                 one host-to-device copy          rc, M and the immediates as words, behind the vectors
+//   zero the columns          hipMemsetAsync                   one per committing unit
+//   every unit                launch_poseidon_chain (k_fr_poseidon_chain<t>) ONE, grid y = unit
+//   tail                      launch_sort_tail                 one per output row, with `usable` only
+//   inverse transform         row_to_coeffs                    one per output row, straight into dst
+//   commit                    multi_msms_finish                ONE pass of n_out scalar sets
+// The five statistics of every unit are u64 words behind the first two evaluation slots of the record and come back in the copy
+// behind the MSM.  With n_out = 0 (checks alone) nothing is transformed back and no MSM runs.  Workspace: distinct sources + n_out
+// vectors of T, and the constants.
+int rows_poseidon_chain_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const kzg_poseidon_params* params,
+                            uint32_t n_units, const kzg_poseidon_chain_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst,
+                            uint8_t* out_c48, uint64_t* out_stats, const Blind* lay) {
+    Lane& A = H.L();
+    Cols F;
+    if (int rc = cols_begin(ctx, A, T, lay, dst, F)) return rc;
+    const uint64_t vw = F.vw, n = F.n;
+    static_assert(40 * KZG_POSEIDON_CHAIN_MAX_UNITS <= STATS_MAX && KZG_POSEIDON_CHAIN_MAX_UNITS == PCH_MAX_UNITS &&
+                      KZG_POSEIDON_CHAIN_SPONGE == PCH_SPONGE && KZG_POSEIDON_CHAIN_PATH == PCH_PATH &&
+                      KZG_POSEIDON_CHAIN_TRACE == PCH_TRACE && KZG_POSEIDON_CHAIN_FLAT == PCH_FLAT &&
+                      KZG_POSEIDON_CHAIN_COL_OUT == POS_MAX_T && KZG_MAX_BATCH_OPEN <= Sources::CAP,
+                  "the five statistics of every unit fit the record's evaluation slots; the header's values are the kernel's");
+    const uint32_t t = params->t, R = params->full + params->partial;
+    Sources S;
+    PchTab tab;
+    memset(&tab, 0, sizeof(tab));
+    tab.t = t;
+    tab.full = params->full;
+    tab.partial = params->partial;
+    tab.n_units = n_units;
+    const uint32_t cw = poseidon_cst_words(t, R, n_units);
+    std::vector<uint32_t> cst(cw, 0);                 // (lives until multi_msms_finish has waited for the stream)
+    for (uint32_t k = 0; k < t * R; k++) poseidon_words(&cst[8 * k], params->rc_be32 + 32 * (size_t)k);
+    for (uint32_t k = 0; k < t * t; k++) poseidon_words(&cst[8 * (t * R + k)], params->mds_be32 + 32 * (size_t)k);
+    auto slot = [&](uint32_t row) { return row == KZG_POSEIDON_CHAIN_ABSENT ? (uint8_t)PCH_NONE : (uint8_t)S.slot_of(inputs.r[row]); };
+    for (uint32_t u = 0; u < n_units; u++) {
+        const kzg_poseidon_chain_unit& in = units[u];
+        PchUnit& U = tab.u[u];
+        U.mode = in.mode;
+        U.layout = in.layout;
+        U.period = in.period;
+        memset(U.col, PCH_NONE, sizeof(U.col));
+        memset(U.slot, PCH_NONE, sizeof(U.slot));
+        for (uint32_t j = 0; j < t; j++) {
+            U.slot[j] = slot(in.in[j]);               // (KZG_POSEIDON_IMM is KZG_POSEIDON_CHAIN_ABSENT's value: POS_IMM)
+            poseidon_words(&cst[8 * (t * R + t * t + u * t + j)], in.imm_be32[j]);
+        }
+        if (in.layout == KZG_POSEIDON_CHAIN_FLAT)
+            for (uint32_t c = 0; c < in.n_out; c++) U.col[in.out[c]] = (uint8_t)c;
+        U.start = slot(in.start);
+        U.pos = slot(in.pos);
+        U.exp = slot(in.expect);
+        U.digest = in.digest == KZG_POSEIDON_CHAIN_ABSENT ? (uint8_t)PCH_NONE : (uint8_t)in.digest;
+    }
+    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_out) * T * 32 + (size_t)cw * 4));
+    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + S.nd * vw, *cdev = outv + n_out * vw;
+    uint8_t* rec = F.rec;
+    uint64_t* st = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF);
+    sources_transform(ctx, A, F, S, src);
+    HIPCHK(ctx, hipMemcpyAsync(cdev, cst.data(), (size_t)cw * 4, hipMemcpyHostToDevice, A.stream));
+    HIPCHK(ctx, hipMemsetAsync(st, 0, 24 * (size_t)n_units, A.stream));
+    HIPCHK(ctx, hipMemsetAsync(st + 3 * n_units, 0xff, 16 * (size_t)n_units, A.stream));   // KZG_POSEIDON_NONE
+    tab.src = src;
+    tab.cst = cdev;
+    for (uint32_t u = 0, c = 0; u < n_units; u++) {
+        if (!units[u].n_out) continue;                // (a check)
+        tab.u[u].out = outv + c * vw;
+        HIPCHK(ctx, hipMemsetAsync(outv + c * vw, 0, (size_t)units[u].n_out * T * 32, A.stream));
+        c += units[u].n_out;
+    }
+    {
+        Span sp(ctx, A, KZG_T_POLY);
+        launch_poseidon_chain(A.stream, tab, T, n, st);
+    }
+    for (uint32_t c = 0; c < n_out; c++)
+        if (int rc = emit_column(ctx, A, F, outv + c * vw, c)) return rc;
+    const uint8_t* stats;
+    if (int rc = stats_finish(ctx, H, i, F, n_out, 40 * n_units, out_c48, &stats)) return rc;
+    memcpy(out_stats, stats, 40 * (size_t)n_units);
+    return KZG_OK;
+}
+
 // The SHA-256 compression columns (kzg_rows_commit_sha256), in the builders' frame, with checks as rows_poseidon_dev has them.
 // Each DISTINCT source row (by device pointer) that some unit reads or expects is transformed forward once.
 //   step                      launches                         per call

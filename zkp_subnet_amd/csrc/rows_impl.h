@@ -99,6 +99,10 @@ int rows_ec(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uin
 int rows_edwards(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
                  const kzg_edwards_curve* curve, uint32_t n_units, const kzg_edwards_unit* units, const kzg_derive_opts* opts,
                  uint8_t* out_commitments48, uint64_t* const out_stats[7], uint64_t* out_handle);
+// opts: as for rows_derived.  out_stats: the six statistics arrays of kzg_rows_commit_poseidon_chain in the order of its arguments
+int rows_poseidon_chain(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                        const kzg_poseidon_params* params, uint32_t n_units, const kzg_poseidon_chain_unit* units,
+                        const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* const out_stats[6], uint64_t* out_handle);
 // opts: the usable layout and its tail as the public call takes them (null: all T rows are evaluated)
 int rows_expr(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_exprs,
               const kzg_expr* exprs, const kzg_expr_opts* opts, uint8_t* out_commitments48, uint64_t* out_nonzero,

@@ -1501,6 +1501,26 @@ int rows_wide(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const u
     return KZG_OK;
 }
 
+// The checks of kzg_poseidon_params, shared by kzg_rows_commit_poseidon and kzg_rows_commit_poseidon_chain (`what` prefixes the
+// messages): the ranges of t, R_F and R_P, then the number of units (units_ok, with the words of its refusal), then every
+// constant and matrix entry canonical
+static int poseidon_params_check(kzg_ctx* ctx, const char* what, const kzg_poseidon_params* params, bool units_ok,
+                                 const char* units_why) {
+    auto bad = [&](const char* why) { return fail(ctx, KZG_E_ARG, std::string(what) + ": " + why); };
+    if (!params || !params->rc_be32 || !params->mds_be32) return bad("params, rc_be32 and mds_be32 must not be null");
+    const uint32_t t = params->t, R = params->full + params->partial;
+    if (t < KZG_POSEIDON_MIN_T || t > KZG_POSEIDON_MAX_T) return bad("the width t must be in [2, 8]");
+    if (params->full < 2 || params->full > KZG_POSEIDON_MAX_FULL || (params->full & 1))
+        return bad("the number of full rounds R_F must be even and in [2, 16]");
+    if (params->partial > KZG_POSEIDON_MAX_PARTIAL) return bad("the number of partial rounds R_P must be in [0, 128]");
+    if (!units_ok) return bad(units_why);
+    for (uint32_t k = 0; k < t * R; k++)
+        if (!fr_be32_canonical(params->rc_be32 + 32 * (size_t)k)) return bad("round constants must be canonical scalars (< r)");
+    for (uint32_t k = 0; k < t * t; k++)
+        if (!fr_be32_canonical(params->mds_be32 + 32 * (size_t)k)) return bad("matrix entries must be canonical scalars (< r)");
+    return KZG_OK;
+}
+
 // kzg_rows_commit_poseidon: a BuilderCall around its own checks; as in rows_expr, no reservation and no set when every unit is
 // a check.  The parameters, the constants and immediates, modes, flags and out lists are checked here, on the host, before a
 // lane is taken
@@ -1511,22 +1531,10 @@ int rows_poseidon(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, con
     if (!ctx || !input_handles || !out_perms || !out_mismatch || !out_first_mismatch || !out_handle) return KZG_E_ARG;
     if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "poseidon: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
-    if (!params || !params->rc_be32 || !params->mds_be32)
-        return fail(ctx, KZG_E_ARG, "poseidon: params, rc_be32 and mds_be32 must not be null");
+    if (int rc = poseidon_params_check(ctx, "poseidon", params, n_units != 0 && n_units <= KZG_POSEIDON_MAX_UNITS && units,
+                                       "n_units must be in [1, KZG_POSEIDON_MAX_UNITS]"))
+        return rc;
     const uint32_t t = params->t, R = params->full + params->partial;
-    if (t < KZG_POSEIDON_MIN_T || t > KZG_POSEIDON_MAX_T) return fail(ctx, KZG_E_ARG, "poseidon: the width t must be in [2, 8]");
-    if (params->full < 2 || params->full > KZG_POSEIDON_MAX_FULL || (params->full & 1))
-        return fail(ctx, KZG_E_ARG, "poseidon: the number of full rounds R_F must be even and in [2, 16]");
-    if (params->partial > KZG_POSEIDON_MAX_PARTIAL)
-        return fail(ctx, KZG_E_ARG, "poseidon: the number of partial rounds R_P must be in [0, 128]");
-    if (n_units == 0 || n_units > KZG_POSEIDON_MAX_UNITS || !units)
-        return fail(ctx, KZG_E_ARG, "poseidon: n_units must be in [1, KZG_POSEIDON_MAX_UNITS]");
-    for (uint32_t k = 0; k < t * R; k++)
-        if (!fr_be32_canonical(params->rc_be32 + 32 * (size_t)k))
-            return fail(ctx, KZG_E_ARG, "poseidon: round constants must be canonical scalars (< r)");
-    for (uint32_t k = 0; k < t * t; k++)
-        if (!fr_be32_canonical(params->mds_be32 + 32 * (size_t)k))
-            return fail(ctx, KZG_E_ARG, "poseidon: matrix entries must be canonical scalars (< r)");
     uint32_t n_out = 0, max_row = 0, n_seen = 0, seen[2 * KZG_POSEIDON_MAX_T * KZG_POSEIDON_MAX_UNITS];
     auto see = [&](uint32_t row) {
         max_row = std::max(max_row, row);
@@ -1583,6 +1591,110 @@ int rows_poseidon(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, con
     for (uint32_t u = 0; u < n_units; u++) out_perms[u] = units[u].mode == KZG_POSEIDON_ROUNDS ? n / units[u].period : n;
     memcpy(out_mismatch, stats, 8 * (size_t)n_units);
     memcpy(out_first_mismatch, stats + n_units, 8 * (size_t)n_units);
+    *out_handle = C.commit();
+    return KZG_OK;
+}
+
+// kzg_rows_commit_poseidon_chain: a BuilderCall around its own checks; as in rows_poseidon, no reservation and no set when every
+// unit is a check.  The parameters, modes, flags, layouts, periods, column ids and the entries a mode does not take are checked
+// here, on the host, before a lane is taken
+int rows_poseidon_chain(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                        const kzg_poseidon_params* params, uint32_t n_units, const kzg_poseidon_chain_unit* units,
+                        const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* const out_stats[6], uint64_t* out_handle) {
+    if (!ctx || !input_handles || !out_stats || !out_handle) return KZG_E_ARG;
+    for (int k = 0; k < 6; k++)
+        if (!out_stats[k]) return KZG_E_ARG;
+    auto bad = [&](const char* why) { return fail(ctx, KZG_E_ARG, std::string("poseidon_chain: ") + why); };
+    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
+        return bad("the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (int rc = poseidon_params_check(ctx, "poseidon_chain", params, n_units != 0 && n_units <= KZG_POSEIDON_CHAIN_MAX_UNITS && units,
+                                       "n_units must be in [1, KZG_POSEIDON_CHAIN_MAX_UNITS]"))
+        return rc;
+    const uint32_t t = params->t, R = params->full + params->partial, ABSENT = KZG_POSEIDON_CHAIN_ABSENT;
+    uint32_t n_out = 0, max_row = 0, n_seen = 0, seen[(KZG_POSEIDON_MAX_T + 3) * KZG_POSEIDON_CHAIN_MAX_UNITS];
+    auto see = [&](uint32_t row) {
+        max_row = std::max(max_row, row);
+        uint32_t d = 0;
+        while (d < n_seen && seen[d] != row) d++;
+        if (d == n_seen) seen[n_seen++] = row;
+    };
+    for (uint32_t u = 0; u < n_units; u++) {
+        const kzg_poseidon_chain_unit& U = units[u];
+        if (U.mode != KZG_POSEIDON_CHAIN_SPONGE && U.mode != KZG_POSEIDON_CHAIN_PATH)
+            return bad("unknown mode (KZG_POSEIDON_CHAIN_SPONGE or KZG_POSEIDON_CHAIN_PATH)");
+        if ((U.flags & ~KZG_POSEIDON_CHAIN_CHECK) || U.reserved) return bad("flags must be 0 or KZG_POSEIDON_CHAIN_CHECK, reserved 0");
+        const bool path = U.mode == KZG_POSEIDON_CHAIN_PATH, check = U.flags == KZG_POSEIDON_CHAIN_CHECK;
+        if (path && t < 3) return bad("a PATH unit needs t >= 3 (the arity is t - 1)");
+        if (U.period == 0) return bad("the period P must be in [1, 2^32)");
+        if (check) {
+            if (U.layout || U.n_out) return bad("layout and n_out must be 0 beside KZG_POSEIDON_CHAIN_CHECK: a check commits nothing");
+            if (U.expect == ABSENT) return bad("expect must be a row with KZG_POSEIDON_CHAIN_CHECK, not an immediate or absent");
+            see(U.expect);
+        } else {
+            if (U.expect != ABSENT) return bad("expect belongs to KZG_POSEIDON_CHAIN_CHECK (KZG_POSEIDON_CHAIN_ABSENT without)");
+            if (U.layout != KZG_POSEIDON_CHAIN_TRACE && U.layout != KZG_POSEIDON_CHAIN_FLAT)
+                return bad("unknown layout (KZG_POSEIDON_CHAIN_TRACE or KZG_POSEIDON_CHAIN_FLAT)");
+            const bool trace = U.layout == KZG_POSEIDON_CHAIN_TRACE;
+            if (trace && U.period <= R) return bad("the period P of a TRACE unit must be at least R + 1");
+            if (trace ? U.n_out != t : (U.n_out == 0 || U.n_out > 2 * t))
+                return bad("n_out must be t on a TRACE unit and in [1, 2 t] on a FLAT unit");
+            uint32_t taken = 0;
+            for (uint32_t c = 0; c < U.n_out; c++) {
+                const uint32_t id = U.out[c];
+                if (trace ? id != c : (id % KZG_POSEIDON_CHAIN_COL_OUT >= t || id >= 2 * KZG_POSEIDON_CHAIN_COL_OUT))
+                    return bad("unknown column id (TRACE: out[j] = j; FLAT: KZG_POSEIDON_CHAIN_COL_IN / _OUT + j, j < t)");
+                if (taken >> id & 1) return bad("a column id is repeated");
+                taken |= 1u << id;
+            }
+        }
+        if (path || check) {
+            if (U.digest >= t) return bad("digest must be a state index below t on a PATH unit and on a check");
+        } else if (U.digest != ABSENT) {
+            return bad("digest belongs to PATH units and checks (KZG_POSEIDON_CHAIN_ABSENT elsewhere)");
+        }
+        if (path) {
+            if (U.pos == ABSENT) return bad("pos must be a row on a PATH unit, not an immediate or absent");
+            see(U.pos);
+        } else if (U.pos != ABSENT) {
+            return bad("pos belongs to PATH units (KZG_POSEIDON_CHAIN_ABSENT on a SPONGE unit)");
+        }
+        if (U.start != ABSENT) see(U.start);
+        for (uint32_t j = 0; j < KZG_POSEIDON_MAX_T; j++) {
+            if (j >= t) {
+                bool zero = U.in[j] == 0;
+                for (int b = 0; b < 32; b++) zero = zero && !U.imm_be32[j][b];
+                if (!zero) return bad("the entries of in and imm_be32 at and above t must be 0");
+            } else if (U.in[j] != KZG_POSEIDON_IMM) {
+                see(U.in[j]);
+                for (int b = 0; b < 32; b++)
+                    if (U.imm_be32[j][b]) return bad("the immediate must be 0 beside a row");
+            } else if (path && j >= 2) {
+                return bad("a sibling of a PATH unit is a row, not an immediate");
+            } else if (!fr_be32_canonical(U.imm_be32[j])) {
+                return bad("immediates must be canonical scalars (< r)");
+            }
+        }
+        if (n_seen > KZG_MAX_BATCH_OPEN) return bad("a call reads at most KZG_MAX_BATCH_OPEN distinct input rows");
+        n_out += U.n_out;
+    }
+    if (n_out > KZG_MAX_BATCH_OPEN) return bad("n_out, the committed columns of all units, must be at most KZG_MAX_BATCH_OPEN");
+    if (n_out && !out_commitments48) return KZG_E_ARG;
+    BuilderCall C(ctx, "poseidon_chain");
+    RowTab it;
+    uint32_t ki = 0;
+    if (int rc = C.begin("poseidon_chain", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
+    if (n_seen && max_row >= ki) return bad("a row must index the concatenated rows of the input sets");
+    if (int rc = C.ready(n_out, 32, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ)) return rc;
+    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    uint64_t stats[5 * KZG_POSEIDON_CHAIN_MAX_UNITS];
+    if (int rc = rows_poseidon_chain_dev(ctx, C.H, C.i, it, params, n_units, units, n_out, C.T, C.dst(), c48, stats, C.blind))
+        return rc;
+    if (n_out) memcpy(out_commitments48, c48, 48 * (size_t)n_out);
+    const uint64_t n = C.blind ? C.blind->usable : C.T;
+    for (uint32_t u = 0; u < n_units; u++) out_stats[0][u] = n / units[u].period;
+    // the device's runs: segments, bad positions, mismatches, then the first rows of the last two
+    static const int run_of[6] = {-1, 0, 1, 3, 2, 4};
+    for (int k = 1; k < 6; k++) memcpy(out_stats[k], stats + run_of[k] * n_units, 8 * (size_t)n_units);
     *out_handle = C.commit();
     return KZG_OK;
 }
@@ -2927,6 +3039,15 @@ int kzg_rows_commit_wide(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t*
                          uint64_t* out_first, uint64_t* out_qover, uint64_t* out_first_qover, uint64_t* out_handle) {
     return rows_wide(ctx, UINT32_MAX, n_input_handles, input_handles, n_ops, ops, opts, out_commitments48, out_counts, out_first,
                      out_qover, out_first_qover, out_handle);
+}
+int kzg_rows_commit_poseidon_chain(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                                   const kzg_poseidon_params* params, uint32_t n_units, const kzg_poseidon_chain_unit* units,
+                                   const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_blocks,
+                                   uint64_t* out_segments, uint64_t* out_bad_pos, uint64_t* out_first_bad_pos,
+                                   uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_handle) {
+    uint64_t* const st[6] = {out_blocks, out_segments, out_bad_pos, out_first_bad_pos, out_mismatch, out_first_mismatch};
+    return rows_poseidon_chain(ctx, UINT32_MAX, n_input_handles, input_handles, params, n_units, units, opts, out_commitments48, st,
+                               out_handle);
 }
 int kzg_rows_commit_poseidon(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
                              const kzg_poseidon_params* params, uint32_t n_units, const kzg_poseidon_unit* units,

@@ -1245,15 +1245,9 @@ class HipEngine:
     _POSEIDON_UNIT_KEYS = ("mode", "in", "out", "expect", "period")
 
     @classmethod
-    def poseidon_call(cls, params, units, what: str = "commit_poseidon") -> Tuple[tuple, List[tuple]]:
-        """The kzg_poseidon_params fields (t, full, partial, rc bytes, mds bytes) and per unit the kzg_poseidon_unit fields
-        (mode, flags, n_out, period, in[8], out[8], expect[8], imm[8] of 32 bytes) of a call.  params: a mapping with t (2 .. 8),
-        full (R_F, even, 2 .. 16), partial (R_P, 0 .. 128), rc (t (R_F + R_P) scalars, round-major) and mds (t t scalars,
-        row-major).  A unit is a mapping: mode "row" with in (t entries), out (1 .. t distinct state indices) and, for a check,
-        expect (one row per entry of out); or mode "rounds" with in and period (at least R_F + R_P + 1).  An entry of in is a row
-        index or ("imm", value).  A scalar is an int, a decimal or 0x string, or 32 big-endian bytes, below r.  Raises
-        KzgError(KZG_E_ARG) with the cause; needs no device."""
-        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: poseidon: {why}")   # noqa: E731
+    def _poseidon_params(cls, params, bad):
+        """The params of poseidon_call and poseidon_chain_call, checked and encoded by one body: (t, R, (t, full, partial, rc
+        bytes, mds bytes), is_u, scalar); bad(why) makes the caller's KzgError"""
         is_u = lambda v, top: isinstance(v, int) and not isinstance(v, bool) and 0 <= v < top   # noqa: E731
         r_mod = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
 
@@ -1290,6 +1284,19 @@ class HipEngine:
             raise bad(f"mds must be a list of t t = {t * t} scalars, row-major")
         rc_b = b"".join(scalar(v, "a round constant") for v in rc)
         mds_b = b"".join(scalar(v, "a matrix entry") for v in mds)
+        return t, R, (t, full, partial, rc_b, mds_b), is_u, scalar
+
+    @classmethod
+    def poseidon_call(cls, params, units, what: str = "commit_poseidon") -> Tuple[tuple, List[tuple]]:
+        """The kzg_poseidon_params fields (t, full, partial, rc bytes, mds bytes) and per unit the kzg_poseidon_unit fields
+        (mode, flags, n_out, period, in[8], out[8], expect[8], imm[8] of 32 bytes) of a call.  params: a mapping with t (2 .. 8),
+        full (R_F, even, 2 .. 16), partial (R_P, 0 .. 128), rc (t (R_F + R_P) scalars, round-major) and mds (t t scalars,
+        row-major).  A unit is a mapping: mode "row" with in (t entries), out (1 .. t distinct state indices) and, for a check,
+        expect (one row per entry of out); or mode "rounds" with in and period (at least R_F + R_P + 1).  An entry of in is a row
+        index or ("imm", value).  A scalar is an int, a decimal or 0x string, or 32 big-endian bytes, below r.  Raises
+        KzgError(KZG_E_ARG) with the cause; needs no device."""
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: poseidon: {why}")   # noqa: E731
+        t, R, par, is_u, scalar = cls._poseidon_params(params, bad)
         units = list(units) if isinstance(units, (list, tuple)) else None
         if not units or len(units) > _native.KZG_POSEIDON_MAX_UNITS:
             raise bad(f"units must be a list of 1 .. {_native.KZG_POSEIDON_MAX_UNITS} entries (n_units)")
@@ -1357,7 +1364,7 @@ class HipEngine:
         n_out = sum(r[2] for r in recs if not r[1])
         if n_out > _native.KZG_MAX_BATCH_OPEN:
             raise bad(f"n_out: the units give {n_out} output rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
-        return (t, full, partial, rc_b, mds_b), recs
+        return par, recs
 
     @staticmethod
     def poseidon_unit_struct(rec) -> "_native.PoseidonUnit":
@@ -1393,6 +1400,168 @@ class HipEngine:
         rs = RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]) if n_out else None
         return rs, {"perms": [int(v) for v in st[0]], "mismatch": [int(v) for v in st[1]],
                     "first_mismatch": [None if int(v) == _native.KZG_POSEIDON_NONE else int(v) for v in st[2]]}
+
+    # ---- a set built from sets: Poseidon sponges and Merkle paths, chained from block to block along the column
+    _POSEIDON_CHAIN_SPONGE_KEYS = ("mode", "in", "start", "period", "layout", "cols", "digest", "expect")
+    _POSEIDON_CHAIN_PATH_KEYS = ("mode", "cap", "leaf", "sib", "pos", "digest", "start", "period", "layout", "cols", "expect")
+
+    @classmethod
+    def poseidon_chain_call(cls, params, units, what: str = "commit_poseidon_chain") -> Tuple[tuple, List[tuple]]:
+        """The kzg_poseidon_params fields (as poseidon_call returns them, from the same body) and per unit the
+        kzg_poseidon_chain_unit fields (mode, flags, layout, period, start, pos, digest, expect, n_out, in[8], out[16], imm[8] of 32
+        bytes) of a call.  A unit is a mapping.  {"mode": "sponge", "in": t slots, "start": row or None, "period": P, "layout":
+        "trace" or "flat"}; {"mode": "path", "cap": slot, "leaf": slot, "sib": t - 2 rows, "pos": row, "digest": j, "start": row or
+        None, "period": P, "layout": ...}.  "flat" takes "cols": 1 .. 2 t distinct names among in0 .. in{t-1}, out0 .. out{t-1};
+        "trace" needs P >= R_F + R_P + 1.  Either mode with "expect": row (and "digest") in place of layout and cols is a check.
+        A slot is a row index or ("imm", value).  Raises KzgError(KZG_E_ARG) with the cause; needs no device."""
+        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: poseidon_chain: {why}")   # noqa: E731
+        t, R, par, is_u, scalar = cls._poseidon_params(params, bad)
+        IMM, ABSENT, TOP = _native.KZG_POSEIDON_IMM, _native.KZG_POSEIDON_CHAIN_ABSENT, _native.KZG_POSEIDON_CHAIN_MAX_UNITS
+        units = list(units) if isinstance(units, (list, tuple)) else None
+        if not units or len(units) > TOP:
+            raise bad(f"units must be a list of 1 .. {TOP} entries (n_units)")
+        recs, seen = [], set()
+
+        def row(v, name, optional=False):
+            if v is None and optional:
+                return ABSENT
+            if isinstance(v, (list, tuple)):
+                raise bad(f"{name} must be a row, not an immediate")
+            if not is_u(v, IMM):
+                raise bad(f"{name} must be a row index, an integer in [0, 2^32 - 1)")
+            seen.add(v)
+            return v
+
+        def slot(v, name):
+            if isinstance(v, (list, tuple)):
+                if len(v) != 2 or v[0] != "imm":
+                    raise bad('an immediate is ("imm", value)')
+                return IMM, scalar(v[1], "an immediate")
+            if not is_u(v, IMM):
+                raise bad(f'{name} must be a row index, an integer in [0, 2^32 - 1), or ("imm", value)')
+            seen.add(v)
+            return v, bytes(32)
+
+        for un in units:
+            if not isinstance(un, dict) or "mode" not in un:
+                raise bad("a unit is a mapping with mode and the fields of its mode")
+            mode = un["mode"]
+            if mode not in ("sponge", "path"):
+                raise bad(f'unknown mode {mode!r} (one of "sponge", "path")')
+            keys = cls._POSEIDON_CHAIN_SPONGE_KEYS if mode == "sponge" else cls._POSEIDON_CHAIN_PATH_KEYS
+            extra = set(un) - set(keys)
+            if extra:
+                name = sorted(extra)[0]
+                if name in cls._POSEIDON_CHAIN_SPONGE_KEYS + cls._POSEIDON_CHAIN_PATH_KEYS:
+                    raise bad(f"a field the mode does not take: {name!r} does not belong to a {mode} unit")
+                raise bad(f"unknown field {name!r} (the fields of a {mode} unit are {', '.join(keys)})")
+            if mode == "sponge":
+                ins = un.get("in")
+                if not isinstance(ins, (list, tuple)) or len(ins) != t:
+                    raise bad(f"in must hold t = {t} entries, each a row index or (\"imm\", value)")
+                slots = [slot(v, "an entry of in") for v in ins]
+                pos = ABSENT
+            else:
+                if t < 3:
+                    raise bad("a path unit needs t >= 3: the arity is t - 1")
+                if "cap" not in un or "leaf" not in un:
+                    raise bad("a path unit needs cap and leaf, each a row index or (\"imm\", value)")
+                sib = un.get("sib")
+                if not isinstance(sib, (list, tuple)) or len(sib) != t - 2:
+                    raise bad(f"sib must hold t - 2 = {t - 2} rows")
+                slots = [slot(un["cap"], "cap"), slot(un["leaf"], "leaf")] + [(row(v, "an entry of sib"), bytes(32)) for v in sib]
+                pos = row(un.get("pos"), "pos")
+            start = row(un.get("start"), "start", optional=True)
+            period = un.get("period")
+            if not is_u(period, 1 << 32) or period < 1:
+                raise bad("the period P must be an integer in [1, 2^32)")
+            digest = un.get("digest")
+            if digest is not None and not is_u(digest, t):
+                raise bad(f"digest must be a state index below t = {t}")
+            flags, layout, out, expect = 0, 0, [], ABSENT
+            if un.get("expect") is not None:
+                if un.get("layout") is not None or un.get("cols") is not None:
+                    raise bad("layout and cols are refused beside expect: a check commits nothing")
+                if digest is None:
+                    raise bad("expect needs digest, the state index that is compared")
+                expect = row(un["expect"], "expect")
+                flags = _native.KZG_POSEIDON_CHAIN_CHECK
+            else:
+                if mode == "path" and digest is None:
+                    raise bad("a path unit needs digest, the state index that a continuing block hashes")
+                if mode == "sponge" and digest is not None:
+                    raise bad("digest belongs to path units and to checks (expect)")
+                lay = un.get("layout")
+                if lay not in ("trace", "flat"):
+                    raise bad(f'unknown layout {lay!r} (one of "trace", "flat")')
+                if lay == "trace":
+                    if un.get("cols") is not None:
+                        raise bad("cols belongs to the flat layout: a trace commits all t columns")
+                    if period < R + 1:
+                        raise bad(f"the period P of a trace must be at least R + 1 = {R + 1}")
+                    layout, out = _native.KZG_POSEIDON_CHAIN_TRACE, list(range(t))
+                else:
+                    cols = un.get("cols")
+                    names = [f"in{j}" for j in range(t)] + [f"out{j}" for j in range(t)]
+                    if not isinstance(cols, (list, tuple)) or not cols:
+                        raise bad(f"cols must hold 1 .. 2 t = {2 * t} column names among {', '.join(names)}")
+                    for name in cols:
+                        if name not in names:
+                            raise bad(f"unknown column name {name!r} (the names are {', '.join(names)})")
+                    if len(set(cols)) != len(cols):
+                        raise bad("a column name is repeated")
+                    layout = _native.KZG_POSEIDON_CHAIN_FLAT
+                    ids = [_native.KZG_POSEIDON_CHAIN_COL_IN + j for j in range(t)] + \
+                          [_native.KZG_POSEIDON_CHAIN_COL_OUT + j for j in range(t)]
+                    out = [ids[names.index(c)] for c in cols]
+            recs.append((_native.KZG_POSEIDON_CHAIN_SPONGE if mode == "sponge" else _native.KZG_POSEIDON_CHAIN_PATH, flags, layout,
+                         period, start, pos, ABSENT if digest is None else digest, expect, len(out),
+                         [s[0] for s in slots] + [0] * (8 - t), out + [0] * (16 - len(out)),
+                         [s[1] for s in slots] + [bytes(32)] * (8 - t)))
+        if len(seen) > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"the units read {len(seen)} distinct input rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+        n_out = sum(r[8] for r in recs)
+        if n_out > _native.KZG_MAX_BATCH_OPEN:
+            raise bad(f"n_out: the units give {n_out} output rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+        return par, recs
+
+    @staticmethod
+    def poseidon_chain_unit_struct(rec) -> "_native.PoseidonChainUnit":
+        u = _native.PoseidonChainUnit(*rec[:9], 0, (ctypes.c_uint32 * 8)(*rec[9]), (ctypes.c_uint32 * 16)(*rec[10]))
+        for j, b in enumerate(rec[11]):
+            u.imm_be32[j][:] = list(b)
+        return u
+
+    def commit_poseidon_chain(self, input_sets: Sequence[object], params: dict, units: Sequence[dict],
+                              usable: Optional[int] = None, tail: Sequence[bytes] = ()) -> Tuple[Optional["RowSet"], dict]:
+        """kzg_rows_commit_poseidon_chain over the concatenated rows of input_sets (RowSet objects or bare handles).  params: as
+        for commit_poseidon; units: see poseidon_chain_call.  Every unit is a chain over blocks of `period` rows, b < floor(n /
+        P) with n = usable, or T: block b starts a segment when b = 0, start is None or its start cell at row b P is not zero,
+        and continues the block before otherwise.  A sponge block that continues adds its cells to the output before it (an
+        immediate enters once per segment); a path block hashes cap and the t - 1 children, the child at position pos being the
+        leaf (a starting block) or element digest of the output before (a pos cell at or above t - 1 is position 0 and counted).
+        Layout "trace" commits the t columns of the round trace, "flat" the named in / out columns at the block's first row;
+        with expect the unit commits nothing and compares element digest of every segment's last output.  A segment is serial:
+        one lane walks it.  Returns (the new RowSet of all committed columns in unit order, or None when every unit is a check;
+        {"blocks", "segments", "bad_pos", "first_bad_pos", "mismatch", "first_mismatch"} per unit).  usable and tail: as for
+        commit_poseidon."""
+        what = "commit_poseidon_chain"
+        ni, hi = self._handle_array(input_sets, what)
+        par, recs = self.poseidon_chain_call(params, units, what)
+        n_out = sum(r[8] for r in recs)
+        wi, T, lay = self._column_layout(what, input_sets, n_out, "n_out", "read", usable, tail)
+        opts = _native.DeriveOpts(*lay) if lay else None
+        pp = _native.PoseidonParams(*par)
+        arr = (_native.PoseidonChainUnit * len(recs))(*[self.poseidon_chain_unit_struct(r) for r in recs])
+        c, h = ctypes.create_string_buffer(48 * max(n_out, 1)), ctypes.c_uint64(0)
+        st = [(ctypes.c_uint64 * len(recs))() for _ in range(6)]
+        self._chk(self._lib.kzg_rows_commit_poseidon_chain(self._h, ni, hi, ctypes.byref(pp), len(recs), arr,
+                                                           ctypes.byref(opts) if opts is not None else None, c if n_out else None,
+                                                           *st, ctypes.byref(h)))
+        rs = RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]) if n_out else None
+        none = lambda xs: [None if int(v) == _native.KZG_POSEIDON_NONE else int(v) for v in xs]   # noqa: E731
+        return rs, {"blocks": [int(v) for v in st[0]], "segments": [int(v) for v in st[1]], "bad_pos": [int(v) for v in st[2]],
+                    "first_bad_pos": none(st[3]), "mismatch": [int(v) for v in st[4]], "first_mismatch": none(st[5])}
 
     # ---- a set built from sets: the SHA-256 compression per row, as a check, or as a chained round trace
     _SHA256_ROW_KEYS = ("mode", "state", "msg", "out", "expect")
