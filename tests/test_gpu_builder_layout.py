@@ -1,12 +1,14 @@
-"""GPU tests (`-m gpu`) of what the nine column builders share: sorted, derived, int, alu, wide, poseidon, expr, recurrence and
-fetch go through one call frame and one check of the `usable` / `tail_be32` layout, and this module pins, for all nine, what
-that frame must keep and what no builder's own module pins for every one of them: the five layout refusals with their WHOLE
-texts, the order of refusals as a caller sees it, the calls that may omit the tail because nothing takes one, and that the
-engine serves the next call with no set and no byte leaked after every refusal.
+"""GPU tests (`-m gpu`) of what the fourteen column builders share: sorted, derived, int, alu, wide, poseidon, expr,
+recurrence, fetch and the five further unit builders sha256, keccak, ec, edwards and poseidon_chain go through one call frame
+and one check of the `usable` / `tail_be32` layout, and this module pins, for all fourteen, what that frame must keep and what
+no builder's own module pins for every one of them: the five layout refusals with their WHOLE texts, the order of refusals as
+a caller sees it, the calls that may omit the tail because nothing takes one, and that the engine serves the next call with no
+set and no byte leaked after every refusal.
 
 Every call goes through the raw binding (the engine's Python checks would answer first) with the builder's cheapest valid
-arguments: one op, unit, expression or read over one or two committed rows.  T = 16 throughout, except where 33 rows must lie
-behind `usable`: T = 64 is the smallest power of two at which more than KZG_MAX_BLIND_ROWS = 32 can."""
+arguments: one op, unit, expression or read over one or two committed rows; the five unit builders' structs come from the
+engine's encoders and are spoilt afterwards.  T = 16 throughout, except where 33 rows must lie behind `usable`: T = 64 is the
+smallest power of two at which more than KZG_MAX_BLIND_ROWS = 32 can."""
 import ctypes
 
 import pytest
@@ -14,6 +16,7 @@ import pytest
 from tests.gpu_common import R, be
 from tests.gpu_rows import commit_sets, engine_cache, release
 from zkp_subnet_amd import _native as N
+from zkp_subnet_amd.engine import HipEngine
 
 pytestmark = pytest.mark.gpu
 SEED_X, SEED_Y = 0x1A7B111D, 0x1A7B111E
@@ -45,10 +48,11 @@ def resident(engines):
         release(list(sets.values()))
 
 
-# ------------------------------------------------------------------------------------------------ the nine raw calls
+# ------------------------------------------------------------------------------------------------ the fourteen raw calls
 # Each takes the engine, the resident sets, the layout (usable, tail bytes or None) and what to get wrong: `row` -- a row index
 # (or, where the builder has none, the row count) that does not fit the input sets; `op` -- the op, unit, flag or count that is
-# refused before a lane is taken; `handle` -- a handle that names no set; `check` -- every unit only checks (expr, poseidon).
+# refused before a lane is taken; `handle` -- a handle that names no set; `check` -- every unit only checks (expr, poseidon,
+# poseidon_chain).
 # Returns (status, handle of the new set).
 def _u64s(vals):
     return (ctypes.c_uint64 * len(vals))(*vals)
@@ -156,6 +160,55 @@ def call_fetch(eng, sets, usable, tail, row=False, op=False, handle=False, check
     return rc, h.value
 
 
+def _unit_call(fn, eng, sets, usable, tail, handle, lead, unit, n_stats):
+    """one unit of a unit builder through its raw call `fn`; lead: the params or curve struct in front of the units, or None"""
+    c, _, h = _outs()
+    st = [(ctypes.c_uint64 * 1)() for _ in range(n_stats)]
+    opts = N.DeriveOpts(usable, tail)
+    rc = fn(eng._h, 1, _handles(sets, "two", handle), *(() if lead is None else (ctypes.byref(lead),)), 1, (type(unit) * 1)(unit),
+            ctypes.byref(opts), c, *st, ctypes.byref(h))
+    return rc, h.value
+
+
+def call_sha256(eng, sets, usable, tail, row=False, op=False, handle=False, check=False):
+    rec, = HipEngine.sha256_call([{"mode": "row", "state": "iv", "msg": [("imm", 0)] * 15 + [0], "out": [0]}])
+    u = HipEngine.sha256_unit_struct(rec)
+    u.mode, u.msg[15] = (9 if op else u.mode), (OOB if row else 0)
+    return _unit_call(N.load().kzg_rows_commit_sha256, eng, sets, usable, tail, handle, None, u, 6)
+
+
+def call_keccak(eng, sets, usable, tail, row=False, op=False, handle=False, check=False):
+    rec, = HipEngine.keccak_call([{"mode": "row", "in": [("imm", 0)] * 24 + [0], "out": [0]}])
+    u = HipEngine.keccak_unit_struct(rec)
+    u.mode, u.in_[24] = (9 if op else u.mode), (OOB if row else 0)
+    return _unit_call(N.load().kzg_rows_commit_keccak, eng, sets, usable, tail, handle, None, u, 6)
+
+
+def call_ec(eng, sets, usable, tail, row=False, op=False, handle=False, check=False):
+    cv, recs = HipEngine.ec_call({"bits": 8, "limbs": 1, "p": 251, "a": 1}, [{"mode": "div", "a": 0, "b": 1, "out": True}])
+    curve, arr = HipEngine.ec_structs(cv, recs)
+    u = arr[0]
+    u.mode, u.in_[0] = (9 if op else u.mode), (OOB if row else 0)
+    return _unit_call(N.load().kzg_rows_commit_ec, eng, sets, usable, tail, handle, curve, u, 9)
+
+
+def call_edwards(eng, sets, usable, tail, row=False, op=False, handle=False, check=False):
+    cv, recs = HipEngine.edwards_call({"a": 2, "d": 3}, [{"mode": "add", "x1": 0, "y1": 1, "x2": 1, "y2": 0, "out": ["x3"]}])
+    curve, arr = HipEngine.edwards_structs(cv, recs)
+    u = arr[0]
+    u.mode, u.in_[0] = (9 if op else u.mode), (OOB if row else 0)
+    return _unit_call(N.load().kzg_rows_commit_edwards, eng, sets, usable, tail, handle, curve, u, 7)
+
+
+def call_poseidon_chain(eng, sets, usable, tail, row=False, op=False, handle=False, check=False):
+    form = {"expect": 1, "digest": 0} if check else {"layout": "flat", "cols": ["out0"]}
+    par, recs = HipEngine.poseidon_chain_call({"t": 2, "full": 2, "partial": 0, "rc": [1, 2, 3, 4], "mds": [2, 1, 1, 3]},
+                                              [dict({"mode": "sponge", "in": [0, 1], "start": None, "period": 1}, **form)])
+    u = HipEngine.poseidon_chain_unit_struct(recs[0])
+    u.mode, u.in_[0] = (9 if op else u.mode), (OOB if row else 0)
+    return _unit_call(N.load().kzg_rows_commit_poseidon_chain, eng, sets, usable, tail, handle, N.PoseidonParams(*par), u, 6)
+
+
 ROW = "%s: a row must index the concatenated rows of the input sets"
 READ, GIVEN = "all T rows are read", "%s: tail_be32 must be given when usable > 0"
 # name -> (call, prefix, the phrase of the first refusal, the tail-missing text, committed columns, closing rows, the text of
@@ -176,6 +229,13 @@ BUILDERS = {
                    "recur: mul and add must not both be empty (v would be the constant start)"),
     "fetch": (call_fetch, "fetch", READ, GIVEN, 1, 0, "fetch: the input sets must hold exactly n_reads * max(n_keys, 1) rows",
               "fetch: flags must be 0 or KZG_FETCH_INDEX"),
+    "sha256": (call_sha256, "sha256", READ, GIVEN, 1, 0, ROW, "sha256: unknown mode (KZG_SHA256_ROW or KZG_SHA256_ROUNDS)"),
+    "keccak": (call_keccak, "keccak", READ, GIVEN, 1, 0, ROW, "keccak: unknown mode (KZG_KECCAK_ROW or KZG_KECCAK_ROUNDS)"),
+    "ec": (call_ec, "ec", READ, GIVEN, 1, 0, "ec: an operand run must lie inside the concatenated rows of the input sets",
+           "ec: unknown mode (KZG_EC_DIV, KZG_EC_ADD or KZG_EC_CHAIN)"),
+    "edwards": (call_edwards, "edwards", READ, GIVEN, 1, 0, ROW, "edwards: unknown mode (KZG_EDWARDS_ADD or KZG_EDWARDS_CHAIN)"),
+    "poseidon_chain": (call_poseidon_chain, "poseidon_chain", READ, GIVEN, 1, 0, ROW,
+                       "poseidon_chain: unknown mode (KZG_POSEIDON_CHAIN_SPONGE or KZG_POSEIDON_CHAIN_PATH)"),
 }
 NAMES = list(BUILDERS)
 
@@ -244,7 +304,7 @@ def test_blind_rows_refusal(resident, name):
 def test_refusal_order(resident, name):
     """two mistakes at once.  The builder's check between the lookup and the layout (a row index outside the input sets; for
     sorted and fetch, which take no row index, the number of rows the sets hold) answers before the layout's.  The op (for
-    sorted n_keys, for fetch the flags, for recurrence two empty sides) is checked before a lane is taken in all nine builders,
+    sorted n_keys, for fetch the flags, for recurrence two empty sides) is checked before a lane is taken in all the builders,
     so it answers before the unknown handle's "<p>: unknown or released handle"."""
     eng, sets = resident(4)
     S, T = Served(eng, sets, name), 16
@@ -253,7 +313,7 @@ def test_refusal_order(resident, name):
     S.refused(b"%s: unknown or released handle" % (b"fetch: inputs" if name == "fetch" else S.prefix.encode()), handle=True)
 
 
-@pytest.mark.parametrize("name", ["expr", "poseidon"])
+@pytest.mark.parametrize("name", ["expr", "poseidon", "poseidon_chain"])
 def test_checks_only_needs_no_tail(resident, name):
     """every unit a check: nothing is committed, so no column takes a tail -- null is accepted in the usable layout, the call
     returns handle 0 and the live sets stay as they were"""

@@ -67,6 +67,9 @@ def _guard(fn):
     return wrapped
 
 
+_NO_PARAMS = object()   # _unit_objects: the request has no params object (None is a params a caller may send)
+
+
 def _handles(handles) -> List[int]:
     """committed-row-set handles from a request: 1 .. 16 non-negative integers"""
     try:
@@ -560,6 +563,46 @@ class Client:
             raise codec.CodecError(f"{what}: usable must not be negative and the tail scalars must be canonical (< r)")
         return usable, tb
 
+    @classmethod
+    def _layout(cls, what: str, usable, tail, null_means: str = "all rows are read") -> tuple:
+        """usable and tail as the column builders take them: (None, []) for usable = null, which takes no tail"""
+        if usable is None:
+            if tail:
+                raise codec.CodecError(f"{what}: a tail needs usable (null: {null_means})")
+            return None, []
+        usable, tb = cls._blind(what, usable, tail)
+        if usable == 0:
+            raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: {null_means})")
+        return usable, tb
+
+    @staticmethod
+    def _unit_objects(what: str, units, slot_lists=(), slots=(), params=_NO_PARAMS) -> list:
+        """The units of a unit builder's request as the engine's encoder takes them: every unit an object; the entries of the
+        fields slot_lists and the fields slots themselves become tuples where they are lists (["imm", value]).  params: the
+        object that leads the request, where the builder has one in this check"""
+        with_params = params is not _NO_PARAMS
+        head = "params must be an object and units a list of objects" if with_params else "units must be a list of objects"
+        try:
+            if with_params and not isinstance(params, dict):
+                raise ValueError(f"params is an object: {params!r}")
+            recs = []
+            for un in units:
+                if not isinstance(un, dict):
+                    raise ValueError(f"a unit is an object: {un!r}")
+                rec = dict(un)
+                for name in slot_lists:
+                    if isinstance(rec.get(name), (list, tuple)):
+                        rec[name] = [tuple(v) if isinstance(v, (list, tuple)) else v for v in rec[name]]
+                for name in slots:
+                    if isinstance(rec.get(name), (list, tuple)):
+                        rec[name] = tuple(rec[name])
+                recs.append(rec)
+        except (TypeError, ValueError, IndexError, KeyError) as e:
+            raise codec.CodecError(f"{what}: {head}: {e!r}") from e
+        if not recs:
+            raise codec.CodecError(f"{what}: units must not be empty")
+        return recs
+
     @_guard
     def worker_commit_grand_product_zk(self, wire_handles: Sequence[int], sigma_handles: Sequence[int], shifts: Sequence[str],
                                        beta: str, gamma: str, usable: int, tail: Sequence[str]):
@@ -683,14 +726,7 @@ class Client:
             raise codec.CodecError(f"{what}: width and n_keys must be integers: {e!r}") from e
         if not 1 <= width <= KZG_MAX_BATCH_OPEN or not 1 <= n_keys <= width:
             raise codec.CodecError(f"{what}: width must be in [1, {KZG_MAX_BATCH_OPEN}] and n_keys in [1, width]")
-        if usable is None:
-            if tail:
-                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are sorted)")
-            tb = []
-        else:
-            usable, tb = self._blind(what, usable, tail)
-            if usable == 0:
-                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are sorted)")
+        usable, tb = self._layout(what, usable, tail, "all rows are sorted")
         rs = self.engine.commit_sorted(hs, width, n_keys, usable, tb)
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments]}
 
@@ -724,14 +760,7 @@ class Client:
                                    f'["limbs", row, bits, count]: {e!r}') from e
         if not recs:
             raise codec.CodecError(f"{what}: ops must not be empty")
-        if usable is None:
-            if tail:
-                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
-            tb = []
-        else:
-            usable, tb = self._blind(what, usable, tail)
-            if usable == 0:
-                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        usable, tb = self._layout(what, usable, tail)
         rs, counts = self.engine.commit_derived(hs, recs, usable, tb)
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
                 "counts": [int(v) for v in counts]}
@@ -768,14 +797,7 @@ class Client:
             raise codec.CodecError(f"{what}: exprs must not be empty")
         if any(int.from_bytes(c, "big") >= codec.R_MODULUS for tt, _ in recs for c, _ in tt):
             raise codec.CodecError(f"{what}: coefficients must be canonical scalars (< r)")
-        if usable is None:
-            if tail:
-                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are evaluated)")
-            tb = []
-        else:
-            usable, tb = self._blind(what, usable, tail)
-            if usable == 0:
-                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are evaluated)")
+        usable, tb = self._layout(what, usable, tail, "all rows are evaluated")
         rs, nonzero, first = self.engine.commit_expr(hs, recs, usable, tb)
         return {"handle": None if rs is None else int(rs.handle),
                 "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments],
@@ -818,14 +840,7 @@ class Client:
         if any(int.from_bytes(c, "big") >= codec.R_MODULUS for m, a, _ in rr for c, _ in m + a) or any(
                 int.from_bytes(st, "big") >= codec.R_MODULUS for _, _, st in rr):
             raise codec.CodecError(f"{what}: coefficients and starts must be canonical scalars (< r)")
-        if usable is None:
-            if tail:
-                raise codec.CodecError(f"{what}: a tail needs usable (null: the plain layout)")
-            tb = []
-        else:
-            usable, tb = self._blind(what, usable, tail)
-            if usable == 0:
-                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: the plain layout)")
+        usable, tb = self._layout(what, usable, tail, "the plain layout")
         rs, closings = self.engine.commit_recurrence(hs, rr, usable, tb)
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
                 "closings": [codec.be32_to_fr(c) for c in closings]}
@@ -853,14 +868,7 @@ class Client:
             raise codec.CodecError(f"{what}: n_reads >= 1, n_keys >= 0 and n_reads * max(n_keys, 1) <= {KZG_MAX_BATCH_OPEN}")
         if with_index and n_keys == 0:
             raise codec.CodecError(f"{what}: with_index needs n_keys >= 1 (by row index the input row is the index)")
-        if usable is None:
-            if tail:
-                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
-            tb = []
-        else:
-            usable, tb = self._blind(what, usable, tail)
-            if usable == 0:
-                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        usable, tb = self._layout(what, usable, tail)
         rs, missing, first = self.engine.commit_fetch(hi, ht, n_reads, n_keys, with_index, usable, tb)
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
                 "missing": [int(v) for v in missing], "first_missing": first}
@@ -947,14 +955,7 @@ class Client:
             raise codec.CodecError(f"{what}: ops must be a list of [kind, w, a, b] or [kind, w, a, b, count]: {e!r}") from e
         if not recs:
             raise codec.CodecError(f"{what}: ops must not be empty")
-        if usable is None:
-            if tail:
-                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
-            tb = []
-        else:
-            usable, tb = self._blind(what, usable, tail)
-            if usable == 0:
-                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        usable, tb = self._layout(what, usable, tail)
         rs, counts, first = self.engine.commit_int(hs, recs, usable, tb)
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
                 "counts": counts, "first": first}
@@ -1003,14 +1004,7 @@ class Client:
             raise codec.CodecError(f"{what}: program must hold 1 to 64 entries")
         if not us or len(us) > 8:
             raise codec.CodecError(f"{what}: units must hold 1 to 8 entries")
-        if usable is None:
-            if tail:
-                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
-            tb = []
-        else:
-            usable, tb = self._blind(what, usable, tail)
-            if usable == 0:
-                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        usable, tb = self._layout(what, usable, tail)
         rs, st = self.engine.commit_alu(hs, prog, us, usable, tb)
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
                 "counts": st["counts"], "first": st["first"], "unknown": st["unknown"], "first_unknown": st["first_unknown"]}
@@ -1045,14 +1039,7 @@ class Client:
             raise codec.CodecError(f"{what}: ops must be a list of objects: {e!r}") from e
         if not recs:
             raise codec.CodecError(f"{what}: ops must not be empty")
-        if usable is None:
-            if tail:
-                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
-            tb = []
-        else:
-            usable, tb = self._blind(what, usable, tail)
-            if usable == 0:
-                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        usable, tb = self._layout(what, usable, tail)
         rs, st = self.engine.commit_wide(hs, recs, usable, tb)
         return {"handle": int(rs.handle), "commitments": [codec.g1_to_b64(c) for c in rs.commitments],
                 "counts": st["counts"], "first": st["first"], "qover": st["qover"], "first_qover": st["first_qover"]}
@@ -1076,30 +1063,8 @@ class Client:
         and the argument is the caller's round gate in the quotient."""
         what = "worker_commit_poseidon"
         hs = _handles(input_handles)
-        try:
-            if not isinstance(params, dict):
-                raise ValueError(f"params is an object: {params!r}")
-            par = dict(params)
-            recs = []
-            for un in units:
-                if not isinstance(un, dict):
-                    raise ValueError(f"a unit is an object: {un!r}")
-                rec = dict(un)
-                if isinstance(rec.get("in"), (list, tuple)):
-                    rec["in"] = [tuple(v) if isinstance(v, (list, tuple)) else v for v in rec["in"]]
-                recs.append(rec)
-        except (TypeError, ValueError, IndexError, KeyError) as e:
-            raise codec.CodecError(f"{what}: params must be an object and units a list of objects: {e!r}") from e
-        if not recs:
-            raise codec.CodecError(f"{what}: units must not be empty")
-        if usable is None:
-            if tail:
-                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
-            tb = []
-        else:
-            usable, tb = self._blind(what, usable, tail)
-            if usable == 0:
-                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        recs, par = self._unit_objects(what, units, ("in",), params=params), dict(params)
+        usable, tb = self._layout(what, usable, tail)
         rs, st = self.engine.commit_poseidon(hs, par, recs, usable, tb)
         return {"handle": None if rs is None else int(rs.handle),
                 "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments],
@@ -1131,33 +1096,8 @@ class Client:
         is a proof: the columns are prover data and the argument is the caller's gates."""
         what = "worker_commit_poseidon_chain"
         hs = _handles(input_handles)
-        try:
-            if not isinstance(params, dict):
-                raise ValueError(f"params is an object: {params!r}")
-            par = dict(params)
-            recs = []
-            for un in units:
-                if not isinstance(un, dict):
-                    raise ValueError(f"a unit is an object: {un!r}")
-                rec = dict(un)
-                if isinstance(rec.get("in"), (list, tuple)):
-                    rec["in"] = [tuple(v) if isinstance(v, (list, tuple)) else v for v in rec["in"]]
-                for name in ("cap", "leaf"):
-                    if isinstance(rec.get(name), (list, tuple)):
-                        rec[name] = tuple(rec[name])
-                recs.append(rec)
-        except (TypeError, ValueError, IndexError, KeyError) as e:
-            raise codec.CodecError(f"{what}: params must be an object and units a list of objects: {e!r}") from e
-        if not recs:
-            raise codec.CodecError(f"{what}: units must not be empty")
-        if usable is None:
-            if tail:
-                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
-            tb = []
-        else:
-            usable, tb = self._blind(what, usable, tail)
-            if usable == 0:
-                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        recs, par = self._unit_objects(what, units, ("in",), ("cap", "leaf"), params=params), dict(params)
+        usable, tb = self._layout(what, usable, tail)
         rs, st = self.engine.commit_poseidon_chain(hs, par, recs, usable, tb)
         return {"handle": None if rs is None else int(rs.handle),
                 "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments], **st}
@@ -1182,28 +1122,8 @@ class Client:
         data and the argument is the caller's gates plus the range lookups of words and carries."""
         what = "worker_commit_sha256"
         hs = _handles(input_handles)
-        try:
-            recs = []
-            for un in units:
-                if not isinstance(un, dict):
-                    raise ValueError(f"a unit is an object: {un!r}")
-                rec = dict(un)
-                for name in ("state", "msg"):
-                    if isinstance(rec.get(name), (list, tuple)):
-                        rec[name] = [tuple(v) if isinstance(v, (list, tuple)) else v for v in rec[name]]
-                recs.append(rec)
-        except (TypeError, ValueError, IndexError, KeyError) as e:
-            raise codec.CodecError(f"{what}: units must be a list of objects: {e!r}") from e
-        if not recs:
-            raise codec.CodecError(f"{what}: units must not be empty")
-        if usable is None:
-            if tail:
-                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
-            tb = []
-        else:
-            usable, tb = self._blind(what, usable, tail)
-            if usable == 0:
-                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        recs = self._unit_objects(what, units, ("state", "msg"))
+        usable, tb = self._layout(what, usable, tail)
         rs, st = self.engine.commit_sha256(hs, recs, usable, tb)
         return {"handle": None if rs is None else int(rs.handle),
                 "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments], **st}
@@ -1229,27 +1149,8 @@ class Client:
         range lookups of the lanes."""
         what = "worker_commit_keccak"
         hs = _handles(input_handles)
-        try:
-            recs = []
-            for un in units:
-                if not isinstance(un, dict):
-                    raise ValueError(f"a unit is an object: {un!r}")
-                rec = dict(un)
-                if isinstance(rec.get("in"), (list, tuple)):
-                    rec["in"] = [tuple(v) if isinstance(v, (list, tuple)) else v for v in rec["in"]]
-                recs.append(rec)
-        except (TypeError, ValueError, IndexError, KeyError) as e:
-            raise codec.CodecError(f"{what}: units must be a list of objects: {e!r}") from e
-        if not recs:
-            raise codec.CodecError(f"{what}: units must not be empty")
-        if usable is None:
-            if tail:
-                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
-            tb = []
-        else:
-            usable, tb = self._blind(what, usable, tail)
-            if usable == 0:
-                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        recs = self._unit_objects(what, units, ("in",))
+        usable, tb = self._layout(what, usable, tail)
         rs, st = self.engine.commit_keccak(hs, recs, usable, tb)
         return {"handle": None if rs is None else int(rs.handle),
                 "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments], **st}
@@ -1276,29 +1177,10 @@ class Client:
         carry gates over them plus the range lookups of the limbs."""
         what = "worker_commit_ec"
         hs = _handles(input_handles)
-        try:
-            recs = []
-            for un in units:
-                if not isinstance(un, dict):
-                    raise ValueError(f"a unit is an object: {un!r}")
-                rec = dict(un)
-                if isinstance(rec.get("b"), list):
-                    rec["b"] = tuple(rec["b"])
-                recs.append(rec)
-        except (TypeError, ValueError, IndexError, KeyError) as e:
-            raise codec.CodecError(f"{what}: units must be a list of objects: {e!r}") from e
-        if not recs:
-            raise codec.CodecError(f"{what}: units must not be empty")
+        recs = self._unit_objects(what, units, slots=("b",))
         if not isinstance(curve, dict):
             raise codec.CodecError(f"{what}: curve must be an object with bits, limbs, p and a")
-        if usable is None:
-            if tail:
-                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
-            tb = []
-        else:
-            usable, tb = self._blind(what, usable, tail)
-            if usable == 0:
-                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        usable, tb = self._layout(what, usable, tail)
         rs, st = self.engine.commit_ec(hs, dict(curve), recs, usable, tb)
         return {"handle": None if rs is None else int(rs.handle),
                 "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments], **st}
@@ -1323,30 +1205,10 @@ class Client:
         proof: the columns are prover data and the argument is the caller's two addition gates under the op-code's selector."""
         what = "worker_commit_edwards"
         hs = _handles(input_handles)
-        try:
-            recs = []
-            for un in units:
-                if not isinstance(un, dict):
-                    raise ValueError(f"a unit is an object: {un!r}")
-                rec = dict(un)
-                for k in ("x1", "y1", "x2", "y2", "px", "py"):
-                    if isinstance(rec.get(k), list):
-                        rec[k] = tuple(rec[k])
-                recs.append(rec)
-        except (TypeError, ValueError, IndexError, KeyError) as e:
-            raise codec.CodecError(f"{what}: units must be a list of objects: {e!r}") from e
-        if not recs:
-            raise codec.CodecError(f"{what}: units must not be empty")
+        recs = self._unit_objects(what, units, slots=("x1", "y1", "x2", "y2", "px", "py"))
         if not isinstance(curve, dict):
             raise codec.CodecError(f"{what}: curve must be an object with a and d")
-        if usable is None:
-            if tail:
-                raise codec.CodecError(f"{what}: a tail needs usable (null: all rows are read)")
-            tb = []
-        else:
-            usable, tb = self._blind(what, usable, tail)
-            if usable == 0:
-                raise codec.CodecError(f"{what}: usable must be in [1, T - 1] (null: all rows are read)")
+        usable, tb = self._layout(what, usable, tail)
         rs, st = self.engine.commit_edwards(hs, dict(curve), recs, usable, tb)
         return {"handle": None if rs is None else int(rs.handle),
                 "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments], **st}

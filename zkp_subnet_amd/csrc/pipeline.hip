@@ -1062,6 +1062,61 @@ static int stats_finish(kzg_ctx* ctx, LaneHold& H, uint32_t i, Cols& F, uint32_t
     return KZG_OK;
 }
 
+// ---- the unit builders' layer over Cols / Sources (rows_poseidon_dev .. rows_edwards_dev): a call is a list of units, every
+// unit writes its columns side by side behind the sources and leaves a few runs of n_units u64 statistics.  A builder fills its
+// kernel's table and Sources, then: units_workspace -- sources_transform -- [its constants] -- units_stats_clear --
+// assign_outputs -- its launch -- units_finish.  Every call therefore has, around the steps in its builder's own table: one
+// launch_fr_ntt per distinct source row named; per output row, with `usable` only, one launch_sort_tail, and one row_to_coeffs
+// straight into dst; ONE multi_msms_finish pass of n_out scalar sets.
+
+// The workspace: the S.nd source vectors at *src, the n_out output vectors at *outv, `extra` bytes behind them
+static int units_workspace(kzg_ctx* ctx, Lane& A, const Cols& F, const Sources& S, uint32_t n_out, size_t extra, uint32_t** src,
+                           uint32_t** outv) {
+    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_out) * F.T * 32 + extra));
+    *src = A.qext.as<uint32_t>();
+    *outv = *src + S.nd * F.vw;
+    return KZG_OK;
+}
+// the statistics in the record: `zero` runs of counts, then `none` runs of first rows (all ones: the builder's NONE)
+static uint64_t* units_stats(const Cols& F) { return reinterpret_cast<uint64_t*>(F.rec + MR_EVAL + CNT_OFF); }
+static int units_stats_clear(kzg_ctx* ctx, Lane& A, uint64_t* st, uint32_t n_units, uint32_t zero, uint32_t none) {
+    HIPCHK(ctx, hipMemsetAsync(st, 0, 8 * (size_t)zero * n_units, A.stream));
+    HIPCHK(ctx, hipMemsetAsync(st + zero * n_units, 0xff, 8 * (size_t)none * n_units, A.stream));
+    return KZG_OK;
+}
+// tab.u[u].out for every unit that commits, in unit order.  commits(u): the number of vectors unit u commits (0: a check);
+// zero_first(u): the kernel does not write every row of them
+template <class Tab, class Commits, class ZeroFirst>
+static int assign_outputs(kzg_ctx* ctx, Lane& A, const Cols& F, Tab& tab, uint32_t n_units, uint32_t* outv, Commits commits,
+                          ZeroFirst zero_first) {
+    for (uint32_t u = 0, c = 0; u < n_units; u++) {
+        const uint32_t k = commits(u);
+        if (!k) continue;
+        tab.u[u].out = outv + c * F.vw;
+        if (zero_first(u)) HIPCHK(ctx, hipMemsetAsync(outv + c * F.vw, 0, (size_t)k * F.T * 32, A.stream));
+        c += k;
+    }
+    return KZG_OK;
+}
+// every output vector into the new set, ONE MSM pass, the `bytes` bytes of statistics out
+static int units_finish(kzg_ctx* ctx, LaneHold& H, uint32_t i, Cols& F, uint32_t* outv, uint32_t n_out, uint32_t bytes,
+                        uint8_t* out_c48, uint64_t* out_stats) {
+    for (uint32_t c = 0; c < n_out; c++)
+        if (int rc = emit_column(ctx, H.L(), F, outv + c * F.vw, c)) return rc;
+    const uint8_t* stats;
+    if (int rc = stats_finish(ctx, H, i, F, n_out, bytes, out_c48, &stats)) return rc;
+    memcpy(out_stats, stats, bytes);
+    return KZG_OK;
+}
+// a unit's own list of distinct vectors (sha256, keccak): the place of vector d in ld[0 .. n_ld), appended when it is new, so
+// that a cell is loaded and counted once
+static uint8_t unit_load_slot(uint8_t* ld, uint32_t& n_ld, uint8_t d) {
+    uint32_t k = 0;
+    while (k < n_ld && ld[k] != d) k++;
+    if (k == n_ld) ld[n_ld++] = d;
+    return (uint8_t)k;
+}
+
 // The sorted columns (kzg_rows_commit_sorted): a set built FROM sets, the second side of a shuffle whose first side is these
 // columns.  All w columns of a row travel together, so the w columns are transformed into w vectors of T in the lane's quotient
 // workspace; behind them lie the n_keys key vectors (the key columns' canonical integers: fr_sort.hip) and, in the staging
@@ -1519,13 +1574,9 @@ int rows_wide_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, u
 // The Poseidon permutation columns (kzg_rows_commit_poseidon), in the builders' frame, with checks as rows_expr_dev has them.
 // Each DISTINCT source row (by device pointer) that some unit reads or expects is transformed forward once.
 //   step                      launches                         per call
-//   forward transforms        launch_fr_ntt                    one per distinct source row named
 //   constants                 one host-to-device copy          rc, M and the immediates as words, behind the vectors
 //   zero the trace columns    hipMemsetAsync                   one per ROUNDS unit
 //   every unit                launch_poseidon (k_fr_poseidon<t>) ONE, grid y = unit
-//   tail                      launch_sort_tail                 one per output row, with `usable` only
-//   inverse transform         row_to_coeffs                    one per output row, straight into dst
-//   commit                    multi_msms_finish                ONE pass of n_out scalar sets
 // The mismatch count and the first mismatching row of every unit are u64 words behind the first two evaluation slots of the
 // record (the layout of rows_expr_dev) and come back in the copy behind the MSM.  With n_out = 0 (checks alone) nothing is
 // transformed back and no MSM runs.  Workspace: distinct sources + n_out vectors of T, and the constants.
@@ -1533,6 +1584,17 @@ static void poseidon_words(uint32_t w[8], const uint8_t* be32) {
     for (int i = 0; i < 8; i++)
         w[i] = ((uint32_t)be32[28 - 4 * i] << 24) | ((uint32_t)be32[29 - 4 * i] << 16) | ((uint32_t)be32[30 - 4 * i] << 8) |
                be32[31 - 4 * i];
+}
+// rc, M and every unit's t immediates as words, in the order of poseidon_cst_words (both Poseidon builders)
+template <class Unit>
+static std::vector<uint32_t> poseidon_constants(const kzg_poseidon_params* params, uint32_t n_units, const Unit* units) {
+    const uint32_t t = params->t, R = params->full + params->partial;
+    std::vector<uint32_t> cst(poseidon_cst_words(t, R, n_units), 0);
+    for (uint32_t k = 0; k < t * R; k++) poseidon_words(&cst[8 * k], params->rc_be32 + 32 * (size_t)k);
+    for (uint32_t k = 0; k < t * t; k++) poseidon_words(&cst[8 * (t * R + k)], params->mds_be32 + 32 * (size_t)k);
+    for (uint32_t u = 0; u < n_units; u++)
+        for (uint32_t j = 0; j < t; j++) poseidon_words(&cst[8 * (t * R + t * t + u * t + j)], units[u].imm_be32[j]);
+    return cst;
 }
 int rows_poseidon_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const kzg_poseidon_params* params,
                       uint32_t n_units, const kzg_poseidon_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst,
@@ -1554,10 +1616,8 @@ int rows_poseidon_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& input
     tab.full = params->full;
     tab.partial = params->partial;
     tab.n_units = n_units;
-    const uint32_t cw = poseidon_cst_words(t, R, n_units);
-    std::vector<uint32_t> cst(cw, 0);                 // (lives until multi_msms_finish has waited for the stream)
-    for (uint32_t k = 0; k < t * R; k++) poseidon_words(&cst[8 * k], params->rc_be32 + 32 * (size_t)k);
-    for (uint32_t k = 0; k < t * t; k++) poseidon_words(&cst[8 * (t * R + k)], params->mds_be32 + 32 * (size_t)k);
+    const std::vector<uint32_t> cst = poseidon_constants(params, n_units, units);   // (lives until the MSM pass has waited)
+    const uint32_t cw = (uint32_t)cst.size();
     for (uint32_t u = 0; u < n_units; u++) {
         const kzg_poseidon_unit& in = units[u];
         PosUnit& U = tab.u[u];
@@ -1565,53 +1625,39 @@ int rows_poseidon_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& input
         U.mode = in.mode;
         U.period = in.period;
         memset(U.col, POS_NO_COL, sizeof(U.col));
-        for (uint32_t j = 0; j < t; j++) {
+        for (uint32_t j = 0; j < t; j++)
             U.slot[j] = in.in[j] == KZG_POSEIDON_IMM ? (uint8_t)POS_IMM : (uint8_t)S.slot_of(inputs.r[in.in[j]]);
-            poseidon_words(&cst[8 * (t * R + t * t + u * t + j)], in.imm_be32[j]);
-        }
         for (uint32_t c = 0; c < in.n_out; c++) {
             U.col[in.out[c]] = (uint8_t)c;
             if (check) U.exp[c] = (uint8_t)S.slot_of(inputs.r[in.expect[c]]);
         }
     }
-    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_out) * T * 32 + (size_t)cw * 4));
-    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + S.nd * vw, *cdev = outv + n_out * vw;
-    uint8_t* rec = F.rec;
-    uint64_t* st = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF);
+    uint32_t *src, *outv;
+    if (int rc = units_workspace(ctx, A, F, S, n_out, (size_t)cw * 4, &src, &outv)) return rc;
+    uint32_t* cdev = outv + n_out * vw;
+    uint64_t* st = units_stats(F);
     sources_transform(ctx, A, F, S, src);
     HIPCHK(ctx, hipMemcpyAsync(cdev, cst.data(), (size_t)cw * 4, hipMemcpyHostToDevice, A.stream));
-    HIPCHK(ctx, hipMemsetAsync(st, 0, 8 * (size_t)n_units, A.stream));
-    HIPCHK(ctx, hipMemsetAsync(st + n_units, 0xff, 8 * (size_t)n_units, A.stream));   // KZG_POSEIDON_NONE
+    if (int rc = units_stats_clear(ctx, A, st, n_units, 1, 1)) return rc;
     tab.src = src;
     tab.cst = cdev;
-    for (uint32_t u = 0, c = 0; u < n_units; u++) {
-        if (units[u].flags & KZG_POSEIDON_CHECK) continue;
-        tab.u[u].out = outv + c * vw;
-        if (units[u].mode == KZG_POSEIDON_ROUNDS) HIPCHK(ctx, hipMemsetAsync(outv + c * vw, 0, (size_t)t * T * 32, A.stream));
-        c += units[u].n_out;
-    }
+    if (int rc = assign_outputs(
+            ctx, A, F, tab, n_units, outv, [&](uint32_t u) { return units[u].flags & KZG_POSEIDON_CHECK ? 0u : units[u].n_out; },
+            [&](uint32_t u) { return units[u].mode == KZG_POSEIDON_ROUNDS; }))   // (a ROUNDS unit commits n_out = t columns)
+        return rc;
     {
         Span sp(ctx, A, KZG_T_POLY);
         launch_poseidon(A.stream, tab, T, n, st);
     }
-    for (uint32_t c = 0; c < n_out; c++)
-        if (int rc = emit_column(ctx, A, F, outv + c * vw, c)) return rc;
-    const uint8_t* stats;
-    if (int rc = stats_finish(ctx, H, i, F, n_out, 16 * n_units, out_c48, &stats)) return rc;
-    memcpy(out_stats, stats, 16 * (size_t)n_units);
-    return KZG_OK;
+    return units_finish(ctx, H, i, F, outv, n_out, 16 * n_units, out_c48, out_stats);
 }
 
 // The Poseidon sponge and Merkle-path chains (kzg_rows_commit_poseidon_chain), in the builders' frame, with checks as
 // rows_poseidon_dev has them.  Each DISTINCT source row (by device pointer) that some unit reads is transformed forward once.
 //   step                      launches                         per call
-//   forward transforms        launch_fr_ntt                    one per distinct source row named
 //   constants                 one host-to-device copy          rc, M and the immediates as words, behind the vectors
 //   zero the columns          hipMemsetAsync                   one per committing unit
 //   every unit                launch_poseidon_chain (k_fr_poseidon_chain<t>) ONE, grid y = unit
-//   tail                      launch_sort_tail                 one per output row, with `usable` only
-//   inverse transform         row_to_coeffs                    one per output row, straight into dst
-//   commit                    multi_msms_finish                ONE pass of n_out scalar sets
 // The five statistics of every unit are u64 words behind the first two evaluation slots of the record and come back in the copy
 // behind the MSM.  With n_out = 0 (checks alone) nothing is transformed back and no MSM runs.  Workspace: distinct sources + n_out
 // vectors of T, and the constants.
@@ -1635,10 +1681,8 @@ int rows_poseidon_chain_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab&
     tab.full = params->full;
     tab.partial = params->partial;
     tab.n_units = n_units;
-    const uint32_t cw = poseidon_cst_words(t, R, n_units);
-    std::vector<uint32_t> cst(cw, 0);                 // (lives until multi_msms_finish has waited for the stream)
-    for (uint32_t k = 0; k < t * R; k++) poseidon_words(&cst[8 * k], params->rc_be32 + 32 * (size_t)k);
-    for (uint32_t k = 0; k < t * t; k++) poseidon_words(&cst[8 * (t * R + k)], params->mds_be32 + 32 * (size_t)k);
+    const std::vector<uint32_t> cst = poseidon_constants(params, n_units, units);   // (lives until the MSM pass has waited)
+    const uint32_t cw = (uint32_t)cst.size();
     auto slot = [&](uint32_t row) { return row == KZG_POSEIDON_CHAIN_ABSENT ? (uint8_t)PCH_NONE : (uint8_t)S.slot_of(inputs.r[row]); };
     for (uint32_t u = 0; u < n_units; u++) {
         const kzg_poseidon_chain_unit& in = units[u];
@@ -1648,10 +1692,7 @@ int rows_poseidon_chain_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab&
         U.period = in.period;
         memset(U.col, PCH_NONE, sizeof(U.col));
         memset(U.slot, PCH_NONE, sizeof(U.slot));
-        for (uint32_t j = 0; j < t; j++) {
-            U.slot[j] = slot(in.in[j]);               // (KZG_POSEIDON_IMM is KZG_POSEIDON_CHAIN_ABSENT's value: POS_IMM)
-            poseidon_words(&cst[8 * (t * R + t * t + u * t + j)], in.imm_be32[j]);
-        }
+        for (uint32_t j = 0; j < t; j++) U.slot[j] = slot(in.in[j]);   // (KZG_POSEIDON_IMM is KZG_POSEIDON_CHAIN_ABSENT's value)
         if (in.layout == KZG_POSEIDON_CHAIN_FLAT)
             for (uint32_t c = 0; c < in.n_out; c++) U.col[in.out[c]] = (uint8_t)c;
         U.start = slot(in.start);
@@ -1659,43 +1700,30 @@ int rows_poseidon_chain_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab&
         U.exp = slot(in.expect);
         U.digest = in.digest == KZG_POSEIDON_CHAIN_ABSENT ? (uint8_t)PCH_NONE : (uint8_t)in.digest;
     }
-    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_out) * T * 32 + (size_t)cw * 4));
-    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + S.nd * vw, *cdev = outv + n_out * vw;
-    uint8_t* rec = F.rec;
-    uint64_t* st = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF);
+    uint32_t *src, *outv;
+    if (int rc = units_workspace(ctx, A, F, S, n_out, (size_t)cw * 4, &src, &outv)) return rc;
+    uint32_t* cdev = outv + n_out * vw;
+    uint64_t* st = units_stats(F);
     sources_transform(ctx, A, F, S, src);
     HIPCHK(ctx, hipMemcpyAsync(cdev, cst.data(), (size_t)cw * 4, hipMemcpyHostToDevice, A.stream));
-    HIPCHK(ctx, hipMemsetAsync(st, 0, 24 * (size_t)n_units, A.stream));
-    HIPCHK(ctx, hipMemsetAsync(st + 3 * n_units, 0xff, 16 * (size_t)n_units, A.stream));   // KZG_POSEIDON_NONE
+    if (int rc = units_stats_clear(ctx, A, st, n_units, 3, 2)) return rc;
     tab.src = src;
     tab.cst = cdev;
-    for (uint32_t u = 0, c = 0; u < n_units; u++) {
-        if (!units[u].n_out) continue;                // (a check)
-        tab.u[u].out = outv + c * vw;
-        HIPCHK(ctx, hipMemsetAsync(outv + c * vw, 0, (size_t)units[u].n_out * T * 32, A.stream));
-        c += units[u].n_out;
-    }
+    if (int rc = assign_outputs(
+            ctx, A, F, tab, n_units, outv, [&](uint32_t u) { return units[u].n_out; }, [](uint32_t) { return true; }))   // (0: a check)
+        return rc;
     {
         Span sp(ctx, A, KZG_T_POLY);
         launch_poseidon_chain(A.stream, tab, T, n, st);
     }
-    for (uint32_t c = 0; c < n_out; c++)
-        if (int rc = emit_column(ctx, A, F, outv + c * vw, c)) return rc;
-    const uint8_t* stats;
-    if (int rc = stats_finish(ctx, H, i, F, n_out, 40 * n_units, out_c48, &stats)) return rc;
-    memcpy(out_stats, stats, 40 * (size_t)n_units);
-    return KZG_OK;
+    return units_finish(ctx, H, i, F, outv, n_out, 40 * n_units, out_c48, out_stats);
 }
 
 // The SHA-256 compression columns (kzg_rows_commit_sha256), in the builders' frame, with checks as rows_poseidon_dev has them.
 // Each DISTINCT source row (by device pointer) that some unit reads or expects is transformed forward once.
 //   step                      launches                         per call
-//   forward transforms        launch_fr_ntt                    one per distinct source row named
 //   zero the trace columns    hipMemsetAsync                   one per ROUNDS unit
 //   every unit                launch_sha256 (k_fr_sha256)      ONE, grid y = unit
-//   tail                      launch_sort_tail                 one per output row, with `usable` only
-//   inverse transform         row_to_coeffs                    one per output row, straight into dst
-//   commit                    multi_msms_finish                ONE pass of n_out scalar sets
 // The five statistics of every unit are u64 words behind the first two evaluation slots of the record and come back in the copy
 // behind the MSM.  With n_out = 0 (checks alone) nothing is transformed back and no MSM runs.  The standard initial value is
 // written into the unit's immediates here.  Workspace: distinct sources + n_out vectors of T.
@@ -1737,47 +1765,30 @@ int rows_sha256_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs,
             const uint32_t row = j < 8 ? in.state[j] : in.msg[j - 8];
             if (j >= 8) U.imm[j] = in.msg_imm[j - 8];
             if (row == KZG_SHA256_IMM) continue;
-            const uint8_t d = (uint8_t)S.slot_of(inputs.r[row]);
-            uint32_t k = 0;
-            while (k < U.n_ld && U.ld[k] != d) k++;
-            if (k == U.n_ld) U.ld[U.n_ld++] = d;
-            U.slot[j] = (uint8_t)k;
+            U.slot[j] = unit_load_slot(U.ld, U.n_ld, (uint8_t)S.slot_of(inputs.r[row]));
         }
     }
-    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_out) * T * 32 + 32));   // (+ 32: a call of immediates alone and checks has no vector)
-    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + S.nd * vw;
-    uint64_t* st = reinterpret_cast<uint64_t*>(F.rec + MR_EVAL + CNT_OFF);
+    uint32_t *src, *outv;   // (+ 32: a call of immediates alone and checks has no vector)
+    if (int rc = units_workspace(ctx, A, F, S, n_out, 32, &src, &outv)) return rc;
+    uint64_t* st = units_stats(F);
     sources_transform(ctx, A, F, S, src);
-    HIPCHK(ctx, hipMemsetAsync(st, 0, 24 * (size_t)n_units, A.stream));
-    HIPCHK(ctx, hipMemsetAsync(st + 3 * n_units, 0xff, 16 * (size_t)n_units, A.stream));   // KZG_SHA256_NONE
+    if (int rc = units_stats_clear(ctx, A, st, n_units, 3, 2)) return rc;
     tab.src = src;
-    for (uint32_t u = 0, c = 0; u < n_units; u++) {
-        if (units[u].flags & KZG_SHA256_CHECK) continue;
-        tab.u[u].out = outv + c * vw;
-        if (units[u].mode == KZG_SHA256_ROUNDS)
-            HIPCHK(ctx, hipMemsetAsync(outv + c * vw, 0, (size_t)units[u].n_out * T * 32, A.stream));
-        c += units[u].n_out;
-    }
+    if (int rc = assign_outputs(
+            ctx, A, F, tab, n_units, outv, [&](uint32_t u) { return units[u].flags & KZG_SHA256_CHECK ? 0u : units[u].n_out; },
+            [&](uint32_t u) { return units[u].mode == KZG_SHA256_ROUNDS; }))
+        return rc;
     {
         Span sp(ctx, A, KZG_T_POLY);
         launch_sha256(A.stream, tab, T, n, st);
     }
-    for (uint32_t c = 0; c < n_out; c++)
-        if (int rc = emit_column(ctx, A, F, outv + c * vw, c)) return rc;
-    const uint8_t* stats;
-    if (int rc = stats_finish(ctx, H, i, F, n_out, 40 * n_units, out_c48, &stats)) return rc;
-    memcpy(out_stats, stats, 40 * (size_t)n_units);
-    return KZG_OK;
+    return units_finish(ctx, H, i, F, outv, n_out, 40 * n_units, out_c48, out_stats);
 }
 
 // The Keccak-f[1600] permutation columns (kzg_rows_commit_keccak), in the builders' frame, step for step as rows_sha256_dev:
 //   step                      launches                         per call
-//   forward transforms        launch_fr_ntt                    one per distinct source row named
 //   zero the trace columns    hipMemsetAsync                   one per ROUNDS unit
 //   every unit                launch_keccak (k_fr_keccak)      ONE, grid y = unit
-//   tail                      launch_sort_tail                 one per output row, with `usable` only
-//   inverse transform         row_to_coeffs                    one per output row, straight into dst
-//   commit                    multi_msms_finish                ONE pass of n_out scalar sets
 // The five statistics of every unit are u64 words behind the first two evaluation slots of the record and come back in the copy
 // behind the MSM.  With n_out = 0 (checks alone) nothing is transformed back and no MSM runs.  A cell that several absorbed
 // lanes of a ROUNDS unit read (a repeated message row, the start column among the message rows) is marked here so that one
@@ -1825,46 +1836,29 @@ int rows_keccak_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs,
         for (uint32_t j = 0; j < 25; j++) {   // the unit's own list of distinct vectors: a cell is loaded and counted once
             U.imm[j] = in.imm[j];
             if (in.in[j] == KZG_KECCAK_IMM) continue;
-            const uint8_t d = (uint8_t)S.slot_of(inputs.r[in.in[j]]);
-            uint32_t k = 0;
-            while (k < U.n_ld && U.ld[k] != d) k++;
-            if (k == U.n_ld) U.ld[U.n_ld++] = d;
-            U.slot[j] = (uint8_t)k;
+            U.slot[j] = unit_load_slot(U.ld, U.n_ld, (uint8_t)S.slot_of(inputs.r[in.in[j]]));
         }
     }
-    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_out) * T * 32 + 32));   // (+ 32: a call of immediates alone and checks has no vector)
-    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + S.nd * vw;
-    uint64_t* st = reinterpret_cast<uint64_t*>(F.rec + MR_EVAL + CNT_OFF);
+    uint32_t *src, *outv;   // (+ 32: a call of immediates alone and checks has no vector)
+    if (int rc = units_workspace(ctx, A, F, S, n_out, 32, &src, &outv)) return rc;
+    uint64_t* st = units_stats(F);
     sources_transform(ctx, A, F, S, src);
-    HIPCHK(ctx, hipMemsetAsync(st, 0, 24 * (size_t)n_units, A.stream));
-    HIPCHK(ctx, hipMemsetAsync(st + 3 * n_units, 0xff, 16 * (size_t)n_units, A.stream));   // KZG_KECCAK_NONE
+    if (int rc = units_stats_clear(ctx, A, st, n_units, 3, 2)) return rc;
     tab.src = src;
-    for (uint32_t u = 0, c = 0; u < n_units; u++) {
-        if (units[u].flags & KZG_KECCAK_CHECK) continue;
-        tab.u[u].out = outv + c * vw;
-        if (units[u].mode == KZG_KECCAK_ROUNDS)
-            HIPCHK(ctx, hipMemsetAsync(outv + c * vw, 0, (size_t)units[u].n_out * T * 32, A.stream));
-        c += units[u].n_out;
-    }
+    if (int rc = assign_outputs(
+            ctx, A, F, tab, n_units, outv, [&](uint32_t u) { return units[u].flags & KZG_KECCAK_CHECK ? 0u : units[u].n_out; },
+            [&](uint32_t u) { return units[u].mode == KZG_KECCAK_ROUNDS; }))
+        return rc;
     {
         Span sp(ctx, A, KZG_T_POLY);
         launch_keccak(A.stream, tab, T, n, st);
     }
-    for (uint32_t c = 0; c < n_out; c++)
-        if (int rc = emit_column(ctx, A, F, outv + c * vw, c)) return rc;
-    const uint8_t* stats;
-    if (int rc = stats_finish(ctx, H, i, F, n_out, 40 * n_units, out_c48, &stats)) return rc;
-    memcpy(out_stats, stats, 40 * (size_t)n_units);
-    return KZG_OK;
+    return units_finish(ctx, H, i, F, outv, n_out, 40 * n_units, out_c48, out_stats);
 }
 
 // The non-native elliptic-curve columns (kzg_rows_commit_ec), in the builders' frame, step for step as rows_keccak_dev:
 //   step                      launches                         per call
-//   forward transforms        launch_fr_ntt                    one per distinct source row named
 //   every unit                launch_ec (k_fr_ec)              ONE, grid y = unit
-//   tail                      launch_sort_tail                 one per output row, with `usable` only
-//   inverse transform         row_to_coeffs                    one per output row, straight into dst
-//   commit                    multi_msms_finish                ONE pass of n_out scalar sets
 // The seven statistics of every unit are u64 words behind the first two evaluation slots of the record and come back in the
 // copy behind the MSM.  With n_out = 0 (checks alone) nothing is transformed back and no MSM runs.  The curve's two derived
 // constants are computed here, on the host, once per call: -p^-1 mod 2^32 by Newton's iteration and 2^512 mod p by 512
@@ -1931,39 +1925,29 @@ int rows_ec_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, con
                 if (in.cols >> k & 1u)
                     for (uint32_t l = 0; l < L; l++) U.exp[k][l] = (uint8_t)S.slot_of(inputs.r[in.expect[k] + l]);
     }
-    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_out) * T * 32 + 32));
-    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + S.nd * vw;
-    uint64_t* st = reinterpret_cast<uint64_t*>(F.rec + MR_EVAL + CNT_OFF);
+    uint32_t *src, *outv;
+    if (int rc = units_workspace(ctx, A, F, S, n_out, 32, &src, &outv)) return rc;
+    uint64_t* st = units_stats(F);
     sources_transform(ctx, A, F, S, src);
-    HIPCHK(ctx, hipMemsetAsync(st, 0, 32 * (size_t)n_units, A.stream));
-    HIPCHK(ctx, hipMemsetAsync(st + 4 * n_units, 0xff, 24 * (size_t)n_units, A.stream));   // KZG_EC_NONE
+    if (int rc = units_stats_clear(ctx, A, st, n_units, 4, 3)) return rc;
     tab.src = src;
-    for (uint32_t u = 0, c = 0; u < n_units; u++) {
-        if (units[u].flags & KZG_EC_CHECK) continue;
-        tab.u[u].out = outv + c * vw;
-        c += (uint32_t)__builtin_popcount(units[u].cols) * L;
-    }
+    if (int rc = assign_outputs(
+            ctx, A, F, tab, n_units, outv,
+            [&](uint32_t u) { return units[u].flags & KZG_EC_CHECK ? 0u : (uint32_t)__builtin_popcount(units[u].cols) * L; },
+            [](uint32_t) { return false; }))
+        return rc;
     {
         Span sp(ctx, A, KZG_T_POLY);
         launch_ec(A.stream, tab, T, n, st);
     }
-    for (uint32_t c = 0; c < n_out; c++)
-        if (int rc = emit_column(ctx, A, F, outv + c * vw, c)) return rc;
-    const uint8_t* stats;
-    if (int rc = stats_finish(ctx, H, i, F, n_out, 56 * n_units, out_c48, &stats)) return rc;
-    memcpy(out_stats, stats, 56 * (size_t)n_units);
-    return KZG_OK;
+    return units_finish(ctx, H, i, F, outv, n_out, 56 * n_units, out_c48, out_stats);
 }
 
 // The native twisted-Edwards columns (kzg_rows_commit_edwards), in the builders' frame:
 //   step                      launches                         per call
-//   forward transforms        launch_fr_ntt                    one per distinct source row named
 //   every unit, phase 1       launch_edwards (k_edwards)       ONE, grid y = unit: numerators or projective X, Y, and Q
 //   the denominators          launch_fr_batch_inv              ONE, over the (units with output) T elements of Q
 //   finish                    launch_edwards_finish            ONE, grid y = output row: out <- out W
-//   tail                      launch_sort_tail                 one per output row, with `usable` only
-//   inverse transform         row_to_coeffs                    one per output row, straight into dst
-//   commit                    multi_msms_finish                ONE pass of n_out scalar sets
 // The outputs lie side by side behind the sources in the order of the set (unit by unit, then the unit's out order), so output
 // row c is vector c; behind them the denominators Q, one slice of T per unit with output, and the inversion's result W of the
 // same shape.  k_edwards writes every element of Q (Montgomery 1 on an exceptional row and on the rows >= n), so the inversion
@@ -2024,14 +2008,15 @@ int rows_edwards_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs
             col[u][in.out_order[j]] = c++ + 1;   // (0: the name is not an output)
         }
     }
-    HIPCHK(ctx, A.qext.ensure(((size_t)S.nd + n_out + 2 * n_q) * T * 32 + 32));
+    uint32_t *src, *outv;
+    if (int rc = units_workspace(ctx, A, F, S, n_out, 2 * (size_t)n_q * T * 32 + 32, &src, &outv)) return rc;
     if (n_q) {
         HIPCHK(ctx, A.hbuf.ensure(poly_level_words(n_q * T) * 4));
         HIPCHK(ctx, A.hnext.ensure(poly_level_words(n_q * T) * 4));
     }
-    uint32_t *src = A.qext.as<uint32_t>(), *outv = src + S.nd * vw, *Q = outv + n_out * vw, *W = Q + n_q * vw;
+    uint32_t *Q = outv + n_out * vw, *W = Q + n_q * vw;
     uint8_t* rec = F.rec;
-    uint64_t* st = reinterpret_cast<uint64_t*>(rec + MR_EVAL + CNT_OFF);
+    uint64_t* st = units_stats(F);
     sources_transform(ctx, A, F, S, src);
     HIPCHK(ctx, hipMemsetAsync(rec + MR_EVAL, 0, CNT_OFF + 24 * (size_t)n_units, A.stream));
     HIPCHK(ctx, hipMemsetAsync(st + 3 * n_units, 0xff, 16 * (size_t)n_units, A.stream));   // KZG_EDWARDS_NONE
@@ -2053,14 +2038,10 @@ int rows_edwards_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs
             launch_edwards_finish(A.stream, fin, n_out, T, n);
         }
     }
-    for (uint32_t c = 0; c < n_out; c++)
-        if (int rc = emit_column(ctx, A, F, outv + c * vw, c)) return rc;
-    const uint8_t* stats;
-    if (int rc = stats_finish(ctx, H, i, F, n_out, 40 * n_units, out_c48, &stats)) return rc;
+    if (int rc = units_finish(ctx, H, i, F, outv, n_out, 40 * n_units, out_c48, out_stats)) return rc;
     uint32_t zf;
     memcpy(&zf, F.ev + 32, 4);
     if (n_q && zf) return fail(ctx, KZG_E_HIP, "edwards: the batched inversion met a zero behind k_edwards");
-    memcpy(out_stats, stats, 40 * (size_t)n_units);
     return KZG_OK;
 }
 

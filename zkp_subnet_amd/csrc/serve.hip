@@ -817,6 +817,82 @@ struct BuilderCall {
     uint64_t commit() { return n_out ? rows_insert(ctx, pend, i, n_out, T) : 0; }   // the new set's handle; 0: nothing committed
 };
 
+// ---- the unit builders (rows_poseidon .. rows_edwards): a call is 1 .. N units, each with a mode, slots that are a row index
+// or an immediate, an out / cols list and an optional expect that makes it a check; what they share around their unit loops.
+
+// The distinct rows the units of a call name, and the largest.  A call may read at most KZG_MAX_BATCH_OPEN distinct rows, so
+// one more than that is all that is ever held: past the capacity a new row is counted, not stored, and max_row goes on.
+struct SeenRows {
+    static constexpr uint32_t CAP = KZG_MAX_BATCH_OPEN + 1;
+    uint32_t n = 0, max_row = 0, rows[CAP];
+    void see(uint32_t row) {
+        max_row = std::max(max_row, row);
+        const uint32_t held = std::min(n, CAP);
+        uint32_t d = 0;
+        while (d < held && rows[d] != row) d++;
+        if (d < held) return;
+        if (n < CAP) rows[n] = row;
+        n++;
+    }
+    // the `count` rows from `first` (a wide value of ec); a row at or beyond 2^32 - 1 ends the run and fails the index check
+    void see_run(uint32_t first, uint32_t count) {
+        for (uint32_t l = 0; l < count; l++) {
+            const uint64_t row = (uint64_t)first + l;   // (cannot wrap a uint64)
+            if (row >= 0xffffffffull) {
+                max_row = 0xffffffffu;
+                return;
+            }
+            see((uint32_t)row);
+        }
+    }
+    bool too_many() const { return n > KZG_MAX_BATCH_OPEN; }
+};
+
+// One call of a unit builder: handles_ok() -- the builder's checks -- open() -- the device call, the statistics -- finish().
+// (Constructed behind the host's checks: a refused call touches no context.)
+struct UnitCall : BuilderCall {
+    RowTab it;                                // the input rows
+    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];     // the commitments, until the call can no longer fail
+    using BuilderCall::BuilderCall;
+    static int handles_ok(kzg_ctx* ctx, const char* what, uint32_t n_handles) {
+        if (n_handles == 0 || n_handles > KZG_MAX_BATCH_OPEN)
+            return fail(ctx, KZG_E_ARG, std::string(what) + ": the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+        return KZG_OK;
+    }
+    // begin; the refusal of a row beyond the input rows, in the builder's words (rows_named: whether the call names any); ready
+    // over the n_cols columns to commit in the column builders' layout
+    int open(uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, bool rows_named, uint32_t max_row, const char* row_why,
+             uint32_t n_cols, const kzg_derive_opts* opts) {
+        uint32_t ki = 0;
+        if (int rc = begin(what, expect_i, n_handles, handles, it, &ki)) return rc;
+        if (rows_named && max_row >= ki) return fail(ctx, KZG_E_ARG, std::string(what) + row_why);
+        return ready(n_cols, 32, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ);
+    }
+    uint64_t n_read() const { return blind ? blind->usable : T; }   // the rows the units read: usable, or T
+    void finish(uint8_t* out_commitments48, uint64_t* out_handle) {
+        if (n_out) memcpy(out_commitments48, c48, 48 * (size_t)n_out);
+        *out_handle = commit();
+    }
+};
+static const char ROW_WHY[] = ": a row must index the concatenated rows of the input sets";
+
+// The statistics of a unit builder come back as runs of n_units u64 words; run_of[k] is the run that feeds the caller's array
+// k, -1 for an array the builder fills itself
+static void stats_scatter(uint64_t* const* out, const int* run_of, int n_arrays, const uint64_t* stats, uint32_t n_units) {
+    for (int k = 0; k < n_arrays; k++)
+        if (run_of[k] >= 0) memcpy(out[k], stats + (size_t)run_of[k] * n_units, 8 * (size_t)n_units);
+}
+// ec and edwards: one run means mismatches on an add or div unit and unknown op-codes on a chain; the array of the other
+// meaning takes `none`
+static void stats_split(uint64_t* const* out, int run, int plain, int chained, uint64_t none, const uint64_t* stats,
+                        uint32_t n_units, const bool* chain) {
+    for (uint32_t u = 0; u < n_units; u++) {
+        const uint64_t v = stats[(size_t)run * n_units + u];
+        out[plain][u] = chain[u] ? none : v;
+        out[chained][u] = chain[u] ? v : none;
+    }
+}
+
 int rows_open(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_handles, const uint64_t* handles, uint32_t m,
               const uint8_t* points_be32, const uint32_t* masks, const uint8_t* gammas_be32, uint8_t* out_evals32,
               uint8_t* out_proofs48) {
@@ -1529,19 +1605,13 @@ int rows_poseidon(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, con
                   uint8_t* out_commitments48, uint64_t* out_perms, uint64_t* out_mismatch, uint64_t* out_first_mismatch,
                   uint64_t* out_handle) {
     if (!ctx || !input_handles || !out_perms || !out_mismatch || !out_first_mismatch || !out_handle) return KZG_E_ARG;
-    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
-        return fail(ctx, KZG_E_ARG, "poseidon: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (int rc = UnitCall::handles_ok(ctx, "poseidon", n_input_handles)) return rc;
     if (int rc = poseidon_params_check(ctx, "poseidon", params, n_units != 0 && n_units <= KZG_POSEIDON_MAX_UNITS && units,
                                        "n_units must be in [1, KZG_POSEIDON_MAX_UNITS]"))
         return rc;
     const uint32_t t = params->t, R = params->full + params->partial;
-    uint32_t n_out = 0, max_row = 0, n_seen = 0, seen[2 * KZG_POSEIDON_MAX_T * KZG_POSEIDON_MAX_UNITS];
-    auto see = [&](uint32_t row) {
-        max_row = std::max(max_row, row);
-        uint32_t d = 0;
-        while (d < n_seen && seen[d] != row) d++;
-        if (d == n_seen) seen[n_seen++] = row;
-    };
+    uint32_t n_out = 0;
+    SeenRows S;
     for (uint32_t u = 0; u < n_units; u++) {
         const kzg_poseidon_unit& U = units[u];
         if (U.mode != KZG_POSEIDON_ROW && U.mode != KZG_POSEIDON_ROUNDS)
@@ -1559,39 +1629,34 @@ int rows_poseidon(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, con
                 return fail(ctx, KZG_E_ARG, "poseidon: an out index must be below t (ROUNDS: out[j] = j)");
             if (taken >> U.out[c] & 1) return fail(ctx, KZG_E_ARG, "poseidon: an out index is repeated");
             taken |= 1u << U.out[c];
-            if (check) see(U.expect[c]);
+            if (check) S.see(U.expect[c]);
         }
         for (uint32_t j = 0; j < t; j++) {
             if (U.in[j] != KZG_POSEIDON_IMM) {
-                see(U.in[j]);
+                S.see(U.in[j]);
                 for (int b = 0; b < 32; b++)
                     if (U.imm_be32[j][b]) return fail(ctx, KZG_E_ARG, "poseidon: the immediate must be 0 beside a row");
             } else if (!fr_be32_canonical(U.imm_be32[j])) {
                 return fail(ctx, KZG_E_ARG, "poseidon: immediates must be canonical scalars (< r)");
             }
         }
-        if (n_seen > KZG_MAX_BATCH_OPEN)
+        if (S.too_many())
             return fail(ctx, KZG_E_ARG, "poseidon: a call reads at most KZG_MAX_BATCH_OPEN distinct input rows");
         n_out += check ? 0 : U.n_out;
     }
     if (n_out > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "poseidon: n_out, the committed columns of all units, must be at most KZG_MAX_BATCH_OPEN");
     if (n_out && !out_commitments48) return KZG_E_ARG;
-    BuilderCall C(ctx, "poseidon");
-    RowTab it;
-    uint32_t ki = 0;
-    if (int rc = C.begin("poseidon", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
-    if (n_seen && max_row >= ki) return fail(ctx, KZG_E_ARG, "poseidon: a row must index the concatenated rows of the input sets");
-    if (int rc = C.ready(n_out, 32, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ)) return rc;
-    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    UnitCall C(ctx, "poseidon");
+    if (int rc = C.open(expect_i, n_input_handles, input_handles, S.n != 0, S.max_row, ROW_WHY, n_out, opts)) return rc;
     uint64_t stats[2 * KZG_POSEIDON_MAX_UNITS];
-    if (int rc = rows_poseidon_dev(ctx, C.H, C.i, it, params, n_units, units, n_out, C.T, C.dst(), c48, stats, C.blind)) return rc;
-    if (n_out) memcpy(out_commitments48, c48, 48 * (size_t)n_out);
-    const uint64_t n = C.blind ? C.blind->usable : C.T;
+    if (int rc = rows_poseidon_dev(ctx, C.H, C.i, C.it, params, n_units, units, n_out, C.T, C.dst(), C.c48, stats, C.blind)) return rc;
+    const uint64_t n = C.n_read();
     for (uint32_t u = 0; u < n_units; u++) out_perms[u] = units[u].mode == KZG_POSEIDON_ROUNDS ? n / units[u].period : n;
-    memcpy(out_mismatch, stats, 8 * (size_t)n_units);
-    memcpy(out_first_mismatch, stats + n_units, 8 * (size_t)n_units);
-    *out_handle = C.commit();
+    static const int run_of[3] = {-1, 0, 1};   // the device's runs: mismatches, then their first rows
+    uint64_t* const out[3] = {out_perms, out_mismatch, out_first_mismatch};
+    stats_scatter(out, run_of, 3, stats, n_units);
+    C.finish(out_commitments48, out_handle);
     return KZG_OK;
 }
 
@@ -1605,19 +1670,13 @@ int rows_poseidon_chain(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handle
     for (int k = 0; k < 6; k++)
         if (!out_stats[k]) return KZG_E_ARG;
     auto bad = [&](const char* why) { return fail(ctx, KZG_E_ARG, std::string("poseidon_chain: ") + why); };
-    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
-        return bad("the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (int rc = UnitCall::handles_ok(ctx, "poseidon_chain", n_input_handles)) return rc;
     if (int rc = poseidon_params_check(ctx, "poseidon_chain", params, n_units != 0 && n_units <= KZG_POSEIDON_CHAIN_MAX_UNITS && units,
                                        "n_units must be in [1, KZG_POSEIDON_CHAIN_MAX_UNITS]"))
         return rc;
     const uint32_t t = params->t, R = params->full + params->partial, ABSENT = KZG_POSEIDON_CHAIN_ABSENT;
-    uint32_t n_out = 0, max_row = 0, n_seen = 0, seen[(KZG_POSEIDON_MAX_T + 3) * KZG_POSEIDON_CHAIN_MAX_UNITS];
-    auto see = [&](uint32_t row) {
-        max_row = std::max(max_row, row);
-        uint32_t d = 0;
-        while (d < n_seen && seen[d] != row) d++;
-        if (d == n_seen) seen[n_seen++] = row;
-    };
+    uint32_t n_out = 0;
+    SeenRows S;
     for (uint32_t u = 0; u < n_units; u++) {
         const kzg_poseidon_chain_unit& U = units[u];
         if (U.mode != KZG_POSEIDON_CHAIN_SPONGE && U.mode != KZG_POSEIDON_CHAIN_PATH)
@@ -1629,7 +1688,7 @@ int rows_poseidon_chain(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handle
         if (check) {
             if (U.layout || U.n_out) return bad("layout and n_out must be 0 beside KZG_POSEIDON_CHAIN_CHECK: a check commits nothing");
             if (U.expect == ABSENT) return bad("expect must be a row with KZG_POSEIDON_CHAIN_CHECK, not an immediate or absent");
-            see(U.expect);
+            S.see(U.expect);
         } else {
             if (U.expect != ABSENT) return bad("expect belongs to KZG_POSEIDON_CHAIN_CHECK (KZG_POSEIDON_CHAIN_ABSENT without)");
             if (U.layout != KZG_POSEIDON_CHAIN_TRACE && U.layout != KZG_POSEIDON_CHAIN_FLAT)
@@ -1654,18 +1713,18 @@ int rows_poseidon_chain(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handle
         }
         if (path) {
             if (U.pos == ABSENT) return bad("pos must be a row on a PATH unit, not an immediate or absent");
-            see(U.pos);
+            S.see(U.pos);
         } else if (U.pos != ABSENT) {
             return bad("pos belongs to PATH units (KZG_POSEIDON_CHAIN_ABSENT on a SPONGE unit)");
         }
-        if (U.start != ABSENT) see(U.start);
+        if (U.start != ABSENT) S.see(U.start);
         for (uint32_t j = 0; j < KZG_POSEIDON_MAX_T; j++) {
             if (j >= t) {
                 bool zero = U.in[j] == 0;
                 for (int b = 0; b < 32; b++) zero = zero && !U.imm_be32[j][b];
                 if (!zero) return bad("the entries of in and imm_be32 at and above t must be 0");
             } else if (U.in[j] != KZG_POSEIDON_IMM) {
-                see(U.in[j]);
+                S.see(U.in[j]);
                 for (int b = 0; b < 32; b++)
                     if (U.imm_be32[j][b]) return bad("the immediate must be 0 beside a row");
             } else if (path && j >= 2) {
@@ -1674,28 +1733,22 @@ int rows_poseidon_chain(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handle
                 return bad("immediates must be canonical scalars (< r)");
             }
         }
-        if (n_seen > KZG_MAX_BATCH_OPEN) return bad("a call reads at most KZG_MAX_BATCH_OPEN distinct input rows");
+        if (S.too_many()) return bad("a call reads at most KZG_MAX_BATCH_OPEN distinct input rows");
         n_out += U.n_out;
     }
     if (n_out > KZG_MAX_BATCH_OPEN) return bad("n_out, the committed columns of all units, must be at most KZG_MAX_BATCH_OPEN");
     if (n_out && !out_commitments48) return KZG_E_ARG;
-    BuilderCall C(ctx, "poseidon_chain");
-    RowTab it;
-    uint32_t ki = 0;
-    if (int rc = C.begin("poseidon_chain", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
-    if (n_seen && max_row >= ki) return bad("a row must index the concatenated rows of the input sets");
-    if (int rc = C.ready(n_out, 32, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ)) return rc;
-    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    UnitCall C(ctx, "poseidon_chain");
+    if (int rc = C.open(expect_i, n_input_handles, input_handles, S.n != 0, S.max_row, ROW_WHY, n_out, opts)) return rc;
     uint64_t stats[5 * KZG_POSEIDON_CHAIN_MAX_UNITS];
-    if (int rc = rows_poseidon_chain_dev(ctx, C.H, C.i, it, params, n_units, units, n_out, C.T, C.dst(), c48, stats, C.blind))
+    if (int rc = rows_poseidon_chain_dev(ctx, C.H, C.i, C.it, params, n_units, units, n_out, C.T, C.dst(), C.c48, stats, C.blind))
         return rc;
-    if (n_out) memcpy(out_commitments48, c48, 48 * (size_t)n_out);
-    const uint64_t n = C.blind ? C.blind->usable : C.T;
+    const uint64_t n = C.n_read();
     for (uint32_t u = 0; u < n_units; u++) out_stats[0][u] = n / units[u].period;
     // the device's runs: segments, bad positions, mismatches, then the first rows of the last two
     static const int run_of[6] = {-1, 0, 1, 3, 2, 4};
-    for (int k = 1; k < 6; k++) memcpy(out_stats[k], stats + run_of[k] * n_units, 8 * (size_t)n_units);
-    *out_handle = C.commit();
+    stats_scatter(out_stats, run_of, 6, stats, n_units);
+    C.finish(out_commitments48, out_handle);
     return KZG_OK;
 }
 
@@ -1709,17 +1762,11 @@ int rows_sha256(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const
     if (!ctx || !input_handles || !out_blocks || !out_messages || !out_counts || !out_first || !out_mismatch ||
         !out_first_mismatch || !out_handle)
         return KZG_E_ARG;
-    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
-        return fail(ctx, KZG_E_ARG, "sha256: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (int rc = UnitCall::handles_ok(ctx, "sha256", n_input_handles)) return rc;
     if (n_units == 0 || n_units > KZG_SHA256_MAX_UNITS || !units)
         return fail(ctx, KZG_E_ARG, "sha256: n_units must be in [1, KZG_SHA256_MAX_UNITS]");
-    uint32_t n_out = 0, max_row = 0, n_seen = 0, seen[(8 + 16 + 8) * KZG_SHA256_MAX_UNITS];
-    auto see = [&](uint32_t row) {
-        max_row = std::max(max_row, row);
-        uint32_t d = 0;
-        while (d < n_seen && seen[d] != row) d++;
-        if (d == n_seen) seen[n_seen++] = row;
-    };
+    uint32_t n_out = 0;
+    SeenRows S;
     for (uint32_t u = 0; u < n_units; u++) {
         const kzg_sha256_unit& U = units[u];
         if (U.mode != KZG_SHA256_ROW && U.mode != KZG_SHA256_ROUNDS)
@@ -1739,14 +1786,14 @@ int rows_sha256(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const
                 return fail(ctx, KZG_E_ARG, "sha256: an out index must be below 8 (ROUNDS: a column id below KZG_SHA256_N_COLS)");
             if (taken >> U.out[c] & 1) return fail(ctx, KZG_E_ARG, "sha256: an out index is repeated");
             taken |= 1u << U.out[c];
-            if (check) see(U.expect[c]);
+            if (check) S.see(U.expect[c]);
         }
         for (uint32_t j = 0; j < 8; j++) {
             if (U.state[j] != KZG_SHA256_IMM) {
                 if (rounds || std_iv)
                     return fail(ctx, KZG_E_ARG, "sha256: a state entry must be KZG_SHA256_IMM on a ROUNDS unit and with KZG_SHA256_STD_IV");
                 if (U.state_imm[j]) return fail(ctx, KZG_E_ARG, "sha256: the immediate must be 0 beside a row");
-                see(U.state[j]);
+                S.see(U.state[j]);
             } else if (std_iv && U.state_imm[j]) {
                 return fail(ctx, KZG_E_ARG, "sha256: the immediate must be 0 with KZG_SHA256_STD_IV");
             }
@@ -1757,41 +1804,33 @@ int rows_sha256(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const
                     return fail(ctx, KZG_E_ARG, "sha256: the message of a ROUNDS unit is a row, not an immediate");
                 if ((j && U.msg[j]) || U.msg_imm[j])
                     return fail(ctx, KZG_E_ARG, "sha256: msg[1 .. 15] and msg_imm must be 0 on a ROUNDS unit");
-                if (j == 0) see(U.msg[0]);
+                if (j == 0) S.see(U.msg[0]);
             } else if (U.msg[j] != KZG_SHA256_IMM) {
                 if (U.msg_imm[j]) return fail(ctx, KZG_E_ARG, "sha256: the immediate must be 0 beside a row");
-                see(U.msg[j]);
+                S.see(U.msg[j]);
             }
         }
         if (U.start != KZG_SHA256_ABSENT) {
             if (!rounds) return fail(ctx, KZG_E_ARG, "sha256: start belongs to ROUNDS units (KZG_SHA256_ABSENT on a ROW unit)");
-            see(U.start);
+            S.see(U.start);
         }
-        if (n_seen > KZG_MAX_BATCH_OPEN)
+        if (S.too_many())
             return fail(ctx, KZG_E_ARG, "sha256: a call reads at most KZG_MAX_BATCH_OPEN distinct input rows");
         n_out += check ? 0 : U.n_out;
     }
     if (n_out > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "sha256: n_out, the committed columns of all units, must be at most KZG_MAX_BATCH_OPEN");
     if (n_out && !out_commitments48) return KZG_E_ARG;
-    BuilderCall C(ctx, "sha256");
-    RowTab it;
-    uint32_t ki = 0;
-    if (int rc = C.begin("sha256", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
-    if (n_seen && max_row >= ki) return fail(ctx, KZG_E_ARG, "sha256: a row must index the concatenated rows of the input sets");
-    if (int rc = C.ready(n_out, 32, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ)) return rc;
-    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    UnitCall C(ctx, "sha256");
+    if (int rc = C.open(expect_i, n_input_handles, input_handles, S.n != 0, S.max_row, ROW_WHY, n_out, opts)) return rc;
     uint64_t stats[5 * KZG_SHA256_MAX_UNITS];
-    if (int rc = rows_sha256_dev(ctx, C.H, C.i, it, n_units, units, n_out, C.T, C.dst(), c48, stats, C.blind)) return rc;
-    if (n_out) memcpy(out_commitments48, c48, 48 * (size_t)n_out);
-    const uint64_t n = C.blind ? C.blind->usable : C.T;
+    if (int rc = rows_sha256_dev(ctx, C.H, C.i, C.it, n_units, units, n_out, C.T, C.dst(), C.c48, stats, C.blind)) return rc;
+    const uint64_t n = C.n_read();
     for (uint32_t u = 0; u < n_units; u++) out_blocks[u] = units[u].mode == KZG_SHA256_ROUNDS ? n / units[u].period : n;
-    memcpy(out_counts, stats, 8 * (size_t)n_units);
-    memcpy(out_mismatch, stats + n_units, 8 * (size_t)n_units);
-    memcpy(out_messages, stats + 2 * n_units, 8 * (size_t)n_units);
-    memcpy(out_first, stats + 3 * n_units, 8 * (size_t)n_units);
-    memcpy(out_first_mismatch, stats + 4 * n_units, 8 * (size_t)n_units);
-    *out_handle = C.commit();
+    static const int run_of[6] = {-1, 2, 0, 3, 1, 4};   // the device's runs: counts, mismatches, messages, then two first rows
+    uint64_t* const out[6] = {out_blocks, out_messages, out_counts, out_first, out_mismatch, out_first_mismatch};
+    stats_scatter(out, run_of, 6, stats, n_units);
+    C.finish(out_commitments48, out_handle);
     return KZG_OK;
 }
 
@@ -1805,17 +1844,11 @@ int rows_keccak(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const
     if (!ctx || !input_handles || !out_perms || !out_messages || !out_counts || !out_first || !out_mismatch ||
         !out_first_mismatch || !out_handle)
         return KZG_E_ARG;
-    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
-        return fail(ctx, KZG_E_ARG, "keccak: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (int rc = UnitCall::handles_ok(ctx, "keccak", n_input_handles)) return rc;
     if (n_units == 0 || n_units > KZG_KECCAK_MAX_UNITS || !units)
         return fail(ctx, KZG_E_ARG, "keccak: n_units must be in [1, KZG_KECCAK_MAX_UNITS]");
-    uint32_t n_out = 0, max_row = 0, n_seen = 0, seen[(25 + KZG_KECCAK_MAX_OUT + 1) * KZG_KECCAK_MAX_UNITS];
-    auto see = [&](uint32_t row) {
-        max_row = std::max(max_row, row);
-        uint32_t d = 0;
-        while (d < n_seen && seen[d] != row) d++;
-        if (d == n_seen) seen[n_seen++] = row;
-    };
+    uint32_t n_out = 0;
+    SeenRows S;
     for (uint32_t u = 0; u < n_units; u++) {
         const kzg_keccak_unit& U = units[u];
         if (U.mode != KZG_KECCAK_ROW && U.mode != KZG_KECCAK_ROUNDS)
@@ -1835,7 +1868,7 @@ int rows_keccak(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const
                 return fail(ctx, KZG_E_ARG, "keccak: a lane index must be below 25 (ROUNDS: a column id below KZG_KECCAK_N_COLS)");
             if (taken >> U.out[c] & 1) return fail(ctx, KZG_E_ARG, "keccak: a lane index or column id is repeated");
             taken |= 1u << U.out[c];
-            if (check) see(U.expect[c]);
+            if (check) S.see(U.expect[c]);
         }
         for (uint32_t j = 0; j < 25; j++) {
             if (rounds) {
@@ -1843,41 +1876,33 @@ int rows_keccak(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const
                     return fail(ctx, KZG_E_ARG, "keccak: the message columns of a ROUNDS unit are rows, not immediates");
                 if ((j >= 5 && U.in[j]) || U.imm[j])
                     return fail(ctx, KZG_E_ARG, "keccak: in[5 .. 24] and imm must be 0 on a ROUNDS unit");
-                if (j < 5) see(U.in[j]);
+                if (j < 5) S.see(U.in[j]);
             } else if (U.in[j] != KZG_KECCAK_IMM) {
                 if (U.imm[j]) return fail(ctx, KZG_E_ARG, "keccak: the immediate must be 0 beside a row");
-                see(U.in[j]);
+                S.see(U.in[j]);
             }
         }
         if (U.start != KZG_KECCAK_ABSENT) {
             if (!rounds) return fail(ctx, KZG_E_ARG, "keccak: start belongs to ROUNDS units (KZG_KECCAK_ABSENT on a ROW unit)");
-            see(U.start);
+            S.see(U.start);
         }
-        if (n_seen > KZG_MAX_BATCH_OPEN)
+        if (S.too_many())
             return fail(ctx, KZG_E_ARG, "keccak: a call reads at most KZG_MAX_BATCH_OPEN distinct input rows");
         n_out += check ? 0 : U.n_out;
     }
     if (n_out > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "keccak: n_out, the committed columns of all units, must be at most KZG_MAX_BATCH_OPEN");
     if (n_out && !out_commitments48) return KZG_E_ARG;
-    BuilderCall C(ctx, "keccak");
-    RowTab it;
-    uint32_t ki = 0;
-    if (int rc = C.begin("keccak", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
-    if (n_seen && max_row >= ki) return fail(ctx, KZG_E_ARG, "keccak: a row must index the concatenated rows of the input sets");
-    if (int rc = C.ready(n_out, 32, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ)) return rc;
-    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    UnitCall C(ctx, "keccak");
+    if (int rc = C.open(expect_i, n_input_handles, input_handles, S.n != 0, S.max_row, ROW_WHY, n_out, opts)) return rc;
     uint64_t stats[5 * KZG_KECCAK_MAX_UNITS];
-    if (int rc = rows_keccak_dev(ctx, C.H, C.i, it, n_units, units, n_out, C.T, C.dst(), c48, stats, C.blind)) return rc;
-    if (n_out) memcpy(out_commitments48, c48, 48 * (size_t)n_out);
-    const uint64_t n = C.blind ? C.blind->usable : C.T;
+    if (int rc = rows_keccak_dev(ctx, C.H, C.i, C.it, n_units, units, n_out, C.T, C.dst(), C.c48, stats, C.blind)) return rc;
+    const uint64_t n = C.n_read();
     for (uint32_t u = 0; u < n_units; u++) out_perms[u] = units[u].mode == KZG_KECCAK_ROUNDS ? n / units[u].period : n;
-    memcpy(out_counts, stats, 8 * (size_t)n_units);
-    memcpy(out_mismatch, stats + n_units, 8 * (size_t)n_units);
-    memcpy(out_messages, stats + 2 * n_units, 8 * (size_t)n_units);
-    memcpy(out_first, stats + 3 * n_units, 8 * (size_t)n_units);
-    memcpy(out_first_mismatch, stats + 4 * n_units, 8 * (size_t)n_units);
-    *out_handle = C.commit();
+    static const int run_of[6] = {-1, 2, 0, 3, 1, 4};   // the device's runs: counts, mismatches, messages, then two first rows
+    uint64_t* const out[6] = {out_perms, out_messages, out_counts, out_first, out_mismatch, out_first_mismatch};
+    stats_scatter(out, run_of, 6, stats, n_units);
+    C.finish(out_commitments48, out_handle);
     return KZG_OK;
 }
 
@@ -1890,8 +1915,7 @@ int rows_ec(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uin
     if (!ctx || !input_handles || !out_stats || !out_handle) return KZG_E_ARG;
     for (int k = 0; k < 9; k++)
         if (!out_stats[k]) return KZG_E_ARG;
-    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
-        return fail(ctx, KZG_E_ARG, "ec: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (int rc = UnitCall::handles_ok(ctx, "ec", n_input_handles)) return rc;
     if (n_units == 0 || n_units > KZG_EC_MAX_UNITS || !units)
         return fail(ctx, KZG_E_ARG, "ec: n_units must be in [1, KZG_EC_MAX_UNITS]");
     if (!curve) return fail(ctx, KZG_E_ARG, "ec: the curve must be given");
@@ -1917,27 +1941,8 @@ int rows_ec(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uin
     if (!(curve->p[0] & 1u) || p_small) return fail(ctx, KZG_E_ARG, "ec: the modulus p must be odd and at least 3");
     if (!fits(curve->p)) return fail(ctx, KZG_E_ARG, "ec: the modulus p must be below 2^W");
     if (!below(curve->a, curve->p)) return fail(ctx, KZG_E_ARG, "ec: the coefficient a must be below p");
-    uint32_t n_out = 0, max_row = 0, n_seen = 0, seen[8 * KZG_EC_MAX_LIMBS * KZG_EC_MAX_UNITS];
-    bool too_many = false;
-    auto see = [&](uint32_t first, uint32_t count) {   // (first < 2^32 - 1: first + l cannot wrap past a uint64)
-        for (uint32_t l = 0; l < count; l++) {
-            const uint64_t row = (uint64_t)first + l;
-            if (row >= 0xffffffffull) {
-                max_row = 0xffffffffu;
-                return;
-            }
-            max_row = std::max(max_row, (uint32_t)row);
-            uint32_t d = 0;
-            while (d < n_seen && seen[d] != (uint32_t)row) d++;
-            if (d == n_seen) {
-                if (n_seen == sizeof(seen) / sizeof(seen[0])) {
-                    too_many = true;
-                    return;
-                }
-                seen[n_seen++] = (uint32_t)row;
-            }
-        }
-    };
+    uint32_t n_out = 0;
+    SeenRows S;
     for (uint32_t u = 0; u < n_units; u++) {
         const kzg_ec_unit& U = units[u];
         if (U.mode != KZG_EC_DIV && U.mode != KZG_EC_ADD && U.mode != KZG_EC_CHAIN)
@@ -1953,50 +1958,40 @@ int rows_ec(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uin
             const bool takes = w < n_in && !(w == 1 && imm_b);
             if (takes != (U.in[w] != KZG_EC_ABSENT))
                 return fail(ctx, KZG_E_ARG, "ec: an operand the mode does not take, or a missing one (KZG_EC_ABSENT beside the mode's operands)");
-            if (takes) see(U.in[w], L);
+            if (takes) S.see_run(U.in[w], L);
             if (!imm_b && U.imm[w]) return fail(ctx, KZG_E_ARG, "ec: the immediate must be 0 without KZG_EC_IMM_B");
         }
         if (imm_b && !fits(U.imm)) return fail(ctx, KZG_E_ARG, "ec: the immediate must be below 2^W");
         if ((U.mode == KZG_EC_CHAIN) != (U.op != KZG_EC_ABSENT))
             return fail(ctx, KZG_E_ARG, "ec: op belongs to CHAIN units, and a CHAIN unit must have one (KZG_EC_ABSENT elsewhere)");
-        if (U.mode == KZG_EC_CHAIN) see(U.op, 1);
+        if (U.mode == KZG_EC_CHAIN) S.see_run(U.op, 1);
         for (uint32_t k = 0; k < 3; k++) {
             const bool takes = check && (U.cols >> k & 1u);
             if (takes != (U.expect[k] != KZG_EC_ABSENT))
                 return fail(ctx, KZG_E_ARG, "ec: expect must hold one first row per name of cols under KZG_EC_CHECK, KZG_EC_ABSENT elsewhere");
-            if (takes) see(U.expect[k], L);
+            if (takes) S.see_run(U.expect[k], L);
         }
-        if (too_many || n_seen > KZG_MAX_BATCH_OPEN)
+        if (S.too_many())
             return fail(ctx, KZG_E_ARG, "ec: a call reads at most KZG_MAX_BATCH_OPEN distinct input rows");
         n_out += check ? 0 : (uint32_t)__builtin_popcount(U.cols) * L;
     }
     if (n_out > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "ec: n_out, the committed rows of all units, must be at most KZG_MAX_BATCH_OPEN");
     if (n_out && !out_commitments48) return KZG_E_ARG;
-    BuilderCall C(ctx, "ec");
-    RowTab it;
-    uint32_t ki = 0;
-    if (int rc = C.begin("ec", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
-    if (max_row >= ki) return fail(ctx, KZG_E_ARG, "ec: an operand run must lie inside the concatenated rows of the input sets");
-    if (int rc = C.ready(n_out, 32, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ)) return rc;
-    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    UnitCall C(ctx, "ec");
+    // (no guard on S.n: every unit of ec names a row)
+    static const char run_why[] = ": an operand run must lie inside the concatenated rows of the input sets";
+    if (int rc = C.open(expect_i, n_input_handles, input_handles, true, S.max_row, run_why, n_out, opts)) return rc;
     uint64_t stats[7 * KZG_EC_MAX_UNITS];
-    if (int rc = rows_ec_dev(ctx, C.H, C.i, it, curve, n_units, units, n_out, C.T, C.dst(), c48, stats, C.blind)) return rc;
-    if (n_out) memcpy(out_commitments48, c48, 48 * (size_t)n_out);
+    if (int rc = rows_ec_dev(ctx, C.H, C.i, C.it, curve, n_units, units, n_out, C.T, C.dst(), C.c48, stats, C.blind)) return rc;
     // the device's runs: counts, singular, mismatch or unknown, segments, first, first_singular, first of the third
-    for (uint32_t u = 0; u < n_units; u++) {
-        const bool chain = units[u].mode == KZG_EC_CHAIN;
-        out_stats[0][u] = stats[u];
-        out_stats[1][u] = stats[4 * n_units + u];
-        out_stats[2][u] = stats[n_units + u];
-        out_stats[3][u] = stats[5 * n_units + u];
-        out_stats[4][u] = chain ? 0 : stats[2 * n_units + u];
-        out_stats[5][u] = chain ? KZG_EC_NONE : stats[6 * n_units + u];
-        out_stats[6][u] = chain ? stats[2 * n_units + u] : 0;
-        out_stats[7][u] = chain ? stats[6 * n_units + u] : KZG_EC_NONE;
-        out_stats[8][u] = stats[3 * n_units + u];
-    }
-    *out_handle = C.commit();
+    static const int run_of[9] = {0, 4, 1, 5, -1, -1, -1, -1, 3};
+    bool chain[KZG_EC_MAX_UNITS];
+    for (uint32_t u = 0; u < n_units; u++) chain[u] = units[u].mode == KZG_EC_CHAIN;
+    stats_scatter(out_stats, run_of, 9, stats, n_units);
+    stats_split(out_stats, 2, 4, 6, 0, stats, n_units, chain);
+    stats_split(out_stats, 6, 5, 7, KZG_EC_NONE, stats, n_units, chain);
+    C.finish(out_commitments48, out_handle);
     return KZG_OK;
 }
 
@@ -2009,8 +2004,7 @@ int rows_edwards(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, cons
     if (!ctx || !input_handles || !out_stats || !out_handle) return KZG_E_ARG;
     for (int k = 0; k < 7; k++)
         if (!out_stats[k]) return KZG_E_ARG;
-    if (n_input_handles == 0 || n_input_handles > KZG_MAX_BATCH_OPEN)
-        return fail(ctx, KZG_E_ARG, "edwards: the number of handles must be in [1, KZG_MAX_BATCH_OPEN]");
+    if (int rc = UnitCall::handles_ok(ctx, "edwards", n_input_handles)) return rc;
     if (n_units == 0 || n_units > KZG_EDWARDS_MAX_UNITS || !units)
         return fail(ctx, KZG_E_ARG, "edwards: n_units must be in [1, KZG_EDWARDS_MAX_UNITS]");
     if (!curve) return fail(ctx, KZG_E_ARG, "edwards: the curve must be given");
@@ -2020,13 +2014,8 @@ int rows_edwards(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, cons
     if (!memcmp(curve->a_be32, zero32, 32) || !memcmp(curve->d_be32, zero32, 32))
         return fail(ctx, KZG_E_ARG, "edwards: the coefficients A and D must not be 0");
     if (!memcmp(curve->a_be32, curve->d_be32, 32)) return fail(ctx, KZG_E_ARG, "edwards: the coefficients A and D must differ");
-    uint32_t n_out = 0, max_row = 0, n_seen = 0, seen[7 * KZG_EDWARDS_MAX_UNITS];
-    auto see = [&](uint32_t row) {
-        max_row = std::max(max_row, row);
-        uint32_t d = 0;
-        while (d < n_seen && seen[d] != row) d++;
-        if (d == n_seen) seen[n_seen++] = row;
-    };
+    uint32_t n_out = 0;
+    SeenRows S;
     for (uint32_t u = 0; u < n_units; u++) {
         const kzg_edwards_unit& U = units[u];
         if (U.mode != KZG_EDWARDS_ADD && U.mode != KZG_EDWARDS_CHAIN)
@@ -2045,21 +2034,21 @@ int rows_edwards(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, cons
                 if (!fr_be32_canonical(U.imm_be32[w])) return fail(ctx, KZG_E_ARG, "edwards: immediates must be canonical scalars (< r)");
             } else {
                 if (memcmp(U.imm_be32[w], zero32, 32)) return fail(ctx, KZG_E_ARG, "edwards: the immediate must be 0 beside a row");
-                if (takes) see(U.in[w]);
+                if (takes) S.see(U.in[w]);
             }
         }
         if (chain != (U.op != KZG_EDWARDS_ABSENT))
             return fail(ctx, KZG_E_ARG, "edwards: op belongs to CHAIN units, and a CHAIN unit must have one (KZG_EDWARDS_ABSENT elsewhere)");
         if (chain) {
             if (U.op == KZG_EDWARDS_IMM) return fail(ctx, KZG_E_ARG, "edwards: op must be a row, not an immediate");
-            see(U.op);
+            S.see(U.op);
         }
         uint32_t ordered = 0;
         for (uint32_t k = 0; k < 2; k++) {
             const bool takes = check && (U.cols >> k & 1u);
             if (takes != (U.expect[k] != KZG_EDWARDS_ABSENT) || U.expect[k] == KZG_EDWARDS_IMM)
                 return fail(ctx, KZG_E_ARG, "edwards: expect must hold one row per name of cols under KZG_EDWARDS_CHECK, KZG_EDWARDS_ABSENT elsewhere");
-            if (takes) see(U.expect[k]);
+            if (takes) S.see(U.expect[k]);
             const uint32_t o = U.out_order[k];
             if (o == KZG_EDWARDS_ABSENT) continue;
             if (check || o > 1 || (ordered >> o & 1u) || (k == 1 && U.out_order[0] == KZG_EDWARDS_ABSENT))
@@ -2068,35 +2057,25 @@ int rows_edwards(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, cons
         }
         if (!check && ordered != U.cols)
             return fail(ctx, KZG_E_ARG, "edwards: out_order must list the names of cols once each (KZG_EDWARDS_ABSENT beyond, and in a check)");
-        if (n_seen > KZG_MAX_BATCH_OPEN)
+        if (S.too_many())
             return fail(ctx, KZG_E_ARG, "edwards: a call reads at most KZG_MAX_BATCH_OPEN distinct input rows");
         n_out += check ? 0 : (uint32_t)__builtin_popcount(U.cols);
     }
     if (n_out > KZG_MAX_BATCH_OPEN)
         return fail(ctx, KZG_E_ARG, "edwards: n_out, the committed rows of all units, must be at most KZG_MAX_BATCH_OPEN");
     if (n_out && !out_commitments48) return KZG_E_ARG;
-    BuilderCall C(ctx, "edwards");
-    RowTab it;
-    uint32_t ki = 0;
-    if (int rc = C.begin("edwards", expect_i, n_input_handles, input_handles, it, &ki)) return rc;
-    if (n_seen && max_row >= ki) return fail(ctx, KZG_E_ARG, "edwards: a row must index the concatenated rows of the input sets");
-    if (int rc = C.ready(n_out, 32, {opts ? opts->usable : 0, opts ? opts->tail_be32 : nullptr}, LAY_READ)) return rc;
-    uint8_t c48[KZG_MAX_BATCH_OPEN * 48];
+    UnitCall C(ctx, "edwards");
+    if (int rc = C.open(expect_i, n_input_handles, input_handles, S.n != 0, S.max_row, ROW_WHY, n_out, opts)) return rc;
     uint64_t stats[5 * KZG_EDWARDS_MAX_UNITS];
-    if (int rc = rows_edwards_dev(ctx, C.H, C.i, it, curve, n_units, units, n_out, C.T, C.dst(), c48, stats, C.blind)) return rc;
-    if (n_out) memcpy(out_commitments48, c48, 48 * (size_t)n_out);
+    if (int rc = rows_edwards_dev(ctx, C.H, C.i, C.it, curve, n_units, units, n_out, C.T, C.dst(), C.c48, stats, C.blind)) return rc;
     // the device's runs: singular, mismatch or unknown, segments, first_singular, first of the second
-    for (uint32_t u = 0; u < n_units; u++) {
-        const bool chain = units[u].mode == KZG_EDWARDS_CHAIN;
-        out_stats[0][u] = stats[u];
-        out_stats[1][u] = stats[3 * n_units + u];
-        out_stats[2][u] = chain ? 0 : stats[n_units + u];
-        out_stats[3][u] = chain ? KZG_EDWARDS_NONE : stats[4 * n_units + u];
-        out_stats[4][u] = chain ? stats[n_units + u] : 0;
-        out_stats[5][u] = chain ? stats[4 * n_units + u] : KZG_EDWARDS_NONE;
-        out_stats[6][u] = stats[2 * n_units + u];
-    }
-    *out_handle = C.commit();
+    static const int run_of[7] = {0, 3, -1, -1, -1, -1, 2};
+    bool chain[KZG_EDWARDS_MAX_UNITS];
+    for (uint32_t u = 0; u < n_units; u++) chain[u] = units[u].mode == KZG_EDWARDS_CHAIN;
+    stats_scatter(out_stats, run_of, 7, stats, n_units);
+    stats_split(out_stats, 1, 2, 4, 0, stats, n_units, chain);
+    stats_split(out_stats, 4, 3, 5, KZG_EDWARDS_NONE, stats, n_units, chain);
+    C.finish(out_commitments48, out_handle);
     return KZG_OK;
 }
 

@@ -121,6 +121,158 @@ def typed_column(col, what: str = "commit_rows_typed"):
     return kind, mv.shape[0], mv, fill
 
 
+_R_MODULUS = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
+_is_u = lambda v, top: isinstance(v, int) and not isinstance(v, bool) and 0 <= v < top   # noqa: E731
+_ZERO32 = bytes(32)
+_pad = lambda xs, k, fill=0: list(xs) + [fill] * (k - len(xs))   # noqa: E731
+
+
+class _UnitSpec:
+    """The field parsers of one call of a unit encoder (poseidon_call .. edwards_call): a call is a list of units, each a
+    mapping with a mode; a unit's slots are row indices or ("imm", value), it has an out / cols list and an optional expect,
+    and the call may name and commit at most KZG_MAX_BATCH_OPEN rows.  The words that differ between the builders are
+    arguments; `seen` collects the distinct input rows.  Every refusal is KzgError(KZG_E_ARG, "<what>: <chip>: <why>")."""
+
+    def __init__(self, what: str, chip: str):
+        self.head, self.seen = f"{what}: {chip}: ", set()
+
+    def bad(self, why) -> KzgError:
+        """why: the words, or a function that makes them -- words that need formatting are made on refusal only"""
+        return KzgError(_native.KZG_E_ARG, self.head + (why if isinstance(why, str) else why()))
+
+    def scalar(self, v, name: str) -> bytes:
+        """a canonical scalar given as an int, a decimal or 0x string, or 32 big-endian bytes, as 32 bytes"""
+        if isinstance(v, (bytes, bytearray)):
+            if len(v) != 32:
+                raise self.bad(f"{name} given as bytes must be of 32 bytes")
+            v = int.from_bytes(v, "big")
+        elif isinstance(v, str):
+            try:
+                v = int(v, 0)
+            except ValueError:
+                raise self.bad(f"{name} must be an integer, a decimal or 0x string, or 32 bytes") from None
+        if not isinstance(v, int) or isinstance(v, bool) or v < 0:
+            raise self.bad(f"{name} must be a non-negative integer")
+        if v >= _R_MODULUS:
+            raise self.bad(f"{name} must be a canonical scalar (< r)")
+        return v.to_bytes(32, "big")
+
+    def units(self, units, top: int) -> list:
+        units = list(units) if isinstance(units, (list, tuple)) else None
+        if not units or len(units) > top:
+            raise self.bad(f"units must be a list of 1 .. {top} entries (n_units)")
+        return units
+
+    def mode(self, un, keys: dict, expect_why: Optional[str] = None, foreign: bool = False) -> str:
+        """the mode of the unit `un`, whose fields must be among keys[mode].  expect_why: the refusal of an expect the mode
+        does not take; foreign: a field of another mode has a refusal of its own"""
+        if not isinstance(un, dict) or "mode" not in un:
+            raise self.bad("a unit is a mapping with mode and the fields of its mode")
+        mode = un["mode"]
+        if not isinstance(mode, str) or mode not in keys:
+            raise self.bad(f"unknown mode {mode!r} (one of " + ", ".join('"%s"' % m for m in keys) + ")")
+        extra = set(un) - set(keys[mode])
+        if extra:
+            name = sorted(extra)[0]
+            if expect_why and "expect" in extra:
+                raise self.bad(expect_why)
+            if foreign and any(name in ks for ks in keys.values()):
+                raise self.bad(f"a field the mode does not take: {name!r} does not belong to a {mode} unit")
+            raise self.bad(f"unknown field {name!r} (the fields of a {mode} unit are {', '.join(keys[mode])})")
+        return mode
+
+    def row(self, v, why, top: int = 0xffffffff) -> int:
+        """a row index below top (why: its refusal)"""
+        if not _is_u(v, top):
+            raise self.bad(why)
+        self.seen.add(v)
+        return v
+
+    def slot(self, v, name: str, imm_bits: int = 0, top: int = 0xffffffff) -> tuple:
+        """a row index or ("imm", value): (the row, a zero) or (top, the immediate) -- an integer below 2^imm_bits, or for
+        imm_bits = 0 a canonical scalar as 32 bytes"""
+        if isinstance(v, (list, tuple)):
+            if len(v) != 2 or v[0] != "imm":
+                raise self.bad('an immediate is ("imm", value)')
+            if not imm_bits:
+                return top, self.scalar(v[1], "an immediate")
+            if not _is_u(v[1], 1 << imm_bits):
+                raise self.bad(f"an immediate must be an integer below 2^{imm_bits}")
+            return top, v[1]
+        if not _is_u(v, top):
+            raise self.bad(f'{name} must be a row index, an integer in [0, 2^32 - 1), or ("imm", value)')
+        self.seen.add(v)
+        return v, (0 if imm_bits else _ZERO32)
+
+    def slots(self, v, count: int, why: str, name: str, imm_bits: int = 0) -> tuple:
+        """a list of `count` slots (why: the refusal of anything else): (the rows, the immediates)"""
+        if not isinstance(v, (list, tuple)) or len(v) != count:
+            raise self.bad(why)
+        rows, imms, see, zero = [], [], self.seen.add, (0 if imm_bits else _ZERO32)
+        for s in v:
+            if type(s) is int and 0 <= s < 0xffffffff:   # (the plain case without a call: it is met per slot of every call)
+                see(s)
+                imm = zero
+            else:
+                s, imm = self.slot(s, name, imm_bits)
+            rows.append(s)
+            imms.append(imm)
+        return rows, imms
+
+    def period(self, v, lo: int, why: str) -> int:
+        if not _is_u(v, 1 << 32) or v < lo:
+            raise self.bad(why)
+        return v
+
+    def indices(self, v, most: int, top: int, why: str, why_index: str, why_repeated: str) -> list:
+        """an out list: 1 .. most distinct indices below top"""
+        if not isinstance(v, (list, tuple)) or not 1 <= len(v) <= most:
+            raise self.bad(why)
+        if any(not _is_u(j, top) for j in v):
+            raise self.bad(why_index)
+        if len(set(v)) != len(v):
+            raise self.bad(why_repeated)
+        return list(v)
+
+    def expects(self, v, n: int) -> list:
+        """an expect list: one row per entry of out"""
+        if not isinstance(v, (list, tuple)) or len(v) != n:
+            raise self.bad("expect must hold one row per entry of out")
+        if any(not _is_u(j, 0xffffffff) for j in v):
+            raise self.bad("an entry of expect must be a row index, an integer in [0, 2^32 - 1)")
+        self.seen.update(v)
+        return list(v)
+
+    def names(self, v, allowed, why, kind: str = "column name", unit: str = "", top: Optional[int] = None) -> list:
+        """a list of 1 .. top (None: any number of) distinct names among `allowed`, as their indices; unit: the mode whose
+        names they are, where the refusal says so"""
+        if not isinstance(v, (list, tuple)) or not v or (top is not None and len(v) > top):
+            raise self.bad(why)
+        for name in v:
+            if name not in allowed:
+                raise self.bad(f"unknown {kind} {name!r} (the names{unit and f' of a {unit} unit'} are {', '.join(allowed)})")
+        if len(set(v)) != len(v):
+            raise self.bad(f"a {kind} is repeated")
+        return [allowed.index(name) for name in v]
+
+    def out_or_expect(self, un) -> bool:
+        """a unit commits (out) or is a check (expect): whether it is a check"""
+        has_out, has_exp = un.get("out") is not None, un.get("expect") is not None
+        if has_out and has_exp:
+            raise self.bad("out together with expect: a unit commits, or it is a check")
+        if not has_out and not has_exp:
+            raise self.bad("a unit needs out, or expect for a check")
+        return has_exp
+
+    def caps(self, n_out: int) -> None:
+        """the two closing caps of a call"""
+        top = _native.KZG_MAX_BATCH_OPEN
+        if len(self.seen) > top:
+            raise self.bad(f"the units read {len(self.seen)} distinct input rows, at most {top} fit one call")
+        if n_out > top:
+            raise self.bad(f"n_out: the units give {n_out} output rows, at most {top} fit one call")
+
+
 class HipEngine:
     # rows from this length up are decoded and uploaded tile by tile (see _Staged); KZG_STREAM_MIN_LOG moves the threshold
     STREAM_MIN = 1 << int(os.environ.get("KZG_STREAM_MIN_LOG", "19"))
@@ -1245,36 +1397,18 @@ class HipEngine:
     _POSEIDON_UNIT_KEYS = ("mode", "in", "out", "expect", "period")
 
     @classmethod
-    def _poseidon_params(cls, params, bad):
+    def _poseidon_params(cls, params, sp):
         """The params of poseidon_call and poseidon_chain_call, checked and encoded by one body: (t, R, (t, full, partial, rc
-        bytes, mds bytes), is_u, scalar); bad(why) makes the caller's KzgError"""
-        is_u = lambda v, top: isinstance(v, int) and not isinstance(v, bool) and 0 <= v < top   # noqa: E731
-        r_mod = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
-
-        def scalar(v, name):
-            if isinstance(v, (bytes, bytearray)):
-                if len(v) != 32:
-                    raise bad(f"{name} given as bytes must be of 32 bytes")
-                v = int.from_bytes(v, "big")
-            elif isinstance(v, str):
-                try:
-                    v = int(v, 0)
-                except ValueError:
-                    raise bad(f"{name} must be an integer, a decimal or 0x string, or 32 bytes") from None
-            if not isinstance(v, int) or isinstance(v, bool) or v < 0:
-                raise bad(f"{name} must be a non-negative integer")
-            if v >= r_mod:
-                raise bad(f"{name} must be a canonical scalar (< r)")
-            return v.to_bytes(32, "big")
-
+        bytes, mds bytes)); sp: the caller's _UnitSpec"""
+        bad = sp.bad
         if not isinstance(params, dict) or set(params) != set(cls._POSEIDON_PARAM_KEYS):
             raise bad(f"params is a mapping with exactly {', '.join(cls._POSEIDON_PARAM_KEYS)}")
         t, full, partial = params["t"], params["full"], params["partial"]
-        if not is_u(t, _native.KZG_POSEIDON_MAX_T + 1) or t < _native.KZG_POSEIDON_MIN_T:
+        if not _is_u(t, _native.KZG_POSEIDON_MAX_T + 1) or t < _native.KZG_POSEIDON_MIN_T:
             raise bad(f"the width t must be an integer in [{_native.KZG_POSEIDON_MIN_T}, {_native.KZG_POSEIDON_MAX_T}]")
-        if not is_u(full, _native.KZG_POSEIDON_MAX_FULL + 1) or full < 2 or full % 2:
+        if not _is_u(full, _native.KZG_POSEIDON_MAX_FULL + 1) or full < 2 or full % 2:
             raise bad(f"the number of full rounds R_F must be even and in [2, {_native.KZG_POSEIDON_MAX_FULL}]")
-        if not is_u(partial, _native.KZG_POSEIDON_MAX_PARTIAL + 1):
+        if not _is_u(partial, _native.KZG_POSEIDON_MAX_PARTIAL + 1):
             raise bad(f"the number of partial rounds R_P must be in [0, {_native.KZG_POSEIDON_MAX_PARTIAL}]")
         R = full + partial
         rc, mds = params["rc"], params["mds"]
@@ -1282,9 +1416,9 @@ class HipEngine:
             raise bad(f"rc must be a list of t (R_F + R_P) = {t * R} scalars, round-major")
         if not isinstance(mds, (list, tuple)) or len(mds) != t * t:
             raise bad(f"mds must be a list of t t = {t * t} scalars, row-major")
-        rc_b = b"".join(scalar(v, "a round constant") for v in rc)
-        mds_b = b"".join(scalar(v, "a matrix entry") for v in mds)
-        return t, R, (t, full, partial, rc_b, mds_b), is_u, scalar
+        rc_b = b"".join(sp.scalar(v, "a round constant") for v in rc)
+        mds_b = b"".join(sp.scalar(v, "a matrix entry") for v in mds)
+        return t, R, (t, full, partial, rc_b, mds_b)
 
     @classmethod
     def poseidon_call(cls, params, units, what: str = "commit_poseidon") -> Tuple[tuple, List[tuple]]:
@@ -1295,13 +1429,11 @@ class HipEngine:
         expect (one row per entry of out); or mode "rounds" with in and period (at least R_F + R_P + 1).  An entry of in is a row
         index or ("imm", value).  A scalar is an int, a decimal or 0x string, or 32 big-endian bytes, below r.  Raises
         KzgError(KZG_E_ARG) with the cause; needs no device."""
-        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: poseidon: {why}")   # noqa: E731
-        t, R, par, is_u, scalar = cls._poseidon_params(params, bad)
-        units = list(units) if isinstance(units, (list, tuple)) else None
-        if not units or len(units) > _native.KZG_POSEIDON_MAX_UNITS:
-            raise bad(f"units must be a list of 1 .. {_native.KZG_POSEIDON_MAX_UNITS} entries (n_units)")
-        recs, seen = [], set()
-        for un in units:
+        sp = _UnitSpec(what, "poseidon")
+        bad = sp.bad
+        t, R, par = cls._poseidon_params(params, sp)
+        recs = []
+        for un in sp.units(units, _native.KZG_POSEIDON_MAX_UNITS):
             if not isinstance(un, dict) or "mode" not in un or "in" not in un:
                 raise bad("a unit is a mapping with mode, in and the fields of its mode")
             extra = set(un) - set(cls._POSEIDON_UNIT_KEYS)
@@ -1310,60 +1442,27 @@ class HipEngine:
             mode = un["mode"]
             if mode not in ("row", "rounds"):
                 raise bad(f'unknown mode {mode!r} (one of "row", "rounds")')
-            ins = un["in"]
-            if not isinstance(ins, (list, tuple)) or len(ins) != t:
-                raise bad(f"in must hold t = {t} entries, each a row index or (\"imm\", value)")
-            rows, imms = [], []
-            for v in ins:
-                if isinstance(v, (list, tuple)):
-                    if len(v) != 2 or v[0] != "imm":
-                        raise bad('an immediate is ("imm", value)')
-                    rows.append(_native.KZG_POSEIDON_IMM)
-                    imms.append(scalar(v[1], "an immediate"))
-                elif is_u(v, _native.KZG_POSEIDON_IMM):
-                    rows.append(v)
-                    imms.append(bytes(32))
-                    seen.add(v)
-                else:
-                    raise bad('an entry of in must be a row index, an integer in [0, 2^32 - 1), or ("imm", value)')
+            rows, imms = sp.slots(un["in"], t, lambda: f'in must hold t = {t} entries, each a row index or ("imm", value)',
+                                  "an entry of in")
             flags, period, expect = 0, 0, []
             if mode == "rounds":
                 if un.get("expect") is not None:
                     raise bad("expect belongs to row units, not to rounds")
                 if un.get("out") is not None:
                     raise bad("out belongs to row units: a rounds unit commits all t columns")
-                period = un.get("period")
-                if not is_u(period, 1 << 32) or period < R + 1:
-                    raise bad(f"the period P of a rounds unit must be an integer in [R + 1, 2^32), R + 1 = {R + 1}")
+                period = sp.period(un.get("period"), R + 1,
+                                   lambda: f"the period P of a rounds unit must be an integer in [R + 1, 2^32), R + 1 = {R + 1}")
                 out = list(range(t))
             else:
                 if un.get("period") is not None:
                     raise bad("period belongs to rounds units, not to row")
-                out = un.get("out")
-                if not isinstance(out, (list, tuple)) or not 1 <= len(out) <= t:
-                    raise bad(f"out must hold 1 .. t = {t} state indices")
-                if any(not is_u(j, t) for j in out):
-                    raise bad(f"an out index must be an integer below t = {t}")
-                if len(set(out)) != len(out):
-                    raise bad("an out index is repeated")
-                out = list(out)
+                out = sp.indices(un.get("out"), t, t, lambda: f"out must hold 1 .. t = {t} state indices",
+                                 lambda: f"an out index must be an integer below t = {t}", "an out index is repeated")
                 if un.get("expect") is not None:
-                    expect = un["expect"]
-                    if not isinstance(expect, (list, tuple)) or len(expect) != len(out):
-                        raise bad("expect must hold one row per entry of out")
-                    if any(not is_u(j, _native.KZG_POSEIDON_IMM) for j in expect):
-                        raise bad("an entry of expect must be a row index, an integer in [0, 2^32 - 1)")
-                    expect = list(expect)
-                    seen.update(expect)
-                    flags = _native.KZG_POSEIDON_CHECK
-            pad = lambda xs: list(xs) + [0] * (8 - len(xs))   # noqa: E731
+                    expect, flags = sp.expects(un["expect"], len(out)), _native.KZG_POSEIDON_CHECK
             recs.append((_native.KZG_POSEIDON_ROW if mode == "row" else _native.KZG_POSEIDON_ROUNDS, flags, len(out), period,
-                         pad(rows), pad(out), pad(expect), imms + [bytes(32)] * (8 - t)))
-        if len(seen) > _native.KZG_MAX_BATCH_OPEN:
-            raise bad(f"the units read {len(seen)} distinct input rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
-        n_out = sum(r[2] for r in recs if not r[1])
-        if n_out > _native.KZG_MAX_BATCH_OPEN:
-            raise bad(f"n_out: the units give {n_out} output rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+                         _pad(rows, 8), _pad(out, 8), _pad(expect, 8), _pad(imms, 8, _ZERO32)))
+        sp.caps(sum(r[2] for r in recs if not r[1]))
         return par, recs
 
     @staticmethod
@@ -1387,23 +1486,35 @@ class HipEngine:
         what = "commit_poseidon"
         ni, hi = self._handle_array(input_sets, what)
         par, recs = self.poseidon_call(params, units, what)
-        n_out = sum(r[2] for r in recs if not r[1])
+        arr = (_native.PoseidonUnit * len(recs))(*[self.poseidon_unit_struct(r) for r in recs])
+        return self._commit_units(what, self._lib.kzg_rows_commit_poseidon, input_sets, ni, hi, _native.PoseidonParams(*par), arr,
+                                  sum(r[2] for r in recs if not r[1]), usable, tail,
+                                  (("perms", 0), ("mismatch", 0), ("first_mismatch", 1)), _native.KZG_POSEIDON_NONE)
+
+    def _commit_units(self, what, fn, input_sets, ni, hi, lead, arr, n_out, usable, tail, stats, none):
+        """The one body behind the six unit builders' commit_*, from the layout on (fn: the library's call; ni, hi: the handle
+        array; lead: the params or curve struct in front of the unit array `arr`, None where the builder has none).  stats: a
+        (name, is a first row) pair per statistics array in the call's order; `none` in a first-row array becomes None.
+        Returns (the new RowSet or None when nothing is committed, {name: one value per unit})."""
         wi, T, lay = self._column_layout(what, input_sets, n_out, "n_out", "read", usable, tail)
         opts = _native.DeriveOpts(*lay) if lay else None
-        pp = _native.PoseidonParams(*par)
-        arr = (_native.PoseidonUnit * len(recs))(*[self.poseidon_unit_struct(r) for r in recs])
         c, h = ctypes.create_string_buffer(48 * max(n_out, 1)), ctypes.c_uint64(0)
-        st = [(ctypes.c_uint64 * len(recs))() for _ in range(3)]
-        self._chk(self._lib.kzg_rows_commit_poseidon(self._h, ni, hi, ctypes.byref(pp), len(recs), arr,
-                                                     ctypes.byref(opts) if opts is not None else None, c if n_out else None,
-                                                     st[0], st[1], st[2], ctypes.byref(h)))
+        st = [(ctypes.c_uint64 * len(arr))() for _ in stats]
+        front = (self._h, ni, hi) if lead is None else (self._h, ni, hi, ctypes.byref(lead))
+        self._chk(fn(*front, len(arr), arr, ctypes.byref(opts) if opts is not None else None, c if n_out else None, *st,
+                     ctypes.byref(h)))
         rs = RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]) if n_out else None
-        return rs, {"perms": [int(v) for v in st[0]], "mismatch": [int(v) for v in st[1]],
-                    "first_mismatch": [None if int(v) == _native.KZG_POSEIDON_NONE else int(v) for v in st[2]]}
+        return rs, {name: [None if v == none else v for v in xs] if first else list(xs) for (name, first), xs in zip(stats, st)}
+
+    @staticmethod
+    def _n_rows(input_sets):
+        """the number of concatenated input rows where every set says its own (a RowSet does, a bare handle does not)"""
+        ks = [getattr(x, "k", None) for x in input_sets]
+        return None if any(k is None for k in ks) else sum(ks)
 
     # ---- a set built from sets: Poseidon sponges and Merkle paths, chained from block to block along the column
-    _POSEIDON_CHAIN_SPONGE_KEYS = ("mode", "in", "start", "period", "layout", "cols", "digest", "expect")
-    _POSEIDON_CHAIN_PATH_KEYS = ("mode", "cap", "leaf", "sib", "pos", "digest", "start", "period", "layout", "cols", "expect")
+    _POSEIDON_CHAIN_KEYS = {"sponge": ("mode", "in", "start", "period", "layout", "cols", "digest", "expect"),
+                            "path": ("mode", "cap", "leaf", "sib", "pos", "digest", "start", "period", "layout", "cols", "expect")}
 
     @classmethod
     def poseidon_chain_call(cls, params, units, what: str = "commit_poseidon_chain") -> Tuple[tuple, List[tuple]]:
@@ -1414,52 +1525,24 @@ class HipEngine:
         None, "period": P, "layout": ...}.  "flat" takes "cols": 1 .. 2 t distinct names among in0 .. in{t-1}, out0 .. out{t-1};
         "trace" needs P >= R_F + R_P + 1.  Either mode with "expect": row (and "digest") in place of layout and cols is a check.
         A slot is a row index or ("imm", value).  Raises KzgError(KZG_E_ARG) with the cause; needs no device."""
-        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: poseidon_chain: {why}")   # noqa: E731
-        t, R, par, is_u, scalar = cls._poseidon_params(params, bad)
-        IMM, ABSENT, TOP = _native.KZG_POSEIDON_IMM, _native.KZG_POSEIDON_CHAIN_ABSENT, _native.KZG_POSEIDON_CHAIN_MAX_UNITS
-        units = list(units) if isinstance(units, (list, tuple)) else None
-        if not units or len(units) > TOP:
-            raise bad(f"units must be a list of 1 .. {TOP} entries (n_units)")
-        recs, seen = [], set()
+        sp = _UnitSpec(what, "poseidon_chain")
+        bad = sp.bad
+        t, R, par = cls._poseidon_params(params, sp)
+        ABSENT = _native.KZG_POSEIDON_CHAIN_ABSENT
+        recs = []
 
         def row(v, name, optional=False):
             if v is None and optional:
                 return ABSENT
             if isinstance(v, (list, tuple)):
                 raise bad(f"{name} must be a row, not an immediate")
-            if not is_u(v, IMM):
-                raise bad(f"{name} must be a row index, an integer in [0, 2^32 - 1)")
-            seen.add(v)
-            return v
+            return sp.row(v, lambda: f"{name} must be a row index, an integer in [0, 2^32 - 1)")
 
-        def slot(v, name):
-            if isinstance(v, (list, tuple)):
-                if len(v) != 2 or v[0] != "imm":
-                    raise bad('an immediate is ("imm", value)')
-                return IMM, scalar(v[1], "an immediate")
-            if not is_u(v, IMM):
-                raise bad(f'{name} must be a row index, an integer in [0, 2^32 - 1), or ("imm", value)')
-            seen.add(v)
-            return v, bytes(32)
-
-        for un in units:
-            if not isinstance(un, dict) or "mode" not in un:
-                raise bad("a unit is a mapping with mode and the fields of its mode")
-            mode = un["mode"]
-            if mode not in ("sponge", "path"):
-                raise bad(f'unknown mode {mode!r} (one of "sponge", "path")')
-            keys = cls._POSEIDON_CHAIN_SPONGE_KEYS if mode == "sponge" else cls._POSEIDON_CHAIN_PATH_KEYS
-            extra = set(un) - set(keys)
-            if extra:
-                name = sorted(extra)[0]
-                if name in cls._POSEIDON_CHAIN_SPONGE_KEYS + cls._POSEIDON_CHAIN_PATH_KEYS:
-                    raise bad(f"a field the mode does not take: {name!r} does not belong to a {mode} unit")
-                raise bad(f"unknown field {name!r} (the fields of a {mode} unit are {', '.join(keys)})")
+        for un in sp.units(units, _native.KZG_POSEIDON_CHAIN_MAX_UNITS):
+            mode = sp.mode(un, cls._POSEIDON_CHAIN_KEYS, foreign=True)
             if mode == "sponge":
-                ins = un.get("in")
-                if not isinstance(ins, (list, tuple)) or len(ins) != t:
-                    raise bad(f"in must hold t = {t} entries, each a row index or (\"imm\", value)")
-                slots = [slot(v, "an entry of in") for v in ins]
+                rows, imms = sp.slots(un.get("in"), t, lambda: f'in must hold t = {t} entries, each a row index or ("imm", value)',
+                                      "an entry of in")
                 pos = ABSENT
             else:
                 if t < 3:
@@ -1469,14 +1552,13 @@ class HipEngine:
                 sib = un.get("sib")
                 if not isinstance(sib, (list, tuple)) or len(sib) != t - 2:
                     raise bad(f"sib must hold t - 2 = {t - 2} rows")
-                slots = [slot(un["cap"], "cap"), slot(un["leaf"], "leaf")] + [(row(v, "an entry of sib"), bytes(32)) for v in sib]
+                (cap, cap_imm), (leaf, leaf_imm) = sp.slot(un["cap"], "cap"), sp.slot(un["leaf"], "leaf")
+                rows, imms = [cap, leaf] + [row(v, "an entry of sib") for v in sib], [cap_imm, leaf_imm] + [_ZERO32] * (t - 2)
                 pos = row(un.get("pos"), "pos")
             start = row(un.get("start"), "start", optional=True)
-            period = un.get("period")
-            if not is_u(period, 1 << 32) or period < 1:
-                raise bad("the period P must be an integer in [1, 2^32)")
+            period = sp.period(un.get("period"), 1, "the period P must be an integer in [1, 2^32)")
             digest = un.get("digest")
-            if digest is not None and not is_u(digest, t):
+            if digest is not None and not _is_u(digest, t):
                 raise bad(f"digest must be a state index below t = {t}")
             flags, layout, out, expect = 0, 0, [], ABSENT
             if un.get("expect") is not None:
@@ -1501,28 +1583,16 @@ class HipEngine:
                         raise bad(f"the period P of a trace must be at least R + 1 = {R + 1}")
                     layout, out = _native.KZG_POSEIDON_CHAIN_TRACE, list(range(t))
                 else:
-                    cols = un.get("cols")
                     names = [f"in{j}" for j in range(t)] + [f"out{j}" for j in range(t)]
-                    if not isinstance(cols, (list, tuple)) or not cols:
-                        raise bad(f"cols must hold 1 .. 2 t = {2 * t} column names among {', '.join(names)}")
-                    for name in cols:
-                        if name not in names:
-                            raise bad(f"unknown column name {name!r} (the names are {', '.join(names)})")
-                    if len(set(cols)) != len(cols):
-                        raise bad("a column name is repeated")
-                    layout = _native.KZG_POSEIDON_CHAIN_FLAT
                     ids = [_native.KZG_POSEIDON_CHAIN_COL_IN + j for j in range(t)] + \
                           [_native.KZG_POSEIDON_CHAIN_COL_OUT + j for j in range(t)]
-                    out = [ids[names.index(c)] for c in cols]
+                    picked = sp.names(un.get("cols"), names,
+                                      lambda: f"cols must hold 1 .. 2 t = {2 * t} column names among {', '.join(names)}")
+                    layout, out = _native.KZG_POSEIDON_CHAIN_FLAT, [ids[k] for k in picked]
             recs.append((_native.KZG_POSEIDON_CHAIN_SPONGE if mode == "sponge" else _native.KZG_POSEIDON_CHAIN_PATH, flags, layout,
                          period, start, pos, ABSENT if digest is None else digest, expect, len(out),
-                         [s[0] for s in slots] + [0] * (8 - t), out + [0] * (16 - len(out)),
-                         [s[1] for s in slots] + [bytes(32)] * (8 - t)))
-        if len(seen) > _native.KZG_MAX_BATCH_OPEN:
-            raise bad(f"the units read {len(seen)} distinct input rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
-        n_out = sum(r[8] for r in recs)
-        if n_out > _native.KZG_MAX_BATCH_OPEN:
-            raise bad(f"n_out: the units give {n_out} output rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+                         _pad(rows, 8), _pad(out, 16), _pad(imms, 8, _ZERO32)))
+        sp.caps(sum(r[8] for r in recs))
         return par, recs
 
     @staticmethod
@@ -1548,24 +1618,14 @@ class HipEngine:
         what = "commit_poseidon_chain"
         ni, hi = self._handle_array(input_sets, what)
         par, recs = self.poseidon_chain_call(params, units, what)
-        n_out = sum(r[8] for r in recs)
-        wi, T, lay = self._column_layout(what, input_sets, n_out, "n_out", "read", usable, tail)
-        opts = _native.DeriveOpts(*lay) if lay else None
-        pp = _native.PoseidonParams(*par)
         arr = (_native.PoseidonChainUnit * len(recs))(*[self.poseidon_chain_unit_struct(r) for r in recs])
-        c, h = ctypes.create_string_buffer(48 * max(n_out, 1)), ctypes.c_uint64(0)
-        st = [(ctypes.c_uint64 * len(recs))() for _ in range(6)]
-        self._chk(self._lib.kzg_rows_commit_poseidon_chain(self._h, ni, hi, ctypes.byref(pp), len(recs), arr,
-                                                           ctypes.byref(opts) if opts is not None else None, c if n_out else None,
-                                                           *st, ctypes.byref(h)))
-        rs = RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]) if n_out else None
-        none = lambda xs: [None if int(v) == _native.KZG_POSEIDON_NONE else int(v) for v in xs]   # noqa: E731
-        return rs, {"blocks": [int(v) for v in st[0]], "segments": [int(v) for v in st[1]], "bad_pos": [int(v) for v in st[2]],
-                    "first_bad_pos": none(st[3]), "mismatch": [int(v) for v in st[4]], "first_mismatch": none(st[5])}
+        return self._commit_units(what, self._lib.kzg_rows_commit_poseidon_chain, input_sets, ni, hi,
+                                  _native.PoseidonParams(*par), arr, sum(r[8] for r in recs), usable, tail,
+                                  (("blocks", 0), ("segments", 0), ("bad_pos", 0), ("first_bad_pos", 1), ("mismatch", 0),
+                                   ("first_mismatch", 1)), _native.KZG_POSEIDON_NONE)
 
     # ---- a set built from sets: the SHA-256 compression per row, as a check, or as a chained round trace
-    _SHA256_ROW_KEYS = ("mode", "state", "msg", "out", "expect")
-    _SHA256_ROUNDS_KEYS = ("mode", "msg", "start", "period", "iv", "cols")
+    _SHA256_KEYS = {"row": ("mode", "state", "msg", "out", "expect"), "rounds": ("mode", "msg", "start", "period", "iv", "cols")}
 
     @classmethod
     def sha256_call(cls, units, what: str = "commit_sha256") -> List[tuple]:
@@ -1575,47 +1635,16 @@ class HipEngine:
         row, "start": row or None, "period": P >= 72, "iv": None or 8 words, "cols": 1 .. 12 distinct names of
         _native.KZG_SHA256_COLS}.  A slot is a row index or ("imm", v) with v < 2^32.  Raises KzgError(KZG_E_ARG) with the
         cause; needs no device."""
-        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: sha256: {why}")   # noqa: E731
-        is_u = lambda v, top: isinstance(v, int) and not isinstance(v, bool) and 0 <= v < top   # noqa: E731
+        sp = _UnitSpec(what, "sha256")
+        bad = sp.bad
         IMM = _native.KZG_SHA256_IMM
-        units = list(units) if isinstance(units, (list, tuple)) else None
-        if not units or len(units) > _native.KZG_SHA256_MAX_UNITS:
-            raise bad(f"units must be a list of 1 .. {_native.KZG_SHA256_MAX_UNITS} entries (n_units)")
-        seen = set()
 
         def slots(v, count, name):
-            if not isinstance(v, (list, tuple)) or len(v) != count:
-                raise bad(f'{name} must hold {count} slots, each a row index or ("imm", value)')
-            rows, imms = [], []
-            for s in v:
-                if isinstance(s, (list, tuple)):
-                    if len(s) != 2 or s[0] != "imm":
-                        raise bad('an immediate is ("imm", value)')
-                    if not is_u(s[1], 1 << 32):
-                        raise bad("an immediate must be an integer below 2^32")
-                    rows.append(IMM)
-                    imms.append(s[1])
-                elif is_u(s, IMM):
-                    rows.append(s)
-                    imms.append(0)
-                    seen.add(s)
-                else:
-                    raise bad('a slot must be a row index, an integer in [0, 2^32 - 1), or ("imm", value)')
-            return rows, imms
+            return sp.slots(v, count, lambda: f'{name} must hold {count} slots, each a row index or ("imm", value)', "a slot", 32)
 
         recs = []
-        for un in units:
-            if not isinstance(un, dict) or "mode" not in un:
-                raise bad("a unit is a mapping with mode and the fields of its mode")
-            mode = un["mode"]
-            if mode not in ("row", "rounds"):
-                raise bad(f'unknown mode {mode!r} (one of "row", "rounds")')
-            keys = cls._SHA256_ROW_KEYS if mode == "row" else cls._SHA256_ROUNDS_KEYS
-            extra = set(un) - set(keys)
-            if extra:
-                if mode == "rounds" and "expect" in extra:
-                    raise bad("expect belongs to row units, not to rounds")
-                raise bad(f"unknown field {sorted(extra)[0]!r} (the fields of a {mode} unit are {', '.join(keys)})")
+        for un in sp.units(units, _native.KZG_SHA256_MAX_UNITS):
+            mode = sp.mode(un, cls._SHA256_KEYS, "expect belongs to row units, not to rounds")
             flags, period, start, expect = 0, 0, _native.KZG_SHA256_ABSENT, []
             if mode == "row":
                 state = un.get("state")
@@ -1625,63 +1654,31 @@ class HipEngine:
                 else:
                     st_rows, st_imm = slots(state, 8, 'state ("iv", or a list)')
                 m_rows, m_imm = slots(un.get("msg"), 16, "msg")
-                out = un.get("out")
-                if not isinstance(out, (list, tuple)) or not 1 <= len(out) <= 8:
-                    raise bad("out must hold 1 .. 8 word indices")
-                if any(not is_u(j, 8) for j in out):
-                    raise bad("an out index must be an integer below 8")
-                if len(set(out)) != len(out):
-                    raise bad("an out index is repeated")
-                out = list(out)
+                out = sp.indices(un.get("out"), 8, 8, "out must hold 1 .. 8 word indices", "an out index must be an integer below 8",
+                                 "an out index is repeated")
                 if un.get("expect") is not None:
-                    expect = un["expect"]
-                    if not isinstance(expect, (list, tuple)) or len(expect) != len(out):
-                        raise bad("expect must hold one row per entry of out")
-                    if any(not is_u(j, IMM) for j in expect):
-                        raise bad("an entry of expect must be a row index, an integer in [0, 2^32 - 1)")
-                    expect = list(expect)
-                    seen.update(expect)
+                    expect = sp.expects(un["expect"], len(out))
                     flags |= _native.KZG_SHA256_CHECK
             else:
-                msg = un.get("msg")
-                if not is_u(msg, IMM):
-                    raise bad("the msg of a rounds unit must be a row index, an integer in [0, 2^32 - 1)")
-                seen.add(msg)
+                msg = sp.row(un.get("msg"), "the msg of a rounds unit must be a row index, an integer in [0, 2^32 - 1)")
                 m_rows, m_imm = [msg] + [0] * 15, [0] * 16
                 if un.get("start") is not None:
-                    start = un["start"]
-                    if not is_u(start, IMM):
-                        raise bad("start must be a row index, an integer in [0, 2^32 - 1), or None")
-                    seen.add(start)
-                period = un.get("period")
-                if not is_u(period, 1 << 32) or period < _native.KZG_SHA256_MIN_PERIOD:
-                    raise bad(f"the period P of a rounds unit must be an integer in [{_native.KZG_SHA256_MIN_PERIOD}, 2^32)")
+                    start = sp.row(un["start"], "start must be a row index, an integer in [0, 2^32 - 1), or None")
+                period = sp.period(un.get("period"), _native.KZG_SHA256_MIN_PERIOD,
+                                   lambda: f"the period P of a rounds unit must be an integer in [{_native.KZG_SHA256_MIN_PERIOD}, 2^32)")
                 st_rows = [IMM] * 8
                 if un.get("iv") is None:
                     flags |= _native.KZG_SHA256_STD_IV
                     st_imm = [0] * 8
                 else:
                     st_imm = un["iv"]
-                    if not isinstance(st_imm, (list, tuple)) or len(st_imm) != 8 or any(not is_u(v, 1 << 32) for v in st_imm):
+                    if not isinstance(st_imm, (list, tuple)) or len(st_imm) != 8 or any(not _is_u(v, 1 << 32) for v in st_imm):
                         raise bad("iv must be None or 8 words, integers below 2^32")
                     st_imm = list(st_imm)
-                cols = un.get("cols")
-                if not isinstance(cols, (list, tuple)) or not cols:
-                    raise bad(f"cols must hold 1 .. {_native.KZG_SHA256_N_COLS} column names")
-                for name in cols:
-                    if name not in _native.KZG_SHA256_COLS:
-                        raise bad(f"unknown column name {name!r} (the names are {', '.join(_native.KZG_SHA256_COLS)})")
-                if len(set(cols)) != len(cols):
-                    raise bad("a column name is repeated")
-                out = [_native.KZG_SHA256_COLS.index(name) for name in cols]
-            pad = lambda xs, k: list(xs) + [0] * (k - len(xs))   # noqa: E731
+                out = sp.names(un.get("cols"), _native.KZG_SHA256_COLS, lambda: f"cols must hold 1 .. {_native.KZG_SHA256_N_COLS} column names")
             recs.append((_native.KZG_SHA256_ROW if mode == "row" else _native.KZG_SHA256_ROUNDS, flags, len(out), period, start,
-                         st_rows, st_imm, m_rows, m_imm, pad(out, 12), pad(expect, 8)))
-        if len(seen) > _native.KZG_MAX_BATCH_OPEN:
-            raise bad(f"the units read {len(seen)} distinct input rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
-        n_out = sum(r[2] for r in recs if not r[1] & _native.KZG_SHA256_CHECK)
-        if n_out > _native.KZG_MAX_BATCH_OPEN:
-            raise bad(f"n_out: the units give {n_out} output rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+                         st_rows, st_imm, m_rows, m_imm, _pad(out, 12), _pad(expect, 8)))
+        sp.caps(sum(r[2] for r in recs if not r[1] & _native.KZG_SHA256_CHECK))
         return recs
 
     @staticmethod
@@ -1689,6 +1686,8 @@ class HipEngine:
         A = lambda k, xs: (ctypes.c_uint32 * k)(*xs)   # noqa: E731
         return _native.Sha256Unit(rec[0], rec[1], rec[2], rec[3], rec[4], A(8, rec[5]), A(8, rec[6]), A(16, rec[7]), A(16, rec[8]),
                                   A(12, rec[9]), A(8, rec[10]))
+
+    _HASH_STATS = (("messages", 0), ("counts", 0), ("first", 1), ("mismatch", 0), ("first_mismatch", 1))
 
     def commit_sha256(self, input_sets: Sequence[object], units: Sequence[dict], usable: Optional[int] = None,
                       tail: Sequence[bytes] = ()) -> Tuple[Optional["RowSet"], dict]:
@@ -1703,22 +1702,13 @@ class HipEngine:
         what = "commit_sha256"
         ni, hi = self._handle_array(input_sets, what)
         recs = self.sha256_call(units, what)
-        n_out = sum(r[2] for r in recs if not r[1] & _native.KZG_SHA256_CHECK)
-        wi, T, lay = self._column_layout(what, input_sets, n_out, "n_out", "read", usable, tail)
-        opts = _native.DeriveOpts(*lay) if lay else None
         arr = (_native.Sha256Unit * len(recs))(*[self.sha256_unit_struct(r) for r in recs])
-        c, h = ctypes.create_string_buffer(48 * max(n_out, 1)), ctypes.c_uint64(0)
-        st = [(ctypes.c_uint64 * len(recs))() for _ in range(6)]
-        self._chk(self._lib.kzg_rows_commit_sha256(self._h, ni, hi, len(recs), arr, ctypes.byref(opts) if opts is not None else None,
-                                                   c if n_out else None, *st, ctypes.byref(h)))
-        rs = RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]) if n_out else None
-        none = lambda xs: [None if int(v) == _native.KZG_SHA256_NONE else int(v) for v in xs]   # noqa: E731
-        return rs, {"blocks": [int(v) for v in st[0]], "messages": [int(v) for v in st[1]], "counts": [int(v) for v in st[2]],
-                    "first": none(st[3]), "mismatch": [int(v) for v in st[4]], "first_mismatch": none(st[5])}
+        return self._commit_units(what, self._lib.kzg_rows_commit_sha256, input_sets, ni, hi, None, arr,
+                                  sum(r[2] for r in recs if not r[1] & _native.KZG_SHA256_CHECK), usable, tail,
+                                  (("blocks", 0),) + self._HASH_STATS, _native.KZG_SHA256_NONE)
 
     # ---- a set built from sets: Keccak-f[1600] per row, as a check, or as a chained round trace of 64-bit lanes
-    _KECCAK_ROW_KEYS = ("mode", "in", "out", "expect")
-    _KECCAK_ROUNDS_KEYS = ("mode", "msg", "rate", "start", "period", "cols")
+    _KECCAK_KEYS = {"row": ("mode", "in", "out", "expect"), "rounds": ("mode", "msg", "rate", "start", "period", "cols")}
 
     @classmethod
     def keccak_call(cls, units, what: str = "commit_keccak") -> List[tuple]:
@@ -1727,97 +1717,37 @@ class HipEngine:
         for a check, "expect": one row per entry of out.  {"mode": "rounds", "msg": 5 rows, "rate": 1 .. 24, "start": row or
         None, "period": P >= 125, "cols": 1 .. 16 distinct names of _native.KZG_KECCAK_COLS}.  A slot is a row index or ("imm",
         v) with v < 2^64; lane (x, y) is slot x + 5 y.  Raises KzgError(KZG_E_ARG) with the cause; needs no device."""
-        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: keccak: {why}")   # noqa: E731
-        is_u = lambda v, top: isinstance(v, int) and not isinstance(v, bool) and 0 <= v < top   # noqa: E731
+        sp = _UnitSpec(what, "keccak")
+        bad = sp.bad
         IMM, TOP = _native.KZG_KECCAK_IMM, _native.KZG_KECCAK_MAX_OUT
-        units = list(units) if isinstance(units, (list, tuple)) else None
-        if not units or len(units) > _native.KZG_KECCAK_MAX_UNITS:
-            raise bad(f"units must be a list of 1 .. {_native.KZG_KECCAK_MAX_UNITS} entries (n_units)")
-        seen = set()
         recs = []
-        for un in units:
-            if not isinstance(un, dict) or "mode" not in un:
-                raise bad("a unit is a mapping with mode and the fields of its mode")
-            mode = un["mode"]
-            if mode not in ("row", "rounds"):
-                raise bad(f'unknown mode {mode!r} (one of "row", "rounds")')
-            keys = cls._KECCAK_ROW_KEYS if mode == "row" else cls._KECCAK_ROUNDS_KEYS
-            extra = set(un) - set(keys)
-            if extra:
-                if mode == "rounds" and "expect" in extra:
-                    raise bad("expect belongs to row units, not to rounds")
-                raise bad(f"unknown field {sorted(extra)[0]!r} (the fields of a {mode} unit are {', '.join(keys)})")
+        for un in sp.units(units, _native.KZG_KECCAK_MAX_UNITS):
+            mode = sp.mode(un, cls._KECCAK_KEYS, "expect belongs to row units, not to rounds")
             flags, period, rate, start, expect = 0, 0, 0, _native.KZG_KECCAK_ABSENT, []
             if mode == "row":
-                v = un.get("in")
-                if not isinstance(v, (list, tuple)) or len(v) != 25:
-                    raise bad('in must hold 25 slots, each a row index or ("imm", value)')
-                rows, imms = [], []
-                for s in v:
-                    if isinstance(s, (list, tuple)):
-                        if len(s) != 2 or s[0] != "imm":
-                            raise bad('an immediate is ("imm", value)')
-                        if not is_u(s[1], 1 << 64):
-                            raise bad("an immediate must be an integer below 2^64")
-                        rows.append(IMM)
-                        imms.append(s[1])
-                    elif is_u(s, IMM):
-                        rows.append(s)
-                        imms.append(0)
-                        seen.add(s)
-                    else:
-                        raise bad('a slot must be a row index, an integer in [0, 2^32 - 1), or ("imm", value)')
-                out = un.get("out")
-                if not isinstance(out, (list, tuple)) or not 1 <= len(out) <= TOP:
-                    raise bad(f"out must hold 1 .. {TOP} lane indices (n_out)")
-                if any(not is_u(j, 25) for j in out):
-                    raise bad("a lane index must be an integer below 25")
-                if len(set(out)) != len(out):
-                    raise bad("a lane index is repeated")
-                out = list(out)
+                rows, imms = sp.slots(un.get("in"), 25, 'in must hold 25 slots, each a row index or ("imm", value)', "a slot", 64)
+                out = sp.indices(un.get("out"), TOP, 25, lambda: f"out must hold 1 .. {TOP} lane indices (n_out)",
+                                 "a lane index must be an integer below 25", "a lane index is repeated")
                 if un.get("expect") is not None:
-                    expect = un["expect"]
-                    if not isinstance(expect, (list, tuple)) or len(expect) != len(out):
-                        raise bad("expect must hold one row per entry of out")
-                    if any(not is_u(j, IMM) for j in expect):
-                        raise bad("an entry of expect must be a row index, an integer in [0, 2^32 - 1)")
-                    expect = list(expect)
-                    seen.update(expect)
+                    expect = sp.expects(un["expect"], len(out))
                     flags |= _native.KZG_KECCAK_CHECK
             else:
                 msg = un.get("msg")
-                if not isinstance(msg, (list, tuple)) or len(msg) != 5 or any(not is_u(r, IMM) for r in msg):
+                if not isinstance(msg, (list, tuple)) or len(msg) != 5 or any(not _is_u(r, IMM) for r in msg):
                     raise bad("the msg of a rounds unit must hold 5 row indices, integers in [0, 2^32 - 1)")
-                seen.update(msg)
+                sp.seen.update(msg)
                 rows, imms = list(msg) + [0] * 20, [0] * 25
                 rate = un.get("rate")
-                if not is_u(rate, 25) or rate < 1:
+                if not _is_u(rate, 25) or rate < 1:
                     raise bad("the rate of a rounds unit must be an integer in [1, 24] lanes")
                 if un.get("start") is not None:
-                    start = un["start"]
-                    if not is_u(start, IMM):
-                        raise bad("start must be a row index, an integer in [0, 2^32 - 1), or None")
-                    seen.add(start)
-                period = un.get("period")
-                if not is_u(period, 1 << 32) or period < _native.KZG_KECCAK_MIN_PERIOD:
-                    raise bad(f"the period P of a rounds unit must be an integer in [{_native.KZG_KECCAK_MIN_PERIOD}, 2^32)")
-                cols = un.get("cols")
-                if not isinstance(cols, (list, tuple)) or not 1 <= len(cols) <= TOP:
-                    raise bad(f"cols must hold 1 .. {TOP} column names (n_out)")
-                for name in cols:
-                    if name not in _native.KZG_KECCAK_COLS:
-                        raise bad(f"unknown column name {name!r} (the names are {', '.join(_native.KZG_KECCAK_COLS)})")
-                if len(set(cols)) != len(cols):
-                    raise bad("a column name is repeated")
-                out = [_native.KZG_KECCAK_COLS.index(name) for name in cols]
-            pad = lambda xs, k: list(xs) + [0] * (k - len(xs))   # noqa: E731
+                    start = sp.row(un["start"], "start must be a row index, an integer in [0, 2^32 - 1), or None")
+                period = sp.period(un.get("period"), _native.KZG_KECCAK_MIN_PERIOD,
+                                   lambda: f"the period P of a rounds unit must be an integer in [{_native.KZG_KECCAK_MIN_PERIOD}, 2^32)")
+                out = sp.names(un.get("cols"), _native.KZG_KECCAK_COLS, lambda: f"cols must hold 1 .. {TOP} column names (n_out)", top=TOP)
             recs.append((_native.KZG_KECCAK_ROW if mode == "row" else _native.KZG_KECCAK_ROUNDS, flags, len(out), period, rate,
-                         start, imms, rows, pad(out, 16), pad(expect, 16)))
-        if len(seen) > _native.KZG_MAX_BATCH_OPEN:
-            raise bad(f"the units read {len(seen)} distinct input rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
-        n_out = sum(r[2] for r in recs if not r[1] & _native.KZG_KECCAK_CHECK)
-        if n_out > _native.KZG_MAX_BATCH_OPEN:
-            raise bad(f"n_out: the units give {n_out} output rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+                         start, imms, rows, _pad(out, 16), _pad(expect, 16)))
+        sp.caps(sum(r[2] for r in recs if not r[1] & _native.KZG_KECCAK_CHECK))
         return recs
 
     @staticmethod
@@ -1839,18 +1769,10 @@ class HipEngine:
         what = "commit_keccak"
         ni, hi = self._handle_array(input_sets, what)
         recs = self.keccak_call(units, what)
-        n_out = sum(r[2] for r in recs if not r[1] & _native.KZG_KECCAK_CHECK)
-        wi, T, lay = self._column_layout(what, input_sets, n_out, "n_out", "read", usable, tail)
-        opts = _native.DeriveOpts(*lay) if lay else None
         arr = (_native.KeccakUnit * len(recs))(*[self.keccak_unit_struct(r) for r in recs])
-        c, h = ctypes.create_string_buffer(48 * max(n_out, 1)), ctypes.c_uint64(0)
-        st = [(ctypes.c_uint64 * len(recs))() for _ in range(6)]
-        self._chk(self._lib.kzg_rows_commit_keccak(self._h, ni, hi, len(recs), arr, ctypes.byref(opts) if opts is not None else None,
-                                                   c if n_out else None, *st, ctypes.byref(h)))
-        rs = RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]) if n_out else None
-        none = lambda xs: [None if int(v) == _native.KZG_KECCAK_NONE else int(v) for v in xs]   # noqa: E731
-        return rs, {"perms": [int(v) for v in st[0]], "messages": [int(v) for v in st[1]], "counts": [int(v) for v in st[2]],
-                    "first": none(st[3]), "mismatch": [int(v) for v in st[4]], "first_mismatch": none(st[5])}
+        return self._commit_units(what, self._lib.kzg_rows_commit_keccak, input_sets, ni, hi, None, arr,
+                                  sum(r[2] for r in recs if not r[1] & _native.KZG_KECCAK_CHECK), usable, tail,
+                                  (("perms", 0),) + self._HASH_STATS, _native.KZG_KECCAK_NONE)
 
     # ---- a set built from sets: arithmetic of an elliptic curve over a foreign field: a / b mod p, point addition, chains
     _EC_CURVE_KEYS = ("bits", "limbs", "p", "a")
@@ -1868,8 +1790,8 @@ class HipEngine:
         {"mode": "chain", "px", "py": first rows, "op": row, "cols": names among ax, ay, lam}.  An integer may be given as a
         Python int or as a decimal or 0x string.  n_rows: the number of concatenated input rows, where known: an operand run
         must lie inside.  Raises KzgError(KZG_E_ARG) with the cause; needs no device."""
-        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: ec: {why}")   # noqa: E731
-        is_u = lambda v, top: isinstance(v, int) and not isinstance(v, bool) and 0 <= v < top   # noqa: E731
+        sp = _UnitSpec(what, "ec")
+        bad = sp.bad
         ABSENT = _native.KZG_EC_ABSENT
 
         def big(v, name):
@@ -1888,9 +1810,9 @@ class HipEngine:
         if extra:
             raise bad(f"unknown field {sorted(extra)[0]!r} of the curve (the fields are {', '.join(cls._EC_CURVE_KEYS)})")
         b, L = curve.get("bits"), curve.get("limbs")
-        if not is_u(b, 65) or b == 0:
+        if not _is_u(b, 65) or b == 0:
             raise bad("the limb width b (bits) must be an integer in [1, 64]")
-        if not is_u(L, _native.KZG_EC_MAX_LIMBS + 1) or L == 0:
+        if not _is_u(L, _native.KZG_EC_MAX_LIMBS + 1) or L == 0:
             raise bad(f"the number of limbs L (limbs) must be an integer in [1, {_native.KZG_EC_MAX_LIMBS}]")
         W = b * L
         if W > 256:
@@ -1904,39 +1826,24 @@ class HipEngine:
             raise bad("the modulus p must be below 2^W")
         if a >= p:
             raise bad("the coefficient a must be below p")
-        units = list(units) if isinstance(units, (list, tuple)) else None
-        if not units or len(units) > _native.KZG_EC_MAX_UNITS:
-            raise bad(f"units must be a list of 1 .. {_native.KZG_EC_MAX_UNITS} entries (n_units)")
-        seen, recs, n_out = set(), [], 0
+        recs, n_out = [], 0
 
         def run(v, name, count=L):
-            if not is_u(v, ABSENT):
+            if not _is_u(v, ABSENT):
                 raise bad(f"{name} must be a first row, an integer in [0, 2^32 - 1)")
             if n_rows is not None and v + count > n_rows:
                 raise bad(f"the operand run of {name} reaches beyond the {n_rows} concatenated rows of the input sets")
-            seen.update(range(v, v + count))
+            sp.seen.update(range(v, v + count))
             return v
 
-        for un in units:
-            if not isinstance(un, dict) or "mode" not in un:
-                raise bad("a unit is a mapping with mode and the fields of its mode")
-            mode = un["mode"]
-            if not isinstance(mode, str) or mode not in cls._EC_MODES:
-                raise bad(f'unknown mode {mode!r} (one of "div", "add", "chain")')
-            keys = cls._EC_KEYS[mode]
-            extra = set(un) - set(keys)
-            if extra:
-                if mode == "chain" and "expect" in extra:
-                    raise bad("expect belongs to div and add units, not to chain")
-                raise bad(f"unknown field {sorted(extra)[0]!r} (the fields of a {mode} unit are {', '.join(keys)})")
-            flags, cols, op, imm, ins, expect = 0, 0, ABSENT, 0, [ABSENT] * 4, [ABSENT] * 3
+        for un in sp.units(units, _native.KZG_EC_MAX_UNITS):
+            mode = sp.mode(un, cls._EC_KEYS, "expect belongs to div and add units, not to chain")
+            flags, op, imm, ins, expect = 0, ABSENT, 0, [ABSENT] * 4, [ABSENT] * 3
             if mode == "chain":
-                names = _native.KZG_EC_CHAIN_NAMES
                 ins[0], ins[1] = run(un.get("px"), "px"), run(un.get("py"), "py")
                 op = run(un.get("op"), "op", 1)
-                picked = un.get("cols")
-                if not isinstance(picked, (list, tuple)) or not picked:
-                    raise bad(f"cols must hold 1 .. 3 column names among {', '.join(names)}")
+                names = _native.KZG_EC_CHAIN_NAMES
+                picked = sp.names(un.get("cols"), names, lambda: f"cols must hold 1 .. 3 column names among {', '.join(names)}", "name", mode)
             else:
                 names = ("r",) if mode == "div" else _native.KZG_EC_ADD_NAMES
                 if mode == "div":
@@ -1953,45 +1860,27 @@ class HipEngine:
                         ins[1] = run(vb, "b")
                 else:
                     ins = [run(un.get(k), k) for k in ("x1", "y1", "x2", "y2")]
-                has_out, has_exp = un.get("out") is not None, un.get("expect") is not None
-                if has_out and has_exp:
-                    raise bad("out together with expect: a unit commits, or it is a check")
-                if not has_out and not has_exp:
-                    raise bad("a unit needs out, or expect for a check")
-                if has_exp:
+                if sp.out_or_expect(un):
                     ex = un["expect"]
                     if not isinstance(ex, (list, tuple)) or len(ex) != len(names):
                         raise bad("a wrong number of expect rows: one first row for div, three entries (lam, x3, y3; None: not "
                                   "compared) for add")
-                    picked = [k for k, v in zip(names, ex) if v is not None]
+                    picked = [j for j, v in enumerate(ex) if v is not None]
                     if not picked:
                         raise bad("expect must name at least one first row")
-                    for j, v in enumerate(ex):
-                        if v is not None:
-                            expect[j] = run(v, "an entry of expect")
+                    for j in picked:
+                        expect[j] = run(ex[j], "an entry of expect")
                     flags |= _native.KZG_EC_CHECK
                 elif mode == "div":
                     if un["out"] is not True:
                         raise bad("the out of a div unit is True")
-                    picked = ["r"]
+                    picked = [0]
                 else:
-                    picked = un["out"]
-                    if not isinstance(picked, (list, tuple)) or not picked:
-                        raise bad(f"out must hold 1 .. 3 names among {', '.join(names)}")
-            for name in picked:
-                if name not in names:
-                    raise bad(f"unknown name {name!r} (the names of a {mode} unit are {', '.join(names)})")
-            if len(set(picked)) != len(picked):
-                raise bad("a name is repeated")
-            for name in picked:
-                cols |= 1 << names.index(name)
+                    picked = sp.names(un["out"], names, lambda: f"out must hold 1 .. 3 names among {', '.join(names)}", "name", mode)
             if not flags & _native.KZG_EC_CHECK:
                 n_out += len(picked) * L
-            recs.append((cls._EC_MODES[mode], flags, cols, op, ins, expect, imm))
-        if len(seen) > _native.KZG_MAX_BATCH_OPEN:
-            raise bad(f"the units read {len(seen)} distinct input rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
-        if n_out > _native.KZG_MAX_BATCH_OPEN:
-            raise bad(f"n_out: the units give {n_out} output rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+            recs.append((cls._EC_MODES[mode], flags, sum(1 << k for k in picked), op, ins, expect, imm))
+        sp.caps(n_out)
         return (b, L, p, a), recs
 
     @staticmethod
@@ -2006,6 +1895,9 @@ class HipEngine:
     def ec_n_out(cv, recs) -> int:
         return sum(bin(r[2]).count("1") * cv[1] for r in recs if not r[1] & _native.KZG_EC_CHECK)
 
+    _CURVE_STATS = (("singular", 0), ("first_singular", 1), ("mismatch", 0), ("first_mismatch", 1), ("unknown", 0),
+                    ("first_unknown", 1), ("segments", 0))
+
     def commit_ec(self, input_sets: Sequence[object], curve: dict, units: Sequence[dict], usable: Optional[int] = None,
                   tail: Sequence[bytes] = ()) -> Tuple[Optional["RowSet"], dict]:
         """kzg_rows_commit_ec over the concatenated rows of input_sets (RowSet objects or bare handles).  curve and units: see
@@ -2019,23 +1911,10 @@ class HipEngine:
         "segments"} per unit).  usable and tail: as for commit_derived, the tail column-major over the committed rows."""
         what = "commit_ec"
         ni, hi = self._handle_array(input_sets, what)
-        ks = [getattr(x, "k", None) for x in input_sets]
-        cv, recs = self.ec_call(curve, units, what, None if any(k is None for k in ks) else sum(ks))
-        n_out = self.ec_n_out(cv, recs)
-        wi, T, lay = self._column_layout(what, input_sets, n_out, "n_out", "read", usable, tail)
-        opts = _native.DeriveOpts(*lay) if lay else None
+        cv, recs = self.ec_call(curve, units, what, self._n_rows(input_sets))
         cs, arr = self.ec_structs(cv, recs)
-        c, h = ctypes.create_string_buffer(48 * max(n_out, 1)), ctypes.c_uint64(0)
-        st = [(ctypes.c_uint64 * len(recs))() for _ in range(9)]
-        self._chk(self._lib.kzg_rows_commit_ec(self._h, ni, hi, ctypes.byref(cs), len(recs), arr,
-                                               ctypes.byref(opts) if opts is not None else None, c if n_out else None, *st,
-                                               ctypes.byref(h)))
-        rs = RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]) if n_out else None
-        none = lambda xs: [None if int(v) == _native.KZG_EC_NONE else int(v) for v in xs]   # noqa: E731
-        ints = lambda xs: [int(v) for v in xs]   # noqa: E731
-        return rs, {"counts": ints(st[0]), "first": none(st[1]), "singular": ints(st[2]), "first_singular": none(st[3]),
-                    "mismatch": ints(st[4]), "first_mismatch": none(st[5]), "unknown": ints(st[6]), "first_unknown": none(st[7]),
-                    "segments": ints(st[8])}
+        return self._commit_units(what, self._lib.kzg_rows_commit_ec, input_sets, ni, hi, cs, arr, self.ec_n_out(cv, recs), usable,
+                                  tail, (("counts", 0), ("first", 1)) + self._CURVE_STATS, _native.KZG_EC_NONE)
 
     # ---- a set built from sets: arithmetic of a twisted Edwards curve over the scalar field itself: point addition, chains
     _EDWARDS_CURVE_KEYS = ("a", "d")
@@ -2052,118 +1931,63 @@ class HipEngine:
         "cols": names among ax, ay}.  A slot is a row index or ("imm", value).  A scalar is an int, a decimal or 0x string, or
         32 big-endian bytes, below r.  n_rows: the number of concatenated input rows, where known: a row must lie inside.
         Raises KzgError(KZG_E_ARG) with the cause; needs no device."""
-        bad = lambda why: KzgError(_native.KZG_E_ARG, f"{what}: edwards: {why}")   # noqa: E731
-        is_u = lambda v, top: isinstance(v, int) and not isinstance(v, bool) and 0 <= v < top   # noqa: E731
+        sp = _UnitSpec(what, "edwards")
+        bad = sp.bad
         ABSENT, IMM = _native.KZG_EDWARDS_ABSENT, _native.KZG_EDWARDS_IMM
-        r_mod = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
-
-        def scalar(v, name):
-            if isinstance(v, (bytes, bytearray)):
-                if len(v) != 32:
-                    raise bad(f"{name} given as bytes must be of 32 bytes")
-                v = int.from_bytes(v, "big")
-            elif isinstance(v, str):
-                try:
-                    v = int(v, 0)
-                except ValueError:
-                    raise bad(f"{name} must be an integer, a decimal or 0x string, or 32 bytes") from None
-            if not isinstance(v, int) or isinstance(v, bool) or v < 0:
-                raise bad(f"{name} must be a non-negative integer")
-            if v >= r_mod:
-                raise bad(f"{name} must be a canonical scalar (< r)")
-            return v.to_bytes(32, "big")
-
         if not isinstance(curve, dict) or set(curve) != set(cls._EDWARDS_CURVE_KEYS):
             raise bad("the curve is a mapping with exactly a and d")
-        a_b, d_b = scalar(curve["a"], "the coefficient A"), scalar(curve["d"], "the coefficient D")
+        a_b, d_b = sp.scalar(curve["a"], "the coefficient A"), sp.scalar(curve["d"], "the coefficient D")
         if a_b == bytes(32) or d_b == bytes(32):
             raise bad("the coefficients A and D must not be 0")
         if a_b == d_b:
             raise bad("the coefficients A and D must differ")
-        units = list(units) if isinstance(units, (list, tuple)) else None
-        if not units or len(units) > _native.KZG_EDWARDS_MAX_UNITS:
-            raise bad(f"units must be a list of 1 .. {_native.KZG_EDWARDS_MAX_UNITS} entries (n_units)")
-        seen, recs, n_out = set(), [], 0
+        recs, n_out = [], 0
 
         def row(v, name):
-            if not is_u(v, IMM):
+            if not _is_u(v, IMM):
                 raise bad(f"{name} must be a row, an integer in [0, 2^32 - 2)")
             if n_rows is not None and v >= n_rows:
                 raise bad(f"{name} reaches beyond the {n_rows} concatenated rows of the input sets")
-            seen.add(v)
+            sp.seen.add(v)
             return v
 
         def slot(v, name):
             if isinstance(v, (list, tuple)):
-                if len(v) != 2 or v[0] != "imm":
-                    raise bad('an immediate is ("imm", value)')
-                return IMM, scalar(v[1], "an immediate")
+                return sp.slot(v, name, top=IMM)
             if v is None or isinstance(v, bool) or not isinstance(v, int):
                 raise bad(f'{name} must be a row index, an integer in [0, 2^32 - 2), or ("imm", value)')
             return row(v, name), bytes(32)
 
-        for un in units:
-            if not isinstance(un, dict) or "mode" not in un:
-                raise bad("a unit is a mapping with mode and the fields of its mode")
-            mode = un["mode"]
-            if not isinstance(mode, str) or mode not in cls._EDWARDS_MODES:
-                raise bad(f'unknown mode {mode!r} (one of "add", "chain")')
-            keys = cls._EDWARDS_KEYS[mode]
-            extra = set(un) - set(keys)
-            if extra:
-                if mode == "chain" and "expect" in extra:
-                    raise bad("expect belongs to add units, not to chain: a chain is never a check")
-                raise bad(f"unknown field {sorted(extra)[0]!r} (the fields of a {mode} unit are {', '.join(keys)})")
+        for un in sp.units(units, _native.KZG_EDWARDS_MAX_UNITS):
+            mode = sp.mode(un, cls._EDWARDS_KEYS, "expect belongs to add units, not to chain: a chain is never a check")
             flags, op, ins, imms, expect = 0, ABSENT, [ABSENT] * 4, [bytes(32)] * 4, [ABSENT] * 2
             if mode == "chain":
                 names = _native.KZG_EDWARDS_CHAIN_NAMES
                 for j, k in enumerate(("px", "py")):
                     ins[j], imms[j] = slot(un.get(k), k)
                 op = row(un.get("op"), "op")
-                picked = un.get("cols")
-                if not isinstance(picked, (list, tuple)) or not picked:
-                    raise bad(f"cols must hold 1 .. 2 column names among {', '.join(names)}")
+                picked = sp.names(un.get("cols"), names, lambda: f"cols must hold 1 .. 2 column names among {', '.join(names)}", "name", mode)
             else:
                 names = _native.KZG_EDWARDS_ADD_NAMES
                 for j, k in enumerate(("x1", "y1", "x2", "y2")):
                     ins[j], imms[j] = slot(un.get(k), k)
-                has_out, has_exp = un.get("out") is not None, un.get("expect") is not None
-                if has_out and has_exp:
-                    raise bad("out together with expect: a unit commits, or it is a check")
-                if not has_out and not has_exp:
-                    raise bad("a unit needs out, or expect for a check")
-                if has_exp:
+                if sp.out_or_expect(un):
                     ex = un["expect"]
                     if not isinstance(ex, (list, tuple)) or len(ex) != 2:
                         raise bad("expect must hold two entries (x3, y3; None: not compared)")
-                    picked = [k for k, v in zip(names, ex) if v is not None]
+                    picked = [j for j, v in enumerate(ex) if v is not None]
                     if not picked:
                         raise bad("expect must name at least one row")
-                    for j, v in enumerate(ex):
-                        if v is not None:
-                            expect[j] = row(v, "an entry of expect")
+                    for j in picked:
+                        expect[j] = row(ex[j], "an entry of expect")
                     flags |= _native.KZG_EDWARDS_CHECK
                 else:
-                    picked = un["out"]
-                    if not isinstance(picked, (list, tuple)) or not picked:
-                        raise bad(f"out must hold 1 .. 2 names among {', '.join(names)}")
-            for name in picked:
-                if name not in names:
-                    raise bad(f"unknown name {name!r} (the names of a {mode} unit are {', '.join(names)})")
-            if len(set(picked)) != len(picked):
-                raise bad("a name is repeated")
-            cols, order = 0, [ABSENT] * 2
-            for j, name in enumerate(picked):
-                cols |= 1 << names.index(name)
-                if not flags:
-                    order[j] = names.index(name)
+                    picked = sp.names(un["out"], names, lambda: f"out must hold 1 .. 2 names among {', '.join(names)}", "name", mode)
             if not flags:
                 n_out += len(picked)
-            recs.append((cls._EDWARDS_MODES[mode], flags, cols, op, ins, expect, order, imms))
-        if len(seen) > _native.KZG_MAX_BATCH_OPEN:
-            raise bad(f"the units read {len(seen)} distinct input rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
-        if n_out > _native.KZG_MAX_BATCH_OPEN:
-            raise bad(f"n_out: the units give {n_out} output rows, at most {_native.KZG_MAX_BATCH_OPEN} fit one call")
+            recs.append((cls._EDWARDS_MODES[mode], flags, sum(1 << k for k in picked), op, ins, expect,
+                         [ABSENT] * 2 if flags else _pad(picked, 2, ABSENT), imms))
+        sp.caps(n_out)
         return (a_b, d_b), recs
 
     @staticmethod
@@ -2194,22 +2018,10 @@ class HipEngine:
         committed rows."""
         what = "commit_edwards"
         ni, hi = self._handle_array(input_sets, what)
-        ks = [getattr(x, "k", None) for x in input_sets]
-        cv, recs = self.edwards_call(curve, units, what, None if any(k is None for k in ks) else sum(ks))
-        n_out = self.edwards_n_out(recs)
-        wi, T, lay = self._column_layout(what, input_sets, n_out, "n_out", "read", usable, tail)
-        opts = _native.DeriveOpts(*lay) if lay else None
+        cv, recs = self.edwards_call(curve, units, what, self._n_rows(input_sets))
         cs, arr = self.edwards_structs(cv, recs)
-        c, h = ctypes.create_string_buffer(48 * max(n_out, 1)), ctypes.c_uint64(0)
-        st = [(ctypes.c_uint64 * len(recs))() for _ in range(7)]
-        self._chk(self._lib.kzg_rows_commit_edwards(self._h, ni, hi, ctypes.byref(cs), len(recs), arr,
-                                                    ctypes.byref(opts) if opts is not None else None, c if n_out else None, *st,
-                                                    ctypes.byref(h)))
-        rs = RowSet(self, h.value, wi, n_out, T, [c.raw[48 * p:48 * p + 48] for p in range(n_out)]) if n_out else None
-        none = lambda xs: [None if int(v) == _native.KZG_EDWARDS_NONE else int(v) for v in xs]   # noqa: E731
-        ints = lambda xs: [int(v) for v in xs]   # noqa: E731
-        return rs, {"singular": ints(st[0]), "first_singular": none(st[1]), "mismatch": ints(st[2]), "first_mismatch": none(st[3]),
-                    "unknown": ints(st[4]), "first_unknown": none(st[5]), "segments": ints(st[6])}
+        return self._commit_units(what, self._lib.kzg_rows_commit_edwards, input_sets, ni, hi, cs, arr, self.edwards_n_out(recs),
+                                  usable, tail, self._CURVE_STATS, _native.KZG_EDWARDS_NONE)
 
     # ---- a set built from sets: columns that are plain arithmetic in resident columns, and gates checked row by row
     def commit_expr(self, input_sets: Sequence[object], exprs: Sequence[Sequence], usable: Optional[int] = None,
