@@ -1303,7 +1303,8 @@ int kzg_rows_commit_wide(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t*
  * refusals of kzg_rows_commit_derived; the handle refusals of kzg_rows_open.  After any error the context keeps serving.
  * OUT OF SCOPE: generating constants (the Grain LFSR); other exponents and the inverse S-box; the optimised partial-round form
  * (sparse matrices, pre-folded constants); sponge chaining of one block's output into the next block's input, which is
- * sequential along the column (a Merkle path is a ROW unit, a kzg_rows_commit_fetch and another ROW unit); Poseidon2.
+ * sequential along the column (a Merkle path is a ROW unit, a kzg_rows_commit_fetch and another ROW unit); Poseidon2 (it has
+ * its own call, kzg_rows_commit_poseidon2, below).
  * (Sponge chaining and Merkle paths along the column have their own call, kzg_rows_commit_poseidon_chain, below.)
  * SOUNDNESS: nothing here is a proof.  The columns are prover data; the argument is the caller's round gate over the trace
  * columns, in the quotient, under the caller's fixed rc and selector columns.  A zero mismatch count convinces no verifier. */
@@ -1337,6 +1338,48 @@ int kzg_rows_commit_poseidon(kzg_ctx* ctx, uint32_t n_input_handles, const uint6
                              const kzg_derive_opts* opts /* NULL: plain */, uint8_t* out_commitments48 /* n_out * 48 */,
                              uint64_t* out_perms /* n_units */, uint64_t* out_mismatch /* n_units */,
                              uint64_t* out_first_mismatch /* n_units */, uint64_t* out_handle);
+/* THE POSEIDON2 PERMUTATION COLUMNS: kzg_rows_commit_poseidon with the Poseidon2 permutation in place of the Hades one: the
+ * external layer has no field product and the internal layer has t, so a permutation costs R_F 3 t + R_P (3 + t) products
+ * against R_F (3 t + t^2) + R_P (3 + t^2): 408 against 816 at t = 3, (8, 56), and 819 against 4523 at t = 8, (8, 57).  The units
+ * are kzg_poseidon_unit with the field meanings, statistics, set, opts and limits of kzg_rows_commit_poseidon; only the
+ * parameters and the permutation differ.  The library generates NO constants and ships none: the caller supplies t in {2, 3, 4,
+ * 8}, R_F (even, 2 <= R_F <= 16), R_P (0 <= R_P <= 128), the t R_F full-round constants rc_full (round-major: rc_full[rho t + i]
+ * for the rho-th FULL round counted over both halves), the R_P partial-round constants rc_partial and the t entries diag, all
+ * canonical scalars of 32 big-endian bytes.  The S-box is x -> x^5.  THE EXTERNAL LAYER E:
+ *   t = 2, 3   y_i = s_i + sum_j s_j, that is circ(2, 1) and circ(2, 1, 1);
+ *   t = 4      y = M4 s, M4 = [[5, 7, 1, 3], [4, 6, 1, 1], [1, 3, 5, 7], [1, 1, 4, 6]];
+ *   t = 8      u = (M4 s[0..3], M4 s[4..7]), y_{4k+j} = u_{4k+j} + u_j + u_{4+j}, that is circ(2 M4, M4).
+ * THE INTERNAL LAYER I: y_i = diag_i s_i + sum_j s_j, the all-ones matrix plus diag(diag); the published mu_i enter as diag_i =
+ * mu_i - 1.  THE PERMUTATION of a state s, R = R_F + R_P:
+ *   1. s <- E(s);
+ *   2. R_F / 2 full rounds: s_i += rc_full[..] for every i; s_i <- s_i^5 for every i; s <- E(s);
+ *   3. R_P partial rounds: s_0 += rc_partial[rho]; s_0 <- s_0^5; s <- I(s);
+ *   4. R_F / 2 full rounds as in step 2.
+ * KZG_POSEIDON_ROW and its check are kzg_rows_commit_poseidon's.  KZG_POSEIDON_ROUNDS has the period P >= R + 2: block b occupies
+ * rows [b P, b P + P); row b P holds the input state, before the first E; row b P + 1 + rho the state BEFORE round rho, so row
+ * b P + 1 is E(input) and row b P + 1 + R the output; the remaining rows of the block and the rows behind the last whole block
+ * are 0.  The extra row against Poseidon makes every transition a uniform gate: one linear gate from row 0 to row 1, then the
+ * round gate.  KZG_E_ARG with a message that begins "poseidon2: " and names the cause: everything kzg_rows_commit_poseidon
+ * refuses, and t outside {2, 3, 4, 8}; a null rc_full, rc_partial (with R_P > 0) or diag; a constant at or above r; a period below
+ * R + 2.  (The lengths of the three lists are the caller's promise here; the Python layers check them.)
+ * OUT OF SCOPE: generating constants and published instance tables; t = 12 .. 24; exponents other than 5; Poseidon2 in
+ * kzg_rows_commit_poseidon_chain (sponges and Merkle paths); t lanes per block for traces; any change to the Poseidon kernels.
+ * SOUNDNESS: as for kzg_rows_commit_poseidon, nothing here is a proof. */
+typedef struct kzg_poseidon2_params {
+    uint32_t t, full, partial;      /* t in {2, 3, 4, 8}; R_F even in [2, 16]; R_P in [0, 128] */
+    const uint8_t* rc_full_be32;    /* t * full scalars: [rho * t + i] for element i of the rho-th FULL round over both halves */
+    const uint8_t* rc_partial_be32; /* `partial` scalars, [rho] for partial round rho; may be NULL when partial = 0 */
+    const uint8_t* diag_be32;       /* t scalars, [i] = diag_i: the internal layer is the all-ones matrix plus diag(diag) */
+} kzg_poseidon2_params;
+#define KZG_POSEIDON2_WIDTHS 0x11cu   /* bit t is set for an allowed width: 2, 3, 4, 8 */
+#define KZG_POSEIDON2_MAX_FULL 16
+#define KZG_POSEIDON2_MAX_PARTIAL 128
+#define KZG_POSEIDON2_MAX_UNITS 8
+int kzg_rows_commit_poseidon2(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                              const kzg_poseidon2_params* params, uint32_t n_units, const kzg_poseidon_unit* units,
+                              const kzg_derive_opts* opts /* NULL: plain */, uint8_t* out_commitments48 /* n_out * 48 */,
+                              uint64_t* out_perms /* n_units */, uint64_t* out_mismatch /* n_units */,
+                              uint64_t* out_first_mismatch /* n_units */, uint64_t* out_handle);
 /* THE POSEIDON SPONGE AND MERKLE-PATH CHAINS: a set built FROM sets, the two uses of the hash chip that kzg_rows_commit_poseidon
  * leaves out because one block's input depends on the block before through the permutation: a sponge over a message longer than
  * the rate, and a Merkle path.  params is kzg_poseidon_params exactly as kzg_rows_commit_poseidon reads and checks it (t in
@@ -2216,6 +2259,11 @@ int kzg_multi_rows_commit_poseidon(kzg_multi* mh, uint32_t i, uint32_t n_input_h
                                    const kzg_poseidon_params* params, uint32_t n_units, const kzg_poseidon_unit* units,
                                    const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_perms,
                                    uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_handle);
+/* kzg_rows_commit_poseidon2 on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
+int kzg_multi_rows_commit_poseidon2(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                    const kzg_poseidon2_params* params, uint32_t n_units, const kzg_poseidon_unit* units,
+                                    const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_perms,
+                                    uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_handle);
 /* kzg_rows_commit_sha256 on the device of worker i: every set named must belong to worker i, else KZG_E_ARG */
 int kzg_multi_rows_commit_sha256(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                  uint32_t n_units, const kzg_sha256_unit* units, const kzg_derive_opts* opts,

@@ -49,6 +49,9 @@ KZG_POSEIDON_IMM = 0xffffffff
 KZG_POSEIDON_NONE = 0xffffffffffffffff
 KZG_POSEIDON_MIN_T, KZG_POSEIDON_MAX_T = 2, 8
 KZG_POSEIDON_MAX_FULL, KZG_POSEIDON_MAX_PARTIAL, KZG_POSEIDON_MAX_UNITS = 16, 128, 8
+# kzg_rows_commit_poseidon2: the allowed widths (bit t set) and the limits; units, flags and "none" are kzg_rows_commit_poseidon's
+KZG_POSEIDON2_WIDTHS = 0x11c
+KZG_POSEIDON2_MAX_FULL, KZG_POSEIDON2_MAX_PARTIAL, KZG_POSEIDON2_MAX_UNITS = 16, 128, 8
 # kzg_rows_commit_poseidon_chain: kzg_poseidon_chain_unit.mode, the flag, the layouts, "no such entry", the column ids of a flat
 # unit (in_j, out_j), the limit; immediates and "none" are KZG_POSEIDON_IMM and KZG_POSEIDON_NONE
 KZG_POSEIDON_CHAIN_SPONGE, KZG_POSEIDON_CHAIN_PATH = 1, 2
@@ -197,6 +200,12 @@ class PoseidonParams(ctypes.Structure):
     _fields_ = [("t", _U32), ("full", _U32), ("partial", _U32), ("rc_be32", ctypes.c_char_p), ("mds_be32", ctypes.c_char_p)]
 
 
+class Poseidon2Params(ctypes.Structure):
+    """kzg_poseidon2_params"""
+    _fields_ = [("t", _U32), ("full", _U32), ("partial", _U32), ("rc_full_be32", ctypes.c_char_p),
+                ("rc_partial_be32", ctypes.c_char_p), ("diag_be32", ctypes.c_char_p)]
+
+
 class PoseidonUnit(ctypes.Structure):
     """kzg_poseidon_unit"""
     _fields_ = [("mode", _U32), ("flags", _U32), ("n_out", _U32), ("period", _U32), ("in_", _U32 * 8), ("out", _U32 * 8),
@@ -331,6 +340,9 @@ SYMBOLS = {
     "kzg_rows_commit_poseidon": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(PoseidonParams), _U32,
                                       ctypes.POINTER(PoseidonUnit), ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64),
                                       ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_rows_commit_poseidon2": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(Poseidon2Params), _U32,
+                                       ctypes.POINTER(PoseidonUnit), ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64),
+                                       ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_rows_commit_poseidon_chain": (_I, [_P, _U32, ctypes.POINTER(_U64), ctypes.POINTER(PoseidonParams), _U32,
                                             ctypes.POINTER(PoseidonChainUnit), ctypes.POINTER(DeriveOpts), _B]
                                        + [ctypes.POINTER(_U64)] * 7),
@@ -472,6 +484,9 @@ SYMBOLS = {
     "kzg_multi_rows_commit_poseidon": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(PoseidonParams), _U32,
                                             ctypes.POINTER(PoseidonUnit), ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64),
                                             ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "kzg_multi_rows_commit_poseidon2": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(Poseidon2Params), _U32,
+                                             ctypes.POINTER(PoseidonUnit), ctypes.POINTER(DeriveOpts), _B, ctypes.POINTER(_U64),
+                                             ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "kzg_multi_rows_commit_poseidon_chain": (_I, [_P, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(PoseidonParams), _U32,
                                                   ctypes.POINTER(PoseidonChainUnit), ctypes.POINTER(DeriveOpts), _B]
                                              + [ctypes.POINTER(_U64)] * 7),

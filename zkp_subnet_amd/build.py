@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libkzg_mi355x.so")
-SOURCES = ["msm_sort.hip", "msm_accumulate.hip", "msm_tree.hip", "g1_kernels.hip", "srs_kernels.hip", "fr_ntt.hip", "fr_poly.hip", "fr_prod.hip", "fr_quot.hip", "fr_lookup.hip", "fr_join.hip", "fr_sort.hip", "fr_sigma.hip", "fr_derive.hip", "fr_int.hip", "fr_alu.hip", "fr_wide.hip", "fr_poseidon.hip", "fr_poseidon_chain.hip", "fr_sha256.hip", "fr_keccak.hip", "fr_ec.hip", "fr_edwards.hip", "fr_expr.hip", "fr_recur.hip", "fr_blind.hip", "lanes.hip", "srs.hip", "pipeline.hip", "serve.hip", "comm.hip", "abi_test.hip", "calibrate.hip",
+SOURCES = ["msm_sort.hip", "msm_accumulate.hip", "msm_tree.hip", "g1_kernels.hip", "srs_kernels.hip", "fr_ntt.hip", "fr_poly.hip", "fr_prod.hip", "fr_quot.hip", "fr_lookup.hip", "fr_join.hip", "fr_sort.hip", "fr_sigma.hip", "fr_derive.hip", "fr_int.hip", "fr_alu.hip", "fr_wide.hip", "fr_poseidon.hip", "fr_poseidon2.hip", "fr_poseidon_chain.hip", "fr_sha256.hip", "fr_keccak.hip", "fr_ec.hip", "fr_edwards.hip", "fr_expr.hip", "fr_recur.hip", "fr_blind.hip", "lanes.hip", "srs.hip", "pipeline.hip", "serve.hip", "comm.hip", "abi_test.hip", "calibrate.hip",
            "pairing_host.cpp", "finish_host.cpp", "rccl_dl.cpp", "multi_host.cpp", "wire_host.cpp"]
 # dev-only prototypes (scripts/proto/), linked only when KZG_WITH_PROTO=1: never part of the shipped library
 PROTO_SOURCES = ["../../scripts/proto/baff_proto.hip"]

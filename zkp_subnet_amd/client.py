@@ -1070,6 +1070,31 @@ class Client:
                 "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments],
                 "perms": st["perms"], "mismatch": st["mismatch"], "first_mismatch": st["first_mismatch"]}
 
+    # ---- the hash chip a prover picks today: the Poseidon2 permutation, the units of worker_commit_poseidon
+    @_guard
+    def worker_commit_poseidon2(self, input_handles: Sequence[int], params: dict, units: Sequence[dict],
+                                usable: Optional[int] = None, tail: Sequence[str] = ()):
+        """Extension: Poseidon2 permutation columns of the rows of the input_handles sets, computed and committed on the device
+        as one new set: worker_commit_poseidon with another permutation.  params: {"t", "full", "partial", "rc_full",
+        "rc_partial", "diag"}: t in {2, 3, 4, 8}, R_F full rounds (even, 2 .. 16), R_P partial rounds (0 .. 128), the t R_F
+        full-round constants round-major over both halves, the R_P partial-round constants, the t entries of diag; scalars below
+        r as integers or decimal / 0x strings.  The library generates no constants.  s <- E(s); R_F / 2 full rounds (s_i +=
+        rc_full[..]; s_i <- s_i^5 for every i; s <- E(s)); R_P partial rounds (s_0 += rc_partial[rho]; s_0 <- s_0^5; s <- I(s));
+        R_F / 2 full rounds.  E: y_i = s_i + sum s_j at t = 2, 3; M4 = [[5, 7, 1, 3], [4, 6, 1, 1], [1, 3, 5, 7], [1, 1, 4, 6]] at t =
+        4; circ(2 M4, M4) at t = 8.  I: y_i = diag_i s_i + sum s_j (the published mu_i enter as diag_i = mu_i - 1).  units: as
+        for worker_commit_poseidon, except that a rounds unit needs P >= R + 2: row b P of block b holds the input, row b P + 1 +
+        rho the state before round rho (row b P + 1 is E(input)), row b P + 1 + R the output, the rest is 0.  usable and tail:
+        as for worker_commit_derived.  Returns the handle (null when every unit is a check), the commitments, and per unit
+        `perms`, `mismatch`, `first_mismatch`.  Nothing here is a proof."""
+        what = "worker_commit_poseidon2"
+        hs = _handles(input_handles)
+        recs, par = self._unit_objects(what, units, ("in",), params=params), dict(params)
+        usable, tb = self._layout(what, usable, tail)
+        rs, st = self.engine.commit_poseidon2(hs, par, recs, usable, tb)
+        return {"handle": None if rs is None else int(rs.handle),
+                "commitments": [] if rs is None else [codec.g1_to_b64(c) for c in rs.commitments],
+                "perms": st["perms"], "mismatch": st["mismatch"], "first_mismatch": st["first_mismatch"]}
+
     # ---- the hash chip's chains: a Poseidon sponge over a long message, a Merkle path, block after block along the column
     @_guard
     def worker_commit_poseidon_chain(self, input_handles: Sequence[int], params: dict, units: Sequence[dict],

@@ -11,6 +11,7 @@
 //   fr_alu.hip    the kernel of kzg_rows_commit_alu: the same arithmetic and its signed kinds, the kind chosen per cell by an op-code column
 //   fr_wide.hip   the kernel of kzg_rows_commit_wide: multi-limb add, sub, mul, divmod, mulmod and the carries of its limb identity
 //   fr_poseidon.hip the kernel of kzg_rows_commit_poseidon: the Hades permutation with x^5 per row, as a check, or as a round trace
+//   fr_poseidon2.hip the kernel of kzg_rows_commit_poseidon2: the Poseidon2 permutation with x^5 (product-free external layer) per row, as a check, or as a round trace
 //   fr_poseidon_chain.hip the kernel of kzg_rows_commit_poseidon_chain: sponge and Merkle-path chains over blocks, one lane walking each segment
 //   fr_sha256.hip the kernel of kzg_rows_commit_sha256: the SHA-256 compression per row, as a check, or as a chained round trace
 //   fr_keccak.hip the kernel of kzg_rows_commit_keccak: Keccak-f[1600] per row, as a check, or as a chained round trace of 64-bit lanes
@@ -515,6 +516,11 @@ int rows_wide_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, u
 int rows_poseidon_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const kzg_poseidon_params* params,
                       uint32_t n_units, const kzg_poseidon_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst,
                       uint8_t* out_c48, uint64_t* out_stats, const Blind* lay);
+// rows_poseidon_dev with the Poseidon2 parameters (checked by the caller: t in {2, 3, 4, 8}, R_F, R_P, periods of at least R + 2,
+// canonical constants); the units, the statistics and lay are rows_poseidon_dev's
+int rows_poseidon2_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const kzg_poseidon2_params* params,
+                       uint32_t n_units, const kzg_poseidon_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst,
+                       uint8_t* out_c48, uint64_t* out_stats, const Blind* lay);
 // the n_out committed columns of the n_units SHA-256 units (checked by the caller: modes, flags, periods, out lists, rows inside
 // `inputs`) into a new n_out-row set's buffer dst (null when n_out = 0: then no transform back and no MSM runs): their
 // commitments and five runs of n_units statistics (over-range cells, mismatching rows, messages, then the smallest row of the

@@ -472,6 +472,13 @@ static_assert(sizeof(PosTab) + 64 <= 4096 && POLY_MAX_ROWS < POS_IMM, "the unit 
 // full + partial + 1, canonical constants: the caller's checks
 uint32_t poseidon_cst_words(uint32_t t, uint32_t rounds, uint32_t n_units);
 void launch_poseidon(hipStream_t s, const PosTab& tab, uint64_t T, uint64_t n, uint64_t* stats);
+// ---- the Poseidon2 permutation columns of kzg_rows_commit_poseidon2 (fr_poseidon2.hip).  The table is PosTab and the units are
+// PosUnit exactly as launch_poseidon reads them, with two differences: a ROUNDS unit writes the input at its block's first row,
+// E(input) at the next and the state behind round rho at row 2 + rho (period >= full + partial + 2); cst holds t x full
+// full-round constants (round-major over both halves), `partial` partial-round constants, t diagonal entries, then t
+// immediates per unit.  t in {2, 3, 4, 8}; stats as for launch_poseidon
+uint32_t poseidon2_cst_words(uint32_t t, uint32_t full, uint32_t partial, uint32_t n_units);
+void launch_poseidon2(hipStream_t s, const PosTab& tab, uint64_t T, uint64_t n, uint64_t* stats);
 // ---- the Poseidon sponge and Merkle-path chains of kzg_rows_commit_poseidon_chain (fr_poseidon_chain.hip).  t, full, partial and
 // cst are PosTab's (t immediates per unit).  A unit walks the blocks of `period` rows, b < floor(n / period); block b starts a
 // segment where b = 0, `start` is PCH_NONE or the cell of source vector `start` at the block's first row is not zero, and

@@ -540,6 +540,15 @@ int kzg_multi_rows_commit_poseidon(kzg_multi* mh, uint32_t i, uint32_t n_input_h
                                        out_perms, out_mismatch, out_first_mismatch, out_handle);
     });
 }
+int kzg_multi_rows_commit_poseidon2(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
+                                    const kzg_poseidon2_params* params, uint32_t n_units, const kzg_poseidon_unit* units,
+                                    const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_perms,
+                                    uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_handle) {
+    return routed(mh, i, [&](kzg_ctx* c, uint32_t s) {
+        return kzg_impl::rows_poseidon2(c, s, n_input_handles, input_handles, params, n_units, units, opts, out_commitments48,
+                                        out_perms, out_mismatch, out_first_mismatch, out_handle);
+    });
+}
 int kzg_multi_rows_commit_poseidon_chain(kzg_multi* mh, uint32_t i, uint32_t n_input_handles, const uint64_t* input_handles,
                                          const kzg_poseidon_params* params, uint32_t n_units,
                                          const kzg_poseidon_chain_unit* units, const kzg_derive_opts* opts,

@@ -1596,9 +1596,25 @@ static std::vector<uint32_t> poseidon_constants(const kzg_poseidon_params* param
         for (uint32_t j = 0; j < t; j++) poseidon_words(&cst[8 * (t * R + t * t + u * t + j)], units[u].imm_be32[j]);
     return cst;
 }
-int rows_poseidon_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const kzg_poseidon_params* params,
-                      uint32_t n_units, const kzg_poseidon_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst,
-                      uint8_t* out_c48, uint64_t* out_stats, const Blind* lay) {
+// the constants of kzg_rows_commit_poseidon2 in the order of poseidon2_cst_words: rc_full, rc_partial, diag, every unit's immediates
+static std::vector<uint32_t> poseidon2_constants(const kzg_poseidon2_params* params, uint32_t n_units,
+                                                 const kzg_poseidon_unit* units) {
+    const uint32_t t = params->t, nf = t * params->full, np = params->partial;
+    std::vector<uint32_t> cst(poseidon2_cst_words(t, params->full, np, n_units), 0);
+    for (uint32_t k = 0; k < nf; k++) poseidon_words(&cst[8 * k], params->rc_full_be32 + 32 * (size_t)k);
+    for (uint32_t k = 0; k < np; k++) poseidon_words(&cst[8 * (nf + k)], params->rc_partial_be32 + 32 * (size_t)k);
+    for (uint32_t k = 0; k < t; k++) poseidon_words(&cst[8 * (nf + np + k)], params->diag_be32 + 32 * (size_t)k);
+    for (uint32_t u = 0; u < n_units; u++)
+        for (uint32_t j = 0; j < t; j++) poseidon_words(&cst[8 * (nf + np + t + u * t + j)], units[u].imm_be32[j]);
+    return cst;
+}
+// The body of rows_poseidon_dev and rows_poseidon2_dev: the table of the units, the steps above, `launch` the builder's kernel;
+// cst: its constants as words (they live until the MSM pass has waited)
+static int poseidon_units_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, uint32_t t, uint32_t full,
+                              uint32_t partial, const std::vector<uint32_t>& cst,
+                              void (*launch)(hipStream_t, const PosTab&, uint64_t, uint64_t, uint64_t*), uint32_t n_units,
+                              const kzg_poseidon_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst, uint8_t* out_c48,
+                              uint64_t* out_stats, const Blind* lay) {
     Lane& A = H.L();
     Cols F;
     if (int rc = cols_begin(ctx, A, T, lay, dst, F)) return rc;
@@ -1608,15 +1624,13 @@ int rows_poseidon_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& input
                       KZG_POSEIDON_ROW == POS_ROW && KZG_POSEIDON_ROUNDS == POS_ROUNDS,
                   "the two statistics of every unit (mismatches, then the first rows) fit the record's evaluation slots; the "
                   "header's caps are the kernel's");
-    const uint32_t t = params->t, R = params->full + params->partial;
     Sources S;
     PosTab tab;
     memset(&tab, 0, sizeof(tab));
     tab.t = t;
-    tab.full = params->full;
-    tab.partial = params->partial;
+    tab.full = full;
+    tab.partial = partial;
     tab.n_units = n_units;
-    const std::vector<uint32_t> cst = poseidon_constants(params, n_units, units);   // (lives until the MSM pass has waited)
     const uint32_t cw = (uint32_t)cst.size();
     for (uint32_t u = 0; u < n_units; u++) {
         const kzg_poseidon_unit& in = units[u];
@@ -1647,9 +1661,28 @@ int rows_poseidon_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& input
         return rc;
     {
         Span sp(ctx, A, KZG_T_POLY);
-        launch_poseidon(A.stream, tab, T, n, st);
+        launch(A.stream, tab, T, n, st);
     }
     return units_finish(ctx, H, i, F, outv, n_out, 16 * n_units, out_c48, out_stats);
+}
+int rows_poseidon_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const kzg_poseidon_params* params,
+                      uint32_t n_units, const kzg_poseidon_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst,
+                      uint8_t* out_c48, uint64_t* out_stats, const Blind* lay) {
+    return poseidon_units_dev(ctx, H, i, inputs, params->t, params->full, params->partial,
+                              poseidon_constants(params, n_units, units), launch_poseidon, n_units, units, n_out, T, dst, out_c48,
+                              out_stats, lay);
+}
+// The Poseidon2 permutation columns (kzg_rows_commit_poseidon2): the frame, the steps and the statistics of rows_poseidon_dev
+// with launch_poseidon2 (k_fr_poseidon2<t>) and its constants: t R_F + R_P + t scalars and the immediates
+int rows_poseidon2_dev(kzg_ctx* ctx, LaneHold& H, uint32_t i, const RowTab& inputs, const kzg_poseidon2_params* params,
+                       uint32_t n_units, const kzg_poseidon_unit* units, uint32_t n_out, uint64_t T, uint32_t* dst,
+                       uint8_t* out_c48, uint64_t* out_stats, const Blind* lay) {
+    static_assert(16 * KZG_POSEIDON2_MAX_UNITS <= STATS_MAX && KZG_POSEIDON2_MAX_UNITS == POS_MAX_UNITS &&
+                      KZG_POSEIDON2_MAX_FULL + KZG_POSEIDON2_MAX_PARTIAL == POS_MAX_ROUNDS && (KZG_POSEIDON2_WIDTHS >> (POS_MAX_T + 1)) == 0,
+                  "the two statistics of every unit fit the record's evaluation slots; the header's caps are the kernel's");
+    return poseidon_units_dev(ctx, H, i, inputs, params->t, params->full, params->partial,
+                              poseidon2_constants(params, n_units, units), launch_poseidon2, n_units, units, n_out, T, dst,
+                              out_c48, out_stats, lay);
 }
 
 // The Poseidon sponge and Merkle-path chains (kzg_rows_commit_poseidon_chain), in the builders' frame, with checks as

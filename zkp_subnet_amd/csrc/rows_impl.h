@@ -82,6 +82,11 @@ int rows_poseidon(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, con
                   uint8_t* out_commitments48, uint64_t* out_perms, uint64_t* out_mismatch, uint64_t* out_first_mismatch,
                   uint64_t* out_handle);
 // opts: as for rows_derived
+int rows_poseidon2(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                   const kzg_poseidon2_params* params, uint32_t n_units, const kzg_poseidon_unit* units,
+                   const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_perms, uint64_t* out_mismatch,
+                   uint64_t* out_first_mismatch, uint64_t* out_handle);
+// opts: as for rows_derived
 int rows_sha256(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_units,
                 const kzg_sha256_unit* units, const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_blocks,
                 uint64_t* out_messages, uint64_t* out_counts, uint64_t* out_first, uint64_t* out_mismatch,

@@ -1577,6 +1577,12 @@ int rows_wide(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const u
     return KZG_OK;
 }
 
+// The ranges of R_F and R_P in the words of every Poseidon parameter check: the refusal, or null
+static const char* poseidon_rounds_why(uint32_t full, uint32_t partial) {
+    if (full < 2 || full > KZG_POSEIDON_MAX_FULL || (full & 1)) return "the number of full rounds R_F must be even and in [2, 16]";
+    if (partial > KZG_POSEIDON_MAX_PARTIAL) return "the number of partial rounds R_P must be in [0, 128]";
+    return nullptr;
+}
 // The checks of kzg_poseidon_params, shared by kzg_rows_commit_poseidon and kzg_rows_commit_poseidon_chain (`what` prefixes the
 // messages): the ranges of t, R_F and R_P, then the number of units (units_ok, with the words of its refusal), then every
 // constant and matrix entry canonical
@@ -1586,14 +1592,87 @@ static int poseidon_params_check(kzg_ctx* ctx, const char* what, const kzg_posei
     if (!params || !params->rc_be32 || !params->mds_be32) return bad("params, rc_be32 and mds_be32 must not be null");
     const uint32_t t = params->t, R = params->full + params->partial;
     if (t < KZG_POSEIDON_MIN_T || t > KZG_POSEIDON_MAX_T) return bad("the width t must be in [2, 8]");
-    if (params->full < 2 || params->full > KZG_POSEIDON_MAX_FULL || (params->full & 1))
-        return bad("the number of full rounds R_F must be even and in [2, 16]");
-    if (params->partial > KZG_POSEIDON_MAX_PARTIAL) return bad("the number of partial rounds R_P must be in [0, 128]");
+    if (const char* why = poseidon_rounds_why(params->full, params->partial)) return bad(why);
     if (!units_ok) return bad(units_why);
     for (uint32_t k = 0; k < t * R; k++)
         if (!fr_be32_canonical(params->rc_be32 + 32 * (size_t)k)) return bad("round constants must be canonical scalars (< r)");
     for (uint32_t k = 0; k < t * t; k++)
         if (!fr_be32_canonical(params->mds_be32 + 32 * (size_t)k)) return bad("matrix entries must be canonical scalars (< r)");
+    return KZG_OK;
+}
+// The checks of kzg_poseidon2_params, in the same order: t, R_F and R_P, the number of units, every constant canonical
+static int poseidon2_params_check(kzg_ctx* ctx, const kzg_poseidon2_params* params, bool units_ok) {
+    auto bad = [&](const char* why) { return fail(ctx, KZG_E_ARG, std::string("poseidon2: ") + why); };
+    if (!params || !params->rc_full_be32 || !params->diag_be32 || (params->partial && !params->rc_partial_be32))
+        return bad("params, rc_full_be32, rc_partial_be32 (with R_P > 0) and diag_be32 must not be null");
+    const uint32_t t = params->t;
+    if (t >= 32 || !(KZG_POSEIDON2_WIDTHS >> t & 1)) return bad("the width t must be 2, 3, 4 or 8");
+    if (const char* why = poseidon_rounds_why(params->full, params->partial)) return bad(why);
+    if (!units_ok) return bad("n_units must be in [1, KZG_POSEIDON2_MAX_UNITS]");
+    for (uint32_t k = 0; k < t * params->full; k++)
+        if (!fr_be32_canonical(params->rc_full_be32 + 32 * (size_t)k)) return bad("round constants must be canonical scalars (< r)");
+    for (uint32_t k = 0; k < params->partial; k++)
+        if (!fr_be32_canonical(params->rc_partial_be32 + 32 * (size_t)k)) return bad("round constants must be canonical scalars (< r)");
+    for (uint32_t k = 0; k < t; k++)
+        if (!fr_be32_canonical(params->diag_be32 + 32 * (size_t)k)) return bad("diagonal entries must be canonical scalars (< r)");
+    return KZG_OK;
+}
+
+// The units of kzg_rows_commit_poseidon and kzg_rows_commit_poseidon2 (one struct, one meaning), behind the parameter checks:
+// modes, flags, periods (a trace block holds R + lead rows: lead = 1 for Poseidon, 2 for Poseidon2 with its row of E(input)), out
+// lists, immediates and the two caps; then the UnitCall, the builder's device call `dev`, the statistics and the new set.
+// `what` prefixes the messages
+template <class Dev>
+static int rows_poseidon_units(kzg_ctx* ctx, const char* what, uint32_t t, uint32_t R, uint32_t lead, uint32_t expect_i,
+                               uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_units,
+                               const kzg_poseidon_unit* units, const kzg_derive_opts* opts, uint8_t* out_commitments48,
+                               uint64_t* out_perms, uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_handle,
+                               Dev dev) {
+    auto bad = [&](const std::string& why) { return fail(ctx, KZG_E_ARG, std::string(what) + ": " + why); };
+    uint32_t n_out = 0;
+    SeenRows S;
+    for (uint32_t u = 0; u < n_units; u++) {
+        const kzg_poseidon_unit& U = units[u];
+        if (U.mode != KZG_POSEIDON_ROW && U.mode != KZG_POSEIDON_ROUNDS)
+            return bad("unknown mode (KZG_POSEIDON_ROW or KZG_POSEIDON_ROUNDS)");
+        if (U.flags & ~KZG_POSEIDON_CHECK) return bad("flags must be 0 or KZG_POSEIDON_CHECK");
+        const bool rounds = U.mode == KZG_POSEIDON_ROUNDS, check = U.flags == KZG_POSEIDON_CHECK;
+        if (rounds && check) return bad("expect (KZG_POSEIDON_CHECK) belongs to ROW units, not to ROUNDS");
+        if (rounds ? U.period < R + lead : U.period != 0)
+            return bad("the period P of a ROUNDS unit must be at least R + " + std::to_string(lead) + " (0 on a ROW unit)");
+        if (rounds ? U.n_out != t : (U.n_out == 0 || U.n_out > t))
+            return bad("n_out must be in [1, t] on a ROW unit and t on a ROUNDS unit");
+        uint32_t taken = 0;
+        for (uint32_t c = 0; c < U.n_out; c++) {
+            if (U.out[c] >= t || (rounds && U.out[c] != c)) return bad("an out index must be below t (ROUNDS: out[j] = j)");
+            if (taken >> U.out[c] & 1) return bad("an out index is repeated");
+            taken |= 1u << U.out[c];
+            if (check) S.see(U.expect[c]);
+        }
+        for (uint32_t j = 0; j < t; j++) {
+            if (U.in[j] != KZG_POSEIDON_IMM) {
+                S.see(U.in[j]);
+                for (int b = 0; b < 32; b++)
+                    if (U.imm_be32[j][b]) return bad("the immediate must be 0 beside a row");
+            } else if (!fr_be32_canonical(U.imm_be32[j])) {
+                return bad("immediates must be canonical scalars (< r)");
+            }
+        }
+        if (S.too_many()) return bad("a call reads at most KZG_MAX_BATCH_OPEN distinct input rows");
+        n_out += check ? 0 : U.n_out;
+    }
+    if (n_out > KZG_MAX_BATCH_OPEN) return bad("n_out, the committed columns of all units, must be at most KZG_MAX_BATCH_OPEN");
+    if (n_out && !out_commitments48) return KZG_E_ARG;
+    UnitCall C(ctx, what);
+    if (int rc = C.open(expect_i, n_input_handles, input_handles, S.n != 0, S.max_row, ROW_WHY, n_out, opts)) return rc;
+    uint64_t stats[2 * KZG_POSEIDON_MAX_UNITS];
+    if (int rc = dev(C, n_out, stats)) return rc;
+    const uint64_t n = C.n_read();
+    for (uint32_t u = 0; u < n_units; u++) out_perms[u] = units[u].mode == KZG_POSEIDON_ROUNDS ? n / units[u].period : n;
+    static const int run_of[3] = {-1, 0, 1};   // the device's runs: mismatches, then their first rows
+    uint64_t* const out[3] = {out_perms, out_mismatch, out_first_mismatch};
+    stats_scatter(out, run_of, 3, stats, n_units);
+    C.finish(out_commitments48, out_handle);
     return KZG_OK;
 }
 
@@ -1609,55 +1688,28 @@ int rows_poseidon(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, con
     if (int rc = poseidon_params_check(ctx, "poseidon", params, n_units != 0 && n_units <= KZG_POSEIDON_MAX_UNITS && units,
                                        "n_units must be in [1, KZG_POSEIDON_MAX_UNITS]"))
         return rc;
-    const uint32_t t = params->t, R = params->full + params->partial;
-    uint32_t n_out = 0;
-    SeenRows S;
-    for (uint32_t u = 0; u < n_units; u++) {
-        const kzg_poseidon_unit& U = units[u];
-        if (U.mode != KZG_POSEIDON_ROW && U.mode != KZG_POSEIDON_ROUNDS)
-            return fail(ctx, KZG_E_ARG, "poseidon: unknown mode (KZG_POSEIDON_ROW or KZG_POSEIDON_ROUNDS)");
-        if (U.flags & ~KZG_POSEIDON_CHECK) return fail(ctx, KZG_E_ARG, "poseidon: flags must be 0 or KZG_POSEIDON_CHECK");
-        const bool rounds = U.mode == KZG_POSEIDON_ROUNDS, check = U.flags == KZG_POSEIDON_CHECK;
-        if (rounds && check) return fail(ctx, KZG_E_ARG, "poseidon: expect (KZG_POSEIDON_CHECK) belongs to ROW units, not to ROUNDS");
-        if (rounds ? U.period <= R : U.period != 0)
-            return fail(ctx, KZG_E_ARG, "poseidon: the period P of a ROUNDS unit must be at least R + 1 (0 on a ROW unit)");
-        if (rounds ? U.n_out != t : (U.n_out == 0 || U.n_out > t))
-            return fail(ctx, KZG_E_ARG, "poseidon: n_out must be in [1, t] on a ROW unit and t on a ROUNDS unit");
-        uint32_t taken = 0;
-        for (uint32_t c = 0; c < U.n_out; c++) {
-            if (U.out[c] >= t || (rounds && U.out[c] != c))
-                return fail(ctx, KZG_E_ARG, "poseidon: an out index must be below t (ROUNDS: out[j] = j)");
-            if (taken >> U.out[c] & 1) return fail(ctx, KZG_E_ARG, "poseidon: an out index is repeated");
-            taken |= 1u << U.out[c];
-            if (check) S.see(U.expect[c]);
-        }
-        for (uint32_t j = 0; j < t; j++) {
-            if (U.in[j] != KZG_POSEIDON_IMM) {
-                S.see(U.in[j]);
-                for (int b = 0; b < 32; b++)
-                    if (U.imm_be32[j][b]) return fail(ctx, KZG_E_ARG, "poseidon: the immediate must be 0 beside a row");
-            } else if (!fr_be32_canonical(U.imm_be32[j])) {
-                return fail(ctx, KZG_E_ARG, "poseidon: immediates must be canonical scalars (< r)");
-            }
-        }
-        if (S.too_many())
-            return fail(ctx, KZG_E_ARG, "poseidon: a call reads at most KZG_MAX_BATCH_OPEN distinct input rows");
-        n_out += check ? 0 : U.n_out;
-    }
-    if (n_out > KZG_MAX_BATCH_OPEN)
-        return fail(ctx, KZG_E_ARG, "poseidon: n_out, the committed columns of all units, must be at most KZG_MAX_BATCH_OPEN");
-    if (n_out && !out_commitments48) return KZG_E_ARG;
-    UnitCall C(ctx, "poseidon");
-    if (int rc = C.open(expect_i, n_input_handles, input_handles, S.n != 0, S.max_row, ROW_WHY, n_out, opts)) return rc;
-    uint64_t stats[2 * KZG_POSEIDON_MAX_UNITS];
-    if (int rc = rows_poseidon_dev(ctx, C.H, C.i, C.it, params, n_units, units, n_out, C.T, C.dst(), C.c48, stats, C.blind)) return rc;
-    const uint64_t n = C.n_read();
-    for (uint32_t u = 0; u < n_units; u++) out_perms[u] = units[u].mode == KZG_POSEIDON_ROUNDS ? n / units[u].period : n;
-    static const int run_of[3] = {-1, 0, 1};   // the device's runs: mismatches, then their first rows
-    uint64_t* const out[3] = {out_perms, out_mismatch, out_first_mismatch};
-    stats_scatter(out, run_of, 3, stats, n_units);
-    C.finish(out_commitments48, out_handle);
-    return KZG_OK;
+    return rows_poseidon_units(ctx, "poseidon", params->t, params->full + params->partial, 1, expect_i, n_input_handles,
+                               input_handles, n_units, units, opts, out_commitments48, out_perms, out_mismatch,
+                               out_first_mismatch, out_handle, [&](UnitCall& C, uint32_t n_out, uint64_t* stats) {
+                                   return rows_poseidon_dev(ctx, C.H, C.i, C.it, params, n_units, units, n_out, C.T, C.dst(),
+                                                            C.c48, stats, C.blind);
+                               });
+}
+
+// kzg_rows_commit_poseidon2: rows_poseidon with its own parameters and device call; a trace block has one row more
+int rows_poseidon2(kzg_ctx* ctx, uint32_t expect_i, uint32_t n_input_handles, const uint64_t* input_handles,
+                   const kzg_poseidon2_params* params, uint32_t n_units, const kzg_poseidon_unit* units,
+                   const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_perms, uint64_t* out_mismatch,
+                   uint64_t* out_first_mismatch, uint64_t* out_handle) {
+    if (!ctx || !input_handles || !out_perms || !out_mismatch || !out_first_mismatch || !out_handle) return KZG_E_ARG;
+    if (int rc = UnitCall::handles_ok(ctx, "poseidon2", n_input_handles)) return rc;
+    if (int rc = poseidon2_params_check(ctx, params, n_units != 0 && n_units <= KZG_POSEIDON2_MAX_UNITS && units)) return rc;
+    return rows_poseidon_units(ctx, "poseidon2", params->t, params->full + params->partial, 2, expect_i, n_input_handles,
+                               input_handles, n_units, units, opts, out_commitments48, out_perms, out_mismatch,
+                               out_first_mismatch, out_handle, [&](UnitCall& C, uint32_t n_out, uint64_t* stats) {
+                                   return rows_poseidon2_dev(ctx, C.H, C.i, C.it, params, n_units, units, n_out, C.T, C.dst(),
+                                                             C.c48, stats, C.blind);
+                               });
 }
 
 // kzg_rows_commit_poseidon_chain: a BuilderCall around its own checks; as in rows_poseidon, no reservation and no set when every
@@ -3034,6 +3086,13 @@ int kzg_rows_commit_poseidon(kzg_ctx* ctx, uint32_t n_input_handles, const uint6
                              uint64_t* out_first_mismatch, uint64_t* out_handle) {
     return rows_poseidon(ctx, UINT32_MAX, n_input_handles, input_handles, params, n_units, units, opts, out_commitments48,
                          out_perms, out_mismatch, out_first_mismatch, out_handle);
+}
+int kzg_rows_commit_poseidon2(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles,
+                              const kzg_poseidon2_params* params, uint32_t n_units, const kzg_poseidon_unit* units,
+                              const kzg_derive_opts* opts, uint8_t* out_commitments48, uint64_t* out_perms,
+                              uint64_t* out_mismatch, uint64_t* out_first_mismatch, uint64_t* out_handle) {
+    return rows_poseidon2(ctx, UINT32_MAX, n_input_handles, input_handles, params, n_units, units, opts, out_commitments48,
+                          out_perms, out_mismatch, out_first_mismatch, out_handle);
 }
 int kzg_rows_commit_sha256(kzg_ctx* ctx, uint32_t n_input_handles, const uint64_t* input_handles, uint32_t n_units,
                            const kzg_sha256_unit* units, const kzg_derive_opts* opts, uint8_t* out_commitments48,

@@ -1430,8 +1430,14 @@ class HipEngine:
         index or ("imm", value).  A scalar is an int, a decimal or 0x string, or 32 big-endian bytes, below r.  Raises
         KzgError(KZG_E_ARG) with the cause; needs no device."""
         sp = _UnitSpec(what, "poseidon")
-        bad = sp.bad
         t, R, par = cls._poseidon_params(params, sp)
+        return par, cls._poseidon_units(sp, t, R, 1, units)
+
+    @classmethod
+    def _poseidon_units(cls, sp, t: int, R: int, lead: int, units) -> List[tuple]:
+        """The units of poseidon_call and poseidon2_call, parsed by one body into kzg_poseidon_unit fields; a trace block holds
+        R + lead rows (lead = 1: Poseidon; 2: Poseidon2, with its row of E(input)); sp: the caller's _UnitSpec"""
+        bad = sp.bad
         recs = []
         for un in sp.units(units, _native.KZG_POSEIDON_MAX_UNITS):
             if not isinstance(un, dict) or "mode" not in un or "in" not in un:
@@ -1450,8 +1456,8 @@ class HipEngine:
                     raise bad("expect belongs to row units, not to rounds")
                 if un.get("out") is not None:
                     raise bad("out belongs to row units: a rounds unit commits all t columns")
-                period = sp.period(un.get("period"), R + 1,
-                                   lambda: f"the period P of a rounds unit must be an integer in [R + 1, 2^32), R + 1 = {R + 1}")
+                period = sp.period(un.get("period"), R + lead, lambda: "the period P of a rounds unit must be an integer in "
+                                   f"[R + {lead}, 2^32), R + {lead} = {R + lead}")
                 out = list(range(t))
             else:
                 if un.get("period") is not None:
@@ -1463,7 +1469,7 @@ class HipEngine:
             recs.append((_native.KZG_POSEIDON_ROW if mode == "row" else _native.KZG_POSEIDON_ROUNDS, flags, len(out), period,
                          _pad(rows, 8), _pad(out, 8), _pad(expect, 8), _pad(imms, 8, _ZERO32)))
         sp.caps(sum(r[2] for r in recs if not r[1]))
-        return par, recs
+        return recs
 
     @staticmethod
     def poseidon_unit_struct(rec) -> "_native.PoseidonUnit":
@@ -1491,8 +1497,53 @@ class HipEngine:
                                   sum(r[2] for r in recs if not r[1]), usable, tail,
                                   (("perms", 0), ("mismatch", 0), ("first_mismatch", 1)), _native.KZG_POSEIDON_NONE)
 
+    # ---- a set built from sets: the Poseidon2 permutation (product-free external layer), the units of commit_poseidon
+    _POSEIDON2_PARAM_KEYS = ("t", "full", "partial", "rc_full", "rc_partial", "diag")
+    _POSEIDON2_WIDTHS = tuple(t for t in range(32) if _native.KZG_POSEIDON2_WIDTHS >> t & 1)
+
+    @classmethod
+    def poseidon2_call(cls, params, units, what: str = "commit_poseidon2") -> Tuple[tuple, List[tuple]]:
+        """The kzg_poseidon2_params fields (t, full, partial, rc_full bytes, rc_partial bytes, diag bytes) and per unit the
+        kzg_poseidon_unit fields as poseidon_call returns them (from the same body).  params: a mapping with t (2, 3, 4 or 8),
+        full (R_F, even, 2 .. 16), partial (R_P, 0 .. 128), rc_full (t R_F scalars, round-major over the full rounds of both
+        halves), rc_partial (R_P scalars) and diag (t scalars: the internal layer is the all-ones matrix plus diag).  Units: as
+        for poseidon_call, with a period of at least R_F + R_P + 2.  Raises KzgError(KZG_E_ARG) with the cause; needs no device."""
+        sp = _UnitSpec(what, "poseidon2")
+        bad = sp.bad
+        if not isinstance(params, dict) or set(params) != set(cls._POSEIDON2_PARAM_KEYS):
+            raise bad(f"params is a mapping with exactly {', '.join(cls._POSEIDON2_PARAM_KEYS)}")
+        t, full, partial = params["t"], params["full"], params["partial"]
+        if not _is_u(t, 32) or t not in cls._POSEIDON2_WIDTHS:
+            raise bad(f"the width t must be one of {', '.join(map(str, cls._POSEIDON2_WIDTHS))}")
+        if not _is_u(full, _native.KZG_POSEIDON2_MAX_FULL + 1) or full < 2 or full % 2:
+            raise bad(f"the number of full rounds R_F must be even and in [2, {_native.KZG_POSEIDON2_MAX_FULL}]")
+        if not _is_u(partial, _native.KZG_POSEIDON2_MAX_PARTIAL + 1):
+            raise bad(f"the number of partial rounds R_P must be in [0, {_native.KZG_POSEIDON2_MAX_PARTIAL}]")
+        lists = []
+        for name, count, words, kind in (("rc_full", t * full, "t R_F", "a round constant"),
+                                         ("rc_partial", partial, "R_P", "a round constant"), ("diag", t, "t", "a diagonal entry")):
+            v = params[name]
+            if not isinstance(v, (list, tuple)) or len(v) != count:
+                raise bad(f"{name} must be a list of {words} = {count} scalars")
+            lists.append(b"".join(sp.scalar(x, kind) for x in v))
+        return (t, full, partial, *lists), cls._poseidon_units(sp, t, full + partial, 2, units)
+
+    def commit_poseidon2(self, input_sets: Sequence[object], params: dict, units: Sequence[dict], usable: Optional[int] = None,
+                         tail: Sequence[bytes] = ()) -> Tuple[Optional["RowSet"], dict]:
+        """kzg_rows_commit_poseidon2 over the concatenated rows of input_sets: commit_poseidon with the Poseidon2 permutation.
+        params and units: see poseidon2_call.  s <- E(s); R_F / 2 full rounds (s_i += rc_full[..]; s_i <- s_i^5; s <- E(s)); R_P
+        partial rounds (s_0 += rc_partial[rho]; s_0 <- s_0^5; s <- I(s)); R_F / 2 full rounds.  A rounds unit's block holds the
+        input, E(input), then the state behind every round: R + 2 rows.  Returns what commit_poseidon returns."""
+        what = "commit_poseidon2"
+        ni, hi = self._handle_array(input_sets, what)
+        par, recs = self.poseidon2_call(params, units, what)
+        arr = (_native.PoseidonUnit * len(recs))(*[self.poseidon_unit_struct(r) for r in recs])
+        return self._commit_units(what, self._lib.kzg_rows_commit_poseidon2, input_sets, ni, hi, _native.Poseidon2Params(*par),
+                                  arr, sum(r[2] for r in recs if not r[1]), usable, tail,
+                                  (("perms", 0), ("mismatch", 0), ("first_mismatch", 1)), _native.KZG_POSEIDON_NONE)
+
     def _commit_units(self, what, fn, input_sets, ni, hi, lead, arr, n_out, usable, tail, stats, none):
-        """The one body behind the six unit builders' commit_*, from the layout on (fn: the library's call; ni, hi: the handle
+        """The one body behind the seven unit builders' commit_*, from the layout on (fn: the library's call; ni, hi: the handle
         array; lead: the params or curve struct in front of the unit array `arr`, None where the builder has none).  stats: a
         (name, is a first row) pair per statistics array in the call's order; `none` in a first-row array becomes None.
         Returns (the new RowSet or None when nothing is committed, {name: one value per unit})."""

@@ -239,6 +239,12 @@ class MultiDeviceClient:
             self._row_owner[int(r.json()["handle"])] = self._owner(list(input_handles))
         return r
 
+    def worker_commit_poseidon2(self, input_handles: Sequence[int], params, units, usable=None, tail=()):
+        r = self._routed_builder("worker_commit_poseidon2", [input_handles], input_handles, params, units, usable, tail, key=None)
+        if r.status_code == 200 and r.json()["handle"] is not None:   # (a call of checks alone makes no set)
+            self._row_owner[int(r.json()["handle"])] = self._owner(list(input_handles))
+        return r
+
     def worker_commit_poseidon_chain(self, input_handles: Sequence[int], params, units, usable=None, tail=()):
         r = self._routed_builder("worker_commit_poseidon_chain", [input_handles], input_handles, params, units, usable, tail,
                                  key=None)
