@@ -4,6 +4,15 @@
  * pairing operations and the host-side point encoder so that tests/test_gpu_*.py, tests/test_abi.py and
  * tests/test_verify.py can compare each of them with the oracle.  A binding of the prover never needs
  * this file.
+ *
+ * The hooks, in the order of this file: unit operations (kzg_test_field, kzg_test_g1), raw limbs (kzg_test_fp_raw,
+ * kzg_test_g1_raw), the NTT's pass plans (kzg_test_ntt_plan_of, kzg_test_ntt_run), the opening scan's plans
+ * (kzg_test_poly_plan_of, kzg_test_poly_run), the hash join (kzg_test_join, kzg_test_join_counts), the MSM's passes
+ * (kzg_test_msm_passes), the host-side encoder (kzg_host_xyzz_*), the communicator stall (kzg_test_comm_stall, _n), the pairing
+ * (kzg_vk_pairing); and,
+ * declared in files of their own that this one includes at its end, the recurrence scan's plans (kzg_mi355x_recur_test.h:
+ * kzg_test_recur_plan_of, kzg_test_recur_run) and the product and additive scans' plans (kzg_mi355x_scan_test.h:
+ * kzg_test_scan_plan_of, kzg_test_scan_run).
  */
 #ifndef KZG_MI355X_TEST_H
 #define KZG_MI355X_TEST_H
@@ -140,4 +149,6 @@ int kzg_vk_pairing(const uint8_t p_be96[96], const uint8_t q_be192[192], uint8_t
 #endif
 /* the plan hooks of the recurrence scan (csrc/fr_recur.hip), declared in a file of their own */
 #include "kzg_mi355x_recur_test.h"
+/* the plan hooks of the product scan and of the additive scan (csrc/fr_prod.hip, csrc/fr_lookup.hip), likewise */
+#include "kzg_mi355x_scan_test.h"
 #endif /* KZG_MI355X_TEST_H */

@@ -596,6 +596,13 @@ RECUR_HOOKS = {
     "kzg_test_recur_run": (_I, [_P, _I, ctypes.c_int64, _P, _P, _P, _U64, _P, _P]),
 }
 
+# the plan hooks of the product and the additive scan (include/kzg_mi355x_scan_test.h, likewise): bound like SYMBOLS
+SCAN_HOOKS = {
+    "kzg_test_scan_plan_of": (_I, [_U64, _I, ctypes.c_int64, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_U64),
+                                   ctypes.POINTER(_U64)]),
+    "kzg_test_scan_run": (_I, [_P, _I, _I, ctypes.c_int64, _P, _P, _P, _U64, _P, _P, ctypes.POINTER(_U32)]),
+}
+
 _lib = None
 
 
@@ -650,7 +657,7 @@ def load() -> ctypes.CDLL:
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback."
             )
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(RECUR_HOOKS.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(RECUR_HOOKS.items()) + list(SCAN_HOOKS.items()):
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

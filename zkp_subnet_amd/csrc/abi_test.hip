@@ -671,6 +671,108 @@ int kzg_test_recur_run(kzg_ctx* ctx, int l0, int64_t top_max, const uint8_t* a_b
     return KZG_OK;
 }
 
+// ---- the product and the additive scan's plans (tests/test_scan_plans_cpu.py, tests/test_gpu_scan_plans.py, reference
+// tests/scan_ref.py).  Both parameters -1: the plan the launchers pick themselves; otherwise the caller's, both taken as given
+static const char* scan_plan_from(uint64_t n, int l0, int64_t top_max, ScanPlan* pl) {
+    if (!n) return "scan plan: no elements";
+    if (l0 == -1 && top_max == -1) *pl = scan_plan(n);
+    else *pl = scan_plan_levels(n, l0, top_max < 0 ? 0 : (uint64_t)top_max);
+    return scan_plan_invalid(*pl, n);
+}
+int kzg_test_scan_plan_of(uint64_t n, int l0, int64_t top_max, int* out_K, int* out_l, uint64_t* out_n, uint64_t* out_off) {
+    if (!out_K || !out_l || !out_n || !out_off) return fail(nullptr, KZG_E_ARG, "scan plan: null output");
+    ScanPlan pl;
+    if (const char* why = scan_plan_from(n, l0, top_max, &pl)) return fail(nullptr, KZG_E_ARG, why);
+    for (int k = 0; k <= pl.K; k++) {
+        out_l[k] = k < pl.K ? pl.l[k] : 0;    // (level K is the top kernel's: it folds nothing into a further level)
+        out_n[k] = pl.n[k];
+        out_off[k] = pl.off[k];
+    }
+    *out_K = pl.K;
+    return KZG_OK;
+}
+#define KZG_TEST_SCAN_MAX_N ((uint64_t)1 << 22)   // elements per plan-hook call (as KZG_TEST_RECUR_MAX_N)
+int kzg_test_scan_run(kzg_ctx* ctx, int form, int l0, int64_t top_max, const uint8_t* a_be32, const uint8_t* b_be32,
+                      const uint8_t* start_be32, uint64_t n, uint8_t* out_be32, uint8_t* out_closing_be32, uint32_t* out_zero_flag) {
+    // the plan is judged first, with no context and no device: nothing invalid reaches a kernel
+    ScanPlan pl;
+    if (const char* why = scan_plan_from(n, l0, top_max, &pl)) return fail(ctx, KZG_E_ARG, why);
+    if (n > KZG_TEST_SCAN_MAX_N) return fail(ctx, KZG_E_ARG, "scan run: at most 2^22 elements");
+    if (form < 0 || form > 4)
+        return fail(ctx, KZG_E_ARG, "scan run: form must be 0 (product), 1 (chained product), 2 (1 / a), 3 (b / a) or 4 (sum)");
+    const bool has_b = form == 0 || form == 1 || form == 3;
+    if (!ctx || !a_be32 || (has_b && !b_be32) || (form == 1 && !start_be32) || !out_be32 || !out_closing_be32 || !out_zero_flag)
+        return fail(ctx, KZG_E_ARG, "scan run: no context or no data");
+    if (form == 1) {   // (the chained grand product checks its start on the host too; k_gp_chain_start takes it as canonical, not 0)
+        static const uint8_t R_BE[32] = {0x73, 0xED, 0xA7, 0x53, 0x29, 0x9D, 0x7D, 0x48, 0x33, 0x39, 0xD8, 0x08, 0x09, 0xA1, 0xD8, 0x05,
+                                         0x53, 0xBD, 0xA4, 0x02, 0xFF, 0xFE, 0x5B, 0xFE, 0xFF, 0xFF, 0xFF, 0xFF, 0x00, 0x00, 0x00, 0x01};
+        static const uint8_t ZERO32[32] = {};
+        if (memcmp(start_be32, R_BE, 32) >= 0 || memcmp(start_be32, ZERO32, 32) == 0)
+            return fail(ctx, KZG_E_ARG, "scan run: start must be a canonical scalar (< r) other than 0");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LaneHold H(ctx);
+    if (int rc = H.take()) return rc;
+    Lane& L = H.L();
+    prof_begin(ctx, L);
+    int rc = clear_flags(ctx, L);
+    if (rc) return rc;
+    hipStream_t s = L.stream;
+    HIPCHK(ctx, L.coeffA.ensure(n * 32));
+    HIPCHK(ctx, L.coeffB.ensure(n * 32));
+    HIPCHK(ctx, L.qbuf.ensure(n * 32));
+    HIPCHK(ctx, L.hbuf.ensure(scan_level_elems(n) * 32));
+    HIPCHK(ctx, L.hnext.ensure(scan_level_elems(n) * 32));
+    HIPCHK(ctx, L.scal.ensure(64));   // [0, 32) the scan's closing slot, [32] its zero flag
+    HIPCHK(ctx, L.out_be.ensure(n * 32));
+    uint32_t *a = L.coeffA.as<uint32_t>(), *b = L.coeffB.as<uint32_t>(), *w = L.qbuf.as<uint32_t>();
+    uint32_t *hN = L.hbuf.as<uint32_t>(), *hD = L.hnext.as<uint32_t>();
+    uint8_t* cl = L.scal.as<uint8_t>();
+    uint32_t* zf = L.scal.as<uint32_t>() + 8;
+    rc = upload_fr(ctx, L, a_be32, n, a, 1);
+    if (rc) return rc;
+    if (has_b) {
+        rc = upload_fr(ctx, L, b_be32, n, b, 1);
+        if (rc) return rc;
+    }
+    // whatever a kernel fails to write must show: W, the level scratch, the closing slot and the flag start from a pattern that
+    // is no result
+    HIPCHK(ctx, hipMemsetAsync(L.qbuf.p, 0xff, n * 32, s));
+    HIPCHK(ctx, hipMemsetAsync(L.hbuf.p, 0xff, scan_level_elems(n) * 32, s));
+    HIPCHK(ctx, hipMemsetAsync(L.hnext.p, 0xff, scan_level_elems(n) * 32, s));
+    HIPCHK(ctx, hipMemsetAsync(L.scal.p, 0xff, 64, s));
+    if (form == 4) HIPCHK(ctx, hipMemsetAsync(zf, 0, 4, s));   // (the additive scan has no flag)
+    const uint32_t* out = nullptr;
+    {
+        Span sp(ctx, L, KZG_T_POLY);
+        if (form == 0 || form == 1) {
+            launch_gp_scan(s, pl, a, b, n, hN, hD, cl, zf, form == 1 ? start_be32 : nullptr);
+            out = a;
+        } else if (form == 2) {
+            launch_fr_batch_inv(s, pl, a, w, nullptr, w, n, hN, hD, cl, zf);
+            out = w;
+        } else if (form == 3) {
+            launch_fr_batch_inv(s, pl, a, w, b, b, n, hN, hD, cl, zf);
+            out = b;
+        } else {
+            launch_lk_sum_scan(s, pl, a, n, hN, cl);
+            out = a;
+        }
+    }
+    // the words as the kernels left them, taken out of Montgomery form WITHOUT a reduction check: an unwritten cell (all ones)
+    // comes back as a value that no reference holds
+    launch_fr_to_be(s, out, L.out_be.as<uint8_t>(), n, 1);
+    rc = finish(ctx, L);
+    if (rc) return rc;
+    uint8_t rec[36];
+    HIPCHK(ctx, hipMemcpy(out_be32, L.out_be.p, n * 32, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(rec, L.scal.p, 36, hipMemcpyDeviceToHost));
+    memcpy(out_closing_be32, rec, 32);
+    memcpy(out_zero_flag, rec + 32, 4);
+    H.clean = true;
+    return KZG_OK;
+}
+
 // ---- the hash join alone (tests/test_join_cpu.py, tests/test_gpu_join.py, reference tests/join_ref.py)
 #define KZG_TEST_JOIN_MAX 4096u      // rows and slots per join-hook call
 static const char* join_args_invalid(int build, int walk, uint64_t T, uint64_t rows, uint32_t w, uint32_t n_pay, int index,

@@ -701,6 +701,37 @@ void launch_recur_scan(hipStream_t s, const uint32_t* A, const uint32_t* B, uint
                        const uint8_t start_be32[32], uint32_t* out, uint8_t* closing_be, uint32_t* close_row);
 void launch_recur_scan(hipStream_t s, const RecurPlan& pl, const uint32_t* A, const uint32_t* B, uint64_t n, uint32_t* scrA,
                        uint32_t* scrB, const uint8_t start_be32[32], uint32_t* out, uint8_t* closing_be, uint32_t* close_row);
+// the one level loop behind recur_plan_levels (min_levels = 0) and scan_plan_levels (1): levels are added while the top one
+// holds more than top_max values or fewer than min_levels levels lie under it
+RecurPlan ladder_plan_levels(uint64_t n, int l0, uint64_t top_max, int min_levels);
+// ---- the plans of the product scan (fr_prod.hip: launch_gp_scan_upper, launch_gp_scan, and launch_fr_batch_inv of fr_lookup.hip
+// behind it) and of the additive scan (fr_lookup.hip: launch_lk_sum_scan).  The ladder is the recurrence scan's, and so is the
+// plan type, with ONE difference: these scans have no K = 0 form.  Level 0 (the vectors themselves, 2^l0 elements per lane) is
+// always folded into level 1 at element 0 of the scratch, even at n = 1; levels of 16 follow while more than top_max values are
+// left for the one workgroup of the top kernel.  scan_plan is what the launchers pick (l0 = 2, raised to 3 or 4 while
+// (n >> (l0 + 1)) >= 16384; SCAN_TOP_MAX), scan_plan_levels a caller's choice, scan_plan_invalid the kernels' preconditions
+// (null: valid): 1 <= n <= 2^32, l0 in 2 .. 4, 1 <= top_max <= SCAN_TOP_MAX, 1 .. SCAN_MAX_LEVELS levels, the stacked levels
+// inside scan_level_elems(n).  The overloads that take a plan run it unchecked.
+#define SCAN_TOP_MAX 2048
+#define SCAN_MAX_LEVELS RECUR_MAX_LEVELS
+typedef RecurPlan ScanPlan;
+// elements of EACH scratch array: what every caller allocates ((n + 3) / 4 * 3 / 2 + 64)
+inline uint64_t scan_level_elems(uint64_t n) { return poly_level_words(n) / 8; }
+ScanPlan scan_plan(uint64_t n);
+ScanPlan scan_plan_levels(uint64_t n, int l0, uint64_t top_max);
+const char* scan_plan_invalid(const ScanPlan& pl, uint64_t n);
+// what the launchers themselves ask before they launch: a plan of n elements with 1 .. SCAN_MAX_LEVELS levels and a top that
+// one workgroup takes
+bool scan_plan_runs(const ScanPlan& pl, uint64_t n);
+// the launchers above by a caller's plan (theirs is scan_plan(n)); launch_gp_scan_upper answers -1, and nothing is launched by
+// any of them, for a plan that is not of n elements or has no level table
+int launch_gp_scan_upper(hipStream_t s, const ScanPlan& pl, const uint32_t* N, const uint32_t* D, uint64_t n, uint32_t* scrN,
+                         uint32_t* scrD, uint8_t* closing_be, uint32_t* zero_flag, const uint8_t* start_be32 = nullptr);
+void launch_gp_scan(hipStream_t s, const ScanPlan& pl, uint32_t* N, uint32_t* D, uint64_t n, uint32_t* scrN, uint32_t* scrD,
+                    uint8_t* closing_be, uint32_t* zero_flag, const uint8_t* start_be32 = nullptr);
+void launch_fr_batch_inv(hipStream_t s, const ScanPlan& pl, const uint32_t* Q, uint32_t* W, const uint32_t* P_or_null,
+                         uint32_t* out, uint64_t n, uint32_t* scrN, uint32_t* scrD, uint8_t* scratch32, uint32_t* zero_flag);
+void launch_lk_sum_scan(hipStream_t s, const ScanPlan& pl, uint32_t* v, uint64_t n, uint32_t* scr, uint8_t* closing_be);
 // ---- blinding rows (fr_blind.hip; the kzg_rows_commit_*_zk builders): rows [usable, n) of evaluation vectors of n Montgomery
 // elements, n - usable <= BLIND_MAX_ROWS (= KZG_MAX_BLIND_ROWS)
 #define BLIND_MAX_ROWS 32

@@ -203,13 +203,17 @@ __global__ void __launch_bounds__(256) k_lk_inv_final(const uint32_t* __restrict
         fr9_mul(p, p, c);
     }
 }
-void launch_fr_batch_inv(hipStream_t s, const uint32_t* Q, uint32_t* W, const uint32_t* P_or_null, uint32_t* out, uint64_t n,
-                         uint32_t* scrN, uint32_t* scrD, uint8_t* scratch32, uint32_t* zero_flag) {
-    if (!n) return;
-    const int l0 = launch_gp_scan_upper(s, Q, Q, n, scrN, scrD, scratch32, zero_flag);
-    const uint32_t blocks = nblk((n + ((uint64_t)1 << l0) - 1) >> l0, 256);
+void launch_fr_batch_inv(hipStream_t s, const ScanPlan& pl, const uint32_t* Q, uint32_t* W, const uint32_t* P_or_null,
+                         uint32_t* out, uint64_t n, uint32_t* scrN, uint32_t* scrD, uint8_t* scratch32, uint32_t* zero_flag) {
+    const int l0 = launch_gp_scan_upper(s, pl, Q, Q, n, scrN, scrD, scratch32, zero_flag);
+    if (l0 < 0) return;
+    const uint32_t blocks = nblk(pl.n[1], 256);
     if (P_or_null) k_lk_inv_final<true><<<blocks, 256, 0, s>>>(Q, W, P_or_null, out, n, l0, scrN, scrD);
     else k_lk_inv_final<false><<<blocks, 256, 0, s>>>(Q, W, nullptr, out, n, l0, scrN, scrD);
+}
+void launch_fr_batch_inv(hipStream_t s, const uint32_t* Q, uint32_t* W, const uint32_t* P_or_null, uint32_t* out, uint64_t n,
+                         uint32_t* scrN, uint32_t* scrD, uint8_t* scratch32, uint32_t* zero_flag) {
+    if (n) launch_fr_batch_inv(s, scan_plan(n), Q, W, P_or_null, out, n, scrN, scrD, scratch32, zero_flag);
 }
 
 // ------------------------------------------------------------------------------------------------ additive scan
@@ -305,26 +309,17 @@ __global__ void __launch_bounds__(256) k_lk_expand_sum(uint32_t* __restrict__ va
         fr9_addmod(p, p, c);
     }
 }
-// The levels of launch_gp_scan_upper: 2^l0 elements per lane at level 0 (4 for short rows, 16 for long ones), 16 above, until
-// at most LK_TOP_MAX values are left.
+// The levels of launch_gp_scan_upper, by the same plan (scan_plan, fr_prod.hip): 2^l[0] elements per lane at level 0 (4 for
+// short rows, 16 for long ones), 16 above, until at most LK_TOP_MAX values are left.
+void launch_lk_sum_scan(hipStream_t s, const ScanPlan& pl, uint32_t* v, uint64_t n, uint32_t* scr, uint8_t* closing_be) {
+    if (!scan_plan_runs(pl, n)) return;
+    const int K = pl.K;
+    for (int k = 0; k < K; k++)
+        k_lk_chunk_sum<<<nblk(pl.n[k + 1], 256), 256, 0, s>>>(k ? scr + 8 * pl.off[k] : v, pl.n[k], pl.l[k], scr + 8 * pl.off[k + 1]);
+    k_lk_top_sum<<<1, 256, 0, s>>>(scr + 8 * pl.off[K], (uint32_t)pl.n[K], closing_be);
+    for (int k = K - 1; k >= 0; k--)
+        k_lk_expand_sum<<<nblk(pl.n[k + 1], 256), 256, 0, s>>>(k ? scr + 8 * pl.off[k] : v, pl.n[k], pl.l[k], scr + 8 * pl.off[k + 1]);
+}
 void launch_lk_sum_scan(hipStream_t s, uint32_t* v, uint64_t n, uint32_t* scr, uint8_t* closing_be) {
-    if (!n) return;
-    int l0 = 2;
-    while (l0 < 4 && (n >> (l0 + 1)) >= 16384) l0++;
-    int K = 1, lv_l[16];
-    uint64_t lv_n[16], lv_off[16];
-    lv_l[0] = l0; lv_n[0] = n; lv_off[0] = 0;
-    lv_n[1] = (n + ((uint64_t)1 << l0) - 1) >> l0; lv_off[1] = 0;
-    k_lk_chunk_sum<<<nblk(lv_n[1], 256), 256, 0, s>>>(v, n, l0, scr);
-    while (lv_n[K] > LK_TOP_MAX && K < 14) {
-        lv_l[K] = 4;
-        lv_n[K + 1] = (lv_n[K] + 15) >> 4;
-        lv_off[K + 1] = lv_off[K] + lv_n[K];
-        k_lk_chunk_sum<<<nblk(lv_n[K + 1], 256), 256, 0, s>>>(scr + 8 * lv_off[K], lv_n[K], 4, scr + 8 * lv_off[K + 1]);
-        K++;
-    }
-    k_lk_top_sum<<<1, 256, 0, s>>>(scr + 8 * lv_off[K], (uint32_t)lv_n[K], closing_be);
-    for (int k = K - 1; k >= 1; k--)
-        k_lk_expand_sum<<<nblk(lv_n[k + 1], 256), 256, 0, s>>>(scr + 8 * lv_off[k], lv_n[k], lv_l[k], scr + 8 * lv_off[k + 1]);
-    k_lk_expand_sum<<<nblk(lv_n[1], 256), 256, 0, s>>>(v, n, l0, scr);
+    if (n) launch_lk_sum_scan(s, scan_plan(n), v, n, scr, closing_be);
 }

@@ -396,44 +396,68 @@ __global__ void __launch_bounds__(256) k_gp_final(uint32_t* __restrict__ N, uint
         fr9_mul(p, p, c);
     }
 }
+// ---- the plan: pure host arithmetic (fr_kernels.hip.h), shared with the additive scan of fr_lookup.hip.  The level loop is the
+// recurrence scan's (ladder_plan_levels) with at least one level under the top
+ScanPlan scan_plan_levels(uint64_t n, int l0, uint64_t top_max) { return ladder_plan_levels(n, l0, top_max, 1); }
+ScanPlan scan_plan(uint64_t n) {
+    int l0 = 2;
+    while (l0 < 4 && (n >> (l0 + 1)) >= 16384) l0++;
+    return scan_plan_levels(n, l0, SCAN_TOP_MAX);
+}
+const char* scan_plan_invalid(const ScanPlan& pl, uint64_t n) {
+    if (!n) return "scan plan: no elements";
+    if (n > ((uint64_t)1 << 32)) return "scan plan: more than 2^32 elements";
+    if (pl.l0 < 2 || pl.l0 > 4) return "scan plan: level-0 chunk outside 2^2 .. 2^4";
+    if (pl.top_max < 1 || pl.top_max > SCAN_TOP_MAX) return "scan plan: the top level takes 1 .. 2048 values";
+    if (pl.K < 1) return "scan plan: no level under the top (these scans have no K = 0 form)";
+    if (pl.K > SCAN_MAX_LEVELS || pl.n[pl.K] > pl.top_max) return "scan plan: more than 14 levels";
+    if (pl.n[0] != n || pl.off[pl.K] + pl.n[pl.K] > scan_level_elems(n))
+        return "scan plan: the stacked levels do not fit scan_level_elems(n)";
+    return nullptr;
+}
+// what a launcher asks of a plan before it launches anything (the rest is the caller's to have checked with scan_plan_invalid;
+// scan_plan's own always pass)
+bool scan_plan_runs(const ScanPlan& pl, uint64_t n) {
+    return n && pl.n[0] == n && pl.K >= 1 && pl.K <= SCAN_MAX_LEVELS && pl.n[pl.K] <= SCAN_TOP_MAX;
+}
+
 // The scan without its last level: chunk products of N and D up to the top, k_gp_top, the expansions back down to level 1.
 // Leaves in scrN[g] / scrD[g] the exclusive prefix product of N in front of level-0 chunk g and the exclusive suffix product
 // of D behind it (times 1 / prod D); returns the level-0 chunk length's log2.  N and D are only read (they may be one
-// vector: the batched inversion of fr_lookup.hip).  Level 0 folds 2^l0 elements per lane (4 for short rows, 16 for long ones,
-// as the opening does), every further level 16, until at most GP_TOP_MAX values are left for k_gp_top.
-int launch_gp_scan_upper(hipStream_t s, const uint32_t* N, const uint32_t* D, uint64_t n, uint32_t* scrN, uint32_t* scrD,
-                         uint8_t* closing_be, uint32_t* zero_flag, const uint8_t* start_be32) {
-    int l0 = 2;
-    while (l0 < 4 && (n >> (l0 + 1)) >= 16384) l0++;
-    int K = 1, lv_l[16];
-    uint64_t lv_n[16], lv_off[16];
-    lv_l[0] = l0; lv_n[0] = n; lv_off[0] = 0;
-    lv_n[1] = (n + ((uint64_t)1 << l0) - 1) >> l0; lv_off[1] = 0;
-    k_gp_chunk_prod<<<dim3(nblk(lv_n[1], 256), 2), 256, 0, s>>>(N, D, n, l0, scrN, scrD);
-    while (lv_n[K] > GP_TOP_MAX && K < 14) {
-        lv_l[K] = 4;
-        lv_n[K + 1] = (lv_n[K] + 15) >> 4;
-        lv_off[K + 1] = lv_off[K] + lv_n[K];
-        k_gp_chunk_prod<<<dim3(nblk(lv_n[K + 1], 256), 2), 256, 0, s>>>(scrN + 8 * lv_off[K], scrD + 8 * lv_off[K], lv_n[K], 4,
-                                                                         scrN + 8 * lv_off[K + 1], scrD + 8 * lv_off[K + 1]);
-        K++;
-    }
-    k_gp_top<<<1, 512, 0, s>>>(scrN + 8 * lv_off[K], scrD + 8 * lv_off[K], (uint32_t)lv_n[K], closing_be, zero_flag);
+// vector: the batched inversion of fr_lookup.hip).  Level 0 folds 2^l[0] elements per lane (4 for short rows, 16 for long ones,
+// as the opening does), every further level 16, until at most GP_TOP_MAX values are left for k_gp_top: the plan.
+int launch_gp_scan_upper(hipStream_t s, const ScanPlan& pl, const uint32_t* N, const uint32_t* D, uint64_t n, uint32_t* scrN,
+                         uint32_t* scrD, uint8_t* closing_be, uint32_t* zero_flag, const uint8_t* start_be32) {
+    if (!scan_plan_runs(pl, n)) return -1;
+    const int K = pl.K;
+    for (int k = 0; k < K; k++)
+        k_gp_chunk_prod<<<dim3(nblk(pl.n[k + 1], 256), 2), 256, 0, s>>>(k ? scrN + 8 * pl.off[k] : N, k ? scrD + 8 * pl.off[k] : D,
+                                                                        pl.n[k], pl.l[k], scrN + 8 * pl.off[k + 1],
+                                                                        scrD + 8 * pl.off[k + 1]);
+    k_gp_top<<<1, 512, 0, s>>>(scrN + 8 * pl.off[K], scrD + 8 * pl.off[K], (uint32_t)pl.n[K], closing_be, zero_flag);
     if (start_be32) {
         FrArg st;
         memcpy(st.w, start_be32, 32);
-        k_gp_chain_start<<<nblk(lv_n[K], 256), 256, 0, s>>>(scrN + 8 * lv_off[K], (uint32_t)lv_n[K], closing_be, st);
+        k_gp_chain_start<<<nblk(pl.n[K], 256), 256, 0, s>>>(scrN + 8 * pl.off[K], (uint32_t)pl.n[K], closing_be, st);
     }
     for (int k = K - 1; k >= 1; k--)
-        k_gp_expand<<<dim3(nblk(lv_n[k + 1], 256), 2), 256, 0, s>>>(scrN + 8 * lv_off[k], scrD + 8 * lv_off[k], lv_n[k], lv_l[k],
-                                                                    scrN + 8 * lv_off[k + 1], scrD + 8 * lv_off[k + 1]);
-    return l0;
+        k_gp_expand<<<dim3(nblk(pl.n[k + 1], 256), 2), 256, 0, s>>>(scrN + 8 * pl.off[k], scrD + 8 * pl.off[k], pl.n[k], pl.l[k],
+                                                                    scrN + 8 * pl.off[k + 1], scrD + 8 * pl.off[k + 1]);
+    return pl.l[0];
+}
+int launch_gp_scan_upper(hipStream_t s, const uint32_t* N, const uint32_t* D, uint64_t n, uint32_t* scrN, uint32_t* scrD,
+                         uint8_t* closing_be, uint32_t* zero_flag, const uint8_t* start_be32) {
+    return launch_gp_scan_upper(s, scan_plan(n), N, D, n, scrN, scrD, closing_be, zero_flag, start_be32);
 }
 // N, D (n Montgomery elements each) -> z's evaluations in N (D is consumed).  scrN / scrD: (n + 3) / 4 * 3 / 2 + 64 elements
 // of level scratch each (the sizing of the opening's h / hnext).
+void launch_gp_scan(hipStream_t s, const ScanPlan& pl, uint32_t* N, uint32_t* D, uint64_t n, uint32_t* scrN, uint32_t* scrD,
+                    uint8_t* closing_be, uint32_t* zero_flag, const uint8_t* start_be32) {
+    const int l0 = launch_gp_scan_upper(s, pl, N, D, n, scrN, scrD, closing_be, zero_flag, start_be32);
+    if (l0 < 0) return;
+    k_gp_final<<<nblk(pl.n[1], 256), 256, 0, s>>>(N, D, n, l0, scrN, scrD);
+}
 void launch_gp_scan(hipStream_t s, uint32_t* N, uint32_t* D, uint64_t n, uint32_t* scrN, uint32_t* scrD,
                     uint8_t* closing_be, uint32_t* zero_flag, const uint8_t* start_be32) {
-    if (!n) return;
-    const int l0 = launch_gp_scan_upper(s, N, D, n, scrN, scrD, closing_be, zero_flag, start_be32);
-    k_gp_final<<<nblk(((n + ((uint64_t)1 << l0) - 1) >> l0), 256), 256, 0, s>>>(N, D, n, l0, scrN, scrD);
+    if (n) launch_gp_scan(s, scan_plan(n), N, D, n, scrN, scrD, closing_be, zero_flag, start_be32);
 }

@@ -170,7 +170,8 @@ __global__ void __launch_bounds__(256) k_recur_walk(const uint32_t* A, const uin
 
 // ---- the plan: pure host arithmetic (fr_kernels.hip.h).  Level k holds n[k] maps; level 0 is the vectors themselves, level
 // k >= 1 starts at element off[k] of both scratch arrays; levels are added while the top one holds more than top_max maps
-RecurPlan recur_plan_levels(uint64_t n, int l0, uint64_t top_max) {
+// (the product and the additive scan share the loop with min_levels = 1: they always fold level 0 once, scan_plan_levels)
+RecurPlan ladder_plan_levels(uint64_t n, int l0, uint64_t top_max, int min_levels) {
     RecurPlan pl;
     memset(&pl, 0, sizeof pl);
     pl.l0 = l0;
@@ -179,7 +180,7 @@ RecurPlan recur_plan_levels(uint64_t n, int l0, uint64_t top_max) {
     pl.n[0] = n;
     if (l0 < 2 || l0 > 4 || top_max < 1) return pl;   // (no level table: recur_plan_invalid names the parameter)
     int K = 0;
-    while (pl.n[K] > top_max && K < RECUR_MAX_LEVELS) {
+    while ((pl.n[K] > top_max || K < min_levels) && K < RECUR_MAX_LEVELS) {
         pl.l[K] = K ? pl.lup : l0;
         pl.n[K + 1] = (pl.n[K] + ((uint64_t)1 << pl.l[K]) - 1) >> pl.l[K];
         pl.off[K + 1] = K ? pl.off[K] + pl.n[K] : 0;
@@ -188,6 +189,7 @@ RecurPlan recur_plan_levels(uint64_t n, int l0, uint64_t top_max) {
     pl.K = K;
     return pl;
 }
+RecurPlan recur_plan_levels(uint64_t n, int l0, uint64_t top_max) { return ladder_plan_levels(n, l0, top_max, 0); }
 RecurPlan recur_plan(uint64_t n) {
     const int l0 = n < ((uint64_t)1 << 17) ? 2 : n < ((uint64_t)1 << 18) ? 3 : 4;
     return recur_plan_levels(n, l0, RECUR_TOP_MAX);

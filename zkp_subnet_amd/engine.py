@@ -2960,6 +2960,19 @@ class HipEngine:
                                                ctypes.addressof(cl)))
         return v.raw[:32 * n], cl.raw
 
+    def test_scan_run(self, form: int, a_be32: bytes, b_be32: Optional[bytes], start_be32: Optional[bytes], n: int,
+                      plan: Sequence[int] = (-1, -1)) -> Tuple[bytes, bytes, int]:
+        """The product scan or the additive scan over n elements by the CALLER'S plan (kzg_test_scan_run; no SRS, no MSM): plan =
+        (l0, top_max), both -1 for the library's own.  form 0: out[t] = prod_{u<t} a[u] / b[u] (launch_gp_scan); 1: the same times
+        start; 2: 1 / a[t] (launch_fr_batch_inv, out = W); 3: b[t] / a[t] (launch_fr_batch_inv, out = P); 4: sum_{u<t} a[u]
+        (launch_lk_sum_scan).  Returns (out as n x 32 bytes, the closing value, the zero-denominator flag word).
+        KzgError(KZG_E_ARG) for a plan the kernels do not admit."""
+        l0, top_max = plan
+        v, cl, zf = ctypes.create_string_buffer(32 * max(1, n)), ctypes.create_string_buffer(32), ctypes.c_uint32(0)
+        self._chk(self._lib.kzg_test_scan_run(self._h, form, l0, top_max, a_be32, b_be32, start_be32, n, ctypes.addressof(v),
+                                              ctypes.addressof(cl), ctypes.byref(zf)))
+        return v.raw[:32 * n], cl.raw, zf.value
+
     def test_join(self, build: int, walk: int, tab_be32: bytes, in_be32: bytes, T: int, rows: int, w: int, cap: int,
                   n_pay: int = 0, index: bool = False, sel_be32: Optional[bytes] = None) -> Dict[str, object]:
         """The hash join alone through the library's own launchers at the CALLER'S capacity (kzg_test_join; no SRS, no MSM):
@@ -3027,6 +3040,20 @@ def recur_plan_of(n: int, l0: int = -1, top_max: int = -1) -> Dict[str, object]:
     K = ctypes.c_int(0)
     al, an, aoff = (ctypes.c_int * 16)(), (ctypes.c_uint64 * 16)(), (ctypes.c_uint64 * 16)()
     rc = lib.kzg_test_recur_plan_of(n, l0, top_max, ctypes.byref(K), al, an, aoff)
+    if rc != _native.KZG_OK:
+        raise KzgError(rc, lib.kzg_last_error(None).decode(errors="replace"))
+    k = K.value + 1
+    return {"K": K.value, "l": list(al[:k]), "n": list(an[:k]), "off": list(aoff[:k])}
+
+
+def scan_plan_of(n: int, l0: int = -1, top_max: int = -1) -> Dict[str, object]:
+    """The level plan of the product scan and of the additive scan for n elements (kzg_test_scan_plan_of; no context, no
+    device): with both parameters -1 the plan the library runs, otherwise the caller's.  {"K", "l", "n", "off" (K + 1 entries
+    each)}, K >= 1; KzgError(KZG_E_ARG) with the reason for a plan outside the kernels' preconditions."""
+    lib = _native.load()
+    K = ctypes.c_int(0)
+    al, an, aoff = (ctypes.c_int * 16)(), (ctypes.c_uint64 * 16)(), (ctypes.c_uint64 * 16)()
+    rc = lib.kzg_test_scan_plan_of(n, l0, top_max, ctypes.byref(K), al, an, aoff)
     if rc != _native.KZG_OK:
         raise KzgError(rc, lib.kzg_last_error(None).decode(errors="replace"))
     k = K.value + 1
